@@ -16,10 +16,18 @@ never as `value`; `--scaling weak` makes it the timed workload.  `--multi-handle
 single-process form instead: ONE bpltv_create_multi handle over N devices (worker thread per device
 and the RCCL collective inside the library) -- the form INTEGRATION.md gives the Julia caller.
 
-Rank 0 prints one JSON line with `roofline` (dominant kernel pdhg_tile_kernel: the binding bound --
+A plain run sets up, warms up, times the K steps, writes the outputs of the last step if `--dump-outputs DIR`
+is given, and rank 0 prints one JSON line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`, `ms_per_step`, ...).
+`--full` adds what takes runs of its own: `roofline` (dominant kernel pdhg_tile_kernel: the binding bound --
 f64 VALU issue or measured HBM traffic, whichever fraction is larger, <= 1 -- with the contractual 56 B per
-pixel-iteration figure aside as `contractual_hbm_frac`) and `cpu_baseline` (the oracle's C restatement timed on
+pixel-iteration figure aside as `contractual_hbm_frac`), the replica figure `weak_value` at N > 1, one
+`learning_function` evaluation, the `extra_workloads` and `cpu_baseline` (the oracle's C restatement timed on
 the host cores: kind "port" -- the reference is Julia and cannot run here).
+
+`--dump-outputs DIR`: what the timed path computed in its last step, as DIR/<name>.npy in float64 -- `u` (the
+denoised batch; `u_rank<r>` per rank at N > 1), `cost_grad` ([cost, grad...] with `--evaluate`), `costs` (`--sweep`);
+an array beyond its share of 64 MB is replaced by a fixed, seeded sample of its entries.  The inputs depend on the
+arguments only, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -31,6 +39,29 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: HBM3E peak 8.0 TB/s (spec)
+DUMP_CAP_BYTES = 64 * 10 ** 6   # --dump-outputs writes at most this much in all
+DUMP_SEED = 20211004
+
+
+def dump_outputs(out_dir, arrays, cap=DUMP_CAP_BYTES):
+    """Write {name: array} as out_dir/<name>.npy in float64.  An array larger than its share of `cap` is replaced by
+    the entries at a fixed, seeded choice of flat indices (sorted), the same for every build and run."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = cap // max(len(arrays), 1) - 4096   # room for the .npy header
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            idx = np.random.default_rng(DUMP_SEED).choice(a.size, share // a.itemsize, replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
+def device_u(torch, solver, shape):
+    """The denoised batch the handle's last solve left in HBM, as a host array (bpltv_copy_u_device)."""
+    u = torch.empty(shape, dtype=torch.float64, device="cuda")
+    solver.copy_u_device(u.data_ptr())
+    return u.cpu().numpy()
 
 
 def synth_batch(O, N, M, seed=20211004):
@@ -155,7 +186,7 @@ def cpu_baseline(args, f_full, ub_full, alpha, N, M):
     }
 
 
-def self_launch(n):
+def self_launch(n, argv):
     """`python bench.py --gpus N` without a launcher: start the N ranks ourselves.  This runs before
     torch is imported or any HIP call is made (a process that has touched the GPU must never be
     replaced or forked into ranks); the child is an ordinary subprocess whose stdout (rank 0's JSON
@@ -168,7 +199,7 @@ def self_launch(n):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n),
-           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
+           "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + argv
     return subprocess.call(cmd, env=env, cwd=ROOT)
 
 
@@ -407,6 +438,8 @@ def sweep_bench(args, TVSolver, shard_range, torch):
     for _ in range(args.steps):
         costs = s.sweep(alphas, maxiter=iters)
     T = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"costs": costs})
     st = s.stats()
     nsh = st["sweep_shards"]
     ranges = [list(shard_range(K, nsh, r)) for r in range(nsh)] if nsh else None
@@ -450,8 +483,13 @@ def main():
                     help="opt-in single-precision PDHG (bpltv_create dtype = 32): narrower than the reference's Float64, "
                          "never the headline; the line then says dtype f32 and counts 28/32 B per pixel-iteration")
     ap.add_argument("--no-graph", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra workloads / weak_value measured outside the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline (with a serialized replay of the launch "
+                         "chains), weak_value at N > 1, one learning-function evaluation, the extra workloads, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step as DIR/<name>.npy (float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the extra workloads / weak_value measured outside the timed region")
     ap.add_argument("--chains", type=int, default=0, help="independent launch chains (0 = library default)")
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; gloo for a 1-GPU rehearsal)")
     ap.add_argument("--one-device", action="store_true", help="rehearsal: every rank / shard uses device 0")
@@ -460,9 +498,13 @@ def main():
                     help="auto (faces_train_128_10 at --size 128, else synthetic) | faces_train_128_10 | "
                          "faces_val_128_10 | cameraman_128_10 | circle_128_10 | synthetic")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
 
+    if args.dump_outputs:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)   # the ranks run with cwd = ROOT
     if "WORLD_SIZE" not in os.environ and args.gpus > 1 and not args.multi_handle and not args.sweep:
-        sys.exit(self_launch(args.gpus))
+        sys.exit(self_launch(args.gpus, sys.argv[1:] + (["--dump-outputs", args.dump_outputs] if args.dump_outputs else [])))
 
     import numpy as np
     import torch
@@ -579,19 +621,21 @@ def main():
 
         def step():
             if args.evaluate:
-                solver.evaluate(alpha, 0.1, fetch_u=False, **kw)
-            else:
-                solver.denoise(alpha, fetch=False, **kw)
+                return solver.evaluate(alpha, 0.1, fetch_u=False, **kw)
+            return solver.denoise(alpha, fetch=False, **kw)
         for _ in range(args.warmup):
             step()
         torch.cuda.synchronize()
         ev_ms, ev_launches, ev_steps = 0.0, 0, []
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            step()   # the ABI call returns when every device is quiescent (SURVEY 8b threading)
+            res = step()   # the ABI call returns when every device is quiescent (SURVEY 8b threading)
             st = solver.stats()
             ev_ms += st["pdhg_ms"]; ev_steps.append(st["pdhg_ms"]); ev_launches += st["launches"]
         T = time.perf_counter() - t0
+        if args.dump_outputs:   # evaluate: the caller receives (None, cost, grad); denoise leaves u on the device(s)
+            dump_outputs(args.dump_outputs, {"cost_grad": np.concatenate([[res[1]], np.ravel(res[2])])} if args.evaluate
+                         else {"u": device_u(torch, solver, (args.images, N, M))})
         st = solver.stats()
         n_eff = st["shards"]
         multi_info = {"mode": "bpltv_create_multi (single process, worker thread per device, RCCL inside the library)",
@@ -616,6 +660,11 @@ def main():
         T, ev_ms, ev_launches, ev_steps = timed(make_step(solver, part), args.steps, args.warmup,
                                                 (lambda: solver.stats()) if solver is not None else None)
         scaling, world_out = args.scaling, world
+        if args.dump_outputs:
+            outs = {"u" if world == 1 else "u_rank%d" % rank: device_u(torch, solver, (O_local, N, M))} if solver is not None else {}
+            if args.evaluate and rank == 0:
+                outs["cost_grad"] = part.cpu().numpy()   # [cost, grad...] of the whole batch (all-reduced)
+            dump_outputs(args.dump_outputs, outs, DUMP_CAP_BYTES // world)
         # what every rank did, and what the collective library itself says about the job
         rank_info = None
         if world > 1:
@@ -627,7 +676,7 @@ def main():
                           "pdhg_event_ms_per_step": float(t[3].item())} for r, t in enumerate(allr)]
         # the replica figure (every rank its own full batch, summed): reported beside `value`, never as it
         weak = None
-        if world > 1 and args.scaling == "strong" and not args.no_extras:
+        if args.full and world > 1 and args.scaling == "strong" and not args.no_extras:
             ubw, fw, _ = load_batch(args.data, args.images, N, M, 20211004 + rank)
             sw = make_solver(ubw, fw, args.images)
             wsteps = max(1, min(args.steps, 5))
@@ -645,7 +694,7 @@ def main():
         # isolated duration of one launch (chains replayed one after the other), the number a
         # rocprofv3 --kernel-trace of this command reports per kernel
         ser_ms, ser_l = 0.0, 0
-        if not args.evaluate and not args.multi_handle:
+        if args.full and not args.evaluate and not args.multi_handle:
             for _ in range(3):
                 solver.denoise(alpha, fetch=False, serialize_chains=1, **kw)
                 s2 = solver.stats(); ser_ms += s2["pdhg_ms"]; ser_l += s2["launches"]
@@ -674,10 +723,11 @@ def main():
                        "images_per_gpu": O_roof, "tile_iters": st["tile_iters"], "tiles_per_launch": st_roof["tiles"],
                        "launches_per_step": st["launches"], "hipgraph": bool(st["graph_used"]),
                        "parallelism": ("images of one batch sharded, dp%d" if scaling == "strong" else "one batch per GPU, dp%d") % world_out},
-            "roofline": roofline_of(args, st_roof, M, N, O_roof, args.iters, launch_us, kernel_us, args.f32),
             "pdhg_event_ms_per_step": ev_ms / args.steps,
             "pdhg_event_ms_median": float(np.median(ev_steps)) if ev_steps else None,   # median of the repeats
         }
+        if args.full:
+            out["roofline"] = roofline_of(args, st_roof, M, N, O_roof, args.iters, launch_us, kernel_us, args.f32)
         if world_out > 1:
             comm = {"form": "torch.distributed, one process per GPU" if not args.multi_handle else "in-library",
                     "world_size": dist.get_world_size() if world > 1 else 1,
@@ -697,7 +747,7 @@ def main():
             out["weak_note"] = "replicas: every rank solves its own %d-image batch; sum over ranks; NOT `value`" % args.images
         default_wl = (world_out == 1 and not args.evaluate and not args.multi_handle and not args.f32 and not args.alpha_map
                       and M == 128 and args.images == 10)
-        if world_out == 1 and not args.evaluate and not args.multi_handle and M * N * O_local <= 16 * 128 * 128:
+        if args.full and world_out == 1 and not args.evaluate and not args.multi_handle and M * N * O_local <= 16 * 128 * 128:
             # outside the timed region: one full learning-function evaluation on the same resident batch
             # (PDHG + loss + adjoint gradient), the unit of work of the outer trust-region loop
             part = torch.zeros(npar, dtype=torch.float64, device="cuda")
@@ -711,7 +761,7 @@ def main():
             out["learning_function"] = {"evaluate_ms": min(tt), "pdhg_ms": min(pm), "adjoint_ms": min(am),
                                         "adjoint_method": s3["adjoint_method"], "adjoint_residual": s3["adjoint_residual"],
                                         "note": "tv_op_learning_function on the same batch, best of 3, not part of `value`"}
-        if default_wl and not args.no_extras:
+        if args.full and default_wl and not args.no_extras:
             # extra workloads of the default run, outside the timed region: the reference's
             # default num_samples = 1, and one GPU's share of BASELINE config 5 (8 x 1024^2, per-pixel alpha)
             try:
@@ -722,7 +772,7 @@ def main():
                 }
             except Exception as e:   # never lose the headline line to an extra
                 out["extra_workloads"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if not args.no_cpu_baseline and world_out == 1:  # the CPU baseline is reported at N = 1 only
+        if args.full and not args.no_cpu_baseline and world_out == 1:  # the CPU baseline is reported at N = 1 only
             out["cpu_baseline"] = cpu_baseline(args, f_full, ub_full, alpha, N, M)
         print(json.dumps(out), flush=True)
     if world > 1:

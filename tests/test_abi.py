@@ -67,12 +67,13 @@ def test_create_without_gpu_fails_cleanly_or_succeeds():
     h = C.c_void_p()
     assert lib.bpltv_create(None, 8, 8, 1, -1, 64) != 0
     assert lib.bpltv_create(C.byref(h), 0, 8, 1, -1, 64) != 0      # bad shape
-    assert lib.bpltv_create(C.byref(h), 8, 8, 1, -1, 32) != 0      # only Float64
-    rc = lib.bpltv_create(C.byref(h), 8, 8, 1, -1, 64)
-    if rc == 0:
-        assert lib.bpltv_destroy(h) == 0
-    else:
-        assert rc == 2                                             # BPLTV_E_HIP: no device
+    assert lib.bpltv_create(C.byref(h), 8, 8, 1, -1, 16) == 1      # BPLTV_E_ARG: dtype is 64 or (opt-in) 32
+    for dtype in (64, 32):
+        rc = lib.bpltv_create(C.byref(h), 8, 8, 1, -1, dtype)
+        if rc == 0:
+            assert lib.bpltv_destroy(h) == 0
+        else:
+            assert rc == 2                                         # BPLTV_E_HIP: no device
     assert lib.bpltv_last_error(None) == b"null handle"
     assert lib.bpltv_destroy(None) == 0
 

@@ -288,7 +288,7 @@ def test_bench_multi_gpu_line(mode):
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--iters", "400",
-           "--no-cpu-baseline"] + (["--multi-handle", "--evaluate"] if mode == "multi-handle" else [])
+           "--full", "--no-cpu-baseline"] + (["--multi-handle", "--evaluate"] if mode == "multi-handle" else [])
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -302,6 +302,14 @@ def test_bench_multi_gpu_line(mode):
         assert mh["nccl_ranks_reported_by_rccl"] == 2 and mh["collective"] == "ncclAllReduce" and mh["shard_ranges"] == [[0, 5], [5, 10]]
 
 
+def _bench_mod():
+    import importlib.util, os
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bench.py"))
+    m = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(m)
+    return m
+
+
 def _bench_line(extra, timeout=900):
     import json, os, subprocess, sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -311,26 +319,38 @@ def _bench_line(extra, timeout=900):
     return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
 
 
-def test_bench_two_ranks_rehearsed_on_one_device():
+def test_bench_two_ranks_rehearsed_on_one_device(tmp_path, oracle):
     """bench.py's N > 1 code under the one-GPU suite: two ranks launched by torch.distributed.run on device 0 (gloo --
     RCCL cannot hold two ranks on one device), ONE faces_train_128_10 batch sharded 5 + 5, the replica figure kept out
-    of `value`; the line carries comm / ranks / weak_value as the driver's multi-GPU run will."""
-    line = _bench_line(["--gpus", "2", "--one-device", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--iters", "400", "--no-cpu-baseline"])
+    of `value`; the line carries comm / ranks / weak_value as a multi-GPU run will.  --dump-outputs: each
+    rank writes its shard of u, together the oracle's PDHG of the batch."""
+    line = _bench_line(["--gpus", "2", "--one-device", "--backend", "gloo", "--steps", "2", "--warmup", "1", "--iters", "400", "--full",
+                        "--no-cpu-baseline", "--dump-outputs", str(tmp_path)])
     assert line["n_gpus"] == 2 and line["scaling"] == "strong" and line["value"] > 0
     assert line["comm"]["world_size"] == 2 and line["comm"]["backend"] == "gloo"
     assert [r_["images"] for r_ in line["ranks"]] == [[0, 5], [5, 10]] and all(r_["device"] == 0 for r_ in line["ranks"])
     assert line["weak_value"] > 0 and "NOT `value`" in line["weak_note"]
     assert line["config"]["images_per_gpu"] == 5 and 0 < line["roofline"]["frac"] <= 1.0
+    u = np.concatenate([np.load(tmp_path / ("u_rank%d.npy" % r)) for r in (0, 1)])
+    _, f, _ = _bench_mod().load_batch("auto", 10, 128, 128, 20211004)
+    assert np.array_equal(u, oracle.pdhg(f, 0.1, maxiter=400))
 
 
-def test_bench_multi_handle_and_sweep_rehearsed_on_one_device():
+def test_bench_multi_handle_and_sweep_rehearsed_on_one_device(tmp_path, oracle):
     """The in-library form (`--multi-handle --evaluate`: two shards on device 0, host sum in place of the collective) and
-    the parameter sweep over replicas (`--sweep`: 7 parameters x 1 image on three devices = 3, 2, 2)."""
-    line = _bench_line(["--gpus", "2", "--multi-handle", "--one-device", "--evaluate", "--steps", "2", "--warmup", "1", "--iters", "400", "--no-cpu-baseline"])
+    the parameter sweep over replicas (`--sweep`: 7 parameters x 1 image on three devices = 3, 2, 2); --dump-outputs
+    writes the [cost, grad] of the last evaluation, the oracle's to the tolerances of smoke()."""
+    line = _bench_line(["--gpus", "2", "--multi-handle", "--one-device", "--evaluate", "--steps", "2", "--warmup", "1", "--iters", "400",
+                        "--full", "--no-cpu-baseline", "--dump-outputs", str(tmp_path)])
     mh = line["multi_handle"]
     assert line["n_gpus"] == 2 and mh["shards"] == 2 and mh["shard_ranges"] == [[0, 5], [5, 10]]
     assert mh["collective"] == "host sum" and mh["nccl_ranks_reported_by_rccl"] == 0
     assert "evaluate" in line["config"]["workload"] and 0 < line["roofline"]["frac"] <= 1.0
+    cg = np.load(tmp_path / "cost_grad.npy")
+    ub, f, _ = _bench_mod().load_batch("auto", 10, 128, 128, 20211004)
+    u0 = oracle.pdhg(f, 0.1, maxiter=400)
+    c0, g0 = oracle.cost(u0, ub), oracle.gradient(0.1, u0, ub)
+    assert cg.shape == (2,) and abs(cg[0] - c0) <= 1e-10 * abs(c0) and np.allclose(cg[1], g0, rtol=1e-5, atol=1e-8), (cg, c0, g0)
     line = _bench_line(["--gpus", "3", "--one-device", "--sweep", "7", "--iters", "300", "--steps", "1", "--warmup", "1"])
     sw = line["sweep"]
     assert sw["sweep_shards"] == 3 and sw["parameter_ranges_per_device"] == [[0, 3], [3, 5], [5, 7]] and sw["image_shards"] == 1

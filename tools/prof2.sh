@@ -18,16 +18,16 @@ pmc() { local tag=$1; local ctr=$2; shift 2; echo "== pmc $tag: $ctr"; rocprofv3
 for part in $PARTS; do
 case $part in
 bench)
-  python3 bench.py --steps 10 --warmup 3 > $OUT/bench.log 2>&1 || { tail -20 $OUT/bench.log; exit 1; }
+  python3 bench.py --full --steps 10 --warmup 3 > $OUT/bench.log 2>&1 || { tail -20 $OUT/bench.log; exit 1; }
   tail -1 $OUT/bench.log | cut -c1-400
-  kt kt_bench python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline
-  B="python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-graph"
+  kt kt_bench python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline
+  B="python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-graph"
   pmc pmc_bench_sq1 "$SQ1" $B
   pmc pmc_bench_fetch "FETCH_SIZE" $B
   pmc pmc_bench_write "WRITE_SIZE" $B
   ;;
 cfg5)
-  C="python3 bench.py --images 8 --size 1024 --alpha-map --iters 400 --steps 2 --warmup 1 --no-cpu-baseline"
+  C="python3 bench.py --full --images 8 --size 1024 --alpha-map --iters 400 --steps 2 --warmup 1 --no-cpu-baseline"
   $C > $OUT/bench_cfg5.log 2>&1 || { tail -20 $OUT/bench_cfg5.log; exit 1; }
   tail -1 $OUT/bench_cfg5.log | cut -c1-400
   kt kt_cfg5 $C
@@ -54,9 +54,9 @@ evalcfg5)
   ;;
 f32)
   # the opt-in single-precision mode (never the headline): both shapes, no counters
-  python3 bench.py --f32 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_f32.log 2>&1 || { tail -20 $OUT/bench_f32.log; exit 1; }
+  python3 bench.py --full --f32 --steps 10 --warmup 3 --no-cpu-baseline > $OUT/bench_f32.log 2>&1 || { tail -20 $OUT/bench_f32.log; exit 1; }
   tail -1 $OUT/bench_f32.log | cut -c1-300
-  python3 bench.py --f32 --images 8 --size 1024 --alpha-map --iters 400 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_cfg5_f32.log 2>&1 || { tail -20 $OUT/bench_cfg5_f32.log; exit 1; }
+  python3 bench.py --full --f32 --images 8 --size 1024 --alpha-map --iters 400 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_cfg5_f32.log 2>&1 || { tail -20 $OUT/bench_cfg5_f32.log; exit 1; }
   tail -1 $OUT/bench_cfg5_f32.log | cut -c1-300
   ;;
 sumregs)

@@ -20,18 +20,18 @@ pmc() { local tag=$1; local ctr=$2; shift 2; echo "== pmc $tag: $ctr"; rocprofv3
 for part in $PARTS; do
 case $part in
 bench)
-  python3 bench.py --steps 10 --warmup 3 > $OUT/bench.log 2>&1 || { tail -20 $OUT/bench.log; exit 1; }
+  python3 bench.py --full --steps 10 --warmup 3 > $OUT/bench.log 2>&1 || { tail -20 $OUT/bench.log; exit 1; }
   tail -1 $OUT/bench.log | cut -c1-300
-  kt kt_bench python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-extras
+  kt kt_bench python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-extras
   # counters of the headline launch as the bench runs it (two chains of 245 tiles; eager launches under the profiler)
-  B="python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-extras --no-graph"
+  B="python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-extras --no-graph"
   pmc pmc_bench_sq1 "$SQ1" $B
   pmc pmc_bench_fetch "FETCH_SIZE" $B
   pmc pmc_bench_write "WRITE_SIZE" $B
   ;;
 cfg5)
   # config 5's per-GPU share through the PDHG kernel of large images (pdhg_rows_kernel): line, trace, counters
-  C="python3 bench.py --images 8 --size 1024 --alpha-map --iters 400 --steps 2 --warmup 1 --no-cpu-baseline --no-extras"
+  C="python3 bench.py --full --images 8 --size 1024 --alpha-map --iters 400 --steps 2 --warmup 1 --no-cpu-baseline --no-extras"
   $C > $OUT/bench_cfg5.log 2>&1 || { tail -20 $OUT/bench_cfg5.log; exit 1; }
   tail -1 $OUT/bench_cfg5.log | cut -c1-400
   kt kt_cfg5 $C
