@@ -570,15 +570,25 @@ int upload_alpha(bpltv_t* h, const double* alpha, int am, int an) {
     return BPLTV_OK;
 }
 
-// The same for a parameter that already lives in HBM (bpltv_denoise_device): copied device to device, checked by
-// alpha_check_kernel (one 16-byte read back).
+// The same for a parameter that already lives in HBM (bpltv_denoise_device): checked in place by alpha_check_kernel (one
+// 16-byte read back), then copied device to device.  Nothing of the handle changes before the array is accepted: a
+// rejected parameter leaves d_alpha, its shape and alpha_min -- and so the duality gap of the last solve -- as they were.
 int upload_alpha_device(bpltv_t* h, const double* d_alpha, int am, int an) {
     if (!d_alpha || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "alpha: null pointer or empty shape");
     if (am > h->M || an > h->N)
         return set_err(h, BPLTV_E_ARG, "alpha shape %dx%d exceeds image %dx%d", am, an, h->M, h->N);
     const size_t need = (size_t)am * an;
+    unsigned long long* chk_d = reinterpret_cast<unsigned long long*>(h->d_scalar + 2);
+    HIPCHK(h, hipMemsetAsync(chk_d, 0xFF, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(chk_d + 1, 0, sizeof(unsigned long long), h->stream));
+    hipLaunchKernelGGL(alpha_check_kernel, dim3((unsigned)std::min<size_t>((need + 255) / 256, 1024)), dim3(256), 0, h->stream, d_alpha, need, chk_d);
+    HIPCHK(h, hipGetLastError());
+    unsigned long long chk_h[2] = {0, 1};
+    HIPCHK(h, hipMemcpyAsync(chk_h, chk_d, sizeof(chk_h), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (chk_h[1] != 0) return set_err(h, BPLTV_E_ARG, "alpha (device array): parameters must be finite and >= 0");
     if (h->alpha_cap < need) {
-        drop_graphs(h);
+        drop_graphs(h);  // captured kernels hold the old pointer
         int rc = ensure(h, &h->d_alpha, &h->alpha_cap, need);
         if (rc) return rc;
     }
@@ -587,15 +597,6 @@ int upload_alpha_device(bpltv_t* h, const double* d_alpha, int am, int an) {
         if (rc) return rc;
     }
     HIPCHK(h, hipMemcpyAsync(h->d_alpha, d_alpha, need * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    unsigned long long* chk_d = reinterpret_cast<unsigned long long*>(h->d_scalar + 2);
-    HIPCHK(h, hipMemsetAsync(chk_d, 0xFF, sizeof(unsigned long long), h->stream));
-    HIPCHK(h, hipMemsetAsync(chk_d + 1, 0, sizeof(unsigned long long), h->stream));
-    hipLaunchKernelGGL(alpha_check_kernel, dim3((unsigned)std::min<size_t>((need + 255) / 256, 1024)), dim3(256), 0, h->stream, h->d_alpha, need, chk_d);
-    HIPCHK(h, hipGetLastError());
-    unsigned long long chk_h[2] = {0, 1};
-    HIPCHK(h, hipMemcpyAsync(chk_h, chk_d, sizeof(chk_h), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (chk_h[1] != 0) return set_err(h, BPLTV_E_ARG, "alpha (device array): parameters must be finite and >= 0");
     double chk[1];
     std::memcpy(chk, chk_h, sizeof(double));
     h->alpha_min = chk[0];

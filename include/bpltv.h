@@ -204,8 +204,9 @@ int bpltv_denoise(bpltv_t *h, const double *alpha, int am, int an, const bpltv_p
 /* The same solve with the parameter already resident in HBM (d_alpha: device pointer, am*an doubles, column major) and
  * the result left there (bpltv_u_device): no host array crosses the boundary, which is how bench.py times a pixel-map
  * parameter (8 MiB for 1024 x 1024) without a PCIe copy in the timed region.  The entries are checked on the device
- * (finite, >= 0) exactly as bpltv_denoise checks a host array.  Single-device handles (multi: BPLTV_E_UNSUPPORTED beyond
- * one shard). */
+ * (finite, >= 0) exactly as bpltv_denoise checks a host array, before anything of the handle changes: a parameter
+ * rejected with BPLTV_E_ARG leaves the handle as it was (its resident parameter, and so bpltv_duality_gap of the last
+ * solve).  Single-device handles (multi: BPLTV_E_UNSUPPORTED beyond one shard). */
 int bpltv_denoise_device(bpltv_t *h, const double *d_alpha, int am, int an, const bpltv_params *p);
 
 /* tv_op_learning_function(x, data, D): src/TVLearningFunctionVec.jl:14-27.

@@ -214,7 +214,9 @@ static void pdhg_image(int M, int N, const double *f, const double *alpha, int a
  * (include/bpltv.h, bpltv_create).  Inputs f and alpha and the f64 step table are rounded to float once; every
  * operation of pdhg_x_pass / pdhg_y_pass is repeated in float with fmaf; the projection uses three Newton steps
  * from the 32-bit seed 0x5F375A86 (e -> 1.5 e^2 from < 3.5e-2: 1.8e-3, 4.7e-6, 3.3e-11 < 2^-24).  The result is
- * widened to double.  Not a restatement of anything in the reference (which is Float64 only).
+ * widened to double; bplo_pdhg_f32_dual widens the dual too into y1_out / y2_out (NULL: not wanted) -- the state
+ * the library's duality gap reads after an f32 solve.  Not a restatement of anything in the reference (which is
+ * Float64 only).
  * ---------------------------------------------------------------------------------------- */
 static inline float rsqrt_nr_f(float n2)
 {
@@ -238,8 +240,9 @@ static inline float alpha_at_f(const float *alpha, int am, int an, int M, int N,
     return alpha[(int)(((long)i * am) / M) + (size_t)am * (int)(((long)j * an) / N)];
 }
 
-BPLO_API int bplo_pdhg_f32(int M, int N, int O, const double *f, const double *alpha, int am, int an,
-                           double rho_, double tau0, double sigma0, int accel, int maxiter, double *x_out)
+BPLO_API int bplo_pdhg_f32_dual(int M, int N, int O, const double *f, const double *alpha, int am, int an,
+                                double rho_, double tau0, double sigma0, int accel, int maxiter, double *x_out,
+                                double *y1_out, double *y2_out)
 {
     if (M < 1 || N < 1 || O < 0 || maxiter < 0) return 1;
     const size_t n = (size_t)M * N, na = (size_t)am * an;
@@ -295,10 +298,18 @@ BPLO_API int bplo_pdhg_f32(int M, int N, int O, const double *f, const double *a
                     }
             }
             for (size_t e = 0; e < n; ++e) x_out[n * k + e] = (double)x[e];
+            if (y1_out) for (size_t e = 0; e < n; ++e) y1_out[n * k + e] = (double)y1[e];
+            if (y2_out) for (size_t e = 0; e < n; ++e) y2_out[n * k + e] = (double)y2[e];
         }
     }
     free(tab); free(ff); free(x); free(y1); free(y2); free(xb); free(al);
     return rc;
+}
+
+BPLO_API int bplo_pdhg_f32(int M, int N, int O, const double *f, const double *alpha, int am, int an,
+                           double rho, double tau0, double sigma0, int accel, int maxiter, double *x_out)
+{
+    return bplo_pdhg_f32_dual(M, N, O, f, alpha, am, an, rho, tau0, sigma0, accel, maxiter, x_out, NULL, NULL);
 }
 
 /* The same recurrence with the work of ONE iteration spread over images x column blocks ("OpenMP over

@@ -118,17 +118,27 @@ def pdhg(f, alpha, maxiter=5000, rho=0.0, tau0=5.0, sigma0=0.99 / 5, accel=True,
     return x
 
 
-def pdhg_f32(f, alpha, maxiter=5000, rho=0.0, tau0=5.0, sigma0=0.99 / 5, accel=True):
+def pdhg_f32(f, alpha, maxiter=5000, rho=0.0, tau0=5.0, sigma0=0.99 / 5, accel=True, return_dual=False):
     """"spec v2f": the recurrence in single precision (bplo_pdhg_f32), the checker of the library's opt-in
-    dtype = 32 mode.  Returns the primal widened to float64."""
+    dtype = 32 mode.  Returns the primal widened to float64; with return_dual (u, y1, y2), the float dual widened too
+    (bplo_pdhg_f32_dual)."""
     f = _c(f)
     f3 = f.reshape((-1,) + f.shape[-2:])
     O, N, M = f3.shape
     a, am, an = alpha_arg(alpha)
     x = np.empty_like(f3)
-    rc = lib().bplo_pdhg_f32(M, N, O, _p(f3), _p(a), am, an, rho, tau0, sigma0, int(accel), maxiter, _p(x))
+    if return_dual:
+        y1 = np.empty_like(f3); y2 = np.empty_like(f3)
+        fn = lib().bplo_pdhg_f32_dual
+        fn.restype = C.c_int
+        fn.argtypes = list(lib().bplo_pdhg_f32.argtypes) + [_dp, _dp]
+        rc = fn(M, N, O, _p(f3), _p(a), am, an, rho, tau0, sigma0, int(accel), maxiter, _p(x), _p(y1), _p(y2))
+    else:
+        rc = lib().bplo_pdhg_f32(M, N, O, _p(f3), _p(a), am, an, rho, tau0, sigma0, int(accel), maxiter, _p(x))
     if rc:
         raise RuntimeError("bplo_pdhg_f32 rc=%d" % rc)
+    if return_dual:
+        return x.reshape(f.shape), y1.reshape(f.shape), y2.reshape(f.shape)
     return x.reshape(f.shape)
 
 

@@ -449,3 +449,45 @@ def test_parameter_resident_in_hbm_and_handle_options(gpu_solver_cls):
     assert np.isclose(gsk, g32, rtol=1e-9) and s.evaluate(0.1, 0.1, maxiter=150)[2] == g32
     s.close()
 
+
+
+@pytest.mark.parametrize("dtype", [64, 32])
+@pytest.mark.parametrize("first", ["scalar", "map"])
+@pytest.mark.parametrize("bad", ["nan", "negative"])
+def test_rejected_device_parameter_leaves_the_handle_as_it_was(gpu_solver_cls, dtype, first, bad):
+    """bpltv_denoise_device checks the caller's array before anything of the handle changes: after a rejected parameter
+    (one NaN or one negative entry; BPLTV_E_ARG) the resident parameter, its shape and minimum are those of the last
+    solve, so duality_gap() -- which reads them -- returns the same bits.  A scalar first (the map would reallocate the
+    parameter buffer) and a device map first (same shape: the copy would overwrite it in place)."""
+    import torch
+    from bpldenoising_amd._lib import BpltvError
+    O, N, M = 2, 70, 64
+    ub, f = synth_batch(O, N, M, seed=52)
+    amap = 0.03 + 0.15 * np.random.default_rng(8).random((N, M))
+    s = gpu_solver_cls(M, N, O, dtype=dtype)
+    s.set_data(ub, f)
+    t_a = torch.from_numpy(amap).cuda()
+    if first == "scalar":
+        s.denoise(0.1, maxiter=60, fetch=False)
+    else:
+        torch.cuda.synchronize()
+        s.denoise_device(t_a.data_ptr(), M, N, maxiter=60)
+    g0 = s.duality_gap()
+    assert np.all(np.isfinite(g0)) and np.all(g0 > 0)
+    t_b = t_a.clone()
+    t_b[0, 0] = float("nan") if bad == "nan" else -0.25    # the entry a scalar parameter would be read from
+    t_b[7, 9] = float("nan") if bad == "nan" else -0.5
+    torch.cuda.synchronize()
+    with pytest.raises(BpltvError) as e:
+        s.denoise_device(t_b.data_ptr(), M, N, maxiter=5)
+    assert e.value.code == 1 and "finite" in str(e.value)
+    g1 = s.duality_gap()
+    assert np.array_equal(g1, g0), (g0, g1)
+    assert s.stats()["iterations"] == 60
+    # and the handle still solves: the accepted map after the rejected one
+    torch.cuda.synchronize()
+    s.denoise_device(t_a.data_ptr(), M, N, maxiter=60)
+    u = torch.empty(O * N * M, dtype=torch.float64, device="cuda")
+    s.copy_u_device(u.data_ptr())
+    assert np.array_equal(u.cpu().numpy().reshape(O, N, M), s.denoise(amap, maxiter=60))
+    s.close()

@@ -92,3 +92,23 @@ def test_pdhg_opts_is_the_oracle_recurrence_with_the_unpinned_choices(oracle):
         assert np.abs(a - oracle.pdhg(f, alpha, maxiter=120)).max() > 1e-9      # and it is a different sequence
     L = 2 * np.sqrt(2) * (1 - 1 / 36)
     assert np.abs(oracle.pdhg_opts(f, alpha, maxiter=120, L=L) - oracle.pdhg_variant(f, alpha, maxiter=120, L=L)).max() < 1e-12
+
+
+@pytest.mark.parametrize("alpha", [0.1, np.array([[0.05, 0.1], [0.2, 0.08]]), "map"])
+def test_f32_dual_outputs(oracle, alpha):
+    """bplo_pdhg_f32's y1_out / y2_out (the float dual widened, what the library's duality gap reads after a dtype = 32
+    solve): asking for them leaves u's bits alone, and the gap of the widened triple is a certificate (>= 0) close to the
+    Float64 gap at the same iteration count.  The float floor: measured |gap32 - gap64| <= 1.1e-6 at 400 iterations
+    (gaps ~5e-5), <= 1e-5 relative up to 50."""
+    ub, f = synth_batch(2, 40, 36, seed=12)
+    if isinstance(alpha, str):
+        alpha = 0.05 + 0.1 * np.random.default_rng(1).random((40, 36))
+    for it, rtol, atol in ((1, 1e-6, 0.0), (50, 1e-4, 0.0), (400, 0.0, 5e-6)):
+        u, y1, y2 = oracle.pdhg_f32(f, alpha, maxiter=it, return_dual=True)
+        assert np.array_equal(u, oracle.pdhg_f32(f, alpha, maxiter=it)), it
+        assert np.array_equal(y1, y1.astype(np.float32)) and np.array_equal(y2, y2.astype(np.float32))   # widened floats
+        assert np.abs(y1).max() > 0 and np.abs(y2).max() > 0
+        g32 = oracle.gap(u, y1, y2, f, alpha)
+        g64 = oracle.gap(*oracle.pdhg(f, alpha, maxiter=it, return_dual=True), f, alpha)
+        assert np.all(g32 >= -1e-9), (it, g32)
+        assert np.allclose(g32, g64, rtol=rtol, atol=atol), (it, g32, g64)
