@@ -47,12 +47,12 @@ class BpltvStats(C.Structure):
         ("collective_ms", C.c_double),
         ("nccl_ranks", C.c_int), ("hb_sync", C.c_int), ("adjoint_chunks", C.c_int),
         ("pdhg_variant", C.c_int),
-        ("ncu", C.c_int), ("launch_chains", C.c_int), ("sweep_shards", C.c_int), ("reserved_i", C.c_int),
+        ("ncu", C.c_int), ("launch_chains", C.c_int), ("sweep_shards", C.c_int), ("sweep_groups", C.c_int),
         ("launch_host_ms", C.c_double * 2),
     ]
 
     def as_dict(self):
-        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("reserved", "reserved_i", "launch_host_ms")}
+        d = {k: getattr(self, k) for k, _ in self._fields_ if k not in ("reserved", "launch_host_ms")}
         d["launch_host_ms"] = [self.launch_host_ms[0], self.launch_host_ms[1]]
         d["adjoint_method"] = {1: "band", 2: "bcr", 3: "band-hbm", 4: "band-lu", 5: "nd", 6: "nd-lu"}.get(self.adjoint_method, "")
         d["hb_sync"] = {0: "", 1: "event", 2: "value"}.get(self.hb_sync, "")
@@ -87,6 +87,7 @@ SYMBOLS = {
     "bpltv_grad_fwd_adjoint": (C.c_int, [_H, _dp, _dp, _dp]),
     "bpltv_gradient": (C.c_int, [_H, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp]),
     "bpltv_sweep": (C.c_int, [_H, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp]),
+    "bpltv_sumregs_sweep": (C.c_int, [_H, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp]),
     "bpltv_per_image": (C.c_int, [_H, _dp]),
     "bpltv_set_option": (C.c_int, [_H, C.c_char_p, C.c_double]),
     "bpltv_stats": (C.c_int, [_H, C.POINTER(BpltvStats)]),

@@ -199,9 +199,12 @@ struct SrGraphKey {
     int maxiter, T, am, an, accel, variant;
     double rho, tau0, sigma0;
     const void* tab;
+    int nimg;              // problems of the solve context (the dataset's O, or a sweep group's K_g * O)
+    const void* state;     // its state set and parameter buffer: a sweep never replays a dataset-context graph, nor the reverse
+    const void* alpha;
     bool operator<(const SrGraphKey& o) const {
-        return std::tie(maxiter, T, am, an, accel, variant, rho, tau0, sigma0, tab) <
-               std::tie(o.maxiter, o.T, o.am, o.an, o.accel, o.variant, o.rho, o.tau0, o.sigma0, o.tab);
+        return std::tie(maxiter, T, am, an, accel, variant, rho, tau0, sigma0, tab, nimg, state, alpha) <
+               std::tie(o.maxiter, o.T, o.am, o.an, o.accel, o.variant, o.rho, o.tau0, o.sigma0, o.tab, o.nimg, o.state, o.alpha);
     }
 };
 
@@ -268,6 +271,7 @@ static void device_streams_release(int device) {
 // bpltv_set_option (include/bpltv.h): aids for tests and measurements; nothing here changes a result.
 struct HandleOptions {
     double adjoint_budget_mb = 0.0;   // > 0: HBM the adjoint's factor workspace may take (forces image groups)
+    double sr_sweep_budget_mb = 0.0;  // > 0: HBM the state of a sum-of-regularisers sweep may take (forces parameter groups)
     int sr_force_lu = 0;              // 1: the LU variant of the nested dissection on the symmetric sum-of-regularisers systems too
     int nd_leaf = 0;                  // > 0: leaf size (pixels) of the nested-dissection tree; 0 = 32
     int nd_wave = 1;                  // 0: the workgroup-per-front kernel on every small level (cross-check of nd_front_wave_kernel)
@@ -350,6 +354,15 @@ struct bpltv_handle {
     double *d_u2 = nullptr, *d_ubar2 = nullptr;  // staging for bpltv_gradient
     // sum-of-regularisers model (sumregs_kernels.hpp): state and adjoint workspace, allocated on first use
     double* d_sr[2][7] = {{nullptr}, {nullptr}};   // x, yf1, yf2, yb1, yb2, yc1, yc2; two sets (ping-pong)
+    // current solve context of run_sr_pdhg: default = the O dataset images in d_sr with the parameters in d_alpha;
+    // bpltv_sumregs_sweep swaps in a group of K_g * O problems, its own state and its own parameter blocks
+    double* (*sr_cur)[7] = nullptr;
+    int sr_cur_nimg = 0, sr_cur_astride = 0;
+    const double* sr_cur_alpha = nullptr;            // nullptr: d_alpha
+    double* d_srsweep[2][7] = {{nullptr}, {nullptr}};
+    size_t srsweep_cap = 0;                          // problems
+    double *d_srsweep_alpha = nullptr, *d_srsweep_cost = nullptr;
+    size_t srsweep_alpha_cap = 0, srsweep_cost_cap = 0;
     bool sr_ready = false, sr_adj_ready = false, sr_band_ready = false;
     int last_slices = 1;                            // parameter slices of the last evaluate: 1 (TV) or 3
     int sr_result_buf = 0;
@@ -1518,12 +1531,19 @@ struct SrVariant {
     int R, threads;
     size_t lds;
     void (*kernel)(SrArgs);
+    void (*sweep_kernel)(SrArgs);   // the same kernel for K * O problems of a parameter sweep (f[img % O], block img / O)
 };
 const SrVariant SR_VARIANTS[] = {
-    {32, 32 * 32, sr_lds_bytes(32, 32), &sr_tile_kernel<32, 32>},
-    {48, 48 * 16, sr_lds_bytes(48, 48), &sr_strip_kernel<3, 48, 16>},
+    {32, 32 * 32, sr_lds_bytes(32, 32), &sr_tile_kernel<32, 32>, &sr_tile_kernel<32, 32, true>},
+    {48, 48 * 16, sr_lds_bytes(48, 48), &sr_strip_kernel<3, 48, 16>, &sr_strip_kernel<3, 48, 16, true>},
 };
 constexpr int SR_NVARIANTS = 2;
+
+void drop_sr_graphs(bpltv_t* h) {
+    for (auto& kv : h->sr_graphs)
+        for (auto e : kv.second) (void)hipGraphExecDestroy(e);
+    h->sr_graphs.clear();
+}
 
 int sr_upload_alpha(bpltv_t* h, const double* alpha, int am, int an) {
     if (!alpha || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "alpha: null pointer or empty shape");
@@ -1538,9 +1558,7 @@ int sr_upload_alpha(bpltv_t* h, const double* alpha, int am, int an) {
     h->alpha_min = amin;
     if (h->alpha_cap < need) {
         drop_graphs(h);
-        for (auto& kv : h->sr_graphs)
-            for (auto e : kv.second) (void)hipGraphExecDestroy(e);
-        h->sr_graphs.clear();
+        drop_sr_graphs(h);
         int rc = ensure(h, &h->d_alpha, &h->alpha_cap, need);
         if (rc) return rc;
     }
@@ -1553,17 +1571,38 @@ int sr_upload_alpha(bpltv_t* h, const double* alpha, int am, int an) {
     return BPLTV_OK;
 }
 
+// The K parameter blocks of a sum-of-regularisers sweep (3*am*an doubles each): finite and >= 0, and > 0 when rho != 0 --
+// sr_upload_alpha's and run_sr_pdhg's conditions, checked before the call changes anything.
+int sr_check_blocks(bpltv_t* h, const double* alphas, int K, int am, int an, double rho, double* amin_out) {
+    if (!alphas || K < 1) return set_err(h, BPLTV_E_ARG, "sumregs_sweep: null pointer or K < 1");
+    if (am < 1 || an < 1 || am > h->M || an > h->N) return set_err(h, BPLTV_E_ARG, "sumregs_sweep: bad parameter shape %dx%dx3", am, an);
+    const size_t n = (size_t)K * 3 * am * an;
+    double amin = alphas[0];
+    for (size_t e = 0; e < n; ++e) {
+        if (!std::isfinite(alphas[e]) || alphas[e] < 0.0)
+            return set_err(h, BPLTV_E_ARG, "sumregs_sweep: alphas[%zu] = %g: parameters must be finite and >= 0", e, alphas[e]);
+        if (alphas[e] < amin) amin = alphas[e];
+    }
+    if (rho != 0.0 && !(amin > 0.0))
+        return set_err(h, BPLTV_E_ARG, "rho != 0 divides by alpha: every parameter entry must be > 0 (min = %g)", amin);
+    if (amin_out) *amin_out = amin;
+    return BPLTV_OK;
+}
+
 int sr_alloc(bpltv_t* h) {
     if (h->sr_ready) return BPLTV_OK;
     for (int s = 0; s < 2; ++s)
         for (int c = 0; c < 7; ++c) HIPCHK(h, hipMalloc((void**)&h->d_sr[s][c], h->tot * sizeof(double)));
     for (const SrVariant& v : SR_VARIANTS)
-        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(v.kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds));
+        for (auto k : {v.kernel, v.sweep_kernel})
+            HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds));
     h->sr_ready = true;
     return BPLTV_OK;
 }
 
-// maxiter iterations of the three-dual PDHG, T fused per launch (halo 2T), replayed from a hipGraph.
+// maxiter iterations of the three-dual PDHG, T fused per launch (halo 2T), replayed from a hipGraph, on the current solve
+// context: h->sr_cur_nimg problems in the state sets h->sr_cur; problem img reads f[img % O] and the parameter block
+// img / O (sr_cur_astride doubles apart) of sr_cur_alpha (d_alpha when null).
 int run_sr_pdhg(bpltv_t* h, const bpltv_params& p) {
     h->has_per_image = false;
     if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "bpltv_set_data has not been called");
@@ -1575,7 +1614,10 @@ int run_sr_pdhg(bpltv_t* h, const bpltv_params& p) {
     double* d_tab = nullptr;
     if (p.init != 0 || p.order != 0)
         return set_err(h, BPLTV_E_UNSUPPORTED, "params.init / params.order are implemented for the TV model only");
-    if (h->O > 65535) return set_err(h, BPLTV_E_UNSUPPORTED, "the sum-of-regularisers solve takes at most 65535 images per handle (images are a grid dimension)");
+    const int nimg = h->sr_cur_nimg;
+    double* (*S)[7] = h->sr_cur;
+    const double* d_alpha = h->sr_cur_alpha ? h->sr_cur_alpha : h->d_alpha;
+    if (nimg > 65535) return set_err(h, BPLTV_E_UNSUPPORTED, "the sum-of-regularisers solve takes at most 65535 problems per launch (problems are a grid dimension)");
     rc = get_table(h, p, &d_tab, 18.0);   // ||G_f||^2 + ||G_b||^2 + ||G_c||^2 <= 8 + 8 + 2 (sumregs_oracle.c: SR_L)
     if (rc) return rc;
     const int M = h->M, N = h->N;
@@ -1590,7 +1632,7 @@ int run_sr_pdhg(bpltv_t* h, const bpltv_params& p) {
         const int ncu = h->ncu > 0 ? h->ncu : 256;
         auto tiles = [&](int R) {
             const int Tt = std::max(1, std::min(4, std::min((M <= R) ? 4 : (R - 1) / 4, (N <= R) ? 4 : (R - 1) / 4)));
-            return (double)tile_count(M, R, 2 * Tt) * tile_count(N, R, 2 * Tt) * h->O;
+            return (double)tile_count(M, R, 2 * Tt) * tile_count(N, R, 2 * Tt) * nimg;
         };
         const double t32 = tiles(32), t48 = tiles(48);
         const double c32 = 0.6 + 0.0056 * t32;
@@ -1605,16 +1647,18 @@ int run_sr_pdhg(bpltv_t* h, const bpltv_params& p) {
     if (T < 1) return set_err(h, BPLTV_E_ARG, "tile_iters must be >= 1");
     const int nTi = tile_count(M, SR_R, 2 * T), nTj = tile_count(N, SR_R, 2 * T);
     if (nTi < 1 || nTj < 1) return set_err(h, BPLTV_E_ARG, "cannot tile %dx%d with T=%d", M, N, T);
-    const int grid = nTi * nTj * h->O;
+    const int grid = nTi * nTj * nimg;
     h->st.tile_iters = T; h->st.tiles = grid; h->st.region_i = SR_R; h->st.region_j = SR_R; h->st.pdhg_variant = vi + 1;
     h->st.launches = 0; h->st.iterations = p.maxiter; h->st.graph_used = 0; h->st.last_gap = -1.0; h->st.launch_chains = 1;
-    if (p.maxiter == 0) {
-        HIPCHK(h, hipMemcpyAsync(h->d_sr[0][0], h->d_f, h->tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        for (int c = 1; c < 7; ++c) HIPCHK(h, hipMemsetAsync(h->d_sr[0][c], 0, h->tot * sizeof(double), h->stream));
+    if (p.maxiter == 0) {   // u = f for every parameter block
+        for (int r = 0; r < nimg / h->O; ++r)
+            HIPCHK(h, hipMemcpyAsync(S[0][0] + (size_t)r * h->tot, h->d_f, h->tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        for (int c = 1; c < 7; ++c) HIPCHK(h, hipMemsetAsync(S[0][c], 0, (size_t)nimg * h->npx * sizeof(double), h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
         h->sr_result_buf = 0; h->sr_has_result = true; h->last_is_sr = true; h->st.pdhg_ms = 0.0;
         return BPLTV_OK;
     }
+    void (*kern)(SrArgs) = nimg == h->O ? V.kernel : V.sweep_kernel;
     // iterations [it0, it1) of the images [lo, hi) from the state set `cur`; returns the set holding the result.
     // stagger: the chain's first launch fuses T/2 iterations and writes set 1 (run_pdhg's launch chains).
     auto enqueue_range = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) -> int {
@@ -1622,19 +1666,20 @@ int run_sr_pdhg(bpltv_t* h, const bpltv_params& p) {
         for (int it = it0; it < it1; it += step, step = T) {
             SrArgs a;
             const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
-            for (int c = 0; c < 7; ++c) { a.in[c] = h->d_sr[cur][c]; a.out[c] = h->d_sr[nxt][c]; }
-            a.f = h->d_f; a.alpha = h->d_alpha; a.tab = d_tab; a.rho = p.rho;
+            for (int c = 0; c < 7; ++c) { a.in[c] = S[cur][c]; a.out[c] = S[nxt][c]; }
+            a.f = h->d_f; a.alpha = d_alpha; a.tab = d_tab; a.rho = p.rho;
             a.am = h->last_am; a.an = h->last_an;
             a.it0 = it; a.nit = std::min(step, it1 - it);
-            a.M = M; a.N = N; a.O = h->O; a.nTi = nTi; a.nTj = nTj; a.halo = 2 * T;
+            a.M = M; a.N = N; a.O = nimg; a.nTi = nTi; a.nTj = nTj; a.halo = 2 * T;
             a.first = (it == 0) ? 1 : 0;
             a.img0 = lo;
-            hipLaunchKernelGGL(V.kernel, dim3(nTi, nTj, hi - lo), dim3(V.threads), V.lds, st, a);
+            a.Odata = h->O; a.astride = h->sr_cur_astride;
+            hipLaunchKernelGGL(kern, dim3(nTi, nTj, hi - lo), dim3(V.threads), V.lds, st, a);
             cur = nxt;
         }
         return cur;
     };
-    auto enqueue = [&](hipStream_t st) -> int { return enqueue_range(st, 0, p.maxiter, 0, 0, h->O, false); };
+    auto enqueue = [&](hipStream_t st) -> int { return enqueue_range(st, 0, p.maxiter, 0, 0, nimg, false); };
     if (p.check_every > 0) {   // duality-gap checks every check_every iterations, early stop at gap_tol (as the TV model)
         HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
         int it = 0, cur = 0, launches = 0;
@@ -1670,23 +1715,20 @@ int run_sr_pdhg(bpltv_t* h, const bpltv_params& p) {
     // two launch chains (image groups) as in run_pdhg: chain 0 on the handle's stream, chain 1 on a second one, half a
     // launch out of phase; reserved[1] = 1 keeps one chain
     const int h0 = std::max(1, T / 2);
-    int nch = p.reserved[1] > 0 ? std::min(p.reserved[1], 2) : ((2 * grid > 3 * (h->ncu > 0 ? h->ncu : 256) && h->O >= 2) ? 2 : 1);
-    if (nch > h->O) nch = h->O;
+    int nch = p.reserved[1] > 0 ? std::min(p.reserved[1], 2) : ((2 * grid > 3 * (h->ncu > 0 ? h->ncu : 256) && nimg >= 2) ? 2 : 1);
+    if (nch > nimg) nch = nimg;
     const bool stag = T >= 2 && nl >= 8 && ((1 + (p.maxiter - h0 + T - 1) / T) - nl) % 2 == 1;
     HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     bool done = false;
     if (p.use_graph && nl <= 50000) {
-        SrGraphKey key{p.maxiter, T, h->last_am, h->last_an, p.accel ? 1 : 0, vi + 16 * nch, p.rho, p.tau0, p.sigma0, (const void*)d_tab};
+        SrGraphKey key{p.maxiter, T, h->last_am, h->last_an, p.accel ? 1 : 0, vi + 16 * nch, p.rho, p.tau0, p.sigma0, (const void*)d_tab,
+                       nimg, (const void*)S[0][0], (const void*)d_alpha};
         auto it = h->sr_graphs.find(key);
         if (it == h->sr_graphs.end()) {
-            if (h->sr_graphs.size() >= 8) {
-                for (auto& kv : h->sr_graphs)
-                    for (auto e : kv.second) (void)hipGraphExecDestroy(e);
-                h->sr_graphs.clear();
-            }
+            if (h->sr_graphs.size() >= 8) drop_sr_graphs(h);
             std::vector<hipGraphExec_t> exs;
             for (int c = 0; c < nch; ++c) {
-                const int lo = (int)(((long)h->O * c) / nch), hi = (int)(((long)h->O * (c + 1)) / nch);
+                const int lo = (int)(((long)nimg * c) / nch), hi = (int)(((long)nimg * (c + 1)) / nch);
                 hipGraph_t g = nullptr;
                 hipGraphExec_t ex = nullptr;
                 if (!h->capture_stream && hipStreamCreateWithFlags(&h->capture_stream, hipStreamNonBlocking) != hipSuccess) { h->capture_stream = nullptr; break; }
@@ -1731,7 +1773,7 @@ int run_sr_pdhg(bpltv_t* h, const bpltv_params& p) {
     h->last_is_sr = true;
     const bool amap = (h->last_am == M && h->last_an == N) && !(M == 1 && N == 1);
     h->st.bytes_per_px_iter = amap ? 144.0 : 120.0;   // read x, 6 y, f (+ 3 alpha), write x, 6 y
-    h->st.algorithmic_bytes = h->st.bytes_per_px_iter * (double)h->tot * p.maxiter;
+    h->st.algorithmic_bytes = h->st.bytes_per_px_iter * (double)h->npx * nimg * p.maxiter;
     return BPLTV_OK;
 }
 
@@ -2340,8 +2382,9 @@ int multi_gradient(bpltv_t* h, const double* u, const double* ubar, const double
     return multi_stats(h);
 }
 
+// slices: 1 TV (bpltv_sweep), 3 sum of regularisers (bpltv_sumregs_sweep; 3*am*an doubles per parameter block)
 int multi_sweep(bpltv_t* h, const double* alphas, int K, int am, int an, const bpltv_params* pp, double* cost_out,
-                double* u_out) {
+                double* u_out, int slices = 1) {
     if (!alphas || !cost_out || K < 1) return set_err(h, BPLTV_E_ARG, "sweep: null pointer or K < 1");
     if (am < 1 || an < 1 || am > h->M || an > h->N) return set_err(h, BPLTV_E_ARG, "sweep: bad parameter shape %dx%d", am, an);
     WallTimer wt;
@@ -2361,13 +2404,14 @@ int multi_sweep(bpltv_t* h, const double* alphas, int K, int am, int an, const b
         if (by_par && nrep >= 1 && !(n == 1 && nrep == 1)) {
             int rc = multi_replicas_ready(h, nrep);
             if (rc) return rc;
-            const size_t npar = (size_t)am * an;
+            const size_t npar = (size_t)am * an * slices;
             rc = rep_run(h, nrep, [&](int r, bpltv_t* c) -> int {
                 int lo, hi;
                 shard_range(K, nrep, r, &lo, &hi);
                 // parameter-major outputs: replica r's blocks [lo, hi) are contiguous in cost_out and u_out
-                return bpltv_sweep(c, alphas + (size_t)lo * npar, hi - lo, am, an, pp, cost_out + lo,
-                                   u_out ? u_out + (size_t)lo * h->O * npx : nullptr);
+                double* uo = u_out ? u_out + (size_t)lo * h->O * npx : nullptr;
+                return slices == 3 ? bpltv_sumregs_sweep(c, alphas + (size_t)lo * npar, hi - lo, am, an, pp, cost_out + lo, uo)
+                                   : bpltv_sweep(c, alphas + (size_t)lo * npar, hi - lo, am, an, pp, cost_out + lo, uo);
             });
             if (rc) return rc;
             bpltv_stats_t a = ms.rep[0]->st;
@@ -2378,6 +2422,7 @@ int multi_sweep(bpltv_t* h, const double* alphas, int K, int am, int an, const b
                 a.pdhg_ms = std::max(a.pdhg_ms, b.pdhg_ms);
                 a.algorithmic_bytes += b.algorithmic_bytes;
                 a.iterations = std::max(a.iterations, b.iterations);
+                a.sweep_groups = std::max(a.sweep_groups, b.sweep_groups);
             }
             a.O = h->O; a.ngpus = h->st.ngpus; a.shards = h->st.shards; a.nccl_ranks = h->st.nccl_ranks;
             a.collective = 0; a.collective_ms = 0.0;
@@ -2392,7 +2437,9 @@ int multi_sweep(bpltv_t* h, const double* alphas, int K, int am, int an, const b
     int rc = multi_run(h, [&](int k, bpltv_t* c) -> int {
         const size_t Ok = (size_t)(ms.hi[k] - ms.lo[k]);
         if (u_out) ubuf[k].resize((size_t)K * Ok * npx);
-        const int r = bpltv_sweep(c, alphas, K, am, an, pp, cost.data() + (size_t)k * K, u_out ? ubuf[k].data() : nullptr);
+        double* co = cost.data() + (size_t)k * K;
+        double* uo = u_out ? ubuf[k].data() : nullptr;
+        const int r = slices == 3 ? bpltv_sumregs_sweep(c, alphas, K, am, an, pp, co, uo) : bpltv_sweep(c, alphas, K, am, an, pp, co, uo);
         if (r == BPLTV_OK && u_out)   // parameter-major [K][O][N][M]: this shard's images of every parameter block
             for (int q = 0; q < K; ++q)
                 std::memcpy(u_out + ((size_t)q * h->O + ms.lo[k]) * npx, ubuf[k].data() + (size_t)q * Ok * npx, Ok * npx * sizeof(double));
@@ -2480,6 +2527,9 @@ int bpltv_create(bpltv_t** out, int M, int N, int O, int device, int dtype) {
     h->cur_state = h->d_state;
     h->cur_nimg = O;
     h->cur_astride = 0;
+    h->sr_cur = h->d_sr;
+    h->sr_cur_nimg = O;
+    h->sr_cur_astride = 0;
     HIPCHK(h, hipMalloc((void**)&h->d_perimg, (size_t)O * sizeof(double)));
     HIPCHK(h, hipMalloc((void**)&h->d_scalar, 4 * sizeof(double)));
     // LDS above 64 KB needs the opt-in attribute
@@ -2549,13 +2599,15 @@ int bpltv_destroy(bpltv_t* h) {
     h->hb_sr.release();
     h->lu_sr.release();
     if (h->d_srdiagU) (void)hipFree(h->d_srdiagU);
-    for (auto& kv : h->sr_graphs)
-        for (auto e : kv.second) (void)hipGraphExecDestroy(e);
-    for (void* q : {(void*)h->d_srcoef, (void*)h->d_srdiag, (void*)h->d_srw, (void*)h->d_srgpix})
+    drop_sr_graphs(h);
+    for (void* q : {(void*)h->d_srcoef, (void*)h->d_srdiag, (void*)h->d_srw, (void*)h->d_srgpix, (void*)h->d_srsweep_alpha,
+                    (void*)h->d_srsweep_cost})
         if (q) (void)hipFree(q);
     for (int s2 = 0; s2 < 2; ++s2)
-        for (int c = 0; c < 7; ++c)
+        for (int c = 0; c < 7; ++c) {
             if (h->d_sr[s2][c]) (void)hipFree(h->d_sr[s2][c]);
+            if (h->d_srsweep[s2][c]) (void)hipFree(h->d_srsweep[s2][c]);
+        }
     if (h->stream) device_streams_release(h->device);
     delete h;
     return BPLTV_OK;
@@ -2901,6 +2953,111 @@ int bpltv_sweep(bpltv_t* h, const double* alphas, int K, int am, int an, const b
     return BPLTV_OK;
 }
 
+// The sum-of-regularisers twin of bpltv_sweep: K parameter blocks x O images as K*O problems of run_sr_pdhg, in groups
+// of whole parameter blocks that fit the grid (65535 problems) and HBM (14 state planes per problem).  Every problem is
+// computed as in any other grouping and its loss reduced on its own, so the result does not depend on the grouping.
+// The dataset context (d_sr, d_alpha and the result flags of the last solve) is left as it was.
+int bpltv_sumregs_sweep(bpltv_t* h, const double* alphas, int K, int am, int an, const bpltv_params* pp, double* cost_out,
+                        double* u_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (!cost_out) return set_err(h, BPLTV_E_ARG, "sumregs_sweep: null output pointer");
+    bpltv_params p;
+    if (pp) p = *pp; else bpltv_sumregs_default_params(&p);
+    double amin = 0.0;
+    if (int rc = sr_check_blocks(h, alphas, K, am, an, p.rho, &amin)) return rc;
+    if (h->multi) return multi_sweep(h, alphas, K, am, an, pp, cost_out, u_out, 3);
+    if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "bpltv_set_data has not been called");
+    if (int prc = check_params(h, p)) return prc;
+    const int O = h->O;
+    if (O > 65535) return set_err(h, BPLTV_E_UNSUPPORTED, "the sum-of-regularisers solve takes at most 65535 images per handle (images are a grid dimension)");
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    p.check_every = 0;  // the gap kernels address the dataset context only
+    const size_t npx = h->npx, nb = 3 * (size_t)am * an;
+    // groups of whole parameter blocks: at most 65535 problems (a grid dimension of the PDHG and loss launches) and what
+    // fits the HBM budget (option "sr_sweep_budget_mb", else what is free plus the state already held, minus 2 GB)
+    const size_t per_problem = 14 * npx * sizeof(double);
+    size_t budget = 0;
+    if (h->opt.sr_sweep_budget_mb > 0.0) {
+        budget = (size_t)(h->opt.sr_sweep_budget_mb * 1e6);
+    } else {
+        size_t freeb = 0, totalb = 0;
+        (void)hipMemGetInfo(&freeb, &totalb);
+        const size_t held = h->srsweep_cap * per_problem, reserve = 2ull << 30;
+        budget = freeb + held > reserve ? freeb + held - reserve : 0;
+    }
+    const size_t kfit = std::min<size_t>(budget / per_problem, 65535) / (size_t)O;
+    if (kfit < 1)
+        return set_err(h, BPLTV_E_NOMEM, "sumregs_sweep: the state of one parameter block (%d problems of %dx%d) needs %.3f GB of HBM, %.3f GB available",
+                       O, h->M, h->N, per_problem * O / 1e9, budget / 1e9);
+    const int ng = (int)(((size_t)K + kfit - 1) / kfit);   // equal groups (sizes differ by at most one block: two graphs)
+    const int kmax = (K + ng - 1) / ng;
+    const size_t pmax = (size_t)kmax * O;
+    if (h->srsweep_cap < pmax) {
+        drop_sr_graphs(h);   // captured launches hold the old planes
+        h->srsweep_cap = 0;
+        for (int sb = 0; sb < 2; ++sb)
+            for (int c = 0; c < 7; ++c) {
+                if (h->d_srsweep[sb][c]) HIPCHK(h, hipFree(h->d_srsweep[sb][c]));
+                h->d_srsweep[sb][c] = nullptr;
+            }
+        for (int sb = 0; sb < 2; ++sb)
+            for (int c = 0; c < 7; ++c) HIPCHK(h, hipMalloc((void**)&h->d_srsweep[sb][c], pmax * npx * sizeof(double)));
+        h->srsweep_cap = pmax;
+    }
+    if (h->srsweep_alpha_cap < kmax * nb) drop_sr_graphs(h);
+    int rc = ensure(h, &h->d_srsweep_alpha, &h->srsweep_alpha_cap, kmax * nb);
+    if (rc) return rc;
+    rc = ensure(h, &h->d_srsweep_cost, &h->srsweep_cost_cap, pmax);
+    if (rc) return rc;
+    const int nblk = 16;
+    rc = ensure(h, &h->d_red, &h->red_cap, pmax * nblk);
+    if (rc) return rc;
+    std::vector<double> per((size_t)K * O);
+    double pdhg_ms = 0.0, abytes = 0.0;
+    int launches = 0, tiles = 0;
+    for (int g = 0; g < ng; ++g) {
+        const int k0 = (int)(((long)K * g) / ng), k1 = (int)(((long)K * (g + 1)) / ng);
+        const int np = (k1 - k0) * O;
+        HIPCHK(h, hipMemcpyAsync(h->d_srsweep_alpha, alphas + (size_t)k0 * nb, (size_t)(k1 - k0) * nb * sizeof(double),
+                                 hipMemcpyHostToDevice, h->stream));
+        // the group's solve context; the dataset context comes back whatever run_sr_pdhg returns
+        const int am0 = h->last_am, an0 = h->last_an, rb0 = h->sr_result_buf;
+        const double amin0 = h->alpha_min;
+        const bool has0 = h->sr_has_result, last0 = h->last_is_sr;
+        h->sr_cur = h->d_srsweep; h->sr_cur_nimg = np; h->sr_cur_astride = (int)nb; h->sr_cur_alpha = h->d_srsweep_alpha;
+        h->last_am = am; h->last_an = an; h->alpha_min = amin;
+        rc = run_sr_pdhg(h, p);
+        const int rb = h->sr_result_buf;
+        h->sr_cur = h->d_sr; h->sr_cur_nimg = O; h->sr_cur_astride = 0; h->sr_cur_alpha = nullptr;
+        h->last_am = am0; h->last_an = an0; h->alpha_min = amin0;
+        h->sr_result_buf = rb0; h->sr_has_result = has0; h->last_is_sr = last0;
+        if (rc) return rc;
+        pdhg_ms += h->st.pdhg_ms; launches += h->st.launches; tiles += h->st.tiles; abytes += h->st.algorithmic_bytes;
+        // loss of every problem against ubar[img % O]; summed per parameter block on the host
+        hipLaunchKernelGGL(cost_partial_mod_kernel, dim3(nblk, (unsigned)np), dim3(256), 0, h->stream, h->d_srsweep[rb][0],
+                           h->d_ubar, (int)npx, O, h->d_red);
+        hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, nblk, np, 0.5, h->d_srsweep_cost,
+                           (double*)nullptr);
+        HIPCHK(h, hipGetLastError());
+        HIPCHK(h, hipMemcpyAsync(per.data() + (size_t)k0 * O, h->d_srsweep_cost, (size_t)np * sizeof(double), hipMemcpyDeviceToHost,
+                                 h->stream));
+        if (u_out)
+            HIPCHK(h, hipMemcpyAsync(u_out + (size_t)k0 * O * npx, h->d_srsweep[rb][0], (size_t)np * npx * sizeof(double),
+                                     hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    for (int k = 0; k < K; ++k) {
+        double sacc = 0.0;
+        for (int i = 0; i < O; ++i) sacc += per[(size_t)k * O + i];
+        cost_out[k] = sacc;
+    }
+    h->st.pdhg_ms = pdhg_ms; h->st.launches = launches; h->st.tiles = tiles; h->st.algorithmic_bytes = abytes;
+    h->st.sweep_groups = ng;
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
 int bpltv_per_image(bpltv_t* h, double* out) {
     if (!h || !out) return BPLTV_E_ARG;
     if (h->multi) {
@@ -2947,6 +3104,9 @@ int bpltv_set_option(bpltv_t* h, const char* name, double value) {
     if (nm == "adjoint_budget_mb") {
         if (value < 0.0) return set_err(h, BPLTV_E_ARG, "set_option(adjoint_budget_mb): must be >= 0");
         h->opt.adjoint_budget_mb = value;
+    } else if (nm == "sr_sweep_budget_mb") {
+        if (value < 0.0) return set_err(h, BPLTV_E_ARG, "set_option(sr_sweep_budget_mb): must be >= 0");
+        h->opt.sr_sweep_budget_mb = value;
     } else if (nm == "sr_force_lu") {
         h->opt.sr_force_lu = iv ? 1 : 0;
     } else if (nm == "nd_leaf") {

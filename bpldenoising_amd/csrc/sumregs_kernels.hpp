@@ -25,15 +25,19 @@ struct SrArgs {
     const double* in[7];   // x, yf1, yf2, yb1, yb2, yc1, yc2
     double* out[7];
     const double* f;
-    const double* alpha;   // 3 slices of am*an doubles
+    const double* alpha;   // parameter blocks of 3 slices of am*an doubles each
     const double* tab;     // [maxiter][TAB_STRIDE], L = sqrt(18)
     double rho;
     int am, an;
     int it0, nit;
-    int M, N, O;
+    int M, N, O;           // O: problems of the solve (state slots)
     int nTi, nTj, halo;    // halo = 2 * fused iterations
     int first;
     int img0;              // first image of this launch (launch chains: grid = tiles per image * images of the chain)
+    int Odata;             // images in the dataset; problem `img` uses f[img % Odata] and the parameter block
+                           // alpha + (img / Odata) * astride (parameter sweeps: K * Odata problems, the SWEEP instances of
+                           // the kernels; O == Odata otherwise)
+    int astride;           // doubles per parameter block: 3 * am * an
 };
 
 __device__ __forceinline__ size_t sr_alpha_index(int am, int an, int M, int N, int i, int j) {
@@ -42,7 +46,11 @@ __device__ __forceinline__ size_t sr_alpha_index(int am, int an, int M, int N, i
     return (size_t)(((unsigned)i * (unsigned)am) / (unsigned)M) + (size_t)am * (((unsigned)j * (unsigned)an) / (unsigned)N);
 }
 
-template <int TI, int TJ>
+// SWEEP = false: the dataset context (O == Odata, problem img reads f[img] and the one parameter block), the prologue of the
+// kernel before parameter sweeps existed.  A runtime O == Odata test (pdhg_data_image) costs two more kernarg loads and a
+// scalar wait in front of every workgroup: +2.5 % on the 10 x 128^2 solve of 1250 launches, so the split of a
+// sweep problem into (image, parameter block) is compiled into the SWEEP = true instances only.
+template <int TI, int TJ, bool SWEEP = false>
 __global__ __launch_bounds__(TI* TJ) void sr_tile_kernel(SrArgs A) {
     constexpr int RI = TI, RJ = TJ, RN = RI * RJ;
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -57,16 +65,20 @@ __global__ __launch_bounds__(TI* TJ) void sr_tile_kernel(SrArgs A) {
     tile_span(ta, A.M, RI, A.halo, oi, ci0, ci1);
     tile_span(tb, A.N, RJ, A.halo, oj, cj0, cj1);
     const int M = A.M, N = A.N;
-    const size_t base = (size_t)img * M * N;
+    int fimg = img, apar = 0;   // uniform over the workgroup: scalar registers
+    if (SWEEP) { fimg = (int)((unsigned)img % (unsigned)A.Odata); apar = (int)((unsigned)img / (unsigned)A.Odata); }
+    const size_t base = (size_t)img * M * N;                             // state planes: one slot per problem
+    const double* __restrict__ fsrc = A.f + (size_t)fimg * M * N;        // dataset plane
+    const double* __restrict__ alpha = A.alpha + (size_t)apar * A.astride;
     const int gi = oi + li, gj = oj + lj;
     const bool in = gi < M && gj < N;
     const int ci = min(gi, M - 1), cj = min(gj, N - 1);
-    const size_t g = base + ci + (size_t)M * cj;
-    const size_t ai = sr_alpha_index(A.am, A.an, M, N, ci, cj), astride = (size_t)A.am * A.an;
+    const size_t q = ci + (size_t)M * cj, g = base + q;
+    const size_t ai = sr_alpha_index(A.am, A.an, M, N, ci, cj), sl = (size_t)A.am * A.an;
     // ---- prologue: all global loads first
     double x, f, y[6], al[3];
-    f = A.f[g];
-    al[0] = A.alpha[ai]; al[1] = A.alpha[astride + ai]; al[2] = A.alpha[2 * astride + ai];
+    f = fsrc[q];
+    al[0] = alpha[ai]; al[1] = alpha[sl + ai]; al[2] = alpha[2 * sl + ai];
     if (!A.first) {
         x = A.in[0][g];
 #pragma unroll
@@ -178,7 +190,7 @@ __global__ __launch_bounds__(TI* TJ) void sr_tile_kernel(SrArgs A) {
 // in registers: of the 12 LDS reads and 7 writes per pixel and iteration of sr_tile_kernel, 8 and 5.33 remain at
 // PJ = 3 (planes yf2 / yb2 are only read across a strip boundary, from the strip's last / first pixel; yc2 from both).
 // Same operation sequence per pixel: bit-identical to sr_tile_kernel and to the oracle.
-template <int PJ, int TI, int TJ>
+template <int PJ, int TI, int TJ, bool SWEEP = false>
 __global__ __launch_bounds__(TI* TJ) void sr_strip_kernel(SrArgs A) {
     constexpr int RI = TI, RJ = PJ * TJ, RN = RI * RJ;
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -193,9 +205,13 @@ __global__ __launch_bounds__(TI* TJ) void sr_strip_kernel(SrArgs A) {
     tile_span(ta, A.M, RI, A.halo, oi, ci0, ci1);
     tile_span(tb, A.N, RJ, A.halo, oj, cj0, cj1);
     const int M = A.M, N = A.N;
+    int fimg = img, apar = 0;   // as in sr_tile_kernel
+    if (SWEEP) { fimg = (int)((unsigned)img % (unsigned)A.Odata); apar = (int)((unsigned)img / (unsigned)A.Odata); }
     const size_t base = (size_t)img * M * N;
+    const double* __restrict__ fsrc = A.f + (size_t)fimg * M * N;
+    const double* __restrict__ alpha = A.alpha + (size_t)apar * A.astride;
     const int gi = oi + li, ci = min(gi, M - 1);
-    const size_t astride = (size_t)A.am * A.an;
+    const size_t sl = (size_t)A.am * A.an;
     double x[PJ], f[PJ], y[PJ][6], al[PJ][3], bc[PJ];
     size_t g[PJ];
     bool hasU[PJ], hasD[PJ];
@@ -203,10 +219,11 @@ __global__ __launch_bounds__(TI* TJ) void sr_strip_kernel(SrArgs A) {
 #pragma unroll
     for (int pj = 0; pj < PJ; ++pj) {
         const int gj = oj + lj0 + pj, cj = min(gj, N - 1);
-        g[pj] = base + ci + (size_t)M * cj;
+        const size_t q = ci + (size_t)M * cj;
+        g[pj] = base + q;
         const size_t ai = sr_alpha_index(A.am, A.an, M, N, ci, cj);
-        f[pj] = A.f[g[pj]];
-        al[pj][0] = A.alpha[ai]; al[pj][1] = A.alpha[astride + ai]; al[pj][2] = A.alpha[2 * astride + ai];
+        f[pj] = fsrc[q];
+        al[pj][0] = alpha[ai]; al[pj][1] = alpha[sl + ai]; al[pj][2] = alpha[2 * sl + ai];
         if (!A.first) {
             x[pj] = A.in[0][g[pj]];
 #pragma unroll

@@ -269,6 +269,24 @@ def generate_2d_tv_cost(dataset_name, parameter_range_1, parameter_range_2, num_
     return costs
 
 
+def generate_sumregs_cost(dataset_name, parameters, num_samples=1, datasets_root=None, npz=None, out_root=None,
+                          ngpus=None, devices=None, **solver_kwargs):
+    """costs[k] = L2CostFunction(sumregs_denoise(data, parameters[k]), true) -- the reference's generate_cost with
+    denoise_function = sumregs_denoise (src/BPLDenoising.jl:92-111, src/SumRegsLearningFunction.jl:38-85): all K
+    triples (K, 3) or blocks (K, 3, n, m) as ONE batch of K*O problems (bpltv_sumregs_sweep; over `ngpus` devices the
+    parameters or the images are split as in generate_scalar_tv_cost).  Saved as <dataset>_sumregs_cost.npz."""
+    from .learning_function import generate_cost, sumregs_denoise
+    _use(ngpus, devices)
+    full = _full(dataset_name)
+    true_, data = _dataset(dataset_name, num_samples, datasets_root, npz)
+    parameters = np.asarray(parameters, dtype=np.float64)
+    costs = np.asarray(generate_cost((true_, data), parameters, denoise_function=sumregs_denoise, **solver_kwargs))
+    out = os.path.join(out_root or default_save_prefix, full)
+    os.makedirs(out, exist_ok=True)
+    np.savez(os.path.join(out, full + "_sumregs_cost.npz"), parameters=parameters, costs=costs)
+    return costs
+
+
 def validate_tv_parameter(parameter, dataset_name="cameraman_128_5", datasets_root=None, npz=None, out_root=None,
                           denoise_function=None, ngpus=None, devices=None, **solver_kwargs):
     """TVDenoise of the whole validation set with a learned parameter; cost + quality table + PNGs

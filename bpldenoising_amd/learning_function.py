@@ -251,6 +251,25 @@ class TVSolver:
                                           _ptr(u) if fetch_u else None))
         return (costs, u) if fetch_u else costs
 
+    def sumregs_sweep(self, alphas, fetch_u=False, **kw):
+        """costs[k] = 0.5*||sumregs_denoise(f, alphas[k]) - ubar||^2 for K parameter triples in one batched solve
+        (generate_cost with denoise_function = sumregs_denoise: the reference's src/BPLDenoising.jl:92-158 and
+        src/SumRegsLearningFunction.jl:38-85).  alphas: (K, 3) vectors or (K, 3, n, m) patch / map blocks
+        (the layout of sumregs_evaluate per block)."""
+        a = np.ascontiguousarray(alphas, dtype=np.float64)
+        if a.ndim == 2 and a.shape[1] == 3:
+            K, am, an = a.shape[0], 1, 1
+        elif a.ndim == 4 and a.shape[1] == 3:
+            K, _, an, am = a.shape
+        else:
+            raise ValueError("alphas must have shape (K, 3) or (K, 3, n, m), got %s" % (a.shape,))
+        p = self.params(_sumregs=True, **kw)
+        costs = np.empty(K)
+        u = np.empty((K, self.O, self.N, self.M)) if fetch_u else None
+        self._check(self._lib.bpltv_sumregs_sweep(self._h, _ptr(a), K, am, an, C.byref(p), _ptr(costs),
+                                                  _ptr(u) if fetch_u else None))
+        return (costs, u) if fetch_u else costs
+
     def per_image(self):
         """(O, 1 + am*an) rows [cost_k, grad_k...] of the last evaluate (scalar / patch parameter): the totals
         are these rows added in image order."""
@@ -404,13 +423,21 @@ def TVDenoise(data, parameter, **kwargs):
     return denoise(data, parameter, FwdGradientOp(), **kwargs)
 
 
-def generate_cost(data, parameters, **kwargs):
+def generate_cost(data, parameters, denoise_function=None, **kwargs):
     """cost curve over a parameter range -- /root/reference/src/BPLDenoising.jl:92-111
-    (`generate_cost`: loop of TVDenoise + L2CostFunction, maxiter = 10000), as ONE batched solve.
-    data = (ubar, f); parameters: (K,) scalars or (K, n, m) matrices (generate_2d_cost: (K, 1, 2))."""
-    kwargs.setdefault("maxiter", 10000)
-    s = _solver_for(data[0], data[1])
-    return s.sweep(parameters, **kwargs)
+    (`generate_cost`: loop of denoise_function + L2CostFunction), as ONE batched solve.
+    data = (ubar, f).  denoise_function None / TVDenoise (maxiter = 10000): parameters (K,) scalars or (K, n, m)
+    matrices (generate_2d_cost: (K, 1, 2)).  denoise_function = sumregs_denoise (maxiter = 5000, as sumregs_denoise):
+    parameters (K, 3) triples or (K, 3, n, m) blocks."""
+    if denoise_function is None or denoise_function is TVDenoise:
+        kwargs.setdefault("maxiter", 10000)
+        s = _solver_for(data[0], data[1])
+        return s.sweep(parameters, **kwargs)
+    if denoise_function is sumregs_denoise:
+        s = _solver_for(data[0], data[1])
+        return s.sumregs_sweep(parameters, **kwargs)
+    raise TypeError("generate_cost: denoise_function must be TVDenoise or sumregs_denoise (the batched sweeps), got %r"
+                    % (denoise_function,))
 
 
 def L2CostFunction(u, true_):

@@ -150,9 +150,10 @@ typedef struct bpltv_stats {
     int ncu;                   /* compute units of the device (hipDeviceProp_t.multiProcessorCount): what bench.py prices
                                   the VALU issue floor against                                                   */
     int launch_chains;         /* independent launch chains (image groups replayed concurrently) of the last solve */
-    int sweep_shards;          /* last bpltv_sweep of a multi handle: devices the K parameter blocks were split over
+    int sweep_shards;          /* last (sumregs_)sweep of a multi handle: devices the K parameter blocks were split over
                                   (replica mode), 0 = the images were split / single device                        */
-    int reserved_i;
+    int sweep_groups;          /* last bpltv_sumregs_sweep: groups of parameter blocks it ran in (1 = all K at once; more
+                                  beyond 65535 problems or when the state does not fit, option "sr_sweep_budget_mb") */
     double launch_host_ms[2];  /* host time the last solve's hipGraphLaunch calls took: chain 0 (calling thread) and
                                   chain 1 (launcher thread); 0 when the solve had one chain or ran without graphs    */
 } bpltv_stats_t;
@@ -285,6 +286,20 @@ int bpltv_gradient(bpltv_t *h, const double *u, const double *ubar, const double
 int bpltv_sweep(bpltv_t *h, const double *alphas, int K, int am, int an, const bpltv_params *p,
                 double *cost_out, double *u_out);
 
+/* The same sweep for the sum-of-regularisers model: generate_cost / generate_2d_cost (src/BPLDenoising.jl:92-158) with
+ * denoise_function = sumregs_denoise (src/SumRegsLearningFunction.jl:38-85).  alphas: K blocks of 3*am*an doubles, each
+ * in the layout bpltv_sumregs_evaluate takes; p = NULL: bpltv_sumregs_default_params.  cost_out: K doubles; u_out: NULL
+ * or K*M*N*O doubles (parameter-major).  Every entry must be finite and >= 0, and > 0 when p->rho != 0; a rejected call
+ * returns BPLTV_E_ARG and leaves the handle as it was.  check_every / gap_tol are ignored (maxiter iterations, as in
+ * bpltv_sweep).  The K*O problems run in groups of whole parameter blocks: at most 65535 problems per group (a grid
+ * dimension) and what fits in HBM (14 planes of M*N doubles per problem; option "sr_sweep_budget_mb"), with bitwise the
+ * same result for any grouping (stats.sweep_groups).  The last solve's result (bpltv_u_device, bpltv_duality_gap) stays
+ * that of the last denoise / evaluate.  Multi-device handles split the images or the parameter blocks as bpltv_sweep does;
+ * the parameter split is bitwise a single handle's result, the image split adds per-shard partial costs on the host and
+ * agrees to rounding. */
+int bpltv_sumregs_sweep(bpltv_t *h, const double *alphas, int K, int am, int an, const bpltv_params *p,
+                        double *cost_out, double *u_out);
+
 /* Handle options: aids for tests and measurements, none of them changes a result or is needed for the reference's
  * behaviour (the reference has no counterpart; its sparse `\` at src/TVLearningFunctionVec.jl:131,248 has no knobs).
  * They replace the environment variables earlier versions read on the product path.  Unknown names: BPLTV_E_ARG.
@@ -304,7 +319,10 @@ int bpltv_sweep(bpltv_t *h, const double *alphas, int K, int am, int an, const b
  *                        rocprofv3 run needs), 2 stream memory operations (BPLTV_E_HIP when the device has none)
  *   "hb_single_stream"   1: that solver's three streams folded into one (rocprofv3 --pmc)
  *   "hb_rw"              32 | 128: rows per workgroup of its substitutions (0 = by size)
- *   "sweep_split"        multi-device handles, bpltv_sweep: 0 automatic, 1 split the images, 2 split the parameter blocks
+ *   "sr_sweep_budget_mb" > 0: HBM (MB) the state of bpltv_sumregs_sweep may take -- forces groups of parameter blocks
+ *                        (stats.sweep_groups; bitwise the same result); 0 = what is free minus a 2 GB reserve
+ *   "sweep_split"        multi-device handles, bpltv_sweep / bpltv_sumregs_sweep: 0 automatic, 1 split the images, 2 split
+ *                        the parameter blocks
  * Multi-device handles pass the other options to every shard (and sweep replica). */
 int bpltv_set_option(bpltv_t *h, const char *name, double value);
 

@@ -166,6 +166,27 @@ function generate_cost_sweep(data, parameters; maxiter = 10000)
     return costs
 end
 
+# generate_cost with denoise_function = sumregs_denoise (src/BPLDenoising.jl:92-111, src/SumRegsLearningFunction.jl:38-85):
+# K weight triples (a 3 x K matrix) or K m x n x 3 parameter arrays (an m x n x 3 x K array; block k is x_k's column-major
+# memory, as sumregs_learning_function passes it) as ONE bpltv_sumregs_sweep call, maxiter = 5000 as sumregs_denoise.
+# Over several GPUs the images or the parameter blocks are split as in generate_cost_sweep.
+function generate_sumregs_cost_sweep(data, parameters; maxiter = 5000)
+    ū, f = data[1], data[2]
+    h = handle_for(ū, f)
+    a = Array{Float64}(parameters)
+    am, an, K = ndims(a) == 2 ? (1, 1, size(a, 2)) : (size(a, 1), size(a, 2), size(a, 4))
+    costs = zeros(K)
+    r = Ref{BpltvParams}()
+    ccall((:bpltv_sumregs_default_params, libbpltv), Cint, (Ref{BpltvParams},), r)
+    d = r[]
+    p = Ref(BpltvParams(d.rho, d.tau0, d.sigma0, d.accel, maxiter, d.delta_t, d.check_every, d.gap_tol, d.tile_iters,
+                        d.use_graph, d.kappa_cap, d.refine, BPLTV_DETERMINISTIC, d.reserved, BPLTV_INIT, BPLTV_ORDER, BPLTV_OPNORM))
+    GC.@preserve a costs bpltv_check(h, ccall((:bpltv_sumregs_sweep, libbpltv), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Cint, Ref{BpltvParams}, Ptr{Cdouble}, Ptr{Cdouble}),
+        h.ptr, a, K, am, an, p, costs, C_NULL))
+    return costs
+end
+
 # test / measurement aids of a handle (include/bpltv.h, bpltv_set_option), e.g. set_option(h, "sweep_split", 2)
 set_option(h::BpltvHandle, name::String, value::Real) =
     bpltv_check(h, ccall((:bpltv_set_option, libbpltv), Cint, (Ptr{Cvoid}, Cstring, Cdouble), h.ptr, name, value))
