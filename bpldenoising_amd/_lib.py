@@ -86,6 +86,9 @@ SYMBOLS = {
     "bpltv_grad_fwd": (C.c_int, [_H, _dp, _dp, _dp]),
     "bpltv_grad_fwd_adjoint": (C.c_int, [_H, _dp, _dp, _dp]),
     "bpltv_gradient": (C.c_int, [_H, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp]),
+    "bpltv_vjp": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
+    "bpltv_vjp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_void_p, C.c_void_p,
+                                   C.c_void_p]),
     "bpltv_sweep": (C.c_int, [_H, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp]),
     "bpltv_sumregs_sweep": (C.c_int, [_H, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp]),
     "bpltv_per_image": (C.c_int, [_H, _dp]),

@@ -29,11 +29,13 @@ constexpr double ADJ_ACT_TOL = 1e-12;  // TVLearningFunctionVec.jl:109,231
 constexpr double ADJ_GAMMA = 1e8;      // TVLearningFunctionVec.jl:142,197
 
 // Per-pixel coefficients (xi, Den, prodesc, active/inactive masks of the reference, fused).
-__global__ __launch_bounds__(256) void adj_setup_kernel(const double* __restrict__ u,
-                                                        const double* __restrict__ ubar,
-                                                        const double* __restrict__ alpha, int am, int an,
-                                                        int M, int N, int O, int patch, int reg,
-                                                        double kappa_act, AdjCoef C) {
+// COT = false: right-hand side of the loss 0.5||u - ubar||^2 (src = ubar); COT = true: of a vector-Jacobian
+// product with the cotangent gu = dL/du (src = gu), which takes the place of u - ubar.  The coefficient planes do
+// not depend on COT.
+template <bool COT>
+__device__ __forceinline__ void adj_setup_body(const double* __restrict__ u, const double* __restrict__ src,
+                                               const double* __restrict__ alpha, int am, int an, int M, int N,
+                                               int O, int patch, int reg, double kappa_act, AdjCoef C) {
     const size_t npx = (size_t)M * N;
     const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (q >= npx * O) return;
@@ -53,7 +55,7 @@ __global__ __launch_bounds__(256) void adj_setup_kernel(const double* __restrict
             c = a / ng;
             h1 = g1 / ng; h2 = g2 / ng;
         }
-        rhs = uk - ubar[q];
+        rhs = COT ? src[q] : uk - src[q];
     } else {
         if (ng > 1.0 / ADJ_GAMMA) {
             t1 = -g2 / ng; t2 = g1 / ng;
@@ -63,7 +65,7 @@ __global__ __launch_bounds__(256) void adj_setup_kernel(const double* __restrict
             kap = patch ? ADJ_GAMMA : a * ADJ_GAMMA;
             h1 = ADJ_GAMMA * g1; h2 = ADJ_GAMMA * g2;
         }
-        rhs = ubar[q] - uk;
+        rhs = COT ? -src[q] : src[q] - uk;   // ubar - u == -(u - ubar) exactly
         if (patch) {
             s = sqrt(a);
             rhs = rhs / s;
@@ -71,6 +73,24 @@ __global__ __launch_bounds__(256) void adj_setup_kernel(const double* __restrict
     }
     C.t1[q] = t1; C.t2[q] = t2; C.c[q] = c; C.kap[q] = kap; C.h1[q] = h1; C.h2[q] = h2;
     C.rhs[q] = rhs; C.s[q] = s;
+}
+
+__global__ __launch_bounds__(256) void adj_setup_kernel(const double* __restrict__ u,
+                                                        const double* __restrict__ ubar,
+                                                        const double* __restrict__ alpha, int am, int an,
+                                                        int M, int N, int O, int patch, int reg,
+                                                        double kappa_act, AdjCoef C) {
+    adj_setup_body<false>(u, ubar, alpha, am, an, M, N, O, patch, reg, kappa_act, C);
+}
+
+// The same coefficients with the right-hand side of a vector-Jacobian product: gu, or -gu (/ s for an array
+// parameter) for gradient_reg.
+__global__ __launch_bounds__(256) void adj_setup_cot_kernel(const double* __restrict__ u,
+                                                            const double* __restrict__ gu,
+                                                            const double* __restrict__ alpha, int am, int an,
+                                                            int M, int N, int O, int patch, int reg,
+                                                            double kappa_act, AdjCoef C) {
+    adj_setup_body<true>(u, gu, alpha, am, an, M, N, O, patch, reg, kappa_act, C);
 }
 
 // Element (pixel a) contribution to the node pairs of {a, b=a+1, c=a+M}.
@@ -775,6 +795,26 @@ __global__ __launch_bounds__(256) void adj_gradpix_kernel(AdjCoef C, const doubl
         const double b = (j < N - 1) ? C.h2[q] : 0.0, bm = (j > 0) ? C.h2[q - M] : 0.0;
         gpix[q] = pk * ((am_ - a) + (bm - b));
     }
+}
+
+// Input gradient of a vector-Jacobian product: the physical adjoint state S q (s = 1 unless reg with an array
+// parameter), negated for gradient_reg, whose right-hand side was -gu.  The same product as oracle/bpltv_oracle.c's
+// p[k] *= s[k] and adj_gradpix_kernel's pk.
+__global__ __launch_bounds__(256) void adj_gradf_kernel(const double* __restrict__ s, const double* __restrict__ p,
+                                                        size_t n, int reg, double* __restrict__ grad_f) {
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    const double v = s[q] * p[q];
+    grad_f[q] = reg ? -v : v;
+}
+
+// Finiteness of a caller's array in HBM (a cotangent): *bad |= 1 if any entry is NaN or infinite.
+__global__ __launch_bounds__(256) void finite_check_kernel(const double* __restrict__ a, size_t n,
+                                                           unsigned long long* __restrict__ bad) {
+    int b = 0;
+    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256)
+        if (!(__builtin_fabs(a[e]) < __builtin_huge_val())) b = 1;
+    if (__any(b) && (threadIdx.x & 63) == 0) atomicOr(bad, 1ull);
 }
 
 // calc_adjoint(PatchOp, .): partial[(pa + am*pb)*O + k] = sum of image k's pixel contributions over

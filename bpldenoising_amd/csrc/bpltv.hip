@@ -351,7 +351,10 @@ struct bpltv_handle {
     double *d_p = nullptr, *d_r = nullptr, *d_gpix = nullptr;
     double* d_resn = nullptr;
     int* d_fail = nullptr;
-    double *d_u2 = nullptr, *d_ubar2 = nullptr;  // staging for bpltv_gradient
+    double *d_u2 = nullptr, *d_ubar2 = nullptr;  // staging for bpltv_gradient (bpltv_vjp: u and the cotangent)
+    double* d_gf2 = nullptr;                      // staging of bpltv_vjp's input gradient
+    double* d_vjp = nullptr;                      // bpltv_vjp(_device): [4 check words | parameter | parameter gradient]
+    size_t vjp_cap = 0;
     // sum-of-regularisers model (sumregs_kernels.hpp): state and adjoint workspace, allocated on first use
     double* d_sr[2][7] = {{nullptr}, {nullptr}};   // x, yf1, yf2, yb1, yb2, yc1, yc2; two sets (ping-pong)
     // current solve context of run_sr_pdhg: default = the O dataset images in d_sr with the parameters in d_alpha;
@@ -1297,20 +1300,40 @@ void solve_band_lds(bpltv_t* h, double* vec, double* accv) {
     }
 }
 
-// Adjoint gradient of the images (d_u, d_ubar) on the device; result (am*an doubles) -> d_out.
+// What one adjoint solve reads and writes besides u: the parameter (device, am*an doubles, its smallest entry checked
+// on the host or by alpha_check_kernel), the source of the right-hand side -- ubar of the loss 0.5||u - ubar||^2, or
+// the cotangent gu of a vector-Jacobian product -- and the outputs.  The resident parameter of the last solve
+// (d_alpha, last_am / last_an, alpha_min) is read only by the callers that pass it (gradient_ctx).
+struct GradCtx {
+    const double* alpha = nullptr;
+    int am = 1, an = 1;
+    double alpha_min = 0.0;
+    const double* src = nullptr;   // ubar, or gu when cot
+    bool cot = false;
+    double* d_out = nullptr;       // am*an parameter gradient, or nullptr: no per-pixel terms, no reduction
+    double* d_grad_f = nullptr;    // M*N*O input gradient (+-S q), or nullptr
+};
+GradCtx gradient_ctx(const bpltv_t* h, const double* d_ubar, double* d_out) {
+    GradCtx g;
+    g.alpha = h->d_alpha; g.am = h->last_am; g.an = h->last_an; g.alpha_min = h->alpha_min;
+    g.src = d_ubar; g.d_out = d_out;
+    return g;
+}
+
+// Adjoint gradient of the images d_u on the device; parameter, right-hand side and outputs from `g`.
 // The images are processed in groups of at most Oc (adj_choose): coefficients, assembly, factorisation, solve and
 // refinement of a group use the factor workspace of the previous one; the per-pixel gradients of all images are
 // summed at the end, per image and in image order, so the result does not depend on the grouping (bitwise).
 // Reference: the per-image loop of /root/reference/src/TVLearningFunctionVec.jl:76-81,168-173 -- sequential, no limit.
-int run_gradient_once(bpltv_t* h, const double* d_u, const double* d_ubar, int reg, const bpltv_params& p,
-                      double* d_out, double kappa_scale) {
+int run_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, const bpltv_params& p,
+                      double kappa_scale) {
     int rc = adj_alloc(h);
     if (rc) return rc;
     AdjMethod method;
     int Oc = h->O;
     rc = adj_choose(h, p, &method, &Oc);
     if (rc) return rc;
-    const int M = h->M, N = h->N, O = h->O, am = h->last_am, an = h->last_an;
+    const int M = h->M, N = h->N, O = h->O, am = g.am, an = g.an;
     const size_t tot = h->tot, npx = h->npx;
     const int patch = !(am == 1 && an == 1);
     const double eps = 2.220446049250313e-16;
@@ -1342,8 +1365,12 @@ int run_gradient_once(bpltv_t* h, const double* d_u, const double* d_ubar, int r
         double *dp = h->d_p + o0, *dr = h->d_r + o0, *dg = h->d_gpix + o0;
         int* dfail = h->d_fail + c0;
         const int gpx = (int)((ctot + 255) / 256);
-        hipLaunchKernelGGL(adj_setup_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, d_ubar + o0, h->d_alpha, am, an, M, N,
-                           nimg, patch, reg, kact, C);
+        if (g.cot)
+            hipLaunchKernelGGL(adj_setup_cot_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0, g.alpha, am, an, M,
+                               N, nimg, patch, reg, kact, C);
+        else
+            hipLaunchKernelGGL(adj_setup_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0, g.alpha, am, an, M, N,
+                               nimg, patch, reg, kact, C);
         hipLaunchKernelGGL(adj_assemble_kernel, dim3(gpx), dim3(256), 0, h->stream, C, M, N, nimg, band4);
         // factorisation
         const BcrArrays bcr = BcrArrays::carve(h->d_bcr, M, N, nimg, h->bcr_MP);
@@ -1384,21 +1411,27 @@ int run_gradient_once(bpltv_t* h, const double* d_u, const double* d_ubar, int r
         hipLaunchKernelGGL(adj_resnorm_final_kernel, dim3((4 * nimg + 63) / 64), dim3(64), 0, h->stream, resn_part, nimg,
                            h->d_resn + 4 * (size_t)c0);
         // gradient per pixel
-        hipLaunchKernelGGL(adj_gradpix_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, patch, reg, dg);
+        if (g.d_out)
+            hipLaunchKernelGGL(adj_gradpix_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, patch, reg, dg);
         HIPCHK(h, hipGetLastError());
     }
-    // ... then per parameter, over all images
-    if (am == M && an == N && !(M == 1 && N == 1)) {  // pixelwise parameter map: plain sum over images
+    // ... then per parameter, over all images (a vector-Jacobian product may not want the parameter gradient)
+    const bool amap = am == M && an == N && !(M == 1 && N == 1);
+    if (g.d_out && amap) {  // pixelwise parameter map: plain sum over images
         hipLaunchKernelGGL(map_sum_kernel, dim3((unsigned)((h->npx + 255) / 256)), dim3(256), 0, h->stream, h->d_gpix, h->npx, O,
-                           d_out);
-    } else {
+                           g.d_out);
+    } else if (g.d_out) {
         rc = ensure(h, &h->d_red, &h->red_cap, (size_t)am * an * O);
         if (rc) return rc;
         hipLaunchKernelGGL(patch_sum_kernel, dim3(am * an, O), dim3(256), 0, h->stream, h->d_gpix, M, N, O, am, an,
                            h->d_red);
-        hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, O, am * an, 1.0, d_out,
+        hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, O, am * an, 1.0, g.d_out,
                            (double*)nullptr);
     }
+    // input gradient of a vector-Jacobian product: d_p and the s plane cover the whole batch after the group loop
+    if (g.d_grad_f)
+        hipLaunchKernelGGL(adj_gradf_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->d_coef + 6 * tot, h->d_p,
+                           tot, reg, g.d_grad_f);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
     std::vector<int> fail(O);
@@ -1436,16 +1469,15 @@ int run_gradient_once(bpltv_t* h, const double* d_u, const double* d_ubar, int r
 // The reduced system is SPD, but its active-set weight (up to 1e14) sits 14 digits above the O(1)
 // terms; should rounding ever produce a non-positive pivot, retry with a 100x smaller weight
 // (1e12 still reproduces the hard-constraint limit to ~1e-5).
-int run_gradient(bpltv_t* h, const double* d_u, const double* d_ubar, int reg, const bpltv_params& p,
-                 double* d_out) {
-    const bool patch = !(h->last_am == 1 && h->last_an == 1);
-    if (reg && patch && !(h->alpha_min > 0.0))
-        return set_err(h, BPLTV_E_ARG, "gradient_reg with a patch / pixel-map parameter symmetrises with sqrt(alpha): every entry must be > 0 (min = %g)", h->alpha_min);
+int run_gradient(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, const bpltv_params& p) {
+    const bool patch = !(g.am == 1 && g.an == 1);
+    if (reg && patch && !(g.alpha_min > 0.0))
+        return set_err(h, BPLTV_E_ARG, "gradient_reg with a patch / pixel-map parameter symmetrises with sqrt(alpha): every entry must be > 0 (min = %g)", g.alpha_min);
     double scale = 1.0;
     int rc = BPLTV_OK;
     h->st.adjoint_attempts = 0;
     for (int attempt = 0; attempt < 3; ++attempt, scale *= 1e-2) {
-        rc = run_gradient_once(h, d_u, d_ubar, reg, p, d_out, scale);
+        rc = run_gradient_once(h, d_u, g, reg, p, scale);
         h->st.adjoint_attempts = attempt + 1;
         if (rc != BPLTV_E_NUMERIC) break;
         if (reg) break;   // gradient_reg has no active-set weight to reduce
@@ -1503,7 +1535,7 @@ int evaluate_common(bpltv_t* h, const double* alpha, int am, int an, double delt
     if (rc) return rc;
     HIPCHK(h, hipEventRecord(h->ev[5], h->stream));
     const int reg = !(delta > p.delta_t);  // TVLearningFunctionVec.jl:21-25
-    rc = run_gradient(h, d_u, h->d_ubar, reg, p, h->d_partial + 1);
+    rc = run_gradient(h, d_u, gradient_ctx(h, h->d_ubar, h->d_partial + 1), reg, p);
     if (rc) return rc;
     const size_t np = 1 + (size_t)am * an;
     if (d_partial_user)
@@ -1521,6 +1553,57 @@ int evaluate_common(bpltv_t* h, const double* alpha, int am, int an, double delt
     return BPLTV_OK;
 }
 
+
+// Vector-Jacobian product of u = denoise(f, alpha) on a single-device handle: d_u, d_gu and the outputs live in HBM
+// (the host form stages them), `alpha` on the host or (alpha_dev) in HBM.  Parameter and cotangent are checked before
+// anything of the handle changes; the parameter is then staged in d_vjp, so that the last solve -- d_alpha with its
+// shape and minimum, the PDHG state and graphs, and so bpltv_u_device and bpltv_duality_gap -- stays as it was.
+// d_grad_alpha: am*an doubles in HBM or nullptr; d_grad_f: M*N*O doubles in HBM or nullptr; not both nullptr.
+int vjp_common(bpltv_t* h, const double* d_u, const double* alpha, bool alpha_dev, int am, int an, int reg,
+               const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alpha) {
+    if (!d_u || !alpha || !d_gu) return set_err(h, BPLTV_E_ARG, "vjp: null pointer");
+    if (!d_grad_f && !d_grad_alpha) return set_err(h, BPLTV_E_ARG, "vjp: both outputs are NULL");
+    if (am < 1 || an < 1 || am > h->M || an > h->N)
+        return set_err(h, BPLTV_E_ARG, "vjp: parameter shape %dx%d (image %dx%d)", am, an, h->M, h->N);
+    bpltv_params p = resolve(pp);
+    if (int prc = check_params(h, p)) return prc;
+    const size_t P = (size_t)am * an;
+    double amin = 0.0;
+    if (!alpha_dev) {   // as upload_alpha
+        amin = alpha[0];
+        for (size_t e = 0; e < P; ++e) {
+            if (!std::isfinite(alpha[e]) || alpha[e] < 0.0)
+                return set_err(h, BPLTV_E_ARG, "vjp: alpha[%zu] = %g: parameters must be finite and >= 0", e, alpha[e]);
+            if (alpha[e] < amin) amin = alpha[e];
+        }
+    }
+    int rc = ensure(h, &h->d_vjp, &h->vjp_cap, 4 + 2 * P);
+    if (rc) return rc;
+    // check words: [0] smallest parameter entry (bits), [1] parameter rejected, [2] cotangent not finite
+    unsigned long long* chk_d = reinterpret_cast<unsigned long long*>(h->d_vjp);
+    HIPCHK(h, hipMemsetAsync(chk_d, 0xFF, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(chk_d + 1, 0, 2 * sizeof(unsigned long long), h->stream));
+    if (alpha_dev)
+        hipLaunchKernelGGL(alpha_check_kernel, dim3((unsigned)std::min<size_t>((P + 255) / 256, 1024)), dim3(256), 0, h->stream, alpha, P,
+                           chk_d);
+    hipLaunchKernelGGL(finite_check_kernel, dim3((unsigned)std::min<size_t>((h->tot + 255) / 256, 1024)), dim3(256), 0, h->stream, d_gu,
+                       h->tot, chk_d + 2);
+    HIPCHK(h, hipGetLastError());
+    unsigned long long chk_h[3] = {0, 0, 0};
+    HIPCHK(h, hipMemcpyAsync(chk_h, chk_d, sizeof(chk_h), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (chk_h[1] != 0) return set_err(h, BPLTV_E_ARG, "vjp: alpha (device array): parameters must be finite and >= 0");
+    if (chk_h[2] != 0) return set_err(h, BPLTV_E_ARG, "vjp: the cotangent gu must be finite");
+    if (alpha_dev) std::memcpy(&amin, chk_h, sizeof(double));
+    double* d_a = h->d_vjp + 4;
+    HIPCHK(h, hipMemcpyAsync(d_a, alpha, P * sizeof(double), alpha_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    GradCtx g;
+    g.alpha = d_a; g.am = am; g.an = an; g.alpha_min = amin;
+    g.src = d_gu; g.cot = true;
+    g.d_out = d_grad_alpha; g.d_grad_f = d_grad_f;
+    h->has_per_image = false;   // the reduction scratch (d_red) no longer holds the last evaluate's rows
+    return run_gradient(h, d_u, g, reg ? 1 : 0, p);
+}
 
 // ============================================================================================
 // Sum-of-regularisers model (sumregs_kernels.hpp; /root/reference/src/SumRegsLearningFunction.jl)
@@ -2382,6 +2465,34 @@ int multi_gradient(bpltv_t* h, const double* u, const double* ubar, const double
     return multi_stats(h);
 }
 
+// bpltv_vjp over the shards: images split as for the gradient, input-gradient slices written in place, the parameter
+// gradients of the shards added in shard order.
+int multi_vjp(bpltv_t* h, const double* u, const double* alpha, int am, int an, int reg, const bpltv_params* pp,
+              const double* gu, double* grad_f_out, double* grad_alpha_out) {
+    if (!u || !gu || !alpha || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "vjp: null pointer or empty shape");
+    if (!grad_f_out && !grad_alpha_out) return set_err(h, BPLTV_E_ARG, "vjp: both outputs are NULL");
+    WallTimer wt;
+    MultiState& ms = *h->multi;
+    const int n = (int)ms.shard.size();
+    const size_t npx = h->npx, P = (size_t)am * an;
+    std::vector<double> g((size_t)n * P);
+    int rc = multi_run(h, [&](int k, bpltv_t* c) {
+        const size_t o0 = ms.lo[k] * npx;
+        return bpltv_vjp(c, u + o0, alpha, am, an, reg, pp, gu + o0, grad_f_out ? grad_f_out + o0 : nullptr,
+                         grad_alpha_out ? g.data() + (size_t)k * P : nullptr);
+    });
+    if (rc) return rc;
+    if (grad_alpha_out)
+        for (size_t e = 0; e < P; ++e) {
+            double acc = g[e];
+            for (int k = 1; k < n; ++k) acc += g[(size_t)k * P + e];
+            grad_alpha_out[e] = acc;
+        }
+    h->has_per_image = false;
+    h->st.total_ms = wt.ms();
+    return multi_stats(h);
+}
+
 // slices: 1 TV (bpltv_sweep), 3 sum of regularisers (bpltv_sumregs_sweep; 3*am*an doubles per parameter block)
 int multi_sweep(bpltv_t* h, const double* alphas, int K, int am, int an, const bpltv_params* pp, double* cost_out,
                 double* u_out, int slices = 1) {
@@ -2581,7 +2692,8 @@ int bpltv_destroy(bpltv_t* h) {
     if (h->f32_f) (void)hipFree(h->f32_f);
     if (h->f32_alpha) (void)hipFree(h->f32_alpha);
     void* ptrs[] = {h->d_ubar, h->d_f, h->d_alpha, h->d_partial, h->d_red, h->d_perimg, h->d_scalar, h->d_coef,
-                    h->d_band4, h->d_bcr, h->d_L, h->d_invF, h->d_invB, h->d_L1, h->d_dump, h->d_Lm, h->d_spill, h->d_p, h->d_r, h->d_gpix, h->d_resn, h->d_fail, h->d_u2, h->d_ubar2};
+                    h->d_band4, h->d_bcr, h->d_L, h->d_invF, h->d_invB, h->d_L1, h->d_dump, h->d_Lm, h->d_spill, h->d_p, h->d_r, h->d_gpix, h->d_resn, h->d_fail, h->d_u2, h->d_ubar2,
+                    h->d_gf2, h->d_vjp};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (int s = 0; s < 2; ++s)
@@ -2870,11 +2982,60 @@ int bpltv_gradient(bpltv_t* h, const double* u, const double* ubar, const double
     }
     HIPCHK(h, hipMemcpyAsync(h->d_u2, u, h->tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_ubar2, ubar, h->tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    rc = run_gradient(h, h->d_u2, h->d_ubar2, reg ? 1 : 0, p, h->d_partial + 1);
+    rc = run_gradient(h, h->d_u2, gradient_ctx(h, h->d_ubar2, h->d_partial + 1), reg ? 1 : 0, p);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(grad_out, h->d_partial + 1, sizeof(double) * (size_t)am * an, hipMemcpyDeviceToHost,
                              h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
+int bpltv_vjp(bpltv_t* h, const double* u, const double* alpha, int am, int an, int reg, const bpltv_params* pp,
+              const double* gu, double* grad_f_out, double* grad_alpha_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi) return multi_vjp(h, u, alpha, am, an, reg, pp, gu, grad_f_out, grad_alpha_out);
+    if (!u || !gu || !alpha) return set_err(h, BPLTV_E_ARG, "vjp: null pointer");
+    if (!grad_f_out && !grad_alpha_out) return set_err(h, BPLTV_E_ARG, "vjp: both outputs are NULL");
+    if (am < 1 || an < 1 || am > h->M || an > h->N)
+        return set_err(h, BPLTV_E_ARG, "vjp: parameter shape %dx%d (image %dx%d)", am, an, h->M, h->N);
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->d_u2) {
+        HIPCHK(h, hipMalloc((void**)&h->d_u2, h->tot * sizeof(double)));
+        HIPCHK(h, hipMalloc((void**)&h->d_ubar2, h->tot * sizeof(double)));
+    }
+    if (grad_f_out && !h->d_gf2) HIPCHK(h, hipMalloc((void**)&h->d_gf2, h->tot * sizeof(double)));
+    HIPCHK(h, hipMemcpyAsync(h->d_u2, u, h->tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_ubar2, gu, h->tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    int rc = ensure(h, &h->d_vjp, &h->vjp_cap, 4 + 2 * (size_t)am * an);
+    if (rc) return rc;
+    double* d_ga = grad_alpha_out ? h->d_vjp + 4 + (size_t)am * an : nullptr;
+    rc = vjp_common(h, h->d_u2, alpha, false, am, an, reg, pp, h->d_ubar2, grad_f_out ? h->d_gf2 : nullptr, d_ga);
+    if (rc) return rc;
+    if (grad_f_out)
+        HIPCHK(h, hipMemcpyAsync(grad_f_out, h->d_gf2, h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (grad_alpha_out)
+        HIPCHK(h, hipMemcpyAsync(grad_alpha_out, d_ga, sizeof(double) * (size_t)am * an, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
+int bpltv_vjp_device(bpltv_t* h, const double* d_u, const double* d_alpha, int am, int an, int reg, const bpltv_params* pp,
+                     const double* d_gu, double* d_grad_f, double* d_grad_alpha) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi) {
+        const int rc = multi_unsupported(h, "bpltv_vjp_device");
+        if (rc >= 0) return rc;
+        const int r = bpltv_vjp_device(h->multi->shard[0], d_u, d_alpha, am, an, reg, pp, d_gu, d_grad_f, d_grad_alpha);
+        if (r) h->err = h->multi->shard[0]->err; else { h->has_per_image = false; multi_stats(h); }
+        return r;
+    }
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int rc = vjp_common(h, d_u, d_alpha, true, am, an, reg, pp, d_gu, d_grad_f, d_grad_alpha);
+    if (rc) return rc;
     h->st.total_ms = wt.ms();
     return BPLTV_OK;
 }

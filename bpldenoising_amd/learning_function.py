@@ -233,6 +233,33 @@ class TVSolver:
                                              C.byref(p), _ptr(grad)))
         return float(grad[0]) if scalar else grad.reshape(an, am)
 
+    def vjp(self, u, x, gu, reg=False, want_f=True, want_alpha=True, **kw):
+        """Vector-Jacobian product of u = denoise(f, x) for the cotangent gu = dL/du (bpltv_vjp): (grad_f, grad_x).
+        u, gu: (O, N, M) batches; x: a float or an (n, m) parameter.  grad_f has the shape of u (None unless want_f),
+        grad_x the type / shape of x (None unless want_alpha).  gu = u - ubar gives gradient(u, ubar, x, reg) bitwise."""
+        if not (want_f or want_alpha):
+            raise ValueError("vjp: want_f and want_alpha are both False")
+        a, am, an, scalar = _alpha_arg(x)
+        p = self.params(**kw)
+        u = self._batch(u, "u")
+        gu = self._batch(gu, "gu")
+        gf = np.empty((self.O, self.N, self.M)) if want_f else None
+        ga = np.empty(am * an) if want_alpha else None
+        self._check(self._lib.bpltv_vjp(self._h, _ptr(u), _ptr(a), am, an, int(bool(reg)), C.byref(p), _ptr(gu),
+                                        _ptr(gf) if want_f else None, _ptr(ga) if want_alpha else None))
+        if ga is not None:
+            ga = float(ga[0]) if scalar else ga.reshape(an, am)
+        return gf, ga
+
+    def vjp_device(self, u_ptr, alpha_ptr, am, an, gu_ptr, grad_f_ptr, grad_alpha_ptr, reg=False, **kw):
+        """bpltv_vjp_device: u, gu and grad_f (M*N*O doubles), the parameter and grad_alpha (am*an doubles, column
+        major) all resident in HBM (raw device pointers, e.g. torch tensors' .data_ptr()); either output pointer may
+        be 0 / None, not both."""
+        p = self.params(**kw)
+        self._check(self._lib.bpltv_vjp_device(self._h, C.c_void_p(u_ptr), C.c_void_p(alpha_ptr), int(am), int(an),
+                                               int(bool(reg)), C.byref(p), C.c_void_p(gu_ptr),
+                                               C.c_void_p(grad_f_ptr or None), C.c_void_p(grad_alpha_ptr or None)))
+
     def sweep(self, alphas, fetch_u=False, **kw):
         """costs[k] = 0.5*||denoise(f, alphas[k]) - ubar||^2 for K parameters in one batched solve
         (generate_cost / generate_2d_cost, /root/reference/src/BPLDenoising.jl:92-111,136-158).

@@ -1,0 +1,126 @@
+"""PyTorch autograd layer over the TV denoiser: u = denoise(f, alpha) as a differentiable operation.
+
+    u = tv_denoise(f, alpha, reg=False, maxiter=5000)      # forward: one batched PDHG solve on the GPU
+    loss(u).backward()                                     # backward: one adjoint solve (bpltv_vjp_device)
+
+f is a float64 tensor of shape (B, H, W) or (H, W) on a ROCm device (torch's "cuda" device type); in the library's
+terms O = B, N = H, M = W, the convention of learning_function.py.  alpha is a float64 tensor on the same device: 0-dim
+(scalar), (pH, pW) (patch parameter, pH <= H, pW <= W) or (H, W) (pixel map).  The backward pass is the vector-Jacobian
+product of include/bpltv.h's bpltv_vjp for the cotangent torch hands it: f.grad and alpha.grad for any loss.  `reg`
+selects the reference's gradient_reg linearisation (delta <= delta_t in tv_op_learning_function).  Double backward is
+not supported (once_differentiable).
+
+Streams: the library runs its kernels on its own HIP streams and blocks until they are done.  Every call below first
+synchronises the tensors' current torch stream, so that the library reads inputs torch has finished writing; its
+outputs are complete when the call returns.
+
+This module imports torch; `import bpldenoising_amd` does not import this module.
+"""
+import torch
+from torch.autograd.function import once_differentiable
+
+from .learning_function import TVSolver
+
+_solvers = {}
+
+
+def _solver(index, M, N, O):
+    """One library handle per (device index, M, N, O), kept for the life of the process (clear_solvers frees them)."""
+    key = (index, M, N, O)
+    s = _solvers.get(key)
+    if s is None:
+        s = TVSolver(M, N, O, device=index)
+        _solvers[key] = s
+    return s
+
+
+def clear_solvers():
+    """Free the cached library handles (their HBM)."""
+    for s in _solvers.values():
+        s.close()
+    _solvers.clear()
+
+
+def _check_args(f, alpha):
+    """(O, N, M, am, an) of a valid (f, alpha) pair; TypeError / ValueError before any library call."""
+    if not isinstance(f, torch.Tensor) or not isinstance(alpha, torch.Tensor):
+        raise TypeError("tv_denoise: f and alpha must be torch tensors")
+    if f.dtype != torch.float64 or alpha.dtype != torch.float64:
+        raise TypeError("tv_denoise: f and alpha must be float64 (got %s, %s)" % (f.dtype, alpha.dtype))
+    if f.dim() not in (2, 3) or f.numel() == 0:
+        raise ValueError("tv_denoise: f must have shape (B, H, W) or (H, W), got %s" % (tuple(f.shape),))
+    H, W = f.shape[-2], f.shape[-1]
+    O = f.shape[0] if f.dim() == 3 else 1
+    if alpha.dim() == 0:
+        am = an = 1
+    elif alpha.dim() == 2 and 1 <= alpha.shape[0] <= H and 1 <= alpha.shape[1] <= W:
+        an, am = alpha.shape
+    else:
+        raise ValueError("tv_denoise: alpha must be 0-dim, (pH, pW) with pH <= %d, pW <= %d, or (%d, %d); got %s"
+                         % (H, W, H, W, tuple(alpha.shape)))
+    if alpha.device != f.device:
+        raise ValueError("tv_denoise: alpha is on %s, f on %s" % (alpha.device, f.device))
+    if f.device.type != "cuda":
+        raise ValueError("tv_denoise: f must be on a ROCm device, got %s" % (f.device,))
+    return O, H, W, am, an
+
+
+def _sync(device):
+    torch.cuda.current_stream(device).synchronize()
+
+
+class TVDenoiseFunction(torch.autograd.Function):
+    """autograd.Function of tv_denoise (below); apply(f, alpha, reg, solver_kw)."""
+
+    @staticmethod
+    def forward(ctx, f, alpha, reg, solver_kw):
+        O, N, M, am, an = _check_args(f, alpha)
+        index = f.device.index if f.device.index is not None else torch.cuda.current_device()
+        s = _solver(index, M, N, O)
+        fc = f.detach().contiguous()
+        ac = alpha.detach().contiguous()
+        u = torch.empty_like(fc)
+        _sync(f.device)
+        s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
+        s.denoise_device(ac.data_ptr(), am, an, **solver_kw)
+        s.copy_u_device(u.data_ptr())
+        ctx.save_for_backward(u, ac)
+        ctx.solver, ctx.am, ctx.an, ctx.reg, ctx.solver_kw = s, am, an, bool(reg), dict(solver_kw)
+        return u
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gu):
+        need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_f or need_a):
+            return None, None, None, None
+        u, alpha = ctx.saved_tensors
+        gu = gu.to(dtype=torch.float64).contiguous()
+        gf = torch.empty_like(u) if need_f else None
+        ga = torch.empty(ctx.am * ctx.an, dtype=torch.float64, device=u.device) if need_a else None
+        _sync(u.device)
+        ctx.solver.vjp_device(u.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(),
+                              gf.data_ptr() if need_f else None, ga.data_ptr() if need_a else None,
+                              reg=ctx.reg, **ctx.solver_kw)
+        return gf, (ga.reshape(alpha.shape) if need_a else None), None, None
+
+
+def tv_denoise(f, alpha, *, reg=False, **solver_kw):
+    """u = denoise(f, alpha) (TVSolver.denoise: the reference's denoise, src/TVLearningFunctionVec.jl:45-70),
+    differentiable in f and alpha.  solver_kw: the solver parameters of TVSolver.params (maxiter, ...), used by the
+    forward solve and the adjoint alike."""
+    return TVDenoiseFunction.apply(f, alpha, reg, solver_kw)
+
+
+class TVDenoise(torch.nn.Module):
+    """TV denoising with a learnable parameter: a scalar (alpha = float), a patch parameter or a pixel map
+    (alpha = (pH, pW) / (H, W) array).  Move it to the device of its inputs with .to(device)."""
+
+    def __init__(self, alpha, reg=False, **solver_kw):
+        super().__init__()
+        self.alpha = torch.nn.Parameter(torch.as_tensor(alpha, dtype=torch.float64).clone())
+        self.reg = bool(reg)
+        self.solver_kw = dict(solver_kw)
+
+    def forward(self, f):
+        return tv_denoise(f, self.alpha, reg=self.reg, **self.solver_kw)

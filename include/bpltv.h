@@ -268,6 +268,29 @@ int bpltv_grad_fwd_adjoint(bpltv_t *h, const double *y1, const double *y2, doubl
 int bpltv_gradient(bpltv_t *h, const double *u, const double *ubar, const double *alpha, int am,
                    int an, int reg, const bpltv_params *p, double *grad_out);
 
+/* Vector-Jacobian product of u = denoise(f, alpha) for a cotangent gu = dL/du of any loss L: the adjoint system of
+ * bpltv_gradient with gu in place of u - ubar (reg = 0), or -gu (reg = 1, divided by sqrt(alpha) for an array
+ * parameter), solved once for the adjoint state p.  grad_f_out = p (reg = 0) or -p (reg = 1), p = S q the physical
+ * adjoint state; grad_alpha_out = the parameter gradient of bpltv_gradient computed from the same p.  So gu = u - ubar
+ * gives bitwise the grad_out of bpltv_gradient(u, ubar, ...).  With reg = 1 and an array parameter the reference's
+ * system is not symmetric and its gradient uses M^-1, not M^-T: both outputs follow it.
+ * u, gu, grad_f_out: host, M*N*O doubles; alpha, grad_alpha_out: am*an doubles.  Either output may be NULL, not
+ * both.  The dataset is not used (no set_data needed).  alpha is checked as bpltv_denoise checks it (finite, >= 0;
+ * > 0 for reg = 1 with an array parameter), gu must be finite: a rejected call returns BPLTV_E_ARG and leaves the handle
+ * as it was.  The parameter is staged apart from the last solve's: bpltv_u_device, bpltv_duality_gap and the next
+ * denoise are unchanged by a VJP (bpltv_per_image is not, as after bpltv_gradient).  The residual gate and the
+ * kappa retry apply as in bpltv_gradient; stats report the adjoint (adjoint_ms, adjoint_residual, adjoint_method,
+ * adjoint_chunks, kappa_used, reg_gradient_used).  dtype = 32 handles too (the adjoint is Float64 there as well).
+ * Multi-device handles split the images as bpltv_gradient does: grad_f_out slices are written in place, grad_alpha_out
+ * is the sum of the shards' in shard order. */
+int bpltv_vjp(bpltv_t *h, const double *u, const double *alpha, int am, int an, int reg, const bpltv_params *p,
+              const double *gu, double *grad_f_out, double *grad_alpha_out);
+/* The same with every array in HBM (device pointers; e.g. torch tensors' .data_ptr()); the outputs are written there.
+ * The parameter and the cotangent are checked on the device.  Single-device handles (multi: BPLTV_E_UNSUPPORTED
+ * beyond one shard). */
+int bpltv_vjp_device(bpltv_t *h, const double *d_u, const double *d_alpha, int am, int an, int reg,
+                     const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alpha);
+
 /* Forward-only parameter sweep: generate_cost / generate_2d_cost (src/BPLDenoising.jl:92-111,
  * :136-158) evaluate cost(alpha_k) = 0.5*||TVDenoise(f, alpha_k) - ubar||^2 for a range of parameters,
  * one solve after the other.  Here the K parameter blocks (each am x an, column major, K*am*an

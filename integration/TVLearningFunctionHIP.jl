@@ -4,7 +4,7 @@
 # NOT EXECUTED HERE: Julia is not available in the build image; the same entry points are exercised through
 # bpldenoising_amd/_lib.py (ctypes) by the test suite.
 # Same exports as src/TVLearningFunctionVec.jl:6
-export tv_op_learning_function, denoise, sumregs_learning_function
+export tv_op_learning_function, denoise, sumregs_learning_function, tv_vjp
 
 const libbpltv = "libbpltv"            # on LD_LIBRARY_PATH, or an absolute path
 
@@ -185,6 +185,19 @@ function generate_sumregs_cost_sweep(data, parameters; maxiter = 5000)
         (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Cint, Ref{BpltvParams}, Ptr{Cdouble}, Ptr{Cdouble}),
         h.ptr, a, K, am, an, p, costs, C_NULL))
     return costs
+end
+
+# Vector-Jacobian product of u = denoise(f, α) for a cotangent ḡ = dL/du of any upper-level loss L (include/bpltv.h,
+# bpltv_vjp): (dL/df, dL/dα) from one adjoint solve.  ḡ = u - ū gives tv_op_learning_function's gradient bit for bit;
+# reg = true is its gradient_reg branch (Δ <= Δt).  The dataset is not used: any handle of u's size will do.
+function tv_vjp(h::BpltvHandle, u::Array{Float64,3}, α, ḡ::Array{Float64,3}; reg = false, kwargs...)
+    a, am, an = alpha_arg(α)
+    gf = similar(u); ga = zeros(am, an)
+    p = Ref(default_params(; kwargs...))
+    GC.@preserve u a ḡ gf ga bpltv_check(h, ccall((:bpltv_vjp, libbpltv), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Ref{BpltvParams}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        h.ptr, u, a, am, an, reg ? 1 : 0, p, ḡ, gf, ga))
+    return gf, α isa Real ? ga[1] : reshape(ga, size(α))
 end
 
 # test / measurement aids of a handle (include/bpltv.h, bpltv_set_option), e.g. set_option(h, "sweep_split", 2)
