@@ -556,7 +556,18 @@ void drop_graphs(bpltv_t* h) {
     h->graphs.clear();
 }
 
-int upload_alpha(bpltv_t* h, const double* alpha, int am, int an) {
+int solve_precheck(bpltv_t* h, const bpltv_params& p, double amin, int what);
+// what: PRE_TV or PRE_SR (the model), | PRE_GRADIENT for an evaluate (the adjoint follows the solve), | PRE_REG_ARRAY when
+// that adjoint is gradient_reg with a patch or map parameter
+enum { PRE_TV = 0, PRE_SR = 1, PRE_GRADIENT = 2, PRE_REG_ARRAY = 4 };
+inline int pre_gradient(double delta, const bpltv_params& p, int am, int an) {
+    const int reg = !(delta > p.delta_t);   // as evaluate_common / sr_evaluate_common
+    return PRE_GRADIENT | ((reg && !(am == 1 && an == 1)) ? PRE_REG_ARRAY : 0);
+}
+
+// solve (nullable): the parameters of the PDHG solve the upload is for -- solve_precheck runs on them before anything of
+// the handle changes.
+int upload_alpha(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* solve = nullptr, int what = PRE_TV) {
     if (!alpha || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "alpha: null pointer or empty shape");
     if (am > h->M || an > h->N)
         return set_err(h, BPLTV_E_ARG, "alpha shape %dx%d exceeds image %dx%d", am, an, h->M, h->N);
@@ -569,6 +580,8 @@ int upload_alpha(bpltv_t* h, const double* alpha, int am, int an) {
             return set_err(h, BPLTV_E_ARG, "alpha[%zu] = %g: parameters must be finite and >= 0", e, alpha[e]);
         if (alpha[e] < amin) amin = alpha[e];
     }
+    if (solve)
+        if (int rc = solve_precheck(h, *solve, amin, what)) return rc;
     h->alpha_min = amin;
     if (h->alpha_cap < need) {
         drop_graphs(h);  // captured kernels hold the old pointer
@@ -589,7 +602,7 @@ int upload_alpha(bpltv_t* h, const double* alpha, int am, int an) {
 // The same for a parameter that already lives in HBM (bpltv_denoise_device): checked in place by alpha_check_kernel (one
 // 16-byte read back), then copied device to device.  Nothing of the handle changes before the array is accepted: a
 // rejected parameter leaves d_alpha, its shape and alpha_min -- and so the duality gap of the last solve -- as they were.
-int upload_alpha_device(bpltv_t* h, const double* d_alpha, int am, int an) {
+int upload_alpha_device(bpltv_t* h, const double* d_alpha, int am, int an, const bpltv_params* solve = nullptr) {
     if (!d_alpha || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "alpha: null pointer or empty shape");
     if (am > h->M || an > h->N)
         return set_err(h, BPLTV_E_ARG, "alpha shape %dx%d exceeds image %dx%d", am, an, h->M, h->N);
@@ -603,6 +616,10 @@ int upload_alpha_device(bpltv_t* h, const double* d_alpha, int am, int an) {
     HIPCHK(h, hipMemcpyAsync(chk_h, chk_d, sizeof(chk_h), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     if (chk_h[1] != 0) return set_err(h, BPLTV_E_ARG, "alpha (device array): parameters must be finite and >= 0");
+    double chk[1];
+    std::memcpy(chk, chk_h, sizeof(double));
+    if (solve)
+        if (int rc = solve_precheck(h, *solve, chk[0], PRE_TV)) return rc;
     if (h->alpha_cap < need) {
         drop_graphs(h);  // captured kernels hold the old pointer
         int rc = ensure(h, &h->d_alpha, &h->alpha_cap, need);
@@ -613,8 +630,6 @@ int upload_alpha_device(bpltv_t* h, const double* d_alpha, int am, int an) {
         if (rc) return rc;
     }
     HIPCHK(h, hipMemcpyAsync(h->d_alpha, d_alpha, need * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    double chk[1];
-    std::memcpy(chk, chk_h, sizeof(double));
     h->alpha_min = chk[0];
     h->last_am = am;
     h->last_an = an;
@@ -1521,7 +1536,7 @@ int evaluate_common(bpltv_t* h, const double* alpha, int am, int an, double delt
     HIPCHK(h, hipSetDevice(h->device));
     bpltv_params p = resolve(pp);
     if (int prc = check_params(h, p)) return prc;
-    int rc = upload_alpha(h, alpha, am, an);
+    int rc = upload_alpha(h, alpha, am, an, &p, PRE_TV | pre_gradient(delta, p, am, an));
     if (rc) return rc;
     if (h->band_ready && h->adj_hbm && p.reserved[4] == 1) {   // HBM band path: zero the band while the PDHG solve runs
         const int prc = h->hb.prefill_async();
@@ -1622,13 +1637,50 @@ const SrVariant SR_VARIANTS[] = {
 };
 constexpr int SR_NVARIANTS = 2;
 
+// What run_pdhg (what = PRE_TV) or run_sr_pdhg (PRE_SR) would reject in a solve of the dataset context with a parameter
+// whose smallest entry is amin; PRE_GRADIENT adds what run_gradient / run_sr_gradient_once reject on the parameters and the
+// shape alone (block cyclic reduction where it does not apply; gradient_reg with a patch or map parameter that has a zero
+// entry, PRE_REG_ARRAY).  The entry points check this before the upload, so that a rejected call leaves the handle --
+// d_alpha, its shape and minimum, the last result, and so bpltv_duality_gap -- as it was (sr_check_blocks does the same
+// for sweeps).
+int solve_precheck(bpltv_t* h, const bpltv_params& p, double amin, int what) {
+    if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "bpltv_set_data has not been called");
+    if (p.maxiter < 0) return set_err(h, BPLTV_E_ARG, "maxiter < 0");
+    if (p.rho != 0.0 && !(amin > 0.0))
+        return set_err(h, BPLTV_E_ARG, "rho != 0 divides by alpha: every parameter entry must be > 0 (min = %g)", amin);
+    const bool sr = (what & PRE_SR) != 0;
+    if (!sr) {
+        Plan pl;
+        if (int rc = make_plan(h, p, &pl)) return rc;
+        if ((p.init != 0 || p.order != 0) && h->dtype == 32)
+            return set_err(h, BPLTV_E_UNSUPPORTED, "params.init / params.order are implemented for dtype = 64 handles");
+    } else {
+        if (p.init != 0 || p.order != 0)
+            return set_err(h, BPLTV_E_UNSUPPORTED, "params.init / params.order are implemented for the TV model only");
+        if (p.reserved[0] < 0 || p.reserved[0] > SR_NVARIANTS)
+            return set_err(h, BPLTV_E_ARG, "variant %d: the sum-of-regularisers model has 1..%d", p.reserved[0], SR_NVARIANTS);
+    }
+    if (!(what & PRE_GRADIENT)) return BPLTV_OK;
+    if (p.reserved[4] == 2) {
+        if (sr) return set_err(h, BPLTV_E_UNSUPPORTED, "block cyclic reduction applies to the TV model only");
+        if (!bcr_applicable(h))
+            return set_err(h, BPLTV_E_UNSUPPORTED, "block cyclic reduction needs M <= %d and N >= 2 (M = %d, N = %d)", BS_MP,
+                           h->M, h->N);
+    }
+    if ((what & PRE_REG_ARRAY) && !(amin > 0.0))
+        return set_err(h, BPLTV_E_ARG, sr ? "sumregs_gradient_reg with a patch parameter needs every entry > 0 (min = %g)"
+                                          : "gradient_reg with a patch / pixel-map parameter symmetrises with sqrt(alpha): every entry must be > 0 (min = %g)",
+                       amin);
+    return BPLTV_OK;
+}
+
 void drop_sr_graphs(bpltv_t* h) {
     for (auto& kv : h->sr_graphs)
         for (auto e : kv.second) (void)hipGraphExecDestroy(e);
     h->sr_graphs.clear();
 }
 
-int sr_upload_alpha(bpltv_t* h, const double* alpha, int am, int an) {
+int sr_upload_alpha(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* solve = nullptr, int what = PRE_SR) {
     if (!alpha || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "alpha: null pointer or empty shape");
     if (am > h->M || an > h->N) return set_err(h, BPLTV_E_ARG, "alpha shape %dx%dx3 exceeds image %dx%d", am, an, h->M, h->N);
     const size_t need = 3 * (size_t)am * an;
@@ -1638,6 +1690,8 @@ int sr_upload_alpha(bpltv_t* h, const double* alpha, int am, int an) {
             return set_err(h, BPLTV_E_ARG, "alpha[%zu] = %g: parameters must be finite and >= 0", e, alpha[e]);
         if (alpha[e] < amin) amin = alpha[e];
     }
+    if (solve)
+        if (int rc = solve_precheck(h, *solve, amin, what)) return rc;
     h->alpha_min = amin;
     if (h->alpha_cap < need) {
         drop_graphs(h);
@@ -2073,7 +2127,8 @@ int sr_evaluate_common(bpltv_t* h, const double* alpha, int am, int an, double d
     HIPCHK(h, hipSetDevice(h->device));
     bpltv_params p = resolve(pp);
     if (int prc = check_params(h, p)) return prc;
-    int rc = sr_upload_alpha(h, alpha, am, an);
+    const int reg = !(delta > p.delta_t);   // SumRegsLearningFunction.jl:14-18, 30-34
+    int rc = sr_upload_alpha(h, alpha, am, an, &p, PRE_SR | pre_gradient(delta, p, am, an));
     if (rc) return rc;
     rc = run_sr_pdhg(h, p);
     if (rc) return rc;
@@ -2082,7 +2137,6 @@ int sr_evaluate_common(bpltv_t* h, const double* alpha, int am, int an, double d
     rc = compute_cost(h, d_u, h->d_ubar, h->d_partial);
     if (rc) return rc;
     HIPCHK(h, hipEventRecord(h->ev[5], h->stream));
-    const int reg = !(delta > p.delta_t);   // SumRegsLearningFunction.jl:14-18, 30-34
     rc = run_sr_gradient(h, d_u, h->d_ubar, reg, p, h->d_partial + 1);
     if (rc) return rc;
     const size_t np = 1 + 3 * (size_t)am * an;
@@ -2761,7 +2815,7 @@ int bpltv_denoise(bpltv_t* h, const double* alpha, int am, int an, const bpltv_p
     HIPCHK(h, hipSetDevice(h->device));
     bpltv_params p = resolve(pp);
     if (int prc = check_params(h, p)) return prc;
-    int rc = upload_alpha(h, alpha, am, an);
+    int rc = upload_alpha(h, alpha, am, an, &p);
     if (rc) return rc;
     rc = run_pdhg(h, p);
     if (rc) return rc;
@@ -2787,7 +2841,7 @@ int bpltv_denoise_device(bpltv_t* h, const double* d_alpha, int am, int an, cons
     HIPCHK(h, hipSetDevice(h->device));
     bpltv_params p = resolve(pp);
     if (int prc = check_params(h, p)) return prc;
-    int rc = upload_alpha_device(h, d_alpha, am, an);
+    int rc = upload_alpha_device(h, d_alpha, am, an, &p);
     if (rc) return rc;
     rc = run_pdhg(h, p);
     if (rc) return rc;
@@ -2824,7 +2878,7 @@ int bpltv_sumregs_denoise(bpltv_t* h, const double* alpha, int am, int an, const
     bpltv_params p;
     if (pp) p = *pp; else bpltv_sumregs_default_params(&p);
     if (int prc = check_params(h, p)) return prc;
-    int rc = sr_upload_alpha(h, alpha, am, an);
+    int rc = sr_upload_alpha(h, alpha, am, an, &p);
     if (rc) return rc;
     rc = run_sr_pdhg(h, p);
     if (rc) return rc;

@@ -513,16 +513,14 @@ __device__ __forceinline__ SrStencil sr_stencil(int k, int M, int N, int i, int 
 // The seven non-zero diagonals of the lower band, offsets {0, 1, 2, M-1, M, M+1, 2M}: planes[t][O][M*N] holds
 // A[q + off_t][q].  Gather form, one thread per column q: every element (operator k, pixel e) that has q among its
 // nodes adds V_a^T W V_b for its node slots b on q and a on rows r >= q.  No atomics: the summation order is fixed.
-__device__ __forceinline__ int sr_diag_slot(int d, int M) {
-    // offsets may coincide for tiny M (M = 1, 2, 3): the first match wins, and hb band_entry adds coinciding planes
-    if (d == 0) return 0;
-    if (d == 1) return 1;
-    if (d == 2) return 2;
-    if (d == M - 1) return 3;
-    if (d == M) return 4;
-    if (d == M + 1) return 5;
-    if (d == 2 * M) return 6;
-    return -1;
+// The plane of an entry, by the position (di, dj) of its upper node relative to its lower one: the nested dissection reads
+// the planes by position (nd_stencil_sr).  For M >= 4 the offsets di + M dj are distinct and name the plane as well; for
+// M <= 3 they coincide (M = 3: (2,0) and (-1,1) are both 2 apart, M = 1: (1,0) and (0,1)) and only the position tells
+// them apart -- hb band_entry adds the planes of coinciding offsets, so the band solvers see the same matrix either way.
+__device__ __forceinline__ int sr_geom_slot(int di, int dj) {
+    if (dj == 0) return (di >= 0 && di <= 2) ? di : -1;
+    if (dj == 1) return (di >= -1 && di <= 1) ? 4 + di : -1;
+    return (dj == 2 && di == 0) ? 6 : -1;
 }
 // rowscale (nullable; with am, an: the parameter array) and planesU (nullable, zero-initialised by the caller): the
 // non-symmetric row-scaled system of sumregs_gradient_reg with a patch parameter -- every entry A(r, q) of term k is
@@ -567,7 +565,8 @@ __global__ __launch_bounds__(256) void sr_adj_assemble_kernel(SrCoef C, int M, i
                     const double ta = t1 * v1[a] + t2 * v2[a];
                     double val = c * ta * tb + kp * (v1[a] * v1[b] + v2[a] * v2[b]);
                     if (rowscale) val *= rowscale[k * astride + sr_alpha_index(am, an, M, N, node[a] % M, node[a] / M)];
-                    const int sl = sr_diag_slot(d < 0 ? -d : d, M);
+                    const int ra = node[a] % M - i, rb = node[a] / M - j;   // position of node a relative to q
+                    const int sl = d < 0 ? sr_geom_slot(-ra, -rb) : sr_geom_slot(ra, rb);
                     if (sl >= 0) { if (d >= 0) acc[sl] += val; else accu[sl] += val; }
                 }
             }
@@ -579,7 +578,7 @@ __global__ __launch_bounds__(256) void sr_adj_assemble_kernel(SrCoef C, int M, i
         const int off[7] = {0, 1, 2, M - 1, M, M + 1, 2 * M};
 #pragma unroll
         for (int t = 1; t < 7; ++t)
-            if (q - off[t] >= 0 && sr_diag_slot(off[t], M) == t) planesU[(size_t)t * C.tot + ib + (q - off[t])] = accu[t];
+            if (q - off[t] >= 0) planesU[(size_t)t * C.tot + ib + (q - off[t])] = accu[t];
     }
 }
 

@@ -93,3 +93,56 @@ def test_golden_vectors_on_reference_images(oracle):
         assert np.abs(g - z[m["name"] + "/grad"]).max() <= 2e-7 * np.abs(z[m["name"] + "/grad"]).max()
         gr = oracle.sumregs_gradient(alpha, u, ub, reg=True)
         assert np.abs(gr - z[m["name"] + "/grad_reg"]).max() <= 1e-8 * np.abs(z[m["name"] + "/grad_reg"]).max()
+
+
+# Edge shapes of the sum-of-regularisers model, shared with tests/test_gpu_sumregs_edges.py: sides of 1, 2, 3
+# and 5 pixels, where the reach-2 stencil of the central-difference operator and the two-pixel separators of the nested
+# dissection meet the image border.  (O, N, M) -> numpy batches; seeds and the PDHG count fix u, and so the active sets.
+EDGE_SHAPES = [(2, 1, 9), (2, 9, 1), (1, 2, 2), (2, 3, 5), (1, 2, 17), (1, 17, 2), (1, 1, 1), (2, 5, 3), (1, 3, 3)]
+EDGE_MAXITER = 300
+# bplo_sumregs_gradient against the literal scipy systems at these shapes, relative to max|g|: every case is <= 1e-9
+# except the ones named here (measured 7.5e-9, 5.0e-9, 9.8e-10 and 1.3e-9; the tolerance is about ten times that).  The
+# literal system of the vector gradient at (2, 9, 1) -- one-pixel-wide images -- is exactly singular (scipy: "Factor is
+# exactly singular"); the C oracle returns a finite gradient there, and the GPU has to match it or fail cleanly.
+EDGE_LITERAL_TOL = {((2, 5, 3), "vector", False): 1e-7, ((2, 5, 3), "patch", False): 1e-7, ((2, 5, 3), "map", False): 1e-8,
+                    ((1, 2, 17), "vector", False): 2e-8}
+EDGE_LITERAL_SINGULAR = {((2, 9, 1), "vector", False)}
+
+
+def edge_case(shape, kind):
+    """(ubar, f, alpha) of one edge case; kind: vector, patch (2 x 3, cut to the image), map (3, N, M)."""
+    O, N, M = shape
+    ub, f = synth_batch(O, N, M, seed=11 + N + 3 * M)
+    rng = np.random.default_rng(100 * N + M)
+    sc = 0.1 if N * M <= 9 else 1.0          # at the default scale u is flat on 2 x 2 and the gradient vanishes
+    if kind == "vector":
+        return ub, f, sc * A3
+    if kind == "patch":
+        return ub, f, sc * (0.02 + 0.04 * rng.random((3, min(2, N), min(3, M))))
+    return ub, f, sc * (0.02 + 0.05 * rng.random((3, N, M)))
+
+
+@pytest.mark.parametrize("shape", EDGE_SHAPES, ids=lambda s: "x".join(map(str, s)))
+def test_edge_shapes_pdhg_twin_and_literal_gradients(oracle, shape):
+    """At the edge shapes the C oracle's PDHG is the numpy twin's, and its gradients (both branches, vector / patch /
+    map parameter) are those of the literal reference systems within EDGE_LITERAL_TOL (default 1e-9 of max|g|)."""
+    import warnings
+    for kind in ("vector", "patch", "map"):
+        ub, f, a = edge_case(shape, kind)
+        u = oracle.sumregs_pdhg(f, a, maxiter=EDGE_MAXITER)
+        assert np.abs(u - S.pdhg(f, a, maxiter=EDGE_MAXITER)).max() < 1e-13
+        for reg in (False, True):
+            g = oracle.sumregs_gradient(a, u, ub, reg=reg)
+            assert np.size(g) == np.size(a) and np.all(np.isfinite(g))    # (3, 1, 1) on 1 x 1 is the vector case
+            if shape == (1, 1, 1):          # no differences exist: every operator is zero, so is the gradient
+                assert not np.any(g)
+                continue
+            key = (shape, kind, reg)
+            if key in EDGE_LITERAL_SINGULAR:
+                with warnings.catch_warnings():
+                    warnings.simplefilter("error")
+                    with pytest.raises(RuntimeError, match="singular"):
+                        S.batch_gradient(a, u, ub, reg=reg)
+                continue
+            gl = S.batch_gradient(a, u, ub, reg=reg)
+            assert np.abs(g - gl).max() <= EDGE_LITERAL_TOL.get(key, 1e-9) * np.abs(gl).max(), key
