@@ -78,6 +78,7 @@ SYMBOLS = {
     "bpltv_sumregs_default_params": (C.c_int, [_PP]),
     "bpltv_sumregs_denoise": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp]),
     "bpltv_sumregs_evaluate": (C.c_int, [_H, _dp, C.c_int, C.c_int, C.c_double, _PP, _dp, _dp, _dp]),
+    "bpltv_sumregs_denoise_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, _PP]),
     "bpltv_evaluate_partial": (C.c_int, [_H, _dp, C.c_int, C.c_int, C.c_double, _PP, _dp, _dp]),
     "bpltv_evaluate_device": (C.c_int, [_H, _dp, C.c_int, C.c_int, C.c_double, _PP, C.c_void_p]),
     "bpltv_u_device": (C.c_int, [_H, C.POINTER(C.c_void_p)]),
@@ -89,6 +90,9 @@ SYMBOLS = {
     "bpltv_vjp": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
     "bpltv_vjp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
+    "bpltv_sumregs_vjp": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
+    "bpltv_sumregs_vjp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
     "bpltv_sweep": (C.c_int, [_H, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp]),
     "bpltv_sumregs_sweep": (C.c_int, [_H, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp]),
     "bpltv_per_image": (C.c_int, [_H, _dp]),

@@ -599,14 +599,20 @@ int upload_alpha(bpltv_t* h, const double* alpha, int am, int an, const bpltv_pa
     return BPLTV_OK;
 }
 
-// The same for a parameter that already lives in HBM (bpltv_denoise_device): checked in place by alpha_check_kernel (one
-// 16-byte read back), then copied device to device.  Nothing of the handle changes before the array is accepted: a
-// rejected parameter leaves d_alpha, its shape and alpha_min -- and so the duality gap of the last solve -- as they were.
-int upload_alpha_device(bpltv_t* h, const double* d_alpha, int am, int an, const bpltv_params* solve = nullptr) {
+void drop_sr_graphs(bpltv_t* h);
+
+// The same for a parameter that already lives in HBM (bpltv_denoise_device, bpltv_sumregs_denoise_device): checked in
+// place by alpha_check_kernel (one 16-byte read back), then copied device to device.  Nothing of the handle changes
+// before the array is accepted: a rejected parameter leaves d_alpha, its shape and alpha_min -- and so the duality gap of
+// the last solve -- as they were.  what & PRE_SR: the sum-of-regularisers model, three slices of am*an doubles.
+int upload_alpha_device(bpltv_t* h, const double* d_alpha, int am, int an, const bpltv_params* solve = nullptr,
+                        int what = PRE_TV) {
+    const bool sr = (what & PRE_SR) != 0;
     if (!d_alpha || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "alpha: null pointer or empty shape");
     if (am > h->M || an > h->N)
-        return set_err(h, BPLTV_E_ARG, "alpha shape %dx%d exceeds image %dx%d", am, an, h->M, h->N);
-    const size_t need = (size_t)am * an;
+        return set_err(h, BPLTV_E_ARG, sr ? "alpha shape %dx%dx3 exceeds image %dx%d" : "alpha shape %dx%d exceeds image %dx%d",
+                       am, an, h->M, h->N);
+    const size_t need = (size_t)(sr ? 3 : 1) * am * an;
     unsigned long long* chk_d = reinterpret_cast<unsigned long long*>(h->d_scalar + 2);
     HIPCHK(h, hipMemsetAsync(chk_d, 0xFF, sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipMemsetAsync(chk_d + 1, 0, sizeof(unsigned long long), h->stream));
@@ -619,9 +625,10 @@ int upload_alpha_device(bpltv_t* h, const double* d_alpha, int am, int an, const
     double chk[1];
     std::memcpy(chk, chk_h, sizeof(double));
     if (solve)
-        if (int rc = solve_precheck(h, *solve, chk[0], PRE_TV)) return rc;
+        if (int rc = solve_precheck(h, *solve, chk[0], what)) return rc;
     if (h->alpha_cap < need) {
         drop_graphs(h);  // captured kernels hold the old pointer
+        if (sr) drop_sr_graphs(h);
         int rc = ensure(h, &h->d_alpha, &h->alpha_cap, need);
         if (rc) return rc;
     }
@@ -633,7 +640,7 @@ int upload_alpha_device(bpltv_t* h, const double* d_alpha, int am, int an, const
     h->alpha_min = chk[0];
     h->last_am = am;
     h->last_an = an;
-    h->last_slices = 1;
+    h->last_slices = sr ? 3 : 1;
     return BPLTV_OK;
 }
 
@@ -1569,20 +1576,25 @@ int evaluate_common(bpltv_t* h, const double* alpha, int am, int an, double delt
 }
 
 
+int run_sr_gradient(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, const bpltv_params& p);
+
 // Vector-Jacobian product of u = denoise(f, alpha) on a single-device handle: d_u, d_gu and the outputs live in HBM
 // (the host form stages them), `alpha` on the host or (alpha_dev) in HBM.  Parameter and cotangent are checked before
 // anything of the handle changes; the parameter is then staged in d_vjp, so that the last solve -- d_alpha with its
 // shape and minimum, the PDHG state and graphs, and so bpltv_u_device and bpltv_duality_gap -- stays as it was.
-// d_grad_alpha: am*an doubles in HBM or nullptr; d_grad_f: M*N*O doubles in HBM or nullptr; not both nullptr.
+// slices: 1 TV (bpltv_vjp), 3 sum of regularisers (bpltv_sumregs_vjp; the parameter is 3*am*an doubles).
+// d_grad_alpha: slices*am*an doubles in HBM or nullptr; d_grad_f: M*N*O doubles in HBM or nullptr; not both nullptr.
 int vjp_common(bpltv_t* h, const double* d_u, const double* alpha, bool alpha_dev, int am, int an, int reg,
-               const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alpha) {
+               const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alpha, int slices = 1) {
     if (!d_u || !alpha || !d_gu) return set_err(h, BPLTV_E_ARG, "vjp: null pointer");
     if (!d_grad_f && !d_grad_alpha) return set_err(h, BPLTV_E_ARG, "vjp: both outputs are NULL");
     if (am < 1 || an < 1 || am > h->M || an > h->N)
         return set_err(h, BPLTV_E_ARG, "vjp: parameter shape %dx%d (image %dx%d)", am, an, h->M, h->N);
+    const bool sr = slices == 3;
     bpltv_params p = resolve(pp);
     if (int prc = check_params(h, p)) return prc;
-    const size_t P = (size_t)am * an;
+    if (sr && p.reserved[4] == 2) return set_err(h, BPLTV_E_UNSUPPORTED, "block cyclic reduction applies to the TV model only");
+    const size_t P = (size_t)slices * am * an;
     double amin = 0.0;
     if (!alpha_dev) {   // as upload_alpha
         amin = alpha[0];
@@ -1610,6 +1622,8 @@ int vjp_common(bpltv_t* h, const double* d_u, const double* alpha, bool alpha_de
     if (chk_h[1] != 0) return set_err(h, BPLTV_E_ARG, "vjp: alpha (device array): parameters must be finite and >= 0");
     if (chk_h[2] != 0) return set_err(h, BPLTV_E_ARG, "vjp: the cotangent gu must be finite");
     if (alpha_dev) std::memcpy(&amin, chk_h, sizeof(double));
+    if (sr && reg && !(am == 1 && an == 1) && !(amin > 0.0))   // run_sr_gradient_once's condition, before anything changes
+        return set_err(h, BPLTV_E_ARG, "sumregs_gradient_reg with a patch parameter needs every entry > 0 (min = %g)", amin);
     double* d_a = h->d_vjp + 4;
     HIPCHK(h, hipMemcpyAsync(d_a, alpha, P * sizeof(double), alpha_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     GradCtx g;
@@ -1617,7 +1631,7 @@ int vjp_common(bpltv_t* h, const double* d_u, const double* alpha, bool alpha_de
     g.src = d_gu; g.cot = true;
     g.d_out = d_grad_alpha; g.d_grad_f = d_grad_f;
     h->has_per_image = false;   // the reduction scratch (d_red) no longer holds the last evaluate's rows
-    return run_gradient(h, d_u, g, reg ? 1 : 0, p);
+    return sr ? run_sr_gradient(h, d_u, g, reg ? 1 : 0, p) : run_gradient(h, d_u, g, reg ? 1 : 0, p);
 }
 
 // ============================================================================================
@@ -1949,11 +1963,11 @@ int sr_band_alloc(bpltv_t* h) {
 // (params.reserved[4] = 1), and -- sumregs_gradient_reg with a patch parameter, whose row-scaled system is not
 // symmetric (SumRegsLearningFunction.jl:250) -- the LU variant of the nested dissection (banded LU with
 // params.reserved[4] = 1).
-int run_sr_gradient_once(bpltv_t* h, const double* d_u, const double* d_ubar, int reg, const bpltv_params& p, double* d_out,
-                         double kappa_scale) {
+// Parameter (three slices of g.am*g.an), right-hand side and outputs come from `g`, as for run_gradient_once.
+int run_sr_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, const bpltv_params& p, double kappa_scale) {
     int rc = sr_adj_alloc(h);
     if (rc) return rc;
-    const int M = h->M, N = h->N, O = h->O, am = h->last_am, an = h->last_an;
+    const int M = h->M, N = h->N, O = h->O, am = g.am, an = g.an;
     const size_t tot = h->tot, P = (size_t)am * an, npx = h->npx;
     const int patch = !(am == 1 && an == 1);
     const bool rowsc = reg && patch;
@@ -1961,8 +1975,8 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const double* d_ubar, in
     if (p.reserved[4] == 2) return set_err(h, BPLTV_E_UNSUPPORTED, "block cyclic reduction applies to the TV model only");
     const bool band = p.reserved[4] == 1;     // the band solvers (Cholesky / LU) instead of nested dissection
     int Oc = O;
-    if (lu && rowsc && !(h->alpha_min > 0.0))
-        return set_err(h, BPLTV_E_ARG, "sumregs_gradient_reg with a patch parameter needs every entry > 0 (min = %g)", h->alpha_min);
+    if (lu && rowsc && !(g.alpha_min > 0.0))
+        return set_err(h, BPLTV_E_ARG, "sumregs_gradient_reg with a patch parameter needs every entry > 0 (min = %g)", g.alpha_min);
     if (lu && !h->d_srdiagU) {
         rc = alloc_all(h, {{(void**)&h->d_srdiagU, 7 * tot * sizeof(double)}}, "sum-of-regularisers adjoint (upper diagonals)");
         if (rc) return rc;
@@ -1996,7 +2010,7 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const double* d_ubar, in
     const int nref = p.refine < 0 ? (reg ? 1 : 2) : p.refine;
     HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_fail, 0, sizeof(int) * O, h->stream));
-    const double* rowscale = rowsc ? h->d_alpha : nullptr;
+    const double* rowscale = rowsc ? g.alpha : nullptr;
     int chunks = 0;
     for (int c0 = 0; c0 < O; c0 += Oc, ++chunks) {
         const int nimg = std::min(Oc, O - c0);
@@ -2009,8 +2023,12 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const double* d_ubar, in
         double *dp = h->d_p + o0, *dr = h->d_r + o0;
         int* dfail = h->d_fail + c0;
         const int gpx = (int)((ctot + 255) / 256);
-        hipLaunchKernelGGL(sr_adj_setup_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, d_ubar + o0, h->d_alpha, am, an, M, N, nimg,
-                           patch, reg, kact, C);
+        if (g.cot)
+            hipLaunchKernelGGL(sr_adj_setup_cot_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0, g.alpha, am, an, M, N,
+                               nimg, patch, reg, kact, C);
+        else
+            hipLaunchKernelGGL(sr_adj_setup_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0, g.alpha, am, an, M, N, nimg,
+                               patch, reg, kact, C);
         if (lu) HIPCHK(h, hipMemsetAsync(h->d_srdiagU, 0, 7 * tot * sizeof(double), h->stream));
         hipLaunchKernelGGL(sr_adj_assemble_kernel, dim3(gpx), dim3(256), 0, h->stream, C, M, N, nimg, diag, rowscale, am, an, diagU);
         BandDiags D;
@@ -2055,21 +2073,27 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const double* d_ubar, in
         double* resn_part = h->d_resn + 4 * (size_t)O + 4 * (size_t)c0 * RESN_BLK;
         hipLaunchKernelGGL(adj_resnorm_kernel, dim3(RESN_BLK, nimg), dim3(256), 0, h->stream, dr, C.rhs, diag, (int)npx, resn_part);
         hipLaunchKernelGGL(adj_resnorm_final_kernel, dim3((4 * nimg + 63) / 64), dim3(64), 0, h->stream, resn_part, nimg, h->d_resn + 4 * (size_t)c0);
-        hipLaunchKernelGGL(sr_adj_gradpix_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, patch, reg, gp);
+        if (g.d_out)
+            hipLaunchKernelGGL(sr_adj_gradpix_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, patch, reg, gp);
         HIPCHK(h, hipGetLastError());
     }
-    if (am == M && an == N && !(M == 1 && N == 1)) {   // three pixelwise maps: plain sums over the images
+    // ... then per parameter, over all images (a vector-Jacobian product may not want the parameter gradient)
+    const bool amap = am == M && an == N && !(M == 1 && N == 1);
+    if (g.d_out && amap) {   // three pixelwise maps: plain sums over the images
         for (int k = 0; k < 3; ++k)
             hipLaunchKernelGGL(map_sum_kernel, dim3((unsigned)((h->npx + 255) / 256)), dim3(256), 0, h->stream, h->d_srgpix + k * tot,
-                               h->npx, O, d_out + (size_t)k * h->npx);
-    } else {
+                               h->npx, O, g.d_out + (size_t)k * h->npx);
+    } else if (g.d_out) {
         rc = ensure(h, &h->d_red, &h->red_cap, 3 * P * O);
         if (rc) return rc;
         for (int k = 0; k < 3; ++k)
             hipLaunchKernelGGL(patch_sum_kernel, dim3((unsigned)P, O), dim3(256), 0, h->stream, h->d_srgpix + k * tot, M, N, O, am, an,
                                h->d_red + (size_t)k * P * O);
-        hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, O, (int)(3 * P), 1.0, d_out, (double*)nullptr);
+        hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, O, (int)(3 * P), 1.0, g.d_out, (double*)nullptr);
     }
+    // input gradient of a vector-Jacobian product: d_p covers the whole batch after the group loop
+    if (g.d_grad_f)
+        hipLaunchKernelGGL(sr_adj_gradf_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->d_p, tot, reg, g.d_grad_f);
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
     std::vector<int> fail(O);
@@ -2106,12 +2130,12 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const double* d_ubar, in
     return BPLTV_OK;
 }
 
-int run_sr_gradient(bpltv_t* h, const double* d_u, const double* d_ubar, int reg, const bpltv_params& p, double* d_out) {
+int run_sr_gradient(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, const bpltv_params& p) {
     double scale = 1.0;
     int rc = BPLTV_OK;
     h->st.adjoint_attempts = 0;
     for (int attempt = 0; attempt < 3; ++attempt, scale *= 1e-2) {
-        rc = run_sr_gradient_once(h, d_u, d_ubar, reg, p, d_out, scale);
+        rc = run_sr_gradient_once(h, d_u, g, reg, p, scale);
         h->st.adjoint_attempts = attempt + 1;
         if (rc != BPLTV_E_NUMERIC || reg) break;
     }
@@ -2137,7 +2161,7 @@ int sr_evaluate_common(bpltv_t* h, const double* alpha, int am, int an, double d
     rc = compute_cost(h, d_u, h->d_ubar, h->d_partial);
     if (rc) return rc;
     HIPCHK(h, hipEventRecord(h->ev[5], h->stream));
-    rc = run_sr_gradient(h, d_u, h->d_ubar, reg, p, h->d_partial + 1);
+    rc = run_sr_gradient(h, d_u, gradient_ctx(h, h->d_ubar, h->d_partial + 1), reg, p);
     if (rc) return rc;
     const size_t np = 1 + 3 * (size_t)am * an;
     if (partial_host) HIPCHK(h, hipMemcpyAsync(partial_host, h->d_partial, np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -2520,20 +2544,22 @@ int multi_gradient(bpltv_t* h, const double* u, const double* ubar, const double
 }
 
 // bpltv_vjp over the shards: images split as for the gradient, input-gradient slices written in place, the parameter
-// gradients of the shards added in shard order.
+// gradients of the shards added in shard order.  slices: 1 TV (bpltv_vjp), 3 sum of regularisers (bpltv_sumregs_vjp).
 int multi_vjp(bpltv_t* h, const double* u, const double* alpha, int am, int an, int reg, const bpltv_params* pp,
-              const double* gu, double* grad_f_out, double* grad_alpha_out) {
+              const double* gu, double* grad_f_out, double* grad_alpha_out, int slices = 1) {
     if (!u || !gu || !alpha || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "vjp: null pointer or empty shape");
     if (!grad_f_out && !grad_alpha_out) return set_err(h, BPLTV_E_ARG, "vjp: both outputs are NULL");
     WallTimer wt;
     MultiState& ms = *h->multi;
     const int n = (int)ms.shard.size();
-    const size_t npx = h->npx, P = (size_t)am * an;
+    const size_t npx = h->npx, P = (size_t)slices * am * an;
     std::vector<double> g((size_t)n * P);
     int rc = multi_run(h, [&](int k, bpltv_t* c) {
         const size_t o0 = ms.lo[k] * npx;
-        return bpltv_vjp(c, u + o0, alpha, am, an, reg, pp, gu + o0, grad_f_out ? grad_f_out + o0 : nullptr,
-                         grad_alpha_out ? g.data() + (size_t)k * P : nullptr);
+        double* gf = grad_f_out ? grad_f_out + o0 : nullptr;
+        double* ga = grad_alpha_out ? g.data() + (size_t)k * P : nullptr;
+        return slices == 3 ? bpltv_sumregs_vjp(c, u + o0, alpha, am, an, reg, pp, gu + o0, gf, ga)
+                           : bpltv_vjp(c, u + o0, alpha, am, an, reg, pp, gu + o0, gf, ga);
     });
     if (rc) return rc;
     if (grad_alpha_out)
@@ -2624,6 +2650,59 @@ int multi_unsupported(bpltv_t* h, const char* what) {
     if (h->multi->shard.size() == 1) return -1;   // one shard: forward to it
     return set_err(h, BPLTV_E_UNSUPPORTED, "%s takes a device pointer, which is ambiguous on a handle over %zu shards; use the host-array entry points",
                    what, h->multi->shard.size());
+}
+
+// bpltv_vjp (slices = 1) and bpltv_sumregs_vjp (3): host arrays staged in d_u2 / d_ubar2 / d_gf2, the parameter gradient
+// read back from d_vjp.
+int vjp_host(bpltv_t* h, const double* u, const double* alpha, int am, int an, int reg, const bpltv_params* pp,
+             const double* gu, double* grad_f_out, double* grad_alpha_out, int slices) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi) return multi_vjp(h, u, alpha, am, an, reg, pp, gu, grad_f_out, grad_alpha_out, slices);
+    if (!u || !gu || !alpha) return set_err(h, BPLTV_E_ARG, "vjp: null pointer");
+    if (!grad_f_out && !grad_alpha_out) return set_err(h, BPLTV_E_ARG, "vjp: both outputs are NULL");
+    if (am < 1 || an < 1 || am > h->M || an > h->N)
+        return set_err(h, BPLTV_E_ARG, "vjp: parameter shape %dx%d (image %dx%d)", am, an, h->M, h->N);
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->d_u2) {
+        HIPCHK(h, hipMalloc((void**)&h->d_u2, h->tot * sizeof(double)));
+        HIPCHK(h, hipMalloc((void**)&h->d_ubar2, h->tot * sizeof(double)));
+    }
+    if (grad_f_out && !h->d_gf2) HIPCHK(h, hipMalloc((void**)&h->d_gf2, h->tot * sizeof(double)));
+    HIPCHK(h, hipMemcpyAsync(h->d_u2, u, h->tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_ubar2, gu, h->tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    const size_t P = (size_t)slices * am * an;
+    int rc = ensure(h, &h->d_vjp, &h->vjp_cap, 4 + 2 * P);
+    if (rc) return rc;
+    double* d_ga = grad_alpha_out ? h->d_vjp + 4 + P : nullptr;
+    rc = vjp_common(h, h->d_u2, alpha, false, am, an, reg, pp, h->d_ubar2, grad_f_out ? h->d_gf2 : nullptr, d_ga, slices);
+    if (rc) return rc;
+    if (grad_f_out)
+        HIPCHK(h, hipMemcpyAsync(grad_f_out, h->d_gf2, h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (grad_alpha_out)
+        HIPCHK(h, hipMemcpyAsync(grad_alpha_out, d_ga, sizeof(double) * P, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
+// bpltv_vjp_device (slices = 1) and bpltv_sumregs_vjp_device (3)
+int vjp_device(bpltv_t* h, const double* d_u, const double* d_alpha, int am, int an, int reg, const bpltv_params* pp,
+               const double* d_gu, double* d_grad_f, double* d_grad_alpha, int slices) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi) {
+        const int rc = multi_unsupported(h, slices == 3 ? "bpltv_sumregs_vjp_device" : "bpltv_vjp_device");
+        if (rc >= 0) return rc;
+        const int r = vjp_device(h->multi->shard[0], d_u, d_alpha, am, an, reg, pp, d_gu, d_grad_f, d_grad_alpha, slices);
+        if (r) h->err = h->multi->shard[0]->err; else { h->has_per_image = false; multi_stats(h); }
+        return r;
+    }
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int rc = vjp_common(h, d_u, d_alpha, true, am, an, reg, pp, d_gu, d_grad_f, d_grad_alpha, slices);
+    if (rc) return rc;
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
 }
 
 }  // namespace
@@ -2890,6 +2969,28 @@ int bpltv_sumregs_denoise(bpltv_t* h, const double* alpha, int am, int an, const
     return BPLTV_OK;
 }
 
+int bpltv_sumregs_denoise_device(bpltv_t* h, const double* d_alpha, int am, int an, const bpltv_params* pp) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi) {
+        const int rc = multi_unsupported(h, "bpltv_sumregs_denoise_device");
+        if (rc >= 0) return rc;
+        const int r = bpltv_sumregs_denoise_device(h->multi->shard[0], d_alpha, am, an, pp);
+        if (r) h->err = h->multi->shard[0]->err; else { h->has_result = true; multi_stats(h); }
+        return r;
+    }
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    bpltv_params p;
+    if (pp) p = *pp; else bpltv_sumregs_default_params(&p);
+    if (int prc = check_params(h, p)) return prc;
+    int rc = upload_alpha_device(h, d_alpha, am, an, &p, PRE_SR);
+    if (rc) return rc;
+    rc = run_sr_pdhg(h, p);
+    if (rc) return rc;
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
 int bpltv_sumregs_evaluate(bpltv_t* h, const double* alpha, int am, int an, double delta, const bpltv_params* pp, double* u_out,
                            double* cost_out, double* grad_out) {
     if (!h) return BPLTV_E_ARG;
@@ -3047,51 +3148,22 @@ int bpltv_gradient(bpltv_t* h, const double* u, const double* ubar, const double
 
 int bpltv_vjp(bpltv_t* h, const double* u, const double* alpha, int am, int an, int reg, const bpltv_params* pp,
               const double* gu, double* grad_f_out, double* grad_alpha_out) {
-    if (!h) return BPLTV_E_ARG;
-    if (h->multi) return multi_vjp(h, u, alpha, am, an, reg, pp, gu, grad_f_out, grad_alpha_out);
-    if (!u || !gu || !alpha) return set_err(h, BPLTV_E_ARG, "vjp: null pointer");
-    if (!grad_f_out && !grad_alpha_out) return set_err(h, BPLTV_E_ARG, "vjp: both outputs are NULL");
-    if (am < 1 || an < 1 || am > h->M || an > h->N)
-        return set_err(h, BPLTV_E_ARG, "vjp: parameter shape %dx%d (image %dx%d)", am, an, h->M, h->N);
-    WallTimer wt;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!h->d_u2) {
-        HIPCHK(h, hipMalloc((void**)&h->d_u2, h->tot * sizeof(double)));
-        HIPCHK(h, hipMalloc((void**)&h->d_ubar2, h->tot * sizeof(double)));
-    }
-    if (grad_f_out && !h->d_gf2) HIPCHK(h, hipMalloc((void**)&h->d_gf2, h->tot * sizeof(double)));
-    HIPCHK(h, hipMemcpyAsync(h->d_u2, u, h->tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_ubar2, gu, h->tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    int rc = ensure(h, &h->d_vjp, &h->vjp_cap, 4 + 2 * (size_t)am * an);
-    if (rc) return rc;
-    double* d_ga = grad_alpha_out ? h->d_vjp + 4 + (size_t)am * an : nullptr;
-    rc = vjp_common(h, h->d_u2, alpha, false, am, an, reg, pp, h->d_ubar2, grad_f_out ? h->d_gf2 : nullptr, d_ga);
-    if (rc) return rc;
-    if (grad_f_out)
-        HIPCHK(h, hipMemcpyAsync(grad_f_out, h->d_gf2, h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (grad_alpha_out)
-        HIPCHK(h, hipMemcpyAsync(grad_alpha_out, d_ga, sizeof(double) * (size_t)am * an, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->st.total_ms = wt.ms();
-    return BPLTV_OK;
+    return vjp_host(h, u, alpha, am, an, reg, pp, gu, grad_f_out, grad_alpha_out, 1);
 }
 
 int bpltv_vjp_device(bpltv_t* h, const double* d_u, const double* d_alpha, int am, int an, int reg, const bpltv_params* pp,
                      const double* d_gu, double* d_grad_f, double* d_grad_alpha) {
-    if (!h) return BPLTV_E_ARG;
-    if (h->multi) {
-        const int rc = multi_unsupported(h, "bpltv_vjp_device");
-        if (rc >= 0) return rc;
-        const int r = bpltv_vjp_device(h->multi->shard[0], d_u, d_alpha, am, an, reg, pp, d_gu, d_grad_f, d_grad_alpha);
-        if (r) h->err = h->multi->shard[0]->err; else { h->has_per_image = false; multi_stats(h); }
-        return r;
-    }
-    WallTimer wt;
-    HIPCHK(h, hipSetDevice(h->device));
-    const int rc = vjp_common(h, d_u, d_alpha, true, am, an, reg, pp, d_gu, d_grad_f, d_grad_alpha);
-    if (rc) return rc;
-    h->st.total_ms = wt.ms();
-    return BPLTV_OK;
+    return vjp_device(h, d_u, d_alpha, am, an, reg, pp, d_gu, d_grad_f, d_grad_alpha, 1);
+}
+
+int bpltv_sumregs_vjp(bpltv_t* h, const double* u, const double* alpha, int am, int an, int reg, const bpltv_params* pp,
+                      const double* gu, double* grad_f_out, double* grad_alpha_out) {
+    return vjp_host(h, u, alpha, am, an, reg, pp, gu, grad_f_out, grad_alpha_out, 3);
+}
+
+int bpltv_sumregs_vjp_device(bpltv_t* h, const double* d_u, const double* d_alpha, int am, int an, int reg,
+                             const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alpha) {
+    return vjp_device(h, d_u, d_alpha, am, an, reg, pp, d_gu, d_grad_f, d_grad_alpha, 3);
 }
 
 int bpltv_sweep(bpltv_t* h, const double* alphas, int K, int am, int an, const bpltv_params* pp, double* cost_out,

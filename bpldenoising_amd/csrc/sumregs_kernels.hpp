@@ -449,9 +449,12 @@ __global__ __launch_bounds__(256) void sr_gap_partial_kernel(SrState S, const do
 
 // per element and operator: coefficients of W_k and of the gradient functional; grid over O*M*N, one thread per
 // pixel, all three operators.  reg: gradient_reg (gamma = 1e3 vector / 1e8 patch parameter).
-__global__ __launch_bounds__(256) void sr_adj_setup_kernel(const double* __restrict__ u, const double* __restrict__ ubar,
-                                                           const double* __restrict__ alpha, int am, int an, int M, int N, int O,
-                                                           int patch, int reg, double kappa_act, SrCoef C) {
+// COT = false: right-hand side of the loss 0.5||u - ubar||^2 (src = ubar); COT = true: of a vector-Jacobian product with
+// the cotangent gu = dL/du (src = gu), which takes the place of u - ubar.  The coefficient planes do not depend on COT.
+template <bool COT>
+__device__ __forceinline__ void sr_adj_setup_body(const double* __restrict__ u, const double* __restrict__ src,
+                                                  const double* __restrict__ alpha, int am, int an, int M, int N, int O,
+                                                  int patch, int reg, double kappa_act, SrCoef C) {
     // reg && patch: the parameter scales ROWS of term k (SumRegsLearningFunction.jl:250) and stays out of c, kap
     const size_t npx = (size_t)M * N;
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -489,7 +492,32 @@ __global__ __launch_bounds__(256) void sr_adj_setup_kernel(const double* __restr
         const size_t o = (size_t)k * C.tot + e;
         C.t1[o] = t1; C.t2[o] = t2; C.c[o] = c; C.kap[o] = kap; C.h1[o] = h1; C.h2[o] = h2;
     }
-    C.rhs[e] = reg ? ubar[e] - u[e] : u[e] - ubar[e];
+    // reg: the row-scaled system of SumRegsLearningFunction.jl:250 takes ubar - u as it is, so the cotangent form is -gu
+    // (no division); ubar - u == -(u - ubar) exactly
+    if (COT) C.rhs[e] = reg ? -src[e] : src[e];
+    else C.rhs[e] = reg ? src[e] - u[e] : u[e] - src[e];
+}
+
+__global__ __launch_bounds__(256) void sr_adj_setup_kernel(const double* __restrict__ u, const double* __restrict__ ubar,
+                                                           const double* __restrict__ alpha, int am, int an, int M, int N, int O,
+                                                           int patch, int reg, double kappa_act, SrCoef C) {
+    sr_adj_setup_body<false>(u, ubar, alpha, am, an, M, N, O, patch, reg, kappa_act, C);
+}
+
+// The same coefficients with the right-hand side of a vector-Jacobian product: gu, or -gu for sumregs_gradient_reg.
+__global__ __launch_bounds__(256) void sr_adj_setup_cot_kernel(const double* __restrict__ u, const double* __restrict__ gu,
+                                                               const double* __restrict__ alpha, int am, int an, int M, int N,
+                                                               int O, int patch, int reg, double kappa_act, SrCoef C) {
+    sr_adj_setup_body<true>(u, gu, alpha, am, an, M, N, O, patch, reg, kappa_act, C);
+}
+
+// Input gradient of a sum-of-regularisers vector-Jacobian product: the adjoint state p (there is no s plane on this
+// model), negated for sumregs_gradient_reg, whose right-hand side was -gu.
+__global__ __launch_bounds__(256) void sr_adj_gradf_kernel(const double* __restrict__ p, size_t n, int reg,
+                                                           double* __restrict__ grad_f) {
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    grad_f[q] = reg ? -p[q] : p[q];
 }
 
 // Element stencil: component c couples node pl (coefficient +s) and node mi (-s); s = 0: absent.

@@ -223,6 +223,42 @@ class TVSolver:
                                                      _ptr(u) if fetch_u else None, C.byref(cost), _ptr(grad)))
         return u, cost.value, (grad.copy() if vec else grad.reshape(3, an, am))
 
+    def sumregs_denoise_device(self, alpha_ptr, am=1, an=1, **kw):
+        """bpltv_sumregs_denoise_device: the parameter (3*am*an doubles, three column-major am x an slices -- a
+        C-contiguous (3, an, am) array) already resident in HBM at `alpha_ptr`; the result stays on the device
+        (u_device_ptr / copy_u_device)."""
+        p = self.params(_sumregs=True, **kw)
+        self._check(self._lib.bpltv_sumregs_denoise_device(self._h, C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p)))
+
+    def sumregs_vjp(self, u, x, gu, reg=False, want_f=True, want_alpha=True, **kw):
+        """Vector-Jacobian product of u = sumregs_denoise(f, x) for the cotangent gu = dL/du (bpltv_sumregs_vjp):
+        (grad_f, grad_x).  u, gu: (O, N, M) batches; x: (3,) or (3, n, m).  grad_f has the shape of u (None unless
+        want_f), grad_x the shape of x (None unless want_alpha).  gu = u - ubar gives sumregs_evaluate's gradient
+        bitwise (reg = the evaluate's delta <= delta_t)."""
+        if not (want_f or want_alpha):
+            raise ValueError("sumregs_vjp: want_f and want_alpha are both False")
+        a, am, an, vec = _sr_alpha_arg(x)
+        p = self.params(_sumregs=True, **kw)
+        u = self._batch(u, "u")
+        gu = self._batch(gu, "gu")
+        gf = np.empty((self.O, self.N, self.M)) if want_f else None
+        ga = np.empty(3 * am * an) if want_alpha else None
+        self._check(self._lib.bpltv_sumregs_vjp(self._h, _ptr(u), _ptr(a), am, an, int(bool(reg)), C.byref(p),
+                                                _ptr(gu), _ptr(gf) if want_f else None,
+                                                _ptr(ga) if want_alpha else None))
+        if ga is not None and not vec:
+            ga = ga.reshape(3, an, am)
+        return gf, ga
+
+    def sumregs_vjp_device(self, u_ptr, alpha_ptr, am, an, gu_ptr, grad_f_ptr, grad_alpha_ptr, reg=False, **kw):
+        """bpltv_sumregs_vjp_device: u, gu and grad_f (M*N*O doubles), the parameter and grad_alpha (3*am*an doubles)
+        all resident in HBM; either output pointer may be 0 / None, not both."""
+        p = self.params(_sumregs=True, **kw)
+        self._check(self._lib.bpltv_sumregs_vjp_device(self._h, C.c_void_p(u_ptr), C.c_void_p(alpha_ptr), int(am),
+                                                       int(an), int(bool(reg)), C.byref(p), C.c_void_p(gu_ptr),
+                                                       C.c_void_p(grad_f_ptr or None),
+                                                       C.c_void_p(grad_alpha_ptr or None)))
+
     def gradient(self, u, ubar, x, reg=False, **kw):
         a, am, an, scalar = _alpha_arg(x)
         p = self.params(**kw)

@@ -1,4 +1,5 @@
-"""PyTorch autograd layer over the TV denoiser: u = denoise(f, alpha) as a differentiable operation.
+"""PyTorch autograd layers over the TV and the sum-of-regularisers denoisers: u = denoise(f, alpha) as a
+differentiable operation.
 
     u = tv_denoise(f, alpha, reg=False, maxiter=5000)      # forward: one batched PDHG solve on the GPU
     loss(u).backward()                                     # backward: one adjoint solve (bpltv_vjp_device)
@@ -9,6 +10,12 @@ terms O = B, N = H, M = W, the convention of learning_function.py.  alpha is a f
 product of include/bpltv.h's bpltv_vjp for the cotangent torch hands it: f.grad and alpha.grad for any loss.  `reg`
 selects the reference's gradient_reg linearisation (delta <= delta_t in tv_op_learning_function).  Double backward is
 not supported (once_differentiable).
+
+    u = sumregs_denoise(f, alpha, reg=False)               # the three-weight model (bpltv_sumregs_*)
+
+alpha is then float64 of shape (3,) (one weight per difference: forward, backward, centred), (3, pH, pW) (patch
+parameter) or (3, H, W) (maps); a C-contiguous (3, pH, pW) tensor is already the library's slice layout (an, am =
+pH, pW).  The backward pass is bpltv_sumregs_vjp_device's; reg selects sumregs_gradient_reg.
 
 Streams: the library runs its kernels on its own HIP streams and blocks until they are done.  Every call below first
 synchronises the tensors' current torch stream, so that the library reads inputs torch has finished writing; its
@@ -41,27 +48,38 @@ def clear_solvers():
     _solvers.clear()
 
 
-def _check_args(f, alpha):
-    """(O, N, M, am, an) of a valid (f, alpha) pair; TypeError / ValueError before any library call."""
+def _check_args(f, alpha, slices=1):
+    """(O, N, M, am, an) of a valid (f, alpha) pair; TypeError / ValueError before any library call.  slices = 3: the
+    sum-of-regularisers parameter, a leading dimension of 3 on the TV model's vector / patch / map shapes."""
+    name = "sumregs_denoise" if slices == 3 else "tv_denoise"
     if not isinstance(f, torch.Tensor) or not isinstance(alpha, torch.Tensor):
-        raise TypeError("tv_denoise: f and alpha must be torch tensors")
+        raise TypeError("%s: f and alpha must be torch tensors" % name)
     if f.dtype != torch.float64 or alpha.dtype != torch.float64:
-        raise TypeError("tv_denoise: f and alpha must be float64 (got %s, %s)" % (f.dtype, alpha.dtype))
+        raise TypeError("%s: f and alpha must be float64 (got %s, %s)" % (name, f.dtype, alpha.dtype))
     if f.dim() not in (2, 3) or f.numel() == 0:
-        raise ValueError("tv_denoise: f must have shape (B, H, W) or (H, W), got %s" % (tuple(f.shape),))
+        raise ValueError("%s: f must have shape (B, H, W) or (H, W), got %s" % (name, tuple(f.shape)))
     H, W = f.shape[-2], f.shape[-1]
     O = f.shape[0] if f.dim() == 3 else 1
-    if alpha.dim() == 0:
-        am = an = 1
-    elif alpha.dim() == 2 and 1 <= alpha.shape[0] <= H and 1 <= alpha.shape[1] <= W:
-        an, am = alpha.shape
+    lead = (3,) if slices == 3 else ()
+    shape = tuple(alpha.shape)
+    if shape[:len(lead)] != lead:
+        shape = None
     else:
-        raise ValueError("tv_denoise: alpha must be 0-dim, (pH, pW) with pH <= %d, pW <= %d, or (%d, %d); got %s"
-                         % (H, W, H, W, tuple(alpha.shape)))
+        shape = shape[len(lead):]
+    if shape == ():
+        am = an = 1
+    elif shape is not None and len(shape) == 2 and 1 <= shape[0] <= H and 1 <= shape[1] <= W:
+        an, am = shape
+    elif slices == 3:
+        raise ValueError("%s: alpha must be (3,), (3, pH, pW) with pH <= %d, pW <= %d, or (3, %d, %d); got %s"
+                         % (name, H, W, H, W, tuple(alpha.shape)))
+    else:
+        raise ValueError("%s: alpha must be 0-dim, (pH, pW) with pH <= %d, pW <= %d, or (%d, %d); got %s"
+                         % (name, H, W, H, W, tuple(alpha.shape)))
     if alpha.device != f.device:
-        raise ValueError("tv_denoise: alpha is on %s, f on %s" % (alpha.device, f.device))
+        raise ValueError("%s: alpha is on %s, f on %s" % (name, alpha.device, f.device))
     if f.device.type != "cuda":
-        raise ValueError("tv_denoise: f must be on a ROCm device, got %s" % (f.device,))
+        raise ValueError("%s: f must be on a ROCm device, got %s" % (name, f.device))
     return O, H, W, am, an
 
 
@@ -124,3 +142,60 @@ class TVDenoise(torch.nn.Module):
 
     def forward(self, f):
         return tv_denoise(f, self.alpha, reg=self.reg, **self.solver_kw)
+
+
+class SumRegsDenoiseFunction(torch.autograd.Function):
+    """autograd.Function of sumregs_denoise (below); apply(f, alpha, reg, solver_kw)."""
+
+    @staticmethod
+    def forward(ctx, f, alpha, reg, solver_kw):
+        O, N, M, am, an = _check_args(f, alpha, slices=3)
+        index = f.device.index if f.device.index is not None else torch.cuda.current_device()
+        s = _solver(index, M, N, O)
+        fc = f.detach().contiguous()
+        ac = alpha.detach().contiguous()
+        u = torch.empty_like(fc)
+        _sync(f.device)
+        s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
+        s.sumregs_denoise_device(ac.data_ptr(), am, an, **solver_kw)
+        s.copy_u_device(u.data_ptr())
+        ctx.save_for_backward(u, ac)
+        ctx.solver, ctx.am, ctx.an, ctx.reg, ctx.solver_kw = s, am, an, bool(reg), dict(solver_kw)
+        return u
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gu):
+        need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_f or need_a):
+            return None, None, None, None
+        u, alpha = ctx.saved_tensors
+        gu = gu.to(dtype=torch.float64).contiguous()
+        gf = torch.empty_like(u) if need_f else None
+        ga = torch.empty(3 * ctx.am * ctx.an, dtype=torch.float64, device=u.device) if need_a else None
+        _sync(u.device)
+        ctx.solver.sumregs_vjp_device(u.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(),
+                                      gf.data_ptr() if need_f else None, ga.data_ptr() if need_a else None,
+                                      reg=ctx.reg, **ctx.solver_kw)
+        return gf, (ga.reshape(alpha.shape) if need_a else None), None, None
+
+
+def sumregs_denoise(f, alpha, *, reg=False, **solver_kw):
+    """u = sumregs_denoise(f, alpha) (TVSolver.sumregs_denoise: the reference's sumregs_denoise,
+    src/SumRegsLearningFunction.jl:38-85), differentiable in f and alpha.  alpha: (3,), (3, pH, pW) or (3, H, W).
+    solver_kw: the solver parameters of TVSolver.params, used by the forward solve and the adjoint alike."""
+    return SumRegsDenoiseFunction.apply(f, alpha, reg, solver_kw)
+
+
+class SumRegsDenoise(torch.nn.Module):
+    """Sum-of-regularisers denoising with a learnable weight: a (3,) vector, or a (3, pH, pW) / (3, H, W) array.  Move
+    it to the device of its inputs with .to(device)."""
+
+    def __init__(self, alpha, reg=False, **solver_kw):
+        super().__init__()
+        self.alpha = torch.nn.Parameter(torch.as_tensor(alpha, dtype=torch.float64).clone())
+        self.reg = bool(reg)
+        self.solver_kw = dict(solver_kw)
+
+    def forward(self, f):
+        return sumregs_denoise(f, self.alpha, reg=self.reg, **self.solver_kw)

@@ -231,6 +231,12 @@ int bpltv_sumregs_default_params(bpltv_params *p);
 int bpltv_sumregs_denoise(bpltv_t *h, const double *alpha, int am, int an, const bpltv_params *p, double *u_out);
 int bpltv_sumregs_evaluate(bpltv_t *h, const double *alpha, int am, int an, double delta, const bpltv_params *p,
                            double *u_out, double *cost_out, double *grad_out);
+/* bpltv_sumregs_denoise with the parameter already resident in HBM (d_alpha: device pointer, 3*am*an doubles in the
+ * layout above) and the result left there (bpltv_u_device / bpltv_copy_u_device), as bpltv_denoise_device is for the
+ * TV model.  The entries are checked on the device (finite, >= 0; > 0 when params.rho != 0) before anything of the
+ * handle changes: a rejected parameter returns BPLTV_E_ARG and leaves the handle, its last result and
+ * bpltv_duality_gap as they were.  Single-device handles (multi: BPLTV_E_UNSUPPORTED beyond one shard). */
+int bpltv_sumregs_denoise_device(bpltv_t *h, const double *d_alpha, int am, int an, const bpltv_params *p);
 
 /* Sharded form: this handle's images only.  partial_out (host, 1 + am*an doubles) receives
  * [cost, grad...] summed over the handle's O images; the caller all-reduces it across shards
@@ -290,6 +296,28 @@ int bpltv_vjp(bpltv_t *h, const double *u, const double *alpha, int am, int an, 
  * beyond one shard). */
 int bpltv_vjp_device(bpltv_t *h, const double *d_u, const double *d_alpha, int am, int an, int reg,
                      const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alpha);
+
+/* Vector-Jacobian product of u = sumregs_denoise(f, x) for a cotangent gu = dL/du: the adjoint system of
+ * bpltv_sumregs_evaluate's gradient with the right-hand side
+ *     reg = 0 (sumregs_gradient):      gu        grad_f_out =  p
+ *     reg = 1 (sumregs_gradient_reg): -gu        grad_f_out = -p
+ * solved once for the adjoint state p; grad_alpha_out = the parameter gradient computed from the same p.  So
+ * gu = u - ubar gives bitwise the grad_out of bpltv_sumregs_evaluate (reg = !(delta > delta_t)) on the same u.
+ * With reg = 1 and a patch or map parameter the reference's system I + sum_k diag(x_k) K_k is row-scaled, not
+ * symmetric, and its gradient uses A^-1, not A^-T: both outputs follow it, so grad_f_out is
+ * then not the transpose of the forward linearisation.  Such a parameter needs every entry > 0.
+ * Argument lists as bpltv_vjp's; alpha and grad_alpha_out: 3*am*an doubles in bpltv_sumregs_evaluate's layout.  alpha
+ * is checked as bpltv_sumregs_denoise checks it (finite, >= 0), gu must be finite; params.reserved[4] = 2 (block
+ * cyclic reduction) returns BPLTV_E_UNSUPPORTED.  Every rejection comes before anything of the handle changes.  The
+ * parameter is staged apart: the last solve, bpltv_u_device, bpltv_duality_gap and the captured graphs stay as they
+ * were (bpltv_per_image does not).  stats report the adjoint.  dtype = 32 handles too (the model is Float64 there).
+ * Multi-device handles split the images as bpltv_vjp does. */
+int bpltv_sumregs_vjp(bpltv_t *h, const double *u, const double *alpha, int am, int an, int reg, const bpltv_params *p,
+                      const double *gu, double *grad_f_out, double *grad_alpha_out);
+/* The same with every array in HBM; the parameter and the cotangent are checked on the device.  Single-device handles
+ * (multi: BPLTV_E_UNSUPPORTED beyond one shard). */
+int bpltv_sumregs_vjp_device(bpltv_t *h, const double *d_u, const double *d_alpha, int am, int an, int reg,
+                             const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alpha);
 
 /* Forward-only parameter sweep: generate_cost / generate_2d_cost (src/BPLDenoising.jl:92-111,
  * :136-158) evaluate cost(alpha_k) = 0.5*||TVDenoise(f, alpha_k) - ubar||^2 for a range of parameters,

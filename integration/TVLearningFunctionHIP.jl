@@ -4,7 +4,7 @@
 # NOT EXECUTED HERE: Julia is not available in the build image; the same entry points are exercised through
 # bpldenoising_amd/_lib.py (ctypes) by the test suite.
 # Same exports as src/TVLearningFunctionVec.jl:6
-export tv_op_learning_function, denoise, sumregs_learning_function, tv_vjp
+export tv_op_learning_function, denoise, sumregs_learning_function, tv_vjp, sumregs_vjp
 
 const libbpltv = "libbpltv"            # on LD_LIBRARY_PATH, or an absolute path
 
@@ -198,6 +198,21 @@ function tv_vjp(h::BpltvHandle, u::Array{Float64,3}, α, ḡ::Array{Float64,3}; 
         (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Ref{BpltvParams}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
         h.ptr, u, a, am, an, reg ? 1 : 0, p, ḡ, gf, ga))
     return gf, α isa Real ? ga[1] : reshape(ga, size(α))
+end
+
+# The same for u = sumregs_denoise(f, x) (include/bpltv.h, bpltv_sumregs_vjp): x a 3-vector or an m x n x 3 array, passed
+# as its column-major memory as in sumregs_learning_function; dL/dx has the shape of x.  ḡ = u - ū gives
+# sumregs_learning_function's gradient bit for bit; reg = true is its sumregs_gradient_reg branch (Δ <= Δt).
+function sumregs_vjp(h::BpltvHandle, u::Array{Float64,3}, x::Union{AbstractVector{Float64},AbstractArray{Float64,3}},
+                     ḡ::Array{Float64,3}; reg = false, kwargs...)
+    a = Array{Float64}(x)
+    am, an = x isa AbstractVector ? (1, 1) : (size(x, 1), size(x, 2))
+    gf = similar(u); ga = zeros(size(a))
+    p = Ref(default_params(; kwargs...))
+    GC.@preserve u a ḡ gf ga bpltv_check(h, ccall((:bpltv_sumregs_vjp, libbpltv), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Ref{BpltvParams}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        h.ptr, u, a, am, an, reg ? 1 : 0, p, ḡ, gf, ga))
+    return gf, ga
 end
 
 # test / measurement aids of a handle (include/bpltv.h, bpltv_set_option), e.g. set_option(h, "sweep_split", 2)
