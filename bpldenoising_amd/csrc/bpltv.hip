@@ -177,9 +177,11 @@ struct GraphKey {
     const void* state;
     const void* tab;   // step table (one per (maxiter, steps, L, dual-first shift): TabKey)
     int from_state;    // 1: the sequence starts from a prepared state (params.init / order), not from x = f, y = 0
+    const void* alpha; // the parameter the launches read: a sweep's blocks and the dataset's parameter are different
+                       // buffers, while a float handle's state (f32_state) is the same for both contexts
     bool operator<(const GraphKey& o) const {
-        return std::tie(maxiter, T, variant, am, an, chains, rho, tau0, sigma0, accel, dbg, nimg, state, tab, from_state) <
-               std::tie(o.maxiter, o.T, o.variant, o.am, o.an, o.chains, o.rho, o.tau0, o.sigma0, o.accel, o.dbg, o.nimg, o.state, o.tab, o.from_state);
+        return std::tie(maxiter, T, variant, am, an, chains, rho, tau0, sigma0, accel, dbg, nimg, state, tab, from_state, alpha) <
+               std::tie(o.maxiter, o.T, o.variant, o.am, o.an, o.chains, o.rho, o.tau0, o.sigma0, o.accel, o.dbg, o.nimg, o.state, o.tab, o.from_state, o.alpha);
     }
 };
 
@@ -302,6 +304,11 @@ struct bpltv_handle {
     double* d_sweep[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
     size_t sweep_cap = 0;  // images
     double* d_sweep_cost = nullptr;
+    // the parameter of the current solve context: nullptr = the dataset's d_alpha; bpltv_sweep swaps in its own K blocks
+    // (d_sweep_alpha, with the float twin f32_sweep_alpha), so that d_alpha and the last result stay as they were
+    const double* cur_alpha = nullptr;
+    double* d_sweep_alpha = nullptr;
+    size_t sweep_alpha_cap = 0;
     int result_buf = 0;  // which state set holds the last result
     bool has_result = false;
     bool has_per_image = false;  // d_perimg (cost) and d_red (gradient partials) hold the last evaluate's rows
@@ -321,8 +328,8 @@ struct bpltv_handle {
     int dtype = 64;
     float* f32_state[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
     size_t f32_state_cap = 0;      // images
-    float *f32_f = nullptr, *f32_alpha = nullptr;
-    size_t f32_alpha_cap = 0;
+    float *f32_f = nullptr, *f32_alpha = nullptr, *f32_sweep_alpha = nullptr;
+    size_t f32_alpha_cap = 0, f32_sweep_alpha_cap = 0;
     bool f32_f_valid = false;
     std::map<TabKey, float*> tabs32;
     std::map<GraphKey, std::vector<hipGraphExec_t>> graphs;  // one exec per chain
@@ -524,14 +531,20 @@ int f32_prepare(bpltv_t* h) {
         cvt_to_f32(h, h->d_f, h->f32_f, h->tot);
         h->f32_f_valid = true;
     }
-    if (h->f32_alpha_cap < h->alpha_cap) {
+    // the float twin of the context's parameter: the dataset's, or a sweep's blocks
+    const bool sweep = h->cur_alpha != nullptr;
+    float*& a32 = sweep ? h->f32_sweep_alpha : h->f32_alpha;
+    size_t& cap32 = sweep ? h->f32_sweep_alpha_cap : h->f32_alpha_cap;
+    const size_t cap = sweep ? h->sweep_alpha_cap : h->alpha_cap;
+    if (cap32 < cap) {
         drop_graphs(h);
-        if (h->f32_alpha) HIPCHK(h, hipFree(h->f32_alpha));
-        h->f32_alpha = nullptr;
-        HIPCHK(h, hipMalloc((void**)&h->f32_alpha, h->alpha_cap * sizeof(float)));
-        h->f32_alpha_cap = h->alpha_cap;
+        if (a32) HIPCHK(h, hipFree(a32));
+        a32 = nullptr;
+        cap32 = 0;
+        HIPCHK(h, hipMalloc((void**)&a32, cap * sizeof(float)));
+        cap32 = cap;
     }
-    cvt_to_f32(h, h->d_alpha, h->f32_alpha, h->alpha_cap);
+    cvt_to_f32(h, sweep ? h->cur_alpha : h->d_alpha, a32, cap);
     HIPCHK(h, hipGetLastError());
     return BPLTV_OK;
 }
@@ -540,8 +553,11 @@ inline double* pdhg_state(bpltv_t* h, int set, int c) {
     return h->dtype == 32 ? reinterpret_cast<double*>(h->f32_state[set][c]) : h->cur_state[set][c];
 }
 inline const double* pdhg_f(bpltv_t* h) { return h->dtype == 32 ? reinterpret_cast<const double*>(h->f32_f) : h->d_f; }
+// the parameter of the current solve context (Float64): the dataset's d_alpha, or a sweep's blocks
+inline const double* ctx_alpha(const bpltv_t* h) { return h->cur_alpha ? h->cur_alpha : h->d_alpha; }
 inline const double* pdhg_alpha(bpltv_t* h) {
-    return h->dtype == 32 ? reinterpret_cast<const double*>(h->f32_alpha) : h->d_alpha;
+    if (h->dtype == 32) return reinterpret_cast<const double*>(h->cur_alpha ? h->f32_sweep_alpha : h->f32_alpha);
+    return ctx_alpha(h);
 }
 // the solve's result (set `buf`) widened into the double state buffers
 int f32_widen(bpltv_t* h, int buf) {
@@ -645,14 +661,16 @@ int upload_alpha_device(bpltv_t* h, const double* d_alpha, int am, int an, const
 }
 
 // Region, fusion depth and launch chains of one solve: plan_pdhg (tiling.hpp -- plain C++, fuzzed under the sanitizers
-// by tools/plan_host_check.cpp) over the geometry of the variant table above.
-int make_plan(bpltv_t* h, const bpltv_params& p, Plan* pl) {
+// by tools/plan_host_check.cpp) over the geometry of the variant table above.  nimg: problems of the solve (-1: the
+// current solve context's).
+int make_plan(bpltv_t* h, const bpltv_params& p, Plan* pl, int nimg = -1) {
     static const std::vector<PlanVariant> geom = [] {
         std::vector<PlanVariant> g;
         for (const Variant& V : kVariants) g.push_back(PlanVariant{V.RI, V.RJ, V.tiles_per_block, V.min_image, V.tmax});
         return g;
     }();
-    PlanRequest q{h->M, h->N, h->cur_nimg, h->ncu, p.maxiter, p.tile_iters, p.reserved[0], p.reserved[1]};
+    if (nimg < 0) nimg = h->cur_nimg;
+    PlanRequest q{h->M, h->N, nimg, h->ncu, p.maxiter, p.tile_iters, p.reserved[0], p.reserved[1]};
     const int rc = plan_pdhg(q, geom.data(), (int)geom.size(), pl);
     switch (rc) {
         case PLAN_OK: return BPLTV_OK;
@@ -662,7 +680,7 @@ int make_plan(bpltv_t* h, const bpltv_params& p, Plan* pl) {
             return set_err(h, BPLTV_E_ARG, "kernel variant %d needs an image of at least %dx%d pixels", p.reserved[0], V.RI, V.RJ);
         }
         case PLAN_E_TILE_ITERS: return set_err(h, BPLTV_E_ARG, "tile_iters must be >= 1");
-        case PLAN_E_GRID: return set_err(h, BPLTV_E_UNSUPPORTED, "%d problems of %dx%d pixels need more than 2^31 tiles per launch", h->cur_nimg, h->M, h->N);
+        case PLAN_E_GRID: return set_err(h, BPLTV_E_UNSUPPORTED, "%d problems of %dx%d pixels need more than 2^31 tiles per launch", nimg, h->M, h->N);
         default: return set_err(h, BPLTV_E_ARG, "cannot tile %dx%d with T=%d", h->M, h->N, pl->T);
     }
 }
@@ -951,7 +969,7 @@ int run_pdhg(bpltv_t* h, const bpltv_params& p) {
     const unsigned gtot = (unsigned)((total + 255) / 256);
     HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     if (from_state) {
-        hipLaunchKernelGGL(pdhg_init_kernel, dim3(gtot), dim3(256), 0, h->stream, h->d_f, h->d_alpha, h->last_am, h->last_an,
+        hipLaunchKernelGGL(pdhg_init_kernel, dim3(gtot), dim3(256), 0, h->stream, h->d_f, ctx_alpha(h), h->last_am, h->last_an,
                            h->M, h->N, h->O, h->cur_astride, total, p.init ? 1 : 0, p.order ? 1 : 0,
                            p.sigma0 / opnorm_of(p, 8.0), p.rho, h->cur_state[1][0], h->cur_state[1][1], h->cur_state[1][2]);
         HIPCHK(h, hipGetLastError());
@@ -960,7 +978,7 @@ int run_pdhg(bpltv_t* h, const bpltv_params& p) {
     if (!chunked) {
         bool done = main_iters == 0;
         if (p.use_graph && !done) {
-            GraphKey key{main_iters, pl.T, pl.variant, h->last_am, h->last_an, pl.chains, p.rho, p.tau0, p.sigma0, p.accel ? 1 : 0, p.reserved[3] | ((p.reserved[2] & 3) << 16), h->cur_nimg, (const void*)pdhg_state(h, 0, 0), (const void*)d_tab, from_state ? 1 : 0};
+            GraphKey key{main_iters, pl.T, pl.variant, h->last_am, h->last_an, pl.chains, p.rho, p.tau0, p.sigma0, p.accel ? 1 : 0, p.reserved[3] | ((p.reserved[2] & 3) << 16), h->cur_nimg, (const void*)pdhg_state(h, 0, 0), (const void*)d_tab, from_state ? 1 : 0, (const void*)pdhg_alpha(h)};
             auto it = h->graphs.find(key);
             const int nl = (main_iters + pl.T - 1) / pl.T;
             if (it == h->graphs.end() && h->graphs.size() >= 16) {  // bounded cache
@@ -2824,7 +2842,8 @@ int bpltv_destroy(bpltv_t* h) {
             if (h->f32_state[s][c]) (void)hipFree(h->f32_state[s][c]);
     if (h->f32_f) (void)hipFree(h->f32_f);
     if (h->f32_alpha) (void)hipFree(h->f32_alpha);
-    void* ptrs[] = {h->d_ubar, h->d_f, h->d_alpha, h->d_partial, h->d_red, h->d_perimg, h->d_scalar, h->d_coef,
+    if (h->f32_sweep_alpha) (void)hipFree(h->f32_sweep_alpha);
+    void* ptrs[] = {h->d_ubar, h->d_f, h->d_alpha, h->d_sweep_alpha, h->d_partial, h->d_red, h->d_perimg, h->d_scalar, h->d_coef,
                     h->d_band4, h->d_bcr, h->d_L, h->d_invF, h->d_invB, h->d_L1, h->d_dump, h->d_Lm, h->d_spill, h->d_p, h->d_r, h->d_gpix, h->d_resn, h->d_fail, h->d_u2, h->d_ubar2,
                     h->d_gf2, h->d_vjp};
     for (void* p : ptrs)
@@ -3169,16 +3188,34 @@ int bpltv_sumregs_vjp_device(bpltv_t* h, const double* d_u, const double* d_alph
 int bpltv_sweep(bpltv_t* h, const double* alphas, int K, int am, int an, const bpltv_params* pp, double* cost_out,
                 double* u_out) {
     if (!h) return BPLTV_E_ARG;
-    if (h->multi) return multi_sweep(h, alphas, K, am, an, pp, cost_out, u_out);
     if (!alphas || !cost_out || K < 1) return set_err(h, BPLTV_E_ARG, "sweep: null pointer or K < 1");
     if (am < 1 || an < 1 || am > h->M || an > h->N) return set_err(h, BPLTV_E_ARG, "sweep: bad parameter shape %dx%d", am, an);
+    bpltv_params p = resolve(pp);
+    // Everything run_pdhg would reject is checked before anything of the handle changes (its buffers included): a
+    // rejected sweep leaves the dataset context -- d_alpha, its shape and minimum, the last result -- as it was.
+    const size_t npar = (size_t)am * an;
+    double amin = alphas[0];
+    for (size_t e = 0; e < (size_t)K * npar; ++e) {
+        if (!std::isfinite(alphas[e]) || alphas[e] < 0.0)
+            return set_err(h, BPLTV_E_ARG, "sweep: alphas[%zu] = %g: parameters must be finite and >= 0", e, alphas[e]);
+        if (alphas[e] < amin) amin = alphas[e];
+    }
+    if (p.rho != 0.0 && !(amin > 0.0))
+        return set_err(h, BPLTV_E_ARG, "sweep: rho != 0 divides by alpha: every parameter entry must be > 0 (min = %g)", amin);
+    if (h->multi) return multi_sweep(h, alphas, K, am, an, pp, cost_out, u_out);
     if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "bpltv_set_data has not been called");
     WallTimer wt;
     HIPCHK(h, hipSetDevice(h->device));
-    bpltv_params p = resolve(pp);
     if (int prc = check_params(h, p)) return prc;
+    if (p.maxiter < 0) return set_err(h, BPLTV_E_ARG, "maxiter < 0");
+    const size_t nimg = (size_t)K * h->O;
+    {
+        Plan pl;
+        if (int rc = make_plan(h, p, &pl, (int)nimg)) return rc;
+    }
+    if ((p.init != 0 || p.order != 0) && h->dtype == 32)
+        return set_err(h, BPLTV_E_UNSUPPORTED, "params.init / params.order are implemented for dtype = 64 handles");
     p.check_every = 0;  // the gap kernels address the dataset context only
-    const size_t nimg = (size_t)K * h->O, npar = (size_t)am * an;
     if (h->sweep_cap < nimg) {
         drop_graphs(h);
         for (int s = 0; s < 2; ++s)
@@ -3191,31 +3228,22 @@ int bpltv_sweep(bpltv_t* h, const double* alphas, int K, int am, int an, const b
         HIPCHK(h, hipMalloc((void**)&h->d_sweep_cost, nimg * sizeof(double)));
         h->sweep_cap = nimg;
     }
-    double amin = alphas[0];
-    for (size_t e = 0; e < (size_t)K * npar; ++e) {
-        if (!std::isfinite(alphas[e]) || alphas[e] < 0.0)
-            return set_err(h, BPLTV_E_ARG, "sweep: alphas[%zu] = %g: parameters must be finite and >= 0", e, alphas[e]);
-        if (alphas[e] < amin) amin = alphas[e];
-    }
-    h->alpha_min = amin;
-    // all K parameter blocks live in the alpha buffer; problem k*O + i uses block k and image i
-    if (h->alpha_cap < K * npar) {
-        drop_graphs(h);
-        int rc = ensure(h, &h->d_alpha, &h->alpha_cap, K * npar);
-        if (rc) return rc;
-    }
-    HIPCHK(h, hipMemcpyAsync(h->d_alpha, alphas, K * npar * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    h->last_am = am;
-    h->last_an = an;
-    h->cur_state = h->d_sweep;
-    h->cur_nimg = (int)nimg;
-    h->cur_astride = (int)npar;
-    int rc = run_pdhg(h, p);
+    // the K parameter blocks live in the sweep's own buffer; problem k*O + i uses block k and image i
+    if (h->sweep_alpha_cap < K * npar) drop_graphs(h);   // captured launches hold the old pointer
+    int rc = ensure(h, &h->d_sweep_alpha, &h->sweep_alpha_cap, K * npar);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_sweep_alpha, alphas, K * npar * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    // the sweep's solve context; the dataset context comes back whatever run_pdhg returns
+    const int am0 = h->last_am, an0 = h->last_an, rb0 = h->result_buf;
+    const double amin0 = h->alpha_min;
+    const bool has0 = h->has_result, last0 = h->last_is_sr;
+    h->cur_state = h->d_sweep; h->cur_nimg = (int)nimg; h->cur_astride = (int)npar; h->cur_alpha = h->d_sweep_alpha;
+    h->last_am = am; h->last_an = an; h->alpha_min = amin;
+    rc = run_pdhg(h, p);
     const int rb = h->result_buf;
-    h->cur_state = h->d_state;
-    h->cur_nimg = h->O;
-    h->cur_astride = 0;
-    h->has_result = false;  // the default context holds no result of this call
+    h->cur_state = h->d_state; h->cur_nimg = h->O; h->cur_astride = 0; h->cur_alpha = nullptr;
+    h->last_am = am0; h->last_an = an0; h->alpha_min = amin0;
+    h->result_buf = rb0; h->has_result = has0; h->last_is_sr = last0;
     if (rc) return rc;
     // loss of every problem against ubar[img % O], then summed per parameter on the host
     const int nblk = 16;

@@ -324,7 +324,11 @@ int bpltv_sumregs_vjp_device(bpltv_t *h, const double *d_u, const double *d_alph
  * one solve after the other.  Here the K parameter blocks (each am x an, column major, K*am*an
  * doubles) times the O resident images form ONE batch of K*O independent ROF problems -- the second
  * data-parallel axis that fills a GPU even with a single image.  cost_out: K doubles; u_out: NULL
- * or K*M*N*O doubles (parameter-major).  Use maxiter = 10000 for the TVDenoise setting.
+ * or K*M*N*O doubles (parameter-major).  Use maxiter = 10000 for the TVDenoise setting.  Every entry must be finite
+ * and >= 0, and > 0 when p->rho != 0; a rejected call (those entries, the kernel plan, p->init / p->order on a dtype = 32
+ * handle) returns an error and leaves the handle as it was.  check_every / gap_tol are ignored (maxiter iterations).  The
+ * blocks live in a parameter buffer of the sweep's own, so the last solve's result (bpltv_u_device, bpltv_duality_gap)
+ * stays that of the last denoise / evaluate.
  * Multi-device handles split whichever axis leaves the smaller largest share per device: the images (device k solves
  * K x O_k problems on the shard it already holds) or the K parameter blocks (device r solves K_r x O problems on a
  * REPLICA -- a second, whole copy of the dataset made on every requested device at the first such sweep, filled from

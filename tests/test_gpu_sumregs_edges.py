@@ -13,8 +13,9 @@ for gradient, 1e-7 for gradient_reg; between factorisations 1e-6 / 1e-9; bitwise
 image groups, deterministic shards of a patch parameter).
 
 Rejected calls (rho > 0 with a zero entry, the TV kernel plan, init / order or an unknown variant on this model, block
-cyclic reduction in its evaluate, gradient_reg with an array parameter that has a zero entry in either model's evaluate)
-leave the handle as it was: duality gap, iteration count, and the next solve."""
+cyclic reduction in its evaluate, gradient_reg with an array parameter that has a zero entry in either model's evaluate;
+a TV sweep with rho > 0 and a zero entry, an unknown variant, or init on a float handle) leave the handle as it was:
+duality gap, iteration count, and the next solve."""
 import numpy as np
 import pytest
 from conftest import synth_batch
@@ -375,8 +376,9 @@ def test_shards_patch_and_map_parameters(gpu_solver_cls, devices):
 # ---------------------------------------------------------------------------------------------------------------------
 # Rejected calls leave the handle as it was
 # ---------------------------------------------------------------------------------------------------------------------
-def _bad_calls(M, N):
-    """(name, call) of every condition that used to be checked after the parameter upload."""
+def _bad_calls(M, N, dtype=64):
+    """(name, call) of every condition that used to be checked after the parameter upload (or, in a TV sweep, after
+    the sweep's blocks replaced the handle's parameter)."""
     a0 = _map(N, M, seed=17)
     a0[1, 3, 4] = 0.0                                  # one zero entry: fine without rho, rejected with rho
     p0 = P22.copy()
@@ -385,7 +387,9 @@ def _bad_calls(M, N):
     t0[5, 6] = 0.0
     tp0 = np.array([[0.05, 0.0, 0.04], [0.03, 0.06, 0.02]])
     big = 0.05 * np.ones((3, N, M))                    # a map: would reallocate the parameter buffer
-    return [
+    sw0 = 0.03 + 0.05 * np.random.default_rng(21).random((4, N, M))   # four map blocks of a TV sweep
+    sw0[2, 7, 3] = 0.0
+    calls = [
         ("tv_rho_zero", lambda s: s.denoise(t0, maxiter=20, rho=0.1)),
         ("tv_eval_rho_zero", lambda s: s.evaluate(t0, 0.1, maxiter=20, rho=0.1)),
         ("tv_variant", lambda s: s.denoise(t0, maxiter=20, variant=99)),
@@ -399,7 +403,12 @@ def _bad_calls(M, N):
         ("sr_eval_bcr", lambda s: s.sumregs_evaluate(big, 0.1, maxiter=20, adjoint_method="bcr")),
         ("tv_eval_reg_map_zero", lambda s: s.evaluate(t0, 0.0, maxiter=20)),
         ("tv_eval_reg_patch_zero", lambda s: s.evaluate(tp0, 0.0, maxiter=20)),
+        ("tv_sweep_rho_zero", lambda s: s.sweep(sw0, maxiter=20, rho=0.1)),
+        ("tv_sweep_variant", lambda s: s.sweep(big, maxiter=20, variant=99)),
     ]
+    if dtype == 32:   # init / order: Float64 handles only
+        calls.append(("tv_sweep_init", lambda s: s.sweep(sw0 + 0.01, maxiter=20, init=1)))
+    return calls
 
 
 @pytest.mark.parametrize("dtype", [64, 32])
@@ -407,7 +416,8 @@ def _bad_calls(M, N):
 def test_rejected_calls_leave_the_handle_as_it_was(gpu_solver_cls, dtype, first):
     """Every check that used to run after the parameter upload (rho > 0 with a zero entry; the TV kernel plan; init /
     order, the kernel variant and block cyclic reduction on the sum-of-regularisers model; gradient_reg with an array
-    parameter that has a zero entry, in both models' evaluate) now runs before it: after the BpltvError, duality_gap() and stats()["iterations"] are those of the last solve, bit for bit, and the
+    parameter that has a zero entry, in both models' evaluate; a TV sweep's rho, variant and float-handle init checks)
+    now runs before it: after the BpltvError, duality_gap() and stats()["iterations"] are those of the last solve, bit for bit, and the
     next accepted solve is bitwise a fresh handle's.  f32 handles solve the TV model only in single precision; the
     sum-of-regularisers model is Float64 on either handle."""
     from bpldenoising_amd._lib import BpltvError
@@ -423,7 +433,7 @@ def test_rejected_calls_leave_the_handle_as_it_was(gpu_solver_cls, dtype, first)
     solve(s)
     g0 = s.duality_gap()
     assert np.all(np.isfinite(g0)) and np.all(g0 > 0)
-    for name, call in _bad_calls(M, N):
+    for name, call in _bad_calls(M, N, dtype):
         with pytest.raises(BpltvError):
             call(s)
         assert np.array_equal(s.duality_gap(), g0), name
