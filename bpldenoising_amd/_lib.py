@@ -90,6 +90,11 @@ SYMBOLS = {
     "bpltv_vjp": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
     "bpltv_vjp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_void_p, C.c_void_p,
                                    C.c_void_p]),
+    "bpltv_denoise_each": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp]),
+    "bpltv_denoise_each_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, _PP]),
+    "bpltv_vjp_each": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
+    "bpltv_vjp_each_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_void_p,
+                                        C.c_void_p, C.c_void_p]),
     "bpltv_sumregs_vjp": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
     "bpltv_sumregs_vjp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),

@@ -34,8 +34,8 @@ constexpr double ADJ_GAMMA = 1e8;      // TVLearningFunctionVec.jl:142,197
 // not depend on COT.
 template <bool COT>
 __device__ __forceinline__ void adj_setup_body(const double* __restrict__ u, const double* __restrict__ src,
-                                               const double* __restrict__ alpha, int am, int an, int M, int N,
-                                               int O, int patch, int reg, double kappa_act, AdjCoef C) {
+                                               const double* __restrict__ alpha, int am, int an, int astride, int M,
+                                               int N, int O, int patch, int reg, double kappa_act, AdjCoef C) {
     const size_t npx = (size_t)M * N;
     const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (q >= npx * O) return;
@@ -45,7 +45,8 @@ __device__ __forceinline__ void adj_setup_body(const double* __restrict__ u, con
     const double g1 = (i < M - 1) ? u[q + 1] - uk : 0.0;
     const double g2 = (j < N - 1) ? u[q + M] - uk : 0.0;
     const double ng = sqrt(g1 * g1 + g2 * g2);
-    const double a = alpha_at(alpha, am, an, M, N, i, j);
+    // astride 0: one parameter for every image; am*an: image q / npx reads its own block (bpltv_vjp_each)
+    const double a = alpha_at(alpha + (q / npx) * (size_t)astride, am, an, M, N, i, j);
     double t1 = 0.0, t2 = 0.0, c = 0.0, kap = 0.0, h1 = 0.0, h2 = 0.0, rhs, s = 1.0;
     if (!reg) {
         if (ng < ADJ_ACT_TOL) {
@@ -77,20 +78,20 @@ __device__ __forceinline__ void adj_setup_body(const double* __restrict__ u, con
 
 __global__ __launch_bounds__(256) void adj_setup_kernel(const double* __restrict__ u,
                                                         const double* __restrict__ ubar,
-                                                        const double* __restrict__ alpha, int am, int an,
+                                                        const double* __restrict__ alpha, int am, int an, int astride,
                                                         int M, int N, int O, int patch, int reg,
                                                         double kappa_act, AdjCoef C) {
-    adj_setup_body<false>(u, ubar, alpha, am, an, M, N, O, patch, reg, kappa_act, C);
+    adj_setup_body<false>(u, ubar, alpha, am, an, astride, M, N, O, patch, reg, kappa_act, C);
 }
 
 // The same coefficients with the right-hand side of a vector-Jacobian product: gu, or -gu (/ s for an array
 // parameter) for gradient_reg.
 __global__ __launch_bounds__(256) void adj_setup_cot_kernel(const double* __restrict__ u,
                                                             const double* __restrict__ gu,
-                                                            const double* __restrict__ alpha, int am, int an,
+                                                            const double* __restrict__ alpha, int am, int an, int astride,
                                                             int M, int N, int O, int patch, int reg,
                                                             double kappa_act, AdjCoef C) {
-    adj_setup_body<true>(u, gu, alpha, am, an, M, N, O, patch, reg, kappa_act, C);
+    adj_setup_body<true>(u, gu, alpha, am, an, astride, M, N, O, patch, reg, kappa_act, C);
 }
 
 // Element (pixel a) contribution to the node pairs of {a, b=a+1, c=a+M}.
@@ -817,11 +818,13 @@ __global__ __launch_bounds__(256) void finite_check_kernel(const double* __restr
     if (__any(b) && (threadIdx.x & 63) == 0) atomicOr(bad, 1ull);
 }
 
-// calc_adjoint(PatchOp, .): partial[(pa + am*pb)*O + k] = sum of image k's pixel contributions over
-// the patch.  grid (am*an, O); sum_final_kernel then adds the O images of each patch in image order
-// (fixed order -> bitwise reproducible, and every image/patch pair gets its own workgroup).
+// calc_adjoint(PatchOp, .): partial[(pa + am*pb)*pstride + k*kstride] = sum of image k's pixel contributions over
+// the patch.  grid (am*an, O).  pstride = O, kstride = 1: sum_final_kernel then adds the O images of each patch in image
+// order (fixed order -> bitwise reproducible, and every image/patch pair gets its own workgroup); pstride = 1,
+// kstride = am*an: the per-image gradients of bpltv_vjp_each, image-major.
 __global__ __launch_bounds__(256) void patch_sum_kernel(const double* __restrict__ gpix, int M, int N, int O,
-                                                        int am, int an, double* __restrict__ partial) {
+                                                        int am, int an, int pstride, int kstride,
+                                                        double* __restrict__ partial) {
     __shared__ double sh[4];
     const int pa = blockIdx.x % am, pb = blockIdx.x / am, k = blockIdx.y;
     // pixels i with (i*am)/M == pa  <=>  i in [ceil(pa*M/am), ceil((pa+1)*M/am))
@@ -836,7 +839,7 @@ __global__ __launch_bounds__(256) void patch_sum_kernel(const double* __restrict
         s += g[i + (size_t)M * j];
     }
     s = block_sum<256>(s, sh);
-    if (threadIdx.x == 0) partial[(size_t)blockIdx.x * O + k] = s;
+    if (threadIdx.x == 0) partial[(size_t)blockIdx.x * pstride + (size_t)k * kstride] = s;
 }
 
 // Residual statistics per image: out[k*4 + {0: ||r||^2, 1: ||rhs||^2, 2: r^T D^-1 r, 3: rhs^T D^-1 rhs}],

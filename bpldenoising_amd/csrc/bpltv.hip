@@ -179,9 +179,11 @@ struct GraphKey {
     int from_state;    // 1: the sequence starts from a prepared state (params.init / order), not from x = f, y = 0
     const void* alpha; // the parameter the launches read: a sweep's blocks and the dataset's parameter are different
                        // buffers, while a float handle's state (f32_state) is the same for both contexts
+    int istride;       // PdhgArgs::istride: a shared parameter and one block per image (bpltv_denoise_each) live in the
+                       // same buffer, d_alpha
     bool operator<(const GraphKey& o) const {
-        return std::tie(maxiter, T, variant, am, an, chains, rho, tau0, sigma0, accel, dbg, nimg, state, tab, from_state, alpha) <
-               std::tie(o.maxiter, o.T, o.variant, o.am, o.an, o.chains, o.rho, o.tau0, o.sigma0, o.accel, o.dbg, o.nimg, o.state, o.tab, o.from_state, o.alpha);
+        return std::tie(maxiter, T, variant, am, an, chains, rho, tau0, sigma0, accel, dbg, nimg, state, tab, from_state, alpha, istride) <
+               std::tie(o.maxiter, o.T, o.variant, o.am, o.an, o.chains, o.rho, o.tau0, o.sigma0, o.accel, o.dbg, o.nimg, o.state, o.tab, o.from_state, o.alpha, o.istride);
     }
 };
 
@@ -315,6 +317,8 @@ struct bpltv_handle {
     double* d_alpha = nullptr;
     size_t alpha_cap = 0;
     int last_am = 1, last_an = 1;
+    int alpha_istride = 0;        // 0: d_alpha holds one parameter for every image; am*an: O blocks, one per image
+                                  // (bpltv_denoise_each), which the PDHG and gap kernels of the dataset context address
     double alpha_min = 0.0;       // smallest entry of the last uploaded parameter (validated on the host)
     double* d_partial = nullptr;  // [1 + am*an]
     size_t partial_cap = 0;
@@ -559,6 +563,8 @@ inline const double* pdhg_alpha(bpltv_t* h) {
     if (h->dtype == 32) return reinterpret_cast<const double*>(h->cur_alpha ? h->f32_sweep_alpha : h->f32_alpha);
     return ctx_alpha(h);
 }
+// PdhgArgs::istride of the current solve context: a sweep's blocks are addressed by astride alone
+inline int pdhg_istride(const bpltv_t* h) { return h->cur_alpha ? 0 : h->alpha_istride; }
 // the solve's result (set `buf`) widened into the double state buffers
 int f32_widen(bpltv_t* h, int buf) {
     for (int c = 0; c < 3; ++c) cvt_to_f64(h, h->f32_state[buf][c], h->cur_state[buf][c], (size_t)h->cur_nimg * h->npx);
@@ -582,12 +588,13 @@ inline int pre_gradient(double delta, const bpltv_params& p, int am, int an) {
 }
 
 // solve (nullable): the parameters of the PDHG solve the upload is for -- solve_precheck runs on them before anything of
-// the handle changes.
-int upload_alpha(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* solve = nullptr, int what = PRE_TV) {
+// the handle changes.  blocks: 1, or O for bpltv_denoise_each (O blocks of am*an doubles, image k reads block k).
+int upload_alpha(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* solve = nullptr, int what = PRE_TV,
+                 int blocks = 1) {
     if (!alpha || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "alpha: null pointer or empty shape");
     if (am > h->M || an > h->N)
         return set_err(h, BPLTV_E_ARG, "alpha shape %dx%d exceeds image %dx%d", am, an, h->M, h->N);
-    const size_t need = (size_t)am * an;
+    const size_t need = (size_t)blocks * am * an;
     // The reference is defined for alpha >= 0 (alpha = 0: u = f); NaN/Inf or a negative ball radius has no
     // meaning on this path and would propagate silently through 5000 iterations.
     double amin = alpha[0];
@@ -612,6 +619,7 @@ int upload_alpha(bpltv_t* h, const double* alpha, int am, int an, const bpltv_pa
     h->last_am = am;
     h->last_an = an;
     h->last_slices = 1;
+    h->alpha_istride = blocks > 1 ? am * an : 0;
     return BPLTV_OK;
 }
 
@@ -620,15 +628,16 @@ void drop_sr_graphs(bpltv_t* h);
 // The same for a parameter that already lives in HBM (bpltv_denoise_device, bpltv_sumregs_denoise_device): checked in
 // place by alpha_check_kernel (one 16-byte read back), then copied device to device.  Nothing of the handle changes
 // before the array is accepted: a rejected parameter leaves d_alpha, its shape and alpha_min -- and so the duality gap of
-// the last solve -- as they were.  what & PRE_SR: the sum-of-regularisers model, three slices of am*an doubles.
+// the last solve -- as they were.  what & PRE_SR: the sum-of-regularisers model, three slices of am*an doubles.  blocks:
+// 1, or O for bpltv_denoise_each_device (TV model).
 int upload_alpha_device(bpltv_t* h, const double* d_alpha, int am, int an, const bpltv_params* solve = nullptr,
-                        int what = PRE_TV) {
+                        int what = PRE_TV, int blocks = 1) {
     const bool sr = (what & PRE_SR) != 0;
     if (!d_alpha || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "alpha: null pointer or empty shape");
     if (am > h->M || an > h->N)
         return set_err(h, BPLTV_E_ARG, sr ? "alpha shape %dx%dx3 exceeds image %dx%d" : "alpha shape %dx%d exceeds image %dx%d",
                        am, an, h->M, h->N);
-    const size_t need = (size_t)(sr ? 3 : 1) * am * an;
+    const size_t need = (size_t)(sr ? 3 : 1) * blocks * am * an;
     unsigned long long* chk_d = reinterpret_cast<unsigned long long*>(h->d_scalar + 2);
     HIPCHK(h, hipMemsetAsync(chk_d, 0xFF, sizeof(unsigned long long), h->stream));
     HIPCHK(h, hipMemsetAsync(chk_d + 1, 0, sizeof(unsigned long long), h->stream));
@@ -657,6 +666,7 @@ int upload_alpha_device(bpltv_t* h, const double* d_alpha, int am, int an, const
     h->last_am = am;
     h->last_an = an;
     h->last_slices = sr ? 3 : 1;
+    h->alpha_istride = blocks > 1 ? am * an : 0;
     return BPLTV_OK;
 }
 
@@ -731,7 +741,7 @@ int build_graphs(bpltv_t* h, const bpltv_params& p, const Plan& pl, const double
             a.f = pdhg_f(h); a.alpha = pdhg_alpha(h); a.tab = d_tab; a.rho = p.rho;
             a.am = h->last_am; a.an = h->last_an;
             a.M = h->M; a.N = h->N; a.O = h->cur_nimg;
-            a.Odata = h->O; a.astride = h->cur_astride;
+            a.Odata = h->O; a.astride = h->cur_astride; a.istride = pdhg_istride(h);
             a.nTi = pl.nTi; a.nTj = pl.nTj; a.halo = pl.T; a.seg = V.RJ;
             a.img0 = lo;
             a.phase = (phased && c == 0) ? h->d_phase : nullptr;
@@ -793,7 +803,7 @@ int enqueue_pdhg(bpltv_t* h, const bpltv_params& p, const Plan& pl, const double
     a.am = h->last_am;
     a.an = h->last_an;
     a.M = h->M; a.N = h->N; a.O = h->cur_nimg;
-    a.Odata = h->O; a.astride = h->cur_astride;
+    a.Odata = h->O; a.astride = h->cur_astride; a.istride = pdhg_istride(h);
     a.nTi = pl.nTi; a.nTj = pl.nTj; a.halo = pl.T; a.seg = V.RJ;
     a.img0 = 0;
     a.ntiles = pl.grid;
@@ -834,7 +844,7 @@ int compute_gap(bpltv_t* h, double* gap_host /*O or null*/, double* gap_max_host
         const int b = h->result_buf;
         hipLaunchKernelGGL(gap_partial_kernel, dim3(nblk, h->O), dim3(256), 0, h->stream, h->d_state[b][0],
                            h->d_state[b][1], h->d_state[b][2], h->d_f, h->d_alpha, h->last_am, h->last_an, h->M,
-                           h->N, h->d_red);
+                           h->N, h->alpha_istride, h->d_red);
     }
     hipLaunchKernelGGL(gap_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, nblk, h->O, h->d_perimg,
                        h->d_scalar);
@@ -970,7 +980,7 @@ int run_pdhg(bpltv_t* h, const bpltv_params& p) {
     HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     if (from_state) {
         hipLaunchKernelGGL(pdhg_init_kernel, dim3(gtot), dim3(256), 0, h->stream, h->d_f, ctx_alpha(h), h->last_am, h->last_an,
-                           h->M, h->N, h->O, h->cur_astride, total, p.init ? 1 : 0, p.order ? 1 : 0,
+                           h->M, h->N, h->O, h->cur_astride, pdhg_istride(h), total, p.init ? 1 : 0, p.order ? 1 : 0,
                            p.sigma0 / opnorm_of(p, 8.0), p.rho, h->cur_state[1][0], h->cur_state[1][1], h->cur_state[1][2]);
         HIPCHK(h, hipGetLastError());
         buf = 1;
@@ -978,7 +988,7 @@ int run_pdhg(bpltv_t* h, const bpltv_params& p) {
     if (!chunked) {
         bool done = main_iters == 0;
         if (p.use_graph && !done) {
-            GraphKey key{main_iters, pl.T, pl.variant, h->last_am, h->last_an, pl.chains, p.rho, p.tau0, p.sigma0, p.accel ? 1 : 0, p.reserved[3] | ((p.reserved[2] & 3) << 16), h->cur_nimg, (const void*)pdhg_state(h, 0, 0), (const void*)d_tab, from_state ? 1 : 0, (const void*)pdhg_alpha(h)};
+            GraphKey key{main_iters, pl.T, pl.variant, h->last_am, h->last_an, pl.chains, p.rho, p.tau0, p.sigma0, p.accel ? 1 : 0, p.reserved[3] | ((p.reserved[2] & 3) << 16), h->cur_nimg, (const void*)pdhg_state(h, 0, 0), (const void*)d_tab, from_state ? 1 : 0, (const void*)pdhg_alpha(h), pdhg_istride(h)};
             auto it = h->graphs.find(key);
             const int nl = (main_iters + pl.T - 1) / pl.T;
             if (it == h->graphs.end() && h->graphs.size() >= 16) {  // bounded cache
@@ -1347,10 +1357,12 @@ void solve_band_lds(bpltv_t* h, double* vec, double* accv) {
 struct GradCtx {
     const double* alpha = nullptr;
     int am = 1, an = 1;
+    int astride = 0;               // 0: one parameter for every image; am*an: image k reads block k (bpltv_vjp_each)
+    bool each = false;             // d_out receives the O per-image parameter gradients (image-major), not their sum
     double alpha_min = 0.0;
     const double* src = nullptr;   // ubar, or gu when cot
     bool cot = false;
-    double* d_out = nullptr;       // am*an parameter gradient, or nullptr: no per-pixel terms, no reduction
+    double* d_out = nullptr;       // am*an parameter gradient (O*am*an when each), or nullptr: no per-pixel terms, no reduction
     double* d_grad_f = nullptr;    // M*N*O input gradient (+-S q), or nullptr
 };
 GradCtx gradient_ctx(const bpltv_t* h, const double* d_ubar, double* d_out) {
@@ -1405,12 +1417,13 @@ int run_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, 
         double *dp = h->d_p + o0, *dr = h->d_r + o0, *dg = h->d_gpix + o0;
         int* dfail = h->d_fail + c0;
         const int gpx = (int)((ctot + 255) / 256);
+        const double* ga = g.alpha + (size_t)c0 * g.astride;   // the group's first image's parameter block
         if (g.cot)
-            hipLaunchKernelGGL(adj_setup_cot_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0, g.alpha, am, an, M,
-                               N, nimg, patch, reg, kact, C);
+            hipLaunchKernelGGL(adj_setup_cot_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0, ga, am, an, g.astride,
+                               M, N, nimg, patch, reg, kact, C);
         else
-            hipLaunchKernelGGL(adj_setup_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0, g.alpha, am, an, M, N,
-                               nimg, patch, reg, kact, C);
+            hipLaunchKernelGGL(adj_setup_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0, ga, am, an, g.astride, M,
+                               N, nimg, patch, reg, kact, C);
         hipLaunchKernelGGL(adj_assemble_kernel, dim3(gpx), dim3(256), 0, h->stream, C, M, N, nimg, band4);
         // factorisation
         const BcrArrays bcr = BcrArrays::carve(h->d_bcr, M, N, nimg, h->bcr_MP);
@@ -1457,13 +1470,19 @@ int run_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, 
     }
     // ... then per parameter, over all images (a vector-Jacobian product may not want the parameter gradient)
     const bool amap = am == M && an == N && !(M == 1 && N == 1);
-    if (g.d_out && amap) {  // pixelwise parameter map: plain sum over images
+    if (g.d_out && g.each) {   // per image, image-major: the pixel maps as they are, or each image's patch sums
+        if (amap)
+            HIPCHK(h, hipMemcpyAsync(g.d_out, h->d_gpix, tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        else
+            hipLaunchKernelGGL(patch_sum_kernel, dim3(am * an, O), dim3(256), 0, h->stream, h->d_gpix, M, N, O, am, an, 1, am * an,
+                               g.d_out);
+    } else if (g.d_out && amap) {  // pixelwise parameter map: plain sum over images
         hipLaunchKernelGGL(map_sum_kernel, dim3((unsigned)((h->npx + 255) / 256)), dim3(256), 0, h->stream, h->d_gpix, h->npx, O,
                            g.d_out);
     } else if (g.d_out) {
         rc = ensure(h, &h->d_red, &h->red_cap, (size_t)am * an * O);
         if (rc) return rc;
-        hipLaunchKernelGGL(patch_sum_kernel, dim3(am * an, O), dim3(256), 0, h->stream, h->d_gpix, M, N, O, am, an,
+        hipLaunchKernelGGL(patch_sum_kernel, dim3(am * an, O), dim3(256), 0, h->stream, h->d_gpix, M, N, O, am, an, O, 1,
                            h->d_red);
         hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, O, am * an, 1.0, g.d_out,
                            (double*)nullptr);
@@ -1602,8 +1621,11 @@ int run_sr_gradient(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, co
 // shape and minimum, the PDHG state and graphs, and so bpltv_u_device and bpltv_duality_gap -- stays as it was.
 // slices: 1 TV (bpltv_vjp), 3 sum of regularisers (bpltv_sumregs_vjp; the parameter is 3*am*an doubles).
 // d_grad_alpha: slices*am*an doubles in HBM or nullptr; d_grad_f: M*N*O doubles in HBM or nullptr; not both nullptr.
+// each (TV model, bpltv_vjp_each): alpha holds O blocks of am*an doubles, image k reads block k, and d_grad_alpha receives
+// the O per-image gradients, image-major.
 int vjp_common(bpltv_t* h, const double* d_u, const double* alpha, bool alpha_dev, int am, int an, int reg,
-               const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alpha, int slices = 1) {
+               const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alpha, int slices = 1,
+               bool each = false) {
     if (!d_u || !alpha || !d_gu) return set_err(h, BPLTV_E_ARG, "vjp: null pointer");
     if (!d_grad_f && !d_grad_alpha) return set_err(h, BPLTV_E_ARG, "vjp: both outputs are NULL");
     if (am < 1 || an < 1 || am > h->M || an > h->N)
@@ -1612,7 +1634,7 @@ int vjp_common(bpltv_t* h, const double* d_u, const double* alpha, bool alpha_de
     bpltv_params p = resolve(pp);
     if (int prc = check_params(h, p)) return prc;
     if (sr && p.reserved[4] == 2) return set_err(h, BPLTV_E_UNSUPPORTED, "block cyclic reduction applies to the TV model only");
-    const size_t P = (size_t)slices * am * an;
+    const size_t P = (size_t)slices * am * an * (each ? h->O : 1);
     double amin = 0.0;
     if (!alpha_dev) {   // as upload_alpha
         amin = alpha[0];
@@ -1646,6 +1668,7 @@ int vjp_common(bpltv_t* h, const double* d_u, const double* alpha, bool alpha_de
     HIPCHK(h, hipMemcpyAsync(d_a, alpha, P * sizeof(double), alpha_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     GradCtx g;
     g.alpha = d_a; g.am = am; g.an = an; g.alpha_min = amin;
+    g.astride = each ? am * an : 0; g.each = each;
     g.src = d_gu; g.cot = true;
     g.d_out = d_grad_alpha; g.d_grad_f = d_grad_f;
     h->has_per_image = false;   // the reduction scratch (d_red) no longer holds the last evaluate's rows
@@ -1736,7 +1759,7 @@ int sr_upload_alpha(bpltv_t* h, const double* alpha, int am, int an, const bpltv
         if (rc) return rc;
     }
     HIPCHK(h, hipMemcpyAsync(h->d_alpha, alpha, need * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    h->last_am = am; h->last_an = an; h->last_slices = 3;
+    h->last_am = am; h->last_an = an; h->last_slices = 3; h->alpha_istride = 0;
     return BPLTV_OK;
 }
 
@@ -2106,7 +2129,7 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int re
         if (rc) return rc;
         for (int k = 0; k < 3; ++k)
             hipLaunchKernelGGL(patch_sum_kernel, dim3((unsigned)P, O), dim3(256), 0, h->stream, h->d_srgpix + k * tot, M, N, O, am, an,
-                               h->d_red + (size_t)k * P * O);
+                               O, 1, h->d_red + (size_t)k * P * O);
         hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, O, (int)(3 * P), 1.0, g.d_out, (double*)nullptr);
     }
     // input gradient of a vector-Jacobian product: d_p covers the whole batch after the group loop
@@ -2420,12 +2443,28 @@ int multi_set_data(bpltv_t* h, const double* ubar, const double* f) {
     return BPLTV_OK;
 }
 
-int multi_denoise(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, double* u_out, int slices = 1) {
+// each (TV model, bpltv_denoise_each): alpha holds O blocks of am*an doubles; shard k takes the blocks [lo_k, hi_k).  Their
+// entries are checked here first, so that a block one shard would reject does not leave the others' solves behind.
+int multi_denoise(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, double* u_out, int slices = 1,
+                  bool each = false) {
     WallTimer wt;
     MultiState& ms = *h->multi;
-    const size_t npx = h->npx;
+    const size_t npx = h->npx, P = (size_t)am * an;
+    if (each) {
+        if (!alpha || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "alpha: null pointer or empty shape");
+        const bpltv_params p = resolve(pp);
+        double amin = alpha[0];
+        for (size_t e = 0; e < (size_t)h->O * P; ++e) {
+            if (!std::isfinite(alpha[e]) || alpha[e] < 0.0)
+                return set_err(h, BPLTV_E_ARG, "alpha[%zu] = %g: parameters must be finite and >= 0", e, alpha[e]);
+            if (alpha[e] < amin) amin = alpha[e];
+        }
+        if (p.rho != 0.0 && !(amin > 0.0))
+            return set_err(h, BPLTV_E_ARG, "rho != 0 divides by alpha: every parameter entry must be > 0 (min = %g)", amin);
+    }
     int rc = multi_run(h, [&](int k, bpltv_t* c) {
         double* uo = u_out ? u_out + ms.lo[k] * npx : nullptr;
+        if (each) return bpltv_denoise_each(c, alpha + ms.lo[k] * P, am, an, pp, uo);
         return slices == 3 ? bpltv_sumregs_denoise(c, alpha, am, an, pp, uo) : bpltv_denoise(c, alpha, am, an, pp, uo);
     });
     if (rc) return rc;
@@ -2563,8 +2602,9 @@ int multi_gradient(bpltv_t* h, const double* u, const double* ubar, const double
 
 // bpltv_vjp over the shards: images split as for the gradient, input-gradient slices written in place, the parameter
 // gradients of the shards added in shard order.  slices: 1 TV (bpltv_vjp), 3 sum of regularisers (bpltv_sumregs_vjp).
+// each (bpltv_vjp_each): shard k takes the parameter blocks [lo_k, hi_k) and writes their gradients in place.
 int multi_vjp(bpltv_t* h, const double* u, const double* alpha, int am, int an, int reg, const bpltv_params* pp,
-              const double* gu, double* grad_f_out, double* grad_alpha_out, int slices = 1) {
+              const double* gu, double* grad_f_out, double* grad_alpha_out, int slices = 1, bool each = false) {
     if (!u || !gu || !alpha || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "vjp: null pointer or empty shape");
     if (!grad_f_out && !grad_alpha_out) return set_err(h, BPLTV_E_ARG, "vjp: both outputs are NULL");
     WallTimer wt;
@@ -2575,12 +2615,15 @@ int multi_vjp(bpltv_t* h, const double* u, const double* alpha, int am, int an, 
     int rc = multi_run(h, [&](int k, bpltv_t* c) {
         const size_t o0 = ms.lo[k] * npx;
         double* gf = grad_f_out ? grad_f_out + o0 : nullptr;
+        if (each)
+            return bpltv_vjp_each(c, u + o0, alpha + ms.lo[k] * P, am, an, reg, pp, gu + o0, gf,
+                                  grad_alpha_out ? grad_alpha_out + ms.lo[k] * P : nullptr);
         double* ga = grad_alpha_out ? g.data() + (size_t)k * P : nullptr;
         return slices == 3 ? bpltv_sumregs_vjp(c, u + o0, alpha, am, an, reg, pp, gu + o0, gf, ga)
                            : bpltv_vjp(c, u + o0, alpha, am, an, reg, pp, gu + o0, gf, ga);
     });
     if (rc) return rc;
-    if (grad_alpha_out)
+    if (grad_alpha_out && !each)
         for (size_t e = 0; e < P; ++e) {
             double acc = g[e];
             for (int k = 1; k < n; ++k) acc += g[(size_t)k * P + e];
@@ -2673,9 +2716,9 @@ int multi_unsupported(bpltv_t* h, const char* what) {
 // bpltv_vjp (slices = 1) and bpltv_sumregs_vjp (3): host arrays staged in d_u2 / d_ubar2 / d_gf2, the parameter gradient
 // read back from d_vjp.
 int vjp_host(bpltv_t* h, const double* u, const double* alpha, int am, int an, int reg, const bpltv_params* pp,
-             const double* gu, double* grad_f_out, double* grad_alpha_out, int slices) {
+             const double* gu, double* grad_f_out, double* grad_alpha_out, int slices, bool each = false) {
     if (!h) return BPLTV_E_ARG;
-    if (h->multi) return multi_vjp(h, u, alpha, am, an, reg, pp, gu, grad_f_out, grad_alpha_out, slices);
+    if (h->multi) return multi_vjp(h, u, alpha, am, an, reg, pp, gu, grad_f_out, grad_alpha_out, slices, each);
     if (!u || !gu || !alpha) return set_err(h, BPLTV_E_ARG, "vjp: null pointer");
     if (!grad_f_out && !grad_alpha_out) return set_err(h, BPLTV_E_ARG, "vjp: both outputs are NULL");
     if (am < 1 || an < 1 || am > h->M || an > h->N)
@@ -2689,11 +2732,11 @@ int vjp_host(bpltv_t* h, const double* u, const double* alpha, int am, int an, i
     if (grad_f_out && !h->d_gf2) HIPCHK(h, hipMalloc((void**)&h->d_gf2, h->tot * sizeof(double)));
     HIPCHK(h, hipMemcpyAsync(h->d_u2, u, h->tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_ubar2, gu, h->tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    const size_t P = (size_t)slices * am * an;
+    const size_t P = (size_t)slices * am * an * (each ? h->O : 1);
     int rc = ensure(h, &h->d_vjp, &h->vjp_cap, 4 + 2 * P);
     if (rc) return rc;
     double* d_ga = grad_alpha_out ? h->d_vjp + 4 + P : nullptr;
-    rc = vjp_common(h, h->d_u2, alpha, false, am, an, reg, pp, h->d_ubar2, grad_f_out ? h->d_gf2 : nullptr, d_ga, slices);
+    rc = vjp_common(h, h->d_u2, alpha, false, am, an, reg, pp, h->d_ubar2, grad_f_out ? h->d_gf2 : nullptr, d_ga, slices, each);
     if (rc) return rc;
     if (grad_f_out)
         HIPCHK(h, hipMemcpyAsync(grad_f_out, h->d_gf2, h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -2706,18 +2749,18 @@ int vjp_host(bpltv_t* h, const double* u, const double* alpha, int am, int an, i
 
 // bpltv_vjp_device (slices = 1) and bpltv_sumregs_vjp_device (3)
 int vjp_device(bpltv_t* h, const double* d_u, const double* d_alpha, int am, int an, int reg, const bpltv_params* pp,
-               const double* d_gu, double* d_grad_f, double* d_grad_alpha, int slices) {
+               const double* d_gu, double* d_grad_f, double* d_grad_alpha, int slices, bool each = false) {
     if (!h) return BPLTV_E_ARG;
     if (h->multi) {
-        const int rc = multi_unsupported(h, slices == 3 ? "bpltv_sumregs_vjp_device" : "bpltv_vjp_device");
+        const int rc = multi_unsupported(h, each ? "bpltv_vjp_each_device" : (slices == 3 ? "bpltv_sumregs_vjp_device" : "bpltv_vjp_device"));
         if (rc >= 0) return rc;
-        const int r = vjp_device(h->multi->shard[0], d_u, d_alpha, am, an, reg, pp, d_gu, d_grad_f, d_grad_alpha, slices);
+        const int r = vjp_device(h->multi->shard[0], d_u, d_alpha, am, an, reg, pp, d_gu, d_grad_f, d_grad_alpha, slices, each);
         if (r) h->err = h->multi->shard[0]->err; else { h->has_per_image = false; multi_stats(h); }
         return r;
     }
     WallTimer wt;
     HIPCHK(h, hipSetDevice(h->device));
-    const int rc = vjp_common(h, d_u, d_alpha, true, am, an, reg, pp, d_gu, d_grad_f, d_grad_alpha, slices);
+    const int rc = vjp_common(h, d_u, d_alpha, true, am, an, reg, pp, d_gu, d_grad_f, d_grad_alpha, slices, each);
     if (rc) return rc;
     h->st.total_ms = wt.ms();
     return BPLTV_OK;
@@ -2940,6 +2983,49 @@ int bpltv_denoise_device(bpltv_t* h, const double* d_alpha, int am, int an, cons
     bpltv_params p = resolve(pp);
     if (int prc = check_params(h, p)) return prc;
     int rc = upload_alpha_device(h, d_alpha, am, an, &p);
+    if (rc) return rc;
+    rc = run_pdhg(h, p);
+    if (rc) return rc;
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
+// bpltv_denoise / bpltv_denoise_device with one parameter block per image: upload_alpha(_device) with O blocks, after
+// which the PDHG and gap kernels of the dataset context address block k for image k (h->alpha_istride).
+int bpltv_denoise_each(bpltv_t* h, const double* alphas, int am, int an, const bpltv_params* pp, double* u_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi) return multi_denoise(h, alphas, am, an, pp, u_out, 1, true);
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    bpltv_params p = resolve(pp);
+    if (int prc = check_params(h, p)) return prc;
+    int rc = upload_alpha(h, alphas, am, an, &p, PRE_TV, h->O);
+    if (rc) return rc;
+    rc = run_pdhg(h, p);
+    if (rc) return rc;
+    if (u_out) {
+        HIPCHK(h, hipMemcpyAsync(u_out, h->d_state[h->result_buf][0], h->tot * sizeof(double), hipMemcpyDeviceToHost,
+                                 h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
+int bpltv_denoise_each_device(bpltv_t* h, const double* d_alphas, int am, int an, const bpltv_params* pp) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi) {
+        const int rc = multi_unsupported(h, "bpltv_denoise_each_device");
+        if (rc >= 0) return rc;
+        const int r = bpltv_denoise_each_device(h->multi->shard[0], d_alphas, am, an, pp);
+        if (r) h->err = h->multi->shard[0]->err; else { h->has_result = true; multi_stats(h); }
+        return r;
+    }
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    bpltv_params p = resolve(pp);
+    if (int prc = check_params(h, p)) return prc;
+    int rc = upload_alpha_device(h, d_alphas, am, an, &p, PRE_TV, h->O);
     if (rc) return rc;
     rc = run_pdhg(h, p);
     if (rc) return rc;
@@ -3175,6 +3261,14 @@ int bpltv_vjp_device(bpltv_t* h, const double* d_u, const double* d_alpha, int a
     return vjp_device(h, d_u, d_alpha, am, an, reg, pp, d_gu, d_grad_f, d_grad_alpha, 1);
 }
 
+int bpltv_vjp_each(bpltv_t* h, const double* u, const double* alphas, int am, int an, int reg, const bpltv_params* pp,
+                   const double* gu, double* grad_f_out, double* grad_alphas_out) {
+    return vjp_host(h, u, alphas, am, an, reg, pp, gu, grad_f_out, grad_alphas_out, 1, true);
+}
+int bpltv_vjp_each_device(bpltv_t* h, const double* d_u, const double* d_alphas, int am, int an, int reg,
+                          const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alphas) {
+    return vjp_device(h, d_u, d_alphas, am, an, reg, pp, d_gu, d_grad_f, d_grad_alphas, 1, true);
+}
 int bpltv_sumregs_vjp(bpltv_t* h, const double* u, const double* alpha, int am, int an, int reg, const bpltv_params* pp,
                       const double* gu, double* grad_f_out, double* grad_alpha_out) {
     return vjp_host(h, u, alpha, am, an, reg, pp, gu, grad_f_out, grad_alpha_out, 3);

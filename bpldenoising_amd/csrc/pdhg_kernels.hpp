@@ -52,6 +52,8 @@ struct PdhgArgs {
     int Odata;  // images in the dataset; image `img` of the solve uses f[img % Odata] and the
                 // parameter block alpha + (img / Odata) * astride (parameter sweeps: K*Odata problems)
     int astride;
+    int istride; // doubles between the parameter blocks of consecutive images when O == Odata: 0 = one block for every image
+                 // (bpltv_denoise, and a one-block sweep), am*an = image img reads block img (bpltv_denoise_each)
     int ntiles; // tiles of this launch (pdhg_wave_kernel: several tiles per workgroup, the last one may be short)
     int grid3d; // 1: the grid is (nTi, nTj, images): tile and image come from blockIdx.x / .y / .z and the kernel's prologue
                 // needs no integer division (4 of them, ~100 scalar instructions per wave, with the 1-D grid)
@@ -107,9 +109,12 @@ __device__ long long pdhg_tlog[2][4096];
         const int t_ = lin_ - imgl * tilesPerImg_;                           \
         ta = t_ % (A).nTi; tb = t_ / (A).nTi;                                \
     }
-__device__ __forceinline__ void pdhg_data_image(int img, int O, int Odata, int& fimg, int& apar) {
-    if (O == Odata) { fimg = img; apar = 0; }        // no sweep: the solve images are the dataset's
-    else { fimg = img % Odata; apar = img / Odata; }
+// Returns the offset of the parameter block (doubles, or floats on a dtype = 32 handle).  Uniform per workgroup: a scalar
+// parameter stays a scalar load; the shared-parameter path costs one scalar multiply by istride = 0, no division.
+__device__ __forceinline__ size_t pdhg_data_image(const PdhgArgs& A, int img, int& fimg) {
+    if (A.O == A.Odata) { fimg = img; return (size_t)img * A.istride; }   // no sweep: the solve images are the dataset's
+    fimg = img % A.Odata;
+    return (size_t)(img / A.Odata) * A.astride;
 }
 
 __device__ __forceinline__ double alpha_at(const double* __restrict__ alpha, int am, int an, int M,
@@ -197,11 +202,11 @@ __global__ __launch_bounds__(TI* TJ) void pdhg_tile_kernel(PdhgArgs A) {
     tile_span(ta, A.M, RI, A.halo, oi, ci0, ci1);
     tile_span(tb, A.N, RJ, A.halo, oj, cj0, cj1);
     const int M = A.M, N = A.N;
-    int fimg, apar;
-    pdhg_data_image(img, A.O, A.Odata, fimg, apar);
+    int fimg;
+    const size_t aoff = pdhg_data_image(A, img, fimg);
     const size_t base = (size_t)img * M * N;                 // state planes: one slot per solve image
     const size_t fbase = (size_t)fimg * M * N;               // dataset planes
-    const T* __restrict__ alpha = reinterpret_cast<const T*>(A.alpha) + (size_t)apar * A.astride;
+    const T* __restrict__ alpha = reinterpret_cast<const T*>(A.alpha) + aoff;
     const int amode = (A.am == 1 && A.an == 1) ? 0 : ((A.am == M && A.an == N) ? 2 : 1);
     const bool first = (A.first != 0) || (BPLTV_DBG(A) & 1);
 
@@ -543,11 +548,11 @@ __global__ __launch_bounds__(64 * TJ) void pdhg_rows_kernel(PdhgArgs A) {
     tile_span(ta, A.M, RI, A.halo, oi, ci0, ci1);
     tile_span(tb, A.N, RJ, A.halo, oj, cj0, cj1);
     const int M = A.M, N = A.N;
-    int fimg, apar;
-    pdhg_data_image(img, A.O, A.Odata, fimg, apar);
+    int fimg;
+    const size_t aoff = pdhg_data_image(A, img, fimg);
     const size_t base = (size_t)img * M * N;
     const size_t fbase = (size_t)fimg * M * N;
-    const T* __restrict__ alpha = reinterpret_cast<const T*>(A.alpha) + (size_t)apar * A.astride;
+    const T* __restrict__ alpha = reinterpret_cast<const T*>(A.alpha) + aoff;
     const int amode = (A.am == 1 && A.an == 1) ? 0 : ((A.am == M && A.an == N) ? 2 : 1);
     const bool first = (A.first != 0) || (BPLTV_DBG(A) & 1);
     const int lj0 = PJ * tj;
@@ -704,11 +709,11 @@ __global__ __launch_bounds__(128 * TJ) void pdhg_rowsw_kernel(PdhgArgs A) {
     tile_span(ta, A.M, RI, A.halo, oi, ci0, ci1);
     tile_span(tb, A.N, RJ, A.halo, oj, cj0, cj1);
     const int M = A.M, N = A.N;
-    int fimg, apar;
-    pdhg_data_image(img, A.O, A.Odata, fimg, apar);
+    int fimg;
+    const size_t aoff = pdhg_data_image(A, img, fimg);
     const size_t base = (size_t)img * M * N;
     const size_t fbase = (size_t)fimg * M * N;
-    const T* __restrict__ alpha = reinterpret_cast<const T*>(A.alpha) + (size_t)apar * A.astride;
+    const T* __restrict__ alpha = reinterpret_cast<const T*>(A.alpha) + aoff;
     const int amode = (A.am == 1 && A.an == 1) ? 0 : ((A.am == M && A.an == N) ? 2 : 1);
     const bool first = (A.first != 0) || (BPLTV_DBG(A) & 1);
     const int lj0 = PJ * tj;
@@ -890,11 +895,11 @@ __global__ __launch_bounds__(64 * TJ, TJ / 2) void pdhg_rows2_kernel(PdhgArgs A)
     tile_span(ta, A.M, RI, A.halo, oi, ci0, ci1);
     tile_span(tb, A.N, RJ, A.halo, oj, cj0, cj1);
     const int M = A.M, N = A.N;
-    int fimg, apar;
-    pdhg_data_image(img, A.O, A.Odata, fimg, apar);
+    int fimg;
+    const size_t aoff = pdhg_data_image(A, img, fimg);
     const size_t base = (size_t)img * M * N;
     const size_t fbase = (size_t)fimg * M * N;
-    const T* __restrict__ alpha = reinterpret_cast<const T*>(A.alpha) + (size_t)apar * A.astride;
+    const T* __restrict__ alpha = reinterpret_cast<const T*>(A.alpha) + aoff;
     const int amode = (A.am == 1 && A.an == 1) ? 0 : ((A.am == M && A.an == N) ? 2 : 1);
     const bool first = A.first != 0;
     const int lj0 = PJ * tj;
@@ -1149,11 +1154,11 @@ __global__ __launch_bounds__(64 * NL, WPE) void pdhg_stream_kernel(PdhgArgs A) {
     tile_span(ta, M, 64, A.halo, oi, ci0, ci1);
     tile_span(tb, N, A.seg, A.halo, rs, cj0, cj1);                 // rows [rs, re) are processed, [cj0, cj1) are stored
     const int re = min(N, rs + A.seg);
-    int fimg, apar;
-    pdhg_data_image(img, A.O, A.Odata, fimg, apar);
+    int fimg;
+    const size_t aoff = pdhg_data_image(A, img, fimg);
     const size_t base = (size_t)img * M * N + (size_t)(oi + ti);
     const size_t fbase = (size_t)fimg * M * N + (size_t)(oi + ti);
-    const T* __restrict__ alpha = reinterpret_cast<const T*>(A.alpha) + (size_t)apar * A.astride;
+    const T* __restrict__ alpha = reinterpret_cast<const T*>(A.alpha) + aoff;
     const int amode = (A.am == 1 && A.an == 1) ? 0 : ((A.am == M && A.an == N) ? 2 : 1);
     const unsigned pa = (amode == 1) ? ((unsigned)(oi + ti) * (unsigned)A.am) / (unsigned)M : 0u;
     const bool first = A.first != 0;
@@ -1322,8 +1327,10 @@ __global__ __launch_bounds__(64 * WPB, 2) void pdhg_wave_kernel(PdhgArgs A) {
     tile_span(tb, A.N, RJ, A.halo, oj, cj0, cj1);
     const int M = A.M, N = A.N;
     const size_t base = (size_t)img * M * N;
-    const size_t fbase = (size_t)(img % A.Odata) * M * N;
-    const T* __restrict__ alpha = reinterpret_cast<const T*>(A.alpha) + (size_t)(img / A.Odata) * A.astride;
+    int fimg;
+    const size_t aoff = pdhg_data_image(A, img, fimg);
+    const size_t fbase = (size_t)fimg * M * N;
+    const T* __restrict__ alpha = reinterpret_cast<const T*>(A.alpha) + aoff;
     const int amode = (A.am == 1 && A.an == 1) ? 0 : ((A.am == M && A.an == N) ? 2 : 1);
     const bool first = A.first != 0;
     const int gi = oi + li, gic = min(gi, M - 1);
@@ -1525,7 +1532,7 @@ __global__ __launch_bounds__(64) void pdhg_phase_gate_kernel(unsigned* __restric
 }
 
 __global__ __launch_bounds__(256) void pdhg_init_kernel(const double* __restrict__ f, const double* __restrict__ alpha,
-                                                        int am, int an, int M, int N, int Odata, int astride, size_t total,
+                                                        int am, int an, int M, int N, int Odata, int astride, int istride, size_t total,
                                                         int init, int dual_first, double sigma, double rho,
                                                         double* __restrict__ x, double* __restrict__ y1,
                                                         double* __restrict__ y2) {
@@ -1543,7 +1550,7 @@ __global__ __launch_bounds__(256) void pdhg_init_kernel(const double* __restrict
         const double xj1 = (j < N - 1) ? (init ? 0.0 : fk[q + M]) : x0;
         const double d1 = (i < M - 1) ? xi1 - x0 : 0.0;
         const double d2 = (j < N - 1) ? xj1 - x0 : 0.0;
-        const double a = alpha_at(alpha + (size_t)(img / Odata) * astride, am, an, M, N, i, j);
+        const double a = alpha_at(alpha + (size_t)(img / Odata) * astride + (size_t)img * istride, am, an, M, N, i, j);
         y1n = __builtin_fma(sigma, d1, 0.0);
         y2n = __builtin_fma(sigma, d2, 0.0);
         if (rho != 0.0) {
@@ -1662,11 +1669,12 @@ __global__ __launch_bounds__(256) void gap_partial_kernel(const double* __restri
                                                           const double* __restrict__ y2,
                                                           const double* __restrict__ f,
                                                           const double* __restrict__ alpha, int am,
-                                                          int an, int M, int N,
+                                                          int an, int M, int N, int astride,
                                                           double* __restrict__ partial) {
     __shared__ double sh[4];
     const int npx = M * N;
     const size_t base = (size_t)blockIdx.y * npx;
+    alpha += (size_t)blockIdx.y * astride;   // astride 0: one parameter for all images; am*an: image k's own block
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
     for (int q = blockIdx.x * 256 + threadIdx.x; q < npx; q += gridDim.x * 256) {
         const int i = q % M, j = q / M;

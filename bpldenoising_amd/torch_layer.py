@@ -11,6 +11,12 @@ product of include/bpltv.h's bpltv_vjp for the cotangent torch hands it: f.grad 
 selects the reference's gradient_reg linearisation (delta <= delta_t in tv_op_learning_function).  Double backward is
 not supported (once_differentiable).
 
+    u = tv_denoise_each(f, alpha, reg=False)               # one parameter per image (bpltv_denoise_each / _vjp_each)
+
+f is then (B, H, W) and alpha float64 of shape (B,) (a scalar per image), (B, pH, pW) (a patch parameter per image) or
+(B, H, W) (a map per image) -- what a network that predicts the parameter per sample outputs.  alpha.grad[k] is image k's
+term alone.  A separate function: tv_denoise never reads a leading batch dimension off alpha's shape.
+
     u = sumregs_denoise(f, alpha, reg=False)               # the three-weight model (bpltv_sumregs_*)
 
 alpha is then float64 of shape (3,) (one weight per difference: forward, backward, centred), (3, pH, pW) (patch
@@ -83,6 +89,31 @@ def _check_args(f, alpha, slices=1):
     return O, H, W, am, an
 
 
+def _check_args_each(f, alpha):
+    """(O, N, M, am, an) of a valid (f, alpha) pair of tv_denoise_each; TypeError / ValueError before any library call."""
+    name = "tv_denoise_each"
+    if not isinstance(f, torch.Tensor) or not isinstance(alpha, torch.Tensor):
+        raise TypeError("%s: f and alpha must be torch tensors" % name)
+    if f.dtype != torch.float64 or alpha.dtype != torch.float64:
+        raise TypeError("%s: f and alpha must be float64 (got %s, %s)" % (name, f.dtype, alpha.dtype))
+    if f.dim() != 3 or f.numel() == 0:
+        raise ValueError("%s: f must have shape (B, H, W), got %s" % (name, tuple(f.shape)))
+    B, H, W = f.shape
+    shape = tuple(alpha.shape)
+    if shape == (B,):
+        am = an = 1
+    elif len(shape) == 3 and shape[0] == B and 1 <= shape[1] <= H and 1 <= shape[2] <= W:
+        an, am = shape[1], shape[2]
+    else:
+        raise ValueError("%s: alpha must be (%d,), (%d, pH, pW) with pH <= %d, pW <= %d, or (%d, %d, %d); got %s"
+                         % (name, B, B, H, W, B, H, W, shape))
+    if alpha.device != f.device:
+        raise ValueError("%s: alpha is on %s, f on %s" % (name, alpha.device, f.device))
+    if f.device.type != "cuda":
+        raise ValueError("%s: f must be on a ROCm device, got %s" % (name, f.device))
+    return B, H, W, am, an
+
+
 def _sync(device):
     torch.cuda.current_stream(device).synchronize()
 
@@ -128,6 +159,50 @@ def tv_denoise(f, alpha, *, reg=False, **solver_kw):
     differentiable in f and alpha.  solver_kw: the solver parameters of TVSolver.params (maxiter, ...), used by the
     forward solve and the adjoint alike."""
     return TVDenoiseFunction.apply(f, alpha, reg, solver_kw)
+
+
+class TVDenoiseEachFunction(torch.autograd.Function):
+    """autograd.Function of tv_denoise_each (below); apply(f, alpha, reg, solver_kw)."""
+
+    @staticmethod
+    def forward(ctx, f, alpha, reg, solver_kw):
+        O, N, M, am, an = _check_args_each(f, alpha)
+        index = f.device.index if f.device.index is not None else torch.cuda.current_device()
+        s = _solver(index, M, N, O)
+        fc = f.detach().contiguous()
+        ac = alpha.detach().contiguous()
+        u = torch.empty_like(fc)
+        _sync(f.device)
+        s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
+        s.denoise_each_device(ac.data_ptr(), am, an, **solver_kw)
+        s.copy_u_device(u.data_ptr())
+        ctx.save_for_backward(u, ac)
+        ctx.solver, ctx.am, ctx.an, ctx.reg, ctx.solver_kw = s, am, an, bool(reg), dict(solver_kw)
+        return u
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gu):
+        need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_f or need_a):
+            return None, None, None, None
+        u, alpha = ctx.saved_tensors
+        gu = gu.to(dtype=torch.float64).contiguous()
+        gf = torch.empty_like(u) if need_f else None
+        ga = torch.empty_like(alpha) if need_a else None
+        _sync(u.device)
+        ctx.solver.vjp_each_device(u.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(),
+                                   gf.data_ptr() if need_f else None, ga.data_ptr() if need_a else None,
+                                   reg=ctx.reg, **ctx.solver_kw)
+        return gf, ga, None, None
+
+
+def tv_denoise_each(f, alpha, *, reg=False, **solver_kw):
+    """u[k] = denoise(f[k], alpha[k]) for a batch f of shape (B, H, W) with one parameter per image: alpha (B,),
+    (B, pH, pW) or (B, H, W) on f's device.  One batched solve forward (TVSolver.denoise_each_device) and one adjoint
+    solve backward (vjp_each_device); differentiable in f and alpha, alpha.grad[k] being image k's term.  solver_kw: as
+    tv_denoise's."""
+    return TVDenoiseEachFunction.apply(f, alpha, reg, solver_kw)
 
 
 class TVDenoise(torch.nn.Module):

@@ -297,6 +297,24 @@ int bpltv_vjp(bpltv_t *h, const double *u, const double *alpha, int am, int an, 
 int bpltv_vjp_device(bpltv_t *h, const double *d_u, const double *d_alpha, int am, int an, int reg,
                      const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alpha);
 
+/* One parameter per image: the solves and vector-Jacobian products above for a batch whose O images each have their
+ * own parameter -- what a network that predicts alpha per sample produces.  alphas: O blocks of am x an doubles, each
+ * column major, block k at alphas + k*am*an, with bpltv_denoise's shape rules (1 x 1 scalar, m x n patch, M x N map).
+ * u_k is bitwise what a one-image handle returns for (f_k, alpha_k).  Each function keeps the contract of its twin
+ * (bpltv_denoise, bpltv_denoise_device, bpltv_vjp, bpltv_vjp_device): every entry is checked (finite, >= 0; > 0 when
+ * params.rho != 0, and for reg = 1 with a patch or map parameter) before anything of the handle changes; dtype = 32
+ * handles solve in float (the adjoint stays Float64); check_every / gap_tol and bpltv_duality_gap use image k's own
+ * block; bpltv_u_device and bpltv_copy_u_device return the result; the VJP leaves the last solve untouched.
+ * grad_f_out is bpltv_vjp's; grad_alphas_out receives O blocks, block k = image k's term alone (not summed over the
+ * images: their sum in image order is bitwise bpltv_vjp's grad_alpha_out when all blocks are equal).  Multi-device
+ * handles hand shard k the blocks [lo_k, hi_k); the device forms return BPLTV_E_UNSUPPORTED beyond one shard. */
+int bpltv_denoise_each(bpltv_t *h, const double *alphas, int am, int an, const bpltv_params *p, double *u_out);
+int bpltv_denoise_each_device(bpltv_t *h, const double *d_alphas, int am, int an, const bpltv_params *p);
+int bpltv_vjp_each(bpltv_t *h, const double *u, const double *alphas, int am, int an, int reg, const bpltv_params *p,
+                   const double *gu, double *grad_f_out, double *grad_alphas_out);
+int bpltv_vjp_each_device(bpltv_t *h, const double *d_u, const double *d_alphas, int am, int an, int reg,
+                          const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alphas);
+
 /* Vector-Jacobian product of u = sumregs_denoise(f, x) for a cotangent gu = dL/du: the adjoint system of
  * bpltv_sumregs_evaluate's gradient with the right-hand side
  *     reg = 0 (sumregs_gradient):      gu        grad_f_out =  p
