@@ -300,15 +300,12 @@ struct bpltv_handle {
     // dataset + state
     double *d_ubar = nullptr, *d_f = nullptr;
     double* d_state[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
-    // current solve context: default = the O dataset images; a parameter sweep swaps in K*O slots
-    double* (*cur_state)[3] = nullptr;
-    int cur_nimg = 0, cur_astride = 0;
+    // bpltv_sweep solves its K*O problems in state sets of its own (SolveCtx below)
     double* d_sweep[2][3] = {{nullptr, nullptr, nullptr}, {nullptr, nullptr, nullptr}};
     size_t sweep_cap = 0;  // images
     double* d_sweep_cost = nullptr;
-    // the parameter of the current solve context: nullptr = the dataset's d_alpha; bpltv_sweep swaps in its own K blocks
-    // (d_sweep_alpha, with the float twin f32_sweep_alpha), so that d_alpha and the last result stay as they were
-    const double* cur_alpha = nullptr;
+    // ... and reads its own K parameter blocks (with the float twin f32_sweep_alpha), so that d_alpha and the last
+    // result stay as they were
     double* d_sweep_alpha = nullptr;
     size_t sweep_alpha_cap = 0;
     int result_buf = 0;  // which state set holds the last result
@@ -368,11 +365,7 @@ struct bpltv_handle {
     size_t vjp_cap = 0;
     // sum-of-regularisers model (sumregs_kernels.hpp): state and adjoint workspace, allocated on first use
     double* d_sr[2][7] = {{nullptr}, {nullptr}};   // x, yf1, yf2, yb1, yb2, yc1, yc2; two sets (ping-pong)
-    // current solve context of run_sr_pdhg: default = the O dataset images in d_sr with the parameters in d_alpha;
-    // bpltv_sumregs_sweep swaps in a group of K_g * O problems, its own state and its own parameter blocks
-    double* (*sr_cur)[7] = nullptr;
-    int sr_cur_nimg = 0, sr_cur_astride = 0;
-    const double* sr_cur_alpha = nullptr;            // nullptr: d_alpha
+    // bpltv_sumregs_sweep solves a group of K_g * O problems in its own state sets, with its own parameter blocks
     double* d_srsweep[2][7] = {{nullptr}, {nullptr}};
     size_t srsweep_cap = 0;                          // problems
     double *d_srsweep_alpha = nullptr, *d_srsweep_cost = nullptr;
@@ -518,17 +511,40 @@ int get_table32(bpltv_t* h, const bpltv_params& p, float** out) {
     *out = d;
     return BPLTV_OK;
 }
-// buffers for the current solve context (cur_nimg images) and fresh float copies of f and of the parameter
-int f32_prepare(bpltv_t* h) {
-    if (h->f32_state_cap < (size_t)h->cur_nimg) {
+// What one PDHG solve works on -- a plain value handed to run_pdhg / run_sr_pdhg and everything below them.  Built in two
+// kinds of places: dataset_ctx (the O dataset images with the handle's d_alpha) and the two sweeps (K*O problems, or a
+// group of them, in the sweep's own state sets with its own parameter blocks).  The solvers say which state set holds the
+// result through a return parameter and write nothing of it into the handle: a solve on the dataset context is committed
+// by solve_dataset, a sweep commits nothing -- so the last result, d_alpha and the duality gap survive a sweep.
+struct SolveCtx {
+    double* const* state[2] = {nullptr, nullptr};   // the two state sets (ping-pong): 3 planes each (TV), 7 (sum of regularisers)
+    int nimg = 0;                   // problems; problem img reads f[img % O]
+    const double* alpha = nullptr;  // the parameter buffer (Float64)
+    bool sweep = false;             // float handle: the parameter's twin is f32_sweep_alpha, not f32_alpha (f32_state is shared)
+    int astride = 0;                // doubles between the parameter blocks of a sweep (problem img reads block img / O)
+    int istride = 0;                // doubles between per-image blocks (bpltv_denoise_each; TV model, dataset context only)
+    int am = 1, an = 1;             // parameter shape
+    double alpha_min = 0.0;         // its smallest entry, validated on the host or by alpha_check_kernel
+};
+SolveCtx dataset_ctx(bpltv_t* h, bool sr) {
+    SolveCtx x;
+    for (int s = 0; s < 2; ++s) x.state[s] = sr ? h->d_sr[s] : h->d_state[s];
+    x.nimg = h->O; x.alpha = h->d_alpha; x.istride = h->alpha_istride;
+    x.am = h->last_am; x.an = h->last_an; x.alpha_min = h->alpha_min;
+    return x;
+}
+
+// buffers for the solve context (x.nimg images) and fresh float copies of f and of the parameter
+int f32_prepare(bpltv_t* h, const SolveCtx& x) {
+    if (h->f32_state_cap < (size_t)x.nimg) {
         drop_graphs(h);   // captured kernels hold the old pointers
         for (int s = 0; s < 2; ++s)
             for (int c = 0; c < 3; ++c) {
                 if (h->f32_state[s][c]) HIPCHK(h, hipFree(h->f32_state[s][c]));
                 h->f32_state[s][c] = nullptr;
-                HIPCHK(h, hipMalloc((void**)&h->f32_state[s][c], (size_t)h->cur_nimg * h->npx * sizeof(float)));
+                HIPCHK(h, hipMalloc((void**)&h->f32_state[s][c], (size_t)x.nimg * h->npx * sizeof(float)));
             }
-        h->f32_state_cap = (size_t)h->cur_nimg;
+        h->f32_state_cap = (size_t)x.nimg;
     }
     if (!h->f32_f) HIPCHK(h, hipMalloc((void**)&h->f32_f, h->tot * sizeof(float)));
     if (!h->f32_f_valid) {
@@ -536,10 +552,9 @@ int f32_prepare(bpltv_t* h) {
         h->f32_f_valid = true;
     }
     // the float twin of the context's parameter: the dataset's, or a sweep's blocks
-    const bool sweep = h->cur_alpha != nullptr;
-    float*& a32 = sweep ? h->f32_sweep_alpha : h->f32_alpha;
-    size_t& cap32 = sweep ? h->f32_sweep_alpha_cap : h->f32_alpha_cap;
-    const size_t cap = sweep ? h->sweep_alpha_cap : h->alpha_cap;
+    float*& a32 = x.sweep ? h->f32_sweep_alpha : h->f32_alpha;
+    size_t& cap32 = x.sweep ? h->f32_sweep_alpha_cap : h->f32_alpha_cap;
+    const size_t cap = x.sweep ? h->sweep_alpha_cap : h->alpha_cap;
     if (cap32 < cap) {
         drop_graphs(h);
         if (a32) HIPCHK(h, hipFree(a32));
@@ -548,26 +563,22 @@ int f32_prepare(bpltv_t* h) {
         HIPCHK(h, hipMalloc((void**)&a32, cap * sizeof(float)));
         cap32 = cap;
     }
-    cvt_to_f32(h, sweep ? h->cur_alpha : h->d_alpha, a32, cap);
+    cvt_to_f32(h, x.alpha, a32, cap);
     HIPCHK(h, hipGetLastError());
     return BPLTV_OK;
 }
 // operand pointers of the PDHG kernel for this handle's dtype (float arrays travel in PdhgArgs' double* fields)
-inline double* pdhg_state(bpltv_t* h, int set, int c) {
-    return h->dtype == 32 ? reinterpret_cast<double*>(h->f32_state[set][c]) : h->cur_state[set][c];
+inline double* pdhg_state(bpltv_t* h, const SolveCtx& x, int set, int c) {
+    return h->dtype == 32 ? reinterpret_cast<double*>(h->f32_state[set][c]) : x.state[set][c];
 }
 inline const double* pdhg_f(bpltv_t* h) { return h->dtype == 32 ? reinterpret_cast<const double*>(h->f32_f) : h->d_f; }
-// the parameter of the current solve context (Float64): the dataset's d_alpha, or a sweep's blocks
-inline const double* ctx_alpha(const bpltv_t* h) { return h->cur_alpha ? h->cur_alpha : h->d_alpha; }
-inline const double* pdhg_alpha(bpltv_t* h) {
-    if (h->dtype == 32) return reinterpret_cast<const double*>(h->cur_alpha ? h->f32_sweep_alpha : h->f32_alpha);
-    return ctx_alpha(h);
+inline const double* pdhg_alpha(bpltv_t* h, const SolveCtx& x) {
+    if (h->dtype == 32) return reinterpret_cast<const double*>(x.sweep ? h->f32_sweep_alpha : h->f32_alpha);
+    return x.alpha;
 }
-// PdhgArgs::istride of the current solve context: a sweep's blocks are addressed by astride alone
-inline int pdhg_istride(const bpltv_t* h) { return h->cur_alpha ? 0 : h->alpha_istride; }
 // the solve's result (set `buf`) widened into the double state buffers
-int f32_widen(bpltv_t* h, int buf) {
-    for (int c = 0; c < 3; ++c) cvt_to_f64(h, h->f32_state[buf][c], h->cur_state[buf][c], (size_t)h->cur_nimg * h->npx);
+int f32_widen(bpltv_t* h, const SolveCtx& x, int buf) {
+    for (int c = 0; c < 3; ++c) cvt_to_f64(h, h->f32_state[buf][c], x.state[buf][c], (size_t)x.nimg * h->npx);
     HIPCHK(h, hipGetLastError());
     return BPLTV_OK;
 }
@@ -583,31 +594,62 @@ int solve_precheck(bpltv_t* h, const bpltv_params& p, double amin, int what);
 // that adjoint is gradient_reg with a patch or map parameter
 enum { PRE_TV = 0, PRE_SR = 1, PRE_GRADIENT = 2, PRE_REG_ARRAY = 4 };
 inline int pre_gradient(double delta, const bpltv_params& p, int am, int an) {
-    const int reg = !(delta > p.delta_t);   // as evaluate_common / sr_evaluate_common
+    const int reg = !(delta > p.delta_t);   // as evaluate_common
     return PRE_GRADIENT | ((reg && !(am == 1 && an == 1)) ? PRE_REG_ARRAY : 0);
 }
 
-// solve (nullable): the parameters of the PDHG solve the upload is for -- solve_precheck runs on them before anything of
-// the handle changes.  blocks: 1, or O for bpltv_denoise_each (O blocks of am*an doubles, image k reads block k).
-int upload_alpha(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* solve = nullptr, int what = PRE_TV,
-                 int blocks = 1) {
+void drop_sr_graphs(bpltv_t* h);
+
+// The host-side parameter check of every entry point: n entries, finite and >= 0; *amin receives the smallest.  `name`
+// is what the message calls the array ("alpha", "sweep: alphas", ...).
+// The reference is defined for alpha >= 0 (alpha = 0: u = f); NaN/Inf or a negative ball radius has no
+// meaning on this path and would propagate silently through 5000 iterations.
+int check_alpha_host(bpltv_t* h, const char* name, const double* a, size_t n, double* amin) {
+    *amin = a[0];
+    for (size_t e = 0; e < n; ++e) {
+        if (!std::isfinite(a[e]) || a[e] < 0.0)
+            return set_err(h, BPLTV_E_ARG, "%s[%zu] = %g: parameters must be finite and >= 0", name, e, a[e]);
+        if (a[e] < *amin) *amin = a[e];
+    }
+    return BPLTV_OK;
+}
+
+// The parameter of the dataset context into d_alpha, from the host or (on_device: bpltv_*denoise*_device) from HBM, where
+// it is checked in place by alpha_check_kernel (one 16-byte read back) and copied device to device.
+// what: the model (PRE_SR: three slices of am*an doubles) and what follows the upload, for solve_precheck.
+// blocks: 1, or O for bpltv_denoise_each(_device) (TV model: O blocks of am*an doubles, image k reads block k).
+// solve (nullable): the parameters of the PDHG solve the upload is for.  The order is the contract: shape, values,
+// solve_precheck, and only then the handle -- a rejected parameter leaves d_alpha, its shape and alpha_min, and so the
+// duality gap of the last solve, as they were.
+int upload_alpha(bpltv_t* h, const double* alpha, bool on_device, int am, int an, int what = PRE_TV, int blocks = 1,
+                 const bpltv_params* solve = nullptr) {
+    const bool sr = (what & PRE_SR) != 0;
     if (!alpha || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "alpha: null pointer or empty shape");
     if (am > h->M || an > h->N)
-        return set_err(h, BPLTV_E_ARG, "alpha shape %dx%d exceeds image %dx%d", am, an, h->M, h->N);
-    const size_t need = (size_t)blocks * am * an;
-    // The reference is defined for alpha >= 0 (alpha = 0: u = f); NaN/Inf or a negative ball radius has no
-    // meaning on this path and would propagate silently through 5000 iterations.
-    double amin = alpha[0];
-    for (size_t e = 0; e < need; ++e) {
-        if (!std::isfinite(alpha[e]) || alpha[e] < 0.0)
-            return set_err(h, BPLTV_E_ARG, "alpha[%zu] = %g: parameters must be finite and >= 0", e, alpha[e]);
-        if (alpha[e] < amin) amin = alpha[e];
+        return set_err(h, BPLTV_E_ARG, sr ? "alpha shape %dx%dx3 exceeds image %dx%d" : "alpha shape %dx%d exceeds image %dx%d",
+                       am, an, h->M, h->N);
+    const size_t need = (size_t)(sr ? 3 : 1) * blocks * am * an;
+    double amin = 0.0;
+    if (on_device) {
+        unsigned long long* chk_d = reinterpret_cast<unsigned long long*>(h->d_scalar + 2);
+        HIPCHK(h, hipMemsetAsync(chk_d, 0xFF, sizeof(unsigned long long), h->stream));
+        HIPCHK(h, hipMemsetAsync(chk_d + 1, 0, sizeof(unsigned long long), h->stream));
+        hipLaunchKernelGGL(alpha_check_kernel, dim3((unsigned)std::min<size_t>((need + 255) / 256, 1024)), dim3(256), 0, h->stream, alpha, need, chk_d);
+        HIPCHK(h, hipGetLastError());
+        unsigned long long chk_h[2] = {0, 1};
+        HIPCHK(h, hipMemcpyAsync(chk_h, chk_d, sizeof(chk_h), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if (chk_h[1] != 0) return set_err(h, BPLTV_E_ARG, "alpha (device array): parameters must be finite and >= 0");
+        std::memcpy(&amin, chk_h, sizeof(double));
+    } else if (int rc = check_alpha_host(h, "alpha", alpha, need, &amin)) {
+        return rc;
     }
     if (solve)
         if (int rc = solve_precheck(h, *solve, amin, what)) return rc;
     h->alpha_min = amin;
     if (h->alpha_cap < need) {
         drop_graphs(h);  // captured kernels hold the old pointer
+        drop_sr_graphs(h);   // ... of either model: both keys hold it, so this only frees graphs no key can reach again
         int rc = ensure(h, &h->d_alpha, &h->alpha_cap, need);
         if (rc) return rc;
     }
@@ -615,54 +657,7 @@ int upload_alpha(bpltv_t* h, const double* alpha, int am, int an, const bpltv_pa
         int rc = ensure(h, &h->d_partial, &h->partial_cap, need + 1);
         if (rc) return rc;
     }
-    HIPCHK(h, hipMemcpyAsync(h->d_alpha, alpha, need * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    h->last_am = am;
-    h->last_an = an;
-    h->last_slices = 1;
-    h->alpha_istride = blocks > 1 ? am * an : 0;
-    return BPLTV_OK;
-}
-
-void drop_sr_graphs(bpltv_t* h);
-
-// The same for a parameter that already lives in HBM (bpltv_denoise_device, bpltv_sumregs_denoise_device): checked in
-// place by alpha_check_kernel (one 16-byte read back), then copied device to device.  Nothing of the handle changes
-// before the array is accepted: a rejected parameter leaves d_alpha, its shape and alpha_min -- and so the duality gap of
-// the last solve -- as they were.  what & PRE_SR: the sum-of-regularisers model, three slices of am*an doubles.  blocks:
-// 1, or O for bpltv_denoise_each_device (TV model).
-int upload_alpha_device(bpltv_t* h, const double* d_alpha, int am, int an, const bpltv_params* solve = nullptr,
-                        int what = PRE_TV, int blocks = 1) {
-    const bool sr = (what & PRE_SR) != 0;
-    if (!d_alpha || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "alpha: null pointer or empty shape");
-    if (am > h->M || an > h->N)
-        return set_err(h, BPLTV_E_ARG, sr ? "alpha shape %dx%dx3 exceeds image %dx%d" : "alpha shape %dx%d exceeds image %dx%d",
-                       am, an, h->M, h->N);
-    const size_t need = (size_t)(sr ? 3 : 1) * blocks * am * an;
-    unsigned long long* chk_d = reinterpret_cast<unsigned long long*>(h->d_scalar + 2);
-    HIPCHK(h, hipMemsetAsync(chk_d, 0xFF, sizeof(unsigned long long), h->stream));
-    HIPCHK(h, hipMemsetAsync(chk_d + 1, 0, sizeof(unsigned long long), h->stream));
-    hipLaunchKernelGGL(alpha_check_kernel, dim3((unsigned)std::min<size_t>((need + 255) / 256, 1024)), dim3(256), 0, h->stream, d_alpha, need, chk_d);
-    HIPCHK(h, hipGetLastError());
-    unsigned long long chk_h[2] = {0, 1};
-    HIPCHK(h, hipMemcpyAsync(chk_h, chk_d, sizeof(chk_h), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (chk_h[1] != 0) return set_err(h, BPLTV_E_ARG, "alpha (device array): parameters must be finite and >= 0");
-    double chk[1];
-    std::memcpy(chk, chk_h, sizeof(double));
-    if (solve)
-        if (int rc = solve_precheck(h, *solve, chk[0], what)) return rc;
-    if (h->alpha_cap < need) {
-        drop_graphs(h);  // captured kernels hold the old pointer
-        if (sr) drop_sr_graphs(h);
-        int rc = ensure(h, &h->d_alpha, &h->alpha_cap, need);
-        if (rc) return rc;
-    }
-    if (h->partial_cap < need + 1) {
-        int rc = ensure(h, &h->d_partial, &h->partial_cap, need + 1);
-        if (rc) return rc;
-    }
-    HIPCHK(h, hipMemcpyAsync(h->d_alpha, d_alpha, need * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    h->alpha_min = chk[0];
+    HIPCHK(h, hipMemcpyAsync(h->d_alpha, alpha, need * sizeof(double), on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     h->last_am = am;
     h->last_an = an;
     h->last_slices = sr ? 3 : 1;
@@ -671,15 +666,13 @@ int upload_alpha_device(bpltv_t* h, const double* d_alpha, int am, int an, const
 }
 
 // Region, fusion depth and launch chains of one solve: plan_pdhg (tiling.hpp -- plain C++, fuzzed under the sanitizers
-// by tools/plan_host_check.cpp) over the geometry of the variant table above.  nimg: problems of the solve (-1: the
-// current solve context's).
-int make_plan(bpltv_t* h, const bpltv_params& p, Plan* pl, int nimg = -1) {
+// by tools/plan_host_check.cpp) over the geometry of the variant table above.  nimg: problems of the solve.
+int make_plan(bpltv_t* h, const bpltv_params& p, Plan* pl, int nimg) {
     static const std::vector<PlanVariant> geom = [] {
         std::vector<PlanVariant> g;
         for (const Variant& V : kVariants) g.push_back(PlanVariant{V.RI, V.RJ, V.tiles_per_block, V.min_image, V.tmax});
         return g;
     }();
-    if (nimg < 0) nimg = h->cur_nimg;
     PlanRequest q{h->M, h->N, nimg, h->ncu, p.maxiter, p.tile_iters, p.reserved[0], p.reserved[1]};
     const int rc = plan_pdhg(q, geom.data(), (int)geom.size(), pl);
     switch (rc) {
@@ -697,13 +690,13 @@ int make_plan(bpltv_t* h, const bpltv_params& p, Plan* pl, int nimg = -1) {
 
 // Build one hipGraph per chain (image group): maxiter iterations as a linear launch sequence.
 // The chains are replayed concurrently, each on its own stream (= its own hardware queue).
-int build_graphs(bpltv_t* h, const bpltv_params& p, const Plan& pl, const double* d_tab, int niter, bool from_state,
-                 std::vector<hipGraphExec_t>* out) {
+int build_graphs(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, const Plan& pl, const double* d_tab, int niter,
+                 bool from_state, std::vector<hipGraphExec_t>* out) {
     const Variant& V = kVariants[pl.variant];
     const int tilesPerImg = pl.nTi * pl.nTj;
     int rc = BPLTV_OK;
     for (int c = 0; c < pl.chains && rc == BPLTV_OK; ++c) {
-        const int lo = (int)(((long)h->cur_nimg * c) / pl.chains), hi = (int)(((long)h->cur_nimg * (c + 1)) / pl.chains);
+        const int lo = (int)(((long)x.nimg * c) / pl.chains), hi = (int)(((long)x.nimg * (c + 1)) / pl.chains);
         if (hi <= lo) continue;
         hipGraph_t g = nullptr;
         HIPCHK(h, hipGraphCreate(&g, 0));
@@ -721,7 +714,7 @@ int build_graphs(bpltv_t* h, const bpltv_params& p, const Plan& pl, const double
         // (LDS-tile kernels only: launches of ~10 us; the row kernels' launches of ~100 us showed one kind of step only;
         // and launches of at most two workgroups per CU: longer ones -- sweeps of many problems -- are not launch-bound)
         const bool phased = pl.chains == 2 && h->d_phase != nullptr && !(p.reserved[2] & 1) && niter / pl.T >= 64 && V.RI <= 48 &&
-                            (long)tilesPerImg * h->cur_nimg <= 4L * (h->ncu > 0 ? h->ncu : 256);
+                            (long)tilesPerImg * x.nimg <= 4L * (h->ncu > 0 ? h->ncu : 256);
         int nlaunch = 0;
         for (int it = 0; it < niter; it += step, step = pl.T) {
             if (phased && c == 1 && (nlaunch == 8 || nlaunch == 40 || nlaunch == 160)) {   // 40, 160: a check, in case the sequence fell back
@@ -738,10 +731,10 @@ int build_graphs(bpltv_t* h, const bpltv_params& p, const Plan& pl, const double
             }
             ++nlaunch;
             PdhgArgs a;
-            a.f = pdhg_f(h); a.alpha = pdhg_alpha(h); a.tab = d_tab; a.rho = p.rho;
-            a.am = h->last_am; a.an = h->last_an;
-            a.M = h->M; a.N = h->N; a.O = h->cur_nimg;
-            a.Odata = h->O; a.astride = h->cur_astride; a.istride = pdhg_istride(h);
+            a.f = pdhg_f(h); a.alpha = pdhg_alpha(h, x); a.tab = d_tab; a.rho = p.rho;
+            a.am = x.am; a.an = x.an;
+            a.M = h->M; a.N = h->N; a.O = x.nimg;
+            a.Odata = h->O; a.astride = x.astride; a.istride = x.istride;
             a.nTi = pl.nTi; a.nTj = pl.nTj; a.halo = pl.T; a.seg = V.RJ;
             a.img0 = lo;
             a.phase = (phased && c == 0) ? h->d_phase : nullptr;
@@ -750,8 +743,8 @@ int build_graphs(bpltv_t* h, const bpltv_params& p, const Plan& pl, const double
 #endif
             const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
             a.first = (it == 0 && !from_state) ? 1 : 0;
-            a.xin = pdhg_state(h, cur, 0); a.y1in = pdhg_state(h, cur, 1); a.y2in = pdhg_state(h, cur, 2);
-            a.xout = pdhg_state(h, nxt, 0); a.y1out = pdhg_state(h, nxt, 1); a.y2out = pdhg_state(h, nxt, 2);
+            a.xin = pdhg_state(h, x, cur, 0); a.y1in = pdhg_state(h, x, cur, 1); a.y2in = pdhg_state(h, x, cur, 2);
+            a.xout = pdhg_state(h, x, nxt, 0); a.y1out = pdhg_state(h, x, nxt, 1); a.y2out = pdhg_state(h, x, nxt, 2);
             a.it0 = it;
             a.nit = std::min(step, niter - it);
             void* kargs[] = {&a};
@@ -792,23 +785,23 @@ int build_graphs(bpltv_t* h, const bpltv_params& p, const Plan& pl, const double
 
 // Enqueue PDHG iterations [it0, it1) on the stream.  *buf: state set holding the current iterate
 // (ignored when it0 == 0), updated to the set holding the result.
-int enqueue_pdhg(bpltv_t* h, const bpltv_params& p, const Plan& pl, const double* d_tab, int it0, int it1,
+int enqueue_pdhg(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, const Plan& pl, const double* d_tab, int it0, int it1,
                  int* buf, int* launches, bool from_state = false) {
     const Variant& V = kVariants[pl.variant];
     PdhgArgs a;
     a.f = pdhg_f(h);
-    a.alpha = pdhg_alpha(h);
+    a.alpha = pdhg_alpha(h, x);
     a.tab = d_tab;
     a.rho = p.rho;
-    a.am = h->last_am;
-    a.an = h->last_an;
-    a.M = h->M; a.N = h->N; a.O = h->cur_nimg;
-    a.Odata = h->O; a.astride = h->cur_astride; a.istride = pdhg_istride(h);
+    a.am = x.am;
+    a.an = x.an;
+    a.M = h->M; a.N = h->N; a.O = x.nimg;
+    a.Odata = h->O; a.astride = x.astride; a.istride = x.istride;
     a.nTi = pl.nTi; a.nTj = pl.nTj; a.halo = pl.T; a.seg = V.RJ;
     a.img0 = 0;
     a.ntiles = pl.grid;
     a.xcd = (p.reserved[2] & 2) ? 1 : 0;
-    a.grid3d = a.xcd ? 0 : pdhg_grid3d_ok(pl.nTj, h->cur_nimg, V.tiles_per_block);
+    a.grid3d = a.xcd ? 0 : pdhg_grid3d_ok(pl.nTj, x.nimg, V.tiles_per_block);
 #ifdef BPLTV_EXPERIMENTS
     a.dbg = p.reserved[3];
 #endif
@@ -817,8 +810,8 @@ int enqueue_pdhg(bpltv_t* h, const bpltv_params& p, const Plan& pl, const double
         const int nit = std::min(pl.T, it1 - it);
         const int nxt = (it == 0) ? 0 : 1 - cur;
         a.first = (it == 0 && !from_state) ? 1 : 0;
-        a.xin = pdhg_state(h, cur, 0); a.y1in = pdhg_state(h, cur, 1); a.y2in = pdhg_state(h, cur, 2);
-        a.xout = pdhg_state(h, nxt, 0); a.y1out = pdhg_state(h, nxt, 1); a.y2out = pdhg_state(h, nxt, 2);
+        a.xin = pdhg_state(h, x, cur, 0); a.y1in = pdhg_state(h, x, cur, 1); a.y2in = pdhg_state(h, x, cur, 2);
+        a.xout = pdhg_state(h, x, nxt, 0); a.y1out = pdhg_state(h, x, nxt, 1); a.y2out = pdhg_state(h, x, nxt, 2);
         a.it0 = it;
         a.nit = nit;
         (h->dtype == 32 ? V.launch32 : V.launch)(a, pl.grid, h->stream);
@@ -830,21 +823,22 @@ int enqueue_pdhg(bpltv_t* h, const bpltv_params& p, const Plan& pl, const double
     return BPLTV_OK;
 }
 
-int compute_gap(bpltv_t* h, double* gap_host /*O or null*/, double* gap_max_host) {
+// Duality gap per image of the iterate in state set `buf` of the dataset context x (the gap kernels address the O dataset
+// images only, which is why the sweeps switch check_every off).  sr: the three-dual model, seven state planes.
+int compute_gap(bpltv_t* h, const SolveCtx& x, bool sr, int buf, double* gap_host /*O or null*/, double* gap_max_host) {
     h->has_per_image = false;   // d_perimg is about to hold the gaps
     const int nblk = 8;
     int rc = ensure(h, &h->d_red, &h->red_cap, (size_t)h->O * nblk * 4);
     if (rc) return rc;
-    if (h->last_is_sr) {   // three-dual model: the seven state planes of the last sum-of-regularisers solve
-        SrState S;
-        for (int c = 0; c < 7; ++c) S.pl[c] = h->d_sr[h->sr_result_buf][c];
-        hipLaunchKernelGGL(sr_gap_partial_kernel, dim3(nblk, h->O), dim3(256), 0, h->stream, S, h->d_f, h->d_alpha, h->last_am,
-                           h->last_an, h->M, h->N, h->d_red);
+    double* const* S = x.state[buf];
+    if (sr) {
+        SrState Ss;
+        for (int c = 0; c < 7; ++c) Ss.pl[c] = S[c];
+        hipLaunchKernelGGL(sr_gap_partial_kernel, dim3(nblk, h->O), dim3(256), 0, h->stream, Ss, h->d_f, x.alpha, x.am, x.an, h->M,
+                           h->N, h->d_red);
     } else {
-        const int b = h->result_buf;
-        hipLaunchKernelGGL(gap_partial_kernel, dim3(nblk, h->O), dim3(256), 0, h->stream, h->d_state[b][0],
-                           h->d_state[b][1], h->d_state[b][2], h->d_f, h->d_alpha, h->last_am, h->last_an, h->M,
-                           h->N, h->alpha_istride, h->d_red);
+        hipLaunchKernelGGL(gap_partial_kernel, dim3(nblk, h->O), dim3(256), 0, h->stream, S[0], S[1], S[2], h->d_f, x.alpha, x.am,
+                           x.an, h->M, h->N, x.istride, h->d_red);
     }
     hipLaunchKernelGGL(gap_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, nblk, h->O, h->d_perimg,
                        h->d_scalar);
@@ -920,14 +914,15 @@ int launch_chains(bpltv_t* h, const std::vector<hipGraphExec_t>& ex, bool thread
     return BPLTV_OK;
 }
 
-int run_pdhg(bpltv_t* h, const bpltv_params& p) {
+// The TV solve of the context x; *result_buf: the state set of x that holds the result (written on success only).
+int run_pdhg(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, int* result_buf) {
     h->has_per_image = false;
     if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "bpltv_set_data has not been called");
     if (p.maxiter < 0) return set_err(h, BPLTV_E_ARG, "maxiter < 0");
-    if (p.rho != 0.0 && !(h->alpha_min > 0.0))
-        return set_err(h, BPLTV_E_ARG, "rho != 0 divides by alpha: every parameter entry must be > 0 (min = %g)", h->alpha_min);
+    if (p.rho != 0.0 && !(x.alpha_min > 0.0))
+        return set_err(h, BPLTV_E_ARG, "rho != 0 divides by alpha: every parameter entry must be > 0 (min = %g)", x.alpha_min);
     Plan pl;
-    int rc = make_plan(h, p, &pl);
+    int rc = make_plan(h, p, &pl, x.nimg);
     if (rc) return rc;
     // params.init / order (the choices of op_denoise_pdps the reference does not pin): the sequence starts from a
     // prepared state (pdhg_init_kernel) instead of x = f, y = 0; dual-first order = the dual step of iteration 0 in
@@ -941,7 +936,7 @@ int run_pdhg(bpltv_t* h, const bpltv_params& p) {
     if (h->dtype == 32) {
         float* t32 = nullptr;
         rc = get_table32(h, p, &t32);
-        if (!rc && p.maxiter > 0) rc = f32_prepare(h);
+        if (!rc && p.maxiter > 0) rc = f32_prepare(h, x);
         d_tab = reinterpret_cast<double*>(t32);
     } else {
         rc = get_table(h, p, &d_tab, 8.0, p.order ? 1 : 0);
@@ -961,34 +956,33 @@ int run_pdhg(bpltv_t* h, const bpltv_params& p) {
     if (p.maxiter == 0) {  // u = x0 = f (params.init = 1: 0)
         for (int c = 0; c < 3; ++c) {
             if (c == 0 && !p.init) {
-                for (int r = 0; r < h->cur_nimg / h->O; ++r)
-                    HIPCHK(h, hipMemcpyAsync(h->cur_state[0][0] + (size_t)r * h->tot, h->d_f, h->tot * sizeof(double),
+                for (int r = 0; r < x.nimg / h->O; ++r)
+                    HIPCHK(h, hipMemcpyAsync(x.state[0][0] + (size_t)r * h->tot, h->d_f, h->tot * sizeof(double),
                                              hipMemcpyDeviceToDevice, h->stream));
             } else {
-                HIPCHK(h, hipMemsetAsync(h->cur_state[0][c], 0, (size_t)h->cur_nimg * h->npx * sizeof(double), h->stream));
+                HIPCHK(h, hipMemsetAsync(x.state[0][c], 0, (size_t)x.nimg * h->npx * sizeof(double), h->stream));
             }
         }
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        h->result_buf = 0;
-        h->has_result = true;
+        *result_buf = 0;
         h->st.pdhg_ms = 0.0;
         return BPLTV_OK;
     }
     const bool chunked = p.check_every > 0;
-    const size_t total = (size_t)h->cur_nimg * h->npx;
+    const size_t total = (size_t)x.nimg * h->npx;
     const unsigned gtot = (unsigned)((total + 255) / 256);
     HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     if (from_state) {
-        hipLaunchKernelGGL(pdhg_init_kernel, dim3(gtot), dim3(256), 0, h->stream, h->d_f, ctx_alpha(h), h->last_am, h->last_an,
-                           h->M, h->N, h->O, h->cur_astride, pdhg_istride(h), total, p.init ? 1 : 0, p.order ? 1 : 0,
-                           p.sigma0 / opnorm_of(p, 8.0), p.rho, h->cur_state[1][0], h->cur_state[1][1], h->cur_state[1][2]);
+        hipLaunchKernelGGL(pdhg_init_kernel, dim3(gtot), dim3(256), 0, h->stream, h->d_f, x.alpha, x.am, x.an,
+                           h->M, h->N, h->O, x.astride, x.istride, total, p.init ? 1 : 0, p.order ? 1 : 0,
+                           p.sigma0 / opnorm_of(p, 8.0), p.rho, x.state[1][0], x.state[1][1], x.state[1][2]);
         HIPCHK(h, hipGetLastError());
         buf = 1;
     }
     if (!chunked) {
         bool done = main_iters == 0;
         if (p.use_graph && !done) {
-            GraphKey key{main_iters, pl.T, pl.variant, h->last_am, h->last_an, pl.chains, p.rho, p.tau0, p.sigma0, p.accel ? 1 : 0, p.reserved[3] | ((p.reserved[2] & 3) << 16), h->cur_nimg, (const void*)pdhg_state(h, 0, 0), (const void*)d_tab, from_state ? 1 : 0, (const void*)pdhg_alpha(h), pdhg_istride(h)};
+            GraphKey key{main_iters, pl.T, pl.variant, x.am, x.an, pl.chains, p.rho, p.tau0, p.sigma0, p.accel ? 1 : 0, p.reserved[3] | ((p.reserved[2] & 3) << 16), x.nimg, (const void*)pdhg_state(h, x, 0, 0), (const void*)d_tab, from_state ? 1 : 0, (const void*)pdhg_alpha(h, x), x.istride};
             auto it = h->graphs.find(key);
             const int nl = (main_iters + pl.T - 1) / pl.T;
             if (it == h->graphs.end() && h->graphs.size() >= 16) {  // bounded cache
@@ -997,7 +991,7 @@ int run_pdhg(bpltv_t* h, const bpltv_params& p) {
             }
             if (it == h->graphs.end() && nl <= 50000) {  // longer sequences are launched eagerly
                 std::vector<hipGraphExec_t> ex;
-                if (build_graphs(h, p, pl, d_tab, main_iters, from_state, &ex) == BPLTV_OK && !ex.empty()) {
+                if (build_graphs(h, x, p, pl, d_tab, main_iters, from_state, &ex) == BPLTV_OK && !ex.empty()) {
                     h->graphs[key] = ex;
                     it = h->graphs.find(key);
                 }
@@ -1027,28 +1021,27 @@ int run_pdhg(bpltv_t* h, const bpltv_params& p) {
             }
         }
         if (!done) {
-            rc = enqueue_pdhg(h, p, pl, d_tab, 0, main_iters, &buf, &launches, from_state);
+            rc = enqueue_pdhg(h, x, p, pl, d_tab, 0, main_iters, &buf, &launches, from_state);
             if (rc) return rc;
         }
         h->st.iterations = p.maxiter;
         if (h->dtype == 32) {
-            rc = f32_widen(h, buf);
+            rc = f32_widen(h, x, buf);
             if (rc) return rc;
         }
     } else {
         int it = 0;
         while (it < main_iters) {
             const int it1 = std::min(main_iters, it + p.check_every);
-            rc = enqueue_pdhg(h, p, pl, d_tab, it, it1, &buf, &launches, from_state);
+            rc = enqueue_pdhg(h, x, p, pl, d_tab, it, it1, &buf, &launches, from_state);
             if (rc) return rc;
             it = it1;
-            h->result_buf = buf;
             if (h->dtype == 32) {   // the gap kernels read the double state
-                rc = f32_widen(h, buf);
+                rc = f32_widen(h, x, buf);
                 if (rc) return rc;
             }
             double gmax = 0.0;
-            rc = compute_gap(h, nullptr, &gmax);
+            rc = compute_gap(h, x, false, buf, nullptr, &gmax);   // of the set this chunk just wrote
             if (rc) return rc;
             h->st.last_gap = gmax;
             if (p.gap_tol > 0.0 && gmax <= p.gap_tol) break;
@@ -1056,8 +1049,8 @@ int run_pdhg(bpltv_t* h, const bpltv_params& p) {
         h->st.iterations = it + ((p.order && it == main_iters) ? 1 : 0);
     }
     if (p.order && h->st.iterations == p.maxiter) {   // dual-first: the primal step of the last iteration
-        hipLaunchKernelGGL(pdhg_xstep_kernel, dim3(gtot), dim3(256), 0, h->stream, h->d_f, h->cur_state[buf][1], h->cur_state[buf][2],
-                           d_tab + (size_t)TAB_STRIDE * (p.maxiter - 1), h->M, h->N, h->O, total, h->cur_state[buf][0]);
+        hipLaunchKernelGGL(pdhg_xstep_kernel, dim3(gtot), dim3(256), 0, h->stream, h->d_f, x.state[buf][1], x.state[buf][2],
+                           d_tab + (size_t)TAB_STRIDE * (p.maxiter - 1), h->M, h->N, h->O, total, x.state[buf][0]);
         HIPCHK(h, hipGetLastError());
     }
     HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
@@ -1066,12 +1059,10 @@ int run_pdhg(bpltv_t* h, const bpltv_params& p) {
     HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
     h->st.pdhg_ms = ms;
     h->st.launches = launches;
-    h->result_buf = buf;
-    h->has_result = true;
-    h->last_is_sr = false;
-    const bool amap = (h->last_am == h->M && h->last_an == h->N) && !(h->M == 1 && h->N == 1);
+    *result_buf = buf;
+    const bool amap = (x.am == h->M && x.an == h->N) && !(h->M == 1 && h->N == 1);
     h->st.bytes_per_px_iter = (amap ? 64.0 : 56.0) * (h->dtype == 32 ? 0.5 : 1.0);
-    h->st.algorithmic_bytes = h->st.bytes_per_px_iter * (double)h->npx * h->cur_nimg * h->st.iterations;
+    h->st.algorithmic_bytes = h->st.bytes_per_px_iter * (double)h->npx * x.nimg * h->st.iterations;
     return BPLTV_OK;
 }
 
@@ -1547,9 +1538,10 @@ int run_gradient(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, const
     return rc;
 }
 
-bpltv_params resolve(const bpltv_params* p) {
+// sr: the defaults of the sum-of-regularisers model (bpltv_sumregs_default_params: another delta_t)
+bpltv_params resolve(const bpltv_params* p, bool sr = false) {
     bpltv_params q;
-    if (p) q = *p; else bpltv_default_params(&q);
+    if (p) q = *p; else if (sr) bpltv_sumregs_default_params(&q); else bpltv_default_params(&q);
     return q;
 }
 
@@ -1572,46 +1564,6 @@ struct WallTimer {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 };
-
-int evaluate_common(bpltv_t* h, const double* alpha, int am, int an, double delta, const bpltv_params* pp,
-                    double* u_out, double* d_partial_user, double* partial_host) {
-    if (!h) return BPLTV_E_ARG;
-    WallTimer wt;
-    HIPCHK(h, hipSetDevice(h->device));
-    bpltv_params p = resolve(pp);
-    if (int prc = check_params(h, p)) return prc;
-    int rc = upload_alpha(h, alpha, am, an, &p, PRE_TV | pre_gradient(delta, p, am, an));
-    if (rc) return rc;
-    if (h->band_ready && h->adj_hbm && p.reserved[4] == 1) {   // HBM band path: zero the band while the PDHG solve runs
-        const int prc = h->hb.prefill_async();
-        if (prc) return set_err(h, prc, "adjoint gradient (HBM band): %s", h->hb.err.c_str());
-    }
-    rc = run_pdhg(h, p);
-    if (rc) return rc;
-    const double* d_u = h->d_state[h->result_buf][0];
-    HIPCHK(h, hipEventRecord(h->ev[4], h->stream));
-    rc = compute_cost(h, d_u, h->d_ubar, h->d_partial);
-    if (rc) return rc;
-    HIPCHK(h, hipEventRecord(h->ev[5], h->stream));
-    const int reg = !(delta > p.delta_t);  // TVLearningFunctionVec.jl:21-25
-    rc = run_gradient(h, d_u, gradient_ctx(h, h->d_ubar, h->d_partial + 1), reg, p);
-    if (rc) return rc;
-    const size_t np = 1 + (size_t)am * an;
-    if (d_partial_user)
-        HIPCHK(h, hipMemcpyAsync(d_partial_user, h->d_partial, np * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    if (partial_host)
-        HIPCHK(h, hipMemcpyAsync(partial_host, h->d_partial, np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (u_out)
-        HIPCHK(h, hipMemcpyAsync(u_out, d_u, h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[4], h->ev[5]));
-    h->st.cost_ms = ms;
-    h->st.total_ms = wt.ms();
-    h->has_per_image = !(am == h->M && an == h->N && !(h->M == 1 && h->N == 1));
-    return BPLTV_OK;
-}
-
 
 int run_sr_gradient(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, const bpltv_params& p);
 
@@ -1636,14 +1588,8 @@ int vjp_common(bpltv_t* h, const double* d_u, const double* alpha, bool alpha_de
     if (sr && p.reserved[4] == 2) return set_err(h, BPLTV_E_UNSUPPORTED, "block cyclic reduction applies to the TV model only");
     const size_t P = (size_t)slices * am * an * (each ? h->O : 1);
     double amin = 0.0;
-    if (!alpha_dev) {   // as upload_alpha
-        amin = alpha[0];
-        for (size_t e = 0; e < P; ++e) {
-            if (!std::isfinite(alpha[e]) || alpha[e] < 0.0)
-                return set_err(h, BPLTV_E_ARG, "vjp: alpha[%zu] = %g: parameters must be finite and >= 0", e, alpha[e]);
-            if (alpha[e] < amin) amin = alpha[e];
-        }
-    }
+    if (!alpha_dev)
+        if (int crc = check_alpha_host(h, "vjp: alpha", alpha, P, &amin)) return crc;
     int rc = ensure(h, &h->d_vjp, &h->vjp_cap, 4 + 2 * P);
     if (rc) return rc;
     // check words: [0] smallest parameter entry (bits), [1] parameter rejected, [2] cotangent not finite
@@ -1695,9 +1641,9 @@ constexpr int SR_NVARIANTS = 2;
 // What run_pdhg (what = PRE_TV) or run_sr_pdhg (PRE_SR) would reject in a solve of the dataset context with a parameter
 // whose smallest entry is amin; PRE_GRADIENT adds what run_gradient / run_sr_gradient_once reject on the parameters and the
 // shape alone (block cyclic reduction where it does not apply; gradient_reg with a patch or map parameter that has a zero
-// entry, PRE_REG_ARRAY).  The entry points check this before the upload, so that a rejected call leaves the handle --
-// d_alpha, its shape and minimum, the last result, and so bpltv_duality_gap -- as it was (sr_check_blocks does the same
-// for sweeps).
+// entry, PRE_REG_ARRAY).  upload_alpha checks this before it touches the handle, so that a rejected call leaves it --
+// d_alpha, its shape and minimum, the last result, and so bpltv_duality_gap -- as it was (the sweeps check the same
+// before they change anything).
 int solve_precheck(bpltv_t* h, const bpltv_params& p, double amin, int what) {
     if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "bpltv_set_data has not been called");
     if (p.maxiter < 0) return set_err(h, BPLTV_E_ARG, "maxiter < 0");
@@ -1706,7 +1652,7 @@ int solve_precheck(bpltv_t* h, const bpltv_params& p, double amin, int what) {
     const bool sr = (what & PRE_SR) != 0;
     if (!sr) {
         Plan pl;
-        if (int rc = make_plan(h, p, &pl)) return rc;
+        if (int rc = make_plan(h, p, &pl, h->O)) return rc;
         if ((p.init != 0 || p.order != 0) && h->dtype == 32)
             return set_err(h, BPLTV_E_UNSUPPORTED, "params.init / params.order are implemented for dtype = 64 handles");
     } else {
@@ -1735,52 +1681,6 @@ void drop_sr_graphs(bpltv_t* h) {
     h->sr_graphs.clear();
 }
 
-int sr_upload_alpha(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* solve = nullptr, int what = PRE_SR) {
-    if (!alpha || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "alpha: null pointer or empty shape");
-    if (am > h->M || an > h->N) return set_err(h, BPLTV_E_ARG, "alpha shape %dx%dx3 exceeds image %dx%d", am, an, h->M, h->N);
-    const size_t need = 3 * (size_t)am * an;
-    double amin = alpha[0];
-    for (size_t e = 0; e < need; ++e) {
-        if (!std::isfinite(alpha[e]) || alpha[e] < 0.0)
-            return set_err(h, BPLTV_E_ARG, "alpha[%zu] = %g: parameters must be finite and >= 0", e, alpha[e]);
-        if (alpha[e] < amin) amin = alpha[e];
-    }
-    if (solve)
-        if (int rc = solve_precheck(h, *solve, amin, what)) return rc;
-    h->alpha_min = amin;
-    if (h->alpha_cap < need) {
-        drop_graphs(h);
-        drop_sr_graphs(h);
-        int rc = ensure(h, &h->d_alpha, &h->alpha_cap, need);
-        if (rc) return rc;
-    }
-    if (h->partial_cap < need + 1) {
-        int rc = ensure(h, &h->d_partial, &h->partial_cap, need + 1);
-        if (rc) return rc;
-    }
-    HIPCHK(h, hipMemcpyAsync(h->d_alpha, alpha, need * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    h->last_am = am; h->last_an = an; h->last_slices = 3; h->alpha_istride = 0;
-    return BPLTV_OK;
-}
-
-// The K parameter blocks of a sum-of-regularisers sweep (3*am*an doubles each): finite and >= 0, and > 0 when rho != 0 --
-// sr_upload_alpha's and run_sr_pdhg's conditions, checked before the call changes anything.
-int sr_check_blocks(bpltv_t* h, const double* alphas, int K, int am, int an, double rho, double* amin_out) {
-    if (!alphas || K < 1) return set_err(h, BPLTV_E_ARG, "sumregs_sweep: null pointer or K < 1");
-    if (am < 1 || an < 1 || am > h->M || an > h->N) return set_err(h, BPLTV_E_ARG, "sumregs_sweep: bad parameter shape %dx%dx3", am, an);
-    const size_t n = (size_t)K * 3 * am * an;
-    double amin = alphas[0];
-    for (size_t e = 0; e < n; ++e) {
-        if (!std::isfinite(alphas[e]) || alphas[e] < 0.0)
-            return set_err(h, BPLTV_E_ARG, "sumregs_sweep: alphas[%zu] = %g: parameters must be finite and >= 0", e, alphas[e]);
-        if (alphas[e] < amin) amin = alphas[e];
-    }
-    if (rho != 0.0 && !(amin > 0.0))
-        return set_err(h, BPLTV_E_ARG, "rho != 0 divides by alpha: every parameter entry must be > 0 (min = %g)", amin);
-    if (amin_out) *amin_out = amin;
-    return BPLTV_OK;
-}
-
 int sr_alloc(bpltv_t* h) {
     if (h->sr_ready) return BPLTV_OK;
     for (int s = 0; s < 2; ++s)
@@ -1792,23 +1692,23 @@ int sr_alloc(bpltv_t* h) {
     return BPLTV_OK;
 }
 
-// maxiter iterations of the three-dual PDHG, T fused per launch (halo 2T), replayed from a hipGraph, on the current solve
-// context: h->sr_cur_nimg problems in the state sets h->sr_cur; problem img reads f[img % O] and the parameter block
-// img / O (sr_cur_astride doubles apart) of sr_cur_alpha (d_alpha when null).
-int run_sr_pdhg(bpltv_t* h, const bpltv_params& p) {
+// maxiter iterations of the three-dual PDHG, T fused per launch (halo 2T), replayed from a hipGraph, on the solve context
+// x: x.nimg problems in the state sets x.state; problem img reads f[img % O] and the parameter block img / O (x.astride
+// doubles apart) of x.alpha.  *result_buf: the state set that holds the result (written on success only).
+int run_sr_pdhg(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, int* result_buf) {
     h->has_per_image = false;
     if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "bpltv_set_data has not been called");
     if (p.maxiter < 0) return set_err(h, BPLTV_E_ARG, "maxiter < 0");
-    if (p.rho != 0.0 && !(h->alpha_min > 0.0))
-        return set_err(h, BPLTV_E_ARG, "rho != 0 divides by alpha: every parameter entry must be > 0 (min = %g)", h->alpha_min);
+    if (p.rho != 0.0 && !(x.alpha_min > 0.0))
+        return set_err(h, BPLTV_E_ARG, "rho != 0 divides by alpha: every parameter entry must be > 0 (min = %g)", x.alpha_min);
     int rc = sr_alloc(h);
     if (rc) return rc;
     double* d_tab = nullptr;
     if (p.init != 0 || p.order != 0)
         return set_err(h, BPLTV_E_UNSUPPORTED, "params.init / params.order are implemented for the TV model only");
-    const int nimg = h->sr_cur_nimg;
-    double* (*S)[7] = h->sr_cur;
-    const double* d_alpha = h->sr_cur_alpha ? h->sr_cur_alpha : h->d_alpha;
+    const int nimg = x.nimg;
+    double* const* const* S = x.state;   // the planes exist from sr_alloc on (the dataset context points into the handle)
+    const double* d_alpha = x.alpha;
     if (nimg > 65535) return set_err(h, BPLTV_E_UNSUPPORTED, "the sum-of-regularisers solve takes at most 65535 problems per launch (problems are a grid dimension)");
     rc = get_table(h, p, &d_tab, 18.0);   // ||G_f||^2 + ||G_b||^2 + ||G_c||^2 <= 8 + 8 + 2 (sumregs_oracle.c: SR_L)
     if (rc) return rc;
@@ -1847,7 +1747,7 @@ int run_sr_pdhg(bpltv_t* h, const bpltv_params& p) {
             HIPCHK(h, hipMemcpyAsync(S[0][0] + (size_t)r * h->tot, h->d_f, h->tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         for (int c = 1; c < 7; ++c) HIPCHK(h, hipMemsetAsync(S[0][c], 0, (size_t)nimg * h->npx * sizeof(double), h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        h->sr_result_buf = 0; h->sr_has_result = true; h->last_is_sr = true; h->st.pdhg_ms = 0.0;
+        *result_buf = 0; h->st.pdhg_ms = 0.0;
         return BPLTV_OK;
     }
     void (*kern)(SrArgs) = nimg == h->O ? V.kernel : V.sweep_kernel;
@@ -1860,12 +1760,12 @@ int run_sr_pdhg(bpltv_t* h, const bpltv_params& p) {
             const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
             for (int c = 0; c < 7; ++c) { a.in[c] = S[cur][c]; a.out[c] = S[nxt][c]; }
             a.f = h->d_f; a.alpha = d_alpha; a.tab = d_tab; a.rho = p.rho;
-            a.am = h->last_am; a.an = h->last_an;
+            a.am = x.am; a.an = x.an;
             a.it0 = it; a.nit = std::min(step, it1 - it);
             a.M = M; a.N = N; a.O = nimg; a.nTi = nTi; a.nTj = nTj; a.halo = 2 * T;
             a.first = (it == 0) ? 1 : 0;
             a.img0 = lo;
-            a.Odata = h->O; a.astride = h->sr_cur_astride;
+            a.Odata = h->O; a.astride = x.astride;
             hipLaunchKernelGGL(kern, dim3(nTi, nTj, hi - lo), dim3(V.threads), V.lds, st, a);
             cur = nxt;
         }
@@ -1875,17 +1775,14 @@ int run_sr_pdhg(bpltv_t* h, const bpltv_params& p) {
     if (p.check_every > 0) {   // duality-gap checks every check_every iterations, early stop at gap_tol (as the TV model)
         HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
         int it = 0, cur = 0, launches = 0;
-        h->last_is_sr = true;
         while (it < p.maxiter) {
             const int it1 = std::min(p.maxiter, it + p.check_every);
             cur = enqueue_range(h->stream, it, it1, cur, 0, h->O, false);
             launches += (it1 - it + T - 1) / T;
             it = it1;
             HIPCHK(h, hipGetLastError());
-            h->sr_result_buf = cur;
-            h->sr_has_result = true;
             double gmax = 0.0;
-            rc = compute_gap(h, nullptr, &gmax);
+            rc = compute_gap(h, x, true, cur, nullptr, &gmax);   // of the set this chunk just wrote
             if (rc) return rc;
             h->st.last_gap = gmax;
             if (p.gap_tol > 0.0 && gmax <= p.gap_tol) break;
@@ -1897,7 +1794,8 @@ int run_sr_pdhg(bpltv_t* h, const bpltv_params& p) {
         h->st.pdhg_ms = ms2;
         h->st.launches = launches;
         h->st.iterations = it;
-        const bool amap2 = (h->last_am == M && h->last_an == N) && !(M == 1 && N == 1);
+        *result_buf = cur;
+        const bool amap2 = (x.am == M && x.an == N) && !(M == 1 && N == 1);
         h->st.bytes_per_px_iter = amap2 ? 144.0 : 120.0;
         h->st.algorithmic_bytes = h->st.bytes_per_px_iter * (double)h->tot * it;
         return BPLTV_OK;
@@ -1913,7 +1811,7 @@ int run_sr_pdhg(bpltv_t* h, const bpltv_params& p) {
     HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
     bool done = false;
     if (p.use_graph && nl <= 50000) {
-        SrGraphKey key{p.maxiter, T, h->last_am, h->last_an, p.accel ? 1 : 0, vi + 16 * nch, p.rho, p.tau0, p.sigma0, (const void*)d_tab,
+        SrGraphKey key{p.maxiter, T, x.am, x.an, p.accel ? 1 : 0, vi + 16 * nch, p.rho, p.tau0, p.sigma0, (const void*)d_tab,
                        nimg, (const void*)S[0][0], (const void*)d_alpha};
         auto it = h->sr_graphs.find(key);
         if (it == h->sr_graphs.end()) {
@@ -1960,10 +1858,8 @@ int run_sr_pdhg(bpltv_t* h, const bpltv_params& p) {
     HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
     h->st.pdhg_ms = ms;
     h->st.launches = done ? nl * nch + ((nch > 1 && stag) ? 1 : 0) : nl;
-    h->sr_result_buf = buf;
-    h->sr_has_result = true;
-    h->last_is_sr = true;
-    const bool amap = (h->last_am == M && h->last_an == N) && !(M == 1 && N == 1);
+    *result_buf = buf;
+    const bool amap = (x.am == M && x.an == N) && !(M == 1 && N == 1);
     h->st.bytes_per_px_iter = amap ? 144.0 : 120.0;   // read x, 6 y, f (+ 3 alpha), write x, 6 y
     h->st.algorithmic_bytes = h->st.bytes_per_px_iter * (double)h->npx * nimg * p.maxiter;
     return BPLTV_OK;
@@ -2184,29 +2080,74 @@ int run_sr_gradient(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, co
     return rc;
 }
 
-// sumregs_learning_function(x, data, D): SumRegsLearningFunction.jl:8-36.  partial: [cost, grad (3*am*an)...]
-int sr_evaluate_common(bpltv_t* h, const double* alpha, int am, int an, double delta, const bpltv_params* pp, double* u_out,
-                       double* partial_host) {
+// One solve of the dataset context (TV, or sr: sum of regularisers).  The result is committed to the handle here, after
+// the solve succeeded -- the only place where result_buf / has_result / last_is_sr and their sr_ twins are written.
+int solve_dataset(bpltv_t* h, bool sr, const bpltv_params& p) {
+    int buf = 0;
+    const SolveCtx x = dataset_ctx(h, sr);
+    const int rc = sr ? run_sr_pdhg(h, x, p, &buf) : run_pdhg(h, x, p, &buf);
+    if (rc) return rc;
+    (sr ? h->sr_result_buf : h->result_buf) = buf;
+    (sr ? h->sr_has_result : h->has_result) = true;
+    h->last_is_sr = sr;
+    return BPLTV_OK;
+}
+// u of the last solve of the model
+inline const double* result_u(const bpltv_t* h, bool sr) { return sr ? h->d_sr[h->sr_result_buf][0] : h->d_state[h->result_buf][0]; }
+
+// The six bpltv_*denoise* entry points on a single-device handle: the parameter from the host or (alpha_dev) from HBM,
+// blocks = 1 or O (bpltv_denoise_each), u copied to the host when u_out is given.
+int denoise_common(bpltv_t* h, bool sr, const double* alpha, bool alpha_dev, int am, int an, int blocks, const bpltv_params* pp,
+                   double* u_out) {
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    const bpltv_params p = resolve(pp, sr);
+    if (int prc = check_params(h, p)) return prc;
+    int rc = upload_alpha(h, alpha, alpha_dev, am, an, sr ? PRE_SR : PRE_TV, blocks, &p);
+    if (rc) return rc;
+    rc = solve_dataset(h, sr, p);
+    if (rc) return rc;
+    if (u_out) {
+        HIPCHK(h, hipMemcpyAsync(u_out, result_u(h, sr), h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
+// tv_op_learning_function (TVLearningFunctionVec.jl:14-27) and, sr, sumregs_learning_function (SumRegsLearningFunction.jl:
+// 8-36) on a single-device handle.  partial: [cost, grad (slices*am*an)...], to HBM (d_partial_user, TV only) and / or the host.
+int evaluate_common(bpltv_t* h, bool sr, const double* alpha, int am, int an, double delta, const bpltv_params* pp,
+                    double* u_out, double* d_partial_user, double* partial_host) {
     if (!h) return BPLTV_E_ARG;
     WallTimer wt;
     HIPCHK(h, hipSetDevice(h->device));
-    bpltv_params p = resolve(pp);
+    const bpltv_params p = resolve(pp, sr);
     if (int prc = check_params(h, p)) return prc;
-    const int reg = !(delta > p.delta_t);   // SumRegsLearningFunction.jl:14-18, 30-34
-    int rc = sr_upload_alpha(h, alpha, am, an, &p, PRE_SR | pre_gradient(delta, p, am, an));
+    int rc = upload_alpha(h, alpha, false, am, an, (sr ? PRE_SR : PRE_TV) | pre_gradient(delta, p, am, an), 1, &p);
     if (rc) return rc;
-    rc = run_sr_pdhg(h, p);
+    if (!sr && h->band_ready && h->adj_hbm && p.reserved[4] == 1) {   // HBM band path: zero the band while the PDHG solve runs
+        const int prc = h->hb.prefill_async();
+        if (prc) return set_err(h, prc, "adjoint gradient (HBM band): %s", h->hb.err.c_str());
+    }
+    rc = solve_dataset(h, sr, p);
     if (rc) return rc;
-    const double* d_u = h->d_sr[h->sr_result_buf][0];
+    const double* d_u = result_u(h, sr);
     HIPCHK(h, hipEventRecord(h->ev[4], h->stream));
     rc = compute_cost(h, d_u, h->d_ubar, h->d_partial);
     if (rc) return rc;
     HIPCHK(h, hipEventRecord(h->ev[5], h->stream));
-    rc = run_sr_gradient(h, d_u, gradient_ctx(h, h->d_ubar, h->d_partial + 1), reg, p);
+    const int reg = !(delta > p.delta_t);  // TVLearningFunctionVec.jl:21-25; SumRegsLearningFunction.jl:14-18, 30-34
+    const GradCtx g = gradient_ctx(h, h->d_ubar, h->d_partial + 1);
+    rc = sr ? run_sr_gradient(h, d_u, g, reg, p) : run_gradient(h, d_u, g, reg, p);
     if (rc) return rc;
-    const size_t np = 1 + 3 * (size_t)am * an;
-    if (partial_host) HIPCHK(h, hipMemcpyAsync(partial_host, h->d_partial, np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (u_out) HIPCHK(h, hipMemcpyAsync(u_out, d_u, h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    const size_t np = 1 + (size_t)(sr ? 3 : 1) * am * an;
+    if (d_partial_user)
+        HIPCHK(h, hipMemcpyAsync(d_partial_user, h->d_partial, np * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    if (partial_host)
+        HIPCHK(h, hipMemcpyAsync(partial_host, h->d_partial, np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (u_out)
+        HIPCHK(h, hipMemcpyAsync(u_out, d_u, h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     float ms = 0.f;
     HIPCHK(h, hipEventElapsedTime(&ms, h->ev[4], h->ev[5]));
@@ -2453,12 +2394,8 @@ int multi_denoise(bpltv_t* h, const double* alpha, int am, int an, const bpltv_p
     if (each) {
         if (!alpha || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "alpha: null pointer or empty shape");
         const bpltv_params p = resolve(pp);
-        double amin = alpha[0];
-        for (size_t e = 0; e < (size_t)h->O * P; ++e) {
-            if (!std::isfinite(alpha[e]) || alpha[e] < 0.0)
-                return set_err(h, BPLTV_E_ARG, "alpha[%zu] = %g: parameters must be finite and >= 0", e, alpha[e]);
-            if (alpha[e] < amin) amin = alpha[e];
-        }
+        double amin = 0.0;
+        if (int crc = check_alpha_host(h, "alpha", alpha, (size_t)h->O * P, &amin)) return crc;
         if (p.rho != 0.0 && !(amin > 0.0))
             return set_err(h, BPLTV_E_ARG, "rho != 0 divides by alpha: every parameter entry must be > 0 (min = %g)", amin);
     }
@@ -2485,8 +2422,7 @@ int multi_evaluate(bpltv_t* h, const double* alpha, int am, int an, double delta
     const bpltv_params p = resolve(pp);
     int rc = multi_run(h, [&](int k, bpltv_t* c) {
         double* uo = u_out ? u_out + ms.lo[k] * npx : nullptr;
-        return slices == 3 ? sr_evaluate_common(c, alpha, am, an, delta, pp, uo, nullptr)
-                           : evaluate_common(c, alpha, am, an, delta, pp, uo, nullptr, nullptr);
+        return evaluate_common(c, slices == 3, alpha, am, an, delta, pp, uo, nullptr, nullptr);
     });
     if (rc) return rc;
     const bool amap = (am == h->M && an == h->N) && !(h->M == 1 && h->N == 1);
@@ -2707,10 +2643,48 @@ int multi_sweep(bpltv_t* h, const double* alphas, int K, int am, int an, const b
     return multi_stats(h);
 }
 
-int multi_unsupported(bpltv_t* h, const char* what) {
-    if (h->multi->shard.size() == 1) return -1;   // one shard: forward to it
-    return set_err(h, BPLTV_E_UNSUPPORTED, "%s takes a device pointer, which is ambiguous on a handle over %zu shards; use the host-array entry points",
-                   what, h->multi->shard.size());
+// An entry point that takes or returns a device pointer, on a multi-device handle: ambiguous over several shards, forwarded
+// (call(shard 0)) when one shard holds everything.  The shard's error text becomes the handle's; what a successful call
+// leaves on the multi handle (has_result, has_data, multi_stats) is the caller's.
+template <class F>
+int multi_forward0(bpltv_t* h, const char* what, F call) {
+    MultiState& ms = *h->multi;
+    if (ms.shard.size() != 1)
+        return set_err(h, BPLTV_E_UNSUPPORTED, "%s takes a device pointer, which is ambiguous on a handle over %zu shards; use the host-array entry points",
+                       what, ms.shard.size());
+    const int r = call(ms.shard[0]);
+    if (r) h->err = ms.shard[0]->err;
+    return r;
+}
+// ... of an entry point that solves: afterwards the multi handle has a result, and the shard's statistics are its own
+template <class F>
+int multi_forward0_solve(bpltv_t* h, const char* what, F call) {
+    const int r = multi_forward0(h, what, call);
+    if (r == BPLTV_OK) { h->has_result = true; multi_stats(h); }
+    return r;
+}
+
+// The tail of a sweep (or of one group of it): the loss of every problem of the kb parameter blocks x O images in d_u against
+// ubar[img % O], summed per parameter block on the host in image order (the order is in the last bit of cost_out);
+// u to the host when u_out is given.  d_cost: kb * O doubles of scratch.
+int sweep_tail(bpltv_t* h, const double* d_u, int kb, double* d_cost, double* cost_out, double* u_out) {
+    const int nblk = 16, O = h->O, np = kb * O;
+    int rc = ensure(h, &h->d_red, &h->red_cap, (size_t)np * nblk);
+    if (rc) return rc;
+    hipLaunchKernelGGL(cost_partial_mod_kernel, dim3(nblk, (unsigned)np), dim3(256), 0, h->stream, d_u, h->d_ubar, (int)h->npx, O,
+                       h->d_red);
+    hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, nblk, np, 0.5, d_cost, (double*)nullptr);
+    HIPCHK(h, hipGetLastError());
+    std::vector<double> per(np);
+    HIPCHK(h, hipMemcpyAsync(per.data(), d_cost, (size_t)np * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (u_out) HIPCHK(h, hipMemcpyAsync(u_out, d_u, (size_t)np * h->npx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int k = 0; k < kb; ++k) {
+        double sacc = 0.0;
+        for (int i = 0; i < O; ++i) sacc += per[(size_t)k * O + i];
+        cost_out[k] = sacc;
+    }
+    return BPLTV_OK;
 }
 
 // bpltv_vjp (slices = 1) and bpltv_sumregs_vjp (3): host arrays staged in d_u2 / d_ubar2 / d_gf2, the parameter gradient
@@ -2752,10 +2726,10 @@ int vjp_device(bpltv_t* h, const double* d_u, const double* d_alpha, int am, int
                const double* d_gu, double* d_grad_f, double* d_grad_alpha, int slices, bool each = false) {
     if (!h) return BPLTV_E_ARG;
     if (h->multi) {
-        const int rc = multi_unsupported(h, each ? "bpltv_vjp_each_device" : (slices == 3 ? "bpltv_sumregs_vjp_device" : "bpltv_vjp_device"));
-        if (rc >= 0) return rc;
-        const int r = vjp_device(h->multi->shard[0], d_u, d_alpha, am, an, reg, pp, d_gu, d_grad_f, d_grad_alpha, slices, each);
-        if (r) h->err = h->multi->shard[0]->err; else { h->has_per_image = false; multi_stats(h); }
+        const int r = multi_forward0(h, each ? "bpltv_vjp_each_device" : (slices == 3 ? "bpltv_sumregs_vjp_device" : "bpltv_vjp_device"), [&](bpltv_t* c) {
+            return vjp_device(c, d_u, d_alpha, am, an, reg, pp, d_gu, d_grad_f, d_grad_alpha, slices, each);
+        });
+        if (r == BPLTV_OK) { h->has_per_image = false; multi_stats(h); }   // no solve ran: has_result stays
         return r;
     }
     WallTimer wt;
@@ -2829,12 +2803,6 @@ int bpltv_create(bpltv_t** out, int M, int N, int O, int device, int dtype) {
     HIPCHK(h, hipMalloc((void**)&h->d_f, h->tot * sizeof(double)));
     for (int s = 0; s < 2; ++s)
         for (int c = 0; c < 3; ++c) HIPCHK(h, hipMalloc((void**)&h->d_state[s][c], h->tot * sizeof(double)));
-    h->cur_state = h->d_state;
-    h->cur_nimg = O;
-    h->cur_astride = 0;
-    h->sr_cur = h->d_sr;
-    h->sr_cur_nimg = O;
-    h->sr_cur_astride = 0;
     HIPCHK(h, hipMalloc((void**)&h->d_perimg, (size_t)O * sizeof(double)));
     HIPCHK(h, hipMalloc((void**)&h->d_scalar, 4 * sizeof(double)));
     // LDS above 64 KB needs the opt-in attribute
@@ -2940,10 +2908,8 @@ int bpltv_set_data(bpltv_t* h, const double* ubar, const double* f) {
 
 int bpltv_set_data_device(bpltv_t* h, const double* d_ubar, const double* d_f) {
     if (h && h->multi) {
-        const int rc = multi_unsupported(h, "bpltv_set_data_device");
-        if (rc >= 0) return rc;
-        const int r = bpltv_set_data_device(h->multi->shard[0], d_ubar, d_f);
-        if (r) h->err = h->multi->shard[0]->err; else h->has_data = true;
+        const int r = multi_forward0(h, "bpltv_set_data_device", [&](bpltv_t* c) { return bpltv_set_data_device(c, d_ubar, d_f); });
+        if (r == BPLTV_OK) h->has_data = true;
         return r;
     }
     return set_data_impl(h, d_ubar, d_f, hipMemcpyDeviceToDevice);
@@ -2952,85 +2918,29 @@ int bpltv_set_data_device(bpltv_t* h, const double* d_ubar, const double* d_f) {
 int bpltv_denoise(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, double* u_out) {
     if (!h) return BPLTV_E_ARG;
     if (h->multi) return multi_denoise(h, alpha, am, an, pp, u_out);
-    WallTimer wt;
-    HIPCHK(h, hipSetDevice(h->device));
-    bpltv_params p = resolve(pp);
-    if (int prc = check_params(h, p)) return prc;
-    int rc = upload_alpha(h, alpha, am, an, &p);
-    if (rc) return rc;
-    rc = run_pdhg(h, p);
-    if (rc) return rc;
-    if (u_out) {
-        HIPCHK(h, hipMemcpyAsync(u_out, h->d_state[h->result_buf][0], h->tot * sizeof(double), hipMemcpyDeviceToHost,
-                                 h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    h->st.total_ms = wt.ms();
-    return BPLTV_OK;
+    return denoise_common(h, false, alpha, false, am, an, 1, pp, u_out);
 }
 
 int bpltv_denoise_device(bpltv_t* h, const double* d_alpha, int am, int an, const bpltv_params* pp) {
     if (!h) return BPLTV_E_ARG;
-    if (h->multi) {
-        const int rc = multi_unsupported(h, "bpltv_denoise_device");
-        if (rc >= 0) return rc;
-        const int r = bpltv_denoise_device(h->multi->shard[0], d_alpha, am, an, pp);
-        if (r) h->err = h->multi->shard[0]->err; else { h->has_result = true; multi_stats(h); }
-        return r;
-    }
-    WallTimer wt;
-    HIPCHK(h, hipSetDevice(h->device));
-    bpltv_params p = resolve(pp);
-    if (int prc = check_params(h, p)) return prc;
-    int rc = upload_alpha_device(h, d_alpha, am, an, &p);
-    if (rc) return rc;
-    rc = run_pdhg(h, p);
-    if (rc) return rc;
-    h->st.total_ms = wt.ms();
-    return BPLTV_OK;
+    if (h->multi)
+        return multi_forward0_solve(h, "bpltv_denoise_device", [&](bpltv_t* c) { return bpltv_denoise_device(c, d_alpha, am, an, pp); });
+    return denoise_common(h, false, d_alpha, true, am, an, 1, pp, nullptr);
 }
 
-// bpltv_denoise / bpltv_denoise_device with one parameter block per image: upload_alpha(_device) with O blocks, after
-// which the PDHG and gap kernels of the dataset context address block k for image k (h->alpha_istride).
+// bpltv_denoise / bpltv_denoise_device with one parameter block per image: upload_alpha with O blocks, after which the
+// PDHG and gap kernels of the dataset context address block k for image k (h->alpha_istride).
 int bpltv_denoise_each(bpltv_t* h, const double* alphas, int am, int an, const bpltv_params* pp, double* u_out) {
     if (!h) return BPLTV_E_ARG;
     if (h->multi) return multi_denoise(h, alphas, am, an, pp, u_out, 1, true);
-    WallTimer wt;
-    HIPCHK(h, hipSetDevice(h->device));
-    bpltv_params p = resolve(pp);
-    if (int prc = check_params(h, p)) return prc;
-    int rc = upload_alpha(h, alphas, am, an, &p, PRE_TV, h->O);
-    if (rc) return rc;
-    rc = run_pdhg(h, p);
-    if (rc) return rc;
-    if (u_out) {
-        HIPCHK(h, hipMemcpyAsync(u_out, h->d_state[h->result_buf][0], h->tot * sizeof(double), hipMemcpyDeviceToHost,
-                                 h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    h->st.total_ms = wt.ms();
-    return BPLTV_OK;
+    return denoise_common(h, false, alphas, false, am, an, h->O, pp, u_out);
 }
 
 int bpltv_denoise_each_device(bpltv_t* h, const double* d_alphas, int am, int an, const bpltv_params* pp) {
     if (!h) return BPLTV_E_ARG;
-    if (h->multi) {
-        const int rc = multi_unsupported(h, "bpltv_denoise_each_device");
-        if (rc >= 0) return rc;
-        const int r = bpltv_denoise_each_device(h->multi->shard[0], d_alphas, am, an, pp);
-        if (r) h->err = h->multi->shard[0]->err; else { h->has_result = true; multi_stats(h); }
-        return r;
-    }
-    WallTimer wt;
-    HIPCHK(h, hipSetDevice(h->device));
-    bpltv_params p = resolve(pp);
-    if (int prc = check_params(h, p)) return prc;
-    int rc = upload_alpha_device(h, d_alphas, am, an, &p, PRE_TV, h->O);
-    if (rc) return rc;
-    rc = run_pdhg(h, p);
-    if (rc) return rc;
-    h->st.total_ms = wt.ms();
-    return BPLTV_OK;
+    if (h->multi)
+        return multi_forward0_solve(h, "bpltv_denoise_each_device", [&](bpltv_t* c) { return bpltv_denoise_each_device(c, d_alphas, am, an, pp); });
+    return denoise_common(h, false, d_alphas, true, am, an, h->O, pp, nullptr);
 }
 
 int bpltv_evaluate(bpltv_t* h, const double* alpha, int am, int an, double delta, const bpltv_params* p,
@@ -3040,7 +2950,7 @@ int bpltv_evaluate(bpltv_t* h, const double* alpha, int am, int an, double delta
     if (am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "alpha: empty shape");
     std::vector<double> part(1 + (size_t)am * an);
     int rc = h->multi ? multi_evaluate(h, alpha, am, an, delta, p, u_out, part.data())
-                      : evaluate_common(h, alpha, am, an, delta, p, u_out, nullptr, part.data());
+                      : evaluate_common(h, false, alpha, am, an, delta, p, u_out, nullptr, part.data());
     if (rc) return rc;
     *cost_out = part[0];
     std::memcpy(grad_out, part.data() + 1, sizeof(double) * (size_t)am * an);
@@ -3057,43 +2967,14 @@ int bpltv_sumregs_default_params(bpltv_params* p) {
 int bpltv_sumregs_denoise(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, double* u_out) {
     if (!h) return BPLTV_E_ARG;
     if (h->multi) return multi_denoise(h, alpha, am, an, pp, u_out, 3);
-    WallTimer wt;
-    HIPCHK(h, hipSetDevice(h->device));
-    bpltv_params p;
-    if (pp) p = *pp; else bpltv_sumregs_default_params(&p);
-    if (int prc = check_params(h, p)) return prc;
-    int rc = sr_upload_alpha(h, alpha, am, an, &p);
-    if (rc) return rc;
-    rc = run_sr_pdhg(h, p);
-    if (rc) return rc;
-    if (u_out) {
-        HIPCHK(h, hipMemcpyAsync(u_out, h->d_sr[h->sr_result_buf][0], h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    h->st.total_ms = wt.ms();
-    return BPLTV_OK;
+    return denoise_common(h, true, alpha, false, am, an, 1, pp, u_out);
 }
 
 int bpltv_sumregs_denoise_device(bpltv_t* h, const double* d_alpha, int am, int an, const bpltv_params* pp) {
     if (!h) return BPLTV_E_ARG;
-    if (h->multi) {
-        const int rc = multi_unsupported(h, "bpltv_sumregs_denoise_device");
-        if (rc >= 0) return rc;
-        const int r = bpltv_sumregs_denoise_device(h->multi->shard[0], d_alpha, am, an, pp);
-        if (r) h->err = h->multi->shard[0]->err; else { h->has_result = true; multi_stats(h); }
-        return r;
-    }
-    WallTimer wt;
-    HIPCHK(h, hipSetDevice(h->device));
-    bpltv_params p;
-    if (pp) p = *pp; else bpltv_sumregs_default_params(&p);
-    if (int prc = check_params(h, p)) return prc;
-    int rc = upload_alpha_device(h, d_alpha, am, an, &p, PRE_SR);
-    if (rc) return rc;
-    rc = run_sr_pdhg(h, p);
-    if (rc) return rc;
-    h->st.total_ms = wt.ms();
-    return BPLTV_OK;
+    if (h->multi)
+        return multi_forward0_solve(h, "bpltv_sumregs_denoise_device", [&](bpltv_t* c) { return bpltv_sumregs_denoise_device(c, d_alpha, am, an, pp); });
+    return denoise_common(h, true, d_alpha, true, am, an, 1, pp, nullptr);
 }
 
 int bpltv_sumregs_evaluate(bpltv_t* h, const double* alpha, int am, int an, double delta, const bpltv_params* pp, double* u_out,
@@ -3101,11 +2982,10 @@ int bpltv_sumregs_evaluate(bpltv_t* h, const double* alpha, int am, int an, doub
     if (!h) return BPLTV_E_ARG;
     if (!cost_out || !grad_out) return set_err(h, BPLTV_E_ARG, "evaluate: null output pointer");
     if (!alpha || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "alpha: null pointer or empty shape");
-    bpltv_params p;
-    if (pp) p = *pp; else bpltv_sumregs_default_params(&p);
+    const bpltv_params p = resolve(pp, true);
     std::vector<double> part(1 + 3 * (size_t)am * an);
     int rc = h->multi ? multi_evaluate(h, alpha, am, an, delta, &p, u_out, part.data(), 3)
-                      : sr_evaluate_common(h, alpha, am, an, delta, &p, u_out, part.data());
+                      : evaluate_common(h, true, alpha, am, an, delta, &p, u_out, nullptr, part.data());
     if (rc) return rc;
     *cost_out = part[0];
     std::memcpy(grad_out, part.data() + 1, sizeof(double) * 3 * (size_t)am * an);
@@ -3120,52 +3000,35 @@ int bpltv_evaluate_partial(bpltv_t* h, const double* alpha, int am, int an, doub
         if (!alpha || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "alpha: null pointer or empty shape");
         return multi_evaluate(h, alpha, am, an, delta, p, u_out, partial_out);
     }
-    return evaluate_common(h, alpha, am, an, delta, p, u_out, nullptr, partial_out);
+    return evaluate_common(h, false, alpha, am, an, delta, p, u_out, nullptr, partial_out);
 }
 
 int bpltv_evaluate_device(bpltv_t* h, const double* alpha, int am, int an, double delta, const bpltv_params* p,
                           double* d_partial) {
     if (!h) return BPLTV_E_ARG;
     if (!d_partial) return set_err(h, BPLTV_E_ARG, "evaluate_device: null output pointer");
-    if (h->multi) {
-        const int rc = multi_unsupported(h, "bpltv_evaluate_device");
-        if (rc >= 0) return rc;
-        const int r = bpltv_evaluate_device(h->multi->shard[0], alpha, am, an, delta, p, d_partial);
-        if (r) h->err = h->multi->shard[0]->err; else { h->has_result = true; multi_stats(h); }
-        return r;
-    }
-    return evaluate_common(h, alpha, am, an, delta, p, nullptr, d_partial, nullptr);
+    if (h->multi)
+        return multi_forward0_solve(h, "bpltv_evaluate_device", [&](bpltv_t* c) { return bpltv_evaluate_device(c, alpha, am, an, delta, p, d_partial); });
+    return evaluate_common(h, false, alpha, am, an, delta, p, nullptr, d_partial, nullptr);
 }
 
 int bpltv_u_device(bpltv_t* h, const double** d_u) {
     if (!h || !d_u) return BPLTV_E_ARG;
-    if (h->multi) {
-        const int rc = multi_unsupported(h, "bpltv_u_device");
-        if (rc >= 0) return rc;
-        const int r = bpltv_u_device(h->multi->shard[0], d_u);
-        if (r) h->err = h->multi->shard[0]->err;
-        return r;
-    }
-    if (h->last_is_sr && h->sr_has_result) { *d_u = h->d_sr[h->sr_result_buf][0]; return BPLTV_OK; }
-    if (!h->has_result) return set_err(h, BPLTV_E_NODATA, "no solve has been run yet");
-    *d_u = h->d_state[h->result_buf][0];
+    if (h->multi)   // (no solve runs: nothing of the multi handle changes, its statistics included)
+        return multi_forward0(h, "bpltv_u_device", [&](bpltv_t* c) { return bpltv_u_device(c, d_u); });
+    const bool sr = h->last_is_sr && h->sr_has_result;
+    if (!sr && !h->has_result) return set_err(h, BPLTV_E_NODATA, "no solve has been run yet");
+    *d_u = result_u(h, sr);
     return BPLTV_OK;
 }
 
 int bpltv_copy_u_device(bpltv_t* h, double* d_dst) {
     if (!h || !d_dst) return BPLTV_E_ARG;
-    if (h->multi) {
-        const int rc = multi_unsupported(h, "bpltv_copy_u_device");
-        if (rc >= 0) return rc;
-        const int r = bpltv_copy_u_device(h->multi->shard[0], d_dst);
-        if (r) h->err = h->multi->shard[0]->err;
-        return r;
-    }
+    if (h->multi) return multi_forward0(h, "bpltv_copy_u_device", [&](bpltv_t* c) { return bpltv_copy_u_device(c, d_dst); });
     const bool sr = h->last_is_sr && h->sr_has_result;
     if (!sr && !h->has_result) return set_err(h, BPLTV_E_NODATA, "no solve has been run yet");
     HIPCHK(h, hipSetDevice(h->device));
-    HIPCHK(h, hipMemcpyAsync(d_dst, sr ? h->d_sr[h->sr_result_buf][0] : h->d_state[h->result_buf][0], h->tot * sizeof(double),
-                             hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_dst, result_u(h, sr), h->tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return BPLTV_OK;
 }
@@ -3180,7 +3043,8 @@ int bpltv_duality_gap(bpltv_t* h, double* gap_out) {
     if (!(h->last_is_sr ? h->sr_has_result : h->has_result)) return set_err(h, BPLTV_E_NODATA, "no solve has been run yet");
     HIPCHK(h, hipSetDevice(h->device));
     double gmax = 0.0;
-    int rc = compute_gap(h, gap_out, &gmax);
+    const bool sr = h->last_is_sr;
+    int rc = compute_gap(h, dataset_ctx(h, sr), sr, sr ? h->sr_result_buf : h->result_buf, gap_out, &gmax);
     if (rc) return rc;
     h->st.last_gap = gmax;
     return BPLTV_OK;
@@ -3234,7 +3098,7 @@ int bpltv_gradient(bpltv_t* h, const double* u, const double* ubar, const double
     HIPCHK(h, hipSetDevice(h->device));
     bpltv_params p = resolve(pp);
     if (int prc = check_params(h, p)) return prc;
-    int rc = upload_alpha(h, alpha, am, an);
+    int rc = upload_alpha(h, alpha, false, am, an);
     if (rc) return rc;
     if (!h->d_u2) {
         HIPCHK(h, hipMalloc((void**)&h->d_u2, h->tot * sizeof(double)));
@@ -3288,12 +3152,8 @@ int bpltv_sweep(bpltv_t* h, const double* alphas, int K, int am, int an, const b
     // Everything run_pdhg would reject is checked before anything of the handle changes (its buffers included): a
     // rejected sweep leaves the dataset context -- d_alpha, its shape and minimum, the last result -- as it was.
     const size_t npar = (size_t)am * an;
-    double amin = alphas[0];
-    for (size_t e = 0; e < (size_t)K * npar; ++e) {
-        if (!std::isfinite(alphas[e]) || alphas[e] < 0.0)
-            return set_err(h, BPLTV_E_ARG, "sweep: alphas[%zu] = %g: parameters must be finite and >= 0", e, alphas[e]);
-        if (alphas[e] < amin) amin = alphas[e];
-    }
+    double amin = 0.0;
+    if (int crc = check_alpha_host(h, "sweep: alphas", alphas, (size_t)K * npar, &amin)) return crc;
     if (p.rho != 0.0 && !(amin > 0.0))
         return set_err(h, BPLTV_E_ARG, "sweep: rho != 0 divides by alpha: every parameter entry must be > 0 (min = %g)", amin);
     if (h->multi) return multi_sweep(h, alphas, K, am, an, pp, cost_out, u_out);
@@ -3327,37 +3187,16 @@ int bpltv_sweep(bpltv_t* h, const double* alphas, int K, int am, int an, const b
     int rc = ensure(h, &h->d_sweep_alpha, &h->sweep_alpha_cap, K * npar);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_sweep_alpha, alphas, K * npar * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    // the sweep's solve context; the dataset context comes back whatever run_pdhg returns
-    const int am0 = h->last_am, an0 = h->last_an, rb0 = h->result_buf;
-    const double amin0 = h->alpha_min;
-    const bool has0 = h->has_result, last0 = h->last_is_sr;
-    h->cur_state = h->d_sweep; h->cur_nimg = (int)nimg; h->cur_astride = (int)npar; h->cur_alpha = h->d_sweep_alpha;
-    h->last_am = am; h->last_an = an; h->alpha_min = amin;
-    rc = run_pdhg(h, p);
-    const int rb = h->result_buf;
-    h->cur_state = h->d_state; h->cur_nimg = h->O; h->cur_astride = 0; h->cur_alpha = nullptr;
-    h->last_am = am0; h->last_an = an0; h->alpha_min = amin0;
-    h->result_buf = rb0; h->has_result = has0; h->last_is_sr = last0;
+    // the sweep's solve context; nothing of it is committed to the handle
+    SolveCtx x;
+    for (int sb = 0; sb < 2; ++sb) x.state[sb] = h->d_sweep[sb];
+    x.nimg = (int)nimg; x.alpha = h->d_sweep_alpha; x.sweep = true; x.astride = (int)npar;
+    x.am = am; x.an = an; x.alpha_min = amin;
+    int rb = 0;
+    rc = run_pdhg(h, x, p, &rb);
     if (rc) return rc;
-    // loss of every problem against ubar[img % O], then summed per parameter on the host
-    const int nblk = 16;
-    rc = ensure(h, &h->d_red, &h->red_cap, nimg * nblk * 4);
+    rc = sweep_tail(h, h->d_sweep[rb][0], K, h->d_sweep_cost, cost_out, u_out);
     if (rc) return rc;
-    hipLaunchKernelGGL(cost_partial_mod_kernel, dim3(nblk, (unsigned)nimg), dim3(256), 0, h->stream, h->d_sweep[rb][0],
-                       h->d_ubar, (int)h->npx, h->O, h->d_red);
-    hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, nblk, (int)nimg, 0.5,
-                       h->d_sweep_cost, (double*)nullptr);
-    HIPCHK(h, hipGetLastError());
-    std::vector<double> per(nimg);
-    HIPCHK(h, hipMemcpyAsync(per.data(), h->d_sweep_cost, nimg * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (u_out)
-        HIPCHK(h, hipMemcpyAsync(u_out, h->d_sweep[rb][0], nimg * h->npx * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int k = 0; k < K; ++k) {
-        double sacc = 0.0;
-        for (int i = 0; i < h->O; ++i) sacc += per[(size_t)k * h->O + i];
-        cost_out[k] = sacc;
-    }
     h->st.total_ms = wt.ms();
     return BPLTV_OK;
 }
@@ -3370,10 +3209,14 @@ int bpltv_sumregs_sweep(bpltv_t* h, const double* alphas, int K, int am, int an,
                         double* u_out) {
     if (!h) return BPLTV_E_ARG;
     if (!cost_out) return set_err(h, BPLTV_E_ARG, "sumregs_sweep: null output pointer");
-    bpltv_params p;
-    if (pp) p = *pp; else bpltv_sumregs_default_params(&p);
+    bpltv_params p = resolve(pp, true);
+    // finite and >= 0, and > 0 when rho != 0 -- upload_alpha's and run_sr_pdhg's conditions, before the call changes anything
+    if (!alphas || K < 1) return set_err(h, BPLTV_E_ARG, "sumregs_sweep: null pointer or K < 1");
+    if (am < 1 || an < 1 || am > h->M || an > h->N) return set_err(h, BPLTV_E_ARG, "sumregs_sweep: bad parameter shape %dx%dx3", am, an);
     double amin = 0.0;
-    if (int rc = sr_check_blocks(h, alphas, K, am, an, p.rho, &amin)) return rc;
+    if (int crc = check_alpha_host(h, "sumregs_sweep: alphas", alphas, (size_t)K * 3 * am * an, &amin)) return crc;
+    if (p.rho != 0.0 && !(amin > 0.0))
+        return set_err(h, BPLTV_E_ARG, "rho != 0 divides by alpha: every parameter entry must be > 0 (min = %g)", amin);
     if (h->multi) return multi_sweep(h, alphas, K, am, an, pp, cost_out, u_out, 3);
     if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "bpltv_set_data has not been called");
     if (int prc = check_params(h, p)) return prc;
@@ -3419,10 +3262,6 @@ int bpltv_sumregs_sweep(bpltv_t* h, const double* alphas, int K, int am, int an,
     if (rc) return rc;
     rc = ensure(h, &h->d_srsweep_cost, &h->srsweep_cost_cap, pmax);
     if (rc) return rc;
-    const int nblk = 16;
-    rc = ensure(h, &h->d_red, &h->red_cap, pmax * nblk);
-    if (rc) return rc;
-    std::vector<double> per((size_t)K * O);
     double pdhg_ms = 0.0, abytes = 0.0;
     int launches = 0, tiles = 0;
     for (int g = 0; g < ng; ++g) {
@@ -3430,36 +3269,17 @@ int bpltv_sumregs_sweep(bpltv_t* h, const double* alphas, int K, int am, int an,
         const int np = (k1 - k0) * O;
         HIPCHK(h, hipMemcpyAsync(h->d_srsweep_alpha, alphas + (size_t)k0 * nb, (size_t)(k1 - k0) * nb * sizeof(double),
                                  hipMemcpyHostToDevice, h->stream));
-        // the group's solve context; the dataset context comes back whatever run_sr_pdhg returns
-        const int am0 = h->last_am, an0 = h->last_an, rb0 = h->sr_result_buf;
-        const double amin0 = h->alpha_min;
-        const bool has0 = h->sr_has_result, last0 = h->last_is_sr;
-        h->sr_cur = h->d_srsweep; h->sr_cur_nimg = np; h->sr_cur_astride = (int)nb; h->sr_cur_alpha = h->d_srsweep_alpha;
-        h->last_am = am; h->last_an = an; h->alpha_min = amin;
-        rc = run_sr_pdhg(h, p);
-        const int rb = h->sr_result_buf;
-        h->sr_cur = h->d_sr; h->sr_cur_nimg = O; h->sr_cur_astride = 0; h->sr_cur_alpha = nullptr;
-        h->last_am = am0; h->last_an = an0; h->alpha_min = amin0;
-        h->sr_result_buf = rb0; h->sr_has_result = has0; h->last_is_sr = last0;
+        // the group's solve context; nothing of it is committed to the handle
+        SolveCtx x;
+        for (int sb = 0; sb < 2; ++sb) x.state[sb] = h->d_srsweep[sb];
+        x.nimg = np; x.alpha = h->d_srsweep_alpha; x.astride = (int)nb;
+        x.am = am; x.an = an; x.alpha_min = amin;
+        int rb = 0;
+        rc = run_sr_pdhg(h, x, p, &rb);
         if (rc) return rc;
         pdhg_ms += h->st.pdhg_ms; launches += h->st.launches; tiles += h->st.tiles; abytes += h->st.algorithmic_bytes;
-        // loss of every problem against ubar[img % O]; summed per parameter block on the host
-        hipLaunchKernelGGL(cost_partial_mod_kernel, dim3(nblk, (unsigned)np), dim3(256), 0, h->stream, h->d_srsweep[rb][0],
-                           h->d_ubar, (int)npx, O, h->d_red);
-        hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, nblk, np, 0.5, h->d_srsweep_cost,
-                           (double*)nullptr);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(per.data() + (size_t)k0 * O, h->d_srsweep_cost, (size_t)np * sizeof(double), hipMemcpyDeviceToHost,
-                                 h->stream));
-        if (u_out)
-            HIPCHK(h, hipMemcpyAsync(u_out + (size_t)k0 * O * npx, h->d_srsweep[rb][0], (size_t)np * npx * sizeof(double),
-                                     hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    for (int k = 0; k < K; ++k) {
-        double sacc = 0.0;
-        for (int i = 0; i < O; ++i) sacc += per[(size_t)k * O + i];
-        cost_out[k] = sacc;
+        rc = sweep_tail(h, h->d_srsweep[rb][0], k1 - k0, h->d_srsweep_cost, cost_out + k0, u_out ? u_out + (size_t)k0 * O * npx : nullptr);
+        if (rc) return rc;
     }
     h->st.pdhg_ms = pdhg_ms; h->st.launches = launches; h->st.tiles = tiles; h->st.algorithmic_bytes = abytes;
     h->st.sweep_groups = ng;
