@@ -98,6 +98,11 @@ SYMBOLS = {
     "bpltv_sumregs_vjp": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
     "bpltv_sumregs_vjp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),
+    "bpltv_sumregs_denoise_each": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp]),
+    "bpltv_sumregs_denoise_each_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, _PP]),
+    "bpltv_sumregs_vjp_each": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
+    "bpltv_sumregs_vjp_each_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_void_p,
+                                                C.c_void_p, C.c_void_p]),
     "bpltv_sweep": (C.c_int, [_H, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp]),
     "bpltv_sumregs_sweep": (C.c_int, [_H, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp]),
     "bpltv_per_image": (C.c_int, [_H, _dp]),

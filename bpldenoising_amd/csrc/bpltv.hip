@@ -206,9 +206,11 @@ struct SrGraphKey {
     int nimg;              // problems of the solve context (the dataset's O, or a sweep group's K_g * O)
     const void* state;     // its state set and parameter buffer: a sweep never replays a dataset-context graph, nor the reverse
     const void* alpha;
+    int istride;           // 0: one parameter block; 3*am*an: one block per image (bpltv_sumregs_denoise_each) -- both live in
+                           // d_alpha, and the two modes run different kernel instances
     bool operator<(const SrGraphKey& o) const {
-        return std::tie(maxiter, T, am, an, accel, variant, rho, tau0, sigma0, tab, nimg, state, alpha) <
-               std::tie(o.maxiter, o.T, o.am, o.an, o.accel, o.variant, o.rho, o.tau0, o.sigma0, o.tab, o.nimg, o.state, o.alpha);
+        return std::tie(maxiter, T, am, an, accel, variant, rho, tau0, sigma0, tab, nimg, state, alpha, istride) <
+               std::tie(o.maxiter, o.T, o.am, o.an, o.accel, o.variant, o.rho, o.tau0, o.sigma0, o.tab, o.nimg, o.state, o.alpha, o.istride);
     }
 };
 
@@ -314,8 +316,9 @@ struct bpltv_handle {
     double* d_alpha = nullptr;
     size_t alpha_cap = 0;
     int last_am = 1, last_an = 1;
-    int alpha_istride = 0;        // 0: d_alpha holds one parameter for every image; am*an: O blocks, one per image
-                                  // (bpltv_denoise_each), which the PDHG and gap kernels of the dataset context address
+    int alpha_istride = 0;        // 0: d_alpha holds one parameter for every image; am*an (TV) or 3*am*an (sum of
+                                  // regularisers): O blocks, one per image (bpltv_denoise_each, bpltv_sumregs_denoise_each),
+                                  // which the PDHG and gap kernels of the dataset context address
     double alpha_min = 0.0;       // smallest entry of the last uploaded parameter (validated on the host)
     double* d_partial = nullptr;  // [1 + am*an]
     size_t partial_cap = 0;
@@ -522,7 +525,8 @@ struct SolveCtx {
     const double* alpha = nullptr;  // the parameter buffer (Float64)
     bool sweep = false;             // float handle: the parameter's twin is f32_sweep_alpha, not f32_alpha (f32_state is shared)
     int astride = 0;                // doubles between the parameter blocks of a sweep (problem img reads block img / O)
-    int istride = 0;                // doubles between per-image blocks (bpltv_denoise_each; TV model, dataset context only)
+    int istride = 0;                // doubles between per-image blocks (bpltv_denoise_each: am*an, bpltv_sumregs_denoise_each:
+                                    // 3*am*an; dataset context only)
     int am = 1, an = 1;             // parameter shape
     double alpha_min = 0.0;         // its smallest entry, validated on the host or by alpha_check_kernel
 };
@@ -617,7 +621,8 @@ int check_alpha_host(bpltv_t* h, const char* name, const double* a, size_t n, do
 // The parameter of the dataset context into d_alpha, from the host or (on_device: bpltv_*denoise*_device) from HBM, where
 // it is checked in place by alpha_check_kernel (one 16-byte read back) and copied device to device.
 // what: the model (PRE_SR: three slices of am*an doubles) and what follows the upload, for solve_precheck.
-// blocks: 1, or O for bpltv_denoise_each(_device) (TV model: O blocks of am*an doubles, image k reads block k).
+// blocks: 1, or O for bpltv_denoise_each(_device) and bpltv_sumregs_denoise_each(_device): O blocks of am*an (3*am*an)
+// doubles, image k reads block k.
 // solve (nullable): the parameters of the PDHG solve the upload is for.  The order is the contract: shape, values,
 // solve_precheck, and only then the handle -- a rejected parameter leaves d_alpha, its shape and alpha_min, and so the
 // duality gap of the last solve, as they were.
@@ -661,7 +666,7 @@ int upload_alpha(bpltv_t* h, const double* alpha, bool on_device, int am, int an
     h->last_am = am;
     h->last_an = an;
     h->last_slices = sr ? 3 : 1;
-    h->alpha_istride = blocks > 1 ? am * an : 0;
+    h->alpha_istride = blocks > 1 ? (sr ? 3 : 1) * am * an : 0;
     return BPLTV_OK;
 }
 
@@ -835,7 +840,7 @@ int compute_gap(bpltv_t* h, const SolveCtx& x, bool sr, int buf, double* gap_hos
         SrState Ss;
         for (int c = 0; c < 7; ++c) Ss.pl[c] = S[c];
         hipLaunchKernelGGL(sr_gap_partial_kernel, dim3(nblk, h->O), dim3(256), 0, h->stream, Ss, h->d_f, x.alpha, x.am, x.an, h->M,
-                           h->N, h->d_red);
+                           h->N, x.istride, h->d_red);
     } else {
         hipLaunchKernelGGL(gap_partial_kernel, dim3(nblk, h->O), dim3(256), 0, h->stream, S[0], S[1], S[2], h->d_f, x.alpha, x.am,
                            x.an, h->M, h->N, x.istride, h->d_red);
@@ -1348,7 +1353,8 @@ void solve_band_lds(bpltv_t* h, double* vec, double* accv) {
 struct GradCtx {
     const double* alpha = nullptr;
     int am = 1, an = 1;
-    int astride = 0;               // 0: one parameter for every image; am*an: image k reads block k (bpltv_vjp_each)
+    int astride = 0;               // 0: one parameter for every image; am*an (3*am*an, sum of regularisers): image k reads block k
+                                   // (bpltv_vjp_each, bpltv_sumregs_vjp_each)
     bool each = false;             // d_out receives the O per-image parameter gradients (image-major), not their sum
     double alpha_min = 0.0;
     const double* src = nullptr;   // ubar, or gu when cot
@@ -1573,8 +1579,8 @@ int run_sr_gradient(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, co
 // shape and minimum, the PDHG state and graphs, and so bpltv_u_device and bpltv_duality_gap -- stays as it was.
 // slices: 1 TV (bpltv_vjp), 3 sum of regularisers (bpltv_sumregs_vjp; the parameter is 3*am*an doubles).
 // d_grad_alpha: slices*am*an doubles in HBM or nullptr; d_grad_f: M*N*O doubles in HBM or nullptr; not both nullptr.
-// each (TV model, bpltv_vjp_each): alpha holds O blocks of am*an doubles, image k reads block k, and d_grad_alpha receives
-// the O per-image gradients, image-major.
+// each (bpltv_vjp_each, bpltv_sumregs_vjp_each): alpha holds O blocks of slices*am*an doubles, image k reads block k, and
+// d_grad_alpha receives the O per-image gradients, image-major.
 int vjp_common(bpltv_t* h, const double* d_u, const double* alpha, bool alpha_dev, int am, int an, int reg,
                const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alpha, int slices = 1,
                bool each = false) {
@@ -1614,7 +1620,7 @@ int vjp_common(bpltv_t* h, const double* d_u, const double* alpha, bool alpha_de
     HIPCHK(h, hipMemcpyAsync(d_a, alpha, P * sizeof(double), alpha_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     GradCtx g;
     g.alpha = d_a; g.am = am; g.an = an; g.alpha_min = amin;
-    g.astride = each ? am * an : 0; g.each = each;
+    g.astride = each ? slices * am * an : 0; g.each = each;
     g.src = d_gu; g.cot = true;
     g.d_out = d_grad_alpha; g.d_grad_f = d_grad_f;
     h->has_per_image = false;   // the reduction scratch (d_red) no longer holds the last evaluate's rows
@@ -1631,10 +1637,12 @@ struct SrVariant {
     size_t lds;
     void (*kernel)(SrArgs);
     void (*sweep_kernel)(SrArgs);   // the same kernel for K * O problems of a parameter sweep (f[img % O], block img / O)
+    void (*each_kernel)(SrArgs);    // ... for the O images with one parameter block each (f[img], block img)
 };
 const SrVariant SR_VARIANTS[] = {
-    {32, 32 * 32, sr_lds_bytes(32, 32), &sr_tile_kernel<32, 32>, &sr_tile_kernel<32, 32, true>},
-    {48, 48 * 16, sr_lds_bytes(48, 48), &sr_strip_kernel<3, 48, 16>, &sr_strip_kernel<3, 48, 16, true>},
+    {32, 32 * 32, sr_lds_bytes(32, 32), &sr_tile_kernel<32, 32>, &sr_tile_kernel<32, 32, SR_SWEEP>, &sr_tile_kernel<32, 32, SR_EACH>},
+    {48, 48 * 16, sr_lds_bytes(48, 48), &sr_strip_kernel<3, 48, 16>, &sr_strip_kernel<3, 48, 16, SR_SWEEP>,
+     &sr_strip_kernel<3, 48, 16, SR_EACH>},
 };
 constexpr int SR_NVARIANTS = 2;
 
@@ -1686,7 +1694,7 @@ int sr_alloc(bpltv_t* h) {
     for (int s = 0; s < 2; ++s)
         for (int c = 0; c < 7; ++c) HIPCHK(h, hipMalloc((void**)&h->d_sr[s][c], h->tot * sizeof(double)));
     for (const SrVariant& v : SR_VARIANTS)
-        for (auto k : {v.kernel, v.sweep_kernel})
+        for (auto k : {v.kernel, v.sweep_kernel, v.each_kernel})
             HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)v.lds));
     h->sr_ready = true;
     return BPLTV_OK;
@@ -1694,7 +1702,8 @@ int sr_alloc(bpltv_t* h) {
 
 // maxiter iterations of the three-dual PDHG, T fused per launch (halo 2T), replayed from a hipGraph, on the solve context
 // x: x.nimg problems in the state sets x.state; problem img reads f[img % O] and the parameter block img / O (x.astride
-// doubles apart) of x.alpha.  *result_buf: the state set that holds the result (written on success only).
+// doubles apart) of x.alpha; with x.istride != 0 (dataset context, bpltv_sumregs_denoise_each) image img reads the block
+// img, x.istride doubles apart.  *result_buf: the state set that holds the result (written on success only).
 int run_sr_pdhg(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, int* result_buf) {
     h->has_per_image = false;
     if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "bpltv_set_data has not been called");
@@ -1750,7 +1759,8 @@ int run_sr_pdhg(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, int* resul
         *result_buf = 0; h->st.pdhg_ms = 0.0;
         return BPLTV_OK;
     }
-    void (*kern)(SrArgs) = nimg == h->O ? V.kernel : V.sweep_kernel;
+    const bool each = x.istride != 0;   // one block per image: the dataset context only (nimg == O)
+    void (*kern)(SrArgs) = each ? V.each_kernel : (nimg == h->O ? V.kernel : V.sweep_kernel);
     // iterations [it0, it1) of the images [lo, hi) from the state set `cur`; returns the set holding the result.
     // stagger: the chain's first launch fuses T/2 iterations and writes set 1 (run_pdhg's launch chains).
     auto enqueue_range = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) -> int {
@@ -1765,7 +1775,7 @@ int run_sr_pdhg(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, int* resul
             a.M = M; a.N = N; a.O = nimg; a.nTi = nTi; a.nTj = nTj; a.halo = 2 * T;
             a.first = (it == 0) ? 1 : 0;
             a.img0 = lo;
-            a.Odata = h->O; a.astride = x.astride;
+            a.Odata = h->O; a.astride = each ? x.istride : x.astride;
             hipLaunchKernelGGL(kern, dim3(nTi, nTj, hi - lo), dim3(V.threads), V.lds, st, a);
             cur = nxt;
         }
@@ -1812,7 +1822,7 @@ int run_sr_pdhg(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, int* resul
     bool done = false;
     if (p.use_graph && nl <= 50000) {
         SrGraphKey key{p.maxiter, T, x.am, x.an, p.accel ? 1 : 0, vi + 16 * nch, p.rho, p.tau0, p.sigma0, (const void*)d_tab,
-                       nimg, (const void*)S[0][0], (const void*)d_alpha};
+                       nimg, (const void*)S[0][0], (const void*)d_alpha, x.istride};
         auto it = h->sr_graphs.find(key);
         if (it == h->sr_graphs.end()) {
             if (h->sr_graphs.size() >= 8) drop_sr_graphs(h);
@@ -1900,7 +1910,8 @@ int sr_band_alloc(bpltv_t* h) {
 // (params.reserved[4] = 1), and -- sumregs_gradient_reg with a patch parameter, whose row-scaled system is not
 // symmetric (SumRegsLearningFunction.jl:250) -- the LU variant of the nested dissection (banded LU with
 // params.reserved[4] = 1).
-// Parameter (three slices of g.am*g.an), right-hand side and outputs come from `g`, as for run_gradient_once.
+// Parameter (three slices of g.am*g.an; g.astride != 0: one such block per image, image k reads block k), right-hand side
+// and outputs come from `g`, as for run_gradient_once.
 int run_sr_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, const bpltv_params& p, double kappa_scale) {
     int rc = sr_adj_alloc(h);
     if (rc) return rc;
@@ -1947,7 +1958,6 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int re
     const int nref = p.refine < 0 ? (reg ? 1 : 2) : p.refine;
     HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_fail, 0, sizeof(int) * O, h->stream));
-    const double* rowscale = rowsc ? g.alpha : nullptr;
     int chunks = 0;
     for (int c0 = 0; c0 < O; c0 += Oc, ++chunks) {
         const int nimg = std::min(Oc, O - c0);
@@ -1960,14 +1970,16 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int re
         double *dp = h->d_p + o0, *dr = h->d_r + o0;
         int* dfail = h->d_fail + c0;
         const int gpx = (int)((ctot + 255) / 256);
+        const double* ga = g.alpha + (size_t)c0 * g.astride;   // the group's first image's parameter block
+        const double* rowscale = rowsc ? ga : nullptr;
         if (g.cot)
-            hipLaunchKernelGGL(sr_adj_setup_cot_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0, g.alpha, am, an, M, N,
-                               nimg, patch, reg, kact, C);
+            hipLaunchKernelGGL(sr_adj_setup_cot_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0, ga, am, an, g.astride,
+                               M, N, nimg, patch, reg, kact, C);
         else
-            hipLaunchKernelGGL(sr_adj_setup_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0, g.alpha, am, an, M, N, nimg,
-                               patch, reg, kact, C);
+            hipLaunchKernelGGL(sr_adj_setup_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0, ga, am, an, g.astride, M,
+                               N, nimg, patch, reg, kact, C);
         if (lu) HIPCHK(h, hipMemsetAsync(h->d_srdiagU, 0, 7 * tot * sizeof(double), h->stream));
-        hipLaunchKernelGGL(sr_adj_assemble_kernel, dim3(gpx), dim3(256), 0, h->stream, C, M, N, nimg, diag, rowscale, am, an, diagU);
+        hipLaunchKernelGGL(sr_adj_assemble_kernel, dim3(gpx), dim3(256), 0, h->stream, C, M, N, nimg, diag, rowscale, am, an, g.astride, diagU);
         BandDiags D;
         D.planes = diag; D.tot = tot; D.nd = 7;
         D.off[0] = 0; D.off[1] = 1; D.off[2] = 2; D.off[3] = M - 1; D.off[4] = M; D.off[5] = M + 1; D.off[6] = 2 * M;
@@ -1988,7 +2000,7 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int re
         }
         auto residual = [&](double* out) {
             hipLaunchKernelGGL(sr_adj_flux_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, w);
-            hipLaunchKernelGGL(sr_adj_residual_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, w, M, N, nimg, out, rowscale, am, an);
+            hipLaunchKernelGGL(sr_adj_residual_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, w, M, N, nimg, out, rowscale, am, an, g.astride);
         };
         auto solve = [&](double* v, double* acc) -> int {
             int r2 = 0;
@@ -2016,7 +2028,15 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int re
     }
     // ... then per parameter, over all images (a vector-Jacobian product may not want the parameter gradient)
     const bool amap = am == M && an == N && !(M == 1 && N == 1);
-    if (g.d_out && amap) {   // three pixelwise maps: plain sums over the images
+    if (g.d_out && g.each) {   // per image, image-major: block k holds image k's three slices, nothing is summed over images
+        if (amap)
+            hipLaunchKernelGGL(sr_gpix_each_kernel, dim3((unsigned)((3 * tot + 255) / 256)), dim3(256), 0, h->stream, h->d_srgpix, npx, O,
+                               g.d_out);
+        else
+            for (int k = 0; k < 3; ++k)
+                hipLaunchKernelGGL(patch_sum_kernel, dim3((unsigned)P, O), dim3(256), 0, h->stream, h->d_srgpix + k * tot, M, N, O, am, an,
+                                   1, (int)(3 * P), g.d_out + (size_t)k * P);
+    } else if (g.d_out && amap) {   // three pixelwise maps: plain sums over the images
         for (int k = 0; k < 3; ++k)
             hipLaunchKernelGGL(map_sum_kernel, dim3((unsigned)((h->npx + 255) / 256)), dim3(256), 0, h->stream, h->d_srgpix + k * tot,
                                h->npx, O, g.d_out + (size_t)k * h->npx);
@@ -2384,13 +2404,13 @@ int multi_set_data(bpltv_t* h, const double* ubar, const double* f) {
     return BPLTV_OK;
 }
 
-// each (TV model, bpltv_denoise_each): alpha holds O blocks of am*an doubles; shard k takes the blocks [lo_k, hi_k).  Their
-// entries are checked here first, so that a block one shard would reject does not leave the others' solves behind.
+// each (bpltv_denoise_each, bpltv_sumregs_denoise_each): alpha holds O blocks of slices*am*an doubles; shard k takes the
+// blocks [lo_k, hi_k).  Their entries are checked here first, so that a block one shard would reject does not leave the others' solves behind.
 int multi_denoise(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, double* u_out, int slices = 1,
                   bool each = false) {
     WallTimer wt;
     MultiState& ms = *h->multi;
-    const size_t npx = h->npx, P = (size_t)am * an;
+    const size_t npx = h->npx, P = (size_t)slices * am * an;
     if (each) {
         if (!alpha || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "alpha: null pointer or empty shape");
         const bpltv_params p = resolve(pp);
@@ -2401,7 +2421,9 @@ int multi_denoise(bpltv_t* h, const double* alpha, int am, int an, const bpltv_p
     }
     int rc = multi_run(h, [&](int k, bpltv_t* c) {
         double* uo = u_out ? u_out + ms.lo[k] * npx : nullptr;
-        if (each) return bpltv_denoise_each(c, alpha + ms.lo[k] * P, am, an, pp, uo);
+        if (each)
+            return slices == 3 ? bpltv_sumregs_denoise_each(c, alpha + ms.lo[k] * P, am, an, pp, uo)
+                               : bpltv_denoise_each(c, alpha + ms.lo[k] * P, am, an, pp, uo);
         return slices == 3 ? bpltv_sumregs_denoise(c, alpha, am, an, pp, uo) : bpltv_denoise(c, alpha, am, an, pp, uo);
     });
     if (rc) return rc;
@@ -2538,7 +2560,8 @@ int multi_gradient(bpltv_t* h, const double* u, const double* ubar, const double
 
 // bpltv_vjp over the shards: images split as for the gradient, input-gradient slices written in place, the parameter
 // gradients of the shards added in shard order.  slices: 1 TV (bpltv_vjp), 3 sum of regularisers (bpltv_sumregs_vjp).
-// each (bpltv_vjp_each): shard k takes the parameter blocks [lo_k, hi_k) and writes their gradients in place.
+// each (bpltv_vjp_each, bpltv_sumregs_vjp_each): shard k takes the parameter blocks [lo_k, hi_k) and writes their gradients
+// in place.
 int multi_vjp(bpltv_t* h, const double* u, const double* alpha, int am, int an, int reg, const bpltv_params* pp,
               const double* gu, double* grad_f_out, double* grad_alpha_out, int slices = 1, bool each = false) {
     if (!u || !gu || !alpha || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "vjp: null pointer or empty shape");
@@ -2551,9 +2574,11 @@ int multi_vjp(bpltv_t* h, const double* u, const double* alpha, int am, int an, 
     int rc = multi_run(h, [&](int k, bpltv_t* c) {
         const size_t o0 = ms.lo[k] * npx;
         double* gf = grad_f_out ? grad_f_out + o0 : nullptr;
-        if (each)
-            return bpltv_vjp_each(c, u + o0, alpha + ms.lo[k] * P, am, an, reg, pp, gu + o0, gf,
-                                  grad_alpha_out ? grad_alpha_out + ms.lo[k] * P : nullptr);
+        if (each) {
+            double* gak = grad_alpha_out ? grad_alpha_out + ms.lo[k] * P : nullptr;
+            return slices == 3 ? bpltv_sumregs_vjp_each(c, u + o0, alpha + ms.lo[k] * P, am, an, reg, pp, gu + o0, gf, gak)
+                               : bpltv_vjp_each(c, u + o0, alpha + ms.lo[k] * P, am, an, reg, pp, gu + o0, gf, gak);
+        }
         double* ga = grad_alpha_out ? g.data() + (size_t)k * P : nullptr;
         return slices == 3 ? bpltv_sumregs_vjp(c, u + o0, alpha, am, an, reg, pp, gu + o0, gf, ga)
                            : bpltv_vjp(c, u + o0, alpha, am, an, reg, pp, gu + o0, gf, ga);
@@ -2726,7 +2751,7 @@ int vjp_device(bpltv_t* h, const double* d_u, const double* d_alpha, int am, int
                const double* d_gu, double* d_grad_f, double* d_grad_alpha, int slices, bool each = false) {
     if (!h) return BPLTV_E_ARG;
     if (h->multi) {
-        const int r = multi_forward0(h, each ? "bpltv_vjp_each_device" : (slices == 3 ? "bpltv_sumregs_vjp_device" : "bpltv_vjp_device"), [&](bpltv_t* c) {
+        const int r = multi_forward0(h, each ? (slices == 3 ? "bpltv_sumregs_vjp_each_device" : "bpltv_vjp_each_device") : (slices == 3 ? "bpltv_sumregs_vjp_device" : "bpltv_vjp_device"), [&](bpltv_t* c) {
             return vjp_device(c, d_u, d_alpha, am, an, reg, pp, d_gu, d_grad_f, d_grad_alpha, slices, each);
         });
         if (r == BPLTV_OK) { h->has_per_image = false; multi_stats(h); }   // no solve ran: has_result stays
@@ -2977,6 +3002,22 @@ int bpltv_sumregs_denoise_device(bpltv_t* h, const double* d_alpha, int am, int 
     return denoise_common(h, true, d_alpha, true, am, an, 1, pp, nullptr);
 }
 
+// bpltv_sumregs_denoise / bpltv_sumregs_denoise_device with one parameter block (three slices) per image: upload_alpha with
+// O blocks, after which the PDHG and gap kernels of the dataset context address block k for image k (h->alpha_istride).
+int bpltv_sumregs_denoise_each(bpltv_t* h, const double* alphas, int am, int an, const bpltv_params* pp, double* u_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi) return multi_denoise(h, alphas, am, an, pp, u_out, 3, true);
+    return denoise_common(h, true, alphas, false, am, an, h->O, pp, u_out);
+}
+
+int bpltv_sumregs_denoise_each_device(bpltv_t* h, const double* d_alphas, int am, int an, const bpltv_params* pp) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return multi_forward0_solve(h, "bpltv_sumregs_denoise_each_device",
+                                    [&](bpltv_t* c) { return bpltv_sumregs_denoise_each_device(c, d_alphas, am, an, pp); });
+    return denoise_common(h, true, d_alphas, true, am, an, h->O, pp, nullptr);
+}
+
 int bpltv_sumregs_evaluate(bpltv_t* h, const double* alpha, int am, int an, double delta, const bpltv_params* pp, double* u_out,
                            double* cost_out, double* grad_out) {
     if (!h) return BPLTV_E_ARG;
@@ -3141,6 +3182,15 @@ int bpltv_sumregs_vjp(bpltv_t* h, const double* u, const double* alpha, int am, 
 int bpltv_sumregs_vjp_device(bpltv_t* h, const double* d_u, const double* d_alpha, int am, int an, int reg,
                              const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alpha) {
     return vjp_device(h, d_u, d_alpha, am, an, reg, pp, d_gu, d_grad_f, d_grad_alpha, 3);
+}
+
+int bpltv_sumregs_vjp_each(bpltv_t* h, const double* u, const double* alphas, int am, int an, int reg, const bpltv_params* pp,
+                           const double* gu, double* grad_f_out, double* grad_alphas_out) {
+    return vjp_host(h, u, alphas, am, an, reg, pp, gu, grad_f_out, grad_alphas_out, 3, true);
+}
+int bpltv_sumregs_vjp_each_device(bpltv_t* h, const double* d_u, const double* d_alphas, int am, int an, int reg,
+                                  const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alphas) {
+    return vjp_device(h, d_u, d_alphas, am, an, reg, pp, d_gu, d_grad_f, d_grad_alphas, 3, true);
 }
 
 int bpltv_sweep(bpltv_t* h, const double* alphas, int K, int am, int an, const bpltv_params* pp, double* cost_out,

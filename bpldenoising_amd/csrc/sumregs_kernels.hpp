@@ -35,9 +35,16 @@ struct SrArgs {
     int first;
     int img0;              // first image of this launch (launch chains: grid = tiles per image * images of the chain)
     int Odata;             // images in the dataset; problem `img` uses f[img % Odata] and the parameter block
-                           // alpha + (img / Odata) * astride (parameter sweeps: K * Odata problems, the SWEEP instances of
+                           // alpha + (img / Odata) * astride (parameter sweeps: K * Odata problems, the SR_SWEEP instances of
                            // the kernels; O == Odata otherwise)
-    int astride;           // doubles per parameter block: 3 * am * an
+    int astride;           // doubles per parameter block: 3 * am * an (SR_SWEEP and SR_EACH; the SR_SHARED instances do not read it)
+};
+
+// How a problem of the launch finds its image and its parameter block -- compiled in, one kernel instance per mode.
+enum SrAddr {
+    SR_SHARED = 0,   // dataset context, one parameter block: f[img], alpha
+    SR_SWEEP = 1,    // K * Odata problems of a parameter sweep: f[img % Odata], alpha + (img / Odata) * astride
+    SR_EACH = 2,     // dataset context, one block per image (bpltv_sumregs_denoise_each): f[img], alpha + img * astride
 };
 
 __device__ __forceinline__ size_t sr_alpha_index(int am, int an, int M, int N, int i, int j) {
@@ -46,11 +53,12 @@ __device__ __forceinline__ size_t sr_alpha_index(int am, int an, int M, int N, i
     return (size_t)(((unsigned)i * (unsigned)am) / (unsigned)M) + (size_t)am * (((unsigned)j * (unsigned)an) / (unsigned)N);
 }
 
-// SWEEP = false: the dataset context (O == Odata, problem img reads f[img] and the one parameter block), the prologue of the
+// SR_SHARED: the dataset context (O == Odata, problem img reads f[img] and the one parameter block), the prologue of the
 // kernel before parameter sweeps existed.  A runtime O == Odata test (pdhg_data_image) costs two more kernarg loads and a
 // scalar wait in front of every workgroup: +2.5 % on the 10 x 128^2 solve of 1250 launches, so the split of a
-// sweep problem into (image, parameter block) is compiled into the SWEEP = true instances only.
-template <int TI, int TJ, bool SWEEP = false>
+// sweep problem into (image, parameter block) is compiled into the SR_SWEEP instances only, and the block of image img
+// (one scalar multiply, no division) into the SR_EACH instances only.
+template <int TI, int TJ, SrAddr ADDR = SR_SHARED>
 __global__ __launch_bounds__(TI* TJ) void sr_tile_kernel(SrArgs A) {
     constexpr int RI = TI, RJ = TJ, RN = RI * RJ;
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -66,7 +74,8 @@ __global__ __launch_bounds__(TI* TJ) void sr_tile_kernel(SrArgs A) {
     tile_span(tb, A.N, RJ, A.halo, oj, cj0, cj1);
     const int M = A.M, N = A.N;
     int fimg = img, apar = 0;   // uniform over the workgroup: scalar registers
-    if (SWEEP) { fimg = (int)((unsigned)img % (unsigned)A.Odata); apar = (int)((unsigned)img / (unsigned)A.Odata); }
+    if (ADDR == SR_SWEEP) { fimg = (int)((unsigned)img % (unsigned)A.Odata); apar = (int)((unsigned)img / (unsigned)A.Odata); }
+    if (ADDR == SR_EACH) apar = img;
     const size_t base = (size_t)img * M * N;                             // state planes: one slot per problem
     const double* __restrict__ fsrc = A.f + (size_t)fimg * M * N;        // dataset plane
     const double* __restrict__ alpha = A.alpha + (size_t)apar * A.astride;
@@ -190,7 +199,7 @@ __global__ __launch_bounds__(TI* TJ) void sr_tile_kernel(SrArgs A) {
 // in registers: of the 12 LDS reads and 7 writes per pixel and iteration of sr_tile_kernel, 8 and 5.33 remain at
 // PJ = 3 (planes yf2 / yb2 are only read across a strip boundary, from the strip's last / first pixel; yc2 from both).
 // Same operation sequence per pixel: bit-identical to sr_tile_kernel and to the oracle.
-template <int PJ, int TI, int TJ, bool SWEEP = false>
+template <int PJ, int TI, int TJ, SrAddr ADDR = SR_SHARED>
 __global__ __launch_bounds__(TI* TJ) void sr_strip_kernel(SrArgs A) {
     constexpr int RI = TI, RJ = PJ * TJ, RN = RI * RJ;
     extern __shared__ __attribute__((aligned(16))) double smem[];
@@ -206,7 +215,8 @@ __global__ __launch_bounds__(TI* TJ) void sr_strip_kernel(SrArgs A) {
     tile_span(tb, A.N, RJ, A.halo, oj, cj0, cj1);
     const int M = A.M, N = A.N;
     int fimg = img, apar = 0;   // as in sr_tile_kernel
-    if (SWEEP) { fimg = (int)((unsigned)img % (unsigned)A.Odata); apar = (int)((unsigned)img / (unsigned)A.Odata); }
+    if (ADDR == SR_SWEEP) { fimg = (int)((unsigned)img % (unsigned)A.Odata); apar = (int)((unsigned)img / (unsigned)A.Odata); }
+    if (ADDR == SR_EACH) apar = img;
     const size_t base = (size_t)img * M * N;
     const double* __restrict__ fsrc = A.f + (size_t)fimg * M * N;
     const double* __restrict__ alpha = A.alpha + (size_t)apar * A.astride;
@@ -409,14 +419,16 @@ __device__ __forceinline__ double sr_gradT_at(int k, const double* __restrict__ 
 // partial[(k*nblk+b)*4 + {0: ||u-f||^2, 1: sum_k sum alpha_k |G_k u|, 2: ||f||^2, 3: ||f - K^T y||^2}], K^T y =
 // (G_f^T y_f + G_b^T y_b) + G_c^T y_c; gap_final_kernel turns them into gap_k >= 0.5 ||u_k - u*_k||^2 for every feasible
 // dual.  Checker: bplo_sumregs_gap.  state: the seven planes x, yf1, yf2, yb1, yb2, yc1, yc2.  grid (nblk, O), block 256.
+// bstride: doubles between per-image parameter blocks (image k's gap uses block k); 0: one block for every image.
 struct SrState { const double* pl[7]; };
 __global__ __launch_bounds__(256) void sr_gap_partial_kernel(SrState S, const double* __restrict__ f, const double* __restrict__ alpha,
-                                                             int am, int an, int M, int N, double* __restrict__ partial) {
+                                                             int am, int an, int M, int N, int bstride, double* __restrict__ partial) {
     __shared__ double sh[4];
     const int npx = M * N;
     const size_t base = (size_t)blockIdx.y * npx;
     const double* u = S.pl[0] + base;
     const size_t asl = (size_t)am * an;
+    alpha += (size_t)blockIdx.y * bstride;
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
     for (int q = blockIdx.x * 256 + threadIdx.x; q < npx; q += gridDim.x * 256) {
         const int i = q % M, j = q / M;
@@ -451,10 +463,12 @@ __global__ __launch_bounds__(256) void sr_gap_partial_kernel(SrState S, const do
 // pixel, all three operators.  reg: gradient_reg (gamma = 1e3 vector / 1e8 patch parameter).
 // COT = false: right-hand side of the loss 0.5||u - ubar||^2 (src = ubar); COT = true: of a vector-Jacobian product with
 // the cotangent gu = dL/du (src = gu), which takes the place of u - ubar.  The coefficient planes do not depend on COT.
+// bstride: doubles between per-image parameter blocks -- image img of the launch reads alpha + img * bstride
+// (bpltv_sumregs_vjp_each); 0: one block for every image.
 template <bool COT>
 __device__ __forceinline__ void sr_adj_setup_body(const double* __restrict__ u, const double* __restrict__ src,
-                                                  const double* __restrict__ alpha, int am, int an, int M, int N, int O,
-                                                  int patch, int reg, double kappa_act, SrCoef C) {
+                                                  const double* __restrict__ alpha, int am, int an, int bstride, int M, int N,
+                                                  int O, int patch, int reg, double kappa_act, SrCoef C) {
     // reg && patch: the parameter scales ROWS of term k (SumRegsLearningFunction.jl:250) and stays out of c, kap
     const size_t npx = (size_t)M * N;
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -463,6 +477,7 @@ __device__ __forceinline__ void sr_adj_setup_body(const double* __restrict__ u, 
     const int i = k0 % M, j = k0 / M;
     const double* ui = u + (size_t)img * npx;
     const size_t ai = sr_alpha_index(am, an, M, N, i, j), astride = (size_t)am * an;
+    alpha += (size_t)img * bstride;
     const double gamma = patch ? 1e8 : 1e3;   // SumRegsLearningFunction.jl:200 / :117
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -499,16 +514,17 @@ __device__ __forceinline__ void sr_adj_setup_body(const double* __restrict__ u, 
 }
 
 __global__ __launch_bounds__(256) void sr_adj_setup_kernel(const double* __restrict__ u, const double* __restrict__ ubar,
-                                                           const double* __restrict__ alpha, int am, int an, int M, int N, int O,
-                                                           int patch, int reg, double kappa_act, SrCoef C) {
-    sr_adj_setup_body<false>(u, ubar, alpha, am, an, M, N, O, patch, reg, kappa_act, C);
+                                                           const double* __restrict__ alpha, int am, int an, int bstride, int M,
+                                                           int N, int O, int patch, int reg, double kappa_act, SrCoef C) {
+    sr_adj_setup_body<false>(u, ubar, alpha, am, an, bstride, M, N, O, patch, reg, kappa_act, C);
 }
 
 // The same coefficients with the right-hand side of a vector-Jacobian product: gu, or -gu for sumregs_gradient_reg.
 __global__ __launch_bounds__(256) void sr_adj_setup_cot_kernel(const double* __restrict__ u, const double* __restrict__ gu,
-                                                               const double* __restrict__ alpha, int am, int an, int M, int N,
-                                                               int O, int patch, int reg, double kappa_act, SrCoef C) {
-    sr_adj_setup_body<true>(u, gu, alpha, am, an, M, N, O, patch, reg, kappa_act, C);
+                                                               const double* __restrict__ alpha, int am, int an, int bstride,
+                                                               int M, int N, int O, int patch, int reg, double kappa_act,
+                                                               SrCoef C) {
+    sr_adj_setup_body<true>(u, gu, alpha, am, an, bstride, M, N, O, patch, reg, kappa_act, C);
 }
 
 // Input gradient of a sum-of-regularisers vector-Jacobian product: the adjoint state p (there is no s plane on this
@@ -553,8 +569,9 @@ __device__ __forceinline__ int sr_geom_slot(int di, int dj) {
 // rowscale (nullable; with am, an: the parameter array) and planesU (nullable, zero-initialised by the caller): the
 // non-symmetric row-scaled system of sumregs_gradient_reg with a patch parameter -- every entry A(r, q) of term k is
 // multiplied by x_k at pixel r, and the strictly upper entries A(q - off, q) go to planesU[t][q - off] (by rows).
+// bstride: doubles between per-image blocks of rowscale (image img of the launch is scaled by block img); 0: one block.
 __global__ __launch_bounds__(256) void sr_adj_assemble_kernel(SrCoef C, int M, int N, int O, double* __restrict__ planes,
-                                                              const double* __restrict__ rowscale, int am, int an,
+                                                              const double* __restrict__ rowscale, int am, int an, int bstride,
                                                               double* __restrict__ planesU) {
     const size_t npx = (size_t)M * N;
     const size_t col = (size_t)blockIdx.x * 256 + threadIdx.x;
@@ -565,6 +582,7 @@ __global__ __launch_bounds__(256) void sr_adj_assemble_kernel(SrCoef C, int M, i
     double accu[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     const size_t astride = (size_t)am * an;
     const size_t ib = (size_t)img * npx;
+    if (rowscale) rowscale += (size_t)img * bstride;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
         // candidate elements whose stencil can contain q: q itself and its four neighbours
@@ -634,7 +652,7 @@ __global__ __launch_bounds__(256) void sr_adj_flux_kernel(SrCoef C, const double
 // residual, pass 2: out = rhs - (p + sum_k G_k^T w_k)
 __global__ __launch_bounds__(256) void sr_adj_residual_kernel(SrCoef C, const double* __restrict__ p, const double* __restrict__ w,
                                                               int M, int N, int O, double* __restrict__ out,
-                                                              const double* __restrict__ rowscale, int am, int an) {
+                                                              const double* __restrict__ rowscale, int am, int an, int bstride) {
     const size_t npx = (size_t)M * N;
     const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= npx * O) return;
@@ -642,6 +660,7 @@ __global__ __launch_bounds__(256) void sr_adj_residual_kernel(SrCoef C, const do
     const int i = k0 % M, j = k0 / M;
     const size_t ib = (size_t)img * npx;
     double s = p[e];
+    if (rowscale) rowscale += (size_t)img * bstride;   // image img's block (0: one block for every image)
     const size_t ai = rowscale ? sr_alpha_index(am, an, M, N, i, j) : 0, astride = (size_t)am * an;
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -673,6 +692,17 @@ __global__ __launch_bounds__(256) void sr_adj_gradpix_kernel(SrCoef C, const dou
         }
         gpix[(size_t)k * C.tot + e] = reg ? v : -v;
     }
+}
+
+// The per-image parameter gradients of three pixel maps (bpltv_sumregs_vjp_each): the planes gpix[slice][image][M*N] as
+// out[image][slice][M*N], image k's three slices side by side.  grid over 3*O*M*N.
+__global__ __launch_bounds__(256) void sr_gpix_each_kernel(const double* __restrict__ gpix, size_t npx, int O,
+                                                           double* __restrict__ out) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;   // index into out
+    if (e >= 3 * npx * O) return;
+    const size_t img = e / (3 * npx), r = e - img * 3 * npx;
+    const size_t k = r / npx, q = r - k * npx;
+    out[e] = gpix[(k * O + img) * npx + q];
 }
 
 }  // namespace bpltv

@@ -348,6 +348,63 @@ class TVSolver:
                                                     int(an), int(bool(reg)), C.byref(p), C.c_void_p(gu_ptr),
                                                     C.c_void_p(grad_f_ptr or None), C.c_void_p(grad_alphas_ptr or None)))
 
+    # -- one block of three weights per image (bpltv_sumregs_denoise_each / bpltv_sumregs_vjp_each) ---------------
+    def _sr_each_arg(self, alphas):
+        """alphas: (O, 3) vectors or (O, 3, n, m) patch / map blocks (the layout of sumregs_evaluate per block), one per
+        image."""
+        a = np.ascontiguousarray(alphas, dtype=np.float64)
+        if a.ndim == 2 and a.shape[1] == 3:
+            am, an = 1, 1
+        elif a.ndim == 4 and a.shape[1] == 3:
+            an, am = a.shape[2], a.shape[3]
+        else:
+            raise ValueError("alphas must have shape (O, 3) or (O, 3, n, m), got %s" % (a.shape,))
+        if a.shape[0] != self.O:
+            raise ValueError("alphas has %d blocks, the handle holds O=%d images" % (a.shape[0], self.O))
+        return a, am, an
+
+    def sumregs_denoise_each(self, alphas, fetch=True, **kw):
+        """sumregs_denoise with image k's own three weights alphas[k] (bpltv_sumregs_denoise_each); u[k] is bitwise a
+        one-image solve of (f[k], alphas[k])."""
+        a, am, an = self._sr_each_arg(alphas)
+        p = self.params(_sumregs=True, **kw)
+        u = np.empty((self.O, self.N, self.M)) if fetch else None
+        self._check(self._lib.bpltv_sumregs_denoise_each(self._h, _ptr(a), am, an, C.byref(p),
+                                                         _ptr(u) if fetch else None))
+        return u
+
+    def sumregs_denoise_each_device(self, alphas_ptr, am=1, an=1, **kw):
+        """bpltv_sumregs_denoise_each_device: O parameter blocks (O*3*am*an doubles, a C-contiguous (O, 3, an, am)
+        array) resident in HBM at `alphas_ptr`; the result stays on the device (u_device_ptr / copy_u_device)."""
+        p = self.params(_sumregs=True, **kw)
+        self._check(self._lib.bpltv_sumregs_denoise_each_device(self._h, C.c_void_p(alphas_ptr), int(am), int(an),
+                                                                C.byref(p)))
+
+    def sumregs_vjp_each(self, u, alphas, gu, reg=False, want_f=True, want_alpha=True, **kw):
+        """sumregs_vjp with image k's own block alphas[k] (bpltv_sumregs_vjp_each): (grad_f, grad_alphas).  grad_alphas
+        has the shape of alphas; grad_alphas[k] is image k's term alone, not summed over the images."""
+        if not (want_f or want_alpha):
+            raise ValueError("sumregs_vjp_each: want_f and want_alpha are both False")
+        a, am, an = self._sr_each_arg(alphas)
+        u = self._batch(u, "u")
+        gu = self._batch(gu, "gu")
+        p = self.params(_sumregs=True, **kw)
+        gf = np.empty((self.O, self.N, self.M)) if want_f else None
+        ga = np.empty(a.shape) if want_alpha else None
+        self._check(self._lib.bpltv_sumregs_vjp_each(self._h, _ptr(u), _ptr(a), am, an, int(bool(reg)), C.byref(p),
+                                                     _ptr(gu), _ptr(gf) if want_f else None,
+                                                     _ptr(ga) if want_alpha else None))
+        return gf, ga
+
+    def sumregs_vjp_each_device(self, u_ptr, alphas_ptr, am, an, gu_ptr, grad_f_ptr, grad_alphas_ptr, reg=False, **kw):
+        """bpltv_sumregs_vjp_each_device: u, gu and grad_f (M*N*O doubles), the O parameter blocks and their O gradients
+        (O*3*am*an doubles each) all resident in HBM; either output pointer may be 0 / None, not both."""
+        p = self.params(_sumregs=True, **kw)
+        self._check(self._lib.bpltv_sumregs_vjp_each_device(self._h, C.c_void_p(u_ptr), C.c_void_p(alphas_ptr), int(am),
+                                                            int(an), int(bool(reg)), C.byref(p), C.c_void_p(gu_ptr),
+                                                            C.c_void_p(grad_f_ptr or None),
+                                                            C.c_void_p(grad_alphas_ptr or None)))
+
     def sweep(self, alphas, fetch_u=False, **kw):
         """costs[k] = 0.5*||denoise(f, alphas[k]) - ubar||^2 for K parameters in one batched solve
         (generate_cost / generate_2d_cost, /root/reference/src/BPLDenoising.jl:92-111,136-158).

@@ -23,6 +23,11 @@ alpha is then float64 of shape (3,) (one weight per difference: forward, backwar
 parameter) or (3, H, W) (maps); a C-contiguous (3, pH, pW) tensor is already the library's slice layout (an, am =
 pH, pW).  The backward pass is bpltv_sumregs_vjp_device's; reg selects sumregs_gradient_reg.
 
+    u = sumregs_denoise_each(f, alpha, reg=False)          # three weights per image (bpltv_sumregs_denoise_each / _vjp_each)
+
+f is then (B, H, W) and alpha float64 of shape (B, 3), (B, 3, pH, pW) or (B, 3, H, W); alpha.grad[k] is image k's term
+alone.  A separate function again: sumregs_denoise rejects a leading batch dimension on alpha.
+
 Streams: the library runs its kernels on its own HIP streams and blocks until they are done.  Every call below first
 synchronises the tensors' current torch stream, so that the library reads inputs torch has finished writing; its
 outputs are complete when the call returns.
@@ -89,9 +94,10 @@ def _check_args(f, alpha, slices=1):
     return O, H, W, am, an
 
 
-def _check_args_each(f, alpha):
-    """(O, N, M, am, an) of a valid (f, alpha) pair of tv_denoise_each; TypeError / ValueError before any library call."""
-    name = "tv_denoise_each"
+def _check_args_each(f, alpha, slices=1):
+    """(O, N, M, am, an) of a valid (f, alpha) pair of tv_denoise_each or (slices = 3: a dimension of 3 behind the batch
+    dimension) sumregs_denoise_each; TypeError / ValueError before any library call."""
+    name = "sumregs_denoise_each" if slices == 3 else "tv_denoise_each"
     if not isinstance(f, torch.Tensor) or not isinstance(alpha, torch.Tensor):
         raise TypeError("%s: f and alpha must be torch tensors" % name)
     if f.dtype != torch.float64 or alpha.dtype != torch.float64:
@@ -100,7 +106,15 @@ def _check_args_each(f, alpha):
         raise ValueError("%s: f must have shape (B, H, W), got %s" % (name, tuple(f.shape)))
     B, H, W = f.shape
     shape = tuple(alpha.shape)
-    if shape == (B,):
+    if slices == 3:
+        if shape == (B, 3):
+            am = an = 1
+        elif len(shape) == 4 and shape[:2] == (B, 3) and 1 <= shape[2] <= H and 1 <= shape[3] <= W:
+            an, am = shape[2], shape[3]
+        else:
+            raise ValueError("%s: alpha must be (%d, 3), (%d, 3, pH, pW) with pH <= %d, pW <= %d, or (%d, 3, %d, %d); got %s"
+                             % (name, B, B, H, W, B, H, W, shape))
+    elif shape == (B,):
         am = an = 1
     elif len(shape) == 3 and shape[0] == B and 1 <= shape[1] <= H and 1 <= shape[2] <= W:
         an, am = shape[1], shape[2]
@@ -260,6 +274,50 @@ def sumregs_denoise(f, alpha, *, reg=False, **solver_kw):
     src/SumRegsLearningFunction.jl:38-85), differentiable in f and alpha.  alpha: (3,), (3, pH, pW) or (3, H, W).
     solver_kw: the solver parameters of TVSolver.params, used by the forward solve and the adjoint alike."""
     return SumRegsDenoiseFunction.apply(f, alpha, reg, solver_kw)
+
+
+class SumRegsDenoiseEachFunction(torch.autograd.Function):
+    """autograd.Function of sumregs_denoise_each (below); apply(f, alpha, reg, solver_kw)."""
+
+    @staticmethod
+    def forward(ctx, f, alpha, reg, solver_kw):
+        O, N, M, am, an = _check_args_each(f, alpha, slices=3)
+        index = f.device.index if f.device.index is not None else torch.cuda.current_device()
+        s = _solver(index, M, N, O)
+        fc = f.detach().contiguous()
+        ac = alpha.detach().contiguous()
+        u = torch.empty_like(fc)
+        _sync(f.device)
+        s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
+        s.sumregs_denoise_each_device(ac.data_ptr(), am, an, **solver_kw)
+        s.copy_u_device(u.data_ptr())
+        ctx.save_for_backward(u, ac)
+        ctx.solver, ctx.am, ctx.an, ctx.reg, ctx.solver_kw = s, am, an, bool(reg), dict(solver_kw)
+        return u
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gu):
+        need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_f or need_a):
+            return None, None, None, None
+        u, alpha = ctx.saved_tensors
+        gu = gu.to(dtype=torch.float64).contiguous()
+        gf = torch.empty_like(u) if need_f else None
+        ga = torch.empty_like(alpha) if need_a else None
+        _sync(u.device)
+        ctx.solver.sumregs_vjp_each_device(u.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(),
+                                           gf.data_ptr() if need_f else None, ga.data_ptr() if need_a else None,
+                                           reg=ctx.reg, **ctx.solver_kw)
+        return gf, ga, None, None
+
+
+def sumregs_denoise_each(f, alpha, *, reg=False, **solver_kw):
+    """u[k] = sumregs_denoise(f[k], alpha[k]) for a batch f of shape (B, H, W) with three weights per image: alpha
+    (B, 3), (B, 3, pH, pW) or (B, 3, H, W) on f's device.  One batched solve forward
+    (TVSolver.sumregs_denoise_each_device) and one adjoint solve backward (sumregs_vjp_each_device); differentiable in f
+    and alpha, alpha.grad[k] being image k's term.  solver_kw: as sumregs_denoise's."""
+    return SumRegsDenoiseEachFunction.apply(f, alpha, reg, solver_kw)
 
 
 class SumRegsDenoise(torch.nn.Module):

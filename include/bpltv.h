@@ -226,7 +226,8 @@ int bpltv_evaluate(bpltv_t *h, const double *alpha, int am, int an, double delta
  * factored by a banded LU).  The adjoint system is a 13-point stencil, factored by nested dissection (separators two
  * pixels wide; params.reserved[4] = 1: the HBM band solver at bandwidth 2M).
  * Both take single- and multi-device handles; set_data, per_image, u_device, duality_gap, stats are shared with the TV
- * model. */
+ * model.  One block of 3 * am * an doubles per image instead of one for the batch: bpltv_sumregs_denoise_each and
+ * bpltv_sumregs_vjp_each below. */
 int bpltv_sumregs_default_params(bpltv_params *p);
 int bpltv_sumregs_denoise(bpltv_t *h, const double *alpha, int am, int an, const bpltv_params *p, double *u_out);
 int bpltv_sumregs_evaluate(bpltv_t *h, const double *alpha, int am, int an, double delta, const bpltv_params *p,
@@ -336,6 +337,28 @@ int bpltv_sumregs_vjp(bpltv_t *h, const double *u, const double *alpha, int am, 
  * (multi: BPLTV_E_UNSUPPORTED beyond one shard). */
 int bpltv_sumregs_vjp_device(bpltv_t *h, const double *d_u, const double *d_alpha, int am, int an, int reg,
                              const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alpha);
+
+/* One parameter block per image for the sum-of-regularisers model: what bpltv_denoise_each and its family are to the TV
+ * model.  alphas: O blocks of 3*am*an doubles, block k at alphas + k*3*am*an, each in bpltv_sumregs_evaluate's layout
+ * (three slices of am x an, column major, forward / backward / centred).  u_k is bitwise what a one-image handle returns
+ * for (f_k, block k).  Each function keeps the contract of its twin (bpltv_sumregs_denoise, bpltv_sumregs_denoise_device,
+ * bpltv_sumregs_vjp, bpltv_sumregs_vjp_device), word for word: every entry of every block is checked (finite, >= 0; > 0
+ * when params.rho != 0, and for reg = 1 with a patch or map parameter) and gu must be finite before anything of the
+ * handle changes; params.reserved[4] = 2 and params.init / params.order return BPLTV_E_UNSUPPORTED; dtype = 32 handles
+ * work (the model is Float64 there); check_every / gap_tol and bpltv_duality_gap use image k's own block; a shared and
+ * a per-image solve on one handle never replay each other's captured graphs; the VJP leaves the last solve,
+ * bpltv_u_device, bpltv_duality_gap and the graphs untouched, and the kappa retry and the residual gate apply to it.
+ * grad_f_out is bpltv_sumregs_vjp's; grad_alphas_out receives O blocks in the layout of alphas, block k = image k's
+ * term alone (their sum in image order is bitwise bpltv_sumregs_vjp's grad_alpha_out when all blocks are equal).
+ * Multi-device handles hand shard k the blocks [lo_k, hi_k) and write its gradient blocks in place; the device forms
+ * return BPLTV_E_UNSUPPORTED beyond one shard.  bpltv_sumregs_evaluate and bpltv_sumregs_sweep take one block for the
+ * batch: their sums over the images define the reference's learning function. */
+int bpltv_sumregs_denoise_each(bpltv_t *h, const double *alphas, int am, int an, const bpltv_params *p, double *u_out);
+int bpltv_sumregs_denoise_each_device(bpltv_t *h, const double *d_alphas, int am, int an, const bpltv_params *p);
+int bpltv_sumregs_vjp_each(bpltv_t *h, const double *u, const double *alphas, int am, int an, int reg,
+                           const bpltv_params *p, const double *gu, double *grad_f_out, double *grad_alphas_out);
+int bpltv_sumregs_vjp_each_device(bpltv_t *h, const double *d_u, const double *d_alphas, int am, int an, int reg,
+                                  const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alphas);
 
 /* Forward-only parameter sweep: generate_cost / generate_2d_cost (src/BPLDenoising.jl:92-111,
  * :136-158) evaluate cost(alpha_k) = 0.5*||TVDenoise(f, alpha_k) - ubar||^2 for a range of parameters,
