@@ -65,7 +65,8 @@ struct PdhgArgs {
                 // the launch + 1, PDHG_PHASE_STAMP) -- pdhg_phase_gate_kernel in the other chain waits for it to change
 #ifdef BPLTV_EXPERIMENTS
     int dbg;    // timing experiments of tools/ builds only (results are wrong): 1 skip state loads, 2 skip
-                // stores, 4 no iterations, 16 nt stores, 32 plain stores, 64 nt loads, 128 no barriers (rows kernel).  The product
+                // stores, 4 no iterations, 16 nt stores, 32 plain stores, 64 nt loads, 128 no barriers (rows kernel); these two keep
+                // the results: 2048 spent halo waves of the 1 px tile kernels go on computing, 4096 they stop inside the one loop.  The product
                 // library is compiled without this field and without the branches it feeds.
 #endif
 };
@@ -296,23 +297,28 @@ __global__ __launch_bounds__(TI* TJ) void pdhg_tile_kernel(PdhgArgs A) {
     // away from a region edge that is not an image border is only ever read for what it held after k iterations (k + 1
     // primal steps at the far edge, where the dual of the row above still reads its xbar); what it computes later is
     // garbage nobody uses.  A wave whose rows are all past their use stops computing and only keeps the barriers
-    // company.  Enabled for the multi-pixel variants of the large images, where the loop is bound by f64 issue (the
-    // freed slots go to the co-resident workgroup); with one pixel per thread -- the small batches, bound by the
-    // latency of the computing waves' dependent chain -- it was measured to buy nothing.
+    // company; the issue slots and LDS cycles it frees go to the waves that share its SIMD -- those of a co-resident
+    // workgroup included, which is what the small batches' two launch chains put there.
+    // Along j only: along i a wave's lanes cannot stop.
     int my_nit = nit;
-    if (PI * PJ > 1 && N > RJ) {
+    if (N > RJ && !(PI * PJ == 1 && (BPLTV_DBG(A) & 2048))) {   // (experiments, 1 px: 2048 keeps every wave computing)
         const int w0 = (tid & ~63) / TI, w1 = min((tid | 63) / TI, TJ - 1);      // thread rows of this wave
         const int r0 = PJ * w0, r1 = PJ * w1 + PJ - 1;                          // pixel rows of this wave
         if (oj > 0) my_nit = min(my_nit, r1);                                   // near edge: row k needs k iterations
         if (oj + RJ < N) my_nit = min(my_nit, RJ - r0);                         // far edge: row k' rows from it needs k' + 1
     }
+    // One pixel per thread: the loop ends with the wave's last needed iteration, and a second loop of bare barriers keeps
+    // the workgroup's count -- the loop of the computing waves carries no test for it.  Several pixels per thread: one
+    // loop, the two halves of an iteration under a wave-uniform branch.  (experiments, 1 px: 4096 takes the one-loop form)
+    const bool split = PI * PJ == 1 && !(BPLTV_DBG(A) & 4096);
+    const int loop_nit = split ? __builtin_amdgcn_readfirstlane(my_nit) : nit;   // wave-uniform: a scalar loop count
     // step sizes of iteration `it`: scalar loads, issued one iteration ahead
     const T* __restrict__ row = reinterpret_cast<const T*>(A.tab) + (size_t)TAB_STRIDE * A.it0;
     T tau = row[0], sigma = row[1], omega = row[2], inv1ptau = row[3], opw = row[4];
-    for (int it = 0; it < nit; ++it) {
+    for (int it = 0; it < loop_nit; ++it) {
         const T* __restrict__ nrow = row + TAB_STRIDE * ((it + 1 < nit) ? it + 1 : it);
         const T ntau = nrow[0], nsigma = nrow[1], nomega = nrow[2], ninv1ptau = nrow[3], nopw = nrow[4];
-        const bool act = it < my_nit;
+        const bool act = split || it < my_nit;
         T xb[PJ][PI];
         // ---- primal step: x <- prox_{tau*fidelity}(x - tau * G^T y); over-relaxation.
         // LDS reads are unconditional (clamped index) and selected afterwards: one wait for all.
@@ -400,6 +406,10 @@ __global__ __launch_bounds__(TI* TJ) void pdhg_tile_kernel(PdhgArgs A) {
             }
         }
         tau = ntau; sigma = nsigma; omega = nomega; inv1ptau = ninv1ptau; opw = nopw;
+        __syncthreads();
+    }
+    for (int it = loop_nit; it < nit; ++it) {   // a spent halo wave: the two barriers of an iteration, nothing else
+        __syncthreads();
         __syncthreads();
     }
 
