@@ -49,7 +49,15 @@ struct Variant {
     int tiles_per_block;   // 1: one workgroup per tile (pdhg_tile_kernel); > 1: that many one-wave tiles per workgroup
     int min_image;         // 1: the image must be at least as large as the region (pdhg_rows_kernel); 2: at least as wide
     int tmax = 0;          // > 0: most iterations a launch can fuse (pdhg_stream_kernel)
+    // pdhg_tile_kernel only: func / func32 are compiled for the (nTi, nTj, images) grid, these for the 1-D grid
+    const void* func_1d = nullptr;
+    const void* func32_1d = nullptr;
 };
+// the kernel symbol of a launch of variant V: the tile kernels know the form of their grid when they are compiled
+inline const void* pdhg_func(const Variant& V, int dtype, int grid3d) {
+    if (!grid3d && V.func_1d) return dtype == 32 ? V.func32_1d : V.func_1d;
+    return dtype == 32 ? V.func32 : V.func;
+}
 
 // grid of a launch of `tiles` tiles: (nTi, nTj, images) when the kernel decodes blockIdx that way (PdhgArgs::grid3d)
 inline dim3 pdhg_grid(const PdhgArgs& a, int tiles) {
@@ -61,16 +69,19 @@ inline int pdhg_grid3d_ok(int nTj, int nimg, int tiles_per_block) { return (tile
 template <typename T, int PI, int PJ, int TI, int TJ>
 void launch_variant(const PdhgArgs& a, int grid, hipStream_t s) {
     constexpr size_t lds = pdhg_lds_bytes(PI * TI, PJ * TJ, sizeof(T));
-    hipLaunchKernelGGL((pdhg_tile_kernel<T, PI, PJ, TI, TJ>), pdhg_grid(a, grid), dim3(TI * TJ), lds, s, a);
+    if (a.grid3d) hipLaunchKernelGGL((pdhg_tile_kernel<T, PI, PJ, TI, TJ, true>), pdhg_grid(a, grid), dim3(TI * TJ), lds, s, a);
+    else hipLaunchKernelGGL((pdhg_tile_kernel<T, PI, PJ, TI, TJ, false>), pdhg_grid(a, grid), dim3(TI * TJ), lds, s, a);
 }
 
 #define VAR(PI, PJ, TI, TJ)                                                                    \
     { PI * TI, PJ * TJ, TI * TJ, &launch_variant<double, PI, PJ, TI, TJ>,                       \
-      reinterpret_cast<const void*>(&pdhg_tile_kernel<double, PI, PJ, TI, TJ>),                 \
+      reinterpret_cast<const void*>(&pdhg_tile_kernel<double, PI, PJ, TI, TJ, true>),           \
       pdhg_lds_bytes(PI * TI, PJ * TJ), #PI "x" #PJ "px_" #TI "x" #TJ "thr",                    \
       &launch_variant<float, PI, PJ, TI, TJ>,                                                   \
-      reinterpret_cast<const void*>(&pdhg_tile_kernel<float, PI, PJ, TI, TJ>),                  \
-      pdhg_lds_bytes(PI * TI, PJ * TJ, sizeof(float)), 1, 0 }
+      reinterpret_cast<const void*>(&pdhg_tile_kernel<float, PI, PJ, TI, TJ, true>),            \
+      pdhg_lds_bytes(PI * TI, PJ * TJ, sizeof(float)), 1, 0, 0,                                 \
+      reinterpret_cast<const void*>(&pdhg_tile_kernel<double, PI, PJ, TI, TJ, false>),          \
+      reinterpret_cast<const void*>(&pdhg_tile_kernel<float, PI, PJ, TI, TJ, false>) }
 // register tiles: one wave per 32 x (2 PJ) region, WPB waves per workgroup (pdhg_wave_kernel)
 template <typename T, int PJ, int WPB>
 void launch_wave_variant(const PdhgArgs& a, int grid, hipStream_t s) {
@@ -681,7 +692,12 @@ int make_plan(bpltv_t* h, const bpltv_params& p, Plan* pl, int nimg) {
     PlanRequest q{h->M, h->N, nimg, h->ncu, p.maxiter, p.tile_iters, p.reserved[0], p.reserved[1]};
     const int rc = plan_pdhg(q, geom.data(), (int)geom.size(), pl);
     switch (rc) {
-        case PLAN_OK: return BPLTV_OK;
+        case PLAN_OK:
+            // pdhg_tile_kernel keeps a launch's step rows in a static LDS array of PDHG_MAX_T rows (only an image that
+            // fits one region can ask for more: a halo otherwise caps T at half a region, 31 at most)
+            if (kVariants[pl->variant].func_1d && pl->T > PDHG_MAX_T)
+                return set_err(h, BPLTV_E_ARG, "tile_iters = %d: the LDS-tile kernels fuse at most %d iterations per launch", pl->T, PDHG_MAX_T);
+            return BPLTV_OK;
         case PLAN_E_VARIANT: return set_err(h, BPLTV_E_ARG, "unknown kernel variant %d", p.reserved[0]);
         case PLAN_E_MIN_IMAGE: {
             const Variant& V = kVariants[p.reserved[0] - 1];
@@ -745,6 +761,7 @@ int build_graphs(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, const Pla
             a.phase = (phased && c == 0) ? h->d_phase : nullptr;
 #ifdef BPLTV_EXPERIMENTS
             a.dbg = p.reserved[3];
+            a.dbg_row[0] = p.tau0; a.dbg_row[1] = p.sigma0; a.dbg_row[2] = 1.0; a.dbg_row[3] = 1.0 / (1.0 + p.tau0); a.dbg_row[4] = 2.0;
 #endif
             const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
             a.first = (it == 0 && !from_state) ? 1 : 0;
@@ -755,10 +772,10 @@ int build_graphs(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, const Pla
             void* kargs[] = {&a};
             hipKernelNodeParams kp;
             std::memset(&kp, 0, sizeof(kp));
-            kp.func = const_cast<void*>(h->dtype == 32 ? V.func32 : V.func);
             a.ntiles = tilesPerImg * (hi - lo);
             a.xcd = (p.reserved[2] & 2) ? 1 : 0;
             a.grid3d = a.xcd ? 0 : pdhg_grid3d_ok(pl.nTj, hi - lo, V.tiles_per_block);
+            kp.func = const_cast<void*>(pdhg_func(V, h->dtype, a.grid3d));
             kp.gridDim = a.grid3d ? pdhg_grid(a, a.ntiles) : dim3((tilesPerImg * (hi - lo) + V.tiles_per_block - 1) / V.tiles_per_block);
             kp.blockDim = dim3(V.threads);
             kp.sharedMemBytes = (unsigned)(h->dtype == 32 ? V.lds32 : V.lds);
@@ -809,6 +826,7 @@ int enqueue_pdhg(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, const Pla
     a.grid3d = a.xcd ? 0 : pdhg_grid3d_ok(pl.nTj, x.nimg, V.tiles_per_block);
 #ifdef BPLTV_EXPERIMENTS
     a.dbg = p.reserved[3];
+    a.dbg_row[0] = p.tau0; a.dbg_row[1] = p.sigma0; a.dbg_row[2] = 1.0; a.dbg_row[3] = 1.0 / (1.0 + p.tau0); a.dbg_row[4] = 2.0;
 #endif
     int cur = *buf;
     for (int it = it0; it < it1; it += pl.T) {
@@ -2836,6 +2854,10 @@ int bpltv_create(bpltv_t** out, int M, int N, int O, int device, int dtype) {
             HIPCHK(h, hipFuncSetAttribute(V.func, hipFuncAttributeMaxDynamicSharedMemorySize, (int)V.lds));
         if (dtype == 32 && V.lds32 > 64 * 1024)
             HIPCHK(h, hipFuncSetAttribute(V.func32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)V.lds32));
+        if (V.func_1d && V.lds > 64 * 1024)
+            HIPCHK(h, hipFuncSetAttribute(V.func_1d, hipFuncAttributeMaxDynamicSharedMemorySize, (int)V.lds));
+        if (V.func32_1d && dtype == 32 && V.lds32 > 64 * 1024)
+            HIPCHK(h, hipFuncSetAttribute(V.func32_1d, hipFuncAttributeMaxDynamicSharedMemorySize, (int)V.lds32));
     }
     return BPLTV_OK;
 }

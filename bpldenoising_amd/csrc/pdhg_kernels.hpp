@@ -31,6 +31,10 @@ constexpr size_t pdhg_lds_bytes(int RI, int RJ, size_t word = sizeof(double)) {
 }
 
 constexpr int TAB_STRIDE = 8;  // doubles per iteration row: tau, sigma, omega, 1/(1+tau), 1+omega, pad
+// Deepest fusion of pdhg_tile_kernel: the step rows of a launch are copied into a static LDS array of PDHG_MAX_T rows, one
+// word per thread (the smallest tile variant has 256 threads = 32 rows).  Images larger than a region cap T at (R - 1) / 2
+// <= 31 anyway; make_plan refuses a deeper plan for an image that fits one region.
+constexpr int PDHG_MAX_T = 32;
 
 struct PdhgArgs {
     const double* xin;
@@ -65,9 +69,13 @@ struct PdhgArgs {
                 // the launch + 1, PDHG_PHASE_STAMP) -- pdhg_phase_gate_kernel in the other chain waits for it to change
 #ifdef BPLTV_EXPERIMENTS
     int dbg;    // timing experiments of tools/ builds only (results are wrong): 1 skip state loads, 2 skip
-                // stores, 4 no iterations, 16 nt stores, 32 plain stores, 64 nt loads, 128 no barriers (rows kernel); these two keep
-                // the results: 2048 spent halo waves of the 1 px tile kernels go on computing, 4096 they stop inside the one loop.  The product
-                // library is compiled without this field and without the branches it feeds.
+                // stores, 4 no iterations, 16 nt stores, 32 plain stores, 64 nt loads, 128 no barriers (rows kernel); these three keep
+                // the results: 2048 spent halo waves of the 1 px tile kernels go on computing, 4096 they stop inside the one loop,
+                // 8192 the tile kernels fetch their step rows by scalar loads (first row behind the first barrier, the next row
+                // inside the loop: the form before the rows moved to LDS).  With 8192, wrong results again: 16384 the loop keeps
+                // the first row and fetches nothing, 32768 the first row is dbg_row instead of a fetch (tools/step_rows_ab.py).
+                // The product library is compiled without these fields and without the branches they feed.
+    double dbg_row[5];
 #endif
 };
 
@@ -95,8 +103,11 @@ __device__ long long pdhg_tlog[2][4096];
 #define PDHG_DECODE_BLOCK(A, imgl, ta, tb)                                   \
     PDHG_PHASE_STAMP(A)                                                      \
     PDHG_TLOG(A)                                                             \
+    PDHG_DECODE_TILE((A).grid3d, A, imgl, ta, tb)
+// the decode alone (pdhg_tile_kernel stamps behind its state loads, and knows the grid's form when it is compiled)
+#define PDHG_DECODE_TILE(G3, A, imgl, ta, tb)                                \
     int imgl, ta, tb;                                                        \
-    if ((A).grid3d) {                                                        \
+    if (G3) {                                                                \
         ta = (int)blockIdx.x; tb = (int)blockIdx.y; imgl = (int)blockIdx.z;  \
     } else {                                                                 \
         const int tilesPerImg_ = (A).nTi * (A).nTj;                          \
@@ -172,7 +183,12 @@ __device__ __forceinline__ float pd_fma(float a, float b, float c) { return __bu
 // T = double: the reference's arithmetic.  T = float: the opt-in single-precision mode of bpltv_create(dtype = 32) --
 // the same operation sequence in f32 ("spec v2f": bplo_pdhg_f32 of the oracle), with state, f, alpha and the step
 // table held as float (the pointers of PdhgArgs then address float arrays): half the LDS and HBM bytes per pixel.
-template <typename T, int PI, int PJ, int TI, int TJ>
+// G3: the grid is (nTi, nTj, images) (PdhgArgs::grid3d; the host launches the instantiation that matches).  A template
+// argument and not a branch: behind a branch at the kernel's entry the compiler fetches the rest of the kernel arguments
+// -- the state pointers among them -- only in the block where the two paths meet, a second scalar round trip in front
+// of the state loads.  This way they are fetched right behind the first wait, the tile arithmetic between them and
+// their first use.
+template <typename T, int PI, int PJ, int TI, int TJ, bool G3>
 __global__ __launch_bounds__(TI* TJ) void pdhg_tile_kernel(PdhgArgs A) {
     constexpr int RI = PI * TI, RJ = PJ * TJ;
     // LDS planes with guard cells so that the neighbour reads need no select:
@@ -187,6 +203,9 @@ __global__ __launch_bounds__(TI* TJ) void pdhg_tile_kernel(PdhgArgs A) {
     T* sy1 = smem;                              // [RJ][S1]
     T* sy2 = smem + RJ * S1;                    // [RJ+1][RI]
     T* sxb = smem + RJ * S1 + (RJ + 1) * RI;    // [RJ][RI] + RI + 1
+    // the step rows [it0, it0 + nit) of this launch (static: beside the dynamic planes, pdhg_lds_bytes does not count it)
+    static_assert(TI * TJ >= PDHG_MAX_T * TAB_STRIDE, "one thread per word of the launch's step rows");
+    __shared__ __attribute__((aligned(16))) T srow[PDHG_MAX_T * TAB_STRIDE];
     const T* __restrict__ Axin = reinterpret_cast<const T*>(A.xin);
     const T* __restrict__ Ay1in = reinterpret_cast<const T*>(A.y1in);
     const T* __restrict__ Ay2in = reinterpret_cast<const T*>(A.y2in);
@@ -197,7 +216,7 @@ __global__ __launch_bounds__(TI* TJ) void pdhg_tile_kernel(PdhgArgs A) {
 
     const int tid = threadIdx.x;
     const int ti = tid % TI, tj = tid / TI;
-    PDHG_DECODE_BLOCK(A, imgl, ta, tb)
+    PDHG_DECODE_TILE(G3, A, imgl, ta, tb)
     const int img = A.img0 + imgl;
     int oi, ci0, ci1, oj, cj0, cj1;
     tile_span(ta, A.M, RI, A.halo, oi, ci0, ci1);
@@ -256,6 +275,19 @@ __global__ __launch_bounds__(TI* TJ) void pdhg_tile_kernel(PdhgArgs A) {
             f[pj][pi] = Af[fidx[pj][pi]];
             al[pj][pi] = alpha[aidx[pj][pi]];
         }
+    // The launch's step rows travel with the state loads: one word per thread, written to LDS in front of the first
+    // barrier -- no round trip and no barrier of their own.  (Fetched by scalar loads where they are used, every wave
+    // waited for them in full: LDS and scalar memory share one counter and scalar loads return out of order, so the
+    // first row cost a round trip behind the first barrier and the "prefetch" of the next row was waited for in front
+    // of the iteration's second barrier, a new 64-byte line every iteration.)
+    const bool lds_rows = !(BPLTV_DBG(A) & 8192);
+    const bool row_word = lds_rows && tid < A.nit * TAB_STRIDE;   // nit <= halo <= PDHG_MAX_T: the host checks
+    T row_w = T(0);
+    if (row_word) row_w = reinterpret_cast<const T*>(A.tab)[(size_t)TAB_STRIDE * A.it0 + tid];
+    // (the stamp is one plain store that waits for nothing; it goes out behind the loads so that no branch stands
+    // between the kernel's entry and them)
+    PDHG_PHASE_STAMP(A)
+    PDHG_TLOG(A)
 #pragma unroll
     for (int pj = 0; pj < PJ; ++pj)
 #pragma unroll
@@ -276,6 +308,7 @@ __global__ __launch_bounds__(TI* TJ) void pdhg_tile_kernel(PdhgArgs A) {
     for (int e = threadIdx.x; e < RJ; e += TI * TJ) sy1[e * S1] = T(0);
     for (int e = threadIdx.x; e < RI; e += TI * TJ) sy2[e] = T(0);
     for (int e = threadIdx.x; e < RI + 1; e += TI * TJ) sxb[RI * RJ + e] = T(0);
+    if (row_word) srow[tid] = row_w;
     __syncthreads();
 
     const T rho = (T)A.rho;
@@ -312,12 +345,28 @@ __global__ __launch_bounds__(TI* TJ) void pdhg_tile_kernel(PdhgArgs A) {
     // loop, the two halves of an iteration under a wave-uniform branch.  (experiments, 1 px: 4096 takes the one-loop form)
     const bool split = PI * PJ == 1 && !(BPLTV_DBG(A) & 4096);
     const int loop_nit = split ? __builtin_amdgcn_readfirstlane(my_nit) : nit;   // wave-uniform: a scalar loop count
-    // step sizes of iteration `it`: scalar loads, issued one iteration ahead
+    // step sizes of iteration `it`: from the launch's rows in LDS (uniform reads; LDS returns in order, so their waits
+    // are counted and no barrier waits for them).  The next row is read behind the first barrier of an iteration,
+    // under the dual step's arithmetic.
+    T tau = srow[0], sigma = srow[1], omega = srow[2], inv1ptau = srow[3], opw = srow[4];
+#ifdef BPLTV_EXPERIMENTS
     const T* __restrict__ row = reinterpret_cast<const T*>(A.tab) + (size_t)TAB_STRIDE * A.it0;
-    T tau = row[0], sigma = row[1], omega = row[2], inv1ptau = row[3], opw = row[4];
+    if (!lds_rows) {   // 8192: scalar loads, as before
+        if (BPLTV_DBG(A) & 32768) {
+            tau = (T)A.dbg_row[0]; sigma = (T)A.dbg_row[1]; omega = (T)A.dbg_row[2]; inv1ptau = (T)A.dbg_row[3]; opw = (T)A.dbg_row[4];
+        } else {
+            tau = row[0]; sigma = row[1]; omega = row[2]; inv1ptau = row[3]; opw = row[4];
+        }
+    }
+#endif
     for (int it = 0; it < loop_nit; ++it) {
-        const T* __restrict__ nrow = row + TAB_STRIDE * ((it + 1 < nit) ? it + 1 : it);
-        const T ntau = nrow[0], nsigma = nrow[1], nomega = nrow[2], ninv1ptau = nrow[3], nopw = nrow[4];
+        T ntau = tau, nsigma = sigma, nomega = omega, ninv1ptau = inv1ptau, nopw = opw;
+#ifdef BPLTV_EXPERIMENTS
+        if (!lds_rows && !(BPLTV_DBG(A) & 16384)) {
+            const T* __restrict__ nrow = row + TAB_STRIDE * ((it + 1 < nit) ? it + 1 : it);
+            ntau = nrow[0]; nsigma = nrow[1]; nomega = nrow[2]; ninv1ptau = nrow[3]; nopw = nrow[4];
+        }
+#endif
         const bool act = split || it < my_nit;
         T xb[PJ][PI];
         // ---- primal step: x <- prox_{tau*fidelity}(x - tau * G^T y); over-relaxation.
@@ -350,6 +399,10 @@ __global__ __launch_bounds__(TI* TJ) void pdhg_tile_kernel(PdhgArgs A) {
         }
         __syncthreads();
         if (act) {
+        if (lds_rows) {
+            const T* nrow = srow + TAB_STRIDE * ((it + 1 < nit) ? it + 1 : it);
+            ntau = nrow[0]; nsigma = nrow[1]; nomega = nrow[2]; ninv1ptau = nrow[3]; nopw = nrow[4];
+        }
         // ---- dual step: y <- proj_{|y_ij| <= alpha_ij}((y + sigma * G xbar) / (1 + sigma*rho/alpha))
         T xp1[PJ][PI], xpM[PJ][PI];
 #pragma unroll
