@@ -881,4 +881,80 @@ __global__ void adj_resnorm_final_kernel(const double* __restrict__ partial, int
     out[e] = s;
 }
 
+// ---- forward mode: the Jacobian-vector product of u = denoise(f, alpha) (bpltv_jvp) --------------------------------
+// The JVP is the linear map whose transpose the vector-Jacobian product above computes, so it solves with the same
+// matrix.  Right-hand side of one direction (df, dalpha), on the coefficient planes adj_setup_body wrote:
+//     reg = 0, and reg = 1 with a scalar:   r = df - G^T (h o up(dalpha))     (transpose of adj_gradpix_kernel's first branch)
+//     reg = 1 with a patch or map:          r = df - (G^T h) o up(dalpha)     (node-wise: of its second branch)
+// written as S r (s = 1 unless reg = 1 with an array parameter): the system solved is (I + S G^T W G S) q = S r.
+// df, dalpha: this group's first image of one direction, or nullptr (a zero tangent); dalpha is addressed like the
+// parameter (am, an, astride: 0 = one block for every image, am*an = image k reads block k).
+__global__ __launch_bounds__(256) void adj_tangent_rhs_kernel(AdjCoef C, const double* __restrict__ df,
+                                                              const double* __restrict__ dalpha, int am, int an,
+                                                              int astride, int M, int N, int O, int patch, int reg) {
+    const size_t npx = (size_t)M * N;
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= npx * O) return;
+    const int k = (int)(q % npx);
+    const int i = k % M, j = k / M;
+    double r = df ? df[q] : 0.0;
+    if (dalpha) {
+        const double* da = dalpha + (q / npx) * (size_t)astride;
+        if (!(reg && patch)) {
+            const double w1 = (i < M - 1) ? C.h1[q] * alpha_at(da, am, an, M, N, i, j) : 0.0;
+            const double w2 = (j < N - 1) ? C.h2[q] * alpha_at(da, am, an, M, N, i, j) : 0.0;
+            const double w1m = (i > 0) ? C.h1[q - 1] * alpha_at(da, am, an, M, N, i - 1, j) : 0.0;
+            const double w2m = (j > 0) ? C.h2[q - M] * alpha_at(da, am, an, M, N, i, j - 1) : 0.0;
+            r -= (w1m - w1) + (w2m - w2);
+        } else {
+            const double a = (i < M - 1) ? C.h1[q] : 0.0, am_ = (i > 0) ? C.h1[q - 1] : 0.0;
+            const double b = (j < N - 1) ? C.h2[q] : 0.0, bm = (j > 0) ? C.h2[q - M] : 0.0;
+            r -= ((am_ - a) + (bm - b)) * alpha_at(da, am, an, M, N, i, j);
+        }
+    }
+    C.rhs[q] = C.s[q] * r;
+}
+
+// The tangent of u: du = S^-1 q, straight into the direction's slice of the caller's array.
+__global__ __launch_bounds__(256) void adj_du_kernel(const double* __restrict__ s, const double* __restrict__ p, size_t n,
+                                                     double* __restrict__ du) {
+    const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (q >= n) return;
+    du[q] = p[q] / s[q];
+}
+
+// Gauss-Newton model of 0.5||u(alpha) - ubar||^2 (bpltv_gauss_newton): the Gram matrix of [J | u - ubar], J = the P
+// columns du/dalpha_j (P planes of tot = npx * O doubles).  grid (P + 1, P, O): block (b, a, k) adds image k's part of
+// <column a, column b> for b >= a (column P = u - ubar) into partial[(a * (P + 1) + b) * O + k]; gn_final_kernel adds the
+// images in image order (fixed order: reproducible) and writes both triangles from the one sum.
+__global__ __launch_bounds__(256) void gn_gram_kernel(const double* __restrict__ J, const double* __restrict__ u,
+                                                      const double* __restrict__ ubar, int npx, int O, int P,
+                                                      double* __restrict__ partial) {
+    __shared__ double sh[4];
+    const int b = blockIdx.x, a = blockIdx.y, k = blockIdx.z;
+    if (b < a) return;
+    const size_t tot = (size_t)npx * O, base = (size_t)k * npx;
+    const double* ca = J + (size_t)a * tot + base;
+    double s = 0.0;
+    if (b < P) {
+        const double* cb = J + (size_t)b * tot + base;
+        for (int q = threadIdx.x; q < npx; q += 256) s += ca[q] * cb[q];
+    } else {
+        for (int q = threadIdx.x; q < npx; q += 256) s += ca[q] * (u[base + q] - ubar[base + q]);
+    }
+    s = block_sum<256>(s, sh);
+    if (threadIdx.x == 0) partial[((size_t)a * (P + 1) + b) * O + k] = s;
+}
+// out: [grad (P) | H (P x P, column major)]
+__global__ void gn_final_kernel(const double* __restrict__ partial, int O, int P, double* __restrict__ out) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= P * (P + 1)) return;
+    const int a = e / (P + 1), b = e % (P + 1);
+    if (b < a) return;
+    double s = 0.0;
+    for (int k = 0; k < O; ++k) s += partial[(size_t)e * O + k];
+    if (b == P) out[a] = s;
+    else { out[P + a + (size_t)P * b] = s; out[P + b + (size_t)P * a] = s; }
+}
+
 }  // namespace bpltv

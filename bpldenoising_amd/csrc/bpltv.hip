@@ -377,6 +377,10 @@ struct bpltv_handle {
     double* d_gf2 = nullptr;                      // staging of bpltv_vjp's input gradient
     double* d_vjp = nullptr;                      // bpltv_vjp(_device): [4 check words | parameter | parameter gradient]
     size_t vjp_cap = 0;
+    double* d_jvp = nullptr;                      // bpltv_jvp's host staging [du | df | dalpha]; bpltv_gauss_newton: [J | e_j | partials | grad, H]
+    size_t jvp_cap = 0;
+    double* d_jres = nullptr;                     // residual statistics of the directions of a bpltv_jvp with ndir > 1
+    size_t jres_cap = 0;
     // sum-of-regularisers model (sumregs_kernels.hpp): state and adjoint workspace, allocated on first use
     double* d_sr[2][7] = {{nullptr}, {nullptr}};   // x, yf1, yf2, yb1, yb2, yc1, yc2; two sets (ping-pong)
     // bpltv_sumregs_sweep solves a group of K_g * O problems in its own state sets, with its own parameter blocks
@@ -1379,6 +1383,13 @@ struct GradCtx {
     bool cot = false;
     double* d_out = nullptr;       // am*an parameter gradient (O*am*an when each), or nullptr: no per-pixel terms, no reduction
     double* d_grad_f = nullptr;    // M*N*O input gradient (+-S q), or nullptr
+    // forward mode (bpltv_jvp): ndir > 0 tangent directions solved against ONE factorisation per image group; src, cot,
+    // d_out and d_grad_f are then unused.  df: ndir * M*N*O doubles or nullptr; dalpha: ndir blocks of am*an doubles
+    // (each: of O * am*an, direction then image) or nullptr; du: ndir * M*N*O doubles -- all in HBM, direction-major.
+    int ndir = 0;
+    const double* df = nullptr;
+    const double* dalpha = nullptr;
+    double* du = nullptr;
 };
 GradCtx gradient_ctx(const bpltv_t* h, const double* d_ubar, double* d_out) {
     GradCtx g;
@@ -1419,6 +1430,16 @@ int run_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, 
     const bool direct = (method == ADJ_BAND_HBM || method == ADJ_ND);
     const int nref_default = direct ? (reg ? 0 : (patch ? 1 : 2)) : ((patch || reg) ? 2 : 3);
     const int nref = p.refine < 0 ? nref_default : p.refine;
+    // forward mode: every direction keeps its own residual statistics (the gate takes the worst)
+    const bool tangent = g.ndir > 0;
+    const int ndir = tangent ? g.ndir : 1;
+    double* resn_fin = h->d_resn;
+    if (ndir > 1) {
+        rc = ensure(h, &h->d_jres, &h->jres_cap, 4 * (size_t)O * ndir);
+        if (rc) return rc;
+        resn_fin = h->d_jres;
+    }
+    const size_t dastride = (size_t)am * an * (g.each ? O : 1);   // doubles between two directions of g.dalpha
     HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_fail, 0, sizeof(int) * O, h->stream));
     int chunks = 0;
@@ -1433,7 +1454,10 @@ int run_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, 
         int* dfail = h->d_fail + c0;
         const int gpx = (int)((ctot + 255) / 256);
         const double* ga = g.alpha + (size_t)c0 * g.astride;   // the group's first image's parameter block
-        if (g.cot)
+        if (tangent)   // the coefficient planes alone: adj_tangent_rhs_kernel writes each direction's right-hand side below
+            hipLaunchKernelGGL(adj_setup_cot_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, d_u + o0, ga, am, an, g.astride,
+                               M, N, nimg, patch, reg, kact, C);
+        else if (g.cot)
             hipLaunchKernelGGL(adj_setup_cot_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0, ga, am, an, g.astride,
                                M, N, nimg, patch, reg, kact, C);
         else
@@ -1464,20 +1488,28 @@ int run_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, 
             else solve_band_lds(h, vec, accv);
             return BPLTV_OK;
         };
-        // solve + iterative refinement against the matrix-free operator
-        HIPCHK(h, hipMemcpyAsync(dp, C.rhs, ctot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        rc = solve(dp, nullptr);
-        if (rc) return rc;
-        for (int it = 0; it < nref; ++it) {
-            hipLaunchKernelGGL(adj_residual_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, dr);
-            rc = solve(dr, dp);
+        for (int d = 0; d < ndir; ++d) {   // one pass, or the tangent directions against this group's factorisation
+            if (tangent)
+                hipLaunchKernelGGL(adj_tangent_rhs_kernel, dim3(gpx), dim3(256), 0, h->stream, C, g.df ? g.df + (size_t)d * tot + o0 : nullptr,
+                                   g.dalpha ? g.dalpha + (size_t)d * dastride + (size_t)c0 * g.astride : nullptr, am, an, g.astride, M, N,
+                                   nimg, patch, reg);
+            // solve + iterative refinement against the matrix-free operator
+            HIPCHK(h, hipMemcpyAsync(dp, C.rhs, ctot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+            rc = solve(dp, nullptr);
             if (rc) return rc;
+            for (int it = 0; it < nref; ++it) {
+                hipLaunchKernelGGL(adj_residual_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, dr);
+                rc = solve(dr, dp);
+                if (rc) return rc;
+            }
+            hipLaunchKernelGGL(adj_residual_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, dr);
+            double* resn_part = h->d_resn + 4 * (size_t)O + 4 * (size_t)c0 * RESN_BLK;
+            hipLaunchKernelGGL(adj_resnorm_kernel, dim3(RESN_BLK, nimg), dim3(256), 0, h->stream, dr, C.rhs, band4, (int)npx, resn_part);
+            hipLaunchKernelGGL(adj_resnorm_final_kernel, dim3((4 * nimg + 63) / 64), dim3(64), 0, h->stream, resn_part, nimg,
+                               resn_fin + 4 * ((size_t)d * O + c0));
+            if (tangent)
+                hipLaunchKernelGGL(adj_du_kernel, dim3(gpx), dim3(256), 0, h->stream, C.s, dp, ctot, g.du + (size_t)d * tot + o0);
         }
-        hipLaunchKernelGGL(adj_residual_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, dr);
-        double* resn_part = h->d_resn + 4 * (size_t)O + 4 * (size_t)c0 * RESN_BLK;
-        hipLaunchKernelGGL(adj_resnorm_kernel, dim3(RESN_BLK, nimg), dim3(256), 0, h->stream, dr, C.rhs, band4, (int)npx, resn_part);
-        hipLaunchKernelGGL(adj_resnorm_final_kernel, dim3((4 * nimg + 63) / 64), dim3(64), 0, h->stream, resn_part, nimg,
-                           h->d_resn + 4 * (size_t)c0);
         // gradient per pixel
         if (g.d_out)
             hipLaunchKernelGGL(adj_gradpix_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, patch, reg, dg);
@@ -1509,9 +1541,9 @@ int run_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, 
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
     std::vector<int> fail(O);
-    std::vector<double> resn(4 * (size_t)O);
+    std::vector<double> resn(4 * (size_t)O * ndir);
     HIPCHK(h, hipMemcpyAsync(fail.data(), h->d_fail, sizeof(int) * O, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(resn.data(), h->d_resn, sizeof(double) * 4 * O, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(resn.data(), resn_fin, sizeof(double) * resn.size(), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     float ms = 0.f;
     HIPCHK(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
@@ -1522,11 +1554,12 @@ int run_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, 
     h->st.hb_sync = (method == ADJ_BAND_HBM) ? (h->hb.value_sync ? 2 : 1) : 0;
     h->st.kappa_used = reg ? 0.0 : kact;
     double worst = 0.0, worst_raw = 0.0;
-    for (int k = 0; k < O; ++k) {
+    for (int k = 0; k < O; ++k)
         if (fail[k] != 0)
             return set_err(h, BPLTV_E_NUMERIC, "adjoint Cholesky: non-positive pivot at %s %d of image %d",
                            method == ADJ_BCR ? "block" : (method == ADJ_ND ? "front" : "column"), fail[k] - 1, k);
-        const double* q = &resn[4 * (size_t)k];
+    for (size_t k = 0; k < (size_t)O * ndir; ++k) {   // (direction, image) pairs: the worst of them
+        const double* q = &resn[4 * k];
         const double raw = std::sqrt(q[0]) / (q[1] > 0 ? std::sqrt(q[1]) : 1.0);
         const double scl = std::sqrt(q[2]) / (q[3] > 0 ? std::sqrt(q[3]) : 1.0);
         if (!(raw <= worst_raw)) worst_raw = raw;   // NaN-propagating max
@@ -1643,6 +1676,56 @@ int vjp_common(bpltv_t* h, const double* d_u, const double* alpha, bool alpha_de
     g.d_out = d_grad_alpha; g.d_grad_f = d_grad_f;
     h->has_per_image = false;   // the reduction scratch (d_red) no longer holds the last evaluate's rows
     return sr ? run_sr_gradient(h, d_u, g, reg ? 1 : 0, p) : run_gradient(h, d_u, g, reg ? 1 : 0, p);
+}
+
+// Jacobian-vector product of u = denoise(f, alpha) on a single-device handle (TV model): the linear map whose transpose
+// vjp_common computes, for ndir directions against one factorisation per image group (run_gradient_once).  d_u, the
+// tangents d_df / d_dalpha (either may be nullptr: a zero tangent) and d_du live in HBM, direction-major; `alpha` on the
+// host or (alpha_dev) in HBM.  Checks and staging as in vjp_common: nothing of the handle changes on a rejection, and
+// the last solve stays as it was.
+int jvp_common(bpltv_t* h, const double* d_u, const double* alpha, bool alpha_dev, int am, int an, int reg,
+               const bpltv_params* pp, int ndir, const double* d_df, const double* d_dalpha, double* d_du, bool each) {
+    if (!d_u || !alpha || !d_du) return set_err(h, BPLTV_E_ARG, "jvp: null pointer");
+    if (ndir < 1) return set_err(h, BPLTV_E_ARG, "jvp: ndir = %d (at least one direction)", ndir);
+    if (!d_df && !d_dalpha) return set_err(h, BPLTV_E_ARG, "jvp: both tangents are NULL");
+    if (am < 1 || an < 1 || am > h->M || an > h->N)
+        return set_err(h, BPLTV_E_ARG, "jvp: parameter shape %dx%d (image %dx%d)", am, an, h->M, h->N);
+    bpltv_params p = resolve(pp);
+    if (int prc = check_params(h, p)) return prc;
+    const size_t P = (size_t)am * an * (each ? h->O : 1);
+    double amin = 0.0;
+    if (!alpha_dev)
+        if (int crc = check_alpha_host(h, "jvp: alpha", alpha, P, &amin)) return crc;
+    int rc = ensure(h, &h->d_vjp, &h->vjp_cap, 4 + 2 * P);
+    if (rc) return rc;
+    // check words: [0] smallest parameter entry (bits), [1] parameter rejected, [2] df not finite, [3] dalpha not finite
+    unsigned long long* chk_d = reinterpret_cast<unsigned long long*>(h->d_vjp);
+    HIPCHK(h, hipMemsetAsync(chk_d, 0xFF, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(chk_d + 1, 0, 3 * sizeof(unsigned long long), h->stream));
+    if (alpha_dev)
+        hipLaunchKernelGGL(alpha_check_kernel, dim3((unsigned)std::min<size_t>((P + 255) / 256, 1024)), dim3(256), 0, h->stream, alpha, P,
+                           chk_d);
+    if (d_df)
+        hipLaunchKernelGGL(finite_check_kernel, dim3((unsigned)std::min<size_t>((ndir * h->tot + 255) / 256, 1024)), dim3(256), 0, h->stream,
+                           d_df, (size_t)ndir * h->tot, chk_d + 2);
+    if (d_dalpha)
+        hipLaunchKernelGGL(finite_check_kernel, dim3((unsigned)std::min<size_t>((ndir * P + 255) / 256, 1024)), dim3(256), 0, h->stream,
+                           d_dalpha, (size_t)ndir * P, chk_d + 3);
+    HIPCHK(h, hipGetLastError());
+    unsigned long long chk_h[4] = {0, 0, 0, 0};
+    HIPCHK(h, hipMemcpyAsync(chk_h, chk_d, sizeof(chk_h), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (chk_h[1] != 0) return set_err(h, BPLTV_E_ARG, "jvp: alpha (device array): parameters must be finite and >= 0");
+    if (chk_h[2] != 0) return set_err(h, BPLTV_E_ARG, "jvp: the tangent df must be finite");
+    if (chk_h[3] != 0) return set_err(h, BPLTV_E_ARG, "jvp: the tangent dalpha must be finite");
+    if (alpha_dev) std::memcpy(&amin, chk_h, sizeof(double));
+    double* d_a = h->d_vjp + 4;
+    HIPCHK(h, hipMemcpyAsync(d_a, alpha, P * sizeof(double), alpha_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    GradCtx g;
+    g.alpha = d_a; g.am = am; g.an = an; g.alpha_min = amin;
+    g.astride = each ? am * an : 0; g.each = each;
+    g.ndir = ndir; g.df = d_df; g.dalpha = d_dalpha; g.du = d_du;
+    return run_gradient(h, d_u, g, reg ? 1 : 0, p);
 }
 
 // ============================================================================================
@@ -2783,6 +2866,156 @@ int vjp_device(bpltv_t* h, const double* d_u, const double* d_alpha, int am, int
     return BPLTV_OK;
 }
 
+// bpltv_jvp / bpltv_jvp_each over the shards: images split as for the VJP.  The arrays are direction-major over the
+// WHOLE batch, so every shard gets its images of every direction packed (and, each, its parameter blocks), and its du
+// slices are scattered back in place: no reduction.
+int multi_jvp(bpltv_t* h, const double* u, const double* alpha, int am, int an, int reg, const bpltv_params* pp, int ndir,
+              const double* df, const double* dalpha, double* du_out, bool each) {
+    if (!u || !alpha || !du_out || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "jvp: null pointer or empty shape");
+    if (ndir < 1) return set_err(h, BPLTV_E_ARG, "jvp: ndir = %d (at least one direction)", ndir);
+    if (!df && !dalpha) return set_err(h, BPLTV_E_ARG, "jvp: both tangents are NULL");
+    WallTimer wt;
+    MultiState& ms = *h->multi;
+    const size_t npx = h->npx, tot = h->tot, P = (size_t)am * an;
+    int rc = multi_run(h, [&](int k, bpltv_t* c) -> int {
+        const size_t o0 = ms.lo[k] * npx, nk = (size_t)(ms.hi[k] - ms.lo[k]), tk = nk * npx;
+        std::vector<double> dfk(df ? ndir * tk : 0), dak(dalpha && each ? ndir * nk * P : 0), duk(ndir * tk);
+        for (int d = 0; d < ndir; ++d) {
+            if (df) std::memcpy(dfk.data() + d * tk, df + d * tot + o0, tk * sizeof(double));
+            if (dalpha && each) std::memcpy(dak.data() + d * nk * P, dalpha + ((size_t)d * h->O + ms.lo[k]) * P, nk * P * sizeof(double));
+        }
+        const int r = each ? bpltv_jvp_each(c, u + o0, alpha + ms.lo[k] * P, am, an, reg, pp, ndir, df ? dfk.data() : nullptr,
+                                            dalpha ? dak.data() : nullptr, duk.data())
+                           : bpltv_jvp(c, u + o0, alpha, am, an, reg, pp, ndir, df ? dfk.data() : nullptr, dalpha, duk.data());
+        if (r == BPLTV_OK)
+            for (int d = 0; d < ndir; ++d) std::memcpy(du_out + d * tot + o0, duk.data() + d * tk, tk * sizeof(double));
+        return r;
+    });
+    if (rc) return rc;
+    h->st.total_ms = wt.ms();
+    return multi_stats(h);
+}
+
+// bpltv_jvp and bpltv_jvp_each: host arrays staged in d_u2 and d_jvp = [du | df | dalpha]
+int jvp_host(bpltv_t* h, const double* u, const double* alpha, int am, int an, int reg, const bpltv_params* pp, int ndir,
+             const double* df, const double* dalpha, double* du_out, bool each) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi) return multi_jvp(h, u, alpha, am, an, reg, pp, ndir, df, dalpha, du_out, each);
+    if (!u || !alpha || !du_out) return set_err(h, BPLTV_E_ARG, "jvp: null pointer");
+    if (ndir < 1) return set_err(h, BPLTV_E_ARG, "jvp: ndir = %d (at least one direction)", ndir);
+    if (!df && !dalpha) return set_err(h, BPLTV_E_ARG, "jvp: both tangents are NULL");
+    if (am < 1 || an < 1 || am > h->M || an > h->N)
+        return set_err(h, BPLTV_E_ARG, "jvp: parameter shape %dx%d (image %dx%d)", am, an, h->M, h->N);
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->d_u2) {
+        HIPCHK(h, hipMalloc((void**)&h->d_u2, h->tot * sizeof(double)));
+        HIPCHK(h, hipMalloc((void**)&h->d_ubar2, h->tot * sizeof(double)));
+    }
+    const size_t nt = (size_t)ndir * h->tot, na = (size_t)ndir * am * an * (each ? h->O : 1);
+    int rc = ensure(h, &h->d_jvp, &h->jvp_cap, 2 * nt + na);
+    if (rc) return rc;
+    double *d_du = h->d_jvp, *d_df = df ? h->d_jvp + nt : nullptr, *d_da = dalpha ? h->d_jvp + 2 * nt : nullptr;
+    HIPCHK(h, hipMemcpyAsync(h->d_u2, u, h->tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (df) HIPCHK(h, hipMemcpyAsync(d_df, df, nt * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (dalpha) HIPCHK(h, hipMemcpyAsync(d_da, dalpha, na * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    rc = jvp_common(h, h->d_u2, alpha, false, am, an, reg, pp, ndir, d_df, d_da, d_du, each);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(du_out, d_du, nt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
+// bpltv_jvp_device and bpltv_jvp_each_device
+int jvp_device(bpltv_t* h, const double* d_u, const double* d_alpha, int am, int an, int reg, const bpltv_params* pp, int ndir,
+               const double* d_df, const double* d_dalpha, double* d_du, bool each) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi) {
+        const int r = multi_forward0(h, each ? "bpltv_jvp_each_device" : "bpltv_jvp_device", [&](bpltv_t* c) {
+            return jvp_device(c, d_u, d_alpha, am, an, reg, pp, ndir, d_df, d_dalpha, d_du, each);
+        });
+        if (r == BPLTV_OK) multi_stats(h);   // no solve ran: has_result stays
+        return r;
+    }
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int rc = jvp_common(h, d_u, d_alpha, true, am, an, reg, pp, ndir, d_df, d_dalpha, d_du, each);
+    if (rc) return rc;
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
+// bpltv_gauss_newton: gradient and Gauss-Newton Hessian of 0.5||u(alpha) - ubar||^2 from the P = am*an <= GN_MAXP
+// columns du/dalpha_j, solved as the unit directions of one jvp_common call (one factorisation per image group).
+constexpr int GN_MAXP = 16;
+int gauss_newton(bpltv_t* h, const double* u, const double* ubar, const double* alpha, int am, int an, int reg,
+                 const bpltv_params* pp, double* grad_out, double* hess_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (!u || !ubar || !alpha || !grad_out || !hess_out) return set_err(h, BPLTV_E_ARG, "gauss_newton: null pointer");
+    if (am < 1 || an < 1 || am > h->M || an > h->N)
+        return set_err(h, BPLTV_E_ARG, "gauss_newton: parameter shape %dx%d (image %dx%d)", am, an, h->M, h->N);
+    const bool amap = am == h->M && an == h->N && !(h->M == 1 && h->N == 1);
+    if (amap || (long)am * an > GN_MAXP)
+        return set_err(h, BPLTV_E_UNSUPPORTED, "gauss_newton: a scalar or a patch parameter of at most %d entries (got %dx%d%s); use bpltv_jvp for Jacobian columns",
+                       GN_MAXP, am, an, amap ? ", a pixel map" : "");
+    const int P = am * an;
+    const size_t nout = (size_t)P + (size_t)P * P;
+    WallTimer wt;
+    if (h->multi) {   // the shards' [grad, H] added on the host in shard order
+        MultiState& ms = *h->multi;
+        const int n = (int)ms.shard.size();
+        std::vector<double> part((size_t)n * nout);
+        const int rc = multi_run(h, [&](int k, bpltv_t* c) {
+            double* o = part.data() + (size_t)k * nout;
+            return bpltv_gauss_newton(c, u + ms.lo[k] * h->npx, ubar + ms.lo[k] * h->npx, alpha, am, an, reg, pp, o, o + P);
+        });
+        if (rc) return rc;
+        for (size_t e = 0; e < nout; ++e) {
+            double acc = part[e];
+            for (int k = 1; k < n; ++k) acc += part[(size_t)k * nout + e];
+            (e < (size_t)P ? grad_out[e] : hess_out[e - P]) = acc;
+        }
+        h->st.total_ms = wt.ms();
+        return multi_stats(h);
+    }
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->d_u2) {
+        HIPCHK(h, hipMalloc((void**)&h->d_u2, h->tot * sizeof(double)));
+        HIPCHK(h, hipMalloc((void**)&h->d_ubar2, h->tot * sizeof(double)));
+    }
+    // workspace [J: P planes | unit directions P x P | per-image partials P (P + 1) O | grad, H]
+    const size_t nJ = (size_t)P * h->tot, npart = (size_t)P * (P + 1) * h->O;
+    const size_t need = nJ + (size_t)P * P + npart + nout;
+    if (h->jvp_cap < need) {
+        if (h->d_jvp) (void)hipFree(h->d_jvp);
+        h->d_jvp = nullptr; h->jvp_cap = 0;
+        const int arc = alloc_all(h, {{(void**)&h->d_jvp, need * sizeof(double)}}, "gauss_newton: workspace of the Jacobian columns");
+        if (arc) return arc;
+        h->jvp_cap = need;
+    }
+    double *d_J = h->d_jvp, *d_e = d_J + nJ, *d_part = d_e + (size_t)P * P, *d_out = d_part + npart;
+    std::vector<double> eye((size_t)P * P, 0.0);
+    for (int j = 0; j < P; ++j) eye[(size_t)j * P + j] = 1.0;
+    HIPCHK(h, hipMemcpyAsync(h->d_u2, u, h->tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_ubar2, ubar, h->tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_e, eye.data(), eye.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // (eye is a local)
+    int rc = jvp_common(h, h->d_u2, alpha, false, am, an, reg, pp, P, nullptr, d_e, d_J, false);
+    if (rc) return rc;
+    hipLaunchKernelGGL(gn_gram_kernel, dim3(P + 1, P, h->O), dim3(256), 0, h->stream, d_J, h->d_u2, h->d_ubar2, (int)h->npx, h->O, P,
+                       d_part);
+    hipLaunchKernelGGL(gn_final_kernel, dim3((P * (P + 1) + 63) / 64), dim3(64), 0, h->stream, d_part, h->O, P, d_out);
+    HIPCHK(h, hipGetLastError());
+    std::vector<double> out(nout);
+    HIPCHK(h, hipMemcpyAsync(out.data(), d_out, nout * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::memcpy(grad_out, out.data(), P * sizeof(double));
+    std::memcpy(hess_out, out.data() + P, (size_t)P * P * sizeof(double));
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
 }  // namespace
 
 // ============================================================================================
@@ -2903,7 +3136,7 @@ int bpltv_destroy(bpltv_t* h) {
     if (h->f32_sweep_alpha) (void)hipFree(h->f32_sweep_alpha);
     void* ptrs[] = {h->d_ubar, h->d_f, h->d_alpha, h->d_sweep_alpha, h->d_partial, h->d_red, h->d_perimg, h->d_scalar, h->d_coef,
                     h->d_band4, h->d_bcr, h->d_L, h->d_invF, h->d_invB, h->d_L1, h->d_dump, h->d_Lm, h->d_spill, h->d_p, h->d_r, h->d_gpix, h->d_resn, h->d_fail, h->d_u2, h->d_ubar2,
-                    h->d_gf2, h->d_vjp};
+                    h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (int s = 0; s < 2; ++s)
@@ -3196,6 +3429,27 @@ int bpltv_vjp_each_device(bpltv_t* h, const double* d_u, const double* d_alphas,
                           const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alphas) {
     return vjp_device(h, d_u, d_alphas, am, an, reg, pp, d_gu, d_grad_f, d_grad_alphas, 1, true);
 }
+int bpltv_jvp(bpltv_t* h, const double* u, const double* alpha, int am, int an, int reg, const bpltv_params* pp, int ndir,
+              const double* df, const double* dalpha, double* du_out) {
+    return jvp_host(h, u, alpha, am, an, reg, pp, ndir, df, dalpha, du_out, false);
+}
+int bpltv_jvp_device(bpltv_t* h, const double* d_u, const double* d_alpha, int am, int an, int reg, const bpltv_params* pp,
+                     int ndir, const double* d_df, const double* d_dalpha, double* d_du) {
+    return jvp_device(h, d_u, d_alpha, am, an, reg, pp, ndir, d_df, d_dalpha, d_du, false);
+}
+int bpltv_jvp_each(bpltv_t* h, const double* u, const double* alphas, int am, int an, int reg, const bpltv_params* pp, int ndir,
+                   const double* df, const double* dalphas, double* du_out) {
+    return jvp_host(h, u, alphas, am, an, reg, pp, ndir, df, dalphas, du_out, true);
+}
+int bpltv_jvp_each_device(bpltv_t* h, const double* d_u, const double* d_alphas, int am, int an, int reg,
+                          const bpltv_params* pp, int ndir, const double* d_df, const double* d_dalphas, double* d_du) {
+    return jvp_device(h, d_u, d_alphas, am, an, reg, pp, ndir, d_df, d_dalphas, d_du, true);
+}
+int bpltv_gauss_newton(bpltv_t* h, const double* u, const double* ubar, const double* alpha, int am, int an, int reg,
+                       const bpltv_params* pp, double* grad_out, double* hess_out) {
+    return gauss_newton(h, u, ubar, alpha, am, an, reg, pp, grad_out, hess_out);
+}
+
 int bpltv_sumregs_vjp(bpltv_t* h, const double* u, const double* alpha, int am, int an, int reg, const bpltv_params* pp,
                       const double* gu, double* grad_f_out, double* grad_alpha_out) {
     return vjp_host(h, u, alpha, am, an, reg, pp, gu, grad_f_out, grad_alpha_out, 3);

@@ -296,6 +296,99 @@ class TVSolver:
                                                int(bool(reg)), C.byref(p), C.c_void_p(gu_ptr),
                                                C.c_void_p(grad_f_ptr or None), C.c_void_p(grad_alpha_ptr or None)))
 
+    # -- forward mode (bpltv_jvp / bpltv_gauss_newton) -------------------------------------------------------
+    def _tangents(self, what, df, dalpha, ashape):
+        """(df, dalpha, K, batched): the tangents as contiguous (K, ...) stacks, either None; batched = a leading K was
+        given.  df: (O, N, M) or (K, O, N, M); dalpha: shaped like the parameter (ashape) or with a leading K."""
+        if df is None and dalpha is None:
+            raise ValueError("%s: df and dalpha are both None" % what)
+        K, batched = None, False
+        if df is not None:
+            df = np.ascontiguousarray(df, dtype=np.float64)
+            if df.ndim == 2:
+                df = df[None]
+            if df.ndim == 3:
+                df = df[None]
+            else:
+                batched = True
+            if df.ndim != 4 or df.shape[1:] != (self.O, self.N, self.M):
+                raise ValueError("%s: df has shape %s, expected (O=%d, N=%d, M=%d) or (K, O, N, M)"
+                                 % (what, df.shape, self.O, self.N, self.M))
+            K = df.shape[0]
+        if dalpha is not None:
+            dalpha = np.asarray(dalpha, dtype=np.float64)
+            if dalpha.shape == tuple(ashape):
+                dalpha = dalpha[None]
+            elif dalpha.ndim >= 1 and dalpha.shape[1:] == tuple(ashape):
+                batched = True
+            else:
+                raise ValueError("%s: dalpha has shape %s, expected %s or (K,) + %s"
+                                 % (what, dalpha.shape, tuple(ashape), tuple(ashape)))
+            dalpha = np.ascontiguousarray(dalpha)
+            if K is None:
+                K = dalpha.shape[0]
+        if K < 1 or (df is not None and df.shape[0] != K) or (dalpha is not None and dalpha.shape[0] != K):
+            raise ValueError("%s: df and dalpha hold different numbers of directions" % what)
+        return df, dalpha, K, batched
+
+    def jvp(self, u, x, df=None, dalpha=None, reg=False, **kw):
+        """Jacobian-vector product of u = denoise(f, x) (bpltv_jvp): du for the tangents (df, dalpha), the linear map
+        whose transpose vjp computes.  df: (O, N, M), or (K, O, N, M) for K directions solved against one
+        factorisation; dalpha: shaped like x, or with a leading K; either may be None (zero), not both.  Returns du
+        of shape (O, N, M), or (K, O, N, M) when a leading K was given."""
+        a, am, an, scalar = _alpha_arg(x)
+        df, dalpha, K, batched = self._tangents("jvp", df, dalpha, () if scalar else (an, am))
+        p = self.params(**kw)
+        u = self._batch(u, "u")
+        du = np.empty((K, self.O, self.N, self.M))
+        self._check(self._lib.bpltv_jvp(self._h, _ptr(u), _ptr(a), am, an, int(bool(reg)), C.byref(p), K,
+                                        _ptr(df) if df is not None else None,
+                                        _ptr(dalpha) if dalpha is not None else None, _ptr(du)))
+        return du if batched else du[0]
+
+    def jvp_device(self, u_ptr, alpha_ptr, am, an, df_ptr, dalpha_ptr, du_ptr, ndir=1, reg=False, **kw):
+        """bpltv_jvp_device: u (M*N*O doubles), the parameter (am*an), df and du (ndir*M*N*O) and dalpha (ndir*am*an)
+        all resident in HBM (raw device pointers); either tangent pointer may be 0 / None, not both."""
+        p = self.params(**kw)
+        self._check(self._lib.bpltv_jvp_device(self._h, C.c_void_p(u_ptr), C.c_void_p(alpha_ptr), int(am), int(an),
+                                               int(bool(reg)), C.byref(p), int(ndir), C.c_void_p(df_ptr or None),
+                                               C.c_void_p(dalpha_ptr or None), C.c_void_p(du_ptr)))
+
+    def jvp_each(self, u, alphas, df=None, dalphas=None, reg=False, **kw):
+        """jvp with image k's own parameter alphas[k] (bpltv_jvp_each).  dalphas: shaped like alphas, or with a leading
+        K; df and the result as in jvp."""
+        a, am, an = self._each_arg(alphas)
+        df, dalphas, K, batched = self._tangents("jvp_each", df, dalphas, a.shape)
+        p = self.params(**kw)
+        u = self._batch(u, "u")
+        du = np.empty((K, self.O, self.N, self.M))
+        self._check(self._lib.bpltv_jvp_each(self._h, _ptr(u), _ptr(a), am, an, int(bool(reg)), C.byref(p), K,
+                                             _ptr(df) if df is not None else None,
+                                             _ptr(dalphas) if dalphas is not None else None, _ptr(du)))
+        return du if batched else du[0]
+
+    def jvp_each_device(self, u_ptr, alphas_ptr, am, an, df_ptr, dalphas_ptr, du_ptr, ndir=1, reg=False, **kw):
+        """bpltv_jvp_each_device: as jvp_device with O parameter blocks (O*am*an doubles) and ndir*O tangent blocks."""
+        p = self.params(**kw)
+        self._check(self._lib.bpltv_jvp_each_device(self._h, C.c_void_p(u_ptr), C.c_void_p(alphas_ptr), int(am),
+                                                    int(an), int(bool(reg)), C.byref(p), int(ndir),
+                                                    C.c_void_p(df_ptr or None), C.c_void_p(dalphas_ptr or None),
+                                                    C.c_void_p(du_ptr)))
+
+    def gauss_newton(self, u, ubar, x, reg=False, **kw):
+        """Gauss-Newton model of 0.5||u(x) - ubar||^2 (bpltv_gauss_newton): (grad, H) with grad = J^T (u - ubar) shaped
+        like x and H = J^T J of shape (P, P), P = x.size, ordered as x's column-major (Julia) entries -- numpy's
+        x.ravel().  A float or an (n, m) patch parameter with at most 16 entries."""
+        a, am, an, scalar = _alpha_arg(x)
+        p = self.params(**kw)
+        u = self._batch(u, "u")
+        ubar = self._batch(ubar, "ubar")
+        P = am * an
+        grad, H = np.empty(P), np.empty((P, P))
+        self._check(self._lib.bpltv_gauss_newton(self._h, _ptr(u), _ptr(ubar), _ptr(a), am, an, int(bool(reg)),
+                                                 C.byref(p), _ptr(grad), _ptr(H)))
+        return (float(grad[0]) if scalar else grad.reshape(an, am)), H
+
     # -- one parameter per image (bpltv_denoise_each / bpltv_vjp_each) ---------------------------------------
     def _each_arg(self, alphas):
         """alphas: (O,) scalars or (O, n, m) blocks (numpy (n, m) == Julia m x n), one per image."""

@@ -28,6 +28,13 @@ pH, pW).  The backward pass is bpltv_sumregs_vjp_device's; reg selects sumregs_g
 f is then (B, H, W) and alpha float64 of shape (B, 3), (B, 3, pH, pW) or (B, 3, H, W); alpha.grad[k] is image k's term
 alone.  A separate function again: sumregs_denoise rejects a leading batch dimension on alpha.
 
+Forward mode: tv_denoise and tv_denoise_each also carry a jvp, so torch.autograd.forward_ad (dual_level, make_dual,
+unpack_dual) works through them: the tangent of u is one bpltv_jvp_device / bpltv_jvp_each_device call with one
+direction on the u of the forward pass -- the linear map whose transpose backward computes, so forward and reverse
+mode agree for both values of reg.  A tangent must be float64 on f's device; an input
+without a tangent counts as zero.  The sum-of-regularisers functions have no forward mode (their reg = 1 patch system
+is row-scaled and would need a transposed solve): forward-mode AD over them raises torch's "not implemented" error.
+
 Streams: the library runs its kernels on its own HIP streams and blocks until they are done.  Every call below first
 synchronises the tensors' current torch stream, so that the library reads inputs torch has finished writing; its
 outputs are complete when the call returns.
@@ -132,6 +139,19 @@ def _sync(device):
     torch.cuda.current_stream(device).synchronize()
 
 
+def _tangent(t, primal, name):
+    """A forward-mode tangent as the contiguous float64 tensor the library reads, or None (no tangent: zero); TypeError
+    / ValueError before any library call."""
+    if t is None:
+        return None
+    if t.dtype != torch.float64:
+        raise TypeError("forward mode: the tangent of %s must be float64, got %s" % (name, t.dtype))
+    if t.numel() != primal.numel() or t.device != primal.device:
+        raise ValueError("forward mode: the tangent of %s has shape %s on %s, its primal %s on %s"
+                         % (name, tuple(t.shape), t.device, tuple(primal.shape), primal.device))
+    return t.detach().contiguous()
+
+
 class TVDenoiseFunction(torch.autograd.Function):
     """autograd.Function of tv_denoise (below); apply(f, alpha, reg, solver_kw)."""
 
@@ -148,14 +168,29 @@ class TVDenoiseFunction(torch.autograd.Function):
         s.denoise_device(ac.data_ptr(), am, an, **solver_kw)
         s.copy_u_device(u.data_ptr())
         ctx.save_for_backward(u, ac)
+        ctx.save_for_forward(u, ac)
+        ctx.set_materialize_grads(False)   # an input without a tangent reaches jvp as None, and the library as NULL
         ctx.solver, ctx.am, ctx.an, ctx.reg, ctx.solver_kw = s, am, an, bool(reg), dict(solver_kw)
         return u
+
+    @staticmethod
+    def jvp(ctx, df, dalpha, _reg, _solver_kw):
+        u, alpha = ctx.saved_tensors
+        df, dalpha = _tangent(df, u, "f"), _tangent(dalpha, alpha, "alpha")
+        if df is None and dalpha is None:
+            return torch.zeros_like(u)
+        du = torch.empty_like(u)
+        _sync(u.device)
+        ctx.solver.jvp_device(u.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, df.data_ptr() if df is not None else None,
+                              dalpha.data_ptr() if dalpha is not None else None, du.data_ptr(), ndir=1, reg=ctx.reg,
+                              **ctx.solver_kw)
+        return du
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gu):
         need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (need_f or need_a):
+        if gu is None or not (need_f or need_a):
             return None, None, None, None
         u, alpha = ctx.saved_tensors
         gu = gu.to(dtype=torch.float64).contiguous()
@@ -191,14 +226,30 @@ class TVDenoiseEachFunction(torch.autograd.Function):
         s.denoise_each_device(ac.data_ptr(), am, an, **solver_kw)
         s.copy_u_device(u.data_ptr())
         ctx.save_for_backward(u, ac)
+        ctx.save_for_forward(u, ac)
+        ctx.set_materialize_grads(False)   # an input without a tangent reaches jvp as None, and the library as NULL
         ctx.solver, ctx.am, ctx.an, ctx.reg, ctx.solver_kw = s, am, an, bool(reg), dict(solver_kw)
         return u
+
+    @staticmethod
+    def jvp(ctx, df, dalpha, _reg, _solver_kw):
+        u, alpha = ctx.saved_tensors
+        df, dalpha = _tangent(df, u, "f"), _tangent(dalpha, alpha, "alpha")
+        if df is None and dalpha is None:
+            return torch.zeros_like(u)
+        du = torch.empty_like(u)
+        _sync(u.device)
+        ctx.solver.jvp_each_device(u.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an,
+                                   df.data_ptr() if df is not None else None,
+                                   dalpha.data_ptr() if dalpha is not None else None, du.data_ptr(), ndir=1,
+                                   reg=ctx.reg, **ctx.solver_kw)
+        return du
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gu):
         need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (need_f or need_a):
+        if gu is None or not (need_f or need_a):
             return None, None, None, None
         u, alpha = ctx.saved_tensors
         gu = gu.to(dtype=torch.float64).contiguous()

@@ -316,6 +316,47 @@ int bpltv_vjp_each(bpltv_t *h, const double *u, const double *alphas, int am, in
 int bpltv_vjp_each_device(bpltv_t *h, const double *d_u, const double *d_alphas, int am, int an, int reg,
                           const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alphas);
 
+/* Jacobian-vector product of u = denoise(f, alpha) (TV model): du for tangents (df, dalpha), defined as the linear map
+ * whose transpose bpltv_vjp computes, in every branch -- <gu, du> = <grad_f(gu), df> + <grad_alpha(gu), dalpha> for any
+ * gu -- so forward and reverse mode agree, also where the reference's linearisation is not the true one (reg = 1 with an
+ * array parameter).  With G the forward-difference gradient, h the per-pixel plane of the gradient's last step and up()
+ * the patch upsampling, one direction solves the system bpltv_vjp factors with
+ *     reg = 0, and reg = 1 with a scalar:    r = df - G^T (h o up(dalpha)),    A q = r,      du = q
+ *     reg = 1 with a patch or map:           r = df - (G^T h) o up(dalpha),    A_s q = S r,  du = S^-1 q,  S = diag(sqrt(alpha)).
+ * For reg = 0 this is the derivative of the solution map itself (active set held fixed).
+ * ndir >= 1 directions, direction-major, are solved against ONE factorisation per image group: df is NULL or
+ * ndir * M*N*O doubles, dalpha NULL or ndir * am*an doubles, not both NULL (a NULL tangent is zero); du_out: ndir * M*N*O
+ * doubles, direction d of a call being bitwise the ndir = 1 call with that direction.  The contract is bpltv_vjp's:
+ * alpha is checked as bpltv_denoise checks it (finite, >= 0; > 0 for reg = 1 with an array parameter) and the tangents
+ * must be finite; ndir < 1 or both tangents NULL is BPLTV_E_ARG; every rejection comes before anything of the handle
+ * changes.  The parameter is staged apart: the last solve, bpltv_u_device, bpltv_duality_gap and the captured graphs stay
+ * as they were.  The residual gate and the kappa retry apply; stats report the adjoint, adjoint_residual being the worst
+ * over the directions.  dtype = 32 handles too; no dataset is needed; image groups ("adjoint_budget_mb") give bitwise the
+ * same result.  Multi-device handles split the images as bpltv_vjp does and write the du slices in place. */
+int bpltv_jvp(bpltv_t *h, const double *u, const double *alpha, int am, int an, int reg, const bpltv_params *p,
+              int ndir, const double *df, const double *dalpha, double *du_out);
+/* The same with every array in HBM (device pointers); parameter and tangents are checked on the device.  Single-device
+ * handles (multi: BPLTV_E_UNSUPPORTED beyond one shard). */
+int bpltv_jvp_device(bpltv_t *h, const double *d_u, const double *d_alpha, int am, int an, int reg,
+                     const bpltv_params *p, int ndir, const double *d_df, const double *d_dalpha, double *d_du);
+/* One parameter per image (the forward mode of bpltv_vjp_each): alphas holds O blocks of am x an doubles, dalphas
+ * ndir x O blocks (direction, then image).  Image k reads its own blocks; its du is bitwise what a one-image handle
+ * returns for block k. */
+int bpltv_jvp_each(bpltv_t *h, const double *u, const double *alphas, int am, int an, int reg, const bpltv_params *p,
+                   int ndir, const double *df, const double *dalphas, double *du_out);
+int bpltv_jvp_each_device(bpltv_t *h, const double *d_u, const double *d_alphas, int am, int an, int reg,
+                          const bpltv_params *p, int ndir, const double *d_df, const double *d_dalphas, double *d_du);
+
+/* Gauss-Newton model of the loss 0.5||u(alpha) - ubar||^2 for one shared parameter (TV model): with J the M*N*O x P
+ * matrix of the columns du/dalpha_j (P = am*an; the unit directions of bpltv_jvp against one factorisation),
+ *     hess_out = J^T J   (P x P doubles, column major, symmetric bit for bit),     grad_out = J^T (u - ubar)   (P doubles),
+ * grad_out being bpltv_gradient's result up to rounding (the transpose identity).  A scalar or a patch parameter with
+ * P <= 16; a larger patch or a pixel map: BPLTV_E_UNSUPPORTED.  The columns live in a workspace of P * M*N*O doubles
+ * (BPLTV_E_NOMEM if it does not fit).  Sums run per image, then over the images in image order (reproducible);
+ * multi-device handles add the shards' [grad, H] on the host in shard order.  Checks, staging and stats as bpltv_jvp. */
+int bpltv_gauss_newton(bpltv_t *h, const double *u, const double *ubar, const double *alpha, int am, int an, int reg,
+                       const bpltv_params *p, double *grad_out, double *hess_out);
+
 /* Vector-Jacobian product of u = sumregs_denoise(f, x) for a cotangent gu = dL/du: the adjoint system of
  * bpltv_sumregs_evaluate's gradient with the right-hand side
  *     reg = 0 (sumregs_gradient):      gu        grad_f_out =  p

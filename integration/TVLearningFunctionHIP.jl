@@ -4,7 +4,7 @@
 # NOT EXECUTED HERE: Julia is not available in the build image; the same entry points are exercised through
 # bpldenoising_amd/_lib.py (ctypes) by the test suite.
 # Same exports as src/TVLearningFunctionVec.jl:6
-export tv_op_learning_function, denoise, sumregs_learning_function, tv_vjp, sumregs_vjp
+export tv_op_learning_function, denoise, sumregs_learning_function, tv_vjp, sumregs_vjp, tv_jvp, tv_gauss_newton
 
 const libbpltv = "libbpltv"            # on LD_LIBRARY_PATH, or an absolute path
 
@@ -198,6 +198,38 @@ function tv_vjp(h::BpltvHandle, u::Array{Float64,3}, α, ḡ::Array{Float64,3}; 
         (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Ref{BpltvParams}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
         h.ptr, u, a, am, an, reg ? 1 : 0, p, ḡ, gf, ga))
     return gf, α isa Real ? ga[1] : reshape(ga, size(α))
+end
+
+# Jacobian-vector product of u = denoise(f, α) (include/bpltv.h, bpltv_jvp): du for the tangents (df, dα), the linear map
+# whose transpose tv_vjp computes, so dot(ḡ, du) == dot(gf, df) + dot(gα, dα).  df: nothing or an M x N x O array, or
+# M x N x O x K for K directions solved against one factorisation; dα: nothing, or shaped like α (a number for a scalar α),
+# or with a trailing dimension K (a K-vector for a scalar α).  Returns du shaped like df (like u for one direction).
+function tv_jvp(h::BpltvHandle, u::Array{Float64,3}, α; df = nothing, dα = nothing, reg = false, kwargs...)
+    a, am, an = alpha_arg(α)
+    df === nothing && dα === nothing && error("tv_jvp: df and dα are both nothing")
+    K = df !== nothing ? size(df, 4) : (dα isa Real ? 1 : div(length(dα), am * an))
+    tf = df === nothing ? C_NULL : Array{Float64}(df)
+    ta = dα === nothing ? C_NULL : (dα isa Real ? Float64[dα] : Array{Float64}(dα))
+    du = zeros(size(u)..., K)
+    p = Ref(default_params(; kwargs...))
+    GC.@preserve u a tf ta du bpltv_check(h, ccall((:bpltv_jvp, libbpltv), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Ref{BpltvParams}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        h.ptr, u, a, am, an, reg ? 1 : 0, p, K, tf, ta, du))
+    return K == 1 && (df === nothing || ndims(df) == 3) ? du[:, :, :, 1] : du
+end
+
+# Gauss-Newton model of 0.5||u(α) - ū||^2 (include/bpltv.h, bpltv_gauss_newton): (g, H) with g = J'(u - ū) shaped like α
+# and H = J'J (P x P, P = length(α) <= 16, in α's column-major order) from the P columns du/dα_j, solved against one
+# factorisation -- a second-order model for the trust region of src/TRBox.jl, whose own model Hessian is B = 0.1 or L-BFGS.
+function tv_gauss_newton(h::BpltvHandle, u::Array{Float64,3}, ū::Array{Float64,3}, α; reg = false, kwargs...)
+    a, am, an = alpha_arg(α)
+    P = am * an
+    g = zeros(am, an); H = zeros(P, P)
+    p = Ref(default_params(; kwargs...))
+    GC.@preserve u ū a g H bpltv_check(h, ccall((:bpltv_gauss_newton, libbpltv), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Ref{BpltvParams}, Ptr{Cdouble}, Ptr{Cdouble}),
+        h.ptr, u, ū, a, am, an, reg ? 1 : 0, p, g, H))
+    return (α isa Real ? g[1] : reshape(g, size(α))), H
 end
 
 # The same for u = sumregs_denoise(f, x) (include/bpltv.h, bpltv_sumregs_vjp): x a 3-vector or an m x n x 3 array, passed
