@@ -102,6 +102,13 @@ SYMBOLS = {
     "bpltv_jvp_each_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_int, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
     "bpltv_gauss_newton": (C.c_int, [_H, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp]),
+    "bpltv_sumregs_jvp": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, C.c_int, _dp, _dp, _dp]),
+    "bpltv_sumregs_jvp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_int, C.c_void_p,
+                                           C.c_void_p, C.c_void_p]),
+    "bpltv_sumregs_jvp_each": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, C.c_int, _dp, _dp, _dp]),
+    "bpltv_sumregs_jvp_each_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_int,
+                                                C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpltv_sumregs_gauss_newton": (C.c_int, [_H, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp]),
     "bpltv_sumregs_vjp": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
     "bpltv_sumregs_vjp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_void_p,
                                            C.c_void_p, C.c_void_p]),

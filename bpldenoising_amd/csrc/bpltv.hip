@@ -1385,7 +1385,8 @@ struct GradCtx {
     double* d_grad_f = nullptr;    // M*N*O input gradient (+-S q), or nullptr
     // forward mode (bpltv_jvp): ndir > 0 tangent directions solved against ONE factorisation per image group; src, cot,
     // d_out and d_grad_f are then unused.  df: ndir * M*N*O doubles or nullptr; dalpha: ndir blocks of am*an doubles
-    // (each: of O * am*an, direction then image) or nullptr; du: ndir * M*N*O doubles -- all in HBM, direction-major.
+    // (each: of O * am*an, direction then image; sum of regularisers: 3*am*an) or nullptr; du: ndir * M*N*O doubles --
+    // all in HBM, direction-major.
     int ndir = 0;
     const double* df = nullptr;
     const double* dalpha = nullptr;
@@ -1678,13 +1679,15 @@ int vjp_common(bpltv_t* h, const double* d_u, const double* alpha, bool alpha_de
     return sr ? run_sr_gradient(h, d_u, g, reg ? 1 : 0, p) : run_gradient(h, d_u, g, reg ? 1 : 0, p);
 }
 
-// Jacobian-vector product of u = denoise(f, alpha) on a single-device handle (TV model): the linear map whose transpose
-// vjp_common computes, for ndir directions against one factorisation per image group (run_gradient_once).  d_u, the
-// tangents d_df / d_dalpha (either may be nullptr: a zero tangent) and d_du live in HBM, direction-major; `alpha` on the
-// host or (alpha_dev) in HBM.  Checks and staging as in vjp_common: nothing of the handle changes on a rejection, and
-// the last solve stays as it was.
+// Jacobian-vector product of u = denoise(f, alpha) on a single-device handle: the linear map whose transpose
+// vjp_common computes, for ndir directions against one factorisation per image group (run_gradient_once /
+// run_sr_gradient_once).  d_u, the tangents d_df / d_dalpha (either may be nullptr: a zero tangent) and d_du live in HBM,
+// direction-major; `alpha` on the host or (alpha_dev) in HBM.  slices: 1 TV (bpltv_jvp), 3 sum of regularisers
+// (bpltv_sumregs_jvp; parameter and tangent blocks are 3*am*an doubles).  Checks and staging as in vjp_common: nothing of
+// the handle changes on a rejection, and the last solve stays as it was.
 int jvp_common(bpltv_t* h, const double* d_u, const double* alpha, bool alpha_dev, int am, int an, int reg,
-               const bpltv_params* pp, int ndir, const double* d_df, const double* d_dalpha, double* d_du, bool each) {
+               const bpltv_params* pp, int ndir, const double* d_df, const double* d_dalpha, double* d_du, bool each,
+               int slices = 1) {
     if (!d_u || !alpha || !d_du) return set_err(h, BPLTV_E_ARG, "jvp: null pointer");
     if (ndir < 1) return set_err(h, BPLTV_E_ARG, "jvp: ndir = %d (at least one direction)", ndir);
     if (!d_df && !d_dalpha) return set_err(h, BPLTV_E_ARG, "jvp: both tangents are NULL");
@@ -1692,7 +1695,9 @@ int jvp_common(bpltv_t* h, const double* d_u, const double* alpha, bool alpha_de
         return set_err(h, BPLTV_E_ARG, "jvp: parameter shape %dx%d (image %dx%d)", am, an, h->M, h->N);
     bpltv_params p = resolve(pp);
     if (int prc = check_params(h, p)) return prc;
-    const size_t P = (size_t)am * an * (each ? h->O : 1);
+    const bool sr = slices == 3;
+    if (sr && p.reserved[4] == 2) return set_err(h, BPLTV_E_UNSUPPORTED, "block cyclic reduction applies to the TV model only");
+    const size_t P = (size_t)slices * am * an * (each ? h->O : 1);
     double amin = 0.0;
     if (!alpha_dev)
         if (int crc = check_alpha_host(h, "jvp: alpha", alpha, P, &amin)) return crc;
@@ -1719,13 +1724,15 @@ int jvp_common(bpltv_t* h, const double* d_u, const double* alpha, bool alpha_de
     if (chk_h[2] != 0) return set_err(h, BPLTV_E_ARG, "jvp: the tangent df must be finite");
     if (chk_h[3] != 0) return set_err(h, BPLTV_E_ARG, "jvp: the tangent dalpha must be finite");
     if (alpha_dev) std::memcpy(&amin, chk_h, sizeof(double));
+    if (sr && reg && !(am == 1 && an == 1) && !(amin > 0.0))   // run_sr_gradient_once's condition, before anything changes
+        return set_err(h, BPLTV_E_ARG, "sumregs_gradient_reg with a patch parameter needs every entry > 0 (min = %g)", amin);
     double* d_a = h->d_vjp + 4;
     HIPCHK(h, hipMemcpyAsync(d_a, alpha, P * sizeof(double), alpha_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
     GradCtx g;
     g.alpha = d_a; g.am = am; g.an = an; g.alpha_min = amin;
-    g.astride = each ? am * an : 0; g.each = each;
+    g.astride = each ? slices * am * an : 0; g.each = each;
     g.ndir = ndir; g.df = d_df; g.dalpha = d_dalpha; g.du = d_du;
-    return run_gradient(h, d_u, g, reg ? 1 : 0, p);
+    return sr ? run_sr_gradient(h, d_u, g, reg ? 1 : 0, p) : run_gradient(h, d_u, g, reg ? 1 : 0, p);
 }
 
 // ============================================================================================
@@ -2013,6 +2020,10 @@ int sr_band_alloc(bpltv_t* h) {
 // params.reserved[4] = 1).
 // Parameter (three slices of g.am*g.an; g.astride != 0: one such block per image, image k reads block k), right-hand side
 // and outputs come from `g`, as for run_gradient_once.
+// Forward mode (g.ndir > 0, bpltv_sumregs_jvp): the directions solve A^T du = df - sum_k w_k o up(dx_k) against one
+// factorisation per image group.  The LU paths factor the transpose by swapping the lower and the upper diagonal planes
+// (the main diagonal copied across), also where sr_force_lu puts a symmetric system on them; the refinement takes the
+// residual of A^T (sr_adj_flux_colscale_kernel).  The planes w_k live in d_srgpix, which only the reverse mode needs.
 int run_sr_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, const bpltv_params& p, double kappa_scale) {
     int rc = sr_adj_alloc(h);
     if (rc) return rc;
@@ -2057,6 +2068,16 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int re
     if (kact > kcap) kact = kcap;
     kact *= kappa_scale;
     const int nref = p.refine < 0 ? (reg ? 1 : 2) : p.refine;
+    // forward mode: every direction keeps its own residual statistics (the gate takes the worst)
+    const bool tangent = g.ndir > 0;
+    const int ndir = tangent ? g.ndir : 1;
+    double* resn_fin = h->d_resn;
+    if (ndir > 1) {
+        rc = ensure(h, &h->d_jres, &h->jres_cap, 4 * (size_t)O * ndir);
+        if (rc) return rc;
+        resn_fin = h->d_jres;
+    }
+    const size_t dastride = 3 * P * (g.each ? O : 1);   // doubles between two directions of g.dalpha
     HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_fail, 0, sizeof(int) * O, h->stream));
     int chunks = 0;
@@ -2073,7 +2094,10 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int re
         const int gpx = (int)((ctot + 255) / 256);
         const double* ga = g.alpha + (size_t)c0 * g.astride;   // the group's first image's parameter block
         const double* rowscale = rowsc ? ga : nullptr;
-        if (g.cot)
+        if (tangent)   // the coefficient planes alone: sr_tangent_rhs_kernel writes each direction's right-hand side below
+            hipLaunchKernelGGL(sr_adj_setup_cot_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, d_u + o0, ga, am, an, g.astride,
+                               M, N, nimg, patch, reg, kact, C);
+        else if (g.cot)
             hipLaunchKernelGGL(sr_adj_setup_cot_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0, ga, am, an, g.astride,
                                M, N, nimg, patch, reg, kact, C);
         else
@@ -2084,13 +2108,21 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int re
         BandDiags D;
         D.planes = diag; D.tot = tot; D.nd = 7;
         D.off[0] = 0; D.off[1] = 1; D.off[2] = 2; D.off[3] = M - 1; D.off[4] = M; D.off[5] = M + 1; D.off[6] = 2 * M;
+        // forward mode on the LU paths: A^T.  Its lower diagonals are A's upper ones and the other way round; the main
+        // diagonal is read from the first argument alone, and the assembly left plane 0 of diagU at zero.
+        const double *facL = diag, *facU = diagU;
+        if (tangent && lu) {
+            HIPCHK(h, hipMemcpyAsync(diagU, diag, ctot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+            facL = diagU; facU = diag;
+        }
         if (lu && !band) {
-            rc = h->nd_sr_lu.factor_lu(diag, diagU, tot, nimg, dfail);
+            rc = h->nd_sr_lu.factor_lu(facL, facU, tot, nimg, dfail);
             if (rc) return set_err(h, rc, "sum-of-regularisers adjoint (nested dissection, LU): %s", h->nd_sr_lu.err.c_str());
         } else if (lu) {
-            BandDiags DU = D;
-            DU.planes = diagU;
-            rc = h->lu_sr.factor(D, DU, dfail);
+            BandDiags DL = D, DU = D;
+            DL.planes = const_cast<double*>(facL);
+            DU.planes = const_cast<double*>(facU);
+            rc = h->lu_sr.factor(DL, DU, dfail);
             if (rc) return set_err(h, rc, "sum-of-regularisers adjoint (banded LU): %s", h->lu_sr.err.c_str());
         } else if (band) {
             rc = h->hb_sr.factor(D, dfail);
@@ -2100,6 +2132,11 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int re
             if (rc) return set_err(h, rc, "sum-of-regularisers adjoint (nested dissection): %s", h->nd_sr.err.c_str());
         }
         auto residual = [&](double* out) {
+            if (tangent && rowsc) {   // of A^T: the parameter scales columns, before G_k
+                hipLaunchKernelGGL(sr_adj_flux_colscale_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, w, rowscale, am, an, g.astride);
+                hipLaunchKernelGGL(sr_adj_residual_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, w, M, N, nimg, out, (const double*)nullptr, am, an, g.astride);
+                return;
+            }
             hipLaunchKernelGGL(sr_adj_flux_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, w);
             hipLaunchKernelGGL(sr_adj_residual_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, w, M, N, nimg, out, rowscale, am, an, g.astride);
         };
@@ -2111,18 +2148,29 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int re
             else if ((r2 = h->nd_sr.solve(v, acc, nimg))) return set_err(h, r2, "sum-of-regularisers adjoint (nested dissection, substitution): %s", h->nd_sr.err.c_str());
             return BPLTV_OK;
         };
-        HIPCHK(h, hipMemcpyAsync(dp, C.rhs, ctot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        rc = solve(dp, nullptr);
-        if (rc) return rc;
-        for (int it = 0; it < nref; ++it) {
-            residual(dr);
-            rc = solve(dr, dp);
+        if (tangent) hipLaunchKernelGGL(sr_adj_wplane_kernel, dim3(gpx), dim3(256), 0, h->stream, C, M, N, nimg, gp);
+        for (int d = 0; d < ndir; ++d) {   // one pass, or the tangent directions against this group's factorisation
+            if (tangent)
+                hipLaunchKernelGGL(sr_tangent_rhs_kernel, dim3(gpx), dim3(256), 0, h->stream, C, (const double*)gp,
+                                   g.df ? g.df + (size_t)d * tot + o0 : nullptr,
+                                   g.dalpha ? g.dalpha + (size_t)d * dastride + (size_t)c0 * g.astride : nullptr, am, an, g.astride, M, N,
+                                   nimg);
+            HIPCHK(h, hipMemcpyAsync(dp, C.rhs, ctot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+            rc = solve(dp, nullptr);
             if (rc) return rc;
+            for (int it = 0; it < nref; ++it) {
+                residual(dr);
+                rc = solve(dr, dp);
+                if (rc) return rc;
+            }
+            residual(dr);
+            double* resn_part = h->d_resn + 4 * (size_t)O + 4 * (size_t)c0 * RESN_BLK;
+            hipLaunchKernelGGL(adj_resnorm_kernel, dim3(RESN_BLK, nimg), dim3(256), 0, h->stream, dr, C.rhs, diag, (int)npx, resn_part);
+            hipLaunchKernelGGL(adj_resnorm_final_kernel, dim3((4 * nimg + 63) / 64), dim3(64), 0, h->stream, resn_part, nimg,
+                               resn_fin + 4 * ((size_t)d * O + c0));
+            if (tangent)   // du is the solution itself: straight into the direction's slice of the caller's array
+                HIPCHK(h, hipMemcpyAsync(g.du + (size_t)d * tot + o0, dp, ctot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
         }
-        residual(dr);
-        double* resn_part = h->d_resn + 4 * (size_t)O + 4 * (size_t)c0 * RESN_BLK;
-        hipLaunchKernelGGL(adj_resnorm_kernel, dim3(RESN_BLK, nimg), dim3(256), 0, h->stream, dr, C.rhs, diag, (int)npx, resn_part);
-        hipLaunchKernelGGL(adj_resnorm_final_kernel, dim3((4 * nimg + 63) / 64), dim3(64), 0, h->stream, resn_part, nimg, h->d_resn + 4 * (size_t)c0);
         if (g.d_out)
             hipLaunchKernelGGL(sr_adj_gradpix_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, patch, reg, gp);
         HIPCHK(h, hipGetLastError());
@@ -2155,9 +2203,9 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int re
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
     std::vector<int> fail(O);
-    std::vector<double> resn(4 * (size_t)O);
+    std::vector<double> resn(4 * (size_t)O * ndir);
     HIPCHK(h, hipMemcpyAsync(fail.data(), h->d_fail, sizeof(int) * O, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(resn.data(), h->d_resn, sizeof(double) * 4 * O, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(resn.data(), resn_fin, sizeof(double) * resn.size(), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     float ms = 0.f;
     HIPCHK(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
@@ -2168,13 +2216,14 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int re
     h->st.hb_sync = (band && !lu) ? (h->hb_sr.value_sync ? 2 : 1) : 0;
     h->st.kappa_used = reg ? 0.0 : kact;
     double worst = 0.0, worst_raw = 0.0;
-    for (int k = 0; k < O; ++k) {
+    for (int k = 0; k < O; ++k)
         if (fail[k] != 0)
             return set_err(h, BPLTV_E_NUMERIC, lu ? (band ? "sum-of-regularisers adjoint, banded LU without pivoting: zero, tiny or non-finite pivot at column %d of image %d"
                                                           : "sum-of-regularisers adjoint, LU without pivoting: zero, tiny or non-finite pivot at front %d of image %d")
                                                   : (band ? "sum-of-regularisers adjoint Cholesky: non-positive pivot at column %d of image %d"
                                                           : "sum-of-regularisers adjoint Cholesky: non-positive pivot at front %d of image %d"), fail[k] - 1, k);
-        const double* q = &resn[4 * (size_t)k];
+    for (size_t k = 0; k < (size_t)O * ndir; ++k) {   // (direction, image) pairs: the worst of them
+        const double* q = &resn[4 * k];
         const double raw = std::sqrt(q[0]) / (q[1] > 0 ? std::sqrt(q[1]) : 1.0);
         const double scl = std::sqrt(q[2]) / (q[3] > 0 ? std::sqrt(q[3]) : 1.0);
         if (!(raw <= worst_raw)) worst_raw = raw;
@@ -2868,15 +2917,16 @@ int vjp_device(bpltv_t* h, const double* d_u, const double* d_alpha, int am, int
 
 // bpltv_jvp / bpltv_jvp_each over the shards: images split as for the VJP.  The arrays are direction-major over the
 // WHOLE batch, so every shard gets its images of every direction packed (and, each, its parameter blocks), and its du
-// slices are scattered back in place: no reduction.
+// slices are scattered back in place: no reduction.  slices: 1 TV, 3 sum of regularisers (blocks of 3*am*an doubles).
 int multi_jvp(bpltv_t* h, const double* u, const double* alpha, int am, int an, int reg, const bpltv_params* pp, int ndir,
-              const double* df, const double* dalpha, double* du_out, bool each) {
+              const double* df, const double* dalpha, double* du_out, bool each, int slices) {
     if (!u || !alpha || !du_out || am < 1 || an < 1) return set_err(h, BPLTV_E_ARG, "jvp: null pointer or empty shape");
     if (ndir < 1) return set_err(h, BPLTV_E_ARG, "jvp: ndir = %d (at least one direction)", ndir);
     if (!df && !dalpha) return set_err(h, BPLTV_E_ARG, "jvp: both tangents are NULL");
     WallTimer wt;
     MultiState& ms = *h->multi;
-    const size_t npx = h->npx, tot = h->tot, P = (size_t)am * an;
+    const size_t npx = h->npx, tot = h->tot, P = (size_t)slices * am * an;
+    const bool sr = slices == 3;
     int rc = multi_run(h, [&](int k, bpltv_t* c) -> int {
         const size_t o0 = ms.lo[k] * npx, nk = (size_t)(ms.hi[k] - ms.lo[k]), tk = nk * npx;
         std::vector<double> dfk(df ? ndir * tk : 0), dak(dalpha && each ? ndir * nk * P : 0), duk(ndir * tk);
@@ -2884,9 +2934,12 @@ int multi_jvp(bpltv_t* h, const double* u, const double* alpha, int am, int an, 
             if (df) std::memcpy(dfk.data() + d * tk, df + d * tot + o0, tk * sizeof(double));
             if (dalpha && each) std::memcpy(dak.data() + d * nk * P, dalpha + ((size_t)d * h->O + ms.lo[k]) * P, nk * P * sizeof(double));
         }
-        const int r = each ? bpltv_jvp_each(c, u + o0, alpha + ms.lo[k] * P, am, an, reg, pp, ndir, df ? dfk.data() : nullptr,
-                                            dalpha ? dak.data() : nullptr, duk.data())
-                           : bpltv_jvp(c, u + o0, alpha, am, an, reg, pp, ndir, df ? dfk.data() : nullptr, dalpha, duk.data());
+        const double *ak = each ? alpha + ms.lo[k] * P : alpha, *dfp = df ? dfk.data() : nullptr;
+        const double* dap = dalpha ? (each ? dak.data() : dalpha) : nullptr;
+        const int r = each ? (sr ? bpltv_sumregs_jvp_each(c, u + o0, ak, am, an, reg, pp, ndir, dfp, dap, duk.data())
+                                 : bpltv_jvp_each(c, u + o0, ak, am, an, reg, pp, ndir, dfp, dap, duk.data()))
+                           : (sr ? bpltv_sumregs_jvp(c, u + o0, ak, am, an, reg, pp, ndir, dfp, dap, duk.data())
+                                 : bpltv_jvp(c, u + o0, ak, am, an, reg, pp, ndir, dfp, dap, duk.data()));
         if (r == BPLTV_OK)
             for (int d = 0; d < ndir; ++d) std::memcpy(du_out + d * tot + o0, duk.data() + d * tk, tk * sizeof(double));
         return r;
@@ -2898,9 +2951,9 @@ int multi_jvp(bpltv_t* h, const double* u, const double* alpha, int am, int an, 
 
 // bpltv_jvp and bpltv_jvp_each: host arrays staged in d_u2 and d_jvp = [du | df | dalpha]
 int jvp_host(bpltv_t* h, const double* u, const double* alpha, int am, int an, int reg, const bpltv_params* pp, int ndir,
-             const double* df, const double* dalpha, double* du_out, bool each) {
+             const double* df, const double* dalpha, double* du_out, bool each, int slices = 1) {
     if (!h) return BPLTV_E_ARG;
-    if (h->multi) return multi_jvp(h, u, alpha, am, an, reg, pp, ndir, df, dalpha, du_out, each);
+    if (h->multi) return multi_jvp(h, u, alpha, am, an, reg, pp, ndir, df, dalpha, du_out, each, slices);
     if (!u || !alpha || !du_out) return set_err(h, BPLTV_E_ARG, "jvp: null pointer");
     if (ndir < 1) return set_err(h, BPLTV_E_ARG, "jvp: ndir = %d (at least one direction)", ndir);
     if (!df && !dalpha) return set_err(h, BPLTV_E_ARG, "jvp: both tangents are NULL");
@@ -2912,14 +2965,14 @@ int jvp_host(bpltv_t* h, const double* u, const double* alpha, int am, int an, i
         HIPCHK(h, hipMalloc((void**)&h->d_u2, h->tot * sizeof(double)));
         HIPCHK(h, hipMalloc((void**)&h->d_ubar2, h->tot * sizeof(double)));
     }
-    const size_t nt = (size_t)ndir * h->tot, na = (size_t)ndir * am * an * (each ? h->O : 1);
+    const size_t nt = (size_t)ndir * h->tot, na = (size_t)ndir * slices * am * an * (each ? h->O : 1);
     int rc = ensure(h, &h->d_jvp, &h->jvp_cap, 2 * nt + na);
     if (rc) return rc;
     double *d_du = h->d_jvp, *d_df = df ? h->d_jvp + nt : nullptr, *d_da = dalpha ? h->d_jvp + 2 * nt : nullptr;
     HIPCHK(h, hipMemcpyAsync(h->d_u2, u, h->tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (df) HIPCHK(h, hipMemcpyAsync(d_df, df, nt * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (dalpha) HIPCHK(h, hipMemcpyAsync(d_da, dalpha, na * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    rc = jvp_common(h, h->d_u2, alpha, false, am, an, reg, pp, ndir, d_df, d_da, d_du, each);
+    rc = jvp_common(h, h->d_u2, alpha, false, am, an, reg, pp, ndir, d_df, d_da, d_du, each, slices);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(du_out, d_du, nt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -2929,37 +2982,40 @@ int jvp_host(bpltv_t* h, const double* u, const double* alpha, int am, int an, i
 
 // bpltv_jvp_device and bpltv_jvp_each_device
 int jvp_device(bpltv_t* h, const double* d_u, const double* d_alpha, int am, int an, int reg, const bpltv_params* pp, int ndir,
-               const double* d_df, const double* d_dalpha, double* d_du, bool each) {
+               const double* d_df, const double* d_dalpha, double* d_du, bool each, int slices = 1) {
     if (!h) return BPLTV_E_ARG;
     if (h->multi) {
-        const int r = multi_forward0(h, each ? "bpltv_jvp_each_device" : "bpltv_jvp_device", [&](bpltv_t* c) {
-            return jvp_device(c, d_u, d_alpha, am, an, reg, pp, ndir, d_df, d_dalpha, d_du, each);
+        const char* name = slices == 3 ? (each ? "bpltv_sumregs_jvp_each_device" : "bpltv_sumregs_jvp_device")
+                                       : (each ? "bpltv_jvp_each_device" : "bpltv_jvp_device");
+        const int r = multi_forward0(h, name, [&](bpltv_t* c) {
+            return jvp_device(c, d_u, d_alpha, am, an, reg, pp, ndir, d_df, d_dalpha, d_du, each, slices);
         });
         if (r == BPLTV_OK) multi_stats(h);   // no solve ran: has_result stays
         return r;
     }
     WallTimer wt;
     HIPCHK(h, hipSetDevice(h->device));
-    const int rc = jvp_common(h, d_u, d_alpha, true, am, an, reg, pp, ndir, d_df, d_dalpha, d_du, each);
+    const int rc = jvp_common(h, d_u, d_alpha, true, am, an, reg, pp, ndir, d_df, d_dalpha, d_du, each, slices);
     if (rc) return rc;
     h->st.total_ms = wt.ms();
     return BPLTV_OK;
 }
 
-// bpltv_gauss_newton: gradient and Gauss-Newton Hessian of 0.5||u(alpha) - ubar||^2 from the P = am*an <= GN_MAXP
+// bpltv_gauss_newton: gradient and Gauss-Newton Hessian of 0.5||u(alpha) - ubar||^2 from the P = slices*am*an <= GN_MAXP
 // columns du/dalpha_j, solved as the unit directions of one jvp_common call (one factorisation per image group).
+// slices: 1 TV, 3 sum of regularisers (bpltv_sumregs_gauss_newton; columns in the order of the parameter layout).
 constexpr int GN_MAXP = 16;
 int gauss_newton(bpltv_t* h, const double* u, const double* ubar, const double* alpha, int am, int an, int reg,
-                 const bpltv_params* pp, double* grad_out, double* hess_out) {
+                 const bpltv_params* pp, double* grad_out, double* hess_out, int slices = 1) {
     if (!h) return BPLTV_E_ARG;
     if (!u || !ubar || !alpha || !grad_out || !hess_out) return set_err(h, BPLTV_E_ARG, "gauss_newton: null pointer");
     if (am < 1 || an < 1 || am > h->M || an > h->N)
         return set_err(h, BPLTV_E_ARG, "gauss_newton: parameter shape %dx%d (image %dx%d)", am, an, h->M, h->N);
     const bool amap = am == h->M && an == h->N && !(h->M == 1 && h->N == 1);
-    if (amap || (long)am * an > GN_MAXP)
-        return set_err(h, BPLTV_E_UNSUPPORTED, "gauss_newton: a scalar or a patch parameter of at most %d entries (got %dx%d%s); use bpltv_jvp for Jacobian columns",
-                       GN_MAXP, am, an, amap ? ", a pixel map" : "");
-    const int P = am * an;
+    if (amap || (long)slices * am * an > GN_MAXP)
+        return set_err(h, BPLTV_E_UNSUPPORTED, "gauss_newton: a scalar or a patch parameter of at most %d entries (got %s%dx%d%s); use bpltv_jvp for Jacobian columns",
+                       GN_MAXP, slices == 3 ? "3 slices of " : "", am, an, amap ? ", a pixel map" : "");
+    const int P = slices * am * an;
     const size_t nout = (size_t)P + (size_t)P * P;
     WallTimer wt;
     if (h->multi) {   // the shards' [grad, H] added on the host in shard order
@@ -2968,7 +3024,9 @@ int gauss_newton(bpltv_t* h, const double* u, const double* ubar, const double* 
         std::vector<double> part((size_t)n * nout);
         const int rc = multi_run(h, [&](int k, bpltv_t* c) {
             double* o = part.data() + (size_t)k * nout;
-            return bpltv_gauss_newton(c, u + ms.lo[k] * h->npx, ubar + ms.lo[k] * h->npx, alpha, am, an, reg, pp, o, o + P);
+            const double *uk = u + ms.lo[k] * h->npx, *bk = ubar + ms.lo[k] * h->npx;
+            return slices == 3 ? bpltv_sumregs_gauss_newton(c, uk, bk, alpha, am, an, reg, pp, o, o + P)
+                               : bpltv_gauss_newton(c, uk, bk, alpha, am, an, reg, pp, o, o + P);
         });
         if (rc) return rc;
         for (size_t e = 0; e < nout; ++e) {
@@ -3001,7 +3059,7 @@ int gauss_newton(bpltv_t* h, const double* u, const double* ubar, const double* 
     HIPCHK(h, hipMemcpyAsync(h->d_ubar2, ubar, h->tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(d_e, eye.data(), eye.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));   // (eye is a local)
-    int rc = jvp_common(h, h->d_u2, alpha, false, am, an, reg, pp, P, nullptr, d_e, d_J, false);
+    int rc = jvp_common(h, h->d_u2, alpha, false, am, an, reg, pp, P, nullptr, d_e, d_J, false, slices);
     if (rc) return rc;
     hipLaunchKernelGGL(gn_gram_kernel, dim3(P + 1, P, h->O), dim3(256), 0, h->stream, d_J, h->d_u2, h->d_ubar2, (int)h->npx, h->O, P,
                        d_part);
@@ -3448,6 +3506,27 @@ int bpltv_jvp_each_device(bpltv_t* h, const double* d_u, const double* d_alphas,
 int bpltv_gauss_newton(bpltv_t* h, const double* u, const double* ubar, const double* alpha, int am, int an, int reg,
                        const bpltv_params* pp, double* grad_out, double* hess_out) {
     return gauss_newton(h, u, ubar, alpha, am, an, reg, pp, grad_out, hess_out);
+}
+
+int bpltv_sumregs_jvp(bpltv_t* h, const double* u, const double* alpha, int am, int an, int reg, const bpltv_params* pp, int ndir,
+                      const double* df, const double* dalpha, double* du_out) {
+    return jvp_host(h, u, alpha, am, an, reg, pp, ndir, df, dalpha, du_out, false, 3);
+}
+int bpltv_sumregs_jvp_device(bpltv_t* h, const double* d_u, const double* d_alpha, int am, int an, int reg, const bpltv_params* pp,
+                             int ndir, const double* d_df, const double* d_dalpha, double* d_du) {
+    return jvp_device(h, d_u, d_alpha, am, an, reg, pp, ndir, d_df, d_dalpha, d_du, false, 3);
+}
+int bpltv_sumregs_jvp_each(bpltv_t* h, const double* u, const double* alphas, int am, int an, int reg, const bpltv_params* pp,
+                           int ndir, const double* df, const double* dalphas, double* du_out) {
+    return jvp_host(h, u, alphas, am, an, reg, pp, ndir, df, dalphas, du_out, true, 3);
+}
+int bpltv_sumregs_jvp_each_device(bpltv_t* h, const double* d_u, const double* d_alphas, int am, int an, int reg,
+                                  const bpltv_params* pp, int ndir, const double* d_df, const double* d_dalphas, double* d_du) {
+    return jvp_device(h, d_u, d_alphas, am, an, reg, pp, ndir, d_df, d_dalphas, d_du, true, 3);
+}
+int bpltv_sumregs_gauss_newton(bpltv_t* h, const double* u, const double* ubar, const double* alpha, int am, int an, int reg,
+                               const bpltv_params* pp, double* grad_out, double* hess_out) {
+    return gauss_newton(h, u, ubar, alpha, am, an, reg, pp, grad_out, hess_out, 3);
 }
 
 int bpltv_sumregs_vjp(bpltv_t* h, const double* u, const double* alpha, int am, int an, int reg, const bpltv_params* pp,

@@ -705,4 +705,82 @@ __global__ __launch_bounds__(256) void sr_gpix_each_kernel(const double* __restr
     out[e] = gpix[(k * O + img) * npx + q];
 }
 
+// ---- forward mode: the Jacobian-vector product of u = sumregs_denoise(f, x) (bpltv_sumregs_jvp) --------------------
+// The JVP is the linear map whose transpose the vector-Jacobian product above computes.  With h_k the planes the setup
+// wrote, w_k = G_k^T h_k per node and A the matrix the VJP factors, one direction (df, dx) solves
+//     A^T du = r,    r = df - sum_k w_k o up(dx_k)
+// (the VJP's -gu / -p pair of sumregs_gradient_reg cancels: no sign).  A^T = A except for the row-scaled system of
+// sumregs_gradient_reg with a patch or map parameter, where A^T = I + sum_k G_k^T W_k G_k diag(up(x_k)).
+
+// The three planes w_k = G_k^T h_k, wpl[k][O][M*N]: they do not depend on the direction.
+__global__ __launch_bounds__(256) void sr_adj_wplane_kernel(SrCoef C, int M, int N, int O, double* __restrict__ wpl) {
+    const size_t npx = (size_t)M * N;
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= npx * O) return;
+    const int img = (int)(e / npx), k0 = (int)(e - (size_t)img * npx);
+    const int i = k0 % M, j = k0 / M;
+    const size_t ib = (size_t)img * npx;
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+        wpl[(size_t)k * C.tot + e] = sr_gradT_at(k, C.h1 + (size_t)k * C.tot + ib, C.h2 + (size_t)k * C.tot + ib, M, N, i, j);
+}
+
+// Right-hand side of one direction into C.rhs.  df, dx: this group's first image of the direction, or nullptr (a zero
+// tangent); dx is addressed like the parameter (three slices of am x an; bstride: 0 = one block for every image,
+// 3*am*an = image k reads block k).
+__global__ __launch_bounds__(256) void sr_tangent_rhs_kernel(SrCoef C, const double* __restrict__ wpl, const double* __restrict__ df,
+                                                             const double* __restrict__ dx, int am, int an, int bstride, int M,
+                                                             int N, int O) {
+    const size_t npx = (size_t)M * N;
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= npx * O) return;
+    const int img = (int)(e / npx), k0 = (int)(e - (size_t)img * npx);
+    const int i = k0 % M, j = k0 / M;
+    double r = df ? df[e] : 0.0;
+    if (dx) {
+        dx += (size_t)img * bstride;
+        const size_t ai = sr_alpha_index(am, an, M, N, i, j), astride = (size_t)am * an;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) r -= wpl[(size_t)k * C.tot + e] * dx[k * astride + ai];
+    }
+    C.rhs[e] = r;
+}
+
+// Residual of the transposed row-scaled system, pass 1: w_k = W_k G_k (x_k o p) per element -- the parameter scales the
+// COLUMNS of term k, so it multiplies p before G_k; pass 2 is sr_adj_residual_kernel without a row scaling.
+// colscale: the parameter (three slices of am x an, bstride as above).
+__global__ __launch_bounds__(256) void sr_adj_flux_colscale_kernel(SrCoef C, const double* __restrict__ p, int M, int N, int O,
+                                                                   double* __restrict__ w, const double* __restrict__ colscale,
+                                                                   int am, int an, int bstride) {
+    const size_t npx = (size_t)M * N;
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= npx * O) return;
+    const int img = (int)(e / npx), k0 = (int)(e - (size_t)img * npx);
+    const int i = k0 % M, j = k0 / M;
+    const double* pi = p + (size_t)img * npx;
+    colscale += (size_t)img * bstride;
+    const size_t astride = (size_t)am * an;
+    const int ip = (i < M - 1) ? i + 1 : i, im = (i > 0) ? i - 1 : i;
+    const int jp = (j < N - 1) ? j + 1 : j, jm = (j > 0) ? j - 1 : j;
+    const size_t ac = sr_alpha_index(am, an, M, N, i, j);
+    const size_t aup = sr_alpha_index(am, an, M, N, ip, j), aum = sr_alpha_index(am, an, M, N, im, j);
+    const size_t avp = sr_alpha_index(am, an, M, N, i, jp), avm = sr_alpha_index(am, an, M, N, i, jm);
+    const double pc = pi[k0], pup = pi[ip + (size_t)M * j], pum = pi[im + (size_t)M * j];
+    const double pvp = pi[i + (size_t)M * jp], pvm = pi[i + (size_t)M * jm];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double* xk = colscale + k * astride;
+        const double uc = xk[ac] * pc, up = xk[aup] * pup, um = xk[aum] * pum, vp = xk[avp] * pvp, vm = xk[avm] * pvm;
+        double d1, d2;
+        if (k == 0) { d1 = up - uc; d2 = vp - uc; }
+        else if (k == 1) { d1 = uc - um; d2 = uc - vm; }
+        else { d1 = 0.5 * (up - um); d2 = 0.5 * (vp - vm); }
+        const size_t o = (size_t)k * C.tot + e;
+        const double t1 = C.t1[o], t2 = C.t2[o], c = C.c[o], kp = C.kap[o];
+        const double bp = t1 * d1 + t2 * d2;
+        w[(size_t)(2 * k) * C.tot + e] = c * bp * t1 + kp * d1;
+        w[(size_t)(2 * k + 1) * C.tot + e] = c * bp * t2 + kp * d2;
+    }
+}
+
 }  // namespace bpltv

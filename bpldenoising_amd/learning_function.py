@@ -259,6 +259,45 @@ class TVSolver:
                                                        C.c_void_p(grad_f_ptr or None),
                                                        C.c_void_p(grad_alpha_ptr or None)))
 
+    # -- forward mode of the sum-of-regularisers model (bpltv_sumregs_jvp / bpltv_sumregs_gauss_newton) ------------
+    def sumregs_jvp(self, u, x, df=None, dalpha=None, reg=False, **kw):
+        """Jacobian-vector product of u = sumregs_denoise(f, x) (bpltv_sumregs_jvp): du for the tangents (df, dalpha),
+        the linear map whose transpose sumregs_vjp computes.  x: (3,) or (3, n, m); df: (O, N, M), or (K, O, N, M) for K
+        directions solved against one factorisation; dalpha: shaped like x, or with a leading K; either may be None
+        (zero), not both.  Returns du of shape (O, N, M), or (K, O, N, M) when a leading K was given."""
+        a, am, an, _vec = _sr_alpha_arg(x)
+        df, dalpha, K, batched = self._tangents("sumregs_jvp", df, dalpha, a.shape)
+        p = self.params(_sumregs=True, **kw)
+        u = self._batch(u, "u")
+        du = np.empty((K, self.O, self.N, self.M))
+        self._check(self._lib.bpltv_sumregs_jvp(self._h, _ptr(u), _ptr(a), am, an, int(bool(reg)), C.byref(p), K,
+                                                _ptr(df) if df is not None else None,
+                                                _ptr(dalpha) if dalpha is not None else None, _ptr(du)))
+        return du if batched else du[0]
+
+    def sumregs_jvp_device(self, u_ptr, alpha_ptr, am, an, df_ptr, dalpha_ptr, du_ptr, ndir=1, reg=False, **kw):
+        """bpltv_sumregs_jvp_device: u (M*N*O doubles), the parameter (3*am*an), df and du (ndir*M*N*O) and dalpha
+        (ndir*3*am*an) all resident in HBM (raw device pointers); either tangent pointer may be 0 / None, not both."""
+        p = self.params(_sumregs=True, **kw)
+        self._check(self._lib.bpltv_sumregs_jvp_device(self._h, C.c_void_p(u_ptr), C.c_void_p(alpha_ptr), int(am),
+                                                       int(an), int(bool(reg)), C.byref(p), int(ndir),
+                                                       C.c_void_p(df_ptr or None), C.c_void_p(dalpha_ptr or None),
+                                                       C.c_void_p(du_ptr)))
+
+    def sumregs_gauss_newton(self, u, ubar, x, reg=False, **kw):
+        """Gauss-Newton model of 0.5||u(x) - ubar||^2 (bpltv_sumregs_gauss_newton): (grad, H) with grad = J^T (u - ubar)
+        shaped like x and H = J^T J of shape (P, P), P = x.size <= 16, ordered as numpy's x.ravel() (the library's
+        parameter layout).  x: (3,), or a (3, n, m) patch."""
+        a, am, an, _vec = _sr_alpha_arg(x)
+        p = self.params(_sumregs=True, **kw)
+        u = self._batch(u, "u")
+        ubar = self._batch(ubar, "ubar")
+        P = 3 * am * an
+        grad, H = np.empty(P), np.empty((P, P))
+        self._check(self._lib.bpltv_sumregs_gauss_newton(self._h, _ptr(u), _ptr(ubar), _ptr(a), am, an,
+                                                         int(bool(reg)), C.byref(p), _ptr(grad), _ptr(H)))
+        return grad.reshape(a.shape), H
+
     def gradient(self, u, ubar, x, reg=False, **kw):
         a, am, an, scalar = _alpha_arg(x)
         p = self.params(**kw)
@@ -299,7 +338,8 @@ class TVSolver:
     # -- forward mode (bpltv_jvp / bpltv_gauss_newton) -------------------------------------------------------
     def _tangents(self, what, df, dalpha, ashape):
         """(df, dalpha, K, batched): the tangents as contiguous (K, ...) stacks, either None; batched = a leading K was
-        given.  df: (O, N, M) or (K, O, N, M); dalpha: shaped like the parameter (ashape) or with a leading K."""
+        given.  df: (O, N, M) or (K, O, N, M); dalpha: shaped like the parameter (ashape: a TV parameter, the three
+        slices (3,) / (3, n, m) of the sum-of-regularisers model, or O blocks of either) or with a leading K."""
         if df is None and dalpha is None:
             raise ValueError("%s: df and dalpha are both None" % what)
         K, batched = None, False
@@ -497,6 +537,28 @@ class TVSolver:
                                                             int(an), int(bool(reg)), C.byref(p), C.c_void_p(gu_ptr),
                                                             C.c_void_p(grad_f_ptr or None),
                                                             C.c_void_p(grad_alphas_ptr or None)))
+
+    def sumregs_jvp_each(self, u, alphas, df=None, dalphas=None, reg=False, **kw):
+        """sumregs_jvp with image k's own block alphas[k] (bpltv_sumregs_jvp_each).  dalphas: shaped like alphas, or
+        with a leading K; df and the result as in sumregs_jvp."""
+        a, am, an = self._sr_each_arg(alphas)
+        df, dalphas, K, batched = self._tangents("sumregs_jvp_each", df, dalphas, a.shape)
+        p = self.params(_sumregs=True, **kw)
+        u = self._batch(u, "u")
+        du = np.empty((K, self.O, self.N, self.M))
+        self._check(self._lib.bpltv_sumregs_jvp_each(self._h, _ptr(u), _ptr(a), am, an, int(bool(reg)), C.byref(p), K,
+                                                     _ptr(df) if df is not None else None,
+                                                     _ptr(dalphas) if dalphas is not None else None, _ptr(du)))
+        return du if batched else du[0]
+
+    def sumregs_jvp_each_device(self, u_ptr, alphas_ptr, am, an, df_ptr, dalphas_ptr, du_ptr, ndir=1, reg=False, **kw):
+        """bpltv_sumregs_jvp_each_device: as sumregs_jvp_device with O parameter blocks (O*3*am*an doubles) and ndir*O
+        tangent blocks."""
+        p = self.params(_sumregs=True, **kw)
+        self._check(self._lib.bpltv_sumregs_jvp_each_device(self._h, C.c_void_p(u_ptr), C.c_void_p(alphas_ptr), int(am),
+                                                            int(an), int(bool(reg)), C.byref(p), int(ndir),
+                                                            C.c_void_p(df_ptr or None), C.c_void_p(dalphas_ptr or None),
+                                                            C.c_void_p(du_ptr)))
 
     def sweep(self, alphas, fetch_u=False, **kw):
         """costs[k] = 0.5*||denoise(f, alphas[k]) - ubar||^2 for K parameters in one batched solve

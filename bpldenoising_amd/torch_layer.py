@@ -32,8 +32,12 @@ Forward mode: tv_denoise and tv_denoise_each also carry a jvp, so torch.autograd
 unpack_dual) works through them: the tangent of u is one bpltv_jvp_device / bpltv_jvp_each_device call with one
 direction on the u of the forward pass -- the linear map whose transpose backward computes, so forward and reverse
 mode agree for both values of reg.  A tangent must be float64 on f's device; an input
-without a tangent counts as zero.  The sum-of-regularisers functions have no forward mode (their reg = 1 patch system
-is row-scaled and would need a transposed solve): forward-mode AD over them raises torch's "not implemented" error.
+without a tangent counts as zero.  As they stand the sum-of-regularisers functions have no forward mode: forward-mode
+AD over them raises torch's "not implemented" error, as it always did.  sumregs_denoise(..., forward_mode=True),
+sumregs_denoise_each(..., forward_mode=True) and SumRegsDenoise(alpha, forward_mode=True) select functions that carry
+the same jvp through bpltv_sumregs_jvp_device / bpltv_sumregs_jvp_each_device (values and backward are bitwise the
+same); their reg = 1 patch system is row-scaled, and the library solves with its transpose there, so the identity with
+backward holds in that branch too.
 
 Streams: the library runs its kernels on its own HIP streams and blocks until they are done.  Every call below first
 synchronises the tensors' current torch stream, so that the library reads inputs torch has finished writing; its
@@ -320,11 +324,51 @@ class SumRegsDenoiseFunction(torch.autograd.Function):
         return gf, (ga.reshape(alpha.shape) if need_a else None), None, None
 
 
-def sumregs_denoise(f, alpha, *, reg=False, **solver_kw):
+def _sumregs_jvp(ctx, df, dalpha, each):
+    """The tangent of u for the forward-mode functions below: one bpltv_sumregs_jvp(_each)_device call, one direction."""
+    u, alpha = ctx.saved_tensors
+    df, dalpha = _tangent(df, u, "f"), _tangent(dalpha, alpha, "alpha")
+    if df is None and dalpha is None:
+        return torch.zeros_like(u)
+    du = torch.empty_like(u)
+    _sync(u.device)
+    call = ctx.solver.sumregs_jvp_each_device if each else ctx.solver.sumregs_jvp_device
+    call(u.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, df.data_ptr() if df is not None else None,
+         dalpha.data_ptr() if dalpha is not None else None, du.data_ptr(), ndir=1, reg=ctx.reg, **ctx.solver_kw)
+    return du
+
+
+class SumRegsDenoiseForwardFunction(SumRegsDenoiseFunction):
+    """SumRegsDenoiseFunction with a jvp (sumregs_denoise(..., forward_mode=True)): forward and backward are the base
+    class's, save_for_forward and set_materialize_grads(False) as the TV functions have them."""
+
+    @staticmethod
+    def forward(ctx, f, alpha, reg, solver_kw):
+        u = SumRegsDenoiseFunction.forward(ctx, f, alpha, reg, solver_kw)
+        ctx.save_for_forward(u, alpha.detach().contiguous())   # what the base class saved for backward
+        ctx.set_materialize_grads(False)   # an input without a tangent reaches jvp as None, and the library as NULL
+        return u
+
+    @staticmethod
+    def jvp(ctx, df, dalpha, _reg, _solver_kw):
+        return _sumregs_jvp(ctx, df, dalpha, False)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gu):
+        if gu is None:
+            return None, None, None, None
+        return SumRegsDenoiseFunction.backward(ctx, gu)
+
+
+def sumregs_denoise(f, alpha, *, reg=False, forward_mode=False, **solver_kw):
     """u = sumregs_denoise(f, alpha) (TVSolver.sumregs_denoise: the reference's sumregs_denoise,
     src/SumRegsLearningFunction.jl:38-85), differentiable in f and alpha.  alpha: (3,), (3, pH, pW) or (3, H, W).
-    solver_kw: the solver parameters of TVSolver.params, used by the forward solve and the adjoint alike."""
-    return SumRegsDenoiseFunction.apply(f, alpha, reg, solver_kw)
+    solver_kw: the solver parameters of TVSolver.params, used by the forward solve and the adjoint alike.
+    forward_mode: also usable under torch.autograd.forward_ad (the function then carries a jvp, bpltv_sumregs_jvp_device);
+    without it forward-mode AD raises torch's "not implemented" error, as before."""
+    fn = SumRegsDenoiseForwardFunction if forward_mode else SumRegsDenoiseFunction
+    return fn.apply(f, alpha, reg, solver_kw)
 
 
 class SumRegsDenoiseEachFunction(torch.autograd.Function):
@@ -363,23 +407,47 @@ class SumRegsDenoiseEachFunction(torch.autograd.Function):
         return gf, ga, None, None
 
 
-def sumregs_denoise_each(f, alpha, *, reg=False, **solver_kw):
+class SumRegsDenoiseEachForwardFunction(SumRegsDenoiseEachFunction):
+    """SumRegsDenoiseEachFunction with a jvp (sumregs_denoise_each(..., forward_mode=True))."""
+
+    @staticmethod
+    def forward(ctx, f, alpha, reg, solver_kw):
+        u = SumRegsDenoiseEachFunction.forward(ctx, f, alpha, reg, solver_kw)
+        ctx.save_for_forward(u, alpha.detach().contiguous())   # what the base class saved for backward
+        ctx.set_materialize_grads(False)   # an input without a tangent reaches jvp as None, and the library as NULL
+        return u
+
+    @staticmethod
+    def jvp(ctx, df, dalpha, _reg, _solver_kw):
+        return _sumregs_jvp(ctx, df, dalpha, True)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gu):
+        if gu is None:
+            return None, None, None, None
+        return SumRegsDenoiseEachFunction.backward(ctx, gu)
+
+
+def sumregs_denoise_each(f, alpha, *, reg=False, forward_mode=False, **solver_kw):
     """u[k] = sumregs_denoise(f[k], alpha[k]) for a batch f of shape (B, H, W) with three weights per image: alpha
     (B, 3), (B, 3, pH, pW) or (B, 3, H, W) on f's device.  One batched solve forward
     (TVSolver.sumregs_denoise_each_device) and one adjoint solve backward (sumregs_vjp_each_device); differentiable in f
-    and alpha, alpha.grad[k] being image k's term.  solver_kw: as sumregs_denoise's."""
-    return SumRegsDenoiseEachFunction.apply(f, alpha, reg, solver_kw)
+    and alpha, alpha.grad[k] being image k's term.  solver_kw and forward_mode: as sumregs_denoise's."""
+    fn = SumRegsDenoiseEachForwardFunction if forward_mode else SumRegsDenoiseEachFunction
+    return fn.apply(f, alpha, reg, solver_kw)
 
 
 class SumRegsDenoise(torch.nn.Module):
     """Sum-of-regularisers denoising with a learnable weight: a (3,) vector, or a (3, pH, pW) / (3, H, W) array.  Move
     it to the device of its inputs with .to(device)."""
 
-    def __init__(self, alpha, reg=False, **solver_kw):
+    def __init__(self, alpha, reg=False, forward_mode=False, **solver_kw):
         super().__init__()
         self.alpha = torch.nn.Parameter(torch.as_tensor(alpha, dtype=torch.float64).clone())
         self.reg = bool(reg)
+        self.forward_mode = bool(forward_mode)   # usable under torch.autograd.forward_ad (sumregs_denoise)
         self.solver_kw = dict(solver_kw)
 
     def forward(self, f):
-        return sumregs_denoise(f, self.alpha, reg=self.reg, **self.solver_kw)
+        return sumregs_denoise(f, self.alpha, reg=self.reg, forward_mode=self.forward_mode, **self.solver_kw)

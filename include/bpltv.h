@@ -401,6 +401,47 @@ int bpltv_sumregs_vjp_each(bpltv_t *h, const double *u, const double *alphas, in
 int bpltv_sumregs_vjp_each_device(bpltv_t *h, const double *d_u, const double *d_alphas, int am, int an, int reg,
                                   const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alphas);
 
+/* Jacobian-vector product of u = sumregs_denoise(f, x): du for tangents (df, dx), defined as the linear map whose
+ * transpose bpltv_sumregs_vjp computes, in every branch -- <gu, du> = <grad_f(gu), df> + <grad_alpha(gu), dx> for any gu.
+ * With h_k the per-element planes of the gradient's last step (k = forward, backward, centred), w_k = G_k^T h_k per node,
+ * up() the patch upsampling and A the matrix bpltv_sumregs_vjp factors for the same (u, x, reg), one direction is
+ *     r = df - sum_k w_k o up(dx_k)   (a vector parameter: dx_k a scalar),      du = A^-T r.
+ * A^T = A except for reg = 1 with a patch or map parameter, whose row-scaled system is not symmetric: there
+ * A^T = I + sum_k K_k diag(up(x_k)), factored as such.  There is no sign: the VJP's -gu / -p pair for reg = 1 cancels.
+ * alpha / dalpha use bpltv_sumregs_evaluate's layout (three slices of am x an); dalpha holds ndir blocks of 3*am*an
+ * doubles, df ndir * M*N*O doubles, either may be NULL (a zero tangent), not both; du_out: ndir * M*N*O doubles.  The
+ * ndir >= 1 directions are solved against ONE factorisation per image group, direction d of a call being bitwise the
+ * ndir = 1 call with that direction.  The contract is bpltv_jvp's and bpltv_sumregs_vjp's: the parameter must be finite
+ * and >= 0 (> 0 for reg = 1 with an array parameter), the tangents finite; ndir < 1 or both tangents NULL is
+ * BPLTV_E_ARG, params.reserved[4] = 2 BPLTV_E_UNSUPPORTED; every rejection comes before anything of the handle changes,
+ * and the last solve, bpltv_u_device, bpltv_duality_gap and the captured graphs stay as they were.  The kappa retry and
+ * the residual gate apply (the gate takes the worst direction); stats report the adjoint.  dtype = 32 handles too; image
+ * groups ("adjoint_budget_mb") give bitwise the same result.  Multi-device handles split the images as bpltv_jvp does. */
+int bpltv_sumregs_jvp(bpltv_t *h, const double *u, const double *alpha, int am, int an, int reg, const bpltv_params *p,
+                      int ndir, const double *df, const double *dalpha, double *du_out);
+/* The same with every array in HBM; parameter and tangents are checked on the device.  Single-device handles (multi:
+ * BPLTV_E_UNSUPPORTED beyond one shard). */
+int bpltv_sumregs_jvp_device(bpltv_t *h, const double *d_u, const double *d_alpha, int am, int an, int reg,
+                             const bpltv_params *p, int ndir, const double *d_df, const double *d_dalpha, double *d_du);
+/* One parameter block per image (the forward mode of bpltv_sumregs_vjp_each): alphas holds O blocks of 3*am*an doubles,
+ * dalphas ndir x O blocks (direction, then image).  Image k reads its own blocks; its du is bitwise what a one-image
+ * handle returns for block k. */
+int bpltv_sumregs_jvp_each(bpltv_t *h, const double *u, const double *alphas, int am, int an, int reg,
+                           const bpltv_params *p, int ndir, const double *df, const double *dalphas, double *du_out);
+int bpltv_sumregs_jvp_each_device(bpltv_t *h, const double *d_u, const double *d_alphas, int am, int an, int reg,
+                                  const bpltv_params *p, int ndir, const double *d_df, const double *d_dalphas,
+                                  double *d_du);
+
+/* Gauss-Newton model of 0.5||u(x) - ubar||^2 for one shared parameter of the sum-of-regularisers model: with J the
+ * M*N*O x P matrix of the columns du/dx_j (P = 3*am*an, ordered as the parameter layout; the unit directions of
+ * bpltv_sumregs_jvp against one factorisation),
+ *     hess_out = J^T J   (P x P doubles, column major, symmetric bit for bit),     grad_out = J^T (u - ubar)   (P doubles).
+ * P <= 16: a vector, or a patch up to 2 x 2 (or 1 x 5); larger patches and pixel maps: BPLTV_E_UNSUPPORTED.  Sums run per
+ * image, then over the images in image order; multi-device handles add the shards' [grad, H] on the host in shard
+ * order.  Checks, staging and stats as bpltv_sumregs_jvp. */
+int bpltv_sumregs_gauss_newton(bpltv_t *h, const double *u, const double *ubar, const double *alpha, int am, int an,
+                               int reg, const bpltv_params *p, double *grad_out, double *hess_out);
+
 /* Forward-only parameter sweep: generate_cost / generate_2d_cost (src/BPLDenoising.jl:92-111,
  * :136-158) evaluate cost(alpha_k) = 0.5*||TVDenoise(f, alpha_k) - ubar||^2 for a range of parameters,
  * one solve after the other.  Here the K parameter blocks (each am x an, column major, K*am*an

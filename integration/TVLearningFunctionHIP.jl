@@ -4,7 +4,8 @@
 # NOT EXECUTED HERE: Julia is not available in the build image; the same entry points are exercised through
 # bpldenoising_amd/_lib.py (ctypes) by the test suite.
 # Same exports as src/TVLearningFunctionVec.jl:6
-export tv_op_learning_function, denoise, sumregs_learning_function, tv_vjp, sumregs_vjp, tv_jvp, tv_gauss_newton
+export tv_op_learning_function, denoise, sumregs_learning_function, tv_vjp, sumregs_vjp, tv_jvp, tv_gauss_newton,
+       sumregs_jvp, sumregs_gauss_newton
 
 const libbpltv = "libbpltv"            # on LD_LIBRARY_PATH, or an absolute path
 
@@ -245,6 +246,43 @@ function sumregs_vjp(h::BpltvHandle, u::Array{Float64,3}, x::Union{AbstractVecto
         (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Ref{BpltvParams}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
         h.ptr, u, a, am, an, reg ? 1 : 0, p, ḡ, gf, ga))
     return gf, ga
+end
+
+# Jacobian-vector product of u = sumregs_denoise(f, x) (include/bpltv.h, bpltv_sumregs_jvp): du for the tangents (df, dx),
+# the linear map whose transpose sumregs_vjp computes, so dot(ḡ, du) == dot(gf, df) + dot(gx, dx) -- also for reg = true
+# with an m x n x 3 parameter, whose row-scaled system the library solves transposed.  df: nothing or an M x N x O array, or
+# M x N x O x K for K directions against one factorisation; dx: nothing, or shaped like x, or with a trailing dimension K.
+function sumregs_jvp(h::BpltvHandle, u::Array{Float64,3}, x::Union{AbstractVector{Float64},AbstractArray{Float64,3}};
+                     df = nothing, dx = nothing, reg = false, kwargs...)
+    a = Array{Float64}(x)
+    am, an = x isa AbstractVector ? (1, 1) : (size(x, 1), size(x, 2))
+    df === nothing && dx === nothing && error("sumregs_jvp: df and dx are both nothing")
+    K = df !== nothing ? size(df, 4) : div(length(dx), length(a))
+    tf = df === nothing ? C_NULL : Array{Float64}(df)
+    ta = dx === nothing ? C_NULL : Array{Float64}(dx)
+    du = zeros(size(u)..., K)
+    p = Ref(default_params(; kwargs...))
+    GC.@preserve u a tf ta du bpltv_check(h, ccall((:bpltv_sumregs_jvp, libbpltv), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Ref{BpltvParams}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        h.ptr, u, a, am, an, reg ? 1 : 0, p, K, tf, ta, du))
+    return K == 1 && (df === nothing || ndims(df) == 3) ? du[:, :, :, 1] : du
+end
+
+# Gauss-Newton model of 0.5||u(x) - ū||^2 for the sum-of-regularisers model (include/bpltv.h, bpltv_sumregs_gauss_newton):
+# (g, H) with g = J'(u - ū) shaped like x and H = J'J (P x P, P = length(x) <= 16, in x's column-major order) from one
+# factorisation -- the 3 x 3 model of the learning problem x = [a1; a2; a3] of src/SumRegsLearningFunction.jl:8, or the
+# 12 x 12 one of a 2 x 2 x 3 patch, for a trust-region step in place of BFGS.
+function sumregs_gauss_newton(h::BpltvHandle, u::Array{Float64,3}, ū::Array{Float64,3},
+                              x::Union{AbstractVector{Float64},AbstractArray{Float64,3}}; reg = false, kwargs...)
+    a = Array{Float64}(x)
+    am, an = x isa AbstractVector ? (1, 1) : (size(x, 1), size(x, 2))
+    P = length(a)
+    g = zeros(size(a)); H = zeros(P, P)
+    p = Ref(default_params(; kwargs...))
+    GC.@preserve u ū a g H bpltv_check(h, ccall((:bpltv_sumregs_gauss_newton, libbpltv), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Ref{BpltvParams}, Ptr{Cdouble}, Ptr{Cdouble}),
+        h.ptr, u, ū, a, am, an, reg ? 1 : 0, p, g, H))
+    return g, H
 end
 
 # test / measurement aids of a handle (include/bpltv.h, bpltv_set_option), e.g. set_option(h, "sweep_split", 2)
