@@ -95,6 +95,11 @@ SYMBOLS = {
     "bpltv_vjp_each": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
     "bpltv_vjp_each_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_void_p,
                                         C.c_void_p, C.c_void_p]),
+    "bpltv_weighted_denoise": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp]),
+    "bpltv_weighted_denoise_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP]),
+    "bpltv_weighted_vjp": (C.c_int, [_H, _dp, _dp, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp, _dp]),
+    "bpltv_weighted_vjp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
+                                            _PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpltv_jvp": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, C.c_int, _dp, _dp, _dp]),
     "bpltv_jvp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),

@@ -27,6 +27,7 @@
 #include "adjoint_kernels.hpp"
 #include "pdhg_kernels.hpp"
 #include "sumregs_kernels.hpp"
+#include "weighted_kernels.hpp"
 #include "multi_gpu.hpp"
 
 using namespace bpltv;
@@ -205,8 +206,20 @@ struct TabKey {
                  // or params.opnorm
     int shift;   // 1: row k carries sigma_{k+1} (dual-first order: the dual step of iteration k+1 follows the
                  // primal step of iteration k inside the fused kernel)
+    double gamma = 1.0;   // strong convexity of the data term the acceleration uses: 1, or min w of a weighted solve
     bool operator<(const TabKey& o) const {
-        return std::tie(maxiter, accel, tau0, sigma0, L, shift) < std::tie(o.maxiter, o.accel, o.tau0, o.sigma0, o.L, o.shift);
+        return std::tie(maxiter, accel, tau0, sigma0, L, shift, gamma) < std::tie(o.maxiter, o.accel, o.tau0, o.sigma0, o.L, o.shift, o.gamma);
+    }
+};
+
+// Captured launch sequence of a weighted solve (run_weighted_pdhg).  A cache of its own: a weighted and an unweighted
+// solve never replay each other's graphs.  d_w, d_f and the state sets are fixed for the life of the handle.
+struct WGraphKey {
+    int maxiter, T, am, an, wo, chains;
+    const void* tab;     // one table per (maxiter, steps, L, gamma): TabKey
+    const void* alpha;
+    bool operator<(const WGraphKey& o) const {
+        return std::tie(maxiter, T, am, an, wo, chains, tab, alpha) < std::tie(o.maxiter, o.T, o.am, o.an, o.wo, o.chains, o.tab, o.alpha);
     }
 };
 
@@ -400,6 +413,14 @@ struct bpltv_handle {
     bool lu_sr_ready = false;
     double* d_srdiagU = nullptr;  // its upper diagonals (7 planes)
     std::map<SrGraphKey, std::vector<hipGraphExec_t>> sr_graphs;   // one graph per launch chain
+    // per-pixel fidelity weight (weighted_kernels.hpp): the handle's copy of the last weighted solve's w (wo planes, gamma =
+    // its smallest entry), allocated on first use and never moved; the solve runs in d_state
+    double* d_w = nullptr;
+    int w_wo = 1;
+    double w_min = 0.0;
+    bool last_weighted = false;                     // the last solve was bpltv_weighted_denoise: u and the gap are its
+    std::map<WGraphKey, std::vector<hipGraphExec_t>> w_graphs;   // one graph per launch chain
+    double* d_wst = nullptr;                        // bpltv_weighted_vjp's host staging [f | grad_w], 2 * M*N*O doubles
     bpltv_stats_t st;
     std::string err;
 };
@@ -461,7 +482,7 @@ void fill_table(const TabKey& k, std::vector<double>& tab) {
     // oracle/bpltv_oracle.c: bplo_step_table_L (same operations, same order)
     const double L = k.L;
     double tau = k.tau0 / L, sigma = k.sigma0 / L;
-    const double gamma = 1.0;
+    const double gamma = k.gamma;
     tab.assign((size_t)TAB_STRIDE * (k.maxiter > 0 ? k.maxiter : 1), 0.0);
     for (int it = 0; it < k.maxiter; ++it) {
         const double omega = k.accel ? 1.0 / std::sqrt(1.0 + 2.0 * gamma * tau) : 1.0;
@@ -482,8 +503,8 @@ void fill_table(const TabKey& k, std::vector<double>& tab) {
 // operator-norm estimate of a solve: params.opnorm, or the model's bound (sqrt(8) TV, sqrt(18) sum of regularisers)
 double opnorm_of(const bpltv_params& p, double L2_default) { return p.opnorm > 0.0 ? p.opnorm : std::sqrt(L2_default); }
 
-int get_table(bpltv_t* h, const bpltv_params& p, double** out, double L2 = 8.0, int shift = 0) {
-    TabKey k{p.maxiter, p.accel ? 1 : 0, p.tau0, p.sigma0, opnorm_of(p, L2), shift};
+int get_table(bpltv_t* h, const bpltv_params& p, double** out, double L2 = 8.0, int shift = 0, double gamma = 1.0) {
+    TabKey k{p.maxiter, p.accel ? 1 : 0, p.tau0, p.sigma0, opnorm_of(p, L2), shift, gamma};
     auto it = h->tabs.find(k);
     if (it != h->tabs.end()) {
         *out = it->second;
@@ -602,10 +623,16 @@ int f32_widen(bpltv_t* h, const SolveCtx& x, int buf) {
     return BPLTV_OK;
 }
 
+void drop_w_graphs(bpltv_t* h) {
+    for (auto& kv : h->w_graphs)
+        for (auto e : kv.second) (void)hipGraphExecDestroy(e);
+    h->w_graphs.clear();
+}
 void drop_graphs(bpltv_t* h) {
     for (auto& kv : h->graphs)
         for (auto e : kv.second) (void)hipGraphExecDestroy(e);
     h->graphs.clear();
+    drop_w_graphs(h);   // they hold d_alpha as well
 }
 
 int solve_precheck(bpltv_t* h, const bpltv_params& p, double amin, int what);
@@ -1391,6 +1418,13 @@ struct GradCtx {
     const double* df = nullptr;
     const double* dalpha = nullptr;
     double* du = nullptr;
+    // weighted model (bpltv_weighted_vjp; reg = 0, cot): w != nullptr selects the system diag(w) + K in its node-scaled form
+    // (weighted_adj_setup_kernel).  w: wo planes in HBM, every entry > 0; d_grad_f then receives w o p; d_grad_w (wo planes,
+    // or nullptr) receives -(u - f) o p, summed over the images in image order when wo == 1; f is read for d_grad_w only.
+    const double* w = nullptr;
+    int wo = 1;
+    const double* f = nullptr;
+    double* d_grad_w = nullptr;
 };
 GradCtx gradient_ctx(const bpltv_t* h, const double* d_ubar, double* d_out) {
     GradCtx g;
@@ -1458,6 +1492,9 @@ int run_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, 
         if (tangent)   // the coefficient planes alone: adj_tangent_rhs_kernel writes each direction's right-hand side below
             hipLaunchKernelGGL(adj_setup_cot_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, d_u + o0, ga, am, an, g.astride,
                                M, N, nimg, patch, reg, kact, C);
+        else if (g.w)
+            hipLaunchKernelGGL(weighted_adj_setup_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0,
+                               g.w + (g.wo > 1 ? o0 : 0), g.wo > 1 ? npx : (size_t)0, ga, am, an, M, N, nimg, kact, C);
         else if (g.cot)
             hipLaunchKernelGGL(adj_setup_cot_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0, ga, am, an, g.astride,
                                M, N, nimg, patch, reg, kact, C);
@@ -1536,7 +1573,14 @@ int run_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, 
                            (double*)nullptr);
     }
     // input gradient of a vector-Jacobian product: d_p and the s plane cover the whole batch after the group loop
-    if (g.d_grad_f)
+    if (g.w) {   // weighted model: w o p, and -(u - f) o p per pixel (d_r is free behind the group loop)
+        double* gw = g.d_grad_w ? (g.wo > 1 ? g.d_grad_w : h->d_r) : nullptr;
+        if (g.d_grad_f || gw)
+            hipLaunchKernelGGL(weighted_adj_out_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->d_coef + 6 * tot,
+                               h->d_p, g.w, g.wo > 1 ? npx : (size_t)0, d_u, g.f, npx, tot, g.d_grad_f, gw);
+        if (gw && g.wo == 1)
+            hipLaunchKernelGGL(map_sum_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, h->d_r, npx, O, g.d_grad_w);
+    } else if (g.d_grad_f)
         hipLaunchKernelGGL(adj_gradf_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->d_coef + 6 * tot, h->d_p,
                            tot, reg, g.d_grad_f);
     HIPCHK(h, hipGetLastError());
@@ -2260,6 +2304,7 @@ int solve_dataset(bpltv_t* h, bool sr, const bpltv_params& p) {
     (sr ? h->sr_result_buf : h->result_buf) = buf;
     (sr ? h->sr_has_result : h->has_result) = true;
     h->last_is_sr = sr;
+    h->last_weighted = false;
     return BPLTV_OK;
 }
 // u of the last solve of the model
@@ -3074,6 +3119,286 @@ int gauss_newton(bpltv_t* h, const double* u, const double* ubar, const double* 
     return BPLTV_OK;
 }
 
+// ============================================================================================
+// Per-pixel data-fidelity weight (weighted_kernels.hpp)
+// ============================================================================================
+// n entries of a weight array, finite and >= 0, on the host or (on_device) in HBM by alpha_check_kernel; *wmin receives the
+// smallest.  Reads only: nothing of the handle changes.
+int check_weight(bpltv_t* h, const char* who, const double* w, bool on_device, size_t n, double* wmin) {
+    if (!on_device) {
+        *wmin = w[0];
+        for (size_t e = 0; e < n; ++e) {
+            if (!std::isfinite(w[e]) || w[e] < 0.0)
+                return set_err(h, BPLTV_E_ARG, "%s: w[%zu] = %g: the fidelity weight must be finite and >= 0", who, e, w[e]);
+            if (w[e] < *wmin) *wmin = w[e];
+        }
+        return BPLTV_OK;
+    }
+    unsigned long long* chk_d = reinterpret_cast<unsigned long long*>(h->d_scalar + 2);
+    HIPCHK(h, hipMemsetAsync(chk_d, 0xFF, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(chk_d + 1, 0, sizeof(unsigned long long), h->stream));
+    hipLaunchKernelGGL(alpha_check_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 1024)), dim3(256), 0, h->stream, w, n, chk_d);
+    HIPCHK(h, hipGetLastError());
+    unsigned long long chk_h[2] = {0, 1};
+    HIPCHK(h, hipMemcpyAsync(chk_h, chk_d, sizeof(chk_h), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (chk_h[1] != 0) return set_err(h, BPLTV_E_ARG, "%s: w (device array): the fidelity weight must be finite and >= 0", who);
+    std::memcpy(wmin, chk_h, sizeof(double));
+    return BPLTV_OK;
+}
+
+// Tiling of a weighted solve: 32 x 32 regions, T iterations per launch (params.tile_iters, default 8; a halo must leave a
+// core, and the kernel keeps at most PDHG_MAX_T step rows).  Results do not depend on T.
+struct WeightedPlan { int T, nTi, nTj; };
+int weighted_plan(bpltv_t* h, const bpltv_params& p, WeightedPlan* pl) {
+    auto maxT = [](int L) { return (L <= WT_R) ? PDHG_MAX_T : (WT_R - 1) / 2; };
+    int T = p.tile_iters > 0 ? p.tile_iters : 8;
+    T = std::min(T, std::min(PDHG_MAX_T, std::min(maxT(h->M), maxT(h->N))));
+    pl->T = T;
+    pl->nTi = tile_count(h->M, WT_R, T);
+    pl->nTj = tile_count(h->N, WT_R, T);
+    if (pl->nTi < 1 || pl->nTj < 1) return set_err(h, BPLTV_E_ARG, "cannot tile %dx%d with T=%d", h->M, h->N, T);
+    if (pl->nTj > 65535 || h->O > 65535 || (long long)pl->nTi * pl->nTj * h->O > 0x7FFFFFFFll)
+        return set_err(h, BPLTV_E_UNSUPPORTED, "weighted solve: at most 65535 tile rows, 65535 images and 2^31 tiles per launch (grid dimensions)");
+    return BPLTV_OK;
+}
+
+// What a weighted call rejects on its parameters alone
+int weighted_check_params(bpltv_t* h, const bpltv_params& p, const char* who) {
+    if (int prc = check_params(h, p)) return prc;
+    if (p.rho != 0.0) return set_err(h, BPLTV_E_UNSUPPORTED, "%s: params.rho must be 0 (no Huber smoothing in the weighted model)", who);
+    if (p.init != 0 || p.order != 0) return set_err(h, BPLTV_E_UNSUPPORTED, "%s: params.init / params.order must be 0", who);
+    return BPLTV_OK;
+}
+
+// maxiter iterations of the weighted recurrence on the dataset images, in the TV state sets, with the handle's d_w / w_wo /
+// w_min and d_alpha.  *result_buf: the state set that holds the result.
+int run_weighted_pdhg(bpltv_t* h, const bpltv_params& p, const WeightedPlan& pl, int* result_buf) {
+    h->has_per_image = false;
+    double* d_tab = nullptr;
+    int rc = get_table(h, p, &d_tab, 8.0, 0, h->w_min);
+    if (rc) return rc;
+    const int M = h->M, N = h->N, O = h->O, T = pl.T;
+    const bool amap = (h->last_am == M && h->last_an == N) && !(M == 1 && N == 1);
+    h->st.tile_iters = T; h->st.tiles = pl.nTi * pl.nTj * O; h->st.region_i = WT_R; h->st.region_j = WT_R; h->st.pdhg_variant = 0;
+    h->st.launches = 0; h->st.iterations = p.maxiter; h->st.graph_used = 0; h->st.last_gap = -1.0; h->st.launch_chains = 1;
+    h->st.launch_host_ms[0] = h->st.launch_host_ms[1] = 0.0;
+    h->st.bytes_per_px_iter = amap ? 72.0 : 64.0;   // read x, y1, y2, f, w (+ alpha), write x, y1, y2
+    h->st.algorithmic_bytes = h->st.bytes_per_px_iter * (double)h->tot * p.maxiter;
+    if (p.maxiter == 0) {   // u = f
+        HIPCHK(h, hipMemcpyAsync(h->d_state[0][0], h->d_f, h->tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        for (int c = 1; c < 3; ++c) HIPCHK(h, hipMemsetAsync(h->d_state[0][c], 0, h->tot * sizeof(double), h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        *result_buf = 0; h->st.pdhg_ms = 0.0;
+        return BPLTV_OK;
+    }
+    // all iterations of the images [lo, hi).  stagger: the chain's first launch fuses T/2 iterations and writes set 1, so that
+    // it runs half a launch out of phase with the other chain and ends in the same set (run_pdhg's launch chains)
+    auto enqueue_range = [&](hipStream_t st, int lo, int hi, bool stagger) {
+        int cur = 0, step = stagger ? std::max(1, T / 2) : T;
+        for (int it = 0; it < p.maxiter; it += step, step = T) {
+            const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
+            WeightedArgs a;
+            a.xin = h->d_state[cur][0]; a.y1in = h->d_state[cur][1]; a.y2in = h->d_state[cur][2];
+            a.xout = h->d_state[nxt][0]; a.y1out = h->d_state[nxt][1]; a.y2out = h->d_state[nxt][2];
+            a.f = h->d_f; a.w = h->d_w; a.alpha = h->d_alpha; a.tab = d_tab;
+            a.wstride = h->w_wo > 1 ? h->npx : 0;
+            a.am = h->last_am; a.an = h->last_an;
+            a.it0 = it; a.nit = std::min(step, p.maxiter - it);
+            a.M = M; a.N = N; a.halo = T; a.first = (it == 0) ? 1 : 0; a.img0 = lo;
+            hipLaunchKernelGGL(weighted_tile_kernel, dim3(pl.nTi, pl.nTj, hi - lo), dim3(WT_R * WT_R), weighted_lds_bytes(), st, a);
+            cur = nxt;
+        }
+    };
+    const int nl = (p.maxiter + T - 1) / T;
+    // two launch chains (image groups on two streams) once the batch is well beyond one workgroup per CU, as run_pdhg;
+    // params.reserved[1] = 1 keeps one chain
+    const int ncu = h->ncu > 0 ? h->ncu : 256;
+    int nch = p.reserved[1] > 0 ? std::min(p.reserved[1], 2) : ((2 * (long)h->st.tiles > 3 * (long)ncu && O >= 2) ? 2 : 1);
+    if (nch > O) nch = O;
+    const int h0 = std::max(1, T / 2);
+    const bool stag = T >= 2 && nl >= 8 && ((1 + (p.maxiter - h0 + T - 1) / T) - nl) % 2 == 1;
+    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+    bool done = false;
+    if (p.use_graph && nl <= 50000) {
+        const WGraphKey key{p.maxiter, T, h->last_am, h->last_an, h->w_wo, nch, (const void*)d_tab, (const void*)h->d_alpha};
+        auto it = h->w_graphs.find(key);
+        if (it == h->w_graphs.end()) {
+            if (h->w_graphs.size() >= 8) drop_w_graphs(h);
+            std::vector<hipGraphExec_t> exs;
+            for (int c = 0; c < nch; ++c) {
+                const int lo = (int)(((long)O * c) / nch), hi = (int)(((long)O * (c + 1)) / nch);
+                hipGraph_t g = nullptr;
+                hipGraphExec_t ex = nullptr;
+                if (!h->capture_stream && hipStreamCreateWithFlags(&h->capture_stream, hipStreamNonBlocking) != hipSuccess) { h->capture_stream = nullptr; break; }
+                if (hipStreamBeginCapture(h->capture_stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+                    enqueue_range(h->capture_stream, lo, hi, (c & 1) && stag);
+                    if (hipStreamEndCapture(h->capture_stream, &g) == hipSuccess && g && hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) == hipSuccess)
+                        exs.push_back(ex);
+                    if (g) (void)hipGraphDestroy(g);
+                }
+            }
+            (void)hipGetLastError();
+            if ((int)exs.size() == nch) {
+                h->w_graphs[key] = exs;
+                it = h->w_graphs.find(key);
+            } else {
+                for (auto e : exs) (void)hipGraphExecDestroy(e);
+            }
+        }
+        if (it != h->w_graphs.end()) {
+            const std::vector<hipGraphExec_t>& exs = it->second;
+            if (exs.size() == 1) {
+                HIPCHK(h, hipGraphLaunch(exs[0], h->stream));
+            } else {
+                rc = launch_chains(h, exs, nl >= 128);
+                if (rc) return rc;
+            }
+            h->st.launch_chains = (int)exs.size();
+            h->st.graph_used = 1;
+            done = true;
+        }
+    }
+    if (!done) enqueue_range(h->stream, 0, O, false);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+    h->st.pdhg_ms = ms;
+    h->st.launches = done ? nl * h->st.launch_chains + ((h->st.launch_chains > 1 && stag) ? 1 : 0) : nl;
+    *result_buf = (nl - 1) % 2 == 0 ? 0 : 1;   // launch 0 writes set 0, launch l writes set l % 2
+    return BPLTV_OK;
+}
+
+// bpltv_weighted_denoise(_device) on a single-device handle: w and the parameter from the host or (dev) from HBM.  The
+// order is the contract: arguments, params, w, then upload_alpha (shape, values, what the solve would reject) -- and only
+// then the handle's copy of w.
+int weighted_denoise_common(bpltv_t* h, const double* w, int wo, const double* alpha, bool dev, int am, int an,
+                            const bpltv_params* pp, double* u_out) {
+    const char* who = dev ? "bpltv_weighted_denoise_device" : "bpltv_weighted_denoise";
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!w) return set_err(h, BPLTV_E_ARG, "%s: w is a null pointer", who);
+    if (wo != 1 && wo != h->O) return set_err(h, BPLTV_E_ARG, "%s: wo = %d: one weight plane (1) or one per image (%d)", who, wo, h->O);
+    const bpltv_params p = resolve(pp);
+    if (int prc = weighted_check_params(h, p, who)) return prc;
+    WeightedPlan pl;
+    if (int prc = weighted_plan(h, p, &pl)) return prc;
+    const size_t nw = (size_t)wo * h->npx;
+    double wmin = 0.0;
+    int rc = check_weight(h, who, w, dev, nw, &wmin);
+    if (rc) return rc;
+    if (!h->d_w) {
+        rc = alloc_all(h, {{(void**)&h->d_w, h->tot * sizeof(double)}}, "fidelity weight");
+        if (rc) return rc;
+    }
+    bpltv_params q = p;   // the TV planner's knobs mean nothing here: upload_alpha's precheck sees the defaults
+    q.tile_iters = 0; q.reserved[0] = 0; q.reserved[1] = 0; q.reserved[2] = 0;
+    rc = upload_alpha(h, alpha, dev, am, an, PRE_TV, 1, &q);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_w, w, nw * sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    h->w_wo = wo;
+    h->w_min = wmin;
+    int buf = 0;
+    rc = run_weighted_pdhg(h, p, pl, &buf);
+    if (rc) return rc;
+    h->result_buf = buf;
+    h->has_result = true;
+    h->last_is_sr = false;
+    h->last_weighted = true;
+    if (u_out) {
+        HIPCHK(h, hipMemcpyAsync(u_out, h->d_state[buf][0], h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
+// Duality gap per image of the last weighted solve (gamma = min w > 0: the dual objective divides by w)
+int weighted_gap(bpltv_t* h, double* gap_host, double* gap_max_host) {
+    if (!(h->w_min > 0.0))
+        return set_err(h, BPLTV_E_UNSUPPORTED, "duality gap of a weighted solve: the dual objective divides by w, every entry must be > 0 (min = %g)", h->w_min);
+    h->has_per_image = false;
+    const int nblk = 8;
+    int rc = ensure(h, &h->d_red, &h->red_cap, (size_t)h->O * nblk * 4);
+    if (rc) return rc;
+    double* const* S = h->d_state[h->result_buf];
+    hipLaunchKernelGGL(weighted_gap_partial_kernel, dim3(nblk, h->O), dim3(256), 0, h->stream, S[0], S[1], S[2], h->d_f, h->d_w,
+                       h->w_wo > 1 ? h->npx : (size_t)0, h->d_alpha, h->last_am, h->last_an, h->M, h->N, h->d_red);
+    hipLaunchKernelGGL(weighted_gap_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, nblk, h->O, h->d_perimg, h->d_scalar);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(gap_host, h->d_perimg, sizeof(double) * h->O, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(gap_max_host, h->d_scalar, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BPLTV_OK;
+}
+
+// bpltv_weighted_vjp(_device) on a single-device handle: d_u, d_f (nullable unless d_grad_w), d_gu and the outputs live in
+// HBM; w and alpha on the host or (dev) in HBM.  Everything is checked before anything of the handle changes; the weight
+// and the parameter are staged in d_vjp = [4 check words | parameter | parameter gradient | w], apart from the last
+// solve's d_alpha and d_w.
+int weighted_vjp_common(bpltv_t* h, const double* d_u, const double* d_f, const double* w, int wo, const double* alpha, bool dev,
+                        int am, int an, const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alpha,
+                        double* d_grad_w) {
+    const char* who = "weighted_vjp";
+    if (!d_u || !w || !alpha || !d_gu) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
+    if (!d_grad_f && !d_grad_alpha && !d_grad_w) return set_err(h, BPLTV_E_ARG, "%s: all three outputs are NULL", who);
+    if (d_grad_w && !d_f) return set_err(h, BPLTV_E_ARG, "%s: grad_w = -(u - f) o p needs f", who);
+    if (wo != 1 && wo != h->O) return set_err(h, BPLTV_E_ARG, "%s: wo = %d: one weight plane (1) or one per image (%d)", who, wo, h->O);
+    if (am < 1 || an < 1 || am > h->M || an > h->N)
+        return set_err(h, BPLTV_E_ARG, "%s: parameter shape %dx%d (image %dx%d)", who, am, an, h->M, h->N);
+    const bpltv_params p = resolve(pp);
+    if (int prc = weighted_check_params(h, p, who)) return prc;
+    const size_t P = (size_t)am * an, nw = (size_t)wo * h->npx;
+    double amin = 0.0, wmin = 0.0;
+    if (!dev)
+        if (int crc = check_alpha_host(h, "weighted_vjp: alpha", alpha, P, &amin)) return crc;
+    int rc = check_weight(h, who, w, dev, nw, &wmin);
+    if (rc) return rc;
+    if (!(wmin > 0.0)) return set_err(h, BPLTV_E_ARG, "%s: the adjoint system scales with 1/sqrt(w): every weight must be > 0 (min = %g)", who, wmin);
+    rc = ensure(h, &h->d_vjp, &h->vjp_cap, 4 + 2 * P + nw);
+    if (rc) return rc;
+    unsigned long long* chk_d = reinterpret_cast<unsigned long long*>(h->d_vjp);
+    HIPCHK(h, hipMemsetAsync(chk_d, 0xFF, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(chk_d + 1, 0, 2 * sizeof(unsigned long long), h->stream));
+    if (dev)
+        hipLaunchKernelGGL(alpha_check_kernel, dim3((unsigned)std::min<size_t>((P + 255) / 256, 1024)), dim3(256), 0, h->stream, alpha, P, chk_d);
+    hipLaunchKernelGGL(finite_check_kernel, dim3((unsigned)std::min<size_t>((h->tot + 255) / 256, 1024)), dim3(256), 0, h->stream, d_gu,
+                       h->tot, chk_d + 2);
+    HIPCHK(h, hipGetLastError());
+    unsigned long long chk_h[3] = {0, 0, 0};
+    HIPCHK(h, hipMemcpyAsync(chk_h, chk_d, sizeof(chk_h), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (chk_h[1] != 0) return set_err(h, BPLTV_E_ARG, "%s: alpha (device array): parameters must be finite and >= 0", who);
+    if (chk_h[2] != 0) return set_err(h, BPLTV_E_ARG, "%s: the cotangent gu must be finite", who);
+    if (dev) std::memcpy(&amin, chk_h, sizeof(double));
+    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    double *d_a = h->d_vjp + 4, *d_wv = h->d_vjp + 4 + 2 * P;
+    HIPCHK(h, hipMemcpyAsync(d_a, alpha, P * sizeof(double), kind, h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_wv, w, nw * sizeof(double), kind, h->stream));
+    GradCtx g;
+    g.alpha = d_a; g.am = am; g.an = an; g.alpha_min = amin;
+    g.src = d_gu; g.cot = true;
+    g.d_out = d_grad_alpha; g.d_grad_f = d_grad_f;
+    g.w = d_wv; g.wo = wo; g.f = d_f; g.d_grad_w = d_grad_w;
+    h->has_per_image = false;
+    return run_gradient(h, d_u, g, 0, p);
+}
+
+// a weighted entry point on a multi-device handle: forwarded when one shard holds everything, unsupported otherwise
+template <class F>
+int weighted_multi(bpltv_t* h, const char* what, bool solve, F call) {
+    MultiState& ms = *h->multi;
+    if (ms.shard.size() != 1)
+        return set_err(h, BPLTV_E_UNSUPPORTED, "%s: the weighted model runs on single-device handles (this one has %zu shards)", what, ms.shard.size());
+    const int r = call(ms.shard[0]);
+    if (r) { h->err = ms.shard[0]->err; return r; }
+    if (solve) h->has_result = true; else h->has_per_image = false;
+    multi_stats(h);
+    return r;
+}
+
 }  // namespace
 
 // ============================================================================================
@@ -3194,7 +3519,7 @@ int bpltv_destroy(bpltv_t* h) {
     if (h->f32_sweep_alpha) (void)hipFree(h->f32_sweep_alpha);
     void* ptrs[] = {h->d_ubar, h->d_f, h->d_alpha, h->d_sweep_alpha, h->d_partial, h->d_red, h->d_perimg, h->d_scalar, h->d_coef,
                     h->d_band4, h->d_bcr, h->d_L, h->d_invF, h->d_invB, h->d_L1, h->d_dump, h->d_Lm, h->d_spill, h->d_p, h->d_r, h->d_gpix, h->d_resn, h->d_fail, h->d_u2, h->d_ubar2,
-                    h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres};
+                    h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres, h->d_w, h->d_wst};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (int s = 0; s < 2; ++s)
@@ -3366,6 +3691,78 @@ int bpltv_evaluate_device(bpltv_t* h, const double* alpha, int am, int an, doubl
     return evaluate_common(h, false, alpha, am, an, delta, p, nullptr, d_partial, nullptr);
 }
 
+int bpltv_weighted_denoise(bpltv_t* h, const double* w, int wo, const double* alpha, int am, int an, const bpltv_params* pp,
+                           double* u_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_weighted_denoise", true, [&](bpltv_t* c) { return bpltv_weighted_denoise(c, w, wo, alpha, am, an, pp, u_out); });
+    return weighted_denoise_common(h, w, wo, alpha, false, am, an, pp, u_out);
+}
+
+int bpltv_weighted_denoise_device(bpltv_t* h, const double* d_w, int wo, const double* d_alpha, int am, int an,
+                                  const bpltv_params* pp) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_weighted_denoise_device", true, [&](bpltv_t* c) { return bpltv_weighted_denoise_device(c, d_w, wo, d_alpha, am, an, pp); });
+    return weighted_denoise_common(h, d_w, wo, d_alpha, true, am, an, pp, nullptr);
+}
+
+int bpltv_weighted_vjp(bpltv_t* h, const double* u, const double* f, const double* w, int wo, const double* alpha, int am, int an,
+                       const bpltv_params* pp, const double* gu, double* grad_f_out, double* grad_alpha_out, double* grad_w_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_weighted_vjp", false, [&](bpltv_t* c) {
+            return bpltv_weighted_vjp(c, u, f, w, wo, alpha, am, an, pp, gu, grad_f_out, grad_alpha_out, grad_w_out);
+        });
+    if (!u || !gu || !w || !alpha) return set_err(h, BPLTV_E_ARG, "weighted_vjp: null pointer");
+    if (!grad_f_out && !grad_alpha_out && !grad_w_out) return set_err(h, BPLTV_E_ARG, "weighted_vjp: all three outputs are NULL");
+    if (grad_w_out && !f) return set_err(h, BPLTV_E_ARG, "weighted_vjp: grad_w = -(u - f) o p needs f");
+    if (wo != 1 && wo != h->O) return set_err(h, BPLTV_E_ARG, "weighted_vjp: wo = %d: one weight plane (1) or one per image (%d)", wo, h->O);
+    if (am < 1 || an < 1 || am > h->M || an > h->N)
+        return set_err(h, BPLTV_E_ARG, "weighted_vjp: parameter shape %dx%d (image %dx%d)", am, an, h->M, h->N);
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t tot = h->tot, P = (size_t)am * an, nw = (size_t)wo * h->npx;
+    if (!h->d_u2) {
+        HIPCHK(h, hipMalloc((void**)&h->d_u2, tot * sizeof(double)));
+        HIPCHK(h, hipMalloc((void**)&h->d_ubar2, tot * sizeof(double)));
+    }
+    if (grad_f_out && !h->d_gf2) HIPCHK(h, hipMalloc((void**)&h->d_gf2, tot * sizeof(double)));
+    if (grad_w_out && !h->d_wst) HIPCHK(h, hipMalloc((void**)&h->d_wst, 2 * tot * sizeof(double)));
+    HIPCHK(h, hipMemcpyAsync(h->d_u2, u, tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_ubar2, gu, tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (grad_w_out) HIPCHK(h, hipMemcpyAsync(h->d_wst, f, tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    int rc = ensure(h, &h->d_vjp, &h->vjp_cap, 4 + 2 * P + nw);
+    if (rc) return rc;
+    double* d_ga = grad_alpha_out ? h->d_vjp + 4 + P : nullptr;
+    double* d_gw = grad_w_out ? h->d_wst + tot : nullptr;
+    rc = weighted_vjp_common(h, h->d_u2, grad_w_out ? h->d_wst : nullptr, w, wo, alpha, false, am, an, pp, h->d_ubar2,
+                             grad_f_out ? h->d_gf2 : nullptr, d_ga, d_gw);
+    if (rc) return rc;
+    if (grad_f_out) HIPCHK(h, hipMemcpyAsync(grad_f_out, h->d_gf2, tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (grad_alpha_out) HIPCHK(h, hipMemcpyAsync(grad_alpha_out, d_ga, P * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (grad_w_out) HIPCHK(h, hipMemcpyAsync(grad_w_out, d_gw, nw * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
+int bpltv_weighted_vjp_device(bpltv_t* h, const double* d_u, const double* d_f, const double* d_w, int wo, const double* d_alpha,
+                              int am, int an, const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alpha,
+                              double* d_grad_w) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_weighted_vjp_device", false, [&](bpltv_t* c) {
+            return bpltv_weighted_vjp_device(c, d_u, d_f, d_w, wo, d_alpha, am, an, pp, d_gu, d_grad_f, d_grad_alpha, d_grad_w);
+        });
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int rc = weighted_vjp_common(h, d_u, d_f, d_w, wo, d_alpha, true, am, an, pp, d_gu, d_grad_f, d_grad_alpha, d_grad_w);
+    if (rc) return rc;
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
 int bpltv_u_device(bpltv_t* h, const double** d_u) {
     if (!h || !d_u) return BPLTV_E_ARG;
     if (h->multi)   // (no solve runs: nothing of the multi handle changes, its statistics included)
@@ -3398,6 +3795,12 @@ int bpltv_duality_gap(bpltv_t* h, double* gap_out) {
     HIPCHK(h, hipSetDevice(h->device));
     double gmax = 0.0;
     const bool sr = h->last_is_sr;
+    if (!sr && h->last_weighted) {   // the weighted model's own gap (BPLTV_E_UNSUPPORTED when min w = 0)
+        const int wrc = weighted_gap(h, gap_out, &gmax);
+        if (wrc) return wrc;
+        h->st.last_gap = gmax;
+        return BPLTV_OK;
+    }
     int rc = compute_gap(h, dataset_ctx(h, sr), sr, sr ? h->sr_result_buf : h->result_buf, gap_out, &gmax);
     if (rc) return rc;
     h->st.last_gap = gmax;

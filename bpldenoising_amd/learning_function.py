@@ -335,6 +335,72 @@ class TVSolver:
                                                int(bool(reg)), C.byref(p), C.c_void_p(gu_ptr),
                                                C.c_void_p(grad_f_ptr or None), C.c_void_p(grad_alpha_ptr or None)))
 
+    # -- per-pixel data-fidelity weight (bpltv_weighted_*) ------------------------------------------------------
+    def _weight(self, w):
+        """(array, wo) of a fidelity weight: (N, M) -- one plane for the batch -- or (O, N, M), one per image."""
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.shape == (self.N, self.M):
+            return w, 1
+        if w.shape == (self.O, self.N, self.M):
+            return w, self.O
+        raise ValueError("w has shape %s, expected (N=%d, M=%d) or (O=%d, N=%d, M=%d)"
+                         % (w.shape, self.N, self.M, self.O, self.N, self.M))
+
+    def weighted_denoise(self, x, w, fetch=True, **kw):
+        """min_u 0.5 sum w (u - f)^2 + sum alpha |grad u| on the resident f (bpltv_weighted_denoise).  x: as denoise;
+        w >= 0: (N, M) or (O, N, M).  w = 1 everywhere is denoise(x) bit for bit."""
+        a, am, an, _ = _alpha_arg(x)
+        wa, wo = self._weight(w)
+        p = self.params(**kw)
+        u = np.empty((self.O, self.N, self.M)) if fetch else None
+        self._check(self._lib.bpltv_weighted_denoise(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p),
+                                                     _ptr(u) if fetch else None))
+        return u
+
+    def weighted_denoise_device(self, w_ptr, wo, alpha_ptr, am=1, an=1, **kw):
+        """bpltv_weighted_denoise_device: w (wo planes of M*N doubles, wo = 1 or O) and the parameter (am x an doubles)
+        already resident in HBM; the result stays on the device (u_device_ptr / copy_u_device)."""
+        p = self.params(**kw)
+        self._check(self._lib.bpltv_weighted_denoise_device(self._h, C.c_void_p(w_ptr), int(wo), C.c_void_p(alpha_ptr),
+                                                            int(am), int(an), C.byref(p)))
+
+    def weighted_vjp(self, u, f, x, w, gu, want_f=True, want_alpha=True, want_w=True, **kw):
+        """Vector-Jacobian product of u = weighted_denoise(f, x, w) for the cotangent gu (bpltv_weighted_vjp):
+        (grad_f, grad_x, grad_w).  u, gu: (O, N, M); f: (O, N, M), or None when grad_w is not wanted; w > 0: (N, M) or
+        (O, N, M).  grad_w has the shape of w -- for (N, M) the sum over the images; an output not wanted is None."""
+        if not (want_f or want_alpha or want_w):
+            raise ValueError("weighted_vjp: want_f, want_alpha and want_w are all False")
+        a, am, an, scalar = _alpha_arg(x)
+        wa, wo = self._weight(w)
+        p = self.params(**kw)
+        u = self._batch(u, "u")
+        gu = self._batch(gu, "gu")
+        if want_w and f is None:
+            raise ValueError("weighted_vjp: grad_w needs f")
+        f = self._batch(f, "f") if f is not None else None
+        gf = np.empty((self.O, self.N, self.M)) if want_f else None
+        ga = np.empty(am * an) if want_alpha else None
+        gw = np.empty(wa.shape) if want_w else None
+        self._check(self._lib.bpltv_weighted_vjp(self._h, _ptr(u), _ptr(f) if f is not None else None, _ptr(wa), wo,
+                                                 _ptr(a), am, an, C.byref(p), _ptr(gu),
+                                                 _ptr(gf) if want_f else None, _ptr(ga) if want_alpha else None,
+                                                 _ptr(gw) if want_w else None))
+        if ga is not None:
+            ga = float(ga[0]) if scalar else ga.reshape(an, am)
+        return gf, ga, gw
+
+    def weighted_vjp_device(self, u_ptr, f_ptr, w_ptr, wo, alpha_ptr, am, an, gu_ptr, grad_f_ptr, grad_alpha_ptr,
+                            grad_w_ptr, **kw):
+        """bpltv_weighted_vjp_device: every array resident in HBM (raw device pointers); any output pointer may be
+        0 / None, not all three; f_ptr may be 0 / None only if grad_w_ptr is."""
+        p = self.params(**kw)
+        self._check(self._lib.bpltv_weighted_vjp_device(self._h, C.c_void_p(u_ptr), C.c_void_p(f_ptr or None),
+                                                        C.c_void_p(w_ptr), int(wo), C.c_void_p(alpha_ptr), int(am),
+                                                        int(an), C.byref(p), C.c_void_p(gu_ptr),
+                                                        C.c_void_p(grad_f_ptr or None),
+                                                        C.c_void_p(grad_alpha_ptr or None),
+                                                        C.c_void_p(grad_w_ptr or None)))
+
     # -- forward mode (bpltv_jvp / bpltv_gauss_newton) -------------------------------------------------------
     def _tangents(self, what, df, dalpha, ashape):
         """(df, dalpha, K, batched): the tangents as contiguous (K, ...) stacks, either None; batched = a leading K was

@@ -39,6 +39,14 @@ the same jvp through bpltv_sumregs_jvp_device / bpltv_sumregs_jvp_each_device (v
 same); their reg = 1 patch system is row-scaled, and the library solves with its transpose there, so the identity with
 backward holds in that branch too.
 
+    u = tv_denoise_weighted(f, alpha, w)                   # per-pixel data-fidelity weight (bpltv_weighted_*)
+
+min_u 0.5 sum w (u - f)^2 + sum alpha |grad u|: f and alpha as for tv_denoise, w a float64 tensor of shape (H, W) (one
+plane for the batch) or f's own shape (B, H, W), on f's device, w >= 0 (> 0 where a gradient is asked for).  backward is
+one bpltv_weighted_vjp_device call and returns f.grad, alpha.grad and w.grad (for an (H, W) weight the sum over the
+batch); the linearisation is tv_denoise's reg=False.  Like the sum-of-regularisers functions it carries no jvp:
+forward-mode AD over it raises torch's "not implemented" error.
+
 Streams: the library runs its kernels on its own HIP streams and blocks until they are done.  Every call below first
 synchronises the tensors' current torch stream, so that the library reads inputs torch has finished writing; its
 outputs are complete when the call returns.
@@ -451,3 +459,72 @@ class SumRegsDenoise(torch.nn.Module):
 
     def forward(self, f):
         return sumregs_denoise(f, self.alpha, reg=self.reg, forward_mode=self.forward_mode, **self.solver_kw)
+
+
+def _check_weight(f, w):
+    """wo (1 or B) of a valid weight for f; TypeError / ValueError before any library call."""
+    if not isinstance(w, torch.Tensor):
+        raise TypeError("tv_denoise_weighted: w must be a torch tensor")
+    if w.dtype != torch.float64:
+        raise TypeError("tv_denoise_weighted: w must be float64 (got %s)" % w.dtype)
+    H, W = f.shape[-2], f.shape[-1]
+    if tuple(w.shape) == (H, W):
+        wo = 1
+    elif f.dim() == 3 and tuple(w.shape) == tuple(f.shape):
+        wo = f.shape[0]
+    else:
+        raise ValueError("tv_denoise_weighted: w must have shape (%d, %d) or f's shape %s; got %s"
+                         % (H, W, tuple(f.shape), tuple(w.shape)))
+    if w.device != f.device:
+        raise ValueError("tv_denoise_weighted: w is on %s, f on %s" % (w.device, f.device))
+    return wo
+
+
+class TVDenoiseWeightedFunction(torch.autograd.Function):
+    """autograd.Function of tv_denoise_weighted (below); apply(f, alpha, w, solver_kw).  No jvp."""
+
+    @staticmethod
+    def forward(ctx, f, alpha, w, solver_kw):
+        if not isinstance(f, torch.Tensor) or f.dim() not in (2, 3) or f.numel() == 0:
+            _check_args(f, alpha)   # raises: f has no (H, W) to hold w against
+        wo = _check_weight(f, w)    # (in front of the device check: a CPU triple with a wrong w reports the w)
+        O, N, M, am, an = _check_args(f, alpha)
+        index = f.device.index if f.device.index is not None else torch.cuda.current_device()
+        s = _solver(index, M, N, O)
+        fc = f.detach().contiguous()
+        ac = alpha.detach().contiguous()
+        wc = w.detach().contiguous()
+        u = torch.empty_like(fc)
+        _sync(f.device)
+        s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
+        s.weighted_denoise_device(wc.data_ptr(), wo, ac.data_ptr(), am, an, **solver_kw)
+        s.copy_u_device(u.data_ptr())
+        ctx.save_for_backward(u, fc, ac, wc)
+        ctx.solver, ctx.am, ctx.an, ctx.wo, ctx.solver_kw = s, am, an, wo, dict(solver_kw)
+        return u
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gu):
+        need_f, need_a, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if not (need_f or need_a or need_w):
+            return None, None, None, None
+        u, f, alpha, w = ctx.saved_tensors
+        gu = gu.to(dtype=torch.float64).contiguous()
+        gf = torch.empty_like(u) if need_f else None
+        ga = torch.empty(ctx.am * ctx.an, dtype=torch.float64, device=u.device) if need_a else None
+        gw = torch.empty_like(w) if need_w else None
+        _sync(u.device)
+        ctx.solver.weighted_vjp_device(u.data_ptr(), f.data_ptr() if need_w else None, w.data_ptr(), ctx.wo,
+                                       alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(),
+                                       gf.data_ptr() if need_f else None, ga.data_ptr() if need_a else None,
+                                       gw.data_ptr() if need_w else None, **ctx.solver_kw)
+        return gf, (ga.reshape(alpha.shape) if need_a else None), gw, None
+
+
+def tv_denoise_weighted(f, alpha, w, **solver_kw):
+    """u = argmin 0.5 sum w (u - f)^2 + sum alpha |grad u| (TVSolver.weighted_denoise), differentiable in f, alpha and
+    w.  w: float64, (H, W) or f's shape (B, H, W), on f's device; w = 1 everywhere is tv_denoise(f, alpha) bit for bit,
+    in value and in f.grad / alpha.grad.  solver_kw: the solver parameters of TVSolver.params (rho, init and order must
+    stay 0), used by the forward solve and the adjoint alike."""
+    return TVDenoiseWeightedFunction.apply(f, alpha, w, solver_kw)

@@ -316,6 +316,48 @@ int bpltv_vjp_each(bpltv_t *h, const double *u, const double *alphas, int am, in
 int bpltv_vjp_each_device(bpltv_t *h, const double *d_u, const double *d_alphas, int am, int an, int reg,
                           const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alphas);
 
+/* Per-pixel data-fidelity weight: the TV model with the data term weighted pixel by pixel,
+ *     min_u 0.5 sum_ij w_ij (u_ij - f_ij)^2 + sum_ij alpha_ij |(grad u)_ij|,
+ * for masks (w in {0, 1}: the solve inpaints where w = 0), a known noise variance per pixel (w = 1 / sigma^2) or a learnable
+ * fidelity map.  The reference has no counterpart; its denoise is w == 1, and with w == 1 the result is
+ * bpltv_denoise's bit for bit.  f is the resident dataset (bpltv_set_data).  w: wo planes of M*N doubles in the layout of f,
+ * wo = 1 (one plane for every image) or wo = O (one per image), anything else BPLTV_E_ARG; every entry finite and >= 0.
+ * alpha, am, an: as bpltv_denoise.  The acceleration uses gamma = the smallest entry of ALL of w (gamma = 0, e.g. a mask: the
+ * unaccelerated iteration).  params: opnorm, tau0, sigma0, accel, maxiter, tile_iters and use_graph apply; rho, init and order
+ * must be 0 (BPLTV_E_UNSUPPORTED); check_every / gap_tol are ignored (always maxiter iterations, as the sweeps).  The solve runs
+ * in Float64 on dtype = 32 handles too.  w and alpha are checked (on the host) before anything of the handle changes: a rejected
+ * call leaves the last solve and bpltv_duality_gap as they were.  The solve becomes the handle's last solve: bpltv_u_device /
+ * bpltv_copy_u_device return its u, bpltv_duality_gap its gap
+ *     0.5 sum w (u - f)^2 + sum alpha |grad u| - sum (d f - d^2 / (2 w)),  d = grad^T y,   >= 0.5 sum w (u - u*)^2
+ * (BPLTV_E_UNSUPPORTED when gamma = 0: the dual objective divides by w).  A weighted and an unweighted solve on one handle never
+ * replay each other's captured graphs.  stats: iterations, launches, tile_iters, tiles, pdhg_ms, total_ms; bytes_per_px_iter = 64
+ * (scalar / patch parameter) or 72 (map); pdhg_variant = 0.  u_out: host, M*N*O doubles, or NULL.  Multi-device handles over
+ * more than one shard: BPLTV_E_UNSUPPORTED (all four functions). */
+int bpltv_weighted_denoise(bpltv_t *h, const double *w, int wo, const double *alpha, int am, int an,
+                           const bpltv_params *p, double *u_out);
+/* The same with w and the parameter already resident in HBM (device pointers) and the result left there (bpltv_u_device);
+ * both are checked on the device, before anything of the handle changes. */
+int bpltv_weighted_denoise_device(bpltv_t *h, const double *d_w, int wo, const double *d_alpha, int am, int an,
+                                  const bpltv_params *p);
+/* Vector-Jacobian product of u = weighted_denoise(f, alpha, w) for a cotangent gu = dL/du, in the reference's `gradient`
+ * linearisation (bpltv_vjp's reg = 0: active set |grad u| < 1e-12 with the kappa weight and its retry).  With
+ * A = diag(w) + K, K the matrix bpltv_vjp builds from (u, alpha), one solve A p = gu gives
+ *     grad_f_out = w o p,     grad_w_out = -(u - f) o p,     grad_alpha_out = bpltv_vjp's parameter gradient with this p.
+ * The system is solved in the node-scaled form (I + S K S) q = S gu, S = diag(w)^-1/2, p = S q, which needs every w > 0
+ * (BPLTV_E_ARG otherwise); with w == 1, grad_f_out and grad_alpha_out are bitwise bpltv_vjp's.  u, gu, grad_f_out: M*N*O
+ * doubles; w as above; grad_w_out: M*N*wo doubles, for wo = 1 the sum over the images in image order; alpha, grad_alpha_out:
+ * am*an doubles.  Any output may be NULL, not all three; f (M*N*O doubles) may be NULL only if grad_w_out is (BPLTV_E_ARG
+ * otherwise).  No dataset is needed.  gu must be finite.  Every rejection comes before anything of the handle changes; w and
+ * the parameter are staged apart, so the last solve, bpltv_u_device, bpltv_duality_gap and the captured graphs stay untouched,
+ * as with bpltv_vjp.  The residual gate, the image groups and the stats of the adjoint are bpltv_vjp's. */
+int bpltv_weighted_vjp(bpltv_t *h, const double *u, const double *f, const double *w, int wo, const double *alpha,
+                       int am, int an, const bpltv_params *p, const double *gu,
+                       double *grad_f_out, double *grad_alpha_out, double *grad_w_out);
+/* The same with every array in HBM (device pointers); w, the parameter and the cotangent are checked on the device. */
+int bpltv_weighted_vjp_device(bpltv_t *h, const double *d_u, const double *d_f, const double *d_w, int wo,
+                              const double *d_alpha, int am, int an, const bpltv_params *p, const double *d_gu,
+                              double *d_grad_f, double *d_grad_alpha, double *d_grad_w);
+
 /* Jacobian-vector product of u = denoise(f, alpha) (TV model): du for tangents (df, dalpha), defined as the linear map
  * whose transpose bpltv_vjp computes, in every branch -- <gu, du> = <grad_f(gu), df> + <grad_alpha(gu), dalpha> for any
  * gu -- so forward and reverse mode agree, also where the reference's linearisation is not the true one (reg = 1 with an

@@ -5,7 +5,7 @@
 # bpldenoising_amd/_lib.py (ctypes) by the test suite.
 # Same exports as src/TVLearningFunctionVec.jl:6
 export tv_op_learning_function, denoise, sumregs_learning_function, tv_vjp, sumregs_vjp, tv_jvp, tv_gauss_newton,
-       sumregs_jvp, sumregs_gauss_newton
+       sumregs_jvp, sumregs_gauss_newton, weighted_denoise, weighted_vjp
 
 const libbpltv = "libbpltv"            # on LD_LIBRARY_PATH, or an absolute path
 
@@ -199,6 +199,34 @@ function tv_vjp(h::BpltvHandle, u::Array{Float64,3}, α, ḡ::Array{Float64,3}; 
         (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Ref{BpltvParams}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
         h.ptr, u, a, am, an, reg ? 1 : 0, p, ḡ, gf, ga))
     return gf, α isa Real ? ga[1] : reshape(ga, size(α))
+end
+
+# Per-pixel data-fidelity weight (include/bpltv.h, bpltv_weighted_denoise): min_u 0.5 Σ w (u - f)^2 + Σ α |∇u| for a mask
+# (w ∈ {0, 1}: inpainting), a known noise variance per pixel (w = 1/σ^2) or a learnable fidelity map.  w >= 0: an M x N
+# matrix (one plane for every image) or an M x N x O array (one per image).  w = 1 everywhere is denoise(data, x, op).
+function weighted_denoise(data::Array{Float64,3}, x, w::Union{Matrix{Float64},Array{Float64,3}}; kwargs...)
+    h = handle_for(data, data)
+    a, am, an = alpha_arg(x)
+    wo = ndims(w) == 2 ? 1 : size(w, 3)
+    u = similar(data)
+    p = Ref(default_params(; kwargs...))
+    GC.@preserve w a u bpltv_check(h, ccall((:bpltv_weighted_denoise, libbpltv), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Cint, Ref{BpltvParams}, Ptr{Cdouble}), h.ptr, w, wo, a, am, an, p, u))
+    return u
+end
+
+# Its vector-Jacobian product (bpltv_weighted_vjp): (dL/df, dL/dα, dL/dw) from one adjoint solve of (diag(w) + K) p = ḡ, in the
+# `gradient` linearisation; dL/dw has the shape of w (an M x N weight: summed over the images).  Every w must be > 0.
+function weighted_vjp(h::BpltvHandle, u::Array{Float64,3}, f::Array{Float64,3}, α, w::Union{Matrix{Float64},Array{Float64,3}},
+                      ḡ::Array{Float64,3}; kwargs...)
+    a, am, an = alpha_arg(α)
+    wo = ndims(w) == 2 ? 1 : size(w, 3)
+    gf = similar(u); ga = zeros(am, an); gw = similar(w)
+    p = Ref(default_params(; kwargs...))
+    GC.@preserve u f w a ḡ gf ga gw bpltv_check(h, ccall((:bpltv_weighted_vjp, libbpltv), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Cint, Ref{BpltvParams}, Ptr{Cdouble},
+         Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}), h.ptr, u, f, w, wo, a, am, an, p, ḡ, gf, ga, gw))
+    return gf, (α isa Real ? ga[1] : reshape(ga, size(α))), gw
 end
 
 # Jacobian-vector product of u = denoise(f, α) (include/bpltv.h, bpltv_jvp): du for the tangents (df, dα), the linear map
