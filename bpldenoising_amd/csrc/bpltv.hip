@@ -9,6 +9,7 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <initializer_list>
 #include <map>
 #include <memory>
@@ -182,20 +183,46 @@ const Variant kVariants[] = {
     //  8 x 1024^2 as well: none beats variant 13)
 };
 
+// The models whose solves the shared launch driver (run_chains) runs
+enum Model { MODEL_TV = 0, MODEL_SR = 1, MODEL_W = 2, NMODELS = 3 };
+
+// What identifies a launch sequence built into graphs: everything its kernel arguments and its cut into launches depend
+// on.  One key type for the three models (a field a model does not use stays 0); each model has a cache of its own
+// (bpltv_handle::graphs), so a weighted and an unweighted solve never replay each other's graphs.
 struct GraphKey {
     int maxiter, T, variant, am, an, chains;
     double rho, tau0, sigma0;
     int accel, dbg, nimg;
-    const void* state;
-    const void* tab;   // step table (one per (maxiter, steps, L, dual-first shift): TabKey)
+    const void* state; // state set 0 of the solve context: a sweep never replays a dataset-context graph, nor the reverse
+    const void* tab;   // step table (one per (maxiter, steps, L, dual-first shift, gamma): TabKey)
     int from_state;    // 1: the sequence starts from a prepared state (params.init / order), not from x = f, y = 0
     const void* alpha; // the parameter the launches read: a sweep's blocks and the dataset's parameter are different
                        // buffers, while a float handle's state (f32_state) is the same for both contexts
-    int istride;       // PdhgArgs::istride: a shared parameter and one block per image (bpltv_denoise_each) live in the
-                       // same buffer, d_alpha
+    int istride;       // doubles between per-image parameter blocks (bpltv_denoise_each, bpltv_sumregs_denoise_each: they live
+                       // in d_alpha like a shared parameter, and run other kernel arguments / instances)
+    int wo;            // weighted model: weight planes (d_w, d_f and the state sets are fixed for the life of the handle)
     bool operator<(const GraphKey& o) const {
-        return std::tie(maxiter, T, variant, am, an, chains, rho, tau0, sigma0, accel, dbg, nimg, state, tab, from_state, alpha, istride) <
-               std::tie(o.maxiter, o.T, o.variant, o.am, o.an, o.chains, o.rho, o.tau0, o.sigma0, o.accel, o.dbg, o.nimg, o.state, o.tab, o.from_state, o.alpha, o.istride);
+        return std::tie(maxiter, T, variant, am, an, chains, rho, tau0, sigma0, accel, dbg, nimg, state, tab, from_state, alpha, istride, wo) <
+               std::tie(o.maxiter, o.T, o.variant, o.am, o.an, o.chains, o.rho, o.tau0, o.sigma0, o.accel, o.dbg, o.nimg, o.state, o.tab, o.from_state, o.alpha, o.istride, o.wo);
+    }
+};
+
+// Bounded cache of instantiated launch sequences, one hipGraphExec_t per launch chain.  A full cache is emptied.
+struct GraphCache {
+    size_t bound = 8;
+    std::map<GraphKey, std::vector<hipGraphExec_t>> map;
+    const std::vector<hipGraphExec_t>* find(const GraphKey& k) const {
+        const auto it = map.find(k);
+        return it == map.end() ? nullptr : &it->second;
+    }
+    void make_room() {   // on a miss, before the new sequence is built
+        if (map.size() >= bound) drop();
+    }
+    const std::vector<hipGraphExec_t>* insert(const GraphKey& k, std::vector<hipGraphExec_t> ex) { return &(map[k] = std::move(ex)); }
+    void drop() {
+        for (auto& kv : map)
+            for (auto e : kv.second) (void)hipGraphExecDestroy(e);
+        map.clear();
     }
 };
 
@@ -209,32 +236,6 @@ struct TabKey {
     double gamma = 1.0;   // strong convexity of the data term the acceleration uses: 1, or min w of a weighted solve
     bool operator<(const TabKey& o) const {
         return std::tie(maxiter, accel, tau0, sigma0, L, shift, gamma) < std::tie(o.maxiter, o.accel, o.tau0, o.sigma0, o.L, o.shift, o.gamma);
-    }
-};
-
-// Captured launch sequence of a weighted solve (run_weighted_pdhg).  A cache of its own: a weighted and an unweighted
-// solve never replay each other's graphs.  d_w, d_f and the state sets are fixed for the life of the handle.
-struct WGraphKey {
-    int maxiter, T, am, an, wo, chains;
-    const void* tab;     // one table per (maxiter, steps, L, gamma): TabKey
-    const void* alpha;
-    bool operator<(const WGraphKey& o) const {
-        return std::tie(maxiter, T, am, an, wo, chains, tab, alpha) < std::tie(o.maxiter, o.T, o.am, o.an, o.wo, o.chains, o.tab, o.alpha);
-    }
-};
-
-struct SrGraphKey {
-    int maxiter, T, am, an, accel, variant;
-    double rho, tau0, sigma0;
-    const void* tab;
-    int nimg;              // problems of the solve context (the dataset's O, or a sweep group's K_g * O)
-    const void* state;     // its state set and parameter buffer: a sweep never replays a dataset-context graph, nor the reverse
-    const void* alpha;
-    int istride;           // 0: one parameter block; 3*am*an: one block per image (bpltv_sumregs_denoise_each) -- both live in
-                           // d_alpha, and the two modes run different kernel instances
-    bool operator<(const SrGraphKey& o) const {
-        return std::tie(maxiter, T, am, an, accel, variant, rho, tau0, sigma0, tab, nimg, state, alpha, istride) <
-               std::tie(o.maxiter, o.T, o.am, o.an, o.accel, o.variant, o.rho, o.tau0, o.sigma0, o.tab, o.nimg, o.state, o.alpha, o.istride);
     }
 };
 
@@ -360,7 +361,7 @@ struct bpltv_handle {
     size_t f32_alpha_cap = 0, f32_sweep_alpha_cap = 0;
     bool f32_f_valid = false;
     std::map<TabKey, float*> tabs32;
-    std::map<GraphKey, std::vector<hipGraphExec_t>> graphs;  // one exec per chain
+    GraphCache graphs[NMODELS] = {{16}, {8}, {8}};   // by Model: at most 16 TV sequences, 8 of each other model
     std::vector<hipStream_t> chain_streams;   // the device's (DeviceStreams), not owned
     std::vector<hipEvent_t> chain_events;
     unsigned* d_phase = nullptr;              // the word chain 0's launches rewrite (PDHG_PHASE_STAMP, pdhg_phase_gate_kernel)
@@ -412,14 +413,12 @@ struct bpltv_handle {
     NdSolver nd_sr_lu;            // ... the same system by nested dissection (LU variant; the default)
     bool lu_sr_ready = false;
     double* d_srdiagU = nullptr;  // its upper diagonals (7 planes)
-    std::map<SrGraphKey, std::vector<hipGraphExec_t>> sr_graphs;   // one graph per launch chain
     // per-pixel fidelity weight (weighted_kernels.hpp): the handle's copy of the last weighted solve's w (wo planes, gamma =
     // its smallest entry), allocated on first use and never moved; the solve runs in d_state
     double* d_w = nullptr;
     int w_wo = 1;
     double w_min = 0.0;
     bool last_weighted = false;                     // the last solve was bpltv_weighted_denoise: u and the gap are its
-    std::map<WGraphKey, std::vector<hipGraphExec_t>> w_graphs;   // one graph per launch chain
     double* d_wst = nullptr;                        // bpltv_weighted_vjp's host staging [f | grad_w], 2 * M*N*O doubles
     bpltv_stats_t st;
     std::string err;
@@ -530,7 +529,15 @@ void cvt_to_f64(bpltv_t* h, const float* src, double* dst, size_t n) {
     const unsigned nb = (unsigned)std::min<size_t>((n + 255) / 256, 65535);
     hipLaunchKernelGGL(cvt_f32_f64_kernel, dim3(nb), dim3(256), 0, h->stream, src, dst, n);
 }
-void drop_graphs(bpltv_t* h);
+// Destroy the cached launch sequences of the models in `which` (DROP_* bits).  A graph holds the pointers its kernel
+// arguments carried when it was built, so whatever frees or moves one of them drops the graphs that can hold it:
+//   d_alpha grows (upload_alpha)                                          every model: all three read it
+//   the float twins grow (f32_prepare: f32_state, f32_alpha, f32_sweep_alpha)   TV: only its kernels have a float form
+//   the TV sweep's state sets or parameter blocks grow (bpltv_sweep)      TV
+//   the sum-of-regularisers sweep's planes or blocks grow (bpltv_sumregs_sweep)   sum of regularisers
+// d_f, d_w, the dataset state sets (d_state, d_sr) and the step tables live as long as the handle.
+enum { DROP_TV = 1 << MODEL_TV, DROP_SR = 1 << MODEL_SR, DROP_W = 1 << MODEL_W, DROP_ALL = DROP_TV | DROP_SR | DROP_W };
+void drop_graphs(bpltv_t* h, int which);
 // step table rounded to float (the oracle's bplo_pdhg_f32 rounds the same f64 table)
 int get_table32(bpltv_t* h, const bpltv_params& p, float** out) {
     TabKey k{p.maxiter, p.accel ? 1 : 0, p.tau0, p.sigma0, opnorm_of(p, 8.0), 0};
@@ -577,7 +584,7 @@ SolveCtx dataset_ctx(bpltv_t* h, bool sr) {
 // buffers for the solve context (x.nimg images) and fresh float copies of f and of the parameter
 int f32_prepare(bpltv_t* h, const SolveCtx& x) {
     if (h->f32_state_cap < (size_t)x.nimg) {
-        drop_graphs(h);   // captured kernels hold the old pointers
+        drop_graphs(h, DROP_TV);   // graph nodes hold the old pointers
         for (int s = 0; s < 2; ++s)
             for (int c = 0; c < 3; ++c) {
                 if (h->f32_state[s][c]) HIPCHK(h, hipFree(h->f32_state[s][c]));
@@ -596,7 +603,7 @@ int f32_prepare(bpltv_t* h, const SolveCtx& x) {
     size_t& cap32 = x.sweep ? h->f32_sweep_alpha_cap : h->f32_alpha_cap;
     const size_t cap = x.sweep ? h->sweep_alpha_cap : h->alpha_cap;
     if (cap32 < cap) {
-        drop_graphs(h);
+        drop_graphs(h, DROP_TV);
         if (a32) HIPCHK(h, hipFree(a32));
         a32 = nullptr;
         cap32 = 0;
@@ -623,16 +630,9 @@ int f32_widen(bpltv_t* h, const SolveCtx& x, int buf) {
     return BPLTV_OK;
 }
 
-void drop_w_graphs(bpltv_t* h) {
-    for (auto& kv : h->w_graphs)
-        for (auto e : kv.second) (void)hipGraphExecDestroy(e);
-    h->w_graphs.clear();
-}
-void drop_graphs(bpltv_t* h) {
-    for (auto& kv : h->graphs)
-        for (auto e : kv.second) (void)hipGraphExecDestroy(e);
-    h->graphs.clear();
-    drop_w_graphs(h);   // they hold d_alpha as well
+void drop_graphs(bpltv_t* h, int which) {
+    for (int m = 0; m < NMODELS; ++m)
+        if (which & (1 << m)) h->graphs[m].drop();
 }
 
 int solve_precheck(bpltv_t* h, const bpltv_params& p, double amin, int what);
@@ -643,8 +643,6 @@ inline int pre_gradient(double delta, const bpltv_params& p, int am, int an) {
     const int reg = !(delta > p.delta_t);   // as evaluate_common
     return PRE_GRADIENT | ((reg && !(am == 1 && an == 1)) ? PRE_REG_ARRAY : 0);
 }
-
-void drop_sr_graphs(bpltv_t* h);
 
 // The host-side parameter check of every entry point: n entries, finite and >= 0; *amin receives the smallest.  `name`
 // is what the message calls the array ("alpha", "sweep: alphas", ...).
@@ -657,6 +655,34 @@ int check_alpha_host(bpltv_t* h, const char* name, const double* a, size_t n, do
             return set_err(h, BPLTV_E_ARG, "%s[%zu] = %g: parameters must be finite and >= 0", name, e, a[e]);
         if (a[e] < *amin) *amin = a[e];
     }
+    return BPLTV_OK;
+}
+
+// The checks of arrays that live in HBM, one read-back and one synchronisation for all of them: `par` (n entries, nullable:
+// no such check) must be finite and >= 0 (alpha_check_kernel; *pmin receives its smallest entry), every array of `fin`
+// (nullable entries are skipped, at most two) must be finite (finite_check_kernel).  chk: 2 + fin.size() words in HBM --
+// [0] the smallest entry of `par` (bits), [1] `par` rejected, [2 + j] fin[j] not finite.  *failed: -1 when everything
+// passed, else the first job that did not (0: par, 1 + j: fin[j]) -- the caller words the message.  Reads only.
+struct DevArray { const double* p; size_t n; const char* name = nullptr; };   // name: what a message calls it ("cotangent gu")
+int check_device_arrays(bpltv_t* h, unsigned long long* chk, DevArray par, std::initializer_list<DevArray> fin, double* pmin, int* failed) {
+    auto blocks = [](size_t n) { return dim3((unsigned)std::min<size_t>((n + 255) / 256, 1024)); };
+    unsigned long long chk_h[4] = {0, 0, 0, 0};
+    const size_t nw = 2 + fin.size();
+    HIPCHK(h, hipMemsetAsync(chk, 0xFF, sizeof(unsigned long long), h->stream));
+    HIPCHK(h, hipMemsetAsync(chk + 1, 0, (nw - 1) * sizeof(unsigned long long), h->stream));
+    if (par.p) hipLaunchKernelGGL(alpha_check_kernel, blocks(par.n), dim3(256), 0, h->stream, par.p, par.n, chk);
+    unsigned long long* word = chk + 2;
+    for (const DevArray& a : fin) {
+        if (a.p) hipLaunchKernelGGL(finite_check_kernel, blocks(a.n), dim3(256), 0, h->stream, a.p, a.n, word);
+        ++word;
+    }
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(chk_h, chk, nw * sizeof(unsigned long long), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    *failed = -1;
+    for (size_t j = nw; j-- > 1;)
+        if (chk_h[j] != 0) *failed = (int)j - 1;
+    if (par.p) std::memcpy(pmin, chk_h, sizeof(double));
     return BPLTV_OK;
 }
 
@@ -678,16 +704,9 @@ int upload_alpha(bpltv_t* h, const double* alpha, bool on_device, int am, int an
     const size_t need = (size_t)(sr ? 3 : 1) * blocks * am * an;
     double amin = 0.0;
     if (on_device) {
-        unsigned long long* chk_d = reinterpret_cast<unsigned long long*>(h->d_scalar + 2);
-        HIPCHK(h, hipMemsetAsync(chk_d, 0xFF, sizeof(unsigned long long), h->stream));
-        HIPCHK(h, hipMemsetAsync(chk_d + 1, 0, sizeof(unsigned long long), h->stream));
-        hipLaunchKernelGGL(alpha_check_kernel, dim3((unsigned)std::min<size_t>((need + 255) / 256, 1024)), dim3(256), 0, h->stream, alpha, need, chk_d);
-        HIPCHK(h, hipGetLastError());
-        unsigned long long chk_h[2] = {0, 1};
-        HIPCHK(h, hipMemcpyAsync(chk_h, chk_d, sizeof(chk_h), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        if (chk_h[1] != 0) return set_err(h, BPLTV_E_ARG, "alpha (device array): parameters must be finite and >= 0");
-        std::memcpy(&amin, chk_h, sizeof(double));
+        int failed = -1;
+        if (int rc = check_device_arrays(h, reinterpret_cast<unsigned long long*>(h->d_scalar + 2), {alpha, need}, {}, &amin, &failed)) return rc;
+        if (failed == 0) return set_err(h, BPLTV_E_ARG, "alpha (device array): parameters must be finite and >= 0");
     } else if (int rc = check_alpha_host(h, "alpha", alpha, need, &amin)) {
         return rc;
     }
@@ -695,8 +714,7 @@ int upload_alpha(bpltv_t* h, const double* alpha, bool on_device, int am, int an
         if (int rc = solve_precheck(h, *solve, amin, what)) return rc;
     h->alpha_min = amin;
     if (h->alpha_cap < need) {
-        drop_graphs(h);  // captured kernels hold the old pointer
-        drop_sr_graphs(h);   // ... of either model: both keys hold it, so this only frees graphs no key can reach again
+        drop_graphs(h, DROP_ALL);   // every model's launches read d_alpha
         int rc = ensure(h, &h->d_alpha, &h->alpha_cap, need);
         if (rc) return rc;
     }
@@ -836,10 +854,13 @@ int build_graphs(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, const Pla
     return rc;
 }
 
-// Enqueue PDHG iterations [it0, it1) on the stream.  *buf: state set holding the current iterate
-// (ignored when it0 == 0), updated to the set holding the result.
-int enqueue_pdhg(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, const Plan& pl, const double* d_tab, int it0, int it1,
-                 int* buf, int* launches, bool from_state = false) {
+// Launch the TV iterations [it0, it1) of the images [lo, hi) on stream st, from the state set `cur` (ignored when it0 == 0
+// and the sequence starts from x = f, y = 0); returns the set holding the result.  stagger: the first launch fuses T/2
+// iterations and writes set 1 (an out-of-phase chain, build_graphs).  The signature is the one run_chains asks of every
+// model; TV's graphs come from build_graphs, so the driver only calls this with (lo, hi, stagger) = (0, nimg, false) -- the
+// eager path and the check_every chunks -- and the image-range and stagger branches below are not taken today.
+int enqueue_pdhg(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, const Plan& pl, const double* d_tab, bool from_state,
+                 hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
     const Variant& V = kVariants[pl.variant];
     PdhgArgs a;
     a.f = pdhg_f(h);
@@ -851,51 +872,51 @@ int enqueue_pdhg(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, const Pla
     a.M = h->M; a.N = h->N; a.O = x.nimg;
     a.Odata = h->O; a.astride = x.astride; a.istride = x.istride;
     a.nTi = pl.nTi; a.nTj = pl.nTj; a.halo = pl.T; a.seg = V.RJ;
-    a.img0 = 0;
-    a.ntiles = pl.grid;
+    a.img0 = lo;
+    a.ntiles = pl.nTi * pl.nTj * (hi - lo);
     a.xcd = (p.reserved[2] & 2) ? 1 : 0;
-    a.grid3d = a.xcd ? 0 : pdhg_grid3d_ok(pl.nTj, x.nimg, V.tiles_per_block);
+    a.grid3d = a.xcd ? 0 : pdhg_grid3d_ok(pl.nTj, hi - lo, V.tiles_per_block);
 #ifdef BPLTV_EXPERIMENTS
     a.dbg = p.reserved[3];
     a.dbg_row[0] = p.tau0; a.dbg_row[1] = p.sigma0; a.dbg_row[2] = 1.0; a.dbg_row[3] = 1.0 / (1.0 + p.tau0); a.dbg_row[4] = 2.0;
 #endif
-    int cur = *buf;
-    for (int it = it0; it < it1; it += pl.T) {
-        const int nit = std::min(pl.T, it1 - it);
-        const int nxt = (it == 0) ? 0 : 1 - cur;
+    int step = stagger ? pl.T / 2 : pl.T;
+    for (int it = it0; it < it1; it += step, step = pl.T) {
+        const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
         a.first = (it == 0 && !from_state) ? 1 : 0;
         a.xin = pdhg_state(h, x, cur, 0); a.y1in = pdhg_state(h, x, cur, 1); a.y2in = pdhg_state(h, x, cur, 2);
         a.xout = pdhg_state(h, x, nxt, 0); a.y1out = pdhg_state(h, x, nxt, 1); a.y2out = pdhg_state(h, x, nxt, 2);
         a.it0 = it;
-        a.nit = nit;
-        (h->dtype == 32 ? V.launch32 : V.launch)(a, pl.grid, h->stream);
+        a.nit = std::min(step, it1 - it);
+        (h->dtype == 32 ? V.launch32 : V.launch)(a, a.ntiles, st);
         cur = nxt;
-        ++*launches;
     }
-    HIPCHK(h, hipGetLastError());
-    *buf = cur;
-    return BPLTV_OK;
+    return cur;
 }
 
 // Duality gap per image of the iterate in state set `buf` of the dataset context x (the gap kernels address the O dataset
-// images only, which is why the sweeps switch check_every off).  sr: the three-dual model, seven state planes.
-int compute_gap(bpltv_t* h, const SolveCtx& x, bool sr, int buf, double* gap_host /*O or null*/, double* gap_max_host) {
+// images only, which is why the sweeps switch check_every off).  MODEL_SR: the three-dual model, seven state planes;
+// MODEL_W: the handle's weight d_w, every entry > 0 (the dual objective divides by w: the caller checks w_min).
+int compute_gap(bpltv_t* h, const SolveCtx& x, Model model, int buf, double* gap_host /*O or null*/, double* gap_max_host) {
     h->has_per_image = false;   // d_perimg is about to hold the gaps
     const int nblk = 8;
     int rc = ensure(h, &h->d_red, &h->red_cap, (size_t)h->O * nblk * 4);
     if (rc) return rc;
     double* const* S = x.state[buf];
-    if (sr) {
+    if (model == MODEL_SR) {
         SrState Ss;
         for (int c = 0; c < 7; ++c) Ss.pl[c] = S[c];
         hipLaunchKernelGGL(sr_gap_partial_kernel, dim3(nblk, h->O), dim3(256), 0, h->stream, Ss, h->d_f, x.alpha, x.am, x.an, h->M,
                            h->N, x.istride, h->d_red);
+    } else if (model == MODEL_W) {
+        hipLaunchKernelGGL(weighted_gap_partial_kernel, dim3(nblk, h->O), dim3(256), 0, h->stream, S[0], S[1], S[2], h->d_f, h->d_w,
+                           h->w_wo > 1 ? h->npx : (size_t)0, x.alpha, x.am, x.an, h->M, h->N, h->d_red);
     } else {
         hipLaunchKernelGGL(gap_partial_kernel, dim3(nblk, h->O), dim3(256), 0, h->stream, S[0], S[1], S[2], h->d_f, x.alpha, x.am,
                            x.an, h->M, h->N, x.istride, h->d_red);
     }
-    hipLaunchKernelGGL(gap_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, nblk, h->O, h->d_perimg,
-                       h->d_scalar);
+    auto final_kernel = model == MODEL_W ? &weighted_gap_final_kernel : &gap_final_kernel;
+    hipLaunchKernelGGL(final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, nblk, h->O, h->d_perimg, h->d_scalar);
     HIPCHK(h, hipGetLastError());
     if (gap_host)
         HIPCHK(h, hipMemcpyAsync(gap_host, h->d_perimg, sizeof(double) * h->O, hipMemcpyDeviceToHost, h->stream));
@@ -968,6 +989,145 @@ int launch_chains(bpltv_t* h, const std::vector<hipGraphExec_t>& ex, bool thread
     return BPLTV_OK;
 }
 
+// ---- the launch driver shared by the three models ------------------------------------------------------------------------
+// One solve = niter iterations cut into launches of T, for `nimg` problems in `chains` image groups.  A model plans (region,
+// T, chains), prepares its step table and describes the rest in a ChainSolve; run_chains turns that into launches.
+using EnqueueFn = std::function<int(hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger)>;
+struct ChainSolve {
+    Model model = MODEL_TV;
+    int nplanes = 3;             // planes of a state set
+    double* const* state0 = nullptr;   // state set 0 (maxiter == 0 writes it)
+    int nimg = 0, niter = 0, T = 1, chains = 1;
+    bool from_state = false;     // TV: the sequence starts from the prepared state in set 1 (`begin` writes it)
+    bool x0_zero = false;        // TV, params.init: maxiter == 0 leaves x = 0, not x = f
+    bool serial = false;         // replay the chains one after the other on the handle's stream (TV, reserved[2] & 1)
+    bool helper_thread = true;   // long sequences launch chain 1 from the handle's launcher thread (launch_chains)
+    double bytes_per_px_iter = 0.0;
+    GraphKey key{};
+    // launch the iterations [it0, it1) of the images [lo, hi) on st from the state set cur; returns the set holding the
+    // result.  stagger: the first launch fuses T/2 iterations and writes set 1
+    EnqueueFn enqueue;
+    // optional: one graph per chain by other means than a stream capture of `enqueue` (TV: build_graphs)
+    std::function<int(std::vector<hipGraphExec_t>*)> build;
+    // optional: the largest duality gap of the iterate in set buf -- enables params.check_every / gap_tol
+    std::function<int(int buf, double* gmax)> gap;
+    // optional: what the timed span holds besides the launches -- in front (TV: pdhg_init_kernel), and behind, with the set
+    // holding the result and the iterations done, which it may raise (TV: widening of a float result, closing primal step)
+    std::function<int()> begin;
+    std::function<int(int buf, int* iterations)> end;
+};
+
+// One graph per chain by stream capture of j.enqueue on the handle's capture stream.  Odd chains run half a launch out of
+// phase when `out_of_phase` (chain_out_of_phase).  All or nothing: on any failure *out stays empty.
+void capture_graphs(bpltv_t* h, const ChainSolve& j, bool out_of_phase, std::vector<hipGraphExec_t>* out) {
+    for (int c = 0; c < j.chains; ++c) {
+        const int lo = (int)(((long)j.nimg * c) / j.chains), hi = (int)(((long)j.nimg * (c + 1)) / j.chains);
+        hipGraph_t g = nullptr;
+        hipGraphExec_t ex = nullptr;
+        if (!h->capture_stream && hipStreamCreateWithFlags(&h->capture_stream, hipStreamNonBlocking) != hipSuccess) { h->capture_stream = nullptr; break; }
+        if (hipStreamBeginCapture(h->capture_stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
+            (void)j.enqueue(h->capture_stream, 0, j.niter, 0, lo, hi, (c & 1) && out_of_phase);
+            if (hipStreamEndCapture(h->capture_stream, &g) == hipSuccess && g && hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) == hipSuccess)
+                out->push_back(ex);
+            if (g) (void)hipGraphDestroy(g);
+        }
+    }
+    if ((int)out->size() != j.chains) {
+        for (auto e : *out) (void)hipGraphExecDestroy(e);
+        out->clear();
+    }
+}
+
+// Run the solve j: statistics, maxiter == 0, then either the chunks of params.check_every with a gap check after each, or
+// the whole sequence -- replayed from the model's graph cache (built on a miss: j.build or capture_graphs; sequences of
+// more than 50000 launches and failed or partial builds are launched eagerly), the chains side by side (launch_chains).  The event
+// pair ev[0] / ev[1] brackets everything.  *result_buf: the state set that holds the result (written on success only).
+int run_chains(bpltv_t* h, const bpltv_params& p, const ChainSolve& j, int* result_buf) {
+    h->st.launches = 0; h->st.iterations = 0; h->st.graph_used = 0; h->st.last_gap = -1.0; h->st.launch_chains = 1;
+    h->st.launch_host_ms[0] = h->st.launch_host_ms[1] = 0.0;
+    h->st.pdhg_ms = 0.0;
+    h->st.bytes_per_px_iter = j.bytes_per_px_iter;
+    h->st.algorithmic_bytes = 0.0;
+    if (p.maxiter == 0) {   // u = x0 = f for every parameter block (x0_zero: 0), y = 0
+        for (int c = 0; c < j.nplanes; ++c) {
+            if (c == 0 && !j.x0_zero) {
+                for (int r = 0; r < j.nimg / h->O; ++r)
+                    HIPCHK(h, hipMemcpyAsync(j.state0[0] + (size_t)r * h->tot, h->d_f, h->tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+            } else {
+                HIPCHK(h, hipMemsetAsync(j.state0[c], 0, (size_t)j.nimg * h->npx * sizeof(double), h->stream));
+            }
+        }
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        *result_buf = 0;
+        return BPLTV_OK;
+    }
+    const int nl = (j.niter + j.T - 1) / j.T;
+    int buf = j.from_state ? 1 : 0, launches = 0, iterations = j.niter;
+    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
+    if (j.begin)
+        if (int rc = j.begin()) return rc;
+    if (p.check_every > 0 && j.gap) {
+        int it = 0;
+        while (it < j.niter) {
+            const int it1 = std::min(j.niter, it + p.check_every);
+            buf = j.enqueue(h->stream, it, it1, buf, 0, j.nimg, false);
+            HIPCHK(h, hipGetLastError());
+            launches += (it1 - it + j.T - 1) / j.T;
+            it = it1;
+            double gmax = 0.0;
+            if (int rc = j.gap(buf, &gmax)) return rc;   // of the set this chunk just wrote
+            h->st.last_gap = gmax;
+            if (p.gap_tol > 0.0 && gmax <= p.gap_tol) break;
+        }
+        iterations = it;
+    } else if (j.niter > 0) {
+        const std::vector<hipGraphExec_t>* ex = nullptr;
+        const bool oop = chain_out_of_phase(j.niter, j.T, j.from_state);
+        if (p.use_graph) {
+            GraphCache& cache = h->graphs[j.model];
+            ex = cache.find(j.key);
+            if (!ex && nl <= 50000) {
+                cache.make_room();
+                std::vector<hipGraphExec_t> built;
+                const int brc = j.build ? j.build(&built) : (capture_graphs(h, j, oop, &built), (int)BPLTV_OK);
+                (void)hipGetLastError();
+                if (brc == BPLTV_OK && (int)built.size() == j.chains) {
+                    ex = cache.insert(j.key, std::move(built));
+                } else {   // a failed or partial build: nothing of it is kept, the sequence is launched eagerly
+                    for (auto e : built) (void)hipGraphExecDestroy(e);
+                }
+            }
+        }
+        if (ex) {
+            if (ex->size() == 1 || j.serial) {
+                for (hipGraphExec_t e : *ex) HIPCHK(h, hipGraphLaunch(e, h->stream));
+            } else if (int rc = launch_chains(h, *ex, nl >= 128 && j.helper_thread)) {   // short sequences: a helper thread costs more than it hides
+                return rc;
+            }
+            h->st.launch_chains = (int)ex->size();
+            h->st.graph_used = 1;
+            buf = chain_result_set(j.niter, j.T);
+            launches = chain_launches(j.niter, j.T, (int)ex->size(), oop);
+        } else {
+            buf = j.enqueue(h->stream, 0, j.niter, buf, 0, j.nimg, false);
+            HIPCHK(h, hipGetLastError());
+            launches = nl;
+        }
+    }
+    if (j.end)
+        if (int rc = j.end(buf, &iterations)) return rc;
+    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
+    h->st.pdhg_ms = ms;
+    h->st.launches = launches;
+    h->st.iterations = iterations;
+    h->st.algorithmic_bytes = j.bytes_per_px_iter * (double)h->npx * j.nimg * iterations;
+    *result_buf = buf;
+    return BPLTV_OK;
+}
+
 // The TV solve of the context x; *result_buf: the state set of x that holds the result (written on success only).
 int run_pdhg(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, int* result_buf) {
     h->has_per_image = false;
@@ -997,127 +1157,59 @@ int run_pdhg(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, int* result_b
     }
     if (rc) return rc;
     h->st.tile_iters = pl.T;
-    h->st.launch_chains = 1;
     h->st.pdhg_variant = pl.variant + 1;
     h->st.tiles = pl.grid;
     h->st.region_i = kVariants[pl.variant].RI;
     h->st.region_j = kVariants[pl.variant].RJ;
-    h->st.launches = 0;
-    h->st.iterations = 0;
-    h->st.graph_used = 0;
-    h->st.last_gap = -1.0;
-    int buf = 0, launches = 0;
-    if (p.maxiter == 0) {  // u = x0 = f (params.init = 1: 0)
-        for (int c = 0; c < 3; ++c) {
-            if (c == 0 && !p.init) {
-                for (int r = 0; r < x.nimg / h->O; ++r)
-                    HIPCHK(h, hipMemcpyAsync(x.state[0][0] + (size_t)r * h->tot, h->d_f, h->tot * sizeof(double),
-                                             hipMemcpyDeviceToDevice, h->stream));
-            } else {
-                HIPCHK(h, hipMemsetAsync(x.state[0][c], 0, (size_t)x.nimg * h->npx * sizeof(double), h->stream));
-            }
-        }
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        *result_buf = 0;
-        h->st.pdhg_ms = 0.0;
-        return BPLTV_OK;
-    }
-    const bool chunked = p.check_every > 0;
     const size_t total = (size_t)x.nimg * h->npx;
     const unsigned gtot = (unsigned)((total + 255) / 256);
-    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    if (from_state) {
-        hipLaunchKernelGGL(pdhg_init_kernel, dim3(gtot), dim3(256), 0, h->stream, h->d_f, x.alpha, x.am, x.an,
-                           h->M, h->N, h->O, x.astride, x.istride, total, p.init ? 1 : 0, p.order ? 1 : 0,
-                           p.sigma0 / opnorm_of(p, 8.0), p.rho, x.state[1][0], x.state[1][1], x.state[1][2]);
-        HIPCHK(h, hipGetLastError());
-        buf = 1;
-    }
-    if (!chunked) {
-        bool done = main_iters == 0;
-        if (p.use_graph && !done) {
-            GraphKey key{main_iters, pl.T, pl.variant, x.am, x.an, pl.chains, p.rho, p.tau0, p.sigma0, p.accel ? 1 : 0, p.reserved[3] | ((p.reserved[2] & 3) << 16), x.nimg, (const void*)pdhg_state(h, x, 0, 0), (const void*)d_tab, from_state ? 1 : 0, (const void*)pdhg_alpha(h, x), x.istride};
-            auto it = h->graphs.find(key);
-            const int nl = (main_iters + pl.T - 1) / pl.T;
-            if (it == h->graphs.end() && h->graphs.size() >= 16) {  // bounded cache
-                drop_graphs(h);
-                it = h->graphs.end();
-            }
-            if (it == h->graphs.end() && nl <= 50000) {  // longer sequences are launched eagerly
-                std::vector<hipGraphExec_t> ex;
-                if (build_graphs(h, x, p, pl, d_tab, main_iters, from_state, &ex) == BPLTV_OK && !ex.empty()) {
-                    h->graphs[key] = ex;
-                    it = h->graphs.find(key);
-                }
-                (void)hipGetLastError();
-            }
-            if (it != h->graphs.end()) {
-                const std::vector<hipGraphExec_t>& ex = it->second;
-                if (ex.size() == 1 || (p.reserved[2] & 1)) {
-                    // reserved[2] = 1: replay the chains one after the other (no kernels in flight
-                    // together) -- used by bench.py to time an isolated launch, as rocprofv3 sees it
-                    for (size_t c = 0; c < ex.size(); ++c) HIPCHK(h, hipGraphLaunch(ex[c], h->stream));
-                } else {
-                    // fork: every chain waits for what is on the handle's stream now (fork_ev is recorded behind
-                    // pdhg_init_kernel when the sequence starts from a prepared state; ev[0] -- the timing start -- sits in
-                    // front of it).  hipGraphLaunch walks the graph on the calling thread (a few us of host time per
-                    // kernel node), so the second chain is launched from the handle's launcher thread -- launched one after
-                    // the other from this thread the second chain starts when the first is half done and nothing
-                    // overlaps (measured: 6.83e5 it/s against 8.2e5 on the 10 x 128^2 batch).
-                    rc = launch_chains(h, ex, nl >= 128 && !(p.reserved[2] & 8));   // reserved[2] & 8 (timing aid): both chains launched from the calling thread
-                    if (rc) return rc;
-                }
-                h->st.launch_chains = (int)ex.size();
-                buf = (nl - 1) % 2 == 0 ? 0 : 1;  // launch 0 writes set 0, launch l writes set l%2
-                launches = nl * (int)ex.size() + (chain_out_of_phase(main_iters, pl.T, from_state) ? (int)ex.size() / 2 : 0);
-                h->st.graph_used = 1;
-                done = true;
-            }
-        }
-        if (!done) {
-            rc = enqueue_pdhg(h, x, p, pl, d_tab, 0, main_iters, &buf, &launches, from_state);
-            if (rc) return rc;
-        }
-        h->st.iterations = p.maxiter;
-        if (h->dtype == 32) {
-            rc = f32_widen(h, x, buf);
-            if (rc) return rc;
-        }
-    } else {
-        int it = 0;
-        while (it < main_iters) {
-            const int it1 = std::min(main_iters, it + p.check_every);
-            rc = enqueue_pdhg(h, x, p, pl, d_tab, it, it1, &buf, &launches, from_state);
-            if (rc) return rc;
-            it = it1;
-            if (h->dtype == 32) {   // the gap kernels read the double state
-                rc = f32_widen(h, x, buf);
-                if (rc) return rc;
-            }
-            double gmax = 0.0;
-            rc = compute_gap(h, x, false, buf, nullptr, &gmax);   // of the set this chunk just wrote
-            if (rc) return rc;
-            h->st.last_gap = gmax;
-            if (p.gap_tol > 0.0 && gmax <= p.gap_tol) break;
-        }
-        h->st.iterations = it + ((p.order && it == main_iters) ? 1 : 0);
-    }
-    if (p.order && h->st.iterations == p.maxiter) {   // dual-first: the primal step of the last iteration
-        hipLaunchKernelGGL(pdhg_xstep_kernel, dim3(gtot), dim3(256), 0, h->stream, h->d_f, x.state[buf][1], x.state[buf][2],
-                           d_tab + (size_t)TAB_STRIDE * (p.maxiter - 1), h->M, h->N, h->O, total, x.state[buf][0]);
-        HIPCHK(h, hipGetLastError());
-    }
-    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    h->st.pdhg_ms = ms;
-    h->st.launches = launches;
-    *result_buf = buf;
+    const bool chunked = p.check_every > 0;
     const bool amap = (x.am == h->M && x.an == h->N) && !(h->M == 1 && h->N == 1);
-    h->st.bytes_per_px_iter = (amap ? 64.0 : 56.0) * (h->dtype == 32 ? 0.5 : 1.0);
-    h->st.algorithmic_bytes = h->st.bytes_per_px_iter * (double)h->npx * x.nimg * h->st.iterations;
-    return BPLTV_OK;
+    ChainSolve j;
+    j.model = MODEL_TV; j.nplanes = 3; j.state0 = x.state[0];
+    j.nimg = x.nimg; j.niter = main_iters; j.T = pl.T; j.chains = pl.chains;
+    j.from_state = from_state; j.x0_zero = p.init != 0;
+    // reserved[2] = 1: replay the chains one after the other (no kernels in flight together) -- used by bench.py to time an
+    // isolated launch, as rocprofv3 sees it; reserved[2] & 8 (timing aid): both chains launched from the calling thread.
+    // hipGraphLaunch walks the graph on the calling thread (a few us of host time per kernel node), so the second chain is
+    // launched from the handle's launcher thread -- launched one after the other from this thread the second chain starts
+    // when the first is half done and nothing overlaps (measured: 6.83e5 it/s against 8.2e5 on the 10 x 128^2 batch).
+    j.serial = (p.reserved[2] & 1) != 0; j.helper_thread = !(p.reserved[2] & 8);
+    j.bytes_per_px_iter = (amap ? 64.0 : 56.0) * (h->dtype == 32 ? 0.5 : 1.0);
+    j.key = GraphKey{main_iters, pl.T, pl.variant, x.am, x.an, pl.chains, p.rho, p.tau0, p.sigma0, p.accel ? 1 : 0,
+                     p.reserved[3] | ((p.reserved[2] & 3) << 16), x.nimg, (const void*)pdhg_state(h, x, 0, 0), (const void*)d_tab,
+                     from_state ? 1 : 0, (const void*)pdhg_alpha(h, x), x.istride, 0};
+    j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
+        return enqueue_pdhg(h, x, p, pl, d_tab, from_state, st, it0, it1, cur, lo, hi, stagger);
+    };
+    j.build = [&](std::vector<hipGraphExec_t>* out) { return build_graphs(h, x, p, pl, d_tab, main_iters, from_state, out); };
+    j.gap = [&](int buf, double* gmax) {
+        if (h->dtype == 32)   // the gap kernels read the double state
+            if (int wrc = f32_widen(h, x, buf)) return wrc;
+        return compute_gap(h, x, MODEL_TV, buf, nullptr, gmax);
+    };
+    // the chains fork behind what the handle's stream holds when they start: behind pdhg_init_kernel, while ev[0] -- the
+    // timing start -- sits in front of it
+    if (from_state)
+        j.begin = [&]() {
+            hipLaunchKernelGGL(pdhg_init_kernel, dim3(gtot), dim3(256), 0, h->stream, h->d_f, x.alpha, x.am, x.an,
+                               h->M, h->N, h->O, x.astride, x.istride, total, p.init ? 1 : 0, p.order ? 1 : 0,
+                               p.sigma0 / opnorm_of(p, 8.0), p.rho, x.state[1][0], x.state[1][1], x.state[1][2]);
+            HIPCHK(h, hipGetLastError());
+            return (int)BPLTV_OK;
+        };
+    j.end = [&](int buf, int* iterations) {
+        if (h->dtype == 32 && !chunked)
+            if (int wrc = f32_widen(h, x, buf)) return wrc;
+        if (p.order && *iterations == main_iters) {   // dual-first: the primal step of the last iteration
+            ++*iterations;
+            hipLaunchKernelGGL(pdhg_xstep_kernel, dim3(gtot), dim3(256), 0, h->stream, h->d_f, x.state[buf][1], x.state[buf][2],
+                               d_tab + (size_t)TAB_STRIDE * (p.maxiter - 1), h->M, h->N, h->O, total, x.state[buf][0]);
+            HIPCHK(h, hipGetLastError());
+        }
+        return (int)BPLTV_OK;
+    };
+    return run_chains(h, p, j, result_buf);
 }
 
 int compute_cost(bpltv_t* h, const double* d_u, const double* d_ubar, double* d_out /*device scalar*/) {
@@ -1669,10 +1761,55 @@ struct WallTimer {
 
 int run_sr_gradient(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, const bpltv_params& p);
 
+int check_weight(bpltv_t* h, const char* who, const double* w, bool on_device, size_t n, double* wmin);
+int weighted_check_params(bpltv_t* h, const bpltv_params& p, const char* who);
+
+// What bpltv_vjp, bpltv_jvp, bpltv_weighted_vjp and their sum-of-regularisers, _each and _device forms do before the
+// adjoint solve, `who` ("vjp", "jvp", "weighted_vjp") in every message: parameter shape, params, the parameter on the host
+// (check_alpha_host) or in HBM (alpha_dev), the weighted model's w, and the cotangent / tangent arrays `extra` (at most
+// two, HBM, nullable) -- all of it checked before anything of the handle changes, the device arrays with one read-back
+// (check_device_arrays).  The parameter is then staged in d_vjp = [4 check words | parameter | parameter gradient | w], so
+// that the last solve -- d_alpha with its shape and minimum, d_w, the PDHG state and graphs, and so bpltv_u_device and
+// bpltv_duality_gap -- stays as it was.  Fills *p (the resolved params) and the parameter fields of *g.
+// slices: 1 TV, 3 sum of regularisers (the parameter is 3*am*an doubles).  each: alpha holds O blocks, image k reads block k.
+// w (nullable; wo planes): the weighted model, every entry > 0; staged behind the parameter gradient.
+int stage_param(bpltv_t* h, const char* who, const double* alpha, bool alpha_dev, int am, int an, int slices, bool each, int reg,
+                const bpltv_params* pp, const double* w, int wo, std::initializer_list<DevArray> extra, bpltv_params* p, GradCtx* g) {
+    if (am < 1 || an < 1 || am > h->M || an > h->N)
+        return set_err(h, BPLTV_E_ARG, "%s: parameter shape %dx%d (image %dx%d)", who, am, an, h->M, h->N);
+    const bool sr = slices == 3;
+    *p = resolve(pp);
+    if (int prc = w ? weighted_check_params(h, *p, who) : check_params(h, *p)) return prc;
+    if (sr && p->reserved[4] == 2) return set_err(h, BPLTV_E_UNSUPPORTED, "block cyclic reduction applies to the TV model only");
+    const size_t P = (size_t)slices * am * an * (each ? h->O : 1), nw = w ? (size_t)wo * h->npx : 0;
+    double amin = 0.0, wmin = 0.0;
+    if (!alpha_dev)
+        if (int crc = check_alpha_host(h, (std::string(who) + ": alpha").c_str(), alpha, P, &amin)) return crc;
+    if (w) {
+        if (int rc = check_weight(h, who, w, alpha_dev, nw, &wmin)) return rc;
+        if (!(wmin > 0.0)) return set_err(h, BPLTV_E_ARG, "%s: the adjoint system scales with 1/sqrt(w): every weight must be > 0 (min = %g)", who, wmin);
+    }
+    int rc = ensure(h, &h->d_vjp, &h->vjp_cap, 4 + 2 * P + nw);
+    if (rc) return rc;
+    int failed = -1;
+    rc = check_device_arrays(h, reinterpret_cast<unsigned long long*>(h->d_vjp), {alpha_dev ? alpha : nullptr, P}, extra, &amin, &failed);
+    if (rc) return rc;
+    if (failed == 0) return set_err(h, BPLTV_E_ARG, "%s: alpha (device array): parameters must be finite and >= 0", who);
+    if (failed > 0) return set_err(h, BPLTV_E_ARG, "%s: the %s must be finite", who, extra.begin()[failed - 1].name);
+    if (sr && reg && !(am == 1 && an == 1) && !(amin > 0.0))   // run_sr_gradient_once's condition, before anything changes
+        return set_err(h, BPLTV_E_ARG, "sumregs_gradient_reg with a patch parameter needs every entry > 0 (min = %g)", amin);
+    const hipMemcpyKind kind = alpha_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    double *d_a = h->d_vjp + 4, *d_wv = h->d_vjp + 4 + 2 * P;
+    HIPCHK(h, hipMemcpyAsync(d_a, alpha, P * sizeof(double), kind, h->stream));
+    if (w) HIPCHK(h, hipMemcpyAsync(d_wv, w, nw * sizeof(double), kind, h->stream));
+    g->alpha = d_a; g->am = am; g->an = an; g->alpha_min = amin;
+    g->astride = each ? slices * am * an : 0; g->each = each;
+    if (w) { g->w = d_wv; g->wo = wo; }
+    return BPLTV_OK;
+}
+
 // Vector-Jacobian product of u = denoise(f, alpha) on a single-device handle: d_u, d_gu and the outputs live in HBM
-// (the host form stages them), `alpha` on the host or (alpha_dev) in HBM.  Parameter and cotangent are checked before
-// anything of the handle changes; the parameter is then staged in d_vjp, so that the last solve -- d_alpha with its
-// shape and minimum, the PDHG state and graphs, and so bpltv_u_device and bpltv_duality_gap -- stays as it was.
+// (the host form stages them), `alpha` on the host or (alpha_dev) in HBM; checks and staging by stage_param.
 // slices: 1 TV (bpltv_vjp), 3 sum of regularisers (bpltv_sumregs_vjp; the parameter is 3*am*an doubles).
 // d_grad_alpha: slices*am*an doubles in HBM or nullptr; d_grad_f: M*N*O doubles in HBM or nullptr; not both nullptr.
 // each (bpltv_vjp_each, bpltv_sumregs_vjp_each): alpha holds O blocks of slices*am*an doubles, image k reads block k, and
@@ -1682,101 +1819,34 @@ int vjp_common(bpltv_t* h, const double* d_u, const double* alpha, bool alpha_de
                bool each = false) {
     if (!d_u || !alpha || !d_gu) return set_err(h, BPLTV_E_ARG, "vjp: null pointer");
     if (!d_grad_f && !d_grad_alpha) return set_err(h, BPLTV_E_ARG, "vjp: both outputs are NULL");
-    if (am < 1 || an < 1 || am > h->M || an > h->N)
-        return set_err(h, BPLTV_E_ARG, "vjp: parameter shape %dx%d (image %dx%d)", am, an, h->M, h->N);
-    const bool sr = slices == 3;
-    bpltv_params p = resolve(pp);
-    if (int prc = check_params(h, p)) return prc;
-    if (sr && p.reserved[4] == 2) return set_err(h, BPLTV_E_UNSUPPORTED, "block cyclic reduction applies to the TV model only");
-    const size_t P = (size_t)slices * am * an * (each ? h->O : 1);
-    double amin = 0.0;
-    if (!alpha_dev)
-        if (int crc = check_alpha_host(h, "vjp: alpha", alpha, P, &amin)) return crc;
-    int rc = ensure(h, &h->d_vjp, &h->vjp_cap, 4 + 2 * P);
-    if (rc) return rc;
-    // check words: [0] smallest parameter entry (bits), [1] parameter rejected, [2] cotangent not finite
-    unsigned long long* chk_d = reinterpret_cast<unsigned long long*>(h->d_vjp);
-    HIPCHK(h, hipMemsetAsync(chk_d, 0xFF, sizeof(unsigned long long), h->stream));
-    HIPCHK(h, hipMemsetAsync(chk_d + 1, 0, 2 * sizeof(unsigned long long), h->stream));
-    if (alpha_dev)
-        hipLaunchKernelGGL(alpha_check_kernel, dim3((unsigned)std::min<size_t>((P + 255) / 256, 1024)), dim3(256), 0, h->stream, alpha, P,
-                           chk_d);
-    hipLaunchKernelGGL(finite_check_kernel, dim3((unsigned)std::min<size_t>((h->tot + 255) / 256, 1024)), dim3(256), 0, h->stream, d_gu,
-                       h->tot, chk_d + 2);
-    HIPCHK(h, hipGetLastError());
-    unsigned long long chk_h[3] = {0, 0, 0};
-    HIPCHK(h, hipMemcpyAsync(chk_h, chk_d, sizeof(chk_h), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (chk_h[1] != 0) return set_err(h, BPLTV_E_ARG, "vjp: alpha (device array): parameters must be finite and >= 0");
-    if (chk_h[2] != 0) return set_err(h, BPLTV_E_ARG, "vjp: the cotangent gu must be finite");
-    if (alpha_dev) std::memcpy(&amin, chk_h, sizeof(double));
-    if (sr && reg && !(am == 1 && an == 1) && !(amin > 0.0))   // run_sr_gradient_once's condition, before anything changes
-        return set_err(h, BPLTV_E_ARG, "sumregs_gradient_reg with a patch parameter needs every entry > 0 (min = %g)", amin);
-    double* d_a = h->d_vjp + 4;
-    HIPCHK(h, hipMemcpyAsync(d_a, alpha, P * sizeof(double), alpha_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    bpltv_params p;
     GradCtx g;
-    g.alpha = d_a; g.am = am; g.an = an; g.alpha_min = amin;
-    g.astride = each ? slices * am * an : 0; g.each = each;
+    if (int rc = stage_param(h, "vjp", alpha, alpha_dev, am, an, slices, each, reg, pp, nullptr, 1, {{d_gu, h->tot, "cotangent gu"}}, &p, &g)) return rc;
     g.src = d_gu; g.cot = true;
     g.d_out = d_grad_alpha; g.d_grad_f = d_grad_f;
     h->has_per_image = false;   // the reduction scratch (d_red) no longer holds the last evaluate's rows
-    return sr ? run_sr_gradient(h, d_u, g, reg ? 1 : 0, p) : run_gradient(h, d_u, g, reg ? 1 : 0, p);
+    return slices == 3 ? run_sr_gradient(h, d_u, g, reg ? 1 : 0, p) : run_gradient(h, d_u, g, reg ? 1 : 0, p);
 }
 
 // Jacobian-vector product of u = denoise(f, alpha) on a single-device handle: the linear map whose transpose
 // vjp_common computes, for ndir directions against one factorisation per image group (run_gradient_once /
 // run_sr_gradient_once).  d_u, the tangents d_df / d_dalpha (either may be nullptr: a zero tangent) and d_du live in HBM,
 // direction-major; `alpha` on the host or (alpha_dev) in HBM.  slices: 1 TV (bpltv_jvp), 3 sum of regularisers
-// (bpltv_sumregs_jvp; parameter and tangent blocks are 3*am*an doubles).  Checks and staging as in vjp_common: nothing of
-// the handle changes on a rejection, and the last solve stays as it was.
+// (bpltv_sumregs_jvp; parameter and tangent blocks are 3*am*an doubles).  Checks and staging by stage_param.
 int jvp_common(bpltv_t* h, const double* d_u, const double* alpha, bool alpha_dev, int am, int an, int reg,
                const bpltv_params* pp, int ndir, const double* d_df, const double* d_dalpha, double* d_du, bool each,
                int slices = 1) {
     if (!d_u || !alpha || !d_du) return set_err(h, BPLTV_E_ARG, "jvp: null pointer");
     if (ndir < 1) return set_err(h, BPLTV_E_ARG, "jvp: ndir = %d (at least one direction)", ndir);
     if (!d_df && !d_dalpha) return set_err(h, BPLTV_E_ARG, "jvp: both tangents are NULL");
-    if (am < 1 || an < 1 || am > h->M || an > h->N)
-        return set_err(h, BPLTV_E_ARG, "jvp: parameter shape %dx%d (image %dx%d)", am, an, h->M, h->N);
-    bpltv_params p = resolve(pp);
-    if (int prc = check_params(h, p)) return prc;
-    const bool sr = slices == 3;
-    if (sr && p.reserved[4] == 2) return set_err(h, BPLTV_E_UNSUPPORTED, "block cyclic reduction applies to the TV model only");
     const size_t P = (size_t)slices * am * an * (each ? h->O : 1);
-    double amin = 0.0;
-    if (!alpha_dev)
-        if (int crc = check_alpha_host(h, "jvp: alpha", alpha, P, &amin)) return crc;
-    int rc = ensure(h, &h->d_vjp, &h->vjp_cap, 4 + 2 * P);
-    if (rc) return rc;
-    // check words: [0] smallest parameter entry (bits), [1] parameter rejected, [2] df not finite, [3] dalpha not finite
-    unsigned long long* chk_d = reinterpret_cast<unsigned long long*>(h->d_vjp);
-    HIPCHK(h, hipMemsetAsync(chk_d, 0xFF, sizeof(unsigned long long), h->stream));
-    HIPCHK(h, hipMemsetAsync(chk_d + 1, 0, 3 * sizeof(unsigned long long), h->stream));
-    if (alpha_dev)
-        hipLaunchKernelGGL(alpha_check_kernel, dim3((unsigned)std::min<size_t>((P + 255) / 256, 1024)), dim3(256), 0, h->stream, alpha, P,
-                           chk_d);
-    if (d_df)
-        hipLaunchKernelGGL(finite_check_kernel, dim3((unsigned)std::min<size_t>((ndir * h->tot + 255) / 256, 1024)), dim3(256), 0, h->stream,
-                           d_df, (size_t)ndir * h->tot, chk_d + 2);
-    if (d_dalpha)
-        hipLaunchKernelGGL(finite_check_kernel, dim3((unsigned)std::min<size_t>((ndir * P + 255) / 256, 1024)), dim3(256), 0, h->stream,
-                           d_dalpha, (size_t)ndir * P, chk_d + 3);
-    HIPCHK(h, hipGetLastError());
-    unsigned long long chk_h[4] = {0, 0, 0, 0};
-    HIPCHK(h, hipMemcpyAsync(chk_h, chk_d, sizeof(chk_h), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (chk_h[1] != 0) return set_err(h, BPLTV_E_ARG, "jvp: alpha (device array): parameters must be finite and >= 0");
-    if (chk_h[2] != 0) return set_err(h, BPLTV_E_ARG, "jvp: the tangent df must be finite");
-    if (chk_h[3] != 0) return set_err(h, BPLTV_E_ARG, "jvp: the tangent dalpha must be finite");
-    if (alpha_dev) std::memcpy(&amin, chk_h, sizeof(double));
-    if (sr && reg && !(am == 1 && an == 1) && !(amin > 0.0))   // run_sr_gradient_once's condition, before anything changes
-        return set_err(h, BPLTV_E_ARG, "sumregs_gradient_reg with a patch parameter needs every entry > 0 (min = %g)", amin);
-    double* d_a = h->d_vjp + 4;
-    HIPCHK(h, hipMemcpyAsync(d_a, alpha, P * sizeof(double), alpha_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    bpltv_params p;
     GradCtx g;
-    g.alpha = d_a; g.am = am; g.an = an; g.alpha_min = amin;
-    g.astride = each ? slices * am * an : 0; g.each = each;
+    if (int rc = stage_param(h, "jvp", alpha, alpha_dev, am, an, slices, each, reg, pp, nullptr, 1,
+                             {{d_df, (size_t)ndir * h->tot, "tangent df"}, {d_dalpha, (size_t)ndir * P, "tangent dalpha"}}, &p, &g))
+        return rc;
     g.ndir = ndir; g.df = d_df; g.dalpha = d_dalpha; g.du = d_du;
-    return sr ? run_sr_gradient(h, d_u, g, reg ? 1 : 0, p) : run_gradient(h, d_u, g, reg ? 1 : 0, p);
+    return slices == 3 ? run_sr_gradient(h, d_u, g, reg ? 1 : 0, p) : run_gradient(h, d_u, g, reg ? 1 : 0, p);
 }
 
 // ============================================================================================
@@ -1835,12 +1905,6 @@ int solve_precheck(bpltv_t* h, const bpltv_params& p, double amin, int what) {
     return BPLTV_OK;
 }
 
-void drop_sr_graphs(bpltv_t* h) {
-    for (auto& kv : h->sr_graphs)
-        for (auto e : kv.second) (void)hipGraphExecDestroy(e);
-    h->sr_graphs.clear();
-}
-
 int sr_alloc(bpltv_t* h) {
     if (h->sr_ready) return BPLTV_OK;
     for (int s = 0; s < 2; ++s)
@@ -1852,7 +1916,7 @@ int sr_alloc(bpltv_t* h) {
     return BPLTV_OK;
 }
 
-// maxiter iterations of the three-dual PDHG, T fused per launch (halo 2T), replayed from a hipGraph, on the solve context
+// maxiter iterations of the three-dual PDHG, T fused per launch (halo 2T), launched by run_chains, on the solve context
 // x: x.nimg problems in the state sets x.state; problem img reads f[img % O] and the parameter block img / O (x.astride
 // doubles apart) of x.alpha; with x.istride != 0 (dataset context, bpltv_sumregs_denoise_each) image img reads the block
 // img, x.istride doubles apart.  *result_buf: the state set that holds the result (written on success only).
@@ -1902,21 +1966,18 @@ int run_sr_pdhg(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, int* resul
     if (nTi < 1 || nTj < 1) return set_err(h, BPLTV_E_ARG, "cannot tile %dx%d with T=%d", M, N, T);
     const int grid = nTi * nTj * nimg;
     h->st.tile_iters = T; h->st.tiles = grid; h->st.region_i = SR_R; h->st.region_j = SR_R; h->st.pdhg_variant = vi + 1;
-    h->st.launches = 0; h->st.iterations = p.maxiter; h->st.graph_used = 0; h->st.last_gap = -1.0; h->st.launch_chains = 1;
-    if (p.maxiter == 0) {   // u = f for every parameter block
-        for (int r = 0; r < nimg / h->O; ++r)
-            HIPCHK(h, hipMemcpyAsync(S[0][0] + (size_t)r * h->tot, h->d_f, h->tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        for (int c = 1; c < 7; ++c) HIPCHK(h, hipMemsetAsync(S[0][c], 0, (size_t)nimg * h->npx * sizeof(double), h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        *result_buf = 0; h->st.pdhg_ms = 0.0;
-        return BPLTV_OK;
-    }
     const bool each = x.istride != 0;   // one block per image: the dataset context only (nimg == O)
     void (*kern)(SrArgs) = each ? V.each_kernel : (nimg == h->O ? V.kernel : V.sweep_kernel);
-    // iterations [it0, it1) of the images [lo, hi) from the state set `cur`; returns the set holding the result.
-    // stagger: the chain's first launch fuses T/2 iterations and writes set 1 (run_pdhg's launch chains).
-    auto enqueue_range = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) -> int {
-        int step = stagger ? std::max(1, T / 2) : T;
+    const bool amap = (x.am == M && x.an == N) && !(M == 1 && N == 1);
+    ChainSolve j;
+    j.model = MODEL_SR; j.nplanes = 7; j.state0 = S[0];
+    j.nimg = nimg; j.niter = p.maxiter; j.T = T;
+    j.chains = plan_chains(p.reserved[1], grid, h->ncu, nimg, 2);   // at most two: chain 0 on the handle's stream, chain 1 on a second one
+    j.bytes_per_px_iter = amap ? 144.0 : 120.0;   // read x, 6 y, f (+ 3 alpha), write x, 6 y
+    j.key = GraphKey{p.maxiter, T, vi, x.am, x.an, j.chains, p.rho, p.tau0, p.sigma0, p.accel ? 1 : 0, 0, nimg, (const void*)S[0][0],
+                     (const void*)d_tab, 0, (const void*)d_alpha, x.istride, 0};
+    j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
+        int step = stagger ? T / 2 : T;
         for (int it = it0; it < it1; it += step, step = T) {
             SrArgs a;
             const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
@@ -1933,98 +1994,9 @@ int run_sr_pdhg(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, int* resul
         }
         return cur;
     };
-    auto enqueue = [&](hipStream_t st) -> int { return enqueue_range(st, 0, p.maxiter, 0, 0, nimg, false); };
-    if (p.check_every > 0) {   // duality-gap checks every check_every iterations, early stop at gap_tol (as the TV model)
-        HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-        int it = 0, cur = 0, launches = 0;
-        while (it < p.maxiter) {
-            const int it1 = std::min(p.maxiter, it + p.check_every);
-            cur = enqueue_range(h->stream, it, it1, cur, 0, h->O, false);
-            launches += (it1 - it + T - 1) / T;
-            it = it1;
-            HIPCHK(h, hipGetLastError());
-            double gmax = 0.0;
-            rc = compute_gap(h, x, true, cur, nullptr, &gmax);   // of the set this chunk just wrote
-            if (rc) return rc;
-            h->st.last_gap = gmax;
-            if (p.gap_tol > 0.0 && gmax <= p.gap_tol) break;
-        }
-        HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        float ms2 = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&ms2, h->ev[0], h->ev[1]));
-        h->st.pdhg_ms = ms2;
-        h->st.launches = launches;
-        h->st.iterations = it;
-        *result_buf = cur;
-        const bool amap2 = (x.am == M && x.an == N) && !(M == 1 && N == 1);
-        h->st.bytes_per_px_iter = amap2 ? 144.0 : 120.0;
-        h->st.algorithmic_bytes = h->st.bytes_per_px_iter * (double)h->tot * it;
-        return BPLTV_OK;
-    }
-    const int nl = (p.maxiter + T - 1) / T;
-    const int buf = (nl - 1) % 2 == 0 ? 0 : 1;   // launch 0 writes set 0, launch l writes set l % 2
-    // two launch chains (image groups) as in run_pdhg: chain 0 on the handle's stream, chain 1 on a second one, half a
-    // launch out of phase; reserved[1] = 1 keeps one chain
-    const int h0 = std::max(1, T / 2);
-    int nch = p.reserved[1] > 0 ? std::min(p.reserved[1], 2) : ((2 * grid > 3 * (h->ncu > 0 ? h->ncu : 256) && nimg >= 2) ? 2 : 1);
-    if (nch > nimg) nch = nimg;
-    const bool stag = T >= 2 && nl >= 8 && ((1 + (p.maxiter - h0 + T - 1) / T) - nl) % 2 == 1;
-    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    bool done = false;
-    if (p.use_graph && nl <= 50000) {
-        SrGraphKey key{p.maxiter, T, x.am, x.an, p.accel ? 1 : 0, vi + 16 * nch, p.rho, p.tau0, p.sigma0, (const void*)d_tab,
-                       nimg, (const void*)S[0][0], (const void*)d_alpha, x.istride};
-        auto it = h->sr_graphs.find(key);
-        if (it == h->sr_graphs.end()) {
-            if (h->sr_graphs.size() >= 8) drop_sr_graphs(h);
-            std::vector<hipGraphExec_t> exs;
-            for (int c = 0; c < nch; ++c) {
-                const int lo = (int)(((long)nimg * c) / nch), hi = (int)(((long)nimg * (c + 1)) / nch);
-                hipGraph_t g = nullptr;
-                hipGraphExec_t ex = nullptr;
-                if (!h->capture_stream && hipStreamCreateWithFlags(&h->capture_stream, hipStreamNonBlocking) != hipSuccess) { h->capture_stream = nullptr; break; }
-                if (hipStreamBeginCapture(h->capture_stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                    (void)enqueue_range(h->capture_stream, 0, p.maxiter, 0, lo, hi, (c & 1) && stag);
-                    if (hipStreamEndCapture(h->capture_stream, &g) == hipSuccess && g && hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) == hipSuccess)
-                        exs.push_back(ex);
-                    if (g) (void)hipGraphDestroy(g);
-                }
-            }
-            (void)hipGetLastError();
-            if ((int)exs.size() == nch) {
-                h->sr_graphs[key] = exs;
-                it = h->sr_graphs.find(key);
-            } else {
-                for (auto e : exs) (void)hipGraphExecDestroy(e);
-            }
-        }
-        if (it != h->sr_graphs.end()) {
-            const std::vector<hipGraphExec_t>& exs = it->second;
-            if (exs.size() == 1) {
-                HIPCHK(h, hipGraphLaunch(exs[0], h->stream));
-            } else {
-                rc = launch_chains(h, exs, nl >= 128);   // short sequences: a helper thread costs more than it hides
-                if (rc) return rc;
-            }
-            h->st.launch_chains = (int)exs.size();
-            h->st.graph_used = 1;
-            done = true;
-        }
-    }
-    if (!done) (void)enqueue(h->stream);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    h->st.pdhg_ms = ms;
-    h->st.launches = done ? nl * nch + ((nch > 1 && stag) ? 1 : 0) : nl;
-    *result_buf = buf;
-    const bool amap = (x.am == M && x.an == N) && !(M == 1 && N == 1);
-    h->st.bytes_per_px_iter = amap ? 144.0 : 120.0;   // read x, 6 y, f (+ 3 alpha), write x, 6 y
-    h->st.algorithmic_bytes = h->st.bytes_per_px_iter * (double)h->npx * nimg * p.maxiter;
-    return BPLTV_OK;
+    // duality-gap checks every check_every iterations, early stop at gap_tol (as the TV model)
+    j.gap = [&](int buf, double* gmax) { return compute_gap(h, x, MODEL_SR, buf, nullptr, gmax); };
+    return run_chains(h, p, j, result_buf);
 }
 
 int sr_adj_alloc(bpltv_t* h) {
@@ -3134,16 +3106,9 @@ int check_weight(bpltv_t* h, const char* who, const double* w, bool on_device, s
         }
         return BPLTV_OK;
     }
-    unsigned long long* chk_d = reinterpret_cast<unsigned long long*>(h->d_scalar + 2);
-    HIPCHK(h, hipMemsetAsync(chk_d, 0xFF, sizeof(unsigned long long), h->stream));
-    HIPCHK(h, hipMemsetAsync(chk_d + 1, 0, sizeof(unsigned long long), h->stream));
-    hipLaunchKernelGGL(alpha_check_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 1024)), dim3(256), 0, h->stream, w, n, chk_d);
-    HIPCHK(h, hipGetLastError());
-    unsigned long long chk_h[2] = {0, 1};
-    HIPCHK(h, hipMemcpyAsync(chk_h, chk_d, sizeof(chk_h), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (chk_h[1] != 0) return set_err(h, BPLTV_E_ARG, "%s: w (device array): the fidelity weight must be finite and >= 0", who);
-    std::memcpy(wmin, chk_h, sizeof(double));
+    int failed = -1;
+    if (int rc = check_device_arrays(h, reinterpret_cast<unsigned long long*>(h->d_scalar + 2), {w, n}, {}, wmin, &failed)) return rc;
+    if (failed == 0) return set_err(h, BPLTV_E_ARG, "%s: w (device array): the fidelity weight must be finite and >= 0", who);
     return BPLTV_OK;
 }
 
@@ -3181,22 +3146,16 @@ int run_weighted_pdhg(bpltv_t* h, const bpltv_params& p, const WeightedPlan& pl,
     const int M = h->M, N = h->N, O = h->O, T = pl.T;
     const bool amap = (h->last_am == M && h->last_an == N) && !(M == 1 && N == 1);
     h->st.tile_iters = T; h->st.tiles = pl.nTi * pl.nTj * O; h->st.region_i = WT_R; h->st.region_j = WT_R; h->st.pdhg_variant = 0;
-    h->st.launches = 0; h->st.iterations = p.maxiter; h->st.graph_used = 0; h->st.last_gap = -1.0; h->st.launch_chains = 1;
-    h->st.launch_host_ms[0] = h->st.launch_host_ms[1] = 0.0;
-    h->st.bytes_per_px_iter = amap ? 72.0 : 64.0;   // read x, y1, y2, f, w (+ alpha), write x, y1, y2
-    h->st.algorithmic_bytes = h->st.bytes_per_px_iter * (double)h->tot * p.maxiter;
-    if (p.maxiter == 0) {   // u = f
-        HIPCHK(h, hipMemcpyAsync(h->d_state[0][0], h->d_f, h->tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        for (int c = 1; c < 3; ++c) HIPCHK(h, hipMemsetAsync(h->d_state[0][c], 0, h->tot * sizeof(double), h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-        *result_buf = 0; h->st.pdhg_ms = 0.0;
-        return BPLTV_OK;
-    }
-    // all iterations of the images [lo, hi).  stagger: the chain's first launch fuses T/2 iterations and writes set 1, so that
-    // it runs half a launch out of phase with the other chain and ends in the same set (run_pdhg's launch chains)
-    auto enqueue_range = [&](hipStream_t st, int lo, int hi, bool stagger) {
-        int cur = 0, step = stagger ? std::max(1, T / 2) : T;
-        for (int it = 0; it < p.maxiter; it += step, step = T) {
+    ChainSolve j;
+    j.model = MODEL_W; j.nplanes = 3; j.state0 = h->d_state[0];
+    j.nimg = O; j.niter = p.maxiter; j.T = T;
+    j.chains = plan_chains(p.reserved[1], h->st.tiles, h->ncu, O, 2);   // at most two (image groups on two streams)
+    j.bytes_per_px_iter = amap ? 72.0 : 64.0;   // read x, y1, y2, f, w (+ alpha), write x, y1, y2
+    j.key = GraphKey{p.maxiter, T, 0, h->last_am, h->last_an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, nullptr, (const void*)d_tab, 0,
+                     (const void*)h->d_alpha, 0, h->w_wo};
+    j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
+        int step = stagger ? T / 2 : T;
+        for (int it = it0; it < it1; it += step, step = T) {
             const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
             WeightedArgs a;
             a.xin = h->d_state[cur][0]; a.y1in = h->d_state[cur][1]; a.y2in = h->d_state[cur][2];
@@ -3204,71 +3163,14 @@ int run_weighted_pdhg(bpltv_t* h, const bpltv_params& p, const WeightedPlan& pl,
             a.f = h->d_f; a.w = h->d_w; a.alpha = h->d_alpha; a.tab = d_tab;
             a.wstride = h->w_wo > 1 ? h->npx : 0;
             a.am = h->last_am; a.an = h->last_an;
-            a.it0 = it; a.nit = std::min(step, p.maxiter - it);
+            a.it0 = it; a.nit = std::min(step, it1 - it);
             a.M = M; a.N = N; a.halo = T; a.first = (it == 0) ? 1 : 0; a.img0 = lo;
             hipLaunchKernelGGL(weighted_tile_kernel, dim3(pl.nTi, pl.nTj, hi - lo), dim3(WT_R * WT_R), weighted_lds_bytes(), st, a);
             cur = nxt;
         }
+        return cur;
     };
-    const int nl = (p.maxiter + T - 1) / T;
-    // two launch chains (image groups on two streams) once the batch is well beyond one workgroup per CU, as run_pdhg;
-    // params.reserved[1] = 1 keeps one chain
-    const int ncu = h->ncu > 0 ? h->ncu : 256;
-    int nch = p.reserved[1] > 0 ? std::min(p.reserved[1], 2) : ((2 * (long)h->st.tiles > 3 * (long)ncu && O >= 2) ? 2 : 1);
-    if (nch > O) nch = O;
-    const int h0 = std::max(1, T / 2);
-    const bool stag = T >= 2 && nl >= 8 && ((1 + (p.maxiter - h0 + T - 1) / T) - nl) % 2 == 1;
-    HIPCHK(h, hipEventRecord(h->ev[0], h->stream));
-    bool done = false;
-    if (p.use_graph && nl <= 50000) {
-        const WGraphKey key{p.maxiter, T, h->last_am, h->last_an, h->w_wo, nch, (const void*)d_tab, (const void*)h->d_alpha};
-        auto it = h->w_graphs.find(key);
-        if (it == h->w_graphs.end()) {
-            if (h->w_graphs.size() >= 8) drop_w_graphs(h);
-            std::vector<hipGraphExec_t> exs;
-            for (int c = 0; c < nch; ++c) {
-                const int lo = (int)(((long)O * c) / nch), hi = (int)(((long)O * (c + 1)) / nch);
-                hipGraph_t g = nullptr;
-                hipGraphExec_t ex = nullptr;
-                if (!h->capture_stream && hipStreamCreateWithFlags(&h->capture_stream, hipStreamNonBlocking) != hipSuccess) { h->capture_stream = nullptr; break; }
-                if (hipStreamBeginCapture(h->capture_stream, hipStreamCaptureModeThreadLocal) == hipSuccess) {
-                    enqueue_range(h->capture_stream, lo, hi, (c & 1) && stag);
-                    if (hipStreamEndCapture(h->capture_stream, &g) == hipSuccess && g && hipGraphInstantiate(&ex, g, nullptr, nullptr, 0) == hipSuccess)
-                        exs.push_back(ex);
-                    if (g) (void)hipGraphDestroy(g);
-                }
-            }
-            (void)hipGetLastError();
-            if ((int)exs.size() == nch) {
-                h->w_graphs[key] = exs;
-                it = h->w_graphs.find(key);
-            } else {
-                for (auto e : exs) (void)hipGraphExecDestroy(e);
-            }
-        }
-        if (it != h->w_graphs.end()) {
-            const std::vector<hipGraphExec_t>& exs = it->second;
-            if (exs.size() == 1) {
-                HIPCHK(h, hipGraphLaunch(exs[0], h->stream));
-            } else {
-                rc = launch_chains(h, exs, nl >= 128);
-                if (rc) return rc;
-            }
-            h->st.launch_chains = (int)exs.size();
-            h->st.graph_used = 1;
-            done = true;
-        }
-    }
-    if (!done) enqueue_range(h->stream, 0, O, false);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev[1], h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[0], h->ev[1]));
-    h->st.pdhg_ms = ms;
-    h->st.launches = done ? nl * h->st.launch_chains + ((h->st.launch_chains > 1 && stag) ? 1 : 0) : nl;
-    *result_buf = (nl - 1) % 2 == 0 ? 0 : 1;   // launch 0 writes set 0, launch l writes set l % 2
-    return BPLTV_OK;
+    return run_chains(h, p, j, result_buf);   // (no gap callback: the weighted solve does not take params.check_every)
 }
 
 // bpltv_weighted_denoise(_device) on a single-device handle: w and the parameter from the host or (dev) from HBM.  The
@@ -3315,29 +3217,9 @@ int weighted_denoise_common(bpltv_t* h, const double* w, int wo, const double* a
     return BPLTV_OK;
 }
 
-// Duality gap per image of the last weighted solve (gamma = min w > 0: the dual objective divides by w)
-int weighted_gap(bpltv_t* h, double* gap_host, double* gap_max_host) {
-    if (!(h->w_min > 0.0))
-        return set_err(h, BPLTV_E_UNSUPPORTED, "duality gap of a weighted solve: the dual objective divides by w, every entry must be > 0 (min = %g)", h->w_min);
-    h->has_per_image = false;
-    const int nblk = 8;
-    int rc = ensure(h, &h->d_red, &h->red_cap, (size_t)h->O * nblk * 4);
-    if (rc) return rc;
-    double* const* S = h->d_state[h->result_buf];
-    hipLaunchKernelGGL(weighted_gap_partial_kernel, dim3(nblk, h->O), dim3(256), 0, h->stream, S[0], S[1], S[2], h->d_f, h->d_w,
-                       h->w_wo > 1 ? h->npx : (size_t)0, h->d_alpha, h->last_am, h->last_an, h->M, h->N, h->d_red);
-    hipLaunchKernelGGL(weighted_gap_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, nblk, h->O, h->d_perimg, h->d_scalar);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(gap_host, h->d_perimg, sizeof(double) * h->O, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(gap_max_host, h->d_scalar, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return BPLTV_OK;
-}
-
 // bpltv_weighted_vjp(_device) on a single-device handle: d_u, d_f (nullable unless d_grad_w), d_gu and the outputs live in
-// HBM; w and alpha on the host or (dev) in HBM.  Everything is checked before anything of the handle changes; the weight
-// and the parameter are staged in d_vjp = [4 check words | parameter | parameter gradient | w], apart from the last
-// solve's d_alpha and d_w.
+// HBM; w and alpha on the host or (dev) in HBM.  Checks and staging by stage_param: nothing of the handle changes on a
+// rejection, and the last solve's d_alpha and d_w stay as they were.
 int weighted_vjp_common(bpltv_t* h, const double* d_u, const double* d_f, const double* w, int wo, const double* alpha, bool dev,
                         int am, int an, const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alpha,
                         double* d_grad_w) {
@@ -3346,42 +3228,12 @@ int weighted_vjp_common(bpltv_t* h, const double* d_u, const double* d_f, const 
     if (!d_grad_f && !d_grad_alpha && !d_grad_w) return set_err(h, BPLTV_E_ARG, "%s: all three outputs are NULL", who);
     if (d_grad_w && !d_f) return set_err(h, BPLTV_E_ARG, "%s: grad_w = -(u - f) o p needs f", who);
     if (wo != 1 && wo != h->O) return set_err(h, BPLTV_E_ARG, "%s: wo = %d: one weight plane (1) or one per image (%d)", who, wo, h->O);
-    if (am < 1 || an < 1 || am > h->M || an > h->N)
-        return set_err(h, BPLTV_E_ARG, "%s: parameter shape %dx%d (image %dx%d)", who, am, an, h->M, h->N);
-    const bpltv_params p = resolve(pp);
-    if (int prc = weighted_check_params(h, p, who)) return prc;
-    const size_t P = (size_t)am * an, nw = (size_t)wo * h->npx;
-    double amin = 0.0, wmin = 0.0;
-    if (!dev)
-        if (int crc = check_alpha_host(h, "weighted_vjp: alpha", alpha, P, &amin)) return crc;
-    int rc = check_weight(h, who, w, dev, nw, &wmin);
-    if (rc) return rc;
-    if (!(wmin > 0.0)) return set_err(h, BPLTV_E_ARG, "%s: the adjoint system scales with 1/sqrt(w): every weight must be > 0 (min = %g)", who, wmin);
-    rc = ensure(h, &h->d_vjp, &h->vjp_cap, 4 + 2 * P + nw);
-    if (rc) return rc;
-    unsigned long long* chk_d = reinterpret_cast<unsigned long long*>(h->d_vjp);
-    HIPCHK(h, hipMemsetAsync(chk_d, 0xFF, sizeof(unsigned long long), h->stream));
-    HIPCHK(h, hipMemsetAsync(chk_d + 1, 0, 2 * sizeof(unsigned long long), h->stream));
-    if (dev)
-        hipLaunchKernelGGL(alpha_check_kernel, dim3((unsigned)std::min<size_t>((P + 255) / 256, 1024)), dim3(256), 0, h->stream, alpha, P, chk_d);
-    hipLaunchKernelGGL(finite_check_kernel, dim3((unsigned)std::min<size_t>((h->tot + 255) / 256, 1024)), dim3(256), 0, h->stream, d_gu,
-                       h->tot, chk_d + 2);
-    HIPCHK(h, hipGetLastError());
-    unsigned long long chk_h[3] = {0, 0, 0};
-    HIPCHK(h, hipMemcpyAsync(chk_h, chk_d, sizeof(chk_h), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (chk_h[1] != 0) return set_err(h, BPLTV_E_ARG, "%s: alpha (device array): parameters must be finite and >= 0", who);
-    if (chk_h[2] != 0) return set_err(h, BPLTV_E_ARG, "%s: the cotangent gu must be finite", who);
-    if (dev) std::memcpy(&amin, chk_h, sizeof(double));
-    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    double *d_a = h->d_vjp + 4, *d_wv = h->d_vjp + 4 + 2 * P;
-    HIPCHK(h, hipMemcpyAsync(d_a, alpha, P * sizeof(double), kind, h->stream));
-    HIPCHK(h, hipMemcpyAsync(d_wv, w, nw * sizeof(double), kind, h->stream));
+    bpltv_params p;
     GradCtx g;
-    g.alpha = d_a; g.am = am; g.an = an; g.alpha_min = amin;
+    if (int rc = stage_param(h, who, alpha, dev, am, an, 1, false, 0, pp, w, wo, {{d_gu, h->tot, "cotangent gu"}}, &p, &g)) return rc;
     g.src = d_gu; g.cot = true;
     g.d_out = d_grad_alpha; g.d_grad_f = d_grad_f;
-    g.w = d_wv; g.wo = wo; g.f = d_f; g.d_grad_w = d_grad_w;
+    g.f = d_f; g.d_grad_w = d_grad_w;
     h->has_per_image = false;
     return run_gradient(h, d_u, g, 0, p);
 }
@@ -3504,7 +3356,7 @@ int bpltv_destroy(bpltv_t* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     h->launcher.reset();   // joins the launcher thread (idle: every call waits for its job)
-    drop_graphs(h);
+    drop_graphs(h, DROP_ALL);
     if (h->fork_ev) (void)hipEventDestroy(h->fork_ev);
     for (auto ce : h->chain_events) (void)hipEventDestroy(ce);   // (the chain streams belong to the device: device_streams_release below)
     if (h->capture_stream) (void)hipStreamDestroy(h->capture_stream);
@@ -3537,7 +3389,6 @@ int bpltv_destroy(bpltv_t* h) {
     h->hb_sr.release();
     h->lu_sr.release();
     if (h->d_srdiagU) (void)hipFree(h->d_srdiagU);
-    drop_sr_graphs(h);
     for (void* q : {(void*)h->d_srcoef, (void*)h->d_srdiag, (void*)h->d_srw, (void*)h->d_srgpix, (void*)h->d_srsweep_alpha,
                     (void*)h->d_srsweep_cost})
         if (q) (void)hipFree(q);
@@ -3795,13 +3646,10 @@ int bpltv_duality_gap(bpltv_t* h, double* gap_out) {
     HIPCHK(h, hipSetDevice(h->device));
     double gmax = 0.0;
     const bool sr = h->last_is_sr;
-    if (!sr && h->last_weighted) {   // the weighted model's own gap (BPLTV_E_UNSUPPORTED when min w = 0)
-        const int wrc = weighted_gap(h, gap_out, &gmax);
-        if (wrc) return wrc;
-        h->st.last_gap = gmax;
-        return BPLTV_OK;
-    }
-    int rc = compute_gap(h, dataset_ctx(h, sr), sr, sr ? h->sr_result_buf : h->result_buf, gap_out, &gmax);
+    const Model model = sr ? MODEL_SR : (h->last_weighted ? MODEL_W : MODEL_TV);
+    if (model == MODEL_W && !(h->w_min > 0.0))   // gamma = min w > 0: the weighted model's dual objective divides by w
+        return set_err(h, BPLTV_E_UNSUPPORTED, "duality gap of a weighted solve: the dual objective divides by w, every entry must be > 0 (min = %g)", h->w_min);
+    int rc = compute_gap(h, dataset_ctx(h, sr), model, sr ? h->sr_result_buf : h->result_buf, gap_out, &gmax);
     if (rc) return rc;
     h->st.last_gap = gmax;
     return BPLTV_OK;
@@ -3979,7 +3827,7 @@ int bpltv_sweep(bpltv_t* h, const double* alphas, int K, int am, int an, const b
         return set_err(h, BPLTV_E_UNSUPPORTED, "params.init / params.order are implemented for dtype = 64 handles");
     p.check_every = 0;  // the gap kernels address the dataset context only
     if (h->sweep_cap < nimg) {
-        drop_graphs(h);
+        drop_graphs(h, DROP_TV);
         for (int s = 0; s < 2; ++s)
             for (int c = 0; c < 3; ++c) {
                 if (h->d_sweep[s][c]) HIPCHK(h, hipFree(h->d_sweep[s][c]));
@@ -3991,7 +3839,7 @@ int bpltv_sweep(bpltv_t* h, const double* alphas, int K, int am, int an, const b
         h->sweep_cap = nimg;
     }
     // the K parameter blocks live in the sweep's own buffer; problem k*O + i uses block k and image i
-    if (h->sweep_alpha_cap < K * npar) drop_graphs(h);   // captured launches hold the old pointer
+    if (h->sweep_alpha_cap < K * npar) drop_graphs(h, DROP_TV);   // the sweep's launches hold the old pointer
     int rc = ensure(h, &h->d_sweep_alpha, &h->sweep_alpha_cap, K * npar);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_sweep_alpha, alphas, K * npar * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -4054,7 +3902,7 @@ int bpltv_sumregs_sweep(bpltv_t* h, const double* alphas, int K, int am, int an,
     const int kmax = (K + ng - 1) / ng;
     const size_t pmax = (size_t)kmax * O;
     if (h->srsweep_cap < pmax) {
-        drop_sr_graphs(h);   // captured launches hold the old planes
+        drop_graphs(h, DROP_SR);   // captured launches hold the old planes
         h->srsweep_cap = 0;
         for (int sb = 0; sb < 2; ++sb)
             for (int c = 0; c < 7; ++c) {
@@ -4065,7 +3913,7 @@ int bpltv_sumregs_sweep(bpltv_t* h, const double* alphas, int K, int am, int an,
             for (int c = 0; c < 7; ++c) HIPCHK(h, hipMalloc((void**)&h->d_srsweep[sb][c], pmax * npx * sizeof(double)));
         h->srsweep_cap = pmax;
     }
-    if (h->srsweep_alpha_cap < kmax * nb) drop_sr_graphs(h);
+    if (h->srsweep_alpha_cap < kmax * nb) drop_graphs(h, DROP_SR);
     int rc = ensure(h, &h->d_srsweep_alpha, &h->srsweep_alpha_cap, kmax * nb);
     if (rc) return rc;
     rc = ensure(h, &h->d_srsweep_cost, &h->srsweep_cost_cap, pmax);

@@ -283,7 +283,7 @@ def test_float_handles_give_the_double_handles_results(gpu_solver_cls, kind):
 @pytest.mark.parametrize("kind", KINDS)
 def test_shared_and_per_image_solves_never_replay_each_other(gpu_solver_cls, oracle, kind):
     """shared -> per-image -> shared -> per-image on one handle, graphs on, one maxiter: every result bitwise a fresh
-    handle's (an SrGraphKey without the block stride would replay the shared graph, block 0 for every image)."""
+    handle's (a GraphKey without the block stride would replay the shared graph, block 0 for every image)."""
     O, N, M = 3, 40, 33
     ub, f = synth_batch(O, N, M, seed=61)
     blocks = _blocks(kind, O, N, M, seed=62)

@@ -130,7 +130,7 @@ def test_runtime_choices(gpu_solver_cls, oracle, kind):
 
 @pytest.mark.parametrize("var", [1, 2])
 def test_launch_chains_stagger_and_gap_checks(gpu_solver_cls, oracle, var):
-    """Two launch chains run half a launch out of phase when the parity allows it (run_sr_pdhg's `stag`: T >= 2, >= 8
+    """Two launch chains run half a launch out of phase when the parity allows it (tiling.hpp's chain_out_of_phase: T >= 2, >= 8
     launches, and the staggered chain ends in the same state set): stats()["launches"] is 2 nl + 1 with the stagger, 2 nl
     without.  One chain, T = 1, fewer than 8 launches, no graph, and gap checks every 7 / 13 iterations at T = 4."""
     ub, f = synth_batch(3, 50, 44, seed=81)

@@ -1,7 +1,8 @@
 // plan_host_check.cpp -- host fuzz of csrc/tiling.hpp: the tiling with halos (tile_span / tile_count), the block
-// distribution over devices (shard_range), the launch-chain phase rule and the region / fusion-depth planner
-// (plan_pdhg) on random and edge shapes.  Plain C++17, no GPU; tests/test_host_sanitize.py builds it with
-// g++ -fsanitize=address,undefined and runs it (sanitizers row: the library's host-only code).
+// distribution over devices (shard_range), the launch-chain rules (count, phase, launches, final state set) and the
+// region / fusion-depth planner (plan_pdhg) on random and edge shapes.  Plain C++17, no GPU; tests/test_host_sanitize.py
+// builds it with g++ -fsanitize=address,undefined and runs it (sanitizers row: the library's host-only
+// code).
 //
 // Invariants checked (what the kernels rely on -- an out-of-range tile is an out-of-bounds access on the device):
 //   * the cores [c0, c1) of tiles 0 .. n-1 partition [0, L) exactly; every region [o, o + R) lies inside the image;
@@ -10,7 +11,8 @@
 //   * tile_count is the number of tiles tile_span needs, and -1 exactly when no core is left;
 //   * shard_range partitions [0, O) into `world` consecutive, balanced ranges;
 //   * a plan has T >= 1, a core left in both directions, grid = nTi * nTj * nimg, 1 <= chains <= nimg, and the chains'
-//     image ranges partition the images; an out-of-phase chain ends in the same state set as an in-phase one.
+//     image ranges partition the images; plan_chains is the rule plan_pdhg applies;
+//     chain_launches counts the launches of all chains literally, and every chain, in phase or not, ends in chain_result_set.
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
@@ -60,6 +62,27 @@ static void check_tiling(int L, int R, int T) {
         expect = c1;
     }
     CHECK(expect == L, "L %d R %d T %d: cores end at %d", L, R, T, expect);
+}
+
+// The launches of every chain of a sequence, as the solvers enqueue them: `for (it = 0; it < niter; it += step, step = T)`,
+// an out-of-phase chain (the odd ones, when chain_out_of_phase allows) with a first step of T / 2 that writes set 1.
+// chain_launches is their literal count, and every chain ends in chain_result_set.
+static void check_chains(int niter, int T, int chains) {
+    const bool oop = chain_out_of_phase(niter, T, false);
+    int launches = 0;
+    for (int c = 0; c < chains; ++c) {
+        const bool stagger = (c & 1) && oop;
+        CHECK(!stagger || T / 2 >= 1, "out-of-phase chain with an empty first launch: niter %d T %d", niter, T);
+        int cur = 0, step = stagger ? T / 2 : T;
+        for (int it = 0; it < niter; it += step, step = T) {
+            cur = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;   // the set this launch writes
+            ++launches;
+        }
+        CHECK(cur == chain_result_set(niter, T), "chain %d of %d ends in set %d, not %d: niter %d T %d", c, chains, cur,
+              chain_result_set(niter, T), niter, T);
+    }
+    CHECK(launches == chain_launches(niter, T, chains, oop), "%d launches counted, chain_launches says %d: niter %d T %d chains %d",
+          launches, chain_launches(niter, T, chains, oop), niter, T, chains);
 }
 
 int main(int argc, char** argv) {
@@ -129,13 +152,20 @@ int main(int argc, char** argv) {
             prev = hi;
         }
         CHECK(prev == q.nimg, "chains end at image %d of %d", prev, q.nimg);
-        if (q.maxiter > 0 && chain_out_of_phase(q.maxiter, pl.T, false)) {
-            // the in-phase chain's launch l writes set l % 2; the out-of-phase chain starts by writing set 1 and has one launch more
-            const int nl = (q.maxiter + pl.T - 1) / pl.T, h0 = pl.T / 2;
-            const int nl1 = 1 + (q.maxiter - h0 + pl.T - 1) / pl.T;
-            CHECK(h0 >= 1 && ((nl - 1) % 2) == ((1 + (nl1 - 1)) % 2), "out-of-phase chain ends in another set: maxiter %d T %d", q.maxiter, pl.T);
+        {   // the chain rule restated: as requested, else two chains from 1.5 workgroups per CU and two images; never more than images
+            const int ncu = q.ncu > 0 ? q.ncu : 256;
+            int ch = q.chains > 0 ? q.chains : ((2 * (long)pl.grid > 3 * (long)ncu && q.nimg >= 2) ? 2 : 1);
+            if (ch > q.nimg) ch = q.nimg;
+            CHECK(plan_chains(q.chains, pl.grid, q.ncu, q.nimg) == pl.chains && pl.chains == ch, "plan_chains %d, plan %d, rule %d",
+                  plan_chains(q.chains, pl.grid, q.ncu, q.nimg), pl.chains, ch);
+            const int cap2 = plan_chains(q.chains, pl.grid, q.ncu, q.nimg, 2);   // the models that run at most two chains
+            CHECK(cap2 == std::min(ch, 2), "plan_chains capped at 2: %d, rule %d", cap2, std::min(ch, 2));
         }
+        if (q.maxiter > 0 && (q.maxiter + pl.T - 1) / pl.T <= 2000) check_chains(q.maxiter, pl.T, pl.chains);
     }
+    for (int niter = 1; niter <= 200; ++niter)
+        for (int T = 1; T <= 24; ++T)
+            for (int chains = 1; chains <= 4; ++chains) check_chains(niter, T, chains);
     printf("%s: %d tilings, %d shard distributions, %d plans checked, %d failures\n", bad ? "FAILED" : "all ok", rounds, rounds, nplans, bad);
     return bad ? 1 : 0;
 }
