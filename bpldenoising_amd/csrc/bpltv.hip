@@ -29,6 +29,7 @@
 #include "pdhg_kernels.hpp"
 #include "sumregs_kernels.hpp"
 #include "weighted_kernels.hpp"
+#include "unrolled_kernels.hpp"
 #include "multi_gpu.hpp"
 
 using namespace bpltv;
@@ -184,16 +185,17 @@ const Variant kVariants[] = {
 };
 
 // The models whose solves the shared launch driver (run_chains) runs
-enum Model { MODEL_TV = 0, MODEL_SR = 1, MODEL_W = 2, NMODELS = 3 };
+enum Model { MODEL_TV = 0, MODEL_SR = 1, MODEL_W = 2, MODEL_UN = 3, NMODELS = 4 };   // MODEL_UN: the taped solve and its reverse sweep
 
 // What identifies a launch sequence built into graphs: everything its kernel arguments and its cut into launches depend
-// on.  One key type for the three models (a field a model does not use stays 0); each model has a cache of its own
+// on.  One key type for all models (a field a model does not use stays 0); each model has a cache of its own
 // (bpltv_handle::graphs), so a weighted and an unweighted solve never replay each other's graphs.
 struct GraphKey {
     int maxiter, T, variant, am, an, chains;
     double rho, tau0, sigma0;
     int accel, dbg, nimg;
     const void* state; // state set 0 of the solve context: a sweep never replays a dataset-context graph, nor the reverse
+                       // (MODEL_UN: the tape the launches write or read, with variant 0 = taped solve, 1 = reverse sweep)
     const void* tab;   // step table (one per (maxiter, steps, L, dual-first shift, gamma): TabKey)
     int from_state;    // 1: the sequence starts from a prepared state (params.init / order), not from x = f, y = 0
     const void* alpha; // the parameter the launches read: a sweep's blocks and the dataset's parameter are different
@@ -361,7 +363,7 @@ struct bpltv_handle {
     size_t f32_alpha_cap = 0, f32_sweep_alpha_cap = 0;
     bool f32_f_valid = false;
     std::map<TabKey, float*> tabs32;
-    GraphCache graphs[NMODELS] = {{16}, {8}, {8}};   // by Model: at most 16 TV sequences, 8 of each other model
+    GraphCache graphs[NMODELS] = {{16}, {8}, {8}, {8}};   // by Model: at most 16 TV sequences, 8 of each other model
     std::vector<hipStream_t> chain_streams;   // the device's (DeviceStreams), not owned
     std::vector<hipEvent_t> chain_events;
     unsigned* d_phase = nullptr;              // the word chain 0's launches rewrite (PDHG_PHASE_STAMP, pdhg_phase_gate_kernel)
@@ -420,6 +422,14 @@ struct bpltv_handle {
     double w_min = 0.0;
     bool last_weighted = false;                     // the last solve was bpltv_weighted_denoise: u and the gap are its
     double* d_wst = nullptr;                        // bpltv_weighted_vjp's host staging [f | grad_w], 2 * M*N*O doubles
+    // reverse mode through the iterations (unrolled_kernels.hpp): the handle's own tape of pre-projection duals (allocated on
+    // demand, only grows), what it was recorded with, and the reverse sweep's planes [2 sets x (gx, gy1, gy2) | gf | ga | gu]
+    double* d_tape = nullptr;
+    size_t tape_cap = 0;                            // doubles
+    bool tape_valid = false;
+    int tape_maxiter = 0, tape_am = 0, tape_an = 0, tape_accel = 0;
+    double tape_tau0 = 0.0, tape_sigma0 = 0.0, tape_opnorm = 0.0;
+    double* d_unr = nullptr;                        // 9 * M*N*O doubles
     bpltv_stats_t st;
     std::string err;
 };
@@ -536,7 +546,7 @@ void cvt_to_f64(bpltv_t* h, const float* src, double* dst, size_t n) {
 //   the TV sweep's state sets or parameter blocks grow (bpltv_sweep)      TV
 //   the sum-of-regularisers sweep's planes or blocks grow (bpltv_sumregs_sweep)   sum of regularisers
 // d_f, d_w, the dataset state sets (d_state, d_sr) and the step tables live as long as the handle.
-enum { DROP_TV = 1 << MODEL_TV, DROP_SR = 1 << MODEL_SR, DROP_W = 1 << MODEL_W, DROP_ALL = DROP_TV | DROP_SR | DROP_W };
+enum { DROP_TV = 1 << MODEL_TV, DROP_SR = 1 << MODEL_SR, DROP_W = 1 << MODEL_W, DROP_UN = 1 << MODEL_UN, DROP_ALL = DROP_TV | DROP_SR | DROP_W | DROP_UN };
 void drop_graphs(bpltv_t* h, int which);
 // step table rounded to float (the oracle's bplo_pdhg_f32 rounds the same f64 table)
 int get_table32(bpltv_t* h, const bpltv_params& p, float** out) {
@@ -3238,17 +3248,226 @@ int weighted_vjp_common(bpltv_t* h, const double* d_u, const double* d_f, const 
     return run_gradient(h, d_u, g, 0, p);
 }
 
-// a weighted entry point on a multi-device handle: forwarded when one shard holds everything, unsupported otherwise
+// a weighted or unrolled entry point on a multi-device handle: forwarded when one shard holds everything, unsupported otherwise
 template <class F>
-int weighted_multi(bpltv_t* h, const char* what, bool solve, F call) {
+int weighted_multi(bpltv_t* h, const char* what, bool solve, F call, const char* model = "the weighted model") {
     MultiState& ms = *h->multi;
     if (ms.shard.size() != 1)
-        return set_err(h, BPLTV_E_UNSUPPORTED, "%s: the weighted model runs on single-device handles (this one has %zu shards)", what, ms.shard.size());
+        return set_err(h, BPLTV_E_UNSUPPORTED, "%s: %s runs on single-device handles (this one has %zu shards)", what, model, ms.shard.size());
     const int r = call(ms.shard[0]);
     if (r) { h->err = ms.shard[0]->err; return r; }
     if (solve) h->has_result = true; else h->has_per_image = false;
     multi_stats(h);
     return r;
+}
+
+// ============================================================================================
+// Reverse mode through the PDHG iterations (unrolled_kernels.hpp)
+// ============================================================================================
+static_assert(UN_R == WT_R, "the unrolled kernels tile like the weighted one");
+
+// What an unrolled call rejects on its parameters alone
+int unrolled_check_params(bpltv_t* h, const bpltv_params& p, const char* who) {
+    if (int prc = check_params(h, p)) return prc;
+    if (p.rho != 0.0) return set_err(h, BPLTV_E_UNSUPPORTED, "%s: params.rho must be 0 (the taped recurrence has no Huber smoothing)", who);
+    if (p.init != 0 || p.order != 0) return set_err(h, BPLTV_E_UNSUPPORTED, "%s: params.init / params.order must be 0", who);
+    if (p.maxiter < 1) return set_err(h, BPLTV_E_ARG, "%s: maxiter = %d (at least one iteration)", who, p.maxiter);
+    return BPLTV_OK;
+}
+
+// weighted_plan with the fusion depth capped at `cap` (the reverse kernel holds UN_REV_T iterations of tape in registers)
+int unrolled_plan(bpltv_t* h, const bpltv_params& p, int cap, WeightedPlan* pl) {
+    bpltv_params q = p;
+    q.tile_iters = std::min(p.tile_iters > 0 ? p.tile_iters : 8, cap);
+    return weighted_plan(h, q, pl);
+}
+
+const char* const kUnrolled = "the unrolled solve";   // what weighted_multi's message calls these entry points
+
+unsigned long long unrolled_tape_doubles(const bpltv_t* h, const bpltv_params& p) { return 2ull * (unsigned long long)p.maxiter * h->tot; }
+
+// maxiter taped iterations on the dataset images, in the TV state sets, with d_alpha; z_k of every pixel into d_tape.
+int run_unrolled_pdhg(bpltv_t* h, const bpltv_params& p, const WeightedPlan& pl, double* d_tape, int* result_buf) {
+    h->has_per_image = false;
+    double* d_tab = nullptr;
+    int rc = get_table(h, p, &d_tab, 8.0, 0);
+    if (rc) return rc;
+    const int M = h->M, N = h->N, O = h->O, T = pl.T;
+    const bool amap = (h->last_am == M && h->last_an == N) && !(M == 1 && N == 1);
+    h->st.tile_iters = T; h->st.tiles = pl.nTi * pl.nTj * O; h->st.region_i = UN_R; h->st.region_j = UN_R; h->st.pdhg_variant = 0;
+    ChainSolve j;
+    j.model = MODEL_UN; j.nplanes = 3; j.state0 = h->d_state[0];
+    j.nimg = O; j.niter = p.maxiter; j.T = T;
+    j.chains = plan_chains(p.reserved[1], h->st.tiles, h->ncu, O, 2);   // at most two (image groups on two streams)
+    j.serial = (p.reserved[2] & 1) != 0; j.helper_thread = !(p.reserved[2] & 8);
+    j.bytes_per_px_iter = amap ? 80.0 : 72.0;   // read x, y1, y2, f (+ alpha), write x, y1, y2 and z1, z2
+    j.key = GraphKey{p.maxiter, T, 0, h->last_am, h->last_an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_tape, (const void*)d_tab, 0,
+                     (const void*)h->d_alpha, 0, 0};
+    j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
+        int step = stagger ? T / 2 : T;
+        for (int it = it0; it < it1; it += step, step = T) {
+            const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
+            UnrolledArgs a;
+            a.xin = h->d_state[cur][0]; a.y1in = h->d_state[cur][1]; a.y2in = h->d_state[cur][2];
+            a.xout = h->d_state[nxt][0]; a.y1out = h->d_state[nxt][1]; a.y2out = h->d_state[nxt][2];
+            a.f = h->d_f; a.alpha = h->d_alpha; a.tab = d_tab; a.tape = d_tape; a.plane = h->tot;
+            a.am = h->last_am; a.an = h->last_an;
+            a.it0 = it; a.nit = std::min(step, it1 - it);
+            a.M = M; a.N = N; a.halo = T; a.first = (it == 0) ? 1 : 0; a.img0 = lo;
+            hipLaunchKernelGGL(unrolled_tile_kernel, dim3(pl.nTi, pl.nTj, hi - lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), st, a);
+            cur = nxt;
+        }
+        return cur;
+    };
+    return run_chains(h, p, j, result_buf);
+}
+
+// bpltv_unrolled_denoise(_device) on a single-device handle.  d_tape_user: the caller's tape, or nullptr for the handle's own,
+// which grows here -- the new buffer is allocated before anything changes and installed only once the parameter is accepted.
+int unrolled_denoise_common(bpltv_t* h, const double* alpha, bool dev, int am, int an, const bpltv_params* pp, double* d_tape_user,
+                            double* u_out) {
+    const char* who = dev ? "bpltv_unrolled_denoise_device" : "bpltv_unrolled_denoise";
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: bpltv_set_data has not been called", who);
+    const bpltv_params p = resolve(pp);
+    if (int prc = unrolled_check_params(h, p, who)) return prc;
+    WeightedPlan pl;
+    if (int prc = unrolled_plan(h, p, PDHG_MAX_T, &pl)) return prc;
+    const size_t need = (size_t)unrolled_tape_doubles(h, p);
+    double* grown = nullptr;
+    if (!d_tape_user && h->tape_cap < need) {
+        const hipError_t e = hipMalloc((void**)&grown, need * sizeof(double));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return set_err(h, e == hipErrorOutOfMemory ? BPLTV_E_NOMEM : BPLTV_E_HIP, "%s: hipMalloc of the tape (%.1f MB) failed: %s", who,
+                           need * sizeof(double) / 1e6, hipGetErrorString(e));
+        }
+    }
+    bpltv_params q = p;   // the TV planner's knobs mean nothing here: upload_alpha's precheck sees the defaults
+    q.tile_iters = 0; q.reserved[0] = 0; q.reserved[1] = 0; q.reserved[2] = 0;
+    int rc = upload_alpha(h, alpha, dev, am, an, PRE_TV, 1, &q);
+    if (rc) {
+        if (grown) (void)hipFree(grown);
+        return rc;
+    }
+    if (grown) {
+        if (h->d_tape) (void)hipFree(h->d_tape);
+        h->d_tape = grown;
+        h->tape_cap = need;
+    }
+    if (!d_tape_user) h->tape_valid = false;   // about to be overwritten
+    int buf = 0;
+    rc = run_unrolled_pdhg(h, p, pl, d_tape_user ? d_tape_user : h->d_tape, &buf);
+    if (rc) return rc;
+    h->result_buf = buf;
+    h->has_result = true;
+    h->last_is_sr = false;
+    h->last_weighted = false;
+    if (!d_tape_user) {
+        h->tape_valid = true;
+        h->tape_maxiter = p.maxiter; h->tape_am = am; h->tape_an = an; h->tape_accel = p.accel ? 1 : 0;
+        h->tape_tau0 = p.tau0; h->tape_sigma0 = p.sigma0; h->tape_opnorm = p.opnorm;
+    }
+    if (u_out) {
+        HIPCHK(h, hipMemcpyAsync(u_out, h->d_state[buf][0], h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
+// bpltv_unrolled_vjp(_device) on a single-device handle: d_gu and the outputs live in HBM, alpha on the host or (dev) in HBM;
+// d_tape_user or the handle's tape.  The parameter is staged apart (stage_param) and the sweep runs in planes of its own, so the
+// last solve stays untouched; the solve statistics are put back after the shared driver has run the sweep.
+int unrolled_vjp_common(bpltv_t* h, const double* d_tape_user, const double* alpha, bool dev, int am, int an, const bpltv_params* pp,
+                        const double* d_gu, double* d_grad_f, double* d_grad_alpha) {
+    const char* who = "unrolled_vjp";
+    if (!alpha || !d_gu) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
+    if (!d_grad_f && !d_grad_alpha) return set_err(h, BPLTV_E_ARG, "%s: both outputs are NULL", who);
+    const bpltv_params p0 = resolve(pp);
+    if (int prc = unrolled_check_params(h, p0, who)) return prc;
+    if (!d_tape_user) {
+        if (!h->tape_valid) return set_err(h, BPLTV_E_NODATA, "%s: the handle holds no tape (bpltv_unrolled_denoise has not run)", who);
+        if (h->tape_maxiter != p0.maxiter || h->tape_am != am || h->tape_an != an || h->tape_accel != (p0.accel ? 1 : 0) ||
+            h->tape_tau0 != p0.tau0 || h->tape_sigma0 != p0.sigma0 || h->tape_opnorm != p0.opnorm)
+            return set_err(h, BPLTV_E_ARG, "%s: the handle's tape was recorded with maxiter = %d, a %dx%d parameter and other steps than this call's (%d, %dx%d)",
+                           who, h->tape_maxiter, h->tape_am, h->tape_an, p0.maxiter, am, an);
+    }
+    WeightedPlan pl;
+    if (int prc = unrolled_plan(h, p0, UN_REV_T, &pl)) return prc;
+    const size_t tot = h->tot, npx = h->npx;
+    if (!h->d_unr)
+        if (int arc = alloc_all(h, {{(void**)&h->d_unr, 9 * tot * sizeof(double)}}, "reverse sweep")) return arc;
+    bpltv_params p;
+    GradCtx g;
+    if (int rc = stage_param(h, who, alpha, dev, am, an, 1, false, 0, pp, nullptr, 1, {{d_gu, tot, "cotangent gu"}}, &p, &g)) return rc;
+    const int M = h->M, N = h->N, O = h->O, T = pl.T, K = p.maxiter;
+    const bool amap = am == M && an == N && !(M == 1 && N == 1);
+    if (d_grad_alpha && !amap)
+        if (int rc = ensure(h, &h->d_red, &h->red_cap, (size_t)am * an * O)) return rc;
+    h->has_per_image = false;
+    double* d_tab = nullptr;
+    if (int rc = get_table(h, p, &d_tab, 8.0, 0)) return rc;
+    const double* d_tape = d_tape_user ? d_tape_user : h->d_tape;
+    double* S[2][3];
+    for (int s = 0; s < 2; ++s)
+        for (int c = 0; c < 3; ++c) S[s][c] = h->d_unr + (size_t)(3 * s + c) * tot;
+    double *d_gf = h->d_unr + 6 * tot, *d_ga = h->d_unr + 7 * tot, *d_g0 = h->d_unr + 8 * tot;
+    const bpltv_stats_t kept = h->st;
+    HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_g0, d_gu, tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    ChainSolve j;
+    j.model = MODEL_UN; j.nplanes = 3; j.state0 = S[0];
+    j.nimg = O; j.niter = K; j.T = T;
+    const int tiles = pl.nTi * pl.nTj * O;
+    j.chains = plan_chains(p.reserved[1], tiles, h->ncu, O, 2);
+    j.serial = (p.reserved[2] & 1) != 0; j.helper_thread = !(p.reserved[2] & 8);
+    j.bytes_per_px_iter = 0.0;   // (the driver's solve statistics are not this call's: `kept` goes back below)
+    j.key = GraphKey{K, T, 1, am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_tape, (const void*)d_tab, 0, (const void*)g.alpha, 0, 0};
+    j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
+        int step = stagger ? T / 2 : T;
+        for (int it = it0; it < it1; it += step, step = T) {   // `it` counts reverse steps: step r undoes iteration K - 1 - r
+            const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
+            UnrolledRevArgs a;
+            a.gxin = (it == 0) ? d_g0 : S[cur][0]; a.gy1in = S[cur][1]; a.gy2in = S[cur][2];
+            a.gxout = S[nxt][0]; a.gy1out = S[nxt][1]; a.gy2out = S[nxt][2];
+            a.gf = d_gf; a.ga = d_ga; a.tape = d_tape; a.alpha = g.alpha; a.tab = d_tab; a.plane = tot;
+            a.am = am; a.an = an;
+            a.khi = K - 1 - it; a.nit = std::min(step, it1 - it);
+            a.M = M; a.N = N; a.halo = T; a.first = (it == 0) ? 1 : 0; a.img0 = lo;
+            hipLaunchKernelGGL(unrolled_reverse_tile_kernel, dim3(pl.nTi, pl.nTj, hi - lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), st, a);
+            cur = nxt;
+        }
+        return cur;
+    };
+    int buf = 0;
+    const int rc = run_chains(h, p, j, &buf);
+    h->st = kept;
+    if (rc) return rc;
+    if (d_grad_f)
+        hipLaunchKernelGGL(unrolled_gradf_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, d_gf, S[buf][0], tot, d_grad_f);
+    if (d_grad_alpha && amap) {   // the per-pixel sums over the images, in image order; then per patch (calc_adjoint) or over everything
+        hipLaunchKernelGGL(map_sum_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, d_ga, npx, O, d_grad_alpha);
+    } else if (d_grad_alpha) {
+        hipLaunchKernelGGL(patch_sum_kernel, dim3(am * an, O), dim3(256), 0, h->stream, d_ga, M, N, O, am, an, O, 1, h->d_red);
+        hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, O, am * an, 1.0, d_grad_alpha, (double*)nullptr);
+    }
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
+    h->st.adjoint_ms = ms;
+    h->st.adjoint_method = 7;
+    h->st.reg_gradient_used = 0;
+    h->st.adjoint_attempts = 1;
+    h->st.adjoint_chunks = 1;
+    h->st.hb_sync = 0;
+    h->st.kappa_used = 0.0;
+    h->st.adjoint_residual = 0.0;
+    h->st.adjoint_residual_raw = 0.0;
+    return BPLTV_OK;
 }
 
 }  // namespace
@@ -3371,7 +3590,7 @@ int bpltv_destroy(bpltv_t* h) {
     if (h->f32_sweep_alpha) (void)hipFree(h->f32_sweep_alpha);
     void* ptrs[] = {h->d_ubar, h->d_f, h->d_alpha, h->d_sweep_alpha, h->d_partial, h->d_red, h->d_perimg, h->d_scalar, h->d_coef,
                     h->d_band4, h->d_bcr, h->d_L, h->d_invF, h->d_invB, h->d_L1, h->d_dump, h->d_Lm, h->d_spill, h->d_p, h->d_r, h->d_gpix, h->d_resn, h->d_fail, h->d_u2, h->d_ubar2,
-                    h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres, h->d_w, h->d_wst};
+                    h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres, h->d_w, h->d_wst, h->d_tape, h->d_unr};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (int s = 0; s < 2; ++s)
@@ -3609,6 +3828,74 @@ int bpltv_weighted_vjp_device(bpltv_t* h, const double* d_u, const double* d_f, 
     WallTimer wt;
     HIPCHK(h, hipSetDevice(h->device));
     const int rc = weighted_vjp_common(h, d_u, d_f, d_w, wo, d_alpha, true, am, an, pp, d_gu, d_grad_f, d_grad_alpha, d_grad_w);
+    if (rc) return rc;
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
+int bpltv_unrolled_tape_doubles(bpltv_t* h, const bpltv_params* pp, unsigned long long* n_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (!n_out) return set_err(h, BPLTV_E_ARG, "bpltv_unrolled_tape_doubles: null pointer");
+    const bpltv_params p = resolve(pp);
+    if (p.maxiter < 1) return set_err(h, BPLTV_E_ARG, "bpltv_unrolled_tape_doubles: maxiter = %d (at least one iteration)", p.maxiter);
+    *n_out = 2ull * (unsigned long long)p.maxiter * (unsigned long long)h->M * h->N * h->O;
+    return BPLTV_OK;
+}
+
+int bpltv_unrolled_denoise(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, double* u_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_unrolled_denoise", true, [&](bpltv_t* c) { return bpltv_unrolled_denoise(c, alpha, am, an, pp, u_out); }, kUnrolled);
+    return unrolled_denoise_common(h, alpha, false, am, an, pp, nullptr, u_out);
+}
+
+int bpltv_unrolled_denoise_device(bpltv_t* h, const double* d_alpha, int am, int an, const bpltv_params* pp, double* d_tape) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_unrolled_denoise_device", true, [&](bpltv_t* c) { return bpltv_unrolled_denoise_device(c, d_alpha, am, an, pp, d_tape); }, kUnrolled);
+    return unrolled_denoise_common(h, d_alpha, true, am, an, pp, d_tape, nullptr);
+}
+
+int bpltv_unrolled_vjp(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, const double* gu,
+                       double* grad_f_out, double* grad_alpha_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_unrolled_vjp", false, [&](bpltv_t* c) { return bpltv_unrolled_vjp(c, alpha, am, an, pp, gu, grad_f_out, grad_alpha_out); }, kUnrolled);
+    if (!gu || !alpha) return set_err(h, BPLTV_E_ARG, "unrolled_vjp: null pointer");
+    if (!grad_f_out && !grad_alpha_out) return set_err(h, BPLTV_E_ARG, "unrolled_vjp: both outputs are NULL");
+    if (am < 1 || an < 1 || am > h->M || an > h->N)
+        return set_err(h, BPLTV_E_ARG, "unrolled_vjp: parameter shape %dx%d (image %dx%d)", am, an, h->M, h->N);
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->d_u2) {
+        HIPCHK(h, hipMalloc((void**)&h->d_u2, h->tot * sizeof(double)));
+        HIPCHK(h, hipMalloc((void**)&h->d_ubar2, h->tot * sizeof(double)));
+    }
+    if (grad_f_out && !h->d_gf2) HIPCHK(h, hipMalloc((void**)&h->d_gf2, h->tot * sizeof(double)));
+    HIPCHK(h, hipMemcpyAsync(h->d_ubar2, gu, h->tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    const size_t P = (size_t)am * an;
+    int rc = ensure(h, &h->d_vjp, &h->vjp_cap, 4 + 2 * P);
+    if (rc) return rc;
+    double* d_ga = grad_alpha_out ? h->d_vjp + 4 + P : nullptr;
+    rc = unrolled_vjp_common(h, nullptr, alpha, false, am, an, pp, h->d_ubar2, grad_f_out ? h->d_gf2 : nullptr, d_ga);
+    if (rc) return rc;
+    if (grad_f_out) HIPCHK(h, hipMemcpyAsync(grad_f_out, h->d_gf2, h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (grad_alpha_out) HIPCHK(h, hipMemcpyAsync(grad_alpha_out, d_ga, sizeof(double) * P, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
+int bpltv_unrolled_vjp_device(bpltv_t* h, const double* d_tape, const double* d_alpha, int am, int an, const bpltv_params* pp,
+                              const double* d_gu, double* d_grad_f, double* d_grad_alpha) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_unrolled_vjp_device", false, [&](bpltv_t* c) {
+            return bpltv_unrolled_vjp_device(c, d_tape, d_alpha, am, an, pp, d_gu, d_grad_f, d_grad_alpha);
+        }, kUnrolled);
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int rc = unrolled_vjp_common(h, d_tape, d_alpha, true, am, an, pp, d_gu, d_grad_f, d_grad_alpha);
     if (rc) return rc;
     h->st.total_ms = wt.ms();
     return BPLTV_OK;

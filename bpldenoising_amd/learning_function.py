@@ -401,6 +401,58 @@ class TVSolver:
                                                         C.c_void_p(grad_alpha_ptr or None),
                                                         C.c_void_p(grad_w_ptr or None)))
 
+    # -- reverse mode through the iterations (bpltv_unrolled_*) --------------------------------------------------
+    def unrolled_tape_doubles(self, **kw):
+        """Doubles of the tape an unrolled solve with these params records: 2 * maxiter * M*N*O."""
+        p = self.params(**kw)
+        n = C.c_ulonglong(0)
+        self._check(self._lib.bpltv_unrolled_tape_doubles(self._h, C.byref(p), C.byref(n)))
+        return int(n.value)
+
+    def unrolled_denoise(self, x, fetch=True, **kw):
+        """denoise(x) with rho = 0 -- the same u bit for bit -- that also records the tape of the iterations in the
+        handle, for unrolled_vjp with the same x and params (bpltv_unrolled_denoise)."""
+        a, am, an, _ = _alpha_arg(x)
+        p = self.params(**kw)
+        u = np.empty((self.O, self.N, self.M)) if fetch else None
+        self._check(self._lib.bpltv_unrolled_denoise(self._h, _ptr(a), am, an, C.byref(p), _ptr(u) if fetch else None))
+        return u
+
+    def unrolled_denoise_device(self, alpha_ptr, am=1, an=1, tape_ptr=None, **kw):
+        """bpltv_unrolled_denoise_device: the parameter resident in HBM, the result left there (u_device_ptr /
+        copy_u_device); tape_ptr: a caller-owned HBM buffer of unrolled_tape_doubles(**kw) doubles, or None / 0 for
+        the handle's own tape."""
+        p = self.params(**kw)
+        self._check(self._lib.bpltv_unrolled_denoise_device(self._h, C.c_void_p(alpha_ptr), int(am), int(an),
+                                                            C.byref(p), C.c_void_p(tape_ptr or None)))
+
+    def unrolled_vjp(self, x, gu, want_f=True, want_alpha=True, **kw):
+        """Vector-Jacobian product of the maxiter-step map u = unrolled_denoise(x) for the cotangent gu = dL/du, by a
+        reverse sweep over the handle's tape (bpltv_unrolled_vjp): (grad_f, grad_x).  x and the params must be those
+        of the solve.  gu: (O, N, M); grad_f has its shape (None unless want_f), grad_x the type / shape of x (None
+        unless want_alpha)."""
+        if not (want_f or want_alpha):
+            raise ValueError("unrolled_vjp: want_f and want_alpha are both False")
+        a, am, an, scalar = _alpha_arg(x)
+        p = self.params(**kw)
+        gu = self._batch(gu, "gu")
+        gf = np.empty((self.O, self.N, self.M)) if want_f else None
+        ga = np.empty(am * an) if want_alpha else None
+        self._check(self._lib.bpltv_unrolled_vjp(self._h, _ptr(a), am, an, C.byref(p), _ptr(gu),
+                                                 _ptr(gf) if want_f else None, _ptr(ga) if want_alpha else None))
+        if ga is not None:
+            ga = float(ga[0]) if scalar else ga.reshape(an, am)
+        return gf, ga
+
+    def unrolled_vjp_device(self, tape_ptr, alpha_ptr, am, an, gu_ptr, grad_f_ptr, grad_alpha_ptr, **kw):
+        """bpltv_unrolled_vjp_device: the tape (None / 0: the handle's own), the parameter, gu and the outputs resident
+        in HBM (raw device pointers); either output pointer may be 0 / None, not both."""
+        p = self.params(**kw)
+        self._check(self._lib.bpltv_unrolled_vjp_device(self._h, C.c_void_p(tape_ptr or None), C.c_void_p(alpha_ptr),
+                                                        int(am), int(an), C.byref(p), C.c_void_p(gu_ptr),
+                                                        C.c_void_p(grad_f_ptr or None),
+                                                        C.c_void_p(grad_alpha_ptr or None)))
+
     # -- forward mode (bpltv_jvp / bpltv_gauss_newton) -------------------------------------------------------
     def _tangents(self, what, df, dalpha, ashape):
         """(df, dalpha, K, batched): the tangents as contiguous (K, ...) stacks, either None; batched = a leading K was

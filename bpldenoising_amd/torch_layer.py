@@ -47,6 +47,16 @@ one bpltv_weighted_vjp_device call and returns f.grad, alpha.grad and w.grad (fo
 batch); the linearisation is tv_denoise's reg=False.  Like the sum-of-regularisers functions it carries no jvp:
 forward-mode AD over it raises torch's "not implemented" error.
 
+    u = tv_denoise_unrolled(f, alpha, maxiter=50)          # reverse mode through the iterations (bpltv_unrolled_*)
+
+f and alpha as for tv_denoise, and the same u bit for bit (rho, init and order must stay 0); but backward is the derivative
+of the maxiter-step map itself -- what finite differences of the layer's own output give for any iteration count --
+where tv_denoise's is implicit differentiation of the exact minimiser.  The forward pass records the dual before every
+projection in a tape it allocates as a torch tensor (2 * maxiter * B*H*W doubles) and saves for backward, which is one
+bpltv_unrolled_vjp_device call: a reverse sweep over that tape, no factorisation, no active-set threshold.  Use it for
+a layer with a fixed, small iteration count; the reference's learning function uses tv_denoise.  It carries no jvp:
+forward-mode AD over it raises torch's "not implemented" error.
+
 Streams: the library runs its kernels on its own HIP streams and blocks until they are done.  Every call below first
 synchronises the tensors' current torch stream, so that the library reads inputs torch has finished writing; its
 outputs are complete when the call returns.
@@ -528,3 +538,62 @@ def tv_denoise_weighted(f, alpha, w, **solver_kw):
     in value and in f.grad / alpha.grad.  solver_kw: the solver parameters of TVSolver.params (rho, init and order must
     stay 0), used by the forward solve and the adjoint alike."""
     return TVDenoiseWeightedFunction.apply(f, alpha, w, solver_kw)
+
+
+class TVDenoiseUnrolledFunction(torch.autograd.Function):
+    """autograd.Function of tv_denoise_unrolled (below); apply(f, alpha, solver_kw).  No jvp."""
+
+    @staticmethod
+    def forward(ctx, f, alpha, solver_kw):
+        O, N, M, am, an = _check_args(f, alpha)
+        index = f.device.index if f.device.index is not None else torch.cuda.current_device()
+        s = _solver(index, M, N, O)
+        fc = f.detach().contiguous()
+        ac = alpha.detach().contiguous()
+        u = torch.empty_like(fc)
+        # the tape is this call's own: a second forward pass on the handle before backward does not overwrite it
+        tape = torch.empty(s.unrolled_tape_doubles(**solver_kw), dtype=torch.float64, device=f.device)
+        _sync(f.device)
+        s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
+        s.unrolled_denoise_device(ac.data_ptr(), am, an, tape_ptr=tape.data_ptr(), **solver_kw)
+        s.copy_u_device(u.data_ptr())
+        ctx.save_for_backward(tape, ac)
+        ctx.solver, ctx.am, ctx.an, ctx.solver_kw = s, am, an, dict(solver_kw)
+        return u
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gu):
+        need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_f or need_a):
+            return None, None, None
+        tape, alpha = ctx.saved_tensors
+        gu = gu.to(dtype=torch.float64).contiguous()
+        gf = torch.empty_like(gu) if need_f else None
+        ga = torch.empty(ctx.am * ctx.an, dtype=torch.float64, device=gu.device) if need_a else None
+        _sync(gu.device)
+        ctx.solver.unrolled_vjp_device(tape.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(),
+                                       gf.data_ptr() if need_f else None, ga.data_ptr() if need_a else None,
+                                       **ctx.solver_kw)
+        return gf, (ga.reshape(alpha.shape) if need_a else None), None
+
+
+def tv_denoise_unrolled(f, alpha, **solver_kw):
+    """u = denoise(f, alpha) by exactly maxiter PDHG iterations (TVSolver.unrolled_denoise_device: tv_denoise's u bit for
+    bit), differentiable in f and alpha THROUGH the iterations: backward is the exact derivative of the maxiter-step map
+    (TVSolver.unrolled_vjp_device), not the implicit gradient of the minimiser.  solver_kw: the solver parameters of
+    TVSolver.params (rho, init and order must stay 0), used by the forward solve and the reverse sweep alike."""
+    return TVDenoiseUnrolledFunction.apply(f, alpha, solver_kw)
+
+
+class TVDenoiseUnrolled(torch.nn.Module):
+    """TVDenoise with tv_denoise_unrolled's backward: a learnable scalar, patch parameter or pixel map behind a fixed
+    number of iterations (solver_kw: maxiter, ...).  Move it to the device of its inputs with .to(device)."""
+
+    def __init__(self, alpha, **solver_kw):
+        super().__init__()
+        self.alpha = torch.nn.Parameter(torch.as_tensor(alpha, dtype=torch.float64).clone())
+        self.solver_kw = dict(solver_kw)
+
+    def forward(self, f):
+        return tv_denoise_unrolled(f, self.alpha, **self.solver_kw)

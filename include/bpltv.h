@@ -131,7 +131,8 @@ typedef struct bpltv_stats {
     int adjoint_method;        /* 1 banded Cholesky (LDS window), 2 block cyclic reduction,
                                   3 banded Cholesky (HBM band), 4 banded LU (sum of regularisers, row-scaled
                                   gradient_reg system, with reserved[4] = 1), 5 nested-dissection (multifrontal)
-                                  Cholesky, 6 nested-dissection LU (that row-scaled system, the default)  */
+                                  Cholesky, 6 nested-dissection LU (that row-scaled system, the default),
+                                  7 reverse sweep over the taped iterations (bpltv_unrolled_vjp)          */
     int reg_gradient_used;     /* 1 if the last evaluate took the gradient_reg branch             */
     int ngpus;                 /* distinct devices behind this handle (1 for bpltv_create)        */
     int shards;                /* image shards (= worker threads) behind this handle              */
@@ -357,6 +358,45 @@ int bpltv_weighted_vjp(bpltv_t *h, const double *u, const double *f, const doubl
 int bpltv_weighted_vjp_device(bpltv_t *h, const double *d_u, const double *d_f, const double *d_w, int wo,
                               const double *d_alpha, int am, int an, const bpltv_params *p, const double *d_gu,
                               double *d_grad_f, double *d_grad_alpha, double *d_grad_w);
+
+/* Reverse mode through the PDHG iterations themselves.  bpltv_vjp differentiates the exact minimiser
+ * (the reference's adjoint system); these differentiate what a fixed number of iterations computed: the derivative of the
+ * K-step map, exact for any K, with no active-set threshold, no kappa and no factorisation.  TV model, Float64 (also on
+ * dtype = 32 handles), one parameter shared by the batch (alpha, am, an as bpltv_denoise); f is the resident dataset
+ * (BPLTV_E_NODATA without one).
+ *
+ * bpltv_unrolled_denoise runs bpltv_denoise's recurrence with rho = 0, init = 0, order = 0 -- u is bpltv_denoise's bit for bit
+ * -- and records, in every iteration, the dual before its projection: the tape, 2 * maxiter * M*N*O doubles
+ * (bpltv_unrolled_tape_doubles; its layout is private).  params: opnorm, tau0, sigma0, accel, maxiter, tile_iters, use_graph,
+ * reserved[1] and reserved[2] apply; rho, init and order must be 0 (BPLTV_E_UNSUPPORTED); check_every / gap_tol are ignored
+ * (always maxiter iterations); maxiter < 1 is BPLTV_E_ARG.  The parameter is checked as bpltv_denoise checks it (finite and
+ * >= 0, on the host or on the device); every rejection comes before anything of the handle changes.  The solve is a TV solve
+ * and becomes the handle's last solve: bpltv_u_device, bpltv_copy_u_device and bpltv_duality_gap work as after bpltv_denoise.
+ * stats: iterations, launches, tile_iters, tiles, pdhg_ms, total_ms; bytes_per_px_iter = 72 (scalar / patch parameter) or 80
+ * (map); pdhg_variant = 0.  The results do not depend on tile_iters, on the launch chains or on use_graph, and the unrolled
+ * calls never replay another solve's captured graphs, nor the reverse.
+ *
+ * The tape: d_tape is a caller-owned HBM buffer of bpltv_unrolled_tape_doubles doubles, so that two solves on one handle do not
+ * overwrite each other's tape (the torch layer).  A NULL d_tape, and the host forms always, use a tape owned by the handle:
+ * allocated on demand, only growing, freed by bpltv_destroy; when it cannot be allocated the call returns BPLTV_E_NOMEM and the
+ * handle stays as it was.  The handle remembers maxiter, am, an and the step parameters (tau0, sigma0, accel, opnorm) its tape was
+ * recorded with: a VJP on the handle's tape returns BPLTV_E_NODATA if there is none and BPLTV_E_ARG if they differ.  With a
+ * caller's tape that match -- same handle geometry, same params, same parameter shape and VALUES as the solve that wrote it --
+ * is the caller's contract; nothing checks it.
+ *
+ * bpltv_unrolled_vjp: for a cotangent gu = dL/du (M*N*O doubles, finite) grad_f_out = dL/df (M*N*O doubles) and grad_alpha_out
+ * = dL/dalpha (am*an doubles: the per-pixel terms summed over the images in image order, then over all pixels, over each
+ * patch, or not at all for a map; fixed order, no atomics).  Either output may be NULL, not both (BPLTV_E_ARG).  alpha must be the
+ * parameter of the solve.  The VJP does not read f.  It stages its parameter apart, as bpltv_vjp does, and leaves the last
+ * solve untouched.  stats: adjoint_ms is the HIP-event time of the reverse sweep, adjoint_method = 7.  Multi-device handles
+ * over more than one shard: BPLTV_E_UNSUPPORTED (the four solve and VJP functions). */
+int bpltv_unrolled_tape_doubles(bpltv_t *h, const bpltv_params *p, unsigned long long *n_out);   /* 2*maxiter*M*N*O */
+int bpltv_unrolled_denoise(bpltv_t *h, const double *alpha, int am, int an, const bpltv_params *p, double *u_out);
+int bpltv_unrolled_denoise_device(bpltv_t *h, const double *d_alpha, int am, int an, const bpltv_params *p, double *d_tape);
+int bpltv_unrolled_vjp(bpltv_t *h, const double *alpha, int am, int an, const bpltv_params *p,
+                       const double *gu, double *grad_f_out, double *grad_alpha_out);
+int bpltv_unrolled_vjp_device(bpltv_t *h, const double *d_tape, const double *d_alpha, int am, int an,
+                              const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alpha);
 
 /* Jacobian-vector product of u = denoise(f, alpha) (TV model): du for tangents (df, dalpha), defined as the linear map
  * whose transpose bpltv_vjp computes, in every branch -- <gu, du> = <grad_f(gu), df> + <grad_alpha(gu), dalpha> for any
