@@ -30,6 +30,7 @@
 #include "sumregs_kernels.hpp"
 #include "weighted_kernels.hpp"
 #include "unrolled_kernels.hpp"
+#include "unrolled_jvp_kernels.hpp"
 #include "multi_gpu.hpp"
 
 using namespace bpltv;
@@ -185,7 +186,7 @@ const Variant kVariants[] = {
 };
 
 // The models whose solves the shared launch driver (run_chains) runs
-enum Model { MODEL_TV = 0, MODEL_SR = 1, MODEL_W = 2, MODEL_UN = 3, NMODELS = 4 };   // MODEL_UN: the taped solve and its reverse sweep
+enum Model { MODEL_TV = 0, MODEL_SR = 1, MODEL_W = 2, MODEL_UN = 3, NMODELS = 4 };   // MODEL_UN: the taped solve, its reverse sweep and the tangent sweep
 
 // What identifies a launch sequence built into graphs: everything its kernel arguments and its cut into launches depend
 // on.  One key type for all models (a field a model does not use stays 0); each model has a cache of its own
@@ -195,7 +196,8 @@ struct GraphKey {
     double rho, tau0, sigma0;
     int accel, dbg, nimg;
     const void* state; // state set 0 of the solve context: a sweep never replays a dataset-context graph, nor the reverse
-                       // (MODEL_UN: the tape the launches write or read, with variant 0 = taped solve, 1 = reverse sweep)
+                       // (MODEL_UN: the tape the launches write or read, with variant 0 = taped solve, 1 = reverse sweep; 2 ... 5 = tangent
+                       // sweep, whose planes stand here instead)
     const void* tab;   // step table (one per (maxiter, steps, L, dual-first shift, gamma): TabKey)
     int from_state;    // 1: the sequence starts from a prepared state (params.init / order), not from x = f, y = 0
     const void* alpha; // the parameter the launches read: a sweep's blocks and the dataset's parameter are different
@@ -430,6 +432,9 @@ struct bpltv_handle {
     int tape_maxiter = 0, tape_am = 0, tape_an = 0, tape_accel = 0;
     double tape_tau0 = 0.0, tape_sigma0 = 0.0, tape_opnorm = 0.0;
     double* d_unr = nullptr;                        // 9 * M*N*O doubles
+    // forward mode through the iterations (unrolled_jvp_kernels.hpp): the tangent sweep's planes [2 sets x (x, y1, y2, dx, dy1,
+    // dy2) | df | dalpha], allocated on first use and never moved
+    double* d_ujv = nullptr;                        // 14 * M*N*O doubles
     bpltv_stats_t st;
     std::string err;
 };
@@ -3470,6 +3475,101 @@ int unrolled_vjp_common(bpltv_t* h, const double* d_tape_user, const double* alp
     return BPLTV_OK;
 }
 
+// bpltv_unrolled_jvp(_device) and bpltv_unrolled_gauss_newton on a single-device handle (unrolled_jvp_kernels.hpp, DESIGN.md
+// section 4.7): ndir tangent sweeps, one after the other, each the same launch sequence (direction d of a call is bitwise the
+// call with that direction alone).  The tangents d_df / d_dalpha (either may be nullptr: a zero tangent) and d_du live in HBM,
+// direction-major; alpha on the host or (dev) in HBM.  Every sweep runs in the planes of d_ujv = [2 sets x (x, y1, y2, dx, dy1,
+// dy2) | df | dalpha] on the staged parameter (stage_param), with the direction's tangents copied into the workspace first, so
+// that no captured graph holds a caller's address and the last solve, the tape and the solve statistics stay as they were.
+// d_u (nullable): receives the primal result, bpltv_denoise's u.  *x_res (nullable): the workspace plane that holds it.
+int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool dev, int am, int an, const bpltv_params* pp, int ndir,
+                        const double* d_df, const double* d_dalpha, double* d_du, double* d_u, const double** x_res) {
+    if (!alpha || !d_du) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
+    if (ndir < 1) return set_err(h, BPLTV_E_ARG, "%s: ndir = %d (at least one direction)", who, ndir);
+    if (!d_df && !d_dalpha) return set_err(h, BPLTV_E_ARG, "%s: both tangents are NULL", who);
+    if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: bpltv_set_data has not been called", who);
+    const bpltv_params p0 = resolve(pp);
+    if (int prc = unrolled_check_params(h, p0, who)) return prc;
+    WeightedPlan pl;
+    if (int prc = unrolled_plan(h, p0, PDHG_MAX_T, &pl)) return prc;
+    const size_t tot = h->tot;
+    if (!h->d_ujv) {
+        if (int arc = alloc_all(h, {{(void**)&h->d_ujv, 14 * tot * sizeof(double)}}, "tangent sweep")) return arc;
+        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&unrolled_jvp_tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                      (int)unrolled_jvp_lds_bytes()));
+    }
+    const size_t P = (size_t)am * an;   // (stage_param checks the shape before it reads anything)
+    bpltv_params p;
+    GradCtx g;
+    if (int rc = stage_param(h, who, alpha, dev, am, an, 1, false, 0, pp, nullptr, 1,
+                             {{d_df, (size_t)ndir * tot, "tangent df"}, {d_dalpha, (size_t)ndir * P, "tangent dalpha"}}, &p, &g))
+        return rc;
+    double* d_tab = nullptr;
+    if (int rc = get_table(h, p, &d_tab, 8.0, 0)) return rc;
+    const int M = h->M, N = h->N, O = h->O, T = pl.T, K = p.maxiter;
+    double* S[2][6];
+    for (int s = 0; s < 2; ++s)
+        for (int c = 0; c < 6; ++c) S[s][c] = h->d_ujv + (size_t)(6 * s + c) * tot;
+    double *d_dfc = h->d_ujv + 12 * tot, *d_dac = h->d_ujv + 13 * tot;   // (a parameter has at most M*N <= tot entries)
+    const bpltv_stats_t kept = h->st;
+    ChainSolve j;
+    j.model = MODEL_UN; j.nplanes = 6; j.state0 = S[0];
+    j.nimg = O; j.niter = K; j.T = T;
+    const int tiles = pl.nTi * pl.nTj * O;
+    j.chains = plan_chains(p.reserved[1], tiles, h->ncu, O, 2);
+    j.serial = (p.reserved[2] & 1) != 0; j.helper_thread = !(p.reserved[2] & 8);
+    j.bytes_per_px_iter = 0.0;   // (the driver's solve statistics are not this call's: `kept` goes back below)
+    // variant 2 ... 5: a tangent sweep, by which tangents it reads (0 = taped solve, 1 = reverse sweep)
+    j.key = GraphKey{K, T, 2 + (d_df ? 1 : 0) + (d_dalpha ? 2 : 0), am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)h->d_ujv,
+                     (const void*)d_tab, 0, (const void*)g.alpha, 0, 0};
+    j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
+        int step = stagger ? T / 2 : T;
+        for (int it = it0; it < it1; it += step, step = T) {
+            const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
+            UnrolledJvpArgs a;
+            for (int c = 0; c < 6; ++c) { a.in[c] = S[cur][c]; a.out[c] = S[nxt][c]; }
+            a.f = h->d_f; a.df = d_df ? d_dfc : nullptr; a.alpha = g.alpha; a.dalpha = d_dalpha ? d_dac : nullptr; a.tab = d_tab;
+            a.am = am; a.an = an;
+            a.it0 = it; a.nit = std::min(step, it1 - it);
+            a.M = M; a.N = N; a.halo = T; a.first = (it == 0) ? 1 : 0; a.img0 = lo;
+            hipLaunchKernelGGL(unrolled_jvp_tile_kernel, dim3(pl.nTi, pl.nTj, hi - lo), dim3(UN_R * UN_R), unrolled_jvp_lds_bytes(), st, a);
+            cur = nxt;
+        }
+        return cur;
+    };
+    int rc = hipEventRecord(h->ev[2], h->stream) == hipSuccess ? (int)BPLTV_OK : set_err(h, BPLTV_E_HIP, "%s: hipEventRecord failed", who);
+    int buf = 0;
+    for (int d = 0; d < ndir && rc == BPLTV_OK; ++d) {
+        hipError_t e = hipSuccess;
+        if (d_df) e = hipMemcpyAsync(d_dfc, d_df + (size_t)d * tot, tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+        if (d_dalpha && e == hipSuccess) e = hipMemcpyAsync(d_dac, d_dalpha + (size_t)d * P, P * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+        if (e != hipSuccess) { rc = set_err(h, BPLTV_E_HIP, "%s: copy of the tangents failed: %s", who, hipGetErrorString(e)); break; }
+        rc = run_chains(h, p, j, &buf);
+        if (rc) break;
+        e = hipMemcpyAsync(d_du + (size_t)d * tot, S[buf][3], tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+        if (e != hipSuccess) rc = set_err(h, BPLTV_E_HIP, "%s: copy of du failed: %s", who, hipGetErrorString(e));
+    }
+    h->st = kept;
+    if (rc) return rc;
+    if (d_u) HIPCHK(h, hipMemcpyAsync(d_u, S[buf][0], tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
+    h->st.adjoint_ms = ms;
+    h->st.adjoint_method = 8;
+    if (x_res) *x_res = S[buf][0];
+    return BPLTV_OK;
+}
+
+// n entries of a host tangent array (nullable), all finite
+int check_tangent_host(bpltv_t* h, const char* who, const char* name, const double* a, size_t n) {
+    if (!a) return BPLTV_OK;
+    for (size_t e = 0; e < n; ++e)
+        if (!std::isfinite(a[e])) return set_err(h, BPLTV_E_ARG, "%s: the %s must be finite (entry %zu = %g)", who, name, e, a[e]);
+    return BPLTV_OK;
+}
+
 }  // namespace
 
 // ============================================================================================
@@ -3590,7 +3690,7 @@ int bpltv_destroy(bpltv_t* h) {
     if (h->f32_sweep_alpha) (void)hipFree(h->f32_sweep_alpha);
     void* ptrs[] = {h->d_ubar, h->d_f, h->d_alpha, h->d_sweep_alpha, h->d_partial, h->d_red, h->d_perimg, h->d_scalar, h->d_coef,
                     h->d_band4, h->d_bcr, h->d_L, h->d_invF, h->d_invB, h->d_L1, h->d_dump, h->d_Lm, h->d_spill, h->d_p, h->d_r, h->d_gpix, h->d_resn, h->d_fail, h->d_u2, h->d_ubar2,
-                    h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres, h->d_w, h->d_wst, h->d_tape, h->d_unr};
+                    h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres, h->d_w, h->d_wst, h->d_tape, h->d_unr, h->d_ujv};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (int s = 0; s < 2; ++s)
@@ -3898,6 +3998,100 @@ int bpltv_unrolled_vjp_device(bpltv_t* h, const double* d_tape, const double* d_
     const int rc = unrolled_vjp_common(h, d_tape, d_alpha, true, am, an, pp, d_gu, d_grad_f, d_grad_alpha);
     if (rc) return rc;
     h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
+int bpltv_unrolled_jvp(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, int ndir, const double* df,
+                       const double* dalpha, double* du_out, double* u_out) {
+    const char* who = "unrolled_jvp";
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_unrolled_jvp", false, [&](bpltv_t* c) { return bpltv_unrolled_jvp(c, alpha, am, an, pp, ndir, df, dalpha, du_out, u_out); }, kUnrolled);
+    if (!alpha || !du_out) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
+    if (ndir < 1) return set_err(h, BPLTV_E_ARG, "%s: ndir = %d (at least one direction)", who, ndir);
+    if (!df && !dalpha) return set_err(h, BPLTV_E_ARG, "%s: both tangents are NULL", who);
+    if (am < 1 || an < 1 || am > h->M || an > h->N)
+        return set_err(h, BPLTV_E_ARG, "%s: parameter shape %dx%d (image %dx%d)", who, am, an, h->M, h->N);
+    const size_t nt = (size_t)ndir * h->tot, na = (size_t)ndir * am * an;
+    if (int crc = check_tangent_host(h, who, "tangent df", df, nt)) return crc;
+    if (int crc = check_tangent_host(h, who, "tangent dalpha", dalpha, na)) return crc;
+    HIPCHK(h, hipSetDevice(h->device));
+    int rc = ensure(h, &h->d_jvp, &h->jvp_cap, 2 * nt + na + h->tot);   // [du | df | dalpha | u]
+    if (rc) return rc;
+    double *d_du = h->d_jvp, *d_df = df ? h->d_jvp + nt : nullptr, *d_da = dalpha ? h->d_jvp + 2 * nt : nullptr;
+    double* d_u = u_out ? h->d_jvp + 2 * nt + na : nullptr;
+    if (df) HIPCHK(h, hipMemcpyAsync(d_df, df, nt * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    if (dalpha) HIPCHK(h, hipMemcpyAsync(d_da, dalpha, na * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    rc = unrolled_jvp_common(h, who, alpha, false, am, an, pp, ndir, d_df, d_da, d_du, d_u, nullptr);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(du_out, d_du, nt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (u_out) HIPCHK(h, hipMemcpyAsync(u_out, d_u, h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BPLTV_OK;
+}
+
+int bpltv_unrolled_jvp_device(bpltv_t* h, const double* d_alpha, int am, int an, const bpltv_params* pp, int ndir, const double* d_df,
+                              const double* d_dalpha, double* d_du, double* d_u) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_unrolled_jvp_device", false, [&](bpltv_t* c) {
+            return bpltv_unrolled_jvp_device(c, d_alpha, am, an, pp, ndir, d_df, d_dalpha, d_du, d_u);
+        }, kUnrolled);
+    HIPCHK(h, hipSetDevice(h->device));
+    return unrolled_jvp_common(h, "unrolled_jvp", d_alpha, true, am, an, pp, ndir, d_df, d_dalpha, d_du, d_u, nullptr);
+}
+
+// Gradient and Gauss-Newton Hessian of the K-step loss 0.5||u_K(alpha) - ubar||^2 from P = am*an <= GN_MAXP unit-direction
+// tangent sweeps: [J | u_K - ubar] into gn_gram_kernel / gn_final_kernel, as gauss_newton does for the implicit Jacobian.
+int bpltv_unrolled_gauss_newton(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, double* cost_out,
+                                double* grad_out, double* hess_out) {
+    const char* who = "unrolled_gauss_newton";
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_unrolled_gauss_newton", false, [&](bpltv_t* c) {
+            return bpltv_unrolled_gauss_newton(c, alpha, am, an, pp, cost_out, grad_out, hess_out);
+        }, kUnrolled);
+    if (!alpha || !cost_out || !grad_out || !hess_out) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
+    if (am < 1 || an < 1 || am > h->M || an > h->N)
+        return set_err(h, BPLTV_E_ARG, "%s: parameter shape %dx%d (image %dx%d)", who, am, an, h->M, h->N);
+    const bool amap = am == h->M && an == h->N && !(h->M == 1 && h->N == 1);
+    if (amap || (long)am * an > GN_MAXP)
+        return set_err(h, BPLTV_E_UNSUPPORTED, "%s: a scalar or a patch parameter of at most %d entries (got %dx%d%s); use bpltv_unrolled_jvp for Jacobian columns",
+                       who, GN_MAXP, am, an, amap ? ", a pixel map" : "");
+    if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: bpltv_set_data has not been called", who);
+    const int P = am * an;
+    const size_t nout = (size_t)P + (size_t)P * P;
+    HIPCHK(h, hipSetDevice(h->device));
+    // workspace [J: P planes | unit directions P x P | per-image partials P (P + 1) O | grad, H | cost]
+    const size_t nJ = (size_t)P * h->tot, npart = (size_t)P * (P + 1) * h->O;
+    const size_t need = nJ + (size_t)P * P + npart + nout + 1;
+    if (h->jvp_cap < need) {
+        if (h->d_jvp) (void)hipFree(h->d_jvp);
+        h->d_jvp = nullptr; h->jvp_cap = 0;
+        const int arc = alloc_all(h, {{(void**)&h->d_jvp, need * sizeof(double)}}, "unrolled_gauss_newton: workspace of the Jacobian columns");
+        if (arc) return arc;
+        h->jvp_cap = need;
+    }
+    double *d_J = h->d_jvp, *d_e = d_J + nJ, *d_part = d_e + (size_t)P * P, *d_out = d_part + npart;
+    std::vector<double> eye((size_t)P * P, 0.0);
+    for (int j = 0; j < P; ++j) eye[(size_t)j * P + j] = 1.0;
+    HIPCHK(h, hipMemcpyAsync(d_e, eye.data(), eye.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));   // (eye is a local)
+    const double* d_x = nullptr;
+    int rc = unrolled_jvp_common(h, who, alpha, false, am, an, pp, P, nullptr, d_e, d_J, nullptr, &d_x);
+    if (rc) return rc;
+    h->has_per_image = false;   // compute_cost writes d_perimg and d_red
+    rc = compute_cost(h, d_x, h->d_ubar, d_out + nout);
+    if (rc) return rc;
+    hipLaunchKernelGGL(gn_gram_kernel, dim3(P + 1, P, h->O), dim3(256), 0, h->stream, d_J, d_x, h->d_ubar, (int)h->npx, h->O, P, d_part);
+    hipLaunchKernelGGL(gn_final_kernel, dim3((P * (P + 1) + 63) / 64), dim3(64), 0, h->stream, d_part, h->O, P, d_out);
+    HIPCHK(h, hipGetLastError());
+    std::vector<double> out(nout + 1);
+    HIPCHK(h, hipMemcpyAsync(out.data(), d_out, (nout + 1) * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    std::memcpy(grad_out, out.data(), P * sizeof(double));
+    std::memcpy(hess_out, out.data() + P, (size_t)P * P * sizeof(double));
+    *cost_out = out[nout];
     return BPLTV_OK;
 }
 

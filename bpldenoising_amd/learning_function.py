@@ -547,6 +547,48 @@ class TVSolver:
                                                  C.byref(p), _ptr(grad), _ptr(H)))
         return (float(grad[0]) if scalar else grad.reshape(an, am)), H
 
+    # -- forward mode through the iterations (bpltv_unrolled_jvp / bpltv_unrolled_gauss_newton) ---------------
+    def unrolled_jvp(self, x, df=None, dalpha=None, want_u=False, **kw):
+        """Jacobian-vector product of the maxiter-step map u = unrolled_denoise(x) of the resident f (bpltv_unrolled_jvp):
+        a tangent sweep through the iterations, no tape -- the linear map whose transpose unrolled_vjp computes.  df:
+        (O, N, M), or (K, O, N, M) for K directions; dalpha: shaped like x, or with a leading K; either may be None
+        (zero), not both.  Returns du of shape (O, N, M), or (K, O, N, M) when a leading K was given; with want_u,
+        (du, u) with u = denoise(x) bit for bit."""
+        a, am, an, scalar = _alpha_arg(x)
+        df, dalpha, K, batched = self._tangents("unrolled_jvp", df, dalpha, () if scalar else (an, am))
+        p = self.params(**kw)
+        du = np.empty((K, self.O, self.N, self.M))
+        u = np.empty((self.O, self.N, self.M)) if want_u else None
+        self._check(self._lib.bpltv_unrolled_jvp(self._h, _ptr(a), am, an, C.byref(p), K,
+                                                 _ptr(df) if df is not None else None,
+                                                 _ptr(dalpha) if dalpha is not None else None, _ptr(du),
+                                                 _ptr(u) if want_u else None))
+        du = du if batched else du[0]
+        return (du, u) if want_u else du
+
+    def unrolled_jvp_device(self, alpha_ptr, am, an, df_ptr, dalpha_ptr, du_ptr, u_ptr=None, ndir=1, **kw):
+        """bpltv_unrolled_jvp_device: the parameter (am*an doubles), df and du (ndir*M*N*O), dalpha (ndir*am*an) and u
+        (M*N*O) all resident in HBM (raw device pointers); either tangent pointer may be 0 / None, not both; u_ptr may
+        be 0 / None."""
+        p = self.params(**kw)
+        self._check(self._lib.bpltv_unrolled_jvp_device(self._h, C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p),
+                                                        int(ndir), C.c_void_p(df_ptr or None),
+                                                        C.c_void_p(dalpha_ptr or None), C.c_void_p(du_ptr),
+                                                        C.c_void_p(u_ptr or None)))
+
+    def unrolled_gauss_newton(self, x, **kw):
+        """Gauss-Newton model of the maxiter-step loss 0.5||u_K(x) - ubar||^2 on the resident dataset
+        (bpltv_unrolled_gauss_newton): (cost, grad, H) with grad = J^T (u_K - ubar) shaped like x and H = J^T J of shape
+        (P, P), P = x.size, ordered as numpy's x.ravel(); J by P tangent sweeps.  A float or an (n, m) patch parameter
+        with at most 16 entries."""
+        a, am, an, scalar = _alpha_arg(x)
+        p = self.params(**kw)
+        P = am * an
+        cost, grad, H = C.c_double(0.0), np.empty(P), np.empty((P, P))
+        self._check(self._lib.bpltv_unrolled_gauss_newton(self._h, _ptr(a), am, an, C.byref(p),
+                                                          C.byref(cost), _ptr(grad), _ptr(H)))
+        return float(cost.value), (float(grad[0]) if scalar else grad.reshape(an, am)), H
+
     # -- one parameter per image (bpltv_denoise_each / bpltv_vjp_each) ---------------------------------------
     def _each_arg(self, alphas):
         """alphas: (O,) scalars or (O, n, m) blocks (numpy (n, m) == Julia m x n), one per image."""

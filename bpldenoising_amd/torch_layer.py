@@ -54,8 +54,10 @@ of the maxiter-step map itself -- what finite differences of the layer's own out
 where tv_denoise's is implicit differentiation of the exact minimiser.  The forward pass records the dual before every
 projection in a tape it allocates as a torch tensor (2 * maxiter * B*H*W doubles) and saves for backward, which is one
 bpltv_unrolled_vjp_device call: a reverse sweep over that tape, no factorisation, no active-set threshold.  Use it for
-a layer with a fixed, small iteration count; the reference's learning function uses tv_denoise.  It carries no jvp:
-forward-mode AD over it raises torch's "not implemented" error.
+a layer with a fixed, small iteration count; the reference's learning function uses tv_denoise.  By default it carries no
+jvp: forward-mode AD over it raises torch's "not implemented" error.  tv_denoise_unrolled(..., forward_mode=True) and
+TVDenoiseUnrolled(alpha, forward_mode=True) select a function whose jvp is one bpltv_unrolled_jvp_device call: a tangent
+sweep through the iterations that reads no tape (its forward still records one, so backward works as well).
 
 Streams: the library runs its kernels on its own HIP streams and blocks until they are done.  Every call below first
 synchronises the tensors' current torch stream, so that the library reads inputs torch has finished writing; its
@@ -578,22 +580,62 @@ class TVDenoiseUnrolledFunction(torch.autograd.Function):
         return gf, (ga.reshape(alpha.shape) if need_a else None), None
 
 
-def tv_denoise_unrolled(f, alpha, **solver_kw):
+class TVDenoiseUnrolledForwardFunction(TVDenoiseUnrolledFunction):
+    """TVDenoiseUnrolledFunction with a jvp (tv_denoise_unrolled(..., forward_mode=True)): forward is the base class's
+    taped solve, so backward keeps working; the jvp is one tangent sweep through the iterations
+    (TVSolver.unrolled_jvp_device, one direction), which reads no tape."""
+
+    @staticmethod
+    def forward(ctx, f, alpha, solver_kw):
+        u = TVDenoiseUnrolledFunction.forward(ctx, f, alpha, solver_kw)
+        ctx.save_for_forward(f.detach().contiguous(), alpha.detach().contiguous())
+        ctx.set_materialize_grads(False)   # an input without a tangent reaches jvp as None, and the library as NULL
+        return u
+
+    @staticmethod
+    def jvp(ctx, df, dalpha, _solver_kw):
+        f, alpha = ctx.saved_tensors
+        df, dalpha = _tangent(df, f, "f"), _tangent(dalpha, alpha, "alpha")
+        if df is None and dalpha is None:
+            return torch.zeros_like(f)
+        du = torch.empty_like(f)
+        _sync(f.device)
+        ctx.solver.set_data_device(f.data_ptr(), f.data_ptr())   # the sweep reads the handle's dataset
+        ctx.solver.unrolled_jvp_device(alpha.data_ptr(), ctx.am, ctx.an, df.data_ptr() if df is not None else None,
+                                       dalpha.data_ptr() if dalpha is not None else None, du.data_ptr(), None, ndir=1,
+                                       **ctx.solver_kw)
+        return du
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gu):
+        if gu is None:
+            return None, None, None
+        return TVDenoiseUnrolledFunction.backward(ctx, gu)
+
+
+def tv_denoise_unrolled(f, alpha, forward_mode=False, **solver_kw):
     """u = denoise(f, alpha) by exactly maxiter PDHG iterations (TVSolver.unrolled_denoise_device: tv_denoise's u bit for
     bit), differentiable in f and alpha THROUGH the iterations: backward is the exact derivative of the maxiter-step map
     (TVSolver.unrolled_vjp_device), not the implicit gradient of the minimiser.  solver_kw: the solver parameters of
-    TVSolver.params (rho, init and order must stay 0), used by the forward solve and the reverse sweep alike."""
-    return TVDenoiseUnrolledFunction.apply(f, alpha, solver_kw)
+    TVSolver.params (rho, init and order must stay 0), used by the forward solve and the sweeps alike.
+    forward_mode: also usable under torch.autograd.forward_ad (the function then carries a jvp, a tangent sweep through
+    the iterations, bpltv_unrolled_jvp_device); without it forward-mode AD raises torch's "not implemented" error, as
+    before."""
+    fn = TVDenoiseUnrolledForwardFunction if forward_mode else TVDenoiseUnrolledFunction
+    return fn.apply(f, alpha, solver_kw)
 
 
 class TVDenoiseUnrolled(torch.nn.Module):
     """TVDenoise with tv_denoise_unrolled's backward: a learnable scalar, patch parameter or pixel map behind a fixed
-    number of iterations (solver_kw: maxiter, ...).  Move it to the device of its inputs with .to(device)."""
+    number of iterations (solver_kw: maxiter, ...).  Move it to the device of its inputs with .to(device).
+    forward_mode: as tv_denoise_unrolled's."""
 
-    def __init__(self, alpha, **solver_kw):
+    def __init__(self, alpha, forward_mode=False, **solver_kw):
         super().__init__()
         self.alpha = torch.nn.Parameter(torch.as_tensor(alpha, dtype=torch.float64).clone())
+        self.forward_mode = bool(forward_mode)
         self.solver_kw = dict(solver_kw)
 
     def forward(self, f):
-        return tv_denoise_unrolled(f, self.alpha, **self.solver_kw)
+        return tv_denoise_unrolled(f, self.alpha, forward_mode=self.forward_mode, **self.solver_kw)

@@ -132,7 +132,8 @@ typedef struct bpltv_stats {
                                   3 banded Cholesky (HBM band), 4 banded LU (sum of regularisers, row-scaled
                                   gradient_reg system, with reserved[4] = 1), 5 nested-dissection (multifrontal)
                                   Cholesky, 6 nested-dissection LU (that row-scaled system, the default),
-                                  7 reverse sweep over the taped iterations (bpltv_unrolled_vjp)          */
+                                  7 reverse sweep over the taped iterations (bpltv_unrolled_vjp),
+                                  8 tangent sweep through the iterations (bpltv_unrolled_jvp)             */
     int reg_gradient_used;     /* 1 if the last evaluate took the gradient_reg branch             */
     int ngpus;                 /* distinct devices behind this handle (1 for bpltv_create)        */
     int shards;                /* image shards (= worker threads) behind this handle              */
@@ -397,6 +398,37 @@ int bpltv_unrolled_vjp(bpltv_t *h, const double *alpha, int am, int an, const bp
                        const double *gu, double *grad_f_out, double *grad_alpha_out);
 int bpltv_unrolled_vjp_device(bpltv_t *h, const double *d_tape, const double *d_alpha, int am, int an,
                               const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alpha);
+
+/* Forward mode through the PDHG iterations: the tangent of the K-step map that bpltv_unrolled_vjp
+ * transposes -- <gu, du> = <grad_f(gu), df> + <grad_alpha(gu), dalpha> for any gu -- exact for any K, with no tape: a sweep
+ * carries (dx, dy1, dy2) beside (x, y1, y2) in 14 planes of M*N*O doubles owned by the handle (allocated on first use, freed by
+ * bpltv_destroy; BPLTV_E_NOMEM, with the handle as it was, when they cannot be allocated), whatever maxiter is.  TV model,
+ * Float64 (also on dtype = 32 handles), one parameter shared by the batch; f is the resident dataset (BPLTV_E_NODATA without
+ * one).  params as for bpltv_unrolled_denoise: rho, init and order must be 0 (BPLTV_E_UNSUPPORTED), maxiter < 1 is BPLTV_E_ARG,
+ * check_every / gap_tol are ignored.
+ *
+ * bpltv_unrolled_jvp: ndir >= 1 directions, direction-major: df is NULL or ndir * M*N*O doubles, dalpha NULL or ndir * am*an
+ * doubles indexed as alpha is, not both NULL (a NULL tangent is zero); du_out: ndir * M*N*O doubles.  The directions are swept
+ * one after the other: direction d of a call is bitwise the ndir = 1 call with that direction.  u_out (may be NULL): the primal
+ * result, M*N*O doubles, bpltv_denoise's u bit for bit.  alpha is checked as bpltv_denoise checks it (finite, >= 0) and the
+ * tangents must be finite (the host form checks them on the host, the device form on the device); ndir < 1, both tangents
+ * NULL, a bad parameter shape or a NULL du_out is BPLTV_E_ARG; every rejection comes before anything of the handle changes.
+ * The sweep stages its parameter and its tangents apart and runs in planes of its own: the last solve, bpltv_u_device,
+ * bpltv_duality_gap, the handle's tape and the solve statistics stay as they were, and it never replays a taped solve's or a
+ * reverse sweep's captured graphs, nor they its.  stats: only adjoint_ms (the HIP-event time of the sweeps) and adjoint_method
+ * = 8 change.  The results do not depend on tile_iters, on the launch chains or on use_graph.
+ *
+ * bpltv_unrolled_gauss_newton: for a scalar or a patch parameter of P = am*an <= 16 entries (anything else:
+ * BPLTV_E_UNSUPPORTED), P unit-direction sweeps (columns in the parameter's column-major order) and, with ubar the resident
+ * dataset's, cost_out = 0.5||u_K - ubar||^2, grad_out = J^T (u_K - ubar) (P doubles) and hess_out = J^T J (P x P, column major,
+ * symmetric bit for bit) of the K-step loss; sums per image, then over the images in image order.
+ * Multi-device handles over more than one shard: BPLTV_E_UNSUPPORTED (all three). */
+int bpltv_unrolled_jvp(bpltv_t *h, const double *alpha, int am, int an, const bpltv_params *p, int ndir,
+                       const double *df, const double *dalpha, double *du_out, double *u_out /* may be NULL */);
+int bpltv_unrolled_jvp_device(bpltv_t *h, const double *d_alpha, int am, int an, const bpltv_params *p, int ndir,
+                              const double *d_df, const double *d_dalpha, double *d_du, double *d_u /* may be NULL */);
+int bpltv_unrolled_gauss_newton(bpltv_t *h, const double *alpha, int am, int an, const bpltv_params *p,
+                                double *cost_out, double *grad_out, double *hess_out);
 
 /* Jacobian-vector product of u = denoise(f, alpha) (TV model): du for tangents (df, dalpha), defined as the linear map
  * whose transpose bpltv_vjp computes, in every branch -- <gu, du> = <grad_f(gu), df> + <grad_alpha(gu), dalpha> for any
