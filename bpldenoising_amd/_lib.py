@@ -111,6 +111,14 @@ SYMBOLS = {
     "bpltv_unrolled_jvp_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, _PP, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                             C.c_void_p]),
     "bpltv_unrolled_gauss_newton": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
+    "bpltv_unrolled_denoise_each": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp]),
+    "bpltv_unrolled_denoise_each_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, _PP, C.c_void_p]),
+    "bpltv_unrolled_vjp_each": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
+    "bpltv_unrolled_vjp_each_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, _PP, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p]),
+    "bpltv_unrolled_jvp_each": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, C.c_int, _dp, _dp, _dp, _dp]),
+    "bpltv_unrolled_jvp_each_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, _PP, C.c_int, C.c_void_p, C.c_void_p,
+                                                 C.c_void_p, C.c_void_p]),
     "bpltv_jvp": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, C.c_int, _dp, _dp, _dp]),
     "bpltv_jvp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_int, C.c_void_p,
                                    C.c_void_p, C.c_void_p]),

@@ -430,6 +430,7 @@ struct bpltv_handle {
     size_t tape_cap = 0;                            // doubles
     bool tape_valid = false;
     int tape_maxiter = 0, tape_am = 0, tape_an = 0, tape_accel = 0;
+    bool tape_each = false;                         // recorded by bpltv_unrolled_denoise_each: one parameter block per image
     double tape_tau0 = 0.0, tape_sigma0 = 0.0, tape_opnorm = 0.0;
     double* d_unr = nullptr;                        // 9 * M*N*O doubles
     // forward mode through the iterations (unrolled_jvp_kernels.hpp): the tangent sweep's planes [2 sets x (x, y1, y2, dx, dy1,
@@ -3306,8 +3307,9 @@ int run_unrolled_pdhg(bpltv_t* h, const bpltv_params& p, const WeightedPlan& pl,
     j.chains = plan_chains(p.reserved[1], h->st.tiles, h->ncu, O, 2);   // at most two (image groups on two streams)
     j.serial = (p.reserved[2] & 1) != 0; j.helper_thread = !(p.reserved[2] & 8);
     j.bytes_per_px_iter = amap ? 80.0 : 72.0;   // read x, y1, y2, f (+ alpha), write x, y1, y2 and z1, z2
+    // (istride: a per-image solve uploads into d_alpha like a shared one, and must not replay its graph, nor the reverse)
     j.key = GraphKey{p.maxiter, T, 0, h->last_am, h->last_an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_tape, (const void*)d_tab, 0,
-                     (const void*)h->d_alpha, 0, 0};
+                     (const void*)h->d_alpha, h->alpha_istride, 0};
     j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
         int step = stagger ? T / 2 : T;
         for (int it = it0; it < it1; it += step, step = T) {
@@ -3316,7 +3318,7 @@ int run_unrolled_pdhg(bpltv_t* h, const bpltv_params& p, const WeightedPlan& pl,
             a.xin = h->d_state[cur][0]; a.y1in = h->d_state[cur][1]; a.y2in = h->d_state[cur][2];
             a.xout = h->d_state[nxt][0]; a.y1out = h->d_state[nxt][1]; a.y2out = h->d_state[nxt][2];
             a.f = h->d_f; a.alpha = h->d_alpha; a.tab = d_tab; a.tape = d_tape; a.plane = h->tot;
-            a.am = h->last_am; a.an = h->last_an;
+            a.am = h->last_am; a.an = h->last_an; a.istride = h->alpha_istride;
             a.it0 = it; a.nit = std::min(step, it1 - it);
             a.M = M; a.N = N; a.halo = T; a.first = (it == 0) ? 1 : 0; a.img0 = lo;
             hipLaunchKernelGGL(unrolled_tile_kernel, dim3(pl.nTi, pl.nTj, hi - lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), st, a);
@@ -3329,9 +3331,11 @@ int run_unrolled_pdhg(bpltv_t* h, const bpltv_params& p, const WeightedPlan& pl,
 
 // bpltv_unrolled_denoise(_device) on a single-device handle.  d_tape_user: the caller's tape, or nullptr for the handle's own,
 // which grows here -- the new buffer is allocated before anything changes and installed only once the parameter is accepted.
+// each (bpltv_unrolled_denoise_each(_device)): alpha holds O blocks of am*an doubles, image k reads block k (upload_alpha).
 int unrolled_denoise_common(bpltv_t* h, const double* alpha, bool dev, int am, int an, const bpltv_params* pp, double* d_tape_user,
-                            double* u_out) {
-    const char* who = dev ? "bpltv_unrolled_denoise_device" : "bpltv_unrolled_denoise";
+                            double* u_out, bool each = false) {
+    const char* who = each ? (dev ? "bpltv_unrolled_denoise_each_device" : "bpltv_unrolled_denoise_each")
+                           : (dev ? "bpltv_unrolled_denoise_device" : "bpltv_unrolled_denoise");
     WallTimer wt;
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: bpltv_set_data has not been called", who);
@@ -3351,7 +3355,7 @@ int unrolled_denoise_common(bpltv_t* h, const double* alpha, bool dev, int am, i
     }
     bpltv_params q = p;   // the TV planner's knobs mean nothing here: upload_alpha's precheck sees the defaults
     q.tile_iters = 0; q.reserved[0] = 0; q.reserved[1] = 0; q.reserved[2] = 0;
-    int rc = upload_alpha(h, alpha, dev, am, an, PRE_TV, 1, &q);
+    int rc = upload_alpha(h, alpha, dev, am, an, PRE_TV, each ? h->O : 1, &q);
     if (rc) {
         if (grown) (void)hipFree(grown);
         return rc;
@@ -3371,7 +3375,7 @@ int unrolled_denoise_common(bpltv_t* h, const double* alpha, bool dev, int am, i
     h->last_weighted = false;
     if (!d_tape_user) {
         h->tape_valid = true;
-        h->tape_maxiter = p.maxiter; h->tape_am = am; h->tape_an = an; h->tape_accel = p.accel ? 1 : 0;
+        h->tape_maxiter = p.maxiter; h->tape_am = am; h->tape_an = an; h->tape_accel = p.accel ? 1 : 0; h->tape_each = each;
         h->tape_tau0 = p.tau0; h->tape_sigma0 = p.sigma0; h->tape_opnorm = p.opnorm;
     }
     if (u_out) {
@@ -3385,9 +3389,11 @@ int unrolled_denoise_common(bpltv_t* h, const double* alpha, bool dev, int am, i
 // bpltv_unrolled_vjp(_device) on a single-device handle: d_gu and the outputs live in HBM, alpha on the host or (dev) in HBM;
 // d_tape_user or the handle's tape.  The parameter is staged apart (stage_param) and the sweep runs in planes of its own, so the
 // last solve stays untouched; the solve statistics are put back after the shared driver has run the sweep.
+// each (bpltv_unrolled_vjp_each(_device)): alpha holds O blocks, image k reads block k, and d_grad_alpha receives the O per-image
+// gradients, image-major -- the ga plane as it is for a map, image k's patch sums otherwise.
 int unrolled_vjp_common(bpltv_t* h, const double* d_tape_user, const double* alpha, bool dev, int am, int an, const bpltv_params* pp,
-                        const double* d_gu, double* d_grad_f, double* d_grad_alpha) {
-    const char* who = "unrolled_vjp";
+                        const double* d_gu, double* d_grad_f, double* d_grad_alpha, bool each = false) {
+    const char* who = each ? "unrolled_vjp_each" : "unrolled_vjp";
     if (!alpha || !d_gu) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
     if (!d_grad_f && !d_grad_alpha) return set_err(h, BPLTV_E_ARG, "%s: both outputs are NULL", who);
     const bpltv_params p0 = resolve(pp);
@@ -3398,6 +3404,9 @@ int unrolled_vjp_common(bpltv_t* h, const double* d_tape_user, const double* alp
             h->tape_tau0 != p0.tau0 || h->tape_sigma0 != p0.sigma0 || h->tape_opnorm != p0.opnorm)
             return set_err(h, BPLTV_E_ARG, "%s: the handle's tape was recorded with maxiter = %d, a %dx%d parameter and other steps than this call's (%d, %dx%d)",
                            who, h->tape_maxiter, h->tape_am, h->tape_an, p0.maxiter, am, an);
+        if (h->tape_each != each)
+            return set_err(h, BPLTV_E_ARG, "%s: the handle's tape was recorded with %s", who,
+                           h->tape_each ? "one parameter block per image (bpltv_unrolled_denoise_each)" : "one shared parameter (bpltv_unrolled_denoise)");
     }
     WeightedPlan pl;
     if (int prc = unrolled_plan(h, p0, UN_REV_T, &pl)) return prc;
@@ -3406,10 +3415,10 @@ int unrolled_vjp_common(bpltv_t* h, const double* d_tape_user, const double* alp
         if (int arc = alloc_all(h, {{(void**)&h->d_unr, 9 * tot * sizeof(double)}}, "reverse sweep")) return arc;
     bpltv_params p;
     GradCtx g;
-    if (int rc = stage_param(h, who, alpha, dev, am, an, 1, false, 0, pp, nullptr, 1, {{d_gu, tot, "cotangent gu"}}, &p, &g)) return rc;
+    if (int rc = stage_param(h, who, alpha, dev, am, an, 1, each, 0, pp, nullptr, 1, {{d_gu, tot, "cotangent gu"}}, &p, &g)) return rc;
     const int M = h->M, N = h->N, O = h->O, T = pl.T, K = p.maxiter;
     const bool amap = am == M && an == N && !(M == 1 && N == 1);
-    if (d_grad_alpha && !amap)
+    if (d_grad_alpha && !amap && !each)
         if (int rc = ensure(h, &h->d_red, &h->red_cap, (size_t)am * an * O)) return rc;
     h->has_per_image = false;
     double* d_tab = nullptr;
@@ -3429,7 +3438,7 @@ int unrolled_vjp_common(bpltv_t* h, const double* d_tape_user, const double* alp
     j.chains = plan_chains(p.reserved[1], tiles, h->ncu, O, 2);
     j.serial = (p.reserved[2] & 1) != 0; j.helper_thread = !(p.reserved[2] & 8);
     j.bytes_per_px_iter = 0.0;   // (the driver's solve statistics are not this call's: `kept` goes back below)
-    j.key = GraphKey{K, T, 1, am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_tape, (const void*)d_tab, 0, (const void*)g.alpha, 0, 0};
+    j.key = GraphKey{K, T, 1, am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_tape, (const void*)d_tab, 0, (const void*)g.alpha, g.astride, 0};
     j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
         int step = stagger ? T / 2 : T;
         for (int it = it0; it < it1; it += step, step = T) {   // `it` counts reverse steps: step r undoes iteration K - 1 - r
@@ -3438,7 +3447,7 @@ int unrolled_vjp_common(bpltv_t* h, const double* d_tape_user, const double* alp
             a.gxin = (it == 0) ? d_g0 : S[cur][0]; a.gy1in = S[cur][1]; a.gy2in = S[cur][2];
             a.gxout = S[nxt][0]; a.gy1out = S[nxt][1]; a.gy2out = S[nxt][2];
             a.gf = d_gf; a.ga = d_ga; a.tape = d_tape; a.alpha = g.alpha; a.tab = d_tab; a.plane = tot;
-            a.am = am; a.an = an;
+            a.am = am; a.an = an; a.istride = g.astride;
             a.khi = K - 1 - it; a.nit = std::min(step, it1 - it);
             a.M = M; a.N = N; a.halo = T; a.first = (it == 0) ? 1 : 0; a.img0 = lo;
             hipLaunchKernelGGL(unrolled_reverse_tile_kernel, dim3(pl.nTi, pl.nTj, hi - lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), st, a);
@@ -3452,7 +3461,11 @@ int unrolled_vjp_common(bpltv_t* h, const double* d_tape_user, const double* alp
     if (rc) return rc;
     if (d_grad_f)
         hipLaunchKernelGGL(unrolled_gradf_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, d_gf, S[buf][0], tot, d_grad_f);
-    if (d_grad_alpha && amap) {   // the per-pixel sums over the images, in image order; then per patch (calc_adjoint) or over everything
+    if (d_grad_alpha && each && amap) {   // per image: the plane as it is, or image k's patch sums (fixed order, no sum over images)
+        HIPCHK(h, hipMemcpyAsync(d_grad_alpha, d_ga, tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    } else if (d_grad_alpha && each) {
+        hipLaunchKernelGGL(patch_sum_kernel, dim3(am * an, O), dim3(256), 0, h->stream, d_ga, M, N, O, am, an, 1, am * an, d_grad_alpha);
+    } else if (d_grad_alpha && amap) {   // the per-pixel sums over the images, in image order; then per patch (calc_adjoint) or over everything
         hipLaunchKernelGGL(map_sum_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, d_ga, npx, O, d_grad_alpha);
     } else if (d_grad_alpha) {
         hipLaunchKernelGGL(patch_sum_kernel, dim3(am * an, O), dim3(256), 0, h->stream, d_ga, M, N, O, am, an, O, 1, h->d_red);
@@ -3482,8 +3495,10 @@ int unrolled_vjp_common(bpltv_t* h, const double* d_tape_user, const double* alp
 // dy2) | df | dalpha] on the staged parameter (stage_param), with the direction's tangents copied into the workspace first, so
 // that no captured graph holds a caller's address and the last solve, the tape and the solve statistics stay as they were.
 // d_u (nullable): receives the primal result, bpltv_denoise's u.  *x_res (nullable): the workspace plane that holds it.
+// each (bpltv_unrolled_jvp_each(_device)): alpha holds O blocks and d_dalpha ndir x O blocks (direction, then image); image k
+// reads block k of both.
 int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool dev, int am, int an, const bpltv_params* pp, int ndir,
-                        const double* d_df, const double* d_dalpha, double* d_du, double* d_u, const double** x_res) {
+                        const double* d_df, const double* d_dalpha, double* d_du, double* d_u, const double** x_res, bool each = false) {
     if (!alpha || !d_du) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
     if (ndir < 1) return set_err(h, BPLTV_E_ARG, "%s: ndir = %d (at least one direction)", who, ndir);
     if (!d_df && !d_dalpha) return set_err(h, BPLTV_E_ARG, "%s: both tangents are NULL", who);
@@ -3498,10 +3513,10 @@ int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool d
         HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&unrolled_jvp_tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
                                       (int)unrolled_jvp_lds_bytes()));
     }
-    const size_t P = (size_t)am * an;   // (stage_param checks the shape before it reads anything)
+    const size_t P = (size_t)am * an * (each ? h->O : 1);   // (stage_param checks the shape before it reads anything)
     bpltv_params p;
     GradCtx g;
-    if (int rc = stage_param(h, who, alpha, dev, am, an, 1, false, 0, pp, nullptr, 1,
+    if (int rc = stage_param(h, who, alpha, dev, am, an, 1, each, 0, pp, nullptr, 1,
                              {{d_df, (size_t)ndir * tot, "tangent df"}, {d_dalpha, (size_t)ndir * P, "tangent dalpha"}}, &p, &g))
         return rc;
     double* d_tab = nullptr;
@@ -3521,7 +3536,7 @@ int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool d
     j.bytes_per_px_iter = 0.0;   // (the driver's solve statistics are not this call's: `kept` goes back below)
     // variant 2 ... 5: a tangent sweep, by which tangents it reads (0 = taped solve, 1 = reverse sweep)
     j.key = GraphKey{K, T, 2 + (d_df ? 1 : 0) + (d_dalpha ? 2 : 0), am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)h->d_ujv,
-                     (const void*)d_tab, 0, (const void*)g.alpha, 0, 0};
+                     (const void*)d_tab, 0, (const void*)g.alpha, g.astride, 0};
     j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
         int step = stagger ? T / 2 : T;
         for (int it = it0; it < it1; it += step, step = T) {
@@ -3529,7 +3544,7 @@ int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool d
             UnrolledJvpArgs a;
             for (int c = 0; c < 6; ++c) { a.in[c] = S[cur][c]; a.out[c] = S[nxt][c]; }
             a.f = h->d_f; a.df = d_df ? d_dfc : nullptr; a.alpha = g.alpha; a.dalpha = d_dalpha ? d_dac : nullptr; a.tab = d_tab;
-            a.am = am; a.an = an;
+            a.am = am; a.an = an; a.istride = g.astride;
             a.it0 = it; a.nit = std::min(step, it1 - it);
             a.M = M; a.N = N; a.halo = T; a.first = (it == 0) ? 1 : 0; a.img0 = lo;
             hipLaunchKernelGGL(unrolled_jvp_tile_kernel, dim3(pl.nTi, pl.nTj, hi - lo), dim3(UN_R * UN_R), unrolled_jvp_lds_bytes(), st, a);
@@ -3956,11 +3971,25 @@ int bpltv_unrolled_denoise_device(bpltv_t* h, const double* d_alpha, int am, int
     return unrolled_denoise_common(h, d_alpha, true, am, an, pp, d_tape, nullptr);
 }
 
-int bpltv_unrolled_vjp(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, const double* gu,
-                       double* grad_f_out, double* grad_alpha_out) {
+// bpltv_unrolled_denoise with one parameter block per image: upload_alpha with O blocks, after which the taped kernel and the
+// gap kernels address block k for image k (h->alpha_istride); the tape remembers it (tape_each).
+int bpltv_unrolled_denoise_each(bpltv_t* h, const double* alphas, int am, int an, const bpltv_params* pp, double* u_out) {
     if (!h) return BPLTV_E_ARG;
     if (h->multi)
-        return weighted_multi(h, "bpltv_unrolled_vjp", false, [&](bpltv_t* c) { return bpltv_unrolled_vjp(c, alpha, am, an, pp, gu, grad_f_out, grad_alpha_out); }, kUnrolled);
+        return weighted_multi(h, "bpltv_unrolled_denoise_each", true, [&](bpltv_t* c) { return bpltv_unrolled_denoise_each(c, alphas, am, an, pp, u_out); }, kUnrolled);
+    return unrolled_denoise_common(h, alphas, false, am, an, pp, nullptr, u_out, true);
+}
+
+int bpltv_unrolled_denoise_each_device(bpltv_t* h, const double* d_alphas, int am, int an, const bpltv_params* pp, double* d_tape) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_unrolled_denoise_each_device", true, [&](bpltv_t* c) { return bpltv_unrolled_denoise_each_device(c, d_alphas, am, an, pp, d_tape); }, kUnrolled);
+    return unrolled_denoise_common(h, d_alphas, true, am, an, pp, d_tape, nullptr, true);
+}
+
+// bpltv_unrolled_vjp and bpltv_unrolled_vjp_each on a single-device handle: the host arrays staged around unrolled_vjp_common
+static int unrolled_vjp_host(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, const double* gu,
+                             double* grad_f_out, double* grad_alpha_out, bool each) {
     if (!gu || !alpha) return set_err(h, BPLTV_E_ARG, "unrolled_vjp: null pointer");
     if (!grad_f_out && !grad_alpha_out) return set_err(h, BPLTV_E_ARG, "unrolled_vjp: both outputs are NULL");
     if (am < 1 || an < 1 || am > h->M || an > h->N)
@@ -3973,15 +4002,46 @@ int bpltv_unrolled_vjp(bpltv_t* h, const double* alpha, int am, int an, const bp
     }
     if (grad_f_out && !h->d_gf2) HIPCHK(h, hipMalloc((void**)&h->d_gf2, h->tot * sizeof(double)));
     HIPCHK(h, hipMemcpyAsync(h->d_ubar2, gu, h->tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    const size_t P = (size_t)am * an;
+    const size_t P = (size_t)am * an * (each ? h->O : 1);
     int rc = ensure(h, &h->d_vjp, &h->vjp_cap, 4 + 2 * P);
     if (rc) return rc;
     double* d_ga = grad_alpha_out ? h->d_vjp + 4 + P : nullptr;
-    rc = unrolled_vjp_common(h, nullptr, alpha, false, am, an, pp, h->d_ubar2, grad_f_out ? h->d_gf2 : nullptr, d_ga);
+    rc = unrolled_vjp_common(h, nullptr, alpha, false, am, an, pp, h->d_ubar2, grad_f_out ? h->d_gf2 : nullptr, d_ga, each);
     if (rc) return rc;
     if (grad_f_out) HIPCHK(h, hipMemcpyAsync(grad_f_out, h->d_gf2, h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (grad_alpha_out) HIPCHK(h, hipMemcpyAsync(grad_alpha_out, d_ga, sizeof(double) * P, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
+int bpltv_unrolled_vjp(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, const double* gu,
+                       double* grad_f_out, double* grad_alpha_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_unrolled_vjp", false, [&](bpltv_t* c) { return bpltv_unrolled_vjp(c, alpha, am, an, pp, gu, grad_f_out, grad_alpha_out); }, kUnrolled);
+    return unrolled_vjp_host(h, alpha, am, an, pp, gu, grad_f_out, grad_alpha_out, false);
+}
+
+int bpltv_unrolled_vjp_each(bpltv_t* h, const double* alphas, int am, int an, const bpltv_params* pp, const double* gu,
+                            double* grad_f_out, double* grad_alphas_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_unrolled_vjp_each", false, [&](bpltv_t* c) { return bpltv_unrolled_vjp_each(c, alphas, am, an, pp, gu, grad_f_out, grad_alphas_out); }, kUnrolled);
+    return unrolled_vjp_host(h, alphas, am, an, pp, gu, grad_f_out, grad_alphas_out, true);
+}
+
+int bpltv_unrolled_vjp_each_device(bpltv_t* h, const double* d_tape, const double* d_alphas, int am, int an, const bpltv_params* pp,
+                                   const double* d_gu, double* d_grad_f, double* d_grad_alphas) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_unrolled_vjp_each_device", false, [&](bpltv_t* c) {
+            return bpltv_unrolled_vjp_each_device(c, d_tape, d_alphas, am, an, pp, d_gu, d_grad_f, d_grad_alphas);
+        }, kUnrolled);
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int rc = unrolled_vjp_common(h, d_tape, d_alphas, true, am, an, pp, d_gu, d_grad_f, d_grad_alphas, true);
+    if (rc) return rc;
     h->st.total_ms = wt.ms();
     return BPLTV_OK;
 }
@@ -4001,18 +4061,16 @@ int bpltv_unrolled_vjp_device(bpltv_t* h, const double* d_tape, const double* d_
     return BPLTV_OK;
 }
 
-int bpltv_unrolled_jvp(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, int ndir, const double* df,
-                       const double* dalpha, double* du_out, double* u_out) {
-    const char* who = "unrolled_jvp";
-    if (!h) return BPLTV_E_ARG;
-    if (h->multi)
-        return weighted_multi(h, "bpltv_unrolled_jvp", false, [&](bpltv_t* c) { return bpltv_unrolled_jvp(c, alpha, am, an, pp, ndir, df, dalpha, du_out, u_out); }, kUnrolled);
+// bpltv_unrolled_jvp and bpltv_unrolled_jvp_each on a single-device handle: the host arrays staged around unrolled_jvp_common
+static int unrolled_jvp_host(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, int ndir, const double* df,
+                             const double* dalpha, double* du_out, double* u_out, bool each) {
+    const char* who = each ? "unrolled_jvp_each" : "unrolled_jvp";
     if (!alpha || !du_out) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
     if (ndir < 1) return set_err(h, BPLTV_E_ARG, "%s: ndir = %d (at least one direction)", who, ndir);
     if (!df && !dalpha) return set_err(h, BPLTV_E_ARG, "%s: both tangents are NULL", who);
     if (am < 1 || an < 1 || am > h->M || an > h->N)
         return set_err(h, BPLTV_E_ARG, "%s: parameter shape %dx%d (image %dx%d)", who, am, an, h->M, h->N);
-    const size_t nt = (size_t)ndir * h->tot, na = (size_t)ndir * am * an;
+    const size_t nt = (size_t)ndir * h->tot, na = (size_t)ndir * am * an * (each ? h->O : 1);
     if (int crc = check_tangent_host(h, who, "tangent df", df, nt)) return crc;
     if (int crc = check_tangent_host(h, who, "tangent dalpha", dalpha, na)) return crc;
     HIPCHK(h, hipSetDevice(h->device));
@@ -4022,12 +4080,39 @@ int bpltv_unrolled_jvp(bpltv_t* h, const double* alpha, int am, int an, const bp
     double* d_u = u_out ? h->d_jvp + 2 * nt + na : nullptr;
     if (df) HIPCHK(h, hipMemcpyAsync(d_df, df, nt * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (dalpha) HIPCHK(h, hipMemcpyAsync(d_da, dalpha, na * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    rc = unrolled_jvp_common(h, who, alpha, false, am, an, pp, ndir, d_df, d_da, d_du, d_u, nullptr);
+    rc = unrolled_jvp_common(h, who, alpha, false, am, an, pp, ndir, d_df, d_da, d_du, d_u, nullptr, each);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(du_out, d_du, nt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (u_out) HIPCHK(h, hipMemcpyAsync(u_out, d_u, h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return BPLTV_OK;
+}
+
+int bpltv_unrolled_jvp(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, int ndir, const double* df,
+                       const double* dalpha, double* du_out, double* u_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_unrolled_jvp", false, [&](bpltv_t* c) { return bpltv_unrolled_jvp(c, alpha, am, an, pp, ndir, df, dalpha, du_out, u_out); }, kUnrolled);
+    return unrolled_jvp_host(h, alpha, am, an, pp, ndir, df, dalpha, du_out, u_out, false);
+}
+
+int bpltv_unrolled_jvp_each(bpltv_t* h, const double* alphas, int am, int an, const bpltv_params* pp, int ndir, const double* df,
+                            const double* dalphas, double* du_out, double* u_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_unrolled_jvp_each", false, [&](bpltv_t* c) { return bpltv_unrolled_jvp_each(c, alphas, am, an, pp, ndir, df, dalphas, du_out, u_out); }, kUnrolled);
+    return unrolled_jvp_host(h, alphas, am, an, pp, ndir, df, dalphas, du_out, u_out, true);
+}
+
+int bpltv_unrolled_jvp_each_device(bpltv_t* h, const double* d_alphas, int am, int an, const bpltv_params* pp, int ndir, const double* d_df,
+                                   const double* d_dalphas, double* d_du, double* d_u) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_unrolled_jvp_each_device", false, [&](bpltv_t* c) {
+            return bpltv_unrolled_jvp_each_device(c, d_alphas, am, an, pp, ndir, d_df, d_dalphas, d_du, d_u);
+        }, kUnrolled);
+    HIPCHK(h, hipSetDevice(h->device));
+    return unrolled_jvp_common(h, "unrolled_jvp_each", d_alphas, true, am, an, pp, ndir, d_df, d_dalphas, d_du, d_u, nullptr, true);
 }
 
 int bpltv_unrolled_jvp_device(bpltv_t* h, const double* d_alpha, int am, int an, const bpltv_params* pp, int ndir, const double* d_df,

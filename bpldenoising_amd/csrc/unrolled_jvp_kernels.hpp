@@ -30,6 +30,7 @@ struct UnrolledJvpArgs {
     const double* dalpha;   // am*an doubles, indexed as alpha, or nullptr: a zero tangent
     const double* tab;      // [maxiter][TAB_STRIDE]
     int am, an;
+    int istride;            // doubles between per-image blocks of alpha and of dalpha: 0 = one block for every image, am*an = image k reads block k
     int it0, nit;
     int M, N;
     int halo;
@@ -69,13 +70,13 @@ __global__ __launch_bounds__(UN_R * UN_R) void unrolled_jvp_tile_kernel(Unrolled
     // address and are zeroed afterwards (they stay 0).
     const int gi = min(oi + li, M - 1), gj = min(oj + lj, N - 1);
     const size_t pix = gi + (size_t)M * gj;
-    size_t ai = 0;
+    size_t ai = (size_t)img * (size_t)A.istride;   // image img's block (the global image index: a launch chain starts at img0)
     if (amode == 2) {
-        ai = pix;
+        ai += pix;
     } else if (amode == 1) {
         const unsigned pa = ((unsigned)gi * (unsigned)A.am) / (unsigned)M;
         const unsigned pb = ((unsigned)gj * (unsigned)A.an) / (unsigned)N;
-        ai = pa + (size_t)A.am * pb;
+        ai += pa + (size_t)A.am * pb;
     }
     double x = 0.0, y1 = 0.0, y2 = 0.0, dx = 0.0, dy1 = 0.0, dy2 = 0.0;
     if (!first) {

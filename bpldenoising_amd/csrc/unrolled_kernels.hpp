@@ -38,6 +38,7 @@ struct UnrolledArgs {
     double* tape;         // [maxiter][2][O][M*N]
     size_t plane;         // O * M*N: doubles of one tape component
     int am, an;
+    int istride;          // doubles between per-image parameter blocks: 0 = one block for every image, am*an = image k reads block k
     int it0, nit;
     int M, N;
     int halo;
@@ -71,13 +72,13 @@ __global__ __launch_bounds__(UN_R * UN_R) void unrolled_tile_kernel(UnrolledArgs
     // address and are zeroed afterwards (they stay 0).
     const int gi = min(oi + li, M - 1), gj = min(oj + lj, N - 1);
     const size_t pix = gi + (size_t)M * gj;
-    size_t ai = 0;
+    size_t ai = (size_t)img * (size_t)A.istride;   // image img's block (the global image index: a launch chain starts at img0)
     if (amode == 2) {
-        ai = pix;
+        ai += pix;
     } else if (amode == 1) {
         const unsigned pa = ((unsigned)gi * (unsigned)A.am) / (unsigned)M;
         const unsigned pb = ((unsigned)gj * (unsigned)A.an) / (unsigned)N;
-        ai = pa + (size_t)A.am * pb;
+        ai += pa + (size_t)A.am * pb;
     }
     double x = 0.0, y1 = 0.0, y2 = 0.0;
     if (!first) {
@@ -184,6 +185,7 @@ struct UnrolledRevArgs {
     const double* tab;
     size_t plane;
     int am, an;
+    int istride;          // as UnrolledArgs: 0, or am*an for one parameter block per image
     int khi, nit;         // this launch runs the iterations khi, khi - 1, ..., khi - nit + 1
     int M, N;
     int halo;
@@ -221,13 +223,13 @@ __global__ __launch_bounds__(UN_R * UN_R) void unrolled_reverse_tile_kernel(Unro
     // ---- prologue: every global load, the launch's taped duals included, is issued before the first use
     const int gi = min(oi + li, M - 1), gj = min(oj + lj, N - 1);
     const size_t pix = gi + (size_t)M * gj;
-    size_t ai = 0;
+    size_t ai = (size_t)img * (size_t)A.istride;   // image img's block (the global image index: a launch chain starts at img0)
     if (amode == 2) {
-        ai = pix;
+        ai += pix;
     } else if (amode == 1) {
         const unsigned pa = ((unsigned)gi * (unsigned)A.am) / (unsigned)M;
         const unsigned pb = ((unsigned)gj * (unsigned)A.an) / (unsigned)N;
-        ai = pa + (size_t)A.am * pb;
+        ai += pa + (size_t)A.am * pb;
     }
     const int qi = oi + li, qj = oj + lj;
     const bool in = (qi < M) && (qj < N);

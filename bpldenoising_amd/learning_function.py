@@ -641,6 +641,72 @@ class TVSolver:
                                                     int(an), int(bool(reg)), C.byref(p), C.c_void_p(gu_ptr),
                                                     C.c_void_p(grad_f_ptr or None), C.c_void_p(grad_alphas_ptr or None)))
 
+    # -- one parameter per image through the iterations (bpltv_unrolled_*_each) ----------------------------------
+    def unrolled_denoise_each(self, alphas, fetch=True, **kw):
+        """unrolled_denoise with image k's own parameter alphas[k] (bpltv_unrolled_denoise_each): denoise_each's u bit for
+        bit, and the handle's tape, recorded per image, for unrolled_vjp_each with the same alphas and params."""
+        a, am, an = self._each_arg(alphas)
+        p = self.params(**kw)
+        u = np.empty((self.O, self.N, self.M)) if fetch else None
+        self._check(self._lib.bpltv_unrolled_denoise_each(self._h, _ptr(a), am, an, C.byref(p),
+                                                          _ptr(u) if fetch else None))
+        return u
+
+    def unrolled_denoise_each_device(self, alphas_ptr, am=1, an=1, tape_ptr=None, **kw):
+        """bpltv_unrolled_denoise_each_device: O parameter blocks (O*am*an doubles, block k column major at k*am*an)
+        resident in HBM, the result left there; tape_ptr as in unrolled_denoise_device."""
+        p = self.params(**kw)
+        self._check(self._lib.bpltv_unrolled_denoise_each_device(self._h, C.c_void_p(alphas_ptr), int(am), int(an),
+                                                                 C.byref(p), C.c_void_p(tape_ptr or None)))
+
+    def unrolled_vjp_each(self, alphas, gu, want_f=True, want_alpha=True, **kw):
+        """unrolled_vjp with image k's own parameter alphas[k], over the handle's per-image tape
+        (bpltv_unrolled_vjp_each): (grad_f, grad_alphas).  grad_alphas has the shape of alphas; grad_alphas[k] is image
+        k's term alone, not summed over the images."""
+        if not (want_f or want_alpha):
+            raise ValueError("unrolled_vjp_each: want_f and want_alpha are both False")
+        a, am, an = self._each_arg(alphas)
+        p = self.params(**kw)
+        gu = self._batch(gu, "gu")
+        gf = np.empty((self.O, self.N, self.M)) if want_f else None
+        ga = np.empty(a.shape) if want_alpha else None
+        self._check(self._lib.bpltv_unrolled_vjp_each(self._h, _ptr(a), am, an, C.byref(p), _ptr(gu),
+                                                      _ptr(gf) if want_f else None, _ptr(ga) if want_alpha else None))
+        return gf, ga
+
+    def unrolled_vjp_each_device(self, tape_ptr, alphas_ptr, am, an, gu_ptr, grad_f_ptr, grad_alphas_ptr, **kw):
+        """bpltv_unrolled_vjp_each_device: as unrolled_vjp_device with O parameter blocks and their O gradients (O*am*an
+        doubles each) resident in HBM; either output pointer may be 0 / None, not both."""
+        p = self.params(**kw)
+        self._check(self._lib.bpltv_unrolled_vjp_each_device(self._h, C.c_void_p(tape_ptr or None),
+                                                             C.c_void_p(alphas_ptr), int(am), int(an), C.byref(p),
+                                                             C.c_void_p(gu_ptr), C.c_void_p(grad_f_ptr or None),
+                                                             C.c_void_p(grad_alphas_ptr or None)))
+
+    def unrolled_jvp_each(self, alphas, df=None, dalphas=None, want_u=False, **kw):
+        """unrolled_jvp with image k's own parameter alphas[k] (bpltv_unrolled_jvp_each).  dalphas: shaped like alphas,
+        or with a leading K; df, want_u and the result as in unrolled_jvp (u = denoise_each(alphas) bit for bit)."""
+        a, am, an = self._each_arg(alphas)
+        df, dalphas, K, batched = self._tangents("unrolled_jvp_each", df, dalphas, a.shape)
+        p = self.params(**kw)
+        du = np.empty((K, self.O, self.N, self.M))
+        u = np.empty((self.O, self.N, self.M)) if want_u else None
+        self._check(self._lib.bpltv_unrolled_jvp_each(self._h, _ptr(a), am, an, C.byref(p), K,
+                                                      _ptr(df) if df is not None else None,
+                                                      _ptr(dalphas) if dalphas is not None else None, _ptr(du),
+                                                      _ptr(u) if want_u else None))
+        du = du if batched else du[0]
+        return (du, u) if want_u else du
+
+    def unrolled_jvp_each_device(self, alphas_ptr, am, an, df_ptr, dalphas_ptr, du_ptr, u_ptr=None, ndir=1, **kw):
+        """bpltv_unrolled_jvp_each_device: as unrolled_jvp_device with O parameter blocks (O*am*an doubles) and ndir*O
+        tangent blocks, direction first."""
+        p = self.params(**kw)
+        self._check(self._lib.bpltv_unrolled_jvp_each_device(self._h, C.c_void_p(alphas_ptr), int(am), int(an),
+                                                             C.byref(p), int(ndir), C.c_void_p(df_ptr or None),
+                                                             C.c_void_p(dalphas_ptr or None), C.c_void_p(du_ptr),
+                                                             C.c_void_p(u_ptr or None)))
+
     # -- one block of three weights per image (bpltv_sumregs_denoise_each / bpltv_sumregs_vjp_each) ---------------
     def _sr_each_arg(self, alphas):
         """alphas: (O, 3) vectors or (O, 3, n, m) patch / map blocks (the layout of sumregs_evaluate per block), one per

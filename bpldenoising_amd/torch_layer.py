@@ -59,6 +59,15 @@ jvp: forward-mode AD over it raises torch's "not implemented" error.  tv_denoise
 TVDenoiseUnrolled(alpha, forward_mode=True) select a function whose jvp is one bpltv_unrolled_jvp_device call: a tangent
 sweep through the iterations that reads no tape (its forward still records one, so backward works as well).
 
+    u = tv_denoise_unrolled_each(f, alpha, maxiter=30)     # ... with one parameter per image (bpltv_unrolled_*_each)
+
+f is then (B, H, W) and alpha (B,), (B, pH, pW) or (B, H, W), as for tv_denoise_each -- a network that predicts the
+parameter per sample in front of a fixed, small number of iterations.  u is tv_denoise_each's bit for bit; forward is
+one taped batched solve into a tape tensor of its own, backward one bpltv_unrolled_vjp_each_device call, alpha.grad[k]
+image k's term alone; forward_mode=True adds the jvp (one bpltv_unrolled_jvp_each_device call).  A separate function:
+tv_denoise_unrolled never reads a leading batch dimension off alpha's shape.  It has no module class: a per-sample
+parameter is a network's output, not an nn.Parameter.
+
 Streams: the library runs its kernels on its own HIP streams and blocks until they are done.  Every call below first
 synchronises the tensors' current torch stream, so that the library reads inputs torch has finished writing; its
 outputs are complete when the call returns.
@@ -125,10 +134,11 @@ def _check_args(f, alpha, slices=1):
     return O, H, W, am, an
 
 
-def _check_args_each(f, alpha, slices=1):
+def _check_args_each(f, alpha, slices=1, name=None):
     """(O, N, M, am, an) of a valid (f, alpha) pair of tv_denoise_each or (slices = 3: a dimension of 3 behind the batch
-    dimension) sumregs_denoise_each; TypeError / ValueError before any library call."""
-    name = "sumregs_denoise_each" if slices == 3 else "tv_denoise_each"
+    dimension) sumregs_denoise_each; TypeError / ValueError before any library call.  name: the caller in the messages,
+    when it is another function with tv_denoise_each's shapes."""
+    name = name or ("sumregs_denoise_each" if slices == 3 else "tv_denoise_each")
     if not isinstance(f, torch.Tensor) or not isinstance(alpha, torch.Tensor):
         raise TypeError("%s: f and alpha must be torch tensors" % name)
     if f.dtype != torch.float64 or alpha.dtype != torch.float64:
@@ -612,6 +622,89 @@ class TVDenoiseUnrolledForwardFunction(TVDenoiseUnrolledFunction):
         if gu is None:
             return None, None, None
         return TVDenoiseUnrolledFunction.backward(ctx, gu)
+
+
+class TVDenoiseUnrolledEachFunction(torch.autograd.Function):
+    """autograd.Function of tv_denoise_unrolled_each (below); apply(f, alpha, solver_kw).  No jvp."""
+
+    @staticmethod
+    def forward(ctx, f, alpha, solver_kw):
+        O, N, M, am, an = _check_args_each(f, alpha, name="tv_denoise_unrolled_each")
+        index = f.device.index if f.device.index is not None else torch.cuda.current_device()
+        s = _solver(index, M, N, O)
+        fc = f.detach().contiguous()
+        ac = alpha.detach().contiguous()
+        u = torch.empty_like(fc)
+        # the tape is this call's own: a second forward pass on the handle before backward does not overwrite it
+        tape = torch.empty(s.unrolled_tape_doubles(**solver_kw), dtype=torch.float64, device=f.device)
+        _sync(f.device)
+        s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
+        s.unrolled_denoise_each_device(ac.data_ptr(), am, an, tape_ptr=tape.data_ptr(), **solver_kw)
+        s.copy_u_device(u.data_ptr())
+        ctx.save_for_backward(tape, ac)
+        ctx.solver, ctx.am, ctx.an, ctx.solver_kw = s, am, an, dict(solver_kw)
+        return u
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gu):
+        need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_f or need_a):
+            return None, None, None
+        tape, alpha = ctx.saved_tensors
+        gu = gu.to(dtype=torch.float64).contiguous()
+        gf = torch.empty_like(gu) if need_f else None
+        ga = torch.empty_like(alpha) if need_a else None
+        _sync(gu.device)
+        ctx.solver.unrolled_vjp_each_device(tape.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(),
+                                            gf.data_ptr() if need_f else None, ga.data_ptr() if need_a else None,
+                                            **ctx.solver_kw)
+        return gf, ga, None
+
+
+class TVDenoiseUnrolledEachForwardFunction(TVDenoiseUnrolledEachFunction):
+    """TVDenoiseUnrolledEachFunction with a jvp (tv_denoise_unrolled_each(..., forward_mode=True)): forward is the base
+    class's taped solve, so backward keeps working; the jvp is one tangent sweep through the iterations
+    (TVSolver.unrolled_jvp_each_device, one direction), which reads no tape."""
+
+    @staticmethod
+    def forward(ctx, f, alpha, solver_kw):
+        u = TVDenoiseUnrolledEachFunction.forward(ctx, f, alpha, solver_kw)
+        ctx.save_for_forward(f.detach().contiguous(), alpha.detach().contiguous())
+        ctx.set_materialize_grads(False)   # an input without a tangent reaches jvp as None, and the library as NULL
+        return u
+
+    @staticmethod
+    def jvp(ctx, df, dalpha, _solver_kw):
+        f, alpha = ctx.saved_tensors
+        df, dalpha = _tangent(df, f, "f"), _tangent(dalpha, alpha, "alpha")
+        if df is None and dalpha is None:
+            return torch.zeros_like(f)
+        du = torch.empty_like(f)
+        _sync(f.device)
+        ctx.solver.set_data_device(f.data_ptr(), f.data_ptr())   # the sweep reads the handle's dataset
+        ctx.solver.unrolled_jvp_each_device(alpha.data_ptr(), ctx.am, ctx.an, df.data_ptr() if df is not None else None,
+                                            dalpha.data_ptr() if dalpha is not None else None, du.data_ptr(), None,
+                                            ndir=1, **ctx.solver_kw)
+        return du
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gu):
+        if gu is None:
+            return None, None, None
+        return TVDenoiseUnrolledEachFunction.backward(ctx, gu)
+
+
+def tv_denoise_unrolled_each(f, alpha, forward_mode=False, **solver_kw):
+    """u[k] = denoise(f[k], alpha[k]) by exactly maxiter PDHG iterations, for a batch f of shape (B, H, W) with one
+    parameter per image: alpha (B,), (B, pH, pW) or (B, H, W) on f's device -- tv_denoise_each's u bit for bit,
+    differentiable THROUGH the iterations as tv_denoise_unrolled is.  One taped batched solve forward
+    (TVSolver.unrolled_denoise_each_device) and one reverse sweep backward (unrolled_vjp_each_device); alpha.grad[k] is
+    image k's term alone.  solver_kw and forward_mode: as tv_denoise_unrolled's (the jvp is one
+    unrolled_jvp_each_device call)."""
+    fn = TVDenoiseUnrolledEachForwardFunction if forward_mode else TVDenoiseUnrolledEachFunction
+    return fn.apply(f, alpha, solver_kw)
 
 
 def tv_denoise_unrolled(f, alpha, forward_mode=False, **solver_kw):

@@ -430,6 +430,36 @@ int bpltv_unrolled_jvp_device(bpltv_t *h, const double *d_alpha, int am, int an,
 int bpltv_unrolled_gauss_newton(bpltv_t *h, const double *alpha, int am, int an, const bpltv_params *p,
                                 double *cost_out, double *grad_out, double *hess_out);
 
+/* The unrolled solve, VJP and JVP with one parameter per image: what a network that predicts alpha per sample needs at a
+ * small, fixed iteration count.  alphas: O blocks of am x an doubles, column major, block k at alphas + k*am*an, image k
+ * reads block k (bpltv_denoise_each's layout, bpltv_denoise's shape rules).  Each function keeps the contract of its shared
+ * twin above -- params, rejections and their codes, what becomes or stays the last solve, the tapes, the statistics
+ * (bytes_per_px_iter 72 / 80, adjoint_method 7 / 8), independence of tile_iters, launch chains and use_graph, dtype = 32
+ * handles in Float64, multi-device handles forwarded on one shard and BPLTV_E_UNSUPPORTED beyond -- with these differences:
+ *  - every entry of every block is checked (finite, >= 0; 0 is legal), on the host or on the device, before anything of the
+ *    handle changes;
+ *  - u of image k is bitwise the one-image solve with block k, the whole u bitwise bpltv_denoise_each's, and after
+ *    bpltv_unrolled_denoise_each bpltv_duality_gap evaluates image k with its own block;
+ *  - the tape has the shared size and layout (bpltv_unrolled_tape_doubles).  The handle's tape remembers whether it was
+ *    recorded per image: bpltv_unrolled_vjp on a per-image tape and bpltv_unrolled_vjp_each on a shared one return
+ *    BPLTV_E_ARG.  A caller's tape stays the caller's contract;
+ *  - grad_alphas_out: O blocks of am*an doubles, block k being image k's term alone (the per-pixel plane as it is for a map,
+ *    image k's sums over all pixels or over each patch otherwise; fixed order, no atomics).  With equal blocks, the blocks
+ *    added in image order are bpltv_unrolled_vjp's grad_alpha_out bit for bit;
+ *  - dalphas: NULL or ndir x O blocks of am*an doubles, direction first, then image (bpltv_jvp_each's layout); image k's du
+ *    is bitwise the one-image sweep with (df_k, dalpha_k);
+ *  - a per-image call never replays a shared call's captured graph, nor the reverse. */
+int bpltv_unrolled_denoise_each(bpltv_t *h, const double *alphas, int am, int an, const bpltv_params *p, double *u_out);
+int bpltv_unrolled_denoise_each_device(bpltv_t *h, const double *d_alphas, int am, int an, const bpltv_params *p, double *d_tape);
+int bpltv_unrolled_vjp_each(bpltv_t *h, const double *alphas, int am, int an, const bpltv_params *p,
+                            const double *gu, double *grad_f_out, double *grad_alphas_out);
+int bpltv_unrolled_vjp_each_device(bpltv_t *h, const double *d_tape, const double *d_alphas, int am, int an,
+                                   const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alphas);
+int bpltv_unrolled_jvp_each(bpltv_t *h, const double *alphas, int am, int an, const bpltv_params *p, int ndir,
+                            const double *df, const double *dalphas, double *du_out, double *u_out /* may be NULL */);
+int bpltv_unrolled_jvp_each_device(bpltv_t *h, const double *d_alphas, int am, int an, const bpltv_params *p, int ndir,
+                                   const double *d_df, const double *d_dalphas, double *d_du, double *d_u /* may be NULL */);
+
 /* Jacobian-vector product of u = denoise(f, alpha) (TV model): du for tangents (df, dalpha), defined as the linear map
  * whose transpose bpltv_vjp computes, in every branch -- <gu, du> = <grad_f(gu), df> + <grad_alpha(gu), dalpha> for any
  * gu -- so forward and reverse mode agree, also where the reference's linearisation is not the true one (reg = 1 with an

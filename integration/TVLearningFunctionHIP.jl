@@ -5,7 +5,8 @@
 # bpldenoising_amd/_lib.py (ctypes) by the test suite.
 # Same exports as src/TVLearningFunctionVec.jl:6
 export tv_op_learning_function, denoise, sumregs_learning_function, tv_vjp, sumregs_vjp, tv_jvp, tv_gauss_newton,
-       sumregs_jvp, sumregs_gauss_newton, weighted_denoise, weighted_vjp
+       sumregs_jvp, sumregs_gauss_newton, weighted_denoise, weighted_vjp, unrolled_denoise_each, unrolled_vjp_each,
+       unrolled_jvp_each
 
 const libbpltv = "libbpltv"            # on LD_LIBRARY_PATH, or an absolute path
 
@@ -259,6 +260,51 @@ function tv_gauss_newton(h::BpltvHandle, u::Array{Float64,3}, ū::Array{Float64,
         (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Cint, Cint, Ref{BpltvParams}, Ptr{Cdouble}, Ptr{Cdouble}),
         h.ptr, u, ū, a, am, an, reg ? 1 : 0, p, g, H))
     return (α isa Real ? g[1] : reshape(g, size(α))), H
+end
+
+# One parameter per image through the PDHG iterations (include/bpltv.h, bpltv_unrolled_denoise_each / _vjp_each / _jvp_each):
+# what a network that predicts α per sample needs in front of a fixed, small maxiter.  αs: an O-vector (one scalar per
+# image) or an m x n x O array (block k = αs[:, :, k], column major, as the library reads it).
+alphas_arg(x::AbstractVector) = (Vector{Float64}(x), 1, 1)
+alphas_arg(x::AbstractArray{<:Real,3}) = (Array{Float64,3}(x), size(x, 1), size(x, 2))
+
+# u[:, :, k] = denoise(data[:, :, k], αs[k]) by exactly maxiter iterations; records the handle's tape, per image.
+function unrolled_denoise_each(data::Array{Float64,3}, αs; kwargs...)
+    h = handle_for(data, data)
+    a, am, an = alphas_arg(αs)
+    length(a) == am * an * size(data, 3) || error("unrolled_denoise_each: one parameter block per image")
+    u = similar(data)
+    p = Ref(default_params(; kwargs...))
+    GC.@preserve a u bpltv_check(h, ccall((:bpltv_unrolled_denoise_each, libbpltv), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Ref{BpltvParams}, Ptr{Cdouble}), h.ptr, a, am, an, p, u))
+    return h, u
+end
+
+# (dL/df, dL/dαs) of the maxiter-step map by a reverse sweep over the handle's per-image tape: same h, αs and params as the
+# solve.  dL/dαs has the shape of αs; block k is image k's term alone.
+function unrolled_vjp_each(h::BpltvHandle, αs, ḡ::Array{Float64,3}; kwargs...)
+    a, am, an = alphas_arg(αs)
+    gf = similar(ḡ); ga = zeros(size(a))
+    p = Ref(default_params(; kwargs...))
+    GC.@preserve a ḡ gf ga bpltv_check(h, ccall((:bpltv_unrolled_vjp_each, libbpltv), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Ref{BpltvParams}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        h.ptr, a, am, an, p, ḡ, gf, ga))
+    return gf, ga
+end
+
+# du of the maxiter-step map of the handle's dataset for one direction (df, dαs): df nothing or M x N x O, dαs nothing or
+# shaped like αs; returns (du, u) with u the primal result.
+function unrolled_jvp_each(h::BpltvHandle, αs; df = nothing, dαs = nothing, kwargs...)
+    a, am, an = alphas_arg(αs)
+    df === nothing && dαs === nothing && error("unrolled_jvp_each: df and dαs are both nothing")
+    tf = df === nothing ? C_NULL : Array{Float64}(df)
+    ta = dαs === nothing ? C_NULL : Array{Float64}(dαs)
+    du = zeros(h.M, h.N, h.O); u = zeros(h.M, h.N, h.O)
+    p = Ref(default_params(; kwargs...))
+    GC.@preserve a tf ta du u bpltv_check(h, ccall((:bpltv_unrolled_jvp_each, libbpltv), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Ref{BpltvParams}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        h.ptr, a, am, an, p, 1, tf, ta, du, u))
+    return du, u
 end
 
 # The same for u = sumregs_denoise(f, x) (include/bpltv.h, bpltv_sumregs_vjp): x a 3-vector or an m x n x 3 array, passed
