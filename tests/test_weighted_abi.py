@@ -116,6 +116,28 @@ def test_twin_with_unit_weight_is_the_unweighted_twin():
             assert d <= 1e-13
 
 
+@pytest.mark.parametrize("shape", [(2, 70, 72), (2, 17, 33), (3, 40, 48), (1, 1, 9), (1, 9, 1)], ids=lambda s: "x".join(map(str, s)))
+def test_twin_with_a_real_weight_is_its_extended_precision_restatement(shape):
+    """The GPU tests hold the library to 1e-13 of this twin (tests/test_gpu_weighted_shapes.py); the twin's own rounding has
+    to sit well inside that: float64 against numpy's 80-bit longdouble, 203 iterations, at those tests' shapes, with a random
+    weight, six decades of weight and a mask, scalar and map parameter.  Measured: 9e-16 at most; the bound keeps a decade
+    between the twin's error and what the library is allowed."""
+    if np.finfo(np.longdouble).nmant < 63:
+        pytest.skip("numpy's longdouble is no wider than float64 on this platform")
+    O, N, M = shape
+    _, f = synth_batch(O, N, M, seed=40 + M)
+    rng = np.random.default_rng(77)
+    rand = 0.25 + 3.75 * rng.random((O, N, M))
+    mask = rand.copy()
+    mask.reshape(O, -1)[:, -3:] = 0.0
+    mask[:, N // 3:N // 3 + 6, M // 3:M // 3 + 6] = 0.0
+    for alpha in (0.1, 0.05 + 0.1 * np.random.default_rng(8).random((N, M))):
+        for name, w in (("rand", rand), ("log", 10.0 ** rng.uniform(-3.0, 3.0, (O, N, M))), ("mask", mask)):
+            d = float(np.abs(wr.pdhg(f, alpha, w, 203) - wr.pdhg(f, alpha, w, 203, dtype=np.longdouble)).max())
+            print("%s alpha %s %s: max|du| = %.3e" % (shape, np.shape(alpha), name, d))
+            assert d <= 1e-14
+
+
 def test_twin_gap_with_unit_weight_is_the_rof_gap():
     _, f = synth_batch(2, 16, 20, seed=4)
     u, y1, y2 = wr.pdhg(f, 0.1, np.ones((16, 20)), 150, return_dual=True)
@@ -147,20 +169,33 @@ def test_scaled_system_is_the_literal_system(kind):
         assert rel <= 1e-12
 
 
-@pytest.mark.parametrize("kind", sorted(KINDS))
-def test_reference_vjp_is_stable_under_refinement(kind):
-    """The tolerances the GPU test holds the library to (rtol 1e-6, atol 1e-8 max|p|, tests/test_gpu_vjp.py) must be wider
+def _vjp_pin_cases():
+    """(2, 16, 20) with KINDS, as tests/test_gpu_weighted.py uses it, and tests/test_gpu_weighted_shapes.py's four shapes
+    with that file's own parameters (scalar 0.1, the 2 x 2 patch, a map of the image's size).  The first three keep the
+    ids they had before the shapes were added."""
+    from test_gpu_weighted import _alpha
+    cases = [pytest.param((2, 16, 20), KINDS[k], id=k) for k in sorted(KINDS)]
+    for O, N, M in wr.VJP_SHAPES:
+        cases += [pytest.param((O, N, M), _alpha(k, N, M), id="%dx%dx%d-%s" % (O, N, M, k)) for k in ("map", "patch", "scalar")]
+    return cases
+
+
+@pytest.mark.parametrize("shape,alpha", _vjp_pin_cases())
+def test_reference_vjp_is_stable_under_refinement(shape, alpha):
+    """The tolerances the GPU tests hold the library to (rtol 1e-6, atol 1e-8 max|p|, tests/test_gpu_vjp.py) must be wider
     than the reference's own error: its plain sparse LU (refine 0) against ten extended-precision sweeps on the GPU
-    test's own case, (2, 16, 20).  Measured: 4e-12 absolute at most."""
-    alpha = KINDS[kind]
-    f, w, u, gu = wr.vjp_case(alpha, seed=21)
+    tests' own cases, seed 21, one weight plane per image.  Measured: 4e-12 absolute at most on (2, 16, 20); 4.2e-11 on
+    (2, 40, 48), (3, 33, 17), (2, 70, 72) and (1, 12, 140), where max|p| is 1.7 ... 5.8."""
+    O, N, M = shape
+    f, w, u, gu = wr.vjp_case(alpha, seed=21, O=O, N=N, M=M)
     kap = wr.kappa_default(alpha)
     r0 = wr.vjp(u, f, alpha, w, gu, kap, refine=0)
     r1 = wr.vjp(u, f, alpha, w, gu, kap, refine=10)
     pmax = float(np.abs(r1[3]).max())
     for name, a, b in zip(("grad_f", "grad_alpha", "grad_w"), r0, r1):
         a, b = np.asarray(a), np.asarray(b)
-        print("%s %s: max|d| = %.3e (max|ref| %.3e)" % (kind, name, float(np.abs(a - b).max()), float(np.abs(b).max())))
+        print("%s %s: max|d| = %.3e (max|ref| %.3e, max|p| %.3e)" % (shape, name, float(np.abs(a - b).max()),
+                                                                   float(np.abs(b).max()), pmax))
         assert np.allclose(a, b, rtol=1e-6, atol=1e-8 * pmax)
         assert np.allclose(a, b, rtol=1e-9, atol=1e-10 * pmax)    # ... with two digits to spare
 

@@ -37,14 +37,20 @@ def step_table(maxiter, gamma, tau0=5.0, sigma0=0.99 / 5, accel=True, opnorm=0.0
     return tab
 
 
-def pdhg(f, alpha, w, maxiter, tau0=5.0, sigma0=0.99 / 5, accel=True, opnorm=0.0, return_dual=False):
+def pdhg(f, alpha, w, maxiter, tau0=5.0, sigma0=0.99 / 5, accel=True, opnorm=0.0, return_dual=False, dtype=np.float64):
     """x = f, y = 0; per iteration: t = div - w f; x = (x - tau t) / (1 + tau w); xbar, dual ascent and the projection on
-    the alpha-ball as np_twin.pdhg_denoise; gamma = min over ALL entries of w."""
+    the alpha-ball as np_twin.pdhg_denoise; gamma = min over ALL entries of w.
+    dtype = np.longdouble: the same recurrence on the same (double) step table in extended precision, with 1 / sqrt for the
+    Newton rsqrt -- what tests/test_weighted_abi.py measures this twin's own rounding against."""
     f = np.asarray(f, dtype=np.float64)
     N, M = f.shape[-2:]
     w = weight_planes(w, f.shape if f.ndim == 3 else (1,) + f.shape)
     amap = tw.alpha_to_map(alpha, M, N)
     tab = step_table(maxiter, float(w.min()), tau0, sigma0, accel, opnorm)
+    rsqrt = tw.rsqrt_nr
+    if dtype is not np.float64:
+        f, w, amap, tab = (a.astype(dtype) for a in (f, w, amap, tab))
+        rsqrt = lambda v: 1.0 / np.sqrt(v)
     x = f.copy()
     y1 = np.zeros_like(f)
     y2 = np.zeros_like(f)
@@ -60,7 +66,7 @@ def pdhg(f, alpha, w, maxiter, tau0=5.0, sigma0=0.99 / 5, accel=True, opnorm=0.0
         y2 = y2 + sigma * d2
         n2 = y1 * y1 + y2 * y2
         with np.errstate(all="ignore"):
-            v = np.where(n2 > a2, amap * tw.rsqrt_nr(np.where(n2 > a2, n2, 1.0)), 1.0)
+            v = np.where(n2 > a2, amap * rsqrt(np.where(n2 > a2, n2, 1.0)), 1.0)
         y1 = y1 * v
         y2 = y2 * v
     if return_dual:
@@ -161,6 +167,12 @@ def vjp(u, f, alpha, w, gu, kappa, refine=0):
     return gf, ga, (gw.sum(axis=0) if w.ndim == 2 else gw), pp
 
 
+# the shapes tests/test_gpu_weighted_shapes.py runs every factorisation on (tests/test_weighted_abi.py pins the reference
+# on each): several tiles and fronts, odd sizes with N > M, the denoise tests' largest, and the only one with M > 138 (the
+# band in HBM instead of LDS; no block cyclic reduction)
+VJP_SHAPES = [(2, 40, 48), (3, 33, 17), (2, 70, 72), (1, 12, 140)]
+
+
 def vjp_case(alpha, seed, O=2, N=16, M=20, iters=60, per_image=True):
     """(f, w, u, gu) for the VJP tests: w random in [0.25, 4], u the twin's iterate after `iters` iterations with two
     flat blocks planted (an active set |G u| < 1e-12 the kappa weight acts on), gu random.  A VJP takes any u; this
@@ -168,6 +180,7 @@ def vjp_case(alpha, seed, O=2, N=16, M=20, iters=60, per_image=True):
     agrees with its extended-precision refinement to 1e-11, while on a converged u (|G u| down to 1e-12 next to the
     active set) the two differ by up to 2e-6 -- more than the tolerance the library is held to."""
     from conftest import synth_batch
+    assert N >= 12 and M >= 16, "the planted blocks sit at rows 3:6 / 10:12 and columns 4:8 / 15:"
     _, f = synth_batch(O, N, M, seed=seed)
     rng = np.random.default_rng(seed + 1)
     w = 0.25 + 3.75 * rng.random((O, N, M) if per_image else (N, M))
