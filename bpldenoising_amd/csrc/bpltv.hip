@@ -31,6 +31,7 @@
 #include "weighted_kernels.hpp"
 #include "unrolled_kernels.hpp"
 #include "unrolled_jvp_kernels.hpp"
+#include "weighted_unrolled_kernels.hpp"
 #include "multi_gpu.hpp"
 
 using namespace bpltv;
@@ -197,7 +198,7 @@ struct GraphKey {
     int accel, dbg, nimg;
     const void* state; // state set 0 of the solve context: a sweep never replays a dataset-context graph, nor the reverse
                        // (MODEL_UN: the tape the launches write or read, with variant 0 = taped solve, 1 = reverse sweep; 2 ... 5 = tangent
-                       // sweep, whose planes stand here instead)
+                       // sweep, whose planes stand here instead; 6 = weighted taped solve, 7 / 8 = its reverse sweep without / with grad_w)
     const void* tab;   // step table (one per (maxiter, steps, L, dual-first shift, gamma): TabKey)
     int from_state;    // 1: the sequence starts from a prepared state (params.init / order), not from x = f, y = 0
     const void* alpha; // the parameter the launches read: a sweep's blocks and the dataset's parameter are different
@@ -433,6 +434,15 @@ struct bpltv_handle {
     bool tape_each = false;                         // recorded by bpltv_unrolled_denoise_each: one parameter block per image
     double tape_tau0 = 0.0, tape_sigma0 = 0.0, tape_opnorm = 0.0;
     double* d_unr = nullptr;                        // 9 * M*N*O doubles
+    // ... of the weighted model (weighted_unrolled_kernels.hpp): a tape of its own (z1, z2 and x per iteration), so that a TV
+    // tape and a weighted one never stand in for each other, with the weight planes and gamma = min w it was recorded with;
+    // the reverse sweep runs in d_unr, its weight gradient in a tenth plane allocated when grad_w is first asked for
+    double* d_wtape = nullptr;
+    size_t wtape_cap = 0;                           // doubles
+    bool wtape_valid = false;
+    int wtape_maxiter = 0, wtape_am = 0, wtape_an = 0, wtape_accel = 0, wtape_wo = 0;
+    double wtape_tau0 = 0.0, wtape_sigma0 = 0.0, wtape_opnorm = 0.0, wtape_gamma = 0.0;
+    double* d_unr_gw = nullptr;                     // M*N*O doubles
     // forward mode through the iterations (unrolled_jvp_kernels.hpp): the tangent sweep's planes [2 sets x (x, y1, y2, dx, dy1,
     // dy2) | df | dalpha], allocated on first use and never moved
     double* d_ujv = nullptr;                        // 14 * M*N*O doubles
@@ -1532,6 +1542,7 @@ struct GradCtx {
     const double* w = nullptr;
     int wo = 1;
     bool w_unit = false;           // every entry of w is exactly 1.0: the system, and the sweeps it gets, are bpltv_vjp's
+    double w_min = 0.0;            // smallest entry of w (the reverse sweep of the weighted iterations: gamma of its step table)
     const double* f = nullptr;
     double* d_grad_w = nullptr;
 };
@@ -1794,9 +1805,11 @@ int weighted_check_params(bpltv_t* h, const bpltv_params& p, const char* who);
 // that the last solve -- d_alpha with its shape and minimum, d_w, the PDHG state and graphs, and so bpltv_u_device and
 // bpltv_duality_gap -- stays as it was.  Fills *p (the resolved params) and the parameter fields of *g.
 // slices: 1 TV, 3 sum of regularisers (the parameter is 3*am*an doubles).  each: alpha holds O blocks, image k reads block k.
-// w (nullable; wo planes): the weighted model, every entry > 0; staged behind the parameter gradient.
+// w (nullable; wo planes): the weighted model, every entry > 0 (w_pos; >= 0 without: the reverse sweep of the iterations
+// divides by nothing); staged behind the parameter gradient.
 int stage_param(bpltv_t* h, const char* who, const double* alpha, bool alpha_dev, int am, int an, int slices, bool each, int reg,
-                const bpltv_params* pp, const double* w, int wo, std::initializer_list<DevArray> extra, bpltv_params* p, GradCtx* g) {
+                const bpltv_params* pp, const double* w, int wo, std::initializer_list<DevArray> extra, bpltv_params* p, GradCtx* g,
+                bool w_pos = true) {
     if (am < 1 || an < 1 || am > h->M || an > h->N)
         return set_err(h, BPLTV_E_ARG, "%s: parameter shape %dx%d (image %dx%d)", who, am, an, h->M, h->N);
     const bool sr = slices == 3;
@@ -1809,7 +1822,7 @@ int stage_param(bpltv_t* h, const char* who, const double* alpha, bool alpha_dev
         if (int crc = check_alpha_host(h, (std::string(who) + ": alpha").c_str(), alpha, P, &amin)) return crc;
     if (w) {
         if (int rc = check_weight(h, who, w, alpha_dev, nw, &wmin, &wmax)) return rc;
-        if (!(wmin > 0.0)) return set_err(h, BPLTV_E_ARG, "%s: the adjoint system scales with 1/sqrt(w): every weight must be > 0 (min = %g)", who, wmin);
+        if (w_pos && !(wmin > 0.0)) return set_err(h, BPLTV_E_ARG, "%s: the adjoint system scales with 1/sqrt(w): every weight must be > 0 (min = %g)", who, wmin);
     }
     int rc = ensure(h, &h->d_vjp, &h->vjp_cap, 4 + 2 * P + nw);
     if (rc) return rc;
@@ -1826,7 +1839,7 @@ int stage_param(bpltv_t* h, const char* who, const double* alpha, bool alpha_dev
     if (w) HIPCHK(h, hipMemcpyAsync(d_wv, w, nw * sizeof(double), kind, h->stream));
     g->alpha = d_a; g->am = am; g->an = an; g->alpha_min = amin;
     g->astride = each ? slices * am * an : 0; g->each = each;
-    if (w) { g->w = d_wv; g->wo = wo; g->w_unit = (wmin == 1.0 && wmax == 1.0); }
+    if (w) { g->w = d_wv; g->wo = wo; g->w_unit = (wmin == 1.0 && wmax == 1.0); g->w_min = wmin; }
     return BPLTV_OK;
 }
 
@@ -3506,6 +3519,223 @@ int unrolled_vjp_common(bpltv_t* h, const double* d_tape_user, const double* alp
     return BPLTV_OK;
 }
 
+// ============================================================================================
+// Reverse mode through the iterations of the weighted model (weighted_unrolled_kernels.hpp)
+// ============================================================================================
+const char* const kWeightedUnrolled = "the weighted unrolled solve";   // what weighted_multi's message calls these entry points
+
+// maxiter taped iterations of the weighted recurrence on the dataset images, in the TV state sets, with the handle's d_w /
+// w_wo / w_min and d_alpha; z_k and x_{k+1} of every pixel into d_tape.
+int run_weighted_unrolled_pdhg(bpltv_t* h, const bpltv_params& p, const WeightedPlan& pl, double* d_tape, int* result_buf) {
+    h->has_per_image = false;
+    double* d_tab = nullptr;
+    int rc = get_table(h, p, &d_tab, 8.0, 0, h->w_min);
+    if (rc) return rc;
+    const int M = h->M, N = h->N, O = h->O, T = pl.T;
+    const bool amap = (h->last_am == M && h->last_an == N) && !(M == 1 && N == 1);
+    h->st.tile_iters = T; h->st.tiles = pl.nTi * pl.nTj * O; h->st.region_i = UN_R; h->st.region_j = UN_R; h->st.pdhg_variant = 0;
+    ChainSolve j;
+    j.model = MODEL_UN; j.nplanes = 3; j.state0 = h->d_state[0];
+    j.nimg = O; j.niter = p.maxiter; j.T = T;
+    j.chains = plan_chains(p.reserved[1], h->st.tiles, h->ncu, O, 2);   // at most two (image groups on two streams)
+    j.serial = (p.reserved[2] & 1) != 0; j.helper_thread = !(p.reserved[2] & 8);
+    j.bytes_per_px_iter = amap ? 96.0 : 88.0;   // read x, y1, y2, f, w (+ alpha), write x, y1, y2 and z1, z2, x
+    j.key = GraphKey{p.maxiter, T, 6, h->last_am, h->last_an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_tape, (const void*)d_tab, 0,
+                     (const void*)h->d_alpha, 0, h->w_wo};
+    j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
+        int step = stagger ? T / 2 : T;
+        for (int it = it0; it < it1; it += step, step = T) {
+            const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
+            WeightedUnrolledArgs a;
+            a.xin = h->d_state[cur][0]; a.y1in = h->d_state[cur][1]; a.y2in = h->d_state[cur][2];
+            a.xout = h->d_state[nxt][0]; a.y1out = h->d_state[nxt][1]; a.y2out = h->d_state[nxt][2];
+            a.f = h->d_f; a.w = h->d_w; a.alpha = h->d_alpha; a.tab = d_tab; a.tape = d_tape; a.plane = h->tot;
+            a.wstride = h->w_wo > 1 ? h->npx : 0;
+            a.am = h->last_am; a.an = h->last_an;
+            a.it0 = it; a.nit = std::min(step, it1 - it);
+            a.M = M; a.N = N; a.halo = T; a.first = (it == 0) ? 1 : 0; a.img0 = lo;
+            hipLaunchKernelGGL(weighted_unrolled_tile_kernel, dim3(pl.nTi, pl.nTj, hi - lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), st, a);
+            cur = nxt;
+        }
+        return cur;
+    };
+    return run_chains(h, p, j, result_buf);
+}
+
+// bpltv_weighted_unrolled_denoise(_device) on a single-device handle: weighted_denoise_common's order (arguments, params, w,
+// then upload_alpha, and only then the handle's copy of w) with unrolled_denoise_common's tape -- d_tape_user or the handle's
+// own, whose new buffer is allocated before anything changes and installed only once the parameter is accepted.
+int weighted_unrolled_denoise_common(bpltv_t* h, const double* w, int wo, const double* alpha, bool dev, int am, int an,
+                                     const bpltv_params* pp, double* d_tape_user, double* u_out) {
+    const char* who = dev ? "bpltv_weighted_unrolled_denoise_device" : "bpltv_weighted_unrolled_denoise";
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: bpltv_set_data has not been called", who);
+    if (!w) return set_err(h, BPLTV_E_ARG, "%s: w is a null pointer", who);
+    if (wo != 1 && wo != h->O) return set_err(h, BPLTV_E_ARG, "%s: wo = %d: one weight plane (1) or one per image (%d)", who, wo, h->O);
+    const bpltv_params p = resolve(pp);
+    if (int prc = unrolled_check_params(h, p, who)) return prc;
+    WeightedPlan pl;
+    if (int prc = unrolled_plan(h, p, PDHG_MAX_T, &pl)) return prc;
+    const size_t nw = (size_t)wo * h->npx;
+    double wmin = 0.0;
+    int rc = check_weight(h, who, w, dev, nw, &wmin);
+    if (rc) return rc;
+    const size_t need = (size_t)3 * p.maxiter * h->tot;
+    double* grown = nullptr;
+    if (!d_tape_user && h->wtape_cap < need) {
+        const hipError_t e = hipMalloc((void**)&grown, need * sizeof(double));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return set_err(h, e == hipErrorOutOfMemory ? BPLTV_E_NOMEM : BPLTV_E_HIP, "%s: hipMalloc of the tape (%.1f MB) failed: %s", who,
+                           need * sizeof(double) / 1e6, hipGetErrorString(e));
+        }
+    }
+    if (!h->d_w) {
+        rc = alloc_all(h, {{(void**)&h->d_w, h->tot * sizeof(double)}}, "fidelity weight");
+        if (rc) {
+            if (grown) (void)hipFree(grown);
+            return rc;
+        }
+    }
+    bpltv_params q = p;   // the TV planner's knobs mean nothing here: upload_alpha's precheck sees the defaults
+    q.tile_iters = 0; q.reserved[0] = 0; q.reserved[1] = 0; q.reserved[2] = 0;
+    rc = upload_alpha(h, alpha, dev, am, an, PRE_TV, 1, &q);
+    if (rc) {
+        if (grown) (void)hipFree(grown);
+        return rc;
+    }
+    if (grown) {
+        if (h->d_wtape) (void)hipFree(h->d_wtape);
+        h->d_wtape = grown;
+        h->wtape_cap = need;
+    }
+    if (!d_tape_user) h->wtape_valid = false;   // about to be overwritten
+    HIPCHK(h, hipMemcpyAsync(h->d_w, w, nw * sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+    h->w_wo = wo;
+    h->w_min = wmin;
+    int buf = 0;
+    rc = run_weighted_unrolled_pdhg(h, p, pl, d_tape_user ? d_tape_user : h->d_wtape, &buf);
+    if (rc) return rc;
+    h->result_buf = buf;
+    h->has_result = true;
+    h->last_is_sr = false;
+    h->last_weighted = true;
+    if (!d_tape_user) {
+        h->wtape_valid = true;
+        h->wtape_maxiter = p.maxiter; h->wtape_am = am; h->wtape_an = an; h->wtape_accel = p.accel ? 1 : 0; h->wtape_wo = wo;
+        h->wtape_tau0 = p.tau0; h->wtape_sigma0 = p.sigma0; h->wtape_opnorm = p.opnorm; h->wtape_gamma = wmin;
+    }
+    if (u_out) {
+        HIPCHK(h, hipMemcpyAsync(u_out, h->d_state[buf][0], h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
+// bpltv_weighted_unrolled_vjp(_device) on a single-device handle: d_gu and the outputs live in HBM, w and alpha on the host or
+// (dev) in HBM; d_tape_user or the handle's weighted tape.  w (every entry >= 0) and the parameter are staged apart
+// (stage_param) and the sweep runs in d_unr, so the last solve stays untouched; of the statistics only adjoint_ms and
+// adjoint_method change.  The resident f is read for d_grad_w only.  The step table is the solve's (gamma = min w), held fixed.
+int weighted_unrolled_vjp_common(bpltv_t* h, const double* d_tape_user, const double* w, int wo, const double* alpha, bool dev, int am,
+                                 int an, const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alpha,
+                                 double* d_grad_w) {
+    const char* who = "weighted_unrolled_vjp";
+    if (!w || !alpha || !d_gu) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
+    if (!d_grad_f && !d_grad_alpha && !d_grad_w) return set_err(h, BPLTV_E_ARG, "%s: all three outputs are NULL", who);
+    if (wo != 1 && wo != h->O) return set_err(h, BPLTV_E_ARG, "%s: wo = %d: one weight plane (1) or one per image (%d)", who, wo, h->O);
+    const bpltv_params p0 = resolve(pp);
+    if (int prc = unrolled_check_params(h, p0, who)) return prc;
+    if (d_grad_w && !h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: grad_w reads the resident f: bpltv_set_data has not been called", who);
+    if (!d_tape_user) {
+        if (!h->wtape_valid)
+            return set_err(h, BPLTV_E_NODATA, "%s: the handle holds no weighted tape (bpltv_weighted_unrolled_denoise has not run)", who);
+        if (h->wtape_maxiter != p0.maxiter || h->wtape_am != am || h->wtape_an != an || h->wtape_wo != wo ||
+            h->wtape_accel != (p0.accel ? 1 : 0) || h->wtape_tau0 != p0.tau0 || h->wtape_sigma0 != p0.sigma0 || h->wtape_opnorm != p0.opnorm)
+            return set_err(h, BPLTV_E_ARG, "%s: the handle's tape was recorded with maxiter = %d, a %dx%d parameter, wo = %d and other steps than this call's (%d, %dx%d, wo = %d)",
+                           who, h->wtape_maxiter, h->wtape_am, h->wtape_an, h->wtape_wo, p0.maxiter, am, an, wo);
+    }
+    WeightedPlan pl;
+    if (int prc = unrolled_plan(h, p0, WUN_REV_T, &pl)) return prc;
+    const size_t tot = h->tot, npx = h->npx;
+    if (!h->d_unr)
+        if (int arc = alloc_all(h, {{(void**)&h->d_unr, 9 * tot * sizeof(double)}}, "reverse sweep")) return arc;
+    if (d_grad_w && !h->d_unr_gw)
+        if (int arc = alloc_all(h, {{(void**)&h->d_unr_gw, tot * sizeof(double)}}, "reverse sweep (weight gradient)")) return arc;
+    bpltv_params p;
+    GradCtx g;
+    if (int rc = stage_param(h, who, alpha, dev, am, an, 1, false, 0, pp, w, wo, {{d_gu, tot, "cotangent gu"}}, &p, &g, false)) return rc;
+    if (!d_tape_user && h->wtape_gamma != g.w_min)
+        return set_err(h, BPLTV_E_ARG, "%s: the handle's tape was recorded with gamma = min w = %g, this call's w has %g", who, h->wtape_gamma, g.w_min);
+    const int M = h->M, N = h->N, O = h->O, T = pl.T, K = p.maxiter;
+    const bool amap = am == M && an == N && !(M == 1 && N == 1);
+    if (d_grad_alpha && !amap)
+        if (int rc = ensure(h, &h->d_red, &h->red_cap, (size_t)am * an * O)) return rc;
+    h->has_per_image = false;
+    double* d_tab = nullptr;
+    if (int rc = get_table(h, p, &d_tab, 8.0, 0, g.w_min)) return rc;
+    const double* d_tape = d_tape_user ? d_tape_user : h->d_wtape;
+    double* S[2][3];
+    for (int s = 0; s < 2; ++s)
+        for (int c = 0; c < 3; ++c) S[s][c] = h->d_unr + (size_t)(3 * s + c) * tot;
+    double *d_gf = h->d_unr + 6 * tot, *d_ga = h->d_unr + 7 * tot, *d_g0 = h->d_unr + 8 * tot;
+    double* d_gw = d_grad_w ? h->d_unr_gw : nullptr;
+    const bpltv_stats_t kept = h->st;
+    HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_g0, d_gu, tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    ChainSolve j;
+    j.model = MODEL_UN; j.nplanes = 3; j.state0 = S[0];
+    j.nimg = O; j.niter = K; j.T = T;
+    const int tiles = pl.nTi * pl.nTj * O;
+    j.chains = plan_chains(p.reserved[1], tiles, h->ncu, O, 2);
+    j.serial = (p.reserved[2] & 1) != 0; j.helper_thread = !(p.reserved[2] & 8);
+    j.bytes_per_px_iter = 0.0;   // (the driver's solve statistics are not this call's: `kept` goes back below)
+    j.key = GraphKey{K, T, d_gw ? 8 : 7, am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_tape, (const void*)d_tab, 0, (const void*)g.alpha, 0, wo};
+    j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
+        int step = stagger ? T / 2 : T;
+        for (int it = it0; it < it1; it += step, step = T) {   // `it` counts reverse steps: step r undoes iteration K - 1 - r
+            const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
+            WeightedUnrolledRevArgs a;
+            a.gxin = (it == 0) ? d_g0 : S[cur][0]; a.gy1in = S[cur][1]; a.gy2in = S[cur][2];
+            a.gxout = S[nxt][0]; a.gy1out = S[nxt][1]; a.gy2out = S[nxt][2];
+            a.gf = d_gf; a.ga = d_ga; a.gw = d_gw; a.tape = d_tape; a.f = h->d_f; a.w = g.w; a.alpha = g.alpha; a.tab = d_tab;
+            a.plane = tot; a.wstride = wo > 1 ? npx : 0;
+            a.am = am; a.an = an;
+            a.khi = K - 1 - it; a.nit = std::min(step, it1 - it);
+            a.M = M; a.N = N; a.halo = T; a.first = (it == 0) ? 1 : 0; a.img0 = lo;
+            hipLaunchKernelGGL(weighted_unrolled_reverse_tile_kernel, dim3(pl.nTi, pl.nTj, hi - lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), st, a);
+            cur = nxt;
+        }
+        return cur;
+    };
+    int buf = 0;
+    const int rc = run_chains(h, p, j, &buf);
+    h->st = kept;
+    if (rc) return rc;
+    if (d_grad_f)
+        hipLaunchKernelGGL(unrolled_gradf_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, d_gf, S[buf][0], tot, d_grad_f);
+    if (d_grad_alpha && amap) {   // the per-pixel sums over the images, in image order; then per patch (calc_adjoint) or over everything
+        hipLaunchKernelGGL(map_sum_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, d_ga, npx, O, d_grad_alpha);
+    } else if (d_grad_alpha) {
+        hipLaunchKernelGGL(patch_sum_kernel, dim3(am * an, O), dim3(256), 0, h->stream, d_ga, M, N, O, am, an, O, 1, h->d_red);
+        hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, O, am * an, 1.0, d_grad_alpha, (double*)nullptr);
+    }
+    if (d_grad_w && wo > 1) {   // per image: the plane as it is; one plane: the sum over the images in image order
+        HIPCHK(h, hipMemcpyAsync(d_grad_w, d_gw, tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    } else if (d_grad_w) {
+        hipLaunchKernelGGL(map_sum_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, d_gw, npx, O, d_grad_w);
+    }
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
+    h->st.adjoint_ms = ms;
+    h->st.adjoint_method = 9;
+    return BPLTV_OK;
+}
+
 // bpltv_unrolled_jvp(_device) and bpltv_unrolled_gauss_newton on a single-device handle (unrolled_jvp_kernels.hpp, DESIGN.md
 // section 4.7): ndir tangent sweeps, one after the other, each the same launch sequence (direction d of a call is bitwise the
 // call with that direction alone).  The tangents d_df / d_dalpha (either may be nullptr: a zero tangent) and d_du live in HBM,
@@ -3723,7 +3953,7 @@ int bpltv_destroy(bpltv_t* h) {
     if (h->f32_sweep_alpha) (void)hipFree(h->f32_sweep_alpha);
     void* ptrs[] = {h->d_ubar, h->d_f, h->d_alpha, h->d_sweep_alpha, h->d_partial, h->d_red, h->d_perimg, h->d_scalar, h->d_coef,
                     h->d_band4, h->d_bcr, h->d_L, h->d_invF, h->d_invB, h->d_L1, h->d_dump, h->d_Lm, h->d_spill, h->d_p, h->d_r, h->d_gpix, h->d_resn, h->d_fail, h->d_u2, h->d_ubar2,
-                    h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres, h->d_w, h->d_wst, h->d_tape, h->d_unr, h->d_ujv};
+                    h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres, h->d_w, h->d_wst, h->d_tape, h->d_unr, h->d_ujv, h->d_wtape, h->d_unr_gw};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (int s = 0; s < 2; ++s)
@@ -4077,6 +4307,77 @@ int bpltv_unrolled_vjp_device(bpltv_t* h, const double* d_tape, const double* d_
     if (rc) return rc;
     h->st.total_ms = wt.ms();
     return BPLTV_OK;
+}
+
+int bpltv_weighted_unrolled_tape_doubles(bpltv_t* h, const bpltv_params* pp, unsigned long long* n_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (!n_out) return set_err(h, BPLTV_E_ARG, "bpltv_weighted_unrolled_tape_doubles: null pointer");
+    const bpltv_params p = resolve(pp);
+    if (p.maxiter < 1) return set_err(h, BPLTV_E_ARG, "bpltv_weighted_unrolled_tape_doubles: maxiter = %d (at least one iteration)", p.maxiter);
+    *n_out = 3ull * (unsigned long long)p.maxiter * (unsigned long long)h->M * h->N * h->O;
+    return BPLTV_OK;
+}
+
+int bpltv_weighted_unrolled_denoise(bpltv_t* h, const double* w, int wo, const double* alpha, int am, int an, const bpltv_params* pp,
+                                    double* u_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_weighted_unrolled_denoise", true, [&](bpltv_t* c) { return bpltv_weighted_unrolled_denoise(c, w, wo, alpha, am, an, pp, u_out); }, kWeightedUnrolled);
+    return weighted_unrolled_denoise_common(h, w, wo, alpha, false, am, an, pp, nullptr, u_out);
+}
+
+int bpltv_weighted_unrolled_denoise_device(bpltv_t* h, const double* d_w, int wo, const double* d_alpha, int am, int an,
+                                           const bpltv_params* pp, double* d_tape) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_weighted_unrolled_denoise_device", true, [&](bpltv_t* c) { return bpltv_weighted_unrolled_denoise_device(c, d_w, wo, d_alpha, am, an, pp, d_tape); }, kWeightedUnrolled);
+    return weighted_unrolled_denoise_common(h, d_w, wo, d_alpha, true, am, an, pp, d_tape, nullptr);
+}
+
+int bpltv_weighted_unrolled_vjp(bpltv_t* h, const double* w, int wo, const double* alpha, int am, int an, const bpltv_params* pp,
+                                const double* gu, double* grad_f_out, double* grad_alpha_out, double* grad_w_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_weighted_unrolled_vjp", false, [&](bpltv_t* c) {
+            return bpltv_weighted_unrolled_vjp(c, w, wo, alpha, am, an, pp, gu, grad_f_out, grad_alpha_out, grad_w_out);
+        }, kWeightedUnrolled);
+    if (!gu || !w || !alpha) return set_err(h, BPLTV_E_ARG, "weighted_unrolled_vjp: null pointer");
+    if (!grad_f_out && !grad_alpha_out && !grad_w_out) return set_err(h, BPLTV_E_ARG, "weighted_unrolled_vjp: all three outputs are NULL");
+    if (wo != 1 && wo != h->O) return set_err(h, BPLTV_E_ARG, "weighted_unrolled_vjp: wo = %d: one weight plane (1) or one per image (%d)", wo, h->O);
+    if (am < 1 || an < 1 || am > h->M || an > h->N)
+        return set_err(h, BPLTV_E_ARG, "weighted_unrolled_vjp: parameter shape %dx%d (image %dx%d)", am, an, h->M, h->N);
+    HIPCHK(h, hipSetDevice(h->device));
+    const size_t tot = h->tot, P = (size_t)am * an, nw = (size_t)wo * h->npx;
+    if (!h->d_u2) {
+        HIPCHK(h, hipMalloc((void**)&h->d_u2, tot * sizeof(double)));
+        HIPCHK(h, hipMalloc((void**)&h->d_ubar2, tot * sizeof(double)));
+    }
+    if (grad_f_out && !h->d_gf2) HIPCHK(h, hipMalloc((void**)&h->d_gf2, tot * sizeof(double)));
+    if (grad_w_out && !h->d_wst) HIPCHK(h, hipMalloc((void**)&h->d_wst, 2 * tot * sizeof(double)));
+    HIPCHK(h, hipMemcpyAsync(h->d_ubar2, gu, tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    int rc = ensure(h, &h->d_vjp, &h->vjp_cap, 4 + 2 * P + nw);
+    if (rc) return rc;
+    double* d_ga = grad_alpha_out ? h->d_vjp + 4 + P : nullptr;
+    double* d_gw = grad_w_out ? h->d_wst + tot : nullptr;
+    rc = weighted_unrolled_vjp_common(h, nullptr, w, wo, alpha, false, am, an, pp, h->d_ubar2, grad_f_out ? h->d_gf2 : nullptr, d_ga, d_gw);
+    if (rc) return rc;
+    if (grad_f_out) HIPCHK(h, hipMemcpyAsync(grad_f_out, h->d_gf2, tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (grad_alpha_out) HIPCHK(h, hipMemcpyAsync(grad_alpha_out, d_ga, P * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    if (grad_w_out) HIPCHK(h, hipMemcpyAsync(grad_w_out, d_gw, nw * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return BPLTV_OK;
+}
+
+int bpltv_weighted_unrolled_vjp_device(bpltv_t* h, const double* d_tape, const double* d_w, int wo, const double* d_alpha, int am, int an,
+                                       const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alpha,
+                                       double* d_grad_w) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, "bpltv_weighted_unrolled_vjp_device", false, [&](bpltv_t* c) {
+            return bpltv_weighted_unrolled_vjp_device(c, d_tape, d_w, wo, d_alpha, am, an, pp, d_gu, d_grad_f, d_grad_alpha, d_grad_w);
+        }, kWeightedUnrolled);
+    HIPCHK(h, hipSetDevice(h->device));
+    return weighted_unrolled_vjp_common(h, d_tape, d_w, wo, d_alpha, true, am, an, pp, d_gu, d_grad_f, d_grad_alpha, d_grad_w);
 }
 
 // bpltv_unrolled_jvp and bpltv_unrolled_jvp_each on a single-device handle: the host arrays staged around unrolled_jvp_common

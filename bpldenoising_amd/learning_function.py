@@ -453,6 +453,69 @@ class TVSolver:
                                                         C.c_void_p(grad_f_ptr or None),
                                                         C.c_void_p(grad_alpha_ptr or None)))
 
+    # -- reverse mode through the weighted iterations (bpltv_weighted_unrolled_*) --------------------------------
+    def weighted_unrolled_tape_doubles(self, **kw):
+        """Doubles of the tape a weighted unrolled solve with these params records: 3 * maxiter * M*N*O."""
+        p = self.params(**kw)
+        n = C.c_ulonglong(0)
+        self._check(self._lib.bpltv_weighted_unrolled_tape_doubles(self._h, C.byref(p), C.byref(n)))
+        return int(n.value)
+
+    def weighted_unrolled_denoise(self, x, w, fetch=True, **kw):
+        """weighted_denoise(x, w) -- the same u bit for bit, w >= 0 with zeros allowed -- that also records the tape of
+        the iterations in the handle, for weighted_unrolled_vjp with the same x, w and params
+        (bpltv_weighted_unrolled_denoise)."""
+        a, am, an, _ = _alpha_arg(x)
+        wa, wo = self._weight(w)
+        p = self.params(**kw)
+        u = np.empty((self.O, self.N, self.M)) if fetch else None
+        self._check(self._lib.bpltv_weighted_unrolled_denoise(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p),
+                                                              _ptr(u) if fetch else None))
+        return u
+
+    def weighted_unrolled_denoise_device(self, w_ptr, wo, alpha_ptr, am=1, an=1, tape_ptr=None, **kw):
+        """bpltv_weighted_unrolled_denoise_device: w (wo planes) and the parameter resident in HBM, the result left
+        there; tape_ptr: a caller-owned HBM buffer of weighted_unrolled_tape_doubles(**kw) doubles, or None / 0 for the
+        handle's own weighted tape."""
+        p = self.params(**kw)
+        self._check(self._lib.bpltv_weighted_unrolled_denoise_device(self._h, C.c_void_p(w_ptr), int(wo),
+                                                                     C.c_void_p(alpha_ptr), int(am), int(an),
+                                                                     C.byref(p), C.c_void_p(tape_ptr or None)))
+
+    def weighted_unrolled_vjp(self, x, w, gu, want_f=True, want_alpha=True, want_w=True, **kw):
+        """Vector-Jacobian product of the maxiter-step map u = weighted_unrolled_denoise(x, w) for the cotangent gu, by
+        a reverse sweep over the handle's weighted tape (bpltv_weighted_unrolled_vjp): (grad_f, grad_x, grad_w).  x, w
+        and the params must be those of the solve; w >= 0, zeros allowed.  grad_w has the shape of w -- for (N, M) the
+        sum over the images; an output not wanted is None."""
+        if not (want_f or want_alpha or want_w):
+            raise ValueError("weighted_unrolled_vjp: want_f, want_alpha and want_w are all False")
+        a, am, an, scalar = _alpha_arg(x)
+        wa, wo = self._weight(w)
+        p = self.params(**kw)
+        gu = self._batch(gu, "gu")
+        gf = np.empty((self.O, self.N, self.M)) if want_f else None
+        ga = np.empty(am * an) if want_alpha else None
+        gw = np.empty(wa.shape) if want_w else None
+        self._check(self._lib.bpltv_weighted_unrolled_vjp(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p), _ptr(gu),
+                                                          _ptr(gf) if want_f else None,
+                                                          _ptr(ga) if want_alpha else None,
+                                                          _ptr(gw) if want_w else None))
+        if ga is not None:
+            ga = float(ga[0]) if scalar else ga.reshape(an, am)
+        return gf, ga, gw
+
+    def weighted_unrolled_vjp_device(self, tape_ptr, w_ptr, wo, alpha_ptr, am, an, gu_ptr, grad_f_ptr, grad_alpha_ptr,
+                                     grad_w_ptr, **kw):
+        """bpltv_weighted_unrolled_vjp_device: the tape (None / 0: the handle's own), w, the parameter, gu and the
+        outputs resident in HBM (raw device pointers); any output pointer may be 0 / None, not all three."""
+        p = self.params(**kw)
+        self._check(self._lib.bpltv_weighted_unrolled_vjp_device(self._h, C.c_void_p(tape_ptr or None),
+                                                                 C.c_void_p(w_ptr), int(wo), C.c_void_p(alpha_ptr),
+                                                                 int(am), int(an), C.byref(p), C.c_void_p(gu_ptr),
+                                                                 C.c_void_p(grad_f_ptr or None),
+                                                                 C.c_void_p(grad_alpha_ptr or None),
+                                                                 C.c_void_p(grad_w_ptr or None)))
+
     # -- forward mode (bpltv_jvp / bpltv_gauss_newton) -------------------------------------------------------
     def _tangents(self, what, df, dalpha, ashape):
         """(df, dalpha, K, batched): the tangents as contiguous (K, ...) stacks, either None; batched = a leading K was

@@ -68,6 +68,14 @@ image k's term alone; forward_mode=True adds the jvp (one bpltv_unrolled_jvp_eac
 tv_denoise_unrolled never reads a leading batch dimension off alpha's shape.  It has no module class: a per-sample
 parameter is a network's output, not an nn.Parameter.
 
+    u = tv_denoise_weighted_unrolled(f, alpha, w, maxiter=50)   # ... of the weighted model (bpltv_weighted_unrolled_*)
+
+f, alpha and w as for tv_denoise_weighted, the same u bit for bit, but w may hold zeros wherever it likes: backward is the
+derivative of the maxiter-step map (one bpltv_weighted_unrolled_vjp_device call over a tape of 3 * maxiter * B*H*W doubles
+the forward pass allocates as a torch tensor), which scales nothing with 1/sqrt(w).  It returns f.grad, alpha.grad and
+w.grad as needs_input_grad asks, so alpha, f and a fidelity map can be trained through a masked (inpainting) solve; at
+w = 0, w.grad is the one-sided derivative.  The step table (gamma = min w) is held fixed.  No jvp.
+
 Streams: the library runs its kernels on its own HIP streams and blocks until they are done.  Every call below first
 synchronises the tensors' current torch stream, so that the library reads inputs torch has finished writing; its
 outputs are complete when the call returns.
@@ -483,22 +491,22 @@ class SumRegsDenoise(torch.nn.Module):
         return sumregs_denoise(f, self.alpha, reg=self.reg, forward_mode=self.forward_mode, **self.solver_kw)
 
 
-def _check_weight(f, w):
+def _check_weight(f, w, name="tv_denoise_weighted"):
     """wo (1 or B) of a valid weight for f; TypeError / ValueError before any library call."""
     if not isinstance(w, torch.Tensor):
-        raise TypeError("tv_denoise_weighted: w must be a torch tensor")
+        raise TypeError("%s: w must be a torch tensor" % name)
     if w.dtype != torch.float64:
-        raise TypeError("tv_denoise_weighted: w must be float64 (got %s)" % w.dtype)
+        raise TypeError("%s: w must be float64 (got %s)" % (name, w.dtype))
     H, W = f.shape[-2], f.shape[-1]
     if tuple(w.shape) == (H, W):
         wo = 1
     elif f.dim() == 3 and tuple(w.shape) == tuple(f.shape):
         wo = f.shape[0]
     else:
-        raise ValueError("tv_denoise_weighted: w must have shape (%d, %d) or f's shape %s; got %s"
-                         % (H, W, tuple(f.shape), tuple(w.shape)))
+        raise ValueError("%s: w must have shape (%d, %d) or f's shape %s; got %s"
+                         % (name, H, W, tuple(f.shape), tuple(w.shape)))
     if w.device != f.device:
-        raise ValueError("tv_denoise_weighted: w is on %s, f on %s" % (w.device, f.device))
+        raise ValueError("%s: w is on %s, f on %s" % (name, w.device, f.device))
     return wo
 
 
@@ -550,6 +558,65 @@ def tv_denoise_weighted(f, alpha, w, **solver_kw):
     in value and in f.grad / alpha.grad.  solver_kw: the solver parameters of TVSolver.params (rho, init and order must
     stay 0), used by the forward solve and the adjoint alike."""
     return TVDenoiseWeightedFunction.apply(f, alpha, w, solver_kw)
+
+
+class TVDenoiseWeightedUnrolledFunction(torch.autograd.Function):
+    """autograd.Function of tv_denoise_weighted_unrolled (below); apply(f, alpha, w, solver_kw).  No jvp."""
+
+    @staticmethod
+    def forward(ctx, f, alpha, w, solver_kw):
+        name = "tv_denoise_weighted_unrolled"
+        if not isinstance(f, torch.Tensor) or f.dim() not in (2, 3) or f.numel() == 0:
+            _check_args(f, alpha)   # raises: f has no (H, W) to hold w against
+        wo = _check_weight(f, w, name)   # (in front of the device check: a CPU triple with a wrong w reports the w)
+        if w.numel() and not bool((w.detach() >= 0).all()):   # (a NaN fails the comparison too)
+            raise ValueError("%s: w must be finite and >= 0 everywhere (zeros are allowed)" % name)
+        O, N, M, am, an = _check_args(f, alpha)
+        index = f.device.index if f.device.index is not None else torch.cuda.current_device()
+        s = _solver(index, M, N, O)
+        fc = f.detach().contiguous()
+        ac = alpha.detach().contiguous()
+        wc = w.detach().contiguous()
+        u = torch.empty_like(fc)
+        # the tape is this call's own: a second forward pass on the handle before backward does not overwrite it
+        tape = torch.empty(s.weighted_unrolled_tape_doubles(**solver_kw), dtype=torch.float64, device=f.device)
+        _sync(f.device)
+        s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
+        s.weighted_unrolled_denoise_device(wc.data_ptr(), wo, ac.data_ptr(), am, an, tape_ptr=tape.data_ptr(), **solver_kw)
+        s.copy_u_device(u.data_ptr())
+        ctx.save_for_backward(tape, fc, ac, wc)
+        ctx.solver, ctx.am, ctx.an, ctx.wo, ctx.solver_kw = s, am, an, wo, dict(solver_kw)
+        return u
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gu):
+        need_f, need_a, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
+        if not (need_f or need_a or need_w):
+            return None, None, None, None
+        tape, f, alpha, w = ctx.saved_tensors
+        gu = gu.to(dtype=torch.float64).contiguous()
+        gf = torch.empty_like(gu) if need_f else None
+        ga = torch.empty(ctx.am * ctx.an, dtype=torch.float64, device=gu.device) if need_a else None
+        gw = torch.empty_like(w) if need_w else None
+        _sync(gu.device)
+        if need_w:
+            ctx.solver.set_data_device(f.data_ptr(), f.data_ptr())   # grad_w reads the handle's dataset
+        ctx.solver.weighted_unrolled_vjp_device(tape.data_ptr(), w.data_ptr(), ctx.wo, alpha.data_ptr(), ctx.am, ctx.an,
+                                                gu.data_ptr(), gf.data_ptr() if need_f else None,
+                                                ga.data_ptr() if need_a else None, gw.data_ptr() if need_w else None,
+                                                **ctx.solver_kw)
+        return gf, (ga.reshape(alpha.shape) if need_a else None), gw, None
+
+
+def tv_denoise_weighted_unrolled(f, alpha, w, maxiter=50, **solver_kw):
+    """u = weighted_denoise(f, alpha, w) by exactly maxiter PDHG iterations (TVSolver.weighted_unrolled_denoise_device:
+    tv_denoise_weighted's u bit for bit at that maxiter), differentiable in f, alpha and w THROUGH the iterations: backward
+    is the exact derivative of the maxiter-step map (TVSolver.weighted_unrolled_vjp_device), with the step table held
+    fixed.  w: float64, (H, W) or f's shape (B, H, W), on f's device, >= 0 -- zeros are allowed, so a mask can be trained
+    through (inpainting), which tv_denoise_weighted's implicit gradient cannot.  solver_kw: the solver parameters of
+    TVSolver.params (rho, init and order must stay 0), used by the forward solve and the sweep alike."""
+    return TVDenoiseWeightedUnrolledFunction.apply(f, alpha, w, dict(solver_kw, maxiter=int(maxiter)))
 
 
 class TVDenoiseUnrolledFunction(torch.autograd.Function):

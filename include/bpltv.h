@@ -134,7 +134,8 @@ typedef struct bpltv_stats {
                                   gradient_reg system, with reserved[4] = 1), 5 nested-dissection (multifrontal)
                                   Cholesky, 6 nested-dissection LU (that row-scaled system, the default),
                                   7 reverse sweep over the taped iterations (bpltv_unrolled_vjp),
-                                  8 tangent sweep through the iterations (bpltv_unrolled_jvp)             */
+                                  8 tangent sweep through the iterations (bpltv_unrolled_jvp),
+                                  9 reverse sweep over the taped weighted iterations (bpltv_weighted_unrolled_vjp) */
     int reg_gradient_used;     /* 1 if the last evaluate took the gradient_reg branch             */
     int ngpus;                 /* distinct devices behind this handle (1 for bpltv_create)        */
     int shards;                /* image shards (= worker threads) behind this handle              */
@@ -399,6 +400,55 @@ int bpltv_unrolled_vjp(bpltv_t *h, const double *alpha, int am, int an, const bp
                        const double *gu, double *grad_f_out, double *grad_alpha_out);
 int bpltv_unrolled_vjp_device(bpltv_t *h, const double *d_tape, const double *d_alpha, int am, int an,
                               const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alpha);
+
+/* Reverse mode through the PDHG iterations of the weighted model: what bpltv_unrolled_* is to
+ * bpltv_denoise, for bpltv_weighted_denoise.  bpltv_weighted_vjp differentiates the exact minimiser and needs every w > 0;
+ * these differentiate the K-step map itself, exactly for any K, with no factorisation, no kappa, no active-set threshold and
+ * no w > 0: a mask (w in {0, 1}) gets gradients in f, alpha and w, and a learnable fidelity map gets dL/dw of the layer it is.
+ * The contract is the union of the two existing ones.
+ *
+ * bpltv_weighted_unrolled_denoise: w, wo, alpha, am, an, params and every rejection as bpltv_weighted_denoise (w finite and
+ * >= 0, wo = 1 or O, gamma = the smallest entry of ALL of w; rho, init and order must be 0, BPLTV_E_UNSUPPORTED; check_every /
+ * gap_tol are ignored; Float64 on dtype = 32 handles too), and maxiter < 1 is BPLTV_E_ARG; reserved[1] and reserved[2] apply as
+ * in bpltv_unrolled_denoise.  u is bpltv_weighted_denoise's bit for bit, for every w.  The solve becomes the handle's last
+ * weighted solve: bpltv_u_device, bpltv_copy_u_device and bpltv_duality_gap behave as after bpltv_weighted_denoise.  In every
+ * iteration it records the dual before its projection and the new primal iterate: the tape, 3 * maxiter * M*N*O doubles
+ * (bpltv_weighted_unrolled_tape_doubles; its layout is private).  stats: as bpltv_weighted_denoise with bytes_per_px_iter = 88
+ * (scalar / patch parameter) or 96 (map).
+ *
+ * The tape: d_tape is a caller-owned HBM buffer of bpltv_weighted_unrolled_tape_doubles doubles; a NULL d_tape, and the host
+ * forms always, use a weighted tape owned by the handle (allocated on demand, only growing, freed by bpltv_destroy;
+ * BPLTV_E_NOMEM, with the handle as it was, when it cannot be allocated).  It is not the tape of bpltv_unrolled_denoise: the
+ * handle keeps the two apart, so a TV tape and a weighted tape are never accepted for each other's VJP, and either survives the
+ * other model's solves.  The handle remembers maxiter, am, an, wo, gamma and the step parameters (tau0, sigma0, accel, opnorm)
+ * its weighted tape was recorded with: a VJP on the handle's tape returns BPLTV_E_NODATA if there is none and BPLTV_E_ARG if
+ * they differ.  With a caller's tape that match -- and the VALUES of w and alpha -- is the caller's contract.
+ *
+ * bpltv_weighted_unrolled_vjp: for a cotangent gu = dL/du (M*N*O doubles, finite) grad_f_out = dL/df (M*N*O doubles),
+ * grad_alpha_out = dL/dalpha (am*an doubles, reduced as bpltv_unrolled_vjp reduces it) and grad_w_out = dL/dw (M*N*wo doubles;
+ * for wo = 1 the sum over the images in image order); fixed order, no atomics.  Any output may be NULL, not all three
+ * (BPLTV_E_ARG).  w and alpha must be those of the solve; w is checked as the solve checks it (>= 0, zeros are legal).  At
+ * w = 0, grad_w is the one-sided derivative.  The resident f is read for grad_w only (BPLTV_E_NODATA without a dataset when
+ * grad_w_out is given).  The step table depends on gamma = min w; the VJP holds it fixed: exact for accel = 0 and for
+ * gamma = 0 (every mask), while with gamma > 0 and acceleration the derivative through the step sizes -- which touches only
+ * the entries of w that attain the minimum -- is omitted.  With w == 1, grad_f and grad_alpha agree with bpltv_unrolled_vjp's
+ * to rounding (u bit for bit).  Every rejection comes before anything of the handle changes; w and the parameter are staged
+ * apart and the last solve stays untouched.  stats: only adjoint_ms (the HIP-event time of the reverse sweep) and
+ * adjoint_method = 9 change.  The results do not depend on tile_iters, on the launch chains, on use_graph, on the host or
+ * device form or on whose tape it is, and these calls never replay the captured graphs of the TV, sum-of-regularisers,
+ * weighted or unrolled calls, nor the reverse.  Multi-device handles over more than one shard: BPLTV_E_UNSUPPORTED (all five);
+ * one shard is forwarded. */
+int bpltv_weighted_unrolled_tape_doubles(bpltv_t *h, const bpltv_params *p, unsigned long long *n_out);   /* 3*maxiter*M*N*O */
+int bpltv_weighted_unrolled_denoise(bpltv_t *h, const double *w, int wo, const double *alpha, int am, int an,
+                                    const bpltv_params *p, double *u_out);
+int bpltv_weighted_unrolled_denoise_device(bpltv_t *h, const double *d_w, int wo, const double *d_alpha, int am, int an,
+                                           const bpltv_params *p, double *d_tape);
+int bpltv_weighted_unrolled_vjp(bpltv_t *h, const double *w, int wo, const double *alpha, int am, int an,
+                                const bpltv_params *p, const double *gu,
+                                double *grad_f_out, double *grad_alpha_out, double *grad_w_out);
+int bpltv_weighted_unrolled_vjp_device(bpltv_t *h, const double *d_tape, const double *d_w, int wo, const double *d_alpha,
+                                       int am, int an, const bpltv_params *p, const double *d_gu,
+                                       double *d_grad_f, double *d_grad_alpha, double *d_grad_w);
 
 /* Forward mode through the PDHG iterations: the tangent of the K-step map that bpltv_unrolled_vjp
  * transposes -- <gu, du> = <grad_f(gu), df> + <grad_alpha(gu), dalpha> for any gu -- exact for any K, with no tape: a sweep
