@@ -32,6 +32,7 @@
 #include "unrolled_kernels.hpp"
 #include "unrolled_jvp_kernels.hpp"
 #include "weighted_unrolled_kernels.hpp"
+#include "sumregs_unrolled_kernels.hpp"
 #include "multi_gpu.hpp"
 
 using namespace bpltv;
@@ -187,7 +188,8 @@ const Variant kVariants[] = {
 };
 
 // The models whose solves the shared launch driver (run_chains) runs
-enum Model { MODEL_TV = 0, MODEL_SR = 1, MODEL_W = 2, MODEL_UN = 3, NMODELS = 4 };   // MODEL_UN: the taped solve, its reverse sweep and the tangent sweep
+enum Model { MODEL_TV = 0, MODEL_SR = 1, MODEL_W = 2, MODEL_UN = 3, MODEL_SRUN = 4, NMODELS = 5 };   // MODEL_UN: the taped solve, its reverse sweep and the tangent sweep
+                                                                                                     // MODEL_SRUN: the same of the sum-of-regularisers model
 
 // What identifies a launch sequence built into graphs: everything its kernel arguments and its cut into launches depend
 // on.  One key type for all models (a field a model does not use stays 0); each model has a cache of its own
@@ -198,7 +200,8 @@ struct GraphKey {
     int accel, dbg, nimg;
     const void* state; // state set 0 of the solve context: a sweep never replays a dataset-context graph, nor the reverse
                        // (MODEL_UN: the tape the launches write or read, with variant 0 = taped solve, 1 = reverse sweep; 2 ... 5 = tangent
-                       // sweep, whose planes stand here instead; 6 = weighted taped solve, 7 / 8 = its reverse sweep without / with grad_w)
+                       // sweep, whose planes stand here instead; 6 = weighted taped solve, 7 / 8 = its reverse sweep without / with grad_w;
+                       // MODEL_SRUN: the tape as well, variant 0 = taped solve, 1 = reverse sweep)
     const void* tab;   // step table (one per (maxiter, steps, L, dual-first shift, gamma): TabKey)
     int from_state;    // 1: the sequence starts from a prepared state (params.init / order), not from x = f, y = 0
     const void* alpha; // the parameter the launches read: a sweep's blocks and the dataset's parameter are different
@@ -366,7 +369,7 @@ struct bpltv_handle {
     size_t f32_alpha_cap = 0, f32_sweep_alpha_cap = 0;
     bool f32_f_valid = false;
     std::map<TabKey, float*> tabs32;
-    GraphCache graphs[NMODELS] = {{16}, {8}, {8}, {8}};   // by Model: at most 16 TV sequences, 8 of each other model
+    GraphCache graphs[NMODELS] = {{16}, {8}, {8}, {8}, {8}};   // by Model: at most 16 TV sequences, 8 of each other model
     std::vector<hipStream_t> chain_streams;   // the device's (DeviceStreams), not owned
     std::vector<hipEvent_t> chain_events;
     unsigned* d_phase = nullptr;              // the word chain 0's launches rewrite (PDHG_PHASE_STAMP, pdhg_phase_gate_kernel)
@@ -443,6 +446,16 @@ struct bpltv_handle {
     int wtape_maxiter = 0, wtape_am = 0, wtape_an = 0, wtape_accel = 0, wtape_wo = 0;
     double wtape_tau0 = 0.0, wtape_sigma0 = 0.0, wtape_opnorm = 0.0, wtape_gamma = 0.0;
     double* d_unr_gw = nullptr;                     // M*N*O doubles
+    // ... of the sum-of-regularisers model (sumregs_unrolled_kernels.hpp): a third tape (six dual components per iteration), kept
+    // apart from the other two and remembered with what it was recorded with; the reverse sweep runs in planes of its own,
+    // [2 sets x (gx, 6 gy) | gf | 3 ga | gu]
+    double* d_srtape = nullptr;
+    size_t srtape_cap = 0;                          // doubles
+    bool srtape_valid = false, srtape_each = false;
+    int srtape_maxiter = 0, srtape_am = 0, srtape_an = 0, srtape_accel = 0;
+    double srtape_tau0 = 0.0, srtape_sigma0 = 0.0, srtape_opnorm = 0.0;
+    double* d_srunr = nullptr;                      // 19 * M*N*O doubles
+    bool srun_ready = false;
     // forward mode through the iterations (unrolled_jvp_kernels.hpp): the tangent sweep's planes [2 sets x (x, y1, y2, dx, dy1,
     // dy2) | df | dalpha], allocated on first use and never moved
     double* d_ujv = nullptr;                        // 14 * M*N*O doubles
@@ -562,7 +575,8 @@ void cvt_to_f64(bpltv_t* h, const float* src, double* dst, size_t n) {
 //   the TV sweep's state sets or parameter blocks grow (bpltv_sweep)      TV
 //   the sum-of-regularisers sweep's planes or blocks grow (bpltv_sumregs_sweep)   sum of regularisers
 // d_f, d_w, the dataset state sets (d_state, d_sr) and the step tables live as long as the handle.
-enum { DROP_TV = 1 << MODEL_TV, DROP_SR = 1 << MODEL_SR, DROP_W = 1 << MODEL_W, DROP_UN = 1 << MODEL_UN, DROP_ALL = DROP_TV | DROP_SR | DROP_W | DROP_UN };
+enum { DROP_TV = 1 << MODEL_TV, DROP_SR = 1 << MODEL_SR, DROP_W = 1 << MODEL_W, DROP_UN = 1 << MODEL_UN, DROP_SRUN = 1 << MODEL_SRUN,
+       DROP_ALL = DROP_TV | DROP_SR | DROP_W | DROP_UN | DROP_SRUN };
 void drop_graphs(bpltv_t* h, int which);
 // step table rounded to float (the oracle's bplo_pdhg_f32 rounds the same f64 table)
 int get_table32(bpltv_t* h, const bpltv_params& p, float** out) {
@@ -3736,6 +3750,232 @@ int weighted_unrolled_vjp_common(bpltv_t* h, const double* d_tape_user, const do
     return BPLTV_OK;
 }
 
+// ============================================================================================
+// Reverse mode through the iterations of the sum-of-regularisers model (sumregs_unrolled_kernels.hpp)
+// ============================================================================================
+const char* const kSrUnrolled = "the sum-of-regularisers unrolled solve";   // what weighted_multi's message calls these entry points
+
+struct SrUnrolledPlan { int T = 0, nTi = 0, nTj = 0; };
+
+// run_sr_pdhg's cut of the image into 32 x 32 regions (halo 2T, default T = 4), with the fusion depth capped at `cap` (the
+// reverse kernel holds SRUN_REV_T iterations of tape in registers); the first use sets the kernels' LDS size
+int sr_unrolled_plan(bpltv_t* h, const bpltv_params& p, int cap, SrUnrolledPlan* pl) {
+    if (p.tile_iters < 0) return set_err(h, BPLTV_E_ARG, "tile_iters must be >= 0");
+    auto maxT = [](int L) { return (L <= SRUN_R) ? (1 << 20) : (SRUN_R - 1) / 4; };   // 2 * halo = 4T must leave a core
+    pl->T = std::min(std::min(p.tile_iters > 0 ? p.tile_iters : 4, cap), std::min(maxT(h->M), maxT(h->N)));
+    pl->nTi = tile_count(h->M, SRUN_R, 2 * pl->T);
+    pl->nTj = tile_count(h->N, SRUN_R, 2 * pl->T);
+    if (pl->T < 1 || pl->nTi < 1 || pl->nTj < 1) return set_err(h, BPLTV_E_ARG, "cannot tile %dx%d with T=%d", h->M, h->N, pl->T);
+    if (h->O > 65535) return set_err(h, BPLTV_E_UNSUPPORTED, "the sum-of-regularisers solve takes at most 65535 problems per launch (problems are a grid dimension)");
+    if (!h->srun_ready) {
+        for (auto k : {&sr_unrolled_tile_kernel<SR_SHARED>, &sr_unrolled_tile_kernel<SR_EACH>})
+            HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sr_lds_bytes(SRUN_R, SRUN_R)));
+        for (auto k : {&sr_unrolled_reverse_tile_kernel<SR_SHARED>, &sr_unrolled_reverse_tile_kernel<SR_EACH>})
+            HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sr_lds_bytes(SRUN_R, SRUN_R)));
+        h->srun_ready = true;
+    }
+    return BPLTV_OK;
+}
+
+// maxiter taped iterations on the dataset images, in the sum-of-regularisers state sets, with d_alpha (alpha_istride != 0: one
+// block per image); the six z_k components of every pixel into d_tape.
+int run_sr_unrolled_pdhg(bpltv_t* h, const bpltv_params& p, const SrUnrolledPlan& pl, double* d_tape, int* result_buf) {
+    h->has_per_image = false;
+    double* d_tab = nullptr;
+    int rc = get_table(h, p, &d_tab, 18.0);
+    if (rc) return rc;
+    const int M = h->M, N = h->N, O = h->O, T = pl.T;
+    const bool amap = (h->last_am == M && h->last_an == N) && !(M == 1 && N == 1);
+    const bool each = h->alpha_istride != 0;
+    h->st.tile_iters = T; h->st.tiles = pl.nTi * pl.nTj * O; h->st.region_i = SRUN_R; h->st.region_j = SRUN_R; h->st.pdhg_variant = 0;
+    void (*kern)(SrUnrolledArgs) = each ? &sr_unrolled_tile_kernel<SR_EACH> : &sr_unrolled_tile_kernel<SR_SHARED>;
+    ChainSolve j;
+    j.model = MODEL_SRUN; j.nplanes = 7; j.state0 = h->d_sr[0];
+    j.nimg = O; j.niter = p.maxiter; j.T = T;
+    j.chains = plan_chains(p.reserved[1], h->st.tiles, h->ncu, O, 2);   // at most two (image groups on two streams)
+    j.serial = (p.reserved[2] & 1) != 0; j.helper_thread = !(p.reserved[2] & 8);
+    j.bytes_per_px_iter = amap ? 192.0 : 168.0;   // read x, 6 y, f (+ 3 alpha), write x, 6 y and the 6 z
+    j.key = GraphKey{p.maxiter, T, 0, h->last_am, h->last_an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_tape, (const void*)d_tab, 0,
+                     (const void*)h->d_alpha, h->alpha_istride, 0};
+    j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
+        int step = stagger ? T / 2 : T;
+        for (int it = it0; it < it1; it += step, step = T) {
+            const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
+            SrUnrolledArgs a;
+            for (int c = 0; c < 7; ++c) { a.in[c] = h->d_sr[cur][c]; a.out[c] = h->d_sr[nxt][c]; }
+            a.f = h->d_f; a.alpha = h->d_alpha; a.tab = d_tab; a.tape = d_tape; a.plane = h->tot;
+            a.am = h->last_am; a.an = h->last_an; a.astride = h->alpha_istride;
+            a.it0 = it; a.nit = std::min(step, it1 - it);
+            a.M = M; a.N = N; a.halo = 2 * T; a.first = (it == 0) ? 1 : 0; a.img0 = lo;
+            hipLaunchKernelGGL(kern, dim3(pl.nTi, pl.nTj, hi - lo), dim3(SRUN_R * SRUN_R), sr_lds_bytes(SRUN_R, SRUN_R), st, a);
+            cur = nxt;
+        }
+        return cur;
+    };
+    return run_chains(h, p, j, result_buf);
+}
+
+// bpltv_sumregs_unrolled_denoise(_each)(_device) on a single-device handle: unrolled_denoise_common for the three-dual model.
+// d_tape_user: the caller's tape, or nullptr for the handle's own, which grows here -- the new buffer is allocated before
+// anything changes and installed only once the parameter is accepted.  The solve is committed like bpltv_sumregs_denoise's.
+int sr_unrolled_denoise_common(bpltv_t* h, const double* alpha, bool dev, int am, int an, const bpltv_params* pp, double* d_tape_user,
+                               double* u_out, bool each) {
+    const char* who = each ? (dev ? "bpltv_sumregs_unrolled_denoise_each_device" : "bpltv_sumregs_unrolled_denoise_each")
+                           : (dev ? "bpltv_sumregs_unrolled_denoise_device" : "bpltv_sumregs_unrolled_denoise");
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: bpltv_set_data has not been called", who);
+    const bpltv_params p = resolve(pp, true);
+    if (int prc = unrolled_check_params(h, p, who)) return prc;
+    SrUnrolledPlan pl;
+    if (int prc = sr_unrolled_plan(h, p, (SRUN_R - 1) / 4, &pl)) return prc;
+    if (int arc = sr_alloc(h)) return arc;
+    const size_t need = (size_t)6 * p.maxiter * h->tot;
+    double* grown = nullptr;
+    if (!d_tape_user && h->srtape_cap < need) {
+        const hipError_t e = hipMalloc((void**)&grown, need * sizeof(double));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return set_err(h, e == hipErrorOutOfMemory ? BPLTV_E_NOMEM : BPLTV_E_HIP, "%s: hipMalloc of the tape (%.1f MB) failed: %s", who,
+                           need * sizeof(double) / 1e6, hipGetErrorString(e));
+        }
+    }
+    bpltv_params q = p;   // the planner's knobs and the forward variant mean nothing here: upload_alpha's precheck sees the defaults
+    q.tile_iters = 0; q.reserved[0] = 0; q.reserved[1] = 0; q.reserved[2] = 0;
+    int rc = upload_alpha(h, alpha, dev, am, an, PRE_SR, each ? h->O : 1, &q);
+    if (rc) {
+        if (grown) (void)hipFree(grown);
+        return rc;
+    }
+    if (grown) {
+        if (h->d_srtape) (void)hipFree(h->d_srtape);
+        h->d_srtape = grown;
+        h->srtape_cap = need;
+    }
+    if (!d_tape_user) h->srtape_valid = false;   // about to be overwritten
+    int buf = 0;
+    rc = run_sr_unrolled_pdhg(h, p, pl, d_tape_user ? d_tape_user : h->d_srtape, &buf);
+    if (rc) return rc;
+    h->sr_result_buf = buf;
+    h->sr_has_result = true;
+    h->last_is_sr = true;
+    h->last_weighted = false;
+    if (!d_tape_user) {
+        h->srtape_valid = true;
+        h->srtape_maxiter = p.maxiter; h->srtape_am = am; h->srtape_an = an; h->srtape_accel = p.accel ? 1 : 0; h->srtape_each = each;
+        h->srtape_tau0 = p.tau0; h->srtape_sigma0 = p.sigma0; h->srtape_opnorm = p.opnorm;
+    }
+    if (u_out) {
+        HIPCHK(h, hipMemcpyAsync(u_out, h->d_sr[buf][0], h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+    }
+    h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
+// bpltv_sumregs_unrolled_vjp(_each)(_device) on a single-device handle: unrolled_vjp_common for the three-dual model.  d_gu and
+// the outputs live in HBM, alpha (3*am*an doubles, or O such blocks: each) on the host or (dev) in HBM; d_tape_user or the
+// handle's sum-of-regularisers tape.  The parameter is staged apart (stage_param) and the sweep runs in d_srunr, so the last
+// solve stays untouched; of the statistics only adjoint_ms and adjoint_method change.  d_grad_alpha: slice r of the shared form
+// is the sum of ga_r over the images in image order, then per patch or over everything; each: O blocks, block k image k's own.
+int sr_unrolled_vjp_common(bpltv_t* h, const double* d_tape_user, const double* alpha, bool dev, int am, int an, const bpltv_params* pp,
+                           const double* d_gu, double* d_grad_f, double* d_grad_alpha, bool each) {
+    const char* who = each ? "sumregs_unrolled_vjp_each" : "sumregs_unrolled_vjp";
+    if (!alpha || !d_gu) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
+    if (!d_grad_f && !d_grad_alpha) return set_err(h, BPLTV_E_ARG, "%s: both outputs are NULL", who);
+    const bpltv_params p0 = resolve(pp, true);
+    if (int prc = unrolled_check_params(h, p0, who)) return prc;
+    if (!d_tape_user) {
+        if (!h->srtape_valid)
+            return set_err(h, BPLTV_E_NODATA, "%s: the handle holds no sum-of-regularisers tape (bpltv_sumregs_unrolled_denoise has not run)", who);
+        if (h->srtape_maxiter != p0.maxiter || h->srtape_am != am || h->srtape_an != an || h->srtape_accel != (p0.accel ? 1 : 0) ||
+            h->srtape_tau0 != p0.tau0 || h->srtape_sigma0 != p0.sigma0 || h->srtape_opnorm != p0.opnorm)
+            return set_err(h, BPLTV_E_ARG, "%s: the handle's tape was recorded with maxiter = %d, a %dx%dx3 parameter and other steps than this call's (%d, %dx%dx3)",
+                           who, h->srtape_maxiter, h->srtape_am, h->srtape_an, p0.maxiter, am, an);
+        if (h->srtape_each != each)
+            return set_err(h, BPLTV_E_ARG, "%s: the handle's tape was recorded with %s", who,
+                           h->srtape_each ? "one parameter block per image (bpltv_sumregs_unrolled_denoise_each)"
+                                          : "one shared parameter (bpltv_sumregs_unrolled_denoise)");
+    }
+    SrUnrolledPlan pl;
+    if (int prc = sr_unrolled_plan(h, p0, SRUN_REV_T, &pl)) return prc;
+    const size_t tot = h->tot, npx = h->npx;
+    if (!h->d_srunr)
+        if (int arc = alloc_all(h, {{(void**)&h->d_srunr, 19 * tot * sizeof(double)}}, "sum-of-regularisers reverse sweep")) return arc;
+    bpltv_params p;
+    GradCtx g;
+    if (int rc = stage_param(h, who, alpha, dev, am, an, 3, each, 0, pp ? pp : &p0, nullptr, 1, {{d_gu, tot, "cotangent gu"}}, &p, &g)) return rc;
+    const int M = h->M, N = h->N, O = h->O, T = pl.T, K = p.maxiter, sl = am * an;
+    const bool amap = am == M && an == N && !(M == 1 && N == 1);
+    if (d_grad_alpha && !amap && !each)
+        if (int rc = ensure(h, &h->d_red, &h->red_cap, (size_t)3 * sl * O)) return rc;
+    h->has_per_image = false;
+    double* d_tab = nullptr;
+    if (int rc = get_table(h, p, &d_tab, 18.0)) return rc;
+    const double* d_tape = d_tape_user ? d_tape_user : h->d_srtape;
+    double* S[2][7];
+    for (int s = 0; s < 2; ++s)
+        for (int c = 0; c < 7; ++c) S[s][c] = h->d_srunr + (size_t)(7 * s + c) * tot;
+    double *d_gf = h->d_srunr + 14 * tot, *d_ga = h->d_srunr + 15 * tot, *d_g0 = h->d_srunr + 18 * tot;
+    void (*kern)(SrUnrolledRevArgs) = each ? &sr_unrolled_reverse_tile_kernel<SR_EACH> : &sr_unrolled_reverse_tile_kernel<SR_SHARED>;
+    const bpltv_stats_t kept = h->st;
+    HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
+    HIPCHK(h, hipMemcpyAsync(d_g0, d_gu, tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    ChainSolve j;
+    j.model = MODEL_SRUN; j.nplanes = 7; j.state0 = S[0];
+    j.nimg = O; j.niter = K; j.T = T;
+    const int tiles = pl.nTi * pl.nTj * O;
+    j.chains = plan_chains(p.reserved[1], tiles, h->ncu, O, 2);
+    j.serial = (p.reserved[2] & 1) != 0; j.helper_thread = !(p.reserved[2] & 8);
+    j.bytes_per_px_iter = 0.0;   // (the driver's solve statistics are not this call's: `kept` goes back below)
+    j.key = GraphKey{K, T, 1, am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_tape, (const void*)d_tab, 0, (const void*)g.alpha, g.astride, 0};
+    j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
+        int step = stagger ? T / 2 : T;
+        for (int it = it0; it < it1; it += step, step = T) {   // `it` counts reverse steps: step r undoes iteration K - 1 - r
+            const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
+            SrUnrolledRevArgs a;
+            for (int c = 0; c < 7; ++c) { a.in[c] = S[cur][c]; a.out[c] = S[nxt][c]; }
+            if (it == 0) a.in[0] = d_g0;
+            a.gf = d_gf; a.ga = d_ga; a.tape = d_tape; a.alpha = g.alpha; a.tab = d_tab; a.plane = tot;
+            a.am = am; a.an = an; a.astride = g.astride;
+            a.khi = K - 1 - it; a.nit = std::min(step, it1 - it);
+            a.M = M; a.N = N; a.halo = 2 * T; a.first = (it == 0) ? 1 : 0; a.img0 = lo;
+            hipLaunchKernelGGL(kern, dim3(pl.nTi, pl.nTj, hi - lo), dim3(SRUN_R * SRUN_R), sr_lds_bytes(SRUN_R, SRUN_R), st, a);
+            cur = nxt;
+        }
+        return cur;
+    };
+    int buf = 0;
+    const int rc = run_chains(h, p, j, &buf);
+    h->st = kept;
+    if (rc) return rc;
+    if (d_grad_f)
+        hipLaunchKernelGGL(unrolled_gradf_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, d_gf, S[buf][0], tot, d_grad_f);
+    for (int r = 0; r < 3 && d_grad_alpha; ++r) {   // slice by slice, the reductions of unrolled_vjp_common (fixed order, no atomics)
+        const double* ga_r = d_ga + (size_t)r * tot;
+        if (each && amap) {          // block k = [3][M*N] of image k: the plane of the slice, image by image
+            HIPCHK(h, hipMemcpy2DAsync(d_grad_alpha + (size_t)r * npx, 3 * npx * sizeof(double), ga_r, npx * sizeof(double), npx * sizeof(double), O,
+                                       hipMemcpyDeviceToDevice, h->stream));
+        } else if (each) {           // image k's patch sums into block k, slice r
+            hipLaunchKernelGGL(patch_sum_kernel, dim3(sl, O), dim3(256), 0, h->stream, ga_r, M, N, O, am, an, 1, 3 * sl, d_grad_alpha + (size_t)r * sl);
+        } else if (amap) {           // the per-pixel sums over the images, in image order
+            hipLaunchKernelGGL(map_sum_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, ga_r, npx, O, d_grad_alpha + (size_t)r * npx);
+        } else {                     // per image and patch, then over the images in image order
+            double* red = h->d_red + (size_t)r * sl * O;
+            hipLaunchKernelGGL(patch_sum_kernel, dim3(sl, O), dim3(256), 0, h->stream, ga_r, M, N, O, am, an, O, 1, red);
+            hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, h->stream, red, O, sl, 1.0, d_grad_alpha + (size_t)r * sl, (double*)nullptr);
+        }
+    }
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
+    h->st.adjoint_ms = ms;
+    h->st.adjoint_method = 10;
+    return BPLTV_OK;
+}
+
 // bpltv_unrolled_jvp(_device) and bpltv_unrolled_gauss_newton on a single-device handle (unrolled_jvp_kernels.hpp, DESIGN.md
 // section 4.7): ndir tangent sweeps, one after the other, each the same launch sequence (direction d of a call is bitwise the
 // call with that direction alone).  The tangents d_df / d_dalpha (either may be nullptr: a zero tangent) and d_du live in HBM,
@@ -3953,7 +4193,7 @@ int bpltv_destroy(bpltv_t* h) {
     if (h->f32_sweep_alpha) (void)hipFree(h->f32_sweep_alpha);
     void* ptrs[] = {h->d_ubar, h->d_f, h->d_alpha, h->d_sweep_alpha, h->d_partial, h->d_red, h->d_perimg, h->d_scalar, h->d_coef,
                     h->d_band4, h->d_bcr, h->d_L, h->d_invF, h->d_invB, h->d_L1, h->d_dump, h->d_Lm, h->d_spill, h->d_p, h->d_r, h->d_gpix, h->d_resn, h->d_fail, h->d_u2, h->d_ubar2,
-                    h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres, h->d_w, h->d_wst, h->d_tape, h->d_unr, h->d_ujv, h->d_wtape, h->d_unr_gw};
+                    h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres, h->d_w, h->d_wst, h->d_tape, h->d_unr, h->d_ujv, h->d_wtape, h->d_unr_gw, h->d_srtape, h->d_srunr};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (int s = 0; s < 2; ++s)
@@ -4235,9 +4475,10 @@ int bpltv_unrolled_denoise_each_device(bpltv_t* h, const double* d_alphas, int a
     return unrolled_denoise_common(h, d_alphas, true, am, an, pp, d_tape, nullptr, true);
 }
 
-// bpltv_unrolled_vjp and bpltv_unrolled_vjp_each on a single-device handle: the host arrays staged around unrolled_vjp_common
+// bpltv_unrolled_vjp and bpltv_unrolled_vjp_each on a single-device handle: the host arrays staged around unrolled_vjp_common;
+// slices = 3: bpltv_sumregs_unrolled_vjp(_each) around sr_unrolled_vjp_common
 static int unrolled_vjp_host(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, const double* gu,
-                             double* grad_f_out, double* grad_alpha_out, bool each) {
+                             double* grad_f_out, double* grad_alpha_out, bool each, int slices = 1) {
     if (!gu || !alpha) return set_err(h, BPLTV_E_ARG, "unrolled_vjp: null pointer");
     if (!grad_f_out && !grad_alpha_out) return set_err(h, BPLTV_E_ARG, "unrolled_vjp: both outputs are NULL");
     if (am < 1 || an < 1 || am > h->M || an > h->N)
@@ -4250,16 +4491,17 @@ static int unrolled_vjp_host(bpltv_t* h, const double* alpha, int am, int an, co
     }
     if (grad_f_out && !h->d_gf2) HIPCHK(h, hipMalloc((void**)&h->d_gf2, h->tot * sizeof(double)));
     HIPCHK(h, hipMemcpyAsync(h->d_ubar2, gu, h->tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    const size_t P = (size_t)am * an * (each ? h->O : 1);
+    const size_t P = (size_t)slices * am * an * (each ? h->O : 1);
     int rc = ensure(h, &h->d_vjp, &h->vjp_cap, 4 + 2 * P);
     if (rc) return rc;
     double* d_ga = grad_alpha_out ? h->d_vjp + 4 + P : nullptr;
-    rc = unrolled_vjp_common(h, nullptr, alpha, false, am, an, pp, h->d_ubar2, grad_f_out ? h->d_gf2 : nullptr, d_ga, each);
+    rc = slices == 3 ? sr_unrolled_vjp_common(h, nullptr, alpha, false, am, an, pp, h->d_ubar2, grad_f_out ? h->d_gf2 : nullptr, d_ga, each)
+                     : unrolled_vjp_common(h, nullptr, alpha, false, am, an, pp, h->d_ubar2, grad_f_out ? h->d_gf2 : nullptr, d_ga, each);
     if (rc) return rc;
     if (grad_f_out) HIPCHK(h, hipMemcpyAsync(grad_f_out, h->d_gf2, h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (grad_alpha_out) HIPCHK(h, hipMemcpyAsync(grad_alpha_out, d_ga, sizeof(double) * P, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    h->st.total_ms = wt.ms();
+    if (slices != 3) h->st.total_ms = wt.ms();   // (the sum-of-regularisers form changes adjoint_ms and adjoint_method only)
     return BPLTV_OK;
 }
 
@@ -4307,6 +4549,64 @@ int bpltv_unrolled_vjp_device(bpltv_t* h, const double* d_tape, const double* d_
     if (rc) return rc;
     h->st.total_ms = wt.ms();
     return BPLTV_OK;
+}
+
+// The sum-of-regularisers forms (sumregs_unrolled_kernels.hpp): one pair of common functions behind the nine entry points
+int bpltv_sumregs_unrolled_tape_doubles(bpltv_t* h, const bpltv_params* pp, unsigned long long* n_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (!n_out) return set_err(h, BPLTV_E_ARG, "bpltv_sumregs_unrolled_tape_doubles: null pointer");
+    const bpltv_params p = resolve(pp, true);
+    if (p.maxiter < 1) return set_err(h, BPLTV_E_ARG, "bpltv_sumregs_unrolled_tape_doubles: maxiter = %d (at least one iteration)", p.maxiter);
+    *n_out = 6ull * (unsigned long long)p.maxiter * (unsigned long long)h->M * h->N * h->O;
+    return BPLTV_OK;
+}
+
+static int sr_unrolled_denoise_entry(bpltv_t* h, const char* what, const double* alpha, bool dev, int am, int an, const bpltv_params* pp,
+                                     double* d_tape, double* u_out, bool each) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, what, true, [&](bpltv_t* c) { return sr_unrolled_denoise_entry(c, what, alpha, dev, am, an, pp, d_tape, u_out, each); }, kSrUnrolled);
+    return sr_unrolled_denoise_common(h, alpha, dev, am, an, pp, d_tape, u_out, each);
+}
+
+int bpltv_sumregs_unrolled_denoise(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, double* u_out) {
+    return sr_unrolled_denoise_entry(h, "bpltv_sumregs_unrolled_denoise", alpha, false, am, an, pp, nullptr, u_out, false);
+}
+int bpltv_sumregs_unrolled_denoise_device(bpltv_t* h, const double* d_alpha, int am, int an, const bpltv_params* pp, double* d_tape) {
+    return sr_unrolled_denoise_entry(h, "bpltv_sumregs_unrolled_denoise_device", d_alpha, true, am, an, pp, d_tape, nullptr, false);
+}
+int bpltv_sumregs_unrolled_denoise_each(bpltv_t* h, const double* alphas, int am, int an, const bpltv_params* pp, double* u_out) {
+    return sr_unrolled_denoise_entry(h, "bpltv_sumregs_unrolled_denoise_each", alphas, false, am, an, pp, nullptr, u_out, true);
+}
+int bpltv_sumregs_unrolled_denoise_each_device(bpltv_t* h, const double* d_alphas, int am, int an, const bpltv_params* pp, double* d_tape) {
+    return sr_unrolled_denoise_entry(h, "bpltv_sumregs_unrolled_denoise_each_device", d_alphas, true, am, an, pp, d_tape, nullptr, true);
+}
+
+static int sr_unrolled_vjp_entry(bpltv_t* h, const char* what, bool dev, const double* d_tape, const double* alpha, int am, int an,
+                                 const bpltv_params* pp, const double* gu, double* grad_f, double* grad_alpha, bool each) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, what, false, [&](bpltv_t* c) { return sr_unrolled_vjp_entry(c, what, dev, d_tape, alpha, am, an, pp, gu, grad_f, grad_alpha, each); }, kSrUnrolled);
+    if (!dev) return unrolled_vjp_host(h, alpha, am, an, pp, gu, grad_f, grad_alpha, each, 3);
+    HIPCHK(h, hipSetDevice(h->device));
+    return sr_unrolled_vjp_common(h, d_tape, alpha, true, am, an, pp, gu, grad_f, grad_alpha, each);
+}
+
+int bpltv_sumregs_unrolled_vjp(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, const double* gu,
+                               double* grad_f_out, double* grad_alpha_out) {
+    return sr_unrolled_vjp_entry(h, "bpltv_sumregs_unrolled_vjp", false, nullptr, alpha, am, an, pp, gu, grad_f_out, grad_alpha_out, false);
+}
+int bpltv_sumregs_unrolled_vjp_device(bpltv_t* h, const double* d_tape, const double* d_alpha, int am, int an, const bpltv_params* pp,
+                                      const double* d_gu, double* d_grad_f, double* d_grad_alpha) {
+    return sr_unrolled_vjp_entry(h, "bpltv_sumregs_unrolled_vjp_device", true, d_tape, d_alpha, am, an, pp, d_gu, d_grad_f, d_grad_alpha, false);
+}
+int bpltv_sumregs_unrolled_vjp_each(bpltv_t* h, const double* alphas, int am, int an, const bpltv_params* pp, const double* gu,
+                                    double* grad_f_out, double* grad_alphas_out) {
+    return sr_unrolled_vjp_entry(h, "bpltv_sumregs_unrolled_vjp_each", false, nullptr, alphas, am, an, pp, gu, grad_f_out, grad_alphas_out, true);
+}
+int bpltv_sumregs_unrolled_vjp_each_device(bpltv_t* h, const double* d_tape, const double* d_alphas, int am, int an, const bpltv_params* pp,
+                                           const double* d_gu, double* d_grad_f, double* d_grad_alphas) {
+    return sr_unrolled_vjp_entry(h, "bpltv_sumregs_unrolled_vjp_each_device", true, d_tape, d_alphas, am, an, pp, d_gu, d_grad_f, d_grad_alphas, true);
 }
 
 int bpltv_weighted_unrolled_tape_doubles(bpltv_t* h, const bpltv_params* pp, unsigned long long* n_out) {

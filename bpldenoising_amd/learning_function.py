@@ -849,6 +849,104 @@ class TVSolver:
                                                             C.c_void_p(df_ptr or None), C.c_void_p(dalphas_ptr or None),
                                                             C.c_void_p(du_ptr)))
 
+    # -- reverse mode through the sum-of-regularisers iterations (bpltv_sumregs_unrolled_*) ------------------------
+    def sumregs_unrolled_tape_doubles(self, **kw):
+        """Doubles of the tape a sum-of-regularisers unrolled solve with these params records: 6 * maxiter * M*N*O."""
+        p = self.params(_sumregs=True, **kw)
+        n = C.c_ulonglong(0)
+        self._check(self._lib.bpltv_sumregs_unrolled_tape_doubles(self._h, C.byref(p), C.byref(n)))
+        return int(n.value)
+
+    def sumregs_unrolled_denoise(self, x, fetch=True, **kw):
+        """sumregs_denoise(x) with rho = 0 -- the same u bit for bit -- that also records the tape of the iterations in
+        the handle, for sumregs_unrolled_vjp with the same x and params (bpltv_sumregs_unrolled_denoise)."""
+        a, am, an, _ = _sr_alpha_arg(x)
+        p = self.params(_sumregs=True, **kw)
+        u = np.empty((self.O, self.N, self.M)) if fetch else None
+        self._check(self._lib.bpltv_sumregs_unrolled_denoise(self._h, _ptr(a), am, an, C.byref(p),
+                                                             _ptr(u) if fetch else None))
+        return u
+
+    def sumregs_unrolled_denoise_device(self, alpha_ptr, am=1, an=1, tape_ptr=None, **kw):
+        """bpltv_sumregs_unrolled_denoise_device: the parameter (3*am*an doubles) resident in HBM, the result left there
+        (u_device_ptr / copy_u_device); tape_ptr: a caller-owned HBM buffer of sumregs_unrolled_tape_doubles(**kw)
+        doubles, or None / 0 for the handle's own tape."""
+        p = self.params(_sumregs=True, **kw)
+        self._check(self._lib.bpltv_sumregs_unrolled_denoise_device(self._h, C.c_void_p(alpha_ptr), int(am), int(an),
+                                                                    C.byref(p), C.c_void_p(tape_ptr or None)))
+
+    def sumregs_unrolled_vjp(self, x, gu, want_f=True, want_alpha=True, **kw):
+        """Vector-Jacobian product of the maxiter-step map u = sumregs_unrolled_denoise(x) for the cotangent gu = dL/du,
+        by a reverse sweep over the handle's tape (bpltv_sumregs_unrolled_vjp): (grad_f, grad_x).  x and the params must
+        be those of the solve.  gu: (O, N, M); grad_f has its shape (None unless want_f), grad_x the shape of x (None
+        unless want_alpha)."""
+        if not (want_f or want_alpha):
+            raise ValueError("sumregs_unrolled_vjp: want_f and want_alpha are both False")
+        a, am, an, vec = _sr_alpha_arg(x)
+        p = self.params(_sumregs=True, **kw)
+        gu = self._batch(gu, "gu")
+        gf = np.empty((self.O, self.N, self.M)) if want_f else None
+        ga = np.empty(3 * am * an) if want_alpha else None
+        self._check(self._lib.bpltv_sumregs_unrolled_vjp(self._h, _ptr(a), am, an, C.byref(p), _ptr(gu),
+                                                         _ptr(gf) if want_f else None,
+                                                         _ptr(ga) if want_alpha else None))
+        if ga is not None and not vec:
+            ga = ga.reshape(3, an, am)
+        return gf, ga
+
+    def sumregs_unrolled_vjp_device(self, tape_ptr, alpha_ptr, am, an, gu_ptr, grad_f_ptr, grad_alpha_ptr, **kw):
+        """bpltv_sumregs_unrolled_vjp_device: the tape (None / 0: the handle's own), the parameter, gu and the outputs
+        resident in HBM (raw device pointers); either output pointer may be 0 / None, not both."""
+        p = self.params(_sumregs=True, **kw)
+        self._check(self._lib.bpltv_sumregs_unrolled_vjp_device(self._h, C.c_void_p(tape_ptr or None),
+                                                                C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p),
+                                                                C.c_void_p(gu_ptr), C.c_void_p(grad_f_ptr or None),
+                                                                C.c_void_p(grad_alpha_ptr or None)))
+
+    def sumregs_unrolled_denoise_each(self, alphas, fetch=True, **kw):
+        """sumregs_unrolled_denoise with image k's own three weights alphas[k] (bpltv_sumregs_unrolled_denoise_each):
+        sumregs_denoise_each's u bit for bit, and the handle's tape, recorded per image."""
+        a, am, an = self._sr_each_arg(alphas)
+        p = self.params(_sumregs=True, **kw)
+        u = np.empty((self.O, self.N, self.M)) if fetch else None
+        self._check(self._lib.bpltv_sumregs_unrolled_denoise_each(self._h, _ptr(a), am, an, C.byref(p),
+                                                                  _ptr(u) if fetch else None))
+        return u
+
+    def sumregs_unrolled_denoise_each_device(self, alphas_ptr, am=1, an=1, tape_ptr=None, **kw):
+        """bpltv_sumregs_unrolled_denoise_each_device: O parameter blocks (a C-contiguous (O, 3, an, am) array) resident
+        in HBM, the result left there; tape_ptr as in sumregs_unrolled_denoise_device."""
+        p = self.params(_sumregs=True, **kw)
+        self._check(self._lib.bpltv_sumregs_unrolled_denoise_each_device(self._h, C.c_void_p(alphas_ptr), int(am),
+                                                                         int(an), C.byref(p),
+                                                                         C.c_void_p(tape_ptr or None)))
+
+    def sumregs_unrolled_vjp_each(self, alphas, gu, want_f=True, want_alpha=True, **kw):
+        """sumregs_unrolled_vjp with image k's own block alphas[k], over the handle's per-image tape
+        (bpltv_sumregs_unrolled_vjp_each): (grad_f, grad_alphas).  grad_alphas has the shape of alphas; grad_alphas[k]
+        is image k's term alone, not summed over the images."""
+        if not (want_f or want_alpha):
+            raise ValueError("sumregs_unrolled_vjp_each: want_f and want_alpha are both False")
+        a, am, an = self._sr_each_arg(alphas)
+        p = self.params(_sumregs=True, **kw)
+        gu = self._batch(gu, "gu")
+        gf = np.empty((self.O, self.N, self.M)) if want_f else None
+        ga = np.empty(a.shape) if want_alpha else None
+        self._check(self._lib.bpltv_sumregs_unrolled_vjp_each(self._h, _ptr(a), am, an, C.byref(p), _ptr(gu),
+                                                              _ptr(gf) if want_f else None,
+                                                              _ptr(ga) if want_alpha else None))
+        return gf, ga
+
+    def sumregs_unrolled_vjp_each_device(self, tape_ptr, alphas_ptr, am, an, gu_ptr, grad_f_ptr, grad_alphas_ptr, **kw):
+        """bpltv_sumregs_unrolled_vjp_each_device: as sumregs_unrolled_vjp_device with O parameter blocks and their O
+        gradients (O*3*am*an doubles each) resident in HBM; either output pointer may be 0 / None, not both."""
+        p = self.params(_sumregs=True, **kw)
+        self._check(self._lib.bpltv_sumregs_unrolled_vjp_each_device(self._h, C.c_void_p(tape_ptr or None),
+                                                                     C.c_void_p(alphas_ptr), int(am), int(an),
+                                                                     C.byref(p), C.c_void_p(gu_ptr),
+                                                                     C.c_void_p(grad_f_ptr or None),
+                                                                     C.c_void_p(grad_alphas_ptr or None)))
+
     def sweep(self, alphas, fetch_u=False, **kw):
         """costs[k] = 0.5*||denoise(f, alphas[k]) - ubar||^2 for K parameters in one batched solve
         (generate_cost / generate_2d_cost, /root/reference/src/BPLDenoising.jl:92-111,136-158).

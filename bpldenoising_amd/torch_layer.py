@@ -76,6 +76,15 @@ the forward pass allocates as a torch tensor), which scales nothing with 1/sqrt(
 w.grad as needs_input_grad asks, so alpha, f and a fidelity map can be trained through a masked (inpainting) solve; at
 w = 0, w.grad is the one-sided derivative.  The step table (gamma = min w) is held fixed.  No jvp.
 
+    u = sumregs_denoise_unrolled(f, alpha, maxiter=50)           # ... of the sum-of-regularisers model (bpltv_sumregs_unrolled_*)
+    u = sumregs_denoise_unrolled_each(f, alpha, maxiter=30)      # ... with three weights per image
+
+f and alpha as for sumregs_denoise / sumregs_denoise_each, the same u bit for bit; backward is the derivative of the
+maxiter-step map (one bpltv_sumregs_unrolled_vjp(_each)_device call over a tape of 6 * maxiter * B*H*W doubles the forward
+pass allocates as a torch tensor): no active-set threshold, no factorisation, zeros in alpha allowed.
+SumRegsDenoiseUnrolled(alpha, maxiter=...) is the module with a learnable parameter.  No jvp: forward_mode=True raises a
+ValueError that names the implicit sumregs_denoise(..., forward_mode=True).
+
 Streams: the library runs its kernels on its own HIP streams and blocks until they are done.  Every call below first
 synchronises the tensors' current torch stream, so that the library reads inputs torch has finished writing; its
 outputs are complete when the call returns.
@@ -799,3 +808,85 @@ class TVDenoiseUnrolled(torch.nn.Module):
 
     def forward(self, f):
         return tv_denoise_unrolled(f, self.alpha, forward_mode=self.forward_mode, **self.solver_kw)
+
+
+class SumRegsDenoiseUnrolledFunction(torch.autograd.Function):
+    """autograd.Function of sumregs_denoise_unrolled and (each) sumregs_denoise_unrolled_each (below);
+    apply(f, alpha, each, solver_kw).  No jvp."""
+
+    @staticmethod
+    def forward(ctx, f, alpha, each, solver_kw):
+        if each:
+            O, N, M, am, an = _check_args_each(f, alpha, slices=3, name="sumregs_denoise_unrolled_each")
+        else:
+            O, N, M, am, an = _check_args(f, alpha, slices=3)
+        index = f.device.index if f.device.index is not None else torch.cuda.current_device()
+        s = _solver(index, M, N, O)
+        fc = f.detach().contiguous()
+        ac = alpha.detach().contiguous()
+        u = torch.empty_like(fc)
+        # the tape is this call's own: a second forward pass on the handle before backward does not overwrite it
+        tape = torch.empty(s.sumregs_unrolled_tape_doubles(**solver_kw), dtype=torch.float64, device=f.device)
+        _sync(f.device)
+        s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
+        solve = s.sumregs_unrolled_denoise_each_device if each else s.sumregs_unrolled_denoise_device
+        solve(ac.data_ptr(), am, an, tape_ptr=tape.data_ptr(), **solver_kw)
+        s.copy_u_device(u.data_ptr())
+        ctx.save_for_backward(tape, ac)
+        ctx.solver, ctx.am, ctx.an, ctx.each, ctx.solver_kw = s, am, an, bool(each), dict(solver_kw)
+        return u
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gu):
+        need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_f or need_a):
+            return None, None, None, None
+        tape, alpha = ctx.saved_tensors
+        gu = gu.to(dtype=torch.float64).contiguous()
+        gf = torch.empty_like(gu) if need_f else None
+        ga = torch.empty_like(alpha) if need_a else None
+        _sync(gu.device)
+        vjp = ctx.solver.sumregs_unrolled_vjp_each_device if ctx.each else ctx.solver.sumregs_unrolled_vjp_device
+        vjp(tape.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(), gf.data_ptr() if need_f else None,
+            ga.data_ptr() if need_a else None, **ctx.solver_kw)
+        return gf, ga, None, None
+
+
+def _no_forward_mode(name, forward_mode):
+    if forward_mode:
+        raise ValueError("%s: forward mode through the sum-of-regularisers iterations does not exist; the implicit "
+                         "sumregs_denoise(..., forward_mode=True) carries a jvp" % name)
+
+
+def sumregs_denoise_unrolled(f, alpha, maxiter=50, forward_mode=False, **solver_kw):
+    """u = sumregs_denoise(f, alpha) by exactly maxiter PDHG iterations (TVSolver.sumregs_unrolled_denoise_device: the same
+    u bit for bit), differentiable in f and the three weights THROUGH the iterations: backward is the exact derivative of
+    the maxiter-step map (one sumregs_unrolled_vjp_device call over a tape of 6 * maxiter * B*H*W doubles the forward pass
+    allocates as a torch tensor), with no active-set threshold and no factorisation; zeros in alpha are legal.  alpha:
+    (3,), (3, pH, pW) or (3, H, W) on f's device.  solver_kw: the solver parameters of TVSolver.params (rho, init and
+    order must stay 0).  forward_mode=True raises: use the implicit sumregs_denoise(..., forward_mode=True)."""
+    _no_forward_mode("sumregs_denoise_unrolled", forward_mode)
+    return SumRegsDenoiseUnrolledFunction.apply(f, alpha, False, dict(solver_kw, maxiter=maxiter))
+
+
+def sumregs_denoise_unrolled_each(f, alpha, maxiter=30, forward_mode=False, **solver_kw):
+    """sumregs_denoise_unrolled for a batch f of shape (B, H, W) with three weights per image: alpha (B, 3),
+    (B, 3, pH, pW) or (B, 3, H, W) -- sumregs_denoise_each's u bit for bit; alpha.grad[k] is image k's term alone.  What
+    a network that predicts the weights per sample in front of a short solve needs."""
+    _no_forward_mode("sumregs_denoise_unrolled_each", forward_mode)
+    return SumRegsDenoiseUnrolledFunction.apply(f, alpha, True, dict(solver_kw, maxiter=maxiter))
+
+
+class SumRegsDenoiseUnrolled(torch.nn.Module):
+    """SumRegsDenoise with sumregs_denoise_unrolled's backward: three learnable weights, patch parameters or pixel maps
+    behind a fixed number of iterations (solver_kw: maxiter, ...).  Move it to the device of its inputs with .to(device)."""
+
+    def __init__(self, alpha, forward_mode=False, **solver_kw):
+        super().__init__()
+        _no_forward_mode("SumRegsDenoiseUnrolled", forward_mode)
+        self.alpha = torch.nn.Parameter(torch.as_tensor(alpha, dtype=torch.float64).clone())
+        self.solver_kw = dict(solver_kw)
+
+    def forward(self, f):
+        return sumregs_denoise_unrolled(f, self.alpha, **self.solver_kw)

@@ -135,7 +135,8 @@ typedef struct bpltv_stats {
                                   Cholesky, 6 nested-dissection LU (that row-scaled system, the default),
                                   7 reverse sweep over the taped iterations (bpltv_unrolled_vjp),
                                   8 tangent sweep through the iterations (bpltv_unrolled_jvp),
-                                  9 reverse sweep over the taped weighted iterations (bpltv_weighted_unrolled_vjp) */
+                                  9 reverse sweep over the taped weighted iterations (bpltv_weighted_unrolled_vjp),
+                                  10 reverse sweep over the taped sum-of-regularisers iterations (bpltv_sumregs_unrolled_vjp) */
     int reg_gradient_used;     /* 1 if the last evaluate took the gradient_reg branch             */
     int ngpus;                 /* distinct devices behind this handle (1 for bpltv_create)        */
     int shards;                /* image shards (= worker threads) behind this handle              */
@@ -510,6 +511,60 @@ int bpltv_unrolled_jvp_each(bpltv_t *h, const double *alphas, int am, int an, co
                             const double *df, const double *dalphas, double *du_out, double *u_out /* may be NULL */);
 int bpltv_unrolled_jvp_each_device(bpltv_t *h, const double *d_alphas, int am, int an, const bpltv_params *p, int ndir,
                                    const double *d_df, const double *d_dalphas, double *d_du, double *d_u /* may be NULL */);
+
+/* Reverse mode through the PDHG iterations of the sum-of-regularisers model: what bpltv_unrolled_* is
+ * to bpltv_denoise, for bpltv_sumregs_denoise -- the exact derivative of the maxiter-step map, with no active-set threshold, no
+ * factorisation and no condition on the parameter beyond >= 0, where bpltv_sumregs_vjp differentiates the minimiser.
+ *
+ * bpltv_sumregs_unrolled_denoise: alpha, am, an as bpltv_sumregs_denoise (3*am*an doubles, the three slices one after the
+ * other; finite and >= 0, checked on the host or on the device; zeros are legal, a whole slice of zeros included), BPLTV_E_NODATA
+ * without a dataset.  params (NULL: bpltv_sumregs_default_params): opnorm, tau0, sigma0, accel, maxiter, tile_iters, use_graph,
+ * reserved[1] and reserved[2] apply; rho, init and order must be 0 (BPLTV_E_UNSUPPORTED), maxiter < 1 is BPLTV_E_ARG,
+ * check_every and gap_tol are ignored (always maxiter iterations), and reserved[0], the forward variant, is ignored: there is
+ * one taped kernel.  u is bpltv_sumregs_denoise's bit for bit, for either of its variants.  The solve is a sum-of-regularisers
+ * solve and becomes the handle's last one: bpltv_u_device, bpltv_copy_u_device and bpltv_duality_gap behave as after
+ * bpltv_sumregs_denoise.  It also records the six dual components before their projection in every iteration: a tape of
+ * 6 * maxiter * M*N*O doubles (bpltv_sumregs_unrolled_tape_doubles; its layout is private).  stats: iterations, launches,
+ * tile_iters, tiles, pdhg_ms, total_ms as bpltv_sumregs_denoise; bytes_per_px_iter = 168 (192 with three maps);
+ * pdhg_variant = 0.  Every rejection comes before anything of the handle changes.
+ *
+ * The tape: d_tape is a caller-owned HBM buffer of bpltv_sumregs_unrolled_tape_doubles doubles; a NULL d_tape, and the host
+ * forms always, use a tape owned by the handle (allocated on demand, only grows, freed by bpltv_destroy; BPLTV_E_NOMEM, with the
+ * handle as it was, when it cannot be allocated).  It is a third tape beside those of bpltv_unrolled_denoise and
+ * bpltv_weighted_unrolled_denoise: none is accepted for another model's VJP and each survives the other models' solves.  The
+ * handle remembers maxiter, am, an, the step parameters and whether the tape was recorded per image; a VJP on the handle's tape
+ * returns BPLTV_E_NODATA when there is none and BPLTV_E_ARG on any mismatch (the shared form on a per-image tape, and the
+ * reverse, included).
+ *
+ * bpltv_sumregs_unrolled_vjp: for a cotangent gu = dL/du (M*N*O doubles, finite) grad_f_out = dL/df (M*N*O doubles) and
+ * grad_alpha_out = dL/dalpha (3*am*an doubles; every slice reduced as bpltv_unrolled_vjp reduces its parameter: over the images
+ * in image order, then over all pixels, each patch, or nothing for a map -- fixed order, no atomics).  Either output may be
+ * NULL, not both.  alpha and params must be the solve's.  f is not read.  The parameter is staged apart and the last solve
+ * stays untouched; of the statistics only adjoint_ms (the HIP-event time of the sweep) and adjoint_method = 10 change.  The
+ * results do not depend on tile_iters, on the launch chains, on use_graph, on the host or device form, or on whose tape it is.
+ *
+ * The _each forms take one block of 3*am*an doubles per image (bpltv_sumregs_denoise_each's layout) and have the contract of
+ * their shared twins; after the solve bpltv_duality_gap evaluates image k with its own block.  grad_alphas_out: O blocks, block
+ * k image k's own.  Image k's results are bitwise the one-image handle's with block k; with equal blocks, the blocks added in
+ * image order are the shared form's grad_alpha_out bit for bit, and grad_f is equal bitwise.
+ *
+ * No captured graph is shared with bpltv_sumregs_denoise, the TV, weighted or other unrolled calls.  Multi-device handles over
+ * more than one shard: BPLTV_E_UNSUPPORTED (all nine); one shard is forwarded.  dtype = 32 handles behave as
+ * bpltv_sumregs_denoise does on them; these calls always compute in Float64. */
+int bpltv_sumregs_unrolled_tape_doubles(bpltv_t *h, const bpltv_params *p, unsigned long long *n_out);   /* 6*maxiter*M*N*O */
+int bpltv_sumregs_unrolled_denoise(bpltv_t *h, const double *alpha, int am, int an, const bpltv_params *p, double *u_out);
+int bpltv_sumregs_unrolled_denoise_device(bpltv_t *h, const double *d_alpha, int am, int an, const bpltv_params *p, double *d_tape);
+int bpltv_sumregs_unrolled_vjp(bpltv_t *h, const double *alpha, int am, int an, const bpltv_params *p,
+                               const double *gu, double *grad_f_out, double *grad_alpha_out);
+int bpltv_sumregs_unrolled_vjp_device(bpltv_t *h, const double *d_tape, const double *d_alpha, int am, int an,
+                                      const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alpha);
+int bpltv_sumregs_unrolled_denoise_each(bpltv_t *h, const double *alphas, int am, int an, const bpltv_params *p, double *u_out);
+int bpltv_sumregs_unrolled_denoise_each_device(bpltv_t *h, const double *d_alphas, int am, int an, const bpltv_params *p,
+                                               double *d_tape);
+int bpltv_sumregs_unrolled_vjp_each(bpltv_t *h, const double *alphas, int am, int an, const bpltv_params *p,
+                                    const double *gu, double *grad_f_out, double *grad_alphas_out);
+int bpltv_sumregs_unrolled_vjp_each_device(bpltv_t *h, const double *d_tape, const double *d_alphas, int am, int an,
+                                           const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alphas);
 
 /* Jacobian-vector product of u = denoise(f, alpha) (TV model): du for tangents (df, dalpha), defined as the linear map
  * whose transpose bpltv_vjp computes, in every branch -- <gu, du> = <grad_f(gu), df> + <grad_alpha(gu), dalpha> for any
