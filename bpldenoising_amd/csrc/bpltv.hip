@@ -322,6 +322,45 @@ struct HandleOptions {
     int hb_rw = 0;                    // ... 32 / 128: row width of its trailing update (0 automatic)
 };
 
+// The tape of a taped solve (bpltv_unrolled_denoise and its weighted and sum-of-regularisers forms) that the handle keeps for
+// the reverse sweep, with the call that recorded it.  One per model: a tape of one model never stands in for another.
+struct Tape {
+    double* d = nullptr;
+    size_t cap = 0;                 // doubles
+    bool valid = false;
+    bool each = false;              // recorded by an _each solve: one parameter block per image
+    int maxiter = 0, am = 0, an = 0, accel = 0;
+    int wo = 0;                     // weighted model: weight planes (0 otherwise)
+    double tau0 = 0.0, sigma0 = 0.0, opnorm = 0.0;
+    double gamma = 0.0;             // weighted model: min w, the strong convexity its step table was made with
+    // a buffer of `need` doubles when the tape is smaller (*grown; nullptr when it is large enough): allocated ahead of
+    // time, so that a call that is rejected afterwards frees it again and leaves the tape as it was
+    hipError_t grow(size_t need, double** grown) const {
+        *grown = nullptr;
+        return cap < need ? hipMalloc((void**)grown, need * sizeof(double)) : hipSuccess;
+    }
+    void install(double* grown, size_t need) {   // (grown may be nullptr: nothing to do)
+        if (!grown) return;
+        if (d) (void)hipFree(d);
+        d = grown;
+        cap = need;
+    }
+    void record(const bpltv_params& p, int am_, int an_, bool each_, int wo_, double gamma_) {
+        valid = true; each = each_;
+        maxiter = p.maxiter; am = am_; an = an_; accel = p.accel ? 1 : 0; wo = wo_;
+        tau0 = p.tau0; sigma0 = p.sigma0; opnorm = p.opnorm; gamma = gamma_;
+    }
+    // the call (params, parameter shape, weight planes) is the one that recorded the tape; `each` and `gamma` are compared apart
+    bool made_with(const bpltv_params& p, int am_, int an_, int wo_) const {
+        return maxiter == p.maxiter && am == am_ && an == an_ && wo == wo_ && accel == (p.accel ? 1 : 0) && tau0 == p.tau0 &&
+               sigma0 == p.sigma0 && opnorm == p.opnorm;
+    }
+    void release() {
+        if (d) (void)hipFree(d);
+        *this = Tape{};
+    }
+};
+
 struct bpltv_handle {
     MultiState* multi = nullptr;   // non-null: this handle only fans out to its shards (multi_gpu.hpp)
     int M = 0, N = 0, O = 0, device = 0, ncu = 0;
@@ -429,31 +468,17 @@ struct bpltv_handle {
     bool last_weighted = false;                     // the last solve was bpltv_weighted_denoise: u and the gap are its
     double* d_wst = nullptr;                        // bpltv_weighted_vjp's host staging [f | grad_w], 2 * M*N*O doubles
     // reverse mode through the iterations (unrolled_kernels.hpp): the handle's own tape of pre-projection duals (allocated on
-    // demand, only grows), what it was recorded with, and the reverse sweep's planes [2 sets x (gx, gy1, gy2) | gf | ga | gu]
-    double* d_tape = nullptr;
-    size_t tape_cap = 0;                            // doubles
-    bool tape_valid = false;
-    int tape_maxiter = 0, tape_am = 0, tape_an = 0, tape_accel = 0;
-    bool tape_each = false;                         // recorded by bpltv_unrolled_denoise_each: one parameter block per image
-    double tape_tau0 = 0.0, tape_sigma0 = 0.0, tape_opnorm = 0.0;
+    // demand, only grows, remembers what it was recorded with), and the reverse sweep's planes [2 sets x (gx, gy1, gy2) | gf | ga | gu]
+    Tape tape;
     double* d_unr = nullptr;                        // 9 * M*N*O doubles
     // ... of the weighted model (weighted_unrolled_kernels.hpp): a tape of its own (z1, z2 and x per iteration), so that a TV
     // tape and a weighted one never stand in for each other, with the weight planes and gamma = min w it was recorded with;
     // the reverse sweep runs in d_unr, its weight gradient in a tenth plane allocated when grad_w is first asked for
-    double* d_wtape = nullptr;
-    size_t wtape_cap = 0;                           // doubles
-    bool wtape_valid = false;
-    int wtape_maxiter = 0, wtape_am = 0, wtape_an = 0, wtape_accel = 0, wtape_wo = 0;
-    double wtape_tau0 = 0.0, wtape_sigma0 = 0.0, wtape_opnorm = 0.0, wtape_gamma = 0.0;
+    Tape wtape;
     double* d_unr_gw = nullptr;                     // M*N*O doubles
     // ... of the sum-of-regularisers model (sumregs_unrolled_kernels.hpp): a third tape (six dual components per iteration), kept
-    // apart from the other two and remembered with what it was recorded with; the reverse sweep runs in planes of its own,
-    // [2 sets x (gx, 6 gy) | gf | 3 ga | gu]
-    double* d_srtape = nullptr;
-    size_t srtape_cap = 0;                          // doubles
-    bool srtape_valid = false, srtape_each = false;
-    int srtape_maxiter = 0, srtape_am = 0, srtape_an = 0, srtape_accel = 0;
-    double srtape_tau0 = 0.0, srtape_sigma0 = 0.0, srtape_opnorm = 0.0;
+    // apart from the other two; the reverse sweep runs in planes of its own, [2 sets x (gx, 6 gy) | gf | 3 ga | gu]
+    Tape srtape;
     double* d_srunr = nullptr;                      // 19 * M*N*O doubles
     bool srun_ready = false;
     // forward mode through the iterations (unrolled_jvp_kernels.hpp): the tangent sweep's planes [2 sets x (x, y1, y2, dx, dy1,
@@ -1056,6 +1081,13 @@ struct ChainSolve {
     std::function<int()> begin;
     std::function<int(int buf, int* iterations)> end;
 };
+
+// The stagger / ping-pong loop of a ChainSolve::enqueue whose launches tile like the weighted kernel (32 x 32 regions, T
+// iterations each): `launch` fills the model's argument struct for one launch -- the iterations [it, it + nit) of the images
+// [lo, hi) on st, from the state set cur into nxt; first: it == 0 -- and launches its kernel.  (Defined with the taped solves.)
+struct LaunchStep { hipStream_t st; int it, nit, cur, nxt, first, lo, hi; };
+using LaunchFn = std::function<void(const LaunchStep&)>;
+EnqueueFn launch_loop(int T, LaunchFn launch);
 
 // One graph per chain by stream capture of j.enqueue on the handle's capture stream.  Odd chains run half a launch out of
 // phase when `out_of_phase` (chain_out_of_phase).  All or nothing: on any failure *out stays empty.
@@ -3214,23 +3246,17 @@ int run_weighted_pdhg(bpltv_t* h, const bpltv_params& p, const WeightedPlan& pl,
     j.bytes_per_px_iter = amap ? 72.0 : 64.0;   // read x, y1, y2, f, w (+ alpha), write x, y1, y2
     j.key = GraphKey{p.maxiter, T, 0, h->last_am, h->last_an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, nullptr, (const void*)d_tab, 0,
                      (const void*)h->d_alpha, 0, h->w_wo};
-    j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
-        int step = stagger ? T / 2 : T;
-        for (int it = it0; it < it1; it += step, step = T) {
-            const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
-            WeightedArgs a;
-            a.xin = h->d_state[cur][0]; a.y1in = h->d_state[cur][1]; a.y2in = h->d_state[cur][2];
-            a.xout = h->d_state[nxt][0]; a.y1out = h->d_state[nxt][1]; a.y2out = h->d_state[nxt][2];
-            a.f = h->d_f; a.w = h->d_w; a.alpha = h->d_alpha; a.tab = d_tab;
-            a.wstride = h->w_wo > 1 ? h->npx : 0;
-            a.am = h->last_am; a.an = h->last_an;
-            a.it0 = it; a.nit = std::min(step, it1 - it);
-            a.M = M; a.N = N; a.halo = T; a.first = (it == 0) ? 1 : 0; a.img0 = lo;
-            hipLaunchKernelGGL(weighted_tile_kernel, dim3(pl.nTi, pl.nTj, hi - lo), dim3(WT_R * WT_R), weighted_lds_bytes(), st, a);
-            cur = nxt;
-        }
-        return cur;
-    };
+    j.enqueue = launch_loop(T, [&](const LaunchStep& s) {
+        WeightedArgs a;
+        a.xin = h->d_state[s.cur][0]; a.y1in = h->d_state[s.cur][1]; a.y2in = h->d_state[s.cur][2];
+        a.xout = h->d_state[s.nxt][0]; a.y1out = h->d_state[s.nxt][1]; a.y2out = h->d_state[s.nxt][2];
+        a.f = h->d_f; a.w = h->d_w; a.alpha = h->d_alpha; a.tab = d_tab;
+        a.wstride = h->w_wo > 1 ? h->npx : 0;
+        a.am = h->last_am; a.an = h->last_an;
+        a.it0 = s.it; a.nit = s.nit;
+        a.M = M; a.N = N; a.halo = T; a.first = s.first; a.img0 = s.lo;
+        hipLaunchKernelGGL(weighted_tile_kernel, dim3(pl.nTi, pl.nTj, s.hi - s.lo), dim3(WT_R * WT_R), weighted_lds_bytes(), s.st, a);
+    });
     return run_chains(h, p, j, result_buf);   // (no gap callback: the weighted solve does not take params.check_every)
 }
 
@@ -3313,9 +3339,22 @@ int weighted_multi(bpltv_t* h, const char* what, bool solve, F call, const char*
 }
 
 // ============================================================================================
-// Reverse mode through the PDHG iterations (unrolled_kernels.hpp)
+// Reverse mode through the PDHG iterations (unrolled_kernels.hpp, weighted_unrolled_kernels.hpp, sumregs_unrolled_kernels.hpp;
+// DESIGN.md sections 4.6, 4.8 and 4.9)
 // ============================================================================================
 static_assert(UN_R == WT_R, "the unrolled kernels tile like the weighted one");
+
+EnqueueFn launch_loop(int T, LaunchFn launch) {
+    return [T, launch](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
+        int step = stagger ? T / 2 : T;
+        for (int it = it0; it < it1; it += step, step = T) {
+            const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
+            launch(LaunchStep{st, it, std::min(step, it1 - it), cur, nxt, (it == 0) ? 1 : 0, lo, hi});
+            cur = nxt;
+        }
+        return cur;
+    };
+}
 
 // What an unrolled call rejects on its parameters alone
 int unrolled_check_params(bpltv_t* h, const bpltv_params& p, const char* who) {
@@ -3333,433 +3372,9 @@ int unrolled_plan(bpltv_t* h, const bpltv_params& p, int cap, WeightedPlan* pl) 
     return weighted_plan(h, q, pl);
 }
 
-const char* const kUnrolled = "the unrolled solve";   // what weighted_multi's message calls these entry points
-
-unsigned long long unrolled_tape_doubles(const bpltv_t* h, const bpltv_params& p) { return 2ull * (unsigned long long)p.maxiter * h->tot; }
-
-// maxiter taped iterations on the dataset images, in the TV state sets, with d_alpha; z_k of every pixel into d_tape.
-int run_unrolled_pdhg(bpltv_t* h, const bpltv_params& p, const WeightedPlan& pl, double* d_tape, int* result_buf) {
-    h->has_per_image = false;
-    double* d_tab = nullptr;
-    int rc = get_table(h, p, &d_tab, 8.0, 0);
-    if (rc) return rc;
-    const int M = h->M, N = h->N, O = h->O, T = pl.T;
-    const bool amap = (h->last_am == M && h->last_an == N) && !(M == 1 && N == 1);
-    h->st.tile_iters = T; h->st.tiles = pl.nTi * pl.nTj * O; h->st.region_i = UN_R; h->st.region_j = UN_R; h->st.pdhg_variant = 0;
-    ChainSolve j;
-    j.model = MODEL_UN; j.nplanes = 3; j.state0 = h->d_state[0];
-    j.nimg = O; j.niter = p.maxiter; j.T = T;
-    j.chains = plan_chains(p.reserved[1], h->st.tiles, h->ncu, O, 2);   // at most two (image groups on two streams)
-    j.serial = (p.reserved[2] & 1) != 0; j.helper_thread = !(p.reserved[2] & 8);
-    j.bytes_per_px_iter = amap ? 80.0 : 72.0;   // read x, y1, y2, f (+ alpha), write x, y1, y2 and z1, z2
-    // (istride: a per-image solve uploads into d_alpha like a shared one, and must not replay its graph, nor the reverse)
-    j.key = GraphKey{p.maxiter, T, 0, h->last_am, h->last_an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_tape, (const void*)d_tab, 0,
-                     (const void*)h->d_alpha, h->alpha_istride, 0};
-    j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
-        int step = stagger ? T / 2 : T;
-        for (int it = it0; it < it1; it += step, step = T) {
-            const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
-            UnrolledArgs a;
-            a.xin = h->d_state[cur][0]; a.y1in = h->d_state[cur][1]; a.y2in = h->d_state[cur][2];
-            a.xout = h->d_state[nxt][0]; a.y1out = h->d_state[nxt][1]; a.y2out = h->d_state[nxt][2];
-            a.f = h->d_f; a.alpha = h->d_alpha; a.tab = d_tab; a.tape = d_tape; a.plane = h->tot;
-            a.am = h->last_am; a.an = h->last_an; a.istride = h->alpha_istride;
-            a.it0 = it; a.nit = std::min(step, it1 - it);
-            a.M = M; a.N = N; a.halo = T; a.first = (it == 0) ? 1 : 0; a.img0 = lo;
-            hipLaunchKernelGGL(unrolled_tile_kernel, dim3(pl.nTi, pl.nTj, hi - lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), st, a);
-            cur = nxt;
-        }
-        return cur;
-    };
-    return run_chains(h, p, j, result_buf);
-}
-
-// bpltv_unrolled_denoise(_device) on a single-device handle.  d_tape_user: the caller's tape, or nullptr for the handle's own,
-// which grows here -- the new buffer is allocated before anything changes and installed only once the parameter is accepted.
-// each (bpltv_unrolled_denoise_each(_device)): alpha holds O blocks of am*an doubles, image k reads block k (upload_alpha).
-int unrolled_denoise_common(bpltv_t* h, const double* alpha, bool dev, int am, int an, const bpltv_params* pp, double* d_tape_user,
-                            double* u_out, bool each = false) {
-    const char* who = each ? (dev ? "bpltv_unrolled_denoise_each_device" : "bpltv_unrolled_denoise_each")
-                           : (dev ? "bpltv_unrolled_denoise_device" : "bpltv_unrolled_denoise");
-    WallTimer wt;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: bpltv_set_data has not been called", who);
-    const bpltv_params p = resolve(pp);
-    if (int prc = unrolled_check_params(h, p, who)) return prc;
-    WeightedPlan pl;
-    if (int prc = unrolled_plan(h, p, PDHG_MAX_T, &pl)) return prc;
-    const size_t need = (size_t)unrolled_tape_doubles(h, p);
-    double* grown = nullptr;
-    if (!d_tape_user && h->tape_cap < need) {
-        const hipError_t e = hipMalloc((void**)&grown, need * sizeof(double));
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return set_err(h, e == hipErrorOutOfMemory ? BPLTV_E_NOMEM : BPLTV_E_HIP, "%s: hipMalloc of the tape (%.1f MB) failed: %s", who,
-                           need * sizeof(double) / 1e6, hipGetErrorString(e));
-        }
-    }
-    bpltv_params q = p;   // the TV planner's knobs mean nothing here: upload_alpha's precheck sees the defaults
-    q.tile_iters = 0; q.reserved[0] = 0; q.reserved[1] = 0; q.reserved[2] = 0;
-    int rc = upload_alpha(h, alpha, dev, am, an, PRE_TV, each ? h->O : 1, &q);
-    if (rc) {
-        if (grown) (void)hipFree(grown);
-        return rc;
-    }
-    if (grown) {
-        if (h->d_tape) (void)hipFree(h->d_tape);
-        h->d_tape = grown;
-        h->tape_cap = need;
-    }
-    if (!d_tape_user) h->tape_valid = false;   // about to be overwritten
-    int buf = 0;
-    rc = run_unrolled_pdhg(h, p, pl, d_tape_user ? d_tape_user : h->d_tape, &buf);
-    if (rc) return rc;
-    h->result_buf = buf;
-    h->has_result = true;
-    h->last_is_sr = false;
-    h->last_weighted = false;
-    if (!d_tape_user) {
-        h->tape_valid = true;
-        h->tape_maxiter = p.maxiter; h->tape_am = am; h->tape_an = an; h->tape_accel = p.accel ? 1 : 0; h->tape_each = each;
-        h->tape_tau0 = p.tau0; h->tape_sigma0 = p.sigma0; h->tape_opnorm = p.opnorm;
-    }
-    if (u_out) {
-        HIPCHK(h, hipMemcpyAsync(u_out, h->d_state[buf][0], h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    h->st.total_ms = wt.ms();
-    return BPLTV_OK;
-}
-
-// bpltv_unrolled_vjp(_device) on a single-device handle: d_gu and the outputs live in HBM, alpha on the host or (dev) in HBM;
-// d_tape_user or the handle's tape.  The parameter is staged apart (stage_param) and the sweep runs in planes of its own, so the
-// last solve stays untouched; the solve statistics are put back after the shared driver has run the sweep.
-// each (bpltv_unrolled_vjp_each(_device)): alpha holds O blocks, image k reads block k, and d_grad_alpha receives the O per-image
-// gradients, image-major -- the ga plane as it is for a map, image k's patch sums otherwise.
-int unrolled_vjp_common(bpltv_t* h, const double* d_tape_user, const double* alpha, bool dev, int am, int an, const bpltv_params* pp,
-                        const double* d_gu, double* d_grad_f, double* d_grad_alpha, bool each = false) {
-    const char* who = each ? "unrolled_vjp_each" : "unrolled_vjp";
-    if (!alpha || !d_gu) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
-    if (!d_grad_f && !d_grad_alpha) return set_err(h, BPLTV_E_ARG, "%s: both outputs are NULL", who);
-    const bpltv_params p0 = resolve(pp);
-    if (int prc = unrolled_check_params(h, p0, who)) return prc;
-    if (!d_tape_user) {
-        if (!h->tape_valid) return set_err(h, BPLTV_E_NODATA, "%s: the handle holds no tape (bpltv_unrolled_denoise has not run)", who);
-        if (h->tape_maxiter != p0.maxiter || h->tape_am != am || h->tape_an != an || h->tape_accel != (p0.accel ? 1 : 0) ||
-            h->tape_tau0 != p0.tau0 || h->tape_sigma0 != p0.sigma0 || h->tape_opnorm != p0.opnorm)
-            return set_err(h, BPLTV_E_ARG, "%s: the handle's tape was recorded with maxiter = %d, a %dx%d parameter and other steps than this call's (%d, %dx%d)",
-                           who, h->tape_maxiter, h->tape_am, h->tape_an, p0.maxiter, am, an);
-        if (h->tape_each != each)
-            return set_err(h, BPLTV_E_ARG, "%s: the handle's tape was recorded with %s", who,
-                           h->tape_each ? "one parameter block per image (bpltv_unrolled_denoise_each)" : "one shared parameter (bpltv_unrolled_denoise)");
-    }
-    WeightedPlan pl;
-    if (int prc = unrolled_plan(h, p0, UN_REV_T, &pl)) return prc;
-    const size_t tot = h->tot, npx = h->npx;
-    if (!h->d_unr)
-        if (int arc = alloc_all(h, {{(void**)&h->d_unr, 9 * tot * sizeof(double)}}, "reverse sweep")) return arc;
-    bpltv_params p;
-    GradCtx g;
-    if (int rc = stage_param(h, who, alpha, dev, am, an, 1, each, 0, pp, nullptr, 1, {{d_gu, tot, "cotangent gu"}}, &p, &g)) return rc;
-    const int M = h->M, N = h->N, O = h->O, T = pl.T, K = p.maxiter;
-    const bool amap = am == M && an == N && !(M == 1 && N == 1);
-    if (d_grad_alpha && !amap && !each)
-        if (int rc = ensure(h, &h->d_red, &h->red_cap, (size_t)am * an * O)) return rc;
-    h->has_per_image = false;
-    double* d_tab = nullptr;
-    if (int rc = get_table(h, p, &d_tab, 8.0, 0)) return rc;
-    const double* d_tape = d_tape_user ? d_tape_user : h->d_tape;
-    double* S[2][3];
-    for (int s = 0; s < 2; ++s)
-        for (int c = 0; c < 3; ++c) S[s][c] = h->d_unr + (size_t)(3 * s + c) * tot;
-    double *d_gf = h->d_unr + 6 * tot, *d_ga = h->d_unr + 7 * tot, *d_g0 = h->d_unr + 8 * tot;
-    const bpltv_stats_t kept = h->st;
-    HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
-    HIPCHK(h, hipMemcpyAsync(d_g0, d_gu, tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    ChainSolve j;
-    j.model = MODEL_UN; j.nplanes = 3; j.state0 = S[0];
-    j.nimg = O; j.niter = K; j.T = T;
-    const int tiles = pl.nTi * pl.nTj * O;
-    j.chains = plan_chains(p.reserved[1], tiles, h->ncu, O, 2);
-    j.serial = (p.reserved[2] & 1) != 0; j.helper_thread = !(p.reserved[2] & 8);
-    j.bytes_per_px_iter = 0.0;   // (the driver's solve statistics are not this call's: `kept` goes back below)
-    j.key = GraphKey{K, T, 1, am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_tape, (const void*)d_tab, 0, (const void*)g.alpha, g.astride, 0};
-    j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
-        int step = stagger ? T / 2 : T;
-        for (int it = it0; it < it1; it += step, step = T) {   // `it` counts reverse steps: step r undoes iteration K - 1 - r
-            const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
-            UnrolledRevArgs a;
-            a.gxin = (it == 0) ? d_g0 : S[cur][0]; a.gy1in = S[cur][1]; a.gy2in = S[cur][2];
-            a.gxout = S[nxt][0]; a.gy1out = S[nxt][1]; a.gy2out = S[nxt][2];
-            a.gf = d_gf; a.ga = d_ga; a.tape = d_tape; a.alpha = g.alpha; a.tab = d_tab; a.plane = tot;
-            a.am = am; a.an = an; a.istride = g.astride;
-            a.khi = K - 1 - it; a.nit = std::min(step, it1 - it);
-            a.M = M; a.N = N; a.halo = T; a.first = (it == 0) ? 1 : 0; a.img0 = lo;
-            hipLaunchKernelGGL(unrolled_reverse_tile_kernel, dim3(pl.nTi, pl.nTj, hi - lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), st, a);
-            cur = nxt;
-        }
-        return cur;
-    };
-    int buf = 0;
-    const int rc = run_chains(h, p, j, &buf);
-    h->st = kept;
-    if (rc) return rc;
-    if (d_grad_f)
-        hipLaunchKernelGGL(unrolled_gradf_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, d_gf, S[buf][0], tot, d_grad_f);
-    if (d_grad_alpha && each && amap) {   // per image: the plane as it is, or image k's patch sums (fixed order, no sum over images)
-        HIPCHK(h, hipMemcpyAsync(d_grad_alpha, d_ga, tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    } else if (d_grad_alpha && each) {
-        hipLaunchKernelGGL(patch_sum_kernel, dim3(am * an, O), dim3(256), 0, h->stream, d_ga, M, N, O, am, an, 1, am * an, d_grad_alpha);
-    } else if (d_grad_alpha && amap) {   // the per-pixel sums over the images, in image order; then per patch (calc_adjoint) or over everything
-        hipLaunchKernelGGL(map_sum_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, d_ga, npx, O, d_grad_alpha);
-    } else if (d_grad_alpha) {
-        hipLaunchKernelGGL(patch_sum_kernel, dim3(am * an, O), dim3(256), 0, h->stream, d_ga, M, N, O, am, an, O, 1, h->d_red);
-        hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, O, am * an, 1.0, d_grad_alpha, (double*)nullptr);
-    }
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
-    h->st.adjoint_ms = ms;
-    h->st.adjoint_method = 7;
-    h->st.reg_gradient_used = 0;
-    h->st.adjoint_attempts = 1;
-    h->st.adjoint_chunks = 1;
-    h->st.hb_sync = 0;
-    h->st.kappa_used = 0.0;
-    h->st.adjoint_residual = 0.0;
-    h->st.adjoint_residual_raw = 0.0;
-    return BPLTV_OK;
-}
-
-// ============================================================================================
-// Reverse mode through the iterations of the weighted model (weighted_unrolled_kernels.hpp)
-// ============================================================================================
-const char* const kWeightedUnrolled = "the weighted unrolled solve";   // what weighted_multi's message calls these entry points
-
-// maxiter taped iterations of the weighted recurrence on the dataset images, in the TV state sets, with the handle's d_w /
-// w_wo / w_min and d_alpha; z_k and x_{k+1} of every pixel into d_tape.
-int run_weighted_unrolled_pdhg(bpltv_t* h, const bpltv_params& p, const WeightedPlan& pl, double* d_tape, int* result_buf) {
-    h->has_per_image = false;
-    double* d_tab = nullptr;
-    int rc = get_table(h, p, &d_tab, 8.0, 0, h->w_min);
-    if (rc) return rc;
-    const int M = h->M, N = h->N, O = h->O, T = pl.T;
-    const bool amap = (h->last_am == M && h->last_an == N) && !(M == 1 && N == 1);
-    h->st.tile_iters = T; h->st.tiles = pl.nTi * pl.nTj * O; h->st.region_i = UN_R; h->st.region_j = UN_R; h->st.pdhg_variant = 0;
-    ChainSolve j;
-    j.model = MODEL_UN; j.nplanes = 3; j.state0 = h->d_state[0];
-    j.nimg = O; j.niter = p.maxiter; j.T = T;
-    j.chains = plan_chains(p.reserved[1], h->st.tiles, h->ncu, O, 2);   // at most two (image groups on two streams)
-    j.serial = (p.reserved[2] & 1) != 0; j.helper_thread = !(p.reserved[2] & 8);
-    j.bytes_per_px_iter = amap ? 96.0 : 88.0;   // read x, y1, y2, f, w (+ alpha), write x, y1, y2 and z1, z2, x
-    j.key = GraphKey{p.maxiter, T, 6, h->last_am, h->last_an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_tape, (const void*)d_tab, 0,
-                     (const void*)h->d_alpha, 0, h->w_wo};
-    j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
-        int step = stagger ? T / 2 : T;
-        for (int it = it0; it < it1; it += step, step = T) {
-            const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
-            WeightedUnrolledArgs a;
-            a.xin = h->d_state[cur][0]; a.y1in = h->d_state[cur][1]; a.y2in = h->d_state[cur][2];
-            a.xout = h->d_state[nxt][0]; a.y1out = h->d_state[nxt][1]; a.y2out = h->d_state[nxt][2];
-            a.f = h->d_f; a.w = h->d_w; a.alpha = h->d_alpha; a.tab = d_tab; a.tape = d_tape; a.plane = h->tot;
-            a.wstride = h->w_wo > 1 ? h->npx : 0;
-            a.am = h->last_am; a.an = h->last_an;
-            a.it0 = it; a.nit = std::min(step, it1 - it);
-            a.M = M; a.N = N; a.halo = T; a.first = (it == 0) ? 1 : 0; a.img0 = lo;
-            hipLaunchKernelGGL(weighted_unrolled_tile_kernel, dim3(pl.nTi, pl.nTj, hi - lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), st, a);
-            cur = nxt;
-        }
-        return cur;
-    };
-    return run_chains(h, p, j, result_buf);
-}
-
-// bpltv_weighted_unrolled_denoise(_device) on a single-device handle: weighted_denoise_common's order (arguments, params, w,
-// then upload_alpha, and only then the handle's copy of w) with unrolled_denoise_common's tape -- d_tape_user or the handle's
-// own, whose new buffer is allocated before anything changes and installed only once the parameter is accepted.
-int weighted_unrolled_denoise_common(bpltv_t* h, const double* w, int wo, const double* alpha, bool dev, int am, int an,
-                                     const bpltv_params* pp, double* d_tape_user, double* u_out) {
-    const char* who = dev ? "bpltv_weighted_unrolled_denoise_device" : "bpltv_weighted_unrolled_denoise";
-    WallTimer wt;
-    HIPCHK(h, hipSetDevice(h->device));
-    if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: bpltv_set_data has not been called", who);
-    if (!w) return set_err(h, BPLTV_E_ARG, "%s: w is a null pointer", who);
-    if (wo != 1 && wo != h->O) return set_err(h, BPLTV_E_ARG, "%s: wo = %d: one weight plane (1) or one per image (%d)", who, wo, h->O);
-    const bpltv_params p = resolve(pp);
-    if (int prc = unrolled_check_params(h, p, who)) return prc;
-    WeightedPlan pl;
-    if (int prc = unrolled_plan(h, p, PDHG_MAX_T, &pl)) return prc;
-    const size_t nw = (size_t)wo * h->npx;
-    double wmin = 0.0;
-    int rc = check_weight(h, who, w, dev, nw, &wmin);
-    if (rc) return rc;
-    const size_t need = (size_t)3 * p.maxiter * h->tot;
-    double* grown = nullptr;
-    if (!d_tape_user && h->wtape_cap < need) {
-        const hipError_t e = hipMalloc((void**)&grown, need * sizeof(double));
-        if (e != hipSuccess) {
-            (void)hipGetLastError();
-            return set_err(h, e == hipErrorOutOfMemory ? BPLTV_E_NOMEM : BPLTV_E_HIP, "%s: hipMalloc of the tape (%.1f MB) failed: %s", who,
-                           need * sizeof(double) / 1e6, hipGetErrorString(e));
-        }
-    }
-    if (!h->d_w) {
-        rc = alloc_all(h, {{(void**)&h->d_w, h->tot * sizeof(double)}}, "fidelity weight");
-        if (rc) {
-            if (grown) (void)hipFree(grown);
-            return rc;
-        }
-    }
-    bpltv_params q = p;   // the TV planner's knobs mean nothing here: upload_alpha's precheck sees the defaults
-    q.tile_iters = 0; q.reserved[0] = 0; q.reserved[1] = 0; q.reserved[2] = 0;
-    rc = upload_alpha(h, alpha, dev, am, an, PRE_TV, 1, &q);
-    if (rc) {
-        if (grown) (void)hipFree(grown);
-        return rc;
-    }
-    if (grown) {
-        if (h->d_wtape) (void)hipFree(h->d_wtape);
-        h->d_wtape = grown;
-        h->wtape_cap = need;
-    }
-    if (!d_tape_user) h->wtape_valid = false;   // about to be overwritten
-    HIPCHK(h, hipMemcpyAsync(h->d_w, w, nw * sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
-    h->w_wo = wo;
-    h->w_min = wmin;
-    int buf = 0;
-    rc = run_weighted_unrolled_pdhg(h, p, pl, d_tape_user ? d_tape_user : h->d_wtape, &buf);
-    if (rc) return rc;
-    h->result_buf = buf;
-    h->has_result = true;
-    h->last_is_sr = false;
-    h->last_weighted = true;
-    if (!d_tape_user) {
-        h->wtape_valid = true;
-        h->wtape_maxiter = p.maxiter; h->wtape_am = am; h->wtape_an = an; h->wtape_accel = p.accel ? 1 : 0; h->wtape_wo = wo;
-        h->wtape_tau0 = p.tau0; h->wtape_sigma0 = p.sigma0; h->wtape_opnorm = p.opnorm; h->wtape_gamma = wmin;
-    }
-    if (u_out) {
-        HIPCHK(h, hipMemcpyAsync(u_out, h->d_state[buf][0], h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
-    h->st.total_ms = wt.ms();
-    return BPLTV_OK;
-}
-
-// bpltv_weighted_unrolled_vjp(_device) on a single-device handle: d_gu and the outputs live in HBM, w and alpha on the host or
-// (dev) in HBM; d_tape_user or the handle's weighted tape.  w (every entry >= 0) and the parameter are staged apart
-// (stage_param) and the sweep runs in d_unr, so the last solve stays untouched; of the statistics only adjoint_ms and
-// adjoint_method change.  The resident f is read for d_grad_w only.  The step table is the solve's (gamma = min w), held fixed.
-int weighted_unrolled_vjp_common(bpltv_t* h, const double* d_tape_user, const double* w, int wo, const double* alpha, bool dev, int am,
-                                 int an, const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alpha,
-                                 double* d_grad_w) {
-    const char* who = "weighted_unrolled_vjp";
-    if (!w || !alpha || !d_gu) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
-    if (!d_grad_f && !d_grad_alpha && !d_grad_w) return set_err(h, BPLTV_E_ARG, "%s: all three outputs are NULL", who);
-    if (wo != 1 && wo != h->O) return set_err(h, BPLTV_E_ARG, "%s: wo = %d: one weight plane (1) or one per image (%d)", who, wo, h->O);
-    const bpltv_params p0 = resolve(pp);
-    if (int prc = unrolled_check_params(h, p0, who)) return prc;
-    if (d_grad_w && !h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: grad_w reads the resident f: bpltv_set_data has not been called", who);
-    if (!d_tape_user) {
-        if (!h->wtape_valid)
-            return set_err(h, BPLTV_E_NODATA, "%s: the handle holds no weighted tape (bpltv_weighted_unrolled_denoise has not run)", who);
-        if (h->wtape_maxiter != p0.maxiter || h->wtape_am != am || h->wtape_an != an || h->wtape_wo != wo ||
-            h->wtape_accel != (p0.accel ? 1 : 0) || h->wtape_tau0 != p0.tau0 || h->wtape_sigma0 != p0.sigma0 || h->wtape_opnorm != p0.opnorm)
-            return set_err(h, BPLTV_E_ARG, "%s: the handle's tape was recorded with maxiter = %d, a %dx%d parameter, wo = %d and other steps than this call's (%d, %dx%d, wo = %d)",
-                           who, h->wtape_maxiter, h->wtape_am, h->wtape_an, h->wtape_wo, p0.maxiter, am, an, wo);
-    }
-    WeightedPlan pl;
-    if (int prc = unrolled_plan(h, p0, WUN_REV_T, &pl)) return prc;
-    const size_t tot = h->tot, npx = h->npx;
-    if (!h->d_unr)
-        if (int arc = alloc_all(h, {{(void**)&h->d_unr, 9 * tot * sizeof(double)}}, "reverse sweep")) return arc;
-    if (d_grad_w && !h->d_unr_gw)
-        if (int arc = alloc_all(h, {{(void**)&h->d_unr_gw, tot * sizeof(double)}}, "reverse sweep (weight gradient)")) return arc;
-    bpltv_params p;
-    GradCtx g;
-    if (int rc = stage_param(h, who, alpha, dev, am, an, 1, false, 0, pp, w, wo, {{d_gu, tot, "cotangent gu"}}, &p, &g, false)) return rc;
-    if (!d_tape_user && h->wtape_gamma != g.w_min)
-        return set_err(h, BPLTV_E_ARG, "%s: the handle's tape was recorded with gamma = min w = %g, this call's w has %g", who, h->wtape_gamma, g.w_min);
-    const int M = h->M, N = h->N, O = h->O, T = pl.T, K = p.maxiter;
-    const bool amap = am == M && an == N && !(M == 1 && N == 1);
-    if (d_grad_alpha && !amap)
-        if (int rc = ensure(h, &h->d_red, &h->red_cap, (size_t)am * an * O)) return rc;
-    h->has_per_image = false;
-    double* d_tab = nullptr;
-    if (int rc = get_table(h, p, &d_tab, 8.0, 0, g.w_min)) return rc;
-    const double* d_tape = d_tape_user ? d_tape_user : h->d_wtape;
-    double* S[2][3];
-    for (int s = 0; s < 2; ++s)
-        for (int c = 0; c < 3; ++c) S[s][c] = h->d_unr + (size_t)(3 * s + c) * tot;
-    double *d_gf = h->d_unr + 6 * tot, *d_ga = h->d_unr + 7 * tot, *d_g0 = h->d_unr + 8 * tot;
-    double* d_gw = d_grad_w ? h->d_unr_gw : nullptr;
-    const bpltv_stats_t kept = h->st;
-    HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
-    HIPCHK(h, hipMemcpyAsync(d_g0, d_gu, tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    ChainSolve j;
-    j.model = MODEL_UN; j.nplanes = 3; j.state0 = S[0];
-    j.nimg = O; j.niter = K; j.T = T;
-    const int tiles = pl.nTi * pl.nTj * O;
-    j.chains = plan_chains(p.reserved[1], tiles, h->ncu, O, 2);
-    j.serial = (p.reserved[2] & 1) != 0; j.helper_thread = !(p.reserved[2] & 8);
-    j.bytes_per_px_iter = 0.0;   // (the driver's solve statistics are not this call's: `kept` goes back below)
-    j.key = GraphKey{K, T, d_gw ? 8 : 7, am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_tape, (const void*)d_tab, 0, (const void*)g.alpha, 0, wo};
-    j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
-        int step = stagger ? T / 2 : T;
-        for (int it = it0; it < it1; it += step, step = T) {   // `it` counts reverse steps: step r undoes iteration K - 1 - r
-            const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
-            WeightedUnrolledRevArgs a;
-            a.gxin = (it == 0) ? d_g0 : S[cur][0]; a.gy1in = S[cur][1]; a.gy2in = S[cur][2];
-            a.gxout = S[nxt][0]; a.gy1out = S[nxt][1]; a.gy2out = S[nxt][2];
-            a.gf = d_gf; a.ga = d_ga; a.gw = d_gw; a.tape = d_tape; a.f = h->d_f; a.w = g.w; a.alpha = g.alpha; a.tab = d_tab;
-            a.plane = tot; a.wstride = wo > 1 ? npx : 0;
-            a.am = am; a.an = an;
-            a.khi = K - 1 - it; a.nit = std::min(step, it1 - it);
-            a.M = M; a.N = N; a.halo = T; a.first = (it == 0) ? 1 : 0; a.img0 = lo;
-            hipLaunchKernelGGL(weighted_unrolled_reverse_tile_kernel, dim3(pl.nTi, pl.nTj, hi - lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), st, a);
-            cur = nxt;
-        }
-        return cur;
-    };
-    int buf = 0;
-    const int rc = run_chains(h, p, j, &buf);
-    h->st = kept;
-    if (rc) return rc;
-    if (d_grad_f)
-        hipLaunchKernelGGL(unrolled_gradf_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, d_gf, S[buf][0], tot, d_grad_f);
-    if (d_grad_alpha && amap) {   // the per-pixel sums over the images, in image order; then per patch (calc_adjoint) or over everything
-        hipLaunchKernelGGL(map_sum_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, d_ga, npx, O, d_grad_alpha);
-    } else if (d_grad_alpha) {
-        hipLaunchKernelGGL(patch_sum_kernel, dim3(am * an, O), dim3(256), 0, h->stream, d_ga, M, N, O, am, an, O, 1, h->d_red);
-        hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, O, am * an, 1.0, d_grad_alpha, (double*)nullptr);
-    }
-    if (d_grad_w && wo > 1) {   // per image: the plane as it is; one plane: the sum over the images in image order
-        HIPCHK(h, hipMemcpyAsync(d_grad_w, d_gw, tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    } else if (d_grad_w) {
-        hipLaunchKernelGGL(map_sum_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, d_gw, npx, O, d_grad_w);
-    }
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
-    h->st.adjoint_ms = ms;
-    h->st.adjoint_method = 9;
-    return BPLTV_OK;
-}
-
-// ============================================================================================
-// Reverse mode through the iterations of the sum-of-regularisers model (sumregs_unrolled_kernels.hpp)
-// ============================================================================================
-const char* const kSrUnrolled = "the sum-of-regularisers unrolled solve";   // what weighted_multi's message calls these entry points
-
-struct SrUnrolledPlan { int T = 0, nTi = 0, nTj = 0; };
-
 // run_sr_pdhg's cut of the image into 32 x 32 regions (halo 2T, default T = 4), with the fusion depth capped at `cap` (the
 // reverse kernel holds SRUN_REV_T iterations of tape in registers); the first use sets the kernels' LDS size
-int sr_unrolled_plan(bpltv_t* h, const bpltv_params& p, int cap, SrUnrolledPlan* pl) {
+int sr_unrolled_plan(bpltv_t* h, const bpltv_params& p, int cap, WeightedPlan* pl) {
     if (p.tile_iters < 0) return set_err(h, BPLTV_E_ARG, "tile_iters must be >= 0");
     auto maxT = [](int L) { return (L <= SRUN_R) ? (1 << 20) : (SRUN_R - 1) / 4; };   // 2 * halo = 4T must leave a core
     pl->T = std::min(std::min(p.tile_iters > 0 ? p.tile_iters : 4, cap), std::min(maxT(h->M), maxT(h->N)));
@@ -3777,202 +3392,397 @@ int sr_unrolled_plan(bpltv_t* h, const bpltv_params& p, int cap, SrUnrolledPlan*
     return BPLTV_OK;
 }
 
-// maxiter taped iterations on the dataset images, in the sum-of-regularisers state sets, with d_alpha (alpha_istride != 0: one
-// block per image); the six z_k components of every pixel into d_tape.
-int run_sr_unrolled_pdhg(bpltv_t* h, const bpltv_params& p, const SrUnrolledPlan& pl, double* d_tape, int* result_buf) {
-    h->has_per_image = false;
-    double* d_tab = nullptr;
-    int rc = get_table(h, p, &d_tab, 18.0);
-    if (rc) return rc;
-    const int M = h->M, N = h->N, O = h->O, T = pl.T;
-    const bool amap = (h->last_am == M && h->last_an == N) && !(M == 1 && N == 1);
-    const bool each = h->alpha_istride != 0;
-    h->st.tile_iters = T; h->st.tiles = pl.nTi * pl.nTj * O; h->st.region_i = SRUN_R; h->st.region_j = SRUN_R; h->st.pdhg_variant = 0;
-    void (*kern)(SrUnrolledArgs) = each ? &sr_unrolled_tile_kernel<SR_EACH> : &sr_unrolled_tile_kernel<SR_SHARED>;
-    ChainSolve j;
-    j.model = MODEL_SRUN; j.nplanes = 7; j.state0 = h->d_sr[0];
-    j.nimg = O; j.niter = p.maxiter; j.T = T;
-    j.chains = plan_chains(p.reserved[1], h->st.tiles, h->ncu, O, 2);   // at most two (image groups on two streams)
-    j.serial = (p.reserved[2] & 1) != 0; j.helper_thread = !(p.reserved[2] & 8);
-    j.bytes_per_px_iter = amap ? 192.0 : 168.0;   // read x, 6 y, f (+ 3 alpha), write x, 6 y and the 6 z
-    j.key = GraphKey{p.maxiter, T, 0, h->last_am, h->last_an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_tape, (const void*)d_tab, 0,
-                     (const void*)h->d_alpha, h->alpha_istride, 0};
-    j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
-        int step = stagger ? T / 2 : T;
-        for (int it = it0; it < it1; it += step, step = T) {
-            const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
-            SrUnrolledArgs a;
-            for (int c = 0; c < 7; ++c) { a.in[c] = h->d_sr[cur][c]; a.out[c] = h->d_sr[nxt][c]; }
-            a.f = h->d_f; a.alpha = h->d_alpha; a.tab = d_tab; a.tape = d_tape; a.plane = h->tot;
-            a.am = h->last_am; a.an = h->last_an; a.astride = h->alpha_istride;
-            a.it0 = it; a.nit = std::min(step, it1 - it);
-            a.M = M; a.N = N; a.halo = 2 * T; a.first = (it == 0) ? 1 : 0; a.img0 = lo;
-            hipLaunchKernelGGL(kern, dim3(pl.nTi, pl.nTj, hi - lo), dim3(SRUN_R * SRUN_R), sr_lds_bytes(SRUN_R, SRUN_R), st, a);
-            cur = nxt;
-        }
-        return cur;
-    };
-    return run_chains(h, p, j, result_buf);
+// What one launch of a taped solve reads besides the handle's last parameter, data and state sets ...
+struct TapedFwd {
+    bpltv_t* h;
+    WeightedPlan pl;
+    const double* tab;
+    double* tape;
+};
+// ... and one launch of a reverse sweep: the staged parameter (and weight) g, the sweep's planes S | gf | ga | g0 (the cotangent,
+// which the first launch reads in place of S[cur][0]) and gw (nullptr: not wanted), K = maxiter
+struct TapedRev {
+    bpltv_t* h;
+    WeightedPlan pl;
+    const double* tab;
+    const double* tape;
+    const GradCtx* g;
+    double* S[2][7];
+    double *gf, *ga, *g0, *gw;
+    int K;
+};
+
+// A model whose iterations can be taped and swept backwards: everything the two shared drivers (taped_denoise, taped_vjp)
+// need to know about it.  The three instances follow; a further model is one more of them and its kernels.
+struct TapedModel {
+    const char* denoise;          // stem of the solve's entry points ("_each", "_device" are appended), in messages
+    const char* vjp;              // ... of the sweep's
+    const char* tape_kind;        // "", "weighted ", ...: what a message calls its tape
+    const char* multi_name;       // what weighted_multi's message calls these entry points
+    Tape bpltv_handle::* tape;    // the handle's tape of this model
+    int tape_planes;              // doubles per pixel and iteration on the tape
+    int slices;                   // parameter slices: 1, or 3 (sum of regularisers: its defaults, PRE_SR, the d_sr state sets)
+    bool weighted;                // takes a fidelity weight w: checked and staged, gamma = min w in the step table, grad_w
+    int nplanes;                  // planes of a state set
+    double L2;                    // squared operator norm of the step table
+    int (*plan)(bpltv_t*, const bpltv_params&, int cap, WeightedPlan*);
+    int fwd_cap, rev_cap;         // deepest fusion of the taped solve / of the reverse sweep
+    Model graphs;                 // graph cache, with the GraphKey variants of the solve and of the sweep (+ 1 with grad_w)
+    int fwd_variant, rev_variant;
+    int region;                   // statistics: region_i = region_j
+    double bytes, bytes_map;      // bytes_per_px_iter of the solve with a scalar or patch parameter / with a map
+    double* bpltv_handle::* sweep;   // the reverse sweep's planes [2 sets x nplanes | gf | slices x ga | gu], allocated on first use
+    const char* sweep_name;
+    int adjoint_method;
+    bool tv_stats;                // the sweep resets every adjoint statistic and its entry points set total_ms (TV), or it
+                                  // changes adjoint_ms and adjoint_method only
+    void (*launch_fwd)(const TapedFwd&, const LaunchStep&);
+    void (*launch_rev)(const TapedRev&, const LaunchStep&);
+};
+
+void tv_launch_fwd(const TapedFwd& x, const LaunchStep& s) {
+    bpltv_t* h = x.h;
+    UnrolledArgs a;
+    a.xin = h->d_state[s.cur][0]; a.y1in = h->d_state[s.cur][1]; a.y2in = h->d_state[s.cur][2];
+    a.xout = h->d_state[s.nxt][0]; a.y1out = h->d_state[s.nxt][1]; a.y2out = h->d_state[s.nxt][2];
+    a.f = h->d_f; a.alpha = h->d_alpha; a.tab = x.tab; a.tape = x.tape; a.plane = h->tot;
+    a.am = h->last_am; a.an = h->last_an; a.istride = h->alpha_istride;
+    a.it0 = s.it; a.nit = s.nit;
+    a.M = h->M; a.N = h->N; a.halo = x.pl.T; a.first = s.first; a.img0 = s.lo;
+    hipLaunchKernelGGL(unrolled_tile_kernel, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), s.st, a);
+}
+void tv_launch_rev(const TapedRev& x, const LaunchStep& s) {   // `it` counts reverse steps: step r undoes iteration K - 1 - r
+    const GradCtx& g = *x.g;
+    UnrolledRevArgs a;
+    a.gxin = s.first ? x.g0 : x.S[s.cur][0]; a.gy1in = x.S[s.cur][1]; a.gy2in = x.S[s.cur][2];
+    a.gxout = x.S[s.nxt][0]; a.gy1out = x.S[s.nxt][1]; a.gy2out = x.S[s.nxt][2];
+    a.gf = x.gf; a.ga = x.ga; a.tape = x.tape; a.alpha = g.alpha; a.tab = x.tab; a.plane = x.h->tot;
+    a.am = g.am; a.an = g.an; a.istride = g.astride;
+    a.khi = x.K - 1 - s.it; a.nit = s.nit;
+    a.M = x.h->M; a.N = x.h->N; a.halo = x.pl.T; a.first = s.first; a.img0 = s.lo;
+    hipLaunchKernelGGL(unrolled_reverse_tile_kernel, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), s.st, a);
 }
 
-// bpltv_sumregs_unrolled_denoise(_each)(_device) on a single-device handle: unrolled_denoise_common for the three-dual model.
-// d_tape_user: the caller's tape, or nullptr for the handle's own, which grows here -- the new buffer is allocated before
-// anything changes and installed only once the parameter is accepted.  The solve is committed like bpltv_sumregs_denoise's.
-int sr_unrolled_denoise_common(bpltv_t* h, const double* alpha, bool dev, int am, int an, const bpltv_params* pp, double* d_tape_user,
-                               double* u_out, bool each) {
-    const char* who = each ? (dev ? "bpltv_sumregs_unrolled_denoise_each_device" : "bpltv_sumregs_unrolled_denoise_each")
-                           : (dev ? "bpltv_sumregs_unrolled_denoise_device" : "bpltv_sumregs_unrolled_denoise");
+void weighted_launch_fwd(const TapedFwd& x, const LaunchStep& s) {   // with the handle's d_w / w_wo
+    bpltv_t* h = x.h;
+    WeightedUnrolledArgs a;
+    a.xin = h->d_state[s.cur][0]; a.y1in = h->d_state[s.cur][1]; a.y2in = h->d_state[s.cur][2];
+    a.xout = h->d_state[s.nxt][0]; a.y1out = h->d_state[s.nxt][1]; a.y2out = h->d_state[s.nxt][2];
+    a.f = h->d_f; a.w = h->d_w; a.alpha = h->d_alpha; a.tab = x.tab; a.tape = x.tape; a.plane = h->tot;
+    a.wstride = h->w_wo > 1 ? h->npx : 0;
+    a.am = h->last_am; a.an = h->last_an;
+    a.it0 = s.it; a.nit = s.nit;
+    a.M = h->M; a.N = h->N; a.halo = x.pl.T; a.first = s.first; a.img0 = s.lo;
+    hipLaunchKernelGGL(weighted_unrolled_tile_kernel, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), s.st, a);
+}
+void weighted_launch_rev(const TapedRev& x, const LaunchStep& s) {   // the resident f is read for gw only
+    const GradCtx& g = *x.g;
+    WeightedUnrolledRevArgs a;
+    a.gxin = s.first ? x.g0 : x.S[s.cur][0]; a.gy1in = x.S[s.cur][1]; a.gy2in = x.S[s.cur][2];
+    a.gxout = x.S[s.nxt][0]; a.gy1out = x.S[s.nxt][1]; a.gy2out = x.S[s.nxt][2];
+    a.gf = x.gf; a.ga = x.ga; a.gw = x.gw; a.tape = x.tape; a.f = x.h->d_f; a.w = g.w; a.alpha = g.alpha; a.tab = x.tab;
+    a.plane = x.h->tot; a.wstride = g.wo > 1 ? x.h->npx : 0;
+    a.am = g.am; a.an = g.an;
+    a.khi = x.K - 1 - s.it; a.nit = s.nit;
+    a.M = x.h->M; a.N = x.h->N; a.halo = x.pl.T; a.first = s.first; a.img0 = s.lo;
+    hipLaunchKernelGGL(weighted_unrolled_reverse_tile_kernel, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), s.st, a);
+}
+
+void sr_launch_fwd(const TapedFwd& x, const LaunchStep& s) {   // alpha_istride != 0: one parameter block per image
+    bpltv_t* h = x.h;
+    SrUnrolledArgs a;
+    for (int c = 0; c < 7; ++c) { a.in[c] = h->d_sr[s.cur][c]; a.out[c] = h->d_sr[s.nxt][c]; }
+    a.f = h->d_f; a.alpha = h->d_alpha; a.tab = x.tab; a.tape = x.tape; a.plane = h->tot;
+    a.am = h->last_am; a.an = h->last_an; a.astride = h->alpha_istride;
+    a.it0 = s.it; a.nit = s.nit;
+    a.M = h->M; a.N = h->N; a.halo = 2 * x.pl.T; a.first = s.first; a.img0 = s.lo;
+    void (*kern)(SrUnrolledArgs) = h->alpha_istride != 0 ? &sr_unrolled_tile_kernel<SR_EACH> : &sr_unrolled_tile_kernel<SR_SHARED>;
+    hipLaunchKernelGGL(kern, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(SRUN_R * SRUN_R), sr_lds_bytes(SRUN_R, SRUN_R), s.st, a);
+}
+void sr_launch_rev(const TapedRev& x, const LaunchStep& s) {
+    const GradCtx& g = *x.g;
+    SrUnrolledRevArgs a;
+    for (int c = 0; c < 7; ++c) { a.in[c] = x.S[s.cur][c]; a.out[c] = x.S[s.nxt][c]; }
+    if (s.first) a.in[0] = x.g0;
+    a.gf = x.gf; a.ga = x.ga; a.tape = x.tape; a.alpha = g.alpha; a.tab = x.tab; a.plane = x.h->tot;
+    a.am = g.am; a.an = g.an; a.astride = g.astride;
+    a.khi = x.K - 1 - s.it; a.nit = s.nit;
+    a.M = x.h->M; a.N = x.h->N; a.halo = 2 * x.pl.T; a.first = s.first; a.img0 = s.lo;
+    void (*kern)(SrUnrolledRevArgs) = g.each ? &sr_unrolled_reverse_tile_kernel<SR_EACH> : &sr_unrolled_reverse_tile_kernel<SR_SHARED>;
+    hipLaunchKernelGGL(kern, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(SRUN_R * SRUN_R), sr_lds_bytes(SRUN_R, SRUN_R), s.st, a);
+}
+
+// bytes / bytes_map: read x, y1, y2, f (+ alpha), write x, y1, y2 and z1, z2
+const TapedModel kTapedTV = [] {
+    TapedModel m{};
+    m.denoise = "bpltv_unrolled_denoise"; m.vjp = "unrolled_vjp"; m.tape_kind = ""; m.multi_name = "the unrolled solve";
+    m.tape = &bpltv_handle::tape; m.tape_planes = 2;
+    m.slices = 1; m.weighted = false; m.nplanes = 3; m.L2 = 8.0;
+    m.plan = unrolled_plan; m.fwd_cap = PDHG_MAX_T; m.rev_cap = UN_REV_T;
+    m.graphs = MODEL_UN; m.fwd_variant = 0; m.rev_variant = 1;
+    m.region = UN_R; m.bytes = 72.0; m.bytes_map = 80.0;
+    m.sweep = &bpltv_handle::d_unr; m.sweep_name = "reverse sweep";
+    m.adjoint_method = 7; m.tv_stats = true;
+    m.launch_fwd = tv_launch_fwd; m.launch_rev = tv_launch_rev;
+    return m;
+}();
+// ... the same, and read w and write x onto the tape as well.  The sweep runs in the TV sweep's planes.
+const TapedModel kTapedWeighted = [] {
+    TapedModel m = kTapedTV;
+    m.denoise = "bpltv_weighted_unrolled_denoise"; m.vjp = "weighted_unrolled_vjp"; m.tape_kind = "weighted ";
+    m.multi_name = "the weighted unrolled solve";
+    m.tape = &bpltv_handle::wtape; m.tape_planes = 3;
+    m.weighted = true; m.rev_cap = WUN_REV_T;
+    m.fwd_variant = 6; m.rev_variant = 7;
+    m.bytes = 88.0; m.bytes_map = 96.0;
+    m.adjoint_method = 9; m.tv_stats = false;
+    m.launch_fwd = weighted_launch_fwd; m.launch_rev = weighted_launch_rev;
+    return m;
+}();
+// ... read x, 6 y, f (+ 3 alpha), write x, 6 y and the 6 z
+const TapedModel kTapedSr = [] {
+    TapedModel m{};
+    m.denoise = "bpltv_sumregs_unrolled_denoise"; m.vjp = "sumregs_unrolled_vjp"; m.tape_kind = "sum-of-regularisers ";
+    m.multi_name = "the sum-of-regularisers unrolled solve";
+    m.tape = &bpltv_handle::srtape; m.tape_planes = 6;
+    m.slices = 3; m.weighted = false; m.nplanes = 7; m.L2 = 18.0;
+    m.plan = sr_unrolled_plan; m.fwd_cap = (SRUN_R - 1) / 4; m.rev_cap = SRUN_REV_T;
+    m.graphs = MODEL_SRUN; m.fwd_variant = 0; m.rev_variant = 1;
+    m.region = SRUN_R; m.bytes = 168.0; m.bytes_map = 192.0;
+    m.sweep = &bpltv_handle::d_srunr; m.sweep_name = "sum-of-regularisers reverse sweep";
+    m.adjoint_method = 10; m.tv_stats = false;
+    m.launch_fwd = sr_launch_fwd; m.launch_rev = sr_launch_rev;
+    return m;
+}();
+const char* const kUnrolled = kTapedTV.multi_name;   // (the tangent sweep's entry points)
+
+// The launch chains of a taped solve or of one of its sweeps: at most two (image groups on two streams)
+void taped_chains(bpltv_t* h, const bpltv_params& p, const WeightedPlan& pl, ChainSolve* j) {
+    j->nimg = h->O; j->niter = p.maxiter; j->T = pl.T;
+    j->chains = plan_chains(p.reserved[1], pl.nTi * pl.nTj * h->O, h->ncu, h->O, 2);
+    j->serial = (p.reserved[2] & 1) != 0; j->helper_thread = !(p.reserved[2] & 8);
+}
+
+// The end of a sweep through the iterations (the caller has put the last solve's statistics back): the time since ev[2] is
+// its adjoint_ms, with its adjoint_method
+int sweep_stats(bpltv_t* h, int method) {
+    HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    float ms = 0.f;
+    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
+    h->st.adjoint_ms = ms;
+    h->st.adjoint_method = method;
+    return BPLTV_OK;
+}
+
+// The taped solves on a single-device handle: bpltv_unrolled_denoise, bpltv_weighted_unrolled_denoise and
+// bpltv_sumregs_unrolled_denoise with their _each and _device forms.  maxiter taped iterations on the dataset images, in the
+// model's state sets, with d_alpha (each: O blocks, image k reads block k: upload_alpha); what the reverse sweep needs of
+// every iteration and pixel goes onto d_tape_user, or (nullptr) onto the handle's own tape of the model, which grows here.
+// The order is the contract: arguments, params, w, then the grown tape -- allocated before anything changes and installed only
+// once upload_alpha has accepted the parameter -- and only then the handle's copy of w.
+int taped_denoise(bpltv_t* h, const TapedModel& m, const double* w, int wo, const double* alpha, bool dev, int am, int an,
+                  const bpltv_params* pp, double* d_tape_user, double* u_out, bool each) {
+    const std::string name = std::string(m.denoise) + (each ? "_each" : "") + (dev ? "_device" : "");
+    const char* who = name.c_str();
+    const bool sr = m.slices == 3;
+    Tape& tape = h->*m.tape;
     WallTimer wt;
     HIPCHK(h, hipSetDevice(h->device));
     if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: bpltv_set_data has not been called", who);
-    const bpltv_params p = resolve(pp, true);
+    if (m.weighted) {
+        if (!w) return set_err(h, BPLTV_E_ARG, "%s: w is a null pointer", who);
+        if (wo != 1 && wo != h->O) return set_err(h, BPLTV_E_ARG, "%s: wo = %d: one weight plane (1) or one per image (%d)", who, wo, h->O);
+    }
+    const bpltv_params p = resolve(pp, sr);
     if (int prc = unrolled_check_params(h, p, who)) return prc;
-    SrUnrolledPlan pl;
-    if (int prc = sr_unrolled_plan(h, p, (SRUN_R - 1) / 4, &pl)) return prc;
-    if (int arc = sr_alloc(h)) return arc;
-    const size_t need = (size_t)6 * p.maxiter * h->tot;
+    WeightedPlan pl;
+    if (int prc = m.plan(h, p, m.fwd_cap, &pl)) return prc;
+    if (sr)
+        if (int arc = sr_alloc(h)) return arc;
+    const size_t nw = (size_t)wo * h->npx;
+    double wmin = 0.0;
+    int rc = m.weighted ? check_weight(h, who, w, dev, nw, &wmin) : (int)BPLTV_OK;
+    if (rc) return rc;
+    const size_t need = (size_t)m.tape_planes * p.maxiter * h->tot;
     double* grown = nullptr;
-    if (!d_tape_user && h->srtape_cap < need) {
-        const hipError_t e = hipMalloc((void**)&grown, need * sizeof(double));
+    if (!d_tape_user) {
+        const hipError_t e = tape.grow(need, &grown);
         if (e != hipSuccess) {
             (void)hipGetLastError();
             return set_err(h, e == hipErrorOutOfMemory ? BPLTV_E_NOMEM : BPLTV_E_HIP, "%s: hipMalloc of the tape (%.1f MB) failed: %s", who,
                            need * sizeof(double) / 1e6, hipGetErrorString(e));
         }
     }
-    bpltv_params q = p;   // the planner's knobs and the forward variant mean nothing here: upload_alpha's precheck sees the defaults
-    q.tile_iters = 0; q.reserved[0] = 0; q.reserved[1] = 0; q.reserved[2] = 0;
-    int rc = upload_alpha(h, alpha, dev, am, an, PRE_SR, each ? h->O : 1, &q);
+    if (m.weighted && !h->d_w) rc = alloc_all(h, {{(void**)&h->d_w, h->tot * sizeof(double)}}, "fidelity weight");
+    if (rc == BPLTV_OK) {
+        bpltv_params q = p;   // the planner's knobs and the forward variant mean nothing here: upload_alpha's precheck sees the defaults
+        q.tile_iters = 0; q.reserved[0] = 0; q.reserved[1] = 0; q.reserved[2] = 0;
+        rc = upload_alpha(h, alpha, dev, am, an, sr ? PRE_SR : PRE_TV, each ? h->O : 1, &q);
+    }
     if (rc) {
         if (grown) (void)hipFree(grown);
         return rc;
     }
-    if (grown) {
-        if (h->d_srtape) (void)hipFree(h->d_srtape);
-        h->d_srtape = grown;
-        h->srtape_cap = need;
+    tape.install(grown, need);
+    if (!d_tape_user) tape.valid = false;   // about to be overwritten
+    if (m.weighted) {
+        HIPCHK(h, hipMemcpyAsync(h->d_w, w, nw * sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
+        h->w_wo = wo;
+        h->w_min = wmin;
     }
-    if (!d_tape_user) h->srtape_valid = false;   // about to be overwritten
-    int buf = 0;
-    rc = run_sr_unrolled_pdhg(h, p, pl, d_tape_user ? d_tape_user : h->d_srtape, &buf);
+    h->has_per_image = false;
+    double* d_tab = nullptr;
+    rc = get_table(h, p, &d_tab, m.L2, 0, m.weighted ? h->w_min : 1.0);
     if (rc) return rc;
-    h->sr_result_buf = buf;
-    h->sr_has_result = true;
-    h->last_is_sr = true;
-    h->last_weighted = false;
-    if (!d_tape_user) {
-        h->srtape_valid = true;
-        h->srtape_maxiter = p.maxiter; h->srtape_am = am; h->srtape_an = an; h->srtape_accel = p.accel ? 1 : 0; h->srtape_each = each;
-        h->srtape_tau0 = p.tau0; h->srtape_sigma0 = p.sigma0; h->srtape_opnorm = p.opnorm;
+    const bool amap = (h->last_am == h->M && h->last_an == h->N) && !(h->M == 1 && h->N == 1);
+    h->st.tile_iters = pl.T; h->st.tiles = pl.nTi * pl.nTj * h->O; h->st.region_i = m.region; h->st.region_j = m.region; h->st.pdhg_variant = 0;
+    const TapedFwd x{h, pl, d_tab, d_tape_user ? d_tape_user : tape.d};
+    ChainSolve j;
+    j.model = m.graphs; j.nplanes = m.nplanes; j.state0 = sr ? h->d_sr[0] : h->d_state[0];
+    taped_chains(h, p, pl, &j);
+    j.bytes_per_px_iter = amap ? m.bytes_map : m.bytes;
+    // (istride: a per-image solve uploads into d_alpha like a shared one, and must not replay its graph, nor the reverse)
+    j.key = GraphKey{p.maxiter, pl.T, m.fwd_variant, h->last_am, h->last_an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)x.tape, (const void*)d_tab, 0,
+                     (const void*)h->d_alpha, m.weighted ? 0 : h->alpha_istride, m.weighted ? h->w_wo : 0};
+    j.enqueue = launch_loop(pl.T, [&](const LaunchStep& s) { m.launch_fwd(x, s); });
+    int buf = 0;
+    rc = run_chains(h, p, j, &buf);
+    if (rc) return rc;
+    if (sr) {   // committed like bpltv_sumregs_denoise's
+        h->sr_result_buf = buf;
+        h->sr_has_result = true;
+    } else {
+        h->result_buf = buf;
+        h->has_result = true;
     }
+    h->last_is_sr = sr;
+    h->last_weighted = m.weighted;
+    if (!d_tape_user) tape.record(p, am, an, each, m.weighted ? wo : 0, wmin);
     if (u_out) {
-        HIPCHK(h, hipMemcpyAsync(u_out, h->d_sr[buf][0], h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(u_out, sr ? h->d_sr[buf][0] : h->d_state[buf][0], h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
     h->st.total_ms = wt.ms();
     return BPLTV_OK;
 }
 
-// bpltv_sumregs_unrolled_vjp(_each)(_device) on a single-device handle: unrolled_vjp_common for the three-dual model.  d_gu and
-// the outputs live in HBM, alpha (3*am*an doubles, or O such blocks: each) on the host or (dev) in HBM; d_tape_user or the
-// handle's sum-of-regularisers tape.  The parameter is staged apart (stage_param) and the sweep runs in d_srunr, so the last
-// solve stays untouched; of the statistics only adjoint_ms and adjoint_method change.  d_grad_alpha: slice r of the shared form
-// is the sum of ga_r over the images in image order, then per patch or over everything; each: O blocks, block k image k's own.
-int sr_unrolled_vjp_common(bpltv_t* h, const double* d_tape_user, const double* alpha, bool dev, int am, int an, const bpltv_params* pp,
-                           const double* d_gu, double* d_grad_f, double* d_grad_alpha, bool each) {
-    const char* who = each ? "sumregs_unrolled_vjp_each" : "sumregs_unrolled_vjp";
-    if (!alpha || !d_gu) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
-    if (!d_grad_f && !d_grad_alpha) return set_err(h, BPLTV_E_ARG, "%s: both outputs are NULL", who);
-    const bpltv_params p0 = resolve(pp, true);
-    if (int prc = unrolled_check_params(h, p0, who)) return prc;
-    if (!d_tape_user) {
-        if (!h->srtape_valid)
-            return set_err(h, BPLTV_E_NODATA, "%s: the handle holds no sum-of-regularisers tape (bpltv_sumregs_unrolled_denoise has not run)", who);
-        if (h->srtape_maxiter != p0.maxiter || h->srtape_am != am || h->srtape_an != an || h->srtape_accel != (p0.accel ? 1 : 0) ||
-            h->srtape_tau0 != p0.tau0 || h->srtape_sigma0 != p0.sigma0 || h->srtape_opnorm != p0.opnorm)
-            return set_err(h, BPLTV_E_ARG, "%s: the handle's tape was recorded with maxiter = %d, a %dx%dx3 parameter and other steps than this call's (%d, %dx%dx3)",
-                           who, h->srtape_maxiter, h->srtape_am, h->srtape_an, p0.maxiter, am, an);
-        if (h->srtape_each != each)
-            return set_err(h, BPLTV_E_ARG, "%s: the handle's tape was recorded with %s", who,
-                           h->srtape_each ? "one parameter block per image (bpltv_sumregs_unrolled_denoise_each)"
-                                          : "one shared parameter (bpltv_sumregs_unrolled_denoise)");
-    }
-    SrUnrolledPlan pl;
-    if (int prc = sr_unrolled_plan(h, p0, SRUN_REV_T, &pl)) return prc;
+// The per-pixel, per-image parameter gradient d_ga ([slices][O][M*N]) into d_grad_alpha, slice by slice in a fixed order
+// without atomics.  Shared parameter: slice r is the sum of ga_r over the images in image order, then per patch
+// (calc_adjoint) or over everything.  each: O blocks of [slices][am*an], block k image k's own -- the plane as it is for a map,
+// image k's patch sums otherwise.
+int reduce_grad_alpha(bpltv_t* h, const double* d_ga, int slices, int am, int an, bool each, double* d_grad_alpha) {
+    const int M = h->M, N = h->N, O = h->O, sl = am * an;
     const size_t tot = h->tot, npx = h->npx;
-    if (!h->d_srunr)
-        if (int arc = alloc_all(h, {{(void**)&h->d_srunr, 19 * tot * sizeof(double)}}, "sum-of-regularisers reverse sweep")) return arc;
-    bpltv_params p;
-    GradCtx g;
-    if (int rc = stage_param(h, who, alpha, dev, am, an, 3, each, 0, pp ? pp : &p0, nullptr, 1, {{d_gu, tot, "cotangent gu"}}, &p, &g)) return rc;
-    const int M = h->M, N = h->N, O = h->O, T = pl.T, K = p.maxiter, sl = am * an;
     const bool amap = am == M && an == N && !(M == 1 && N == 1);
-    if (d_grad_alpha && !amap && !each)
-        if (int rc = ensure(h, &h->d_red, &h->red_cap, (size_t)3 * sl * O)) return rc;
-    h->has_per_image = false;
-    double* d_tab = nullptr;
-    if (int rc = get_table(h, p, &d_tab, 18.0)) return rc;
-    const double* d_tape = d_tape_user ? d_tape_user : h->d_srtape;
-    double* S[2][7];
-    for (int s = 0; s < 2; ++s)
-        for (int c = 0; c < 7; ++c) S[s][c] = h->d_srunr + (size_t)(7 * s + c) * tot;
-    double *d_gf = h->d_srunr + 14 * tot, *d_ga = h->d_srunr + 15 * tot, *d_g0 = h->d_srunr + 18 * tot;
-    void (*kern)(SrUnrolledRevArgs) = each ? &sr_unrolled_reverse_tile_kernel<SR_EACH> : &sr_unrolled_reverse_tile_kernel<SR_SHARED>;
-    const bpltv_stats_t kept = h->st;
-    HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
-    HIPCHK(h, hipMemcpyAsync(d_g0, d_gu, tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    ChainSolve j;
-    j.model = MODEL_SRUN; j.nplanes = 7; j.state0 = S[0];
-    j.nimg = O; j.niter = K; j.T = T;
-    const int tiles = pl.nTi * pl.nTj * O;
-    j.chains = plan_chains(p.reserved[1], tiles, h->ncu, O, 2);
-    j.serial = (p.reserved[2] & 1) != 0; j.helper_thread = !(p.reserved[2] & 8);
-    j.bytes_per_px_iter = 0.0;   // (the driver's solve statistics are not this call's: `kept` goes back below)
-    j.key = GraphKey{K, T, 1, am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_tape, (const void*)d_tab, 0, (const void*)g.alpha, g.astride, 0};
-    j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
-        int step = stagger ? T / 2 : T;
-        for (int it = it0; it < it1; it += step, step = T) {   // `it` counts reverse steps: step r undoes iteration K - 1 - r
-            const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
-            SrUnrolledRevArgs a;
-            for (int c = 0; c < 7; ++c) { a.in[c] = S[cur][c]; a.out[c] = S[nxt][c]; }
-            if (it == 0) a.in[0] = d_g0;
-            a.gf = d_gf; a.ga = d_ga; a.tape = d_tape; a.alpha = g.alpha; a.tab = d_tab; a.plane = tot;
-            a.am = am; a.an = an; a.astride = g.astride;
-            a.khi = K - 1 - it; a.nit = std::min(step, it1 - it);
-            a.M = M; a.N = N; a.halo = 2 * T; a.first = (it == 0) ? 1 : 0; a.img0 = lo;
-            hipLaunchKernelGGL(kern, dim3(pl.nTi, pl.nTj, hi - lo), dim3(SRUN_R * SRUN_R), sr_lds_bytes(SRUN_R, SRUN_R), st, a);
-            cur = nxt;
-        }
-        return cur;
-    };
-    int buf = 0;
-    const int rc = run_chains(h, p, j, &buf);
-    h->st = kept;
-    if (rc) return rc;
-    if (d_grad_f)
-        hipLaunchKernelGGL(unrolled_gradf_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, d_gf, S[buf][0], tot, d_grad_f);
-    for (int r = 0; r < 3 && d_grad_alpha; ++r) {   // slice by slice, the reductions of unrolled_vjp_common (fixed order, no atomics)
+    for (int r = 0; r < slices; ++r) {
         const double* ga_r = d_ga + (size_t)r * tot;
-        if (each && amap) {          // block k = [3][M*N] of image k: the plane of the slice, image by image
-            HIPCHK(h, hipMemcpy2DAsync(d_grad_alpha + (size_t)r * npx, 3 * npx * sizeof(double), ga_r, npx * sizeof(double), npx * sizeof(double), O,
+        if (each && amap && slices == 1) {
+            HIPCHK(h, hipMemcpyAsync(d_grad_alpha, ga_r, tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        } else if (each && amap) {   // the plane of the slice, image by image
+            HIPCHK(h, hipMemcpy2DAsync(d_grad_alpha + (size_t)r * npx, slices * npx * sizeof(double), ga_r, npx * sizeof(double), npx * sizeof(double), O,
                                        hipMemcpyDeviceToDevice, h->stream));
-        } else if (each) {           // image k's patch sums into block k, slice r
-            hipLaunchKernelGGL(patch_sum_kernel, dim3(sl, O), dim3(256), 0, h->stream, ga_r, M, N, O, am, an, 1, 3 * sl, d_grad_alpha + (size_t)r * sl);
-        } else if (amap) {           // the per-pixel sums over the images, in image order
+        } else if (each) {
+            hipLaunchKernelGGL(patch_sum_kernel, dim3(sl, O), dim3(256), 0, h->stream, ga_r, M, N, O, am, an, 1, slices * sl, d_grad_alpha + (size_t)r * sl);
+        } else if (amap) {
             hipLaunchKernelGGL(map_sum_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, ga_r, npx, O, d_grad_alpha + (size_t)r * npx);
-        } else {                     // per image and patch, then over the images in image order
+        } else {
             double* red = h->d_red + (size_t)r * sl * O;
             hipLaunchKernelGGL(patch_sum_kernel, dim3(sl, O), dim3(256), 0, h->stream, ga_r, M, N, O, am, an, O, 1, red);
             hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, h->stream, red, O, sl, 1.0, d_grad_alpha + (size_t)r * sl, (double*)nullptr);
         }
     }
+    return BPLTV_OK;
+}
+
+// The reverse sweeps on a single-device handle: bpltv_unrolled_vjp, bpltv_weighted_unrolled_vjp and bpltv_sumregs_unrolled_vjp
+// with their _each and _device forms.  d_gu and the outputs live in HBM; alpha (slices*am*an doubles, or O such blocks: each)
+// and the weighted model's w (every entry >= 0) on the host or (dev) in HBM; d_tape_user or the handle's tape of the model,
+// which must have been recorded by this call's solve.  Parameter and weight are staged apart (stage_param) and the sweep runs
+// in planes of its own, so the last solve stays untouched; the solve statistics are put back after the shared driver has run
+// the sweep.  The step table is the solve's (weighted: gamma = min w), held fixed.  d_grad_w (weighted only) needs the resident f.
+int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const double* w, int wo, const double* alpha, bool dev, int am,
+              int an, const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alpha, double* d_grad_w, bool each) {
+    const std::string name = std::string(m.vjp) + (each ? "_each" : "");
+    const char* who = name.c_str();
+    const bool sr = m.slices == 3;
+    const Tape& tape = h->*m.tape;
+    if (!alpha || !d_gu || (m.weighted && !w)) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
+    if (!d_grad_f && !d_grad_alpha && !d_grad_w) return set_err(h, BPLTV_E_ARG, "%s: %s outputs are NULL", who, m.weighted ? "all three" : "both");
+    if (m.weighted && wo != 1 && wo != h->O)
+        return set_err(h, BPLTV_E_ARG, "%s: wo = %d: one weight plane (1) or one per image (%d)", who, wo, h->O);
+    const bpltv_params p0 = resolve(pp, sr);
+    if (int prc = unrolled_check_params(h, p0, who)) return prc;
+    if (d_grad_w && !h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: grad_w reads the resident f: bpltv_set_data has not been called", who);
+    if (!d_tape_user) {
+        if (!tape.valid) return set_err(h, BPLTV_E_NODATA, "%s: the handle holds no %stape (%s has not run)", who, m.tape_kind, m.denoise);
+        if (!tape.made_with(p0, am, an, m.weighted ? wo : 0))
+            return set_err(h, BPLTV_E_ARG, "%s: the handle's tape was recorded with maxiter = %d, a %dx%d parameter, wo = %d and other steps than this call's (%d, %dx%d, wo = %d)",
+                           who, tape.maxiter, tape.am, tape.an, tape.wo, p0.maxiter, am, an, m.weighted ? wo : 0);
+        if (tape.each != each)
+            return set_err(h, BPLTV_E_ARG, "%s: the handle's tape was recorded with one %s (%s%s)", who,
+                           tape.each ? "parameter block per image" : "shared parameter", m.denoise, tape.each ? "_each" : "");
+    }
+    WeightedPlan pl;
+    if (int prc = m.plan(h, p0, m.rev_cap, &pl)) return prc;
+    const size_t tot = h->tot, npx = h->npx;
+    const int np = m.nplanes;
+    double*& d_ws = h->*m.sweep;
+    if (!d_ws)
+        if (int arc = alloc_all(h, {{(void**)&d_ws, (2 * np + 2 + m.slices) * tot * sizeof(double)}}, m.sweep_name)) return arc;
+    if (d_grad_w && !h->d_unr_gw)
+        if (int arc = alloc_all(h, {{(void**)&h->d_unr_gw, tot * sizeof(double)}}, "reverse sweep (weight gradient)")) return arc;
+    bpltv_params p;
+    GradCtx g;
+    if (int rc = stage_param(h, who, alpha, dev, am, an, m.slices, each, 0, &p0, m.weighted ? w : nullptr, m.weighted ? wo : 1,
+                             {{d_gu, tot, "cotangent gu"}}, &p, &g, false))
+        return rc;
+    if (m.weighted && !d_tape_user && tape.gamma != g.w_min)
+        return set_err(h, BPLTV_E_ARG, "%s: the handle's tape was recorded with gamma = min w = %g, this call's w has %g", who, tape.gamma, g.w_min);
+    const bool amap = am == h->M && an == h->N && !(h->M == 1 && h->N == 1);
+    if (d_grad_alpha && !amap && !each)
+        if (int rc = ensure(h, &h->d_red, &h->red_cap, (size_t)m.slices * am * an * h->O)) return rc;
+    h->has_per_image = false;
+    double* d_tab = nullptr;
+    if (int rc = get_table(h, p, &d_tab, m.L2, 0, m.weighted ? g.w_min : 1.0)) return rc;
+    TapedRev x{h, pl, d_tab, d_tape_user ? d_tape_user : tape.d, &g, {}, d_ws + (size_t)2 * np * tot, d_ws + (size_t)(2 * np + 1) * tot,
+               d_ws + (size_t)(2 * np + 1 + m.slices) * tot, d_grad_w ? h->d_unr_gw : nullptr, p.maxiter};
+    for (int s = 0; s < 2; ++s)
+        for (int c = 0; c < np; ++c) x.S[s][c] = d_ws + (size_t)(np * s + c) * tot;
+    const bpltv_stats_t kept = h->st;
+    HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
+    HIPCHK(h, hipMemcpyAsync(x.g0, d_gu, tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    ChainSolve j;
+    j.model = m.graphs; j.nplanes = np; j.state0 = x.S[0];
+    taped_chains(h, p, pl, &j);
+    j.bytes_per_px_iter = 0.0;   // (the driver's solve statistics are not this call's: `kept` goes back below)
+    j.key = GraphKey{p.maxiter, pl.T, m.rev_variant + (x.gw ? 1 : 0), am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)x.tape, (const void*)d_tab, 0,
+                     (const void*)g.alpha, m.weighted ? 0 : g.astride, m.weighted ? wo : 0};
+    j.enqueue = launch_loop(pl.T, [&](const LaunchStep& s) { m.launch_rev(x, s); });
+    int buf = 0;
+    const int rc = run_chains(h, p, j, &buf);
+    h->st = kept;
+    if (rc) return rc;
+    if (d_grad_f)
+        hipLaunchKernelGGL(unrolled_gradf_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, x.gf, x.S[buf][0], tot, d_grad_f);
+    if (d_grad_alpha)
+        if (int rrc = reduce_grad_alpha(h, x.ga, m.slices, am, an, each, d_grad_alpha)) return rrc;
+    if (d_grad_w && wo > 1) {   // per image: the plane as it is; one plane: the sum over the images in image order
+        HIPCHK(h, hipMemcpyAsync(d_grad_w, x.gw, tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+    } else if (d_grad_w) {
+        hipLaunchKernelGGL(map_sum_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, x.gw, npx, h->O, d_grad_w);
+    }
     HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
-    h->st.adjoint_ms = ms;
-    h->st.adjoint_method = 10;
+    if (int src = sweep_stats(h, m.adjoint_method)) return src;
+    if (m.tv_stats) {
+        h->st.reg_gradient_used = 0;
+        h->st.adjoint_attempts = 1;
+        h->st.adjoint_chunks = 1;
+        h->st.hb_sync = 0;
+        h->st.kappa_used = 0.0;
+        h->st.adjoint_residual = 0.0;
+        h->st.adjoint_residual_raw = 0.0;
+    }
     return BPLTV_OK;
 }
 
@@ -4009,7 +3819,7 @@ int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool d
         return rc;
     double* d_tab = nullptr;
     if (int rc = get_table(h, p, &d_tab, 8.0, 0)) return rc;
-    const int M = h->M, N = h->N, O = h->O, T = pl.T, K = p.maxiter;
+    const int M = h->M, N = h->N, T = pl.T, K = p.maxiter;
     double* S[2][6];
     for (int s = 0; s < 2; ++s)
         for (int c = 0; c < 6; ++c) S[s][c] = h->d_ujv + (size_t)(6 * s + c) * tot;
@@ -4017,29 +3827,20 @@ int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool d
     const bpltv_stats_t kept = h->st;
     ChainSolve j;
     j.model = MODEL_UN; j.nplanes = 6; j.state0 = S[0];
-    j.nimg = O; j.niter = K; j.T = T;
-    const int tiles = pl.nTi * pl.nTj * O;
-    j.chains = plan_chains(p.reserved[1], tiles, h->ncu, O, 2);
-    j.serial = (p.reserved[2] & 1) != 0; j.helper_thread = !(p.reserved[2] & 8);
+    taped_chains(h, p, pl, &j);
     j.bytes_per_px_iter = 0.0;   // (the driver's solve statistics are not this call's: `kept` goes back below)
     // variant 2 ... 5: a tangent sweep, by which tangents it reads (0 = taped solve, 1 = reverse sweep)
     j.key = GraphKey{K, T, 2 + (d_df ? 1 : 0) + (d_dalpha ? 2 : 0), am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)h->d_ujv,
                      (const void*)d_tab, 0, (const void*)g.alpha, g.astride, 0};
-    j.enqueue = [&](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
-        int step = stagger ? T / 2 : T;
-        for (int it = it0; it < it1; it += step, step = T) {
-            const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
-            UnrolledJvpArgs a;
-            for (int c = 0; c < 6; ++c) { a.in[c] = S[cur][c]; a.out[c] = S[nxt][c]; }
-            a.f = h->d_f; a.df = d_df ? d_dfc : nullptr; a.alpha = g.alpha; a.dalpha = d_dalpha ? d_dac : nullptr; a.tab = d_tab;
-            a.am = am; a.an = an; a.istride = g.astride;
-            a.it0 = it; a.nit = std::min(step, it1 - it);
-            a.M = M; a.N = N; a.halo = T; a.first = (it == 0) ? 1 : 0; a.img0 = lo;
-            hipLaunchKernelGGL(unrolled_jvp_tile_kernel, dim3(pl.nTi, pl.nTj, hi - lo), dim3(UN_R * UN_R), unrolled_jvp_lds_bytes(), st, a);
-            cur = nxt;
-        }
-        return cur;
-    };
+    j.enqueue = launch_loop(T, [&](const LaunchStep& s) {
+        UnrolledJvpArgs a;
+        for (int c = 0; c < 6; ++c) { a.in[c] = S[s.cur][c]; a.out[c] = S[s.nxt][c]; }
+        a.f = h->d_f; a.df = d_df ? d_dfc : nullptr; a.alpha = g.alpha; a.dalpha = d_dalpha ? d_dac : nullptr; a.tab = d_tab;
+        a.am = am; a.an = an; a.istride = g.astride;
+        a.it0 = s.it; a.nit = s.nit;
+        a.M = M; a.N = N; a.halo = T; a.first = s.first; a.img0 = s.lo;
+        hipLaunchKernelGGL(unrolled_jvp_tile_kernel, dim3(pl.nTi, pl.nTj, s.hi - s.lo), dim3(UN_R * UN_R), unrolled_jvp_lds_bytes(), s.st, a);
+    });
     int rc = hipEventRecord(h->ev[2], h->stream) == hipSuccess ? (int)BPLTV_OK : set_err(h, BPLTV_E_HIP, "%s: hipEventRecord failed", who);
     int buf = 0;
     for (int d = 0; d < ndir && rc == BPLTV_OK; ++d) {
@@ -4055,12 +3856,7 @@ int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool d
     h->st = kept;
     if (rc) return rc;
     if (d_u) HIPCHK(h, hipMemcpyAsync(d_u, S[buf][0], tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
-    h->st.adjoint_ms = ms;
-    h->st.adjoint_method = 8;
+    if (int src = sweep_stats(h, 8)) return src;
     if (x_res) *x_res = S[buf][0];
     return BPLTV_OK;
 }
@@ -4193,9 +3989,10 @@ int bpltv_destroy(bpltv_t* h) {
     if (h->f32_sweep_alpha) (void)hipFree(h->f32_sweep_alpha);
     void* ptrs[] = {h->d_ubar, h->d_f, h->d_alpha, h->d_sweep_alpha, h->d_partial, h->d_red, h->d_perimg, h->d_scalar, h->d_coef,
                     h->d_band4, h->d_bcr, h->d_L, h->d_invF, h->d_invB, h->d_L1, h->d_dump, h->d_Lm, h->d_spill, h->d_p, h->d_r, h->d_gpix, h->d_resn, h->d_fail, h->d_u2, h->d_ubar2,
-                    h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres, h->d_w, h->d_wst, h->d_tape, h->d_unr, h->d_ujv, h->d_wtape, h->d_unr_gw, h->d_srtape, h->d_srunr};
+                    h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres, h->d_w, h->d_wst, h->d_unr, h->d_ujv, h->d_unr_gw, h->d_srunr};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
+    for (Tape* t : {&h->tape, &h->wtape, &h->srtape}) t->release();
     for (int s = 0; s < 2; ++s)
         for (int c = 0; c < 3; ++c) {
             if (h->d_state[s][c]) (void)hipFree(h->d_state[s][c]);
@@ -4436,218 +4233,39 @@ int bpltv_weighted_vjp_device(bpltv_t* h, const double* d_u, const double* d_f, 
     return BPLTV_OK;
 }
 
-int bpltv_unrolled_tape_doubles(bpltv_t* h, const bpltv_params* pp, unsigned long long* n_out) {
+// The taped solves and their sweeps (TV, weighted, sum of regularisers: TapedModel): one helper per kind behind the entry points
+static int tape_doubles_entry(bpltv_t* h, const TapedModel& m, const char* what, const bpltv_params* pp, unsigned long long* n_out) {
     if (!h) return BPLTV_E_ARG;
-    if (!n_out) return set_err(h, BPLTV_E_ARG, "bpltv_unrolled_tape_doubles: null pointer");
-    const bpltv_params p = resolve(pp);
-    if (p.maxiter < 1) return set_err(h, BPLTV_E_ARG, "bpltv_unrolled_tape_doubles: maxiter = %d (at least one iteration)", p.maxiter);
-    *n_out = 2ull * (unsigned long long)p.maxiter * (unsigned long long)h->M * h->N * h->O;
+    if (!n_out) return set_err(h, BPLTV_E_ARG, "%s: null pointer", what);
+    const bpltv_params p = resolve(pp, m.slices == 3);
+    if (p.maxiter < 1) return set_err(h, BPLTV_E_ARG, "%s: maxiter = %d (at least one iteration)", what, p.maxiter);
+    *n_out = (unsigned long long)m.tape_planes * (unsigned long long)p.maxiter * (unsigned long long)h->M * h->N * h->O;
     return BPLTV_OK;
 }
 
-int bpltv_unrolled_denoise(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, double* u_out) {
+static int taped_denoise_entry(bpltv_t* h, const TapedModel& m, const char* what, const double* w, int wo, const double* alpha, bool dev,
+                               int am, int an, const bpltv_params* pp, double* d_tape, double* u_out, bool each) {
     if (!h) return BPLTV_E_ARG;
     if (h->multi)
-        return weighted_multi(h, "bpltv_unrolled_denoise", true, [&](bpltv_t* c) { return bpltv_unrolled_denoise(c, alpha, am, an, pp, u_out); }, kUnrolled);
-    return unrolled_denoise_common(h, alpha, false, am, an, pp, nullptr, u_out);
+        return weighted_multi(h, what, true, [&](bpltv_t* c) { return taped_denoise_entry(c, m, what, w, wo, alpha, dev, am, an, pp, d_tape, u_out, each); },
+                              m.multi_name);
+    return taped_denoise(h, m, w, wo, alpha, dev, am, an, pp, d_tape, u_out, each);
 }
 
-int bpltv_unrolled_denoise_device(bpltv_t* h, const double* d_alpha, int am, int an, const bpltv_params* pp, double* d_tape) {
-    if (!h) return BPLTV_E_ARG;
-    if (h->multi)
-        return weighted_multi(h, "bpltv_unrolled_denoise_device", true, [&](bpltv_t* c) { return bpltv_unrolled_denoise_device(c, d_alpha, am, an, pp, d_tape); }, kUnrolled);
-    return unrolled_denoise_common(h, d_alpha, true, am, an, pp, d_tape, nullptr);
-}
-
-// bpltv_unrolled_denoise with one parameter block per image: upload_alpha with O blocks, after which the taped kernel and the
-// gap kernels address block k for image k (h->alpha_istride); the tape remembers it (tape_each).
-int bpltv_unrolled_denoise_each(bpltv_t* h, const double* alphas, int am, int an, const bpltv_params* pp, double* u_out) {
-    if (!h) return BPLTV_E_ARG;
-    if (h->multi)
-        return weighted_multi(h, "bpltv_unrolled_denoise_each", true, [&](bpltv_t* c) { return bpltv_unrolled_denoise_each(c, alphas, am, an, pp, u_out); }, kUnrolled);
-    return unrolled_denoise_common(h, alphas, false, am, an, pp, nullptr, u_out, true);
-}
-
-int bpltv_unrolled_denoise_each_device(bpltv_t* h, const double* d_alphas, int am, int an, const bpltv_params* pp, double* d_tape) {
-    if (!h) return BPLTV_E_ARG;
-    if (h->multi)
-        return weighted_multi(h, "bpltv_unrolled_denoise_each_device", true, [&](bpltv_t* c) { return bpltv_unrolled_denoise_each_device(c, d_alphas, am, an, pp, d_tape); }, kUnrolled);
-    return unrolled_denoise_common(h, d_alphas, true, am, an, pp, d_tape, nullptr, true);
-}
-
-// bpltv_unrolled_vjp and bpltv_unrolled_vjp_each on a single-device handle: the host arrays staged around unrolled_vjp_common;
-// slices = 3: bpltv_sumregs_unrolled_vjp(_each) around sr_unrolled_vjp_common
-static int unrolled_vjp_host(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, const double* gu,
-                             double* grad_f_out, double* grad_alpha_out, bool each, int slices = 1) {
-    if (!gu || !alpha) return set_err(h, BPLTV_E_ARG, "unrolled_vjp: null pointer");
-    if (!grad_f_out && !grad_alpha_out) return set_err(h, BPLTV_E_ARG, "unrolled_vjp: both outputs are NULL");
+// The host forms of the sweeps on a single-device handle: the host arrays staged around taped_vjp, on the handle's tape
+static int taped_vjp_host(bpltv_t* h, const TapedModel& m, const double* w, int wo, const double* alpha, int am, int an,
+                          const bpltv_params* pp, const double* gu, double* grad_f_out, double* grad_alpha_out, double* grad_w_out, bool each) {
+    const char* who = m.slices == 3 ? "unrolled_vjp" : m.vjp;   // (what the messages of these checks have always said)
+    if (!gu || !alpha || (m.weighted && !w)) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
+    if (!grad_f_out && !grad_alpha_out && !grad_w_out)
+        return set_err(h, BPLTV_E_ARG, "%s: %s outputs are NULL", who, m.weighted ? "all three" : "both");
+    if (m.weighted && wo != 1 && wo != h->O)
+        return set_err(h, BPLTV_E_ARG, "%s: wo = %d: one weight plane (1) or one per image (%d)", who, wo, h->O);
     if (am < 1 || an < 1 || am > h->M || an > h->N)
-        return set_err(h, BPLTV_E_ARG, "unrolled_vjp: parameter shape %dx%d (image %dx%d)", am, an, h->M, h->N);
+        return set_err(h, BPLTV_E_ARG, "%s: parameter shape %dx%d (image %dx%d)", who, am, an, h->M, h->N);
     WallTimer wt;
     HIPCHK(h, hipSetDevice(h->device));
-    if (!h->d_u2) {
-        HIPCHK(h, hipMalloc((void**)&h->d_u2, h->tot * sizeof(double)));
-        HIPCHK(h, hipMalloc((void**)&h->d_ubar2, h->tot * sizeof(double)));
-    }
-    if (grad_f_out && !h->d_gf2) HIPCHK(h, hipMalloc((void**)&h->d_gf2, h->tot * sizeof(double)));
-    HIPCHK(h, hipMemcpyAsync(h->d_ubar2, gu, h->tot * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    const size_t P = (size_t)slices * am * an * (each ? h->O : 1);
-    int rc = ensure(h, &h->d_vjp, &h->vjp_cap, 4 + 2 * P);
-    if (rc) return rc;
-    double* d_ga = grad_alpha_out ? h->d_vjp + 4 + P : nullptr;
-    rc = slices == 3 ? sr_unrolled_vjp_common(h, nullptr, alpha, false, am, an, pp, h->d_ubar2, grad_f_out ? h->d_gf2 : nullptr, d_ga, each)
-                     : unrolled_vjp_common(h, nullptr, alpha, false, am, an, pp, h->d_ubar2, grad_f_out ? h->d_gf2 : nullptr, d_ga, each);
-    if (rc) return rc;
-    if (grad_f_out) HIPCHK(h, hipMemcpyAsync(grad_f_out, h->d_gf2, h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    if (grad_alpha_out) HIPCHK(h, hipMemcpyAsync(grad_alpha_out, d_ga, sizeof(double) * P, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    if (slices != 3) h->st.total_ms = wt.ms();   // (the sum-of-regularisers form changes adjoint_ms and adjoint_method only)
-    return BPLTV_OK;
-}
-
-int bpltv_unrolled_vjp(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, const double* gu,
-                       double* grad_f_out, double* grad_alpha_out) {
-    if (!h) return BPLTV_E_ARG;
-    if (h->multi)
-        return weighted_multi(h, "bpltv_unrolled_vjp", false, [&](bpltv_t* c) { return bpltv_unrolled_vjp(c, alpha, am, an, pp, gu, grad_f_out, grad_alpha_out); }, kUnrolled);
-    return unrolled_vjp_host(h, alpha, am, an, pp, gu, grad_f_out, grad_alpha_out, false);
-}
-
-int bpltv_unrolled_vjp_each(bpltv_t* h, const double* alphas, int am, int an, const bpltv_params* pp, const double* gu,
-                            double* grad_f_out, double* grad_alphas_out) {
-    if (!h) return BPLTV_E_ARG;
-    if (h->multi)
-        return weighted_multi(h, "bpltv_unrolled_vjp_each", false, [&](bpltv_t* c) { return bpltv_unrolled_vjp_each(c, alphas, am, an, pp, gu, grad_f_out, grad_alphas_out); }, kUnrolled);
-    return unrolled_vjp_host(h, alphas, am, an, pp, gu, grad_f_out, grad_alphas_out, true);
-}
-
-int bpltv_unrolled_vjp_each_device(bpltv_t* h, const double* d_tape, const double* d_alphas, int am, int an, const bpltv_params* pp,
-                                   const double* d_gu, double* d_grad_f, double* d_grad_alphas) {
-    if (!h) return BPLTV_E_ARG;
-    if (h->multi)
-        return weighted_multi(h, "bpltv_unrolled_vjp_each_device", false, [&](bpltv_t* c) {
-            return bpltv_unrolled_vjp_each_device(c, d_tape, d_alphas, am, an, pp, d_gu, d_grad_f, d_grad_alphas);
-        }, kUnrolled);
-    WallTimer wt;
-    HIPCHK(h, hipSetDevice(h->device));
-    const int rc = unrolled_vjp_common(h, d_tape, d_alphas, true, am, an, pp, d_gu, d_grad_f, d_grad_alphas, true);
-    if (rc) return rc;
-    h->st.total_ms = wt.ms();
-    return BPLTV_OK;
-}
-
-int bpltv_unrolled_vjp_device(bpltv_t* h, const double* d_tape, const double* d_alpha, int am, int an, const bpltv_params* pp,
-                              const double* d_gu, double* d_grad_f, double* d_grad_alpha) {
-    if (!h) return BPLTV_E_ARG;
-    if (h->multi)
-        return weighted_multi(h, "bpltv_unrolled_vjp_device", false, [&](bpltv_t* c) {
-            return bpltv_unrolled_vjp_device(c, d_tape, d_alpha, am, an, pp, d_gu, d_grad_f, d_grad_alpha);
-        }, kUnrolled);
-    WallTimer wt;
-    HIPCHK(h, hipSetDevice(h->device));
-    const int rc = unrolled_vjp_common(h, d_tape, d_alpha, true, am, an, pp, d_gu, d_grad_f, d_grad_alpha);
-    if (rc) return rc;
-    h->st.total_ms = wt.ms();
-    return BPLTV_OK;
-}
-
-// The sum-of-regularisers forms (sumregs_unrolled_kernels.hpp): one pair of common functions behind the nine entry points
-int bpltv_sumregs_unrolled_tape_doubles(bpltv_t* h, const bpltv_params* pp, unsigned long long* n_out) {
-    if (!h) return BPLTV_E_ARG;
-    if (!n_out) return set_err(h, BPLTV_E_ARG, "bpltv_sumregs_unrolled_tape_doubles: null pointer");
-    const bpltv_params p = resolve(pp, true);
-    if (p.maxiter < 1) return set_err(h, BPLTV_E_ARG, "bpltv_sumregs_unrolled_tape_doubles: maxiter = %d (at least one iteration)", p.maxiter);
-    *n_out = 6ull * (unsigned long long)p.maxiter * (unsigned long long)h->M * h->N * h->O;
-    return BPLTV_OK;
-}
-
-static int sr_unrolled_denoise_entry(bpltv_t* h, const char* what, const double* alpha, bool dev, int am, int an, const bpltv_params* pp,
-                                     double* d_tape, double* u_out, bool each) {
-    if (!h) return BPLTV_E_ARG;
-    if (h->multi)
-        return weighted_multi(h, what, true, [&](bpltv_t* c) { return sr_unrolled_denoise_entry(c, what, alpha, dev, am, an, pp, d_tape, u_out, each); }, kSrUnrolled);
-    return sr_unrolled_denoise_common(h, alpha, dev, am, an, pp, d_tape, u_out, each);
-}
-
-int bpltv_sumregs_unrolled_denoise(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, double* u_out) {
-    return sr_unrolled_denoise_entry(h, "bpltv_sumregs_unrolled_denoise", alpha, false, am, an, pp, nullptr, u_out, false);
-}
-int bpltv_sumregs_unrolled_denoise_device(bpltv_t* h, const double* d_alpha, int am, int an, const bpltv_params* pp, double* d_tape) {
-    return sr_unrolled_denoise_entry(h, "bpltv_sumregs_unrolled_denoise_device", d_alpha, true, am, an, pp, d_tape, nullptr, false);
-}
-int bpltv_sumregs_unrolled_denoise_each(bpltv_t* h, const double* alphas, int am, int an, const bpltv_params* pp, double* u_out) {
-    return sr_unrolled_denoise_entry(h, "bpltv_sumregs_unrolled_denoise_each", alphas, false, am, an, pp, nullptr, u_out, true);
-}
-int bpltv_sumregs_unrolled_denoise_each_device(bpltv_t* h, const double* d_alphas, int am, int an, const bpltv_params* pp, double* d_tape) {
-    return sr_unrolled_denoise_entry(h, "bpltv_sumregs_unrolled_denoise_each_device", d_alphas, true, am, an, pp, d_tape, nullptr, true);
-}
-
-static int sr_unrolled_vjp_entry(bpltv_t* h, const char* what, bool dev, const double* d_tape, const double* alpha, int am, int an,
-                                 const bpltv_params* pp, const double* gu, double* grad_f, double* grad_alpha, bool each) {
-    if (!h) return BPLTV_E_ARG;
-    if (h->multi)
-        return weighted_multi(h, what, false, [&](bpltv_t* c) { return sr_unrolled_vjp_entry(c, what, dev, d_tape, alpha, am, an, pp, gu, grad_f, grad_alpha, each); }, kSrUnrolled);
-    if (!dev) return unrolled_vjp_host(h, alpha, am, an, pp, gu, grad_f, grad_alpha, each, 3);
-    HIPCHK(h, hipSetDevice(h->device));
-    return sr_unrolled_vjp_common(h, d_tape, alpha, true, am, an, pp, gu, grad_f, grad_alpha, each);
-}
-
-int bpltv_sumregs_unrolled_vjp(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, const double* gu,
-                               double* grad_f_out, double* grad_alpha_out) {
-    return sr_unrolled_vjp_entry(h, "bpltv_sumregs_unrolled_vjp", false, nullptr, alpha, am, an, pp, gu, grad_f_out, grad_alpha_out, false);
-}
-int bpltv_sumregs_unrolled_vjp_device(bpltv_t* h, const double* d_tape, const double* d_alpha, int am, int an, const bpltv_params* pp,
-                                      const double* d_gu, double* d_grad_f, double* d_grad_alpha) {
-    return sr_unrolled_vjp_entry(h, "bpltv_sumregs_unrolled_vjp_device", true, d_tape, d_alpha, am, an, pp, d_gu, d_grad_f, d_grad_alpha, false);
-}
-int bpltv_sumregs_unrolled_vjp_each(bpltv_t* h, const double* alphas, int am, int an, const bpltv_params* pp, const double* gu,
-                                    double* grad_f_out, double* grad_alphas_out) {
-    return sr_unrolled_vjp_entry(h, "bpltv_sumregs_unrolled_vjp_each", false, nullptr, alphas, am, an, pp, gu, grad_f_out, grad_alphas_out, true);
-}
-int bpltv_sumregs_unrolled_vjp_each_device(bpltv_t* h, const double* d_tape, const double* d_alphas, int am, int an, const bpltv_params* pp,
-                                           const double* d_gu, double* d_grad_f, double* d_grad_alphas) {
-    return sr_unrolled_vjp_entry(h, "bpltv_sumregs_unrolled_vjp_each_device", true, d_tape, d_alphas, am, an, pp, d_gu, d_grad_f, d_grad_alphas, true);
-}
-
-int bpltv_weighted_unrolled_tape_doubles(bpltv_t* h, const bpltv_params* pp, unsigned long long* n_out) {
-    if (!h) return BPLTV_E_ARG;
-    if (!n_out) return set_err(h, BPLTV_E_ARG, "bpltv_weighted_unrolled_tape_doubles: null pointer");
-    const bpltv_params p = resolve(pp);
-    if (p.maxiter < 1) return set_err(h, BPLTV_E_ARG, "bpltv_weighted_unrolled_tape_doubles: maxiter = %d (at least one iteration)", p.maxiter);
-    *n_out = 3ull * (unsigned long long)p.maxiter * (unsigned long long)h->M * h->N * h->O;
-    return BPLTV_OK;
-}
-
-int bpltv_weighted_unrolled_denoise(bpltv_t* h, const double* w, int wo, const double* alpha, int am, int an, const bpltv_params* pp,
-                                    double* u_out) {
-    if (!h) return BPLTV_E_ARG;
-    if (h->multi)
-        return weighted_multi(h, "bpltv_weighted_unrolled_denoise", true, [&](bpltv_t* c) { return bpltv_weighted_unrolled_denoise(c, w, wo, alpha, am, an, pp, u_out); }, kWeightedUnrolled);
-    return weighted_unrolled_denoise_common(h, w, wo, alpha, false, am, an, pp, nullptr, u_out);
-}
-
-int bpltv_weighted_unrolled_denoise_device(bpltv_t* h, const double* d_w, int wo, const double* d_alpha, int am, int an,
-                                           const bpltv_params* pp, double* d_tape) {
-    if (!h) return BPLTV_E_ARG;
-    if (h->multi)
-        return weighted_multi(h, "bpltv_weighted_unrolled_denoise_device", true, [&](bpltv_t* c) { return bpltv_weighted_unrolled_denoise_device(c, d_w, wo, d_alpha, am, an, pp, d_tape); }, kWeightedUnrolled);
-    return weighted_unrolled_denoise_common(h, d_w, wo, d_alpha, true, am, an, pp, d_tape, nullptr);
-}
-
-int bpltv_weighted_unrolled_vjp(bpltv_t* h, const double* w, int wo, const double* alpha, int am, int an, const bpltv_params* pp,
-                                const double* gu, double* grad_f_out, double* grad_alpha_out, double* grad_w_out) {
-    if (!h) return BPLTV_E_ARG;
-    if (h->multi)
-        return weighted_multi(h, "bpltv_weighted_unrolled_vjp", false, [&](bpltv_t* c) {
-            return bpltv_weighted_unrolled_vjp(c, w, wo, alpha, am, an, pp, gu, grad_f_out, grad_alpha_out, grad_w_out);
-        }, kWeightedUnrolled);
-    if (!gu || !w || !alpha) return set_err(h, BPLTV_E_ARG, "weighted_unrolled_vjp: null pointer");
-    if (!grad_f_out && !grad_alpha_out && !grad_w_out) return set_err(h, BPLTV_E_ARG, "weighted_unrolled_vjp: all three outputs are NULL");
-    if (wo != 1 && wo != h->O) return set_err(h, BPLTV_E_ARG, "weighted_unrolled_vjp: wo = %d: one weight plane (1) or one per image (%d)", wo, h->O);
-    if (am < 1 || an < 1 || am > h->M || an > h->N)
-        return set_err(h, BPLTV_E_ARG, "weighted_unrolled_vjp: parameter shape %dx%d (image %dx%d)", am, an, h->M, h->N);
-    HIPCHK(h, hipSetDevice(h->device));
-    const size_t tot = h->tot, P = (size_t)am * an, nw = (size_t)wo * h->npx;
+    const size_t tot = h->tot, P = (size_t)m.slices * am * an * (each ? h->O : 1), nw = m.weighted ? (size_t)wo * h->npx : 0;
     if (!h->d_u2) {
         HIPCHK(h, hipMalloc((void**)&h->d_u2, tot * sizeof(double)));
         HIPCHK(h, hipMalloc((void**)&h->d_ubar2, tot * sizeof(double)));
@@ -4659,25 +4277,120 @@ int bpltv_weighted_unrolled_vjp(bpltv_t* h, const double* w, int wo, const doubl
     if (rc) return rc;
     double* d_ga = grad_alpha_out ? h->d_vjp + 4 + P : nullptr;
     double* d_gw = grad_w_out ? h->d_wst + tot : nullptr;
-    rc = weighted_unrolled_vjp_common(h, nullptr, w, wo, alpha, false, am, an, pp, h->d_ubar2, grad_f_out ? h->d_gf2 : nullptr, d_ga, d_gw);
+    rc = taped_vjp(h, m, nullptr, w, wo, alpha, false, am, an, pp, h->d_ubar2, grad_f_out ? h->d_gf2 : nullptr, d_ga, d_gw, each);
     if (rc) return rc;
     if (grad_f_out) HIPCHK(h, hipMemcpyAsync(grad_f_out, h->d_gf2, tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (grad_alpha_out) HIPCHK(h, hipMemcpyAsync(grad_alpha_out, d_ga, P * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (grad_w_out) HIPCHK(h, hipMemcpyAsync(grad_w_out, d_gw, nw * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (m.tv_stats) h->st.total_ms = wt.ms();   // (the other two models' sweeps change adjoint_ms and adjoint_method only)
     return BPLTV_OK;
 }
 
+static int taped_vjp_entry(bpltv_t* h, const TapedModel& m, const char* what, bool dev, const double* d_tape, const double* w, int wo,
+                           const double* alpha, int am, int an, const bpltv_params* pp, const double* gu, double* grad_f, double* grad_alpha,
+                           double* grad_w, bool each) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, what, false, [&](bpltv_t* c) {
+            return taped_vjp_entry(c, m, what, dev, d_tape, w, wo, alpha, am, an, pp, gu, grad_f, grad_alpha, grad_w, each);
+        }, m.multi_name);
+    if (!dev) return taped_vjp_host(h, m, w, wo, alpha, am, an, pp, gu, grad_f, grad_alpha, grad_w, each);
+    WallTimer wt;
+    HIPCHK(h, hipSetDevice(h->device));
+    const int rc = taped_vjp(h, m, d_tape, w, wo, alpha, true, am, an, pp, gu, grad_f, grad_alpha, grad_w, each);
+    if (rc) return rc;
+    if (m.tv_stats) h->st.total_ms = wt.ms();
+    return BPLTV_OK;
+}
+
+int bpltv_unrolled_tape_doubles(bpltv_t* h, const bpltv_params* pp, unsigned long long* n_out) {
+    return tape_doubles_entry(h, kTapedTV, "bpltv_unrolled_tape_doubles", pp, n_out);
+}
+int bpltv_unrolled_denoise(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, double* u_out) {
+    return taped_denoise_entry(h, kTapedTV, "bpltv_unrolled_denoise", nullptr, 1, alpha, false, am, an, pp, nullptr, u_out, false);
+}
+int bpltv_unrolled_denoise_device(bpltv_t* h, const double* d_alpha, int am, int an, const bpltv_params* pp, double* d_tape) {
+    return taped_denoise_entry(h, kTapedTV, "bpltv_unrolled_denoise_device", nullptr, 1, d_alpha, true, am, an, pp, d_tape, nullptr, false);
+}
+// bpltv_unrolled_denoise with one parameter block per image: upload_alpha with O blocks, after which the taped kernel and the
+// gap kernels address block k for image k (h->alpha_istride); the tape remembers it (Tape::each).
+int bpltv_unrolled_denoise_each(bpltv_t* h, const double* alphas, int am, int an, const bpltv_params* pp, double* u_out) {
+    return taped_denoise_entry(h, kTapedTV, "bpltv_unrolled_denoise_each", nullptr, 1, alphas, false, am, an, pp, nullptr, u_out, true);
+}
+int bpltv_unrolled_denoise_each_device(bpltv_t* h, const double* d_alphas, int am, int an, const bpltv_params* pp, double* d_tape) {
+    return taped_denoise_entry(h, kTapedTV, "bpltv_unrolled_denoise_each_device", nullptr, 1, d_alphas, true, am, an, pp, d_tape, nullptr, true);
+}
+int bpltv_unrolled_vjp(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, const double* gu,
+                       double* grad_f_out, double* grad_alpha_out) {
+    return taped_vjp_entry(h, kTapedTV, "bpltv_unrolled_vjp", false, nullptr, nullptr, 1, alpha, am, an, pp, gu, grad_f_out, grad_alpha_out, nullptr, false);
+}
+int bpltv_unrolled_vjp_each(bpltv_t* h, const double* alphas, int am, int an, const bpltv_params* pp, const double* gu,
+                            double* grad_f_out, double* grad_alphas_out) {
+    return taped_vjp_entry(h, kTapedTV, "bpltv_unrolled_vjp_each", false, nullptr, nullptr, 1, alphas, am, an, pp, gu, grad_f_out, grad_alphas_out, nullptr, true);
+}
+int bpltv_unrolled_vjp_each_device(bpltv_t* h, const double* d_tape, const double* d_alphas, int am, int an, const bpltv_params* pp,
+                                   const double* d_gu, double* d_grad_f, double* d_grad_alphas) {
+    return taped_vjp_entry(h, kTapedTV, "bpltv_unrolled_vjp_each_device", true, d_tape, nullptr, 1, d_alphas, am, an, pp, d_gu, d_grad_f, d_grad_alphas, nullptr, true);
+}
+int bpltv_unrolled_vjp_device(bpltv_t* h, const double* d_tape, const double* d_alpha, int am, int an, const bpltv_params* pp,
+                              const double* d_gu, double* d_grad_f, double* d_grad_alpha) {
+    return taped_vjp_entry(h, kTapedTV, "bpltv_unrolled_vjp_device", true, d_tape, nullptr, 1, d_alpha, am, an, pp, d_gu, d_grad_f, d_grad_alpha, nullptr, false);
+}
+
+int bpltv_sumregs_unrolled_tape_doubles(bpltv_t* h, const bpltv_params* pp, unsigned long long* n_out) {
+    return tape_doubles_entry(h, kTapedSr, "bpltv_sumregs_unrolled_tape_doubles", pp, n_out);
+}
+int bpltv_sumregs_unrolled_denoise(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, double* u_out) {
+    return taped_denoise_entry(h, kTapedSr, "bpltv_sumregs_unrolled_denoise", nullptr, 1, alpha, false, am, an, pp, nullptr, u_out, false);
+}
+int bpltv_sumregs_unrolled_denoise_device(bpltv_t* h, const double* d_alpha, int am, int an, const bpltv_params* pp, double* d_tape) {
+    return taped_denoise_entry(h, kTapedSr, "bpltv_sumregs_unrolled_denoise_device", nullptr, 1, d_alpha, true, am, an, pp, d_tape, nullptr, false);
+}
+int bpltv_sumregs_unrolled_denoise_each(bpltv_t* h, const double* alphas, int am, int an, const bpltv_params* pp, double* u_out) {
+    return taped_denoise_entry(h, kTapedSr, "bpltv_sumregs_unrolled_denoise_each", nullptr, 1, alphas, false, am, an, pp, nullptr, u_out, true);
+}
+int bpltv_sumregs_unrolled_denoise_each_device(bpltv_t* h, const double* d_alphas, int am, int an, const bpltv_params* pp, double* d_tape) {
+    return taped_denoise_entry(h, kTapedSr, "bpltv_sumregs_unrolled_denoise_each_device", nullptr, 1, d_alphas, true, am, an, pp, d_tape, nullptr, true);
+}
+int bpltv_sumregs_unrolled_vjp(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, const double* gu,
+                               double* grad_f_out, double* grad_alpha_out) {
+    return taped_vjp_entry(h, kTapedSr, "bpltv_sumregs_unrolled_vjp", false, nullptr, nullptr, 1, alpha, am, an, pp, gu, grad_f_out, grad_alpha_out, nullptr, false);
+}
+int bpltv_sumregs_unrolled_vjp_device(bpltv_t* h, const double* d_tape, const double* d_alpha, int am, int an, const bpltv_params* pp,
+                                      const double* d_gu, double* d_grad_f, double* d_grad_alpha) {
+    return taped_vjp_entry(h, kTapedSr, "bpltv_sumregs_unrolled_vjp_device", true, d_tape, nullptr, 1, d_alpha, am, an, pp, d_gu, d_grad_f, d_grad_alpha, nullptr, false);
+}
+int bpltv_sumregs_unrolled_vjp_each(bpltv_t* h, const double* alphas, int am, int an, const bpltv_params* pp, const double* gu,
+                                    double* grad_f_out, double* grad_alphas_out) {
+    return taped_vjp_entry(h, kTapedSr, "bpltv_sumregs_unrolled_vjp_each", false, nullptr, nullptr, 1, alphas, am, an, pp, gu, grad_f_out, grad_alphas_out, nullptr, true);
+}
+int bpltv_sumregs_unrolled_vjp_each_device(bpltv_t* h, const double* d_tape, const double* d_alphas, int am, int an, const bpltv_params* pp,
+                                           const double* d_gu, double* d_grad_f, double* d_grad_alphas) {
+    return taped_vjp_entry(h, kTapedSr, "bpltv_sumregs_unrolled_vjp_each_device", true, d_tape, nullptr, 1, d_alphas, am, an, pp, d_gu, d_grad_f, d_grad_alphas, nullptr, true);
+}
+
+int bpltv_weighted_unrolled_tape_doubles(bpltv_t* h, const bpltv_params* pp, unsigned long long* n_out) {
+    return tape_doubles_entry(h, kTapedWeighted, "bpltv_weighted_unrolled_tape_doubles", pp, n_out);
+}
+int bpltv_weighted_unrolled_denoise(bpltv_t* h, const double* w, int wo, const double* alpha, int am, int an, const bpltv_params* pp,
+                                    double* u_out) {
+    return taped_denoise_entry(h, kTapedWeighted, "bpltv_weighted_unrolled_denoise", w, wo, alpha, false, am, an, pp, nullptr, u_out, false);
+}
+int bpltv_weighted_unrolled_denoise_device(bpltv_t* h, const double* d_w, int wo, const double* d_alpha, int am, int an,
+                                           const bpltv_params* pp, double* d_tape) {
+    return taped_denoise_entry(h, kTapedWeighted, "bpltv_weighted_unrolled_denoise_device", d_w, wo, d_alpha, true, am, an, pp, d_tape, nullptr, false);
+}
+int bpltv_weighted_unrolled_vjp(bpltv_t* h, const double* w, int wo, const double* alpha, int am, int an, const bpltv_params* pp,
+                                const double* gu, double* grad_f_out, double* grad_alpha_out, double* grad_w_out) {
+    return taped_vjp_entry(h, kTapedWeighted, "bpltv_weighted_unrolled_vjp", false, nullptr, w, wo, alpha, am, an, pp, gu, grad_f_out, grad_alpha_out,
+                           grad_w_out, false);
+}
 int bpltv_weighted_unrolled_vjp_device(bpltv_t* h, const double* d_tape, const double* d_w, int wo, const double* d_alpha, int am, int an,
                                        const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alpha,
                                        double* d_grad_w) {
-    if (!h) return BPLTV_E_ARG;
-    if (h->multi)
-        return weighted_multi(h, "bpltv_weighted_unrolled_vjp_device", false, [&](bpltv_t* c) {
-            return bpltv_weighted_unrolled_vjp_device(c, d_tape, d_w, wo, d_alpha, am, an, pp, d_gu, d_grad_f, d_grad_alpha, d_grad_w);
-        }, kWeightedUnrolled);
-    HIPCHK(h, hipSetDevice(h->device));
-    return weighted_unrolled_vjp_common(h, d_tape, d_w, wo, d_alpha, true, am, an, pp, d_gu, d_grad_f, d_grad_alpha, d_grad_w);
+    return taped_vjp_entry(h, kTapedWeighted, "bpltv_weighted_unrolled_vjp_device", true, d_tape, d_w, wo, d_alpha, am, an, pp, d_gu, d_grad_f,
+                           d_grad_alpha, d_grad_w, false);
 }
 
 // bpltv_unrolled_jvp and bpltv_unrolled_jvp_each on a single-device handle: the host arrays staged around unrolled_jvp_common
@@ -4707,42 +4420,32 @@ static int unrolled_jvp_host(bpltv_t* h, const double* alpha, int am, int an, co
     return BPLTV_OK;
 }
 
+static int unrolled_jvp_entry(bpltv_t* h, const char* what, bool dev, const double* alpha, int am, int an, const bpltv_params* pp, int ndir,
+                              const double* df, const double* dalpha, double* du, double* u, bool each) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, what, false, [&](bpltv_t* c) { return unrolled_jvp_entry(c, what, dev, alpha, am, an, pp, ndir, df, dalpha, du, u, each); },
+                              kUnrolled);
+    if (!dev) return unrolled_jvp_host(h, alpha, am, an, pp, ndir, df, dalpha, du, u, each);
+    HIPCHK(h, hipSetDevice(h->device));
+    return unrolled_jvp_common(h, each ? "unrolled_jvp_each" : "unrolled_jvp", alpha, true, am, an, pp, ndir, df, dalpha, du, u, nullptr, each);
+}
+
 int bpltv_unrolled_jvp(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, int ndir, const double* df,
                        const double* dalpha, double* du_out, double* u_out) {
-    if (!h) return BPLTV_E_ARG;
-    if (h->multi)
-        return weighted_multi(h, "bpltv_unrolled_jvp", false, [&](bpltv_t* c) { return bpltv_unrolled_jvp(c, alpha, am, an, pp, ndir, df, dalpha, du_out, u_out); }, kUnrolled);
-    return unrolled_jvp_host(h, alpha, am, an, pp, ndir, df, dalpha, du_out, u_out, false);
+    return unrolled_jvp_entry(h, "bpltv_unrolled_jvp", false, alpha, am, an, pp, ndir, df, dalpha, du_out, u_out, false);
 }
-
 int bpltv_unrolled_jvp_each(bpltv_t* h, const double* alphas, int am, int an, const bpltv_params* pp, int ndir, const double* df,
                             const double* dalphas, double* du_out, double* u_out) {
-    if (!h) return BPLTV_E_ARG;
-    if (h->multi)
-        return weighted_multi(h, "bpltv_unrolled_jvp_each", false, [&](bpltv_t* c) { return bpltv_unrolled_jvp_each(c, alphas, am, an, pp, ndir, df, dalphas, du_out, u_out); }, kUnrolled);
-    return unrolled_jvp_host(h, alphas, am, an, pp, ndir, df, dalphas, du_out, u_out, true);
+    return unrolled_jvp_entry(h, "bpltv_unrolled_jvp_each", false, alphas, am, an, pp, ndir, df, dalphas, du_out, u_out, true);
 }
-
 int bpltv_unrolled_jvp_each_device(bpltv_t* h, const double* d_alphas, int am, int an, const bpltv_params* pp, int ndir, const double* d_df,
                                    const double* d_dalphas, double* d_du, double* d_u) {
-    if (!h) return BPLTV_E_ARG;
-    if (h->multi)
-        return weighted_multi(h, "bpltv_unrolled_jvp_each_device", false, [&](bpltv_t* c) {
-            return bpltv_unrolled_jvp_each_device(c, d_alphas, am, an, pp, ndir, d_df, d_dalphas, d_du, d_u);
-        }, kUnrolled);
-    HIPCHK(h, hipSetDevice(h->device));
-    return unrolled_jvp_common(h, "unrolled_jvp_each", d_alphas, true, am, an, pp, ndir, d_df, d_dalphas, d_du, d_u, nullptr, true);
+    return unrolled_jvp_entry(h, "bpltv_unrolled_jvp_each_device", true, d_alphas, am, an, pp, ndir, d_df, d_dalphas, d_du, d_u, true);
 }
-
 int bpltv_unrolled_jvp_device(bpltv_t* h, const double* d_alpha, int am, int an, const bpltv_params* pp, int ndir, const double* d_df,
                               const double* d_dalpha, double* d_du, double* d_u) {
-    if (!h) return BPLTV_E_ARG;
-    if (h->multi)
-        return weighted_multi(h, "bpltv_unrolled_jvp_device", false, [&](bpltv_t* c) {
-            return bpltv_unrolled_jvp_device(c, d_alpha, am, an, pp, ndir, d_df, d_dalpha, d_du, d_u);
-        }, kUnrolled);
-    HIPCHK(h, hipSetDevice(h->device));
-    return unrolled_jvp_common(h, "unrolled_jvp", d_alpha, true, am, an, pp, ndir, d_df, d_dalpha, d_du, d_u, nullptr);
+    return unrolled_jvp_entry(h, "bpltv_unrolled_jvp_device", true, d_alpha, am, an, pp, ndir, d_df, d_dalpha, d_du, d_u, false);
 }
 
 // Gradient and Gauss-Newton Hessian of the K-step loss 0.5||u_K(alpha) - ubar||^2 from P = am*an <= GN_MAXP unit-direction

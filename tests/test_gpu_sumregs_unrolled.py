@@ -265,11 +265,25 @@ def test_the_handle_s_sumregs_tape(gpu_solver_cls):
     assert code(n.weighted_unrolled_vjp, 0.08, w, gu, maxiter=20) == E_NODATA
     n.close()
     s.sumregs_unrolled_denoise(VEC, maxiter=20)
+    st0 = s.stats()
+    assert st0["iterations"] == 20 and st0["tiles"] >= O and st0["tile_iters"] >= 1 and st0["launch_chains"] >= 1, st0
+
+    def sweep_stats(method="sumregs-unrolled"):
+        """what a reverse sweep leaves: its adjoint_method, and the solve fields the taped solve left"""
+        st = s.stats()
+        assert st["adjoint_method"] == method, st
+        assert all(st[k] == st0[k] for k in ("iterations", "tile_iters", "tiles", "launch_chains")), (st, st0)
+        return st
+
     gf, ga = s.sumregs_unrolled_vjp(VEC, np.zeros_like(gu), maxiter=20)
+    assert sweep_stats()["total_ms"] == st0["total_ms"]    # (this sweep leaves the solve's wall time too)
     assert not gf.any() and not ga.any()
     gf, ga = s.sumregs_unrolled_vjp(VEC, gu, maxiter=20)
+    sweep_stats()
     assert gf.any() and ga.all()
     s.sumregs_unrolled_denoise(VEC, maxiter=12)            # a second, shorter solve: the tape is now its
+    st0 = s.stats()
+    assert st0["iterations"] == 12, st0
     assert code(s.sumregs_unrolled_vjp, VEC, gu, maxiter=20) == E_ARG
     for kw in (dict(accel=0), dict(tau0=4.0), dict(sigma0=0.1), dict(opnorm=2.5)):     # other steps than the tape's
         assert code(s.sumregs_unrolled_vjp, VEC, gu, maxiter=12, **kw) == E_ARG
@@ -277,11 +291,17 @@ def test_the_handle_s_sumregs_tape(gpu_solver_cls):
     assert code(s.sumregs_unrolled_vjp, _alpha("patch", N, M)[:, :1], gu, maxiter=12) == E_ARG   # another an alone
     a, b = s.sumregs_unrolled_vjp(VEC, gu, maxiter=12), s.sumregs_unrolled_vjp(VEC, gu, maxiter=12)
     assert all(_same(x, y) for x, y in zip(a, b))
+    sweep_stats()                                          # (the rejected sweeps in between changed nothing either)
     s.sumregs_denoise(VEC, maxiter=33)                     # a plain solve in the same state sets leaves the tape alone
+    st0 = s.stats()
     assert all(_same(x, y) for x, y in zip(s.sumregs_unrolled_vjp(VEC, gu, maxiter=12), a))
+    sweep_stats()
     # the TV and weighted tapes survived all of it
     assert all(_same(x, y) for x, y in zip(s.unrolled_vjp(0.08, gu, maxiter=20), g_tv))
+    st = sweep_stats("unrolled")
+    assert st["adjoint_attempts"] == 1 and st["adjoint_residual"] == 0.0, st
     assert all(_same(x, y) for x, y in zip(s.weighted_unrolled_vjp(0.08, w, gu, maxiter=20), g_w))
+    sweep_stats("weighted-unrolled")
     s.unrolled_denoise(0.08, maxiter=9)                    # ... and this one survives theirs
     s.weighted_unrolled_denoise(0.08, w, maxiter=9)
     assert all(_same(x, y) for x, y in zip(s.sumregs_unrolled_vjp(VEC, gu, maxiter=12), a))

@@ -179,11 +179,24 @@ def test_zero_cotangent_and_the_handle_s_tape(gpu_solver_cls):
         s.unrolled_vjp(0.08, gu, maxiter=20)
     assert e.value.code == E_NODATA
     s.unrolled_denoise(0.08, maxiter=20)
+    st0 = s.stats()
+    assert st0["iterations"] == 20 and st0["tiles"] >= O and st0["tile_iters"] >= 1 and st0["launch_chains"] >= 1, st0
+
+    def sweep_stats():
+        """what a reverse sweep leaves: its own adjoint fields, and the solve fields the taped solve left"""
+        st = s.stats()
+        assert st["adjoint_method"] == "unrolled" and st["adjoint_attempts"] == 1 and st["adjoint_residual"] == 0.0, st
+        assert all(st[k] == st0[k] for k in ("iterations", "tile_iters", "tiles", "launch_chains")), (st, st0)
+
     gf, ga = s.unrolled_vjp(0.08, np.zeros_like(gu), maxiter=20)
+    sweep_stats()
     assert not gf.any() and ga == 0.0
     gf, ga = s.unrolled_vjp(0.08, gu, maxiter=20)
+    sweep_stats()
     assert gf.any() and ga != 0.0
     s.unrolled_denoise(0.08, maxiter=12)       # a second, shorter solve: the tape is now its
+    st0 = s.stats()
+    assert st0["iterations"] == 12, st0
     with pytest.raises(BpltvError) as e:
         s.unrolled_vjp(0.08, gu, maxiter=20)
     assert e.value.code == E_ARG
@@ -195,6 +208,7 @@ def test_zero_cotangent_and_the_handle_s_tape(gpu_solver_cls):
         s.unrolled_vjp(np.full((2, 2), 0.08), gu, maxiter=12)
     assert e.value.code == E_ARG
     assert _same(s.unrolled_vjp(0.08, gu, maxiter=12)[0], s.unrolled_vjp(0.08, gu, maxiter=12)[0])
+    sweep_stats()                              # (the rejected sweeps in between changed nothing either)
     n = gpu_solver_cls(M, N, O)                # no dataset
     with pytest.raises(BpltvError) as e:
         n.unrolled_denoise(0.08, maxiter=5)

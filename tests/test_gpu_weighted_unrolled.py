@@ -252,13 +252,29 @@ def test_the_handle_s_weighted_tape(gpu_solver_cls):
     assert code(n.unrolled_vjp, 0.08, gu, maxiter=20) == E_NODATA
     n.close()
     s.weighted_unrolled_denoise(0.08, w, maxiter=20)
+    st0 = s.stats()
+    assert st0["iterations"] == 20 and st0["tiles"] >= O and st0["tile_iters"] >= 1 and st0["launch_chains"] >= 1, st0
+
+    def sweep_stats(method="weighted-unrolled"):
+        """what a reverse sweep leaves: its adjoint_method, and the solve fields the taped solve left"""
+        st = s.stats()
+        assert st["adjoint_method"] == method, st
+        assert all(st[k] == st0[k] for k in ("iterations", "tile_iters", "tiles", "launch_chains")), (st, st0)
+        return st
+
     gf, ga, gw = s.weighted_unrolled_vjp(0.08, w, np.zeros_like(gu), maxiter=20)
+    assert sweep_stats()["total_ms"] == st0["total_ms"]    # (the weighted sweep leaves the solve's wall time too)
     assert not gf.any() and ga == 0.0 and not gw.any()
     gf, ga, gw = s.weighted_unrolled_vjp(0.08, w, gu, maxiter=20)
+    sweep_stats()
     assert gf.any() and ga != 0.0 and gw.any()
     g_tv = s.unrolled_vjp(0.08, gu, maxiter=20)                                        # both tapes live side by side
+    st = sweep_stats("unrolled")
+    assert st["adjoint_attempts"] == 1 and st["adjoint_residual"] == 0.0, st
     assert g_tv[0].any()
     s.weighted_unrolled_denoise(0.08, w, maxiter=12)       # a second, shorter solve: the tape is now its
+    st0 = s.stats()
+    assert st0["iterations"] == 12, st0
     assert code(s.weighted_unrolled_vjp, 0.08, w, gu, maxiter=20) == E_ARG
     for kw in (dict(accel=0), dict(tau0=4.0), dict(sigma0=0.1), dict(opnorm=2.5)):     # other steps than the tape's
         assert code(s.weighted_unrolled_vjp, 0.08, w, gu, maxiter=12, **kw) == E_ARG
@@ -270,7 +286,9 @@ def test_the_handle_s_weighted_tape(gpu_solver_cls):
     assert code(s.weighted_unrolled_vjp, 0.08, np.broadcast_to(mask, w.shape), gu, maxiter=12) == E_ARG   # (gamma = 0)
     a, b = s.weighted_unrolled_vjp(0.08, w, gu, maxiter=12), s.weighted_unrolled_vjp(0.08, w, gu, maxiter=12)
     assert all(_same(x, y) for x, y in zip(a, b))
+    sweep_stats()                                          # (the rejected sweeps in between changed nothing either)
     assert all(_same(x, y) for x, y in zip(s.unrolled_vjp(0.08, gu, maxiter=20), g_tv))    # the TV tape survived all of it
+    sweep_stats("unrolled")
     n = gpu_solver_cls(M, N, O)                # no dataset
     assert code(n.weighted_unrolled_denoise, 0.08, w, maxiter=5) == E_NODATA
     n.close()
