@@ -845,23 +845,33 @@ __global__ __launch_bounds__(256) void patch_sum_kernel(const double* __restrict
 // Residual statistics per image: out[k*4 + {0: ||r||^2, 1: ||rhs||^2, 2: r^T D^-1 r, 3: rhs^T D^-1 rhs}],
 // D = diag(A) (plane 0 of band4).  The diagonally scaled pair is the quality gate: the raw residual is
 // dominated by the rounding of the rows that carry the 1e14 active-set weight (|r_k| ~ eps * 1e14 * |p|),
-// which say nothing about the solve; scaled by 1/sqrt(d_k) = 1e-7 they fall to rounding level.
+// which say nothing about the solve; scaled by 1/sqrt(d_k) = 1e-7 they fall to rounding level -- as long as some row
+// of the image has a diagonal of order one.  On an image whose every element is active (a constant image) every
+// diagonal is 4 kappa, the scaling cancels in the quotient, and the rounding of p itself (no double vector does better:
+// r = kappa G^T G (p - round(p))) reads as a residual of kappa eps |p| / |rhs| ~ 1e-4: the gate refused a solve
+// that was correct to 3e-11 and the call went on to a weight of 1e12 or 1e10.  So the scaled pair leaves out the rows
+// that carry the weight: d_k >= skip * s_k^2 (skip = the active-set weight; s the node scaling, nullptr = 1; skip =
+// +inf: every row counts, as for gradient_reg and the sum of regularisers).  An image with no other row reports 0.
 // grid (RESN_BLK, O): partials[(img * RESN_BLK + b) * 4 + {0..3}]; adj_resnorm_final_kernel adds them in block order
 // (no atomics: reproducible) into out[img * 4 + {0..3}].
 constexpr int RESN_BLK = 64;
 __global__ __launch_bounds__(256) void adj_resnorm_kernel(const double* __restrict__ r,
                                                           const double* __restrict__ rhs,
                                                           const double* __restrict__ diag, int npx,
-                                                          double* __restrict__ partial) {
+                                                          double* __restrict__ partial,
+                                                          const double* __restrict__ s, double skip) {
     __shared__ double sh[4];
     const size_t base = (size_t)blockIdx.y * npx;
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
     for (size_t q = (size_t)blockIdx.x * 256 + threadIdx.x; q < (size_t)npx; q += (size_t)RESN_BLK * 256) {
-        const double rv = r[base + q], bv = rhs[base + q], di = 1.0 / diag[base + q];
+        const double rv = r[base + q], bv = rhs[base + q], d = diag[base + q], di = 1.0 / d;
+        const double sv = s ? s[base + q] : 1.0;
         s0 += rv * rv;
         s1 += bv * bv;
-        s2 += rv * rv * di;
-        s3 += bv * bv * di;
+        if (!(d >= skip * (sv * sv))) {
+            s2 += rv * rv * di;
+            s3 += bv * bv * di;
+        }
     }
     s0 = block_sum<256>(s0, sh);
     s1 = block_sum<256>(s1, sh);

@@ -1587,7 +1587,6 @@ struct GradCtx {
     // or nullptr) receives -(u - f) o p, summed over the images in image order when wo == 1; f is read for d_grad_w only.
     const double* w = nullptr;
     int wo = 1;
-    bool w_unit = false;           // every entry of w is exactly 1.0: the system, and the sweeps it gets, are bpltv_vjp's
     double w_min = 0.0;            // smallest entry of w (the reverse sweep of the weighted iterations: gamma of its step table)
     const double* f = nullptr;
     double* d_grad_w = nullptr;
@@ -1629,12 +1628,16 @@ int run_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, 
     // 1.4e-9 after two).  The regularised systems (gamma = 1e8 instead of 1/eps) need none: 4e-10 / 1e-9 / 5e-11 from
     // the converged value without a sweep, scaled residual <= 4e-12.
     const bool direct = (method == ADJ_BAND_HBM || method == ADJ_ND);
-    int nref_default = direct ? (reg ? 0 : (patch ? 1 : 2)) : ((patch || reg) ? 2 : 3);
-    // Weighted model with a scalar parameter (the 1e14 weight) on a direct factorisation: against the literal system the two
-    // sweeps leave up to 5.3e-7 in grad_f (1 x 12 x 140 with a 2 x 125 flat block, nested dissection; 2.1e-8 on the HBM band),
-    // three 5.5e-9, four 5.8e-11 -- the level the LDS band and block cyclic reduction reach (tests/test_gpu_weighted_shapes.py:
-    // tolerance 1e-8 max|p|).  A weight that is one everywhere keeps bpltv_vjp's count: that call is bpltv_vjp bit for bit.
-    if (g.w && !g.w_unit && direct && !patch) nref_default = 4;
+    // Scalar parameter (the 1e14 weight) on a direct factorisation: FOUR sweeps.  Against the literal system on images with a
+    // planted active set (tests/test_gpu_tv_active_set.py: blocks, strips across the separators, a constant image; bound 1e-8
+    // max|p| + 1e-6 |ref|), worst |difference| of grad_f / grad_alpha and worst fraction of the bound over the cases:
+    //     nested dissection   2 sweeps 1.8e-7 / 2.1e-5 (2.2 of the bound: refused)   3: 2.4e-9 / 2.7e-7 (0.022)   4: 4.3e-11 / 3.5e-9 (< 0.001)
+    //     band in HBM         2 sweeps 3.7e-9 / 3.3e-7 (0.047)                       3: 1.5e-11 / 1.3e-9           4: 5.1e-12 / 1.2e-11
+    // Three would do for w = 1 (a tenth of the bound is the margin kept), but with a per-pixel weight three leave 5.5e-9 of a bound
+    // of 1.7e-8 (0.32; 1 x 12 x 140 with a 2 x 125 flat block, tests/test_gpu_weighted_shapes.py) and four 5.8e-11: one count for
+    // both, so that bpltv_weighted_vjp with w = 1 stays bpltv_vjp bit for bit without asking what w holds.  Cost: adjoint_ms of
+    // the 10 x 128^2 scalar evaluate 0.94 -> 1.28 ms (1.11 with three; median of 20).
+    int nref_default = direct ? (reg ? 0 : (patch ? 1 : 4)) : ((patch || reg) ? 2 : 3);
     const int nref = p.refine < 0 ? nref_default : p.refine;
     // forward mode: every direction keeps its own residual statistics (the gate takes the worst)
     const bool tangent = g.ndir > 0;
@@ -1713,7 +1716,8 @@ int run_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, 
             }
             hipLaunchKernelGGL(adj_residual_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, dr);
             double* resn_part = h->d_resn + 4 * (size_t)O + 4 * (size_t)c0 * RESN_BLK;
-            hipLaunchKernelGGL(adj_resnorm_kernel, dim3(RESN_BLK, nimg), dim3(256), 0, h->stream, dr, C.rhs, band4, (int)npx, resn_part);
+            hipLaunchKernelGGL(adj_resnorm_kernel, dim3(RESN_BLK, nimg), dim3(256), 0, h->stream, dr, C.rhs, band4, (int)npx, resn_part,
+                               (const double*)C.s, reg ? HUGE_VAL : kact);
             hipLaunchKernelGGL(adj_resnorm_final_kernel, dim3((4 * nimg + 63) / 64), dim3(64), 0, h->stream, resn_part, nimg,
                                resn_fin + 4 * ((size_t)d * O + c0));
             if (tangent)
@@ -1840,7 +1844,7 @@ struct WallTimer {
 
 int run_sr_gradient(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, const bpltv_params& p);
 
-int check_weight(bpltv_t* h, const char* who, const double* w, bool on_device, size_t n, double* wmin, double* wmax = nullptr);
+int check_weight(bpltv_t* h, const char* who, const double* w, bool on_device, size_t n, double* wmin);
 int weighted_check_params(bpltv_t* h, const bpltv_params& p, const char* who);
 
 // What bpltv_vjp, bpltv_jvp, bpltv_weighted_vjp and their sum-of-regularisers, _each and _device forms do before the
@@ -1863,11 +1867,11 @@ int stage_param(bpltv_t* h, const char* who, const double* alpha, bool alpha_dev
     if (int prc = w ? weighted_check_params(h, *p, who) : check_params(h, *p)) return prc;
     if (sr && p->reserved[4] == 2) return set_err(h, BPLTV_E_UNSUPPORTED, "block cyclic reduction applies to the TV model only");
     const size_t P = (size_t)slices * am * an * (each ? h->O : 1), nw = w ? (size_t)wo * h->npx : 0;
-    double amin = 0.0, wmin = 0.0, wmax = 0.0;
+    double amin = 0.0, wmin = 0.0;
     if (!alpha_dev)
         if (int crc = check_alpha_host(h, (std::string(who) + ": alpha").c_str(), alpha, P, &amin)) return crc;
     if (w) {
-        if (int rc = check_weight(h, who, w, alpha_dev, nw, &wmin, &wmax)) return rc;
+        if (int rc = check_weight(h, who, w, alpha_dev, nw, &wmin)) return rc;
         if (w_pos && !(wmin > 0.0)) return set_err(h, BPLTV_E_ARG, "%s: the adjoint system scales with 1/sqrt(w): every weight must be > 0 (min = %g)", who, wmin);
     }
     int rc = ensure(h, &h->d_vjp, &h->vjp_cap, 4 + 2 * P + nw);
@@ -1885,7 +1889,7 @@ int stage_param(bpltv_t* h, const char* who, const double* alpha, bool alpha_dev
     if (w) HIPCHK(h, hipMemcpyAsync(d_wv, w, nw * sizeof(double), kind, h->stream));
     g->alpha = d_a; g->am = am; g->an = an; g->alpha_min = amin;
     g->astride = each ? slices * am * an : 0; g->each = each;
-    if (w) { g->w = d_wv; g->wo = wo; g->w_unit = (wmin == 1.0 && wmax == 1.0); g->w_min = wmin; }
+    if (w) { g->w = d_wv; g->wo = wo; g->w_min = wmin; }
     return BPLTV_OK;
 }
 
@@ -2262,7 +2266,8 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int re
             }
             residual(dr);
             double* resn_part = h->d_resn + 4 * (size_t)O + 4 * (size_t)c0 * RESN_BLK;
-            hipLaunchKernelGGL(adj_resnorm_kernel, dim3(RESN_BLK, nimg), dim3(256), 0, h->stream, dr, C.rhs, diag, (int)npx, resn_part);
+            hipLaunchKernelGGL(adj_resnorm_kernel, dim3(RESN_BLK, nimg), dim3(256), 0, h->stream, dr, C.rhs, diag, (int)npx, resn_part,
+                               (const double*)nullptr, (double)HUGE_VAL);
             hipLaunchKernelGGL(adj_resnorm_final_kernel, dim3((4 * nimg + 63) / 64), dim3(64), 0, h->stream, resn_part, nimg,
                                resn_fin + 4 * ((size_t)d * O + c0));
             if (tangent)   // du is the solution itself: straight into the direction's slice of the caller's array
@@ -3176,32 +3181,22 @@ int gauss_newton(bpltv_t* h, const double* u, const double* ubar, const double* 
 // Per-pixel data-fidelity weight (weighted_kernels.hpp)
 // ============================================================================================
 // n entries of a weight array, finite and >= 0, on the host or (on_device) in HBM by alpha_check_kernel; *wmin receives the
-// smallest and *wmax (nullable; weight_max_kernel and one more 8-byte read back) the largest.  Reads only: nothing of the
-// handle changes.
-int check_weight(bpltv_t* h, const char* who, const double* w, bool on_device, size_t n, double* wmin, double* wmax) {
+// smallest.  Reads only: nothing of the handle changes.
+int check_weight(bpltv_t* h, const char* who, const double* w, bool on_device, size_t n, double* wmin) {
     if (!on_device) {
-        double mn = w[0], mx = w[0];
+        double mn = w[0];
         for (size_t e = 0; e < n; ++e) {
             if (!std::isfinite(w[e]) || w[e] < 0.0)
                 return set_err(h, BPLTV_E_ARG, "%s: w[%zu] = %g: the fidelity weight must be finite and >= 0", who, e, w[e]);
             if (w[e] < mn) mn = w[e];
-            if (w[e] > mx) mx = w[e];
         }
         *wmin = mn;
-        if (wmax) *wmax = mx;
         return BPLTV_OK;
     }
     int failed = -1;
     unsigned long long* chk = reinterpret_cast<unsigned long long*>(h->d_scalar + 2);
     if (int rc = check_device_arrays(h, chk, {w, n}, {}, wmin, &failed)) return rc;
     if (failed == 0) return set_err(h, BPLTV_E_ARG, "%s: w (device array): the fidelity weight must be finite and >= 0", who);
-    if (wmax) {   // every entry is finite and >= 0 here: the bit patterns order as the values do
-        HIPCHK(h, hipMemsetAsync(chk, 0, sizeof(unsigned long long), h->stream));
-        hipLaunchKernelGGL(weight_max_kernel, dim3((unsigned)std::min<size_t>((n + 255) / 256, 1024)), dim3(256), 0, h->stream, w, n, chk);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(wmax, chk, sizeof(double), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
-    }
     return BPLTV_OK;
 }
 

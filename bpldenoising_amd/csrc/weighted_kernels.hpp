@@ -217,19 +217,6 @@ __global__ __launch_bounds__(256) void weighted_gap_final_kernel(const double* _
     }
 }
 
-// Largest entry of a weight array whose entries are all finite and >= 0 (alpha_check_kernel has said so): out, zeroed by
-// the host, receives its bit pattern.  Grid-stride, block 256.
-__global__ __launch_bounds__(256) void weight_max_kernel(const double* __restrict__ w, size_t n, unsigned long long* __restrict__ out) {
-    __shared__ double smax[4];
-    double mx = 0.0;
-    for (size_t e = (size_t)blockIdx.x * 256 + threadIdx.x; e < n; e += (size_t)gridDim.x * 256) mx = fmax(mx, w[e]);
-    for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_down(mx, off));
-    if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = mx;
-    __syncthreads();
-    if (threadIdx.x == 0)
-        atomicMax(out, (unsigned long long)__double_as_longlong(fmax(fmax(smax[0], smax[1]), fmax(smax[2], smax[3]))));
-}
-
 // Adjoint of the weighted model (reg = 0: the reference's `gradient` linearisation): the system is diag(w) + K, and with
 // S = diag(w)^-1/2 it is S^-1 (I + S K S) S^-1 -- the node-scaled form adj_assemble_kernel, adj_residual_kernel,
 // adj_gradpix_kernel and every factorisation handle through the s plane.  adj_setup_body<true> with reg = 0, then

@@ -73,11 +73,10 @@ typedef struct bpltv_params {
                             0 = library default for the image size                                */
     int use_graph;       /* 1 (default): replay the launch sequence from a hipGraph               */
     double kappa_cap;    /* cap on the active-set weight 1/eps() of the adjoint system; 0 = 1e14  */
-    int refine;          /* iterative-refinement sweeps of the adjoint solve; < 0 = default: 2 / 1 / 0 for the
+    int refine;          /* iterative-refinement sweeps of the adjoint solve; < 0 = default: 4 / 1 / 0 for the
                             scalar gradient / patch and pixel-map parameters / gradient_reg with nested
                             dissection and the HBM band, 3 / 2 / 2 with block cyclic reduction and the
-                            LDS band; bpltv_weighted_vjp with a scalar parameter and a weight that is not
-                            one everywhere: 4 with nested dissection and the HBM band               */
+                            LDS band (bpltv_weighted_vjp included)                                   */
     int deterministic;   /* multi-GPU handles, scalar / patch parameters: 1 = all-gather the per-image rows
                             [cost_k, grad_k...] and add them in global image order, so that cost and grad are
                             bitwise the same for every number of GPUs (and equal to a single handle's);
@@ -120,15 +119,17 @@ typedef struct bpltv_stats {
     double algorithmic_bytes;  /* bytes_per_px_iter * M*N*O * iterations                          */
     double last_gap;           /* max over images of the duality gap if it was computed, else -1  */
     double adjoint_residual;   /* max over images of ||D^-1/2 (rhs - A p)|| / ||D^-1/2 rhs||, D = diag(A), after
-                                  refinement: the quality gate of the adjoint solve (<= 1e-8 on a correct
-                                  solve; above BPLTV_RESIDUAL_GATE the call fails with BPLTV_E_NUMERIC)   */
+                                  refinement, over the rows that do not carry the active-set weight (a constant
+                                  image has none and reports 0): the quality gate of the adjoint solve (<= 1e-8 on
+                                  a correct solve; above BPLTV_RESIDUAL_GATE the call fails with BPLTV_E_NUMERIC) */
     double adjoint_residual_raw; /* the same without the diagonal scaling: dominated by the rounding of
                                   the 1e14-weighted active rows, informational only                   */
     double kappa_used;         /* active-set weight of the adjoint system that produced the returned
                                   gradient: 1/eps() capped by kappa_cap (scalar), 1/sqrt(eps()) (patch),
                                   times 1e-2 per retry; 0 for gradient_reg                             */
     int adjoint_attempts;      /* factorisations tried by the last gradient: 1 = no breakdown, 2..3 = the
-                                  weight was reduced by 1e-2 per retry after a non-positive pivot      */
+                                  weight was reduced by 1e-2 per retry after a non-positive pivot or a
+                                  residual above the gate                                              */
     int adjoint_method;        /* 1 banded Cholesky (LDS window), 2 block cyclic reduction,
                                   3 banded Cholesky (HBM band), 4 banded LU (sum of regularisers, row-scaled
                                   gradient_reg system, with reserved[4] = 1), 5 nested-dissection (multifrontal)

@@ -572,6 +572,11 @@ def test_skinny_fronts_whatever_the_batch_size(gpu_solver_cls):
     _, _, g2 = s.evaluate(alpha, 0.1, maxiter=300)
     assert np.allclose(g2, g0, rtol=1e-9, atol=1e-12 * np.abs(g0).max())
     s.close()
+    # ... and the oracle on the same u, at the tolerance of test_pixelwise_alpha_gradient
+    gref = co.gradient(alpha, u0, ub)
+    for g in (g0, g1, g2):
+        print("skinny fronts: max|g - oracle| = %.3e max|oracle|" % (np.abs(g - gref).max() / np.abs(gref).max()))
+        assert np.allclose(g, gref, rtol=1e-5, atol=1e-8 * np.abs(gref).max())
 
 
 def test_nd_solver_unit_checks(gpu_solver_cls):

@@ -311,8 +311,8 @@ def test_vjp_on_every_factorisation_matches_the_literal_system(gpu_solver_cls, c
         scalar       band in HBM (4 sweeps), M = 140  4.7e-11 / 1.6e-10 / 7.0e-12
         scalar       nested dissection (4 sweeps)     3.6e-9 / 2.0e-9 / 1.2e-10
     With the two sweeps bpltv_vjp runs on the direct factorisations nested dissection left 5.3e-7 / 5.0e-7 / 1.9e-8 on
-    1 x 12 x 140 (max|p| 1.7, a 2 x 125 flat block) and failed here, the band in HBM 2.1e-8; the weighted scalar system now gets
-    four unless w is one everywhere."""
+    1 x 12 x 140 (max|p| 1.7, a 2 x 125 flat block) and failed here, the band in HBM 2.1e-8; the scalar system gets four
+    (DESIGN.md sections 4.3 and 4.5)."""
     from bpldenoising_amd._lib import BpltvError
     shape, kind, per_image = case
     O, N, M = shape
