@@ -209,9 +209,14 @@ struct GraphKey {
     int istride;       // doubles between per-image parameter blocks (bpltv_denoise_each, bpltv_sumregs_denoise_each: they live
                        // in d_alpha like a shared parameter, and run other kernel arguments / instances)
     int wo;            // weighted model: weight planes (d_w, d_f and the state sets are fixed for the life of the handle)
+    int spacing;       // taped solves and reverse sweeps: checkpoint spacing (0: the full tape).  One sequence holds every
+                       // segment of the call, so the segments are part of the graph and a call shape has one graph per chain
+    const void* seg;   // checkpointed reverse sweep: its segment tape and recompute planes (bpltv_handle::d_seg)
+    int T2;            // ... and the fusion depth of its recompute launches (T: of its reverse launches)
     bool operator<(const GraphKey& o) const {
-        return std::tie(maxiter, T, variant, am, an, chains, rho, tau0, sigma0, accel, dbg, nimg, state, tab, from_state, alpha, istride, wo) <
-               std::tie(o.maxiter, o.T, o.variant, o.am, o.an, o.chains, o.rho, o.tau0, o.sigma0, o.accel, o.dbg, o.nimg, o.state, o.tab, o.from_state, o.alpha, o.istride, o.wo);
+        return std::tie(maxiter, T, variant, am, an, chains, rho, tau0, sigma0, accel, dbg, nimg, state, tab, from_state, alpha, istride, wo, spacing, seg, T2) <
+               std::tie(o.maxiter, o.T, o.variant, o.am, o.an, o.chains, o.rho, o.tau0, o.sigma0, o.accel, o.dbg, o.nimg, o.state, o.tab, o.from_state, o.alpha, o.istride, o.wo,
+                        o.spacing, o.seg, o.T2);
     }
 };
 
@@ -320,6 +325,7 @@ struct HandleOptions {
     int hb_sync = 0;                  // HBM band cross-check solver: 0 automatic, 1 HIP events, 2 stream memory operations (fails if unavailable)
     int hb_single_stream = 0;         // ... 1: its three streams folded into one (rocprofv3 --pmc)
     int hb_rw = 0;                    // ... 32 / 128: row width of its trailing update (0 automatic)
+    int tape_checkpoint = 0;          // unrolled solves and sweeps: 0 the full tape, C >= 1 a checkpoint every C iterations, -1 automatic
 };
 
 // The tape of a taped solve (bpltv_unrolled_denoise and its weighted and sum-of-regularisers forms) that the handle keeps for
@@ -333,6 +339,7 @@ struct Tape {
     int wo = 0;                     // weighted model: weight planes (0 otherwise)
     double tau0 = 0.0, sigma0 = 0.0, opnorm = 0.0;
     double gamma = 0.0;             // weighted model: min w, the strong convexity its step table was made with
+    int spacing = 0;                // 0: the full tape; C >= 1: the buffer holds the state every C iterations (checkpoints) instead
     // a buffer of `need` doubles when the tape is smaller (*grown; nullptr when it is large enough): allocated ahead of
     // time, so that a call that is rejected afterwards frees it again and leaves the tape as it was
     hipError_t grow(size_t need, double** grown) const {
@@ -345,8 +352,8 @@ struct Tape {
         d = grown;
         cap = need;
     }
-    void record(const bpltv_params& p, int am_, int an_, bool each_, int wo_, double gamma_) {
-        valid = true; each = each_;
+    void record(const bpltv_params& p, int am_, int an_, bool each_, int wo_, double gamma_, int spacing_) {
+        valid = true; each = each_; spacing = spacing_;
         maxiter = p.maxiter; am = am_; an = an_; accel = p.accel ? 1 : 0; wo = wo_;
         tau0 = p.tau0; sigma0 = p.sigma0; opnorm = p.opnorm; gamma = gamma_;
     }
@@ -481,6 +488,10 @@ struct bpltv_handle {
     Tape srtape;
     double* d_srunr = nullptr;                      // 19 * M*N*O doubles
     bool srun_ready = false;
+    // checkpointed reverse sweeps of the three models (option "tape_checkpoint"): [segment tape | 2 recompute state sets],
+    // allocated on first use, only grows
+    double* d_seg = nullptr;
+    size_t seg_cap = 0;                             // doubles
     // forward mode through the iterations (unrolled_jvp_kernels.hpp): the tangent sweep's planes [2 sets x (x, y1, y2, dx, dy1,
     // dy2) | df | dalpha], allocated on first use and never moved
     double* d_ujv = nullptr;                        // 14 * M*N*O doubles
@@ -1068,6 +1079,8 @@ struct ChainSolve {
     bool serial = false;         // replay the chains one after the other on the handle's stream (TV, reserved[2] & 1)
     bool helper_thread = true;   // long sequences launch chain 1 from the handle's launcher thread (launch_chains)
     double bytes_per_px_iter = 0.0;
+    int result_set = -1;         // >= 0: `enqueue` ends every chain in this set, whatever niter and T (segmented sequences)
+    std::function<int(bool stagger)> chain_launches;   // optional: launches of one chain of such a sequence (statistics)
     GraphKey key{};
     // launch the iterations [it0, it1) of the images [lo, hi) on st from the state set cur; returns the set holding the
     // result.  stagger: the first launch fuses T/2 iterations and writes set 1
@@ -1085,7 +1098,14 @@ struct ChainSolve {
 // The stagger / ping-pong loop of a ChainSolve::enqueue whose launches tile like the weighted kernel (32 x 32 regions, T
 // iterations each): `launch` fills the model's argument struct for one launch -- the iterations [it, it + nit) of the images
 // [lo, hi) on st, from the state set cur into nxt; first: it == 0 -- and launches its kernel.  (Defined with the taped solves.)
-struct LaunchStep { hipStream_t st; int it, nit, cur, nxt, first, lo, hi; };
+// Checkpointed taped sequences add: tk0, the tape base iteration of the launch's segment, and a
+// checkpoint slot (nplanes planes, M*N*O doubles apart) the launch reads its state from / writes it to instead of a state set.
+struct LaunchStep {
+    hipStream_t st; int it, nit, cur, nxt, first, lo, hi;
+    int tk0 = 0;
+    const double* ckin = nullptr;
+    double* ckout = nullptr;
+};
 using LaunchFn = std::function<void(const LaunchStep&)>;
 EnqueueFn launch_loop(int T, LaunchFn launch);
 
@@ -1178,12 +1198,16 @@ int run_chains(bpltv_t* h, const bpltv_params& p, const ChainSolve& j, int* resu
             }
             h->st.launch_chains = (int)ex->size();
             h->st.graph_used = 1;
-            buf = chain_result_set(j.niter, j.T);
+            buf = j.result_set >= 0 ? j.result_set : chain_result_set(j.niter, j.T);
             launches = chain_launches(j.niter, j.T, (int)ex->size(), oop);
+            if (j.chain_launches) {
+                launches = 0;
+                for (size_t c = 0; c < ex->size(); ++c) launches += j.chain_launches((c & 1) && oop);
+            }
         } else {
             buf = j.enqueue(h->stream, 0, j.niter, buf, 0, j.nimg, false);
             HIPCHK(h, hipGetLastError());
-            launches = nl;
+            launches = j.chain_launches ? j.chain_launches(false) : nl;
         }
     }
     if (j.end)
@@ -3378,7 +3402,8 @@ int sr_unrolled_plan(bpltv_t* h, const bpltv_params& p, int cap, WeightedPlan* p
     if (pl->T < 1 || pl->nTi < 1 || pl->nTj < 1) return set_err(h, BPLTV_E_ARG, "cannot tile %dx%d with T=%d", h->M, h->N, pl->T);
     if (h->O > 65535) return set_err(h, BPLTV_E_UNSUPPORTED, "the sum-of-regularisers solve takes at most 65535 problems per launch (problems are a grid dimension)");
     if (!h->srun_ready) {
-        for (auto k : {&sr_unrolled_tile_kernel<SR_SHARED>, &sr_unrolled_tile_kernel<SR_EACH>})
+        for (auto k : {&sr_unrolled_tile_kernel<SR_SHARED, true>, &sr_unrolled_tile_kernel<SR_EACH, true>, &sr_unrolled_tile_kernel<SR_SHARED, false>,
+                       &sr_unrolled_tile_kernel<SR_EACH, false>})
             HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sr_lds_bytes(SRUN_R, SRUN_R)));
         for (auto k : {&sr_unrolled_reverse_tile_kernel<SR_SHARED>, &sr_unrolled_reverse_tile_kernel<SR_EACH>})
             HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(k), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sr_lds_bytes(SRUN_R, SRUN_R)));
@@ -3387,13 +3412,28 @@ int sr_unrolled_plan(bpltv_t* h, const bpltv_params& p, int cap, WeightedPlan* p
     return BPLTV_OK;
 }
 
-// What one launch of a taped solve reads besides the handle's last parameter, data and state sets ...
+// What one launch of a taped solve reads besides the resident f: its two state sets, the parameter (and weight) and the tape --
+// the handle's last ones for a solve, planes of its own, the staged parameter and the segment tape for the recompute of a
+// checkpointed sweep.  tape == nullptr: the no-tape instantiation (the checkpoint pass) ...
 struct TapedFwd {
     bpltv_t* h;
     WeightedPlan pl;
     const double* tab;
     double* tape;
+    double* S[2][7];
+    const double* alpha;
+    int am, an;
+    int astride;         // doubles between per-image parameter blocks (0: one block for every image)
+    const double* w;     // weighted model
+    int wo;
 };
+// the planes a launch reads and writes: a state set, or the step's checkpoint slot
+static void taped_planes(const LaunchStep& s, int np, size_t tot, double* const (*S)[7], const double** in, double** out) {
+    for (int c = 0; c < np; ++c) {
+        in[c] = s.ckin ? s.ckin + (size_t)c * tot : S[s.cur][c];
+        out[c] = s.ckout ? s.ckout + (size_t)c * tot : S[s.nxt][c];
+    }
+}
 // ... and one launch of a reverse sweep: the staged parameter (and weight) g, the sweep's planes S | gf | ga | g0 (the cotangent,
 // which the first launch reads in place of S[cur][0]) and gw (nullptr: not wanted), K = maxiter
 struct TapedRev {
@@ -3426,6 +3466,7 @@ struct TapedModel {
     int fwd_variant, rev_variant;
     int region;                   // statistics: region_i = region_j
     double bytes, bytes_map;      // bytes_per_px_iter of the solve with a scalar or patch parameter / with a map
+    double plain_bytes, plain_bytes_map;   // ... of the model's plain solve: the checkpoint pass writes no tape
     double* bpltv_handle::* sweep;   // the reverse sweep's planes [2 sets x nplanes | gf | slices x ga | gu], allocated on first use
     const char* sweep_name;
     int adjoint_method;
@@ -3438,13 +3479,16 @@ struct TapedModel {
 void tv_launch_fwd(const TapedFwd& x, const LaunchStep& s) {
     bpltv_t* h = x.h;
     UnrolledArgs a;
-    a.xin = h->d_state[s.cur][0]; a.y1in = h->d_state[s.cur][1]; a.y2in = h->d_state[s.cur][2];
-    a.xout = h->d_state[s.nxt][0]; a.y1out = h->d_state[s.nxt][1]; a.y2out = h->d_state[s.nxt][2];
-    a.f = h->d_f; a.alpha = h->d_alpha; a.tab = x.tab; a.tape = x.tape; a.plane = h->tot;
-    a.am = h->last_am; a.an = h->last_an; a.istride = h->alpha_istride;
-    a.it0 = s.it; a.nit = s.nit;
+    const double* in[3];
+    double* out[3];
+    taped_planes(s, 3, h->tot, x.S, in, out);
+    a.xin = in[0]; a.y1in = in[1]; a.y2in = in[2];
+    a.xout = out[0]; a.y1out = out[1]; a.y2out = out[2];
+    a.f = h->d_f; a.alpha = x.alpha; a.tab = x.tab; a.tape = x.tape; a.plane = h->tot;
+    a.am = x.am; a.an = x.an; a.istride = x.astride;
+    a.it0 = s.it; a.nit = s.nit; a.tk0 = s.tk0;
     a.M = h->M; a.N = h->N; a.halo = x.pl.T; a.first = s.first; a.img0 = s.lo;
-    hipLaunchKernelGGL(unrolled_tile_kernel, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), s.st, a);
+    hipLaunchKernelGGL(x.tape ? &unrolled_tile_kernel<true> : &unrolled_tile_kernel<false>, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), s.st, a);
 }
 void tv_launch_rev(const TapedRev& x, const LaunchStep& s) {   // `it` counts reverse steps: step r undoes iteration K - 1 - r
     const GradCtx& g = *x.g;
@@ -3453,24 +3497,27 @@ void tv_launch_rev(const TapedRev& x, const LaunchStep& s) {   // `it` counts re
     a.gxout = x.S[s.nxt][0]; a.gy1out = x.S[s.nxt][1]; a.gy2out = x.S[s.nxt][2];
     a.gf = x.gf; a.ga = x.ga; a.tape = x.tape; a.alpha = g.alpha; a.tab = x.tab; a.plane = x.h->tot;
     a.am = g.am; a.an = g.an; a.istride = g.astride;
-    a.khi = x.K - 1 - s.it; a.nit = s.nit;
+    a.khi = x.K - 1 - s.it; a.nit = s.nit; a.tk0 = s.tk0;
     a.M = x.h->M; a.N = x.h->N; a.halo = x.pl.T; a.first = s.first; a.img0 = s.lo;
     hipLaunchKernelGGL(unrolled_reverse_tile_kernel, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), s.st, a);
 }
 
-void weighted_launch_fwd(const TapedFwd& x, const LaunchStep& s) {   // with the handle's d_w / w_wo
+void weighted_launch_fwd(const TapedFwd& x, const LaunchStep& s) {
     bpltv_t* h = x.h;
     WeightedUnrolledArgs a;
-    a.xin = h->d_state[s.cur][0]; a.y1in = h->d_state[s.cur][1]; a.y2in = h->d_state[s.cur][2];
-    a.xout = h->d_state[s.nxt][0]; a.y1out = h->d_state[s.nxt][1]; a.y2out = h->d_state[s.nxt][2];
-    a.f = h->d_f; a.w = h->d_w; a.alpha = h->d_alpha; a.tab = x.tab; a.tape = x.tape; a.plane = h->tot;
-    a.wstride = h->w_wo > 1 ? h->npx : 0;
-    a.am = h->last_am; a.an = h->last_an;
-    a.it0 = s.it; a.nit = s.nit;
+    const double* in[3];
+    double* out[3];
+    taped_planes(s, 3, h->tot, x.S, in, out);
+    a.xin = in[0]; a.y1in = in[1]; a.y2in = in[2];
+    a.xout = out[0]; a.y1out = out[1]; a.y2out = out[2];
+    a.f = h->d_f; a.w = x.w; a.alpha = x.alpha; a.tab = x.tab; a.tape = x.tape; a.plane = h->tot;
+    a.wstride = x.wo > 1 ? h->npx : 0;
+    a.am = x.am; a.an = x.an;
+    a.it0 = s.it; a.nit = s.nit; a.tk0 = s.tk0;
     a.M = h->M; a.N = h->N; a.halo = x.pl.T; a.first = s.first; a.img0 = s.lo;
-    hipLaunchKernelGGL(weighted_unrolled_tile_kernel, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), s.st, a);
+    hipLaunchKernelGGL(x.tape ? &weighted_unrolled_tile_kernel<true> : &weighted_unrolled_tile_kernel<false>, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), s.st, a);
 }
-void weighted_launch_rev(const TapedRev& x, const LaunchStep& s) {   // the resident f is read for gw only
+void weighted_launch_rev(const TapedRev& x, const LaunchStep& s) {   // the kernel reads the resident f for gw only
     const GradCtx& g = *x.g;
     WeightedUnrolledRevArgs a;
     a.gxin = s.first ? x.g0 : x.S[s.cur][0]; a.gy1in = x.S[s.cur][1]; a.gy2in = x.S[s.cur][2];
@@ -3478,20 +3525,21 @@ void weighted_launch_rev(const TapedRev& x, const LaunchStep& s) {   // the resi
     a.gf = x.gf; a.ga = x.ga; a.gw = x.gw; a.tape = x.tape; a.f = x.h->d_f; a.w = g.w; a.alpha = g.alpha; a.tab = x.tab;
     a.plane = x.h->tot; a.wstride = g.wo > 1 ? x.h->npx : 0;
     a.am = g.am; a.an = g.an;
-    a.khi = x.K - 1 - s.it; a.nit = s.nit;
+    a.khi = x.K - 1 - s.it; a.nit = s.nit; a.tk0 = s.tk0;
     a.M = x.h->M; a.N = x.h->N; a.halo = x.pl.T; a.first = s.first; a.img0 = s.lo;
     hipLaunchKernelGGL(weighted_unrolled_reverse_tile_kernel, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), s.st, a);
 }
 
-void sr_launch_fwd(const TapedFwd& x, const LaunchStep& s) {   // alpha_istride != 0: one parameter block per image
+void sr_launch_fwd(const TapedFwd& x, const LaunchStep& s) {   // astride != 0: one parameter block per image
     bpltv_t* h = x.h;
     SrUnrolledArgs a;
-    for (int c = 0; c < 7; ++c) { a.in[c] = h->d_sr[s.cur][c]; a.out[c] = h->d_sr[s.nxt][c]; }
-    a.f = h->d_f; a.alpha = h->d_alpha; a.tab = x.tab; a.tape = x.tape; a.plane = h->tot;
-    a.am = h->last_am; a.an = h->last_an; a.astride = h->alpha_istride;
-    a.it0 = s.it; a.nit = s.nit;
+    taped_planes(s, 7, h->tot, x.S, a.in, a.out);
+    a.f = h->d_f; a.alpha = x.alpha; a.tab = x.tab; a.tape = x.tape; a.plane = h->tot;
+    a.am = x.am; a.an = x.an; a.astride = x.astride;
+    a.it0 = s.it; a.nit = s.nit; a.tk0 = s.tk0;
     a.M = h->M; a.N = h->N; a.halo = 2 * x.pl.T; a.first = s.first; a.img0 = s.lo;
-    void (*kern)(SrUnrolledArgs) = h->alpha_istride != 0 ? &sr_unrolled_tile_kernel<SR_EACH> : &sr_unrolled_tile_kernel<SR_SHARED>;
+    void (*kern)(SrUnrolledArgs) = x.astride != 0 ? (x.tape ? &sr_unrolled_tile_kernel<SR_EACH, true> : &sr_unrolled_tile_kernel<SR_EACH, false>)
+                                                  : (x.tape ? &sr_unrolled_tile_kernel<SR_SHARED, true> : &sr_unrolled_tile_kernel<SR_SHARED, false>);
     hipLaunchKernelGGL(kern, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(SRUN_R * SRUN_R), sr_lds_bytes(SRUN_R, SRUN_R), s.st, a);
 }
 void sr_launch_rev(const TapedRev& x, const LaunchStep& s) {
@@ -3501,7 +3549,7 @@ void sr_launch_rev(const TapedRev& x, const LaunchStep& s) {
     if (s.first) a.in[0] = x.g0;
     a.gf = x.gf; a.ga = x.ga; a.tape = x.tape; a.alpha = g.alpha; a.tab = x.tab; a.plane = x.h->tot;
     a.am = g.am; a.an = g.an; a.astride = g.astride;
-    a.khi = x.K - 1 - s.it; a.nit = s.nit;
+    a.khi = x.K - 1 - s.it; a.nit = s.nit; a.tk0 = s.tk0;
     a.M = x.h->M; a.N = x.h->N; a.halo = 2 * x.pl.T; a.first = s.first; a.img0 = s.lo;
     void (*kern)(SrUnrolledRevArgs) = g.each ? &sr_unrolled_reverse_tile_kernel<SR_EACH> : &sr_unrolled_reverse_tile_kernel<SR_SHARED>;
     hipLaunchKernelGGL(kern, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(SRUN_R * SRUN_R), sr_lds_bytes(SRUN_R, SRUN_R), s.st, a);
@@ -3515,7 +3563,7 @@ const TapedModel kTapedTV = [] {
     m.slices = 1; m.weighted = false; m.nplanes = 3; m.L2 = 8.0;
     m.plan = unrolled_plan; m.fwd_cap = PDHG_MAX_T; m.rev_cap = UN_REV_T;
     m.graphs = MODEL_UN; m.fwd_variant = 0; m.rev_variant = 1;
-    m.region = UN_R; m.bytes = 72.0; m.bytes_map = 80.0;
+    m.region = UN_R; m.bytes = 72.0; m.bytes_map = 80.0; m.plain_bytes = 56.0; m.plain_bytes_map = 64.0;
     m.sweep = &bpltv_handle::d_unr; m.sweep_name = "reverse sweep";
     m.adjoint_method = 7; m.tv_stats = true;
     m.launch_fwd = tv_launch_fwd; m.launch_rev = tv_launch_rev;
@@ -3529,7 +3577,7 @@ const TapedModel kTapedWeighted = [] {
     m.tape = &bpltv_handle::wtape; m.tape_planes = 3;
     m.weighted = true; m.rev_cap = WUN_REV_T;
     m.fwd_variant = 6; m.rev_variant = 7;
-    m.bytes = 88.0; m.bytes_map = 96.0;
+    m.bytes = 88.0; m.bytes_map = 96.0; m.plain_bytes = 64.0; m.plain_bytes_map = 72.0;
     m.adjoint_method = 9; m.tv_stats = false;
     m.launch_fwd = weighted_launch_fwd; m.launch_rev = weighted_launch_rev;
     return m;
@@ -3543,7 +3591,7 @@ const TapedModel kTapedSr = [] {
     m.slices = 3; m.weighted = false; m.nplanes = 7; m.L2 = 18.0;
     m.plan = sr_unrolled_plan; m.fwd_cap = (SRUN_R - 1) / 4; m.rev_cap = SRUN_REV_T;
     m.graphs = MODEL_SRUN; m.fwd_variant = 0; m.rev_variant = 1;
-    m.region = SRUN_R; m.bytes = 168.0; m.bytes_map = 192.0;
+    m.region = SRUN_R; m.bytes = 168.0; m.bytes_map = 192.0; m.plain_bytes = 120.0; m.plain_bytes_map = 144.0;
     m.sweep = &bpltv_handle::d_srunr; m.sweep_name = "sum-of-regularisers reverse sweep";
     m.adjoint_method = 10; m.tv_stats = false;
     m.launch_fwd = sr_launch_fwd; m.launch_rev = sr_launch_rev;
@@ -3570,12 +3618,44 @@ int sweep_stats(bpltv_t* h, int method) {
     return BPLTV_OK;
 }
 
+// Checkpointing (option "tape_checkpoint").  The effective spacing of a call of K iterations: 0 (the
+// full tape), min(C, K), or (C = -1) the C that minimises nplanes * ceil(K / C) + tape_planes * C up to rounding:
+// ceil(sqrt(nplanes * K / tape_planes)) in [1, K], in integers.
+int tape_spacing(const TapedModel& m, int K, int C) {
+    if (C == 0) return 0;
+    if (C > 0) return std::min(C, K);
+    const long long need = (long long)m.nplanes * K;
+    long long c = (long long)std::sqrt((double)need / m.tape_planes);
+    while (c * c * m.tape_planes < need) ++c;
+    while (c > 1 && (c - 1) * (c - 1) * m.tape_planes >= need) --c;
+    return (int)std::min<long long>(std::max<long long>(c, 1), K);
+}
+inline int tape_segments(int K, int C) { return (K + C - 1) / C; }
+
+// The launches of the iterations [0, K) in segments of C, at most T per launch and none across a segment boundary:
+// fn(it, nit, k0, e) for the iterations [it, it + nit) of the segment [k0, e).  stagger: the very first launch has T/2.
+template <class F>
+void segment_launches(int K, int C, int T, bool stagger, F fn) {
+    int step = (stagger && T >= 2) ? T / 2 : T;
+    for (int k0 = 0; k0 < K; k0 += C) {
+        const int e = std::min(k0 + C, K);
+        for (int it = k0; it < e; step = T) {
+            const int nit = std::min(step, e - it);
+            fn(it, nit, k0, e);
+            it += nit;
+        }
+    }
+}
+
 // The taped solves on a single-device handle: bpltv_unrolled_denoise, bpltv_weighted_unrolled_denoise and
 // bpltv_sumregs_unrolled_denoise with their _each and _device forms.  maxiter taped iterations on the dataset images, in the
 // model's state sets, with d_alpha (each: O blocks, image k reads block k: upload_alpha); what the reverse sweep needs of
 // every iteration and pixel goes onto d_tape_user, or (nullptr) onto the handle's own tape of the model, which grows here.
 // The order is the contract: arguments, params, w, then the grown tape -- allocated before anything changes and installed only
 // once upload_alpha has accepted the parameter -- and only then the handle's copy of w.
+// With a checkpoint spacing C (option "tape_checkpoint") the same launches, cut at the segment boundaries, run the no-tape
+// instantiation; the launch that ends segment s - 1 writes its state into slot s of the buffer instead of a state set, and
+// the next one reads it from there (slot 0: x = f, y = 0).  The result ends in state set 0.
 int taped_denoise(bpltv_t* h, const TapedModel& m, const double* w, int wo, const double* alpha, bool dev, int am, int an,
                   const bpltv_params* pp, double* d_tape_user, double* u_out, bool each) {
     const std::string name = std::string(m.denoise) + (each ? "_each" : "") + (dev ? "_device" : "");
@@ -3599,7 +3679,9 @@ int taped_denoise(bpltv_t* h, const TapedModel& m, const double* w, int wo, cons
     double wmin = 0.0;
     int rc = m.weighted ? check_weight(h, who, w, dev, nw, &wmin) : (int)BPLTV_OK;
     if (rc) return rc;
-    const size_t need = (size_t)m.tape_planes * p.maxiter * h->tot;
+    const int K = p.maxiter, C = tape_spacing(m, K, h->opt.tape_checkpoint), np = m.nplanes;
+    const size_t tot = h->tot;
+    const size_t need = C ? (size_t)np * tape_segments(K, C) * tot : (size_t)m.tape_planes * K * tot;
     double* grown = nullptr;
     if (!d_tape_user) {
         const hipError_t e = tape.grow(need, &grown);
@@ -3632,15 +3714,55 @@ int taped_denoise(bpltv_t* h, const TapedModel& m, const double* w, int wo, cons
     if (rc) return rc;
     const bool amap = (h->last_am == h->M && h->last_an == h->N) && !(h->M == 1 && h->N == 1);
     h->st.tile_iters = pl.T; h->st.tiles = pl.nTi * pl.nTj * h->O; h->st.region_i = m.region; h->st.region_j = m.region; h->st.pdhg_variant = 0;
-    const TapedFwd x{h, pl, d_tab, d_tape_user ? d_tape_user : tape.d};
+    double* const buffer = d_tape_user ? d_tape_user : tape.d;   // the tape, or the checkpoints
+    TapedFwd x{h, pl, d_tab, C ? nullptr : buffer, {}, h->d_alpha, h->last_am, h->last_an, h->alpha_istride, h->d_w, h->w_wo};
+    for (int s = 0; s < 2; ++s)
+        for (int c = 0; c < np; ++c) x.S[s][c] = sr ? h->d_sr[s][c] : h->d_state[s][c];
     ChainSolve j;
-    j.model = m.graphs; j.nplanes = m.nplanes; j.state0 = sr ? h->d_sr[0] : h->d_state[0];
+    j.model = m.graphs; j.nplanes = np; j.state0 = sr ? h->d_sr[0] : h->d_state[0];
     taped_chains(h, p, pl, &j);
-    j.bytes_per_px_iter = amap ? m.bytes_map : m.bytes;
+    j.bytes_per_px_iter = C ? (amap ? m.plain_bytes_map : m.plain_bytes) : (amap ? m.bytes_map : m.bytes);
     // (istride: a per-image solve uploads into d_alpha like a shared one, and must not replay its graph, nor the reverse)
-    j.key = GraphKey{p.maxiter, pl.T, m.fwd_variant, h->last_am, h->last_an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)x.tape, (const void*)d_tab, 0,
-                     (const void*)h->d_alpha, m.weighted ? 0 : h->alpha_istride, m.weighted ? h->w_wo : 0};
-    j.enqueue = launch_loop(pl.T, [&](const LaunchStep& s) { m.launch_fwd(x, s); });
+    j.key = GraphKey{K, pl.T, m.fwd_variant, h->last_am, h->last_an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)buffer, (const void*)d_tab, 0,
+                     (const void*)h->d_alpha, m.weighted ? 0 : h->alpha_istride, m.weighted ? h->w_wo : 0, C, nullptr, 0};
+    if (!C) {
+        j.enqueue = launch_loop(pl.T, [&](const LaunchStep& s) { m.launch_fwd(x, s); });
+    } else {
+        const int T = pl.T;
+        auto to_slot = [K](int nit_end, int e) { return nit_end == e && e < K; };   // the launch ends a segment that has a successor
+        // slot 0, the state every solve starts from, is layout only: it keeps the slots uniform and a caller's buffer fully
+        // defined, but neither the solve nor the sweep reads it -- segment 0 starts with first = 1, as a full-tape solve does
+        j.begin = [&]() {
+            HIPCHK(h, hipMemcpyAsync(buffer, h->d_f, tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+            HIPCHK(h, hipMemsetAsync(buffer + tot, 0, (size_t)(np - 1) * tot * sizeof(double), h->stream));
+            return (int)BPLTV_OK;
+        };
+        j.result_set = 0;
+        j.chain_launches = [=](bool stagger) {
+            int n = 0;
+            segment_launches(K, C, T, stagger, [&](int, int, int, int) { ++n; });
+            return n;
+        };
+        // the launches that write a state set alternate so that the last one writes set 0; one that reads a set reads the one
+        // written last, which is the other one
+        j.enqueue = [&, K, C, T, np, tot, buffer, to_slot](hipStream_t st, int, int, int, int lo, int hi, bool stagger) {
+            int W = 0, wr = 0, cur = 0;
+            segment_launches(K, C, T, stagger, [&](int it, int nit, int, int e) { W += to_slot(it + nit, e) ? 0 : 1; });
+            segment_launches(K, C, T, stagger, [&](int it, int nit, int k0, int e) {
+                LaunchStep ls{st, it, nit, cur, cur, (it == 0) ? 1 : 0, lo, hi};
+                if (it == k0 && it > 0) ls.ckin = buffer + (size_t)(k0 / C) * np * tot;
+                if (to_slot(it + nit, e)) {
+                    ls.ckout = buffer + (size_t)(e / C) * np * tot;
+                } else {
+                    ls.nxt = (W - 1 - wr) % 2;
+                    ++wr;
+                    cur = ls.nxt;
+                }
+                m.launch_fwd(x, ls);
+            });
+            return 0;
+        };
+    }
     int buf = 0;
     rc = run_chains(h, p, j, &buf);
     if (rc) return rc;
@@ -3653,7 +3775,7 @@ int taped_denoise(bpltv_t* h, const TapedModel& m, const double* w, int wo, cons
     }
     h->last_is_sr = sr;
     h->last_weighted = m.weighted;
-    if (!d_tape_user) tape.record(p, am, an, each, m.weighted ? wo : 0, wmin);
+    if (!d_tape_user) tape.record(p, am, an, each, m.weighted ? wo : 0, wmin, C);
     if (u_out) {
         HIPCHK(h, hipMemcpyAsync(u_out, sr ? h->d_sr[buf][0] : h->d_state[buf][0], h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3696,6 +3818,11 @@ int reduce_grad_alpha(bpltv_t* h, const double* d_ga, int slices, int am, int an
 // which must have been recorded by this call's solve.  Parameter and weight are staged apart (stage_param) and the sweep runs
 // in planes of its own, so the last solve stays untouched; the solve statistics are put back after the shared driver has run
 // the sweep.  The step table is the solve's (weighted: gamma = min w), held fixed.  d_grad_w (weighted only) needs the resident f.
+// With a checkpoint spacing C (option "tape_checkpoint") the buffer holds the checkpoints of that spacing, and the sweep runs
+// segment by segment, last to first, all in one launch sequence: the taping kernel re-runs the segment's iterations from its
+// checkpoint on the staged parameter (and weight) and the resident f, in state planes of its own, into the handle's segment
+// tape (d_seg); the reverse kernel then undoes them, carrying its planes on from the segment before.  The checkpoints are
+// only read.  An out-of-phase chain starts its first recompute launch at half depth, as the solve's does.
 int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const double* w, int wo, const double* alpha, bool dev, int am,
               int an, const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alpha, double* d_grad_w, bool each) {
     const std::string name = std::string(m.vjp) + (each ? "_each" : "");
@@ -3709,6 +3836,9 @@ int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const 
     const bpltv_params p0 = resolve(pp, sr);
     if (int prc = unrolled_check_params(h, p0, who)) return prc;
     if (d_grad_w && !h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: grad_w reads the resident f: bpltv_set_data has not been called", who);
+    const int K = p0.maxiter, C = tape_spacing(m, K, h->opt.tape_checkpoint);
+    if (C && !h->has_data)
+        return set_err(h, BPLTV_E_NODATA, "%s: a checkpointed sweep recomputes on the resident f: bpltv_set_data has not been called", who);
     if (!d_tape_user) {
         if (!tape.valid) return set_err(h, BPLTV_E_NODATA, "%s: the handle holds no %stape (%s has not run)", who, m.tape_kind, m.denoise);
         if (!tape.made_with(p0, am, an, m.weighted ? wo : 0))
@@ -3717,9 +3847,14 @@ int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const 
         if (tape.each != each)
             return set_err(h, BPLTV_E_ARG, "%s: the handle's tape was recorded with one %s (%s%s)", who,
                            tape.each ? "parameter block per image" : "shared parameter", m.denoise, tape.each ? "_each" : "");
+        if (tape.spacing != C)
+            return set_err(h, BPLTV_E_ARG, "%s: the handle's %stape was recorded with checkpoint spacing %d (0: the full tape), option tape_checkpoint gives %d",
+                           who, m.tape_kind, tape.spacing, C);
     }
-    WeightedPlan pl;
+    WeightedPlan pl, plf{};
     if (int prc = m.plan(h, p0, m.rev_cap, &pl)) return prc;
+    if (C)
+        if (int prc = m.plan(h, p0, m.fwd_cap, &plf)) return prc;
     const size_t tot = h->tot, npx = h->npx;
     const int np = m.nplanes;
     double*& d_ws = h->*m.sweep;
@@ -3740,6 +3875,21 @@ int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const 
     h->has_per_image = false;
     double* d_tab = nullptr;
     if (int rc = get_table(h, p, &d_tab, m.L2, 0, m.weighted ? g.w_min : 1.0)) return rc;
+    const size_t seg_tape = (size_t)m.tape_planes * C * tot, seg_need = seg_tape + (size_t)2 * np * tot;
+    // grown after the last rejection, so that a rejected call never moves it (and orphans the graphs keyed by it); the new
+    // buffer first: a failed allocation leaves the handle as it was
+    if (C && h->seg_cap < seg_need) {
+        double* d_new = nullptr;
+        const hipError_t e = hipMalloc((void**)&d_new, seg_need * sizeof(double));
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return set_err(h, e == hipErrorOutOfMemory ? BPLTV_E_NOMEM : BPLTV_E_HIP, "%s: hipMalloc of the segment tape (%.1f MB) failed: %s", who,
+                           seg_need * sizeof(double) / 1e6, hipGetErrorString(e));
+        }
+        if (h->d_seg) (void)hipFree(h->d_seg);
+        h->d_seg = d_new;
+        h->seg_cap = seg_need;
+    }
     TapedRev x{h, pl, d_tab, d_tape_user ? d_tape_user : tape.d, &g, {}, d_ws + (size_t)2 * np * tot, d_ws + (size_t)(2 * np + 1) * tot,
                d_ws + (size_t)(2 * np + 1 + m.slices) * tot, d_grad_w ? h->d_unr_gw : nullptr, p.maxiter};
     for (int s = 0; s < 2; ++s)
@@ -3752,8 +3902,53 @@ int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const 
     taped_chains(h, p, pl, &j);
     j.bytes_per_px_iter = 0.0;   // (the driver's solve statistics are not this call's: `kept` goes back below)
     j.key = GraphKey{p.maxiter, pl.T, m.rev_variant + (x.gw ? 1 : 0), am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)x.tape, (const void*)d_tab, 0,
-                     (const void*)g.alpha, m.weighted ? 0 : g.astride, m.weighted ? wo : 0};
-    j.enqueue = launch_loop(pl.T, [&](const LaunchStep& s) { m.launch_rev(x, s); });
+                     (const void*)g.alpha, m.weighted ? 0 : g.astride, m.weighted ? wo : 0, C, C ? (const void*)h->d_seg : nullptr, C ? plf.T : 0};
+    TapedFwd xf{h, plf, d_tab, h->d_seg, {}, g.alpha, g.am, g.an, g.astride, g.w, g.wo};   // the recompute of a segment
+    if (!C) {
+        j.enqueue = launch_loop(pl.T, [&](const LaunchStep& s) { m.launch_rev(x, s); });
+    } else {
+        const int Tr = pl.T, Tf = plf.T, nseg = tape_segments(K, C);
+        const double* const ck = x.tape;   // the checkpoints
+        x.tape = h->d_seg;                 // what the reverse launches read
+        for (int s = 0; s < 2; ++s)
+            for (int c = 0; c < np; ++c) xf.S[s][c] = h->d_seg + seg_tape + (size_t)(np * s + c) * tot;
+        auto rev_launches = [=](int len) { return (len + Tr - 1) / Tr; };
+        int W = 0, F = 0;   // reverse / recompute launches of a chain
+        for (int k0 = 0; k0 < K; k0 += C) {
+            W += rev_launches(std::min(C, K - k0));
+            F += (std::min(C, K - k0) + Tf - 1) / Tf;
+        }
+        // an out-of-phase chain: the first recompute launch (of the last segment) has Tf / 2 iterations
+        const int last_len = K - (nseg - 1) * C, half = Tf / 2;
+        const int F_oop = F - (last_len + Tf - 1) / Tf + 1 + (last_len > half && half > 0 ? (last_len - half + Tf - 1) / Tf : 0);
+        j.result_set = 0;
+        j.chain_launches = [=](bool stagger) { return W + ((stagger && half > 0) ? F_oop : F); };
+        // the reverse launches alternate between the sweep's two sets so that the last one writes set 0
+        j.enqueue = [&, K, C, Tr, Tf, nseg, np, tot, ck, W](hipStream_t st, int, int, int, int lo, int hi, bool stagger) {
+            int wr = 0, rcur = 0;
+            int step = (stagger && Tf >= 2) ? Tf / 2 : Tf;
+            for (int sg = nseg - 1; sg >= 0; --sg) {
+                const int k0 = sg * C, e = std::min(k0 + C, K);
+                int fcur = 0;
+                for (int it = k0, nit = 0; it < e; it += nit, step = Tf) {
+                    nit = std::min(step, e - it);
+                    LaunchStep ls{st, it, nit, fcur, 1 - fcur, (it == 0) ? 1 : 0, lo, hi};
+                    ls.tk0 = k0;
+                    if (it == k0 && it > 0) ls.ckin = ck + (size_t)sg * np * tot;
+                    m.launch_fwd(xf, ls);
+                    fcur = 1 - fcur;
+                }
+                for (int khi = e - 1; khi >= k0; khi -= Tr) {
+                    LaunchStep ls{st, K - 1 - khi, std::min(Tr, khi - k0 + 1), rcur, (W - 1 - wr) % 2, (wr == 0) ? 1 : 0, lo, hi};
+                    ls.tk0 = k0;
+                    m.launch_rev(x, ls);
+                    rcur = ls.nxt;
+                    ++wr;
+                }
+            }
+            return 0;
+        };
+    }
     int buf = 0;
     const int rc = run_chains(h, p, j, &buf);
     h->st = kept;
@@ -3984,7 +4179,7 @@ int bpltv_destroy(bpltv_t* h) {
     if (h->f32_sweep_alpha) (void)hipFree(h->f32_sweep_alpha);
     void* ptrs[] = {h->d_ubar, h->d_f, h->d_alpha, h->d_sweep_alpha, h->d_partial, h->d_red, h->d_perimg, h->d_scalar, h->d_coef,
                     h->d_band4, h->d_bcr, h->d_L, h->d_invF, h->d_invB, h->d_L1, h->d_dump, h->d_Lm, h->d_spill, h->d_p, h->d_r, h->d_gpix, h->d_resn, h->d_fail, h->d_u2, h->d_ubar2,
-                    h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres, h->d_w, h->d_wst, h->d_unr, h->d_ujv, h->d_unr_gw, h->d_srunr};
+                    h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres, h->d_w, h->d_wst, h->d_unr, h->d_ujv, h->d_unr_gw, h->d_srunr, h->d_seg};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (Tape* t : {&h->tape, &h->wtape, &h->srtape}) t->release();
@@ -4026,6 +4221,8 @@ static int set_data_impl(bpltv_t* h, const double* ubar, const double* f, hipMem
     h->has_data = true;
     h->has_result = false;
     h->f32_f_valid = false;
+    for (Tape* t : {&h->tape, &h->wtape, &h->srtape})   // checkpoints are states of the solve on the old f: the sweep would recompute on the new one
+        if (t->spacing) t->valid = false;
     return BPLTV_OK;
 }
 
@@ -4234,7 +4431,9 @@ static int tape_doubles_entry(bpltv_t* h, const TapedModel& m, const char* what,
     if (!n_out) return set_err(h, BPLTV_E_ARG, "%s: null pointer", what);
     const bpltv_params p = resolve(pp, m.slices == 3);
     if (p.maxiter < 1) return set_err(h, BPLTV_E_ARG, "%s: maxiter = %d (at least one iteration)", what, p.maxiter);
-    *n_out = (unsigned long long)m.tape_planes * (unsigned long long)p.maxiter * (unsigned long long)h->M * h->N * h->O;
+    const int C = tape_spacing(m, p.maxiter, h->opt.tape_checkpoint);   // checkpoints: one state set per segment
+    const unsigned long long planes = C ? (unsigned long long)m.nplanes * tape_segments(p.maxiter, C) : (unsigned long long)m.tape_planes * p.maxiter;
+    *n_out = planes * (unsigned long long)h->M * h->N * h->O;
     return BPLTV_OK;
 }
 
@@ -4860,6 +5059,11 @@ int bpltv_set_option(bpltv_t* h, const char* name, double value) {
             h->multi->sweep_split = v;
             return BPLTV_OK;
         }
+        if (nm == "tape_checkpoint") {   // (the handle's own copy: bpltv_*_unrolled_tape_doubles reads it)
+            if (value != std::floor(value) || value < -1.0 || value > 2147483647.0)
+                return set_err(h, BPLTV_E_ARG, "set_option(tape_checkpoint): 0 the full tape, C >= 1 iterations between checkpoints, -1 automatic");
+            h->opt.tape_checkpoint = (int)value;
+        }
         int rc = multi_run(h, [&](int, bpltv_t* c) { return bpltv_set_option(c, nm.c_str(), value); });
         if (rc == BPLTV_OK && !h->multi->rep.empty())
             rc = rep_run(h, (int)h->multi->rep.size(), [&](int r, bpltv_t* c) { return (r == 0 && h->multi->rep_borrowed0()) ? BPLTV_OK : bpltv_set_option(c, nm.c_str(), value); });
@@ -4877,6 +5081,10 @@ int bpltv_set_option(bpltv_t* h, const char* name, double value) {
         h->opt.sr_sweep_budget_mb = value;
     } else if (nm == "sr_force_lu") {
         h->opt.sr_force_lu = iv ? 1 : 0;
+    } else if (nm == "tape_checkpoint") {
+        if (value != std::floor(value) || value < -1.0 || value > 2147483647.0)
+            return set_err(h, BPLTV_E_ARG, "set_option(tape_checkpoint): 0 the full tape, C >= 1 iterations between checkpoints, -1 automatic");
+        h->opt.tape_checkpoint = iv;
     } else if (nm == "nd_leaf") {
         if (iv < 0 || iv > 4096) return set_err(h, BPLTV_E_ARG, "set_option(nd_leaf): 0 (default) or 1..4096 pixels");
         if (iv != h->opt.nd_leaf) {   // the trees are built for a leaf size: drop them

@@ -35,10 +35,12 @@ struct SrUnrolledArgs {
     const double* f;       // the dataset, O planes
     const double* alpha;   // one block of 3 slices of am*an doubles (SR_SHARED), or one per image, astride apart (SR_EACH)
     const double* tab;     // [maxiter][TAB_STRIDE], L = sqrt(18)
-    double* tape;          // [maxiter][6][O][M*N]
+    double* tape;          // [maxiter][6][O][M*N] (TAPE = false: not read)
     size_t plane;          // O * M*N: doubles of one tape component
     int am, an;
     int it0, nit;
+    int tk0;               // tape base iteration: iteration k lives in slot k - tk0 (0: the full tape; a checkpointed sweep's
+                           // segment tape starts at its segment's first iteration).  tab stays indexed by k itself
     int M, N;
     int halo;              // 2 * fused iterations
     int first;             // 1: start from x = f, y = 0
@@ -48,7 +50,8 @@ struct SrUnrolledArgs {
 
 // One workgroup per tile, grid (nTi, nTj, images), block 1024: sr_tile_kernel<32, 32> without the Huber branch, plus six
 // stores per iteration -- the duals before their projection -- for the core pixels (valid in every iteration of a launch).
-template <SrAddr ADDR>
+// TAPE = false: the same recurrence without those stores (the checkpoint pass).
+template <SrAddr ADDR, bool TAPE = true>
 __global__ __launch_bounds__(SRUN_R* SRUN_R) void sr_unrolled_tile_kernel(SrUnrolledArgs A) {
     static_assert(ADDR == SR_SHARED || ADDR == SR_EACH, "the taped solve runs in the dataset context");
     constexpr int RI = SRUN_R, RJ = SRUN_R, RN = RI * RJ;
@@ -103,7 +106,7 @@ __global__ __launch_bounds__(SRUN_R* SRUN_R) void sr_unrolled_tile_kernel(SrUnro
 
     const bool core = gi >= ci0 && gi < ci1 && gj >= cj0 && gj < cj1;
     const size_t idx = base + gi + (size_t)M * gj;   // used by core pixels only
-    double* tz = A.tape + (size_t)6 * A.plane * A.it0 + idx;
+    double* tz = TAPE ? A.tape + (size_t)6 * A.plane * (A.it0 - A.tk0) + idx : nullptr;
     const double* __restrict__ row = A.tab + (size_t)TAB_STRIDE * A.it0;
     double tau = row[0], sigma = row[1], omega = row[2], inv1ptau = row[3], opw = row[4];
     for (int it = 0; it < A.nit; ++it) {
@@ -140,11 +143,13 @@ __global__ __launch_bounds__(SRUN_R* SRUN_R) void sr_unrolled_tile_kernel(SrUnro
             y[2 * k + 1] = __builtin_fma(sigma, d2[k], y[2 * k + 1]);
             n2v[k] = __builtin_fma(y[2 * k + 1], y[2 * k + 1], y[2 * k] * y[2 * k]);
         }
-        if (core) {   // the tape: the duals before their projection
+        if (TAPE) {
+            if (core) {   // the tape: the duals before their projection
 #pragma unroll
-            for (int c = 0; c < 6; ++c) __hip_atomic_store(tz + c * A.plane, y[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                for (int c = 0; c < 6; ++c) __hip_atomic_store(tz + c * A.plane, y[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            tz += 6 * A.plane;
         }
-        tz += 6 * A.plane;
 #pragma unroll
         for (int k = 0; k < 3; ++k) {   // per regulariser: lanes outside the ball project
             const double a = al[k];
@@ -178,6 +183,7 @@ struct SrUnrolledRevArgs {
     size_t plane;
     int am, an;
     int khi, nit;          // this launch runs the iterations khi, khi - 1, ..., khi - nit + 1
+    int tk0;               // tape base iteration, as SrUnrolledArgs (khi - nit + 1 >= tk0)
     int M, N;
     int halo;              // 2 * fused reverse iterations
     int first;             // 1: start from gx = in[0], gy = gf = ga = 0
@@ -234,7 +240,7 @@ __global__ __launch_bounds__(SRUN_R* SRUN_R) void sr_unrolled_reverse_tile_kerne
     }
     al[0] = alpha[ai]; al[1] = alpha[sl + ai]; al[2] = alpha[2 * sl + ai];
     double z[SRUN_REV_T][6];   // [s]: iteration khi - s
-    const double* tz = A.tape + (size_t)6 * A.plane * A.khi + g;
+    const double* tz = A.tape + (size_t)6 * A.plane * (A.khi - A.tk0) + g;
 #pragma unroll
     for (int s = 0; s < SRUN_REV_T; ++s) {
 #pragma unroll

@@ -35,11 +35,13 @@ struct UnrolledArgs {
     const double* f;      // the dataset, O planes
     const double* alpha;  // am*an doubles, column major
     const double* tab;    // [maxiter][TAB_STRIDE]
-    double* tape;         // [maxiter][2][O][M*N]
+    double* tape;         // [maxiter][2][O][M*N] (TAPE = false: not read)
     size_t plane;         // O * M*N: doubles of one tape component
     int am, an;
     int istride;          // doubles between per-image parameter blocks: 0 = one block for every image, am*an = image k reads block k
     int it0, nit;
+    int tk0;              // tape base iteration: iteration k lives in slot k - tk0 (0: the full tape; a checkpointed sweep's
+                          // segment tape starts at its segment's first iteration).  tab stays indexed by k itself
     int M, N;
     int halo;
     int first;            // 1: start from x = f, y = 0
@@ -48,6 +50,8 @@ struct UnrolledArgs {
 
 // One workgroup per tile, grid (nTi, nTj, images), block 1024: weighted_tile_kernel's structure with the unweighted primal
 // step, plus two stores per iteration of the pre-projection dual for the core pixels (valid in every iteration of a launch).
+// TAPE = false: the same recurrence without those stores (the checkpoint pass of a checkpointed solve).
+template <bool TAPE>
 __global__ __launch_bounds__(UN_R * UN_R) void unrolled_tile_kernel(UnrolledArgs A) {
     constexpr int RI = UN_R, RJ = UN_R, S1 = RI + 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char un_smem[];
@@ -110,7 +114,7 @@ __global__ __launch_bounds__(UN_R * UN_R) void unrolled_tile_kernel(UnrolledArgs
     const int qi = oi + li, qj = oj + lj;
     const bool core = qi >= ci0 && qi < ci1 && qj >= cj0 && qj < cj1;
     const size_t idx = base + qi + (size_t)M * qj;   // used by core pixels only
-    double* tz = A.tape + (size_t)2 * A.plane * A.it0 + idx;
+    double* tz = TAPE ? A.tape + (size_t)2 * A.plane * (A.it0 - A.tk0) + idx : nullptr;
     // halo rows do not need all the iterations (pdhg_tile_kernel): a wave owns two adjacent rows; core rows run them all
     int my_nit = nit;
     if (N > RJ) {
@@ -139,11 +143,13 @@ __global__ __launch_bounds__(UN_R * UN_R) void unrolled_tile_kernel(UnrolledArgs
         const double d2 = sxb[n2] - b;
         double y1n = __builtin_fma(sigma, d1, y1);
         double y2n = __builtin_fma(sigma, d2, y2);
-        if (core) {   // the tape: the dual before the projection
-            __hip_atomic_store(tz, y1n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(tz + A.plane, y2n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (TAPE) {
+            if (core) {   // the tape: the dual before the projection
+                __hip_atomic_store(tz, y1n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(tz + A.plane, y2n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            tz += 2 * A.plane;
         }
-        tz += 2 * A.plane;
         const double nn = __builtin_fma(y2n, y2n, y1n * y1n);
         const bool outp = nn > al * al;
         if (outp) {   // a wave whose pixels all lie inside the ball skips the rsqrt
@@ -187,6 +193,7 @@ struct UnrolledRevArgs {
     int am, an;
     int istride;          // as UnrolledArgs: 0, or am*an for one parameter block per image
     int khi, nit;         // this launch runs the iterations khi, khi - 1, ..., khi - nit + 1
+    int tk0;              // tape base iteration, as UnrolledArgs (the launch stays inside the tape: khi - nit + 1 >= tk0)
     int M, N;
     int halo;
     int first;            // 1: start from gx = gxin, gy = gf = ga = 0
@@ -245,7 +252,7 @@ __global__ __launch_bounds__(UN_R * UN_R) void unrolled_reverse_tile_kernel(Unro
     }
     double al = A.alpha[ai];
     double z1[UN_REV_T], z2[UN_REV_T];   // z?[s]: iteration khi - s
-    const double* tz = A.tape + (size_t)2 * A.plane * A.khi + base + pix;
+    const double* tz = A.tape + (size_t)2 * A.plane * (A.khi - A.tk0) + base + pix;
 #pragma unroll
     for (int s = 0; s < UN_REV_T; ++s) {
         z1[s] = 0.0; z2[s] = 0.0;

@@ -37,11 +37,12 @@ struct WeightedUnrolledArgs {
     const double* w;      // fidelity weight: one plane (wstride 0) or O planes (wstride M*N)
     const double* alpha;  // am*an doubles, column major
     const double* tab;    // [maxiter][TAB_STRIDE]; the row's 1/(1 + tau) is not read
-    double* tape;         // [maxiter][3][O][M*N]
+    double* tape;         // [maxiter][3][O][M*N] (TAPE = false: not read)
     size_t plane;         // O * M*N: doubles of one tape component
     size_t wstride;
     int am, an;
     int it0, nit;
+    int tk0;              // tape base iteration, as UnrolledArgs: iteration k lives in slot k - tk0
     int M, N;
     int halo;
     int first;            // 1: start from x = f, y = 0
@@ -50,6 +51,8 @@ struct WeightedUnrolledArgs {
 
 // One workgroup per tile, grid (nTi, nTj, images), block 1024: weighted_tile_kernel plus three stores per iteration -- the
 // dual before the projection and the new primal iterate -- for the core pixels (valid in every iteration of a launch).
+// TAPE = false: the same recurrence without those stores (the checkpoint pass).
+template <bool TAPE>
 __global__ __launch_bounds__(UN_R * UN_R) void weighted_unrolled_tile_kernel(WeightedUnrolledArgs A) {
     constexpr int RI = UN_R, RJ = UN_R, S1 = RI + 1;
     extern __shared__ __attribute__((aligned(16))) unsigned char wun_smem[];
@@ -113,7 +116,7 @@ __global__ __launch_bounds__(UN_R * UN_R) void weighted_unrolled_tile_kernel(Wei
     const int qi = oi + li, qj = oj + lj;
     const bool core = qi >= ci0 && qi < ci1 && qj >= cj0 && qj < cj1;
     const size_t idx = base + qi + (size_t)M * qj;   // used by core pixels only
-    double* tz = A.tape + (size_t)3 * A.plane * A.it0 + idx;
+    double* tz = TAPE ? A.tape + (size_t)3 * A.plane * (A.it0 - A.tk0) + idx : nullptr;
     // halo rows do not need all the iterations (pdhg_tile_kernel): a wave owns two adjacent rows; core rows run them all
     int my_nit = nit;
     if (N > RJ) {
@@ -143,12 +146,14 @@ __global__ __launch_bounds__(UN_R * UN_R) void weighted_unrolled_tile_kernel(Wei
         const double d2 = sxb[n2] - b;
         double y1n = __builtin_fma(sigma, d1, y1);
         double y2n = __builtin_fma(sigma, d2, y2);
-        if (core) {   // the tape: the dual before the projection, and the primal iterate grad_w reads
-            __hip_atomic_store(tz, y1n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(tz + A.plane, y2n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(tz + 2 * A.plane, xn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (TAPE) {
+            if (core) {   // the tape: the dual before the projection, and the primal iterate grad_w reads
+                __hip_atomic_store(tz, y1n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(tz + A.plane, y2n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(tz + 2 * A.plane, xn, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+            tz += 3 * A.plane;
         }
-        tz += 3 * A.plane;
         const double nn = __builtin_fma(y2n, y2n, y1n * y1n);
         const bool outp = nn > al * al;
         if (outp) {   // a wave whose pixels all lie inside the ball skips the rsqrt
@@ -195,6 +200,7 @@ struct WeightedUnrolledRevArgs {
     size_t wstride;
     int am, an;
     int khi, nit;         // this launch runs the iterations khi, khi - 1, ..., khi - nit + 1
+    int tk0;              // tape base iteration, as UnrolledArgs (khi - nit + 1 >= tk0)
     int M, N;
     int halo;
     int first;            // 1: start from gx = gxin, gy = gf = ga = gw = 0
@@ -257,7 +263,7 @@ __global__ __launch_bounds__(UN_R * UN_R) void weighted_unrolled_reverse_tile_ke
     double f = 0.0;
     if (want_w) f = A.f[base + pix];
     double z1[WUN_REV_T], z2[WUN_REV_T], xp[WUN_REV_T];   // [s]: iteration khi - s
-    const double* tz = A.tape + (size_t)3 * A.plane * A.khi + base + pix;
+    const double* tz = A.tape + (size_t)3 * A.plane * (A.khi - A.tk0) + base + pix;
 #pragma unroll
     for (int s = 0; s < WUN_REV_T; ++s) {
         z1[s] = 0.0; z2[s] = 0.0; xp[s] = 0.0;

@@ -11,6 +11,9 @@ Array convention: a Julia `Array{Float64,3}` of size (M, N, O) (column major) is
 numpy array of shape (O, N, M).  A Julia m x n parameter matrix is a numpy array of shape (n, m).
 """
 import ctypes as C
+import functools
+import math
+import re
 import numpy as np
 
 from . import _lib
@@ -63,6 +66,19 @@ _PARAM_ALIASES = {
 }
 _IGNORED = {"verbose_iter", "save_results", "save_iterations", "op", "α", "alpha"}
 # ^ reference keys with no numerical meaning on this path (TVLearningFunctionVec.jl:39-42)
+
+
+def _restores_full_tape(method):
+    """A taped method of TVSolver: the tape_checkpoint option its checkpoint_every= set is back at 0 when it returns or raises."""
+    @functools.wraps(method)
+    def call(self, *args, **kw):
+        try:
+            return method(self, *args, **kw)
+        finally:
+            if getattr(self, "_spacing_set", False) and self._h:
+                self._spacing_set = False
+                self._lib.bpltv_set_option(self._h, b"tape_checkpoint", 0.0)
+    return call
 
 
 class TVSolver:
@@ -402,9 +418,39 @@ class TVSolver:
                                                         C.c_void_p(grad_w_ptr or None)))
 
     # -- reverse mode through the iterations (bpltv_unrolled_*) --------------------------------------------------
+    # Every *_unrolled_tape_doubles, *_unrolled_denoise* and *_unrolled_vjp* method takes checkpoint_every=C on top of the
+    # params keywords (option "tape_checkpoint"): None / 0 the full tape, C >= 1 the iteration state
+    # every C iterations instead of a tape -- the sweep then recomputes each segment's tape, same bits, one more forward
+    # solve -- and -1 the spacing of least memory (auto_checkpoint_every).  Solve, sweep and tape_doubles of one tape take the
+    # same value.
+    def _taped_params(self, kw, **model):
+        """params(**kw) without checkpoint_every=, which becomes the handle's tape_checkpoint option right before the
+        ABI call; absent means 0, so a handle shared between calls never inherits a spacing.  A spacing set here is taken
+        back when the method returns (_restores_full_tape), so the handle keeps none for direct ABI calls either."""
+        c = kw.pop("checkpoint_every", None)
+        p = self.params(**model, **kw)
+        self.set_option("tape_checkpoint", 0 if c is None else c)
+        self._spacing_set = bool(c)
+        return p
+
+    @staticmethod
+    def auto_checkpoint_every(maxiter, model="tv"):
+        """The spacing checkpoint_every=-1 stands for: ceil(sqrt(nplanes * maxiter / tape_planes)) in [1, maxiter], which
+        minimises nplanes * ceil(maxiter / C) + tape_planes * C up to rounding.  model: "tv" (3 state planes, 2 tape
+        planes per iteration), "weighted" (3, 3) or "sumregs" (7, 6)."""
+        nplanes, tape_planes = {"tv": (3, 2), "weighted": (3, 3), "sumregs": (7, 6)}[model]
+        maxiter = int(maxiter)
+        if maxiter < 1:
+            raise ValueError("auto_checkpoint_every: maxiter must be at least 1")
+        need = nplanes * maxiter
+        c = math.isqrt(need // tape_planes)
+        while c * c * tape_planes < need:
+            c += 1
+        return max(1, min(c, maxiter))
+
     def unrolled_tape_doubles(self, **kw):
         """Doubles of the tape an unrolled solve with these params records: 2 * maxiter * M*N*O."""
-        p = self.params(**kw)
+        p = self._taped_params(kw)
         n = C.c_ulonglong(0)
         self._check(self._lib.bpltv_unrolled_tape_doubles(self._h, C.byref(p), C.byref(n)))
         return int(n.value)
@@ -413,7 +459,7 @@ class TVSolver:
         """denoise(x) with rho = 0 -- the same u bit for bit -- that also records the tape of the iterations in the
         handle, for unrolled_vjp with the same x and params (bpltv_unrolled_denoise)."""
         a, am, an, _ = _alpha_arg(x)
-        p = self.params(**kw)
+        p = self._taped_params(kw)
         u = np.empty((self.O, self.N, self.M)) if fetch else None
         self._check(self._lib.bpltv_unrolled_denoise(self._h, _ptr(a), am, an, C.byref(p), _ptr(u) if fetch else None))
         return u
@@ -422,7 +468,7 @@ class TVSolver:
         """bpltv_unrolled_denoise_device: the parameter resident in HBM, the result left there (u_device_ptr /
         copy_u_device); tape_ptr: a caller-owned HBM buffer of unrolled_tape_doubles(**kw) doubles, or None / 0 for
         the handle's own tape."""
-        p = self.params(**kw)
+        p = self._taped_params(kw)
         self._check(self._lib.bpltv_unrolled_denoise_device(self._h, C.c_void_p(alpha_ptr), int(am), int(an),
                                                             C.byref(p), C.c_void_p(tape_ptr or None)))
 
@@ -434,7 +480,7 @@ class TVSolver:
         if not (want_f or want_alpha):
             raise ValueError("unrolled_vjp: want_f and want_alpha are both False")
         a, am, an, scalar = _alpha_arg(x)
-        p = self.params(**kw)
+        p = self._taped_params(kw)
         gu = self._batch(gu, "gu")
         gf = np.empty((self.O, self.N, self.M)) if want_f else None
         ga = np.empty(am * an) if want_alpha else None
@@ -447,7 +493,7 @@ class TVSolver:
     def unrolled_vjp_device(self, tape_ptr, alpha_ptr, am, an, gu_ptr, grad_f_ptr, grad_alpha_ptr, **kw):
         """bpltv_unrolled_vjp_device: the tape (None / 0: the handle's own), the parameter, gu and the outputs resident
         in HBM (raw device pointers); either output pointer may be 0 / None, not both."""
-        p = self.params(**kw)
+        p = self._taped_params(kw)
         self._check(self._lib.bpltv_unrolled_vjp_device(self._h, C.c_void_p(tape_ptr or None), C.c_void_p(alpha_ptr),
                                                         int(am), int(an), C.byref(p), C.c_void_p(gu_ptr),
                                                         C.c_void_p(grad_f_ptr or None),
@@ -456,7 +502,7 @@ class TVSolver:
     # -- reverse mode through the weighted iterations (bpltv_weighted_unrolled_*) --------------------------------
     def weighted_unrolled_tape_doubles(self, **kw):
         """Doubles of the tape a weighted unrolled solve with these params records: 3 * maxiter * M*N*O."""
-        p = self.params(**kw)
+        p = self._taped_params(kw)
         n = C.c_ulonglong(0)
         self._check(self._lib.bpltv_weighted_unrolled_tape_doubles(self._h, C.byref(p), C.byref(n)))
         return int(n.value)
@@ -467,7 +513,7 @@ class TVSolver:
         (bpltv_weighted_unrolled_denoise)."""
         a, am, an, _ = _alpha_arg(x)
         wa, wo = self._weight(w)
-        p = self.params(**kw)
+        p = self._taped_params(kw)
         u = np.empty((self.O, self.N, self.M)) if fetch else None
         self._check(self._lib.bpltv_weighted_unrolled_denoise(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p),
                                                               _ptr(u) if fetch else None))
@@ -477,7 +523,7 @@ class TVSolver:
         """bpltv_weighted_unrolled_denoise_device: w (wo planes) and the parameter resident in HBM, the result left
         there; tape_ptr: a caller-owned HBM buffer of weighted_unrolled_tape_doubles(**kw) doubles, or None / 0 for the
         handle's own weighted tape."""
-        p = self.params(**kw)
+        p = self._taped_params(kw)
         self._check(self._lib.bpltv_weighted_unrolled_denoise_device(self._h, C.c_void_p(w_ptr), int(wo),
                                                                      C.c_void_p(alpha_ptr), int(am), int(an),
                                                                      C.byref(p), C.c_void_p(tape_ptr or None)))
@@ -491,7 +537,7 @@ class TVSolver:
             raise ValueError("weighted_unrolled_vjp: want_f, want_alpha and want_w are all False")
         a, am, an, scalar = _alpha_arg(x)
         wa, wo = self._weight(w)
-        p = self.params(**kw)
+        p = self._taped_params(kw)
         gu = self._batch(gu, "gu")
         gf = np.empty((self.O, self.N, self.M)) if want_f else None
         ga = np.empty(am * an) if want_alpha else None
@@ -508,7 +554,7 @@ class TVSolver:
                                      grad_w_ptr, **kw):
         """bpltv_weighted_unrolled_vjp_device: the tape (None / 0: the handle's own), w, the parameter, gu and the
         outputs resident in HBM (raw device pointers); any output pointer may be 0 / None, not all three."""
-        p = self.params(**kw)
+        p = self._taped_params(kw)
         self._check(self._lib.bpltv_weighted_unrolled_vjp_device(self._h, C.c_void_p(tape_ptr or None),
                                                                  C.c_void_p(w_ptr), int(wo), C.c_void_p(alpha_ptr),
                                                                  int(am), int(an), C.byref(p), C.c_void_p(gu_ptr),
@@ -709,7 +755,7 @@ class TVSolver:
         """unrolled_denoise with image k's own parameter alphas[k] (bpltv_unrolled_denoise_each): denoise_each's u bit for
         bit, and the handle's tape, recorded per image, for unrolled_vjp_each with the same alphas and params."""
         a, am, an = self._each_arg(alphas)
-        p = self.params(**kw)
+        p = self._taped_params(kw)
         u = np.empty((self.O, self.N, self.M)) if fetch else None
         self._check(self._lib.bpltv_unrolled_denoise_each(self._h, _ptr(a), am, an, C.byref(p),
                                                           _ptr(u) if fetch else None))
@@ -718,7 +764,7 @@ class TVSolver:
     def unrolled_denoise_each_device(self, alphas_ptr, am=1, an=1, tape_ptr=None, **kw):
         """bpltv_unrolled_denoise_each_device: O parameter blocks (O*am*an doubles, block k column major at k*am*an)
         resident in HBM, the result left there; tape_ptr as in unrolled_denoise_device."""
-        p = self.params(**kw)
+        p = self._taped_params(kw)
         self._check(self._lib.bpltv_unrolled_denoise_each_device(self._h, C.c_void_p(alphas_ptr), int(am), int(an),
                                                                  C.byref(p), C.c_void_p(tape_ptr or None)))
 
@@ -729,7 +775,7 @@ class TVSolver:
         if not (want_f or want_alpha):
             raise ValueError("unrolled_vjp_each: want_f and want_alpha are both False")
         a, am, an = self._each_arg(alphas)
-        p = self.params(**kw)
+        p = self._taped_params(kw)
         gu = self._batch(gu, "gu")
         gf = np.empty((self.O, self.N, self.M)) if want_f else None
         ga = np.empty(a.shape) if want_alpha else None
@@ -740,7 +786,7 @@ class TVSolver:
     def unrolled_vjp_each_device(self, tape_ptr, alphas_ptr, am, an, gu_ptr, grad_f_ptr, grad_alphas_ptr, **kw):
         """bpltv_unrolled_vjp_each_device: as unrolled_vjp_device with O parameter blocks and their O gradients (O*am*an
         doubles each) resident in HBM; either output pointer may be 0 / None, not both."""
-        p = self.params(**kw)
+        p = self._taped_params(kw)
         self._check(self._lib.bpltv_unrolled_vjp_each_device(self._h, C.c_void_p(tape_ptr or None),
                                                              C.c_void_p(alphas_ptr), int(am), int(an), C.byref(p),
                                                              C.c_void_p(gu_ptr), C.c_void_p(grad_f_ptr or None),
@@ -852,7 +898,7 @@ class TVSolver:
     # -- reverse mode through the sum-of-regularisers iterations (bpltv_sumregs_unrolled_*) ------------------------
     def sumregs_unrolled_tape_doubles(self, **kw):
         """Doubles of the tape a sum-of-regularisers unrolled solve with these params records: 6 * maxiter * M*N*O."""
-        p = self.params(_sumregs=True, **kw)
+        p = self._taped_params(kw, _sumregs=True)
         n = C.c_ulonglong(0)
         self._check(self._lib.bpltv_sumregs_unrolled_tape_doubles(self._h, C.byref(p), C.byref(n)))
         return int(n.value)
@@ -861,7 +907,7 @@ class TVSolver:
         """sumregs_denoise(x) with rho = 0 -- the same u bit for bit -- that also records the tape of the iterations in
         the handle, for sumregs_unrolled_vjp with the same x and params (bpltv_sumregs_unrolled_denoise)."""
         a, am, an, _ = _sr_alpha_arg(x)
-        p = self.params(_sumregs=True, **kw)
+        p = self._taped_params(kw, _sumregs=True)
         u = np.empty((self.O, self.N, self.M)) if fetch else None
         self._check(self._lib.bpltv_sumregs_unrolled_denoise(self._h, _ptr(a), am, an, C.byref(p),
                                                              _ptr(u) if fetch else None))
@@ -871,7 +917,7 @@ class TVSolver:
         """bpltv_sumregs_unrolled_denoise_device: the parameter (3*am*an doubles) resident in HBM, the result left there
         (u_device_ptr / copy_u_device); tape_ptr: a caller-owned HBM buffer of sumregs_unrolled_tape_doubles(**kw)
         doubles, or None / 0 for the handle's own tape."""
-        p = self.params(_sumregs=True, **kw)
+        p = self._taped_params(kw, _sumregs=True)
         self._check(self._lib.bpltv_sumregs_unrolled_denoise_device(self._h, C.c_void_p(alpha_ptr), int(am), int(an),
                                                                     C.byref(p), C.c_void_p(tape_ptr or None)))
 
@@ -883,7 +929,7 @@ class TVSolver:
         if not (want_f or want_alpha):
             raise ValueError("sumregs_unrolled_vjp: want_f and want_alpha are both False")
         a, am, an, vec = _sr_alpha_arg(x)
-        p = self.params(_sumregs=True, **kw)
+        p = self._taped_params(kw, _sumregs=True)
         gu = self._batch(gu, "gu")
         gf = np.empty((self.O, self.N, self.M)) if want_f else None
         ga = np.empty(3 * am * an) if want_alpha else None
@@ -897,7 +943,7 @@ class TVSolver:
     def sumregs_unrolled_vjp_device(self, tape_ptr, alpha_ptr, am, an, gu_ptr, grad_f_ptr, grad_alpha_ptr, **kw):
         """bpltv_sumregs_unrolled_vjp_device: the tape (None / 0: the handle's own), the parameter, gu and the outputs
         resident in HBM (raw device pointers); either output pointer may be 0 / None, not both."""
-        p = self.params(_sumregs=True, **kw)
+        p = self._taped_params(kw, _sumregs=True)
         self._check(self._lib.bpltv_sumregs_unrolled_vjp_device(self._h, C.c_void_p(tape_ptr or None),
                                                                 C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p),
                                                                 C.c_void_p(gu_ptr), C.c_void_p(grad_f_ptr or None),
@@ -907,7 +953,7 @@ class TVSolver:
         """sumregs_unrolled_denoise with image k's own three weights alphas[k] (bpltv_sumregs_unrolled_denoise_each):
         sumregs_denoise_each's u bit for bit, and the handle's tape, recorded per image."""
         a, am, an = self._sr_each_arg(alphas)
-        p = self.params(_sumregs=True, **kw)
+        p = self._taped_params(kw, _sumregs=True)
         u = np.empty((self.O, self.N, self.M)) if fetch else None
         self._check(self._lib.bpltv_sumregs_unrolled_denoise_each(self._h, _ptr(a), am, an, C.byref(p),
                                                                   _ptr(u) if fetch else None))
@@ -916,7 +962,7 @@ class TVSolver:
     def sumregs_unrolled_denoise_each_device(self, alphas_ptr, am=1, an=1, tape_ptr=None, **kw):
         """bpltv_sumregs_unrolled_denoise_each_device: O parameter blocks (a C-contiguous (O, 3, an, am) array) resident
         in HBM, the result left there; tape_ptr as in sumregs_unrolled_denoise_device."""
-        p = self.params(_sumregs=True, **kw)
+        p = self._taped_params(kw, _sumregs=True)
         self._check(self._lib.bpltv_sumregs_unrolled_denoise_each_device(self._h, C.c_void_p(alphas_ptr), int(am),
                                                                          int(an), C.byref(p),
                                                                          C.c_void_p(tape_ptr or None)))
@@ -928,7 +974,7 @@ class TVSolver:
         if not (want_f or want_alpha):
             raise ValueError("sumregs_unrolled_vjp_each: want_f and want_alpha are both False")
         a, am, an = self._sr_each_arg(alphas)
-        p = self.params(_sumregs=True, **kw)
+        p = self._taped_params(kw, _sumregs=True)
         gu = self._batch(gu, "gu")
         gf = np.empty((self.O, self.N, self.M)) if want_f else None
         ga = np.empty(a.shape) if want_alpha else None
@@ -940,7 +986,7 @@ class TVSolver:
     def sumregs_unrolled_vjp_each_device(self, tape_ptr, alphas_ptr, am, an, gu_ptr, grad_f_ptr, grad_alphas_ptr, **kw):
         """bpltv_sumregs_unrolled_vjp_each_device: as sumregs_unrolled_vjp_device with O parameter blocks and their O
         gradients (O*3*am*an doubles each) resident in HBM; either output pointer may be 0 / None, not both."""
-        p = self.params(_sumregs=True, **kw)
+        p = self._taped_params(kw, _sumregs=True)
         self._check(self._lib.bpltv_sumregs_unrolled_vjp_each_device(self._h, C.c_void_p(tape_ptr or None),
                                                                      C.c_void_p(alphas_ptr), int(am), int(an),
                                                                      C.byref(p), C.c_void_p(gu_ptr),
@@ -1159,3 +1205,8 @@ def L2CostFunction(u, true_):
     results already fetched; inside evaluate the loss is reduced on the GPU)."""
     d = np.asarray(u, dtype=np.float64) - np.asarray(true_, dtype=np.float64)
     return 0.5 * float(np.sum(d * d))
+
+
+for _name in [n for n in vars(TVSolver) if re.search(r"unrolled_(tape_doubles|denoise|vjp)", n)]:
+    setattr(TVSolver, _name, _restores_full_tape(getattr(TVSolver, _name)))
+del _name

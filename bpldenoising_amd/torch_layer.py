@@ -569,6 +569,28 @@ def tv_denoise_weighted(f, alpha, w, **solver_kw):
     return TVDenoiseWeightedFunction.apply(f, alpha, w, solver_kw)
 
 
+# checkpoint_every= of the unrolled layers (TVSolver's keyword of that name): the "tape" the forward pass
+# allocates then holds the iteration state every C iterations only, and backward recomputes each segment's tape from it -- the
+# same gradients bit for bit, one more forward solve.  That recompute reads the handle's dataset, so forward saves f next to the
+# checkpoints and backward installs it again: another forward pass on the shared solver may have replaced it.
+def _checkpoint_f(solver_kw, fc):
+    return (fc,) if solver_kw.get("checkpoint_every") else ()
+
+
+def _reinstall(solver, f):
+    if f:
+        solver.set_data_device(f[0].data_ptr(), f[0].data_ptr())
+
+
+def _no_checkpoint(solver_kw):
+    """solver_kw for a tangent sweep, which reads no tape."""
+    return {k: v for k, v in solver_kw.items() if k != "checkpoint_every"}
+
+
+def _with_checkpoint(solver_kw, checkpoint_every):
+    return solver_kw if checkpoint_every is None else dict(solver_kw, checkpoint_every=int(checkpoint_every))
+
+
 class TVDenoiseWeightedUnrolledFunction(torch.autograd.Function):
     """autograd.Function of tv_denoise_weighted_unrolled (below); apply(f, alpha, w, solver_kw).  No jvp."""
 
@@ -609,8 +631,8 @@ class TVDenoiseWeightedUnrolledFunction(torch.autograd.Function):
         ga = torch.empty(ctx.am * ctx.an, dtype=torch.float64, device=gu.device) if need_a else None
         gw = torch.empty_like(w) if need_w else None
         _sync(gu.device)
-        if need_w:
-            ctx.solver.set_data_device(f.data_ptr(), f.data_ptr())   # grad_w reads the handle's dataset
+        if need_w or ctx.solver_kw.get("checkpoint_every"):   # grad_w, and a checkpointed sweep's recompute, read the handle's dataset
+            ctx.solver.set_data_device(f.data_ptr(), f.data_ptr())
         ctx.solver.weighted_unrolled_vjp_device(tape.data_ptr(), w.data_ptr(), ctx.wo, alpha.data_ptr(), ctx.am, ctx.an,
                                                 gu.data_ptr(), gf.data_ptr() if need_f else None,
                                                 ga.data_ptr() if need_a else None, gw.data_ptr() if need_w else None,
@@ -618,14 +640,15 @@ class TVDenoiseWeightedUnrolledFunction(torch.autograd.Function):
         return gf, (ga.reshape(alpha.shape) if need_a else None), gw, None
 
 
-def tv_denoise_weighted_unrolled(f, alpha, w, maxiter=50, **solver_kw):
+def tv_denoise_weighted_unrolled(f, alpha, w, maxiter=50, checkpoint_every=None, **solver_kw):
     """u = weighted_denoise(f, alpha, w) by exactly maxiter PDHG iterations (TVSolver.weighted_unrolled_denoise_device:
     tv_denoise_weighted's u bit for bit at that maxiter), differentiable in f, alpha and w THROUGH the iterations: backward
     is the exact derivative of the maxiter-step map (TVSolver.weighted_unrolled_vjp_device), with the step table held
     fixed.  w: float64, (H, W) or f's shape (B, H, W), on f's device, >= 0 -- zeros are allowed, so a mask can be trained
     through (inpainting), which tv_denoise_weighted's implicit gradient cannot.  solver_kw: the solver parameters of
-    TVSolver.params (rho, init and order must stay 0), used by the forward solve and the sweep alike."""
-    return TVDenoiseWeightedUnrolledFunction.apply(f, alpha, w, dict(solver_kw, maxiter=int(maxiter)))
+    TVSolver.params (rho, init and order must stay 0), used by the forward solve and the sweep alike.  checkpoint_every: as
+    tv_denoise_unrolled's."""
+    return TVDenoiseWeightedUnrolledFunction.apply(f, alpha, w, _with_checkpoint(dict(solver_kw, maxiter=int(maxiter)), checkpoint_every))
 
 
 class TVDenoiseUnrolledFunction(torch.autograd.Function):
@@ -645,7 +668,7 @@ class TVDenoiseUnrolledFunction(torch.autograd.Function):
         s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
         s.unrolled_denoise_device(ac.data_ptr(), am, an, tape_ptr=tape.data_ptr(), **solver_kw)
         s.copy_u_device(u.data_ptr())
-        ctx.save_for_backward(tape, ac)
+        ctx.save_for_backward(tape, ac, *_checkpoint_f(solver_kw, fc))
         ctx.solver, ctx.am, ctx.an, ctx.solver_kw = s, am, an, dict(solver_kw)
         return u
 
@@ -655,11 +678,12 @@ class TVDenoiseUnrolledFunction(torch.autograd.Function):
         need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if not (need_f or need_a):
             return None, None, None
-        tape, alpha = ctx.saved_tensors
+        tape, alpha, *f = ctx.saved_tensors
         gu = gu.to(dtype=torch.float64).contiguous()
         gf = torch.empty_like(gu) if need_f else None
         ga = torch.empty(ctx.am * ctx.an, dtype=torch.float64, device=gu.device) if need_a else None
         _sync(gu.device)
+        _reinstall(ctx.solver, f)
         ctx.solver.unrolled_vjp_device(tape.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(),
                                        gf.data_ptr() if need_f else None, ga.data_ptr() if need_a else None,
                                        **ctx.solver_kw)
@@ -689,7 +713,7 @@ class TVDenoiseUnrolledForwardFunction(TVDenoiseUnrolledFunction):
         ctx.solver.set_data_device(f.data_ptr(), f.data_ptr())   # the sweep reads the handle's dataset
         ctx.solver.unrolled_jvp_device(alpha.data_ptr(), ctx.am, ctx.an, df.data_ptr() if df is not None else None,
                                        dalpha.data_ptr() if dalpha is not None else None, du.data_ptr(), None, ndir=1,
-                                       **ctx.solver_kw)
+                                       **_no_checkpoint(ctx.solver_kw))
         return du
 
     @staticmethod
@@ -717,7 +741,7 @@ class TVDenoiseUnrolledEachFunction(torch.autograd.Function):
         s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
         s.unrolled_denoise_each_device(ac.data_ptr(), am, an, tape_ptr=tape.data_ptr(), **solver_kw)
         s.copy_u_device(u.data_ptr())
-        ctx.save_for_backward(tape, ac)
+        ctx.save_for_backward(tape, ac, *_checkpoint_f(solver_kw, fc))
         ctx.solver, ctx.am, ctx.an, ctx.solver_kw = s, am, an, dict(solver_kw)
         return u
 
@@ -727,11 +751,12 @@ class TVDenoiseUnrolledEachFunction(torch.autograd.Function):
         need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if not (need_f or need_a):
             return None, None, None
-        tape, alpha = ctx.saved_tensors
+        tape, alpha, *f = ctx.saved_tensors
         gu = gu.to(dtype=torch.float64).contiguous()
         gf = torch.empty_like(gu) if need_f else None
         ga = torch.empty_like(alpha) if need_a else None
         _sync(gu.device)
+        _reinstall(ctx.solver, f)
         ctx.solver.unrolled_vjp_each_device(tape.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(),
                                             gf.data_ptr() if need_f else None, ga.data_ptr() if need_a else None,
                                             **ctx.solver_kw)
@@ -761,7 +786,7 @@ class TVDenoiseUnrolledEachForwardFunction(TVDenoiseUnrolledEachFunction):
         ctx.solver.set_data_device(f.data_ptr(), f.data_ptr())   # the sweep reads the handle's dataset
         ctx.solver.unrolled_jvp_each_device(alpha.data_ptr(), ctx.am, ctx.an, df.data_ptr() if df is not None else None,
                                             dalpha.data_ptr() if dalpha is not None else None, du.data_ptr(), None,
-                                            ndir=1, **ctx.solver_kw)
+                                            ndir=1, **_no_checkpoint(ctx.solver_kw))
         return du
 
     @staticmethod
@@ -772,39 +797,43 @@ class TVDenoiseUnrolledEachForwardFunction(TVDenoiseUnrolledEachFunction):
         return TVDenoiseUnrolledEachFunction.backward(ctx, gu)
 
 
-def tv_denoise_unrolled_each(f, alpha, forward_mode=False, **solver_kw):
+def tv_denoise_unrolled_each(f, alpha, forward_mode=False, checkpoint_every=None, **solver_kw):
     """u[k] = denoise(f[k], alpha[k]) by exactly maxiter PDHG iterations, for a batch f of shape (B, H, W) with one
     parameter per image: alpha (B,), (B, pH, pW) or (B, H, W) on f's device -- tv_denoise_each's u bit for bit,
     differentiable THROUGH the iterations as tv_denoise_unrolled is.  One taped batched solve forward
     (TVSolver.unrolled_denoise_each_device) and one reverse sweep backward (unrolled_vjp_each_device); alpha.grad[k] is
-    image k's term alone.  solver_kw and forward_mode: as tv_denoise_unrolled's (the jvp is one
+    image k's term alone.  solver_kw, forward_mode and checkpoint_every: as tv_denoise_unrolled's (the jvp is one
     unrolled_jvp_each_device call)."""
     fn = TVDenoiseUnrolledEachForwardFunction if forward_mode else TVDenoiseUnrolledEachFunction
-    return fn.apply(f, alpha, solver_kw)
+    return fn.apply(f, alpha, _with_checkpoint(solver_kw, checkpoint_every))
 
 
-def tv_denoise_unrolled(f, alpha, forward_mode=False, **solver_kw):
+def tv_denoise_unrolled(f, alpha, forward_mode=False, checkpoint_every=None, **solver_kw):
     """u = denoise(f, alpha) by exactly maxiter PDHG iterations (TVSolver.unrolled_denoise_device: tv_denoise's u bit for
     bit), differentiable in f and alpha THROUGH the iterations: backward is the exact derivative of the maxiter-step map
     (TVSolver.unrolled_vjp_device), not the implicit gradient of the minimiser.  solver_kw: the solver parameters of
     TVSolver.params (rho, init and order must stay 0), used by the forward solve and the sweeps alike.
     forward_mode: also usable under torch.autograd.forward_ad (the function then carries a jvp, a tangent sweep through
     the iterations, bpltv_unrolled_jvp_device); without it forward-mode AD raises torch's "not implemented" error, as
-    before."""
+    before.
+    checkpoint_every: None / 0 keeps the full tape (2 * maxiter * B*H*W doubles); C >= 1 keeps the iteration state every C
+    iterations instead and lets backward recompute the tape segment by segment -- the same gradients bit for bit for one
+    more forward solve, in O(sqrt(maxiter)) memory at C = -1 (TVSolver.auto_checkpoint_every).  The tangent sweep of
+    forward_mode reads no tape and is unaffected."""
     fn = TVDenoiseUnrolledForwardFunction if forward_mode else TVDenoiseUnrolledFunction
-    return fn.apply(f, alpha, solver_kw)
+    return fn.apply(f, alpha, _with_checkpoint(solver_kw, checkpoint_every))
 
 
 class TVDenoiseUnrolled(torch.nn.Module):
     """TVDenoise with tv_denoise_unrolled's backward: a learnable scalar, patch parameter or pixel map behind a fixed
     number of iterations (solver_kw: maxiter, ...).  Move it to the device of its inputs with .to(device).
-    forward_mode: as tv_denoise_unrolled's."""
+    forward_mode, checkpoint_every: as tv_denoise_unrolled's."""
 
-    def __init__(self, alpha, forward_mode=False, **solver_kw):
+    def __init__(self, alpha, forward_mode=False, checkpoint_every=None, **solver_kw):
         super().__init__()
         self.alpha = torch.nn.Parameter(torch.as_tensor(alpha, dtype=torch.float64).clone())
         self.forward_mode = bool(forward_mode)
-        self.solver_kw = dict(solver_kw)
+        self.solver_kw = _with_checkpoint(dict(solver_kw), checkpoint_every)
 
     def forward(self, f):
         return tv_denoise_unrolled(f, self.alpha, forward_mode=self.forward_mode, **self.solver_kw)
@@ -832,7 +861,7 @@ class SumRegsDenoiseUnrolledFunction(torch.autograd.Function):
         solve = s.sumregs_unrolled_denoise_each_device if each else s.sumregs_unrolled_denoise_device
         solve(ac.data_ptr(), am, an, tape_ptr=tape.data_ptr(), **solver_kw)
         s.copy_u_device(u.data_ptr())
-        ctx.save_for_backward(tape, ac)
+        ctx.save_for_backward(tape, ac, *_checkpoint_f(solver_kw, fc))
         ctx.solver, ctx.am, ctx.an, ctx.each, ctx.solver_kw = s, am, an, bool(each), dict(solver_kw)
         return u
 
@@ -842,11 +871,12 @@ class SumRegsDenoiseUnrolledFunction(torch.autograd.Function):
         need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         if not (need_f or need_a):
             return None, None, None, None
-        tape, alpha = ctx.saved_tensors
+        tape, alpha, *f = ctx.saved_tensors
         gu = gu.to(dtype=torch.float64).contiguous()
         gf = torch.empty_like(gu) if need_f else None
         ga = torch.empty_like(alpha) if need_a else None
         _sync(gu.device)
+        _reinstall(ctx.solver, f)
         vjp = ctx.solver.sumregs_unrolled_vjp_each_device if ctx.each else ctx.solver.sumregs_unrolled_vjp_device
         vjp(tape.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(), gf.data_ptr() if need_f else None,
             ga.data_ptr() if need_a else None, **ctx.solver_kw)
@@ -859,34 +889,36 @@ def _no_forward_mode(name, forward_mode):
                          "sumregs_denoise(..., forward_mode=True) carries a jvp" % name)
 
 
-def sumregs_denoise_unrolled(f, alpha, maxiter=50, forward_mode=False, **solver_kw):
+def sumregs_denoise_unrolled(f, alpha, maxiter=50, forward_mode=False, checkpoint_every=None, **solver_kw):
     """u = sumregs_denoise(f, alpha) by exactly maxiter PDHG iterations (TVSolver.sumregs_unrolled_denoise_device: the same
     u bit for bit), differentiable in f and the three weights THROUGH the iterations: backward is the exact derivative of
     the maxiter-step map (one sumregs_unrolled_vjp_device call over a tape of 6 * maxiter * B*H*W doubles the forward pass
     allocates as a torch tensor), with no active-set threshold and no factorisation; zeros in alpha are legal.  alpha:
     (3,), (3, pH, pW) or (3, H, W) on f's device.  solver_kw: the solver parameters of TVSolver.params (rho, init and
-    order must stay 0).  forward_mode=True raises: use the implicit sumregs_denoise(..., forward_mode=True)."""
+    order must stay 0).  forward_mode=True raises: use the implicit sumregs_denoise(..., forward_mode=True).
+    checkpoint_every: as tv_denoise_unrolled's (here 7 state planes every C iterations against 6 tape planes per iteration)."""
     _no_forward_mode("sumregs_denoise_unrolled", forward_mode)
-    return SumRegsDenoiseUnrolledFunction.apply(f, alpha, False, dict(solver_kw, maxiter=maxiter))
+    return SumRegsDenoiseUnrolledFunction.apply(f, alpha, False, _with_checkpoint(dict(solver_kw, maxiter=maxiter), checkpoint_every))
 
 
-def sumregs_denoise_unrolled_each(f, alpha, maxiter=30, forward_mode=False, **solver_kw):
+def sumregs_denoise_unrolled_each(f, alpha, maxiter=30, forward_mode=False, checkpoint_every=None, **solver_kw):
     """sumregs_denoise_unrolled for a batch f of shape (B, H, W) with three weights per image: alpha (B, 3),
     (B, 3, pH, pW) or (B, 3, H, W) -- sumregs_denoise_each's u bit for bit; alpha.grad[k] is image k's term alone.  What
-    a network that predicts the weights per sample in front of a short solve needs."""
+    a network that predicts the weights per sample in front of a short solve needs.  checkpoint_every: as
+    sumregs_denoise_unrolled's."""
     _no_forward_mode("sumregs_denoise_unrolled_each", forward_mode)
-    return SumRegsDenoiseUnrolledFunction.apply(f, alpha, True, dict(solver_kw, maxiter=maxiter))
+    return SumRegsDenoiseUnrolledFunction.apply(f, alpha, True, _with_checkpoint(dict(solver_kw, maxiter=maxiter), checkpoint_every))
 
 
 class SumRegsDenoiseUnrolled(torch.nn.Module):
     """SumRegsDenoise with sumregs_denoise_unrolled's backward: three learnable weights, patch parameters or pixel maps
     behind a fixed number of iterations (solver_kw: maxiter, ...).  Move it to the device of its inputs with .to(device)."""
 
-    def __init__(self, alpha, forward_mode=False, **solver_kw):
+    def __init__(self, alpha, forward_mode=False, checkpoint_every=None, **solver_kw):
         super().__init__()
         _no_forward_mode("SumRegsDenoiseUnrolled", forward_mode)
         self.alpha = torch.nn.Parameter(torch.as_tensor(alpha, dtype=torch.float64).clone())
-        self.solver_kw = dict(solver_kw)
+        self.solver_kw = _with_checkpoint(dict(solver_kw), checkpoint_every)
 
     def forward(self, f):
         return sumregs_denoise_unrolled(f, self.alpha, **self.solver_kw)

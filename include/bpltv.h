@@ -394,8 +394,34 @@ int bpltv_weighted_vjp_device(bpltv_t *h, const double *d_u, const double *d_f, 
  * patch, or not at all for a map; fixed order, no atomics).  Either output may be NULL, not both (BPLTV_E_ARG).  alpha must be the
  * parameter of the solve.  The VJP does not read f.  It stages its parameter apart, as bpltv_vjp does, and leaves the last
  * solve untouched.  stats: adjoint_ms is the HIP-event time of the reverse sweep, adjoint_method = 7.  Multi-device handles
- * over more than one shard: BPLTV_E_UNSUPPORTED (the four solve and VJP functions). */
-int bpltv_unrolled_tape_doubles(bpltv_t *h, const bpltv_params *p, unsigned long long *n_out);   /* 2*maxiter*M*N*O */
+ * over more than one shard: BPLTV_E_UNSUPPORTED (the four solve and VJP functions).
+ *
+ * Checkpointing: the tape grows with maxiter.  bpltv_set_option(h, "tape_checkpoint", C) with C != 0
+ * trades it for one more forward solve, for this model, the weighted one and the sum of regularisers, shared and _each, host
+ * and _device forms alike; C = 0 (the default) is everything described above, unchanged.  C >= 1 is the spacing in iterations,
+ * Ceff = min(C, maxiter); C = -1 chooses Ceff = clamp(ceil(sqrt(nplanes * maxiter / tape_planes)), 1, maxiter), with nplanes /
+ * tape_planes = 3 / 2 here, 3 / 3 weighted and 7 / 6 for the sum of regularisers: the spacing of least memory.
+ *  - *_unrolled_tape_doubles returns nplanes * ceil(maxiter / Ceff) * M*N*O: one state set per segment of Ceff iterations, the
+ *    state at its start (segment 0's too, so the count is never 0).  That is what a caller's d_tape must hold.
+ *  - *_unrolled_denoise* runs the same recurrence -- u is still the plain denoise's bit for bit, and the solve becomes the
+ *    handle's last solve as above -- with a kernel instantiation that stores no tape, and writes only those states, into
+ *    d_tape or the handle's tape of the model.  stats.bytes_per_px_iter is the plain solve's (56 / 64 here, 64 / 72 weighted,
+ *    120 / 144 sum of regularisers); the checkpoints are nplanes planes more per Ceff iterations, written in place of a state
+ *    set by the launch that ends a segment.
+ *  - *_unrolled_vjp* walks the segments from the last to the first: it re-runs a segment's iterations from its checkpoint with
+ *    the taping kernel -- in state planes of its own, on the staged parameter (and weight) and the RESIDENT f, into a segment
+ *    tape of tape_planes * Ceff * M*N*O doubles -- and reverses them with the reverse kernel, carrying its planes from segment
+ *    to segment.  Same kernels, same state: every gradient is bitwise the full tape's.  The sweep therefore reads f for every
+ *    model (BPLTV_E_NODATA without a dataset, before anything changes); d_tape stays const and is not written.  Segment tape
+ *    and recompute planes belong to the handle: allocated on first use, only growing, freed by bpltv_destroy, BPLTV_E_NOMEM
+ *    with the handle as it was when they cannot be had.  adjoint_ms includes the recompute; adjoint_method is unchanged.
+ *  - The handle's tape remembers its spacing: a VJP on it under an option that gives another spacing (full against
+ *    checkpointed included) is BPLTV_E_ARG.  bpltv_set_data(_device) invalidates a CHECKPOINTED handle tape -- its states no
+ *    longer belong to the resident f -- and the next VJP on it is BPLTV_E_NODATA; a full tape is unaffected.  With a caller's
+ *    buffer the spacing and the same resident f are part of the caller's contract.
+ *  - As before the results do not depend on tile_iters, the launch chains, use_graph or whose buffer it is.  A call is one
+ *    launch sequence (one graph per chain, all segments inside, keyed by the spacing), never one graph per segment. */
+int bpltv_unrolled_tape_doubles(bpltv_t *h, const bpltv_params *p, unsigned long long *n_out);   /* 2*maxiter*M*N*O (option "tape_checkpoint" = 0) */
 int bpltv_unrolled_denoise(bpltv_t *h, const double *alpha, int am, int an, const bpltv_params *p, double *u_out);
 int bpltv_unrolled_denoise_device(bpltv_t *h, const double *d_alpha, int am, int an, const bpltv_params *p, double *d_tape);
 int bpltv_unrolled_vjp(bpltv_t *h, const double *alpha, int am, int an, const bpltv_params *p,
@@ -440,7 +466,7 @@ int bpltv_unrolled_vjp_device(bpltv_t *h, const double *d_tape, const double *d_
  * device form or on whose tape it is, and these calls never replay the captured graphs of the TV, sum-of-regularisers,
  * weighted or unrolled calls, nor the reverse.  Multi-device handles over more than one shard: BPLTV_E_UNSUPPORTED (all five);
  * one shard is forwarded. */
-int bpltv_weighted_unrolled_tape_doubles(bpltv_t *h, const bpltv_params *p, unsigned long long *n_out);   /* 3*maxiter*M*N*O */
+int bpltv_weighted_unrolled_tape_doubles(bpltv_t *h, const bpltv_params *p, unsigned long long *n_out);   /* 3*maxiter*M*N*O; option "tape_checkpoint": see bpltv_unrolled_tape_doubles */
 int bpltv_weighted_unrolled_denoise(bpltv_t *h, const double *w, int wo, const double *alpha, int am, int an,
                                     const bpltv_params *p, double *u_out);
 int bpltv_weighted_unrolled_denoise_device(bpltv_t *h, const double *d_w, int wo, const double *d_alpha, int am, int an,
@@ -552,7 +578,7 @@ int bpltv_unrolled_jvp_each_device(bpltv_t *h, const double *d_alphas, int am, i
  * No captured graph is shared with bpltv_sumregs_denoise, the TV, weighted or other unrolled calls.  Multi-device handles over
  * more than one shard: BPLTV_E_UNSUPPORTED (all nine); one shard is forwarded.  dtype = 32 handles behave as
  * bpltv_sumregs_denoise does on them; these calls always compute in Float64. */
-int bpltv_sumregs_unrolled_tape_doubles(bpltv_t *h, const bpltv_params *p, unsigned long long *n_out);   /* 6*maxiter*M*N*O */
+int bpltv_sumregs_unrolled_tape_doubles(bpltv_t *h, const bpltv_params *p, unsigned long long *n_out);   /* 6*maxiter*M*N*O; option "tape_checkpoint": see bpltv_unrolled_tape_doubles */
 int bpltv_sumregs_unrolled_denoise(bpltv_t *h, const double *alpha, int am, int an, const bpltv_params *p, double *u_out);
 int bpltv_sumregs_unrolled_denoise_device(bpltv_t *h, const double *d_alpha, int am, int an, const bpltv_params *p, double *d_tape);
 int bpltv_sumregs_unrolled_vjp(bpltv_t *h, const double *alpha, int am, int an, const bpltv_params *p,
@@ -752,6 +778,11 @@ int bpltv_sumregs_sweep(bpltv_t *h, const double *alphas, int K, int am, int an,
  *                        (stats.sweep_groups; bitwise the same result); 0 = what is free minus a 2 GB reserve
  *   "sweep_split"        multi-device handles, bpltv_sweep / bpltv_sumregs_sweep: 0 automatic, 1 split the images, 2 split
  *                        the parameter blocks
+ *   "tape_checkpoint"    the unrolled solves and sweeps of the three models (see bpltv_unrolled_tape_doubles): 0 the full tape,
+ *                        C >= 1 the iteration state every C iterations instead (the sweep recomputes each segment's tape: the
+ *                        same bits, one more forward solve), -1 the spacing of least memory.  A value that is no integer or
+ *                        lies below -1 is BPLTV_E_ARG and the option keeps its value.  The one option that is no test aid:
+ *                        bpltv_params cannot grow
  * Multi-device handles pass the other options to every shard (and sweep replica). */
 int bpltv_set_option(bpltv_t *h, const char *name, double value);
 
