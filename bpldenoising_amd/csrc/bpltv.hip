@@ -31,6 +31,7 @@
 #include "weighted_kernels.hpp"
 #include "unrolled_kernels.hpp"
 #include "unrolled_jvp_kernels.hpp"
+#include "weighted_unrolled_jvp_kernels.hpp"
 #include "weighted_unrolled_kernels.hpp"
 #include "sumregs_unrolled_kernels.hpp"
 #include "multi_gpu.hpp"
@@ -200,7 +201,8 @@ struct GraphKey {
     int accel, dbg, nimg;
     const void* state; // state set 0 of the solve context: a sweep never replays a dataset-context graph, nor the reverse
                        // (MODEL_UN: the tape the launches write or read, with variant 0 = taped solve, 1 = reverse sweep; 2 ... 5 = tangent
-                       // sweep, whose planes stand here instead; 6 = weighted taped solve, 7 / 8 = its reverse sweep without / with grad_w;
+                       // sweep, whose planes stand here instead; 6 = weighted taped solve, 7 / 8 = its reverse sweep without / with grad_w,
+                       // 9 ... 16 = its tangent sweep, by the tangents it reads, its planes here;
                        // MODEL_SRUN: the tape as well, variant 0 = taped solve, 1 = reverse sweep)
     const void* tab;   // step table (one per (maxiter, steps, L, dual-first shift, gamma): TabKey)
     int from_state;    // 1: the sequence starts from a prepared state (params.init / order), not from x = f, y = 0
@@ -495,6 +497,9 @@ struct bpltv_handle {
     // forward mode through the iterations (unrolled_jvp_kernels.hpp): the tangent sweep's planes [2 sets x (x, y1, y2, dx, dy1,
     // dy2) | df | dalpha], allocated on first use and never moved
     double* d_ujv = nullptr;                        // 14 * M*N*O doubles
+    // ... of the weighted model (weighted_unrolled_jvp_kernels.hpp): planes of its own, [2 sets x 6 | df | dalpha | w | dw] and
+    // eight words for the device check of dw, allocated on first use and never moved
+    double* d_wjv = nullptr;                        // 16 * M*N*O + 8 doubles
     bpltv_stats_t st;
     std::string err;
 };
@@ -3976,53 +3981,91 @@ int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const 
     return BPLTV_OK;
 }
 
-// bpltv_unrolled_jvp(_device) and bpltv_unrolled_gauss_newton on a single-device handle (unrolled_jvp_kernels.hpp, DESIGN.md
-// section 4.7): ndir tangent sweeps, one after the other, each the same launch sequence (direction d of a call is bitwise the
-// call with that direction alone).  The tangents d_df / d_dalpha (either may be nullptr: a zero tangent) and d_du live in HBM,
-// direction-major; alpha on the host or (dev) in HBM.  Every sweep runs in the planes of d_ujv = [2 sets x (x, y1, y2, dx, dy1,
-// dy2) | df | dalpha] on the staged parameter (stage_param), with the direction's tangents copied into the workspace first, so
-// that no captured graph holds a caller's address and the last solve, the tape and the solve statistics stay as they were.
-// d_u (nullable): receives the primal result, bpltv_denoise's u.  *x_res (nullable): the workspace plane that holds it.
+// bpltv_unrolled_jvp(_device), bpltv_weighted_unrolled_jvp(_device) and the two Gauss-Newton calls on a single-device handle
+// (unrolled_jvp_kernels.hpp, weighted_unrolled_jvp_kernels.hpp; DESIGN.md sections 4.7 and 4.11): ndir tangent sweeps, one after
+// the other, each the same launch sequence (direction d of a call is bitwise the call with that direction alone).  The tangents
+// d_df / d_dalpha (and the weighted model's d_dw; any may be nullptr: a zero tangent) and d_du live in HBM, direction-major; alpha
+// (and w) on the host or (dev) in HBM.  Every sweep runs in planes of the handle's own -- d_ujv = [2 sets x (x, y1, y2, dx, dy1,
+// dy2) | df | dalpha], weighted: d_wjv = [2 sets | df | dalpha | w | dw | 8 check words] -- on the staged parameter (stage_param),
+// with the direction's tangents copied into the workspace first, so that no captured graph holds a caller's address and the
+// last solve, the tapes and the solve statistics stay as they were.
+// d_u (nullable): receives the primal result, bpltv_denoise's (bpltv_weighted_denoise's) u.  *x_res (nullable): the workspace
+// plane that holds it.
 // each (bpltv_unrolled_jvp_each(_device)): alpha holds O blocks and d_dalpha ndir x O blocks (direction, then image); image k
 // reads block k of both.
+// W (nullable: the TV model): the weighted model's w (wo planes, every entry >= 0) and d_dw (ndir x wo planes).  The step table
+// has gamma = min w, held fixed.
+struct JvpWeight {
+    const double* w;
+    int wo;
+    const double* dw;   // HBM in unrolled_jvp_common; the host array in unrolled_jvp_host
+};
 int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool dev, int am, int an, const bpltv_params* pp, int ndir,
-                        const double* d_df, const double* d_dalpha, double* d_du, double* d_u, const double** x_res, bool each = false) {
-    if (!alpha || !d_du) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
+                        const double* d_df, const double* d_dalpha, double* d_du, double* d_u, const double** x_res, bool each = false,
+                        const JvpWeight* W = nullptr) {
+    const double* d_dw = W ? W->dw : nullptr;
+    if (!alpha || !d_du || (W && !W->w)) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
     if (ndir < 1) return set_err(h, BPLTV_E_ARG, "%s: ndir = %d (at least one direction)", who, ndir);
-    if (!d_df && !d_dalpha) return set_err(h, BPLTV_E_ARG, "%s: both tangents are NULL", who);
+    if (!d_df && !d_dalpha && !d_dw) return set_err(h, BPLTV_E_ARG, "%s: %s tangents are NULL", who, W ? "all three" : "both");
+    if (W && W->wo != 1 && W->wo != h->O)
+        return set_err(h, BPLTV_E_ARG, "%s: wo = %d: one weight plane (1) or one per image (%d)", who, W->wo, h->O);
     if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: bpltv_set_data has not been called", who);
     const bpltv_params p0 = resolve(pp);
     if (int prc = unrolled_check_params(h, p0, who)) return prc;
     WeightedPlan pl;
     if (int prc = unrolled_plan(h, p0, PDHG_MAX_T, &pl)) return prc;
-    const size_t tot = h->tot;
-    if (!h->d_ujv) {
-        if (int arc = alloc_all(h, {{(void**)&h->d_ujv, 14 * tot * sizeof(double)}}, "tangent sweep")) return arc;
-        HIPCHK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&unrolled_jvp_tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      (int)unrolled_jvp_lds_bytes()));
+    const size_t tot = h->tot, nw = W ? (size_t)W->wo * h->npx : 0;
+    double*& d_ws = W ? h->d_wjv : h->d_ujv;
+    if (!d_ws) {
+        if (int arc = alloc_all(h, {{(void**)&d_ws, ((W ? 16 : 14) * tot + (W ? 8 : 0)) * sizeof(double)}}, W ? "weighted tangent sweep" : "tangent sweep"))
+            return arc;
+        HIPCHK(h, hipFuncSetAttribute(W ? reinterpret_cast<const void*>(&weighted_unrolled_jvp_tile_kernel) : reinterpret_cast<const void*>(&unrolled_jvp_tile_kernel),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)unrolled_jvp_lds_bytes()));
     }
     const size_t P = (size_t)am * an * (each ? h->O : 1);   // (stage_param checks the shape before it reads anything)
+    if (d_dw) {   // the third tangent: a read-back of its own (stage_param's takes two), into the workspace's check words
+        int failed = -1;
+        double unused = 0.0;
+        if (int rc = check_device_arrays(h, reinterpret_cast<unsigned long long*>(d_ws + 16 * tot), {nullptr, 0}, {{d_dw, (size_t)ndir * nw, "tangent dw"}}, &unused, &failed))
+            return rc;
+        if (failed > 0) return set_err(h, BPLTV_E_ARG, "%s: the tangent dw must be finite", who);
+    }
     bpltv_params p;
     GradCtx g;
-    if (int rc = stage_param(h, who, alpha, dev, am, an, 1, each, 0, pp, nullptr, 1,
-                             {{d_df, (size_t)ndir * tot, "tangent df"}, {d_dalpha, (size_t)ndir * P, "tangent dalpha"}}, &p, &g))
+    if (int rc = stage_param(h, who, alpha, dev, am, an, 1, each, 0, pp, W ? W->w : nullptr, W ? W->wo : 1,
+                             {{d_df, (size_t)ndir * tot, "tangent df"}, {d_dalpha, (size_t)ndir * P, "tangent dalpha"}}, &p, &g, false))
         return rc;
     double* d_tab = nullptr;
-    if (int rc = get_table(h, p, &d_tab, 8.0, 0)) return rc;
+    if (int rc = get_table(h, p, &d_tab, 8.0, 0, W ? g.w_min : 1.0)) return rc;
     const int M = h->M, N = h->N, T = pl.T, K = p.maxiter;
     double* S[2][6];
     for (int s = 0; s < 2; ++s)
-        for (int c = 0; c < 6; ++c) S[s][c] = h->d_ujv + (size_t)(6 * s + c) * tot;
-    double *d_dfc = h->d_ujv + 12 * tot, *d_dac = h->d_ujv + 13 * tot;   // (a parameter has at most M*N <= tot entries)
+        for (int c = 0; c < 6; ++c) S[s][c] = d_ws + (size_t)(6 * s + c) * tot;
+    double *d_dfc = d_ws + 12 * tot, *d_dac = d_ws + 13 * tot;   // (a parameter has at most M*N <= tot entries)
+    double *d_wc = W ? d_ws + 14 * tot : nullptr, *d_dwc = W ? d_ws + 15 * tot : nullptr;
+    if (W) HIPCHK(h, hipMemcpyAsync(d_wc, g.w, nw * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     const bpltv_stats_t kept = h->st;
     ChainSolve j;
     j.model = MODEL_UN; j.nplanes = 6; j.state0 = S[0];
     taped_chains(h, p, pl, &j);
     j.bytes_per_px_iter = 0.0;   // (the driver's solve statistics are not this call's: `kept` goes back below)
-    // variant 2 ... 5: a tangent sweep, by which tangents it reads (0 = taped solve, 1 = reverse sweep)
-    j.key = GraphKey{K, T, 2 + (d_df ? 1 : 0) + (d_dalpha ? 2 : 0), am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)h->d_ujv,
-                     (const void*)d_tab, 0, (const void*)g.alpha, g.astride, 0};
+    // variant 2 ... 5: a tangent sweep, by which tangents it reads (0 = taped solve, 1 = reverse sweep); 9 ... 16: a weighted one
+    const int tangents = (d_df ? 1 : 0) + (d_dalpha ? 2 : 0) + (d_dw ? 4 : 0);
+    j.key = GraphKey{K, T, (W ? 9 : 2) + tangents, am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_ws,
+                     (const void*)d_tab, 0, (const void*)g.alpha, g.astride, W ? W->wo : 0};
     j.enqueue = launch_loop(T, [&](const LaunchStep& s) {
+        if (W) {
+            WeightedUnrolledJvpArgs a;
+            for (int c = 0; c < 6; ++c) { a.in[c] = S[s.cur][c]; a.out[c] = S[s.nxt][c]; }
+            a.f = h->d_f; a.w = d_wc; a.df = d_df ? d_dfc : nullptr; a.dw = d_dw ? d_dwc : nullptr;
+            a.alpha = g.alpha; a.dalpha = d_dalpha ? d_dac : nullptr; a.tab = d_tab;
+            a.wstride = W->wo > 1 ? h->npx : 0;
+            a.am = am; a.an = an;
+            a.it0 = s.it; a.nit = s.nit;
+            a.M = M; a.N = N; a.halo = T; a.first = s.first; a.img0 = s.lo;
+            hipLaunchKernelGGL(weighted_unrolled_jvp_tile_kernel, dim3(pl.nTi, pl.nTj, s.hi - s.lo), dim3(UN_R * UN_R), unrolled_jvp_lds_bytes(), s.st, a);
+            return;
+        }
         UnrolledJvpArgs a;
         for (int c = 0; c < 6; ++c) { a.in[c] = S[s.cur][c]; a.out[c] = S[s.nxt][c]; }
         a.f = h->d_f; a.df = d_df ? d_dfc : nullptr; a.alpha = g.alpha; a.dalpha = d_dalpha ? d_dac : nullptr; a.tab = d_tab;
@@ -4037,6 +4080,7 @@ int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool d
         hipError_t e = hipSuccess;
         if (d_df) e = hipMemcpyAsync(d_dfc, d_df + (size_t)d * tot, tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
         if (d_dalpha && e == hipSuccess) e = hipMemcpyAsync(d_dac, d_dalpha + (size_t)d * P, P * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
+        if (d_dw && e == hipSuccess) e = hipMemcpyAsync(d_dwc, d_dw + (size_t)d * nw, nw * sizeof(double), hipMemcpyDeviceToDevice, h->stream);
         if (e != hipSuccess) { rc = set_err(h, BPLTV_E_HIP, "%s: copy of the tangents failed: %s", who, hipGetErrorString(e)); break; }
         rc = run_chains(h, p, j, &buf);
         if (rc) break;
@@ -4046,7 +4090,7 @@ int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool d
     h->st = kept;
     if (rc) return rc;
     if (d_u) HIPCHK(h, hipMemcpyAsync(d_u, S[buf][0], tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    if (int src = sweep_stats(h, 8)) return src;
+    if (int src = sweep_stats(h, W ? 11 : 8)) return src;
     if (x_res) *x_res = S[buf][0];
     return BPLTV_OK;
 }
@@ -4179,7 +4223,7 @@ int bpltv_destroy(bpltv_t* h) {
     if (h->f32_sweep_alpha) (void)hipFree(h->f32_sweep_alpha);
     void* ptrs[] = {h->d_ubar, h->d_f, h->d_alpha, h->d_sweep_alpha, h->d_partial, h->d_red, h->d_perimg, h->d_scalar, h->d_coef,
                     h->d_band4, h->d_bcr, h->d_L, h->d_invF, h->d_invB, h->d_L1, h->d_dump, h->d_Lm, h->d_spill, h->d_p, h->d_r, h->d_gpix, h->d_resn, h->d_fail, h->d_u2, h->d_ubar2,
-                    h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres, h->d_w, h->d_wst, h->d_unr, h->d_ujv, h->d_unr_gw, h->d_srunr, h->d_seg};
+                    h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres, h->d_w, h->d_wst, h->d_unr, h->d_ujv, h->d_wjv, h->d_unr_gw, h->d_srunr, h->d_seg};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
     for (Tape* t : {&h->tape, &h->wtape, &h->srtape}) t->release();
@@ -4587,26 +4631,34 @@ int bpltv_weighted_unrolled_vjp_device(bpltv_t* h, const double* d_tape, const d
                            d_grad_alpha, d_grad_w, false);
 }
 
-// bpltv_unrolled_jvp and bpltv_unrolled_jvp_each on a single-device handle: the host arrays staged around unrolled_jvp_common
-static int unrolled_jvp_host(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, int ndir, const double* df,
-                             const double* dalpha, double* du_out, double* u_out, bool each) {
-    const char* who = each ? "unrolled_jvp_each" : "unrolled_jvp";
-    if (!alpha || !du_out) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
+// bpltv_unrolled_jvp, bpltv_unrolled_jvp_each and bpltv_weighted_unrolled_jvp on a single-device handle: the host arrays
+// staged around unrolled_jvp_common.  W (nullable: the TV model): the weighted model's host w and host dw.
+static int unrolled_jvp_host(bpltv_t* h, const char* who, const double* alpha, int am, int an, const bpltv_params* pp, int ndir, const double* df,
+                             const double* dalpha, double* du_out, double* u_out, bool each, const JvpWeight* W) {
+    const double* dw = W ? W->dw : nullptr;
+    if (!alpha || !du_out || (W && !W->w)) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
     if (ndir < 1) return set_err(h, BPLTV_E_ARG, "%s: ndir = %d (at least one direction)", who, ndir);
-    if (!df && !dalpha) return set_err(h, BPLTV_E_ARG, "%s: both tangents are NULL", who);
+    if (!df && !dalpha && !dw) return set_err(h, BPLTV_E_ARG, "%s: %s tangents are NULL", who, W ? "all three" : "both");
+    if (W && W->wo != 1 && W->wo != h->O)
+        return set_err(h, BPLTV_E_ARG, "%s: wo = %d: one weight plane (1) or one per image (%d)", who, W->wo, h->O);
     if (am < 1 || an < 1 || am > h->M || an > h->N)
         return set_err(h, BPLTV_E_ARG, "%s: parameter shape %dx%d (image %dx%d)", who, am, an, h->M, h->N);
-    const size_t nt = (size_t)ndir * h->tot, na = (size_t)ndir * am * an * (each ? h->O : 1);
+    const size_t nt = (size_t)ndir * h->tot, na = (size_t)ndir * am * an * (each ? h->O : 1), nd = W ? (size_t)ndir * W->wo * h->npx : 0;
     if (int crc = check_tangent_host(h, who, "tangent df", df, nt)) return crc;
     if (int crc = check_tangent_host(h, who, "tangent dalpha", dalpha, na)) return crc;
+    if (int crc = check_tangent_host(h, who, "tangent dw", dw, nd)) return crc;
     HIPCHK(h, hipSetDevice(h->device));
-    int rc = ensure(h, &h->d_jvp, &h->jvp_cap, 2 * nt + na + h->tot);   // [du | df | dalpha | u]
+    int rc = ensure(h, &h->d_jvp, &h->jvp_cap, 2 * nt + na + h->tot + nd);   // [du | df | dalpha | u | dw]
     if (rc) return rc;
     double *d_du = h->d_jvp, *d_df = df ? h->d_jvp + nt : nullptr, *d_da = dalpha ? h->d_jvp + 2 * nt : nullptr;
     double* d_u = u_out ? h->d_jvp + 2 * nt + na : nullptr;
+    double* d_dw = dw ? h->d_jvp + 2 * nt + na + h->tot : nullptr;
     if (df) HIPCHK(h, hipMemcpyAsync(d_df, df, nt * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (dalpha) HIPCHK(h, hipMemcpyAsync(d_da, dalpha, na * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    rc = unrolled_jvp_common(h, who, alpha, false, am, an, pp, ndir, d_df, d_da, d_du, d_u, nullptr, each);
+    if (dw) HIPCHK(h, hipMemcpyAsync(d_dw, dw, nd * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    JvpWeight Wd{};
+    if (W) Wd = JvpWeight{W->w, W->wo, d_dw};
+    rc = unrolled_jvp_common(h, who, alpha, false, am, an, pp, ndir, d_df, d_da, d_du, d_u, nullptr, each, W ? &Wd : nullptr);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(du_out, d_du, nt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (u_out) HIPCHK(h, hipMemcpyAsync(u_out, d_u, h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -4615,14 +4667,15 @@ static int unrolled_jvp_host(bpltv_t* h, const double* alpha, int am, int an, co
 }
 
 static int unrolled_jvp_entry(bpltv_t* h, const char* what, bool dev, const double* alpha, int am, int an, const bpltv_params* pp, int ndir,
-                              const double* df, const double* dalpha, double* du, double* u, bool each) {
+                              const double* df, const double* dalpha, double* du, double* u, bool each, const JvpWeight* W = nullptr) {
     if (!h) return BPLTV_E_ARG;
     if (h->multi)
-        return weighted_multi(h, what, false, [&](bpltv_t* c) { return unrolled_jvp_entry(c, what, dev, alpha, am, an, pp, ndir, df, dalpha, du, u, each); },
-                              kUnrolled);
-    if (!dev) return unrolled_jvp_host(h, alpha, am, an, pp, ndir, df, dalpha, du, u, each);
+        return weighted_multi(h, what, false, [&](bpltv_t* c) { return unrolled_jvp_entry(c, what, dev, alpha, am, an, pp, ndir, df, dalpha, du, u, each, W); },
+                              W ? kTapedWeighted.multi_name : kUnrolled);
+    const char* who = W ? "weighted_unrolled_jvp" : (each ? "unrolled_jvp_each" : "unrolled_jvp");
+    if (!dev) return unrolled_jvp_host(h, who, alpha, am, an, pp, ndir, df, dalpha, du, u, each, W);
     HIPCHK(h, hipSetDevice(h->device));
-    return unrolled_jvp_common(h, each ? "unrolled_jvp_each" : "unrolled_jvp", alpha, true, am, an, pp, ndir, df, dalpha, du, u, nullptr, each);
+    return unrolled_jvp_common(h, who, alpha, true, am, an, pp, ndir, df, dalpha, du, u, nullptr, each, W);
 }
 
 int bpltv_unrolled_jvp(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, int ndir, const double* df,
@@ -4641,24 +4694,35 @@ int bpltv_unrolled_jvp_device(bpltv_t* h, const double* d_alpha, int am, int an,
                               const double* d_dalpha, double* d_du, double* d_u) {
     return unrolled_jvp_entry(h, "bpltv_unrolled_jvp_device", true, d_alpha, am, an, pp, ndir, d_df, d_dalpha, d_du, d_u, false);
 }
+int bpltv_weighted_unrolled_jvp(bpltv_t* h, const double* w, int wo, const double* alpha, int am, int an, const bpltv_params* pp, int ndir,
+                                const double* df, const double* dalpha, const double* dw, double* du_out, double* u_out) {
+    const JvpWeight W{w, wo, dw};
+    return unrolled_jvp_entry(h, "bpltv_weighted_unrolled_jvp", false, alpha, am, an, pp, ndir, df, dalpha, du_out, u_out, false, &W);
+}
+int bpltv_weighted_unrolled_jvp_device(bpltv_t* h, const double* d_w, int wo, const double* d_alpha, int am, int an, const bpltv_params* pp,
+                                       int ndir, const double* d_df, const double* d_dalpha, const double* d_dw, double* d_du, double* d_u) {
+    const JvpWeight W{d_w, wo, d_dw};
+    return unrolled_jvp_entry(h, "bpltv_weighted_unrolled_jvp_device", true, d_alpha, am, an, pp, ndir, d_df, d_dalpha, d_du, d_u, false, &W);
+}
 
 // Gradient and Gauss-Newton Hessian of the K-step loss 0.5||u_K(alpha) - ubar||^2 from P = am*an <= GN_MAXP unit-direction
 // tangent sweeps: [J | u_K - ubar] into gn_gram_kernel / gn_final_kernel, as gauss_newton does for the implicit Jacobian.
-int bpltv_unrolled_gauss_newton(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, double* cost_out,
-                                double* grad_out, double* hess_out) {
-    const char* who = "unrolled_gauss_newton";
+// w (nullable: the TV model; wo planes on the host): the weighted iterations' loss.
+static int unrolled_gauss_newton_entry(bpltv_t* h, const char* what, const double* w, int wo, const double* alpha, int am, int an,
+                                       const bpltv_params* pp, double* cost_out, double* grad_out, double* hess_out) {
+    const char* who = what + 6;   // (without "bpltv_")
     if (!h) return BPLTV_E_ARG;
     if (h->multi)
-        return weighted_multi(h, "bpltv_unrolled_gauss_newton", false, [&](bpltv_t* c) {
-            return bpltv_unrolled_gauss_newton(c, alpha, am, an, pp, cost_out, grad_out, hess_out);
-        }, kUnrolled);
+        return weighted_multi(h, what, false, [&](bpltv_t* c) {
+            return unrolled_gauss_newton_entry(c, what, w, wo, alpha, am, an, pp, cost_out, grad_out, hess_out);
+        }, w ? kTapedWeighted.multi_name : kUnrolled);
     if (!alpha || !cost_out || !grad_out || !hess_out) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
     if (am < 1 || an < 1 || am > h->M || an > h->N)
         return set_err(h, BPLTV_E_ARG, "%s: parameter shape %dx%d (image %dx%d)", who, am, an, h->M, h->N);
     const bool amap = am == h->M && an == h->N && !(h->M == 1 && h->N == 1);
     if (amap || (long)am * an > GN_MAXP)
-        return set_err(h, BPLTV_E_UNSUPPORTED, "%s: a scalar or a patch parameter of at most %d entries (got %dx%d%s); use bpltv_unrolled_jvp for Jacobian columns",
-                       who, GN_MAXP, am, an, amap ? ", a pixel map" : "");
+        return set_err(h, BPLTV_E_UNSUPPORTED, "%s: a scalar or a patch parameter of at most %d entries (got %dx%d%s); use bpltv_%sunrolled_jvp for Jacobian columns",
+                       who, GN_MAXP, am, an, amap ? ", a pixel map" : "", w ? "weighted_" : "");
     if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: bpltv_set_data has not been called", who);
     const int P = am * an;
     const size_t nout = (size_t)P + (size_t)P * P;
@@ -4679,7 +4743,8 @@ int bpltv_unrolled_gauss_newton(bpltv_t* h, const double* alpha, int am, int an,
     HIPCHK(h, hipMemcpyAsync(d_e, eye.data(), eye.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));   // (eye is a local)
     const double* d_x = nullptr;
-    int rc = unrolled_jvp_common(h, who, alpha, false, am, an, pp, P, nullptr, d_e, d_J, nullptr, &d_x);
+    const JvpWeight W{w, wo, nullptr};
+    int rc = unrolled_jvp_common(h, who, alpha, false, am, an, pp, P, nullptr, d_e, d_J, nullptr, &d_x, false, w ? &W : nullptr);
     if (rc) return rc;
     h->has_per_image = false;   // compute_cost writes d_perimg and d_red
     rc = compute_cost(h, d_x, h->d_ubar, d_out + nout);
@@ -4694,6 +4759,16 @@ int bpltv_unrolled_gauss_newton(bpltv_t* h, const double* alpha, int am, int an,
     std::memcpy(hess_out, out.data() + P, (size_t)P * P * sizeof(double));
     *cost_out = out[nout];
     return BPLTV_OK;
+}
+int bpltv_unrolled_gauss_newton(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, double* cost_out,
+                                double* grad_out, double* hess_out) {
+    return unrolled_gauss_newton_entry(h, "bpltv_unrolled_gauss_newton", nullptr, 1, alpha, am, an, pp, cost_out, grad_out, hess_out);
+}
+int bpltv_weighted_unrolled_gauss_newton(bpltv_t* h, const double* w, int wo, const double* alpha, int am, int an, const bpltv_params* pp,
+                                         double* cost_out, double* grad_out, double* hess_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (!w) return set_err(h, BPLTV_E_ARG, "weighted_unrolled_gauss_newton: w is a null pointer");
+    return unrolled_gauss_newton_entry(h, "bpltv_weighted_unrolled_gauss_newton", w, wo, alpha, am, an, pp, cost_out, grad_out, hess_out);
 }
 
 int bpltv_u_device(bpltv_t* h, const double** d_u) {

@@ -698,6 +698,70 @@ class TVSolver:
                                                           C.byref(cost), _ptr(grad), _ptr(H)))
         return float(cost.value), (float(grad[0]) if scalar else grad.reshape(an, am)), H
 
+    # -- forward mode through the weighted iterations (bpltv_weighted_unrolled_jvp / _gauss_newton) -----------
+    def weighted_unrolled_jvp(self, x, w, df=None, dalpha=None, dw=None, want_u=False, **kw):
+        """Jacobian-vector product of the maxiter-step map u = weighted_unrolled_denoise(x, w) of the resident f
+        (bpltv_weighted_unrolled_jvp): a tangent sweep through the weighted iterations, no tape -- the linear map whose
+        transpose weighted_unrolled_vjp computes; w >= 0, zeros allowed (a mask).  df: (O, N, M), or (K, O, N, M) for K
+        directions; dalpha: shaped like x, or with a leading K; dw: shaped like w, or with a leading K; any may be None
+        (zero), not all three.  Returns du of shape (O, N, M), or (K, O, N, M) when a leading K was given; with want_u,
+        (du, u) with u = weighted_denoise(x, w) bit for bit.  The step table (gamma = min w) is held fixed."""
+        what = "weighted_unrolled_jvp"
+        a, am, an, scalar = _alpha_arg(x)
+        wa, wo = self._weight(w)
+        if df is None and dalpha is None and dw is None:
+            raise ValueError("%s: df, dalpha and dw are all None" % what)
+        K, batched = None, False
+        if df is not None or dalpha is not None:
+            df, dalpha, K, batched = self._tangents(what, df, dalpha, () if scalar else (an, am))
+        if dw is not None:
+            dw = np.ascontiguousarray(dw, dtype=np.float64)
+            if dw.shape == wa.shape:
+                dw = dw[None]
+            elif dw.shape[1:] == wa.shape:
+                batched = True
+            else:
+                raise ValueError("%s: dw has shape %s, expected %s or (K,) + %s" % (what, dw.shape, wa.shape, wa.shape))
+            if K is None:
+                K = dw.shape[0]
+            if K < 1 or dw.shape[0] != K:
+                raise ValueError("%s: the tangents hold different numbers of directions" % what)
+        p = self.params(**kw)
+        du = np.empty((K, self.O, self.N, self.M))
+        u = np.empty((self.O, self.N, self.M)) if want_u else None
+        self._check(self._lib.bpltv_weighted_unrolled_jvp(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p), K,
+                                                          _ptr(df) if df is not None else None,
+                                                          _ptr(dalpha) if dalpha is not None else None,
+                                                          _ptr(dw) if dw is not None else None, _ptr(du),
+                                                          _ptr(u) if want_u else None))
+        du = du if batched else du[0]
+        return (du, u) if want_u else du
+
+    def weighted_unrolled_jvp_device(self, w_ptr, wo, alpha_ptr, am, an, df_ptr, dalpha_ptr, dw_ptr, du_ptr, u_ptr=None,
+                                     ndir=1, **kw):
+        """bpltv_weighted_unrolled_jvp_device: w (wo planes), the parameter (am*an doubles), df and du (ndir*M*N*O), dalpha
+        (ndir*am*an), dw (ndir*M*N*wo) and u (M*N*O) all resident in HBM (raw device pointers); any tangent pointer may be
+        0 / None, not all three; u_ptr may be 0 / None."""
+        p = self.params(**kw)
+        self._check(self._lib.bpltv_weighted_unrolled_jvp_device(self._h, C.c_void_p(w_ptr), int(wo), C.c_void_p(alpha_ptr),
+                                                                 int(am), int(an), C.byref(p), int(ndir),
+                                                                 C.c_void_p(df_ptr or None), C.c_void_p(dalpha_ptr or None),
+                                                                 C.c_void_p(dw_ptr or None), C.c_void_p(du_ptr),
+                                                                 C.c_void_p(u_ptr or None)))
+
+    def weighted_unrolled_gauss_newton(self, x, w, **kw):
+        """Gauss-Newton model of the maxiter-step loss 0.5||u_K(x) - ubar||^2 of the weighted iterations on the resident
+        dataset (bpltv_weighted_unrolled_gauss_newton): (cost, grad, H) as unrolled_gauss_newton's, J by P tangent sweeps
+        in the parameter.  A float or an (n, m) patch parameter with at most 16 entries; w >= 0, zeros allowed."""
+        a, am, an, scalar = _alpha_arg(x)
+        wa, wo = self._weight(w)
+        p = self.params(**kw)
+        P = am * an
+        cost, grad, H = C.c_double(0.0), np.empty(P), np.empty((P, P))
+        self._check(self._lib.bpltv_weighted_unrolled_gauss_newton(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p),
+                                                                   C.byref(cost), _ptr(grad), _ptr(H)))
+        return float(cost.value), (float(grad[0]) if scalar else grad.reshape(an, am)), H
+
     # -- one parameter per image (bpltv_denoise_each / bpltv_vjp_each) ---------------------------------------
     def _each_arg(self, alphas):
         """alphas: (O,) scalars or (O, n, m) blocks (numpy (n, m) == Julia m x n), one per image."""

@@ -74,7 +74,9 @@ f, alpha and w as for tv_denoise_weighted, the same u bit for bit, but w may hol
 derivative of the maxiter-step map (one bpltv_weighted_unrolled_vjp_device call over a tape of 3 * maxiter * B*H*W doubles
 the forward pass allocates as a torch tensor), which scales nothing with 1/sqrt(w).  It returns f.grad, alpha.grad and
 w.grad as needs_input_grad asks, so alpha, f and a fidelity map can be trained through a masked (inpainting) solve; at
-w = 0, w.grad is the one-sided derivative.  The step table (gamma = min w) is held fixed.  No jvp.
+w = 0, w.grad is the one-sided derivative.  The step table (gamma = min w) is held fixed.  By default it carries no jvp;
+tv_denoise_weighted_unrolled(..., forward_mode=True) selects a function whose jvp is one bpltv_weighted_unrolled_jvp_device
+call: a tangent sweep through the weighted iterations with tangents on f, alpha and w, which reads no tape.
 
     u = sumregs_denoise_unrolled(f, alpha, maxiter=50)           # ... of the sum-of-regularisers model (bpltv_sumregs_unrolled_*)
     u = sumregs_denoise_unrolled_each(f, alpha, maxiter=30)      # ... with three weights per image
@@ -640,15 +642,55 @@ class TVDenoiseWeightedUnrolledFunction(torch.autograd.Function):
         return gf, (ga.reshape(alpha.shape) if need_a else None), gw, None
 
 
-def tv_denoise_weighted_unrolled(f, alpha, w, maxiter=50, checkpoint_every=None, **solver_kw):
+class TVDenoiseWeightedUnrolledForwardFunction(TVDenoiseWeightedUnrolledFunction):
+    """TVDenoiseWeightedUnrolledFunction with a jvp (tv_denoise_weighted_unrolled(..., forward_mode=True)): forward is the
+    base class's taped solve, so backward keeps working; the jvp is one tangent sweep through the weighted iterations
+    (TVSolver.weighted_unrolled_jvp_device, one direction), which reads no tape."""
+
+    @staticmethod
+    def forward(ctx, f, alpha, w, solver_kw):
+        u = TVDenoiseWeightedUnrolledFunction.forward(ctx, f, alpha, w, solver_kw)
+        ctx.save_for_forward(f.detach().contiguous(), alpha.detach().contiguous(), w.detach().contiguous())
+        ctx.set_materialize_grads(False)   # an input without a tangent reaches jvp as None, and the library as NULL
+        return u
+
+    @staticmethod
+    def jvp(ctx, df, dalpha, dw, _solver_kw):
+        f, alpha, w = ctx.saved_tensors
+        df, dalpha, dw = _tangent(df, f, "f"), _tangent(dalpha, alpha, "alpha"), _tangent(dw, w, "w")
+        if df is None and dalpha is None and dw is None:
+            return torch.zeros_like(f)
+        du = torch.empty_like(f)
+        _sync(f.device)
+        ctx.solver.set_data_device(f.data_ptr(), f.data_ptr())   # the sweep reads the handle's dataset
+        ctx.solver.weighted_unrolled_jvp_device(w.data_ptr(), ctx.wo, alpha.data_ptr(), ctx.am, ctx.an,
+                                                df.data_ptr() if df is not None else None,
+                                                dalpha.data_ptr() if dalpha is not None else None,
+                                                dw.data_ptr() if dw is not None else None, du.data_ptr(), None, ndir=1,
+                                                **_no_checkpoint(ctx.solver_kw))
+        return du
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gu):
+        if gu is None:
+            return None, None, None, None
+        return TVDenoiseWeightedUnrolledFunction.backward(ctx, gu)
+
+
+def tv_denoise_weighted_unrolled(f, alpha, w, maxiter=50, checkpoint_every=None, forward_mode=False, **solver_kw):
     """u = weighted_denoise(f, alpha, w) by exactly maxiter PDHG iterations (TVSolver.weighted_unrolled_denoise_device:
     tv_denoise_weighted's u bit for bit at that maxiter), differentiable in f, alpha and w THROUGH the iterations: backward
     is the exact derivative of the maxiter-step map (TVSolver.weighted_unrolled_vjp_device), with the step table held
     fixed.  w: float64, (H, W) or f's shape (B, H, W), on f's device, >= 0 -- zeros are allowed, so a mask can be trained
     through (inpainting), which tv_denoise_weighted's implicit gradient cannot.  solver_kw: the solver parameters of
-    TVSolver.params (rho, init and order must stay 0), used by the forward solve and the sweep alike.  checkpoint_every: as
-    tv_denoise_unrolled's."""
-    return TVDenoiseWeightedUnrolledFunction.apply(f, alpha, w, _with_checkpoint(dict(solver_kw, maxiter=int(maxiter)), checkpoint_every))
+    TVSolver.params (rho, init and order must stay 0), used by the forward solve and the sweeps alike.  checkpoint_every: as
+    tv_denoise_unrolled's.
+    forward_mode: also usable under torch.autograd.forward_ad, with tangents on f, alpha and w (the function then carries a
+    jvp, a tangent sweep through the weighted iterations, bpltv_weighted_unrolled_jvp_device, which reads no tape and is
+    unaffected by checkpoint_every); without it forward-mode AD raises torch's "not implemented" error, as before."""
+    fn = TVDenoiseWeightedUnrolledForwardFunction if forward_mode else TVDenoiseWeightedUnrolledFunction
+    return fn.apply(f, alpha, w, _with_checkpoint(dict(solver_kw, maxiter=int(maxiter)), checkpoint_every))
 
 
 class TVDenoiseUnrolledFunction(torch.autograd.Function):

@@ -137,7 +137,8 @@ typedef struct bpltv_stats {
                                   7 reverse sweep over the taped iterations (bpltv_unrolled_vjp),
                                   8 tangent sweep through the iterations (bpltv_unrolled_jvp),
                                   9 reverse sweep over the taped weighted iterations (bpltv_weighted_unrolled_vjp),
-                                  10 reverse sweep over the taped sum-of-regularisers iterations (bpltv_sumregs_unrolled_vjp) */
+                                  10 reverse sweep over the taped sum-of-regularisers iterations (bpltv_sumregs_unrolled_vjp),
+                                  11 tangent sweep through the weighted iterations (bpltv_weighted_unrolled_jvp) */
     int reg_gradient_used;     /* 1 if the last evaluate took the gradient_reg branch             */
     int ngpus;                 /* distinct devices behind this handle (1 for bpltv_create)        */
     int shards;                /* image shards (= worker threads) behind this handle              */
@@ -508,6 +509,47 @@ int bpltv_unrolled_jvp_device(bpltv_t *h, const double *d_alpha, int am, int an,
                               const double *d_df, const double *d_dalpha, double *d_du, double *d_u /* may be NULL */);
 int bpltv_unrolled_gauss_newton(bpltv_t *h, const double *alpha, int am, int an, const bpltv_params *p,
                                 double *cost_out, double *grad_out, double *hess_out);
+
+/* Forward mode through the PDHG iterations of the weighted model: the tangent of the K-step map that
+ * bpltv_weighted_unrolled_vjp transposes -- <gu, du> = <grad_f(gu), df> + <grad_alpha(gu), dalpha> + <grad_w(gu), dw> for any
+ * gu -- with no tape and, like that VJP, no w > 0: a mask (w in {0, 1}) has sensitivities in f, alpha and w.  A sweep carries
+ * (dx, dy1, dy2) beside (x, y1, y2) in 16 planes of M*N*O doubles (two state sets of six planes, then the staged df, dalpha, w
+ * and dw) and 8 check words, owned by the handle and apart from the TV sweep's 14 (allocated on first use, freed by
+ * bpltv_destroy; BPLTV_E_NOMEM, with the handle as it was, when they cannot be allocated), whatever maxiter is.  Float64 (also
+ * on dtype = 32 handles), one parameter shared by the batch; f is the resident dataset (BPLTV_E_NODATA without one).  The
+ * contract is the union of bpltv_unrolled_jvp's and bpltv_weighted_unrolled_denoise's.
+ *
+ * bpltv_weighted_unrolled_jvp: w, wo, alpha, am, an and params as bpltv_weighted_unrolled_denoise (w and alpha finite and >= 0,
+ * zeros legal, wo = 1 or O; rho, init and order must be 0, BPLTV_E_UNSUPPORTED; maxiter < 1 is BPLTV_E_ARG; check_every, gap_tol
+ * and the option "tape_checkpoint" are ignored).  ndir >= 1 directions, direction-major: df is NULL or ndir * M*N*O doubles,
+ * dalpha NULL or ndir * am*an doubles indexed as alpha is, dw NULL or ndir * M*N*wo doubles laid out as w is (wo = 1: one plane
+ * shared by all images), not all three NULL (a NULL tangent is zero and is not loaded); du_out: ndir * M*N*O doubles.  Direction
+ * d of a call is bitwise the ndir = 1 call with that direction.  u_out (may be NULL): the primal result, M*N*O doubles,
+ * bpltv_weighted_denoise's u bit for bit.  The tangents must be finite (the host form checks them on the host, the device form
+ * on the device); ndir < 1, all tangents NULL, a bad wo or parameter shape or a NULL du_out is BPLTV_E_ARG; every rejection
+ * comes before anything of the handle changes.  At w = 0, dw is the one-sided derivative.  The step table depends on gamma =
+ * min w; the sweep holds it fixed, exactly as bpltv_weighted_unrolled_vjp does, so it is that VJP's exact transpose: exact for
+ * accel = 0 and for gamma = 0 (every mask), while with gamma > 0 and acceleration the derivative through the step sizes --
+ * which touches only the entries of w that attain the minimum -- is omitted.  With w == 1 and dw NULL, du agrees with
+ * bpltv_unrolled_jvp's to rounding (u bit for bit).  The sweep stages w, the parameter and the tangents apart and runs in planes
+ * of its own: the last solve, bpltv_u_device, bpltv_duality_gap, the three tapes and the solve statistics stay as they were,
+ * and it shares no captured graph with any other call.  stats: only adjoint_ms (the HIP-event time of the sweeps) and
+ * adjoint_method = 11 change.  The results do not depend on tile_iters, on the launch chains, on use_graph or on the host or
+ * device form.
+ *
+ * bpltv_weighted_unrolled_gauss_newton: as bpltv_unrolled_gauss_newton, for the weighted iterations: a scalar or a patch
+ * parameter of P = am*an <= 16 entries (anything else: BPLTV_E_UNSUPPORTED), P unit-direction sweeps in alpha and, with ubar the
+ * resident dataset's, cost_out = 0.5||u_K - ubar||^2, grad_out = J^T (u_K - ubar) and hess_out = J^T J (P x P, column major,
+ * symmetric bit for bit); sums per image, then over the images in image order, no atomics.
+ * Multi-device handles over more than one shard: BPLTV_E_UNSUPPORTED (all three); one shard is forwarded. */
+int bpltv_weighted_unrolled_jvp(bpltv_t *h, const double *w, int wo, const double *alpha, int am, int an,
+                                const bpltv_params *p, int ndir, const double *df, const double *dalpha, const double *dw,
+                                double *du_out, double *u_out /* may be NULL */);
+int bpltv_weighted_unrolled_jvp_device(bpltv_t *h, const double *d_w, int wo, const double *d_alpha, int am, int an,
+                                       const bpltv_params *p, int ndir, const double *d_df, const double *d_dalpha,
+                                       const double *d_dw, double *d_du, double *d_u /* may be NULL */);
+int bpltv_weighted_unrolled_gauss_newton(bpltv_t *h, const double *w, int wo, const double *alpha, int am, int an,
+                                         const bpltv_params *p, double *cost_out, double *grad_out, double *hess_out);
 
 /* The unrolled solve, VJP and JVP with one parameter per image: what a network that predicts alpha per sample needs at a
  * small, fixed iteration count.  alphas: O blocks of am x an doubles, column major, block k at alphas + k*am*an, image k

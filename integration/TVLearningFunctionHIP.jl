@@ -6,7 +6,7 @@
 # Same exports as src/TVLearningFunctionVec.jl:6
 export tv_op_learning_function, denoise, sumregs_learning_function, tv_vjp, sumregs_vjp, tv_jvp, tv_gauss_newton,
        sumregs_jvp, sumregs_gauss_newton, weighted_denoise, weighted_vjp, unrolled_denoise_each, unrolled_vjp_each,
-       unrolled_jvp_each
+       unrolled_jvp_each, weighted_unrolled_jvp
 
 const libbpltv = "libbpltv"            # on LD_LIBRARY_PATH, or an absolute path
 
@@ -228,6 +228,29 @@ function weighted_vjp(h::BpltvHandle, u::Array{Float64,3}, f::Array{Float64,3}, 
         (Ptr{Cvoid}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Cint, Ref{BpltvParams}, Ptr{Cdouble},
          Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}), h.ptr, u, f, w, wo, a, am, an, p, ḡ, gf, ga, gw))
     return gf, (α isa Real ? ga[1] : reshape(ga, size(α))), gw
+end
+
+# Forward mode through the weighted PDHG iterations (include/bpltv.h, bpltv_weighted_unrolled_jvp): du of the maxiter-step map
+# u = weighted_denoise(data, x, w) for one direction (df, dα, dw), by a tangent sweep that records no tape and -- unlike
+# weighted_vjp -- needs no w > 0, so a mask has sensitivities.  df: nothing or M x N x O; dα: nothing, a number for a scalar x
+# or shaped like x; dw: nothing or shaped like w; not all three nothing.  Returns (du, u) with u the primal result.  The step
+# table (γ = min w) is held fixed.
+function weighted_unrolled_jvp(data::Array{Float64,3}, x, w::Union{Matrix{Float64},Array{Float64,3}};
+                               df = nothing, dα = nothing, dw = nothing, kwargs...)
+    h = handle_for(data, data)
+    a, am, an = alpha_arg(x)
+    wo = ndims(w) == 2 ? 1 : size(w, 3)
+    df === nothing && dα === nothing && dw === nothing && error("weighted_unrolled_jvp: df, dα and dw are all nothing")
+    dw === nothing || size(dw) == size(w) || error("weighted_unrolled_jvp: dw must have the shape of w")
+    tf = df === nothing ? C_NULL : Array{Float64}(df)
+    ta = dα === nothing ? C_NULL : (dα isa Real ? [Float64(dα)] : Array{Float64}(dα))
+    tw = dw === nothing ? C_NULL : Array{Float64}(dw)
+    du = similar(data); u = similar(data)
+    p = Ref(default_params(; kwargs...))
+    GC.@preserve w a tf ta tw du u bpltv_check(h, ccall((:bpltv_weighted_unrolled_jvp, libbpltv), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Cint, Ref{BpltvParams}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+         Ptr{Cdouble}, Ptr{Cdouble}), h.ptr, w, wo, a, am, an, p, 1, tf, ta, tw, du, u))
+    return du, u
 end
 
 # Jacobian-vector product of u = denoise(f, α) (include/bpltv.h, bpltv_jvp): du for the tangents (df, dα), the linear map
