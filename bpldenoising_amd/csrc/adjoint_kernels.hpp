@@ -850,8 +850,10 @@ __global__ __launch_bounds__(256) void patch_sum_kernel(const double* __restrict
 // diagonal is 4 kappa, the scaling cancels in the quotient, and the rounding of p itself (no double vector does better:
 // r = kappa G^T G (p - round(p))) reads as a residual of kappa eps |p| / |rhs| ~ 1e-4: the gate refused a solve
 // that was correct to 3e-11 and the call went on to a weight of 1e12 or 1e10.  So the scaled pair leaves out the rows
-// that carry the weight: d_k >= skip * s_k^2 (skip = the active-set weight; s the node scaling, nullptr = 1; skip =
-// +inf: every row counts, as for gradient_reg and the sum of regularisers).  An image with no other row reports 0.
+// that carry the weight: d_k >= skip * s_k^2 (skip = the smallest share one active element adds to a diagonal: the
+// active-set weight for TV, a quarter of it for the sum of regularisers, whose centred operator has coefficients 1/2;
+// s the node scaling, nullptr = 1; skip = +inf: every row counts, as for both models' gradient_reg).  An image with no
+// other row reports 0.
 // grid (RESN_BLK, O): partials[(img * RESN_BLK + b) * 4 + {0..3}]; adj_resnorm_final_kernel adds them in block order
 // (no atomics: reproducible) into out[img * 4 + {0..3}].
 constexpr int RESN_BLK = 64;

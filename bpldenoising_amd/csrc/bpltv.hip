@@ -2197,7 +2197,9 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int re
     const double kcap = p.kappa_cap > 0.0 ? p.kappa_cap : 1e14;
     if (kact > kcap) kact = kcap;
     kact *= kappa_scale;
-    const int nref = p.refine < 0 ? (reg ? 1 : 2) : p.refine;
+    // kappa = 1e14 for every parameter kind here: on images with a real active set two sweeps left the gradients up to 5e2
+    // times outside 1e-8 max|p| + 1e-6 |.| and four 1.2 times; five leave 0.06 of it on every factorisation
+    const int nref = p.refine < 0 ? (reg ? 1 : 5) : p.refine;
     // forward mode: every direction keeps its own residual statistics (the gate takes the worst)
     const bool tangent = g.ndir > 0;
     const int ndir = tangent ? g.ndir : 1;
@@ -2295,8 +2297,10 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int re
             }
             residual(dr);
             double* resn_part = h->d_resn + 4 * (size_t)O + 4 * (size_t)c0 * RESN_BLK;
+            // the gate leaves out the rows that carry the active-set weight: the smallest share an active element adds to a
+            // diagonal is the centred operator's (1/2)^2 kappa (forward and backward differences add kappa or more)
             hipLaunchKernelGGL(adj_resnorm_kernel, dim3(RESN_BLK, nimg), dim3(256), 0, h->stream, dr, C.rhs, diag, (int)npx, resn_part,
-                               (const double*)nullptr, (double)HUGE_VAL);
+                               (const double*)nullptr, reg ? (double)HUGE_VAL : 0.25 * kact);
             hipLaunchKernelGGL(adj_resnorm_final_kernel, dim3((4 * nimg + 63) / 64), dim3(64), 0, h->stream, resn_part, nimg,
                                resn_fin + 4 * ((size_t)d * O + c0));
             if (tangent)   // du is the solution itself: straight into the direction's slice of the caller's array

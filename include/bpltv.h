@@ -76,7 +76,8 @@ typedef struct bpltv_params {
     int refine;          /* iterative-refinement sweeps of the adjoint solve; < 0 = default: 4 / 1 / 0 for the
                             scalar gradient / patch and pixel-map parameters / gradient_reg with nested
                             dissection and the HBM band, 3 / 2 / 2 with block cyclic reduction and the
-                            LDS band (bpltv_weighted_vjp included)                                   */
+                            LDS band (bpltv_weighted_vjp included); the sum of regularisers: 5, and 1 for
+                            gradient_reg, on every factorisation                                      */
     int deterministic;   /* multi-GPU handles, scalar / patch parameters: 1 = all-gather the per-image rows
                             [cost_k, grad_k...] and add them in global image order, so that cost and grad are
                             bitwise the same for every number of GPUs (and equal to a single handle's);

@@ -15,7 +15,9 @@ and the reduced system is assembled with scipy.sparse from oracle.np_twin_sumreg
 du = A^-T r by scipy's sparse LU (jvp_image); for images of a few dozen pixels, where kap = 1e14 can push cond(A) past
 what double precision resolves, by a rational solve of the same system (jvp_image_exact, jvp_image_small).  Nothing here
 shares code with the library's kernels.  tests/test_sumregs_jvp_abi.py pins this reference to the oracle's own gradients
-by the transpose identity, and the rational solve to scipy's where the system is well conditioned."""
+by the transpose identity, and the rational solve to scipy's where the system is well conditioned.  On images with a
+real active set (flat regions of more than a few pixels) jvp_image is off by 1e-4 of max|du| and more; the reference there
+is the literal unreduced system of tests/sumregs_active_ref.py."""
 import numpy as np
 
 ACT_TOL = 1e-12

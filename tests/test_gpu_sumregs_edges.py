@@ -177,15 +177,15 @@ def _methods(reg, alpha, npx):
     return [x for x in m if npx > 1 or x[1] == "nd"]
 
 
-# Refinement sweeps of the factorisation comparisons.  The oracle refines three times (nref = 3), the device twice by
-# default; each sweep gains several digits with Cholesky on the kappa = 1/eps rows of the gradient, so at the oracle's
-# count every factorisation lands within 3e-7 of max|g| of it, thin shapes included (at two sweeps (2, 1, 9), (1, 2, 2)
+# Refinement sweeps of the factorisation comparisons.  The oracle refines three times (nref = 3), the device five times by
+# default (twice until tests/test_gpu_sumregs_active_set.py); each sweep gains a digit and more with Cholesky on the
+# kappa = 1/eps rows of the gradient, so at the oracle's count every factorisation lands within 3e-7 of max|g| of it, thin shapes included (at two sweeps (2, 1, 9), (1, 2, 2)
 # and (2, 5, 3) stay at 1.1e-6 / 3.0e-6 / 1.4e-6).  LU without pivoting forced on that symmetric system (option
 # sr_force_lu, a test aid) inverts its pivot blocks by Gauss-Jordan without pivoting and gains about one digit per sweep
 # there (1 x 2 patch on 4 x 64 x 80: 2.7e-5 / 7.5e-6 / 2.1e-6 / 1.6e-7 / 9e-10 after 2 / 3 / 4 / 6 / 10 sweeps), so it
 # gets ten.  gradient_reg (gamma = 1e8 instead of 1/eps) is at rounding level after one sweep in every factorisation.
 REFINE, REFINE_FORCED_LU = 3, 10
-# The device's default of two sweeps, on the thin shapes named above (the product path, nd): 5x the measured gap.
+# The device's former default of two sweeps, on the thin shapes named above (the product path, nd): 5x the gap measured then.
 THIN_TOL = {(2, 1, 9): 5e-6, (1, 2, 2): 1.5e-5, (2, 5, 3): 7e-6}
 
 
