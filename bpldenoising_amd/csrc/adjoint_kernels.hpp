@@ -852,8 +852,9 @@ __global__ __launch_bounds__(256) void patch_sum_kernel(const double* __restrict
 // that was correct to 3e-11 and the call went on to a weight of 1e12 or 1e10.  So the scaled pair leaves out the rows
 // that carry the weight: d_k >= skip * s_k^2 (skip = the smallest share one active element adds to a diagonal: the
 // active-set weight for TV, a quarter of it for the sum of regularisers, whose centred operator has coefficients 1/2;
-// s the node scaling, nullptr = 1; skip = +inf: every row counts, as for both models' gradient_reg).  An image with no
-// other row reports 0.
+// s the node scaling, nullptr = 1; skip = +inf: every row counts, as for both models' gradient_reg).  kap != nullptr (the
+// weighted model, whose element weights may be smaller than skip): also the rows an active element of that plane adds to.
+// An image with no other row reports 0.
 // grid (RESN_BLK, O): partials[(img * RESN_BLK + b) * 4 + {0..3}]; adj_resnorm_final_kernel adds them in block order
 // (no atomics: reproducible) into out[img * 4 + {0..3}].
 constexpr int RESN_BLK = 64;
@@ -861,7 +862,8 @@ __global__ __launch_bounds__(256) void adj_resnorm_kernel(const double* __restri
                                                           const double* __restrict__ rhs,
                                                           const double* __restrict__ diag, int npx,
                                                           double* __restrict__ partial,
-                                                          const double* __restrict__ s, double skip) {
+                                                          const double* __restrict__ s, double skip,
+                                                          const double* __restrict__ kap, int M) {
     __shared__ double sh[4];
     const size_t base = (size_t)blockIdx.y * npx;
     double s0 = 0.0, s1 = 0.0, s2 = 0.0, s3 = 0.0;
@@ -870,7 +872,13 @@ __global__ __launch_bounds__(256) void adj_resnorm_kernel(const double* __restri
         const double sv = s ? s[base + q] : 1.0;
         s0 += rv * rv;
         s1 += bv * bv;
-        if (!(d >= skip * (sv * sv))) {
+        bool touched = false;   // weighted model: an element's weight may lie below skip (weighted_adj_setup_kernel)
+        if (kap) {
+            const int i = (int)(q % M);
+            touched = (kap[base + q] > 0.0 && (i < M - 1 || q + M < (size_t)npx)) || (i > 0 && kap[base + q - 1] > 0.0) ||
+                      (q >= (size_t)M && kap[base + q - M] > 0.0);
+        }
+        if (!(d >= skip * (sv * sv)) && !touched) {
             s2 += rv * rv * di;
             s3 += bv * bv * di;
         }

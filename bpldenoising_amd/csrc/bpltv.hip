@@ -1746,7 +1746,7 @@ int run_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, 
             hipLaunchKernelGGL(adj_residual_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, dr);
             double* resn_part = h->d_resn + 4 * (size_t)O + 4 * (size_t)c0 * RESN_BLK;
             hipLaunchKernelGGL(adj_resnorm_kernel, dim3(RESN_BLK, nimg), dim3(256), 0, h->stream, dr, C.rhs, band4, (int)npx, resn_part,
-                               (const double*)C.s, reg ? HUGE_VAL : kact);
+                               (const double*)C.s, reg ? HUGE_VAL : kact, g.w ? (const double*)C.kap : (const double*)nullptr, M);
             hipLaunchKernelGGL(adj_resnorm_final_kernel, dim3((4 * nimg + 63) / 64), dim3(64), 0, h->stream, resn_part, nimg,
                                resn_fin + 4 * ((size_t)d * O + c0));
             if (tangent)
@@ -2300,7 +2300,7 @@ int run_sr_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int re
             // the gate leaves out the rows that carry the active-set weight: the smallest share an active element adds to a
             // diagonal is the centred operator's (1/2)^2 kappa (forward and backward differences add kappa or more)
             hipLaunchKernelGGL(adj_resnorm_kernel, dim3(RESN_BLK, nimg), dim3(256), 0, h->stream, dr, C.rhs, diag, (int)npx, resn_part,
-                               (const double*)nullptr, reg ? (double)HUGE_VAL : 0.25 * kact);
+                               (const double*)nullptr, reg ? (double)HUGE_VAL : 0.25 * kact, (const double*)nullptr, M);
             hipLaunchKernelGGL(adj_resnorm_final_kernel, dim3((4 * nimg + 63) / 64), dim3(64), 0, h->stream, resn_part, nimg,
                                resn_fin + 4 * ((size_t)d * O + c0));
             if (tangent)   // du is the solution itself: straight into the direction's slice of the caller's array

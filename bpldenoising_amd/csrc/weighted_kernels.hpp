@@ -222,6 +222,7 @@ __global__ __launch_bounds__(256) void weighted_gap_final_kernel(const double* _
 // adj_gradpix_kernel and every factorisation handle through the s plane.  adj_setup_body<true> with reg = 0, then
 //     s = 1 / sqrt(w),   rhs = gu * s            (w == 1: s = 1 and rhs = gu exactly)
 // so that q solves (I + S K S) q = S gu and the physical adjoint state is p = S q.
+constexpr double WEIGHTED_KAPPA_CAP = 4e14;
 __global__ __launch_bounds__(256) void weighted_adj_setup_kernel(const double* __restrict__ u, const double* __restrict__ gu,
                                                                  const double* __restrict__ w, size_t wstride,
                                                                  const double* __restrict__ alpha, int am, int an, int M, int N,
@@ -230,9 +231,24 @@ __global__ __launch_bounds__(256) void weighted_adj_setup_kernel(const double* _
     const size_t npx = (size_t)M * N;
     const size_t q = (size_t)blockIdx.x * 256 + threadIdx.x;
     if (q >= npx * O) return;
-    const double s = 1.0 / sqrt(w[(q / npx) * wstride + q % npx]);
+    const double* wp = w + (q / npx) * wstride;
+    const int k = (int)(q % npx);
+    const double s = 1.0 / sqrt(wp[k]);
     C.s[q] = s;
     C.rhs[q] = gu[q] * s;
+    // An active element enters the scaled matrix as kappa s_a s_b.  Above WEIGHTED_KAPPA_CAP (w < 1/4 at kappa = 1e14) those
+    // entries pass 1/eps and what ties a flat region to the rest of the image -- the identity and its inactive neighbours --
+    // falls below their rounding: every factorisation is then wrong by O(1) in the mode that moves the region as a whole and
+    // the refinement stalls or diverges.  So the element's weight is kappa relative to the smallest
+    // fidelity weight of its nodes: min(kappa, cap * w_min), which keeps kappa s^2 <= cap on all three.
+    const double kp = C.kap[q];
+    if (kp > 0.0) {
+        const int i = k % M, j = k / M;
+        double wmin = wp[k];
+        if (i < M - 1) wmin = fmin(wmin, wp[k + 1]);
+        if (j < N - 1) wmin = fmin(wmin, wp[k + M]);
+        C.kap[q] = fmin(kp, WEIGHTED_KAPPA_CAP * wmin);
+    }
 }
 
 // The outputs: grad_f = w o p and the per-pixel grad_w = -(u - f) o p, p = s q (adj_gradf_kernel's product).  Either

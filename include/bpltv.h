@@ -357,7 +357,11 @@ int bpltv_weighted_denoise_device(bpltv_t *h, const double *d_w, int wo, const d
  * am*an doubles.  Any output may be NULL, not all three; f (M*N*O doubles) may be NULL only if grad_w_out is (BPLTV_E_ARG
  * otherwise).  No dataset is needed.  gu must be finite.  Every rejection comes before anything of the handle changes; w and
  * the parameter are staged apart, so the last solve, bpltv_u_device, bpltv_duality_gap and the captured graphs stay untouched,
- * as with bpltv_vjp.  The residual gate, the image groups and the stats of the adjoint are bpltv_vjp's. */
+ * as with bpltv_vjp.  The residual gate, the image groups and the stats of the adjoint are bpltv_vjp's.  The active-set
+ * weight is relative to the fidelity weight where that is small: an active element gets min(kappa, 4e14 * w_min), w_min the
+ * smallest w of its nodes, so that no entry kappa s^2 of the scaled matrix passes 4e14 (nothing changes while w >= 1/4 at
+ * kappa = 1e14; the result then moves by less than 1e-3 of 1e-8 max|p| from the system with kappa throughout, DESIGN.md
+ * section 4.5); stats.kappa_used stays the kappa of the call. */
 int bpltv_weighted_vjp(bpltv_t *h, const double *u, const double *f, const double *w, int wo, const double *alpha,
                        int am, int an, const bpltv_params *p, const double *gu,
                        double *grad_f_out, double *grad_alpha_out, double *grad_w_out);

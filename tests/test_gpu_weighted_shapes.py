@@ -332,7 +332,7 @@ def test_vjp_on_every_factorisation_matches_the_literal_system(gpu_solver_cls, c
           "(max|p| %.3e)" % (_id(shape), kind, "wO" if per_image else "w1", METHODS[method], st["adjoint_method"],
                              st["kappa_used"], st["adjoint_attempts"], st["adjoint_residual"], d[0], d[1], d[2], pmax))
     assert st["adjoint_method"] == _expected_method(method, M), st
-    assert st["adjoint_residual"] <= 1e-6 and st["adjoint_attempts"] >= 1 and st["adjoint_chunks"] == 1, st
+    assert st["adjoint_residual"] <= 1e-6 and st["adjoint_attempts"] == 1 and st["adjoint_chunks"] == 1, st
     assert gw.shape == w.shape
     for name, a, b in (("grad_f", gf, rf), ("grad_alpha", ga, ra), ("grad_w", gw, rw)):
         assert _close(a, b, pmax), name
