@@ -29,10 +29,7 @@
 #include "pdhg_kernels.hpp"
 #include "sumregs_kernels.hpp"
 #include "weighted_kernels.hpp"
-#include "unrolled_kernels.hpp"
-#include "unrolled_jvp_kernels.hpp"
-#include "weighted_unrolled_jvp_kernels.hpp"
-#include "weighted_unrolled_kernels.hpp"
+#include "tv_tile_kernels.hpp"
 #include "sumregs_unrolled_kernels.hpp"
 #include "multi_gpu.hpp"
 
@@ -476,11 +473,11 @@ struct bpltv_handle {
     double w_min = 0.0;
     bool last_weighted = false;                     // the last solve was bpltv_weighted_denoise: u and the gap are its
     double* d_wst = nullptr;                        // bpltv_weighted_vjp's host staging [f | grad_w], 2 * M*N*O doubles
-    // reverse mode through the iterations (unrolled_kernels.hpp): the handle's own tape of pre-projection duals (allocated on
+    // reverse mode through the iterations (tv_tile_kernels.hpp): the handle's own tape of pre-projection duals (allocated on
     // demand, only grows, remembers what it was recorded with), and the reverse sweep's planes [2 sets x (gx, gy1, gy2) | gf | ga | gu]
     Tape tape;
     double* d_unr = nullptr;                        // 9 * M*N*O doubles
-    // ... of the weighted model (weighted_unrolled_kernels.hpp): a tape of its own (z1, z2 and x per iteration), so that a TV
+    // ... of the weighted model: a tape of its own (z1, z2 and x per iteration), so that a TV
     // tape and a weighted one never stand in for each other, with the weight planes and gamma = min w it was recorded with;
     // the reverse sweep runs in d_unr, its weight gradient in a tenth plane allocated when grad_w is first asked for
     Tape wtape;
@@ -494,10 +491,10 @@ struct bpltv_handle {
     // allocated on first use, only grows
     double* d_seg = nullptr;
     size_t seg_cap = 0;                             // doubles
-    // forward mode through the iterations (unrolled_jvp_kernels.hpp): the tangent sweep's planes [2 sets x (x, y1, y2, dx, dy1,
+    // forward mode through the iterations (tv_tile_kernels.hpp): the tangent sweep's planes [2 sets x (x, y1, y2, dx, dy1,
     // dy2) | df | dalpha], allocated on first use and never moved
     double* d_ujv = nullptr;                        // 14 * M*N*O doubles
-    // ... of the weighted model (weighted_unrolled_jvp_kernels.hpp): planes of its own, [2 sets x 6 | df | dalpha | w | dw] and
+    // ... of the weighted model: planes of its own, [2 sets x 6 | df | dalpha | w | dw] and
     // eight words for the device check of dw, allocated on first use and never moved
     double* d_wjv = nullptr;                        // 16 * M*N*O + 8 doubles
     bpltv_stats_t st;
@@ -3237,12 +3234,12 @@ int check_weight(bpltv_t* h, const char* who, const double* w, bool on_device, s
 // core, and the kernel keeps at most PDHG_MAX_T step rows).  Results do not depend on T.
 struct WeightedPlan { int T, nTi, nTj; };
 int weighted_plan(bpltv_t* h, const bpltv_params& p, WeightedPlan* pl) {
-    auto maxT = [](int L) { return (L <= WT_R) ? PDHG_MAX_T : (WT_R - 1) / 2; };
+    auto maxT = [](int L) { return (L <= TV_R) ? PDHG_MAX_T : (TV_R - 1) / 2; };
     int T = p.tile_iters > 0 ? p.tile_iters : 8;
     T = std::min(T, std::min(PDHG_MAX_T, std::min(maxT(h->M), maxT(h->N))));
     pl->T = T;
-    pl->nTi = tile_count(h->M, WT_R, T);
-    pl->nTj = tile_count(h->N, WT_R, T);
+    pl->nTi = tile_count(h->M, TV_R, T);
+    pl->nTj = tile_count(h->N, TV_R, T);
     if (pl->nTi < 1 || pl->nTj < 1) return set_err(h, BPLTV_E_ARG, "cannot tile %dx%d with T=%d", h->M, h->N, T);
     if (pl->nTj > 65535 || h->O > 65535 || (long long)pl->nTi * pl->nTj * h->O > 0x7FFFFFFFll)
         return set_err(h, BPLTV_E_UNSUPPORTED, "weighted solve: at most 65535 tile rows, 65535 images and 2^31 tiles per launch (grid dimensions)");
@@ -3257,6 +3254,18 @@ int weighted_check_params(bpltv_t* h, const bpltv_params& p, const char* who) {
     return BPLTV_OK;
 }
 
+// One launch of tv_tile_kernel.  The caller has set what its entry point owns -- the planes, alpha (and w), the tape, the
+// tangents; here: what every launch has, and the instance (a tape means TAPE)
+void tv_tile_launch(bpltv_t* h, const WeightedPlan& pl, const double* tab, const LaunchStep& s, bool weighted, bool tangent, TvTileArgs& a) {
+    a.f = h->d_f; a.tab = tab;
+    a.it0 = s.it; a.nit = s.nit;
+    a.M = h->M; a.N = h->N; a.halo = pl.T; a.first = s.first; a.img0 = s.lo;
+    void (*kern)(TvTileArgs) = tangent    ? (weighted ? &tv_tile_kernel<true, false, true> : &tv_tile_kernel<false, false, true>)
+                               : a.tape   ? (weighted ? &tv_tile_kernel<true, true, false> : &tv_tile_kernel<false, true, false>)
+                                          : (weighted ? &tv_tile_kernel<true, false, false> : &tv_tile_kernel<false, false, false>);
+    hipLaunchKernelGGL(kern, dim3(pl.nTi, pl.nTj, s.hi - s.lo), dim3(TV_R * TV_R), tangent ? tv_tangent_lds_bytes() : tv_lds_bytes(), s.st, a);
+}
+
 // maxiter iterations of the weighted recurrence on the dataset images, in the TV state sets, with the handle's d_w / w_wo /
 // w_min and d_alpha.  *result_buf: the state set that holds the result.
 int run_weighted_pdhg(bpltv_t* h, const bpltv_params& p, const WeightedPlan& pl, int* result_buf) {
@@ -3266,7 +3275,7 @@ int run_weighted_pdhg(bpltv_t* h, const bpltv_params& p, const WeightedPlan& pl,
     if (rc) return rc;
     const int M = h->M, N = h->N, O = h->O, T = pl.T;
     const bool amap = (h->last_am == M && h->last_an == N) && !(M == 1 && N == 1);
-    h->st.tile_iters = T; h->st.tiles = pl.nTi * pl.nTj * O; h->st.region_i = WT_R; h->st.region_j = WT_R; h->st.pdhg_variant = 0;
+    h->st.tile_iters = T; h->st.tiles = pl.nTi * pl.nTj * O; h->st.region_i = TV_R; h->st.region_j = TV_R; h->st.pdhg_variant = 0;
     ChainSolve j;
     j.model = MODEL_W; j.nplanes = 3; j.state0 = h->d_state[0];
     j.nimg = O; j.niter = p.maxiter; j.T = T;
@@ -3275,15 +3284,11 @@ int run_weighted_pdhg(bpltv_t* h, const bpltv_params& p, const WeightedPlan& pl,
     j.key = GraphKey{p.maxiter, T, 0, h->last_am, h->last_an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, nullptr, (const void*)d_tab, 0,
                      (const void*)h->d_alpha, 0, h->w_wo};
     j.enqueue = launch_loop(T, [&](const LaunchStep& s) {
-        WeightedArgs a;
-        a.xin = h->d_state[s.cur][0]; a.y1in = h->d_state[s.cur][1]; a.y2in = h->d_state[s.cur][2];
-        a.xout = h->d_state[s.nxt][0]; a.y1out = h->d_state[s.nxt][1]; a.y2out = h->d_state[s.nxt][2];
-        a.f = h->d_f; a.w = h->d_w; a.alpha = h->d_alpha; a.tab = d_tab;
-        a.wstride = h->w_wo > 1 ? h->npx : 0;
-        a.am = h->last_am; a.an = h->last_an;
-        a.it0 = s.it; a.nit = s.nit;
-        a.M = M; a.N = N; a.halo = T; a.first = s.first; a.img0 = s.lo;
-        hipLaunchKernelGGL(weighted_tile_kernel, dim3(pl.nTi, pl.nTj, s.hi - s.lo), dim3(WT_R * WT_R), weighted_lds_bytes(), s.st, a);
+        TvTileArgs a{};
+        for (int c = 0; c < 3; ++c) { a.in[c] = h->d_state[s.cur][c]; a.out[c] = h->d_state[s.nxt][c]; }
+        a.w = h->d_w; a.wstride = h->w_wo > 1 ? h->npx : 0;
+        a.alpha = h->d_alpha; a.am = h->last_am; a.an = h->last_an;
+        tv_tile_launch(h, pl, d_tab, s, true, false, a);
     });
     return run_chains(h, p, j, result_buf);   // (no gap callback: the weighted solve does not take params.check_every)
 }
@@ -3367,11 +3372,9 @@ int weighted_multi(bpltv_t* h, const char* what, bool solve, F call, const char*
 }
 
 // ============================================================================================
-// Reverse mode through the PDHG iterations (unrolled_kernels.hpp, weighted_unrolled_kernels.hpp, sumregs_unrolled_kernels.hpp;
+// Reverse mode through the PDHG iterations (tv_tile_kernels.hpp, sumregs_unrolled_kernels.hpp;
 // DESIGN.md sections 4.6, 4.8 and 4.9)
 // ============================================================================================
-static_assert(UN_R == WT_R, "the unrolled kernels tile like the weighted one");
-
 EnqueueFn launch_loop(int T, LaunchFn launch) {
     return [T, launch](hipStream_t st, int it0, int it1, int cur, int lo, int hi, bool stagger) {
         int step = stagger ? T / 2 : T;
@@ -3393,7 +3396,7 @@ int unrolled_check_params(bpltv_t* h, const bpltv_params& p, const char* who) {
     return BPLTV_OK;
 }
 
-// weighted_plan with the fusion depth capped at `cap` (the reverse kernel holds UN_REV_T iterations of tape in registers)
+// weighted_plan with the fusion depth capped at `cap` (the reverse kernel holds TV_REV_T iterations of tape in registers)
 int unrolled_plan(bpltv_t* h, const bpltv_params& p, int cap, WeightedPlan* pl) {
     bpltv_params q = p;
     q.tile_iters = std::min(p.tile_iters > 0 ? p.tile_iters : 8, cap);
@@ -3433,7 +3436,7 @@ struct TapedFwd {
     const double* alpha;
     int am, an;
     int astride;         // doubles between per-image parameter blocks (0: one block for every image)
-    const double* w;     // weighted model
+    const double* w;     // weighted model; nullptr otherwise
     int wo;
 };
 // the planes a launch reads and writes: a state set, or the step's checkpoint slot
@@ -3485,58 +3488,29 @@ struct TapedModel {
     void (*launch_rev)(const TapedRev&, const LaunchStep&);
 };
 
-void tv_launch_fwd(const TapedFwd& x, const LaunchStep& s) {
+void tv_launch_fwd(const TapedFwd& x, const LaunchStep& s) {   // x.w != nullptr: the weighted model
     bpltv_t* h = x.h;
-    UnrolledArgs a;
-    const double* in[3];
-    double* out[3];
-    taped_planes(s, 3, h->tot, x.S, in, out);
-    a.xin = in[0]; a.y1in = in[1]; a.y2in = in[2];
-    a.xout = out[0]; a.y1out = out[1]; a.y2out = out[2];
-    a.f = h->d_f; a.alpha = x.alpha; a.tab = x.tab; a.tape = x.tape; a.plane = h->tot;
-    a.am = x.am; a.an = x.an; a.istride = x.astride;
-    a.it0 = s.it; a.nit = s.nit; a.tk0 = s.tk0;
-    a.M = h->M; a.N = h->N; a.halo = x.pl.T; a.first = s.first; a.img0 = s.lo;
-    hipLaunchKernelGGL(x.tape ? &unrolled_tile_kernel<true> : &unrolled_tile_kernel<false>, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), s.st, a);
+    TvTileArgs a{};
+    taped_planes(s, 3, h->tot, x.S, a.in, a.out);
+    a.w = x.w; a.wstride = x.wo > 1 ? h->npx : 0;
+    a.alpha = x.alpha; a.am = x.am; a.an = x.an; a.istride = x.astride;
+    a.tape = x.tape; a.plane = h->tot; a.tk0 = s.tk0;
+    tv_tile_launch(h, x.pl, x.tab, s, x.w != nullptr, false, a);
 }
-void tv_launch_rev(const TapedRev& x, const LaunchStep& s) {   // `it` counts reverse steps: step r undoes iteration K - 1 - r
+// `it` counts reverse steps: step r undoes iteration K - 1 - r.  g.w != nullptr: the weighted model (its kernel reads the
+// resident f for gw only)
+void tv_launch_rev(const TapedRev& x, const LaunchStep& s) {
     const GradCtx& g = *x.g;
-    UnrolledRevArgs a;
-    a.gxin = s.first ? x.g0 : x.S[s.cur][0]; a.gy1in = x.S[s.cur][1]; a.gy2in = x.S[s.cur][2];
-    a.gxout = x.S[s.nxt][0]; a.gy1out = x.S[s.nxt][1]; a.gy2out = x.S[s.nxt][2];
-    a.gf = x.gf; a.ga = x.ga; a.tape = x.tape; a.alpha = g.alpha; a.tab = x.tab; a.plane = x.h->tot;
+    TvTileRevArgs a{};
+    for (int c = 0; c < 3; ++c) { a.in[c] = x.S[s.cur][c]; a.out[c] = x.S[s.nxt][c]; }
+    if (s.first) a.in[0] = x.g0;
+    a.gf = x.gf; a.ga = x.ga; a.gw = x.gw; a.tape = x.tape; a.f = x.h->d_f; a.w = g.w; a.alpha = g.alpha; a.tab = x.tab;
+    a.plane = x.h->tot; a.wstride = g.wo > 1 ? x.h->npx : 0;
     a.am = g.am; a.an = g.an; a.istride = g.astride;
     a.khi = x.K - 1 - s.it; a.nit = s.nit; a.tk0 = s.tk0;
     a.M = x.h->M; a.N = x.h->N; a.halo = x.pl.T; a.first = s.first; a.img0 = s.lo;
-    hipLaunchKernelGGL(unrolled_reverse_tile_kernel, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), s.st, a);
-}
-
-void weighted_launch_fwd(const TapedFwd& x, const LaunchStep& s) {
-    bpltv_t* h = x.h;
-    WeightedUnrolledArgs a;
-    const double* in[3];
-    double* out[3];
-    taped_planes(s, 3, h->tot, x.S, in, out);
-    a.xin = in[0]; a.y1in = in[1]; a.y2in = in[2];
-    a.xout = out[0]; a.y1out = out[1]; a.y2out = out[2];
-    a.f = h->d_f; a.w = x.w; a.alpha = x.alpha; a.tab = x.tab; a.tape = x.tape; a.plane = h->tot;
-    a.wstride = x.wo > 1 ? h->npx : 0;
-    a.am = x.am; a.an = x.an;
-    a.it0 = s.it; a.nit = s.nit; a.tk0 = s.tk0;
-    a.M = h->M; a.N = h->N; a.halo = x.pl.T; a.first = s.first; a.img0 = s.lo;
-    hipLaunchKernelGGL(x.tape ? &weighted_unrolled_tile_kernel<true> : &weighted_unrolled_tile_kernel<false>, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), s.st, a);
-}
-void weighted_launch_rev(const TapedRev& x, const LaunchStep& s) {   // the kernel reads the resident f for gw only
-    const GradCtx& g = *x.g;
-    WeightedUnrolledRevArgs a;
-    a.gxin = s.first ? x.g0 : x.S[s.cur][0]; a.gy1in = x.S[s.cur][1]; a.gy2in = x.S[s.cur][2];
-    a.gxout = x.S[s.nxt][0]; a.gy1out = x.S[s.nxt][1]; a.gy2out = x.S[s.nxt][2];
-    a.gf = x.gf; a.ga = x.ga; a.gw = x.gw; a.tape = x.tape; a.f = x.h->d_f; a.w = g.w; a.alpha = g.alpha; a.tab = x.tab;
-    a.plane = x.h->tot; a.wstride = g.wo > 1 ? x.h->npx : 0;
-    a.am = g.am; a.an = g.an;
-    a.khi = x.K - 1 - s.it; a.nit = s.nit; a.tk0 = s.tk0;
-    a.M = x.h->M; a.N = x.h->N; a.halo = x.pl.T; a.first = s.first; a.img0 = s.lo;
-    hipLaunchKernelGGL(weighted_unrolled_reverse_tile_kernel, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(UN_R * UN_R), unrolled_lds_bytes(), s.st, a);
+    hipLaunchKernelGGL(g.w ? &tv_reverse_tile_kernel<true> : &tv_reverse_tile_kernel<false>, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(TV_R * TV_R),
+                       tv_lds_bytes(), s.st, a);
 }
 
 void sr_launch_fwd(const TapedFwd& x, const LaunchStep& s) {   // astride != 0: one parameter block per image
@@ -3570,9 +3544,9 @@ const TapedModel kTapedTV = [] {
     m.denoise = "bpltv_unrolled_denoise"; m.vjp = "unrolled_vjp"; m.tape_kind = ""; m.multi_name = "the unrolled solve";
     m.tape = &bpltv_handle::tape; m.tape_planes = 2;
     m.slices = 1; m.weighted = false; m.nplanes = 3; m.L2 = 8.0;
-    m.plan = unrolled_plan; m.fwd_cap = PDHG_MAX_T; m.rev_cap = UN_REV_T;
+    m.plan = unrolled_plan; m.fwd_cap = PDHG_MAX_T; m.rev_cap = TV_REV_T;
     m.graphs = MODEL_UN; m.fwd_variant = 0; m.rev_variant = 1;
-    m.region = UN_R; m.bytes = 72.0; m.bytes_map = 80.0; m.plain_bytes = 56.0; m.plain_bytes_map = 64.0;
+    m.region = TV_R; m.bytes = 72.0; m.bytes_map = 80.0; m.plain_bytes = 56.0; m.plain_bytes_map = 64.0;
     m.sweep = &bpltv_handle::d_unr; m.sweep_name = "reverse sweep";
     m.adjoint_method = 7; m.tv_stats = true;
     m.launch_fwd = tv_launch_fwd; m.launch_rev = tv_launch_rev;
@@ -3584,11 +3558,10 @@ const TapedModel kTapedWeighted = [] {
     m.denoise = "bpltv_weighted_unrolled_denoise"; m.vjp = "weighted_unrolled_vjp"; m.tape_kind = "weighted ";
     m.multi_name = "the weighted unrolled solve";
     m.tape = &bpltv_handle::wtape; m.tape_planes = 3;
-    m.weighted = true; m.rev_cap = WUN_REV_T;
+    m.weighted = true;
     m.fwd_variant = 6; m.rev_variant = 7;
     m.bytes = 88.0; m.bytes_map = 96.0; m.plain_bytes = 64.0; m.plain_bytes_map = 72.0;
     m.adjoint_method = 9; m.tv_stats = false;
-    m.launch_fwd = weighted_launch_fwd; m.launch_rev = weighted_launch_rev;
     return m;
 }();
 // ... read x, 6 y, f (+ 3 alpha), write x, 6 y and the 6 z
@@ -3724,7 +3697,7 @@ int taped_denoise(bpltv_t* h, const TapedModel& m, const double* w, int wo, cons
     const bool amap = (h->last_am == h->M && h->last_an == h->N) && !(h->M == 1 && h->N == 1);
     h->st.tile_iters = pl.T; h->st.tiles = pl.nTi * pl.nTj * h->O; h->st.region_i = m.region; h->st.region_j = m.region; h->st.pdhg_variant = 0;
     double* const buffer = d_tape_user ? d_tape_user : tape.d;   // the tape, or the checkpoints
-    TapedFwd x{h, pl, d_tab, C ? nullptr : buffer, {}, h->d_alpha, h->last_am, h->last_an, h->alpha_istride, h->d_w, h->w_wo};
+    TapedFwd x{h, pl, d_tab, C ? nullptr : buffer, {}, h->d_alpha, h->last_am, h->last_an, h->alpha_istride, m.weighted ? h->d_w : nullptr, h->w_wo};
     for (int s = 0; s < 2; ++s)
         for (int c = 0; c < np; ++c) x.S[s][c] = sr ? h->d_sr[s][c] : h->d_state[s][c];
     ChainSolve j;
@@ -3986,7 +3959,7 @@ int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const 
 }
 
 // bpltv_unrolled_jvp(_device), bpltv_weighted_unrolled_jvp(_device) and the two Gauss-Newton calls on a single-device handle
-// (unrolled_jvp_kernels.hpp, weighted_unrolled_jvp_kernels.hpp; DESIGN.md sections 4.7 and 4.11): ndir tangent sweeps, one after
+// (tv_tile_kernels.hpp; DESIGN.md sections 4.7 and 4.11): ndir tangent sweeps, one after
 // the other, each the same launch sequence (direction d of a call is bitwise the call with that direction alone).  The tangents
 // d_df / d_dalpha (and the weighted model's d_dw; any may be nullptr: a zero tangent) and d_du live in HBM, direction-major; alpha
 // (and w) on the host or (dev) in HBM.  Every sweep runs in planes of the handle's own -- d_ujv = [2 sets x (x, y1, y2, dx, dy1,
@@ -4023,8 +3996,8 @@ int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool d
     if (!d_ws) {
         if (int arc = alloc_all(h, {{(void**)&d_ws, ((W ? 16 : 14) * tot + (W ? 8 : 0)) * sizeof(double)}}, W ? "weighted tangent sweep" : "tangent sweep"))
             return arc;
-        HIPCHK(h, hipFuncSetAttribute(W ? reinterpret_cast<const void*>(&weighted_unrolled_jvp_tile_kernel) : reinterpret_cast<const void*>(&unrolled_jvp_tile_kernel),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)unrolled_jvp_lds_bytes()));
+        HIPCHK(h, hipFuncSetAttribute(W ? reinterpret_cast<const void*>(&tv_tile_kernel<true, false, true>) : reinterpret_cast<const void*>(&tv_tile_kernel<false, false, true>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)tv_tangent_lds_bytes()));
     }
     const size_t P = (size_t)am * an * (each ? h->O : 1);   // (stage_param checks the shape before it reads anything)
     if (d_dw) {   // the third tangent: a read-back of its own (stage_param's takes two), into the workspace's check words
@@ -4041,7 +4014,7 @@ int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool d
         return rc;
     double* d_tab = nullptr;
     if (int rc = get_table(h, p, &d_tab, 8.0, 0, W ? g.w_min : 1.0)) return rc;
-    const int M = h->M, N = h->N, T = pl.T, K = p.maxiter;
+    const int T = pl.T, K = p.maxiter;
     double* S[2][6];
     for (int s = 0; s < 2; ++s)
         for (int c = 0; c < 6; ++c) S[s][c] = d_ws + (size_t)(6 * s + c) * tot;
@@ -4058,25 +4031,12 @@ int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool d
     j.key = GraphKey{K, T, (W ? 9 : 2) + tangents, am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_ws,
                      (const void*)d_tab, 0, (const void*)g.alpha, g.astride, W ? W->wo : 0};
     j.enqueue = launch_loop(T, [&](const LaunchStep& s) {
-        if (W) {
-            WeightedUnrolledJvpArgs a;
-            for (int c = 0; c < 6; ++c) { a.in[c] = S[s.cur][c]; a.out[c] = S[s.nxt][c]; }
-            a.f = h->d_f; a.w = d_wc; a.df = d_df ? d_dfc : nullptr; a.dw = d_dw ? d_dwc : nullptr;
-            a.alpha = g.alpha; a.dalpha = d_dalpha ? d_dac : nullptr; a.tab = d_tab;
-            a.wstride = W->wo > 1 ? h->npx : 0;
-            a.am = am; a.an = an;
-            a.it0 = s.it; a.nit = s.nit;
-            a.M = M; a.N = N; a.halo = T; a.first = s.first; a.img0 = s.lo;
-            hipLaunchKernelGGL(weighted_unrolled_jvp_tile_kernel, dim3(pl.nTi, pl.nTj, s.hi - s.lo), dim3(UN_R * UN_R), unrolled_jvp_lds_bytes(), s.st, a);
-            return;
-        }
-        UnrolledJvpArgs a;
+        TvTileArgs a{};
         for (int c = 0; c < 6; ++c) { a.in[c] = S[s.cur][c]; a.out[c] = S[s.nxt][c]; }
-        a.f = h->d_f; a.df = d_df ? d_dfc : nullptr; a.alpha = g.alpha; a.dalpha = d_dalpha ? d_dac : nullptr; a.tab = d_tab;
-        a.am = am; a.an = an; a.istride = g.astride;
-        a.it0 = s.it; a.nit = s.nit;
-        a.M = M; a.N = N; a.halo = T; a.first = s.first; a.img0 = s.lo;
-        hipLaunchKernelGGL(unrolled_jvp_tile_kernel, dim3(pl.nTi, pl.nTj, s.hi - s.lo), dim3(UN_R * UN_R), unrolled_jvp_lds_bytes(), s.st, a);
+        a.w = d_wc; a.wstride = (W && W->wo > 1) ? h->npx : 0;
+        a.alpha = g.alpha; a.am = am; a.an = an; a.istride = g.astride;
+        a.df = d_df ? d_dfc : nullptr; a.dw = d_dw ? d_dwc : nullptr; a.dalpha = d_dalpha ? d_dac : nullptr;
+        tv_tile_launch(h, pl, d_tab, s, W != nullptr, true, a);
     });
     int rc = hipEventRecord(h->ev[2], h->stream) == hipSuccess ? (int)BPLTV_OK : set_err(h, BPLTV_E_HIP, "%s: hipEventRecord failed", who);
     int buf = 0;
