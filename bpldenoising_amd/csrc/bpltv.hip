@@ -58,7 +58,11 @@ struct Variant {
     const void* func32_1d = nullptr;
 };
 // the kernel symbol of a launch of variant V: the tile kernels know the form of their grid when they are compiled
-inline const void* pdhg_func(const Variant& V, int dtype, int grid3d) {
+// fast: PdhgArgs::fast of the launch (pdhg_fill_invariants) -- the FAST instantiation of variant 1, 3-D grid
+inline const void* pdhg_func(const Variant& V, int dtype, int grid3d, int fast) {
+    if (fast)
+        return dtype == 32 ? reinterpret_cast<const void*>(&pdhg_tile_kernel<float, 1, 1, 32, 32, true, true>)
+                           : reinterpret_cast<const void*>(&pdhg_tile_kernel<double, 1, 1, 32, 32, true, true>);
     if (!grid3d && V.func_1d) return dtype == 32 ? V.func32_1d : V.func_1d;
     return dtype == 32 ? V.func32 : V.func;
 }
@@ -73,6 +77,12 @@ inline int pdhg_grid3d_ok(int nTj, int nimg, int tiles_per_block) { return (tile
 template <typename T, int PI, int PJ, int TI, int TJ>
 void launch_variant(const PdhgArgs& a, int grid, hipStream_t s) {
     constexpr size_t lds = pdhg_lds_bytes(PI * TI, PJ * TJ, sizeof(T));
+    if constexpr (PI == 1 && PJ == 1 && TI == 32 && TJ == 32) {
+        if (a.fast) {
+            hipLaunchKernelGGL((pdhg_tile_kernel<T, PI, PJ, TI, TJ, true, true>), pdhg_grid(a, grid), dim3(TI * TJ), lds, s, a);
+            return;
+        }
+    }
     if (a.grid3d) hipLaunchKernelGGL((pdhg_tile_kernel<T, PI, PJ, TI, TJ, true>), pdhg_grid(a, grid), dim3(TI * TJ), lds, s, a);
     else hipLaunchKernelGGL((pdhg_tile_kernel<T, PI, PJ, TI, TJ, false>), pdhg_grid(a, grid), dim3(TI * TJ), lds, s, a);
 }
@@ -137,7 +147,9 @@ void launch_stream_variant(const PdhgArgs& a, int grid, hipStream_t s) {
       "stream_64x" #SEG "rows_" #NL "levels_d" #D, &launch_stream_variant<float, NL, D, FD, PF, WPE>, \
       reinterpret_cast<const void*>(&pdhg_stream_kernel<float, NL, D, FD, PF, WPE>), pdhg_stream_lds<NL, D, FD>(sizeof(float)), 1, 2, NL }
 const Variant kVariants[] = {
-    VAR(1, 1, 32, 32),  // 1: 32x32 region, 1 px/thread   (small images, shallow blocking)
+    VAR(1, 1, 32, 32),  // 1: 32x32 region, 1 px/thread   (small images, shallow blocking).  Besides the general instantiations
+                        //    of both grid forms, this variant alone has pdhg_tile_kernel<double / float, 1, 1, 32, 32, true, true>:
+                        //    FAST, the 3-D grid, for solves without sweep and rho with a scalar or full-map alpha (pdhg_func)
     VAR(2, 2, 32, 32),  // 2: 64x64 region, 4 px/thread
     VAR(1, 1, 16, 16),  // 3: 16x16 region
     VAR(2, 2, 16, 16),  // 4: 32x32 region, 256 threads
@@ -836,6 +848,26 @@ int make_plan(bpltv_t* h, const bpltv_params& p, Plan* pl, int nimg) {
     }
 }
 
+// The words of a launch's arguments that are the same for every workgroup, worked out here instead of by every wave of
+// every workgroup, and whether the launch runs the FAST instantiation of pdhg_tile_kernel.  Call with the geometry, the
+// parameter's shape, O / Odata, rho, img0 and grid3d set.  FAST indexes with 32 bits: every plane its launches address --
+// the state and data planes and a full-map parameter, O * M * N elements at most -- must stay below 2^31 bytes (counted
+// with 8-byte elements on float handles too); a larger handle takes the general instantiation, 64-bit indices.
+inline void pdhg_fill_invariants(PdhgArgs& a, const Variant& V, int dtype) {
+    a.MN = (unsigned long long)a.M * (unsigned long long)a.N;
+    a.base0 = a.MN * (unsigned long long)a.img0;
+    a.Si = V.RI - 2 * a.halo;
+    a.Sj = V.RJ - 2 * a.halo;
+    a.amode = (a.am == 1 && a.an == 1) ? 0 : ((a.am == a.M && a.an == a.N) ? 2 : 1);
+    a.sweep = (a.O != a.Odata) ? 1 : 0;
+    const bool rho0 = dtype == 32 ? ((float)a.rho == 0.0f) : (a.rho == 0.0);   // the test the kernel makes
+    const bool narrow = a.MN * (unsigned long long)std::max(a.O, a.Odata) * 8ull < (1ull << 31);
+    a.fast = (&V == &kVariants[PLAN_V_TILE32] && a.grid3d && !a.sweep && rho0 && a.amode != 1 && narrow) ? 1 : 0;
+#ifdef BPLTV_EXPERIMENTS
+    if (a.dbg & 262144) a.fast = 0;   // tools/prologue_ab.py: the general instantiation on the headline solve
+#endif
+}
+
 // Build one hipGraph per chain (image group): maxiter iterations as a linear launch sequence.
 // The chains are replayed concurrently, each on its own stream (= its own hardware queue).
 int build_graphs(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, const Plan& pl, const double* d_tab, int niter,
@@ -892,7 +924,10 @@ int build_graphs(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, const Pla
 #endif
             const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
             a.first = (it == 0 && !from_state) ? 1 : 0;
-            a.xin = pdhg_state(h, x, cur, 0); a.y1in = pdhg_state(h, x, cur, 1); a.y2in = pdhg_state(h, x, cur, 2);
+            // (a first launch takes x = f, y = 0 and ignores what it reads; the FAST instantiation issues the loads all the
+            //  same, from the set the launch does not write)
+            const int rd = a.first ? 1 - nxt : cur;
+            a.xin = pdhg_state(h, x, rd, 0); a.y1in = pdhg_state(h, x, rd, 1); a.y2in = pdhg_state(h, x, rd, 2);
             a.xout = pdhg_state(h, x, nxt, 0); a.y1out = pdhg_state(h, x, nxt, 1); a.y2out = pdhg_state(h, x, nxt, 2);
             a.it0 = it;
             a.nit = std::min(step, niter - it);
@@ -902,7 +937,8 @@ int build_graphs(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, const Pla
             a.ntiles = tilesPerImg * (hi - lo);
             a.xcd = (p.reserved[2] & 2) ? 1 : 0;
             a.grid3d = a.xcd ? 0 : pdhg_grid3d_ok(pl.nTj, hi - lo, V.tiles_per_block);
-            kp.func = const_cast<void*>(pdhg_func(V, h->dtype, a.grid3d));
+            pdhg_fill_invariants(a, V, h->dtype);
+            kp.func = const_cast<void*>(pdhg_func(V, h->dtype, a.grid3d, a.fast));
             kp.gridDim = a.grid3d ? pdhg_grid(a, a.ntiles) : dim3((tilesPerImg * (hi - lo) + V.tiles_per_block - 1) / V.tiles_per_block);
             kp.blockDim = dim3(V.threads);
             kp.sharedMemBytes = (unsigned)(h->dtype == 32 ? V.lds32 : V.lds);
@@ -958,11 +994,13 @@ int enqueue_pdhg(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, const Pla
     a.dbg = p.reserved[3];
     a.dbg_row[0] = p.tau0; a.dbg_row[1] = p.sigma0; a.dbg_row[2] = 1.0; a.dbg_row[3] = 1.0 / (1.0 + p.tau0); a.dbg_row[4] = 2.0;
 #endif
+    pdhg_fill_invariants(a, V, h->dtype);
     int step = stagger ? pl.T / 2 : pl.T;
     for (int it = it0; it < it1; it += step, step = pl.T) {
         const int nxt = (it == 0) ? (stagger ? 1 : 0) : 1 - cur;
         a.first = (it == 0 && !from_state) ? 1 : 0;
-        a.xin = pdhg_state(h, x, cur, 0); a.y1in = pdhg_state(h, x, cur, 1); a.y2in = pdhg_state(h, x, cur, 2);
+        const int rd = a.first ? 1 - nxt : cur;   // as build_graphs
+        a.xin = pdhg_state(h, x, rd, 0); a.y1in = pdhg_state(h, x, rd, 1); a.y2in = pdhg_state(h, x, rd, 2);
         a.xout = pdhg_state(h, x, nxt, 0); a.y1out = pdhg_state(h, x, nxt, 1); a.y2out = pdhg_state(h, x, nxt, 2);
         a.it0 = it;
         a.nit = std::min(step, it1 - it);

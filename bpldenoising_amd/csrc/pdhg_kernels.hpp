@@ -20,6 +20,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <type_traits>   // std::conditional, std::true_type
+
 #include "tiling.hpp"   // tile_span, tile_count (host + device; also compiled by g++ under the sanitizers)
 
 namespace bpltv {
@@ -37,27 +39,44 @@ constexpr int TAB_STRIDE = 8;  // doubles per iteration row: tau, sigma, omega, 
 constexpr int PDHG_MAX_T = 32;
 
 struct PdhgArgs {
+    // Bytes 0x00-0x3f, one 64-byte line: what the addresses of pdhg_tile_kernel's state loads are made of.  Kernel arguments
+    // are cold behind a kernel boundary and every wave fetches them for itself, so the order of the fields is the order of
+    // their first use ("One argument round trip").
     const double* xin;
     const double* y1in;
     const double* y2in;
-    double* xout;
-    double* y1out;
-    double* y2out;
     const double* f;
     const double* alpha;  // device, am*an doubles (column major)
     const double* tab;    // device, [maxiter][TAB_STRIDE]
-    double rho;
-    int am, an;
-    int it0, nit;
-    int M, N, O;
-    int nTi, nTj, halo;
-    int first;  // 1: start from x = f, y = 0 (inputs xin/y1in/y2in ignored)
+    int M, N;
+    int halo;
     int img0;   // first image handled by this launch (grid = tiles per image * images of the chain)
+    // 0x40-0x7f: the launch-invariant words the host works out once per launch (pdhg_fill_invariants), and the launch itself
+    unsigned long long MN = 0;      // M * N
+    unsigned long long base0 = 0;   // img0 * M * N: where the launch's first image starts in the state planes, and -- no sweep --
+                                    // its data image in f
+    int Si = 0, Sj = 0;   // core stride of interior tiles, R - 2 * halo, along i and j (pdhg_tile_kernel: its own region)
+    int amode = 0;        // 0: scalar alpha, 2: a full M x N map, 1: a patch map (am x an, upsampled piecewise constant)
+    int sweep = 0;        // 1: O != Odata, a solve image reads f[img % Odata] and parameter block img / Odata
+    int fast = 0;         // 1: the launch runs the FAST instantiation of pdhg_tile_kernel (no sweep, rho = 0, amode 0 or 2,
+                          // every plane of the handle below 2^31 bytes: 32-bit indices)
+    int first;  // 1: start from x = f, y = 0 (inputs xin/y1in/y2in ignored)
+    int it0, nit;
+    int istride; // doubles between the parameter blocks of consecutive images when O == Odata: 0 = one block for every image
+                 // (bpltv_denoise, and a one-block sweep), am*an = image img reads block img (bpltv_denoise_each)
+    int am, an;
+    // 0x80-: the stores, and what only some kernels or some launches read
+    double* xout;
+    double* y1out;
+    double* y2out;
+    unsigned* phase = nullptr;   // chain 0 of a two-chain solve: a word the first workgroup of every launch rewrites (first iteration of
+                // the launch + 1, PDHG_PHASE_STAMP) -- pdhg_phase_gate_kernel in the other chain waits for it to change
+    double rho;
+    int O;
+    int nTi, nTj;
     int Odata;  // images in the dataset; image `img` of the solve uses f[img % Odata] and the
                 // parameter block alpha + (img / Odata) * astride (parameter sweeps: K*Odata problems)
     int astride;
-    int istride; // doubles between the parameter blocks of consecutive images when O == Odata: 0 = one block for every image
-                 // (bpltv_denoise, and a one-block sweep), am*an = image img reads block img (bpltv_denoise_each)
     int ntiles; // tiles of this launch (pdhg_wave_kernel: several tiles per workgroup, the last one may be short)
     int grid3d; // 1: the grid is (nTi, nTj, images): tile and image come from blockIdx.x / .y / .z and the kernel's prologue
                 // needs no integer division (4 of them, ~100 scalar instructions per wave, with the 1-D grid)
@@ -65,8 +84,6 @@ struct PdhgArgs {
     int xcd;    // 1 (1-D grid only): workgroups are dealt round-robin over the 8 XCDs, each with its own L2; remap the
                 // linear workgroup index so that every XCD works on a contiguous run of tiles (neighbouring tiles re-read
                 // each other's halos: from the same L2 instead of from the memory side)
-    unsigned* phase = nullptr;   // chain 0 of a two-chain solve: a word the first workgroup of every launch rewrites (first iteration of
-                // the launch + 1, PDHG_PHASE_STAMP) -- pdhg_phase_gate_kernel in the other chain waits for it to change
 #ifdef BPLTV_EXPERIMENTS
     int dbg;    // timing experiments of tools/ builds only (results are wrong): 1 skip state loads, 2 skip
                 // stores, 4 no iterations, 16 nt stores, 32 plain stores, 64 nt loads, 128 no barriers (rows kernel); these three keep
@@ -74,6 +91,8 @@ struct PdhgArgs {
                 // 8192 the tile kernels fetch their step rows by scalar loads (first row behind the first barrier, the next row
                 // inside the loop: the form before the rows moved to LDS).  With 8192, wrong results again: 16384 the loop keeps
                 // the first row and fetches nothing, 32768 the first row is dbg_row instead of a fetch (tools/step_rows_ab.py).
+                // Results kept: 262144 the host launches the general instantiation where FAST would run, 524288 the last
+                // iteration of a launch is not peeled (tools/prologue_ab.py).
                 // The product library is compiled without these fields and without the branches they feed.
     double dbg_row[5];
 #endif
@@ -180,6 +199,28 @@ __host__ __device__ constexpr int rsqrt_nr_steps(float) { return 3; }
 __device__ __forceinline__ double pd_fma(double a, double b, double c) { return __builtin_fma(a, b, c); }
 __device__ __forceinline__ float pd_fma(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 
+// tile_span (tiling.hpp) for pdhg_tile_kernel's prologue: the same numbers, by selects instead of branches, with the core
+// stride S = R - 2T handed in (an argument word).  An image inside one region has one tile, a = 0: oo = L - R <= 0.
+__device__ __forceinline__ void pdhg_tile_span(int a, int L, int R, int T, int S, int& o, int& c0, int& c1) {
+    const int cs = (a == 0) ? 0 : (R - T) + (a - 1) * S;
+    int oo = (a == 0) ? 0 : cs - T;
+    const bool last = oo + R >= L;
+    oo = last ? L - R : oo;
+    c1 = last ? L : oo + R - T;
+    o = max(oo, 0);
+    c0 = cs;
+}
+// Element i of a plane.  A 64-bit index is an element index; a 32-bit one (the FAST instantiation) becomes a 32-bit byte
+// offset beside the plane's base in scalar registers -- the host checked that every plane stays below 2^31 bytes.
+template <typename T> __device__ __forceinline__ const T* pdhg_elem(const T* p, size_t i) { return p + i; }
+template <typename T> __device__ __forceinline__ T* pdhg_elem(T* p, size_t i) { return p + i; }
+template <typename T> __device__ __forceinline__ const T* pdhg_elem(const T* p, unsigned i) {
+    return reinterpret_cast<const T*>(reinterpret_cast<const char*>(p) + i * (unsigned)sizeof(T));
+}
+template <typename T> __device__ __forceinline__ T* pdhg_elem(T* p, unsigned i) {
+    return reinterpret_cast<T*>(reinterpret_cast<char*>(p) + i * (unsigned)sizeof(T));
+}
+
 // T = double: the reference's arithmetic.  T = float: the opt-in single-precision mode of bpltv_create(dtype = 32) --
 // the same operation sequence in f32 ("spec v2f": bplo_pdhg_f32 of the oracle), with state, f, alpha and the step
 // table held as float (the pointers of PdhgArgs then address float arrays): half the LDS and HBM bytes per pixel.
@@ -188,8 +229,31 @@ __device__ __forceinline__ float pd_fma(float a, float b, float c) { return __bu
 // -- the state pointers among them -- only in the block where the two paths meet, a second scalar round trip in front
 // of the state loads.  This way they are fetched right behind the first wait, the tile arithmetic between them and
 // their first use.
-template <typename T, int PI, int PJ, int TI, int TJ, bool G3>
+//
+// Every argument word the kernel reads is fetched in its entry block and waited for once: the empty asm below holds no
+// instruction, only scalar-register constraints on the fields, so all of them are live at the kernel's first instruction
+// and the compiler cannot sink their loads behind the tile arithmetic.  What is the same for every workgroup of a launch
+// (M * N, the first image's offset, R - 2T, the form of alpha, sweep or not) arrives as argument words the host worked out.
+// FAST: the common solve -- no sweep, rho = 0, a scalar or a full-map alpha, every plane of the handle below 2^31 bytes, so
+// indices are 32-bit -- without the branches, divisions and 64-bit multiplies of the general prologue and without the rho
+// test in the loop.  The host launches it when PdhgArgs::fast says so (pdhg_fast_ok in bpltv.hip); the general
+// instantiation runs everything else, 64-bit indices throughout.  Same arithmetic per pixel: bit-identical results.
+template <typename T, int PI, int PJ, int TI, int TJ, bool G3, bool FAST = false>
 __global__ __launch_bounds__(TI* TJ) void pdhg_tile_kernel(PdhgArgs A) {
+    // (one statement per form: an asm volatile is not moved across another, so a second one would wait a second time)
+#define PDHG_ARGS_COMMON_                                                                                                        \
+    "s"(A.xin), "s"(A.y1in), "s"(A.y2in), "s"(A.f), "s"(A.alpha), "s"(A.tab), "s"(A.M), "s"(A.N), "s"(A.halo), "s"(A.img0),       \
+        "s"(A.MN), "s"(A.base0), "s"(A.Si), "s"(A.Sj), "s"(A.amode), "s"(A.first), "s"(A.it0), "s"(A.nit), "s"(A.istride),       \
+        "s"(A.xout), "s"(A.y1out), "s"(A.y2out), "s"(A.phase)
+#define PDHG_ARGS_GENERAL_ "s"(A.sweep), "s"(A.am), "s"(A.an), "s"(A.rho), "s"(A.Odata), "s"(A.astride)
+    if (FAST) asm volatile("" ::PDHG_ARGS_COMMON_);
+    else if (G3) asm volatile("" ::PDHG_ARGS_COMMON_, PDHG_ARGS_GENERAL_);
+    else asm volatile("" ::PDHG_ARGS_COMMON_, PDHG_ARGS_GENERAL_, "s"(A.nTi), "s"(A.nTj), "s"(A.xcd), "s"((int)gridDim.x));   // (the XCD remap reads the grid size)
+#undef PDHG_ARGS_COMMON_
+#undef PDHG_ARGS_GENERAL_
+#ifdef BPLTV_EXPERIMENTS
+    asm volatile("" ::"s"(A.dbg));
+#endif
     constexpr int RI = PI * TI, RJ = PJ * TJ;
     // LDS planes with guard cells so that the neighbour reads need no select:
     //   sy1: rows of RI+1, a leading zero column  -> y1(i-1,j) at li = 0 reads 0
@@ -214,57 +278,69 @@ __global__ __launch_bounds__(TI* TJ) void pdhg_tile_kernel(PdhgArgs A) {
     T* __restrict__ Ay2out = reinterpret_cast<T*>(A.y2out);
     const T* __restrict__ Af = reinterpret_cast<const T*>(A.f);
 
+    using IX = typename std::conditional<FAST, unsigned, size_t>::type;   // element indices: 32-bit where the host checked
     const int tid = threadIdx.x;
     const int ti = tid % TI, tj = tid / TI;
     PDHG_DECODE_TILE(G3, A, imgl, ta, tb)
-    const int img = A.img0 + imgl;
     int oi, ci0, ci1, oj, cj0, cj1;
-    tile_span(ta, A.M, RI, A.halo, oi, ci0, ci1);
-    tile_span(tb, A.N, RJ, A.halo, oj, cj0, cj1);
+    pdhg_tile_span(ta, A.M, RI, A.halo, A.Si, oi, ci0, ci1);
+    pdhg_tile_span(tb, A.N, RJ, A.halo, A.Sj, oj, cj0, cj1);
     const int M = A.M, N = A.N;
-    int fimg;
-    const size_t aoff = pdhg_data_image(A, img, fimg);
-    const size_t base = (size_t)img * M * N;                 // state planes: one slot per solve image
-    const size_t fbase = (size_t)fimg * M * N;               // dataset planes
-    const T* __restrict__ alpha = reinterpret_cast<const T*>(A.alpha) + aoff;
-    const int amode = (A.am == 1 && A.an == 1) ? 0 : ((A.am == M && A.an == N) ? 2 : 1);
+    const IX MN = (IX)A.MN;
+    const IX base = (IX)A.base0 + (IX)imgl * MN;             // state planes: one slot per solve image
+    IX fbase = base;                                         // dataset planes: no sweep, the solve images are the dataset's
+    IX aoff = (IX)(A.img0 + imgl) * (IX)A.istride;           // parameter block (istride = 0: one block for every image)
+    if (!FAST && A.sweep) {                                  // image img reads f[img % Odata] and parameter block img / Odata
+        const int img = A.img0 + imgl, blk = img / A.Odata;
+        fbase = (IX)(img - blk * A.Odata) * MN;
+        aoff = (IX)blk * (IX)A.astride;
+    }
+    const T* __restrict__ alpha = reinterpret_cast<const T*>(A.alpha);
+    const int amode = A.amode;
     const bool first = (A.first != 0) || (BPLTV_DBG(A) & 1);
 
     // ---- prologue: every global load is issued before the first use (one memory round trip).
     // Out-of-image pixels read a clamped in-image address and are zeroed afterwards.
     T x[PJ][PI], y1[PJ][PI], y2[PJ][PI], f[PJ][PI], al[PJ][PI];
-    size_t gidx[PJ][PI], fidx[PJ][PI], aidx[PJ][PI];
+    IX gidx[PJ][PI], fidx[PJ][PI], aidx[PJ][PI];
 #pragma unroll
     for (int pj = 0; pj < PJ; ++pj)
 #pragma unroll
         for (int pi = 0; pi < PI; ++pi) {
             const int li = ti + TI * pi, lj = PJ * tj + pj;
             const int gi = min(oi + li, M - 1), gj = min(oj + lj, N - 1);
-            gidx[pj][pi] = base + gi + (size_t)M * gj;
-            fidx[pj][pi] = fbase + gi + (size_t)M * gj;
-            size_t ai = 0;  // scalar alpha
-            if (amode == 2) {
-                ai = gi + (size_t)M * gj;
+            const IX pix = (IX)gi + (IX)M * (IX)gj;
+            gidx[pj][pi] = base + pix;
+            fidx[pj][pi] = fbase + pix;
+            IX ai = 0;  // scalar alpha
+            if (FAST) {
+                ai = amode ? pix : 0;   // a select: scalar or full map
+            } else if (amode == 2) {
+                ai = pix;
             } else if (amode == 1) {  // PatchOp: piecewise-constant upsampling
                 const unsigned pa = ((unsigned)gi * (unsigned)A.am) / (unsigned)M;
                 const unsigned pb = ((unsigned)gj * (unsigned)A.an) / (unsigned)N;
-                ai = pa + (size_t)A.am * pb;
+                ai = pa + (IX)A.am * pb;
             }
-            aidx[pj][pi] = ai;
+            aidx[pj][pi] = aoff + ai;
         }
-    if (!first) {
+    // all loads of a thread go out back to back: state, f, alpha, and its word of the launch's step rows (below).  FAST
+    // loads the state in a first launch too (set 0 of the context: allocated, its content unused -- the select below
+    // takes f and 0), so that no branch stands between the argument wait and the loads, and the addresses are a 32-bit
+    // offset beside a scalar base in all of them.
+    if (FAST || !first) {
 #pragma unroll
         for (int pj = 0; pj < PJ; ++pj)
 #pragma unroll
             for (int pi = 0; pi < PI; ++pi) {
                 if (BPLTV_DBG(A) & 64) {  // experiment: non-temporal loads
-                    x[pj][pi] = __builtin_nontemporal_load(&Axin[gidx[pj][pi]]);
-                    y1[pj][pi] = __builtin_nontemporal_load(&Ay1in[gidx[pj][pi]]);
-                    y2[pj][pi] = __builtin_nontemporal_load(&Ay2in[gidx[pj][pi]]);
+                    x[pj][pi] = __builtin_nontemporal_load(pdhg_elem(Axin, gidx[pj][pi]));
+                    y1[pj][pi] = __builtin_nontemporal_load(pdhg_elem(Ay1in, gidx[pj][pi]));
+                    y2[pj][pi] = __builtin_nontemporal_load(pdhg_elem(Ay2in, gidx[pj][pi]));
                 } else {
-                    x[pj][pi] = Axin[gidx[pj][pi]];
-                    y1[pj][pi] = Ay1in[gidx[pj][pi]];
-                    y2[pj][pi] = Ay2in[gidx[pj][pi]];
+                    x[pj][pi] = *pdhg_elem(Axin, gidx[pj][pi]);
+                    y1[pj][pi] = *pdhg_elem(Ay1in, gidx[pj][pi]);
+                    y2[pj][pi] = *pdhg_elem(Ay2in, gidx[pj][pi]);
                 }
             }
     }
@@ -272,8 +348,8 @@ __global__ __launch_bounds__(TI* TJ) void pdhg_tile_kernel(PdhgArgs A) {
     for (int pj = 0; pj < PJ; ++pj)
 #pragma unroll
         for (int pi = 0; pi < PI; ++pi) {
-            f[pj][pi] = Af[fidx[pj][pi]];
-            al[pj][pi] = alpha[aidx[pj][pi]];
+            f[pj][pi] = *pdhg_elem(Af, fidx[pj][pi]);
+            al[pj][pi] = *pdhg_elem(alpha, aidx[pj][pi]);
         }
     // The launch's step rows travel with the state loads: one word per thread, written to LDS in front of the first
     // barrier -- no round trip and no barrier of their own.  (Fetched by scalar loads where they are used, every wave
@@ -311,7 +387,7 @@ __global__ __launch_bounds__(TI* TJ) void pdhg_tile_kernel(PdhgArgs A) {
     if (row_word) srow[tid] = row_w;
     __syncthreads();
 
-    const T rho = (T)A.rho;
+    const T rho = FAST ? T(0) : (T)A.rho;   // FAST: no rho test in the loop
     const int nit = (BPLTV_DBG(A) & 4) ? 0 : A.nit;
     // Neumann border without a select in the loop: at the last image row/column (and outside the
     // image) the "neighbour" read is redirected to the pixel's own xbar cell, so the forward
@@ -359,7 +435,40 @@ __global__ __launch_bounds__(TI* TJ) void pdhg_tile_kernel(PdhgArgs A) {
         }
     }
 #endif
-    for (int it = 0; it < loop_nit; ++it) {
+    // The stores of the core: x is final behind the last primal step and goes out there, y1 / y2 behind the last dual step.
+    auto store_core = [&](const bool with_x, const bool with_y) __attribute__((always_inline)) {
+#pragma unroll
+        for (int pj = 0; pj < PJ; ++pj)
+#pragma unroll
+            for (int pi = 0; pi < PI; ++pi) {
+                const int li = ti + TI * pi, lj = PJ * tj + pj;
+                const int gi = oi + li, gj = oj + lj;
+                if (gi >= ci0 && gi < ci1 && gj >= cj0 && gj < cj1 && !(BPLTV_DBG(A) & 2)) {
+                    const IX idx = base + (IX)gi + (IX)M * (IX)gj;
+                    if (BPLTV_DBG(A) & 16) {  // experiment: non-temporal stores
+                        if (with_x) __builtin_nontemporal_store(x[pj][pi], pdhg_elem(Axout, idx));
+                        if (with_y) __builtin_nontemporal_store(y1[pj][pi], pdhg_elem(Ay1out, idx));
+                        if (with_y) __builtin_nontemporal_store(y2[pj][pi], pdhg_elem(Ay2out, idx));
+                    } else if (!(BPLTV_DBG(A) & 32)) {
+                        // write-through (sc1) stores: the state of this launch is read next by workgroups
+                        // on other XCDs, so it has to reach memory anyway; writing through while the
+                        // kernel still runs leaves no dirty L2 lines for the end-of-kernel release
+                        // (-0.9 us per launch on MI355X, profiles/README.md)
+                        if (with_x) __hip_atomic_store(pdhg_elem(Axout, idx), x[pj][pi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (with_y) __hip_atomic_store(pdhg_elem(Ay1out, idx), y1[pj][pi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        if (with_y) __hip_atomic_store(pdhg_elem(Ay2out, idx), y2[pj][pi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    } else {
+                        if (with_x) *pdhg_elem(Axout, idx) = x[pj][pi];
+                        if (with_y) *pdhg_elem(Ay1out, idx) = y1[pj][pi];
+                        if (with_y) *pdhg_elem(Ay2out, idx) = y2[pj][pi];
+                    }
+                }
+            }
+    };
+    // One fused iteration.  LAST: the last one of the launch -- nobody reads the y planes or the next step row again, so it
+    // writes neither y1 / y2 to LDS nor passes barrier #2, and x goes out behind its primal step, under the dual step.
+    auto iteration = [&](const int it, auto last_tag) __attribute__((always_inline)) {
+        constexpr bool LAST = decltype(last_tag)::value;
         T ntau = tau, nsigma = sigma, nomega = omega, ninv1ptau = inv1ptau, nopw = opw;
 #ifdef BPLTV_EXPERIMENTS
         if (!lds_rows && !(BPLTV_DBG(A) & 16384)) {
@@ -397,9 +506,10 @@ __global__ __launch_bounds__(TI* TJ) void pdhg_tile_kernel(PdhgArgs A) {
                 sxb[l] = b;
             }
         }
+        if (LAST) store_core(true, false);
         __syncthreads();
         if (act) {
-        if (lds_rows) {
+        if (lds_rows && !LAST) {
             const T* nrow = srow + TAB_STRIDE * ((it + 1 < nit) ? it + 1 : it);
             ntau = nrow[0]; nsigma = nrow[1]; nomega = nrow[2]; ninv1ptau = nrow[3]; nopw = nrow[4];
         }
@@ -449,6 +559,7 @@ __global__ __launch_bounds__(TI* TJ) void pdhg_tile_kernel(PdhgArgs A) {
                     y2[pj][pi] = outp ? y2[pj][pi] * v : y2[pj][pi];
                 }
         }
+        if (!LAST) {
 #pragma unroll
         for (int pj = 0; pj < PJ; ++pj)
 #pragma unroll
@@ -458,41 +569,30 @@ __global__ __launch_bounds__(TI* TJ) void pdhg_tile_kernel(PdhgArgs A) {
                 sy2[(lj + 1) * RI + li] = y2[pj][pi];
             }
         }
-        tau = ntau; sigma = nsigma; omega = nomega; inv1ptau = ninv1ptau; opw = nopw;
-        __syncthreads();
-    }
-    for (int it = loop_nit; it < nit; ++it) {   // a spent halo wave: the two barriers of an iteration, nothing else
-        __syncthreads();
-        __syncthreads();
-    }
-
-#pragma unroll
-    for (int pj = 0; pj < PJ; ++pj)
-#pragma unroll
-        for (int pi = 0; pi < PI; ++pi) {
-            const int li = ti + TI * pi, lj = PJ * tj + pj;
-            const int gi = oi + li, gj = oj + lj;
-            if (gi >= ci0 && gi < ci1 && gj >= cj0 && gj < cj1 && !(BPLTV_DBG(A) & 2)) {
-                const size_t idx = base + gi + (size_t)M * gj;
-                if (BPLTV_DBG(A) & 16) {  // experiment: non-temporal stores
-                    __builtin_nontemporal_store(x[pj][pi], &Axout[idx]);
-                    __builtin_nontemporal_store(y1[pj][pi], &Ay1out[idx]);
-                    __builtin_nontemporal_store(y2[pj][pi], &Ay2out[idx]);
-                } else if (!(BPLTV_DBG(A) & 32)) {
-                    // write-through (sc1) stores: the state of this launch is read next by workgroups
-                    // on other XCDs, so it has to reach memory anyway; writing through while the
-                    // kernel still runs leaves no dirty L2 lines for the end-of-kernel release
-                    // (-0.9 us per launch on MI355X, profiles/README.md)
-                    __hip_atomic_store(&Axout[idx], x[pj][pi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&Ay1out[idx], y1[pj][pi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    __hip_atomic_store(&Ay2out[idx], y2[pj][pi], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                } else {
-                    Axout[idx] = x[pj][pi];
-                    Ay1out[idx] = y1[pj][pi];
-                    Ay2out[idx] = y2[pj][pi];
-                }
-            }
         }
+        if (!LAST) {
+            tau = ntau; sigma = nsigma; omega = nomega; inv1ptau = ninv1ptau; opw = nopw;
+            __syncthreads();
+        }
+    };
+    // One pixel per thread: every wave passes 2 * nit - 1 barriers, two per iteration and one in the last.  A wave that
+    // computes the last iteration runs it peeled behind the loop; a spent halo wave keeps the barriers company (and has no
+    // core pixel to store).  Several pixels per thread: the loop as it was, 2 * nit barriers, the stores behind it.
+    const bool PEEL = PI * PJ == 1 && !(BPLTV_DBG(A) & 524288);   // (experiments: 524288 keeps the tail as it was)
+    const bool peel = PEEL && nit > 0 && loop_nit == nit;   // wave-uniform
+    const int full_nit = peel ? nit - 1 : loop_nit;
+    for (int it = 0; it < full_nit; ++it) iteration(it, std::false_type());
+    if (__builtin_expect(peel, 1)) {
+        iteration(nit - 1, std::true_type());
+        store_core(false, true);
+    } else {
+        for (int it = loop_nit; it < nit - (PEEL ? 1 : 0); ++it) {   // a spent halo wave: the two barriers of an iteration, nothing else
+            __syncthreads();
+            __syncthreads();
+        }
+        if (PEEL && nit > 0) __syncthreads();
+        store_core(true, true);
+    }
 }
 
 // ------------------------------------------------------------------------------------------
