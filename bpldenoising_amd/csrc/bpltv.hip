@@ -1462,23 +1462,36 @@ int nd_alloc(bpltv_t* h, NdSolver& nd, const NdStencil& st, const char* what, in
     return BPLTV_OK;
 }
 
+// Workspace of a whole-batch band solver in HBM (HbBandSolver, HbLuSolver) at bandwidth bw, refused while it would leave
+// less than 2 GB free.  refusal: the message of that, a format of two %.1f (GB needed, GB free); `what` opens the message of
+// a failed allocation.
+template <class Solver>
+int hbm_band_alloc(bpltv_t* h, Solver& s, int bw, const char* what, const char* refusal) {
+    size_t freeb = 0, totalb = 0;
+    (void)hipMemGetInfo(&freeb, &totalb);
+    const size_t need = s.bytes_needed(bw, (int)h->npx, h->O);
+    if (need + (2ull << 30) > freeb) return set_err(h, BPLTV_E_NOMEM, refusal, need / 1e9, freeb / 1e9);
+    if constexpr (std::is_same<Solver, HbBandSolver>::value) {
+        s.opt_sync = h->opt.hb_sync; s.opt_single_stream = h->opt.hb_single_stream; s.opt_rw = h->opt.hb_rw;
+    }
+    const int rc = s.alloc(bw, (int)h->npx, h->O, h->stream);
+    if (rc) return set_err(h, rc, "%s: %s", what, s.err.c_str());
+    return BPLTV_OK;
+}
+
 int band_alloc(bpltv_t* h) {
     if (h->band_ready) return BPLTV_OK;
     const size_t tot = h->tot;
     const size_t W = (size_t)h->M + 1;
     h->adj_hbm = adj_factor_lds(h->M, 4) > 160 * 1024;
-    if (h->adj_hbm) {
-        size_t freeb = 0, totalb = 0;
-        (void)hipMemGetInfo(&freeb, &totalb);
-        const size_t need = h->hb.bytes_needed(h->M, (int)h->npx, h->O);
-        if (need + (2ull << 30) > freeb)
-            return set_err(h, BPLTV_E_NOMEM, "adjoint gradient: the band and its inverted diagonal blocks of %d images of %dx%d need %.1f GB of HBM (%.1f GB free); the nested-dissection factorisation (the default for this shape) needs a fraction of that and runs in image groups",
-                           h->O, h->M, h->N, need / 1e9, freeb / 1e9);
-        h->hb.opt_sync = h->opt.hb_sync; h->hb.opt_single_stream = h->opt.hb_single_stream; h->hb.opt_rw = h->opt.hb_rw;
-        const int rc = h->hb.alloc(h->M, (int)h->npx, h->O, h->stream);
-        if (rc) return set_err(h, rc, "adjoint gradient (HBM band): %s", h->hb.err.c_str());
-    }
     int rc = BPLTV_OK;
+    if (h->adj_hbm) {
+        char refusal[400];
+        snprintf(refusal, sizeof(refusal), "adjoint gradient: the band and its inverted diagonal blocks of %d images of %dx%d need %%.1f GB of HBM (%%.1f GB free); the nested-dissection factorisation (the default for this shape) needs a fraction of that and runs in image groups",
+                 h->O, h->M, h->N);
+        rc = hbm_band_alloc(h, h->hb, h->M, "adjoint gradient (HBM band)", refusal);
+        if (rc) return rc;
+    }
     if (!h->adj_hbm) {
         const size_t nblk = (h->npx + SB - 1) / SB;
         rc = alloc_all(h, {{(void**)&h->d_L, tot * W * sizeof(double)},
@@ -1662,47 +1675,61 @@ GradCtx gradient_ctx(const bpltv_t* h, const double* d_ubar, double* d_out) {
     return g;
 }
 
-// Adjoint gradient of the images d_u on the device; parameter, right-hand side and outputs from `g`.
-// The images are processed in groups of at most Oc (adj_choose): coefficients, assembly, factorisation, solve and
-// refinement of a group use the factor workspace of the previous one; the per-pixel gradients of all images are
-// summed at the end, per image and in image order, so the result does not depend on the grouping (bitwise).
+// ---- the adjoint driver shared by the models ---------------------------------------------------------
+// One adjoint solve = per image group the coefficient planes, the assembly and the factorisation, then per right-hand side
+// a solve, refinement sweeps against the matrix-free operator and the residual statistics; behind the groups the reduction
+// of the per-pixel gradients over the images and the input gradient.  A model describes its linear system in an AdjSystem;
+// run_adjoint turns that into launches.
+struct AdjGroup {                  // one image group, handed to every per-group hook
+    int c0 = 0, nimg = 0;          // its first image, its images
+    size_t o0 = 0, ctot = 0;       // c0 * npx, nimg * npx
+    unsigned gpx = 0;              // blocks of 256 threads over its pixels
+    const double* ga = nullptr;    // its first image's parameter block
+    double kact = 0.0;             // the active-set weight of this attempt
+    double *dp = nullptr, *dr = nullptr;   // its solution and residual (d_p, d_r)
+    int* dfail = nullptr;
+    // written by AdjSystem::factor, read by the copy of the right-hand side and by adj_resnorm_kernel: the right-hand side,
+    // the main diagonal of the assembled matrix, and (nullable) the node scaling and the kappa plane
+    const double *rhs = nullptr, *diag = nullptr, *s = nullptr, *kap = nullptr;
+};
+struct AdjPlan {   // what AdjSystem::prepare decides once the workspace exists
+    int Oc;                  // images per group
+    int method, hb_sync;     // bpltv_stats_t::adjoint_method, ::hb_sync
+    int nref;                // refinement sweeps unless params.refine sets them
+    const char* pivot_msg;   // a failed factorisation: %d position, %d image
+    double* gpix;            // per-pixel parameter gradients: AdjSystem::slices planes of M*N*O doubles
+};
+struct AdjSystem {
+    int slices = 1;          // parameter slices (1 TV, 3 sum of regularisers)
+    double kact = 0.0;       // active-set weight, before params.kappa_cap and the retry's scale
+    double gate_skip = 1.0;  // the residual gate leaves out the rows whose diagonal carries gate_skip * weight (reg: none)
+    const char* alpha_msg = nullptr;   // reg with a patch / map parameter that holds a zero: %g its smallest entry
+    const char* gate_msg = nullptr;    // %.3e residual, %.1e gate (and, if it names them, %.3e weight, %d sweeps)
+    std::function<int(AdjPlan*)> prepare;   // workspace and choice of the factorisation
+    // coefficient planes, assembly and factorisation of a group (forward mode on an LU path: of A^T)
+    std::function<int(AdjGroup&)> factor;
+    // forward mode: the right-hand side of one direction from its tangents (either may be nullptr), and its du from G.dp
+    std::function<void(const AdjGroup&, const double* df, const double* dalpha)> tangent_rhs;
+    std::function<int(const AdjGroup&, double* du)> store_du;
+    std::function<void(const AdjGroup&, double* out)> residual;              // out <- rhs - A G.dp
+    std::function<int(const AdjGroup&, double* vec, double* acc)> solve;     // vec <- A^-1 vec, acc += the solution
+    std::function<void(const AdjGroup&)> gradpix;                            // the group's planes of AdjPlan::gpix from G.dp
+    std::function<void()> grad_in;   // behind the groups: the input gradient(s), d_p covering the whole batch
+};
+
+// One attempt at the weight sys.kact * kappa_scale.  The images are processed in groups of at most Oc (AdjSystem::prepare):
+// a group uses the factor workspace of the previous one; the per-pixel gradients of all images are summed at the end, per
+// image and in image order, so the result does not depend on the grouping (bitwise).
 // Reference: the per-image loop of /root/reference/src/TVLearningFunctionVec.jl:76-81,168-173 -- sequential, no limit.
-int run_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, const bpltv_params& p,
-                      double kappa_scale) {
-    int rc = adj_alloc(h);
+int run_adjoint_once(bpltv_t* h, const GradCtx& g, int reg, const bpltv_params& p, double kappa_scale, const AdjSystem& sys) {
+    AdjPlan pl{h->O, 0, 0, 0, nullptr, nullptr};
+    int rc = sys.prepare(&pl);
     if (rc) return rc;
-    AdjMethod method;
-    int Oc = h->O;
-    rc = adj_choose(h, p, &method, &Oc);
-    if (rc) return rc;
-    const int M = h->M, N = h->N, O = h->O, am = g.am, an = g.an;
-    const size_t tot = h->tot, npx = h->npx;
-    const int patch = !(am == 1 && an == 1);
-    const double eps = 2.220446049250313e-16;
-    double kcap = p.kappa_cap > 0.0 ? p.kappa_cap : 1e14;
-    double kact = 1.0 / (patch ? std::sqrt(eps) : eps);  // TVLearningFunctionVec.jl:128 / :245
-    if (kact > kcap) kact = kcap;
-    kact *= kappa_scale;
-    // Refinement sweeps: every sweep gains ~2 digits with the 1e14 active-set weight of the scalar gradient and
-    // 4-5 digits with the 6.7e7 / 1e8 weights of the patch and regularised gradients, where the second sweep
-    // already reaches rounding level (round-1 sweep of the refinement count).
-    // The HBM band and nested-dissection paths solve with true triangular factors (only 128 x 128 diagonal blocks
-    // are inverted): one sweep already reaches the level the block-cyclic-reduction path needs two for
-    // (1024^2: pixel map 3.6e-9 / patch 6e-11 / regularised 1e-16 from the converged value after ONE sweep, scalar
-    // 1.4e-9 after two).  The regularised systems (gamma = 1e8 instead of 1/eps) need none: 4e-10 / 1e-9 / 5e-11 from
-    // the converged value without a sweep, scaled residual <= 4e-12.
-    const bool direct = (method == ADJ_BAND_HBM || method == ADJ_ND);
-    // Scalar parameter (the 1e14 weight) on a direct factorisation: FOUR sweeps.  Against the literal system on images with a
-    // planted active set (tests/test_gpu_tv_active_set.py: blocks, strips across the separators, a constant image; bound 1e-8
-    // max|p| + 1e-6 |ref|), worst |difference| of grad_f / grad_alpha and worst fraction of the bound over the cases:
-    //     nested dissection   2 sweeps 1.8e-7 / 2.1e-5 (2.2 of the bound: refused)   3: 2.4e-9 / 2.7e-7 (0.022)   4: 4.3e-11 / 3.5e-9 (< 0.001)
-    //     band in HBM         2 sweeps 3.7e-9 / 3.3e-7 (0.047)                       3: 1.5e-11 / 1.3e-9           4: 5.1e-12 / 1.2e-11
-    // Three would do for w = 1 (a tenth of the bound is the margin kept), but with a per-pixel weight three leave 5.5e-9 of a bound
-    // of 1.7e-8 (0.32; 1 x 12 x 140 with a 2 x 125 flat block, tests/test_gpu_weighted_shapes.py) and four 5.8e-11: one count for
-    // both, so that bpltv_weighted_vjp with w = 1 stays bpltv_vjp bit for bit without asking what w holds.  Cost: adjoint_ms of
-    // the 10 x 128^2 scalar evaluate 0.94 -> 1.28 ms (1.11 with three; median of 20).
-    int nref_default = direct ? (reg ? 0 : (patch ? 1 : 4)) : ((patch || reg) ? 2 : 3);
-    const int nref = p.refine < 0 ? nref_default : p.refine;
+    const int M = h->M, N = h->N, O = h->O, am = g.am, an = g.an, S = sys.slices;
+    const size_t tot = h->tot, npx = h->npx, P = (size_t)am * an;
+    const double kcap = p.kappa_cap > 0.0 ? p.kappa_cap : 1e14;
+    const double kact = std::min(sys.kact, kcap) * kappa_scale;
+    const int nref = p.refine < 0 ? pl.nref : p.refine;
     // forward mode: every direction keeps its own residual statistics (the gate takes the worst)
     const bool tangent = g.ndir > 0;
     const int ndir = tangent ? g.ndir : 1;
@@ -1712,116 +1739,74 @@ int run_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, 
         if (rc) return rc;
         resn_fin = h->d_jres;
     }
-    const size_t dastride = (size_t)am * an * (g.each ? O : 1);   // doubles between two directions of g.dalpha
+    const size_t dastride = S * P * (g.each ? O : 1);   // doubles between two directions of g.dalpha
     HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
     HIPCHK(h, hipMemsetAsync(h->d_fail, 0, sizeof(int) * O, h->stream));
     int chunks = 0;
-    for (int c0 = 0; c0 < O; c0 += Oc, ++chunks) {
-        const int nimg = std::min(Oc, O - c0);
-        const size_t o0 = (size_t)c0 * npx, ctot = (size_t)nimg * npx;
-        AdjCoef C;   // coefficient planes of the group: the whole-batch planes at the group's first image
-        C.t1 = h->d_coef + o0; C.t2 = h->d_coef + tot + o0; C.c = h->d_coef + 2 * tot + o0; C.kap = h->d_coef + 3 * tot + o0;
-        C.h1 = h->d_coef + 4 * tot + o0; C.h2 = h->d_coef + 5 * tot + o0; C.s = h->d_coef + 6 * tot + o0; C.rhs = h->d_coef + 7 * tot + o0;
-        double* band4 = h->d_band4;   // the four diagonals of the group's matrices, planes of nimg * npx doubles
-        double *dp = h->d_p + o0, *dr = h->d_r + o0, *dg = h->d_gpix + o0;
-        int* dfail = h->d_fail + c0;
-        const int gpx = (int)((ctot + 255) / 256);
-        const double* ga = g.alpha + (size_t)c0 * g.astride;   // the group's first image's parameter block
-        if (tangent)   // the coefficient planes alone: adj_tangent_rhs_kernel writes each direction's right-hand side below
-            hipLaunchKernelGGL(adj_setup_cot_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, d_u + o0, ga, am, an, g.astride,
-                               M, N, nimg, patch, reg, kact, C);
-        else if (g.w)
-            hipLaunchKernelGGL(weighted_adj_setup_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0,
-                               g.w + (g.wo > 1 ? o0 : 0), g.wo > 1 ? npx : (size_t)0, ga, am, an, M, N, nimg, kact, C);
-        else if (g.cot)
-            hipLaunchKernelGGL(adj_setup_cot_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0, ga, am, an, g.astride,
-                               M, N, nimg, patch, reg, kact, C);
-        else
-            hipLaunchKernelGGL(adj_setup_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0, ga, am, an, g.astride, M,
-                               N, nimg, patch, reg, kact, C);
-        hipLaunchKernelGGL(adj_assemble_kernel, dim3(gpx), dim3(256), 0, h->stream, C, M, N, nimg, band4);
-        // factorisation
-        const BcrArrays bcr = BcrArrays::carve(h->d_bcr, M, N, nimg, h->bcr_MP);
-        if (method == ADJ_BCR) {
-            bcr_factor_band4_launch(h->stream, bcr, band4, M, N, nimg, h->bcr_MP, dfail);
-        } else if (method == ADJ_ND) {
-            const int r2 = h->nd.factor(band4, ctot, nimg, dfail);
-            if (r2) return set_err(h, r2, "adjoint gradient (nested dissection): %s", h->nd.err.c_str());
-        } else if (method == ADJ_BAND_HBM) {
-            rc = factor_band_hbm(h);
-            if (rc) return rc;
-        } else {
-            factor_band_lds(h);
-        }
+    for (int c0 = 0; c0 < O; c0 += pl.Oc, ++chunks) {
+        AdjGroup G;
+        G.c0 = c0; G.nimg = std::min(pl.Oc, O - c0);
+        G.o0 = (size_t)c0 * npx; G.ctot = (size_t)G.nimg * npx;
+        G.gpx = (unsigned)((G.ctot + 255) / 256);
+        G.ga = g.alpha + (size_t)c0 * g.astride;
+        G.kact = kact;
+        G.dp = h->d_p + G.o0; G.dr = h->d_r + G.o0; G.dfail = h->d_fail + c0;
+        rc = sys.factor(G);
+        if (rc) return rc;
         HIPCHK(h, hipGetLastError());
-        auto solve = [&](double* vec, double* accv) -> int {
-            if (method == ADJ_BCR) bcr_solve_launch(h->stream, bcr, M, N, nimg, h->bcr_MP, vec, accv, band4);
-            else if (method == ADJ_ND) {
-                const int r2 = h->nd.solve(vec, accv, nimg);
-                if (r2) return set_err(h, r2, "adjoint gradient (nested dissection, substitution): %s", h->nd.err.c_str());
-            }
-            else if (method == ADJ_BAND_HBM) solve_band_hbm(h, vec, accv);
-            else solve_band_lds(h, vec, accv);
-            return BPLTV_OK;
-        };
         for (int d = 0; d < ndir; ++d) {   // one pass, or the tangent directions against this group's factorisation
             if (tangent)
-                hipLaunchKernelGGL(adj_tangent_rhs_kernel, dim3(gpx), dim3(256), 0, h->stream, C, g.df ? g.df + (size_t)d * tot + o0 : nullptr,
-                                   g.dalpha ? g.dalpha + (size_t)d * dastride + (size_t)c0 * g.astride : nullptr, am, an, g.astride, M, N,
-                                   nimg, patch, reg);
+                sys.tangent_rhs(G, g.df ? g.df + (size_t)d * tot + G.o0 : nullptr,
+                                g.dalpha ? g.dalpha + (size_t)d * dastride + (size_t)c0 * g.astride : nullptr);
             // solve + iterative refinement against the matrix-free operator
-            HIPCHK(h, hipMemcpyAsync(dp, C.rhs, ctot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            rc = solve(dp, nullptr);
+            HIPCHK(h, hipMemcpyAsync(G.dp, G.rhs, G.ctot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+            rc = sys.solve(G, G.dp, nullptr);
             if (rc) return rc;
             for (int it = 0; it < nref; ++it) {
-                hipLaunchKernelGGL(adj_residual_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, dr);
-                rc = solve(dr, dp);
+                sys.residual(G, G.dr);
+                rc = sys.solve(G, G.dr, G.dp);
                 if (rc) return rc;
             }
-            hipLaunchKernelGGL(adj_residual_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, dr);
+            sys.residual(G, G.dr);
             double* resn_part = h->d_resn + 4 * (size_t)O + 4 * (size_t)c0 * RESN_BLK;
-            hipLaunchKernelGGL(adj_resnorm_kernel, dim3(RESN_BLK, nimg), dim3(256), 0, h->stream, dr, C.rhs, band4, (int)npx, resn_part,
-                               (const double*)C.s, reg ? HUGE_VAL : kact, g.w ? (const double*)C.kap : (const double*)nullptr, M);
-            hipLaunchKernelGGL(adj_resnorm_final_kernel, dim3((4 * nimg + 63) / 64), dim3(64), 0, h->stream, resn_part, nimg,
+            hipLaunchKernelGGL(adj_resnorm_kernel, dim3(RESN_BLK, G.nimg), dim3(256), 0, h->stream, G.dr, G.rhs, G.diag, (int)npx, resn_part,
+                               G.s, reg ? (double)HUGE_VAL : sys.gate_skip * kact, G.kap, M);
+            hipLaunchKernelGGL(adj_resnorm_final_kernel, dim3((4 * G.nimg + 63) / 64), dim3(64), 0, h->stream, resn_part, G.nimg,
                                resn_fin + 4 * ((size_t)d * O + c0));
-            if (tangent)
-                hipLaunchKernelGGL(adj_du_kernel, dim3(gpx), dim3(256), 0, h->stream, C.s, dp, ctot, g.du + (size_t)d * tot + o0);
+            if (tangent) {
+                rc = sys.store_du(G, g.du + (size_t)d * tot + G.o0);
+                if (rc) return rc;
+            }
         }
-        // gradient per pixel
-        if (g.d_out)
-            hipLaunchKernelGGL(adj_gradpix_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, patch, reg, dg);
+        if (g.d_out) sys.gradpix(G);
         HIPCHK(h, hipGetLastError());
     }
-    // ... then per parameter, over all images (a vector-Jacobian product may not want the parameter gradient)
+    // ... then per parameter, over all images (a vector-Jacobian product may not want the parameter gradient): slice k of
+    // the result from plane k of the per-pixel gradients
     const bool amap = am == M && an == N && !(M == 1 && N == 1);
-    if (g.d_out && g.each) {   // per image, image-major: the pixel maps as they are, or each image's patch sums
-        if (amap)
-            HIPCHK(h, hipMemcpyAsync(g.d_out, h->d_gpix, tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        else
-            hipLaunchKernelGGL(patch_sum_kernel, dim3(am * an, O), dim3(256), 0, h->stream, h->d_gpix, M, N, O, am, an, 1, am * an,
+    if (g.d_out && g.each) {   // per image, image-major (block k holds image k's slices): nothing is summed over images
+        if (amap && S == 1)
+            HIPCHK(h, hipMemcpyAsync(g.d_out, pl.gpix, tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        else if (amap)
+            hipLaunchKernelGGL(sr_gpix_each_kernel, dim3((unsigned)((3 * tot + 255) / 256)), dim3(256), 0, h->stream, pl.gpix, npx, O,
                                g.d_out);
-    } else if (g.d_out && amap) {  // pixelwise parameter map: plain sum over images
-        hipLaunchKernelGGL(map_sum_kernel, dim3((unsigned)((h->npx + 255) / 256)), dim3(256), 0, h->stream, h->d_gpix, h->npx, O,
-                           g.d_out);
+        else
+            for (int k = 0; k < S; ++k)
+                hipLaunchKernelGGL(patch_sum_kernel, dim3((unsigned)P, O), dim3(256), 0, h->stream, pl.gpix + k * tot, M, N, O, am, an,
+                                   1, (int)(S * P), g.d_out + (size_t)k * P);
+    } else if (g.d_out && amap) {   // pixelwise parameter maps: plain sums over the images
+        for (int k = 0; k < S; ++k)
+            hipLaunchKernelGGL(map_sum_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, pl.gpix + k * tot, npx, O,
+                               g.d_out + (size_t)k * npx);
     } else if (g.d_out) {
-        rc = ensure(h, &h->d_red, &h->red_cap, (size_t)am * an * O);
+        rc = ensure(h, &h->d_red, &h->red_cap, S * P * O);
         if (rc) return rc;
-        hipLaunchKernelGGL(patch_sum_kernel, dim3(am * an, O), dim3(256), 0, h->stream, h->d_gpix, M, N, O, am, an, O, 1,
-                           h->d_red);
-        hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, O, am * an, 1.0, g.d_out,
-                           (double*)nullptr);
+        for (int k = 0; k < S; ++k)
+            hipLaunchKernelGGL(patch_sum_kernel, dim3((unsigned)P, O), dim3(256), 0, h->stream, pl.gpix + k * tot, M, N, O, am, an, O,
+                               1, h->d_red + (size_t)k * P * O);
+        hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, O, (int)(S * P), 1.0, g.d_out, (double*)nullptr);
     }
-    // input gradient of a vector-Jacobian product: d_p and the s plane cover the whole batch after the group loop
-    if (g.w) {   // weighted model: w o p, and -(u - f) o p per pixel (d_r is free behind the group loop)
-        double* gw = g.d_grad_w ? (g.wo > 1 ? g.d_grad_w : h->d_r) : nullptr;
-        if (g.d_grad_f || gw)
-            hipLaunchKernelGGL(weighted_adj_out_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->d_coef + 6 * tot,
-                               h->d_p, g.w, g.wo > 1 ? npx : (size_t)0, d_u, g.f, npx, tot, g.d_grad_f, gw);
-        if (gw && g.wo == 1)
-            hipLaunchKernelGGL(map_sum_kernel, dim3((unsigned)((npx + 255) / 256)), dim3(256), 0, h->stream, h->d_r, npx, O, g.d_grad_w);
-    } else if (g.d_grad_f)
-        hipLaunchKernelGGL(adj_gradf_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->d_coef + 6 * tot, h->d_p,
-                           tot, reg, g.d_grad_f);
+    sys.grad_in();
     HIPCHK(h, hipGetLastError());
     HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
     std::vector<int> fail(O);
@@ -1833,15 +1818,13 @@ int run_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, 
     HIPCHK(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
     h->st.adjoint_ms = ms;
     h->st.reg_gradient_used = reg;
-    h->st.adjoint_method = (int)method;
+    h->st.adjoint_method = pl.method;
     h->st.adjoint_chunks = chunks;
-    h->st.hb_sync = (method == ADJ_BAND_HBM) ? (h->hb.value_sync ? 2 : 1) : 0;
+    h->st.hb_sync = pl.hb_sync;
     h->st.kappa_used = reg ? 0.0 : kact;
     double worst = 0.0, worst_raw = 0.0;
     for (int k = 0; k < O; ++k)
-        if (fail[k] != 0)
-            return set_err(h, BPLTV_E_NUMERIC, "adjoint Cholesky: non-positive pivot at %s %d of image %d",
-                           method == ADJ_BCR ? "block" : (method == ADJ_ND ? "front" : "column"), fail[k] - 1, k);
+        if (fail[k] != 0) return set_err(h, BPLTV_E_NUMERIC, pl.pivot_msg, fail[k] - 1, k);
     for (size_t k = 0; k < (size_t)O * ndir; ++k) {   // (direction, image) pairs: the worst of them
         const double* q = &resn[4 * k];
         const double raw = std::sqrt(q[0]) / (q[1] > 0 ? std::sqrt(q[1]) : 1.0);
@@ -1851,24 +1834,21 @@ int run_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, 
     }
     h->st.adjoint_residual = worst;
     h->st.adjoint_residual_raw = worst_raw;
-    if (!(worst <= BPLTV_RESIDUAL_GATE))
-        return set_err(h, BPLTV_E_NUMERIC, "adjoint solve: scaled residual %.3e above the gate %.1e (weight %.3e, %d refinement sweeps)",
-                       worst, (double)BPLTV_RESIDUAL_GATE, kact, nref);
+    if (!(worst <= BPLTV_RESIDUAL_GATE)) return set_err(h, BPLTV_E_NUMERIC, sys.gate_msg, worst, (double)BPLTV_RESIDUAL_GATE, kact, nref);
     return BPLTV_OK;
 }
 
 // The reduced system is SPD, but its active-set weight (up to 1e14) sits 14 digits above the O(1)
 // terms; should rounding ever produce a non-positive pivot, retry with a 100x smaller weight
 // (1e12 still reproduces the hard-constraint limit to ~1e-5).
-int run_gradient(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, const bpltv_params& p) {
+int run_adjoint(bpltv_t* h, const GradCtx& g, int reg, const bpltv_params& p, const AdjSystem& sys) {
     const bool patch = !(g.am == 1 && g.an == 1);
-    if (reg && patch && !(g.alpha_min > 0.0))
-        return set_err(h, BPLTV_E_ARG, "gradient_reg with a patch / pixel-map parameter symmetrises with sqrt(alpha): every entry must be > 0 (min = %g)", g.alpha_min);
+    if (reg && patch && !(g.alpha_min > 0.0)) return set_err(h, BPLTV_E_ARG, sys.alpha_msg, g.alpha_min);
     double scale = 1.0;
     int rc = BPLTV_OK;
     h->st.adjoint_attempts = 0;
     for (int attempt = 0; attempt < 3; ++attempt, scale *= 1e-2) {
-        rc = run_gradient_once(h, d_u, g, reg, p, scale);
+        rc = run_adjoint_once(h, g, reg, p, scale, sys);
         h->st.adjoint_attempts = attempt + 1;
         if (rc != BPLTV_E_NUMERIC) break;
         if (reg) break;   // gradient_reg has no active-set weight to reduce
@@ -1877,6 +1857,282 @@ int run_gradient(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, const
     // not an error, so the message of the failed attempt does not stay behind
     if (rc == BPLTV_OK) h->err.clear();
     return rc;
+}
+
+// The TV and weighted TV systems: AdjCoef, the four diagonals of adj_assemble_kernel and the factorisations of adj_choose.
+int run_gradient(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, const bpltv_params& p) {
+    const int M = h->M, N = h->N, O = h->O, am = g.am, an = g.an;
+    const size_t tot = h->tot, npx = h->npx;
+    const int patch = !(am == 1 && an == 1);
+    const dim3 blk(256);
+    AdjMethod method = ADJ_ND;
+    AdjCoef C{};      // coefficient planes of the group: the whole-batch planes at the group's first image
+    BcrArrays bcr{};
+    AdjSystem sys;
+    sys.kact = 1.0 / (patch ? std::sqrt(2.220446049250313e-16) : 2.220446049250313e-16);   // TVLearningFunctionVec.jl:128 / :245
+    sys.alpha_msg = "gradient_reg with a patch / pixel-map parameter symmetrises with sqrt(alpha): every entry must be > 0 (min = %g)";
+    sys.gate_msg = "adjoint solve: scaled residual %.3e above the gate %.1e (weight %.3e, %d refinement sweeps)";
+    sys.prepare = [&](AdjPlan* pl) -> int {
+        int rc = adj_alloc(h);
+        if (rc) return rc;
+        rc = adj_choose(h, p, &method, &pl->Oc);
+        if (rc) return rc;
+        // Refinement sweeps: every sweep gains ~2 digits with the 1e14 active-set weight of the scalar gradient and
+        // 4-5 digits with the 6.7e7 / 1e8 weights of the patch and regularised gradients, where the second sweep
+        // already reaches rounding level (round-1 sweep of the refinement count).
+        // The HBM band and nested-dissection paths solve with true triangular factors (only 128 x 128 diagonal blocks
+        // are inverted): one sweep already reaches the level the block-cyclic-reduction path needs two for
+        // (1024^2: pixel map 3.6e-9 / patch 6e-11 / regularised 1e-16 from the converged value after ONE sweep, scalar
+        // 1.4e-9 after two).  The regularised systems (gamma = 1e8 instead of 1/eps) need none: 4e-10 / 1e-9 / 5e-11 from
+        // the converged value without a sweep, scaled residual <= 4e-12.
+        const bool direct = (method == ADJ_BAND_HBM || method == ADJ_ND);
+        // Scalar parameter (the 1e14 weight) on a direct factorisation: FOUR sweeps.  Against the literal system on images with a
+        // planted active set (tests/test_gpu_tv_active_set.py: blocks, strips across the separators, a constant image; bound 1e-8
+        // max|p| + 1e-6 |ref|), worst |difference| of grad_f / grad_alpha and worst fraction of the bound over the cases:
+        //     nested dissection   2 sweeps 1.8e-7 / 2.1e-5 (2.2 of the bound: refused)   3: 2.4e-9 / 2.7e-7 (0.022)   4: 4.3e-11 / 3.5e-9 (< 0.001)
+        //     band in HBM         2 sweeps 3.7e-9 / 3.3e-7 (0.047)                       3: 1.5e-11 / 1.3e-9           4: 5.1e-12 / 1.2e-11
+        // Three would do for w = 1 (a tenth of the bound is the margin kept), but with a per-pixel weight three leave 5.5e-9 of a bound
+        // of 1.7e-8 (0.32; 1 x 12 x 140 with a 2 x 125 flat block, tests/test_gpu_weighted_shapes.py) and four 5.8e-11: one count for
+        // both, so that bpltv_weighted_vjp with w = 1 stays bpltv_vjp bit for bit without asking what w holds.  Cost: adjoint_ms of
+        // the 10 x 128^2 scalar evaluate 0.94 -> 1.28 ms (1.11 with three; median of 20).
+        pl->nref = direct ? (reg ? 0 : (patch ? 1 : 4)) : ((patch || reg) ? 2 : 3);
+        pl->method = (int)method;
+        pl->hb_sync = (method == ADJ_BAND_HBM) ? (h->hb.value_sync ? 2 : 1) : 0;
+        pl->pivot_msg = method == ADJ_BCR ? "adjoint Cholesky: non-positive pivot at block %d of image %d"
+                                          : (method == ADJ_ND ? "adjoint Cholesky: non-positive pivot at front %d of image %d"
+                                                              : "adjoint Cholesky: non-positive pivot at column %d of image %d");
+        pl->gpix = h->d_gpix;
+        return BPLTV_OK;
+    };
+    sys.factor = [&](AdjGroup& G) -> int {
+        const size_t o0 = G.o0;
+        const int nimg = G.nimg;
+        C.t1 = h->d_coef + o0; C.t2 = h->d_coef + tot + o0; C.c = h->d_coef + 2 * tot + o0; C.kap = h->d_coef + 3 * tot + o0;
+        C.h1 = h->d_coef + 4 * tot + o0; C.h2 = h->d_coef + 5 * tot + o0; C.s = h->d_coef + 6 * tot + o0; C.rhs = h->d_coef + 7 * tot + o0;
+        double* band4 = h->d_band4;   // the four diagonals of the group's matrices, planes of nimg * npx doubles
+        G.rhs = C.rhs; G.diag = band4; G.s = C.s; G.kap = g.w ? C.kap : nullptr;
+        const bool tangent = g.ndir > 0;
+        if (g.w && !tangent)
+            hipLaunchKernelGGL(weighted_adj_setup_kernel, dim3(G.gpx), blk, 0, h->stream, d_u + o0, g.src + o0,
+                               g.w + (g.wo > 1 ? o0 : 0), g.wo > 1 ? npx : (size_t)0, G.ga, am, an, M, N, nimg, G.kact, C);
+        else if (tangent || g.cot)   // forward mode: the coefficient planes alone (adj_tangent_rhs_kernel writes each direction's right-hand side)
+            hipLaunchKernelGGL(adj_setup_cot_kernel, dim3(G.gpx), blk, 0, h->stream, d_u + o0, (tangent ? d_u : g.src) + o0, G.ga, am,
+                               an, g.astride, M, N, nimg, patch, reg, G.kact, C);
+        else
+            hipLaunchKernelGGL(adj_setup_kernel, dim3(G.gpx), blk, 0, h->stream, d_u + o0, g.src + o0, G.ga, am, an, g.astride, M,
+                               N, nimg, patch, reg, G.kact, C);
+        hipLaunchKernelGGL(adj_assemble_kernel, dim3(G.gpx), blk, 0, h->stream, C, M, N, nimg, band4);
+        if (method == ADJ_BCR) {
+            bcr = BcrArrays::carve(h->d_bcr, M, N, nimg, h->bcr_MP);
+            bcr_factor_band4_launch(h->stream, bcr, band4, M, N, nimg, h->bcr_MP, G.dfail);
+        } else if (method == ADJ_ND) {
+            const int r2 = h->nd.factor(band4, G.ctot, nimg, G.dfail);
+            if (r2) return set_err(h, r2, "adjoint gradient (nested dissection): %s", h->nd.err.c_str());
+        } else if (method == ADJ_BAND_HBM) {
+            return factor_band_hbm(h);
+        } else {
+            factor_band_lds(h);
+        }
+        return BPLTV_OK;
+    };
+    sys.solve = [&](const AdjGroup& G, double* vec, double* accv) -> int {
+        if (method == ADJ_BCR) bcr_solve_launch(h->stream, bcr, M, N, G.nimg, h->bcr_MP, vec, accv, h->d_band4);
+        else if (method == ADJ_ND) {
+            const int r2 = h->nd.solve(vec, accv, G.nimg);
+            if (r2) return set_err(h, r2, "adjoint gradient (nested dissection, substitution): %s", h->nd.err.c_str());
+        }
+        else if (method == ADJ_BAND_HBM) solve_band_hbm(h, vec, accv);
+        else solve_band_lds(h, vec, accv);
+        return BPLTV_OK;
+    };
+    sys.tangent_rhs = [&](const AdjGroup& G, const double* df, const double* dalpha) {
+        hipLaunchKernelGGL(adj_tangent_rhs_kernel, dim3(G.gpx), blk, 0, h->stream, C, df, dalpha, am, an, g.astride, M, N, G.nimg, patch, reg);
+    };
+    sys.residual = [&](const AdjGroup& G, double* out) {
+        hipLaunchKernelGGL(adj_residual_kernel, dim3(G.gpx), blk, 0, h->stream, C, G.dp, M, N, G.nimg, out);
+    };
+    sys.store_du = [&](const AdjGroup& G, double* du) -> int {
+        hipLaunchKernelGGL(adj_du_kernel, dim3(G.gpx), blk, 0, h->stream, C.s, G.dp, G.ctot, du);
+        return BPLTV_OK;
+    };
+    sys.gradpix = [&](const AdjGroup& G) {
+        hipLaunchKernelGGL(adj_gradpix_kernel, dim3(G.gpx), blk, 0, h->stream, C, G.dp, M, N, G.nimg, patch, reg, h->d_gpix + G.o0);
+    };
+    sys.grad_in = [&]() {   // the s plane covers the whole batch after the group loop
+        const dim3 gtot((unsigned)((tot + 255) / 256));
+        if (g.w) {   // weighted model: w o p, and -(u - f) o p per pixel (d_r is free behind the group loop)
+            double* gw = g.d_grad_w ? (g.wo > 1 ? g.d_grad_w : h->d_r) : nullptr;
+            if (g.d_grad_f || gw)
+                hipLaunchKernelGGL(weighted_adj_out_kernel, gtot, blk, 0, h->stream, h->d_coef + 6 * tot, h->d_p, g.w,
+                                   g.wo > 1 ? npx : (size_t)0, d_u, g.f, npx, tot, g.d_grad_f, gw);
+            if (gw && g.wo == 1)
+                hipLaunchKernelGGL(map_sum_kernel, dim3((unsigned)((npx + 255) / 256)), blk, 0, h->stream, h->d_r, npx, O, g.d_grad_w);
+        } else if (g.d_grad_f)
+            hipLaunchKernelGGL(adj_gradf_kernel, gtot, blk, 0, h->stream, h->d_coef + 6 * tot, h->d_p, tot, reg, g.d_grad_f);
+    };
+    return run_adjoint(h, g, reg, p, sys);
+}
+
+int sr_adj_alloc(bpltv_t* h) {
+    int rc = adj_alloc(h);   // d_p, d_r, d_gpix, d_resn, d_fail
+    if (rc) return rc;
+    if (h->sr_adj_ready) return BPLTV_OK;
+    const size_t tot = h->tot;
+    rc = alloc_all(h, {{(void**)&h->d_srcoef, 19 * tot * sizeof(double)},
+                       {(void**)&h->d_srdiag, 7 * tot * sizeof(double)},
+                       {(void**)&h->d_srw, 6 * tot * sizeof(double)},
+                       {(void**)&h->d_srgpix, 3 * tot * sizeof(double)}}, "sum-of-regularisers adjoint workspace");
+    if (rc) return rc;
+    h->sr_adj_ready = true;
+    return BPLTV_OK;
+}
+
+// The 13-point system of the sum-of-regularisers model (SrCoef; parameter: three slices of g.am*g.an; g.astride != 0: one
+// such block per image, image k reads block k).  Factorisations: nested dissection (default, separators two pixels wide,
+// image groups when the workspace does not fit), the HBM band at bandwidth 2M (params.reserved[4] = 1, whole batch: the
+// cross-check of the nested dissection), and -- sumregs_gradient_reg with a patch parameter, whose row-scaled system is
+// not symmetric (SumRegsLearningFunction.jl:250) -- the LU variant of the nested dissection (banded LU with
+// params.reserved[4] = 1).
+// Forward mode (g.ndir > 0, bpltv_sumregs_jvp): the directions solve A^T du = df - sum_k w_k o up(dx_k) against one
+// factorisation per image group.  The LU paths factor the transpose by swapping the lower and the upper diagonal planes
+// (the main diagonal copied across), also where sr_force_lu puts a symmetric system on them; the refinement takes the
+// residual of A^T (sr_adj_flux_colscale_kernel).  The planes w_k live in d_srgpix, which only the reverse mode needs.
+int run_sr_gradient(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, const bpltv_params& p) {
+    const int M = h->M, N = h->N, am = g.am, an = g.an;
+    const size_t tot = h->tot;
+    const int patch = !(am == 1 && an == 1);
+    const bool rowsc = reg && patch;
+    const bool lu = rowsc || h->opt.sr_force_lu == 1;   // option "sr_force_lu": test aid, the LU path on the symmetric systems too
+    const bool band = p.reserved[4] == 1;     // the band solvers (Cholesky / LU) instead of nested dissection
+    const bool tangent = g.ndir > 0;
+    const int bw = std::min(2 * M, (int)h->npx - 1);
+    const dim3 blk(256);
+    SrCoef C{};   // planes keep the whole-batch stride C.tot; the group starts at its first image
+    double *diag = nullptr, *diagU = nullptr, *w = nullptr, *gp = nullptr;
+    const double* rowscale = nullptr;
+    AdjSystem sys;
+    sys.slices = 3;
+    sys.kact = 1.0 / 2.220446049250313e-16;   // eps() in the vector AND the patch variant (:319, :389)
+    // the gate leaves out the rows that carry the active-set weight: the smallest share an active element adds to a
+    // diagonal is the centred operator's (1/2)^2 kappa (forward and backward differences add kappa or more)
+    sys.gate_skip = 0.25;
+    sys.alpha_msg = "sumregs_gradient_reg with a patch parameter needs every entry > 0 (min = %g)";
+    sys.gate_msg = "sum-of-regularisers adjoint solve: scaled residual %.3e above the gate %.1e";
+    sys.prepare = [&](AdjPlan* pl) -> int {
+        int rc = sr_adj_alloc(h);
+        if (rc) return rc;
+        if (p.reserved[4] == 2) return set_err(h, BPLTV_E_UNSUPPORTED, "block cyclic reduction applies to the TV model only");
+        if (lu && !h->d_srdiagU) {
+            rc = alloc_all(h, {{(void**)&h->d_srdiagU, 7 * tot * sizeof(double)}}, "sum-of-regularisers adjoint (upper diagonals)");
+            if (rc) return rc;
+        }
+        if (lu && !band) {
+            rc = nd_alloc(h, h->nd_sr_lu, nd_stencil_sr(), "sum of regularisers, nested dissection (LU)", &pl->Oc, true);
+        } else if (lu) {
+            if (!h->lu_sr_ready)
+                rc = hbm_band_alloc(h, h->lu_sr, bw, "sum-of-regularisers adjoint (banded LU)",
+                                    "sum-of-regularisers adjoint (banded LU): %.1f GB of HBM needed, %.1f GB free");
+            if (!rc) h->lu_sr_ready = true;
+        } else if (band) {
+            if (!h->sr_band_ready)
+                rc = hbm_band_alloc(h, h->hb_sr, bw, "sum-of-regularisers adjoint (HBM band)",
+                                    "sum-of-regularisers adjoint (HBM band): %.1f GB of HBM needed, %.1f GB free");
+            if (!rc) h->sr_band_ready = true;
+        } else {
+            rc = nd_alloc(h, h->nd_sr, nd_stencil_sr(), "sum of regularisers, nested dissection", &pl->Oc);
+        }
+        if (rc) return rc;
+        // kappa = 1e14 for every parameter kind here: on images with a real active set two sweeps left the gradients up to 5e2
+        // times outside 1e-8 max|p| + 1e-6 |.| and four 1.2 times; five leave 0.06 of it on every factorisation
+        pl->nref = reg ? 1 : 5;
+        pl->method = lu ? (band ? (int)ADJ_BAND_LU : (int)ADJ_ND_LU) : (band ? (int)ADJ_BAND_HBM : (int)ADJ_ND);
+        pl->hb_sync = (band && !lu) ? (h->hb_sr.value_sync ? 2 : 1) : 0;
+        pl->pivot_msg = lu ? (band ? "sum-of-regularisers adjoint, banded LU without pivoting: zero, tiny or non-finite pivot at column %d of image %d"
+                                   : "sum-of-regularisers adjoint, LU without pivoting: zero, tiny or non-finite pivot at front %d of image %d")
+                           : (band ? "sum-of-regularisers adjoint Cholesky: non-positive pivot at column %d of image %d"
+                                   : "sum-of-regularisers adjoint Cholesky: non-positive pivot at front %d of image %d");
+        pl->gpix = h->d_srgpix;
+        return BPLTV_OK;
+    };
+    sys.factor = [&](AdjGroup& G) -> int {
+        const size_t o0 = G.o0;
+        const int nimg = G.nimg;
+        C.tot = tot;
+        C.t1 = h->d_srcoef + o0; C.t2 = h->d_srcoef + 3 * tot + o0; C.c = h->d_srcoef + 6 * tot + o0; C.kap = h->d_srcoef + 9 * tot + o0;
+        C.h1 = h->d_srcoef + 12 * tot + o0; C.h2 = h->d_srcoef + 15 * tot + o0; C.rhs = h->d_srcoef + 18 * tot + o0;
+        diag = h->d_srdiag + o0; diagU = lu ? h->d_srdiagU + o0 : nullptr; w = h->d_srw + o0; gp = h->d_srgpix + o0;
+        rowscale = rowsc ? G.ga : nullptr;
+        G.rhs = C.rhs; G.diag = diag;
+        if (tangent || g.cot)   // forward mode: the coefficient planes alone (sr_tangent_rhs_kernel writes each direction's right-hand side)
+            hipLaunchKernelGGL(sr_adj_setup_cot_kernel, dim3(G.gpx), blk, 0, h->stream, d_u + o0, (tangent ? d_u : g.src) + o0, G.ga, am,
+                               an, g.astride, M, N, nimg, patch, reg, G.kact, C);
+        else
+            hipLaunchKernelGGL(sr_adj_setup_kernel, dim3(G.gpx), blk, 0, h->stream, d_u + o0, g.src + o0, G.ga, am, an, g.astride, M,
+                               N, nimg, patch, reg, G.kact, C);
+        if (lu) HIPCHK(h, hipMemsetAsync(h->d_srdiagU, 0, 7 * tot * sizeof(double), h->stream));
+        hipLaunchKernelGGL(sr_adj_assemble_kernel, dim3(G.gpx), blk, 0, h->stream, C, M, N, nimg, diag, rowscale, am, an, g.astride, diagU);
+        BandDiags D;
+        D.planes = diag; D.tot = tot; D.nd = 7;
+        D.off[0] = 0; D.off[1] = 1; D.off[2] = 2; D.off[3] = M - 1; D.off[4] = M; D.off[5] = M + 1; D.off[6] = 2 * M;
+        // forward mode on the LU paths: A^T.  Its lower diagonals are A's upper ones and the other way round; the main
+        // diagonal is read from the first argument alone, and the assembly left plane 0 of diagU at zero.
+        const double *facL = diag, *facU = diagU;
+        if (tangent && lu) {
+            HIPCHK(h, hipMemcpyAsync(diagU, diag, G.ctot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+            facL = diagU; facU = diag;
+        }
+        int rc = 0;
+        if (lu && !band) {
+            rc = h->nd_sr_lu.factor_lu(facL, facU, tot, nimg, G.dfail);
+            if (rc) return set_err(h, rc, "sum-of-regularisers adjoint (nested dissection, LU): %s", h->nd_sr_lu.err.c_str());
+        } else if (lu) {
+            BandDiags DL = D, DU = D;
+            DL.planes = facL;
+            DU.planes = facU;
+            rc = h->lu_sr.factor(DL, DU, G.dfail);
+            if (rc) return set_err(h, rc, "sum-of-regularisers adjoint (banded LU): %s", h->lu_sr.err.c_str());
+        } else if (band) {
+            rc = h->hb_sr.factor(D, G.dfail);
+            if (rc) return set_err(h, rc, "sum-of-regularisers adjoint (HBM band): %s", h->hb_sr.err.c_str());
+        } else {
+            rc = h->nd_sr.factor(diag, tot, nimg, G.dfail);
+            if (rc) return set_err(h, rc, "sum-of-regularisers adjoint (nested dissection): %s", h->nd_sr.err.c_str());
+        }
+        if (tangent) hipLaunchKernelGGL(sr_adj_wplane_kernel, dim3(G.gpx), blk, 0, h->stream, C, M, N, nimg, gp);
+        return BPLTV_OK;
+    };
+    sys.solve = [&](const AdjGroup& G, double* v, double* acc) -> int {
+        int r2 = 0;
+        if (lu && !band) { if ((r2 = h->nd_sr_lu.solve(v, acc, G.nimg))) return set_err(h, r2, "sum-of-regularisers adjoint (nested dissection, LU, substitution): %s", h->nd_sr_lu.err.c_str()); }
+        else if (lu) h->lu_sr.solve(v, acc, h->d_gpix);
+        else if (band) h->hb_sr.solve(v, acc, h->d_gpix);
+        else if ((r2 = h->nd_sr.solve(v, acc, G.nimg))) return set_err(h, r2, "sum-of-regularisers adjoint (nested dissection, substitution): %s", h->nd_sr.err.c_str());
+        return BPLTV_OK;
+    };
+    sys.tangent_rhs = [&](const AdjGroup& G, const double* df, const double* dalpha) {
+        hipLaunchKernelGGL(sr_tangent_rhs_kernel, dim3(G.gpx), blk, 0, h->stream, C, (const double*)gp, df, dalpha, am, an, g.astride, M, N, G.nimg);
+    };
+    sys.residual = [&](const AdjGroup& G, double* out) {
+        const bool colsc = tangent && rowsc;   // of A^T: the parameter scales columns, before G_k
+        if (colsc)
+            hipLaunchKernelGGL(sr_adj_flux_colscale_kernel, dim3(G.gpx), blk, 0, h->stream, C, G.dp, M, N, G.nimg, w, rowscale, am, an, g.astride);
+        else
+            hipLaunchKernelGGL(sr_adj_flux_kernel, dim3(G.gpx), blk, 0, h->stream, C, G.dp, M, N, G.nimg, w);
+        hipLaunchKernelGGL(sr_adj_residual_kernel, dim3(G.gpx), blk, 0, h->stream, C, G.dp, w, M, N, G.nimg, out,
+                           colsc ? (const double*)nullptr : rowscale, am, an, g.astride);
+    };
+    sys.store_du = [&](const AdjGroup& G, double* du) -> int {   // du is the solution itself: straight into the caller's array
+        HIPCHK(h, hipMemcpyAsync(du, G.dp, G.ctot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+        return BPLTV_OK;
+    };
+    sys.gradpix = [&](const AdjGroup& G) {
+        hipLaunchKernelGGL(sr_adj_gradpix_kernel, dim3(G.gpx), blk, 0, h->stream, C, G.dp, M, N, G.nimg, patch, reg, gp);
+    };
+    sys.grad_in = [&]() {
+        if (g.d_grad_f)
+            hipLaunchKernelGGL(sr_adj_gradf_kernel, dim3((unsigned)((tot + 255) / 256)), blk, 0, h->stream, h->d_p, tot, reg, g.d_grad_f);
+    };
+    return run_adjoint(h, g, reg, p, sys);
 }
 
 // sr: the defaults of the sum-of-regularisers model (bpltv_sumregs_default_params: another delta_t)
@@ -1905,8 +2161,6 @@ struct WallTimer {
     std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
     double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 };
-
-int run_sr_gradient(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, const bpltv_params& p);
 
 int check_weight(bpltv_t* h, const char* who, const double* w, bool on_device, size_t n, double* wmin);
 int weighted_check_params(bpltv_t* h, const bpltv_params& p, const char* who);
@@ -1945,7 +2199,7 @@ int stage_param(bpltv_t* h, const char* who, const double* alpha, bool alpha_dev
     if (rc) return rc;
     if (failed == 0) return set_err(h, BPLTV_E_ARG, "%s: alpha (device array): parameters must be finite and >= 0", who);
     if (failed > 0) return set_err(h, BPLTV_E_ARG, "%s: the %s must be finite", who, extra.begin()[failed - 1].name);
-    if (sr && reg && !(am == 1 && an == 1) && !(amin > 0.0))   // run_sr_gradient_once's condition, before anything changes
+    if (sr && reg && !(am == 1 && an == 1) && !(amin > 0.0))   // run_adjoint's refusal for this model, before anything changes
         return set_err(h, BPLTV_E_ARG, "sumregs_gradient_reg with a patch parameter needs every entry > 0 (min = %g)", amin);
     const hipMemcpyKind kind = alpha_dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
     double *d_a = h->d_vjp + 4, *d_wv = h->d_vjp + 4 + 2 * P;
@@ -1978,8 +2232,8 @@ int vjp_common(bpltv_t* h, const double* d_u, const double* alpha, bool alpha_de
 }
 
 // Jacobian-vector product of u = denoise(f, alpha) on a single-device handle: the linear map whose transpose
-// vjp_common computes, for ndir directions against one factorisation per image group (run_gradient_once /
-// run_sr_gradient_once).  d_u, the tangents d_df / d_dalpha (either may be nullptr: a zero tangent) and d_du live in HBM,
+// vjp_common computes, for ndir directions against one factorisation per image group
+// (run_adjoint_once).  d_u, the tangents d_df / d_dalpha (either may be nullptr: a zero tangent) and d_du live in HBM,
 // direction-major; `alpha` on the host or (alpha_dev) in HBM.  slices: 1 TV (bpltv_jvp), 3 sum of regularisers
 // (bpltv_sumregs_jvp; parameter and tangent blocks are 3*am*an doubles).  Checks and staging by stage_param.
 int jvp_common(bpltv_t* h, const double* d_u, const double* alpha, bool alpha_dev, int am, int an, int reg,
@@ -2018,7 +2272,7 @@ const SrVariant SR_VARIANTS[] = {
 constexpr int SR_NVARIANTS = 2;
 
 // What run_pdhg (what = PRE_TV) or run_sr_pdhg (PRE_SR) would reject in a solve of the dataset context with a parameter
-// whose smallest entry is amin; PRE_GRADIENT adds what run_gradient / run_sr_gradient_once reject on the parameters and the
+// whose smallest entry is amin; PRE_GRADIENT adds what run_gradient / run_sr_gradient reject on the parameters and the
 // shape alone (block cyclic reduction where it does not apply; gradient_reg with a patch or map parameter that has a zero
 // entry, PRE_REG_ARRAY).  upload_alpha checks this before it touches the handle, so that a rejected call leaves it --
 // d_alpha, its shape and minimum, the last result, and so bpltv_duality_gap -- as it was (the sweeps check the same
@@ -2146,278 +2400,6 @@ int run_sr_pdhg(bpltv_t* h, const SolveCtx& x, const bpltv_params& p, int* resul
     // duality-gap checks every check_every iterations, early stop at gap_tol (as the TV model)
     j.gap = [&](int buf, double* gmax) { return compute_gap(h, x, MODEL_SR, buf, nullptr, gmax); };
     return run_chains(h, p, j, result_buf);
-}
-
-int sr_adj_alloc(bpltv_t* h) {
-    int rc = adj_alloc(h);   // d_p, d_r, d_gpix, d_resn, d_fail
-    if (rc) return rc;
-    if (h->sr_adj_ready) return BPLTV_OK;
-    const size_t tot = h->tot;
-    rc = alloc_all(h, {{(void**)&h->d_srcoef, 19 * tot * sizeof(double)},
-                       {(void**)&h->d_srdiag, 7 * tot * sizeof(double)},
-                       {(void**)&h->d_srw, 6 * tot * sizeof(double)},
-                       {(void**)&h->d_srgpix, 3 * tot * sizeof(double)}}, "sum-of-regularisers adjoint workspace");
-    if (rc) return rc;
-    h->sr_adj_ready = true;
-    return BPLTV_OK;
-}
-
-// HBM band solver of the 13-point system (bandwidth 2M), whole batch: the cross-check of the nested-dissection path
-int sr_band_alloc(bpltv_t* h) {
-    if (h->sr_band_ready) return BPLTV_OK;
-    size_t freeb = 0, totalb = 0;
-    (void)hipMemGetInfo(&freeb, &totalb);
-    const int n = (int)h->npx, bw = std::min(2 * h->M, n - 1);
-    const size_t need = h->hb_sr.bytes_needed(bw, n, h->O);
-    if (need + (2ull << 30) > freeb)
-        return set_err(h, BPLTV_E_NOMEM, "sum-of-regularisers adjoint (HBM band): %.1f GB of HBM needed, %.1f GB free", need / 1e9, freeb / 1e9);
-    h->hb_sr.opt_sync = h->opt.hb_sync; h->hb_sr.opt_single_stream = h->opt.hb_single_stream; h->hb_sr.opt_rw = h->opt.hb_rw;
-    const int rc = h->hb_sr.alloc(bw, n, h->O, h->stream);
-    if (rc) return set_err(h, rc, "sum-of-regularisers adjoint (HBM band): %s", h->hb_sr.err.c_str());
-    h->sr_band_ready = true;
-    return BPLTV_OK;
-}
-
-// Gradient of the sum-of-regularisers model.  Factorisations of its 13-point system: nested dissection (default,
-// separators two pixels wide, image groups when the workspace does not fit), the HBM band at bandwidth 2M
-// (params.reserved[4] = 1), and -- sumregs_gradient_reg with a patch parameter, whose row-scaled system is not
-// symmetric (SumRegsLearningFunction.jl:250) -- the LU variant of the nested dissection (banded LU with
-// params.reserved[4] = 1).
-// Parameter (three slices of g.am*g.an; g.astride != 0: one such block per image, image k reads block k), right-hand side
-// and outputs come from `g`, as for run_gradient_once.
-// Forward mode (g.ndir > 0, bpltv_sumregs_jvp): the directions solve A^T du = df - sum_k w_k o up(dx_k) against one
-// factorisation per image group.  The LU paths factor the transpose by swapping the lower and the upper diagonal planes
-// (the main diagonal copied across), also where sr_force_lu puts a symmetric system on them; the refinement takes the
-// residual of A^T (sr_adj_flux_colscale_kernel).  The planes w_k live in d_srgpix, which only the reverse mode needs.
-int run_sr_gradient_once(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, const bpltv_params& p, double kappa_scale) {
-    int rc = sr_adj_alloc(h);
-    if (rc) return rc;
-    const int M = h->M, N = h->N, O = h->O, am = g.am, an = g.an;
-    const size_t tot = h->tot, P = (size_t)am * an, npx = h->npx;
-    const int patch = !(am == 1 && an == 1);
-    const bool rowsc = reg && patch;
-    const bool lu = rowsc || h->opt.sr_force_lu == 1;   // option "sr_force_lu": test aid, the LU path on the symmetric systems too
-    if (p.reserved[4] == 2) return set_err(h, BPLTV_E_UNSUPPORTED, "block cyclic reduction applies to the TV model only");
-    const bool band = p.reserved[4] == 1;     // the band solvers (Cholesky / LU) instead of nested dissection
-    int Oc = O;
-    if (lu && rowsc && !(g.alpha_min > 0.0))
-        return set_err(h, BPLTV_E_ARG, "sumregs_gradient_reg with a patch parameter needs every entry > 0 (min = %g)", g.alpha_min);
-    if (lu && !h->d_srdiagU) {
-        rc = alloc_all(h, {{(void**)&h->d_srdiagU, 7 * tot * sizeof(double)}}, "sum-of-regularisers adjoint (upper diagonals)");
-        if (rc) return rc;
-    }
-    if (lu && !band) {
-        rc = nd_alloc(h, h->nd_sr_lu, nd_stencil_sr(), "sum of regularisers, nested dissection (LU)", &Oc, true);
-        if (rc) return rc;
-    } else if (lu) {
-        if (!h->lu_sr_ready) {
-            const int n = (int)h->npx, bw = std::min(2 * M, n - 1);
-            size_t freeb = 0, totalb = 0;
-            (void)hipMemGetInfo(&freeb, &totalb);
-            const size_t need = h->lu_sr.bytes_needed(bw, n, O);
-            if (need + (2ull << 30) > freeb)
-                return set_err(h, BPLTV_E_NOMEM, "sum-of-regularisers adjoint (banded LU): %.1f GB of HBM needed, %.1f GB free", need / 1e9, freeb / 1e9);
-            const int rc2 = h->lu_sr.alloc(bw, n, O, h->stream);
-            if (rc2) return set_err(h, rc2, "sum-of-regularisers adjoint (banded LU): %s", h->lu_sr.err.c_str());
-            h->lu_sr_ready = true;
-        }
-    } else if (band) {
-        rc = sr_band_alloc(h);
-        if (rc) return rc;
-    } else {
-        rc = nd_alloc(h, h->nd_sr, nd_stencil_sr(), "sum of regularisers, nested dissection", &Oc);
-        if (rc) return rc;
-    }
-    double kact = 1.0 / 2.220446049250313e-16;   // eps() in the vector AND the patch variant (:319, :389)
-    const double kcap = p.kappa_cap > 0.0 ? p.kappa_cap : 1e14;
-    if (kact > kcap) kact = kcap;
-    kact *= kappa_scale;
-    // kappa = 1e14 for every parameter kind here: on images with a real active set two sweeps left the gradients up to 5e2
-    // times outside 1e-8 max|p| + 1e-6 |.| and four 1.2 times; five leave 0.06 of it on every factorisation
-    const int nref = p.refine < 0 ? (reg ? 1 : 5) : p.refine;
-    // forward mode: every direction keeps its own residual statistics (the gate takes the worst)
-    const bool tangent = g.ndir > 0;
-    const int ndir = tangent ? g.ndir : 1;
-    double* resn_fin = h->d_resn;
-    if (ndir > 1) {
-        rc = ensure(h, &h->d_jres, &h->jres_cap, 4 * (size_t)O * ndir);
-        if (rc) return rc;
-        resn_fin = h->d_jres;
-    }
-    const size_t dastride = 3 * P * (g.each ? O : 1);   // doubles between two directions of g.dalpha
-    HIPCHK(h, hipEventRecord(h->ev[2], h->stream));
-    HIPCHK(h, hipMemsetAsync(h->d_fail, 0, sizeof(int) * O, h->stream));
-    int chunks = 0;
-    for (int c0 = 0; c0 < O; c0 += Oc, ++chunks) {
-        const int nimg = std::min(Oc, O - c0);
-        const size_t o0 = (size_t)c0 * npx, ctot = (size_t)nimg * npx;
-        SrCoef C;   // planes keep the whole-batch stride C.tot; the group starts at its first image
-        C.tot = tot;
-        C.t1 = h->d_srcoef + o0; C.t2 = h->d_srcoef + 3 * tot + o0; C.c = h->d_srcoef + 6 * tot + o0; C.kap = h->d_srcoef + 9 * tot + o0;
-        C.h1 = h->d_srcoef + 12 * tot + o0; C.h2 = h->d_srcoef + 15 * tot + o0; C.rhs = h->d_srcoef + 18 * tot + o0;
-        double *diag = h->d_srdiag + o0, *diagU = lu ? h->d_srdiagU + o0 : nullptr, *w = h->d_srw + o0, *gp = h->d_srgpix + o0;
-        double *dp = h->d_p + o0, *dr = h->d_r + o0;
-        int* dfail = h->d_fail + c0;
-        const int gpx = (int)((ctot + 255) / 256);
-        const double* ga = g.alpha + (size_t)c0 * g.astride;   // the group's first image's parameter block
-        const double* rowscale = rowsc ? ga : nullptr;
-        if (tangent)   // the coefficient planes alone: sr_tangent_rhs_kernel writes each direction's right-hand side below
-            hipLaunchKernelGGL(sr_adj_setup_cot_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, d_u + o0, ga, am, an, g.astride,
-                               M, N, nimg, patch, reg, kact, C);
-        else if (g.cot)
-            hipLaunchKernelGGL(sr_adj_setup_cot_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0, ga, am, an, g.astride,
-                               M, N, nimg, patch, reg, kact, C);
-        else
-            hipLaunchKernelGGL(sr_adj_setup_kernel, dim3(gpx), dim3(256), 0, h->stream, d_u + o0, g.src + o0, ga, am, an, g.astride, M,
-                               N, nimg, patch, reg, kact, C);
-        if (lu) HIPCHK(h, hipMemsetAsync(h->d_srdiagU, 0, 7 * tot * sizeof(double), h->stream));
-        hipLaunchKernelGGL(sr_adj_assemble_kernel, dim3(gpx), dim3(256), 0, h->stream, C, M, N, nimg, diag, rowscale, am, an, g.astride, diagU);
-        BandDiags D;
-        D.planes = diag; D.tot = tot; D.nd = 7;
-        D.off[0] = 0; D.off[1] = 1; D.off[2] = 2; D.off[3] = M - 1; D.off[4] = M; D.off[5] = M + 1; D.off[6] = 2 * M;
-        // forward mode on the LU paths: A^T.  Its lower diagonals are A's upper ones and the other way round; the main
-        // diagonal is read from the first argument alone, and the assembly left plane 0 of diagU at zero.
-        const double *facL = diag, *facU = diagU;
-        if (tangent && lu) {
-            HIPCHK(h, hipMemcpyAsync(diagU, diag, ctot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            facL = diagU; facU = diag;
-        }
-        if (lu && !band) {
-            rc = h->nd_sr_lu.factor_lu(facL, facU, tot, nimg, dfail);
-            if (rc) return set_err(h, rc, "sum-of-regularisers adjoint (nested dissection, LU): %s", h->nd_sr_lu.err.c_str());
-        } else if (lu) {
-            BandDiags DL = D, DU = D;
-            DL.planes = const_cast<double*>(facL);
-            DU.planes = const_cast<double*>(facU);
-            rc = h->lu_sr.factor(DL, DU, dfail);
-            if (rc) return set_err(h, rc, "sum-of-regularisers adjoint (banded LU): %s", h->lu_sr.err.c_str());
-        } else if (band) {
-            rc = h->hb_sr.factor(D, dfail);
-            if (rc) return set_err(h, rc, "sum-of-regularisers adjoint (HBM band): %s", h->hb_sr.err.c_str());
-        } else {
-            rc = h->nd_sr.factor(diag, tot, nimg, dfail);
-            if (rc) return set_err(h, rc, "sum-of-regularisers adjoint (nested dissection): %s", h->nd_sr.err.c_str());
-        }
-        auto residual = [&](double* out) {
-            if (tangent && rowsc) {   // of A^T: the parameter scales columns, before G_k
-                hipLaunchKernelGGL(sr_adj_flux_colscale_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, w, rowscale, am, an, g.astride);
-                hipLaunchKernelGGL(sr_adj_residual_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, w, M, N, nimg, out, (const double*)nullptr, am, an, g.astride);
-                return;
-            }
-            hipLaunchKernelGGL(sr_adj_flux_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, w);
-            hipLaunchKernelGGL(sr_adj_residual_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, w, M, N, nimg, out, rowscale, am, an, g.astride);
-        };
-        auto solve = [&](double* v, double* acc) -> int {
-            int r2 = 0;
-            if (lu && !band) { if ((r2 = h->nd_sr_lu.solve(v, acc, nimg))) return set_err(h, r2, "sum-of-regularisers adjoint (nested dissection, LU, substitution): %s", h->nd_sr_lu.err.c_str()); }
-            else if (lu) h->lu_sr.solve(v, acc, h->d_gpix);
-            else if (band) h->hb_sr.solve(v, acc, h->d_gpix);
-            else if ((r2 = h->nd_sr.solve(v, acc, nimg))) return set_err(h, r2, "sum-of-regularisers adjoint (nested dissection, substitution): %s", h->nd_sr.err.c_str());
-            return BPLTV_OK;
-        };
-        if (tangent) hipLaunchKernelGGL(sr_adj_wplane_kernel, dim3(gpx), dim3(256), 0, h->stream, C, M, N, nimg, gp);
-        for (int d = 0; d < ndir; ++d) {   // one pass, or the tangent directions against this group's factorisation
-            if (tangent)
-                hipLaunchKernelGGL(sr_tangent_rhs_kernel, dim3(gpx), dim3(256), 0, h->stream, C, (const double*)gp,
-                                   g.df ? g.df + (size_t)d * tot + o0 : nullptr,
-                                   g.dalpha ? g.dalpha + (size_t)d * dastride + (size_t)c0 * g.astride : nullptr, am, an, g.astride, M, N,
-                                   nimg);
-            HIPCHK(h, hipMemcpyAsync(dp, C.rhs, ctot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-            rc = solve(dp, nullptr);
-            if (rc) return rc;
-            for (int it = 0; it < nref; ++it) {
-                residual(dr);
-                rc = solve(dr, dp);
-                if (rc) return rc;
-            }
-            residual(dr);
-            double* resn_part = h->d_resn + 4 * (size_t)O + 4 * (size_t)c0 * RESN_BLK;
-            // the gate leaves out the rows that carry the active-set weight: the smallest share an active element adds to a
-            // diagonal is the centred operator's (1/2)^2 kappa (forward and backward differences add kappa or more)
-            hipLaunchKernelGGL(adj_resnorm_kernel, dim3(RESN_BLK, nimg), dim3(256), 0, h->stream, dr, C.rhs, diag, (int)npx, resn_part,
-                               (const double*)nullptr, reg ? (double)HUGE_VAL : 0.25 * kact, (const double*)nullptr, M);
-            hipLaunchKernelGGL(adj_resnorm_final_kernel, dim3((4 * nimg + 63) / 64), dim3(64), 0, h->stream, resn_part, nimg,
-                               resn_fin + 4 * ((size_t)d * O + c0));
-            if (tangent)   // du is the solution itself: straight into the direction's slice of the caller's array
-                HIPCHK(h, hipMemcpyAsync(g.du + (size_t)d * tot + o0, dp, ctot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-        }
-        if (g.d_out)
-            hipLaunchKernelGGL(sr_adj_gradpix_kernel, dim3(gpx), dim3(256), 0, h->stream, C, dp, M, N, nimg, patch, reg, gp);
-        HIPCHK(h, hipGetLastError());
-    }
-    // ... then per parameter, over all images (a vector-Jacobian product may not want the parameter gradient)
-    const bool amap = am == M && an == N && !(M == 1 && N == 1);
-    if (g.d_out && g.each) {   // per image, image-major: block k holds image k's three slices, nothing is summed over images
-        if (amap)
-            hipLaunchKernelGGL(sr_gpix_each_kernel, dim3((unsigned)((3 * tot + 255) / 256)), dim3(256), 0, h->stream, h->d_srgpix, npx, O,
-                               g.d_out);
-        else
-            for (int k = 0; k < 3; ++k)
-                hipLaunchKernelGGL(patch_sum_kernel, dim3((unsigned)P, O), dim3(256), 0, h->stream, h->d_srgpix + k * tot, M, N, O, am, an,
-                                   1, (int)(3 * P), g.d_out + (size_t)k * P);
-    } else if (g.d_out && amap) {   // three pixelwise maps: plain sums over the images
-        for (int k = 0; k < 3; ++k)
-            hipLaunchKernelGGL(map_sum_kernel, dim3((unsigned)((h->npx + 255) / 256)), dim3(256), 0, h->stream, h->d_srgpix + k * tot,
-                               h->npx, O, g.d_out + (size_t)k * h->npx);
-    } else if (g.d_out) {
-        rc = ensure(h, &h->d_red, &h->red_cap, 3 * P * O);
-        if (rc) return rc;
-        for (int k = 0; k < 3; ++k)
-            hipLaunchKernelGGL(patch_sum_kernel, dim3((unsigned)P, O), dim3(256), 0, h->stream, h->d_srgpix + k * tot, M, N, O, am, an,
-                               O, 1, h->d_red + (size_t)k * P * O);
-        hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, h->stream, h->d_red, O, (int)(3 * P), 1.0, g.d_out, (double*)nullptr);
-    }
-    // input gradient of a vector-Jacobian product: d_p covers the whole batch after the group loop
-    if (g.d_grad_f)
-        hipLaunchKernelGGL(sr_adj_gradf_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, h->stream, h->d_p, tot, reg, g.d_grad_f);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipEventRecord(h->ev[3], h->stream));
-    std::vector<int> fail(O);
-    std::vector<double> resn(4 * (size_t)O * ndir);
-    HIPCHK(h, hipMemcpyAsync(fail.data(), h->d_fail, sizeof(int) * O, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(resn.data(), resn_fin, sizeof(double) * resn.size(), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    float ms = 0.f;
-    HIPCHK(h, hipEventElapsedTime(&ms, h->ev[2], h->ev[3]));
-    h->st.adjoint_ms = ms;
-    h->st.reg_gradient_used = reg;
-    h->st.adjoint_method = lu ? (band ? (int)ADJ_BAND_LU : (int)ADJ_ND_LU) : (band ? (int)ADJ_BAND_HBM : (int)ADJ_ND);
-    h->st.adjoint_chunks = chunks;
-    h->st.hb_sync = (band && !lu) ? (h->hb_sr.value_sync ? 2 : 1) : 0;
-    h->st.kappa_used = reg ? 0.0 : kact;
-    double worst = 0.0, worst_raw = 0.0;
-    for (int k = 0; k < O; ++k)
-        if (fail[k] != 0)
-            return set_err(h, BPLTV_E_NUMERIC, lu ? (band ? "sum-of-regularisers adjoint, banded LU without pivoting: zero, tiny or non-finite pivot at column %d of image %d"
-                                                          : "sum-of-regularisers adjoint, LU without pivoting: zero, tiny or non-finite pivot at front %d of image %d")
-                                                  : (band ? "sum-of-regularisers adjoint Cholesky: non-positive pivot at column %d of image %d"
-                                                          : "sum-of-regularisers adjoint Cholesky: non-positive pivot at front %d of image %d"), fail[k] - 1, k);
-    for (size_t k = 0; k < (size_t)O * ndir; ++k) {   // (direction, image) pairs: the worst of them
-        const double* q = &resn[4 * k];
-        const double raw = std::sqrt(q[0]) / (q[1] > 0 ? std::sqrt(q[1]) : 1.0);
-        const double scl = std::sqrt(q[2]) / (q[3] > 0 ? std::sqrt(q[3]) : 1.0);
-        if (!(raw <= worst_raw)) worst_raw = raw;
-        if (!(scl <= worst)) worst = scl;
-    }
-    h->st.adjoint_residual = worst;
-    h->st.adjoint_residual_raw = worst_raw;
-    if (!(worst <= BPLTV_RESIDUAL_GATE))
-        return set_err(h, BPLTV_E_NUMERIC, "sum-of-regularisers adjoint solve: scaled residual %.3e above the gate %.1e", worst,
-                       (double)BPLTV_RESIDUAL_GATE);
-    return BPLTV_OK;
-}
-
-int run_sr_gradient(bpltv_t* h, const double* d_u, const GradCtx& g, int reg, const bpltv_params& p) {
-    double scale = 1.0;
-    int rc = BPLTV_OK;
-    h->st.adjoint_attempts = 0;
-    for (int attempt = 0; attempt < 3; ++attempt, scale *= 1e-2) {
-        rc = run_sr_gradient_once(h, d_u, g, reg, p, scale);
-        h->st.adjoint_attempts = attempt + 1;
-        if (rc != BPLTV_E_NUMERIC || reg) break;
-    }
-    if (rc == BPLTV_OK) h->err.clear();
-    return rc;
 }
 
 // One solve of the dataset context (TV, or sr: sum of regularisers).  The result is committed to the handle here, after

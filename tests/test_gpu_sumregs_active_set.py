@@ -25,7 +25,7 @@ KINDS = ["vector", "patch22", "map"]
 # change nothing (forced LU on the symmetric system gains about a digit per sweep: tests/test_gpu_sumregs_vjp._methods)
 METHODS = [("nd", "nd", 0, 6), ("nd-lu", "nd", 1, 10), ("band-hbm", "band", 0, 6), ("band-lu", "band", 1, 10)]
 METHOD_IDS = [m[0] for m in METHODS]
-# the default factorisation and one LU path, for the entry points that share run_sr_gradient_once with sumregs_vjp
+# the default factorisation and one LU path, for the entry points that share run_sr_gradient with sumregs_vjp
 TWO = [METHODS[0], METHODS[1]]
 TWO_IDS = [m[0] for m in TWO]
 
@@ -107,7 +107,7 @@ def test_vjp_at_converged_refinement_matches_the_literal_system(gpu_solver_cls, 
         nested dissection        vector 3.8e-11 / 2.6e-10    patch, map 5.6e-11 / 2.4e-10    at most 0.0029 of the bound
         band in HBM              vector 8.5e-11 / 5.7e-10    patch, map 8.4e-11 / 4.2e-10    at most 0.0025
         nd-lu, band-lu (forced)  vector 1.8e-12 / 9.6e-12    patch, map 7.4e-13 / 3.7e-12    at most 0.0001
-    Until the gate of run_sr_gradient_once left out the rows that carry the weight, both "flat" batches were refused at
+    Until the gate of run_sr_gradient left out the rows that carry the weight, both "flat" batches were refused at
     kappa = 1e14 and again at 1e12 on every factorisation, whatever the sweep count, and solved with 1e10 (adjoint_attempts 3,
     residual 9.6e-8): DESIGN.md section 4.4, "Held to the literal system on active sets"."""
     st, okf, okx = vjp_distances(gpu_solver_cls, shape, kind, layout, method, method[3])
@@ -119,7 +119,7 @@ def test_vjp_at_converged_refinement_matches_the_literal_system(gpu_solver_cls, 
 @pytest.mark.parametrize("method", METHODS, ids=METHOD_IDS)
 @pytest.mark.parametrize("shape,kind,layout", VJP_CASES, ids=VJP_IDS)
 def test_vjp_at_the_default_refinement_matches_the_literal_system(gpu_solver_cls, shape, kind, layout, method):
-    """The same calls with the sweep count left to the library (nref in run_sr_gradient_once: five).
+    """The same calls with the sweep count left to the library (AdjPlan::nref of run_sr_gradient: five).
 
     Measured on the MI355X, grad_f / grad_x and the worst fraction of the elementwise bound: nested dissection 1.4e-9 / 7.0e-9,
     0.059 (3 x 33 x 17 "flat", vector); band in HBM 1.9e-9 / 1.6e-8, 0.038; nd-lu 1.7e-10 / 5.2e-10, 0.0015; band-lu 2.3e-10 /

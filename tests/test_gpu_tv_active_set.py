@@ -115,7 +115,7 @@ def test_vjp_at_converged_refinement_matches_the_literal_system(gpu_solver_cls, 
 @pytest.mark.parametrize("method", sorted(METHODS), ids=METHOD_IDS)
 @pytest.mark.parametrize("shape,kind,layout", VJP_CASES, ids=VJP_IDS)
 def test_vjp_at_the_default_refinement_matches_the_literal_system(gpu_solver_cls, shape, kind, layout, method):
-    """The same calls with the sweep count left to the library (nref_default in run_gradient_once).
+    """The same calls with the sweep count left to the library (AdjPlan::nref of run_gradient).
 
     Measured on the MI355X with a scalar (patch and map as above): LDS band (3 sweeps) 2.6e-8 / 2.0e-7, 0.67 of the bound on
     3 x 33 x 17; block cyclic reduction (3) 3.5e-10 / 1.6e-8; nested dissection (4) 4.3e-11 / 3.5e-9; band in HBM (4) 5.1e-12 /

@@ -108,7 +108,7 @@ def test_weighted_vjp_at_converged_refinement_matches_the_literal_system(gpu_sol
 @pytest.mark.parametrize("method", sorted(METHODS), ids=METHOD_IDS)
 @pytest.mark.parametrize("case", wa.CASES, ids=wa.IDS)
 def test_weighted_vjp_at_the_default_refinement_matches_the_literal_system(gpu_solver_cls, case, method):
-    """The same calls with the sweep count left to the library (nref_default in run_gradient_once: 3 on the LDS band and block
+    """The same calls with the sweep count left to the library (AdjPlan::nref of run_gradient: 3 on the LDS band and block
     cyclic reduction, 4 on nested dissection and the band in HBM with a scalar; 2 and 1 with a patch or a map).
 
     Measured on the MI355X: the figures of the test above, except with a scalar under `step` on block cyclic reduction:
