@@ -30,6 +30,7 @@
 #include "sumregs_kernels.hpp"
 #include "weighted_kernels.hpp"
 #include "tv_tile_kernels.hpp"
+#include "color_tile_kernels.hpp"
 #include "sumregs_unrolled_kernels.hpp"
 #include "multi_gpu.hpp"
 
@@ -198,8 +199,9 @@ const Variant kVariants[] = {
 };
 
 // The models whose solves the shared launch driver (run_chains) runs
-enum Model { MODEL_TV = 0, MODEL_SR = 1, MODEL_W = 2, MODEL_UN = 3, MODEL_SRUN = 4, NMODELS = 5 };   // MODEL_UN: the taped solve, its reverse sweep and the tangent sweep
+enum Model { MODEL_TV = 0, MODEL_SR = 1, MODEL_W = 2, MODEL_UN = 3, MODEL_SRUN = 4, MODEL_COLOR = 5, NMODELS = 6 };   // MODEL_UN: the taped solve, its reverse sweep and the tangent sweep
                                                                                                      // MODEL_SRUN: the same of the sum-of-regularisers model
+                                                                                                     // MODEL_COLOR: the solves and the reverse sweep of the channel-coupled model
 
 // What identifies a launch sequence built into graphs: everything its kernel arguments and its cut into launches depend
 // on.  One key type for all models (a field a model does not use stays 0); each model has a cache of its own
@@ -212,7 +214,9 @@ struct GraphKey {
                        // (MODEL_UN: the tape the launches write or read, with variant 0 = taped solve, 1 = reverse sweep; 2 ... 5 = tangent
                        // sweep, whose planes stand here instead; 6 = weighted taped solve, 7 / 8 = its reverse sweep without / with grad_w,
                        // 9 ... 16 = its tangent sweep, by the tangents it reads, its planes here;
-                       // MODEL_SRUN: the tape as well, variant 0 = taped solve, 1 = reverse sweep)
+                       // MODEL_SRUN: the tape as well, variant 0 = taped solve, 1 = reverse sweep;
+                       // MODEL_COLOR: the tape as well (nullptr: none), variant 10 * channels + 0 = taped solve, + 1 = reverse sweep,
+                       // + 2 = the solve without a tape)
     const void* tab;   // step table (one per (maxiter, steps, L, dual-first shift, gamma): TabKey)
     int from_state;    // 1: the sequence starts from a prepared state (params.init / order), not from x = f, y = 0
     const void* alpha; // the parameter the launches read: a sweep's blocks and the dataset's parameter are different
@@ -351,6 +355,7 @@ struct Tape {
     double tau0 = 0.0, sigma0 = 0.0, opnorm = 0.0;
     double gamma = 0.0;             // weighted model: min w, the strong convexity its step table was made with
     int spacing = 0;                // 0: the full tape; C >= 1: the buffer holds the state every C iterations (checkpoints) instead
+    int channels = 0;               // channel-coupled model: planes of a colour image (0 otherwise)
     // a buffer of `need` doubles when the tape is smaller (*grown; nullptr when it is large enough): allocated ahead of
     // time, so that a call that is rejected afterwards frees it again and leaves the tape as it was
     hipError_t grow(size_t need, double** grown) const {
@@ -426,7 +431,7 @@ struct bpltv_handle {
     size_t f32_alpha_cap = 0, f32_sweep_alpha_cap = 0;
     bool f32_f_valid = false;
     std::map<TabKey, float*> tabs32;
-    GraphCache graphs[NMODELS] = {{16}, {8}, {8}, {8}, {8}};   // by Model: at most 16 TV sequences, 8 of each other model
+    GraphCache graphs[NMODELS] = {{16}, {8}, {8}, {8}, {8}, {8}};   // by Model: at most 16 TV sequences, 8 of each other model
     std::vector<hipStream_t> chain_streams;   // the device's (DeviceStreams), not owned
     std::vector<hipEvent_t> chain_events;
     unsigned* d_phase = nullptr;              // the word chain 0's launches rewrite (PDHG_PHASE_STAMP, pdhg_phase_gate_kernel)
@@ -499,7 +504,13 @@ struct bpltv_handle {
     Tape srtape;
     double* d_srunr = nullptr;                      // 19 * M*N*O doubles
     bool srun_ready = false;
-    // checkpointed reverse sweeps of the three models (option "tape_checkpoint"): [segment tape | 2 recompute state sets],
+    // ... of the channel-coupled model (color_tile_kernels.hpp): a fourth tape, in the TV tape's layout, that remembers the
+    // channels it was recorded with; the reverse sweep runs in d_unr.  last_channels: the last solve was this model's, with
+    // that many planes per colour image (0: another model's)
+    Tape ctape;
+    int last_channels = 0;
+    bool color_ready = false;
+    // checkpointed reverse sweeps of the four models (option "tape_checkpoint"): [segment tape | 2 recompute state sets],
     // allocated on first use, only grows
     double* d_seg = nullptr;
     size_t seg_cap = 0;                             // doubles
@@ -2413,6 +2424,7 @@ int solve_dataset(bpltv_t* h, bool sr, const bpltv_params& p) {
     (sr ? h->sr_has_result : h->has_result) = true;
     h->last_is_sr = sr;
     h->last_weighted = false;
+    h->last_channels = 0;
     return BPLTV_OK;
 }
 // u of the last solve of the model
@@ -3349,6 +3361,7 @@ int weighted_denoise_common(bpltv_t* h, const double* w, int wo, const double* a
     h->has_result = true;
     h->last_is_sr = false;
     h->last_weighted = true;
+    h->last_channels = 0;
     if (u_out) {
         HIPCHK(h, hipMemcpyAsync(u_out, h->d_state[buf][0], h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3458,6 +3471,7 @@ struct TapedFwd {
     int astride;         // doubles between per-image parameter blocks (0: one block for every image)
     const double* w;     // weighted model; nullptr otherwise
     int wo;
+    int channels = 1;    // channel-coupled model: planes of a colour image
 };
 // the planes a launch reads and writes: a state set, or the step's checkpoint slot
 static void taped_planes(const LaunchStep& s, int np, size_t tot, double* const (*S)[7], const double** in, double** out) {
@@ -3477,10 +3491,11 @@ struct TapedRev {
     double* S[2][7];
     double *gf, *ga, *g0, *gw;
     int K;
+    int channels = 1;    // channel-coupled model: planes of a colour image
 };
 
 // A model whose iterations can be taped and swept backwards: everything the two shared drivers (taped_denoise, taped_vjp)
-// need to know about it.  The three instances follow; a further model is one more of them and its kernels.
+// need to know about it.  The instances follow; a further model is one more of them and its kernels.
 struct TapedModel {
     const char* denoise;          // stem of the solve's entry points ("_each", "_device" are appended), in messages
     const char* vjp;              // ... of the sweep's
@@ -3490,6 +3505,8 @@ struct TapedModel {
     int tape_planes;              // doubles per pixel and iteration on the tape
     int slices;                   // parameter slices: 1, or 3 (sum of regularisers: its defaults, PRE_SR, the d_sr state sets)
     bool weighted;                // takes a fidelity weight w: checked and staged, gamma = min w in the step table, grad_w
+    int channels;                 // channel-coupled model: the planes of a colour image, which the launch chains keep together
+                                  // and the handle's tape remembers (0: every plane is an image of its own)
     int nplanes;                  // planes of a state set
     double L2;                    // squared operator norm of the step table
     int (*plan)(bpltv_t*, const bpltv_params&, int cap, WeightedPlan*);
@@ -3601,10 +3618,78 @@ const TapedModel kTapedSr = [] {
 }();
 const char* const kUnrolled = kTapedTV.multi_name;   // (the tangent sweep's entry points)
 
+// The channel-coupled model (color_tile_kernels.hpp): the TV model's planes, tape layout, step table and sweep planes; the
+// launches count colour images (s.lo, s.hi) and one workgroup holds the C planes of its colour image.  channels = 1 is the TV
+// model: its kernels run.
+template <int C>
+void color_launch_fwd_c(const TapedFwd& x, const LaunchStep& s, TvTileArgs& a) {
+    void (*kern)(TvTileArgs) = x.tape ? &color_tile_kernel<C, true> : &color_tile_kernel<C, false>;
+    hipLaunchKernelGGL(kern, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(TV_R * TV_R), color_lds_bytes(C), s.st, a);
+}
+void color_launch_fwd(const TapedFwd& x, const LaunchStep& s) {
+    if (x.channels == 1) return tv_launch_fwd(x, s);
+    bpltv_t* h = x.h;
+    TvTileArgs a{};
+    taped_planes(s, 3, h->tot, x.S, a.in, a.out);
+    a.f = h->d_f; a.alpha = x.alpha; a.am = x.am; a.an = x.an; a.tab = x.tab;
+    a.tape = x.tape; a.plane = h->tot; a.tk0 = s.tk0;
+    a.it0 = s.it; a.nit = s.nit;
+    a.M = h->M; a.N = h->N; a.halo = x.pl.T; a.first = s.first; a.img0 = s.lo;
+    if (x.channels == 2) color_launch_fwd_c<2>(x, s, a);
+    else if (x.channels == 3) color_launch_fwd_c<3>(x, s, a);
+    else color_launch_fwd_c<4>(x, s, a);
+}
+void color_launch_rev(const TapedRev& x, const LaunchStep& s) {
+    if (x.channels == 1) return tv_launch_rev(x, s);
+    const GradCtx& g = *x.g;
+    TvTileRevArgs a{};
+    for (int c = 0; c < 3; ++c) { a.in[c] = x.S[s.cur][c]; a.out[c] = x.S[s.nxt][c]; }
+    if (s.first) a.in[0] = x.g0;
+    a.gf = x.gf; a.ga = x.ga; a.tape = x.tape; a.alpha = g.alpha; a.tab = x.tab;
+    a.plane = x.h->tot;
+    a.am = g.am; a.an = g.an;
+    a.khi = x.K - 1 - s.it; a.nit = s.nit; a.tk0 = s.tk0;
+    a.M = x.h->M; a.N = x.h->N; a.halo = x.pl.T; a.first = s.first; a.img0 = s.lo;
+    void (*kern)(TvTileRevArgs) = x.channels == 2 ? &color_reverse_tile_kernel<2> : (x.channels == 3 ? &color_reverse_tile_kernel<3> : &color_reverse_tile_kernel<4>);
+    hipLaunchKernelGGL(kern, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(TV_R * TV_R), color_lds_bytes(x.channels), s.st, a);
+}
+// unrolled_plan; the first use raises the LDS the colour kernels may take (three and four sets of planes pass 64 KB)
+int color_plan(bpltv_t* h, const bpltv_params& p, int cap, WeightedPlan* pl) {
+    if (int prc = unrolled_plan(h, p, cap, pl)) return prc;
+    if (!h->color_ready) {
+        const void* k2[] = {(const void*)&color_tile_kernel<2, true>, (const void*)&color_tile_kernel<2, false>, (const void*)&color_reverse_tile_kernel<2>};
+        const void* k3[] = {(const void*)&color_tile_kernel<3, true>, (const void*)&color_tile_kernel<3, false>, (const void*)&color_reverse_tile_kernel<3>};
+        const void* k4[] = {(const void*)&color_tile_kernel<4, true>, (const void*)&color_tile_kernel<4, false>, (const void*)&color_reverse_tile_kernel<4>};
+        for (const void* k : k2) HIPCHK(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)color_lds_bytes(2)));
+        for (const void* k : k3) HIPCHK(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)color_lds_bytes(3)));
+        for (const void* k : k4) HIPCHK(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)color_lds_bytes(4)));
+        h->color_ready = true;
+    }
+    return BPLTV_OK;
+}
+// bytes: TV's per plane; the map's 8 bytes are read once for the C planes of a colour image
+TapedModel taped_color(int C) {
+    TapedModel m = kTapedTV;
+    m.denoise = "bpltv_color_unrolled_denoise"; m.vjp = "color_unrolled_vjp"; m.tape_kind = "colour ";
+    m.multi_name = "the channel-coupled solve";
+    m.tape = &bpltv_handle::ctape;
+    m.channels = C;
+    m.plan = color_plan; m.rev_cap = color_rev_t(C);
+    m.graphs = MODEL_COLOR; m.fwd_variant = 10 * C; m.rev_variant = 10 * C + 1;
+    m.bytes_map = 72.0 + 8.0 / C; m.plain_bytes_map = 56.0 + 8.0 / C;
+    m.adjoint_method = 12; m.tv_stats = false;
+    m.launch_fwd = color_launch_fwd; m.launch_rev = color_launch_rev;
+    return m;
+}
+const TapedModel kTapedColor[COLOR_MAX_C] = {taped_color(1), taped_color(2), taped_color(3), taped_color(4)};
+
 // The launch chains of a taped solve or of one of its sweeps: at most two (image groups on two streams)
-void taped_chains(bpltv_t* h, const bpltv_params& p, const WeightedPlan& pl, ChainSolve* j) {
-    j->nimg = h->O; j->niter = p.maxiter; j->T = pl.T;
-    j->chains = plan_chains(p.reserved[1], pl.nTi * pl.nTj * h->O, h->ncu, h->O, 2);
+// (channels > 1: the images of a chain are colour images, [lo, hi) the planes lo * channels ... hi * channels, so that no chain
+// splits one)
+void taped_chains(bpltv_t* h, const bpltv_params& p, const WeightedPlan& pl, ChainSolve* j, int channels = 1) {
+    const int nimg = h->O / channels;
+    j->nimg = nimg; j->niter = p.maxiter; j->T = pl.T;
+    j->chains = plan_chains(p.reserved[1], pl.nTi * pl.nTj * nimg, h->ncu, nimg, 2);
     j->serial = (p.reserved[2] & 1) != 0; j->helper_thread = !(p.reserved[2] & 8);
 }
 
@@ -3658,10 +3743,14 @@ void segment_launches(int K, int C, int T, bool stagger, F fn) {
 // With a checkpoint spacing C (option "tape_checkpoint") the same launches, cut at the segment boundaries, run the no-tape
 // instantiation; the launch that ends segment s - 1 writes its state into slot s of the buffer instead of a state set, and
 // the next one reads it from there (slot 0: x = f, y = 0).  The result ends in state set 0.
+// !taped (bpltv_color_denoise): the same launches of the no-tape instantiation and nothing else: no tape is written, grown or
+// invalidated, and the checkpoint option does not apply.
 int taped_denoise(bpltv_t* h, const TapedModel& m, const double* w, int wo, const double* alpha, bool dev, int am, int an,
-                  const bpltv_params* pp, double* d_tape_user, double* u_out, bool each) {
-    const std::string name = std::string(m.denoise) + (each ? "_each" : "") + (dev ? "_device" : "");
+                  const bpltv_params* pp, double* d_tape_user, double* u_out, bool each, bool taped = true) {
+    const std::string name = taped ? std::string(m.denoise) + (each ? "_each" : "") + (dev ? "_device" : "")
+                                   : std::string(dev ? "bpltv_color_denoise_device" : "bpltv_color_denoise");
     const char* who = name.c_str();
+    const int ch = m.channels ? m.channels : 1;
     const bool sr = m.slices == 3;
     Tape& tape = h->*m.tape;
     WallTimer wt;
@@ -3681,11 +3770,11 @@ int taped_denoise(bpltv_t* h, const TapedModel& m, const double* w, int wo, cons
     double wmin = 0.0;
     int rc = m.weighted ? check_weight(h, who, w, dev, nw, &wmin) : (int)BPLTV_OK;
     if (rc) return rc;
-    const int K = p.maxiter, C = tape_spacing(m, K, h->opt.tape_checkpoint), np = m.nplanes;
+    const int K = p.maxiter, C = taped ? tape_spacing(m, K, h->opt.tape_checkpoint) : 0, np = m.nplanes;
     const size_t tot = h->tot;
     const size_t need = C ? (size_t)np * tape_segments(K, C) * tot : (size_t)m.tape_planes * K * tot;
     double* grown = nullptr;
-    if (!d_tape_user) {
+    if (!d_tape_user && taped) {
         const hipError_t e = tape.grow(need, &grown);
         if (e != hipSuccess) {
             (void)hipGetLastError();
@@ -3704,7 +3793,7 @@ int taped_denoise(bpltv_t* h, const TapedModel& m, const double* w, int wo, cons
         return rc;
     }
     tape.install(grown, need);
-    if (!d_tape_user) tape.valid = false;   // about to be overwritten
+    if (!d_tape_user && taped) tape.valid = false;   // about to be overwritten
     if (m.weighted) {
         HIPCHK(h, hipMemcpyAsync(h->d_w, w, nw * sizeof(double), dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, h->stream));
         h->w_wo = wo;
@@ -3715,17 +3804,18 @@ int taped_denoise(bpltv_t* h, const TapedModel& m, const double* w, int wo, cons
     rc = get_table(h, p, &d_tab, m.L2, 0, m.weighted ? h->w_min : 1.0);
     if (rc) return rc;
     const bool amap = (h->last_am == h->M && h->last_an == h->N) && !(h->M == 1 && h->N == 1);
-    h->st.tile_iters = pl.T; h->st.tiles = pl.nTi * pl.nTj * h->O; h->st.region_i = m.region; h->st.region_j = m.region; h->st.pdhg_variant = 0;
-    double* const buffer = d_tape_user ? d_tape_user : tape.d;   // the tape, or the checkpoints
+    h->st.tile_iters = pl.T; h->st.tiles = pl.nTi * pl.nTj * (h->O / ch); h->st.region_i = m.region; h->st.region_j = m.region; h->st.pdhg_variant = 0;
+    double* const buffer = !taped ? nullptr : (d_tape_user ? d_tape_user : tape.d);   // the tape, or the checkpoints
     TapedFwd x{h, pl, d_tab, C ? nullptr : buffer, {}, h->d_alpha, h->last_am, h->last_an, h->alpha_istride, m.weighted ? h->d_w : nullptr, h->w_wo};
+    x.channels = ch;
     for (int s = 0; s < 2; ++s)
         for (int c = 0; c < np; ++c) x.S[s][c] = sr ? h->d_sr[s][c] : h->d_state[s][c];
     ChainSolve j;
     j.model = m.graphs; j.nplanes = np; j.state0 = sr ? h->d_sr[0] : h->d_state[0];
-    taped_chains(h, p, pl, &j);
-    j.bytes_per_px_iter = C ? (amap ? m.plain_bytes_map : m.plain_bytes) : (amap ? m.bytes_map : m.bytes);
+    taped_chains(h, p, pl, &j, ch);
+    j.bytes_per_px_iter = (C || !taped) ? (amap ? m.plain_bytes_map : m.plain_bytes) : (amap ? m.bytes_map : m.bytes);
     // (istride: a per-image solve uploads into d_alpha like a shared one, and must not replay its graph, nor the reverse)
-    j.key = GraphKey{K, pl.T, m.fwd_variant, h->last_am, h->last_an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)buffer, (const void*)d_tab, 0,
+    j.key = GraphKey{K, pl.T, m.fwd_variant + (taped ? 0 : 2), h->last_am, h->last_an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)buffer, (const void*)d_tab, 0,
                      (const void*)h->d_alpha, m.weighted ? 0 : h->alpha_istride, m.weighted ? h->w_wo : 0, C, nullptr, 0};
     if (!C) {
         j.enqueue = launch_loop(pl.T, [&](const LaunchStep& s) { m.launch_fwd(x, s); });
@@ -3768,6 +3858,7 @@ int taped_denoise(bpltv_t* h, const TapedModel& m, const double* w, int wo, cons
     int buf = 0;
     rc = run_chains(h, p, j, &buf);
     if (rc) return rc;
+    h->st.algorithmic_bytes *= ch;   // (the driver counted colour images)
     if (sr) {   // committed like bpltv_sumregs_denoise's
         h->sr_result_buf = buf;
         h->sr_has_result = true;
@@ -3777,7 +3868,11 @@ int taped_denoise(bpltv_t* h, const TapedModel& m, const double* w, int wo, cons
     }
     h->last_is_sr = sr;
     h->last_weighted = m.weighted;
-    if (!d_tape_user) tape.record(p, am, an, each, m.weighted ? wo : 0, wmin, C);
+    h->last_channels = m.channels;
+    if (!d_tape_user && taped) {
+        tape.record(p, am, an, each, m.weighted ? wo : 0, wmin, C);
+        tape.channels = m.channels;
+    }
     if (u_out) {
         HIPCHK(h, hipMemcpyAsync(u_out, sr ? h->d_sr[buf][0] : h->d_state[buf][0], h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3849,6 +3944,8 @@ int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const 
         if (tape.each != each)
             return set_err(h, BPLTV_E_ARG, "%s: the handle's tape was recorded with one %s (%s%s)", who,
                            tape.each ? "parameter block per image" : "shared parameter", m.denoise, tape.each ? "_each" : "");
+        if (tape.channels != m.channels)
+            return set_err(h, BPLTV_E_ARG, "%s: the handle's %stape was recorded with channels = %d, this call has %d", who, m.tape_kind, tape.channels, m.channels);
         if (tape.spacing != C)
             return set_err(h, BPLTV_E_ARG, "%s: the handle's %stape was recorded with checkpoint spacing %d (0: the full tape), option tape_checkpoint gives %d",
                            who, m.tape_kind, tape.spacing, C);
@@ -3894,6 +3991,7 @@ int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const 
     }
     TapedRev x{h, pl, d_tab, d_tape_user ? d_tape_user : tape.d, &g, {}, d_ws + (size_t)2 * np * tot, d_ws + (size_t)(2 * np + 1) * tot,
                d_ws + (size_t)(2 * np + 1 + m.slices) * tot, d_grad_w ? h->d_unr_gw : nullptr, p.maxiter};
+    x.channels = m.channels ? m.channels : 1;
     for (int s = 0; s < 2; ++s)
         for (int c = 0; c < np; ++c) x.S[s][c] = d_ws + (size_t)(np * s + c) * tot;
     const bpltv_stats_t kept = h->st;
@@ -3901,11 +3999,12 @@ int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const 
     HIPCHK(h, hipMemcpyAsync(x.g0, d_gu, tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     ChainSolve j;
     j.model = m.graphs; j.nplanes = np; j.state0 = x.S[0];
-    taped_chains(h, p, pl, &j);
+    taped_chains(h, p, pl, &j, x.channels);
     j.bytes_per_px_iter = 0.0;   // (the driver's solve statistics are not this call's: `kept` goes back below)
     j.key = GraphKey{p.maxiter, pl.T, m.rev_variant + (x.gw ? 1 : 0), am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)x.tape, (const void*)d_tab, 0,
                      (const void*)g.alpha, m.weighted ? 0 : g.astride, m.weighted ? wo : 0, C, C ? (const void*)h->d_seg : nullptr, C ? plf.T : 0};
     TapedFwd xf{h, plf, d_tab, h->d_seg, {}, g.alpha, g.am, g.an, g.astride, g.w, g.wo};   // the recompute of a segment
+    xf.channels = x.channels;
     if (!C) {
         j.enqueue = launch_loop(pl.T, [&](const LaunchStep& s) { m.launch_rev(x, s); });
     } else {
@@ -4210,7 +4309,7 @@ int bpltv_destroy(bpltv_t* h) {
                     h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres, h->d_w, h->d_wst, h->d_unr, h->d_ujv, h->d_wjv, h->d_unr_gw, h->d_srunr, h->d_seg};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
-    for (Tape* t : {&h->tape, &h->wtape, &h->srtape}) t->release();
+    for (Tape* t : {&h->tape, &h->wtape, &h->srtape, &h->ctape}) t->release();
     for (int s = 0; s < 2; ++s)
         for (int c = 0; c < 3; ++c) {
             if (h->d_state[s][c]) (void)hipFree(h->d_state[s][c]);
@@ -4249,7 +4348,7 @@ static int set_data_impl(bpltv_t* h, const double* ubar, const double* f, hipMem
     h->has_data = true;
     h->has_result = false;
     h->f32_f_valid = false;
-    for (Tape* t : {&h->tape, &h->wtape, &h->srtape})   // checkpoints are states of the solve on the old f: the sweep would recompute on the new one
+    for (Tape* t : {&h->tape, &h->wtape, &h->srtape, &h->ctape})   // checkpoints are states of the solve on the old f: the sweep would recompute on the new one
         if (t->spacing) t->valid = false;
     return BPLTV_OK;
 }
@@ -4592,6 +4691,59 @@ int bpltv_sumregs_unrolled_vjp_each_device(bpltv_t* h, const double* d_tape, con
     return taped_vjp_entry(h, kTapedSr, "bpltv_sumregs_unrolled_vjp_each_device", true, d_tape, nullptr, 1, d_alphas, am, an, pp, d_gu, d_grad_f, d_grad_alphas, nullptr, true);
 }
 
+// The channel-coupled model: channels picks the instance; a colour image is `channels` consecutive planes
+static const TapedModel* color_model(bpltv_t* h, const char* what, int channels, int* rc) {
+    *rc = BPLTV_OK;
+    if (channels < 1 || channels > COLOR_MAX_C) {
+        *rc = set_err(h, BPLTV_E_ARG, "%s: channels = %d (1 ... %d)", what, channels, COLOR_MAX_C);
+        return nullptr;
+    }
+    if (!h->multi && h->O % channels != 0) {   // (a forwarding handle leaves it to its shard)
+        *rc = set_err(h, BPLTV_E_ARG, "%s: channels = %d does not divide the handle's %d planes", what, channels, h->O);
+        return nullptr;
+    }
+    return &kTapedColor[channels - 1];
+}
+static int color_denoise_entry(bpltv_t* h, const char* what, int channels, const double* alpha, bool dev, int am, int an, const bpltv_params* pp,
+                               double* d_tape, double* u_out, bool taped) {
+    if (!h) return BPLTV_E_ARG;
+    int rc = BPLTV_OK;
+    const TapedModel* m = color_model(h, what, channels, &rc);
+    if (!m) return rc;
+    if (h->multi)
+        return weighted_multi(h, what, true, [&](bpltv_t* c) { return color_denoise_entry(c, what, channels, alpha, dev, am, an, pp, d_tape, u_out, taped); },
+                              m->multi_name);
+    return taped_denoise(h, *m, nullptr, 1, alpha, dev, am, an, pp, d_tape, u_out, false, taped);
+}
+int bpltv_color_denoise(bpltv_t* h, int channels, const double* alpha, int am, int an, const bpltv_params* pp, double* u_out) {
+    return color_denoise_entry(h, "bpltv_color_denoise", channels, alpha, false, am, an, pp, nullptr, u_out, false);
+}
+int bpltv_color_denoise_device(bpltv_t* h, int channels, const double* d_alpha, int am, int an, const bpltv_params* pp) {
+    return color_denoise_entry(h, "bpltv_color_denoise_device", channels, d_alpha, true, am, an, pp, nullptr, nullptr, false);
+}
+int bpltv_color_unrolled_denoise(bpltv_t* h, int channels, const double* alpha, int am, int an, const bpltv_params* pp, double* u_out) {
+    return color_denoise_entry(h, "bpltv_color_unrolled_denoise", channels, alpha, false, am, an, pp, nullptr, u_out, true);
+}
+int bpltv_color_unrolled_denoise_device(bpltv_t* h, int channels, const double* d_alpha, int am, int an, const bpltv_params* pp, double* d_tape) {
+    return color_denoise_entry(h, "bpltv_color_unrolled_denoise_device", channels, d_alpha, true, am, an, pp, d_tape, nullptr, true);
+}
+int bpltv_color_unrolled_vjp(bpltv_t* h, int channels, const double* alpha, int am, int an, const bpltv_params* pp, const double* gu, double* grad_f_out,
+                             double* grad_alpha_out) {
+    if (!h) return BPLTV_E_ARG;
+    int rc = BPLTV_OK;
+    const TapedModel* m = color_model(h, "bpltv_color_unrolled_vjp", channels, &rc);
+    if (!m) return rc;
+    return taped_vjp_entry(h, *m, "bpltv_color_unrolled_vjp", false, nullptr, nullptr, 1, alpha, am, an, pp, gu, grad_f_out, grad_alpha_out, nullptr, false);
+}
+int bpltv_color_unrolled_vjp_device(bpltv_t* h, int channels, const double* d_tape, const double* d_alpha, int am, int an, const bpltv_params* pp,
+                                    const double* d_gu, double* d_grad_f, double* d_grad_alpha) {
+    if (!h) return BPLTV_E_ARG;
+    int rc = BPLTV_OK;
+    const TapedModel* m = color_model(h, "bpltv_color_unrolled_vjp_device", channels, &rc);
+    if (!m) return rc;
+    return taped_vjp_entry(h, *m, "bpltv_color_unrolled_vjp_device", true, d_tape, nullptr, 1, d_alpha, am, an, pp, d_gu, d_grad_f, d_grad_alpha, nullptr, false);
+}
+
 int bpltv_weighted_unrolled_tape_doubles(bpltv_t* h, const bpltv_params* pp, unsigned long long* n_out) {
     return tape_doubles_entry(h, kTapedWeighted, "bpltv_weighted_unrolled_tape_doubles", pp, n_out);
 }
@@ -4787,6 +4939,8 @@ int bpltv_duality_gap(bpltv_t* h, double* gap_out) {
     HIPCHK(h, hipSetDevice(h->device));
     double gmax = 0.0;
     const bool sr = h->last_is_sr;
+    if (!sr && h->last_channels)
+        return set_err(h, BPLTV_E_UNSUPPORTED, "duality gap of a channel-coupled solve (channels = %d): the gap of the coupled model is not implemented", h->last_channels);
     const Model model = sr ? MODEL_SR : (h->last_weighted ? MODEL_W : MODEL_TV);
     if (model == MODEL_W && !(h->w_min > 0.0))   // gamma = min w > 0: the weighted model's dual objective divides by w
         return set_err(h, BPLTV_E_UNSUPPORTED, "duality gap of a weighted solve: the dual objective divides by w, every entry must be > 0 (min = %g)", h->w_min);

@@ -1,0 +1,363 @@
+// color_tile_kernels.hpp -- channel-coupled (vectorial) TV on a 32 x 32 region: tv_tile_kernel<0, TAPE, 0> and
+// tv_reverse_tile_kernel<0> (tv_tile_kernels.hpp) with the projection taken over the C consecutive planes of a colour image.
+// The reference has no counterpart: its datasets are grey.  DESIGN.md section 4.12.
+//
+//     min_u  1/2 sum_c |u_c - f_c|^2  +  sum_pixels alpha * sqrt( sum_c |(grad u_c)|^2 )
+//
+// Layout: a handle of O = B*C planes; colour image b owns the planes b*C ... b*C + C-1.  alpha is shared by the batch and by
+// the channels (scalar, patch or map).
+//
+// Forward, per plane c of a colour image, iteration k = 0 ... K-1 from x = f, y = 0: div, t, x_new, xbar and
+// z = fma(sigma_k, G xbar, y) are tv_tile_kernel's !WEIGHTED forms, operation for operation.  Then, per pixel of the colour
+// image, over its planes in channel order:
+//     n2 = z1_0*z1_0;  n2 = fma(z2_0, z2_0, n2);   c = 1 ... C-1:  n2 = fma(z1_c, z1_c, n2);  n2 = fma(z2_c, z2_c, n2)
+//     out = n2 > alpha^2;   y_c = out ? z_c * (alpha*rsqrt_nr(n2)) : z_c   for every c
+// With C = 1 this is tv_tile_kernel's expression; channels = 1 runs the TV kernels themselves.
+// TAPE: z1, z2 of every plane before the projection, in the TV tape's layout, [k][component][plane][pixel].
+//
+// Reverse, k = K-1 ... 0, from gx = dL/du, gy = gf = ga = 0: n2 and out as above on the taped values; where out:
+//     q = rsqrt_nr(n2);  e_c = z_c*q;  dot = (e1_0*gy1_0 + e2_0*gy2_0), then dot += (e1_c*gy1_c + e2_c*gy2_c), c = 1 ... C-1
+//     gz_c = (alpha*q)*(gy_c - e_c*dot);  ga += dot       (once per pixel of the colour image)
+// elsewhere gz = gy.  The rest is tv_reverse_tile_kernel<0>'s tail, per plane.  ga is written into the colour image's
+// channel-0 plane of the driver's ga planes and +0.0 into the others, so that the TV reduction sums colour images in image
+// order.
+//
+// One workgroup per (tile, colour image): 1024 threads, one pixel per thread with its C channels in registers.  LDS: C sets
+// of the TV planes.  Two barriers per iteration, every load first, the step rows in LDS, spent halo waves keep the barriers
+// company only, agent-scope write-through stores of the core: tv_tile_kernel's structure.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include "tv_tile_kernels.hpp"
+
+namespace bpltv {
+
+constexpr int COLOR_MAX_C = 4;
+// Most reverse iterations per launch: 2*C*T taped doubles sit in registers beside 5*C doubles of sweep state, in the 128
+// VGPRs a lane of a 1024-thread workgroup has.  The deepest that leaves no instantiation with scratch: 96 / 108 / 118 VGPRs
+// (4 / 3 / 2 take 80 / 96 / 102 and a sweep 14 % longer).
+constexpr int color_rev_t(int C) { return C <= 1 ? TV_REV_T : (C == 2 ? 6 : (C == 3 ? 4 : 3)); }
+constexpr size_t color_lds_bytes(int C) { return (size_t)C * tv_lds_bytes(); }
+
+// TvTileArgs with: img0 / grid.z count colour images; in, out, f, tape address the planes img*C + c; w, df, dw, dalpha,
+// wstride and istride are not read.
+template <int C, bool TAPE>
+__global__ __launch_bounds__(TV_R * TV_R) void color_tile_kernel(TvTileArgs A) {
+    static_assert(C >= 2 && C <= COLOR_MAX_C, "channels = 1 is tv_tile_kernel");
+    constexpr int RI = TV_R, RJ = TV_R, S1 = RI + 1;
+    constexpr int PLANES = RJ * S1 + (RJ + 1) * RI + RJ * RI + RI + 1;   // doubles of one channel's planes (pdhg_lds_bytes)
+    static_assert(PLANES * sizeof(double) == tv_lds_bytes(), "the plane layout is pdhg_lds_bytes'");
+    extern __shared__ __attribute__((aligned(16))) unsigned char tv_smem[];
+    double* sy1 = reinterpret_cast<double*>(tv_smem);   // [RJ][S1]               channel c: + c * PLANES
+    double* sy2 = sy1 + RJ * S1;                        // [RJ+1][RI]
+    double* sxb = sy2 + (RJ + 1) * RI;                  // [RJ][RI] + RI + 1
+    __shared__ __attribute__((aligned(16))) double srow[PDHG_MAX_T * TAB_STRIDE];
+
+    const int tid = threadIdx.x;
+    const int li = tid % RI, lj = tid / RI;
+    const int ta = (int)blockIdx.x, tb = (int)blockIdx.y, img = A.img0 + (int)blockIdx.z;
+    const int M = A.M, N = A.N;
+    int oi, ci0, ci1, oj, cj0, cj1;
+    tile_span(ta, M, RI, A.halo, oi, ci0, ci1);
+    tile_span(tb, N, RJ, A.halo, oj, cj0, cj1);
+    const size_t npx = (size_t)M * N;
+    const size_t base = (size_t)img * C * npx;   // channel 0 of the colour image
+    const int amode = (A.am == 1 && A.an == 1) ? 0 : ((A.am == M && A.an == N) ? 2 : 1);
+    const bool first = A.first != 0;
+
+    // ---- prologue: every global load is issued before the first use.  Out-of-image pixels read a clamped in-image
+    // address and are zeroed afterwards (they stay 0).
+    const int gi = min(oi + li, M - 1), gj = min(oj + lj, N - 1);
+    const size_t pix = gi + (size_t)M * gj;
+    size_t ai = 0;
+    if (amode == 2) {
+        ai = pix;
+    } else if (amode == 1) {
+        const unsigned pa = ((unsigned)gi * (unsigned)A.am) / (unsigned)M;
+        const unsigned pb = ((unsigned)gj * (unsigned)A.an) / (unsigned)N;
+        ai = pa + (size_t)A.am * pb;
+    }
+    double x[C], y1[C], y2[C], f[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        x[c] = 0.0; y1[c] = 0.0; y2[c] = 0.0;
+        if (!first) {
+            x[c] = A.in[0][base + c * npx + pix];
+            y1[c] = A.in[1][base + c * npx + pix];
+            y2[c] = A.in[2][base + c * npx + pix];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) f[c] = A.f[base + c * npx + pix];
+    double al = A.alpha[ai];
+    const bool row_word = tid < A.nit * TAB_STRIDE;   // nit <= PDHG_MAX_T: the host checks
+    double row_w = 0.0;
+    if (row_word) row_w = A.tab[(size_t)TAB_STRIDE * A.it0 + tid];
+    const bool in = (oi + li < M) && (oj + lj < N);
+    if (!in) al = 0.0;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        if (first) { x[c] = f[c]; y1[c] = 0.0; y2[c] = 0.0; }
+        if (!in) { f[c] = 0.0; x[c] = 0.0; y1[c] = 0.0; y2[c] = 0.0; }
+        sy1[c * PLANES + lj * S1 + li + 1] = y1[c];
+        sy2[c * PLANES + (lj + 1) * RI + li] = y2[c];
+        if (tid < RJ) sy1[c * PLANES + tid * S1] = 0.0;
+        if (tid < RI) sy2[c * PLANES + tid] = 0.0;
+        if (tid < RI + 1) sxb[c * PLANES + RI * RJ + tid] = 0.0;
+    }
+    if (row_word) srow[tid] = row_w;
+    __syncthreads();
+
+    const int nit = A.nit;
+    // Neumann border: at the last image row / column the "neighbour" is the pixel's own xbar cell (difference +0)
+    const int l = lj * RI + li;
+    const int n1 = l + (((oi + li) < M - 1) ? 1 : 0);
+    const int n2 = l + (((oj + lj) < N - 1) ? RI : 0);
+    const int qi = oi + li, qj = oj + lj;
+    const bool core = qi >= ci0 && qi < ci1 && qj >= cj0 && qj < cj1;
+    const size_t idx = base + qi + (size_t)M * qj;   // channel 0; used by core pixels only
+    double* tz = TAPE ? A.tape + (size_t)2 * A.plane * (A.it0 - A.tk0) + idx : nullptr;
+    // halo rows do not need all the iterations (tv_tile_kernel): a wave owns two adjacent rows; core rows run them all
+    int my_nit = nit;
+    if (N > RJ) {
+        const int r0 = (tid & ~63) / RI, r1 = min((tid | 63) / RI, RJ - 1);
+        if (oj > 0) my_nit = min(my_nit, r1);
+        if (oj + RJ < N) my_nit = min(my_nit, RJ - r0);
+    }
+    const int loop_nit = __builtin_amdgcn_readfirstlane(my_nit);
+    double tau = srow[0], sigma = srow[1], omega = srow[2], r = srow[3], opw = srow[4];
+    for (int it = 0; it < loop_nit; ++it) {
+        // ---- primal step of every channel
+        double b[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const double y1m = sy1[c * PLANES + lj * S1 + li];
+            const double y2m = sy2[c * PLANES + lj * RI + li];
+            const double div = (y1m - y1[c]) + (y2m - y2[c]);
+            const double t = div - f[c];
+            const double xo = x[c];
+            const double xn = __builtin_fma(-tau, t, xo) * r;
+            b[c] = __builtin_fma(-omega, xo, opw * xn);
+            x[c] = xn;
+            sxb[c * PLANES + l] = b[c];
+        }
+        __syncthreads();
+        const double* nrow = srow + TAB_STRIDE * ((it + 1 < nit) ? it + 1 : it);
+        const double ntau = nrow[0], nsigma = nrow[1], nomega = nrow[2], nopw = nrow[4];
+        r = nrow[3];
+        // ---- dual step: z of every channel, then one projection for the pixel
+        double nn = 0.0;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const double d1 = sxb[c * PLANES + n1] - b[c];
+            const double d2 = sxb[c * PLANES + n2] - b[c];
+            y1[c] = __builtin_fma(sigma, d1, y1[c]);
+            y2[c] = __builtin_fma(sigma, d2, y2[c]);
+            if constexpr (TAPE) {
+                if (core) {   // the tape: the dual before the projection
+                    __hip_atomic_store(tz + c * npx, y1[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    __hip_atomic_store(tz + c * npx + A.plane, y2[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+            nn = (c == 0) ? y1[c] * y1[c] : __builtin_fma(y1[c], y1[c], nn);
+            nn = __builtin_fma(y2[c], y2[c], nn);
+        }
+        if constexpr (TAPE) tz += 2 * A.plane;
+        if (nn > al * al) {   // a wave whose pixels all lie inside the ball skips the rsqrt
+            const double v = al * rsqrt_nr(nn);
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                y1[c] = y1[c] * v;
+                y2[c] = y2[c] * v;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            sy1[c * PLANES + lj * S1 + li + 1] = y1[c];
+            sy2[c * PLANES + (lj + 1) * RI + li] = y2[c];
+        }
+        tau = ntau; sigma = nsigma; omega = nomega; opw = nopw;
+        __syncthreads();
+    }
+    for (int it = loop_nit; it < nit; ++it) {   // a spent halo wave: the two barriers of an iteration, nothing else
+        __syncthreads();
+        __syncthreads();
+    }
+
+    if (core) {
+        // write-through stores, as tv_tile_kernel: the next launch reads this state from other XCDs
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            __hip_atomic_store(&A.out[0][idx + c * npx], x[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&A.out[1][idx + c * npx], y1[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&A.out[2][idx + c * npx], y2[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// TvTileRevArgs with: img0 / grid.z count colour images; in, out, gf, tape address the planes img*C + c; ga: the colour
+// image's value in its channel-0 plane, +0.0 in the others; gw, f, w, wstride and istride are not read.  nit <= color_rev_t(C).
+template <int C>
+__global__ __launch_bounds__(TV_R * TV_R) void color_reverse_tile_kernel(TvTileRevArgs A) {
+    static_assert(C >= 2 && C <= COLOR_MAX_C, "channels = 1 is tv_reverse_tile_kernel");
+    constexpr int RI = TV_R, RJ = TV_R, S1 = RI + 1;
+    constexpr int PLANES = RJ * S1 + (RJ + 1) * RI + RJ * RI + RI + 1;
+    constexpr int T = color_rev_t(C);
+    extern __shared__ __attribute__((aligned(16))) unsigned char tv_smem[];
+    double* sg1 = reinterpret_cast<double*>(tv_smem);   // [RJ][S1]               channel c: + c * PLANES
+    double* sg2 = sg1 + RJ * S1;                        // [RJ+1][RI]
+    double* sxn = sg2 + (RJ + 1) * RI;                  // [RJ][RI] + RI + 1
+    __shared__ __attribute__((aligned(16))) double srow[T * TAB_STRIDE];
+
+    const int tid = threadIdx.x;
+    const int li = tid % RI, lj = tid / RI;
+    const int ta = (int)blockIdx.x, tb = (int)blockIdx.y, img = A.img0 + (int)blockIdx.z;
+    const int M = A.M, N = A.N;
+    int oi, ci0, ci1, oj, cj0, cj1;
+    tile_span(ta, M, RI, A.halo, oi, ci0, ci1);
+    tile_span(tb, N, RJ, A.halo, oj, cj0, cj1);
+    const size_t npx = (size_t)M * N;
+    const size_t base = (size_t)img * C * npx;
+    const int amode = (A.am == 1 && A.an == 1) ? 0 : ((A.am == M && A.an == N) ? 2 : 1);
+    const bool first = A.first != 0;
+    const int nit = A.nit;
+    const int klo = A.khi - nit + 1;
+
+    // ---- prologue: every global load, the launch's taped values included, is issued before the first use
+    const int gi = min(oi + li, M - 1), gj = min(oj + lj, N - 1);
+    const size_t pix = gi + (size_t)M * gj;
+    size_t ai = 0;
+    if (amode == 2) {
+        ai = pix;
+    } else if (amode == 1) {
+        const unsigned pa = ((unsigned)gi * (unsigned)A.am) / (unsigned)M;
+        const unsigned pb = ((unsigned)gj * (unsigned)A.an) / (unsigned)N;
+        ai = pa + (size_t)A.am * pb;
+    }
+    const int qi = oi + li, qj = oj + lj;
+    const bool in = (qi < M) && (qj < N);
+    const bool core = qi >= ci0 && qi < ci1 && qj >= cj0 && qj < cj1;
+    double gx[C], gy1[C], gy2[C], gf[C], ga = 0.0;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        gx[c] = A.in[0][base + c * npx + pix];
+        gy1[c] = 0.0; gy2[c] = 0.0; gf[c] = 0.0;
+        if (!first) {
+            gy1[c] = A.in[1][base + c * npx + pix];
+            gy2[c] = A.in[2][base + c * npx + pix];
+            if (core) gf[c] = A.gf[base + c * npx + pix];
+        }
+    }
+    if (!first && core) ga = A.ga[base + pix];
+    double al = A.alpha[ai];
+    double z1[C][T], z2[C][T];   // [c][s]: iteration khi - s
+    const double* tz = A.tape + (size_t)2 * A.plane * (A.khi - A.tk0) + base + pix;
+#pragma unroll
+    for (int s = 0; s < T; ++s) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            z1[c][s] = 0.0; z2[c][s] = 0.0;
+            if (s < nit) {
+                z1[c][s] = tz[c * npx];
+                z2[c][s] = tz[c * npx + A.plane];
+            }
+        }
+        tz -= 2 * A.plane;
+    }
+    const bool row_word = tid < nit * TAB_STRIDE;   // nit <= T: the host checks
+    double row_w = 0.0;
+    if (row_word) row_w = A.tab[(size_t)TAB_STRIDE * klo + tid];
+    if (!in) al = 0.0;
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        if (!in) { gx[c] = 0.0; gy1[c] = 0.0; gy2[c] = 0.0; }
+        if (tid < RJ) sg1[c * PLANES + tid * S1] = 0.0;
+        if (tid < RI) sg2[c * PLANES + tid] = 0.0;
+        if (tid < RI + 1) sxn[c * PLANES + RI * RJ + tid] = 0.0;
+    }
+    if (row_word) srow[tid] = row_w;
+    __syncthreads();
+
+    const int l = lj * RI + li;
+    const bool e1 = qi < M - 1, e2 = qj < N - 1;   // the pixel has a forward difference along i / j
+    const int n1 = l + (e1 ? 1 : 0);
+    const int n2 = l + (e2 ? RI : 0);
+    const double a2 = al * al;
+#pragma unroll
+    for (int s = 0; s < T; ++s) {
+        if (s < nit) {   // (uniform)
+            const double* row = srow + TAB_STRIDE * (nit - 1 - s);
+            const double tau = row[0], sigma = row[1], omega = row[2], cr = row[3], opw = row[4];
+            // ---- adjoint of the projection, on the taped duals of the pixel's channels (gy becomes gz)
+            double za[C], zb[C], nn = 0.0;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                za[c] = in ? z1[c][s] : 0.0;
+                zb[c] = in ? z2[c][s] : 0.0;
+                nn = (c == 0) ? za[c] * za[c] : __builtin_fma(za[c], za[c], nn);
+                nn = __builtin_fma(zb[c], zb[c], nn);
+            }
+            if (nn > a2) {
+                const double q = rsqrt_nr(nn);
+                double dot = 0.0;
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    za[c] = za[c] * q;
+                    zb[c] = zb[c] * q;
+                    const double d = za[c] * gy1[c] + zb[c] * gy2[c];
+                    dot = (c == 0) ? d : dot + d;
+                }
+                const double v = al * q;
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    gy1[c] = v * (gy1[c] - za[c] * dot);
+                    gy2[c] = v * (gy2[c] - zb[c] * dot);
+                }
+                ga += dot;
+            }
+            double m1[C], m2[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                m1[c] = e1 ? gy1[c] : 0.0;
+                m2[c] = e2 ? gy2[c] : 0.0;
+                sg1[c * PLANES + lj * S1 + li + 1] = m1[c];
+                sg2[c * PLANES + (lj + 1) * RI + li] = m2[c];
+            }
+            __syncthreads();
+            // ---- adjoint of the over-relaxation and the primal step, per channel
+            double gxb[C], gxn[C];
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const double gt = (sg1[c * PLANES + lj * S1 + li] - m1[c]) + (sg2[c * PLANES + lj * RI + li] - m2[c]);
+                gxb[c] = sigma * gt;
+                gxn[c] = gx[c] + opw * gxb[c];
+                sxn[c * PLANES + l] = gxn[c];
+            }
+            __syncthreads();
+            const double tc = tau * cr;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const double d1 = sxn[c * PLANES + n1] - gxn[c];
+                const double d2 = sxn[c * PLANES + n2] - gxn[c];
+                gf[c] += tc * gxn[c];
+                gy1[c] = gy1[c] - tc * d1;
+                gy2[c] = gy2[c] - tc * d2;
+                gx[c] = cr * gxn[c] - omega * gxb[c];
+            }
+        }
+    }
+
+    if (core) {
+        const size_t idx = base + qi + (size_t)M * qj;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            __hip_atomic_store(&A.out[0][idx + c * npx], gx[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&A.out[1][idx + c * npx], gy1[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&A.out[2][idx + c * npx], gy2[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&A.gf[idx + c * npx], gf[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&A.ga[idx + c * npx], c == 0 ? ga : 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+}  // namespace bpltv

@@ -499,6 +499,65 @@ class TVSolver:
                                                         C.c_void_p(grad_f_ptr or None),
                                                         C.c_void_p(grad_alpha_ptr or None)))
 
+    # -- channel-coupled TV for colour images (bpltv_color_*) ------------------------------------------------------
+    # The handle's O planes are O / channels colour images of `channels` consecutive planes; x is one parameter shared by the
+    # batch and the channels.  The tape has the TV tape's size: unrolled_tape_doubles.
+    def color_denoise(self, x, channels, fetch=True, **kw):
+        """Vectorial TV: the channels of a colour image share one projection per pixel (bpltv_color_denoise).  No tape, any
+        maxiter >= 1; u is bitwise color_unrolled_denoise's."""
+        a, am, an, _ = _alpha_arg(x)
+        p = self.params(**kw)
+        u = np.empty((self.O, self.N, self.M)) if fetch else None
+        self._check(self._lib.bpltv_color_denoise(self._h, int(channels), _ptr(a), am, an, C.byref(p), _ptr(u) if fetch else None))
+        return u
+
+    def color_denoise_device(self, channels, alpha_ptr, am=1, an=1, **kw):
+        """bpltv_color_denoise_device: the parameter resident in HBM, the result left there (u_device_ptr / copy_u_device)."""
+        p = self.params(**kw)
+        self._check(self._lib.bpltv_color_denoise_device(self._h, int(channels), C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p)))
+
+    def color_unrolled_denoise(self, x, channels, fetch=True, **kw):
+        """color_denoise that also records the tape of the iterations in the handle, for color_unrolled_vjp with the same
+        x, channels and params (bpltv_color_unrolled_denoise)."""
+        a, am, an, _ = _alpha_arg(x)
+        p = self._taped_params(kw)
+        u = np.empty((self.O, self.N, self.M)) if fetch else None
+        self._check(self._lib.bpltv_color_unrolled_denoise(self._h, int(channels), _ptr(a), am, an, C.byref(p),
+                                                           _ptr(u) if fetch else None))
+        return u
+
+    def color_unrolled_denoise_device(self, channels, alpha_ptr, am=1, an=1, tape_ptr=None, **kw):
+        """bpltv_color_unrolled_denoise_device: the parameter resident in HBM, the result left there; tape_ptr: a
+        caller-owned HBM buffer of unrolled_tape_doubles(**kw) doubles, or None / 0 for the handle's colour tape."""
+        p = self._taped_params(kw)
+        self._check(self._lib.bpltv_color_unrolled_denoise_device(self._h, int(channels), C.c_void_p(alpha_ptr), int(am), int(an),
+                                                                  C.byref(p), C.c_void_p(tape_ptr or None)))
+
+    def color_unrolled_vjp(self, x, channels, gu, want_f=True, want_alpha=True, **kw):
+        """Vector-Jacobian product of the maxiter-step map u = color_unrolled_denoise(x, channels) for the cotangent gu, by
+        a reverse sweep over the handle's colour tape (bpltv_color_unrolled_vjp): (grad_f, grad_x), as unrolled_vjp."""
+        if not (want_f or want_alpha):
+            raise ValueError("color_unrolled_vjp: want_f and want_alpha are both False")
+        a, am, an, scalar = _alpha_arg(x)
+        p = self._taped_params(kw)
+        gu = self._batch(gu, "gu")
+        gf = np.empty((self.O, self.N, self.M)) if want_f else None
+        ga = np.empty(am * an) if want_alpha else None
+        self._check(self._lib.bpltv_color_unrolled_vjp(self._h, int(channels), _ptr(a), am, an, C.byref(p), _ptr(gu),
+                                                       _ptr(gf) if want_f else None, _ptr(ga) if want_alpha else None))
+        if ga is not None:
+            ga = float(ga[0]) if scalar else ga.reshape(an, am)
+        return gf, ga
+
+    def color_unrolled_vjp_device(self, channels, tape_ptr, alpha_ptr, am, an, gu_ptr, grad_f_ptr, grad_alpha_ptr, **kw):
+        """bpltv_color_unrolled_vjp_device: the tape (None / 0: the handle's own), the parameter, gu and the outputs
+        resident in HBM (raw device pointers); either output pointer may be 0 / None, not both."""
+        p = self._taped_params(kw)
+        self._check(self._lib.bpltv_color_unrolled_vjp_device(self._h, int(channels), C.c_void_p(tape_ptr or None),
+                                                              C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p),
+                                                              C.c_void_p(gu_ptr), C.c_void_p(grad_f_ptr or None),
+                                                              C.c_void_p(grad_alpha_ptr or None)))
+
     # -- reverse mode through the weighted iterations (bpltv_weighted_unrolled_*) --------------------------------
     def weighted_unrolled_tape_doubles(self, **kw):
         """Doubles of the tape a weighted unrolled solve with these params records: 3 * maxiter * M*N*O."""

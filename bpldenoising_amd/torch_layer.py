@@ -87,6 +87,15 @@ pass allocates as a torch tensor): no active-set threshold, no factorisation, ze
 SumRegsDenoiseUnrolled(alpha, maxiter=...) is the module with a learnable parameter.  No jvp: forward_mode=True raises a
 ValueError that names the implicit sumregs_denoise(..., forward_mode=True).
 
+    u = tv_denoise_color_unrolled(f, alpha, maxiter=50)          # colour images: channel-coupled TV (bpltv_color_unrolled_*)
+
+f is (B, C, H, W) or (C, H, W) with 1 <= C <= 4, alpha one 0-dim, (pH, pW) or (H, W) parameter for the batch and the channels.
+The model is vectorial TV, 0.5 sum_c |u_c - f_c|^2 + sum alpha sqrt(sum_c |grad u_c|^2): every pixel projects the duals of
+its channels onto one ball, so the channels share their edges (reshaping to B*C grey planes is channel-by-channel TV and
+gives colour fringes).  Forward is one taped solve into a tape tensor of its own (2 * maxiter * B*C*H*W doubles), backward
+one bpltv_color_unrolled_vjp_device call; C = 1 is tv_denoise_unrolled bit for bit.  TVDenoiseColorUnrolled(alpha,
+maxiter=50) is the module with a learnable parameter.  No jvp.  The other functions keep refusing 4-D input.
+
 Streams: the library runs its kernels on its own HIP streams and blocks until they are done.  Every call below first
 synchronises the tensors' current torch stream, so that the library reads inputs torch has finished writing; its
 outputs are complete when the call returns.
@@ -964,3 +973,97 @@ class SumRegsDenoiseUnrolled(torch.nn.Module):
 
     def forward(self, f):
         return sumregs_denoise_unrolled(f, self.alpha, **self.solver_kw)
+
+
+# ---- channel-coupled TV for colour images (TVSolver.color_unrolled_*): the planes of a colour image share one projection ----
+def _check_args_color(f, alpha):
+    """(B, C, H, W, am, an) of a valid (f, alpha) pair of tv_denoise_color_unrolled; TypeError / ValueError before any
+    library call."""
+    name = "tv_denoise_color_unrolled"
+    if not isinstance(f, torch.Tensor) or not isinstance(alpha, torch.Tensor):
+        raise TypeError("%s: f and alpha must be torch tensors" % name)
+    if f.dtype != torch.float64 or alpha.dtype != torch.float64:
+        raise TypeError("%s: f and alpha must be float64 (got %s, %s)" % (name, f.dtype, alpha.dtype))
+    if f.dim() not in (3, 4) or f.numel() == 0:
+        raise ValueError("%s: f must have shape (B, C, H, W) or (C, H, W), got %s" % (name, tuple(f.shape)))
+    C, H, W = f.shape[-3], f.shape[-2], f.shape[-1]
+    B = f.shape[0] if f.dim() == 4 else 1
+    if not 1 <= C <= 4:
+        raise ValueError("%s: f has %d channels (1 ... 4)" % (name, C))
+    shape = tuple(alpha.shape)
+    if shape == ():
+        am = an = 1
+    elif len(shape) == 2 and 1 <= shape[0] <= H and 1 <= shape[1] <= W:
+        an, am = shape
+    else:
+        raise ValueError("%s: alpha must be 0-dim, (pH, pW) with pH <= %d, pW <= %d, or (%d, %d); got %s"
+                         % (name, H, W, H, W, shape))
+    if alpha.device != f.device:
+        raise ValueError("%s: alpha is on %s, f on %s" % (name, alpha.device, f.device))
+    if f.device.type != "cuda":
+        raise ValueError("%s: f must be on a ROCm device, got %s" % (name, f.device))
+    return B, C, H, W, am, an
+
+
+class TVDenoiseColorUnrolledFunction(torch.autograd.Function):
+    """autograd.Function of tv_denoise_color_unrolled (below); apply(f, alpha, solver_kw).  No jvp."""
+
+    @staticmethod
+    def forward(ctx, f, alpha, solver_kw):
+        B, C, N, M, am, an = _check_args_color(f, alpha)
+        index = f.device.index if f.device.index is not None else torch.cuda.current_device()
+        s = _solver(index, M, N, B * C)
+        fc = f.detach().contiguous()   # (B, C, H, W): colour image b owns the planes b*C ... b*C + C-1
+        ac = alpha.detach().contiguous()
+        u = torch.empty_like(fc)
+        # the tape is this call's own: a second forward pass on the handle before backward does not overwrite it
+        tape = torch.empty(s.unrolled_tape_doubles(**solver_kw), dtype=torch.float64, device=f.device)
+        _sync(f.device)
+        s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
+        s.color_unrolled_denoise_device(C, ac.data_ptr(), am, an, tape_ptr=tape.data_ptr(), **solver_kw)
+        s.copy_u_device(u.data_ptr())
+        ctx.save_for_backward(tape, ac, *_checkpoint_f(solver_kw, fc))
+        ctx.solver, ctx.channels, ctx.am, ctx.an, ctx.solver_kw = s, C, am, an, dict(solver_kw)
+        return u
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gu):
+        need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (need_f or need_a):
+            return None, None, None
+        tape, alpha, *f = ctx.saved_tensors
+        gu = gu.to(dtype=torch.float64).contiguous()
+        gf = torch.empty_like(gu) if need_f else None
+        ga = torch.empty(ctx.am * ctx.an, dtype=torch.float64, device=gu.device) if need_a else None
+        _sync(gu.device)
+        _reinstall(ctx.solver, f)
+        ctx.solver.color_unrolled_vjp_device(ctx.channels, tape.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(),
+                                             gf.data_ptr() if need_f else None, ga.data_ptr() if need_a else None,
+                                             **ctx.solver_kw)
+        return gf, (ga.reshape(alpha.shape) if need_a else None), None
+
+
+def tv_denoise_color_unrolled(f, alpha, maxiter=50, checkpoint_every=None, **solver_kw):
+    """Vectorial TV of colour images by exactly maxiter PDHG iterations: min_u 1/2 sum_c |u_c - f_c|^2 + sum_pixels alpha *
+    sqrt(sum_c |grad u_c|^2) -- the channels of an image share one projection per pixel, so an edge is found in all of them
+    at once (TVSolver.color_unrolled_denoise_device).  Differentiable in f and alpha through the iterations
+    (TVSolver.color_unrolled_vjp_device), as tv_denoise_unrolled.
+    f: (B, C, H, W) or (C, H, W), float64, on a ROCm device, 1 <= C <= 4; alpha, shared by the batch and the channels: 0-dim,
+    (pH, pW) or (H, W).  checkpoint_every, solver_kw: as tv_denoise_unrolled's.  Reverse mode only."""
+    return TVDenoiseColorUnrolledFunction.apply(f, alpha, _with_checkpoint(dict(solver_kw, maxiter=int(maxiter)), checkpoint_every))
+
+
+class TVDenoiseColorUnrolled(torch.nn.Module):
+    """tv_denoise_color_unrolled behind a learnable scalar, patch parameter or pixel map.  Move it to the device of its inputs
+    with .to(device)."""
+
+    def __init__(self, alpha, maxiter=50, checkpoint_every=None, **solver_kw):
+        super().__init__()
+        self.alpha = torch.nn.Parameter(torch.as_tensor(alpha, dtype=torch.float64).clone())
+        self.maxiter = int(maxiter)
+        self.checkpoint_every = checkpoint_every
+        self.solver_kw = dict(solver_kw)
+
+    def forward(self, f):
+        return tv_denoise_color_unrolled(f, self.alpha, maxiter=self.maxiter, checkpoint_every=self.checkpoint_every, **self.solver_kw)

@@ -139,7 +139,8 @@ typedef struct bpltv_stats {
                                   8 tangent sweep through the iterations (bpltv_unrolled_jvp),
                                   9 reverse sweep over the taped weighted iterations (bpltv_weighted_unrolled_vjp),
                                   10 reverse sweep over the taped sum-of-regularisers iterations (bpltv_sumregs_unrolled_vjp),
-                                  11 tangent sweep through the weighted iterations (bpltv_weighted_unrolled_jvp) */
+                                  11 tangent sweep through the weighted iterations (bpltv_weighted_unrolled_jvp),
+                                  12 reverse sweep over the taped channel-coupled iterations (bpltv_color_unrolled_vjp) */
     int reg_gradient_used;     /* 1 if the last evaluate took the gradient_reg branch             */
     int ngpus;                 /* distinct devices behind this handle (1 for bpltv_create)        */
     int shards;                /* image shards (= worker threads) behind this handle              */
@@ -640,6 +641,47 @@ int bpltv_sumregs_unrolled_vjp_each(bpltv_t *h, const double *alphas, int am, in
 int bpltv_sumregs_unrolled_vjp_each_device(bpltv_t *h, const double *d_tape, const double *d_alphas, int am, int an,
                                            const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alphas);
 
+/* Channel-coupled (vectorial) TV for colour images:
+ *
+ *     min_u  1/2 sum_c |u_c - f_c|^2  +  sum_pixels alpha * sqrt( sum_c |(grad u_c)|^2 )
+ *
+ * The handle's O planes are O / channels colour images: image b owns the planes b*channels ... b*channels + channels-1 (a
+ * contiguous (B, C, H, W) array as it is).  alpha is one parameter shared by the batch and by the channels: scalar, patch or
+ * per-pixel map, with bpltv_denoise's shape rules and upsampling.  The iteration is bpltv_unrolled_denoise's per plane; only
+ * the projection couples the channels: every pixel of a colour image projects the 2*channels dual values of its planes onto
+ * one ball of radius alpha.  channels = 1 returns the bits of the bpltv_unrolled_* calls.
+ *
+ * The contract is bpltv_unrolled_denoise's and bpltv_unrolled_vjp's: params opnorm, tau0, sigma0, accel, maxiter, tile_iters,
+ * use_graph, reserved[1] and reserved[2] apply; rho, init and order must be 0 (BPLTV_E_UNSUPPORTED), maxiter < 1 is
+ * BPLTV_E_ARG, check_every and gap_tol are ignored; alpha is checked finite and >= 0 on the host or on the device; every
+ * rejection comes before anything of the handle changes.  In addition channels outside 1 ... 4, or not dividing O, is
+ * BPLTV_E_ARG.  The results do not depend on tile_iters, on the launch chains (a chain never splits a colour image), on
+ * use_graph, on the host or device form, or on whose tape it is.  dtype = 32 handles compute in Float64.  Multi-device handles
+ * over more than one shard: BPLTV_E_UNSUPPORTED; one shard is forwarded.
+ *
+ * bpltv_color_denoise: the recurrence without a tape, for any maxiter >= 1; u is bitwise the taped solve's.  It touches no tape.
+ * bpltv_color_unrolled_denoise: the same and the tape of the dual values before the projection, in the TV tape's layout and
+ * size: bpltv_unrolled_tape_doubles gives the doubles of a caller-owned d_tape (option "tape_checkpoint" included).  A NULL
+ * d_tape, and the host form always, use a fourth tape owned by the handle, which remembers channels.  It is never accepted by
+ * bpltv_unrolled_vjp, nor a TV tape by bpltv_color_unrolled_vjp, and each survives the other models' solves.
+ * Either solve becomes the handle's last one for bpltv_u_device / bpltv_copy_u_device.  bpltv_duality_gap after it returns
+ * BPLTV_E_UNSUPPORTED, until another model solves: the gap of the coupled model is not implemented.  stats: as
+ * bpltv_unrolled_denoise, with tiles counting workgroups (tiles times colour images) and bytes_per_px_iter per plane: 72
+ * (56 without a tape), plus 8 / channels with a map, which the planes of a colour image share; pdhg_variant = 0.
+ *
+ * bpltv_color_unrolled_vjp: the exact reverse mode through the iterations, as bpltv_unrolled_vjp: gu and grad_f_out have M*N*O
+ * doubles, grad_alpha_out am*an (summed over the colour images in image order, then as bpltv_unrolled_vjp reduces).  channels,
+ * alpha and params must be the solve's: BPLTV_E_ARG on the handle's tape otherwise.  Of the statistics only adjoint_ms and
+ * adjoint_method = 12 change. */
+int bpltv_color_denoise(bpltv_t *h, int channels, const double *alpha, int am, int an, const bpltv_params *p, double *u_out);
+int bpltv_color_denoise_device(bpltv_t *h, int channels, const double *d_alpha, int am, int an, const bpltv_params *p);
+int bpltv_color_unrolled_denoise(bpltv_t *h, int channels, const double *alpha, int am, int an, const bpltv_params *p, double *u_out);
+int bpltv_color_unrolled_denoise_device(bpltv_t *h, int channels, const double *d_alpha, int am, int an, const bpltv_params *p, double *d_tape);
+int bpltv_color_unrolled_vjp(bpltv_t *h, int channels, const double *alpha, int am, int an, const bpltv_params *p,
+                             const double *gu, double *grad_f_out, double *grad_alpha_out);
+int bpltv_color_unrolled_vjp_device(bpltv_t *h, int channels, const double *d_tape, const double *d_alpha, int am, int an,
+                                    const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alpha);
+
 /* Jacobian-vector product of u = denoise(f, alpha) (TV model): du for tangents (df, dalpha), defined as the linear map
  * whose transpose bpltv_vjp computes, in every branch -- <gu, du> = <grad_f(gu), df> + <grad_alpha(gu), dalpha> for any
  * gu -- so forward and reverse mode agree, also where the reference's linearisation is not the true one (reg = 1 with an
@@ -825,7 +867,7 @@ int bpltv_sumregs_sweep(bpltv_t *h, const double *alphas, int K, int am, int an,
  *                        (stats.sweep_groups; bitwise the same result); 0 = what is free minus a 2 GB reserve
  *   "sweep_split"        multi-device handles, bpltv_sweep / bpltv_sumregs_sweep: 0 automatic, 1 split the images, 2 split
  *                        the parameter blocks
- *   "tape_checkpoint"    the unrolled solves and sweeps of the three models (see bpltv_unrolled_tape_doubles): 0 the full tape,
+ *   "tape_checkpoint"    the unrolled solves and sweeps of the four models, the channel-coupled one included (see bpltv_unrolled_tape_doubles): 0 the full tape,
  *                        C >= 1 the iteration state every C iterations instead (the sweep recomputes each segment's tape: the
  *                        same bits, one more forward solve), -1 the spacing of least memory.  A value that is no integer or
  *                        lies below -1 is BPLTV_E_ARG and the option keeps its value.  The one option that is no test aid:

@@ -6,7 +6,7 @@
 # Same exports as src/TVLearningFunctionVec.jl:6
 export tv_op_learning_function, denoise, sumregs_learning_function, tv_vjp, sumregs_vjp, tv_jvp, tv_gauss_newton,
        sumregs_jvp, sumregs_gauss_newton, weighted_denoise, weighted_vjp, unrolled_denoise_each, unrolled_vjp_each,
-       unrolled_jvp_each, weighted_unrolled_jvp
+       unrolled_jvp_each, weighted_unrolled_jvp, color_denoise
 
 const libbpltv = "libbpltv"            # on LD_LIBRARY_PATH, or an absolute path
 
@@ -328,6 +328,19 @@ function unrolled_jvp_each(h::BpltvHandle, αs; df = nothing, dαs = nothing, kw
         (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Cint, Ref{BpltvParams}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
         h.ptr, a, am, an, p, 1, tf, ta, du, u))
     return du, u
+end
+
+# Channel-coupled (vectorial) TV of colour images (include/bpltv.h, bpltv_color_denoise): data is M x N x (C*B), colour image b
+# owns the planes (b-1)*C+1 ... b*C, and the channels of a pixel share one projection.  α: a scalar or an m x n matrix, shared
+# by the batch and the channels.  bpltv_color_unrolled_denoise / bpltv_color_unrolled_vjp take the same leading `channels`.
+function color_denoise(data::Array{Float64,3}, α, channels::Integer; kwargs...)
+    h = handle_for(data, data)
+    a, am, an = alpha_arg(α)
+    u = similar(data)
+    p = Ref(default_params(; kwargs...))
+    GC.@preserve a u bpltv_check(h, ccall((:bpltv_color_denoise, libbpltv), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Cint, Cint, Ref{BpltvParams}, Ptr{Cdouble}), h.ptr, channels, a, am, an, p, u))
+    return u
 end
 
 # The same for u = sumregs_denoise(f, x) (include/bpltv.h, bpltv_sumregs_vjp): x a 3-vector or an m x n x 3 array, passed
