@@ -201,7 +201,7 @@ const Variant kVariants[] = {
 // The models whose solves the shared launch driver (run_chains) runs
 enum Model { MODEL_TV = 0, MODEL_SR = 1, MODEL_W = 2, MODEL_UN = 3, MODEL_SRUN = 4, MODEL_COLOR = 5, NMODELS = 6 };   // MODEL_UN: the taped solve, its reverse sweep and the tangent sweep
                                                                                                      // MODEL_SRUN: the same of the sum-of-regularisers model
-                                                                                                     // MODEL_COLOR: the solves and the reverse sweep of the channel-coupled model
+                                                                                                     // MODEL_COLOR: the solves, the reverse sweep and the tangent sweep of the channel-coupled model
 
 // What identifies a launch sequence built into graphs: everything its kernel arguments and its cut into launches depend
 // on.  One key type for all models (a field a model does not use stays 0); each model has a cache of its own
@@ -216,7 +216,7 @@ struct GraphKey {
                        // 9 ... 16 = its tangent sweep, by the tangents it reads, its planes here;
                        // MODEL_SRUN: the tape as well, variant 0 = taped solve, 1 = reverse sweep;
                        // MODEL_COLOR: the tape as well (nullptr: none), variant 10 * channels + 0 = taped solve, + 1 = reverse sweep,
-                       // + 2 = the solve without a tape)
+                       // + 2 = the solve without a tape, + 4 ... 6 = its tangent sweep, by the tangents it reads, its planes here)
     const void* tab;   // step table (one per (maxiter, steps, L, dual-first shift, gamma): TabKey)
     int from_state;    // 1: the sequence starts from a prepared state (params.init / order), not from x = f, y = 0
     const void* alpha; // the parameter the launches read: a sweep's blocks and the dataset's parameter are different
@@ -510,6 +510,7 @@ struct bpltv_handle {
     Tape ctape;
     int last_channels = 0;
     bool color_ready = false;
+    bool color_jvp_ready = false;
     // checkpointed reverse sweeps of the four models (option "tape_checkpoint"): [segment tape | 2 recompute state sets],
     // allocated on first use, only grows
     double* d_seg = nullptr;
@@ -3693,6 +3694,27 @@ void taped_chains(bpltv_t* h, const bpltv_params& p, const WeightedPlan& pl, Cha
     j->serial = (p.reserved[2] & 1) != 0; j->helper_thread = !(p.reserved[2] & 8);
 }
 
+// The tangent sweep of the channel-coupled model (color_tangent_tile_kernel): unrolled_jvp_common's
+// launches with channels > 1.  The plan is the colour solve's; the first use raises the LDS its kernels may take.
+int color_jvp_plan(bpltv_t* h, const bpltv_params& p, WeightedPlan* pl) {
+    if (int prc = color_plan(h, p, PDHG_MAX_T, pl)) return prc;
+    if (!h->color_jvp_ready) {
+        HIPCHK(h, hipFuncSetAttribute((const void*)&color_tangent_tile_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)color_tangent_lds_bytes(2)));
+        HIPCHK(h, hipFuncSetAttribute((const void*)&color_tangent_tile_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)color_tangent_lds_bytes(3)));
+        HIPCHK(h, hipFuncSetAttribute((const void*)&color_tangent_tile_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)color_tangent_lds_bytes(4)));
+        h->color_jvp_ready = true;
+    }
+    return BPLTV_OK;
+}
+// One launch of it: the caller has set the planes, alpha and the tangents (tv_tile_launch); s.lo, s.hi count colour images
+void color_tangent_launch(bpltv_t* h, const WeightedPlan& pl, const double* tab, const LaunchStep& s, int channels, TvTileArgs& a) {
+    a.f = h->d_f; a.tab = tab;
+    a.it0 = s.it; a.nit = s.nit;
+    a.M = h->M; a.N = h->N; a.halo = pl.T; a.first = s.first; a.img0 = s.lo;
+    void (*kern)(TvTileArgs) = channels == 2 ? &color_tangent_tile_kernel<2> : (channels == 3 ? &color_tangent_tile_kernel<3> : &color_tangent_tile_kernel<4>);
+    hipLaunchKernelGGL(kern, dim3(pl.nTi, pl.nTj, s.hi - s.lo), dim3(TV_R * TV_R), color_tangent_lds_bytes(channels), s.st, a);
+}
+
 // The end of a sweep through the iterations (the caller has put the last solve's statistics back): the time since ev[2] is
 // its adjoint_ms, with its adjoint_method
 int sweep_stats(bpltv_t* h, int method) {
@@ -4091,6 +4113,9 @@ int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const 
 // reads block k of both.
 // W (nullable: the TV model): the weighted model's w (wo planes, every entry >= 0) and d_dw (ndir x wo planes).  The step table
 // has gamma = min w, held fixed.
+// channels (bpltv_color_unrolled_jvp(_device), bpltv_color_unrolled_gauss_newton): the planes of a colour
+// image, 1 ... 4, dividing O; 0: the TV or weighted call.  The same driver with color_plan's plan, launch chains that count
+// colour images, color_tangent_tile_kernel and graphs of their own under MODEL_COLOR; channels = 1 runs the TV tangent kernel.
 struct JvpWeight {
     const double* w;
     int wo;
@@ -4098,7 +4123,7 @@ struct JvpWeight {
 };
 int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool dev, int am, int an, const bpltv_params* pp, int ndir,
                         const double* d_df, const double* d_dalpha, double* d_du, double* d_u, const double** x_res, bool each = false,
-                        const JvpWeight* W = nullptr) {
+                        const JvpWeight* W = nullptr, int channels = 0) {
     const double* d_dw = W ? W->dw : nullptr;
     if (!alpha || !d_du || (W && !W->w)) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
     if (ndir < 1) return set_err(h, BPLTV_E_ARG, "%s: ndir = %d (at least one direction)", who, ndir);
@@ -4109,7 +4134,7 @@ int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool d
     const bpltv_params p0 = resolve(pp);
     if (int prc = unrolled_check_params(h, p0, who)) return prc;
     WeightedPlan pl;
-    if (int prc = unrolled_plan(h, p0, PDHG_MAX_T, &pl)) return prc;
+    if (int prc = channels > 1 ? color_jvp_plan(h, p0, &pl) : unrolled_plan(h, p0, PDHG_MAX_T, &pl)) return prc;
     const size_t tot = h->tot, nw = W ? (size_t)W->wo * h->npx : 0;
     double*& d_ws = W ? h->d_wjv : h->d_ujv;
     if (!d_ws) {
@@ -4142,12 +4167,13 @@ int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool d
     if (W) HIPCHK(h, hipMemcpyAsync(d_wc, g.w, nw * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
     const bpltv_stats_t kept = h->st;
     ChainSolve j;
-    j.model = MODEL_UN; j.nplanes = 6; j.state0 = S[0];
-    taped_chains(h, p, pl, &j);
+    j.model = channels > 1 ? MODEL_COLOR : MODEL_UN; j.nplanes = 6; j.state0 = S[0];
+    taped_chains(h, p, pl, &j, channels ? channels : 1);
     j.bytes_per_px_iter = 0.0;   // (the driver's solve statistics are not this call's: `kept` goes back below)
-    // variant 2 ... 5: a tangent sweep, by which tangents it reads (0 = taped solve, 1 = reverse sweep); 9 ... 16: a weighted one
+    // variant 2 ... 5: a tangent sweep, by which tangents it reads (0 = taped solve, 1 = reverse sweep); 9 ... 16: a weighted one;
+    // MODEL_COLOR: 10 * channels + 3 + tangents (+ 0 ... 2 are the model's solves and its reverse sweep)
     const int tangents = (d_df ? 1 : 0) + (d_dalpha ? 2 : 0) + (d_dw ? 4 : 0);
-    j.key = GraphKey{K, T, (W ? 9 : 2) + tangents, am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_ws,
+    j.key = GraphKey{K, T, (channels > 1 ? 10 * channels + 3 : (W ? 9 : 2)) + tangents, am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_ws,
                      (const void*)d_tab, 0, (const void*)g.alpha, g.astride, W ? W->wo : 0};
     j.enqueue = launch_loop(T, [&](const LaunchStep& s) {
         TvTileArgs a{};
@@ -4155,7 +4181,8 @@ int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool d
         a.w = d_wc; a.wstride = (W && W->wo > 1) ? h->npx : 0;
         a.alpha = g.alpha; a.am = am; a.an = an; a.istride = g.astride;
         a.df = d_df ? d_dfc : nullptr; a.dw = d_dw ? d_dwc : nullptr; a.dalpha = d_dalpha ? d_dac : nullptr;
-        tv_tile_launch(h, pl, d_tab, s, W != nullptr, true, a);
+        if (channels > 1) color_tangent_launch(h, pl, d_tab, s, channels, a);
+        else tv_tile_launch(h, pl, d_tab, s, W != nullptr, true, a);
     });
     int rc = hipEventRecord(h->ev[2], h->stream) == hipSuccess ? (int)BPLTV_OK : set_err(h, BPLTV_E_HIP, "%s: hipEventRecord failed", who);
     int buf = 0;
@@ -4173,7 +4200,7 @@ int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool d
     h->st = kept;
     if (rc) return rc;
     if (d_u) HIPCHK(h, hipMemcpyAsync(d_u, S[buf][0], tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    if (int src = sweep_stats(h, W ? 11 : 8)) return src;
+    if (int src = sweep_stats(h, channels ? 13 : (W ? 11 : 8))) return src;
     if (x_res) *x_res = S[buf][0];
     return BPLTV_OK;
 }
@@ -4770,7 +4797,7 @@ int bpltv_weighted_unrolled_vjp_device(bpltv_t* h, const double* d_tape, const d
 // bpltv_unrolled_jvp, bpltv_unrolled_jvp_each and bpltv_weighted_unrolled_jvp on a single-device handle: the host arrays
 // staged around unrolled_jvp_common.  W (nullable: the TV model): the weighted model's host w and host dw.
 static int unrolled_jvp_host(bpltv_t* h, const char* who, const double* alpha, int am, int an, const bpltv_params* pp, int ndir, const double* df,
-                             const double* dalpha, double* du_out, double* u_out, bool each, const JvpWeight* W) {
+                             const double* dalpha, double* du_out, double* u_out, bool each, const JvpWeight* W, int channels = 0) {
     const double* dw = W ? W->dw : nullptr;
     if (!alpha || !du_out || (W && !W->w)) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
     if (ndir < 1) return set_err(h, BPLTV_E_ARG, "%s: ndir = %d (at least one direction)", who, ndir);
@@ -4794,7 +4821,7 @@ static int unrolled_jvp_host(bpltv_t* h, const char* who, const double* alpha, i
     if (dw) HIPCHK(h, hipMemcpyAsync(d_dw, dw, nd * sizeof(double), hipMemcpyHostToDevice, h->stream));
     JvpWeight Wd{};
     if (W) Wd = JvpWeight{W->w, W->wo, d_dw};
-    rc = unrolled_jvp_common(h, who, alpha, false, am, an, pp, ndir, d_df, d_da, d_du, d_u, nullptr, each, W ? &Wd : nullptr);
+    rc = unrolled_jvp_common(h, who, alpha, false, am, an, pp, ndir, d_df, d_da, d_du, d_u, nullptr, each, W ? &Wd : nullptr, channels);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(du_out, d_du, nt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     if (u_out) HIPCHK(h, hipMemcpyAsync(u_out, d_u, h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -4803,15 +4830,18 @@ static int unrolled_jvp_host(bpltv_t* h, const char* who, const double* alpha, i
 }
 
 static int unrolled_jvp_entry(bpltv_t* h, const char* what, bool dev, const double* alpha, int am, int an, const bpltv_params* pp, int ndir,
-                              const double* df, const double* dalpha, double* du, double* u, bool each, const JvpWeight* W = nullptr) {
+                              const double* df, const double* dalpha, double* du, double* u, bool each, const JvpWeight* W = nullptr,
+                              int channels = 0) {
     if (!h) return BPLTV_E_ARG;
     if (h->multi)
-        return weighted_multi(h, what, false, [&](bpltv_t* c) { return unrolled_jvp_entry(c, what, dev, alpha, am, an, pp, ndir, df, dalpha, du, u, each, W); },
-                              W ? kTapedWeighted.multi_name : kUnrolled);
-    const char* who = W ? "weighted_unrolled_jvp" : (each ? "unrolled_jvp_each" : "unrolled_jvp");
-    if (!dev) return unrolled_jvp_host(h, who, alpha, am, an, pp, ndir, df, dalpha, du, u, each, W);
+        return weighted_multi(h, what, false, [&](bpltv_t* c) { return unrolled_jvp_entry(c, what, dev, alpha, am, an, pp, ndir, df, dalpha, du, u, each, W, channels); },
+                              channels ? kTapedColor[0].multi_name : (W ? kTapedWeighted.multi_name : kUnrolled));
+    int crc = BPLTV_OK;   // (color_model leaves the division to a forwarding handle's shard: this is where it arrives)
+    if (channels && !color_model(h, what, channels, &crc)) return crc;
+    const char* who = channels ? "color_unrolled_jvp" : (W ? "weighted_unrolled_jvp" : (each ? "unrolled_jvp_each" : "unrolled_jvp"));
+    if (!dev) return unrolled_jvp_host(h, who, alpha, am, an, pp, ndir, df, dalpha, du, u, each, W, channels);
     HIPCHK(h, hipSetDevice(h->device));
-    return unrolled_jvp_common(h, who, alpha, true, am, an, pp, ndir, df, dalpha, du, u, nullptr, each, W);
+    return unrolled_jvp_common(h, who, alpha, true, am, an, pp, ndir, df, dalpha, du, u, nullptr, each, W, channels);
 }
 
 int bpltv_unrolled_jvp(bpltv_t* h, const double* alpha, int am, int an, const bpltv_params* pp, int ndir, const double* df,
@@ -4844,21 +4874,24 @@ int bpltv_weighted_unrolled_jvp_device(bpltv_t* h, const double* d_w, int wo, co
 // Gradient and Gauss-Newton Hessian of the K-step loss 0.5||u_K(alpha) - ubar||^2 from P = am*an <= GN_MAXP unit-direction
 // tangent sweeps: [J | u_K - ubar] into gn_gram_kernel / gn_final_kernel, as gauss_newton does for the implicit Jacobian.
 // w (nullable: the TV model; wo planes on the host): the weighted iterations' loss.
+// channels: 0 = the TV and weighted entry points; 1 ... 4 = the channel-coupled model's (the loss runs over all planes).
 static int unrolled_gauss_newton_entry(bpltv_t* h, const char* what, const double* w, int wo, const double* alpha, int am, int an,
-                                       const bpltv_params* pp, double* cost_out, double* grad_out, double* hess_out) {
+                                       const bpltv_params* pp, double* cost_out, double* grad_out, double* hess_out, int channels = 0) {
     const char* who = what + 6;   // (without "bpltv_")
     if (!h) return BPLTV_E_ARG;
     if (h->multi)
         return weighted_multi(h, what, false, [&](bpltv_t* c) {
-            return unrolled_gauss_newton_entry(c, what, w, wo, alpha, am, an, pp, cost_out, grad_out, hess_out);
-        }, w ? kTapedWeighted.multi_name : kUnrolled);
+            return unrolled_gauss_newton_entry(c, what, w, wo, alpha, am, an, pp, cost_out, grad_out, hess_out, channels);
+        }, channels ? kTapedColor[0].multi_name : (w ? kTapedWeighted.multi_name : kUnrolled));
+    int crc = BPLTV_OK;   // (color_model leaves the division to a forwarding handle's shard: this is where it arrives)
+    if (channels && !color_model(h, what, channels, &crc)) return crc;
     if (!alpha || !cost_out || !grad_out || !hess_out) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
     if (am < 1 || an < 1 || am > h->M || an > h->N)
         return set_err(h, BPLTV_E_ARG, "%s: parameter shape %dx%d (image %dx%d)", who, am, an, h->M, h->N);
     const bool amap = am == h->M && an == h->N && !(h->M == 1 && h->N == 1);
     if (amap || (long)am * an > GN_MAXP)
         return set_err(h, BPLTV_E_UNSUPPORTED, "%s: a scalar or a patch parameter of at most %d entries (got %dx%d%s); use bpltv_%sunrolled_jvp for Jacobian columns",
-                       who, GN_MAXP, am, an, amap ? ", a pixel map" : "", w ? "weighted_" : "");
+                       who, GN_MAXP, am, an, amap ? ", a pixel map" : "", channels ? "color_" : (w ? "weighted_" : ""));
     if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: bpltv_set_data has not been called", who);
     const int P = am * an;
     const size_t nout = (size_t)P + (size_t)P * P;
@@ -4880,7 +4913,7 @@ static int unrolled_gauss_newton_entry(bpltv_t* h, const char* what, const doubl
     HIPCHK(h, hipStreamSynchronize(h->stream));   // (eye is a local)
     const double* d_x = nullptr;
     const JvpWeight W{w, wo, nullptr};
-    int rc = unrolled_jvp_common(h, who, alpha, false, am, an, pp, P, nullptr, d_e, d_J, nullptr, &d_x, false, w ? &W : nullptr);
+    int rc = unrolled_jvp_common(h, who, alpha, false, am, an, pp, P, nullptr, d_e, d_J, nullptr, &d_x, false, w ? &W : nullptr, channels);
     if (rc) return rc;
     h->has_per_image = false;   // compute_cost writes d_perimg and d_red
     rc = compute_cost(h, d_x, h->d_ubar, d_out + nout);
@@ -4905,6 +4938,29 @@ int bpltv_weighted_unrolled_gauss_newton(bpltv_t* h, const double* w, int wo, co
     if (!h) return BPLTV_E_ARG;
     if (!w) return set_err(h, BPLTV_E_ARG, "weighted_unrolled_gauss_newton: w is a null pointer");
     return unrolled_gauss_newton_entry(h, "bpltv_weighted_unrolled_gauss_newton", w, wo, alpha, am, an, pp, cost_out, grad_out, hess_out);
+}
+
+// Forward mode through the channel-coupled iterations (color_tangent_tile_kernel)
+int bpltv_color_unrolled_jvp(bpltv_t* h, int channels, const double* alpha, int am, int an, const bpltv_params* pp, int ndir, const double* df,
+                             const double* dalpha, double* du_out, double* u_out) {
+    if (!h) return BPLTV_E_ARG;
+    int rc = BPLTV_OK;
+    if (!color_model(h, "bpltv_color_unrolled_jvp", channels, &rc)) return rc;
+    return unrolled_jvp_entry(h, "bpltv_color_unrolled_jvp", false, alpha, am, an, pp, ndir, df, dalpha, du_out, u_out, false, nullptr, channels);
+}
+int bpltv_color_unrolled_jvp_device(bpltv_t* h, int channels, const double* d_alpha, int am, int an, const bpltv_params* pp, int ndir,
+                                    const double* d_df, const double* d_dalpha, double* d_du, double* d_u) {
+    if (!h) return BPLTV_E_ARG;
+    int rc = BPLTV_OK;
+    if (!color_model(h, "bpltv_color_unrolled_jvp_device", channels, &rc)) return rc;
+    return unrolled_jvp_entry(h, "bpltv_color_unrolled_jvp_device", true, d_alpha, am, an, pp, ndir, d_df, d_dalpha, d_du, d_u, false, nullptr, channels);
+}
+int bpltv_color_unrolled_gauss_newton(bpltv_t* h, int channels, const double* alpha, int am, int an, const bpltv_params* pp, double* cost_out,
+                                      double* grad_out, double* hess_out) {
+    if (!h) return BPLTV_E_ARG;
+    int rc = BPLTV_OK;
+    if (!color_model(h, "bpltv_color_unrolled_gauss_newton", channels, &rc)) return rc;
+    return unrolled_gauss_newton_entry(h, "bpltv_color_unrolled_gauss_newton", nullptr, 1, alpha, am, an, pp, cost_out, grad_out, hess_out, channels);
 }
 
 int bpltv_u_device(bpltv_t* h, const double** d_u) {

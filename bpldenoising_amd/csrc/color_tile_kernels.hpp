@@ -25,6 +25,7 @@
 // One workgroup per (tile, colour image): 1024 threads, one pixel per thread with its C channels in registers.  LDS: C sets
 // of the TV planes.  Two barriers per iteration, every load first, the step rows in LDS, spent halo waves keep the barriers
 // company only, agent-scope write-through stores of the core: tv_tile_kernel's structure.
+// color_tangent_tile_kernel<C> (below) carries the tangent through the same iterations: DESIGN.md section 4.13.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -191,6 +192,210 @@ __global__ __launch_bounds__(TV_R * TV_R) void color_tile_kernel(TvTileArgs A) {
             __hip_atomic_store(&A.out[0][idx + c * npx], x[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(&A.out[1][idx + c * npx], y1[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(&A.out[2][idx + c * npx], y2[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// The tangent sweep: color_tile_kernel<C, false> carrying tv_tile_kernel<0, 0, 1>'s tangent, with the
+// derivative of the projection taken over the C planes of a colour image.  Per plane c, beside iteration k, from dx = df, dy = 0
+// (no fma in it; the step table is held fixed):
+//     ddiv_c = G^T dy_c;  dt_c = ddiv_c - df_c
+//     dxn_c  = (dx_c - tau_k*dt_c)*r_k;   dxb_c = (1 + omega_k)*dxn_c - omega_k*dx_c;   dx_c = dxn_c
+//     dz_c   = dy_c + sigma_k * G dxb_c
+// then once per pixel of the colour image, on the primal's own n2 and decision:
+//     out:  q = rsqrt_nr(n2);  e_c = z_c*q;  dot = (e1_0*dz1_0 + e2_0*dz2_0), then dot += (e1_c*dz1_c + e2_c*dz2_c), c = 1 ... C-1
+//           dy_c = dalpha*e_c + (alpha*q)*(dz_c - e_c*dot)
+//     else: dy_c = dz_c
+// and du = dx after the last step: the transpose of color_reverse_tile_kernel's sweep.  The primal half is color_tile_kernel's,
+// operation for operation.
+//
+// LDS: 2*C sets of planes, channel c's primal set at c, its tangent set at C + c.  Four channels of full TV sets (202 816 B)
+// pass the 163 840 B of a CU, so a set keeps no y1 / dy1 plane: the left neighbour is lane li - 1 of the same 32-pixel row, and
+// a wave holds two whole rows, so it comes by a lane shift (pd_lane_prev_or0) with the zero guard for li = 0.  That only moves
+// data: the bits do not change.  Two and three channels would fit with the planes; the shift is not slower there (DESIGN.md
+// section 4.13), so every instantiation has the one exchange.
+constexpr size_t color_tangent_set_doubles() { return (TV_R + 1) * TV_R + TV_R * TV_R + TV_R + 1; }   // y2 and xbar planes
+constexpr size_t color_tangent_lds_bytes(int C) { return (size_t)2 * C * color_tangent_set_doubles() * sizeof(double); }
+
+// TvTileArgs as color_tile_kernel, with in / out of six planes (x, y1, y2, dx, dy1, dy2), df (the planes img*C + c) and dalpha
+// (indexed as alpha); either may be nullptr: a zero tangent.  tape, w, dw, wstride and istride are not read.
+template <int C>
+__global__ __launch_bounds__(TV_R * TV_R) void color_tangent_tile_kernel(TvTileArgs A) {
+    static_assert(C >= 2 && C <= COLOR_MAX_C, "channels = 1 is tv_tile_kernel<0, 0, 1>");
+    constexpr int RI = TV_R, RJ = TV_R;
+    constexpr int PLANES = (int)color_tangent_set_doubles();
+    static_assert(color_tangent_lds_bytes(C) + PDHG_MAX_T * TAB_STRIDE * sizeof(double) <= 163840, "the LDS of a CU");
+    extern __shared__ __attribute__((aligned(16))) unsigned char tv_smem[];
+    double* sy2 = reinterpret_cast<double*>(tv_smem);   // [RJ+1][RI]             channel c: + c * PLANES
+    double* sxb = sy2 + (RJ + 1) * RI;                  // [RJ][RI] + RI + 1
+    double* sd2 = sy2 + C * PLANES;                     // the tangent's planes
+    double* sdb = sxb + C * PLANES;
+    __shared__ __attribute__((aligned(16))) double srow[PDHG_MAX_T * TAB_STRIDE];
+
+    const int tid = threadIdx.x;
+    const int li = tid % RI, lj = tid / RI;
+    const int ta = (int)blockIdx.x, tb = (int)blockIdx.y, img = A.img0 + (int)blockIdx.z;
+    const int M = A.M, N = A.N;
+    int oi, ci0, ci1, oj, cj0, cj1;
+    tile_span(ta, M, RI, A.halo, oi, ci0, ci1);
+    tile_span(tb, N, RJ, A.halo, oj, cj0, cj1);
+    const size_t npx = (size_t)M * N;
+    const size_t base = (size_t)img * C * npx;   // channel 0 of the colour image
+    const int amode = (A.am == 1 && A.an == 1) ? 0 : ((A.am == M && A.an == N) ? 2 : 1);
+    const bool first = A.first != 0;
+
+    // ---- prologue: every global load is issued before the first use.  Out-of-image pixels read a clamped in-image
+    // address and are zeroed afterwards (they stay 0).
+    const int gi = min(oi + li, M - 1), gj = min(oj + lj, N - 1);
+    const size_t pix = gi + (size_t)M * gj;
+    size_t ai = 0;
+    if (amode == 2) {
+        ai = pix;
+    } else if (amode == 1) {
+        const unsigned pa = ((unsigned)gi * (unsigned)A.am) / (unsigned)M;
+        const unsigned pb = ((unsigned)gj * (unsigned)A.an) / (unsigned)N;
+        ai = pa + (size_t)A.am * pb;
+    }
+    double x[C], y1[C], y2[C], f[C], dx[C], dy1[C], dy2[C], df[C];
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        x[c] = 0.0; y1[c] = 0.0; y2[c] = 0.0; dx[c] = 0.0; dy1[c] = 0.0; dy2[c] = 0.0;
+        if (!first) {
+            x[c] = A.in[0][base + c * npx + pix];
+            y1[c] = A.in[1][base + c * npx + pix];
+            y2[c] = A.in[2][base + c * npx + pix];
+            dx[c] = A.in[3][base + c * npx + pix];
+            dy1[c] = A.in[4][base + c * npx + pix];
+            dy2[c] = A.in[5][base + c * npx + pix];
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        f[c] = A.f[base + c * npx + pix];
+        df[c] = 0.0;
+        if (A.df) df[c] = A.df[base + c * npx + pix];
+    }
+    double al = A.alpha[ai], dal = 0.0;
+    if (A.dalpha) dal = A.dalpha[ai];
+    const bool row_word = tid < A.nit * TAB_STRIDE;   // nit <= PDHG_MAX_T: the host checks
+    double row_w = 0.0;
+    if (row_word) row_w = A.tab[(size_t)TAB_STRIDE * A.it0 + tid];
+    const bool in = (oi + li < M) && (oj + lj < N);
+    if (!in) { al = 0.0; dal = 0.0; }
+#pragma unroll
+    for (int c = 0; c < C; ++c) {
+        if (first) { x[c] = f[c]; y1[c] = 0.0; y2[c] = 0.0; dx[c] = df[c]; dy1[c] = 0.0; dy2[c] = 0.0; }
+        if (!in) { f[c] = 0.0; x[c] = 0.0; y1[c] = 0.0; y2[c] = 0.0; df[c] = 0.0; dx[c] = 0.0; dy1[c] = 0.0; dy2[c] = 0.0; }
+        sy2[c * PLANES + (lj + 1) * RI + li] = y2[c];
+        sd2[c * PLANES + (lj + 1) * RI + li] = dy2[c];
+        if (tid < RI) { sy2[c * PLANES + tid] = 0.0; sd2[c * PLANES + tid] = 0.0; }
+        if (tid < RI + 1) { sxb[c * PLANES + RI * RJ + tid] = 0.0; sdb[c * PLANES + RI * RJ + tid] = 0.0; }
+    }
+    if (row_word) srow[tid] = row_w;
+    __syncthreads();
+
+    const int nit = A.nit;
+    // Neumann border: at the last image row / column the "neighbour" is the pixel's own xbar cell (difference +0)
+    const int l = lj * RI + li;
+    const int n1 = l + (((oi + li) < M - 1) ? 1 : 0);
+    const int n2 = l + (((oj + lj) < N - 1) ? RI : 0);
+    const int qi = oi + li, qj = oj + lj;
+    const bool core = qi >= ci0 && qi < ci1 && qj >= cj0 && qj < cj1;
+    const size_t idx = base + qi + (size_t)M * qj;   // channel 0; used by core pixels only
+    // halo rows do not need all the iterations (tv_tile_kernel): a wave owns two adjacent rows; core rows run them all
+    int my_nit = nit;
+    if (N > RJ) {
+        const int r0 = (tid & ~63) / RI, r1 = min((tid | 63) / RI, RJ - 1);
+        if (oj > 0) my_nit = min(my_nit, r1);
+        if (oj + RJ < N) my_nit = min(my_nit, RJ - r0);
+    }
+    const int loop_nit = __builtin_amdgcn_readfirstlane(my_nit);
+    double tau = srow[0], sigma = srow[1], omega = srow[2], r = srow[3], opw = srow[4];
+    for (int it = 0; it < loop_nit; ++it) {
+        // ---- primal step of every channel, and its tangent
+        double b[C], db[C];
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            // lane li - 1 of the row (every lane of the wave is here); li = 0: the zero guard column
+            const double p = pd_lane_prev_or0(y1[c]), dp = pd_lane_prev_or0(dy1[c]);
+            const double y1m = li ? p : 0.0, dy1m = li ? dp : 0.0;
+            const double y2m = sy2[c * PLANES + lj * RI + li];
+            const double dy2m = sd2[c * PLANES + lj * RI + li];
+            const double div = (y1m - y1[c]) + (y2m - y2[c]);
+            const double t = div - f[c];
+            const double xo = x[c];
+            const double xn = __builtin_fma(-tau, t, xo) * r;
+            b[c] = __builtin_fma(-omega, xo, opw * xn);
+            x[c] = xn;
+            const double ddiv = (dy1m - dy1[c]) + (dy2m - dy2[c]);
+            const double dt = ddiv - df[c];
+            const double dxn = (dx[c] - tau * dt) * r;
+            db[c] = opw * dxn - omega * dx[c];
+            dx[c] = dxn;
+            sxb[c * PLANES + l] = b[c];
+            sdb[c * PLANES + l] = db[c];
+        }
+        __syncthreads();
+        const double* nrow = srow + TAB_STRIDE * ((it + 1 < nit) ? it + 1 : it);
+        const double ntau = nrow[0], nsigma = nrow[1], nomega = nrow[2], nopw = nrow[4];
+        r = nrow[3];
+        // ---- dual step: z and dz of every channel (y becomes z, dy becomes dz), then one projection for the pixel
+        double nn = 0.0;
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            const double d1 = sxb[c * PLANES + n1] - b[c];
+            const double d2 = sxb[c * PLANES + n2] - b[c];
+            y1[c] = __builtin_fma(sigma, d1, y1[c]);
+            y2[c] = __builtin_fma(sigma, d2, y2[c]);
+            const double dd1 = sdb[c * PLANES + n1] - db[c];
+            const double dd2 = sdb[c * PLANES + n2] - db[c];
+            dy1[c] = dy1[c] + sigma * dd1;
+            dy2[c] = dy2[c] + sigma * dd2;
+            nn = (c == 0) ? y1[c] * y1[c] : __builtin_fma(y1[c], y1[c], nn);
+            nn = __builtin_fma(y2[c], y2[c], nn);
+        }
+        if (nn > al * al) {   // a wave whose pixels all lie inside the ball skips the rsqrt
+            const double q = rsqrt_nr(nn);
+            const double v = al * q;
+            double e1[C], e2[C], dot = 0.0;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                e1[c] = y1[c] * q;
+                e2[c] = y2[c] * q;
+                const double d = e1[c] * dy1[c] + e2[c] * dy2[c];
+                dot = (c == 0) ? d : dot + d;
+            }
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                dy1[c] = dal * e1[c] + v * (dy1[c] - e1[c] * dot);
+                dy2[c] = dal * e2[c] + v * (dy2[c] - e2[c] * dot);
+                y1[c] = y1[c] * v;
+                y2[c] = y2[c] * v;
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            sy2[c * PLANES + (lj + 1) * RI + li] = y2[c];
+            sd2[c * PLANES + (lj + 1) * RI + li] = dy2[c];
+        }
+        tau = ntau; sigma = nsigma; omega = nomega; opw = nopw;
+        __syncthreads();
+    }
+    for (int it = loop_nit; it < nit; ++it) {   // a spent halo wave: the two barriers of an iteration, nothing else
+        __syncthreads();
+        __syncthreads();
+    }
+
+    if (core) {
+        // write-through stores, as tv_tile_kernel: the next launch reads this state from other XCDs
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            __hip_atomic_store(&A.out[0][idx + c * npx], x[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&A.out[1][idx + c * npx], y1[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&A.out[2][idx + c * npx], y2[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&A.out[3][idx + c * npx], dx[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&A.out[4][idx + c * npx], dy1[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&A.out[5][idx + c * npx], dy2[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }

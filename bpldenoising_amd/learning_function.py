@@ -558,6 +558,42 @@ class TVSolver:
                                                               C.c_void_p(gu_ptr), C.c_void_p(grad_f_ptr or None),
                                                               C.c_void_p(grad_alpha_ptr or None)))
 
+    def color_unrolled_jvp(self, x, channels, df=None, dalpha=None, want_u=False, **kw):
+        """Jacobian-vector product of the maxiter-step map u = color_denoise(x, channels) of the resident f
+        (bpltv_color_unrolled_jvp): a tangent sweep through the channel-coupled iterations, no tape -- the linear map whose
+        transpose color_unrolled_vjp computes.  Tangents, result and want_u as unrolled_jvp; channels = 1 is unrolled_jvp
+        bit for bit."""
+        a, am, an, scalar = _alpha_arg(x)
+        df, dalpha, K, batched = self._tangents("color_unrolled_jvp", df, dalpha, () if scalar else (an, am))
+        p = self.params(**kw)
+        du = np.empty((K, self.O, self.N, self.M))
+        u = np.empty((self.O, self.N, self.M)) if want_u else None
+        self._check(self._lib.bpltv_color_unrolled_jvp(self._h, int(channels), _ptr(a), am, an, C.byref(p), K,
+                                                       _ptr(df) if df is not None else None,
+                                                       _ptr(dalpha) if dalpha is not None else None, _ptr(du),
+                                                       _ptr(u) if want_u else None))
+        du = du if batched else du[0]
+        return (du, u) if want_u else du
+
+    def color_unrolled_jvp_device(self, channels, alpha_ptr, am, an, df_ptr, dalpha_ptr, du_ptr, u_ptr=None, ndir=1, **kw):
+        """bpltv_color_unrolled_jvp_device: as unrolled_jvp_device, for colour images of `channels` planes."""
+        p = self.params(**kw)
+        self._check(self._lib.bpltv_color_unrolled_jvp_device(self._h, int(channels), C.c_void_p(alpha_ptr), int(am), int(an),
+                                                              C.byref(p), int(ndir), C.c_void_p(df_ptr or None),
+                                                              C.c_void_p(dalpha_ptr or None), C.c_void_p(du_ptr),
+                                                              C.c_void_p(u_ptr or None)))
+
+    def color_unrolled_gauss_newton(self, x, channels, **kw):
+        """Gauss-Newton model of the maxiter-step loss 0.5||u_K(x) - ubar||^2 of the channel-coupled solve, over all planes
+        (bpltv_color_unrolled_gauss_newton): (cost, grad, H) as unrolled_gauss_newton."""
+        a, am, an, scalar = _alpha_arg(x)
+        p = self.params(**kw)
+        P = am * an
+        cost, grad, H = C.c_double(0.0), np.empty(P), np.empty((P, P))
+        self._check(self._lib.bpltv_color_unrolled_gauss_newton(self._h, int(channels), _ptr(a), am, an, C.byref(p),
+                                                                C.byref(cost), _ptr(grad), _ptr(H)))
+        return float(cost.value), (float(grad[0]) if scalar else grad.reshape(an, am)), H
+
     # -- reverse mode through the weighted iterations (bpltv_weighted_unrolled_*) --------------------------------
     def weighted_unrolled_tape_doubles(self, **kw):
         """Doubles of the tape a weighted unrolled solve with these params records: 3 * maxiter * M*N*O."""

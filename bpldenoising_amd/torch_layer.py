@@ -94,7 +94,10 @@ The model is vectorial TV, 0.5 sum_c |u_c - f_c|^2 + sum alpha sqrt(sum_c |grad 
 its channels onto one ball, so the channels share their edges (reshaping to B*C grey planes is channel-by-channel TV and
 gives colour fringes).  Forward is one taped solve into a tape tensor of its own (2 * maxiter * B*C*H*W doubles), backward
 one bpltv_color_unrolled_vjp_device call; C = 1 is tv_denoise_unrolled bit for bit.  TVDenoiseColorUnrolled(alpha,
-maxiter=50) is the module with a learnable parameter.  No jvp.  The other functions keep refusing 4-D input.
+maxiter=50) is the module with a learnable parameter.  The default function has no jvp; tv_denoise_color_unrolled(...,
+forward_mode=True) and TVDenoiseColorUnrolled(alpha, forward_mode=True) select a function whose jvp is one
+bpltv_color_unrolled_jvp_device call: a tangent sweep through the coupled iterations, which reads no tape.  The other functions
+keep refusing 4-D input.
 
 Streams: the library runs its kernels on its own HIP streams and blocks until they are done.  Every call below first
 synchronises the tensors' current torch stream, so that the library reads inputs torch has finished writing; its
@@ -1044,26 +1047,67 @@ class TVDenoiseColorUnrolledFunction(torch.autograd.Function):
         return gf, (ga.reshape(alpha.shape) if need_a else None), None
 
 
-def tv_denoise_color_unrolled(f, alpha, maxiter=50, checkpoint_every=None, **solver_kw):
+class TVDenoiseColorUnrolledForwardFunction(TVDenoiseColorUnrolledFunction):
+    """TVDenoiseColorUnrolledFunction with a jvp (tv_denoise_color_unrolled(..., forward_mode=True)): forward is the base
+    class's taped solve, so backward keeps working; the jvp is one tangent sweep through the channel-coupled iterations
+    (TVSolver.color_unrolled_jvp_device, one direction), which reads no tape."""
+
+    @staticmethod
+    def forward(ctx, f, alpha, solver_kw):
+        u = TVDenoiseColorUnrolledFunction.forward(ctx, f, alpha, solver_kw)
+        ctx.save_for_forward(f.detach().contiguous(), alpha.detach().contiguous())
+        ctx.set_materialize_grads(False)   # an input without a tangent reaches jvp as None, and the library as NULL
+        return u
+
+    @staticmethod
+    def jvp(ctx, df, dalpha, _solver_kw):
+        f, alpha = ctx.saved_tensors
+        df, dalpha = _tangent(df, f, "f"), _tangent(dalpha, alpha, "alpha")
+        if df is None and dalpha is None:
+            return torch.zeros_like(f)
+        du = torch.empty_like(f)
+        _sync(f.device)
+        ctx.solver.set_data_device(f.data_ptr(), f.data_ptr())   # the sweep reads the handle's dataset
+        ctx.solver.color_unrolled_jvp_device(ctx.channels, alpha.data_ptr(), ctx.am, ctx.an,
+                                             df.data_ptr() if df is not None else None,
+                                             dalpha.data_ptr() if dalpha is not None else None, du.data_ptr(), None, ndir=1,
+                                             **_no_checkpoint(ctx.solver_kw))
+        return du
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gu):
+        if gu is None:
+            return None, None, None
+        return TVDenoiseColorUnrolledFunction.backward(ctx, gu)
+
+
+def tv_denoise_color_unrolled(f, alpha, maxiter=50, checkpoint_every=None, forward_mode=False, **solver_kw):
     """Vectorial TV of colour images by exactly maxiter PDHG iterations: min_u 1/2 sum_c |u_c - f_c|^2 + sum_pixels alpha *
     sqrt(sum_c |grad u_c|^2) -- the channels of an image share one projection per pixel, so an edge is found in all of them
     at once (TVSolver.color_unrolled_denoise_device).  Differentiable in f and alpha through the iterations
     (TVSolver.color_unrolled_vjp_device), as tv_denoise_unrolled.
     f: (B, C, H, W) or (C, H, W), float64, on a ROCm device, 1 <= C <= 4; alpha, shared by the batch and the channels: 0-dim,
-    (pH, pW) or (H, W).  checkpoint_every, solver_kw: as tv_denoise_unrolled's.  Reverse mode only."""
-    return TVDenoiseColorUnrolledFunction.apply(f, alpha, _with_checkpoint(dict(solver_kw, maxiter=int(maxiter)), checkpoint_every))
+    (pH, pW) or (H, W).  checkpoint_every, solver_kw: as tv_denoise_unrolled's.
+    forward_mode: also usable under torch.autograd.forward_ad (the function then carries a jvp, a tangent sweep through the
+    coupled iterations, TVSolver.color_unrolled_jvp_device, unaffected by checkpoint_every); without it forward-mode AD raises
+    torch's "not implemented" error, as before."""
+    fn = TVDenoiseColorUnrolledForwardFunction if forward_mode else TVDenoiseColorUnrolledFunction
+    return fn.apply(f, alpha, _with_checkpoint(dict(solver_kw, maxiter=int(maxiter)), checkpoint_every))
 
 
 class TVDenoiseColorUnrolled(torch.nn.Module):
     """tv_denoise_color_unrolled behind a learnable scalar, patch parameter or pixel map.  Move it to the device of its inputs
-    with .to(device)."""
+    with .to(device).  forward_mode: as tv_denoise_color_unrolled's."""
 
-    def __init__(self, alpha, maxiter=50, checkpoint_every=None, **solver_kw):
+    def __init__(self, alpha, maxiter=50, checkpoint_every=None, forward_mode=False, **solver_kw):
         super().__init__()
         self.alpha = torch.nn.Parameter(torch.as_tensor(alpha, dtype=torch.float64).clone())
         self.maxiter = int(maxiter)
         self.checkpoint_every = checkpoint_every
+        self.forward_mode = bool(forward_mode)
         self.solver_kw = dict(solver_kw)
 
     def forward(self, f):
-        return tv_denoise_color_unrolled(f, self.alpha, maxiter=self.maxiter, checkpoint_every=self.checkpoint_every, **self.solver_kw)
+        return tv_denoise_color_unrolled(f, self.alpha, maxiter=self.maxiter, checkpoint_every=self.checkpoint_every,
+                                         forward_mode=self.forward_mode, **self.solver_kw)

@@ -140,7 +140,8 @@ typedef struct bpltv_stats {
                                   9 reverse sweep over the taped weighted iterations (bpltv_weighted_unrolled_vjp),
                                   10 reverse sweep over the taped sum-of-regularisers iterations (bpltv_sumregs_unrolled_vjp),
                                   11 tangent sweep through the weighted iterations (bpltv_weighted_unrolled_jvp),
-                                  12 reverse sweep over the taped channel-coupled iterations (bpltv_color_unrolled_vjp) */
+                                  12 reverse sweep over the taped channel-coupled iterations (bpltv_color_unrolled_vjp),
+                                  13 tangent sweep through the channel-coupled iterations (bpltv_color_unrolled_jvp) */
     int reg_gradient_used;     /* 1 if the last evaluate took the gradient_reg branch             */
     int ngpus;                 /* distinct devices behind this handle (1 for bpltv_create)        */
     int shards;                /* image shards (= worker threads) behind this handle              */
@@ -681,6 +682,39 @@ int bpltv_color_unrolled_vjp(bpltv_t *h, int channels, const double *alpha, int 
                              const double *gu, double *grad_f_out, double *grad_alpha_out);
 int bpltv_color_unrolled_vjp_device(bpltv_t *h, int channels, const double *d_tape, const double *d_alpha, int am, int an,
                                     const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alpha);
+
+/* Forward mode through the channel-coupled iterations: bpltv_unrolled_jvp and
+ * bpltv_unrolled_gauss_newton for the model above.  The tangent (dx, dy) is carried beside (x, y) through the same maxiter
+ * iterations, from dx = df, dy = 0, with the step table held fixed; the derivative of the projection is taken per pixel of a
+ * colour image over its planes, on the primal's own decision:
+ *
+ *     out:  q = rsqrt_nr(n2);  e_c = z_c*q;  dot = sum_c (e1_c*dz1_c + e2_c*dz2_c);  dy_c = dalpha*e_c + (alpha*q)*(dz_c - e_c*dot)
+ *     else: dy_c = dz_c
+ *
+ * and du = dx after the last step: the exact transpose of bpltv_color_unrolled_vjp, <du, gu> = <df, grad_f> + <dalpha,
+ * grad_alpha> to rounding.  No tape is read or written, so the memory does not grow with maxiter.
+ *
+ * bpltv_color_unrolled_jvp: ndir directions, one sweep each, one after the other.  df (ndir x M*N*O doubles) and dalpha
+ * (ndir x am*an) are direction-major; either may be NULL (a zero tangent), not both (BPLTV_E_ARG); tangents must be finite.
+ * du_out: ndir x M*N*O doubles.  u_out (may be NULL): bpltv_color_denoise's u, bit for bit.  Direction d of a call is bitwise
+ * the call with that direction alone.  The _device form takes HBM addresses throughout (d_u may be NULL).
+ * bpltv_color_unrolled_gauss_newton: for a scalar or a patch of P = am*an <= 16 entries (a map or a larger patch:
+ * BPLTV_E_UNSUPPORTED) the cost 0.5 |u_K - ubar|^2 over all planes, grad_out = J^T (u_K - ubar) (P doubles) and hess_out =
+ * J^T J (P x P, column major) from P unit-direction sweeps; bpltv_set_data's ubar is the target.
+ *
+ * The contract is bpltv_unrolled_jvp's with the colour solve's rules for channels and params: channels outside 1 ... 4 or not
+ * dividing O, ndir < 1, maxiter < 1 and a bad parameter shape are BPLTV_E_ARG; rho, init and order must be 0
+ * (BPLTV_E_UNSUPPORTED); no data is BPLTV_E_NODATA; every rejection comes before anything of the handle changes.  channels = 1
+ * returns the bits of bpltv_unrolled_jvp.  The sweeps run in planes of the handle's own: the last solve, bpltv_u_device, the
+ * colour tape and the TV tapes stay as they were, and of the statistics only adjoint_ms (the HIP-event time of the sweeps) and
+ * adjoint_method = 13 change.  The results do not depend on tile_iters, on the launch chains, on use_graph or on the host or
+ * device form.  Multi-device handles behave as for bpltv_unrolled_jvp. */
+int bpltv_color_unrolled_jvp(bpltv_t *h, int channels, const double *alpha, int am, int an, const bpltv_params *p, int ndir,
+                             const double *df, const double *dalpha, double *du_out, double *u_out /* may be NULL */);
+int bpltv_color_unrolled_jvp_device(bpltv_t *h, int channels, const double *d_alpha, int am, int an, const bpltv_params *p,
+                                    int ndir, const double *d_df, const double *d_dalpha, double *d_du, double *d_u);
+int bpltv_color_unrolled_gauss_newton(bpltv_t *h, int channels, const double *alpha, int am, int an, const bpltv_params *p,
+                                      double *cost_out, double *grad_out, double *hess_out);
 
 /* Jacobian-vector product of u = denoise(f, alpha) (TV model): du for tangents (df, dalpha), defined as the linear map
  * whose transpose bpltv_vjp computes, in every branch -- <gu, du> = <grad_f(gu), df> + <grad_alpha(gu), dalpha> for any

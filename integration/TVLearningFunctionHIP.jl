@@ -343,6 +343,47 @@ function color_denoise(data::Array{Float64,3}, α, channels::Integer; kwargs...)
     return u
 end
 
+# Forward mode through the channel-coupled iterations (include/bpltv.h, bpltv_color_unrolled_jvp): du of the maxiter-step map
+# of the handle's dataset for one direction (df, dα): df nothing or M x N x (C*B), dα nothing or shaped like α; returns
+# (du, u) with u = color_denoise's result.  No tape is read: the transpose of bpltv_color_unrolled_vjp.
+function color_unrolled_jvp(h::BpltvHandle, α, channels::Integer; df = nothing, dα = nothing, kwargs...)
+    a, am, an = alpha_arg(α)
+    df === nothing && dα === nothing && error("color_unrolled_jvp: df and dα are both nothing")
+    tf = df === nothing ? C_NULL : Array{Float64}(df)
+    ta = dα === nothing ? C_NULL : (dα isa Real ? [Float64(dα)] : Array{Float64}(dα))
+    du = zeros(h.M, h.N, h.O); u = zeros(h.M, h.N, h.O)
+    p = Ref(default_params(; kwargs...))
+    GC.@preserve a tf ta du u bpltv_check(h, ccall((:bpltv_color_unrolled_jvp, libbpltv), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Cint, Cint, Ref{BpltvParams}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        h.ptr, channels, a, am, an, p, 1, tf, ta, du, u))
+    return du, u
+end
+
+# The same with everything resident in HBM (bpltv_color_unrolled_jvp_device): raw device addresses, ndir directions,
+# direction-major; d_df or d_dα may be C_NULL (not both), d_u may be C_NULL.
+function color_unrolled_jvp_device(h::BpltvHandle, channels::Integer, d_α::Ptr{Cvoid}, am::Integer, an::Integer, d_df::Ptr{Cvoid},
+                                   d_dα::Ptr{Cvoid}, d_du::Ptr{Cvoid}, d_u::Ptr{Cvoid} = C_NULL; ndir::Integer = 1, kwargs...)
+    p = Ref(default_params(; kwargs...))
+    bpltv_check(h, ccall((:bpltv_color_unrolled_jvp_device, libbpltv), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Cvoid}, Cint, Cint, Ref{BpltvParams}, Cint, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cvoid}),
+        h.ptr, channels, d_α, am, an, p, ndir, d_df, d_dα, d_du, d_u))
+    return nothing
+end
+
+# Gauss-Newton model of the maxiter-step loss 0.5||u_K(α) - ū||^2 of the channel-coupled solve on the handle's dataset
+# (bpltv_color_unrolled_gauss_newton): (cost, g, H) with g = J'(u_K - ū) shaped like α and H = J'J (P x P, P = length(α) <= 16,
+# in α's column-major order) from P tangent sweeps -- the model the trust region of src/TRBox.jl consumes.
+function color_unrolled_gauss_newton(h::BpltvHandle, α, channels::Integer; kwargs...)
+    a, am, an = alpha_arg(α)
+    P = am * an
+    cost = Ref(0.0); g = zeros(am, an); H = zeros(P, P)
+    p = Ref(default_params(; kwargs...))
+    GC.@preserve a g H bpltv_check(h, ccall((:bpltv_color_unrolled_gauss_newton, libbpltv), Cint,
+        (Ptr{Cvoid}, Cint, Ptr{Cdouble}, Cint, Cint, Ref{BpltvParams}, Ref{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble}),
+        h.ptr, channels, a, am, an, p, cost, g, H))
+    return cost[], (α isa Real ? g[1] : reshape(g, size(α))), H
+end
+
 # The same for u = sumregs_denoise(f, x) (include/bpltv.h, bpltv_sumregs_vjp): x a 3-vector or an m x n x 3 array, passed
 # as its column-major memory as in sumregs_learning_function; dL/dx has the shape of x.  ḡ = u - ū gives
 # sumregs_learning_function's gradient bit for bit; reg = true is its sumregs_gradient_reg branch (Δ <= Δt).
