@@ -105,6 +105,10 @@ outputs are complete when the call returns.
 
 This module imports torch; `import bpldenoising_amd` does not import this module.
 """
+import functools
+import math
+import typing
+
 import torch
 from torch.autograd.function import once_differentiable
 
@@ -130,14 +134,27 @@ def clear_solvers():
     _solvers.clear()
 
 
-def _check_args(f, alpha, slices=1):
-    """(O, N, M, am, an) of a valid (f, alpha) pair; TypeError / ValueError before any library call.  slices = 3: the
-    sum-of-regularisers parameter, a leading dimension of 3 on the TV model's vector / patch / map shapes."""
-    name = "sumregs_denoise" if slices == 3 else "tv_denoise"
+def _check_tensors(name, f, alpha):
+    """The head of every checker below: two float64 tensors."""
     if not isinstance(f, torch.Tensor) or not isinstance(alpha, torch.Tensor):
         raise TypeError("%s: f and alpha must be torch tensors" % name)
     if f.dtype != torch.float64 or alpha.dtype != torch.float64:
         raise TypeError("%s: f and alpha must be float64 (got %s, %s)" % (name, f.dtype, alpha.dtype))
+
+
+def _check_device(name, f, alpha):
+    """The tail of every checker below: both on one ROCm device."""
+    if alpha.device != f.device:
+        raise ValueError("%s: alpha is on %s, f on %s" % (name, alpha.device, f.device))
+    if f.device.type != "cuda":
+        raise ValueError("%s: f must be on a ROCm device, got %s" % (name, f.device))
+
+
+def _check_args(f, alpha, slices=1):
+    """(O, N, M, am, an) of a valid (f, alpha) pair; TypeError / ValueError before any library call.  slices = 3: the
+    sum-of-regularisers parameter, a leading dimension of 3 on the TV model's vector / patch / map shapes."""
+    name = "sumregs_denoise" if slices == 3 else "tv_denoise"
+    _check_tensors(name, f, alpha)
     if f.dim() not in (2, 3) or f.numel() == 0:
         raise ValueError("%s: f must have shape (B, H, W) or (H, W), got %s" % (name, tuple(f.shape)))
     H, W = f.shape[-2], f.shape[-1]
@@ -158,10 +175,7 @@ def _check_args(f, alpha, slices=1):
     else:
         raise ValueError("%s: alpha must be 0-dim, (pH, pW) with pH <= %d, pW <= %d, or (%d, %d); got %s"
                          % (name, H, W, H, W, tuple(alpha.shape)))
-    if alpha.device != f.device:
-        raise ValueError("%s: alpha is on %s, f on %s" % (name, alpha.device, f.device))
-    if f.device.type != "cuda":
-        raise ValueError("%s: f must be on a ROCm device, got %s" % (name, f.device))
+    _check_device(name, f, alpha)
     return O, H, W, am, an
 
 
@@ -170,10 +184,7 @@ def _check_args_each(f, alpha, slices=1, name=None):
     dimension) sumregs_denoise_each; TypeError / ValueError before any library call.  name: the caller in the messages,
     when it is another function with tv_denoise_each's shapes."""
     name = name or ("sumregs_denoise_each" if slices == 3 else "tv_denoise_each")
-    if not isinstance(f, torch.Tensor) or not isinstance(alpha, torch.Tensor):
-        raise TypeError("%s: f and alpha must be torch tensors" % name)
-    if f.dtype != torch.float64 or alpha.dtype != torch.float64:
-        raise TypeError("%s: f and alpha must be float64 (got %s, %s)" % (name, f.dtype, alpha.dtype))
+    _check_tensors(name, f, alpha)
     if f.dim() != 3 or f.numel() == 0:
         raise ValueError("%s: f must have shape (B, H, W), got %s" % (name, tuple(f.shape)))
     B, H, W = f.shape
@@ -193,11 +204,50 @@ def _check_args_each(f, alpha, slices=1, name=None):
     else:
         raise ValueError("%s: alpha must be (%d,), (%d, pH, pW) with pH <= %d, pW <= %d, or (%d, %d, %d); got %s"
                          % (name, B, B, H, W, B, H, W, shape))
-    if alpha.device != f.device:
-        raise ValueError("%s: alpha is on %s, f on %s" % (name, alpha.device, f.device))
-    if f.device.type != "cuda":
-        raise ValueError("%s: f must be on a ROCm device, got %s" % (name, f.device))
+    _check_device(name, f, alpha)
     return B, H, W, am, an
+
+
+def _check_args_color(f, alpha):
+    """(B, C, H, W, am, an) of a valid (f, alpha) pair of tv_denoise_color_unrolled; TypeError / ValueError before any
+    library call."""
+    name = "tv_denoise_color_unrolled"
+    _check_tensors(name, f, alpha)
+    if f.dim() not in (3, 4) or f.numel() == 0:
+        raise ValueError("%s: f must have shape (B, C, H, W) or (C, H, W), got %s" % (name, tuple(f.shape)))
+    C, H, W = f.shape[-3], f.shape[-2], f.shape[-1]
+    B = f.shape[0] if f.dim() == 4 else 1
+    if not 1 <= C <= 4:
+        raise ValueError("%s: f has %d channels (1 ... 4)" % (name, C))
+    shape = tuple(alpha.shape)
+    if shape == ():
+        am = an = 1
+    elif len(shape) == 2 and 1 <= shape[0] <= H and 1 <= shape[1] <= W:
+        an, am = shape
+    else:
+        raise ValueError("%s: alpha must be 0-dim, (pH, pW) with pH <= %d, pW <= %d, or (%d, %d); got %s"
+                         % (name, H, W, H, W, shape))
+    _check_device(name, f, alpha)
+    return B, C, H, W, am, an
+
+
+def _check_weight(f, w, name="tv_denoise_weighted"):
+    """wo (1 or B) of a valid weight for f; TypeError / ValueError before any library call."""
+    if not isinstance(w, torch.Tensor):
+        raise TypeError("%s: w must be a torch tensor" % name)
+    if w.dtype != torch.float64:
+        raise TypeError("%s: w must be float64 (got %s)" % (name, w.dtype))
+    H, W = f.shape[-2], f.shape[-1]
+    if tuple(w.shape) == (H, W):
+        wo = 1
+    elif f.dim() == 3 and tuple(w.shape) == tuple(f.shape):
+        wo = f.shape[0]
+    else:
+        raise ValueError("%s: w must have shape (%d, %d) or f's shape %s; got %s"
+                         % (name, H, W, tuple(f.shape), tuple(w.shape)))
+    if w.device != f.device:
+        raise ValueError("%s: w is on %s, f on %s" % (name, w.device, f.device))
+    return wo
 
 
 def _sync(device):
@@ -217,55 +267,165 @@ def _tangent(t, primal, name):
     return t.detach().contiguous()
 
 
+def _ptr(t):
+    """A tensor's device address; None (the library's NULL: an output nobody wants, a tangent that is zero) stays None."""
+    return None if t is None else t.data_ptr()
+
+
+def _no_checkpoint(solver_kw):
+    """solver_kw for a tangent sweep, which reads no tape."""
+    return {k: v for k, v in solver_kw.items() if k != "checkpoint_every"}
+
+
+# ---- the one implementation behind the sixteen Functions below ------------------------------------------------------------------
+# A model is a row of this record; _forward, _backward and _jvp are every Function's three methods, written once over it.
+# The TVSolver entries are named, not held: they are looked up on the handle of the call.  Their argument lists mirror the C
+# ABI and are not regular -- the channel count first, `w, wo` in front of alpha, the tape first in a vjp, a trailing u_ptr in
+# an unrolled jvp -- so the three functions splice them.
+class _Model(typing.NamedTuple):
+    check: typing.Callable   # (f, alpha) -> (O, N, M, am, an), with channels (B, C, N, M, am, an); raises before any library call
+    solve: str               # TVSolver's solve ...
+    vjp: str                 # ... and the one call of backward
+    jvp: typing.Optional[str] = None    # the one call of the tangent; None: the model has no forward mode
+    tape: typing.Optional[str] = None   # the entry that sizes the tape of an unrolled model; None: implicit differentiation at u
+    slices: int = 1          # parameter planes: 3 in the sum-of-regularisers model
+    each: bool = False       # a parameter per image: alpha.grad is written in alpha's own shape
+    w: typing.Optional[str] = None      # a per-pixel weight behind alpha: the caller's name in the messages of its check
+    w_zeros: bool = False    # ... which may hold zeros, so the layer itself refuses what is negative or not finite
+    channels: bool = False   # f is (B, C, H, W): the handle holds B*C planes and every entry takes C first
+
+    @property
+    def reg(self):           # the implicit TV and sum-of-regularisers adjoints take the reference's linearisation switch
+        return self.tape is None and self.w is None
+
+
+_check_sr, _check_sr_each = functools.partial(_check_args, slices=3), functools.partial(_check_args_each, slices=3)
+_TV =_Model(_check_args, "denoise_device", "vjp_device", "jvp_device")
+_TV_EACH = _Model(_check_args_each, "denoise_each_device", "vjp_each_device", "jvp_each_device", each=True)
+_SUMREGS = _Model(_check_sr, "sumregs_denoise_device", "sumregs_vjp_device", "sumregs_jvp_device", slices=3)
+_SUMREGS_EACH = _Model(_check_sr_each, "sumregs_denoise_each_device", "sumregs_vjp_each_device", "sumregs_jvp_each_device",
+                       slices=3, each=True)
+_WEIGHTED = _Model(_check_args, "weighted_denoise_device", "weighted_vjp_device", w="tv_denoise_weighted")
+_UNROLLED = _Model(_check_args, "unrolled_denoise_device", "unrolled_vjp_device", "unrolled_jvp_device", "unrolled_tape_doubles")
+_UNROLLED_EACH = _Model(functools.partial(_check_args_each, name="tv_denoise_unrolled_each"), "unrolled_denoise_each_device",
+                        "unrolled_vjp_each_device", "unrolled_jvp_each_device", "unrolled_tape_doubles", each=True)
+_WEIGHTED_UNROLLED = _Model(_check_args, "weighted_unrolled_denoise_device", "weighted_unrolled_vjp_device",
+                            "weighted_unrolled_jvp_device", "weighted_unrolled_tape_doubles", w="tv_denoise_weighted_unrolled",
+                            w_zeros=True)
+_SUMREGS_UNROLLED = _Model(_check_sr, "sumregs_unrolled_denoise_device", "sumregs_unrolled_vjp_device", None,
+                           "sumregs_unrolled_tape_doubles", slices=3)
+_SUMREGS_UNROLLED_EACH = _Model(functools.partial(_check_sr_each, name="sumregs_denoise_unrolled_each"),
+                                "sumregs_unrolled_denoise_each_device", "sumregs_unrolled_vjp_each_device", None,
+                                "sumregs_unrolled_tape_doubles", slices=3, each=True)
+_COLOR_UNROLLED = _Model(_check_args_color, "color_unrolled_denoise_device", "color_unrolled_vjp_device",
+                         "color_unrolled_jvp_device", "unrolled_tape_doubles", channels=True)
+
+
+def _forward(m, ctx, f, alpha, solver_kw, reg=None, w=None, jvp=False):
+    """forward of every Function.  In this order: every check, the cached handle, detached contiguous copies, the tape, _sync,
+    f installed, the solve, u fetched; then what backward and (jvp: the class carries one) the tangent need is saved."""
+    if m.w:
+        if not isinstance(f, torch.Tensor) or f.dim() not in (2, 3) or f.numel() == 0:
+            m.check(f, alpha)   # raises: f has no (H, W) to hold w against
+        wo = _check_weight(f, w, m.w)   # (in front of the device check: a CPU triple with a wrong w reports the w)
+        if m.w_zeros and w.numel() and not bool((w.detach() >= 0).all()):   # (a NaN fails the comparison too)
+            raise ValueError("%s: w must be finite and >= 0 everywhere (zeros are allowed)" % m.w)
+    *planes, N, M, am, an = m.check(f, alpha)   # planes: (O,), with channels (B, C)
+    index = f.device.index if f.device.index is not None else torch.cuda.current_device()
+    s = _solver(index, M, N, math.prod(planes))
+    fc = f.detach().contiguous()   # (of (B, C, H, W), colour image b owns the planes b*C ... b*C + C-1)
+    ac = alpha.detach().contiguous()
+    wc = (w.detach().contiguous(),) if m.w else ()
+    u = torch.empty_like(fc)
+    lead = ((planes[1],) if m.channels else ()) + ((wc[0].data_ptr(), wo) if m.w else ())
+    tape, kw = None, solver_kw
+    if m.tape:   # the tape is this call's own: a second forward pass on the handle before backward does not overwrite it
+        tape = torch.empty(getattr(s, m.tape)(**solver_kw), dtype=torch.float64, device=f.device)
+        kw = dict(tape_ptr=tape.data_ptr(), **solver_kw)
+    _sync(f.device)
+    s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
+    getattr(s, m.solve)(*lead, ac.data_ptr(), am, an, **kw)
+    s.copy_u_device(u.data_ptr())
+    # checkpoint_every= (TVSolver's keyword of that name, DESIGN.md section 4.10): the "tape" then holds the iteration state every C
+    # iterations only, and backward recomputes each segment's tape from it -- the same gradients bit for bit, one more forward
+    # solve.  That recompute reads the handle's dataset, so f is saved next to the checkpoints and backward installs it again:
+    # another forward pass on the shared solver may have replaced it.  (The weighted models save f anyway: w.grad reads it.)
+    x = u if tape is None else tape
+    keep_f = (fc,) if tape is not None and solver_kw.get("checkpoint_every") else ()
+    ctx.save_for_backward(*((x, fc, ac) + wc if m.w else (x, ac) + keep_f))
+    if jvp:
+        ctx.save_for_forward(*((u, ac) if tape is None else (fc, ac) + wc))
+        ctx.set_materialize_grads(False)   # an input without a tangent reaches jvp as None, and the library as NULL
+    ctx.solver, ctx.am, ctx.an, ctx.solver_kw = s, am, an, dict(solver_kw)
+    if m.reg:
+        ctx.reg = bool(reg)
+    if m.w:
+        ctx.wo = wo
+    if m.channels:
+        ctx.channels = planes[1]
+    return u
+
+
+def _backward(m, ctx, gu):
+    """backward of every Function: the gradients needs_input_grad asks for from one vjp call (a gradient nobody wants is a NULL
+    pointer there), one entry per argument of apply."""
+    need = ctx.needs_input_grad
+    need_f, need_a, need_w = need[0], need[1], m.w is not None and need[2]
+    if gu is None or not (need_f or need_a or need_w):
+        return (None,) * len(need)
+    x, *rest = ctx.saved_tensors   # x: u, or the tape of an unrolled model
+    f, alpha, w = rest if m.w else (rest[1] if len(rest) > 1 else None, rest[0], None)
+    gu = gu.to(dtype=torch.float64).contiguous()
+    gf = torch.empty_like(gu) if need_f else None
+    ga = None
+    if need_a:   # a shared parameter: the library's slices * am * an doubles, handed back in alpha's shape
+        ga = torch.empty_like(alpha) if m.each else torch.empty(m.slices * ctx.am * ctx.an, dtype=torch.float64, device=gu.device)
+    gw = torch.empty_like(w) if need_w else None
+    _sync(gu.device)
+    s, kw = ctx.solver, ctx.solver_kw
+    lead = ((ctx.channels,) if m.channels else ()) + (x.data_ptr(),)
+    if m.w:   # the implicit w.grad reads f through a pointer of its own, given only when it is wanted
+        lead += (() if m.tape else (_ptr(f if need_w else None),)) + (w.data_ptr(), ctx.wo)
+    if m.tape and f is not None and (need_w or kw.get("checkpoint_every")):
+        s.set_data_device(f.data_ptr(), f.data_ptr())   # the unrolled w.grad and a checkpointed sweep's recompute read the dataset
+    if m.reg:
+        kw = dict(reg=ctx.reg, **kw)
+    getattr(s, m.vjp)(*lead, alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(), _ptr(gf), _ptr(ga), *((_ptr(gw),) if m.w else ()), **kw)
+    grads = (gf, ga.reshape(alpha.shape) if need_a else None) + ((gw,) if m.w else ())
+    return grads + (None,) * (len(need) - len(grads))
+
+
+def _jvp(m, ctx, df, dalpha, dw=None):
+    """jvp of every Function that carries one: the tangents checked (None: zero; all None: zero out, no library call), then one
+    call with one direction.  An implicit model saved (u, alpha) and solves its linear system at u; an unrolled one saved
+    (f, alpha[, w]), installs f and sweeps through the iterations, reading no tape."""
+    x, alpha, *w = ctx.saved_tensors
+    df, dalpha = _tangent(df, x, "f"), _tangent(dalpha, alpha, "alpha")
+    dw = _tangent(dw, w[0], "w") if m.w else None
+    if df is None and dalpha is None and dw is None:
+        return torch.zeros_like(x)
+    du = torch.empty_like(x)
+    _sync(x.device)
+    s = ctx.solver
+    tangents = (_ptr(df), _ptr(dalpha)) + ((_ptr(dw),) if m.w else ())
+    if m.tape is None:
+        getattr(s, m.jvp)(x.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, *tangents, du.data_ptr(), ndir=1, reg=ctx.reg,
+                          **ctx.solver_kw)
+        return du
+    lead = ((ctx.channels,) if m.channels else ()) + ((w[0].data_ptr(), ctx.wo) if m.w else ())
+    s.set_data_device(x.data_ptr(), x.data_ptr())   # the sweep reads the handle's dataset
+    getattr(s, m.jvp)(*lead, alpha.data_ptr(), ctx.am, ctx.an, *tangents, du.data_ptr(), None, ndir=1,
+                      **_no_checkpoint(ctx.solver_kw))
+    return du
+
+
+# Each Function below binds the three to its row: forward and jvp with one slot per argument of apply, backward
+# once_differentiable.  A ...ForwardFunction is its base with jvp=True in forward and a jvp; backward is inherited.
 class TVDenoiseFunction(torch.autograd.Function):
     """autograd.Function of tv_denoise (below); apply(f, alpha, reg, solver_kw)."""
-
-    @staticmethod
-    def forward(ctx, f, alpha, reg, solver_kw):
-        O, N, M, am, an = _check_args(f, alpha)
-        index = f.device.index if f.device.index is not None else torch.cuda.current_device()
-        s = _solver(index, M, N, O)
-        fc = f.detach().contiguous()
-        ac = alpha.detach().contiguous()
-        u = torch.empty_like(fc)
-        _sync(f.device)
-        s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
-        s.denoise_device(ac.data_ptr(), am, an, **solver_kw)
-        s.copy_u_device(u.data_ptr())
-        ctx.save_for_backward(u, ac)
-        ctx.save_for_forward(u, ac)
-        ctx.set_materialize_grads(False)   # an input without a tangent reaches jvp as None, and the library as NULL
-        ctx.solver, ctx.am, ctx.an, ctx.reg, ctx.solver_kw = s, am, an, bool(reg), dict(solver_kw)
-        return u
-
-    @staticmethod
-    def jvp(ctx, df, dalpha, _reg, _solver_kw):
-        u, alpha = ctx.saved_tensors
-        df, dalpha = _tangent(df, u, "f"), _tangent(dalpha, alpha, "alpha")
-        if df is None and dalpha is None:
-            return torch.zeros_like(u)
-        du = torch.empty_like(u)
-        _sync(u.device)
-        ctx.solver.jvp_device(u.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, df.data_ptr() if df is not None else None,
-                              dalpha.data_ptr() if dalpha is not None else None, du.data_ptr(), ndir=1, reg=ctx.reg,
-                              **ctx.solver_kw)
-        return du
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gu):
-        need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if gu is None or not (need_f or need_a):
-            return None, None, None, None
-        u, alpha = ctx.saved_tensors
-        gu = gu.to(dtype=torch.float64).contiguous()
-        gf = torch.empty_like(u) if need_f else None
-        ga = torch.empty(ctx.am * ctx.an, dtype=torch.float64, device=u.device) if need_a else None
-        _sync(u.device)
-        ctx.solver.vjp_device(u.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(),
-                              gf.data_ptr() if need_f else None, ga.data_ptr() if need_a else None,
-                              reg=ctx.reg, **ctx.solver_kw)
-        return gf, (ga.reshape(alpha.shape) if need_a else None), None, None
+    forward = staticmethod(lambda ctx, f, alpha, reg, solver_kw: _forward(_TV, ctx, f, alpha, solver_kw, reg=reg, jvp=True))
+    jvp = staticmethod(lambda ctx, df, dalpha, _reg, _solver_kw: _jvp(_TV, ctx, df, dalpha))
+    backward = staticmethod(once_differentiable(lambda ctx, gu: _backward(_TV, ctx, gu)))
 
 
 def tv_denoise(f, alpha, *, reg=False, **solver_kw):
@@ -277,54 +437,9 @@ def tv_denoise(f, alpha, *, reg=False, **solver_kw):
 
 class TVDenoiseEachFunction(torch.autograd.Function):
     """autograd.Function of tv_denoise_each (below); apply(f, alpha, reg, solver_kw)."""
-
-    @staticmethod
-    def forward(ctx, f, alpha, reg, solver_kw):
-        O, N, M, am, an = _check_args_each(f, alpha)
-        index = f.device.index if f.device.index is not None else torch.cuda.current_device()
-        s = _solver(index, M, N, O)
-        fc = f.detach().contiguous()
-        ac = alpha.detach().contiguous()
-        u = torch.empty_like(fc)
-        _sync(f.device)
-        s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
-        s.denoise_each_device(ac.data_ptr(), am, an, **solver_kw)
-        s.copy_u_device(u.data_ptr())
-        ctx.save_for_backward(u, ac)
-        ctx.save_for_forward(u, ac)
-        ctx.set_materialize_grads(False)   # an input without a tangent reaches jvp as None, and the library as NULL
-        ctx.solver, ctx.am, ctx.an, ctx.reg, ctx.solver_kw = s, am, an, bool(reg), dict(solver_kw)
-        return u
-
-    @staticmethod
-    def jvp(ctx, df, dalpha, _reg, _solver_kw):
-        u, alpha = ctx.saved_tensors
-        df, dalpha = _tangent(df, u, "f"), _tangent(dalpha, alpha, "alpha")
-        if df is None and dalpha is None:
-            return torch.zeros_like(u)
-        du = torch.empty_like(u)
-        _sync(u.device)
-        ctx.solver.jvp_each_device(u.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an,
-                                   df.data_ptr() if df is not None else None,
-                                   dalpha.data_ptr() if dalpha is not None else None, du.data_ptr(), ndir=1,
-                                   reg=ctx.reg, **ctx.solver_kw)
-        return du
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gu):
-        need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if gu is None or not (need_f or need_a):
-            return None, None, None, None
-        u, alpha = ctx.saved_tensors
-        gu = gu.to(dtype=torch.float64).contiguous()
-        gf = torch.empty_like(u) if need_f else None
-        ga = torch.empty_like(alpha) if need_a else None
-        _sync(u.device)
-        ctx.solver.vjp_each_device(u.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(),
-                                   gf.data_ptr() if need_f else None, ga.data_ptr() if need_a else None,
-                                   reg=ctx.reg, **ctx.solver_kw)
-        return gf, ga, None, None
+    forward = staticmethod(lambda ctx, f, alpha, reg, solver_kw: _forward(_TV_EACH, ctx, f, alpha, solver_kw, reg=reg, jvp=True))
+    jvp = staticmethod(lambda ctx, df, dalpha, _reg, _solver_kw: _jvp(_TV_EACH, ctx, df, dalpha))
+    backward = staticmethod(once_differentiable(lambda ctx, gu: _backward(_TV_EACH, ctx, gu)))
 
 
 def tv_denoise_each(f, alpha, *, reg=False, **solver_kw):
@@ -351,75 +466,15 @@ class TVDenoise(torch.nn.Module):
 
 class SumRegsDenoiseFunction(torch.autograd.Function):
     """autograd.Function of sumregs_denoise (below); apply(f, alpha, reg, solver_kw)."""
-
-    @staticmethod
-    def forward(ctx, f, alpha, reg, solver_kw):
-        O, N, M, am, an = _check_args(f, alpha, slices=3)
-        index = f.device.index if f.device.index is not None else torch.cuda.current_device()
-        s = _solver(index, M, N, O)
-        fc = f.detach().contiguous()
-        ac = alpha.detach().contiguous()
-        u = torch.empty_like(fc)
-        _sync(f.device)
-        s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
-        s.sumregs_denoise_device(ac.data_ptr(), am, an, **solver_kw)
-        s.copy_u_device(u.data_ptr())
-        ctx.save_for_backward(u, ac)
-        ctx.solver, ctx.am, ctx.an, ctx.reg, ctx.solver_kw = s, am, an, bool(reg), dict(solver_kw)
-        return u
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gu):
-        need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (need_f or need_a):
-            return None, None, None, None
-        u, alpha = ctx.saved_tensors
-        gu = gu.to(dtype=torch.float64).contiguous()
-        gf = torch.empty_like(u) if need_f else None
-        ga = torch.empty(3 * ctx.am * ctx.an, dtype=torch.float64, device=u.device) if need_a else None
-        _sync(u.device)
-        ctx.solver.sumregs_vjp_device(u.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(),
-                                      gf.data_ptr() if need_f else None, ga.data_ptr() if need_a else None,
-                                      reg=ctx.reg, **ctx.solver_kw)
-        return gf, (ga.reshape(alpha.shape) if need_a else None), None, None
-
-
-def _sumregs_jvp(ctx, df, dalpha, each):
-    """The tangent of u for the forward-mode functions below: one bpltv_sumregs_jvp(_each)_device call, one direction."""
-    u, alpha = ctx.saved_tensors
-    df, dalpha = _tangent(df, u, "f"), _tangent(dalpha, alpha, "alpha")
-    if df is None and dalpha is None:
-        return torch.zeros_like(u)
-    du = torch.empty_like(u)
-    _sync(u.device)
-    call = ctx.solver.sumregs_jvp_each_device if each else ctx.solver.sumregs_jvp_device
-    call(u.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, df.data_ptr() if df is not None else None,
-         dalpha.data_ptr() if dalpha is not None else None, du.data_ptr(), ndir=1, reg=ctx.reg, **ctx.solver_kw)
-    return du
+    forward = staticmethod(lambda ctx, f, alpha, reg, solver_kw: _forward(_SUMREGS, ctx, f, alpha, solver_kw, reg=reg))
+    backward = staticmethod(once_differentiable(lambda ctx, gu: _backward(_SUMREGS, ctx, gu)))
 
 
 class SumRegsDenoiseForwardFunction(SumRegsDenoiseFunction):
     """SumRegsDenoiseFunction with a jvp (sumregs_denoise(..., forward_mode=True)): forward and backward are the base
     class's, save_for_forward and set_materialize_grads(False) as the TV functions have them."""
-
-    @staticmethod
-    def forward(ctx, f, alpha, reg, solver_kw):
-        u = SumRegsDenoiseFunction.forward(ctx, f, alpha, reg, solver_kw)
-        ctx.save_for_forward(u, alpha.detach().contiguous())   # what the base class saved for backward
-        ctx.set_materialize_grads(False)   # an input without a tangent reaches jvp as None, and the library as NULL
-        return u
-
-    @staticmethod
-    def jvp(ctx, df, dalpha, _reg, _solver_kw):
-        return _sumregs_jvp(ctx, df, dalpha, False)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gu):
-        if gu is None:
-            return None, None, None, None
-        return SumRegsDenoiseFunction.backward(ctx, gu)
+    forward = staticmethod(lambda ctx, f, alpha, reg, solver_kw: _forward(_SUMREGS, ctx, f, alpha, solver_kw, reg=reg, jvp=True))
+    jvp = staticmethod(lambda ctx, df, dalpha, _reg, _solver_kw: _jvp(_SUMREGS, ctx, df, dalpha))
 
 
 def sumregs_denoise(f, alpha, *, reg=False, forward_mode=False, **solver_kw):
@@ -434,60 +489,14 @@ def sumregs_denoise(f, alpha, *, reg=False, forward_mode=False, **solver_kw):
 
 class SumRegsDenoiseEachFunction(torch.autograd.Function):
     """autograd.Function of sumregs_denoise_each (below); apply(f, alpha, reg, solver_kw)."""
-
-    @staticmethod
-    def forward(ctx, f, alpha, reg, solver_kw):
-        O, N, M, am, an = _check_args_each(f, alpha, slices=3)
-        index = f.device.index if f.device.index is not None else torch.cuda.current_device()
-        s = _solver(index, M, N, O)
-        fc = f.detach().contiguous()
-        ac = alpha.detach().contiguous()
-        u = torch.empty_like(fc)
-        _sync(f.device)
-        s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
-        s.sumregs_denoise_each_device(ac.data_ptr(), am, an, **solver_kw)
-        s.copy_u_device(u.data_ptr())
-        ctx.save_for_backward(u, ac)
-        ctx.solver, ctx.am, ctx.an, ctx.reg, ctx.solver_kw = s, am, an, bool(reg), dict(solver_kw)
-        return u
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gu):
-        need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (need_f or need_a):
-            return None, None, None, None
-        u, alpha = ctx.saved_tensors
-        gu = gu.to(dtype=torch.float64).contiguous()
-        gf = torch.empty_like(u) if need_f else None
-        ga = torch.empty_like(alpha) if need_a else None
-        _sync(u.device)
-        ctx.solver.sumregs_vjp_each_device(u.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(),
-                                           gf.data_ptr() if need_f else None, ga.data_ptr() if need_a else None,
-                                           reg=ctx.reg, **ctx.solver_kw)
-        return gf, ga, None, None
+    forward = staticmethod(lambda ctx, f, alpha, reg, solver_kw: _forward(_SUMREGS_EACH, ctx, f, alpha, solver_kw, reg=reg))
+    backward = staticmethod(once_differentiable(lambda ctx, gu: _backward(_SUMREGS_EACH, ctx, gu)))
 
 
 class SumRegsDenoiseEachForwardFunction(SumRegsDenoiseEachFunction):
     """SumRegsDenoiseEachFunction with a jvp (sumregs_denoise_each(..., forward_mode=True))."""
-
-    @staticmethod
-    def forward(ctx, f, alpha, reg, solver_kw):
-        u = SumRegsDenoiseEachFunction.forward(ctx, f, alpha, reg, solver_kw)
-        ctx.save_for_forward(u, alpha.detach().contiguous())   # what the base class saved for backward
-        ctx.set_materialize_grads(False)   # an input without a tangent reaches jvp as None, and the library as NULL
-        return u
-
-    @staticmethod
-    def jvp(ctx, df, dalpha, _reg, _solver_kw):
-        return _sumregs_jvp(ctx, df, dalpha, True)
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gu):
-        if gu is None:
-            return None, None, None, None
-        return SumRegsDenoiseEachFunction.backward(ctx, gu)
+    forward = staticmethod(lambda ctx, f, alpha, reg, solver_kw: _forward(_SUMREGS_EACH, ctx, f, alpha, solver_kw, reg=reg, jvp=True))
+    jvp = staticmethod(lambda ctx, df, dalpha, _reg, _solver_kw: _jvp(_SUMREGS_EACH, ctx, df, dalpha))
 
 
 def sumregs_denoise_each(f, alpha, *, reg=False, forward_mode=False, **solver_kw):
@@ -514,65 +523,10 @@ class SumRegsDenoise(torch.nn.Module):
         return sumregs_denoise(f, self.alpha, reg=self.reg, forward_mode=self.forward_mode, **self.solver_kw)
 
 
-def _check_weight(f, w, name="tv_denoise_weighted"):
-    """wo (1 or B) of a valid weight for f; TypeError / ValueError before any library call."""
-    if not isinstance(w, torch.Tensor):
-        raise TypeError("%s: w must be a torch tensor" % name)
-    if w.dtype != torch.float64:
-        raise TypeError("%s: w must be float64 (got %s)" % (name, w.dtype))
-    H, W = f.shape[-2], f.shape[-1]
-    if tuple(w.shape) == (H, W):
-        wo = 1
-    elif f.dim() == 3 and tuple(w.shape) == tuple(f.shape):
-        wo = f.shape[0]
-    else:
-        raise ValueError("%s: w must have shape (%d, %d) or f's shape %s; got %s"
-                         % (name, H, W, tuple(f.shape), tuple(w.shape)))
-    if w.device != f.device:
-        raise ValueError("%s: w is on %s, f on %s" % (name, w.device, f.device))
-    return wo
-
-
 class TVDenoiseWeightedFunction(torch.autograd.Function):
     """autograd.Function of tv_denoise_weighted (below); apply(f, alpha, w, solver_kw).  No jvp."""
-
-    @staticmethod
-    def forward(ctx, f, alpha, w, solver_kw):
-        if not isinstance(f, torch.Tensor) or f.dim() not in (2, 3) or f.numel() == 0:
-            _check_args(f, alpha)   # raises: f has no (H, W) to hold w against
-        wo = _check_weight(f, w)    # (in front of the device check: a CPU triple with a wrong w reports the w)
-        O, N, M, am, an = _check_args(f, alpha)
-        index = f.device.index if f.device.index is not None else torch.cuda.current_device()
-        s = _solver(index, M, N, O)
-        fc = f.detach().contiguous()
-        ac = alpha.detach().contiguous()
-        wc = w.detach().contiguous()
-        u = torch.empty_like(fc)
-        _sync(f.device)
-        s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
-        s.weighted_denoise_device(wc.data_ptr(), wo, ac.data_ptr(), am, an, **solver_kw)
-        s.copy_u_device(u.data_ptr())
-        ctx.save_for_backward(u, fc, ac, wc)
-        ctx.solver, ctx.am, ctx.an, ctx.wo, ctx.solver_kw = s, am, an, wo, dict(solver_kw)
-        return u
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gu):
-        need_f, need_a, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        if not (need_f or need_a or need_w):
-            return None, None, None, None
-        u, f, alpha, w = ctx.saved_tensors
-        gu = gu.to(dtype=torch.float64).contiguous()
-        gf = torch.empty_like(u) if need_f else None
-        ga = torch.empty(ctx.am * ctx.an, dtype=torch.float64, device=u.device) if need_a else None
-        gw = torch.empty_like(w) if need_w else None
-        _sync(u.device)
-        ctx.solver.weighted_vjp_device(u.data_ptr(), f.data_ptr() if need_w else None, w.data_ptr(), ctx.wo,
-                                       alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(),
-                                       gf.data_ptr() if need_f else None, ga.data_ptr() if need_a else None,
-                                       gw.data_ptr() if need_w else None, **ctx.solver_kw)
-        return gf, (ga.reshape(alpha.shape) if need_a else None), gw, None
+    forward = staticmethod(lambda ctx, f, alpha, w, solver_kw: _forward(_WEIGHTED, ctx, f, alpha, solver_kw, w=w))
+    backward = staticmethod(once_differentiable(lambda ctx, gu: _backward(_WEIGHTED, ctx, gu)))
 
 
 def tv_denoise_weighted(f, alpha, w, **solver_kw):
@@ -583,111 +537,23 @@ def tv_denoise_weighted(f, alpha, w, **solver_kw):
     return TVDenoiseWeightedFunction.apply(f, alpha, w, solver_kw)
 
 
-# checkpoint_every= of the unrolled layers (TVSolver's keyword of that name): the "tape" the forward pass
-# allocates then holds the iteration state every C iterations only, and backward recomputes each segment's tape from it -- the
-# same gradients bit for bit, one more forward solve.  That recompute reads the handle's dataset, so forward saves f next to the
-# checkpoints and backward installs it again: another forward pass on the shared solver may have replaced it.
-def _checkpoint_f(solver_kw, fc):
-    return (fc,) if solver_kw.get("checkpoint_every") else ()
-
-
-def _reinstall(solver, f):
-    if f:
-        solver.set_data_device(f[0].data_ptr(), f[0].data_ptr())
-
-
-def _no_checkpoint(solver_kw):
-    """solver_kw for a tangent sweep, which reads no tape."""
-    return {k: v for k, v in solver_kw.items() if k != "checkpoint_every"}
-
-
 def _with_checkpoint(solver_kw, checkpoint_every):
+    """solver_kw with the unrolled layers' checkpoint_every= in it (_forward says what it does)."""
     return solver_kw if checkpoint_every is None else dict(solver_kw, checkpoint_every=int(checkpoint_every))
 
 
 class TVDenoiseWeightedUnrolledFunction(torch.autograd.Function):
     """autograd.Function of tv_denoise_weighted_unrolled (below); apply(f, alpha, w, solver_kw).  No jvp."""
-
-    @staticmethod
-    def forward(ctx, f, alpha, w, solver_kw):
-        name = "tv_denoise_weighted_unrolled"
-        if not isinstance(f, torch.Tensor) or f.dim() not in (2, 3) or f.numel() == 0:
-            _check_args(f, alpha)   # raises: f has no (H, W) to hold w against
-        wo = _check_weight(f, w, name)   # (in front of the device check: a CPU triple with a wrong w reports the w)
-        if w.numel() and not bool((w.detach() >= 0).all()):   # (a NaN fails the comparison too)
-            raise ValueError("%s: w must be finite and >= 0 everywhere (zeros are allowed)" % name)
-        O, N, M, am, an = _check_args(f, alpha)
-        index = f.device.index if f.device.index is not None else torch.cuda.current_device()
-        s = _solver(index, M, N, O)
-        fc = f.detach().contiguous()
-        ac = alpha.detach().contiguous()
-        wc = w.detach().contiguous()
-        u = torch.empty_like(fc)
-        # the tape is this call's own: a second forward pass on the handle before backward does not overwrite it
-        tape = torch.empty(s.weighted_unrolled_tape_doubles(**solver_kw), dtype=torch.float64, device=f.device)
-        _sync(f.device)
-        s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
-        s.weighted_unrolled_denoise_device(wc.data_ptr(), wo, ac.data_ptr(), am, an, tape_ptr=tape.data_ptr(), **solver_kw)
-        s.copy_u_device(u.data_ptr())
-        ctx.save_for_backward(tape, fc, ac, wc)
-        ctx.solver, ctx.am, ctx.an, ctx.wo, ctx.solver_kw = s, am, an, wo, dict(solver_kw)
-        return u
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gu):
-        need_f, need_a, need_w = ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[2]
-        if not (need_f or need_a or need_w):
-            return None, None, None, None
-        tape, f, alpha, w = ctx.saved_tensors
-        gu = gu.to(dtype=torch.float64).contiguous()
-        gf = torch.empty_like(gu) if need_f else None
-        ga = torch.empty(ctx.am * ctx.an, dtype=torch.float64, device=gu.device) if need_a else None
-        gw = torch.empty_like(w) if need_w else None
-        _sync(gu.device)
-        if need_w or ctx.solver_kw.get("checkpoint_every"):   # grad_w, and a checkpointed sweep's recompute, read the handle's dataset
-            ctx.solver.set_data_device(f.data_ptr(), f.data_ptr())
-        ctx.solver.weighted_unrolled_vjp_device(tape.data_ptr(), w.data_ptr(), ctx.wo, alpha.data_ptr(), ctx.am, ctx.an,
-                                                gu.data_ptr(), gf.data_ptr() if need_f else None,
-                                                ga.data_ptr() if need_a else None, gw.data_ptr() if need_w else None,
-                                                **ctx.solver_kw)
-        return gf, (ga.reshape(alpha.shape) if need_a else None), gw, None
+    forward = staticmethod(lambda ctx, f, alpha, w, solver_kw: _forward(_WEIGHTED_UNROLLED, ctx, f, alpha, solver_kw, w=w))
+    backward = staticmethod(once_differentiable(lambda ctx, gu: _backward(_WEIGHTED_UNROLLED, ctx, gu)))
 
 
 class TVDenoiseWeightedUnrolledForwardFunction(TVDenoiseWeightedUnrolledFunction):
     """TVDenoiseWeightedUnrolledFunction with a jvp (tv_denoise_weighted_unrolled(..., forward_mode=True)): forward is the
     base class's taped solve, so backward keeps working; the jvp is one tangent sweep through the weighted iterations
     (TVSolver.weighted_unrolled_jvp_device, one direction), which reads no tape."""
-
-    @staticmethod
-    def forward(ctx, f, alpha, w, solver_kw):
-        u = TVDenoiseWeightedUnrolledFunction.forward(ctx, f, alpha, w, solver_kw)
-        ctx.save_for_forward(f.detach().contiguous(), alpha.detach().contiguous(), w.detach().contiguous())
-        ctx.set_materialize_grads(False)   # an input without a tangent reaches jvp as None, and the library as NULL
-        return u
-
-    @staticmethod
-    def jvp(ctx, df, dalpha, dw, _solver_kw):
-        f, alpha, w = ctx.saved_tensors
-        df, dalpha, dw = _tangent(df, f, "f"), _tangent(dalpha, alpha, "alpha"), _tangent(dw, w, "w")
-        if df is None and dalpha is None and dw is None:
-            return torch.zeros_like(f)
-        du = torch.empty_like(f)
-        _sync(f.device)
-        ctx.solver.set_data_device(f.data_ptr(), f.data_ptr())   # the sweep reads the handle's dataset
-        ctx.solver.weighted_unrolled_jvp_device(w.data_ptr(), ctx.wo, alpha.data_ptr(), ctx.am, ctx.an,
-                                                df.data_ptr() if df is not None else None,
-                                                dalpha.data_ptr() if dalpha is not None else None,
-                                                dw.data_ptr() if dw is not None else None, du.data_ptr(), None, ndir=1,
-                                                **_no_checkpoint(ctx.solver_kw))
-        return du
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gu):
-        if gu is None:
-            return None, None, None, None
-        return TVDenoiseWeightedUnrolledFunction.backward(ctx, gu)
+    forward = staticmethod(lambda ctx, f, alpha, w, solver_kw: _forward(_WEIGHTED_UNROLLED, ctx, f, alpha, solver_kw, w=w, jvp=True))
+    jvp = staticmethod(lambda ctx, df, dalpha, dw, _solver_kw: _jvp(_WEIGHTED_UNROLLED, ctx, df, dalpha, dw))
 
 
 def tv_denoise_weighted_unrolled(f, alpha, w, maxiter=50, checkpoint_every=None, forward_mode=False, **solver_kw):
@@ -707,148 +573,30 @@ def tv_denoise_weighted_unrolled(f, alpha, w, maxiter=50, checkpoint_every=None,
 
 class TVDenoiseUnrolledFunction(torch.autograd.Function):
     """autograd.Function of tv_denoise_unrolled (below); apply(f, alpha, solver_kw).  No jvp."""
-
-    @staticmethod
-    def forward(ctx, f, alpha, solver_kw):
-        O, N, M, am, an = _check_args(f, alpha)
-        index = f.device.index if f.device.index is not None else torch.cuda.current_device()
-        s = _solver(index, M, N, O)
-        fc = f.detach().contiguous()
-        ac = alpha.detach().contiguous()
-        u = torch.empty_like(fc)
-        # the tape is this call's own: a second forward pass on the handle before backward does not overwrite it
-        tape = torch.empty(s.unrolled_tape_doubles(**solver_kw), dtype=torch.float64, device=f.device)
-        _sync(f.device)
-        s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
-        s.unrolled_denoise_device(ac.data_ptr(), am, an, tape_ptr=tape.data_ptr(), **solver_kw)
-        s.copy_u_device(u.data_ptr())
-        ctx.save_for_backward(tape, ac, *_checkpoint_f(solver_kw, fc))
-        ctx.solver, ctx.am, ctx.an, ctx.solver_kw = s, am, an, dict(solver_kw)
-        return u
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gu):
-        need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (need_f or need_a):
-            return None, None, None
-        tape, alpha, *f = ctx.saved_tensors
-        gu = gu.to(dtype=torch.float64).contiguous()
-        gf = torch.empty_like(gu) if need_f else None
-        ga = torch.empty(ctx.am * ctx.an, dtype=torch.float64, device=gu.device) if need_a else None
-        _sync(gu.device)
-        _reinstall(ctx.solver, f)
-        ctx.solver.unrolled_vjp_device(tape.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(),
-                                       gf.data_ptr() if need_f else None, ga.data_ptr() if need_a else None,
-                                       **ctx.solver_kw)
-        return gf, (ga.reshape(alpha.shape) if need_a else None), None
+    forward = staticmethod(lambda ctx, f, alpha, solver_kw: _forward(_UNROLLED, ctx, f, alpha, solver_kw))
+    backward = staticmethod(once_differentiable(lambda ctx, gu: _backward(_UNROLLED, ctx, gu)))
 
 
 class TVDenoiseUnrolledForwardFunction(TVDenoiseUnrolledFunction):
     """TVDenoiseUnrolledFunction with a jvp (tv_denoise_unrolled(..., forward_mode=True)): forward is the base class's
     taped solve, so backward keeps working; the jvp is one tangent sweep through the iterations
     (TVSolver.unrolled_jvp_device, one direction), which reads no tape."""
-
-    @staticmethod
-    def forward(ctx, f, alpha, solver_kw):
-        u = TVDenoiseUnrolledFunction.forward(ctx, f, alpha, solver_kw)
-        ctx.save_for_forward(f.detach().contiguous(), alpha.detach().contiguous())
-        ctx.set_materialize_grads(False)   # an input without a tangent reaches jvp as None, and the library as NULL
-        return u
-
-    @staticmethod
-    def jvp(ctx, df, dalpha, _solver_kw):
-        f, alpha = ctx.saved_tensors
-        df, dalpha = _tangent(df, f, "f"), _tangent(dalpha, alpha, "alpha")
-        if df is None and dalpha is None:
-            return torch.zeros_like(f)
-        du = torch.empty_like(f)
-        _sync(f.device)
-        ctx.solver.set_data_device(f.data_ptr(), f.data_ptr())   # the sweep reads the handle's dataset
-        ctx.solver.unrolled_jvp_device(alpha.data_ptr(), ctx.am, ctx.an, df.data_ptr() if df is not None else None,
-                                       dalpha.data_ptr() if dalpha is not None else None, du.data_ptr(), None, ndir=1,
-                                       **_no_checkpoint(ctx.solver_kw))
-        return du
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gu):
-        if gu is None:
-            return None, None, None
-        return TVDenoiseUnrolledFunction.backward(ctx, gu)
+    forward = staticmethod(lambda ctx, f, alpha, solver_kw: _forward(_UNROLLED, ctx, f, alpha, solver_kw, jvp=True))
+    jvp = staticmethod(lambda ctx, df, dalpha, _solver_kw: _jvp(_UNROLLED, ctx, df, dalpha))
 
 
 class TVDenoiseUnrolledEachFunction(torch.autograd.Function):
     """autograd.Function of tv_denoise_unrolled_each (below); apply(f, alpha, solver_kw).  No jvp."""
-
-    @staticmethod
-    def forward(ctx, f, alpha, solver_kw):
-        O, N, M, am, an = _check_args_each(f, alpha, name="tv_denoise_unrolled_each")
-        index = f.device.index if f.device.index is not None else torch.cuda.current_device()
-        s = _solver(index, M, N, O)
-        fc = f.detach().contiguous()
-        ac = alpha.detach().contiguous()
-        u = torch.empty_like(fc)
-        # the tape is this call's own: a second forward pass on the handle before backward does not overwrite it
-        tape = torch.empty(s.unrolled_tape_doubles(**solver_kw), dtype=torch.float64, device=f.device)
-        _sync(f.device)
-        s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
-        s.unrolled_denoise_each_device(ac.data_ptr(), am, an, tape_ptr=tape.data_ptr(), **solver_kw)
-        s.copy_u_device(u.data_ptr())
-        ctx.save_for_backward(tape, ac, *_checkpoint_f(solver_kw, fc))
-        ctx.solver, ctx.am, ctx.an, ctx.solver_kw = s, am, an, dict(solver_kw)
-        return u
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gu):
-        need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (need_f or need_a):
-            return None, None, None
-        tape, alpha, *f = ctx.saved_tensors
-        gu = gu.to(dtype=torch.float64).contiguous()
-        gf = torch.empty_like(gu) if need_f else None
-        ga = torch.empty_like(alpha) if need_a else None
-        _sync(gu.device)
-        _reinstall(ctx.solver, f)
-        ctx.solver.unrolled_vjp_each_device(tape.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(),
-                                            gf.data_ptr() if need_f else None, ga.data_ptr() if need_a else None,
-                                            **ctx.solver_kw)
-        return gf, ga, None
+    forward = staticmethod(lambda ctx, f, alpha, solver_kw: _forward(_UNROLLED_EACH, ctx, f, alpha, solver_kw))
+    backward = staticmethod(once_differentiable(lambda ctx, gu: _backward(_UNROLLED_EACH, ctx, gu)))
 
 
 class TVDenoiseUnrolledEachForwardFunction(TVDenoiseUnrolledEachFunction):
     """TVDenoiseUnrolledEachFunction with a jvp (tv_denoise_unrolled_each(..., forward_mode=True)): forward is the base
     class's taped solve, so backward keeps working; the jvp is one tangent sweep through the iterations
     (TVSolver.unrolled_jvp_each_device, one direction), which reads no tape."""
-
-    @staticmethod
-    def forward(ctx, f, alpha, solver_kw):
-        u = TVDenoiseUnrolledEachFunction.forward(ctx, f, alpha, solver_kw)
-        ctx.save_for_forward(f.detach().contiguous(), alpha.detach().contiguous())
-        ctx.set_materialize_grads(False)   # an input without a tangent reaches jvp as None, and the library as NULL
-        return u
-
-    @staticmethod
-    def jvp(ctx, df, dalpha, _solver_kw):
-        f, alpha = ctx.saved_tensors
-        df, dalpha = _tangent(df, f, "f"), _tangent(dalpha, alpha, "alpha")
-        if df is None and dalpha is None:
-            return torch.zeros_like(f)
-        du = torch.empty_like(f)
-        _sync(f.device)
-        ctx.solver.set_data_device(f.data_ptr(), f.data_ptr())   # the sweep reads the handle's dataset
-        ctx.solver.unrolled_jvp_each_device(alpha.data_ptr(), ctx.am, ctx.an, df.data_ptr() if df is not None else None,
-                                            dalpha.data_ptr() if dalpha is not None else None, du.data_ptr(), None,
-                                            ndir=1, **_no_checkpoint(ctx.solver_kw))
-        return du
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gu):
-        if gu is None:
-            return None, None, None
-        return TVDenoiseUnrolledEachFunction.backward(ctx, gu)
+    forward = staticmethod(lambda ctx, f, alpha, solver_kw: _forward(_UNROLLED_EACH, ctx, f, alpha, solver_kw, jvp=True))
+    jvp = staticmethod(lambda ctx, df, dalpha, _solver_kw: _jvp(_UNROLLED_EACH, ctx, df, dalpha))
 
 
 def tv_denoise_unrolled_each(f, alpha, forward_mode=False, checkpoint_every=None, **solver_kw):
@@ -899,42 +647,13 @@ class SumRegsDenoiseUnrolledFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, f, alpha, each, solver_kw):
-        if each:
-            O, N, M, am, an = _check_args_each(f, alpha, slices=3, name="sumregs_denoise_unrolled_each")
-        else:
-            O, N, M, am, an = _check_args(f, alpha, slices=3)
-        index = f.device.index if f.device.index is not None else torch.cuda.current_device()
-        s = _solver(index, M, N, O)
-        fc = f.detach().contiguous()
-        ac = alpha.detach().contiguous()
-        u = torch.empty_like(fc)
-        # the tape is this call's own: a second forward pass on the handle before backward does not overwrite it
-        tape = torch.empty(s.sumregs_unrolled_tape_doubles(**solver_kw), dtype=torch.float64, device=f.device)
-        _sync(f.device)
-        s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
-        solve = s.sumregs_unrolled_denoise_each_device if each else s.sumregs_unrolled_denoise_device
-        solve(ac.data_ptr(), am, an, tape_ptr=tape.data_ptr(), **solver_kw)
-        s.copy_u_device(u.data_ptr())
-        ctx.save_for_backward(tape, ac, *_checkpoint_f(solver_kw, fc))
-        ctx.solver, ctx.am, ctx.an, ctx.each, ctx.solver_kw = s, am, an, bool(each), dict(solver_kw)
-        return u
+        ctx.each = bool(each)
+        return _forward(_SUMREGS_UNROLLED_EACH if each else _SUMREGS_UNROLLED, ctx, f, alpha, solver_kw)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, gu):
-        need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (need_f or need_a):
-            return None, None, None, None
-        tape, alpha, *f = ctx.saved_tensors
-        gu = gu.to(dtype=torch.float64).contiguous()
-        gf = torch.empty_like(gu) if need_f else None
-        ga = torch.empty_like(alpha) if need_a else None
-        _sync(gu.device)
-        _reinstall(ctx.solver, f)
-        vjp = ctx.solver.sumregs_unrolled_vjp_each_device if ctx.each else ctx.solver.sumregs_unrolled_vjp_device
-        vjp(tape.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(), gf.data_ptr() if need_f else None,
-            ga.data_ptr() if need_a else None, **ctx.solver_kw)
-        return gf, ga, None, None
+        return _backward(_SUMREGS_UNROLLED_EACH if ctx.each else _SUMREGS_UNROLLED, ctx, gu)
 
 
 def _no_forward_mode(name, forward_mode):
@@ -979,107 +698,18 @@ class SumRegsDenoiseUnrolled(torch.nn.Module):
 
 
 # ---- channel-coupled TV for colour images (TVSolver.color_unrolled_*): the planes of a colour image share one projection ----
-def _check_args_color(f, alpha):
-    """(B, C, H, W, am, an) of a valid (f, alpha) pair of tv_denoise_color_unrolled; TypeError / ValueError before any
-    library call."""
-    name = "tv_denoise_color_unrolled"
-    if not isinstance(f, torch.Tensor) or not isinstance(alpha, torch.Tensor):
-        raise TypeError("%s: f and alpha must be torch tensors" % name)
-    if f.dtype != torch.float64 or alpha.dtype != torch.float64:
-        raise TypeError("%s: f and alpha must be float64 (got %s, %s)" % (name, f.dtype, alpha.dtype))
-    if f.dim() not in (3, 4) or f.numel() == 0:
-        raise ValueError("%s: f must have shape (B, C, H, W) or (C, H, W), got %s" % (name, tuple(f.shape)))
-    C, H, W = f.shape[-3], f.shape[-2], f.shape[-1]
-    B = f.shape[0] if f.dim() == 4 else 1
-    if not 1 <= C <= 4:
-        raise ValueError("%s: f has %d channels (1 ... 4)" % (name, C))
-    shape = tuple(alpha.shape)
-    if shape == ():
-        am = an = 1
-    elif len(shape) == 2 and 1 <= shape[0] <= H and 1 <= shape[1] <= W:
-        an, am = shape
-    else:
-        raise ValueError("%s: alpha must be 0-dim, (pH, pW) with pH <= %d, pW <= %d, or (%d, %d); got %s"
-                         % (name, H, W, H, W, shape))
-    if alpha.device != f.device:
-        raise ValueError("%s: alpha is on %s, f on %s" % (name, alpha.device, f.device))
-    if f.device.type != "cuda":
-        raise ValueError("%s: f must be on a ROCm device, got %s" % (name, f.device))
-    return B, C, H, W, am, an
-
-
 class TVDenoiseColorUnrolledFunction(torch.autograd.Function):
     """autograd.Function of tv_denoise_color_unrolled (below); apply(f, alpha, solver_kw).  No jvp."""
-
-    @staticmethod
-    def forward(ctx, f, alpha, solver_kw):
-        B, C, N, M, am, an = _check_args_color(f, alpha)
-        index = f.device.index if f.device.index is not None else torch.cuda.current_device()
-        s = _solver(index, M, N, B * C)
-        fc = f.detach().contiguous()   # (B, C, H, W): colour image b owns the planes b*C ... b*C + C-1
-        ac = alpha.detach().contiguous()
-        u = torch.empty_like(fc)
-        # the tape is this call's own: a second forward pass on the handle before backward does not overwrite it
-        tape = torch.empty(s.unrolled_tape_doubles(**solver_kw), dtype=torch.float64, device=f.device)
-        _sync(f.device)
-        s.set_data_device(fc.data_ptr(), fc.data_ptr())   # ubar is not used by a solve
-        s.color_unrolled_denoise_device(C, ac.data_ptr(), am, an, tape_ptr=tape.data_ptr(), **solver_kw)
-        s.copy_u_device(u.data_ptr())
-        ctx.save_for_backward(tape, ac, *_checkpoint_f(solver_kw, fc))
-        ctx.solver, ctx.channels, ctx.am, ctx.an, ctx.solver_kw = s, C, am, an, dict(solver_kw)
-        return u
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gu):
-        need_f, need_a = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
-        if not (need_f or need_a):
-            return None, None, None
-        tape, alpha, *f = ctx.saved_tensors
-        gu = gu.to(dtype=torch.float64).contiguous()
-        gf = torch.empty_like(gu) if need_f else None
-        ga = torch.empty(ctx.am * ctx.an, dtype=torch.float64, device=gu.device) if need_a else None
-        _sync(gu.device)
-        _reinstall(ctx.solver, f)
-        ctx.solver.color_unrolled_vjp_device(ctx.channels, tape.data_ptr(), alpha.data_ptr(), ctx.am, ctx.an, gu.data_ptr(),
-                                             gf.data_ptr() if need_f else None, ga.data_ptr() if need_a else None,
-                                             **ctx.solver_kw)
-        return gf, (ga.reshape(alpha.shape) if need_a else None), None
+    forward = staticmethod(lambda ctx, f, alpha, solver_kw: _forward(_COLOR_UNROLLED, ctx, f, alpha, solver_kw))
+    backward = staticmethod(once_differentiable(lambda ctx, gu: _backward(_COLOR_UNROLLED, ctx, gu)))
 
 
 class TVDenoiseColorUnrolledForwardFunction(TVDenoiseColorUnrolledFunction):
     """TVDenoiseColorUnrolledFunction with a jvp (tv_denoise_color_unrolled(..., forward_mode=True)): forward is the base
     class's taped solve, so backward keeps working; the jvp is one tangent sweep through the channel-coupled iterations
     (TVSolver.color_unrolled_jvp_device, one direction), which reads no tape."""
-
-    @staticmethod
-    def forward(ctx, f, alpha, solver_kw):
-        u = TVDenoiseColorUnrolledFunction.forward(ctx, f, alpha, solver_kw)
-        ctx.save_for_forward(f.detach().contiguous(), alpha.detach().contiguous())
-        ctx.set_materialize_grads(False)   # an input without a tangent reaches jvp as None, and the library as NULL
-        return u
-
-    @staticmethod
-    def jvp(ctx, df, dalpha, _solver_kw):
-        f, alpha = ctx.saved_tensors
-        df, dalpha = _tangent(df, f, "f"), _tangent(dalpha, alpha, "alpha")
-        if df is None and dalpha is None:
-            return torch.zeros_like(f)
-        du = torch.empty_like(f)
-        _sync(f.device)
-        ctx.solver.set_data_device(f.data_ptr(), f.data_ptr())   # the sweep reads the handle's dataset
-        ctx.solver.color_unrolled_jvp_device(ctx.channels, alpha.data_ptr(), ctx.am, ctx.an,
-                                             df.data_ptr() if df is not None else None,
-                                             dalpha.data_ptr() if dalpha is not None else None, du.data_ptr(), None, ndir=1,
-                                             **_no_checkpoint(ctx.solver_kw))
-        return du
-
-    @staticmethod
-    @once_differentiable
-    def backward(ctx, gu):
-        if gu is None:
-            return None, None, None
-        return TVDenoiseColorUnrolledFunction.backward(ctx, gu)
+    forward = staticmethod(lambda ctx, f, alpha, solver_kw: _forward(_COLOR_UNROLLED, ctx, f, alpha, solver_kw, jvp=True))
+    jvp = staticmethod(lambda ctx, df, dalpha, _solver_kw: _jvp(_COLOR_UNROLLED, ctx, df, dalpha))
 
 
 def tv_denoise_color_unrolled(f, alpha, maxiter=50, checkpoint_every=None, forward_mode=False, **solver_kw):
