@@ -253,11 +253,13 @@ def test_rows_kernel_alpha_modes_and_huber(gpu_solver_cls, oracle, amode):
             assert np.array_equal(u, u0), (amode, rho, variant, T_)
     s.close()
     s = gpu_solver_cls(60, 300, 1)
-    s.set_data(*synth_batch(1, 300, 60, seed=2))
+    ub, f = synth_batch(1, 300, 60, seed=2)
+    s.set_data(ub, f)
     with pytest.raises(RuntimeError, match="at least 64x64"):
         s.denoise(0.1, maxiter=8, variant=19)
     u = s.denoise(0.1, maxiter=8)                          # automatic plan: the 48x48 tile kernel
     assert s.stats()["region_i"] == 48
+    assert np.array_equal(u, oracle.pdhg(f, 0.1, maxiter=8))
     s.close()
 
 
