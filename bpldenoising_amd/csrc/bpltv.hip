@@ -216,7 +216,9 @@ struct GraphKey {
                        // 9 ... 16 = its tangent sweep, by the tangents it reads, its planes here;
                        // MODEL_SRUN: the tape as well, variant 0 = taped solve, 1 = reverse sweep;
                        // MODEL_COLOR: the tape as well (nullptr: none), variant 10 * channels + 0 = taped solve, + 1 = reverse sweep,
-                       // + 2 = the solve without a tape, + 4 ... 6 = its tangent sweep, by the tangents it reads, its planes here)
+                       // + 2 = the solve without a tape, + 4 ... 6 = its tangent sweep, by the tangents it reads, its planes here;
+                       // 100 + 10 * channels + 0 / 2 / 3 / 4 = the weighted form's taped solve, plain solve and reverse sweep
+                       // without / with grad_w)
     const void* tab;   // step table (one per (maxiter, steps, L, dual-first shift, gamma): TabKey)
     int from_state;    // 1: the sequence starts from a prepared state (params.init / order), not from x = f, y = 0
     const void* alpha; // the parameter the launches read: a sweep's blocks and the dataset's parameter are different
@@ -509,6 +511,9 @@ struct bpltv_handle {
     // that many planes per colour image (0: another model's)
     Tape ctape;
     int last_channels = 0;
+    // ... and of its weighted form: a fifth tape, in the weighted tape's layout, that remembers the
+    // channels, the weight planes and gamma = min w it was recorded with; the reverse sweep runs in d_unr and d_unr_gw
+    Tape cwtape;
     bool color_ready = false;
     bool color_jvp_ready = false;
     // checkpointed reverse sweeps of the four models (option "tape_checkpoint"): [segment tape | 2 recompute state sets],
@@ -3621,10 +3626,12 @@ const char* const kUnrolled = kTapedTV.multi_name;   // (the tangent sweep's ent
 
 // The channel-coupled model (color_tile_kernels.hpp): the TV model's planes, tape layout, step table and sweep planes; the
 // launches count colour images (s.lo, s.hi) and one workgroup holds the C planes of its colour image.  channels = 1 is the TV
-// model: its kernels run.
+// model: its kernels run.  x.w / g.w != nullptr: the weighted form, whose channels = 1 is the weighted
+// TV model.
 template <int C>
 void color_launch_fwd_c(const TapedFwd& x, const LaunchStep& s, TvTileArgs& a) {
-    void (*kern)(TvTileArgs) = x.tape ? &color_tile_kernel<C, true> : &color_tile_kernel<C, false>;
+    void (*kern)(TvTileArgs) = x.w ? (x.tape ? &color_tile_kernel<C, true, true> : &color_tile_kernel<C, false, true>)
+                                   : (x.tape ? &color_tile_kernel<C, true> : &color_tile_kernel<C, false>);
     hipLaunchKernelGGL(kern, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(TV_R * TV_R), color_lds_bytes(C), s.st, a);
 }
 void color_launch_fwd(const TapedFwd& x, const LaunchStep& s) {
@@ -3633,6 +3640,7 @@ void color_launch_fwd(const TapedFwd& x, const LaunchStep& s) {
     TvTileArgs a{};
     taped_planes(s, 3, h->tot, x.S, a.in, a.out);
     a.f = h->d_f; a.alpha = x.alpha; a.am = x.am; a.an = x.an; a.tab = x.tab;
+    a.w = x.w; a.wstride = x.wo > 1 ? h->npx : 0;
     a.tape = x.tape; a.plane = h->tot; a.tk0 = s.tk0;
     a.it0 = s.it; a.nit = s.nit;
     a.M = h->M; a.N = h->N; a.halo = x.pl.T; a.first = s.first; a.img0 = s.lo;
@@ -3647,20 +3655,28 @@ void color_launch_rev(const TapedRev& x, const LaunchStep& s) {
     for (int c = 0; c < 3; ++c) { a.in[c] = x.S[s.cur][c]; a.out[c] = x.S[s.nxt][c]; }
     if (s.first) a.in[0] = x.g0;
     a.gf = x.gf; a.ga = x.ga; a.tape = x.tape; a.alpha = g.alpha; a.tab = x.tab;
-    a.plane = x.h->tot;
+    a.gw = x.gw; a.f = x.h->d_f; a.w = g.w;
+    a.plane = x.h->tot; a.wstride = g.wo > 1 ? x.h->npx : 0;
     a.am = g.am; a.an = g.an;
     a.khi = x.K - 1 - s.it; a.nit = s.nit; a.tk0 = s.tk0;
     a.M = x.h->M; a.N = x.h->N; a.halo = x.pl.T; a.first = s.first; a.img0 = s.lo;
     void (*kern)(TvTileRevArgs) = x.channels == 2 ? &color_reverse_tile_kernel<2> : (x.channels == 3 ? &color_reverse_tile_kernel<3> : &color_reverse_tile_kernel<4>);
+    if (g.w) kern = x.channels == 2 ? &color_reverse_tile_kernel<2, true> : (x.channels == 3 ? &color_reverse_tile_kernel<3, true> : &color_reverse_tile_kernel<4, true>);
     hipLaunchKernelGGL(kern, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(TV_R * TV_R), color_lds_bytes(x.channels), s.st, a);
 }
 // unrolled_plan; the first use raises the LDS the colour kernels may take (three and four sets of planes pass 64 KB)
 int color_plan(bpltv_t* h, const bpltv_params& p, int cap, WeightedPlan* pl) {
     if (int prc = unrolled_plan(h, p, cap, pl)) return prc;
     if (!h->color_ready) {
-        const void* k2[] = {(const void*)&color_tile_kernel<2, true>, (const void*)&color_tile_kernel<2, false>, (const void*)&color_reverse_tile_kernel<2>};
-        const void* k3[] = {(const void*)&color_tile_kernel<3, true>, (const void*)&color_tile_kernel<3, false>, (const void*)&color_reverse_tile_kernel<3>};
-        const void* k4[] = {(const void*)&color_tile_kernel<4, true>, (const void*)&color_tile_kernel<4, false>, (const void*)&color_reverse_tile_kernel<4>};
+        const void* k2[] = {(const void*)&color_tile_kernel<2, true>, (const void*)&color_tile_kernel<2, false>, (const void*)&color_reverse_tile_kernel<2>,
+                            (const void*)&color_tile_kernel<2, true, true>, (const void*)&color_tile_kernel<2, false, true>,
+                            (const void*)&color_reverse_tile_kernel<2, true>};
+        const void* k3[] = {(const void*)&color_tile_kernel<3, true>, (const void*)&color_tile_kernel<3, false>, (const void*)&color_reverse_tile_kernel<3>,
+                            (const void*)&color_tile_kernel<3, true, true>, (const void*)&color_tile_kernel<3, false, true>,
+                            (const void*)&color_reverse_tile_kernel<3, true>};
+        const void* k4[] = {(const void*)&color_tile_kernel<4, true>, (const void*)&color_tile_kernel<4, false>, (const void*)&color_reverse_tile_kernel<4>,
+                            (const void*)&color_tile_kernel<4, true, true>, (const void*)&color_tile_kernel<4, false, true>,
+                            (const void*)&color_reverse_tile_kernel<4, true>};
         for (const void* k : k2) HIPCHK(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)color_lds_bytes(2)));
         for (const void* k : k3) HIPCHK(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)color_lds_bytes(3)));
         for (const void* k : k4) HIPCHK(h, hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)color_lds_bytes(4)));
@@ -3683,6 +3699,23 @@ TapedModel taped_color(int C) {
     return m;
 }
 const TapedModel kTapedColor[COLOR_MAX_C] = {taped_color(1), taped_color(2), taped_color(3), taped_color(4)};
+// Its weighted form: the weighted model's tape layout, weight and gamma in the step table, and a shallower
+// sweep.  bytes: the weighted model's per plane.  Graph variants of its own, 100 + 10 * C + 0 = taped solve, + 2 = plain solve,
+// + 3 = reverse sweep, + 4 = with grad_w: no graph is shared with the colour model's 10 * C + 0 ... 6.
+TapedModel taped_color_weighted(int C) {
+    TapedModel m = taped_color(C);
+    m.denoise = "bpltv_color_weighted_unrolled_denoise"; m.vjp = "color_weighted_unrolled_vjp"; m.tape_kind = "colour-weighted ";
+    m.multi_name = "the weighted channel-coupled solve";
+    m.tape = &bpltv_handle::cwtape; m.tape_planes = 3;
+    m.weighted = true;
+    m.rev_cap = color_weighted_rev_t(C);
+    m.fwd_variant = 100 + 10 * C; m.rev_variant = 100 + 10 * C + 3;
+    m.bytes = 88.0; m.bytes_map = 88.0 + 8.0 / C; m.plain_bytes = 64.0; m.plain_bytes_map = 64.0 + 8.0 / C;
+    m.adjoint_method = 14;
+    return m;
+}
+const TapedModel kTapedColorWeighted[COLOR_MAX_C] = {taped_color_weighted(1), taped_color_weighted(2), taped_color_weighted(3),
+                                                     taped_color_weighted(4)};
 
 // The launch chains of a taped solve or of one of its sweeps: at most two (image groups on two streams)
 // (channels > 1: the images of a chain are colour images, [lo, hi) the planes lo * channels ... hi * channels, so that no chain
@@ -3765,12 +3798,12 @@ void segment_launches(int K, int C, int T, bool stagger, F fn) {
 // With a checkpoint spacing C (option "tape_checkpoint") the same launches, cut at the segment boundaries, run the no-tape
 // instantiation; the launch that ends segment s - 1 writes its state into slot s of the buffer instead of a state set, and
 // the next one reads it from there (slot 0: x = f, y = 0).  The result ends in state set 0.
-// !taped (bpltv_color_denoise): the same launches of the no-tape instantiation and nothing else: no tape is written, grown or
+// !taped (bpltv_color_denoise, bpltv_color_weighted_denoise): the same launches of the no-tape instantiation and nothing else: no tape is written, grown or
 // invalidated, and the checkpoint option does not apply.
 int taped_denoise(bpltv_t* h, const TapedModel& m, const double* w, int wo, const double* alpha, bool dev, int am, int an,
                   const bpltv_params* pp, double* d_tape_user, double* u_out, bool each, bool taped = true) {
     const std::string name = taped ? std::string(m.denoise) + (each ? "_each" : "") + (dev ? "_device" : "")
-                                   : std::string(dev ? "bpltv_color_denoise_device" : "bpltv_color_denoise");
+                                   : std::string(m.weighted ? "bpltv_color_weighted_denoise" : "bpltv_color_denoise") + (dev ? "_device" : "");
     const char* who = name.c_str();
     const int ch = m.channels ? m.channels : 1;
     const bool sr = m.slices == 3;
@@ -4336,7 +4369,7 @@ int bpltv_destroy(bpltv_t* h) {
                     h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres, h->d_w, h->d_wst, h->d_unr, h->d_ujv, h->d_wjv, h->d_unr_gw, h->d_srunr, h->d_seg};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
-    for (Tape* t : {&h->tape, &h->wtape, &h->srtape, &h->ctape}) t->release();
+    for (Tape* t : {&h->tape, &h->wtape, &h->srtape, &h->ctape, &h->cwtape}) t->release();
     for (int s = 0; s < 2; ++s)
         for (int c = 0; c < 3; ++c) {
             if (h->d_state[s][c]) (void)hipFree(h->d_state[s][c]);
@@ -4375,7 +4408,7 @@ static int set_data_impl(bpltv_t* h, const double* ubar, const double* f, hipMem
     h->has_data = true;
     h->has_result = false;
     h->f32_f_valid = false;
-    for (Tape* t : {&h->tape, &h->wtape, &h->srtape, &h->ctape})   // checkpoints are states of the solve on the old f: the sweep would recompute on the new one
+    for (Tape* t : {&h->tape, &h->wtape, &h->srtape, &h->ctape, &h->cwtape})   // checkpoints are states of the solve on the old f: the sweep would recompute on the new one
         if (t->spacing) t->valid = false;
     return BPLTV_OK;
 }
@@ -4719,7 +4752,7 @@ int bpltv_sumregs_unrolled_vjp_each_device(bpltv_t* h, const double* d_tape, con
 }
 
 // The channel-coupled model: channels picks the instance; a colour image is `channels` consecutive planes
-static const TapedModel* color_model(bpltv_t* h, const char* what, int channels, int* rc) {
+static const TapedModel* color_model(bpltv_t* h, const char* what, int channels, int* rc, bool weighted = false) {
     *rc = BPLTV_OK;
     if (channels < 1 || channels > COLOR_MAX_C) {
         *rc = set_err(h, BPLTV_E_ARG, "%s: channels = %d (1 ... %d)", what, channels, COLOR_MAX_C);
@@ -4729,18 +4762,20 @@ static const TapedModel* color_model(bpltv_t* h, const char* what, int channels,
         *rc = set_err(h, BPLTV_E_ARG, "%s: channels = %d does not divide the handle's %d planes", what, channels, h->O);
         return nullptr;
     }
-    return &kTapedColor[channels - 1];
+    return weighted ? &kTapedColorWeighted[channels - 1] : &kTapedColor[channels - 1];
 }
+// w != nullptr or weighted: the weighted form (a null w is its own rejection, after the channels')
 static int color_denoise_entry(bpltv_t* h, const char* what, int channels, const double* alpha, bool dev, int am, int an, const bpltv_params* pp,
-                               double* d_tape, double* u_out, bool taped) {
+                               double* d_tape, double* u_out, bool taped, bool weighted = false, const double* w = nullptr, int wo = 1) {
     if (!h) return BPLTV_E_ARG;
     int rc = BPLTV_OK;
-    const TapedModel* m = color_model(h, what, channels, &rc);
+    const TapedModel* m = color_model(h, what, channels, &rc, weighted);
     if (!m) return rc;
     if (h->multi)
-        return weighted_multi(h, what, true, [&](bpltv_t* c) { return color_denoise_entry(c, what, channels, alpha, dev, am, an, pp, d_tape, u_out, taped); },
-                              m->multi_name);
-    return taped_denoise(h, *m, nullptr, 1, alpha, dev, am, an, pp, d_tape, u_out, false, taped);
+        return weighted_multi(h, what, true, [&](bpltv_t* c) {
+            return color_denoise_entry(c, what, channels, alpha, dev, am, an, pp, d_tape, u_out, taped, weighted, w, wo);
+        }, m->multi_name);
+    return taped_denoise(h, *m, w, wo, alpha, dev, am, an, pp, d_tape, u_out, false, taped);
 }
 int bpltv_color_denoise(bpltv_t* h, int channels, const double* alpha, int am, int an, const bpltv_params* pp, double* u_out) {
     return color_denoise_entry(h, "bpltv_color_denoise", channels, alpha, false, am, an, pp, nullptr, u_out, false);
@@ -4769,6 +4804,44 @@ int bpltv_color_unrolled_vjp_device(bpltv_t* h, int channels, const double* d_ta
     const TapedModel* m = color_model(h, "bpltv_color_unrolled_vjp_device", channels, &rc);
     if (!m) return rc;
     return taped_vjp_entry(h, *m, "bpltv_color_unrolled_vjp_device", true, d_tape, nullptr, 1, d_alpha, am, an, pp, d_gu, d_grad_f, d_grad_alpha, nullptr, false);
+}
+
+// The weighted channel-coupled model
+int bpltv_color_weighted_denoise(bpltv_t* h, int channels, const double* w, int wo, const double* alpha, int am, int an, const bpltv_params* pp,
+                                 double* u_out) {
+    return color_denoise_entry(h, "bpltv_color_weighted_denoise", channels, alpha, false, am, an, pp, nullptr, u_out, false, true, w, wo);
+}
+int bpltv_color_weighted_denoise_device(bpltv_t* h, int channels, const double* d_w, int wo, const double* d_alpha, int am, int an,
+                                        const bpltv_params* pp) {
+    return color_denoise_entry(h, "bpltv_color_weighted_denoise_device", channels, d_alpha, true, am, an, pp, nullptr, nullptr, false, true, d_w, wo);
+}
+int bpltv_color_weighted_unrolled_denoise(bpltv_t* h, int channels, const double* w, int wo, const double* alpha, int am, int an,
+                                          const bpltv_params* pp, double* u_out) {
+    return color_denoise_entry(h, "bpltv_color_weighted_unrolled_denoise", channels, alpha, false, am, an, pp, nullptr, u_out, true, true, w, wo);
+}
+int bpltv_color_weighted_unrolled_denoise_device(bpltv_t* h, int channels, const double* d_w, int wo, const double* d_alpha, int am, int an,
+                                                 const bpltv_params* pp, double* d_tape) {
+    return color_denoise_entry(h, "bpltv_color_weighted_unrolled_denoise_device", channels, d_alpha, true, am, an, pp, d_tape, nullptr, true, true, d_w,
+                               wo);
+}
+int bpltv_color_weighted_unrolled_vjp(bpltv_t* h, int channels, const double* w, int wo, const double* alpha, int am, int an,
+                                      const bpltv_params* pp, const double* gu, double* grad_f_out, double* grad_alpha_out, double* grad_w_out) {
+    if (!h) return BPLTV_E_ARG;
+    int rc = BPLTV_OK;
+    const TapedModel* m = color_model(h, "bpltv_color_weighted_unrolled_vjp", channels, &rc, true);
+    if (!m) return rc;
+    return taped_vjp_entry(h, *m, "bpltv_color_weighted_unrolled_vjp", false, nullptr, w, wo, alpha, am, an, pp, gu, grad_f_out, grad_alpha_out,
+                           grad_w_out, false);
+}
+int bpltv_color_weighted_unrolled_vjp_device(bpltv_t* h, int channels, const double* d_tape, const double* d_w, int wo, const double* d_alpha,
+                                             int am, int an, const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alpha,
+                                             double* d_grad_w) {
+    if (!h) return BPLTV_E_ARG;
+    int rc = BPLTV_OK;
+    const TapedModel* m = color_model(h, "bpltv_color_weighted_unrolled_vjp_device", channels, &rc, true);
+    if (!m) return rc;
+    return taped_vjp_entry(h, *m, "bpltv_color_weighted_unrolled_vjp_device", true, d_tape, d_w, wo, d_alpha, am, an, pp, d_gu, d_grad_f,
+                           d_grad_alpha, d_grad_w, false);
 }
 
 int bpltv_weighted_unrolled_tape_doubles(bpltv_t* h, const bpltv_params* pp, unsigned long long* n_out) {

@@ -26,6 +26,13 @@
 // of the TV planes.  Two barriers per iteration, every load first, the step rows in LDS, spent halo waves keep the barriers
 // company only, agent-scope write-through stores of the core: tv_tile_kernel's structure.
 // color_tangent_tile_kernel<C> (below) carries the tangent through the same iterations: DESIGN.md section 4.13.
+//
+// WEIGHTED: the fidelity 1/2 sum_c sum_pixels w_c (u_c - f_c)^2, w >= 0, one weight plane for all planes
+// or one per plane.  The primal step of every plane is tv_tile_kernel<1, ...>'s -- t = fma(-w_c, f_c, div), r_c = 1.0 / fma(tau_k,
+// w_c, 1.0), x_new = fma(-tau_k, t, x) * r_c -- the projection stays the one above, and the tape also holds x_new of every plane
+// ([k][z1, z2, x][plane][pixel]).  Reverse: the projection adjoint above, then tv_reverse_tile_kernel<1>'s tail per plane:
+//     h = gxn*r_c;  gf += tau_k*(w_c*h);  gw_c += tau_k*((f_c - x_new_c)*h);  gy = gz - tau_k * G h;  gx = h - omega_k*gxb
+// With w == 1.0 every weighted operation returns the bits of the one it replaces.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -40,9 +47,16 @@ constexpr int COLOR_MAX_C = 4;
 constexpr int color_rev_t(int C) { return C <= 1 ? TV_REV_T : (C == 2 ? 6 : (C == 3 ? 4 : 3)); }
 constexpr size_t color_lds_bytes(int C) { return (size_t)C * tv_lds_bytes(); }
 
-// TvTileArgs with: img0 / grid.z count colour images; in, out, f, tape address the planes img*C + c; w, df, dw, dalpha,
-// wstride and istride are not read.
-template <int C, bool TAPE>
+// The weighted sweep also holds x+ of every taped iteration (for gw) beside w and f: 3*C*T taped doubles and 8*C of sweep state,
+// weight and data.  The deepest that leaves no instantiation with scratch: 119 / 112 / 106 VGPRs (one
+// more iteration spills 20 / 12 / 52 bytes per lane).
+constexpr int color_weighted_rev_t(int C) { return C <= 1 ? TV_REV_T : (C == 2 ? 5 : (C == 3 ? 2 : 1)); }
+
+// TvTileArgs with: img0 / grid.z count colour images; in, out, f, tape address the planes img*C + c; df, dw, dalpha and istride
+// are not read.  WEIGHTED: w is one plane (wstride 0) or O planes (wstride M*N: plane img*C + c), the
+// primal step of every plane is tv_tile_kernel<1, ...>'s and the tape has its three components; otherwise w and wstride are not
+// read.
+template <int C, bool TAPE, bool WEIGHTED = false>
 __global__ __launch_bounds__(TV_R * TV_R) void color_tile_kernel(TvTileArgs A) {
     static_assert(C >= 2 && C <= COLOR_MAX_C, "channels = 1 is tv_tile_kernel");
     constexpr int RI = TV_R, RJ = TV_R, S1 = RI + 1;
@@ -90,6 +104,11 @@ __global__ __launch_bounds__(TV_R * TV_R) void color_tile_kernel(TvTileArgs A) {
     }
 #pragma unroll
     for (int c = 0; c < C; ++c) f[c] = A.f[base + c * npx + pix];
+    double w[WEIGHTED ? C : 1];   // WEIGHTED: the weight of every channel (one plane: the same value C times)
+    if constexpr (WEIGHTED) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) w[c] = A.w[(size_t)(img * C + c) * A.wstride + pix];
+    }
     double al = A.alpha[ai];
     const bool row_word = tid < A.nit * TAB_STRIDE;   // nit <= PDHG_MAX_T: the host checks
     double row_w = 0.0;
@@ -100,6 +119,8 @@ __global__ __launch_bounds__(TV_R * TV_R) void color_tile_kernel(TvTileArgs A) {
     for (int c = 0; c < C; ++c) {
         if (first) { x[c] = f[c]; y1[c] = 0.0; y2[c] = 0.0; }
         if (!in) { f[c] = 0.0; x[c] = 0.0; y1[c] = 0.0; y2[c] = 0.0; }
+        if constexpr (WEIGHTED)
+            if (!in) w[c] = 0.0;   // r = 1 there: the lane stays zero
         sy1[c * PLANES + lj * S1 + li + 1] = y1[c];
         sy2[c * PLANES + (lj + 1) * RI + li] = y2[c];
         if (tid < RJ) sy1[c * PLANES + tid * S1] = 0.0;
@@ -117,7 +138,8 @@ __global__ __launch_bounds__(TV_R * TV_R) void color_tile_kernel(TvTileArgs A) {
     const int qi = oi + li, qj = oj + lj;
     const bool core = qi >= ci0 && qi < ci1 && qj >= cj0 && qj < cj1;
     const size_t idx = base + qi + (size_t)M * qj;   // channel 0; used by core pixels only
-    double* tz = TAPE ? A.tape + (size_t)2 * A.plane * (A.it0 - A.tk0) + idx : nullptr;
+    constexpr int NC = WEIGHTED ? 3 : 2;   // tape components
+    double* tz = TAPE ? A.tape + (size_t)NC * A.plane * (A.it0 - A.tk0) + idx : nullptr;
     // halo rows do not need all the iterations (tv_tile_kernel): a wave owns two adjacent rows; core rows run them all
     int my_nit = nit;
     if (N > RJ) {
@@ -126,6 +148,7 @@ __global__ __launch_bounds__(TV_R * TV_R) void color_tile_kernel(TvTileArgs A) {
         if (oj + RJ < N) my_nit = min(my_nit, RJ - r0);
     }
     const int loop_nit = __builtin_amdgcn_readfirstlane(my_nit);
+    // r: the tabulated 1/(1 + tau) of the row, or (WEIGHTED) computed per plane in the iteration
     double tau = srow[0], sigma = srow[1], omega = srow[2], r = srow[3], opw = srow[4];
     for (int it = 0; it < loop_nit; ++it) {
         // ---- primal step of every channel
@@ -135,7 +158,13 @@ __global__ __launch_bounds__(TV_R * TV_R) void color_tile_kernel(TvTileArgs A) {
             const double y1m = sy1[c * PLANES + lj * S1 + li];
             const double y2m = sy2[c * PLANES + lj * RI + li];
             const double div = (y1m - y1[c]) + (y2m - y2[c]);
-            const double t = div - f[c];
+            double t;
+            if constexpr (WEIGHTED) {
+                t = __builtin_fma(-w[c], f[c], div);
+                r = 1.0 / __builtin_fma(tau, w[c], 1.0);
+            } else {
+                t = div - f[c];
+            }
             const double xo = x[c];
             const double xn = __builtin_fma(-tau, t, xo) * r;
             b[c] = __builtin_fma(-omega, xo, opw * xn);
@@ -145,7 +174,7 @@ __global__ __launch_bounds__(TV_R * TV_R) void color_tile_kernel(TvTileArgs A) {
         __syncthreads();
         const double* nrow = srow + TAB_STRIDE * ((it + 1 < nit) ? it + 1 : it);
         const double ntau = nrow[0], nsigma = nrow[1], nomega = nrow[2], nopw = nrow[4];
-        r = nrow[3];
+        if constexpr (!WEIGHTED) r = nrow[3];
         // ---- dual step: z of every channel, then one projection for the pixel
         double nn = 0.0;
 #pragma unroll
@@ -155,15 +184,16 @@ __global__ __launch_bounds__(TV_R * TV_R) void color_tile_kernel(TvTileArgs A) {
             y1[c] = __builtin_fma(sigma, d1, y1[c]);
             y2[c] = __builtin_fma(sigma, d2, y2[c]);
             if constexpr (TAPE) {
-                if (core) {   // the tape: the dual before the projection
+                if (core) {   // the tape: the dual before the projection (WEIGHTED: and the primal iterate grad_w reads)
                     __hip_atomic_store(tz + c * npx, y1[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     __hip_atomic_store(tz + c * npx + A.plane, y2[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    if constexpr (WEIGHTED) __hip_atomic_store(tz + c * npx + 2 * A.plane, x[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                 }
             }
             nn = (c == 0) ? y1[c] * y1[c] : __builtin_fma(y1[c], y1[c], nn);
             nn = __builtin_fma(y2[c], y2[c], nn);
         }
-        if constexpr (TAPE) tz += 2 * A.plane;
+        if constexpr (TAPE) tz += NC * A.plane;
         if (nn > al * al) {   // a wave whose pixels all lie inside the ball skips the rsqrt
             const double v = al * rsqrt_nr(nn);
 #pragma unroll
@@ -401,13 +431,17 @@ __global__ __launch_bounds__(TV_R * TV_R) void color_tangent_tile_kernel(TvTileA
 }
 
 // TvTileRevArgs with: img0 / grid.z count colour images; in, out, gf, tape address the planes img*C + c; ga: the colour
-// image's value in its channel-0 plane, +0.0 in the others; gw, f, w, wstride and istride are not read.  nit <= color_rev_t(C).
-template <int C>
+// image's value in its channel-0 plane, +0.0 in the others; istride is not read.  nit <= color_rev_t(C).
+// WEIGHTED: tv_reverse_tile_kernel<1>'s tail per plane -- h = r_c o gxn goes through the padded plane,
+// gw into a plane of its own (nullptr: not wanted, and neither f nor the taped x+ is loaded); w as color_tile_kernel's; the
+// tape has three components; nit <= color_weighted_rev_t(C).  Otherwise gw, f, w and wstride are not read.
+template <int C, bool WEIGHTED = false>
 __global__ __launch_bounds__(TV_R * TV_R) void color_reverse_tile_kernel(TvTileRevArgs A) {
     static_assert(C >= 2 && C <= COLOR_MAX_C, "channels = 1 is tv_reverse_tile_kernel");
     constexpr int RI = TV_R, RJ = TV_R, S1 = RI + 1;
     constexpr int PLANES = RJ * S1 + (RJ + 1) * RI + RJ * RI + RI + 1;
-    constexpr int T = color_rev_t(C);
+    constexpr int T = WEIGHTED ? color_weighted_rev_t(C) : color_rev_t(C);
+    constexpr int NC = WEIGHTED ? 3 : 2;   // tape components
     extern __shared__ __attribute__((aligned(16))) unsigned char tv_smem[];
     double* sg1 = reinterpret_cast<double*>(tv_smem);   // [RJ][S1]               channel c: + c * PLANES
     double* sg2 = sg1 + RJ * S1;                        // [RJ+1][RI]
@@ -425,6 +459,7 @@ __global__ __launch_bounds__(TV_R * TV_R) void color_reverse_tile_kernel(TvTileR
     const size_t base = (size_t)img * C * npx;
     const int amode = (A.am == 1 && A.an == 1) ? 0 : ((A.am == M && A.an == N) ? 2 : 1);
     const bool first = A.first != 0;
+    const bool want_w = WEIGHTED && A.gw != nullptr;   // (uniform)
     const int nit = A.nit;
     const int klo = A.khi - nit + 1;
 
@@ -454,9 +489,22 @@ __global__ __launch_bounds__(TV_R * TV_R) void color_reverse_tile_kernel(TvTileR
         }
     }
     if (!first && core) ga = A.ga[base + pix];
+    double gw[WEIGHTED ? C : 1], w[WEIGHTED ? C : 1], f[WEIGHTED ? C : 1];
+    if constexpr (WEIGHTED) {
+#pragma unroll
+        for (int c = 0; c < C; ++c) {
+            gw[c] = 0.0; f[c] = 0.0;
+            w[c] = A.w[(size_t)(img * C + c) * A.wstride + pix];
+            if (want_w) {
+                f[c] = A.f[base + c * npx + pix];
+                if (!first && core) gw[c] = A.gw[base + c * npx + pix];
+            }
+        }
+    }
     double al = A.alpha[ai];
     double z1[C][T], z2[C][T];   // [c][s]: iteration khi - s
-    const double* tz = A.tape + (size_t)2 * A.plane * (A.khi - A.tk0) + base + pix;
+    double xp[WEIGHTED ? C : 1][T];   // WEIGHTED: the primal iterate, for gw
+    const double* tz = A.tape + (size_t)NC * A.plane * (A.khi - A.tk0) + base + pix;
 #pragma unroll
     for (int s = 0; s < T; ++s) {
 #pragma unroll
@@ -466,8 +514,12 @@ __global__ __launch_bounds__(TV_R * TV_R) void color_reverse_tile_kernel(TvTileR
                 z1[c][s] = tz[c * npx];
                 z2[c][s] = tz[c * npx + A.plane];
             }
+            if constexpr (WEIGHTED) {
+                xp[c][s] = 0.0;
+                if (s < nit && want_w) xp[c][s] = tz[c * npx + 2 * A.plane];
+            }
         }
-        tz -= 2 * A.plane;
+        tz -= NC * A.plane;
     }
     const bool row_word = tid < nit * TAB_STRIDE;   // nit <= T: the host checks
     double row_w = 0.0;
@@ -476,6 +528,8 @@ __global__ __launch_bounds__(TV_R * TV_R) void color_reverse_tile_kernel(TvTileR
 #pragma unroll
     for (int c = 0; c < C; ++c) {
         if (!in) { gx[c] = 0.0; gy1[c] = 0.0; gy2[c] = 0.0; }
+        if constexpr (WEIGHTED)
+            if (!in) w[c] = 0.0;   // r = 1 there: the lane stays zero
         if (tid < RJ) sg1[c * PLANES + tid * S1] = 0.0;
         if (tid < RI) sg2[c * PLANES + tid] = 0.0;
         if (tid < RI + 1) sxn[c * PLANES + RI * RJ + tid] = 0.0;
@@ -530,24 +584,42 @@ __global__ __launch_bounds__(TV_R * TV_R) void color_reverse_tile_kernel(TvTileR
             }
             __syncthreads();
             // ---- adjoint of the over-relaxation and the primal step, per channel
-            double gxb[C], gxn[C];
+            double gxb[C], gxn[C];   // (WEIGHTED: gxn holds h = r_c o gxn)
 #pragma unroll
             for (int c = 0; c < C; ++c) {
                 const double gt = (sg1[c * PLANES + lj * S1 + li] - m1[c]) + (sg2[c * PLANES + lj * RI + li] - m2[c]);
                 gxb[c] = sigma * gt;
                 gxn[c] = gx[c] + opw * gxb[c];
+                if constexpr (WEIGHTED) {
+                    const double r = 1.0 / __builtin_fma(tau, w[c], 1.0);
+                    gxn[c] = gxn[c] * r;
+                }
                 sxn[c * PLANES + l] = gxn[c];
             }
             __syncthreads();
-            const double tc = tau * cr;
+            if constexpr (WEIGHTED) {
 #pragma unroll
-            for (int c = 0; c < C; ++c) {
-                const double d1 = sxn[c * PLANES + n1] - gxn[c];
-                const double d2 = sxn[c * PLANES + n2] - gxn[c];
-                gf[c] += tc * gxn[c];
-                gy1[c] = gy1[c] - tc * d1;
-                gy2[c] = gy2[c] - tc * d2;
-                gx[c] = cr * gxn[c] - omega * gxb[c];
+                for (int c = 0; c < C; ++c) {
+                    const double h = gxn[c];
+                    const double d1 = sxn[c * PLANES + n1] - h;
+                    const double d2 = sxn[c * PLANES + n2] - h;
+                    gf[c] += tau * (w[c] * h);
+                    if (want_w) gw[c] += tau * ((f[c] - xp[c][s]) * h);
+                    gy1[c] = gy1[c] - tau * d1;
+                    gy2[c] = gy2[c] - tau * d2;
+                    gx[c] = h - omega * gxb[c];
+                }
+            } else {
+                const double tc = tau * cr;
+#pragma unroll
+                for (int c = 0; c < C; ++c) {
+                    const double d1 = sxn[c * PLANES + n1] - gxn[c];
+                    const double d2 = sxn[c * PLANES + n2] - gxn[c];
+                    gf[c] += tc * gxn[c];
+                    gy1[c] = gy1[c] - tc * d1;
+                    gy2[c] = gy2[c] - tc * d2;
+                    gx[c] = cr * gxn[c] - omega * gxb[c];
+                }
             }
         }
     }
@@ -561,6 +633,8 @@ __global__ __launch_bounds__(TV_R * TV_R) void color_reverse_tile_kernel(TvTileR
             __hip_atomic_store(&A.out[2][idx + c * npx], gy2[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(&A.gf[idx + c * npx], gf[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(&A.ga[idx + c * npx], c == 0 ? ga : 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if constexpr (WEIGHTED)
+                if (want_w) __hip_atomic_store(&A.gw[idx + c * npx], gw[c], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
 }

@@ -594,6 +594,80 @@ class TVSolver:
                                                                 C.byref(cost), _ptr(grad), _ptr(H)))
         return float(cost.value), (float(grad[0]) if scalar else grad.reshape(an, am)), H
 
+    # -- channel-coupled TV with a per-pixel fidelity weight (bpltv_color_weighted_*) ------------------------------
+    # w >= 0, zeros allowed: (N, M) -- one plane for every plane of the batch -- or (O, N, M), one per plane (per channel).  The
+    # tape has the weighted tape's size: weighted_unrolled_tape_doubles.
+    def color_weighted_denoise(self, x, channels, w, fetch=True, **kw):
+        """Vectorial TV with the fidelity 0.5 sum_c w_c (u_c - f_c)^2 (bpltv_color_weighted_denoise): colour inpainting,
+        demosaicing, a variance per channel.  No tape; u is bitwise color_weighted_unrolled_denoise's, and with w = 1
+        color_denoise's."""
+        a, am, an, _ = _alpha_arg(x)
+        wa, wo = self._weight(w)
+        p = self.params(**kw)
+        u = np.empty((self.O, self.N, self.M)) if fetch else None
+        self._check(self._lib.bpltv_color_weighted_denoise(self._h, int(channels), _ptr(wa), wo, _ptr(a), am, an, C.byref(p),
+                                                           _ptr(u) if fetch else None))
+        return u
+
+    def color_weighted_denoise_device(self, channels, w_ptr, wo, alpha_ptr, am=1, an=1, **kw):
+        """bpltv_color_weighted_denoise_device: w (wo planes) and the parameter resident in HBM, the result left there."""
+        p = self.params(**kw)
+        self._check(self._lib.bpltv_color_weighted_denoise_device(self._h, int(channels), C.c_void_p(w_ptr), int(wo),
+                                                                  C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p)))
+
+    def color_weighted_unrolled_denoise(self, x, channels, w, fetch=True, **kw):
+        """color_weighted_denoise that also records the tape of the iterations in the handle, for
+        color_weighted_unrolled_vjp with the same x, channels, w and params (bpltv_color_weighted_unrolled_denoise)."""
+        a, am, an, _ = _alpha_arg(x)
+        wa, wo = self._weight(w)
+        p = self._taped_params(kw)
+        u = np.empty((self.O, self.N, self.M)) if fetch else None
+        self._check(self._lib.bpltv_color_weighted_unrolled_denoise(self._h, int(channels), _ptr(wa), wo, _ptr(a), am, an,
+                                                                    C.byref(p), _ptr(u) if fetch else None))
+        return u
+
+    def color_weighted_unrolled_denoise_device(self, channels, w_ptr, wo, alpha_ptr, am=1, an=1, tape_ptr=None, **kw):
+        """bpltv_color_weighted_unrolled_denoise_device: w (wo planes) and the parameter resident in HBM, the result left
+        there; tape_ptr: a caller-owned HBM buffer of weighted_unrolled_tape_doubles(**kw) doubles, or None / 0 for the
+        handle's colour-weighted tape."""
+        p = self._taped_params(kw)
+        self._check(self._lib.bpltv_color_weighted_unrolled_denoise_device(self._h, int(channels), C.c_void_p(w_ptr), int(wo),
+                                                                           C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p),
+                                                                           C.c_void_p(tape_ptr or None)))
+
+    def color_weighted_unrolled_vjp(self, x, channels, w, gu, want_f=True, want_alpha=True, want_w=True, **kw):
+        """Vector-Jacobian product of the maxiter-step map u = color_weighted_unrolled_denoise(x, channels, w) for the
+        cotangent gu, by a reverse sweep over the handle's colour-weighted tape (bpltv_color_weighted_unrolled_vjp):
+        (grad_f, grad_x, grad_w), as weighted_unrolled_vjp.  grad_w has the shape of w -- for (N, M) the sum over the planes."""
+        if not (want_f or want_alpha or want_w):
+            raise ValueError("color_weighted_unrolled_vjp: want_f, want_alpha and want_w are all False")
+        a, am, an, scalar = _alpha_arg(x)
+        wa, wo = self._weight(w)
+        p = self._taped_params(kw)
+        gu = self._batch(gu, "gu")
+        gf = np.empty((self.O, self.N, self.M)) if want_f else None
+        ga = np.empty(am * an) if want_alpha else None
+        gw = np.empty(wa.shape) if want_w else None
+        self._check(self._lib.bpltv_color_weighted_unrolled_vjp(self._h, int(channels), _ptr(wa), wo, _ptr(a), am, an, C.byref(p),
+                                                                _ptr(gu), _ptr(gf) if want_f else None,
+                                                                _ptr(ga) if want_alpha else None,
+                                                                _ptr(gw) if want_w else None))
+        if ga is not None:
+            ga = float(ga[0]) if scalar else ga.reshape(an, am)
+        return gf, ga, gw
+
+    def color_weighted_unrolled_vjp_device(self, channels, tape_ptr, w_ptr, wo, alpha_ptr, am, an, gu_ptr, grad_f_ptr,
+                                           grad_alpha_ptr, grad_w_ptr, **kw):
+        """bpltv_color_weighted_unrolled_vjp_device: the tape (None / 0: the handle's own), w, the parameter, gu and the
+        outputs resident in HBM (raw device pointers); any output pointer may be 0 / None, not all three."""
+        p = self._taped_params(kw)
+        self._check(self._lib.bpltv_color_weighted_unrolled_vjp_device(self._h, int(channels), C.c_void_p(tape_ptr or None),
+                                                                       C.c_void_p(w_ptr), int(wo), C.c_void_p(alpha_ptr),
+                                                                       int(am), int(an), C.byref(p), C.c_void_p(gu_ptr),
+                                                                       C.c_void_p(grad_f_ptr or None),
+                                                                       C.c_void_p(grad_alpha_ptr or None),
+                                                                       C.c_void_p(grad_w_ptr or None)))
+
     # -- reverse mode through the weighted iterations (bpltv_weighted_unrolled_*) --------------------------------
     def weighted_unrolled_tape_doubles(self, **kw):
         """Doubles of the tape a weighted unrolled solve with these params records: 3 * maxiter * M*N*O."""

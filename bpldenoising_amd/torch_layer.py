@@ -99,6 +99,13 @@ forward_mode=True) and TVDenoiseColorUnrolled(alpha, forward_mode=True) select a
 bpltv_color_unrolled_jvp_device call: a tangent sweep through the coupled iterations, which reads no tape.  The other functions
 keep refusing 4-D input.
 
+    u = tv_denoise_color_weighted_unrolled(f, alpha, w, maxiter=50)   # ... with a fidelity weight (bpltv_color_weighted_unrolled_*)
+
+f and alpha as for tv_denoise_color_unrolled, w >= 0 (zeros allowed) of shape (H, W) or f's shape: 0.5 sum_c w_c (u_c - f_c)^2
+in place of the fidelity.  One mask for the channels is colour inpainting, a mask per channel demosaicing; the coupled
+regulariser fills a masked channel in from the others.  backward is one bpltv_color_weighted_unrolled_vjp_device call over a
+tape of 3 * maxiter * B*C*H*W doubles and returns f.grad, alpha.grad and w.grad.  No jvp: forward_mode=True raises a ValueError.
+
 Streams: the library runs its kernels on its own HIP streams and blocks until they are done.  Every call below first
 synchronises the tensors' current torch stream, so that the library reads inputs torch has finished writing; its
 outputs are complete when the call returns.
@@ -208,10 +215,9 @@ def _check_args_each(f, alpha, slices=1, name=None):
     return B, H, W, am, an
 
 
-def _check_args_color(f, alpha):
-    """(B, C, H, W, am, an) of a valid (f, alpha) pair of tv_denoise_color_unrolled; TypeError / ValueError before any
-    library call."""
-    name = "tv_denoise_color_unrolled"
+def _check_args_color(f, alpha, name="tv_denoise_color_unrolled"):
+    """(B, C, H, W, am, an) of a valid (f, alpha) pair of tv_denoise_color_unrolled (name: the caller in the messages, when
+    it is another function with its shapes); TypeError / ValueError before any library call."""
     _check_tensors(name, f, alpha)
     if f.dim() not in (3, 4) or f.numel() == 0:
         raise ValueError("%s: f must have shape (B, C, H, W) or (C, H, W), got %s" % (name, tuple(f.shape)))
@@ -232,7 +238,8 @@ def _check_args_color(f, alpha):
 
 
 def _check_weight(f, w, name="tv_denoise_weighted"):
-    """wo (1 or B) of a valid weight for f; TypeError / ValueError before any library call."""
+    """wo (1, or the planes of f: B, of a colour batch B*C) of a valid weight for f; TypeError / ValueError before any library
+    call."""
     if not isinstance(w, torch.Tensor):
         raise TypeError("%s: w must be a torch tensor" % name)
     if w.dtype != torch.float64:
@@ -240,8 +247,8 @@ def _check_weight(f, w, name="tv_denoise_weighted"):
     H, W = f.shape[-2], f.shape[-1]
     if tuple(w.shape) == (H, W):
         wo = 1
-    elif f.dim() == 3 and tuple(w.shape) == tuple(f.shape):
-        wo = f.shape[0]
+    elif f.dim() >= 3 and tuple(w.shape) == tuple(f.shape):
+        wo = f.numel() // (H * W)
     else:
         raise ValueError("%s: w must have shape (%d, %d) or f's shape %s; got %s"
                          % (name, H, W, tuple(f.shape), tuple(w.shape)))
@@ -277,7 +284,7 @@ def _no_checkpoint(solver_kw):
     return {k: v for k, v in solver_kw.items() if k != "checkpoint_every"}
 
 
-# ---- the one implementation behind the sixteen Functions below ------------------------------------------------------------------
+# ---- the one implementation behind the seventeen Functions below ----------------------------------------------------------------
 # A model is a row of this record; _forward, _backward and _jvp are every Function's three methods, written once over it.
 # The TVSolver entries are named, not held: they are looked up on the handle of the call.  Their argument lists mirror the C
 # ABI and are not regular -- the channel count first, `w, wo` in front of alpha, the tape first in a vjp, a trailing u_ptr in
@@ -319,13 +326,17 @@ _SUMREGS_UNROLLED_EACH = _Model(functools.partial(_check_sr_each, name="sumregs_
                                 "sumregs_unrolled_tape_doubles", slices=3, each=True)
 _COLOR_UNROLLED = _Model(_check_args_color, "color_unrolled_denoise_device", "color_unrolled_vjp_device",
                          "color_unrolled_jvp_device", "unrolled_tape_doubles", channels=True)
+_COLOR_WEIGHTED_UNROLLED = _Model(functools.partial(_check_args_color, name="tv_denoise_color_weighted_unrolled"),
+                                  "color_weighted_unrolled_denoise_device", "color_weighted_unrolled_vjp_device", None,
+                                  "weighted_unrolled_tape_doubles", w="tv_denoise_color_weighted_unrolled", w_zeros=True,
+                                  channels=True)
 
 
 def _forward(m, ctx, f, alpha, solver_kw, reg=None, w=None, jvp=False):
     """forward of every Function.  In this order: every check, the cached handle, detached contiguous copies, the tape, _sync,
     f installed, the solve, u fetched; then what backward and (jvp: the class carries one) the tangent need is saved."""
     if m.w:
-        if not isinstance(f, torch.Tensor) or f.dim() not in (2, 3) or f.numel() == 0:
+        if not isinstance(f, torch.Tensor) or f.dim() not in ((3, 4) if m.channels else (2, 3)) or f.numel() == 0:
             m.check(f, alpha)   # raises: f has no (H, W) to hold w against
         wo = _check_weight(f, w, m.w)   # (in front of the device check: a CPU triple with a wrong w reports the w)
         if m.w_zeros and w.numel() and not bool((w.detach() >= 0).all()):   # (a NaN fails the comparison too)
@@ -656,10 +667,10 @@ class SumRegsDenoiseUnrolledFunction(torch.autograd.Function):
         return _backward(_SUMREGS_UNROLLED_EACH if ctx.each else _SUMREGS_UNROLLED, ctx, gu)
 
 
-def _no_forward_mode(name, forward_mode):
+def _no_forward_mode(name, forward_mode, what="the sum-of-regularisers iterations",
+                     instead="the implicit sumregs_denoise(..., forward_mode=True)"):
     if forward_mode:
-        raise ValueError("%s: forward mode through the sum-of-regularisers iterations does not exist; the implicit "
-                         "sumregs_denoise(..., forward_mode=True) carries a jvp" % name)
+        raise ValueError("%s: forward mode through %s does not exist; %s carries a jvp" % (name, what, instead))
 
 
 def sumregs_denoise_unrolled(f, alpha, maxiter=50, forward_mode=False, checkpoint_every=None, **solver_kw):
@@ -741,3 +752,27 @@ class TVDenoiseColorUnrolled(torch.nn.Module):
     def forward(self, f):
         return tv_denoise_color_unrolled(f, self.alpha, maxiter=self.maxiter, checkpoint_every=self.checkpoint_every,
                                          forward_mode=self.forward_mode, **self.solver_kw)
+
+
+# ---- ... with a per-pixel data-fidelity weight (TVSolver.color_weighted_unrolled_*): colour inpainting, demosaicing ----
+class TVDenoiseColorWeightedUnrolledFunction(torch.autograd.Function):
+    """autograd.Function of tv_denoise_color_weighted_unrolled (below); apply(f, alpha, w, solver_kw).  No jvp."""
+    forward = staticmethod(lambda ctx, f, alpha, w, solver_kw: _forward(_COLOR_WEIGHTED_UNROLLED, ctx, f, alpha, solver_kw, w=w))
+    backward = staticmethod(once_differentiable(lambda ctx, gu: _backward(_COLOR_WEIGHTED_UNROLLED, ctx, gu)))
+
+
+def tv_denoise_color_weighted_unrolled(f, alpha, w, maxiter=50, checkpoint_every=None, forward_mode=False, **solver_kw):
+    """Vectorial TV of colour images with a per-pixel fidelity weight, by exactly maxiter PDHG iterations: min_u 1/2 sum_c
+    sum_pixels w_c (u_c - f_c)^2 + sum_pixels alpha * sqrt(sum_c |grad u_c|^2) (TVSolver.color_weighted_unrolled_denoise_device).
+    The channels keep sharing one projection per pixel, so a masked channel is filled in from the others' edges: colour
+    inpainting (one mask), demosaicing (a mask per channel), a noise variance per channel.  Differentiable in f, alpha and w
+    through the iterations (TVSolver.color_weighted_unrolled_vjp_device), with the step table (gamma = min w) held fixed.
+    f and alpha as tv_denoise_color_unrolled's; w: float64 on f's device, >= 0 with zeros allowed, (H, W) -- one plane for the
+    batch and the channels, w.grad then summed over them -- or f's shape, one plane per channel.  A (B, 1, H, W) mask goes in
+    as w.expand_as(f).contiguous(); autograd sums its gradient over the channels.  checkpoint_every, solver_kw: as
+    tv_denoise_unrolled's.  w = 1 everywhere is tv_denoise_color_unrolled's u bit for bit, C = 1 tv_denoise_weighted_unrolled.
+    forward_mode=True raises: the tangent sweep of this model is not built."""
+    _no_forward_mode("tv_denoise_color_weighted_unrolled", forward_mode, "the weighted channel-coupled iterations",
+                     "tv_denoise_color_unrolled(..., forward_mode=True), without a weight,")
+    return TVDenoiseColorWeightedUnrolledFunction.apply(f, alpha, w, _with_checkpoint(dict(solver_kw, maxiter=int(maxiter)),
+                                                                                       checkpoint_every))

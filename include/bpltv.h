@@ -141,7 +141,9 @@ typedef struct bpltv_stats {
                                   10 reverse sweep over the taped sum-of-regularisers iterations (bpltv_sumregs_unrolled_vjp),
                                   11 tangent sweep through the weighted iterations (bpltv_weighted_unrolled_jvp),
                                   12 reverse sweep over the taped channel-coupled iterations (bpltv_color_unrolled_vjp),
-                                  13 tangent sweep through the channel-coupled iterations (bpltv_color_unrolled_jvp) */
+                                  13 tangent sweep through the channel-coupled iterations (bpltv_color_unrolled_jvp),
+                                  14 reverse sweep over the taped weighted channel-coupled iterations
+                                  (bpltv_color_weighted_unrolled_vjp) */
     int reg_gradient_used;     /* 1 if the last evaluate took the gradient_reg branch             */
     int ngpus;                 /* distinct devices behind this handle (1 for bpltv_create)        */
     int shards;                /* image shards (= worker threads) behind this handle              */
@@ -682,6 +684,51 @@ int bpltv_color_unrolled_vjp(bpltv_t *h, int channels, const double *alpha, int 
                              const double *gu, double *grad_f_out, double *grad_alpha_out);
 int bpltv_color_unrolled_vjp_device(bpltv_t *h, int channels, const double *d_tape, const double *d_alpha, int am, int an,
                                     const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alpha);
+
+/* Channel-coupled TV with a per-pixel data-fidelity weight: colour inpainting (one mask for the
+ * channels), demosaicing (a mask per channel), a noise variance per channel, a learned fidelity map.
+ *
+ *     min_u  1/2 sum_c sum_pixels w_c (u_c - f_c)^2  +  sum_pixels alpha * sqrt( sum_c |(grad u_c)|^2 ),      w >= 0
+ *
+ * Planes and alpha as bpltv_color_denoise; w as bpltv_weighted_denoise: wo = 1 (one plane for all O planes) or wo = O (one per
+ * plane, that is per channel of every colour image); a caller with one mask per colour image passes it expanded to O planes.
+ * gamma = min w over everything passed goes into the step table (a mask: gamma = 0, omega = 1, and accel changes nothing).  The
+ * primal step of every plane is bpltv_weighted_unrolled_denoise's, the projection bpltv_color_denoise's.  channels = 1 returns
+ * the bits of the bpltv_weighted_unrolled_* calls; w == 1 the bits of bpltv_color_denoise.
+ *
+ * The contract is the union of bpltv_color_unrolled_*'s and bpltv_weighted_unrolled_*'s: channels outside 1 ... 4 or not
+ * dividing O, wo other than 1 or O, a NULL, negative or non-finite w, maxiter < 1 and a bad parameter are BPLTV_E_ARG; rho, init
+ * and order must be 0 (BPLTV_E_UNSUPPORTED); no data is BPLTV_E_NODATA; multi-device handles over more than one shard are
+ * BPLTV_E_UNSUPPORTED; every rejection comes before anything of the handle changes.  The results do not depend on tile_iters, on
+ * the launch chains, on use_graph, on the host or device form, on whose tape it is, or on option "tape_checkpoint".
+ *
+ * bpltv_color_weighted_denoise: the recurrence without a tape; u is bitwise the taped solve's.
+ * bpltv_color_weighted_unrolled_denoise: the same and the tape of z1, z2 (before the projection) and x+ of every plane, in the
+ * weighted tape's layout and size: bpltv_weighted_unrolled_tape_doubles gives the doubles of a caller-owned d_tape.  A NULL
+ * d_tape, and the host form always, use a fifth tape owned by the handle, which remembers channels, wo and gamma.  No other
+ * model's sweep accepts it, nor this sweep a TV, weighted or colour tape, and each survives the others' solves.  Either solve
+ * becomes the handle's last one for bpltv_u_device / bpltv_copy_u_device; bpltv_duality_gap after it is BPLTV_E_UNSUPPORTED.
+ * stats: as bpltv_color_unrolled_denoise, with bytes_per_px_iter 88 (64 without a tape) per plane, plus 8 / channels with a map.
+ *
+ * bpltv_color_weighted_unrolled_vjp: the exact reverse mode through the iterations with the step table held fixed (exact for
+ * masks and for accel = 0): grad_f_out M*N*O doubles, grad_alpha_out am*an, grad_w_out w's shape (wo = 1: summed over the planes
+ * in plane order); any may be NULL, not all three.  channels, w's planes and gamma, alpha's shape and params must be the
+ * solve's: BPLTV_E_ARG on the handle's tape otherwise; no colour-weighted tape, or grad_w_out without a dataset, is
+ * BPLTV_E_NODATA.  Of the statistics only adjoint_ms and adjoint_method = 14 change. */
+int bpltv_color_weighted_denoise(bpltv_t *h, int channels, const double *w, int wo, const double *alpha, int am, int an,
+                                 const bpltv_params *p, double *u_out);
+int bpltv_color_weighted_denoise_device(bpltv_t *h, int channels, const double *d_w, int wo, const double *d_alpha, int am, int an,
+                                        const bpltv_params *p);
+int bpltv_color_weighted_unrolled_denoise(bpltv_t *h, int channels, const double *w, int wo, const double *alpha, int am, int an,
+                                          const bpltv_params *p, double *u_out);
+int bpltv_color_weighted_unrolled_denoise_device(bpltv_t *h, int channels, const double *d_w, int wo, const double *d_alpha, int am,
+                                                 int an, const bpltv_params *p, double *d_tape);
+int bpltv_color_weighted_unrolled_vjp(bpltv_t *h, int channels, const double *w, int wo, const double *alpha, int am, int an,
+                                      const bpltv_params *p, const double *gu, double *grad_f_out, double *grad_alpha_out,
+                                      double *grad_w_out);
+int bpltv_color_weighted_unrolled_vjp_device(bpltv_t *h, int channels, const double *d_tape, const double *d_w, int wo,
+                                             const double *d_alpha, int am, int an, const bpltv_params *p, const double *d_gu,
+                                             double *d_grad_f, double *d_grad_alpha, double *d_grad_w);
 
 /* Forward mode through the channel-coupled iterations: bpltv_unrolled_jvp and
  * bpltv_unrolled_gauss_newton for the model above.  The tangent (dx, dy) is carried beside (x, y) through the same maxiter
