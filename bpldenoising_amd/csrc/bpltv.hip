@@ -514,6 +514,10 @@ struct bpltv_handle {
     // ... and of its weighted form: a fifth tape, in the weighted tape's layout, that remembers the
     // channels, the weight planes and gamma = min w it was recorded with; the reverse sweep runs in d_unr and d_unr_gw
     Tape cwtape;
+    // ... of the TV-L1 model: a sixth tape, in the weighted tape's layout, that remembers the weight
+    // planes (its gamma is 0 whatever w is); the reverse sweep runs in d_unr and d_unr_gw.  last_l1: the last solve was this model's
+    Tape l1tape;
+    bool last_l1 = false;
     bool color_ready = false;
     bool color_jvp_ready = false;
     // checkpointed reverse sweeps of the four models (option "tape_checkpoint"): [segment tape | 2 recompute state sets],
@@ -2431,6 +2435,7 @@ int solve_dataset(bpltv_t* h, bool sr, const bpltv_params& p) {
     h->last_is_sr = sr;
     h->last_weighted = false;
     h->last_channels = 0;
+    h->last_l1 = false;
     return BPLTV_OK;
 }
 // u of the last solve of the model
@@ -3294,13 +3299,15 @@ int weighted_check_params(bpltv_t* h, const bpltv_params& p, const char* who) {
 
 // One launch of tv_tile_kernel.  The caller has set what its entry point owns -- the planes, alpha (and w), the tape, the
 // tangents; here: what every launch has, and the instance (a tape means TAPE)
-void tv_tile_launch(bpltv_t* h, const WeightedPlan& pl, const double* tab, const LaunchStep& s, bool weighted, bool tangent, TvTileArgs& a) {
+void tv_tile_launch(bpltv_t* h, const WeightedPlan& pl, const double* tab, const LaunchStep& s, bool weighted, bool tangent, TvTileArgs& a,
+                    bool l1 = false) {
     a.f = h->d_f; a.tab = tab;
     a.it0 = s.it; a.nit = s.nit;
     a.M = h->M; a.N = h->N; a.halo = pl.T; a.first = s.first; a.img0 = s.lo;
     void (*kern)(TvTileArgs) = tangent    ? (weighted ? &tv_tile_kernel<true, false, true> : &tv_tile_kernel<false, false, true>)
                                : a.tape   ? (weighted ? &tv_tile_kernel<true, true, false> : &tv_tile_kernel<false, true, false>)
                                           : (weighted ? &tv_tile_kernel<true, false, false> : &tv_tile_kernel<false, false, false>);
+    if (l1) kern = a.tape ? &tv_tile_kernel<true, true, false, true> : &tv_tile_kernel<true, false, false, true>;   // (weighted, no tangent)
     hipLaunchKernelGGL(kern, dim3(pl.nTi, pl.nTj, s.hi - s.lo), dim3(TV_R * TV_R), tangent ? tv_tangent_lds_bytes() : tv_lds_bytes(), s.st, a);
 }
 
@@ -3368,6 +3375,7 @@ int weighted_denoise_common(bpltv_t* h, const double* w, int wo, const double* a
     h->last_is_sr = false;
     h->last_weighted = true;
     h->last_channels = 0;
+    h->last_l1 = false;
     if (u_out) {
         HIPCHK(h, hipMemcpyAsync(u_out, h->d_state[buf][0], h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3478,6 +3486,7 @@ struct TapedFwd {
     const double* w;     // weighted model; nullptr otherwise
     int wo;
     int channels = 1;    // channel-coupled model: planes of a colour image
+    bool l1 = false;     // TV-L1 model: the weighted launch with the L1 primal step
 };
 // the planes a launch reads and writes: a state set, or the step's checkpoint slot
 static void taped_planes(const LaunchStep& s, int np, size_t tot, double* const (*S)[7], const double** in, double** out) {
@@ -3498,6 +3507,7 @@ struct TapedRev {
     double *gf, *ga, *g0, *gw;
     int K;
     int channels = 1;    // channel-coupled model: planes of a colour image
+    bool l1 = false;     // TV-L1 model: the weighted launch with the L1 tail
 };
 
 // A model whose iterations can be taped and swept backwards: everything the two shared drivers (taped_denoise, taped_vjp)
@@ -3511,6 +3521,8 @@ struct TapedModel {
     int tape_planes;              // doubles per pixel and iteration on the tape
     int slices;                   // parameter slices: 1, or 3 (sum of regularisers: its defaults, PRE_SR, the d_sr state sets)
     bool weighted;                // takes a fidelity weight w: checked and staged, gamma = min w in the step table, grad_w
+    bool l1;                      // TV-L1 model: weighted's plumbing with gamma = 0 whatever w is (no strong convexity), a sweep
+                                  // that always reads the resident f, and no duality gap after its solves
     int channels;                 // channel-coupled model: the planes of a colour image, which the launch chains keep together
                                   // and the handle's tape remembers (0: every plane is an image of its own)
     int nplanes;                  // planes of a state set
@@ -3538,7 +3550,7 @@ void tv_launch_fwd(const TapedFwd& x, const LaunchStep& s) {   // x.w != nullptr
     a.w = x.w; a.wstride = x.wo > 1 ? h->npx : 0;
     a.alpha = x.alpha; a.am = x.am; a.an = x.an; a.istride = x.astride;
     a.tape = x.tape; a.plane = h->tot; a.tk0 = s.tk0;
-    tv_tile_launch(h, x.pl, x.tab, s, x.w != nullptr, false, a);
+    tv_tile_launch(h, x.pl, x.tab, s, x.w != nullptr, false, a, x.l1);
 }
 // `it` counts reverse steps: step r undoes iteration K - 1 - r.  g.w != nullptr: the weighted model (its kernel reads the
 // resident f for gw only)
@@ -3552,8 +3564,8 @@ void tv_launch_rev(const TapedRev& x, const LaunchStep& s) {
     a.am = g.am; a.an = g.an; a.istride = g.astride;
     a.khi = x.K - 1 - s.it; a.nit = s.nit; a.tk0 = s.tk0;
     a.M = x.h->M; a.N = x.h->N; a.halo = x.pl.T; a.first = s.first; a.img0 = s.lo;
-    hipLaunchKernelGGL(g.w ? &tv_reverse_tile_kernel<true> : &tv_reverse_tile_kernel<false>, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(TV_R * TV_R),
-                       tv_lds_bytes(), s.st, a);
+    void (*kern)(TvTileRevArgs) = x.l1 ? &tv_reverse_tile_kernel<true, true> : (g.w ? &tv_reverse_tile_kernel<true> : &tv_reverse_tile_kernel<false>);
+    hipLaunchKernelGGL(kern, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(TV_R * TV_R), tv_lds_bytes(), s.st, a);
 }
 
 void sr_launch_fwd(const TapedFwd& x, const LaunchStep& s) {   // astride != 0: one parameter block per image
@@ -3605,6 +3617,19 @@ const TapedModel kTapedWeighted = [] {
     m.fwd_variant = 6; m.rev_variant = 7;
     m.bytes = 88.0; m.bytes_map = 96.0; m.plain_bytes = 64.0; m.plain_bytes_map = 72.0;
     m.adjoint_method = 9; m.tv_stats = false;
+    return m;
+}();
+// The TV-L1 model: the weighted model's plumbing, tape layout, sweep planes and traffic -- read x, y1,
+// y2, f, w (+ alpha), write x, y1, y2 and z1, z2, x+ -- with a tape of its own and graph variants of its own under MODEL_UN:
+// 20 = taped solve, 22 = plain solve, 23 / 24 = reverse sweep without / with grad_w.
+const TapedModel kTapedL1 = [] {
+    TapedModel m = kTapedWeighted;
+    m.denoise = "bpltv_lone_unrolled_denoise"; m.vjp = "l1_unrolled_vjp"; m.tape_kind = "L1 ";
+    m.multi_name = "the TV-L1 solve";
+    m.tape = &bpltv_handle::l1tape;
+    m.l1 = true;
+    m.fwd_variant = 20; m.rev_variant = 23;
+    m.adjoint_method = 15;
     return m;
 }();
 // ... read x, 6 y, f (+ 3 alpha), write x, 6 y and the 6 z
@@ -3803,7 +3828,7 @@ void segment_launches(int K, int C, int T, bool stagger, F fn) {
 int taped_denoise(bpltv_t* h, const TapedModel& m, const double* w, int wo, const double* alpha, bool dev, int am, int an,
                   const bpltv_params* pp, double* d_tape_user, double* u_out, bool each, bool taped = true) {
     const std::string name = taped ? std::string(m.denoise) + (each ? "_each" : "") + (dev ? "_device" : "")
-                                   : std::string(m.weighted ? "bpltv_color_weighted_denoise" : "bpltv_color_denoise") + (dev ? "_device" : "");
+                                   : std::string(m.l1 ? "bpltv_lone_denoise" : (m.weighted ? "bpltv_color_weighted_denoise" : "bpltv_color_denoise")) + (dev ? "_device" : "");
     const char* who = name.c_str();
     const int ch = m.channels ? m.channels : 1;
     const bool sr = m.slices == 3;
@@ -3856,13 +3881,13 @@ int taped_denoise(bpltv_t* h, const TapedModel& m, const double* w, int wo, cons
     }
     h->has_per_image = false;
     double* d_tab = nullptr;
-    rc = get_table(h, p, &d_tab, m.L2, 0, m.weighted ? h->w_min : 1.0);
+    rc = get_table(h, p, &d_tab, m.L2, 0, m.l1 ? 0.0 : (m.weighted ? h->w_min : 1.0));
     if (rc) return rc;
     const bool amap = (h->last_am == h->M && h->last_an == h->N) && !(h->M == 1 && h->N == 1);
     h->st.tile_iters = pl.T; h->st.tiles = pl.nTi * pl.nTj * (h->O / ch); h->st.region_i = m.region; h->st.region_j = m.region; h->st.pdhg_variant = 0;
     double* const buffer = !taped ? nullptr : (d_tape_user ? d_tape_user : tape.d);   // the tape, or the checkpoints
     TapedFwd x{h, pl, d_tab, C ? nullptr : buffer, {}, h->d_alpha, h->last_am, h->last_an, h->alpha_istride, m.weighted ? h->d_w : nullptr, h->w_wo};
-    x.channels = ch;
+    x.channels = ch; x.l1 = m.l1;
     for (int s = 0; s < 2; ++s)
         for (int c = 0; c < np; ++c) x.S[s][c] = sr ? h->d_sr[s][c] : h->d_state[s][c];
     ChainSolve j;
@@ -3924,8 +3949,9 @@ int taped_denoise(bpltv_t* h, const TapedModel& m, const double* w, int wo, cons
     h->last_is_sr = sr;
     h->last_weighted = m.weighted;
     h->last_channels = m.channels;
+    h->last_l1 = m.l1;
     if (!d_tape_user && taped) {
-        tape.record(p, am, an, each, m.weighted ? wo : 0, wmin, C);
+        tape.record(p, am, an, each, m.weighted ? wo : 0, m.l1 ? 0.0 : wmin, C);
         tape.channels = m.channels;
     }
     if (u_out) {
@@ -3988,6 +4014,7 @@ int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const 
     const bpltv_params p0 = resolve(pp, sr);
     if (int prc = unrolled_check_params(h, p0, who)) return prc;
     if (d_grad_w && !h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: grad_w reads the resident f: bpltv_set_data has not been called", who);
+    if (m.l1 && !h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: the L1 sweep reads the resident f: bpltv_set_data has not been called", who);
     const int K = p0.maxiter, C = tape_spacing(m, K, h->opt.tape_checkpoint);
     if (C && !h->has_data)
         return set_err(h, BPLTV_E_NODATA, "%s: a checkpointed sweep recomputes on the resident f: bpltv_set_data has not been called", who);
@@ -4021,14 +4048,14 @@ int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const 
     if (int rc = stage_param(h, who, alpha, dev, am, an, m.slices, each, 0, &p0, m.weighted ? w : nullptr, m.weighted ? wo : 1,
                              {{d_gu, tot, "cotangent gu"}}, &p, &g, false))
         return rc;
-    if (m.weighted && !d_tape_user && tape.gamma != g.w_min)
+    if (m.weighted && !m.l1 && !d_tape_user && tape.gamma != g.w_min)
         return set_err(h, BPLTV_E_ARG, "%s: the handle's tape was recorded with gamma = min w = %g, this call's w has %g", who, tape.gamma, g.w_min);
     const bool amap = am == h->M && an == h->N && !(h->M == 1 && h->N == 1);
     if (d_grad_alpha && !amap && !each)
         if (int rc = ensure(h, &h->d_red, &h->red_cap, (size_t)m.slices * am * an * h->O)) return rc;
     h->has_per_image = false;
     double* d_tab = nullptr;
-    if (int rc = get_table(h, p, &d_tab, m.L2, 0, m.weighted ? g.w_min : 1.0)) return rc;
+    if (int rc = get_table(h, p, &d_tab, m.L2, 0, m.l1 ? 0.0 : (m.weighted ? g.w_min : 1.0))) return rc;
     const size_t seg_tape = (size_t)m.tape_planes * C * tot, seg_need = seg_tape + (size_t)2 * np * tot;
     // grown after the last rejection, so that a rejected call never moves it (and orphans the graphs keyed by it); the new
     // buffer first: a failed allocation leaves the handle as it was
@@ -4046,7 +4073,7 @@ int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const 
     }
     TapedRev x{h, pl, d_tab, d_tape_user ? d_tape_user : tape.d, &g, {}, d_ws + (size_t)2 * np * tot, d_ws + (size_t)(2 * np + 1) * tot,
                d_ws + (size_t)(2 * np + 1 + m.slices) * tot, d_grad_w ? h->d_unr_gw : nullptr, p.maxiter};
-    x.channels = m.channels ? m.channels : 1;
+    x.channels = m.channels ? m.channels : 1; x.l1 = m.l1;
     for (int s = 0; s < 2; ++s)
         for (int c = 0; c < np; ++c) x.S[s][c] = d_ws + (size_t)(np * s + c) * tot;
     const bpltv_stats_t kept = h->st;
@@ -4059,7 +4086,7 @@ int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const 
     j.key = GraphKey{p.maxiter, pl.T, m.rev_variant + (x.gw ? 1 : 0), am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)x.tape, (const void*)d_tab, 0,
                      (const void*)g.alpha, m.weighted ? 0 : g.astride, m.weighted ? wo : 0, C, C ? (const void*)h->d_seg : nullptr, C ? plf.T : 0};
     TapedFwd xf{h, plf, d_tab, h->d_seg, {}, g.alpha, g.am, g.an, g.astride, g.w, g.wo};   // the recompute of a segment
-    xf.channels = x.channels;
+    xf.channels = x.channels; xf.l1 = m.l1;
     if (!C) {
         j.enqueue = launch_loop(pl.T, [&](const LaunchStep& s) { m.launch_rev(x, s); });
     } else {
@@ -4369,7 +4396,7 @@ int bpltv_destroy(bpltv_t* h) {
                     h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres, h->d_w, h->d_wst, h->d_unr, h->d_ujv, h->d_wjv, h->d_unr_gw, h->d_srunr, h->d_seg};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
-    for (Tape* t : {&h->tape, &h->wtape, &h->srtape, &h->ctape, &h->cwtape}) t->release();
+    for (Tape* t : {&h->tape, &h->wtape, &h->srtape, &h->ctape, &h->cwtape, &h->l1tape}) t->release();
     for (int s = 0; s < 2; ++s)
         for (int c = 0; c < 3; ++c) {
             if (h->d_state[s][c]) (void)hipFree(h->d_state[s][c]);
@@ -4408,7 +4435,7 @@ static int set_data_impl(bpltv_t* h, const double* ubar, const double* f, hipMem
     h->has_data = true;
     h->has_result = false;
     h->f32_f_valid = false;
-    for (Tape* t : {&h->tape, &h->wtape, &h->srtape, &h->ctape, &h->cwtape})   // checkpoints are states of the solve on the old f: the sweep would recompute on the new one
+    for (Tape* t : {&h->tape, &h->wtape, &h->srtape, &h->ctape, &h->cwtape, &h->l1tape})   // checkpoints are states of the solve on the old f: the sweep would recompute on the new one
         if (t->spacing) t->valid = false;
     return BPLTV_OK;
 }
@@ -4867,6 +4894,39 @@ int bpltv_weighted_unrolled_vjp_device(bpltv_t* h, const double* d_tape, const d
                            d_grad_alpha, d_grad_w, false);
 }
 
+// The TV-L1 model: the plain solve is the taped solve's launches of the no-tape instantiation
+static int l1_denoise_entry(bpltv_t* h, const char* what, const double* w, int wo, const double* alpha, bool dev, int am, int an,
+                            const bpltv_params* pp, double* u_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, what, true, [&](bpltv_t* c) { return l1_denoise_entry(c, what, w, wo, alpha, dev, am, an, pp, u_out); },
+                              kTapedL1.multi_name);
+    return taped_denoise(h, kTapedL1, w, wo, alpha, dev, am, an, pp, nullptr, u_out, false, false);
+}
+int bpltv_lone_denoise(bpltv_t* h, const double* w, int wo, const double* alpha, int am, int an, const bpltv_params* pp, double* u_out) {
+    return l1_denoise_entry(h, "bpltv_lone_denoise", w, wo, alpha, false, am, an, pp, u_out);
+}
+int bpltv_lone_denoise_device(bpltv_t* h, const double* d_w, int wo, const double* d_alpha, int am, int an, const bpltv_params* pp) {
+    return l1_denoise_entry(h, "bpltv_lone_denoise_device", d_w, wo, d_alpha, true, am, an, pp, nullptr);
+}
+int bpltv_lone_unrolled_denoise(bpltv_t* h, const double* w, int wo, const double* alpha, int am, int an, const bpltv_params* pp, double* u_out) {
+    return taped_denoise_entry(h, kTapedL1, "bpltv_lone_unrolled_denoise", w, wo, alpha, false, am, an, pp, nullptr, u_out, false);
+}
+int bpltv_lone_unrolled_denoise_device(bpltv_t* h, const double* d_w, int wo, const double* d_alpha, int am, int an, const bpltv_params* pp,
+                                     double* d_tape) {
+    return taped_denoise_entry(h, kTapedL1, "bpltv_lone_unrolled_denoise_device", d_w, wo, d_alpha, true, am, an, pp, d_tape, nullptr, false);
+}
+int bpltv_lone_unrolled_vjp(bpltv_t* h, const double* w, int wo, const double* alpha, int am, int an, const bpltv_params* pp, const double* gu,
+                          double* grad_f_out, double* grad_alpha_out, double* grad_w_out) {
+    return taped_vjp_entry(h, kTapedL1, "bpltv_lone_unrolled_vjp", false, nullptr, w, wo, alpha, am, an, pp, gu, grad_f_out, grad_alpha_out, grad_w_out,
+                           false);
+}
+int bpltv_lone_unrolled_vjp_device(bpltv_t* h, const double* d_tape, const double* d_w, int wo, const double* d_alpha, int am, int an,
+                                 const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alpha, double* d_grad_w) {
+    return taped_vjp_entry(h, kTapedL1, "bpltv_lone_unrolled_vjp_device", true, d_tape, d_w, wo, d_alpha, am, an, pp, d_gu, d_grad_f, d_grad_alpha,
+                           d_grad_w, false);
+}
+
 // bpltv_unrolled_jvp, bpltv_unrolled_jvp_each and bpltv_weighted_unrolled_jvp on a single-device handle: the host arrays
 // staged around unrolled_jvp_common.  W (nullable: the TV model): the weighted model's host w and host dw.
 static int unrolled_jvp_host(bpltv_t* h, const char* who, const double* alpha, int am, int an, const bpltv_params* pp, int ndir, const double* df,
@@ -5070,6 +5130,8 @@ int bpltv_duality_gap(bpltv_t* h, double* gap_out) {
     const bool sr = h->last_is_sr;
     if (!sr && h->last_channels)
         return set_err(h, BPLTV_E_UNSUPPORTED, "duality gap of a channel-coupled solve (channels = %d): the gap of the coupled model is not implemented", h->last_channels);
+    if (!sr && h->last_l1)
+        return set_err(h, BPLTV_E_UNSUPPORTED, "duality gap of a TV-L1 solve: its dual has a pointwise constraint the iterate does not meet; the gap is not implemented");
     const Model model = sr ? MODEL_SR : (h->last_weighted ? MODEL_W : MODEL_TV);
     if (model == MODEL_W && !(h->w_min > 0.0))   // gamma = min w > 0: the weighted model's dual objective divides by w
         return set_err(h, BPLTV_E_UNSUPPORTED, "duality gap of a weighted solve: the dual objective divides by w, every entry must be > 0 (min = %g)", h->w_min);

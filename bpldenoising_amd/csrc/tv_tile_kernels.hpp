@@ -8,8 +8,10 @@
 //         <0,1,0>  bpltv_unrolled_denoise (4.6)                    <0,0,0>  its checkpoint pass (4.10)
 //         <1,1,0>  bpltv_weighted_unrolled_denoise (4.8)
 //         <0,0,1>  bpltv_unrolled_jvp (4.7)                        <1,0,1>  bpltv_weighted_unrolled_jvp (4.11)
-//     tv_reverse_tile_kernel<WEIGHTED>
+//         <1,1,0,L1>  bpltv_lone_unrolled_denoise (4.18)             <1,0,0,L1>  bpltv_lone_denoise and the checkpoint pass (4.18)
+//     tv_reverse_tile_kernel<WEIGHTED, L1>
 //         <0>      bpltv_unrolled_vjp (4.6)                        <1>      bpltv_weighted_unrolled_vjp (4.8)
+//         <1,L1>   bpltv_lone_unrolled_vjp (4.18)
 //
 // Forward, per pixel, iteration k = 0 ... K-1 from x = f, y = 0 ("spec v2" of pdhg_tile_kernel<double, 1, 1, 32, 32> with
 // rho = 0; explicit fma, -ffp-contract=off):
@@ -20,6 +22,8 @@
 //     z     = fma(sigma_k, G xbar, y)
 //     TAPE:       store z1, z2 (WEIGHTED: and x_new) of the core pixels: [k][component][image][pixel], private
 //     n2    = fma(z2, z2, z1*z1);  out = n2 > alpha^2;   y = out ? z * (alpha*rsqrt_nr(n2)) : z
+//      L1 (the data term w |u - f| in place of w/2 (u - f)^2; WEIGHTED's registers, tape and launch; step table with gamma = 0):
+//                 v = fma(-tau_k, div, x);  d = v - f;  m = |d| - tau_k*w;  x_new = m > 0 ? f + copysign(m, d) : f
 // The two primal steps are two forms, not one with w = 1: each is pinned bit for bit.  !WEIGHTED gives bpltv_denoise's u
 // (tests/test_gpu_unrolled.py), WEIGHTED bpltv_weighted_denoise's (tests/test_gpu_weighted_unrolled.py), whatever TAPE and
 // TANGENT; and with w == 1.0 each weighted operation returns the bits of the one it replaces (tests/test_gpu_weighted.py).
@@ -42,6 +46,10 @@
 //     !WEIGHTED:  c = 1/(1 + tau_k) (tabulated);  gf += tau_k*c*gxn;  gy = gz - tau_k*c * G gxn;  gx = c*gxn - omega_k*gxb
 //      WEIGHTED:  r = 1.0 / fma(tau_k, w, 1.0);  h = gxn*r;  gf += tau_k*(w*h);  gw += tau_k*((f - x_{k+1})*h);
 //                 gy = gz - tau_k * G h;  gx = h - omega_k*gxb
+//      L1:        act = x_{k+1} != f || w == 0;  h = act ? gxn : 0;  gf += act ? 0 : gxn;  gw += -tau_k*(sign(x_{k+1} - f)*h);
+//                 gy = gz - tau_k * G h;  gx = h - omega_k*gxb                        (decided on the tape alone)
+//                 (w == 0: the threshold is the identity, x_new = v whatever d is, and so is its derivative -- without it a
+//                 pixel without data whose d is zero up to rounding would be read as held at f or not by that rounding)
 // and dL/df = gf + gx after the last step (x_0 = f, y_0 = 0).  The two tails agree to rounding only at w = 1
 // (tests/test_gpu_weighted_unrolled.py).  The weighted sweep needs no w > 0: a mask (w in {0, 1}) gets gradients in f, alpha, w.
 #pragma once
@@ -88,9 +96,10 @@ struct TvTileArgs {
 // TAPE: two or three stores per iteration for the core pixels (valid in every iteration of a launch).
 // TANGENT: a second set of LDS planes (same layout, same zero guards) for the tangent duals and dxb, written in front of the
 // same two barriers as the primal ones.  Out-of-image lanes hold zero in every value (w = 0 there: r = 1) and keep it.
-template <bool WEIGHTED, bool TAPE, bool TANGENT>
+template <bool WEIGHTED, bool TAPE, bool TANGENT, bool L1 = false>
 __global__ __launch_bounds__(TV_R * TV_R) void tv_tile_kernel(TvTileArgs A) {
     static_assert(!(TAPE && TANGENT), "the tangent sweep records nothing");
+    static_assert(!L1 || (WEIGHTED && !TANGENT), "the L1 data term takes the weighted model's w and tape, and has no tangent sweep");
     constexpr int RI = TV_R, RJ = TV_R, S1 = RI + 1;
     constexpr int PLANES = RJ * S1 + (RJ + 1) * RI + RJ * RI + RI + 1;   // doubles of one set of planes (pdhg_lds_bytes)
     static_assert(PLANES * sizeof(double) == tv_lds_bytes(), "the plane layout is pdhg_lds_bytes'");
@@ -213,15 +222,23 @@ __global__ __launch_bounds__(TV_R * TV_R) void tv_tile_kernel(TvTileArgs A) {
             dy2m = sd2[lj * RI + li];
         }
         const double div = (y1m - y1) + (y2m - y2);
-        double t;
-        if constexpr (WEIGHTED) {
-            t = __builtin_fma(-w, f, div);
-            r = 1.0 / __builtin_fma(tau, w, 1.0);
-        } else {
-            t = div - f;
-        }
         const double xo = x;
-        const double xn = __builtin_fma(-tau, t, xo) * r;
+        double xn;
+        if constexpr (L1) {   // soft threshold around f: no division, no r
+            const double v = __builtin_fma(-tau, div, xo);
+            const double d = v - f;
+            const double m = __builtin_fabs(d) - tau * w;
+            xn = (m > 0.0) ? f + __builtin_copysign(m, d) : f;
+        } else {
+            double t;
+            if constexpr (WEIGHTED) {
+                t = __builtin_fma(-w, f, div);
+                r = 1.0 / __builtin_fma(tau, w, 1.0);
+            } else {
+                t = div - f;
+            }
+            xn = __builtin_fma(-tau, t, xo) * r;
+        }
         const double b = __builtin_fma(-omega, xo, opw * xn);
         x = xn;
         double db = 0.0;
@@ -312,7 +329,7 @@ struct TvTileRevArgs {
     double* ga;             // in place, owning core only: per-pixel parameter gradient
     double* gw;             // WEIGHTED: in place, owning core only: per-pixel, per-image weight gradient; nullptr: not wanted
     const double* tape;     // [maxiter][2 or 3][O][M*N]
-    const double* f;        // WEIGHTED: the dataset; read only when gw is wanted
+    const double* f;        // WEIGHTED: the dataset; read only when gw is wanted (L1: always)
     const double* w;        // WEIGHTED
     const double* alpha;
     const double* tab;
@@ -334,8 +351,9 @@ struct TvTileRevArgs {
 // guard row (G^T: neighbours i-1, j-1); gxn (WEIGHTED: h = r o gxn) through the padded plane (G: neighbours i+1, j+1) -- the
 // layouts of sy1, sy2, sxb.  Out-of-image lanes stay zero (w = 0 there: r = 1): the duals of the last image row / column
 // enter the planes as 0, as G^T treats them.  w and f are loaded once per launch.
-template <bool WEIGHTED>
+template <bool WEIGHTED, bool L1 = false>
 __global__ __launch_bounds__(TV_R * TV_R) void tv_reverse_tile_kernel(TvTileRevArgs A) {
+    static_assert(!L1 || WEIGHTED, "the L1 data term takes the weighted model's w and tape");
     constexpr int RI = TV_R, RJ = TV_R, S1 = RI + 1;
     constexpr int NC = WEIGHTED ? 3 : 2;             // tape components
     extern __shared__ __attribute__((aligned(16))) unsigned char tv_smem[];
@@ -356,6 +374,7 @@ __global__ __launch_bounds__(TV_R * TV_R) void tv_reverse_tile_kernel(TvTileRevA
     const int amode = (A.am == 1 && A.an == 1) ? 0 : ((A.am == M && A.an == N) ? 2 : 1);
     const bool first = A.first != 0;
     const bool want_w = WEIGHTED && A.gw != nullptr;   // (uniform)
+    const bool want_x = L1 || want_w;                  // L1: the taped iterate and f decide the branch, whatever is wanted
     const int nit = A.nit;
     const int klo = A.khi - nit + 1;
 
@@ -386,7 +405,7 @@ __global__ __launch_bounds__(TV_R * TV_R) void tv_reverse_tile_kernel(TvTileRevA
     double al = A.alpha[ai];
     double w = 0.0, f = 0.0;
     if constexpr (WEIGHTED) w = A.w[(size_t)img * A.wstride + pix];
-    if (want_w) f = A.f[base + pix];
+    if (want_x) f = A.f[base + pix];
     double z1[TV_REV_T], z2[TV_REV_T], xp[TV_REV_T];   // [s]: iteration khi - s (xp: the primal iterate, for gw)
     const double* tz = A.tape + (size_t)NC * A.plane * (A.khi - A.tk0) + base + pix;
 #pragma unroll
@@ -395,7 +414,7 @@ __global__ __launch_bounds__(TV_R * TV_R) void tv_reverse_tile_kernel(TvTileRevA
         if (s < nit) {
             z1[s] = tz[0];
             z2[s] = tz[A.plane];
-            if (want_w) xp[s] = tz[2 * A.plane];
+            if (want_x) xp[s] = tz[2 * A.plane];
         }
         tz -= NC * A.plane;
     }
@@ -440,7 +459,21 @@ __global__ __launch_bounds__(TV_R * TV_R) void tv_reverse_tile_kernel(TvTileRevA
             const double gt = (sg1[lj * S1 + li] - m1) + (sg2[lj * RI + li] - m2);
             const double gxb = sigma * gt;
             const double gxn = gx + opw * gxb;
-            if constexpr (WEIGHTED) {
+            if constexpr (L1) {
+                const double xk = xp[s];
+                const bool act = in && (xk != f || w == 0.0);   // the threshold let the step through, or there is none (w == 0:
+                                                                // the identity); out-of-image lanes stay zero
+                const double h = act ? gxn : 0.0;
+                sxn[l] = h;
+                __syncthreads();
+                const double d1 = sxn[n1] - h;
+                const double d2 = sxn[n2] - h;
+                gf += act ? 0.0 : gxn;
+                if (want_w) gw += -tau * ((xk > f) ? h : ((xk < f) ? -h : 0.0));   // (x+ == f with w == 0: d = 0, no side)
+                gy1 = gz1 - tau * d1;
+                gy2 = gz2 - tau * d2;
+                gx = h - omega * gxb;
+            } else if constexpr (WEIGHTED) {
                 const double r = 1.0 / __builtin_fma(tau, w, 1.0);
                 const double h = gxn * r;
                 sxn[l] = h;

@@ -106,6 +106,14 @@ in place of the fidelity.  One mask for the channels is colour inpainting, a mas
 regulariser fills a masked channel in from the others.  backward is one bpltv_color_weighted_unrolled_vjp_device call over a
 tape of 3 * maxiter * B*C*H*W doubles and returns f.grad, alpha.grad and w.grad.  No jvp: forward_mode=True raises a ValueError.
 
+    u = tv_l1_denoise_unrolled(f, alpha, w, maxiter=50)          # TV-L1, for impulse noise (bpltv_lone_unrolled_*)
+
+f, alpha and w as for tv_denoise_weighted_unrolled, but the data term is sum w |u - f|: salt-and-pepper noise, outliers and dead
+pixels are removed exactly instead of being smeared, and the rest keeps its contrast.  backward is one
+bpltv_lone_unrolled_vjp_device call over a tape of 3 * maxiter * B*H*W doubles and returns f.grad, alpha.grad and w.grad, so a
+fidelity map can be trained against impulse noise.  TVL1DenoiseUnrolled(alpha, w, maxiter=50, learn_w=False) is the module: w
+is a buffer, or a Parameter with learn_w=True.  No jvp: forward_mode=True raises a ValueError.
+
 Streams: the library runs its kernels on its own HIP streams and blocks until they are done.  Every call below first
 synchronises the tensors' current torch stream, so that the library reads inputs torch has finished writing; its
 outputs are complete when the call returns.
@@ -284,7 +292,7 @@ def _no_checkpoint(solver_kw):
     return {k: v for k, v in solver_kw.items() if k != "checkpoint_every"}
 
 
-# ---- the one implementation behind the seventeen Functions below ----------------------------------------------------------------
+# ---- the one implementation behind the eighteen Functions below ----------------------------------------------------------------
 # A model is a row of this record; _forward, _backward and _jvp are every Function's three methods, written once over it.
 # The TVSolver entries are named, not held: they are looked up on the handle of the call.  Their argument lists mirror the C
 # ABI and are not regular -- the channel count first, `w, wo` in front of alpha, the tape first in a vjp, a trailing u_ptr in
@@ -300,6 +308,7 @@ class _Model(typing.NamedTuple):
     w: typing.Optional[str] = None      # a per-pixel weight behind alpha: the caller's name in the messages of its check
     w_zeros: bool = False    # ... which may hold zeros, so the layer itself refuses what is negative or not finite
     channels: bool = False   # f is (B, C, H, W): the handle holds B*C planes and every entry takes C first
+    reads_f: bool = False    # the reverse sweep reads the dataset whatever is asked of it (TV-L1: f decides the branch)
 
     @property
     def reg(self):           # the implicit TV and sum-of-regularisers adjoints take the reference's linearisation switch
@@ -330,6 +339,8 @@ _COLOR_WEIGHTED_UNROLLED = _Model(functools.partial(_check_args_color, name="tv_
                                   "color_weighted_unrolled_denoise_device", "color_weighted_unrolled_vjp_device", None,
                                   "weighted_unrolled_tape_doubles", w="tv_denoise_color_weighted_unrolled", w_zeros=True,
                                   channels=True)
+_L1_UNROLLED = _Model(_check_args, "l1_unrolled_denoise_device", "l1_unrolled_vjp_device", None, "weighted_unrolled_tape_doubles",
+                      w="tv_l1_denoise_unrolled", w_zeros=True, reads_f=True)
 
 
 def _forward(m, ctx, f, alpha, solver_kw, reg=None, w=None, jvp=False):
@@ -397,7 +408,7 @@ def _backward(m, ctx, gu):
     lead = ((ctx.channels,) if m.channels else ()) + (x.data_ptr(),)
     if m.w:   # the implicit w.grad reads f through a pointer of its own, given only when it is wanted
         lead += (() if m.tape else (_ptr(f if need_w else None),)) + (w.data_ptr(), ctx.wo)
-    if m.tape and f is not None and (need_w or kw.get("checkpoint_every")):
+    if m.tape and f is not None and (need_w or m.reads_f or kw.get("checkpoint_every")):
         s.set_data_device(f.data_ptr(), f.data_ptr())   # the unrolled w.grad and a checkpointed sweep's recompute read the dataset
     if m.reg:
         kw = dict(reg=ctx.reg, **kw)
@@ -776,3 +787,46 @@ def tv_denoise_color_weighted_unrolled(f, alpha, w, maxiter=50, checkpoint_every
                      "tv_denoise_color_unrolled(..., forward_mode=True), without a weight,")
     return TVDenoiseColorWeightedUnrolledFunction.apply(f, alpha, w, _with_checkpoint(dict(solver_kw, maxiter=int(maxiter)),
                                                                                        checkpoint_every))
+
+
+# ---- TV-L1 (TVSolver.l1_unrolled_*): the data term w |u - f|, for salt-and-pepper noise, outliers and dead pixels ----
+class TVL1DenoiseUnrolledFunction(torch.autograd.Function):
+    """autograd.Function of tv_l1_denoise_unrolled (below); apply(f, alpha, w, solver_kw).  No jvp."""
+    forward = staticmethod(lambda ctx, f, alpha, w, solver_kw: _forward(_L1_UNROLLED, ctx, f, alpha, solver_kw, w=w))
+    backward = staticmethod(once_differentiable(lambda ctx, gu: _backward(_L1_UNROLLED, ctx, gu)))
+
+
+def tv_l1_denoise_unrolled(f, alpha, w, maxiter=50, checkpoint_every=None, forward_mode=False, **solver_kw):
+    """TV-L1 denoising by exactly maxiter PDHG iterations: min_u sum_pixels w |u - f| + sum_pixels alpha |grad u|
+    (TVSolver.l1_unrolled_denoise_device).  The primal step is a soft threshold around f, so an isolated outlier of any height
+    is removed exactly and the rest of the image keeps its contrast.  Differentiable in f, alpha and w through the iterations
+    (TVSolver.l1_unrolled_vjp_device); the derivative is exact wherever no pixel sits on the threshold.
+    f, alpha, w, checkpoint_every and solver_kw as tv_denoise_weighted_unrolled's: w float64 on f's device, >= 0 with zeros
+    allowed, (H, W) -- w.grad then summed over the batch -- or f's shape (B, H, W).  accel changes nothing: the data term has no
+    strong convexity and the steps are constant.
+    forward_mode=True raises: the tangent sweep of this model is not built."""
+    _no_forward_mode("tv_l1_denoise_unrolled", forward_mode, "the TV-L1 iterations",
+                     "tv_denoise_weighted_unrolled(..., forward_mode=True), with the quadratic data term,")
+    return TVL1DenoiseUnrolledFunction.apply(f, alpha, w, _with_checkpoint(dict(solver_kw, maxiter=int(maxiter)), checkpoint_every))
+
+
+class TVL1DenoiseUnrolled(torch.nn.Module):
+    """tv_l1_denoise_unrolled behind a learnable scalar, patch parameter or pixel map alpha and a fidelity map w: a buffer, or
+    with learn_w=True a Parameter too (keep it >= 0, by clamping after the optimiser's step).  Move it to the device of its
+    inputs with .to(device)."""
+
+    def __init__(self, alpha, w, maxiter=50, learn_w=False, checkpoint_every=None, **solver_kw):
+        super().__init__()
+        self.alpha = torch.nn.Parameter(torch.as_tensor(alpha, dtype=torch.float64).clone())
+        wt = torch.as_tensor(w, dtype=torch.float64).clone()
+        if learn_w:
+            self.w = torch.nn.Parameter(wt)
+        else:
+            self.register_buffer("w", wt)
+        self.maxiter = int(maxiter)
+        self.checkpoint_every = checkpoint_every
+        self.solver_kw = dict(solver_kw)
+
+    def forward(self, f):
+        return tv_l1_denoise_unrolled(f, self.alpha, self.w, maxiter=self.maxiter, checkpoint_every=self.checkpoint_every,
+                                      **self.solver_kw)

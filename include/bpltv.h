@@ -143,7 +143,8 @@ typedef struct bpltv_stats {
                                   12 reverse sweep over the taped channel-coupled iterations (bpltv_color_unrolled_vjp),
                                   13 tangent sweep through the channel-coupled iterations (bpltv_color_unrolled_jvp),
                                   14 reverse sweep over the taped weighted channel-coupled iterations
-                                  (bpltv_color_weighted_unrolled_vjp) */
+                                  (bpltv_color_weighted_unrolled_vjp),
+                                  15 reverse sweep over the taped TV-L1 iterations (bpltv_lone_unrolled_vjp) */
     int reg_gradient_used;     /* 1 if the last evaluate took the gradient_reg branch             */
     int ngpus;                 /* distinct devices behind this handle (1 for bpltv_create)        */
     int shards;                /* image shards (= worker threads) behind this handle              */
@@ -729,6 +730,61 @@ int bpltv_color_weighted_unrolled_vjp(bpltv_t *h, int channels, const double *w,
 int bpltv_color_weighted_unrolled_vjp_device(bpltv_t *h, int channels, const double *d_tape, const double *d_w, int wo,
                                              const double *d_alpha, int am, int an, const bpltv_params *p, const double *d_gu,
                                              double *d_grad_f, double *d_grad_alpha, double *d_grad_w);
+
+/* TV-L1 denoising: the absolute value in place of the square in the data term -- the model for
+ * salt-and-pepper noise, outliers and dead pixels, which a quadratic term smears into blobs ("lone": L-one; the names of this
+ * interface hold no digits):
+ *
+ *     min_u  sum_pixels w |u - f|  +  sum_pixels alpha |grad u|,      w >= 0
+ *
+ * Grey planes, Float64.  alpha as bpltv_denoise (scalar, patch or map); w as bpltv_weighted_denoise: wo = 1 (one plane for all O
+ * images) or wo = O, zeros legal (a pixel without data).  The data term has no strong convexity, so the step table is made with
+ * gamma = 0 whatever w is: omega = 1, constant steps, and accel = 0 and 1 give the same bits.  Iteration k, from x = f, y = 0, is
+ * bpltv_weighted_unrolled_denoise's except for the primal step, a soft threshold around f (explicit fma, no division):
+ *
+ *     v = fma(-tau_k, G^T y, x);  d = v - f;  m = |d| - tau_k*w;  x+ = m > 0 ? f + copysign(m, d) : f
+ *
+ * The contract is bpltv_weighted_unrolled_*'s: wo other than 1 or O, a NULL, negative or non-finite w, maxiter < 1 and a bad
+ * parameter are BPLTV_E_ARG; rho, init and order must be 0 (BPLTV_E_UNSUPPORTED); no data is BPLTV_E_NODATA; check_every and
+ * gap_tol are ignored; dtype = 32 handles compute in Float64; a multi-device handle forwards to its one shard and is
+ * BPLTV_E_UNSUPPORTED over more; every rejection comes before anything of the handle changes.  The results do not depend on
+ * tile_iters, on the launch chains, on use_graph, on the host or device form, on whose tape it is, or on option
+ * "tape_checkpoint".
+ *
+ * bpltv_lone_denoise: the recurrence without a tape; u is bitwise the taped solve's.
+ * bpltv_lone_unrolled_denoise: the same and the tape of z1, z2 (before the projection) and x+, in the weighted tape's layout and
+ * size: bpltv_weighted_unrolled_tape_doubles gives the doubles of a caller-owned d_tape.  A NULL d_tape, and the host form
+ * always, use a sixth tape owned by the handle, which remembers wo.  No other model's sweep accepts it, nor this sweep another
+ * model's tape, and each survives the others' solves; no captured graph is shared with the weighted model.  Either solve becomes
+ * the handle's last one for bpltv_u_device / bpltv_copy_u_device; bpltv_duality_gap after it is BPLTV_E_UNSUPPORTED until
+ * another model solves (the L1 dual has a pointwise constraint the iterate does not meet).
+ * stats: as bpltv_weighted_unrolled_denoise.  bytes_per_px_iter, from what the kernels load and store per pixel and iteration of
+ * a launch of one iteration: read x, y1, y2, f, w (40 bytes; + 8 for alpha with a map), write x, y1, y2 (24) -- 64 / 72 without a
+ * tape -- and write z1, z2, x+ onto the tape (24): 88 / 96.
+ *
+ * bpltv_lone_unrolled_vjp: reverse mode through the iterations, exact wherever no pixel sits on the threshold (the step table does
+ * not depend on w or alpha).  The tail of reverse step k decides on the tape alone:
+ *
+ *     act = (x+ != f) || (w == 0);  h = act ? gxn : 0;  gf += act ? 0 : gxn;  gw += -tau_k * (sign(x+ - f) * h)
+ *     gy = gz - tau_k * G h;  gx = h - omega_k * gxb
+ *
+ * (w == 0: the threshold is the identity, whatever d is, and so is its derivative; grad_w there is the one-sided derivative
+ * -tau_k * sign(d) * h, which is a choice of subgradient where d is zero up to rounding.)
+ * grad_f_out M*N*O doubles, grad_alpha_out am*an, grad_w_out w's shape (wo = 1: summed over the images in image order); any may
+ * be NULL, not all three.  The sweep always reads the resident f.  w's planes, alpha's shape and params must be the solve's:
+ * BPLTV_E_ARG on the handle's tape otherwise; no L1 tape or no dataset is BPLTV_E_NODATA.  Of the statistics only adjoint_ms
+ * and adjoint_method = 15 change. */
+int bpltv_lone_denoise(bpltv_t *h, const double *w, int wo, const double *alpha, int am, int an, const bpltv_params *p,
+                     double *u_out);
+int bpltv_lone_denoise_device(bpltv_t *h, const double *d_w, int wo, const double *d_alpha, int am, int an, const bpltv_params *p);
+int bpltv_lone_unrolled_denoise(bpltv_t *h, const double *w, int wo, const double *alpha, int am, int an, const bpltv_params *p,
+                              double *u_out);
+int bpltv_lone_unrolled_denoise_device(bpltv_t *h, const double *d_w, int wo, const double *d_alpha, int am, int an,
+                                     const bpltv_params *p, double *d_tape);
+int bpltv_lone_unrolled_vjp(bpltv_t *h, const double *w, int wo, const double *alpha, int am, int an, const bpltv_params *p,
+                          const double *gu, double *grad_f_out, double *grad_alpha_out, double *grad_w_out);
+int bpltv_lone_unrolled_vjp_device(bpltv_t *h, const double *d_tape, const double *d_w, int wo, const double *d_alpha, int am, int an,
+                                 const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alpha, double *d_grad_w);
 
 /* Forward mode through the channel-coupled iterations: bpltv_unrolled_jvp and
  * bpltv_unrolled_gauss_newton for the model above.  The tangent (dx, dy) is carried beside (x, y) through the same maxiter
