@@ -518,6 +518,12 @@ struct bpltv_handle {
     // planes (its gamma is 0 whatever w is); the reverse sweep runs in d_unr and d_unr_gw.  last_l1: the last solve was this model's
     Tape l1tape;
     bool last_l1 = false;
+    // ... of the TV-KL model: a seventh tape, as the L1 tape.  last_kl: the last solve was this model's.
+    // f_nonneg: the installed dataset is finite and >= 0, as the KL data term needs (-1: not looked at yet, 0: it is not, 1: it
+    // is) -- remembered with the dataset, so that it is reduced at most once
+    Tape kltape;
+    bool last_kl = false;
+    int f_nonneg = -1;
     bool color_ready = false;
     bool color_jvp_ready = false;
     // checkpointed reverse sweeps of the four models (option "tape_checkpoint"): [segment tape | 2 recompute state sets],
@@ -2436,6 +2442,7 @@ int solve_dataset(bpltv_t* h, bool sr, const bpltv_params& p) {
     h->last_weighted = false;
     h->last_channels = 0;
     h->last_l1 = false;
+    h->last_kl = false;
     return BPLTV_OK;
 }
 // u of the last solve of the model
@@ -3273,6 +3280,21 @@ int check_weight(bpltv_t* h, const char* who, const double* w, bool on_device, s
     return BPLTV_OK;
 }
 
+// The TV-KL model's dataset: finite and >= 0, by alpha_check_kernel on the resident f.  The answer is
+// kept with the dataset (bpltv_set_data forgets it), so a dataset is reduced at most once.  Reads only, but for that memo.
+int check_dataset_nonneg(bpltv_t* h, const char* who) {
+    if (h->f_nonneg < 0) {
+        int failed = -1;
+        double fmin = 0.0;
+        unsigned long long* chk = reinterpret_cast<unsigned long long*>(h->d_scalar + 2);
+        if (int rc = check_device_arrays(h, chk, {h->d_f, h->tot}, {}, &fmin, &failed)) return rc;
+        h->f_nonneg = failed == 0 ? 0 : 1;
+    }
+    if (!h->f_nonneg)
+        return set_err(h, BPLTV_E_ARG, "%s: the dataset f has a negative or non-finite entry: the Kullback-Leibler data term needs f finite and >= 0", who);
+    return BPLTV_OK;
+}
+
 // Tiling of a weighted solve: 32 x 32 regions, T iterations per launch (params.tile_iters, default 8; a halo must leave a
 // core, and the kernel keeps at most PDHG_MAX_T step rows).  Results do not depend on T.
 struct WeightedPlan { int T, nTi, nTj; };
@@ -3300,7 +3322,7 @@ int weighted_check_params(bpltv_t* h, const bpltv_params& p, const char* who) {
 // One launch of tv_tile_kernel.  The caller has set what its entry point owns -- the planes, alpha (and w), the tape, the
 // tangents; here: what every launch has, and the instance (a tape means TAPE)
 void tv_tile_launch(bpltv_t* h, const WeightedPlan& pl, const double* tab, const LaunchStep& s, bool weighted, bool tangent, TvTileArgs& a,
-                    bool l1 = false) {
+                    bool l1 = false, bool kl = false) {
     a.f = h->d_f; a.tab = tab;
     a.it0 = s.it; a.nit = s.nit;
     a.M = h->M; a.N = h->N; a.halo = pl.T; a.first = s.first; a.img0 = s.lo;
@@ -3308,6 +3330,7 @@ void tv_tile_launch(bpltv_t* h, const WeightedPlan& pl, const double* tab, const
                                : a.tape   ? (weighted ? &tv_tile_kernel<true, true, false> : &tv_tile_kernel<false, true, false>)
                                           : (weighted ? &tv_tile_kernel<true, false, false> : &tv_tile_kernel<false, false, false>);
     if (l1) kern = a.tape ? &tv_tile_kernel<true, true, false, true> : &tv_tile_kernel<true, false, false, true>;   // (weighted, no tangent)
+    if (kl) kern = a.tape ? &tv_tile_kernel<true, true, false, false, true> : &tv_tile_kernel<true, false, false, false, true>;
     hipLaunchKernelGGL(kern, dim3(pl.nTi, pl.nTj, s.hi - s.lo), dim3(TV_R * TV_R), tangent ? tv_tangent_lds_bytes() : tv_lds_bytes(), s.st, a);
 }
 
@@ -3376,6 +3399,7 @@ int weighted_denoise_common(bpltv_t* h, const double* w, int wo, const double* a
     h->last_weighted = true;
     h->last_channels = 0;
     h->last_l1 = false;
+    h->last_kl = false;
     if (u_out) {
         HIPCHK(h, hipMemcpyAsync(u_out, h->d_state[buf][0], h->tot * sizeof(double), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
@@ -3487,6 +3511,7 @@ struct TapedFwd {
     int wo;
     int channels = 1;    // channel-coupled model: planes of a colour image
     bool l1 = false;     // TV-L1 model: the weighted launch with the L1 primal step
+    bool kl = false;     // TV-KL model: the weighted launch with the KL primal step
 };
 // the planes a launch reads and writes: a state set, or the step's checkpoint slot
 static void taped_planes(const LaunchStep& s, int np, size_t tot, double* const (*S)[7], const double** in, double** out) {
@@ -3508,6 +3533,7 @@ struct TapedRev {
     int K;
     int channels = 1;    // channel-coupled model: planes of a colour image
     bool l1 = false;     // TV-L1 model: the weighted launch with the L1 tail
+    bool kl = false;     // TV-KL model: the weighted launch with the KL tail
 };
 
 // A model whose iterations can be taped and swept backwards: everything the two shared drivers (taped_denoise, taped_vjp)
@@ -3523,6 +3549,8 @@ struct TapedModel {
     bool weighted;                // takes a fidelity weight w: checked and staged, gamma = min w in the step table, grad_w
     bool l1;                      // TV-L1 model: weighted's plumbing with gamma = 0 whatever w is (no strong convexity), a sweep
                                   // that always reads the resident f, and no duality gap after its solves
+    bool kl;                      // TV-KL model: the same, and a dataset that must be finite and >= 0
+    bool flat() const { return l1 || kl; }   // no strong convexity: gamma = 0, omega = 1, constant steps
     int channels;                 // channel-coupled model: the planes of a colour image, which the launch chains keep together
                                   // and the handle's tape remembers (0: every plane is an image of its own)
     int nplanes;                  // planes of a state set
@@ -3550,7 +3578,7 @@ void tv_launch_fwd(const TapedFwd& x, const LaunchStep& s) {   // x.w != nullptr
     a.w = x.w; a.wstride = x.wo > 1 ? h->npx : 0;
     a.alpha = x.alpha; a.am = x.am; a.an = x.an; a.istride = x.astride;
     a.tape = x.tape; a.plane = h->tot; a.tk0 = s.tk0;
-    tv_tile_launch(h, x.pl, x.tab, s, x.w != nullptr, false, a, x.l1);
+    tv_tile_launch(h, x.pl, x.tab, s, x.w != nullptr, false, a, x.l1, x.kl);
 }
 // `it` counts reverse steps: step r undoes iteration K - 1 - r.  g.w != nullptr: the weighted model (its kernel reads the
 // resident f for gw only)
@@ -3565,6 +3593,7 @@ void tv_launch_rev(const TapedRev& x, const LaunchStep& s) {
     a.khi = x.K - 1 - s.it; a.nit = s.nit; a.tk0 = s.tk0;
     a.M = x.h->M; a.N = x.h->N; a.halo = x.pl.T; a.first = s.first; a.img0 = s.lo;
     void (*kern)(TvTileRevArgs) = x.l1 ? &tv_reverse_tile_kernel<true, true> : (g.w ? &tv_reverse_tile_kernel<true> : &tv_reverse_tile_kernel<false>);
+    if (x.kl) kern = &tv_reverse_tile_kernel<true, false, true>;
     hipLaunchKernelGGL(kern, dim3(x.pl.nTi, x.pl.nTj, s.hi - s.lo), dim3(TV_R * TV_R), tv_lds_bytes(), s.st, a);
 }
 
@@ -3630,6 +3659,18 @@ const TapedModel kTapedL1 = [] {
     m.l1 = true;
     m.fwd_variant = 20; m.rev_variant = 23;
     m.adjoint_method = 15;
+    return m;
+}();
+// The TV-KL model: as the TV-L1 model, with a tape of its own and graph variants of its own under
+// MODEL_UN: 30 = taped solve, 32 = plain solve, 33 / 34 = reverse sweep without / with grad_w.
+const TapedModel kTapedKL = [] {
+    TapedModel m = kTapedWeighted;
+    m.denoise = "bpltv_kl_unrolled_denoise"; m.vjp = "kl_unrolled_vjp"; m.tape_kind = "KL ";
+    m.multi_name = "the TV-KL solve";
+    m.tape = &bpltv_handle::kltape;
+    m.kl = true;
+    m.fwd_variant = 30; m.rev_variant = 33;
+    m.adjoint_method = 16;
     return m;
 }();
 // ... read x, 6 y, f (+ 3 alpha), write x, 6 y and the 6 z
@@ -3828,7 +3869,7 @@ void segment_launches(int K, int C, int T, bool stagger, F fn) {
 int taped_denoise(bpltv_t* h, const TapedModel& m, const double* w, int wo, const double* alpha, bool dev, int am, int an,
                   const bpltv_params* pp, double* d_tape_user, double* u_out, bool each, bool taped = true) {
     const std::string name = taped ? std::string(m.denoise) + (each ? "_each" : "") + (dev ? "_device" : "")
-                                   : std::string(m.l1 ? "bpltv_lone_denoise" : (m.weighted ? "bpltv_color_weighted_denoise" : "bpltv_color_denoise")) + (dev ? "_device" : "");
+                                   : std::string(m.kl ? "bpltv_kl_denoise" : m.l1 ? "bpltv_lone_denoise" : (m.weighted ? "bpltv_color_weighted_denoise" : "bpltv_color_denoise")) + (dev ? "_device" : "");
     const char* who = name.c_str();
     const int ch = m.channels ? m.channels : 1;
     const bool sr = m.slices == 3;
@@ -3850,6 +3891,8 @@ int taped_denoise(bpltv_t* h, const TapedModel& m, const double* w, int wo, cons
     double wmin = 0.0;
     int rc = m.weighted ? check_weight(h, who, w, dev, nw, &wmin) : (int)BPLTV_OK;
     if (rc) return rc;
+    if (m.kl)
+        if (int frc = check_dataset_nonneg(h, who)) return frc;
     const int K = p.maxiter, C = taped ? tape_spacing(m, K, h->opt.tape_checkpoint) : 0, np = m.nplanes;
     const size_t tot = h->tot;
     const size_t need = C ? (size_t)np * tape_segments(K, C) * tot : (size_t)m.tape_planes * K * tot;
@@ -3881,13 +3924,13 @@ int taped_denoise(bpltv_t* h, const TapedModel& m, const double* w, int wo, cons
     }
     h->has_per_image = false;
     double* d_tab = nullptr;
-    rc = get_table(h, p, &d_tab, m.L2, 0, m.l1 ? 0.0 : (m.weighted ? h->w_min : 1.0));
+    rc = get_table(h, p, &d_tab, m.L2, 0, m.flat() ? 0.0 : (m.weighted ? h->w_min : 1.0));
     if (rc) return rc;
     const bool amap = (h->last_am == h->M && h->last_an == h->N) && !(h->M == 1 && h->N == 1);
     h->st.tile_iters = pl.T; h->st.tiles = pl.nTi * pl.nTj * (h->O / ch); h->st.region_i = m.region; h->st.region_j = m.region; h->st.pdhg_variant = 0;
     double* const buffer = !taped ? nullptr : (d_tape_user ? d_tape_user : tape.d);   // the tape, or the checkpoints
     TapedFwd x{h, pl, d_tab, C ? nullptr : buffer, {}, h->d_alpha, h->last_am, h->last_an, h->alpha_istride, m.weighted ? h->d_w : nullptr, h->w_wo};
-    x.channels = ch; x.l1 = m.l1;
+    x.channels = ch; x.l1 = m.l1; x.kl = m.kl;
     for (int s = 0; s < 2; ++s)
         for (int c = 0; c < np; ++c) x.S[s][c] = sr ? h->d_sr[s][c] : h->d_state[s][c];
     ChainSolve j;
@@ -3950,8 +3993,9 @@ int taped_denoise(bpltv_t* h, const TapedModel& m, const double* w, int wo, cons
     h->last_weighted = m.weighted;
     h->last_channels = m.channels;
     h->last_l1 = m.l1;
+    h->last_kl = m.kl;
     if (!d_tape_user && taped) {
-        tape.record(p, am, an, each, m.weighted ? wo : 0, m.l1 ? 0.0 : wmin, C);
+        tape.record(p, am, an, each, m.weighted ? wo : 0, m.flat() ? 0.0 : wmin, C);
         tape.channels = m.channels;
     }
     if (u_out) {
@@ -4015,6 +4059,7 @@ int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const 
     if (int prc = unrolled_check_params(h, p0, who)) return prc;
     if (d_grad_w && !h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: grad_w reads the resident f: bpltv_set_data has not been called", who);
     if (m.l1 && !h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: the L1 sweep reads the resident f: bpltv_set_data has not been called", who);
+    if (m.kl && !h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: the KL sweep reads the resident f: bpltv_set_data has not been called", who);
     const int K = p0.maxiter, C = tape_spacing(m, K, h->opt.tape_checkpoint);
     if (C && !h->has_data)
         return set_err(h, BPLTV_E_NODATA, "%s: a checkpointed sweep recomputes on the resident f: bpltv_set_data has not been called", who);
@@ -4048,14 +4093,14 @@ int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const 
     if (int rc = stage_param(h, who, alpha, dev, am, an, m.slices, each, 0, &p0, m.weighted ? w : nullptr, m.weighted ? wo : 1,
                              {{d_gu, tot, "cotangent gu"}}, &p, &g, false))
         return rc;
-    if (m.weighted && !m.l1 && !d_tape_user && tape.gamma != g.w_min)
+    if (m.weighted && !m.flat() && !d_tape_user && tape.gamma != g.w_min)
         return set_err(h, BPLTV_E_ARG, "%s: the handle's tape was recorded with gamma = min w = %g, this call's w has %g", who, tape.gamma, g.w_min);
     const bool amap = am == h->M && an == h->N && !(h->M == 1 && h->N == 1);
     if (d_grad_alpha && !amap && !each)
         if (int rc = ensure(h, &h->d_red, &h->red_cap, (size_t)m.slices * am * an * h->O)) return rc;
     h->has_per_image = false;
     double* d_tab = nullptr;
-    if (int rc = get_table(h, p, &d_tab, m.L2, 0, m.l1 ? 0.0 : (m.weighted ? g.w_min : 1.0))) return rc;
+    if (int rc = get_table(h, p, &d_tab, m.L2, 0, m.flat() ? 0.0 : (m.weighted ? g.w_min : 1.0))) return rc;
     const size_t seg_tape = (size_t)m.tape_planes * C * tot, seg_need = seg_tape + (size_t)2 * np * tot;
     // grown after the last rejection, so that a rejected call never moves it (and orphans the graphs keyed by it); the new
     // buffer first: a failed allocation leaves the handle as it was
@@ -4073,7 +4118,7 @@ int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const 
     }
     TapedRev x{h, pl, d_tab, d_tape_user ? d_tape_user : tape.d, &g, {}, d_ws + (size_t)2 * np * tot, d_ws + (size_t)(2 * np + 1) * tot,
                d_ws + (size_t)(2 * np + 1 + m.slices) * tot, d_grad_w ? h->d_unr_gw : nullptr, p.maxiter};
-    x.channels = m.channels ? m.channels : 1; x.l1 = m.l1;
+    x.channels = m.channels ? m.channels : 1; x.l1 = m.l1; x.kl = m.kl;
     for (int s = 0; s < 2; ++s)
         for (int c = 0; c < np; ++c) x.S[s][c] = d_ws + (size_t)(np * s + c) * tot;
     const bpltv_stats_t kept = h->st;
@@ -4086,7 +4131,7 @@ int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const 
     j.key = GraphKey{p.maxiter, pl.T, m.rev_variant + (x.gw ? 1 : 0), am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)x.tape, (const void*)d_tab, 0,
                      (const void*)g.alpha, m.weighted ? 0 : g.astride, m.weighted ? wo : 0, C, C ? (const void*)h->d_seg : nullptr, C ? plf.T : 0};
     TapedFwd xf{h, plf, d_tab, h->d_seg, {}, g.alpha, g.am, g.an, g.astride, g.w, g.wo};   // the recompute of a segment
-    xf.channels = x.channels; xf.l1 = m.l1;
+    xf.channels = x.channels; xf.l1 = m.l1; xf.kl = m.kl;
     if (!C) {
         j.enqueue = launch_loop(pl.T, [&](const LaunchStep& s) { m.launch_rev(x, s); });
     } else {
@@ -4396,7 +4441,7 @@ int bpltv_destroy(bpltv_t* h) {
                     h->d_gf2, h->d_vjp, h->d_jvp, h->d_jres, h->d_w, h->d_wst, h->d_unr, h->d_ujv, h->d_wjv, h->d_unr_gw, h->d_srunr, h->d_seg};
     for (void* p : ptrs)
         if (p) (void)hipFree(p);
-    for (Tape* t : {&h->tape, &h->wtape, &h->srtape, &h->ctape, &h->cwtape, &h->l1tape}) t->release();
+    for (Tape* t : {&h->tape, &h->wtape, &h->srtape, &h->ctape, &h->cwtape, &h->l1tape, &h->kltape}) t->release();
     for (int s = 0; s < 2; ++s)
         for (int c = 0; c < 3; ++c) {
             if (h->d_state[s][c]) (void)hipFree(h->d_state[s][c]);
@@ -4435,7 +4480,8 @@ static int set_data_impl(bpltv_t* h, const double* ubar, const double* f, hipMem
     h->has_data = true;
     h->has_result = false;
     h->f32_f_valid = false;
-    for (Tape* t : {&h->tape, &h->wtape, &h->srtape, &h->ctape, &h->cwtape, &h->l1tape})   // checkpoints are states of the solve on the old f: the sweep would recompute on the new one
+    h->f_nonneg = -1;
+    for (Tape* t : {&h->tape, &h->wtape, &h->srtape, &h->ctape, &h->cwtape, &h->l1tape, &h->kltape})   // checkpoints are states of the solve on the old f: the sweep would recompute on the new one
         if (t->spacing) t->valid = false;
     return BPLTV_OK;
 }
@@ -4927,6 +4973,39 @@ int bpltv_lone_unrolled_vjp_device(bpltv_t* h, const double* d_tape, const doubl
                            d_grad_w, false);
 }
 
+// The TV-KL model, as the TV-L1 model's entry points
+static int kl_denoise_entry(bpltv_t* h, const char* what, const double* w, int wo, const double* alpha, bool dev, int am, int an,
+                            const bpltv_params* pp, double* u_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (h->multi)
+        return weighted_multi(h, what, true, [&](bpltv_t* c) { return kl_denoise_entry(c, what, w, wo, alpha, dev, am, an, pp, u_out); },
+                              kTapedKL.multi_name);
+    return taped_denoise(h, kTapedKL, w, wo, alpha, dev, am, an, pp, nullptr, u_out, false, false);
+}
+int bpltv_kl_denoise(bpltv_t* h, const double* w, int wo, const double* alpha, int am, int an, const bpltv_params* pp, double* u_out) {
+    return kl_denoise_entry(h, "bpltv_kl_denoise", w, wo, alpha, false, am, an, pp, u_out);
+}
+int bpltv_kl_denoise_device(bpltv_t* h, const double* d_w, int wo, const double* d_alpha, int am, int an, const bpltv_params* pp) {
+    return kl_denoise_entry(h, "bpltv_kl_denoise_device", d_w, wo, d_alpha, true, am, an, pp, nullptr);
+}
+int bpltv_kl_unrolled_denoise(bpltv_t* h, const double* w, int wo, const double* alpha, int am, int an, const bpltv_params* pp, double* u_out) {
+    return taped_denoise_entry(h, kTapedKL, "bpltv_kl_unrolled_denoise", w, wo, alpha, false, am, an, pp, nullptr, u_out, false);
+}
+int bpltv_kl_unrolled_denoise_device(bpltv_t* h, const double* d_w, int wo, const double* d_alpha, int am, int an, const bpltv_params* pp,
+                                     double* d_tape) {
+    return taped_denoise_entry(h, kTapedKL, "bpltv_kl_unrolled_denoise_device", d_w, wo, d_alpha, true, am, an, pp, d_tape, nullptr, false);
+}
+int bpltv_kl_unrolled_vjp(bpltv_t* h, const double* w, int wo, const double* alpha, int am, int an, const bpltv_params* pp, const double* gu,
+                          double* grad_f_out, double* grad_alpha_out, double* grad_w_out) {
+    return taped_vjp_entry(h, kTapedKL, "bpltv_kl_unrolled_vjp", false, nullptr, w, wo, alpha, am, an, pp, gu, grad_f_out, grad_alpha_out, grad_w_out,
+                           false);
+}
+int bpltv_kl_unrolled_vjp_device(bpltv_t* h, const double* d_tape, const double* d_w, int wo, const double* d_alpha, int am, int an,
+                                 const bpltv_params* pp, const double* d_gu, double* d_grad_f, double* d_grad_alpha, double* d_grad_w) {
+    return taped_vjp_entry(h, kTapedKL, "bpltv_kl_unrolled_vjp_device", true, d_tape, d_w, wo, d_alpha, am, an, pp, d_gu, d_grad_f, d_grad_alpha,
+                           d_grad_w, false);
+}
+
 // bpltv_unrolled_jvp, bpltv_unrolled_jvp_each and bpltv_weighted_unrolled_jvp on a single-device handle: the host arrays
 // staged around unrolled_jvp_common.  W (nullable: the TV model): the weighted model's host w and host dw.
 static int unrolled_jvp_host(bpltv_t* h, const char* who, const double* alpha, int am, int an, const bpltv_params* pp, int ndir, const double* df,
@@ -5132,6 +5211,8 @@ int bpltv_duality_gap(bpltv_t* h, double* gap_out) {
         return set_err(h, BPLTV_E_UNSUPPORTED, "duality gap of a channel-coupled solve (channels = %d): the gap of the coupled model is not implemented", h->last_channels);
     if (!sr && h->last_l1)
         return set_err(h, BPLTV_E_UNSUPPORTED, "duality gap of a TV-L1 solve: its dual has a pointwise constraint the iterate does not meet; the gap is not implemented");
+    if (!sr && h->last_kl)
+        return set_err(h, BPLTV_E_UNSUPPORTED, "duality gap of a TV-KL solve: the gap of the Kullback-Leibler data term is not implemented");
     const Model model = sr ? MODEL_SR : (h->last_weighted ? MODEL_W : MODEL_TV);
     if (model == MODEL_W && !(h->w_min > 0.0))   // gamma = min w > 0: the weighted model's dual objective divides by w
         return set_err(h, BPLTV_E_UNSUPPORTED, "duality gap of a weighted solve: the dual objective divides by w, every entry must be > 0 (min = %g)", h->w_min);

@@ -9,9 +9,10 @@
 //         <1,1,0>  bpltv_weighted_unrolled_denoise (4.8)
 //         <0,0,1>  bpltv_unrolled_jvp (4.7)                        <1,0,1>  bpltv_weighted_unrolled_jvp (4.11)
 //         <1,1,0,L1>  bpltv_lone_unrolled_denoise (4.18)             <1,0,0,L1>  bpltv_lone_denoise and the checkpoint pass (4.18)
-//     tv_reverse_tile_kernel<WEIGHTED, L1>
+//         <1,1,0,0,KL>  bpltv_kl_unrolled_denoise (4.19)            <1,0,0,0,KL>  bpltv_kl_denoise and the checkpoint pass (4.19)
+//     tv_reverse_tile_kernel<WEIGHTED, L1, KL>
 //         <0>      bpltv_unrolled_vjp (4.6)                        <1>      bpltv_weighted_unrolled_vjp (4.8)
-//         <1,L1>   bpltv_lone_unrolled_vjp (4.18)
+//         <1,L1>   bpltv_lone_unrolled_vjp (4.18)                  <1,0,KL> bpltv_kl_unrolled_vjp (4.19)
 //
 // Forward, per pixel, iteration k = 0 ... K-1 from x = f, y = 0 ("spec v2" of pdhg_tile_kernel<double, 1, 1, 32, 32> with
 // rho = 0; explicit fma, -ffp-contract=off):
@@ -24,6 +25,11 @@
 //     n2    = fma(z2, z2, z1*z1);  out = n2 > alpha^2;   y = out ? z * (alpha*rsqrt_nr(n2)) : z
 //      L1 (the data term w |u - f| in place of w/2 (u - f)^2; WEIGHTED's registers, tape and launch; step table with gamma = 0):
 //                 v = fma(-tau_k, div, x);  d = v - f;  m = |d| - tau_k*w;  x_new = m > 0 ? f + copysign(m, d) : f
+//      KL (the data term w (u - f log u), u >= 0, for Poisson noise; WEIGHTED's registers, tape and launch; gamma = 0):
+//                 v = fma(-tau_k, div, x);  t = tau_k*w;  c = v - t;  g = t*f;  s = sqrt(c*c + 4*g)      (IEEE sqrt, division)
+//                 x_new = c >= 0 ? 0.5*(c + s) : (2*g) / (s - c)
+//                 (both are the positive root of u^2 - c u - t f = 0; the second has no cancellation when t is large.  c < 0
+//                 gives s - c > 0: no guard.  w = 0 or f = 0: x_new = max(c, 0).  Out-of-image lanes: c = s = 0, x_new = 0)
 // The two primal steps are two forms, not one with w = 1: each is pinned bit for bit.  !WEIGHTED gives bpltv_denoise's u
 // (tests/test_gpu_unrolled.py), WEIGHTED bpltv_weighted_denoise's (tests/test_gpu_weighted_unrolled.py), whatever TAPE and
 // TANGENT; and with w == 1.0 each weighted operation returns the bits of the one it replaces (tests/test_gpu_weighted.py).
@@ -50,6 +56,12 @@
 //                 gy = gz - tau_k * G h;  gx = h - omega_k*gxb                        (decided on the tape alone)
 //                 (w == 0: the threshold is the identity, x_new = v whatever d is, and so is its derivative -- without it a
 //                 pixel without data whose d is zero up to rounding would be read as held at f or not by that rounding)
+//      KL:        t = tau_k*w;  D = fma(t, f, x_{k+1}*x_{k+1});  q = D > 0 ? x_{k+1} / D : 0;  e = q*gxn;  h = x_{k+1}*e;
+//                 gf += t*e;  gw += tau_k*((f - x_{k+1})*e);  gy = gz - tau_k * G h;  gx = h - omega_k*gxb
+//                 (e = gxn / s, since s = x+ + t f / x+: dx+/dv = x+/s, dx+/df = t/s, dx+/dw = tau (f - x+)/s, from the tape, f
+//                 and w alone.  Exact wherever x+ > 0.  Convention: where x+ = 0 exactly -- possible only where w f = 0 and the
+//                 iterate was clamped -- the tail passes nothing (q = 0); the one-sided terms tau w/|c| and tau f/|c| of grad_f
+//                 and grad_w there, which the tape cannot give, are dropped)
 // and dL/df = gf + gx after the last step (x_0 = f, y_0 = 0).  The two tails agree to rounding only at w = 1
 // (tests/test_gpu_weighted_unrolled.py).  The weighted sweep needs no w > 0: a mask (w in {0, 1}) gets gradients in f, alpha, w.
 #pragma once
@@ -96,10 +108,11 @@ struct TvTileArgs {
 // TAPE: two or three stores per iteration for the core pixels (valid in every iteration of a launch).
 // TANGENT: a second set of LDS planes (same layout, same zero guards) for the tangent duals and dxb, written in front of the
 // same two barriers as the primal ones.  Out-of-image lanes hold zero in every value (w = 0 there: r = 1) and keep it.
-template <bool WEIGHTED, bool TAPE, bool TANGENT, bool L1 = false>
+template <bool WEIGHTED, bool TAPE, bool TANGENT, bool L1 = false, bool KL = false>
 __global__ __launch_bounds__(TV_R * TV_R) void tv_tile_kernel(TvTileArgs A) {
     static_assert(!(TAPE && TANGENT), "the tangent sweep records nothing");
     static_assert(!L1 || (WEIGHTED && !TANGENT), "the L1 data term takes the weighted model's w and tape, and has no tangent sweep");
+    static_assert(!KL || (WEIGHTED && !TANGENT && !L1), "the KL data term takes the weighted model's w and tape, has no tangent sweep, and is not L1");
     constexpr int RI = TV_R, RJ = TV_R, S1 = RI + 1;
     constexpr int PLANES = RJ * S1 + (RJ + 1) * RI + RJ * RI + RI + 1;   // doubles of one set of planes (pdhg_lds_bytes)
     static_assert(PLANES * sizeof(double) == tv_lds_bytes(), "the plane layout is pdhg_lds_bytes'");
@@ -229,6 +242,13 @@ __global__ __launch_bounds__(TV_R * TV_R) void tv_tile_kernel(TvTileArgs A) {
             const double d = v - f;
             const double m = __builtin_fabs(d) - tau * w;
             xn = (m > 0.0) ? f + __builtin_copysign(m, d) : f;
+        } else if constexpr (KL) {   // the positive root of u^2 - c u - tau w f = 0, in the form without cancellation; no r
+            const double v = __builtin_fma(-tau, div, xo);
+            const double t = tau * w;
+            const double c = v - t;
+            const double g = t * f;
+            const double s = __builtin_sqrt(c * c + 4.0 * g);
+            xn = (c >= 0.0) ? 0.5 * (c + s) : (2.0 * g) / (s - c);
         } else {
             double t;
             if constexpr (WEIGHTED) {
@@ -329,7 +349,7 @@ struct TvTileRevArgs {
     double* ga;             // in place, owning core only: per-pixel parameter gradient
     double* gw;             // WEIGHTED: in place, owning core only: per-pixel, per-image weight gradient; nullptr: not wanted
     const double* tape;     // [maxiter][2 or 3][O][M*N]
-    const double* f;        // WEIGHTED: the dataset; read only when gw is wanted (L1: always)
+    const double* f;        // WEIGHTED: the dataset; read only when gw is wanted (L1, KL: always)
     const double* w;        // WEIGHTED
     const double* alpha;
     const double* tab;
@@ -351,9 +371,10 @@ struct TvTileRevArgs {
 // guard row (G^T: neighbours i-1, j-1); gxn (WEIGHTED: h = r o gxn) through the padded plane (G: neighbours i+1, j+1) -- the
 // layouts of sy1, sy2, sxb.  Out-of-image lanes stay zero (w = 0 there: r = 1): the duals of the last image row / column
 // enter the planes as 0, as G^T treats them.  w and f are loaded once per launch.
-template <bool WEIGHTED, bool L1 = false>
+template <bool WEIGHTED, bool L1 = false, bool KL = false>
 __global__ __launch_bounds__(TV_R * TV_R) void tv_reverse_tile_kernel(TvTileRevArgs A) {
     static_assert(!L1 || WEIGHTED, "the L1 data term takes the weighted model's w and tape");
+    static_assert(!KL || (WEIGHTED && !L1), "the KL data term takes the weighted model's w and tape, and is not L1");
     constexpr int RI = TV_R, RJ = TV_R, S1 = RI + 1;
     constexpr int NC = WEIGHTED ? 3 : 2;             // tape components
     extern __shared__ __attribute__((aligned(16))) unsigned char tv_smem[];
@@ -374,7 +395,8 @@ __global__ __launch_bounds__(TV_R * TV_R) void tv_reverse_tile_kernel(TvTileRevA
     const int amode = (A.am == 1 && A.an == 1) ? 0 : ((A.am == M && A.an == N) ? 2 : 1);
     const bool first = A.first != 0;
     const bool want_w = WEIGHTED && A.gw != nullptr;   // (uniform)
-    const bool want_x = L1 || want_w;                  // L1: the taped iterate and f decide the branch, whatever is wanted
+    const bool want_x = L1 || KL || want_w;            // L1: the taped iterate and f decide the branch, whatever is wanted;
+                                                       // KL: they are the derivative's denominator
     const int nit = A.nit;
     const int klo = A.khi - nit + 1;
 
@@ -470,6 +492,22 @@ __global__ __launch_bounds__(TV_R * TV_R) void tv_reverse_tile_kernel(TvTileRevA
                 const double d2 = sxn[n2] - h;
                 gf += act ? 0.0 : gxn;
                 if (want_w) gw += -tau * ((xk > f) ? h : ((xk < f) ? -h : 0.0));   // (x+ == f with w == 0: d = 0, no side)
+                gy1 = gz1 - tau * d1;
+                gy2 = gz2 - tau * d2;
+                gx = h - omega * gxb;
+            } else if constexpr (KL) {
+                const double xk = in ? xp[s] : 0.0;   // out-of-image lanes stay zero (f is the clamped pixel's there; D > 0 then)
+                const double t = tau * w;
+                const double D = __builtin_fma(t, f, xk * xk);
+                const double q = (D > 0.0) ? xk / D : 0.0;   // x+ = 0: the tail passes nothing (the convention)
+                const double e = q * gxn;
+                const double h = xk * e;
+                sxn[l] = h;
+                __syncthreads();
+                const double d1 = sxn[n1] - h;
+                const double d2 = sxn[n2] - h;
+                gf += t * e;
+                if (want_w) gw += tau * ((f - xk) * e);
                 gy1 = gz1 - tau * d1;
                 gy2 = gz2 - tau * d2;
                 gx = h - omega * gxb;

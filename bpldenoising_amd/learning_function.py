@@ -797,6 +797,72 @@ class TVSolver:
                                                            C.c_void_p(gu_ptr), C.c_void_p(grad_f_ptr or None),
                                                            C.c_void_p(grad_alpha_ptr or None), C.c_void_p(grad_w_ptr or None)))
 
+    # -- TV-KL: the data term w (u - f log u), for Poisson noise (bpltv_kl_*) ------------------------------------------
+    # f finite and >= 0 (zero counts allowed); w >= 0, zeros allowed: (N, M) or (O, N, M).  The tape has the weighted tape's size.
+    def kl_denoise(self, x, w, fetch=True, **kw):
+        """TV-KL denoising of the resident f (bpltv_kl_denoise): min sum w (u - f log u) + sum alpha |grad u| over u >= 0,
+        maxiter iterations of the weighted recurrence with the closed-form prox of the Kullback-Leibler divergence as the primal
+        step.  The model for photon counts.  No tape; u is bitwise kl_unrolled_denoise's."""
+        a, am, an, _ = _alpha_arg(x)
+        wa, wo = self._weight(w)
+        p = self.params(**kw)
+        u = np.empty((self.O, self.N, self.M)) if fetch else None
+        self._check(self._lib.bpltv_kl_denoise(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p), _ptr(u) if fetch else None))
+        return u
+
+    def kl_denoise_device(self, w_ptr, wo, alpha_ptr, am=1, an=1, **kw):
+        """bpltv_kl_denoise_device: w (wo planes) and the parameter resident in HBM, the result left there."""
+        p = self.params(**kw)
+        self._check(self._lib.bpltv_kl_denoise_device(self._h, C.c_void_p(w_ptr), int(wo), C.c_void_p(alpha_ptr), int(am),
+                                                      int(an), C.byref(p)))
+
+    def kl_unrolled_denoise(self, x, w, fetch=True, **kw):
+        """kl_denoise(x, w) -- the same u bit for bit -- that also records the tape of the iterations in the handle, for
+        kl_unrolled_vjp with the same x, w and params (bpltv_kl_unrolled_denoise)."""
+        a, am, an, _ = _alpha_arg(x)
+        wa, wo = self._weight(w)
+        p = self._taped_params(kw)
+        u = np.empty((self.O, self.N, self.M)) if fetch else None
+        self._check(self._lib.bpltv_kl_unrolled_denoise(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p),
+                                                        _ptr(u) if fetch else None))
+        return u
+
+    def kl_unrolled_denoise_device(self, w_ptr, wo, alpha_ptr, am=1, an=1, tape_ptr=None, **kw):
+        """bpltv_kl_unrolled_denoise_device: w (wo planes) and the parameter resident in HBM, the result left there;
+        tape_ptr: a caller-owned HBM buffer of weighted_unrolled_tape_doubles(**kw) doubles, or None / 0 for the handle's
+        own KL tape."""
+        p = self._taped_params(kw)
+        self._check(self._lib.bpltv_kl_unrolled_denoise_device(self._h, C.c_void_p(w_ptr), int(wo), C.c_void_p(alpha_ptr),
+                                                               int(am), int(an), C.byref(p), C.c_void_p(tape_ptr or None)))
+
+    def kl_unrolled_vjp(self, x, w, gu, want_f=True, want_alpha=True, want_w=True, **kw):
+        """Vector-Jacobian product of the maxiter-step map u = kl_unrolled_denoise(x, w) for the cotangent gu, by a reverse
+        sweep over the handle's KL tape (bpltv_kl_unrolled_vjp): (grad_f, grad_x, grad_w), as weighted_unrolled_vjp."""
+        if not (want_f or want_alpha or want_w):
+            raise ValueError("kl_unrolled_vjp: want_f, want_alpha and want_w are all False")
+        a, am, an, scalar = _alpha_arg(x)
+        wa, wo = self._weight(w)
+        p = self._taped_params(kw)
+        gu = self._batch(gu, "gu")
+        gf = np.empty((self.O, self.N, self.M)) if want_f else None
+        ga = np.empty(am * an) if want_alpha else None
+        gw = np.empty(wa.shape) if want_w else None
+        self._check(self._lib.bpltv_kl_unrolled_vjp(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p), _ptr(gu),
+                                                    _ptr(gf) if want_f else None, _ptr(ga) if want_alpha else None,
+                                                    _ptr(gw) if want_w else None))
+        if ga is not None:
+            ga = float(ga[0]) if scalar else ga.reshape(an, am)
+        return gf, ga, gw
+
+    def kl_unrolled_vjp_device(self, tape_ptr, w_ptr, wo, alpha_ptr, am, an, gu_ptr, grad_f_ptr, grad_alpha_ptr, grad_w_ptr, **kw):
+        """bpltv_kl_unrolled_vjp_device: the tape (None / 0: the handle's own), w, the parameter, gu and the outputs resident
+        in HBM (raw device pointers); any output pointer may be 0 / None, not all three."""
+        p = self._taped_params(kw)
+        self._check(self._lib.bpltv_kl_unrolled_vjp_device(self._h, C.c_void_p(tape_ptr or None), C.c_void_p(w_ptr), int(wo),
+                                                           C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p),
+                                                           C.c_void_p(gu_ptr), C.c_void_p(grad_f_ptr or None),
+                                                           C.c_void_p(grad_alpha_ptr or None), C.c_void_p(grad_w_ptr or None)))
+
     # -- forward mode (bpltv_jvp / bpltv_gauss_newton) -------------------------------------------------------
     def _tangents(self, what, df, dalpha, ashape):
         """(df, dalpha, K, batched): the tangents as contiguous (K, ...) stacks, either None; batched = a leading K was

@@ -114,6 +114,13 @@ bpltv_lone_unrolled_vjp_device call over a tape of 3 * maxiter * B*H*W doubles a
 fidelity map can be trained against impulse noise.  TVL1DenoiseUnrolled(alpha, w, maxiter=50, learn_w=False) is the module: w
 is a buffer, or a Parameter with learn_w=True.  No jvp: forward_mode=True raises a ValueError.
 
+    u = tv_kl_denoise_unrolled(f, alpha, w, maxiter=50)          # TV-KL, for Poisson noise (bpltv_kl_unrolled_*)
+
+f, alpha and w as for tv_l1_denoise_unrolled, but the data term is the Kullback-Leibler divergence sum w (u - f log u) over u >= 0:
+the model for photon counts, whose noise grows with the signal.  f must be finite and >= 0 (zero counts are allowed).  backward is
+one bpltv_kl_unrolled_vjp_device call over a tape of 3 * maxiter * B*H*W doubles and returns f.grad, alpha.grad and w.grad.
+TVKLDenoiseUnrolled(alpha, w, maxiter=50, learn_w=False) is the module.  No jvp: forward_mode=True raises a ValueError.
+
 Streams: the library runs its kernels on its own HIP streams and blocks until they are done.  Every call below first
 synchronises the tensors' current torch stream, so that the library reads inputs torch has finished writing; its
 outputs are complete when the call returns.
@@ -292,7 +299,7 @@ def _no_checkpoint(solver_kw):
     return {k: v for k, v in solver_kw.items() if k != "checkpoint_every"}
 
 
-# ---- the one implementation behind the eighteen Functions below ----------------------------------------------------------------
+# ---- the one implementation behind the nineteen Functions below ----------------------------------------------------------------
 # A model is a row of this record; _forward, _backward and _jvp are every Function's three methods, written once over it.
 # The TVSolver entries are named, not held: they are looked up on the handle of the call.  Their argument lists mirror the C
 # ABI and are not regular -- the channel count first, `w, wo` in front of alpha, the tape first in a vjp, a trailing u_ptr in
@@ -309,6 +316,7 @@ class _Model(typing.NamedTuple):
     w_zeros: bool = False    # ... which may hold zeros, so the layer itself refuses what is negative or not finite
     channels: bool = False   # f is (B, C, H, W): the handle holds B*C planes and every entry takes C first
     reads_f: bool = False    # the reverse sweep reads the dataset whatever is asked of it (TV-L1: f decides the branch)
+    f_nonneg: bool = False   # the data term needs f >= 0 (TV-KL): the layer itself refuses what is negative or not finite
 
     @property
     def reg(self):           # the implicit TV and sum-of-regularisers adjoints take the reference's linearisation switch
@@ -341,6 +349,8 @@ _COLOR_WEIGHTED_UNROLLED = _Model(functools.partial(_check_args_color, name="tv_
                                   channels=True)
 _L1_UNROLLED = _Model(_check_args, "l1_unrolled_denoise_device", "l1_unrolled_vjp_device", None, "weighted_unrolled_tape_doubles",
                       w="tv_l1_denoise_unrolled", w_zeros=True, reads_f=True)
+_KL_UNROLLED = _Model(_check_args, "kl_unrolled_denoise_device", "kl_unrolled_vjp_device", None, "weighted_unrolled_tape_doubles",
+                      w="tv_kl_denoise_unrolled", w_zeros=True, reads_f=True, f_nonneg=True)
 
 
 def _forward(m, ctx, f, alpha, solver_kw, reg=None, w=None, jvp=False):
@@ -352,6 +362,8 @@ def _forward(m, ctx, f, alpha, solver_kw, reg=None, w=None, jvp=False):
         wo = _check_weight(f, w, m.w)   # (in front of the device check: a CPU triple with a wrong w reports the w)
         if m.w_zeros and w.numel() and not bool((w.detach() >= 0).all()):   # (a NaN fails the comparison too)
             raise ValueError("%s: w must be finite and >= 0 everywhere (zeros are allowed)" % m.w)
+        if m.f_nonneg and not bool((f.detach() >= 0).all() and torch.isfinite(f.detach()).all()):
+            raise ValueError("%s: f must be finite and >= 0 everywhere (zero counts are allowed)" % m.w)
     *planes, N, M, am, an = m.check(f, alpha)   # planes: (O,), with channels (B, C)
     index = f.device.index if f.device.index is not None else torch.cuda.current_device()
     s = _solver(index, M, N, math.prod(planes))
@@ -829,4 +841,48 @@ class TVL1DenoiseUnrolled(torch.nn.Module):
 
     def forward(self, f):
         return tv_l1_denoise_unrolled(f, self.alpha, self.w, maxiter=self.maxiter, checkpoint_every=self.checkpoint_every,
+                                      **self.solver_kw)
+
+
+# ---- TV-KL (TVSolver.kl_unrolled_*): the data term w (u - f log u), for Poisson noise (photon counts) ----
+class TVKLDenoiseUnrolledFunction(torch.autograd.Function):
+    """autograd.Function of tv_kl_denoise_unrolled (below); apply(f, alpha, w, solver_kw).  No jvp."""
+    forward = staticmethod(lambda ctx, f, alpha, w, solver_kw: _forward(_KL_UNROLLED, ctx, f, alpha, solver_kw, w=w))
+    backward = staticmethod(once_differentiable(lambda ctx, gu: _backward(_KL_UNROLLED, ctx, gu)))
+
+
+def tv_kl_denoise_unrolled(f, alpha, w, maxiter=50, checkpoint_every=None, forward_mode=False, **solver_kw):
+    """TV-KL denoising by exactly maxiter PDHG iterations: min_{u >= 0} sum_pixels w (u - f log u) + sum_pixels alpha |grad u|
+    (TVSolver.kl_unrolled_denoise_device), the model for Poisson noise.  The primal step is the closed-form prox of the
+    Kullback-Leibler divergence.  Differentiable in f, alpha and w through the iterations (TVSolver.kl_unrolled_vjp_device); the
+    derivative is exact wherever the iterates are > 0, which they are wherever w f > 0; where an iterate is exactly 0 (only where
+    w f = 0) the data step passes no gradient.
+    f must be finite and >= 0 (zero counts are allowed): a ValueError otherwise.  alpha, w, checkpoint_every and solver_kw as
+    tv_l1_denoise_unrolled's: w float64 on f's device, >= 0 with zeros allowed, (H, W) -- w.grad then summed over the batch -- or
+    f's shape (B, H, W).  accel changes nothing: the steps are constant.
+    forward_mode=True raises: the tangent sweep of this model is not built."""
+    _no_forward_mode("tv_kl_denoise_unrolled", forward_mode, "the TV-KL iterations",
+                     "tv_denoise_weighted_unrolled(..., forward_mode=True), with the quadratic data term,")
+    return TVKLDenoiseUnrolledFunction.apply(f, alpha, w, _with_checkpoint(dict(solver_kw, maxiter=int(maxiter)), checkpoint_every))
+
+
+class TVKLDenoiseUnrolled(torch.nn.Module):
+    """tv_kl_denoise_unrolled behind a learnable scalar, patch parameter or pixel map alpha and a fidelity map w: a buffer, or
+    with learn_w=True a Parameter too (keep it >= 0, by clamping after the optimiser's step).  Move it to the device of its
+    inputs with .to(device)."""
+
+    def __init__(self, alpha, w, maxiter=50, learn_w=False, checkpoint_every=None, **solver_kw):
+        super().__init__()
+        self.alpha = torch.nn.Parameter(torch.as_tensor(alpha, dtype=torch.float64).clone())
+        wt = torch.as_tensor(w, dtype=torch.float64).clone()
+        if learn_w:
+            self.w = torch.nn.Parameter(wt)
+        else:
+            self.register_buffer("w", wt)
+        self.maxiter = int(maxiter)
+        self.checkpoint_every = checkpoint_every
+        self.solver_kw = dict(solver_kw)
+
+    def forward(self, f):
+        return tv_kl_denoise_unrolled(f, self.alpha, self.w, maxiter=self.maxiter, checkpoint_every=self.checkpoint_every,
                                       **self.solver_kw)

@@ -144,7 +144,8 @@ typedef struct bpltv_stats {
                                   13 tangent sweep through the channel-coupled iterations (bpltv_color_unrolled_jvp),
                                   14 reverse sweep over the taped weighted channel-coupled iterations
                                   (bpltv_color_weighted_unrolled_vjp),
-                                  15 reverse sweep over the taped TV-L1 iterations (bpltv_lone_unrolled_vjp) */
+                                  15 reverse sweep over the taped TV-L1 iterations (bpltv_lone_unrolled_vjp),
+                                  16 reverse sweep over the taped TV-KL iterations (bpltv_kl_unrolled_vjp) */
     int reg_gradient_used;     /* 1 if the last evaluate took the gradient_reg branch             */
     int ngpus;                 /* distinct devices behind this handle (1 for bpltv_create)        */
     int shards;                /* image shards (= worker threads) behind this handle              */
@@ -784,6 +785,71 @@ int bpltv_lone_unrolled_denoise_device(bpltv_t *h, const double *d_w, int wo, co
 int bpltv_lone_unrolled_vjp(bpltv_t *h, const double *w, int wo, const double *alpha, int am, int an, const bpltv_params *p,
                           const double *gu, double *grad_f_out, double *grad_alpha_out, double *grad_w_out);
 int bpltv_lone_unrolled_vjp_device(bpltv_t *h, const double *d_tape, const double *d_w, int wo, const double *d_alpha, int am, int an,
+                                 const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alpha, double *d_grad_w);
+
+/* TV-KL denoising: the Kullback-Leibler divergence as the data term -- the model for Poisson noise
+ * (photon counts: microscopy, astronomy, low-dose imaging), whose variance grows with the signal, so that a quadratic term
+ * over-smooths the dark regions and under-smooths the bright ones:
+ *
+ *     min_u  sum_pixels w (u - f log u)  +  sum_pixels alpha |grad u|,      w >= 0,  f >= 0,  u >= 0
+ *
+ * Grey planes, Float64.  alpha as bpltv_denoise (scalar, patch or map); w as bpltv_weighted_denoise: wo = 1 (one plane for all O
+ * images) or wo = O, zeros legal (a pixel without data).  f is the handle's dataset and must be finite and >= 0; zero counts are
+ * legal.  The data term is strongly convex on bounded sets only, so the step table is made with gamma = 0 whatever w is:
+ * omega = 1, constant steps, and accel = 0 and 1 give the same bits.  Iteration k, from x = f, y = 0, is
+ * bpltv_weighted_unrolled_denoise's except for the primal step, the prox of the data term in closed form (explicit fma; IEEE
+ * square root and division):
+ *
+ *     v = fma(-tau_k, G^T y, x);  t = tau_k*w;  c = v - t;  g = t*f;  s = sqrt(c*c + 4*g)
+ *     x+ = (c >= 0) ? 0.5*(c + s) : (2*g) / (s - c)
+ *
+ * Both branches are the positive root of u^2 - c u - t f = 0; the second has no cancellation when t is large (w = 1e30 returns f
+ * to rounding), and c < 0 gives s - c > 0.  w = 0 or f = 0 gives x+ = max(c, 0): a pixel without data is inpainted under u >= 0.
+ *
+ * The contract is bpltv_weighted_unrolled_*'s: wo other than 1 or O, a NULL, negative or non-finite w, maxiter < 1 and a bad
+ * parameter are BPLTV_E_ARG; rho, init and order must be 0 (BPLTV_E_UNSUPPORTED); no data is BPLTV_E_NODATA; check_every and
+ * gap_tol are ignored; dtype = 32 handles compute in Float64; a multi-device handle forwards to its one shard and is
+ * BPLTV_E_UNSUPPORTED over more.  One rule more: a dataset with a negative or non-finite entry is BPLTV_E_ARG for the three
+ * solves, with a message that names f; the dataset is looked at once after each bpltv_set_data(_device) and the answer kept,
+ * and the other models take the same dataset as before.  Every rejection comes before anything of the handle changes.  The
+ * results do not depend on tile_iters, on the launch chains, on use_graph, on the host or device form, on whose tape it is, or on
+ * option "tape_checkpoint".
+ *
+ * bpltv_kl_denoise: the recurrence without a tape; u is bitwise the taped solve's.
+ * bpltv_kl_unrolled_denoise: the same and the tape of z1, z2 (before the projection) and x+, in the weighted tape's layout and
+ * size: bpltv_weighted_unrolled_tape_doubles gives the doubles of a caller-owned d_tape.  A NULL d_tape, and the host form
+ * always, use a seventh tape owned by the handle, which remembers wo.  No other model's sweep accepts it, nor this sweep another
+ * model's tape, and each survives the others' solves; no captured graph is shared with the weighted or the TV-L1 model.  Either
+ * solve becomes the handle's last one for bpltv_u_device / bpltv_copy_u_device; bpltv_duality_gap after it is
+ * BPLTV_E_UNSUPPORTED until another model solves (the gap of this data term is not implemented).
+ * stats: as bpltv_weighted_unrolled_denoise.  bytes_per_px_iter, from what the kernels load and store per pixel and iteration of
+ * a launch of one iteration: read x, y1, y2, f, w (40 bytes; + 8 for alpha with a map), write x, y1, y2 (24) -- 64 / 72 without a
+ * tape -- and write z1, z2, x+ onto the tape (24): 88 / 96.
+ *
+ * bpltv_kl_unrolled_vjp: reverse mode through the iterations.  The step table depends on neither w nor alpha, and the primal
+ * step has no kink where w f > 0, so the derivative is exact wherever x+ > 0.  The tail of reverse step k needs only the tape, f,
+ * w and tau_k:
+ *
+ *     t = tau_k*w;  D = fma(t, f, x+*x+);  q = (D > 0) ? x+ / D : 0;  e = q*gxn          (e = gxn / s, since s = x+ + t f / x+)
+ *     h = x+*e;  gf += t*e;  gw += tau_k*((f - x+)*e);  gy = gz - tau_k * G h;  gx = h - omega_k * gxb
+ *
+ * (dx+/dv = x+/s, dx+/df = tau w/s, dx+/dw = tau (f - x+)/s.)  Convention: where x+ = 0 exactly -- possible only where w f = 0 and
+ * the iterate was clamped at zero -- the tail passes nothing (q = 0); the one-sided terms tau w/|c| of grad_f and tau f/|c| of
+ * grad_w there, which the tape cannot give, are dropped.
+ * grad_f_out M*N*O doubles, grad_alpha_out am*an, grad_w_out w's shape (wo = 1: summed over the images in image order); any may
+ * be NULL, not all three.  The sweep always reads the resident f (and does not look at its sign).  w's planes, alpha's shape and
+ * params must be the solve's: BPLTV_E_ARG on the handle's tape otherwise; no KL tape or no dataset is BPLTV_E_NODATA.  Of the
+ * statistics only adjoint_ms and adjoint_method = 16 change. */
+int bpltv_kl_denoise(bpltv_t *h, const double *w, int wo, const double *alpha, int am, int an, const bpltv_params *p,
+                     double *u_out);
+int bpltv_kl_denoise_device(bpltv_t *h, const double *d_w, int wo, const double *d_alpha, int am, int an, const bpltv_params *p);
+int bpltv_kl_unrolled_denoise(bpltv_t *h, const double *w, int wo, const double *alpha, int am, int an, const bpltv_params *p,
+                              double *u_out);
+int bpltv_kl_unrolled_denoise_device(bpltv_t *h, const double *d_w, int wo, const double *d_alpha, int am, int an,
+                                     const bpltv_params *p, double *d_tape);
+int bpltv_kl_unrolled_vjp(bpltv_t *h, const double *w, int wo, const double *alpha, int am, int an, const bpltv_params *p,
+                          const double *gu, double *grad_f_out, double *grad_alpha_out, double *grad_w_out);
+int bpltv_kl_unrolled_vjp_device(bpltv_t *h, const double *d_tape, const double *d_w, int wo, const double *d_alpha, int am, int an,
                                  const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alpha, double *d_grad_w);
 
 /* Forward mode through the channel-coupled iterations: bpltv_unrolled_jvp and

@@ -6,7 +6,7 @@
 # Same exports as src/TVLearningFunctionVec.jl:6
 export tv_op_learning_function, denoise, sumregs_learning_function, tv_vjp, sumregs_vjp, tv_jvp, tv_gauss_newton,
        sumregs_jvp, sumregs_gauss_newton, weighted_denoise, weighted_vjp, unrolled_denoise_each, unrolled_vjp_each,
-       unrolled_jvp_each, weighted_unrolled_jvp, color_denoise, l1_denoise
+       unrolled_jvp_each, weighted_unrolled_jvp, color_denoise, l1_denoise, kl_denoise
 
 const libbpltv = "libbpltv"            # on LD_LIBRARY_PATH, or an absolute path
 
@@ -225,6 +225,19 @@ function l1_denoise(data::Array{Float64,3}, x, w::Union{Matrix{Float64},Array{Fl
     u = similar(data)
     p = Ref(default_params(; kwargs...))
     GC.@preserve w a u bpltv_check(h, ccall((:bpltv_lone_denoise, libbpltv), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Cint, Ref{BpltvParams}, Ptr{Cdouble}), h.ptr, w, wo, a, am, an, p, u))
+    return u
+end
+
+# TV-KL (include/bpltv.h, bpltv_kl_denoise): min_u Σ w (u - f log u) + Σ α |∇u| over u ≥ 0, the model for Poisson noise (photon
+# counts).  data must be finite and ≥ 0, zero counts allowed; w as in weighted_denoise; maxiter iterations.
+function kl_denoise(data::Array{Float64,3}, x, w::Union{Matrix{Float64},Array{Float64,3}}; kwargs...)
+    h = handle_for(data, data)
+    a, am, an = alpha_arg(x)
+    wo = ndims(w) == 2 ? 1 : size(w, 3)
+    u = similar(data)
+    p = Ref(default_params(; kwargs...))
+    GC.@preserve w a u bpltv_check(h, ccall((:bpltv_kl_denoise, libbpltv), Cint,
         (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Cint, Ref{BpltvParams}, Ptr{Cdouble}), h.ptr, w, wo, a, am, an, p, u))
     return u
 end
