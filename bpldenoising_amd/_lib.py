@@ -58,7 +58,7 @@ class BpltvStats(C.Structure):
                                7: "unrolled", 8: "unrolled-jvp", 9: "weighted-unrolled", 10: "sumregs-unrolled",
                                11: "weighted-unrolled-jvp", 12: "color-unrolled",
                                13: "color-unrolled-jvp", 14: "color-weighted-unrolled",
-                               15: "l1-unrolled", 16: "kl-unrolled"}.get(self.adjoint_method, "")
+                               15: "l1-unrolled", 16: "kl-unrolled", 17: "l1-unrolled-jvp", 18: "kl-unrolled-jvp"}.get(self.adjoint_method, "")
         d["hb_sync"] = {0: "", 1: "event", 2: "value"}.get(self.hb_sync, "")
         d["collective"] = {0: "none", 1: "ncclAllReduce", 2: "ncclAllGather+ordered sum", 3: "host sum"}.get(self.collective, "")
         return d
@@ -169,6 +169,14 @@ SYMBOLS = {
     "bpltv_weighted_unrolled_jvp_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP, C.c_int,
                                                      C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "bpltv_weighted_unrolled_gauss_newton": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
+    "bpltv_lone_unrolled_jvp": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "bpltv_lone_unrolled_jvp_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpltv_lone_unrolled_gauss_newton": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
+    "bpltv_kl_unrolled_jvp": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, C.c_int, _dp, _dp, _dp, _dp, _dp]),
+    "bpltv_kl_unrolled_jvp_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP, C.c_int,
+                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "bpltv_kl_unrolled_gauss_newton": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
     "bpltv_unrolled_denoise_each": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp]),
     "bpltv_unrolled_denoise_each_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, _PP, C.c_void_p]),
     "bpltv_unrolled_vjp_each": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),

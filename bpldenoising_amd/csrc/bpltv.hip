@@ -213,7 +213,8 @@ struct GraphKey {
     const void* state; // state set 0 of the solve context: a sweep never replays a dataset-context graph, nor the reverse
                        // (MODEL_UN: the tape the launches write or read, with variant 0 = taped solve, 1 = reverse sweep; 2 ... 5 = tangent
                        // sweep, whose planes stand here instead; 6 = weighted taped solve, 7 / 8 = its reverse sweep without / with grad_w,
-                       // 9 ... 16 = its tangent sweep, by the tangents it reads, its planes here;
+                       // 9 ... 16 = its tangent sweep, by the tangents it reads, its planes here; 20 ... 24 / 30 ... 34 = the TV-L1 /
+                       // TV-KL solves and reverse sweeps, 41 ... 47 / 51 ... 57 = their tangent sweeps, in the weighted sweep's planes;
                        // MODEL_SRUN: the tape as well, variant 0 = taped solve, 1 = reverse sweep;
                        // MODEL_COLOR: the tape as well (nullptr: none), variant 10 * channels + 0 = taped solve, + 1 = reverse sweep,
                        // + 2 = the solve without a tape, + 4 ... 6 = its tangent sweep, by the tangents it reads, its planes here;
@@ -536,6 +537,7 @@ struct bpltv_handle {
     // ... of the weighted model: planes of its own, [2 sets x 6 | df | dalpha | w | dw] and
     // eight words for the device check of dw, allocated on first use and never moved
     double* d_wjv = nullptr;                        // 16 * M*N*O + 8 doubles
+    bool tangent_lds_set[4] = {false, false, false, false};   // TV, weighted, L1, KL: the tangent kernel's dynamic LDS is allowed
     bpltv_stats_t st;
     std::string err;
 };
@@ -3329,8 +3331,9 @@ void tv_tile_launch(bpltv_t* h, const WeightedPlan& pl, const double* tab, const
     void (*kern)(TvTileArgs) = tangent    ? (weighted ? &tv_tile_kernel<true, false, true> : &tv_tile_kernel<false, false, true>)
                                : a.tape   ? (weighted ? &tv_tile_kernel<true, true, false> : &tv_tile_kernel<false, true, false>)
                                           : (weighted ? &tv_tile_kernel<true, false, false> : &tv_tile_kernel<false, false, false>);
-    if (l1) kern = a.tape ? &tv_tile_kernel<true, true, false, true> : &tv_tile_kernel<true, false, false, true>;   // (weighted, no tangent)
-    if (kl) kern = a.tape ? &tv_tile_kernel<true, true, false, false, true> : &tv_tile_kernel<true, false, false, false, true>;
+    if (l1) kern = tangent ? &tv_tile_kernel<true, false, true, true> : (a.tape ? &tv_tile_kernel<true, true, false, true> : &tv_tile_kernel<true, false, false, true>);   // (weighted)
+    if (kl) kern = tangent ? &tv_tile_kernel<true, false, true, false, true>
+                           : (a.tape ? &tv_tile_kernel<true, true, false, false, true> : &tv_tile_kernel<true, false, false, false, true>);
     hipLaunchKernelGGL(kern, dim3(pl.nTi, pl.nTj, s.hi - s.lo), dim3(TV_R * TV_R), tangent ? tv_tangent_lds_bytes() : tv_lds_bytes(), s.st, a);
 }
 
@@ -4217,19 +4220,39 @@ int taped_vjp(bpltv_t* h, const TapedModel& m, const double* d_tape_user, const 
 // each (bpltv_unrolled_jvp_each(_device)): alpha holds O blocks and d_dalpha ndir x O blocks (direction, then image); image k
 // reads block k of both.
 // W (nullable: the TV model): the weighted model's w (wo planes, every entry >= 0) and d_dw (ndir x wo planes).  The step table
-// has gamma = min w, held fixed.
+// has gamma = min w, held fixed.  W->data (bpltv_lone_unrolled_jvp, bpltv_kl_unrolled_jvp and their Gauss-Newton calls; DESIGN.md
+// section 4.20): the TV-L1 or the TV-KL data term in place of the quadratic one -- the same workspace and launches with the
+// model's tangent instantiation, the step table of gamma = 0 (TapedModel::flat()) and graph variants of its own; TV-KL looks at
+// the dataset first (check_dataset_nonneg).
 // channels (bpltv_color_unrolled_jvp(_device), bpltv_color_unrolled_gauss_newton): the planes of a colour
 // image, 1 ... 4, dividing O; 0: the TV or weighted call.  The same driver with color_plan's plan, launch chains that count
 // colour images, color_tangent_tile_kernel and graphs of their own under MODEL_COLOR; channels = 1 runs the TV tangent kernel.
+enum JvpData { JVP_QUADRATIC = 0, JVP_L1 = 1, JVP_KL = 2 };   // the data term of a weighted sweep
 struct JvpWeight {
     const double* w;
     int wo;
     const double* dw;   // HBM in unrolled_jvp_common; the host array in unrolled_jvp_host
+    int data = JVP_QUADRATIC;
 };
+// The tangent instantiation of tv_tile_kernel of a model, with its dynamic LDS (two sets of planes: above the default limit)
+// allowed: once per instantiation and handle (the attribute is the device's), whoever allocated the workspace the sweeps share
+int tangent_kernel_ready(bpltv_t* h, bool weighted, int data) {
+    const int k = !weighted ? 0 : 1 + data;
+    if (h->tangent_lds_set[k]) return BPLTV_OK;
+    const void* fn = k == 0   ? reinterpret_cast<const void*>(&tv_tile_kernel<false, false, true>)
+                     : k == 1 ? reinterpret_cast<const void*>(&tv_tile_kernel<true, false, true>)
+                     : k == 2 ? reinterpret_cast<const void*>(&tv_tile_kernel<true, false, true, true>)
+                              : reinterpret_cast<const void*>(&tv_tile_kernel<true, false, true, false, true>);
+    HIPCHK(h, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)tv_tangent_lds_bytes()));
+    h->tangent_lds_set[k] = true;
+    return BPLTV_OK;
+}
 int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool dev, int am, int an, const bpltv_params* pp, int ndir,
                         const double* d_df, const double* d_dalpha, double* d_du, double* d_u, const double** x_res, bool each = false,
                         const JvpWeight* W = nullptr, int channels = 0) {
     const double* d_dw = W ? W->dw : nullptr;
+    const int data = W ? W->data : (int)JVP_QUADRATIC;
+    const bool flat = data != JVP_QUADRATIC;   // TapedModel::flat(): no strong convexity, gamma = 0
     if (!alpha || !d_du || (W && !W->w)) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
     if (ndir < 1) return set_err(h, BPLTV_E_ARG, "%s: ndir = %d (at least one direction)", who, ndir);
     if (!d_df && !d_dalpha && !d_dw) return set_err(h, BPLTV_E_ARG, "%s: %s tangents are NULL", who, W ? "all three" : "both");
@@ -4240,14 +4263,15 @@ int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool d
     if (int prc = unrolled_check_params(h, p0, who)) return prc;
     WeightedPlan pl;
     if (int prc = channels > 1 ? color_jvp_plan(h, p0, &pl) : unrolled_plan(h, p0, PDHG_MAX_T, &pl)) return prc;
+    if (data == JVP_KL)   // (memoised with the dataset; before anything of the handle changes)
+        if (int frc = check_dataset_nonneg(h, who)) return frc;
     const size_t tot = h->tot, nw = W ? (size_t)W->wo * h->npx : 0;
-    double*& d_ws = W ? h->d_wjv : h->d_ujv;
-    if (!d_ws) {
+    double*& d_ws = W ? h->d_wjv : h->d_ujv;   // (the three weighted models share d_wjv)
+    if (!d_ws)
         if (int arc = alloc_all(h, {{(void**)&d_ws, ((W ? 16 : 14) * tot + (W ? 8 : 0)) * sizeof(double)}}, W ? "weighted tangent sweep" : "tangent sweep"))
             return arc;
-        HIPCHK(h, hipFuncSetAttribute(W ? reinterpret_cast<const void*>(&tv_tile_kernel<true, false, true>) : reinterpret_cast<const void*>(&tv_tile_kernel<false, false, true>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)tv_tangent_lds_bytes()));
-    }
+    if (channels <= 1)
+        if (int lrc = tangent_kernel_ready(h, W != nullptr, data)) return lrc;
     const size_t P = (size_t)am * an * (each ? h->O : 1);   // (stage_param checks the shape before it reads anything)
     if (d_dw) {   // the third tangent: a read-back of its own (stage_param's takes two), into the workspace's check words
         int failed = -1;
@@ -4262,7 +4286,7 @@ int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool d
                              {{d_df, (size_t)ndir * tot, "tangent df"}, {d_dalpha, (size_t)ndir * P, "tangent dalpha"}}, &p, &g, false))
         return rc;
     double* d_tab = nullptr;
-    if (int rc = get_table(h, p, &d_tab, 8.0, 0, W ? g.w_min : 1.0)) return rc;
+    if (int rc = get_table(h, p, &d_tab, 8.0, 0, flat ? 0.0 : (W ? g.w_min : 1.0))) return rc;
     const int T = pl.T, K = p.maxiter;
     double* S[2][6];
     for (int s = 0; s < 2; ++s)
@@ -4276,9 +4300,10 @@ int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool d
     taped_chains(h, p, pl, &j, channels ? channels : 1);
     j.bytes_per_px_iter = 0.0;   // (the driver's solve statistics are not this call's: `kept` goes back below)
     // variant 2 ... 5: a tangent sweep, by which tangents it reads (0 = taped solve, 1 = reverse sweep); 9 ... 16: a weighted one;
+    // 41 ... 47: a TV-L1 one; 51 ... 57: a TV-KL one (the three share d_wjv, and with min w = 0 the step table as well);
     // MODEL_COLOR: 10 * channels + 3 + tangents (+ 0 ... 2 are the model's solves and its reverse sweep)
     const int tangents = (d_df ? 1 : 0) + (d_dalpha ? 2 : 0) + (d_dw ? 4 : 0);
-    j.key = GraphKey{K, T, (channels > 1 ? 10 * channels + 3 : (W ? 9 : 2)) + tangents, am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_ws,
+    j.key = GraphKey{K, T, (channels > 1 ? 10 * channels + 3 : (data == JVP_L1 ? 40 : data == JVP_KL ? 50 : (W ? 9 : 2))) + tangents, am, an, j.chains, 0.0, 0.0, 0.0, 0, 0, 0, (const void*)d_ws,
                      (const void*)d_tab, 0, (const void*)g.alpha, g.astride, W ? W->wo : 0};
     j.enqueue = launch_loop(T, [&](const LaunchStep& s) {
         TvTileArgs a{};
@@ -4287,7 +4312,7 @@ int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool d
         a.alpha = g.alpha; a.am = am; a.an = an; a.istride = g.astride;
         a.df = d_df ? d_dfc : nullptr; a.dw = d_dw ? d_dwc : nullptr; a.dalpha = d_dalpha ? d_dac : nullptr;
         if (channels > 1) color_tangent_launch(h, pl, d_tab, s, channels, a);
-        else tv_tile_launch(h, pl, d_tab, s, W != nullptr, true, a);
+        else tv_tile_launch(h, pl, d_tab, s, W != nullptr, true, a, data == JVP_L1, data == JVP_KL);
     });
     int rc = hipEventRecord(h->ev[2], h->stream) == hipSuccess ? (int)BPLTV_OK : set_err(h, BPLTV_E_HIP, "%s: hipEventRecord failed", who);
     int buf = 0;
@@ -4305,7 +4330,7 @@ int unrolled_jvp_common(bpltv_t* h, const char* who, const double* alpha, bool d
     h->st = kept;
     if (rc) return rc;
     if (d_u) HIPCHK(h, hipMemcpyAsync(d_u, S[buf][0], tot * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
-    if (int src = sweep_stats(h, channels ? 13 : (W ? 11 : 8))) return src;
+    if (int src = sweep_stats(h, channels ? 13 : (data == JVP_L1 ? 17 : data == JVP_KL ? 18 : (W ? 11 : 8)))) return src;
     if (x_res) *x_res = S[buf][0];
     return BPLTV_OK;
 }
@@ -5032,7 +5057,7 @@ static int unrolled_jvp_host(bpltv_t* h, const char* who, const double* alpha, i
     if (dalpha) HIPCHK(h, hipMemcpyAsync(d_da, dalpha, na * sizeof(double), hipMemcpyHostToDevice, h->stream));
     if (dw) HIPCHK(h, hipMemcpyAsync(d_dw, dw, nd * sizeof(double), hipMemcpyHostToDevice, h->stream));
     JvpWeight Wd{};
-    if (W) Wd = JvpWeight{W->w, W->wo, d_dw};
+    if (W) Wd = JvpWeight{W->w, W->wo, d_dw, W->data};
     rc = unrolled_jvp_common(h, who, alpha, false, am, an, pp, ndir, d_df, d_da, d_du, d_u, nullptr, each, W ? &Wd : nullptr, channels);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(du_out, d_du, nt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
@@ -5041,16 +5066,21 @@ static int unrolled_jvp_host(bpltv_t* h, const char* who, const double* alpha, i
     return BPLTV_OK;
 }
 
+// the taped model a weighted tangent sweep belongs to (its name on a multi-device handle)
+static const TapedModel& jvp_weighted_model(int data) { return data == JVP_L1 ? kTapedL1 : (data == JVP_KL ? kTapedKL : kTapedWeighted); }
+
 static int unrolled_jvp_entry(bpltv_t* h, const char* what, bool dev, const double* alpha, int am, int an, const bpltv_params* pp, int ndir,
                               const double* df, const double* dalpha, double* du, double* u, bool each, const JvpWeight* W = nullptr,
                               int channels = 0) {
     if (!h) return BPLTV_E_ARG;
     if (h->multi)
         return weighted_multi(h, what, false, [&](bpltv_t* c) { return unrolled_jvp_entry(c, what, dev, alpha, am, an, pp, ndir, df, dalpha, du, u, each, W, channels); },
-                              channels ? kTapedColor[0].multi_name : (W ? kTapedWeighted.multi_name : kUnrolled));
+                              channels ? kTapedColor[0].multi_name : (W ? jvp_weighted_model(W->data).multi_name : kUnrolled));
     int crc = BPLTV_OK;   // (color_model leaves the division to a forwarding handle's shard: this is where it arrives)
     if (channels && !color_model(h, what, channels, &crc)) return crc;
-    const char* who = channels ? "color_unrolled_jvp" : (W ? "weighted_unrolled_jvp" : (each ? "unrolled_jvp_each" : "unrolled_jvp"));
+    const char* who = channels ? "color_unrolled_jvp"
+                      : W      ? (W->data == JVP_L1 ? "l1_unrolled_jvp" : W->data == JVP_KL ? "kl_unrolled_jvp" : "weighted_unrolled_jvp")
+                               : (each ? "unrolled_jvp_each" : "unrolled_jvp");
     if (!dev) return unrolled_jvp_host(h, who, alpha, am, an, pp, ndir, df, dalpha, du, u, each, W, channels);
     HIPCHK(h, hipSetDevice(h->device));
     return unrolled_jvp_common(h, who, alpha, true, am, an, pp, ndir, df, dalpha, du, u, nullptr, each, W, channels);
@@ -5088,13 +5118,14 @@ int bpltv_weighted_unrolled_jvp_device(bpltv_t* h, const double* d_w, int wo, co
 // w (nullable: the TV model; wo planes on the host): the weighted iterations' loss.
 // channels: 0 = the TV and weighted entry points; 1 ... 4 = the channel-coupled model's (the loss runs over all planes).
 static int unrolled_gauss_newton_entry(bpltv_t* h, const char* what, const double* w, int wo, const double* alpha, int am, int an,
-                                       const bpltv_params* pp, double* cost_out, double* grad_out, double* hess_out, int channels = 0) {
+                                       const bpltv_params* pp, double* cost_out, double* grad_out, double* hess_out, int channels = 0,
+                                       int data = JVP_QUADRATIC) {
     const char* who = what + 6;   // (without "bpltv_")
     if (!h) return BPLTV_E_ARG;
     if (h->multi)
         return weighted_multi(h, what, false, [&](bpltv_t* c) {
-            return unrolled_gauss_newton_entry(c, what, w, wo, alpha, am, an, pp, cost_out, grad_out, hess_out, channels);
-        }, channels ? kTapedColor[0].multi_name : (w ? kTapedWeighted.multi_name : kUnrolled));
+            return unrolled_gauss_newton_entry(c, what, w, wo, alpha, am, an, pp, cost_out, grad_out, hess_out, channels, data);
+        }, channels ? kTapedColor[0].multi_name : (w ? jvp_weighted_model(data).multi_name : kUnrolled));
     int crc = BPLTV_OK;   // (color_model leaves the division to a forwarding handle's shard: this is where it arrives)
     if (channels && !color_model(h, what, channels, &crc)) return crc;
     if (!alpha || !cost_out || !grad_out || !hess_out) return set_err(h, BPLTV_E_ARG, "%s: null pointer", who);
@@ -5103,7 +5134,8 @@ static int unrolled_gauss_newton_entry(bpltv_t* h, const char* what, const doubl
     const bool amap = am == h->M && an == h->N && !(h->M == 1 && h->N == 1);
     if (amap || (long)am * an > GN_MAXP)
         return set_err(h, BPLTV_E_UNSUPPORTED, "%s: a scalar or a patch parameter of at most %d entries (got %dx%d%s); use bpltv_%sunrolled_jvp for Jacobian columns",
-                       who, GN_MAXP, am, an, amap ? ", a pixel map" : "", channels ? "color_" : (w ? "weighted_" : ""));
+                       who, GN_MAXP, am, an, amap ? ", a pixel map" : "",
+                       channels ? "color_" : (data == JVP_L1 ? "lone_" : data == JVP_KL ? "kl_" : (w ? "weighted_" : "")));
     if (!h->has_data) return set_err(h, BPLTV_E_NODATA, "%s: bpltv_set_data has not been called", who);
     const int P = am * an;
     const size_t nout = (size_t)P + (size_t)P * P;
@@ -5124,7 +5156,7 @@ static int unrolled_gauss_newton_entry(bpltv_t* h, const char* what, const doubl
     HIPCHK(h, hipMemcpyAsync(d_e, eye.data(), eye.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));   // (eye is a local)
     const double* d_x = nullptr;
-    const JvpWeight W{w, wo, nullptr};
+    const JvpWeight W{w, wo, nullptr, data};
     int rc = unrolled_jvp_common(h, who, alpha, false, am, an, pp, P, nullptr, d_e, d_J, nullptr, &d_x, false, w ? &W : nullptr, channels);
     if (rc) return rc;
     h->has_per_image = false;   // compute_cost writes d_perimg and d_red
@@ -5150,6 +5182,41 @@ int bpltv_weighted_unrolled_gauss_newton(bpltv_t* h, const double* w, int wo, co
     if (!h) return BPLTV_E_ARG;
     if (!w) return set_err(h, BPLTV_E_ARG, "weighted_unrolled_gauss_newton: w is a null pointer");
     return unrolled_gauss_newton_entry(h, "bpltv_weighted_unrolled_gauss_newton", w, wo, alpha, am, an, pp, cost_out, grad_out, hess_out);
+}
+
+// Forward mode through the TV-L1 and the TV-KL iterations (tv_tile_kernel<1,0,1,L1> and <1,0,1,0,KL>):
+// the weighted sweep's driver, workspace and contract with the model's data term, step table (gamma = 0) and graphs
+int bpltv_lone_unrolled_jvp(bpltv_t* h, const double* w, int wo, const double* alpha, int am, int an, const bpltv_params* pp, int ndir,
+                            const double* df, const double* dalpha, const double* dw, double* du_out, double* u_out) {
+    const JvpWeight W{w, wo, dw, JVP_L1};
+    return unrolled_jvp_entry(h, "bpltv_lone_unrolled_jvp", false, alpha, am, an, pp, ndir, df, dalpha, du_out, u_out, false, &W);
+}
+int bpltv_lone_unrolled_jvp_device(bpltv_t* h, const double* d_w, int wo, const double* d_alpha, int am, int an, const bpltv_params* pp,
+                                   int ndir, const double* d_df, const double* d_dalpha, const double* d_dw, double* d_du, double* d_u) {
+    const JvpWeight W{d_w, wo, d_dw, JVP_L1};
+    return unrolled_jvp_entry(h, "bpltv_lone_unrolled_jvp_device", true, d_alpha, am, an, pp, ndir, d_df, d_dalpha, d_du, d_u, false, &W);
+}
+int bpltv_lone_unrolled_gauss_newton(bpltv_t* h, const double* w, int wo, const double* alpha, int am, int an, const bpltv_params* pp,
+                                     double* cost_out, double* grad_out, double* hess_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (!w) return set_err(h, BPLTV_E_ARG, "lone_unrolled_gauss_newton: w is a null pointer");
+    return unrolled_gauss_newton_entry(h, "bpltv_lone_unrolled_gauss_newton", w, wo, alpha, am, an, pp, cost_out, grad_out, hess_out, 0, JVP_L1);
+}
+int bpltv_kl_unrolled_jvp(bpltv_t* h, const double* w, int wo, const double* alpha, int am, int an, const bpltv_params* pp, int ndir,
+                          const double* df, const double* dalpha, const double* dw, double* du_out, double* u_out) {
+    const JvpWeight W{w, wo, dw, JVP_KL};
+    return unrolled_jvp_entry(h, "bpltv_kl_unrolled_jvp", false, alpha, am, an, pp, ndir, df, dalpha, du_out, u_out, false, &W);
+}
+int bpltv_kl_unrolled_jvp_device(bpltv_t* h, const double* d_w, int wo, const double* d_alpha, int am, int an, const bpltv_params* pp,
+                                 int ndir, const double* d_df, const double* d_dalpha, const double* d_dw, double* d_du, double* d_u) {
+    const JvpWeight W{d_w, wo, d_dw, JVP_KL};
+    return unrolled_jvp_entry(h, "bpltv_kl_unrolled_jvp_device", true, d_alpha, am, an, pp, ndir, d_df, d_dalpha, d_du, d_u, false, &W);
+}
+int bpltv_kl_unrolled_gauss_newton(bpltv_t* h, const double* w, int wo, const double* alpha, int am, int an, const bpltv_params* pp,
+                                   double* cost_out, double* grad_out, double* hess_out) {
+    if (!h) return BPLTV_E_ARG;
+    if (!w) return set_err(h, BPLTV_E_ARG, "kl_unrolled_gauss_newton: w is a null pointer");
+    return unrolled_gauss_newton_entry(h, "bpltv_kl_unrolled_gauss_newton", w, wo, alpha, am, an, pp, cost_out, grad_out, hess_out, 0, JVP_KL);
 }
 
 // Forward mode through the channel-coupled iterations (color_tangent_tile_kernel)

@@ -10,6 +10,7 @@
 //         <0,0,1>  bpltv_unrolled_jvp (4.7)                        <1,0,1>  bpltv_weighted_unrolled_jvp (4.11)
 //         <1,1,0,L1>  bpltv_lone_unrolled_denoise (4.18)             <1,0,0,L1>  bpltv_lone_denoise and the checkpoint pass (4.18)
 //         <1,1,0,0,KL>  bpltv_kl_unrolled_denoise (4.19)            <1,0,0,0,KL>  bpltv_kl_denoise and the checkpoint pass (4.19)
+//         <1,0,1,L1>  bpltv_lone_unrolled_jvp (4.20)                 <1,0,1,0,KL>  bpltv_kl_unrolled_jvp (4.20)
 //     tv_reverse_tile_kernel<WEIGHTED, L1, KL>
 //         <0>      bpltv_unrolled_vjp (4.6)                        <1>      bpltv_weighted_unrolled_vjp (4.8)
 //         <1,L1>   bpltv_lone_unrolled_vjp (4.18)                  <1,0,KL> bpltv_kl_unrolled_vjp (4.19)
@@ -39,6 +40,12 @@
 //     !WEIGHTED:  dt = ddiv - df
 //      WEIGHTED:  dt = (ddiv - w*df) - dw*(f - x_new)
 //     dxn  = (dx - tau_k*dt)*r;   dxb = (1 + omega_k)*dxn - omega_k*dx;   dx = dxn          (the primal's own r)
+//      L1:        dv = dx - tau_k*ddiv;  act = x_new != f || w == 0;  dxn = act ? dv - tau_k*(sign(x_new - f)*dw) : df
+//                 (the reverse tail's act and three-way sign, on x_new, f and w: a held pixel passes df and nothing else, a
+//                 pixel without data passes dv)
+//      KL:        dv = dx - tau_k*ddiv;  t = tau_k*w;  D = fma(t, f, x_new*x_new);  q = D > 0 ? x_new / D : 0;
+//                 dxn = q*(x_new*dv + t*df + tau_k*((f - x_new)*dw))       (the reverse tail's D and q: x_new = 0 passes nothing)
+//                 (both: dxb and dx as above; neither reads r)
 //     dz   = dy + sigma_k * G dxb
 //     out:  q = rsqrt_nr(n2); e = z*q; dot = e1*dz1 + e2*dz2; dy = dalpha*e + (alpha*q)*(dz - e*dot)   (the primal's decision)
 //     else: dy = dz
@@ -111,8 +118,8 @@ struct TvTileArgs {
 template <bool WEIGHTED, bool TAPE, bool TANGENT, bool L1 = false, bool KL = false>
 __global__ __launch_bounds__(TV_R * TV_R) void tv_tile_kernel(TvTileArgs A) {
     static_assert(!(TAPE && TANGENT), "the tangent sweep records nothing");
-    static_assert(!L1 || (WEIGHTED && !TANGENT), "the L1 data term takes the weighted model's w and tape, and has no tangent sweep");
-    static_assert(!KL || (WEIGHTED && !TANGENT && !L1), "the KL data term takes the weighted model's w and tape, has no tangent sweep, and is not L1");
+    static_assert(!L1 || WEIGHTED, "the L1 data term takes the weighted model's w and tape");
+    static_assert(!KL || (WEIGHTED && !L1), "the KL data term takes the weighted model's w and tape, and is not L1");
     constexpr int RI = TV_R, RJ = TV_R, S1 = RI + 1;
     constexpr int PLANES = RJ * S1 + (RJ + 1) * RI + RJ * RI + RI + 1;   // doubles of one set of planes (pdhg_lds_bytes)
     static_assert(PLANES * sizeof(double) == tv_lds_bytes(), "the plane layout is pdhg_lds_bytes'");
@@ -264,10 +271,24 @@ __global__ __launch_bounds__(TV_R * TV_R) void tv_tile_kernel(TvTileArgs A) {
         double db = 0.0;
         if constexpr (TANGENT) {
             const double ddiv = (dy1m - dy1) + (dy2m - dy2);
-            double dt;
-            if constexpr (WEIGHTED) dt = (ddiv - wdf) - dw * (f - xn);
-            else dt = ddiv - df;
-            const double dxn = (dx - tau * dt) * r;
+            double dxn;
+            if constexpr (L1) {   // the threshold's derivative, decided on x+, f and w as the reverse tail decides it from the tape
+                const double dv = dx - tau * ddiv;
+                const bool act = xn != f || w == 0.0;   // let through, or no threshold at all (w == 0: the identity)
+                const double sdw = (xn > f) ? dw : ((xn < f) ? -dw : 0.0);
+                dxn = act ? dv - tau * sdw : df;        // a held pixel moves with f and with nothing else
+            } else if constexpr (KL) {   // dx+/dv = x+/s, dx+/df = t/s, dx+/dw = tau (f - x+)/s with 1/s = x+/D: the reverse tail's q
+                const double dv = dx - tau * ddiv;
+                const double t = tau * w;
+                const double D = __builtin_fma(t, f, xn * xn);
+                const double q = (D > 0.0) ? xn / D : 0.0;   // x+ = 0: the step passes nothing (the convention)
+                dxn = q * (xn * dv + t * df + tau * ((f - xn) * dw));
+            } else {
+                double dt;
+                if constexpr (WEIGHTED) dt = (ddiv - wdf) - dw * (f - xn);
+                else dt = ddiv - df;
+                dxn = (dx - tau * dt) * r;
+            }
             db = opw * dxn - omega * dx;
             dx = dxn;
         }

@@ -1000,14 +1000,8 @@ class TVSolver:
         return float(cost.value), (float(grad[0]) if scalar else grad.reshape(an, am)), H
 
     # -- forward mode through the weighted iterations (bpltv_weighted_unrolled_jvp / _gauss_newton) -----------
-    def weighted_unrolled_jvp(self, x, w, df=None, dalpha=None, dw=None, want_u=False, **kw):
-        """Jacobian-vector product of the maxiter-step map u = weighted_unrolled_denoise(x, w) of the resident f
-        (bpltv_weighted_unrolled_jvp): a tangent sweep through the weighted iterations, no tape -- the linear map whose
-        transpose weighted_unrolled_vjp computes; w >= 0, zeros allowed (a mask).  df: (O, N, M), or (K, O, N, M) for K
-        directions; dalpha: shaped like x, or with a leading K; dw: shaped like w, or with a leading K; any may be None
-        (zero), not all three.  Returns du of shape (O, N, M), or (K, O, N, M) when a leading K was given; with want_u,
-        (du, u) with u = weighted_denoise(x, w) bit for bit.  The step table (gamma = min w) is held fixed."""
-        what = "weighted_unrolled_jvp"
+    def _weighted_jvp(self, what, fn, x, w, df, dalpha, dw, want_u, kw):
+        """weighted_unrolled_jvp and its TV-L1 / TV-KL twins: the tangents as stacks of K directions, one call of fn."""
         a, am, an, scalar = _alpha_arg(x)
         wa, wo = self._weight(w)
         if df is None and dalpha is None and dw is None:
@@ -1030,38 +1024,86 @@ class TVSolver:
         p = self.params(**kw)
         du = np.empty((K, self.O, self.N, self.M))
         u = np.empty((self.O, self.N, self.M)) if want_u else None
-        self._check(self._lib.bpltv_weighted_unrolled_jvp(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p), K,
-                                                          _ptr(df) if df is not None else None,
-                                                          _ptr(dalpha) if dalpha is not None else None,
-                                                          _ptr(dw) if dw is not None else None, _ptr(du),
-                                                          _ptr(u) if want_u else None))
+        self._check(fn(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p), K,
+                       _ptr(df) if df is not None else None,
+                       _ptr(dalpha) if dalpha is not None else None,
+                       _ptr(dw) if dw is not None else None, _ptr(du),
+                       _ptr(u) if want_u else None))
         du = du if batched else du[0]
         return (du, u) if want_u else du
+
+    def _weighted_jvp_device(self, fn, w_ptr, wo, alpha_ptr, am, an, df_ptr, dalpha_ptr, dw_ptr, du_ptr, u_ptr, ndir, kw):
+        p = self.params(**kw)
+        self._check(fn(self._h, C.c_void_p(w_ptr), int(wo), C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p), int(ndir),
+                       C.c_void_p(df_ptr or None), C.c_void_p(dalpha_ptr or None), C.c_void_p(dw_ptr or None),
+                       C.c_void_p(du_ptr), C.c_void_p(u_ptr or None)))
+
+    def _weighted_gauss_newton(self, fn, x, w, kw):
+        a, am, an, scalar = _alpha_arg(x)
+        wa, wo = self._weight(w)
+        p = self.params(**kw)
+        P = am * an
+        cost, grad, H = C.c_double(0.0), np.empty(P), np.empty((P, P))
+        self._check(fn(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p), C.byref(cost), _ptr(grad), _ptr(H)))
+        return float(cost.value), (float(grad[0]) if scalar else grad.reshape(an, am)), H
+
+    def weighted_unrolled_jvp(self, x, w, df=None, dalpha=None, dw=None, want_u=False, **kw):
+        """Jacobian-vector product of the maxiter-step map u = weighted_unrolled_denoise(x, w) of the resident f
+        (bpltv_weighted_unrolled_jvp): a tangent sweep through the weighted iterations, no tape -- the linear map whose
+        transpose weighted_unrolled_vjp computes; w >= 0, zeros allowed (a mask).  df: (O, N, M), or (K, O, N, M) for K
+        directions; dalpha: shaped like x, or with a leading K; dw: shaped like w, or with a leading K; any may be None
+        (zero), not all three.  Returns du of shape (O, N, M), or (K, O, N, M) when a leading K was given; with want_u,
+        (du, u) with u = weighted_denoise(x, w) bit for bit.  The step table (gamma = min w) is held fixed."""
+        return self._weighted_jvp("weighted_unrolled_jvp", self._lib.bpltv_weighted_unrolled_jvp, x, w, df, dalpha, dw, want_u, kw)
 
     def weighted_unrolled_jvp_device(self, w_ptr, wo, alpha_ptr, am, an, df_ptr, dalpha_ptr, dw_ptr, du_ptr, u_ptr=None,
                                      ndir=1, **kw):
         """bpltv_weighted_unrolled_jvp_device: w (wo planes), the parameter (am*an doubles), df and du (ndir*M*N*O), dalpha
         (ndir*am*an), dw (ndir*M*N*wo) and u (M*N*O) all resident in HBM (raw device pointers); any tangent pointer may be
         0 / None, not all three; u_ptr may be 0 / None."""
-        p = self.params(**kw)
-        self._check(self._lib.bpltv_weighted_unrolled_jvp_device(self._h, C.c_void_p(w_ptr), int(wo), C.c_void_p(alpha_ptr),
-                                                                 int(am), int(an), C.byref(p), int(ndir),
-                                                                 C.c_void_p(df_ptr or None), C.c_void_p(dalpha_ptr or None),
-                                                                 C.c_void_p(dw_ptr or None), C.c_void_p(du_ptr),
-                                                                 C.c_void_p(u_ptr or None)))
+        self._weighted_jvp_device(self._lib.bpltv_weighted_unrolled_jvp_device, w_ptr, wo, alpha_ptr, am, an, df_ptr, dalpha_ptr,
+                                  dw_ptr, du_ptr, u_ptr, ndir, kw)
 
     def weighted_unrolled_gauss_newton(self, x, w, **kw):
         """Gauss-Newton model of the maxiter-step loss 0.5||u_K(x) - ubar||^2 of the weighted iterations on the resident
         dataset (bpltv_weighted_unrolled_gauss_newton): (cost, grad, H) as unrolled_gauss_newton's, J by P tangent sweeps
         in the parameter.  A float or an (n, m) patch parameter with at most 16 entries; w >= 0, zeros allowed."""
-        a, am, an, scalar = _alpha_arg(x)
-        wa, wo = self._weight(w)
-        p = self.params(**kw)
-        P = am * an
-        cost, grad, H = C.c_double(0.0), np.empty(P), np.empty((P, P))
-        self._check(self._lib.bpltv_weighted_unrolled_gauss_newton(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p),
-                                                                   C.byref(cost), _ptr(grad), _ptr(H)))
-        return float(cost.value), (float(grad[0]) if scalar else grad.reshape(an, am)), H
+        return self._weighted_gauss_newton(self._lib.bpltv_weighted_unrolled_gauss_newton, x, w, kw)
+
+    # -- forward mode through the TV-L1 and the TV-KL iterations (bpltv_lone_unrolled_jvp, bpltv_kl_unrolled_jvp) -----
+    def l1_unrolled_jvp(self, x, w, df=None, dalpha=None, dw=None, want_u=False, **kw):
+        """Jacobian-vector product of the maxiter-step map u = l1_denoise(x, w) of the resident f (bpltv_lone_unrolled_jvp): a
+        tangent sweep through the TV-L1 iterations, no tape -- the linear map whose transpose l1_unrolled_vjp computes, with
+        its conventions (a pixel held at f moves with f alone).  Arguments and result as weighted_unrolled_jvp; with want_u,
+        (du, u) with u = l1_denoise(x, w) bit for bit."""
+        return self._weighted_jvp("l1_unrolled_jvp", self._lib.bpltv_lone_unrolled_jvp, x, w, df, dalpha, dw, want_u, kw)
+
+    def l1_unrolled_jvp_device(self, w_ptr, wo, alpha_ptr, am, an, df_ptr, dalpha_ptr, dw_ptr, du_ptr, u_ptr=None, ndir=1, **kw):
+        """bpltv_lone_unrolled_jvp_device: everything resident in HBM (raw device pointers), as weighted_unrolled_jvp_device."""
+        self._weighted_jvp_device(self._lib.bpltv_lone_unrolled_jvp_device, w_ptr, wo, alpha_ptr, am, an, df_ptr, dalpha_ptr,
+                                  dw_ptr, du_ptr, u_ptr, ndir, kw)
+
+    def l1_unrolled_gauss_newton(self, x, w, **kw):
+        """Gauss-Newton model of the maxiter-step loss 0.5||u_K(x) - ubar||^2 of the TV-L1 iterations on the resident dataset
+        (bpltv_lone_unrolled_gauss_newton): (cost, grad, H) as weighted_unrolled_gauss_newton's."""
+        return self._weighted_gauss_newton(self._lib.bpltv_lone_unrolled_gauss_newton, x, w, kw)
+
+    def kl_unrolled_jvp(self, x, w, df=None, dalpha=None, dw=None, want_u=False, **kw):
+        """Jacobian-vector product of the maxiter-step map u = kl_denoise(x, w) of the resident f >= 0 (bpltv_kl_unrolled_jvp): a
+        tangent sweep through the TV-KL iterations, no tape -- the linear map whose transpose kl_unrolled_vjp computes, with
+        its convention (a pixel clamped at zero passes nothing).  Arguments and result as weighted_unrolled_jvp; with want_u,
+        (du, u) with u = kl_denoise(x, w) bit for bit."""
+        return self._weighted_jvp("kl_unrolled_jvp", self._lib.bpltv_kl_unrolled_jvp, x, w, df, dalpha, dw, want_u, kw)
+
+    def kl_unrolled_jvp_device(self, w_ptr, wo, alpha_ptr, am, an, df_ptr, dalpha_ptr, dw_ptr, du_ptr, u_ptr=None, ndir=1, **kw):
+        """bpltv_kl_unrolled_jvp_device: everything resident in HBM (raw device pointers), as weighted_unrolled_jvp_device."""
+        self._weighted_jvp_device(self._lib.bpltv_kl_unrolled_jvp_device, w_ptr, wo, alpha_ptr, am, an, df_ptr, dalpha_ptr,
+                                  dw_ptr, du_ptr, u_ptr, ndir, kw)
+
+    def kl_unrolled_gauss_newton(self, x, w, **kw):
+        """Gauss-Newton model of the maxiter-step loss 0.5||u_K(x) - ubar||^2 of the TV-KL iterations on the resident dataset
+        (bpltv_kl_unrolled_gauss_newton): (cost, grad, H) as weighted_unrolled_gauss_newton's."""
+        return self._weighted_gauss_newton(self._lib.bpltv_kl_unrolled_gauss_newton, x, w, kw)
 
     # -- one parameter per image (bpltv_denoise_each / bpltv_vjp_each) ---------------------------------------
     def _each_arg(self, alphas):

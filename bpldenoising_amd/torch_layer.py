@@ -112,14 +112,19 @@ f, alpha and w as for tv_denoise_weighted_unrolled, but the data term is sum w |
 pixels are removed exactly instead of being smeared, and the rest keeps its contrast.  backward is one
 bpltv_lone_unrolled_vjp_device call over a tape of 3 * maxiter * B*H*W doubles and returns f.grad, alpha.grad and w.grad, so a
 fidelity map can be trained against impulse noise.  TVL1DenoiseUnrolled(alpha, w, maxiter=50, learn_w=False) is the module: w
-is a buffer, or a Parameter with learn_w=True.  No jvp: forward_mode=True raises a ValueError.
+is a buffer, or a Parameter with learn_w=True.  No jvp: forward_mode=True raises a ValueError that names
+tv_l1_denoise_unrolled_fwd(f, alpha, w, maxiter=50), a separate function with the same u and the same backward whose jvp is one
+bpltv_lone_unrolled_jvp_device call: a tangent sweep through the TV-L1 iterations, no tape, tangents on f, alpha and w.  The
+module takes forward_mode=True and then runs it.
 
     u = tv_kl_denoise_unrolled(f, alpha, w, maxiter=50)          # TV-KL, for Poisson noise (bpltv_kl_unrolled_*)
 
 f, alpha and w as for tv_l1_denoise_unrolled, but the data term is the Kullback-Leibler divergence sum w (u - f log u) over u >= 0:
 the model for photon counts, whose noise grows with the signal.  f must be finite and >= 0 (zero counts are allowed).  backward is
 one bpltv_kl_unrolled_vjp_device call over a tape of 3 * maxiter * B*H*W doubles and returns f.grad, alpha.grad and w.grad.
-TVKLDenoiseUnrolled(alpha, w, maxiter=50, learn_w=False) is the module.  No jvp: forward_mode=True raises a ValueError.
+TVKLDenoiseUnrolled(alpha, w, maxiter=50, learn_w=False) is the module.  No jvp: forward_mode=True raises a ValueError that
+names tv_kl_denoise_unrolled_fwd(f, alpha, w, maxiter=50), the same function with a jvp (one bpltv_kl_unrolled_jvp_device call);
+TVKLDenoiseUnrolled(..., forward_mode=True) runs it.
 
 Streams: the library runs its kernels on its own HIP streams and blocks until they are done.  Every call below first
 synchronises the tensors' current torch stream, so that the library reads inputs torch has finished writing; its
@@ -299,7 +304,7 @@ def _no_checkpoint(solver_kw):
     return {k: v for k, v in solver_kw.items() if k != "checkpoint_every"}
 
 
-# ---- the one implementation behind the nineteen Functions below ----------------------------------------------------------------
+# ---- the one implementation behind the twenty-one Functions below ----------------------------------------------------------------
 # A model is a row of this record; _forward, _backward and _jvp are every Function's three methods, written once over it.
 # The TVSolver entries are named, not held: they are looked up on the handle of the call.  Their argument lists mirror the C
 # ABI and are not regular -- the channel count first, `w, wo` in front of alpha, the tape first in a vjp, a trailing u_ptr in
@@ -351,6 +356,10 @@ _L1_UNROLLED = _Model(_check_args, "l1_unrolled_denoise_device", "l1_unrolled_vj
                       w="tv_l1_denoise_unrolled", w_zeros=True, reads_f=True)
 _KL_UNROLLED = _Model(_check_args, "kl_unrolled_denoise_device", "kl_unrolled_vjp_device", None, "weighted_unrolled_tape_doubles",
                       w="tv_kl_denoise_unrolled", w_zeros=True, reads_f=True, f_nonneg=True)
+# ... and the same two with the tangent sweep (tv_l1_denoise_unrolled_fwd, tv_kl_denoise_unrolled_fwd): rows of their own, as the
+# two above stay without a jvp
+_L1_UNROLLED_FWD = _L1_UNROLLED._replace(jvp="l1_unrolled_jvp_device", w="tv_l1_denoise_unrolled_fwd")
+_KL_UNROLLED_FWD = _KL_UNROLLED._replace(jvp="kl_unrolled_jvp_device", w="tv_kl_denoise_unrolled_fwd")
 
 
 def _forward(m, ctx, f, alpha, solver_kw, reg=None, w=None, jvp=False):
@@ -816,18 +825,34 @@ def tv_l1_denoise_unrolled(f, alpha, w, maxiter=50, checkpoint_every=None, forwa
     f, alpha, w, checkpoint_every and solver_kw as tv_denoise_weighted_unrolled's: w float64 on f's device, >= 0 with zeros
     allowed, (H, W) -- w.grad then summed over the batch -- or f's shape (B, H, W).  accel changes nothing: the data term has no
     strong convexity and the steps are constant.
-    forward_mode=True raises: the tangent sweep of this model is not built."""
-    _no_forward_mode("tv_l1_denoise_unrolled", forward_mode, "the TV-L1 iterations",
-                     "tv_denoise_weighted_unrolled(..., forward_mode=True), with the quadratic data term,")
+    forward_mode=True raises: this function carries no jvp; tv_l1_denoise_unrolled_fwd (below) does."""
+    _no_forward_mode("tv_l1_denoise_unrolled", forward_mode, "the TV-L1 iterations", "tv_l1_denoise_unrolled_fwd(f, alpha, w, ...)")
     return TVL1DenoiseUnrolledFunction.apply(f, alpha, w, _with_checkpoint(dict(solver_kw, maxiter=int(maxiter)), checkpoint_every))
+
+
+class TVL1DenoiseUnrolledForwardFunction(TVL1DenoiseUnrolledFunction):
+    """TVL1DenoiseUnrolledFunction with a jvp (tv_l1_denoise_unrolled_fwd): forward is the base class's taped solve, so backward
+    keeps working; the jvp is one tangent sweep through the TV-L1 iterations (TVSolver.l1_unrolled_jvp_device, one direction),
+    which reads no tape."""
+    forward = staticmethod(lambda ctx, f, alpha, w, solver_kw: _forward(_L1_UNROLLED_FWD, ctx, f, alpha, solver_kw, w=w, jvp=True))
+    jvp = staticmethod(lambda ctx, df, dalpha, dw, _solver_kw: _jvp(_L1_UNROLLED_FWD, ctx, df, dalpha, dw))
+
+
+def tv_l1_denoise_unrolled_fwd(f, alpha, w, maxiter=50, checkpoint_every=None, **solver_kw):
+    """tv_l1_denoise_unrolled -- the same u and the same backward, bit for bit -- that is also usable under
+    torch.autograd.forward_ad, with tangents on f, alpha and w: the function carries a jvp, a tangent sweep through the TV-L1
+    iterations (bpltv_lone_unrolled_jvp_device), the exact transpose of backward.  It reads no tape and is unaffected by
+    checkpoint_every.  A pixel held at f by the threshold moves with f alone."""
+    return TVL1DenoiseUnrolledForwardFunction.apply(f, alpha, w, _with_checkpoint(dict(solver_kw, maxiter=int(maxiter)), checkpoint_every))
 
 
 class TVL1DenoiseUnrolled(torch.nn.Module):
     """tv_l1_denoise_unrolled behind a learnable scalar, patch parameter or pixel map alpha and a fidelity map w: a buffer, or
     with learn_w=True a Parameter too (keep it >= 0, by clamping after the optimiser's step).  Move it to the device of its
-    inputs with .to(device)."""
+    inputs with .to(device).  forward_mode=True: the module runs tv_l1_denoise_unrolled_fwd, usable under
+    torch.autograd.forward_ad as well."""
 
-    def __init__(self, alpha, w, maxiter=50, learn_w=False, checkpoint_every=None, **solver_kw):
+    def __init__(self, alpha, w, maxiter=50, learn_w=False, checkpoint_every=None, forward_mode=False, **solver_kw):
         super().__init__()
         self.alpha = torch.nn.Parameter(torch.as_tensor(alpha, dtype=torch.float64).clone())
         wt = torch.as_tensor(w, dtype=torch.float64).clone()
@@ -837,11 +862,12 @@ class TVL1DenoiseUnrolled(torch.nn.Module):
             self.register_buffer("w", wt)
         self.maxiter = int(maxiter)
         self.checkpoint_every = checkpoint_every
+        self.forward_mode = bool(forward_mode)
         self.solver_kw = dict(solver_kw)
 
     def forward(self, f):
-        return tv_l1_denoise_unrolled(f, self.alpha, self.w, maxiter=self.maxiter, checkpoint_every=self.checkpoint_every,
-                                      **self.solver_kw)
+        fn = tv_l1_denoise_unrolled_fwd if self.forward_mode else tv_l1_denoise_unrolled
+        return fn(f, self.alpha, self.w, maxiter=self.maxiter, checkpoint_every=self.checkpoint_every, **self.solver_kw)
 
 
 # ---- TV-KL (TVSolver.kl_unrolled_*): the data term w (u - f log u), for Poisson noise (photon counts) ----
@@ -860,18 +886,34 @@ def tv_kl_denoise_unrolled(f, alpha, w, maxiter=50, checkpoint_every=None, forwa
     f must be finite and >= 0 (zero counts are allowed): a ValueError otherwise.  alpha, w, checkpoint_every and solver_kw as
     tv_l1_denoise_unrolled's: w float64 on f's device, >= 0 with zeros allowed, (H, W) -- w.grad then summed over the batch -- or
     f's shape (B, H, W).  accel changes nothing: the steps are constant.
-    forward_mode=True raises: the tangent sweep of this model is not built."""
-    _no_forward_mode("tv_kl_denoise_unrolled", forward_mode, "the TV-KL iterations",
-                     "tv_denoise_weighted_unrolled(..., forward_mode=True), with the quadratic data term,")
+    forward_mode=True raises: this function carries no jvp; tv_kl_denoise_unrolled_fwd (below) does."""
+    _no_forward_mode("tv_kl_denoise_unrolled", forward_mode, "the TV-KL iterations", "tv_kl_denoise_unrolled_fwd(f, alpha, w, ...)")
     return TVKLDenoiseUnrolledFunction.apply(f, alpha, w, _with_checkpoint(dict(solver_kw, maxiter=int(maxiter)), checkpoint_every))
+
+
+class TVKLDenoiseUnrolledForwardFunction(TVKLDenoiseUnrolledFunction):
+    """TVKLDenoiseUnrolledFunction with a jvp (tv_kl_denoise_unrolled_fwd): forward is the base class's taped solve, so backward
+    keeps working; the jvp is one tangent sweep through the TV-KL iterations (TVSolver.kl_unrolled_jvp_device, one direction),
+    which reads no tape."""
+    forward = staticmethod(lambda ctx, f, alpha, w, solver_kw: _forward(_KL_UNROLLED_FWD, ctx, f, alpha, solver_kw, w=w, jvp=True))
+    jvp = staticmethod(lambda ctx, df, dalpha, dw, _solver_kw: _jvp(_KL_UNROLLED_FWD, ctx, df, dalpha, dw))
+
+
+def tv_kl_denoise_unrolled_fwd(f, alpha, w, maxiter=50, checkpoint_every=None, **solver_kw):
+    """tv_kl_denoise_unrolled -- the same u and the same backward, bit for bit -- that is also usable under
+    torch.autograd.forward_ad, with tangents on f, alpha and w: the function carries a jvp, a tangent sweep through the TV-KL
+    iterations (bpltv_kl_unrolled_jvp_device), the exact transpose of backward.  It reads no tape and is unaffected by
+    checkpoint_every.  f must be finite and >= 0: a ValueError otherwise.  A pixel clamped at zero passes nothing."""
+    return TVKLDenoiseUnrolledForwardFunction.apply(f, alpha, w, _with_checkpoint(dict(solver_kw, maxiter=int(maxiter)), checkpoint_every))
 
 
 class TVKLDenoiseUnrolled(torch.nn.Module):
     """tv_kl_denoise_unrolled behind a learnable scalar, patch parameter or pixel map alpha and a fidelity map w: a buffer, or
     with learn_w=True a Parameter too (keep it >= 0, by clamping after the optimiser's step).  Move it to the device of its
-    inputs with .to(device)."""
+    inputs with .to(device).  forward_mode=True: the module runs tv_kl_denoise_unrolled_fwd, usable under
+    torch.autograd.forward_ad as well."""
 
-    def __init__(self, alpha, w, maxiter=50, learn_w=False, checkpoint_every=None, **solver_kw):
+    def __init__(self, alpha, w, maxiter=50, learn_w=False, checkpoint_every=None, forward_mode=False, **solver_kw):
         super().__init__()
         self.alpha = torch.nn.Parameter(torch.as_tensor(alpha, dtype=torch.float64).clone())
         wt = torch.as_tensor(w, dtype=torch.float64).clone()
@@ -881,8 +923,9 @@ class TVKLDenoiseUnrolled(torch.nn.Module):
             self.register_buffer("w", wt)
         self.maxiter = int(maxiter)
         self.checkpoint_every = checkpoint_every
+        self.forward_mode = bool(forward_mode)
         self.solver_kw = dict(solver_kw)
 
     def forward(self, f):
-        return tv_kl_denoise_unrolled(f, self.alpha, self.w, maxiter=self.maxiter, checkpoint_every=self.checkpoint_every,
-                                      **self.solver_kw)
+        fn = tv_kl_denoise_unrolled_fwd if self.forward_mode else tv_kl_denoise_unrolled
+        return fn(f, self.alpha, self.w, maxiter=self.maxiter, checkpoint_every=self.checkpoint_every, **self.solver_kw)

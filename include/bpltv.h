@@ -145,7 +145,9 @@ typedef struct bpltv_stats {
                                   14 reverse sweep over the taped weighted channel-coupled iterations
                                   (bpltv_color_weighted_unrolled_vjp),
                                   15 reverse sweep over the taped TV-L1 iterations (bpltv_lone_unrolled_vjp),
-                                  16 reverse sweep over the taped TV-KL iterations (bpltv_kl_unrolled_vjp) */
+                                  16 reverse sweep over the taped TV-KL iterations (bpltv_kl_unrolled_vjp),
+                                  17 tangent sweep through the TV-L1 iterations (bpltv_lone_unrolled_jvp),
+                                  18 tangent sweep through the TV-KL iterations (bpltv_kl_unrolled_jvp) */
     int reg_gradient_used;     /* 1 if the last evaluate took the gradient_reg branch             */
     int ngpus;                 /* distinct devices behind this handle (1 for bpltv_create)        */
     int shards;                /* image shards (= worker threads) behind this handle              */
@@ -851,6 +853,46 @@ int bpltv_kl_unrolled_vjp(bpltv_t *h, const double *w, int wo, const double *alp
                           const double *gu, double *grad_f_out, double *grad_alpha_out, double *grad_w_out);
 int bpltv_kl_unrolled_vjp_device(bpltv_t *h, const double *d_tape, const double *d_w, int wo, const double *d_alpha, int am, int an,
                                  const bpltv_params *p, const double *d_gu, double *d_grad_f, double *d_grad_alpha, double *d_grad_w);
+
+/* Forward mode through the TV-L1 and the TV-KL iterations: bpltv_weighted_unrolled_jvp(_device) and
+ * bpltv_weighted_unrolled_gauss_newton for the two models above, argument for argument.  The tangent (dx, dy) is carried beside
+ * (x, y) through the same maxiter iterations, from dx = df, dy = 0, on the step table of gamma = 0 (constant steps: nothing of
+ * it depends on w, so nothing is omitted); the dual step and the projection's derivative are the weighted sweep's, and the
+ * primal step's tangent is, with dv = dx - tau * G^T dy,
+ *
+ *     TV-L1:  dx+ = dv - tau * sign(x+ - f) * dw   where x+ != f or w = 0   (the threshold let the step through, or is the
+ *             dx+ = df                             where x+ == f, w > 0      identity; a held pixel moves with f alone)
+ *     TV-KL:  dx+ = (x+ * dv + tau w * df + tau (f - x+) * dw) / s,   1/s = x+ / (tau w f + x+^2);   dx+ = 0 where x+ = 0
+ *
+ * each decided on x+, f and w exactly as the model's reverse sweep decides it from the tape: the sweep is that VJP's transpose
+ * pixel for pixel, <du, gu> = <df, grad_f> + <dalpha, grad_alpha> + <dw, grad_w>, and shares its conventions (TV-L1: the
+ * derivative on the threshold's kink is the held side's; TV-KL: a clamped pixel passes nothing).  No tape: 16 planes of M*N*O
+ * doubles, the weighted sweep's own workspace, whatever maxiter is.  u_out (may be NULL) is bpltv_lone_denoise's /
+ * bpltv_kl_denoise's u bit for bit.  Everything else -- ndir directions one after the other, each bitwise the single call; NULL
+ * tangents (not all three); finite tangents; the rejections, every one before anything of the handle changes; the last solve,
+ * every tape and the solve statistics left as they were; no captured graph shared with any other call, the weighted sweep's
+ * included; one shard forwarded, more BPLTV_E_UNSUPPORTED -- is bpltv_weighted_unrolled_jvp's contract.  TV-KL: the resident f
+ * must be finite and >= 0 (BPLTV_E_ARG naming f; checked once per dataset).  stats: only adjoint_ms and adjoint_method = 17
+ * (TV-L1) / 18 (TV-KL) change.
+ * The two _gauss_newton calls: a scalar or a patch parameter of P = am*an <= 16 entries (a map or more: BPLTV_E_UNSUPPORTED;
+ * use the model's _jvp for Jacobian columns), cost_out = 0.5||u_K - ubar||^2 on the resident ubar, grad_out = J^T (u_K - ubar),
+ * hess_out = J^T J, as bpltv_weighted_unrolled_gauss_newton. */
+int bpltv_lone_unrolled_jvp(bpltv_t *h, const double *w, int wo, const double *alpha, int am, int an,
+                            const bpltv_params *p, int ndir, const double *df, const double *dalpha, const double *dw,
+                            double *du_out, double *u_out /* may be NULL */);
+int bpltv_lone_unrolled_jvp_device(bpltv_t *h, const double *d_w, int wo, const double *d_alpha, int am, int an,
+                                   const bpltv_params *p, int ndir, const double *d_df, const double *d_dalpha,
+                                   const double *d_dw, double *d_du, double *d_u /* may be NULL */);
+int bpltv_lone_unrolled_gauss_newton(bpltv_t *h, const double *w, int wo, const double *alpha, int am, int an,
+                                     const bpltv_params *p, double *cost_out, double *grad_out, double *hess_out);
+int bpltv_kl_unrolled_jvp(bpltv_t *h, const double *w, int wo, const double *alpha, int am, int an,
+                          const bpltv_params *p, int ndir, const double *df, const double *dalpha, const double *dw,
+                          double *du_out, double *u_out /* may be NULL */);
+int bpltv_kl_unrolled_jvp_device(bpltv_t *h, const double *d_w, int wo, const double *d_alpha, int am, int an,
+                                 const bpltv_params *p, int ndir, const double *d_df, const double *d_dalpha,
+                                 const double *d_dw, double *d_du, double *d_u /* may be NULL */);
+int bpltv_kl_unrolled_gauss_newton(bpltv_t *h, const double *w, int wo, const double *alpha, int am, int an,
+                                   const bpltv_params *p, double *cost_out, double *grad_out, double *hess_out);
 
 /* Forward mode through the channel-coupled iterations: bpltv_unrolled_jvp and
  * bpltv_unrolled_gauss_newton for the model above.  The tangent (dx, dy) is carried beside (x, y) through the same maxiter

@@ -6,7 +6,7 @@
 # Same exports as src/TVLearningFunctionVec.jl:6
 export tv_op_learning_function, denoise, sumregs_learning_function, tv_vjp, sumregs_vjp, tv_jvp, tv_gauss_newton,
        sumregs_jvp, sumregs_gauss_newton, weighted_denoise, weighted_vjp, unrolled_denoise_each, unrolled_vjp_each,
-       unrolled_jvp_each, weighted_unrolled_jvp, color_denoise, l1_denoise, kl_denoise
+       unrolled_jvp_each, weighted_unrolled_jvp, color_denoise, l1_denoise, kl_denoise, l1_unrolled_jvp, kl_unrolled_jvp
 
 const libbpltv = "libbpltv"            # on LD_LIBRARY_PATH, or an absolute path
 
@@ -274,6 +274,48 @@ function weighted_unrolled_jvp(data::Array{Float64,3}, x, w::Union{Matrix{Float6
     du = similar(data); u = similar(data)
     p = Ref(default_params(; kwargs...))
     GC.@preserve w a tf ta tw du u bpltv_check(h, ccall((:bpltv_weighted_unrolled_jvp, libbpltv), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Cint, Ref{BpltvParams}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+         Ptr{Cdouble}, Ptr{Cdouble}), h.ptr, w, wo, a, am, an, p, 1, tf, ta, tw, du, u))
+    return du, u
+end
+
+# Forward mode through the TV-L1 iterations (include/bpltv.h, bpltv_lone_unrolled_jvp): du of the maxiter-step map
+# u = l1_denoise(data, x, w) for one direction (df, dα, dw), by a tangent sweep that records no tape; arguments and result as
+# weighted_unrolled_jvp's.  A pixel the threshold holds at f moves with f alone.
+function l1_unrolled_jvp(data::Array{Float64,3}, x, w::Union{Matrix{Float64},Array{Float64,3}};
+                         df = nothing, dα = nothing, dw = nothing, kwargs...)
+    h = handle_for(data, data)
+    a, am, an = alpha_arg(x)
+    wo = ndims(w) == 2 ? 1 : size(w, 3)
+    df === nothing && dα === nothing && dw === nothing && error("l1_unrolled_jvp: df, dα and dw are all nothing")
+    dw === nothing || size(dw) == size(w) || error("l1_unrolled_jvp: dw must have the shape of w")
+    tf = df === nothing ? C_NULL : Array{Float64}(df)
+    ta = dα === nothing ? C_NULL : (dα isa Real ? [Float64(dα)] : Array{Float64}(dα))
+    tw = dw === nothing ? C_NULL : Array{Float64}(dw)
+    du = similar(data); u = similar(data)
+    p = Ref(default_params(; kwargs...))
+    GC.@preserve w a tf ta tw du u bpltv_check(h, ccall((:bpltv_lone_unrolled_jvp, libbpltv), Cint,
+        (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Cint, Ref{BpltvParams}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
+         Ptr{Cdouble}, Ptr{Cdouble}), h.ptr, w, wo, a, am, an, p, 1, tf, ta, tw, du, u))
+    return du, u
+end
+
+# Forward mode through the TV-KL iterations (include/bpltv.h, bpltv_kl_unrolled_jvp): du of the maxiter-step map
+# u = kl_denoise(data, x, w) for one direction (df, dα, dw), by a tangent sweep that records no tape; arguments and result as
+# weighted_unrolled_jvp's.  data must be finite and >= 0; a pixel clamped at zero passes nothing.
+function kl_unrolled_jvp(data::Array{Float64,3}, x, w::Union{Matrix{Float64},Array{Float64,3}};
+                         df = nothing, dα = nothing, dw = nothing, kwargs...)
+    h = handle_for(data, data)
+    a, am, an = alpha_arg(x)
+    wo = ndims(w) == 2 ? 1 : size(w, 3)
+    df === nothing && dα === nothing && dw === nothing && error("kl_unrolled_jvp: df, dα and dw are all nothing")
+    dw === nothing || size(dw) == size(w) || error("kl_unrolled_jvp: dw must have the shape of w")
+    tf = df === nothing ? C_NULL : Array{Float64}(df)
+    ta = dα === nothing ? C_NULL : (dα isa Real ? [Float64(dα)] : Array{Float64}(dα))
+    tw = dw === nothing ? C_NULL : Array{Float64}(dw)
+    du = similar(data); u = similar(data)
+    p = Ref(default_params(; kwargs...))
+    GC.@preserve w a tf ta tw du u bpltv_check(h, ccall((:bpltv_kl_unrolled_jvp, libbpltv), Cint,
         (Ptr{Cvoid}, Ptr{Cdouble}, Cint, Ptr{Cdouble}, Cint, Cint, Ref{BpltvParams}, Cint, Ptr{Cdouble}, Ptr{Cdouble}, Ptr{Cdouble},
          Ptr{Cdouble}, Ptr{Cdouble}), h.ptr, w, wo, a, am, an, p, 1, tf, ta, tw, du, u))
     return du, u
