@@ -67,153 +67,85 @@ class BpltvStats(C.Structure):
 # every symbol include/bpltv.h declares: name -> (restype, argtypes)
 _H = C.c_void_p
 _PP = C.POINTER(BpltvParams)
+_I = C.c_int
+
+
+def _sig(op, device=False, w=False, channels=False, taped=False):
+    """(restype, argtypes) of bpltv_<model>_<op>[_each][_device].  Every model splices in the same places: the handle, [channels],
+    the leading arrays, [w, wo], alpha, am, an, [reg], the params, the tail.  Arrays are double pointers on the host and addresses
+    on the device.  A taped (unrolled) model reads the resident f and its tape; any other is implicit: vjp, jvp and gauss_newton
+    lead with the solution and take reg (a model with a w takes f after u instead, for grad_w)."""
+    a, implicit = (C.c_void_p if device else _dp), not taped
+    if op == "denoise":          # the host fetches u; on the device a taped solve ends on the tape
+        lead, reg, tail = 0, False, [a] * (taped if device else 1)
+    elif op == "vjp":            # [u[, f]], on the device a taped sweep's tape; gu, grad_f, grad_alpha[, grad_w]
+        lead, reg, tail = (1 + w if implicit else int(device)), implicit and not w, [a] * (3 + w)
+    elif op == "jvp":            # [u]; ndir, df, dalpha[, dw], du[, u_out]
+        lead, reg, tail = int(implicit), implicit, [_I] + [a] * (3 + w + taped)
+    else:                        # gauss_newton: [u, ubar]; [cost,] grad, H
+        lead, reg, tail = 2 * implicit, implicit, [a] * (2 + taped)
+    return C.c_int, [_H] + [_I] * channels + [a] * lead + [a, _I] * w + [a, _I, _I] + [_I] * reg + [_PP] + tail
+
+
+def _model(prefix, both, host_only="", each="", **flags):
+    """A model's entries: `both` on the host and as _device, `host_only` on the host, `each` also per image (the same lists)."""
+    out = {}
+    for op in (both + " " + host_only).split():
+        for e in ("", "_each") if op in each.split() else ("",):
+            for device in (False, True) if op in both.split() else (False,):
+                out["bpltv_%s%s%s%s" % (prefix, op, e, "_device" if device else "")] = _sig(op, device, **flags)
+    return out
+
+
+_EVALUATE = [_H, _dp, _I, _I, C.c_double, _PP, _dp]             # alpha, am, an, delta, params, u_out; then the outputs
+_CREATE = [C.POINTER(_H), _I, _I, _I]                            # handle, M, N, O; then the placement and the dtype
+_TAPE_DOUBLES = (C.c_int, [_H, _PP, C.POINTER(C.c_ulonglong)])
+_SWEEP = (C.c_int, [_H, _dp, _I, _I, _I, _PP, _dp, _dp])
 SYMBOLS = {
     "bpltv_version": (C.c_int, []),
     "bpltv_default_params": (C.c_int, [_PP]),
-    "bpltv_create": (C.c_int, [C.POINTER(_H), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "bpltv_create_multi": (C.c_int, [C.POINTER(_H), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "bpltv_create_sharded": (C.c_int, [C.POINTER(_H), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int]),
+    "bpltv_sumregs_default_params": (C.c_int, [_PP]),
+    "bpltv_create": (C.c_int, _CREATE + [_I, _I]),
+    "bpltv_create_multi": (C.c_int, _CREATE + [_I, _I]),
+    "bpltv_create_sharded": (C.c_int, _CREATE + [C.POINTER(_I), _I, _I]),
     "bpltv_destroy": (C.c_int, [_H]),
     "bpltv_set_data": (C.c_int, [_H, _dp, _dp]),
     "bpltv_set_data_device": (C.c_int, [_H, C.c_void_p, C.c_void_p]),
-    "bpltv_denoise": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp]),
-    "bpltv_denoise_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, _PP]),
-    "bpltv_evaluate": (C.c_int, [_H, _dp, C.c_int, C.c_int, C.c_double, _PP, _dp, _dp, _dp]),
-    "bpltv_sumregs_default_params": (C.c_int, [_PP]),
-    "bpltv_sumregs_denoise": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp]),
-    "bpltv_sumregs_evaluate": (C.c_int, [_H, _dp, C.c_int, C.c_int, C.c_double, _PP, _dp, _dp, _dp]),
-    "bpltv_sumregs_denoise_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, _PP]),
-    "bpltv_evaluate_partial": (C.c_int, [_H, _dp, C.c_int, C.c_int, C.c_double, _PP, _dp, _dp]),
-    "bpltv_evaluate_device": (C.c_int, [_H, _dp, C.c_int, C.c_int, C.c_double, _PP, C.c_void_p]),
+    "bpltv_evaluate": (C.c_int, _EVALUATE + [_dp, _dp]),
+    "bpltv_sumregs_evaluate": (C.c_int, _EVALUATE + [_dp, _dp]),
+    "bpltv_evaluate_partial": (C.c_int, _EVALUATE + [_dp]),
+    "bpltv_evaluate_device": (C.c_int, _EVALUATE[:-1] + [C.c_void_p]),
     "bpltv_u_device": (C.c_int, [_H, C.POINTER(C.c_void_p)]),
     "bpltv_copy_u_device": (C.c_int, [_H, C.c_void_p]),
     "bpltv_duality_gap": (C.c_int, [_H, _dp]),
     "bpltv_grad_fwd": (C.c_int, [_H, _dp, _dp, _dp]),
     "bpltv_grad_fwd_adjoint": (C.c_int, [_H, _dp, _dp, _dp]),
-    "bpltv_gradient": (C.c_int, [_H, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp]),
-    "bpltv_vjp": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
-    "bpltv_vjp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_void_p, C.c_void_p,
-                                   C.c_void_p]),
-    "bpltv_denoise_each": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp]),
-    "bpltv_denoise_each_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, _PP]),
-    "bpltv_vjp_each": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
-    "bpltv_vjp_each_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_void_p,
-                                        C.c_void_p, C.c_void_p]),
-    "bpltv_weighted_denoise": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp]),
-    "bpltv_weighted_denoise_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP]),
-    "bpltv_weighted_vjp": (C.c_int, [_H, _dp, _dp, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp, _dp]),
-    "bpltv_weighted_vjp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int,
-                                            _PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bpltv_unrolled_tape_doubles": (C.c_int, [_H, _PP, C.POINTER(C.c_ulonglong)]),
-    "bpltv_unrolled_denoise": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp]),
-    "bpltv_unrolled_denoise_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, _PP, C.c_void_p]),
-    "bpltv_unrolled_vjp": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
-    "bpltv_unrolled_vjp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, _PP, C.c_void_p, C.c_void_p,
-                                            C.c_void_p]),
-    "bpltv_weighted_unrolled_tape_doubles": (C.c_int, [_H, _PP, C.POINTER(C.c_ulonglong)]),
-    "bpltv_weighted_unrolled_denoise": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp]),
-    "bpltv_weighted_unrolled_denoise_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP,
-                                                         C.c_void_p]),
-    "bpltv_weighted_unrolled_vjp": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp, _dp]),
-    "bpltv_weighted_unrolled_vjp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP,
-                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bpltv_sumregs_unrolled_tape_doubles": (C.c_int, [_H, _PP, C.POINTER(C.c_ulonglong)]),
-    "bpltv_sumregs_unrolled_denoise": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp]),
-    "bpltv_sumregs_unrolled_denoise_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, _PP, C.c_void_p]),
-    "bpltv_sumregs_unrolled_vjp": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
-    "bpltv_sumregs_unrolled_vjp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, _PP, C.c_void_p,
-                                                    C.c_void_p, C.c_void_p]),
-    "bpltv_sumregs_unrolled_denoise_each": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp]),
-    "bpltv_sumregs_unrolled_denoise_each_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, _PP, C.c_void_p]),
-    "bpltv_sumregs_unrolled_vjp_each": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
-    "bpltv_sumregs_unrolled_vjp_each_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, _PP, C.c_void_p,
-                                                         C.c_void_p, C.c_void_p]),
-    "bpltv_color_denoise": (C.c_int, [_H, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp]),
-    "bpltv_color_denoise_device": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP]),
-    "bpltv_color_unrolled_denoise": (C.c_int, [_H, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp]),
-    "bpltv_color_unrolled_denoise_device": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP, C.c_void_p]),
-    "bpltv_color_unrolled_vjp": (C.c_int, [_H, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
-    "bpltv_color_unrolled_vjp_device": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, _PP, C.c_void_p,
-                                                  C.c_void_p, C.c_void_p]),
-    "bpltv_color_unrolled_jvp": (C.c_int, [_H, C.c_int, _dp, C.c_int, C.c_int, _PP, C.c_int, _dp, _dp, _dp, _dp]),
-    "bpltv_color_unrolled_jvp_device": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP, C.c_int, C.c_void_p, C.c_void_p,
-                                                  C.c_void_p, C.c_void_p]),
-    "bpltv_color_unrolled_gauss_newton": (C.c_int, [_H, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
-    "bpltv_color_weighted_denoise": (C.c_int, [_H, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp]),
-    "bpltv_color_weighted_denoise_device": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP]),
-    "bpltv_color_weighted_unrolled_denoise": (C.c_int, [_H, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp]),
-    "bpltv_color_weighted_unrolled_denoise_device": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP,
-                                                               C.c_void_p]),
-    "bpltv_color_weighted_unrolled_vjp": (C.c_int, [_H, C.c_int, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp, _dp]),
-    "bpltv_color_weighted_unrolled_vjp_device": (C.c_int, [_H, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
-                                                           C.c_int, _PP, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bpltv_lone_denoise": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp]),
-    "bpltv_lone_denoise_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP]),
-    "bpltv_lone_unrolled_denoise": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp]),
-    "bpltv_lone_unrolled_denoise_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP, C.c_void_p]),
-    "bpltv_lone_unrolled_vjp": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp, _dp]),
-    "bpltv_lone_unrolled_vjp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bpltv_kl_denoise": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp]),
-    "bpltv_kl_denoise_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP]),
-    "bpltv_kl_unrolled_denoise": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp]),
-    "bpltv_kl_unrolled_denoise_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP, C.c_void_p]),
-    "bpltv_kl_unrolled_vjp": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp, _dp]),
-    "bpltv_kl_unrolled_vjp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP,
-                                               C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bpltv_unrolled_jvp": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, C.c_int, _dp, _dp, _dp, _dp]),
-    "bpltv_unrolled_jvp_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, _PP, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
-                                            C.c_void_p]),
-    "bpltv_unrolled_gauss_newton": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
-    "bpltv_weighted_unrolled_jvp": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, C.c_int, _dp, _dp, _dp, _dp, _dp]),
-    "bpltv_weighted_unrolled_jvp_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP, C.c_int,
-                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bpltv_weighted_unrolled_gauss_newton": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
-    "bpltv_lone_unrolled_jvp": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, C.c_int, _dp, _dp, _dp, _dp, _dp]),
-    "bpltv_lone_unrolled_jvp_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP, C.c_int,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bpltv_lone_unrolled_gauss_newton": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
-    "bpltv_kl_unrolled_jvp": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, C.c_int, _dp, _dp, _dp, _dp, _dp]),
-    "bpltv_kl_unrolled_jvp_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, _PP, C.c_int,
-                                                 C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bpltv_kl_unrolled_gauss_newton": (C.c_int, [_H, _dp, C.c_int, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
-    "bpltv_unrolled_denoise_each": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp]),
-    "bpltv_unrolled_denoise_each_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, _PP, C.c_void_p]),
-    "bpltv_unrolled_vjp_each": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
-    "bpltv_unrolled_vjp_each_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, _PP, C.c_void_p, C.c_void_p,
-                                                 C.c_void_p]),
-    "bpltv_unrolled_jvp_each": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, C.c_int, _dp, _dp, _dp, _dp]),
-    "bpltv_unrolled_jvp_each_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, _PP, C.c_int, C.c_void_p, C.c_void_p,
-                                                 C.c_void_p, C.c_void_p]),
-    "bpltv_jvp": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, C.c_int, _dp, _dp, _dp]),
-    "bpltv_jvp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_int, C.c_void_p,
-                                   C.c_void_p, C.c_void_p]),
-    "bpltv_jvp_each": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, C.c_int, _dp, _dp, _dp]),
-    "bpltv_jvp_each_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_int, C.c_void_p,
-                                        C.c_void_p, C.c_void_p]),
-    "bpltv_gauss_newton": (C.c_int, [_H, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp]),
-    "bpltv_sumregs_jvp": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, C.c_int, _dp, _dp, _dp]),
-    "bpltv_sumregs_jvp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_int, C.c_void_p,
-                                           C.c_void_p, C.c_void_p]),
-    "bpltv_sumregs_jvp_each": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, C.c_int, _dp, _dp, _dp]),
-    "bpltv_sumregs_jvp_each_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_int,
-                                                C.c_void_p, C.c_void_p, C.c_void_p]),
-    "bpltv_sumregs_gauss_newton": (C.c_int, [_H, _dp, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp]),
-    "bpltv_sumregs_vjp": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
-    "bpltv_sumregs_vjp_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_void_p,
-                                           C.c_void_p, C.c_void_p]),
-    "bpltv_sumregs_denoise_each": (C.c_int, [_H, _dp, C.c_int, C.c_int, _PP, _dp]),
-    "bpltv_sumregs_denoise_each_device": (C.c_int, [_H, C.c_void_p, C.c_int, C.c_int, _PP]),
-    "bpltv_sumregs_vjp_each": (C.c_int, [_H, _dp, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp, _dp]),
-    "bpltv_sumregs_vjp_each_device": (C.c_int, [_H, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, _PP, C.c_void_p,
-                                                C.c_void_p, C.c_void_p]),
-    "bpltv_sweep": (C.c_int, [_H, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp]),
-    "bpltv_sumregs_sweep": (C.c_int, [_H, _dp, C.c_int, C.c_int, C.c_int, _PP, _dp, _dp]),
+    "bpltv_gradient": (C.c_int, [_H, _dp, _dp, _dp, _I, _I, _I, _PP, _dp]),
+    "bpltv_unrolled_tape_doubles": _TAPE_DOUBLES,
+    "bpltv_weighted_unrolled_tape_doubles": _TAPE_DOUBLES,
+    "bpltv_sumregs_unrolled_tape_doubles": _TAPE_DOUBLES,
+    "bpltv_sweep": _SWEEP,
+    "bpltv_sumregs_sweep": _SWEEP,
     "bpltv_per_image": (C.c_int, [_H, _dp]),
     "bpltv_set_option": (C.c_int, [_H, C.c_char_p, C.c_double]),
     "bpltv_stats": (C.c_int, [_H, C.POINTER(BpltvStats)]),
     "bpltv_last_error": (C.c_char_p, [_H]),
 }
+# the models: a new one is a line here (and a row of learning_function's table)
+for _prefix in ("", "sumregs_"):
+    SYMBOLS.update(_model(_prefix, "denoise vjp jvp", "gauss_newton", each="denoise vjp jvp"))
+SYMBOLS.update(_model("unrolled_", "denoise vjp jvp", "gauss_newton", each="denoise vjp jvp", taped=True))
+SYMBOLS.update(_model("sumregs_unrolled_", "denoise vjp", each="denoise vjp", taped=True))
+SYMBOLS.update(_model("weighted_", "denoise vjp", w=True))
+SYMBOLS.update(_model("color_", "denoise", channels=True))
+SYMBOLS.update(_model("color_weighted_", "denoise", w=True, channels=True))
+SYMBOLS.update(_model("color_unrolled_", "denoise vjp jvp", "gauss_newton", channels=True, taped=True))
+SYMBOLS.update(_model("color_weighted_unrolled_", "denoise vjp", w=True, channels=True, taped=True))
+for _prefix in ("lone_", "kl_"):
+    SYMBOLS.update(_model(_prefix, "denoise", w=True))
+for _prefix in ("weighted_", "lone_", "kl_"):
+    SYMBOLS.update(_model(_prefix + "unrolled_", "denoise vjp jvp", "gauss_newton", w=True, taped=True))
+del _prefix
 
 _lib = None
 

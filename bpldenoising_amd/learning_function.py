@@ -11,9 +11,8 @@ Array convention: a Julia `Array{Float64,3}` of size (M, N, O) (column major) is
 numpy array of shape (O, N, M).  A Julia m x n parameter matrix is a numpy array of shape (n, m).
 """
 import ctypes as C
-import functools
 import math
-import re
+import typing
 import numpy as np
 
 from . import _lib
@@ -23,6 +22,16 @@ _dp = C.POINTER(C.c_double)
 
 def _ptr(a):
     return a.ctypes.data_as(_dp)
+
+
+def _opt(a):
+    """A host array an entry may do without: NULL for None."""
+    return _ptr(a) if a is not None else None
+
+
+def _dev(ptr):
+    """A device address an entry may do without: NULL for 0 / None."""
+    return C.c_void_p(ptr or None)
 
 
 def _alpha_arg(x):
@@ -66,19 +75,6 @@ _PARAM_ALIASES = {
 }
 _IGNORED = {"verbose_iter", "save_results", "save_iterations", "op", "α", "alpha"}
 # ^ reference keys with no numerical meaning on this path (TVLearningFunctionVec.jl:39-42)
-
-
-def _restores_full_tape(method):
-    """A taped method of TVSolver: the tape_checkpoint option its checkpoint_every= set is back at 0 when it returns or raises."""
-    @functools.wraps(method)
-    def call(self, *args, **kw):
-        try:
-            return method(self, *args, **kw)
-        finally:
-            if getattr(self, "_spacing_set", False) and self._h:
-                self._spacing_set = False
-                self._lib.bpltv_set_option(self._h, b"tape_checkpoint", 0.0)
-    return call
 
 
 class TVSolver:
@@ -162,6 +158,203 @@ class TVSolver:
             raise ValueError("%s has shape %s, expected (O=%d, N=%d, M=%d)" % (what, a.shape, self.O, self.N, self.M))
         return a
 
+    # -- the cores ---------------------------------------------------------------------
+    # Every public solve, vjp, jvp and gauss_newton method below is one of these with a row of the _Model table under the class:
+    # the row says which entries to call and what their argument lists splice in, the public method keeps name, signature and text.
+    def _param(self, row, x):
+        """(a, am, an, scalar) by row's parser; scalar: a TV float, whose gradient goes back as a float."""
+        if row.each:
+            return row.parse(self, x) + (False,)
+        a, am, an, one = row.parse(x)
+        return a, am, an, one and row.slices == 1
+
+    def _call(self, row, op, p, alpha, am, an, tail, lead=(), w=None, wo=None, channels=None, reg=None, device=False):
+        """One call of row's entry `op`.  Every entry splices its arguments in the same places: the handle, [channels], the
+        leading arrays (u, f, ubar or the tape), [w, wo], alpha, am, an, [reg], the params, then the entry's own tail.  w and
+        alpha go as double pointers from the host and as addresses with device=True; lead and tail come converted."""
+        conv = C.c_void_p if device else _ptr
+        args = [self._h]
+        if row.channels:
+            args.append(int(channels))
+        args += lead
+        if row.w:
+            args += [conv(w), int(wo)]
+        args += [conv(alpha), int(am), int(an)]
+        if reg is not None:
+            args.append(int(bool(reg)))
+        args.append(C.byref(p))
+        args += tail
+        self._check(getattr(self._lib, row.entry(op, device))(*args))
+
+    def _taped_params(self, row, kw):
+        """(params, spacing set): params(**kw), for a taped row without checkpoint_every=, which becomes the handle's
+        tape_checkpoint option right here, before the ABI call; absent means 0, so a handle shared between calls never inherits
+        a spacing.  The caller's finally hands `spacing set` to _full_tape, so the handle keeps none for direct ABI calls either."""
+        if not row.taped:
+            return self.params(_sumregs=row.sumregs, **kw), False
+        c = kw.pop("checkpoint_every", None)
+        p = self.params(_sumregs=row.sumregs, **kw)
+        self.set_option("tape_checkpoint", 0 if c is None else c)
+        return p, bool(c)
+
+    def _full_tape(self, spacing_set):
+        if spacing_set and self._h:
+            self._lib.bpltv_set_option(self._h, b"tape_checkpoint", 0.0)
+
+    def _like(self, g, a, scalar):
+        """A gradient in the library's flat layout as the type / shape of the parameter."""
+        if g is None:
+            return None
+        if scalar:
+            return float(g[0])
+        return g if g.shape == a.shape else g.reshape(a.shape)
+
+    def _solve(self, row, x, fetch, kw, w=None, channels=None):
+        """<row>_denoise: u (None unless fetch); a taped row also records the tape in the handle."""
+        a, am, an, _ = self._param(row, x)
+        wa, wo = self._weight(w) if row.w else (None, None)
+        p, spacing_set = self._taped_params(row, kw)
+        try:
+            u = np.empty((self.O, self.N, self.M)) if fetch else None
+            self._call(row, "denoise", p, a, am, an, [_opt(u)], w=wa, wo=wo, channels=channels)
+            return u
+        finally:
+            self._full_tape(spacing_set)
+
+    def _solve_device(self, row, alpha_ptr, am, an, kw, w_ptr=None, wo=None, channels=None, tape_ptr=None):
+        """<row>_denoise_device; a taped row ends on the tape pointer (0 / None: the handle's own tape)."""
+        p, spacing_set = self._taped_params(row, kw)
+        try:
+            self._call(row, "denoise", p, alpha_ptr, am, an, [_dev(tape_ptr)] if row.taped else [], w=w_ptr, wo=wo,
+                       channels=channels, device=True)
+        finally:
+            self._full_tape(spacing_set)
+
+    def _tape_doubles(self, row, kw):
+        p, spacing_set = self._taped_params(row, kw)
+        try:
+            n = C.c_ulonglong(0)
+            self._check(getattr(self._lib, row.entry("tape_doubles"))(self._h, C.byref(p), C.byref(n)))
+            return int(n.value)
+        finally:
+            self._full_tape(spacing_set)
+
+    def _evaluate(self, row, x, delta, fetch_u, kw):
+        a, am, an, scalar = self._param(row, x)
+        self._last_npar = row.slices * am * an
+        p = self.params(_sumregs=row.sumregs, **kw)
+        u = np.empty((self.O, self.N, self.M)) if fetch_u else None
+        cost = C.c_double(0.0)
+        grad = np.empty(row.slices * am * an)
+        self._check(getattr(self._lib, row.entry("evaluate"))(self._h, _ptr(a), am, an, float(delta), C.byref(p), _opt(u),
+                                                              C.byref(cost), _ptr(grad)))
+        return u, cost.value, self._like(grad, a, scalar)
+
+    def _vjp(self, row, what, x, gu, want, kw, w=None, channels=None, u=None, f=None, reg=None, arrays_first=False):
+        """<row>_vjp: (grad_f, grad_x[, grad_w]), want = (want_f, want_alpha[, want_w]).  A taped row sweeps the handle's tape;
+        any other is implicit -- it leads with the solution u, then f where there is a w (read for grad_w only), and takes reg
+        where there is none.  arrays_first: u and gu are checked before the keywords (sumregs_vjp_each always did)."""
+        if not any(want):
+            raise ValueError("%s: %s False" % (what, "want_f, want_alpha and want_w are all" if row.w else
+                                               "want_f and want_alpha are both"))
+        a, am, an, scalar = self._param(row, x)
+        wa, wo = self._weight(w) if row.w else (None, None)
+        if arrays_first:
+            u, gu = self._batch(u, "u"), self._batch(gu, "gu")
+        p, spacing_set = self._taped_params(row, kw)
+        try:
+            lead = []
+            if not row.taped:
+                u = self._batch(u, "u")
+                lead.append(_ptr(u))
+            gu = self._batch(gu, "gu")
+            if row.w and not row.taped:
+                if want[2] and f is None:
+                    raise ValueError("%s: grad_w needs f" % what)
+                f = self._batch(f, "f") if f is not None else None
+                lead.append(_opt(f))
+            gf = np.empty((self.O, self.N, self.M)) if want[0] else None
+            ga = np.empty(a.shape if row.each else row.slices * am * an) if want[1] else None
+            gw = np.empty(wa.shape) if row.w and want[2] else None
+            self._call(row, "vjp", p, a, am, an, [_ptr(gu), _opt(gf), _opt(ga)] + ([_opt(gw)] if row.w else []), lead=lead,
+                       w=wa, wo=wo, channels=channels, reg=None if row.taped or row.w else bool(reg))
+            return (gf, self._like(ga, a, scalar)) + ((gw,) if row.w else ())
+        finally:
+            self._full_tape(spacing_set)
+
+    def _vjp_device(self, row, first_ptr, alpha_ptr, am, an, gu_ptr, grad_ptrs, kw, w_ptr=None, wo=None, channels=None, f_ptr=None,
+                    reg=None):
+        """<row>_vjp_device.  first_ptr: the tape of a taped row (0 / None: the handle's own), u of an implicit one; grad_ptrs:
+        the outputs in the order of _vjp's result, any of them 0 / None."""
+        p, spacing_set = self._taped_params(row, kw)
+        try:
+            lead = [_dev(first_ptr)] if row.taped else [C.c_void_p(first_ptr)] + ([_dev(f_ptr)] if row.w else [])
+            self._call(row, "vjp", p, alpha_ptr, am, an, [C.c_void_p(gu_ptr)] + [_dev(g) for g in grad_ptrs], lead=lead, w=w_ptr,
+                       wo=wo, channels=channels, reg=None if row.taped or row.w else bool(reg), device=True)
+        finally:
+            self._full_tape(spacing_set)
+
+    def _jvp(self, row, what, x, df, dalpha, kw, w=None, dw=None, channels=None, u=None, reg=None, want_u=False):
+        """<row>_jvp: du for the tangents as stacks of K directions, one call.  An unrolled (taped) row sweeps the iterations --
+        no tape, the spacing is never touched -- and ends on u (None unless want_u); any other is implicit: it leads with the
+        solution u and takes reg.  A row with a w takes the tangent dw after dalpha."""
+        a, am, an, scalar = self._param(row, x)
+        wa, wo = self._weight(w) if row.w else (None, None)
+        if row.w and df is None and dalpha is None and dw is None:
+            raise ValueError("%s: df, dalpha and dw are all None" % what)
+        K, batched = None, False
+        if not row.w or df is not None or dalpha is not None:
+            df, dalpha, K, batched = self._tangents(what, df, dalpha, () if scalar else a.shape)
+        if dw is not None:
+            dw = np.ascontiguousarray(dw, dtype=np.float64)
+            if dw.shape == wa.shape:
+                dw = dw[None]
+            elif dw.shape[1:] == wa.shape:
+                batched = True
+            else:
+                raise ValueError("%s: dw has shape %s, expected %s or (K,) + %s" % (what, dw.shape, wa.shape, wa.shape))
+            if K is None:
+                K = dw.shape[0]
+            if K < 1 or dw.shape[0] != K:
+                raise ValueError("%s: the tangents hold different numbers of directions" % what)
+        p = self.params(_sumregs=row.sumregs, **kw)
+        lead = []
+        if not row.taped:
+            u = self._batch(u, "u")
+            lead.append(_ptr(u))
+        du = np.empty((K, self.O, self.N, self.M))
+        uo = np.empty((self.O, self.N, self.M)) if want_u else None
+        self._call(row, "jvp", p, a, am, an, [K, _opt(df), _opt(dalpha)] + ([_opt(dw)] if row.w else []) + [_ptr(du)]
+                   + ([_opt(uo)] if row.taped else []), lead=lead, w=wa, wo=wo, channels=channels,
+                   reg=None if row.taped else bool(reg))
+        du = du if batched else du[0]
+        return (du, uo) if want_u else du
+
+    def _jvp_device(self, row, alpha_ptr, am, an, tangent_ptrs, du_ptr, ndir, kw, w_ptr=None, wo=None, channels=None, u_ptr=None,
+                    reg=None):
+        """<row>_jvp_device.  tangent_ptrs: (df, dalpha[, dw]), any of them 0 / None; u_ptr: the solution an implicit row leads
+        with, the output an unrolled one ends on (0 / None: not wanted)."""
+        p = self.params(_sumregs=row.sumregs, **kw)
+        self._call(row, "jvp", p, alpha_ptr, am, an, [int(ndir)] + [_dev(t) for t in tangent_ptrs] + [C.c_void_p(du_ptr)]
+                   + ([_dev(u_ptr)] if row.taped else []), lead=[] if row.taped else [C.c_void_p(u_ptr)], w=w_ptr, wo=wo,
+                   channels=channels, reg=None if row.taped else bool(reg), device=True)
+
+    def _gauss_newton(self, row, x, kw, w=None, channels=None, u=None, ubar=None, reg=None):
+        """<row>_gauss_newton: (grad, H) of an implicit row, for the given u and ubar; (cost, grad, H) of an unrolled (taped)
+        one, on the resident dataset.  grad has the type / shape of x, H is (P, P) with P = x.size."""
+        a, am, an, scalar = self._param(row, x)
+        wa, wo = self._weight(w) if row.w else (None, None)
+        p = self.params(_sumregs=row.sumregs, **kw)
+        P = row.slices * am * an
+        cost, grad, H = C.c_double(0.0), np.empty(P), np.empty((P, P))
+        if row.taped:
+            self._call(row, "gauss_newton", p, a, am, an, [C.byref(cost), _ptr(grad), _ptr(H)], w=wa, wo=wo, channels=channels)
+            return float(cost.value), self._like(grad, a, scalar), H
+        u = self._batch(u, "u")
+        ubar = self._batch(ubar, "ubar")
+        self._call(row, "gauss_newton", p, a, am, an, [_ptr(grad), _ptr(H)], lead=[_ptr(u), _ptr(ubar)], reg=bool(reg))
+        return self._like(grad, a, scalar), H
+
     # -- data ---------------------------------------------------------------------------------
     def set_data(self, ubar, f):
         ubar = self._batch(ubar, "ubar")
@@ -174,29 +367,15 @@ class TVSolver:
 
     # -- solve --------------------------------------------------------------------------------
     def denoise(self, x, fetch=True, **kw):
-        a, am, an, _ = _alpha_arg(x)
-        p = self.params(**kw)
-        u = np.empty((self.O, self.N, self.M)) if fetch else None
-        self._check(self._lib.bpltv_denoise(self._h, _ptr(a), am, an, C.byref(p), _ptr(u) if fetch else None))
-        return u
+        return self._solve(_TV, x, fetch, kw)
 
     def denoise_device(self, alpha_ptr, am=1, an=1, **kw):
         """bpltv_denoise_device: the parameter (am x an doubles, column major) already resident in HBM at `alpha_ptr`
         (e.g. a torch tensor's .data_ptr()); the result stays on the device (u_device_ptr / copy_u_device)."""
-        p = self.params(**kw)
-        self._check(self._lib.bpltv_denoise_device(self._h, C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p)))
+        self._solve_device(_TV, alpha_ptr, am, an, kw)
 
     def evaluate(self, x, delta, fetch_u=True, **kw):
-        a, am, an, scalar = _alpha_arg(x)
-        self._last_npar = am * an
-        p = self.params(**kw)
-        u = np.empty((self.O, self.N, self.M)) if fetch_u else None
-        cost = C.c_double(0.0)
-        grad = np.empty(am * an)
-        self._check(self._lib.bpltv_evaluate(self._h, _ptr(a), am, an, float(delta), C.byref(p),
-                                             _ptr(u) if fetch_u else None, C.byref(cost), _ptr(grad)))
-        g = float(grad[0]) if scalar else grad.reshape(an, am)
-        return u, cost.value, g
+        return self._evaluate(_TV, x, delta, fetch_u, kw)
 
     def evaluate_partial(self, x, delta, fetch_u=True, **kw):
         """[cost, grad...] of this handle's images only (to be all-reduced across shards)."""
@@ -221,59 +400,29 @@ class TVSolver:
     def sumregs_denoise(self, x, fetch=True, **kw):
         """sumregs_denoise(data, x, op1, op2, op3[, pOp]) (:38-85).  x: (3,) vector or (3, n, m) patch parameter
         (numpy (3, n, m) == Julia m x n x 3)."""
-        a, am, an, _ = _sr_alpha_arg(x)
-        p = self.params(_sumregs=True, **kw)
-        u = np.empty((self.O, self.N, self.M)) if fetch else None
-        self._check(self._lib.bpltv_sumregs_denoise(self._h, _ptr(a), am, an, C.byref(p), _ptr(u) if fetch else None))
-        return u
+        return self._solve(_SUMREGS, x, fetch, kw)
 
     def sumregs_evaluate(self, x, delta, fetch_u=True, **kw):
         """sumregs_learning_function(x, data, D; Dt = 1e-3) -> (u, cost, grad) (:8-36); grad has the shape of x."""
-        a, am, an, vec = _sr_alpha_arg(x)
-        self._last_npar = 3 * am * an
-        p = self.params(_sumregs=True, **kw)
-        u = np.empty((self.O, self.N, self.M)) if fetch_u else None
-        cost = C.c_double(0.0)
-        grad = np.empty(3 * am * an)
-        self._check(self._lib.bpltv_sumregs_evaluate(self._h, _ptr(a), am, an, float(delta), C.byref(p),
-                                                     _ptr(u) if fetch_u else None, C.byref(cost), _ptr(grad)))
-        return u, cost.value, (grad.copy() if vec else grad.reshape(3, an, am))
+        return self._evaluate(_SUMREGS, x, delta, fetch_u, kw)
 
     def sumregs_denoise_device(self, alpha_ptr, am=1, an=1, **kw):
         """bpltv_sumregs_denoise_device: the parameter (3*am*an doubles, three column-major am x an slices -- a
         C-contiguous (3, an, am) array) already resident in HBM at `alpha_ptr`; the result stays on the device
         (u_device_ptr / copy_u_device)."""
-        p = self.params(_sumregs=True, **kw)
-        self._check(self._lib.bpltv_sumregs_denoise_device(self._h, C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p)))
+        self._solve_device(_SUMREGS, alpha_ptr, am, an, kw)
 
     def sumregs_vjp(self, u, x, gu, reg=False, want_f=True, want_alpha=True, **kw):
         """Vector-Jacobian product of u = sumregs_denoise(f, x) for the cotangent gu = dL/du (bpltv_sumregs_vjp):
         (grad_f, grad_x).  u, gu: (O, N, M) batches; x: (3,) or (3, n, m).  grad_f has the shape of u (None unless
         want_f), grad_x the shape of x (None unless want_alpha).  gu = u - ubar gives sumregs_evaluate's gradient
         bitwise (reg = the evaluate's delta <= delta_t)."""
-        if not (want_f or want_alpha):
-            raise ValueError("sumregs_vjp: want_f and want_alpha are both False")
-        a, am, an, vec = _sr_alpha_arg(x)
-        p = self.params(_sumregs=True, **kw)
-        u = self._batch(u, "u")
-        gu = self._batch(gu, "gu")
-        gf = np.empty((self.O, self.N, self.M)) if want_f else None
-        ga = np.empty(3 * am * an) if want_alpha else None
-        self._check(self._lib.bpltv_sumregs_vjp(self._h, _ptr(u), _ptr(a), am, an, int(bool(reg)), C.byref(p),
-                                                _ptr(gu), _ptr(gf) if want_f else None,
-                                                _ptr(ga) if want_alpha else None))
-        if ga is not None and not vec:
-            ga = ga.reshape(3, an, am)
-        return gf, ga
+        return self._vjp(_SUMREGS, "sumregs_vjp", x, gu, (want_f, want_alpha), kw, u=u, reg=reg)
 
     def sumregs_vjp_device(self, u_ptr, alpha_ptr, am, an, gu_ptr, grad_f_ptr, grad_alpha_ptr, reg=False, **kw):
         """bpltv_sumregs_vjp_device: u, gu and grad_f (M*N*O doubles), the parameter and grad_alpha (3*am*an doubles)
         all resident in HBM; either output pointer may be 0 / None, not both."""
-        p = self.params(_sumregs=True, **kw)
-        self._check(self._lib.bpltv_sumregs_vjp_device(self._h, C.c_void_p(u_ptr), C.c_void_p(alpha_ptr), int(am),
-                                                       int(an), int(bool(reg)), C.byref(p), C.c_void_p(gu_ptr),
-                                                       C.c_void_p(grad_f_ptr or None),
-                                                       C.c_void_p(grad_alpha_ptr or None)))
+        self._vjp_device(_SUMREGS, u_ptr, alpha_ptr, am, an, gu_ptr, (grad_f_ptr, grad_alpha_ptr), kw, reg=reg)
 
     # -- forward mode of the sum-of-regularisers model (bpltv_sumregs_jvp / bpltv_sumregs_gauss_newton) ------------
     def sumregs_jvp(self, u, x, df=None, dalpha=None, reg=False, **kw):
@@ -281,38 +430,18 @@ class TVSolver:
         the linear map whose transpose sumregs_vjp computes.  x: (3,) or (3, n, m); df: (O, N, M), or (K, O, N, M) for K
         directions solved against one factorisation; dalpha: shaped like x, or with a leading K; either may be None
         (zero), not both.  Returns du of shape (O, N, M), or (K, O, N, M) when a leading K was given."""
-        a, am, an, _vec = _sr_alpha_arg(x)
-        df, dalpha, K, batched = self._tangents("sumregs_jvp", df, dalpha, a.shape)
-        p = self.params(_sumregs=True, **kw)
-        u = self._batch(u, "u")
-        du = np.empty((K, self.O, self.N, self.M))
-        self._check(self._lib.bpltv_sumregs_jvp(self._h, _ptr(u), _ptr(a), am, an, int(bool(reg)), C.byref(p), K,
-                                                _ptr(df) if df is not None else None,
-                                                _ptr(dalpha) if dalpha is not None else None, _ptr(du)))
-        return du if batched else du[0]
+        return self._jvp(_SUMREGS, "sumregs_jvp", x, df, dalpha, kw, u=u, reg=reg)
 
     def sumregs_jvp_device(self, u_ptr, alpha_ptr, am, an, df_ptr, dalpha_ptr, du_ptr, ndir=1, reg=False, **kw):
         """bpltv_sumregs_jvp_device: u (M*N*O doubles), the parameter (3*am*an), df and du (ndir*M*N*O) and dalpha
         (ndir*3*am*an) all resident in HBM (raw device pointers); either tangent pointer may be 0 / None, not both."""
-        p = self.params(_sumregs=True, **kw)
-        self._check(self._lib.bpltv_sumregs_jvp_device(self._h, C.c_void_p(u_ptr), C.c_void_p(alpha_ptr), int(am),
-                                                       int(an), int(bool(reg)), C.byref(p), int(ndir),
-                                                       C.c_void_p(df_ptr or None), C.c_void_p(dalpha_ptr or None),
-                                                       C.c_void_p(du_ptr)))
+        self._jvp_device(_SUMREGS, alpha_ptr, am, an, (df_ptr, dalpha_ptr), du_ptr, ndir, kw, u_ptr=u_ptr, reg=reg)
 
     def sumregs_gauss_newton(self, u, ubar, x, reg=False, **kw):
         """Gauss-Newton model of 0.5||u(x) - ubar||^2 (bpltv_sumregs_gauss_newton): (grad, H) with grad = J^T (u - ubar)
         shaped like x and H = J^T J of shape (P, P), P = x.size <= 16, ordered as numpy's x.ravel() (the library's
         parameter layout).  x: (3,), or a (3, n, m) patch."""
-        a, am, an, _vec = _sr_alpha_arg(x)
-        p = self.params(_sumregs=True, **kw)
-        u = self._batch(u, "u")
-        ubar = self._batch(ubar, "ubar")
-        P = 3 * am * an
-        grad, H = np.empty(P), np.empty((P, P))
-        self._check(self._lib.bpltv_sumregs_gauss_newton(self._h, _ptr(u), _ptr(ubar), _ptr(a), am, an,
-                                                         int(bool(reg)), C.byref(p), _ptr(grad), _ptr(H)))
-        return grad.reshape(a.shape), H
+        return self._gauss_newton(_SUMREGS, x, kw, u=u, ubar=ubar, reg=reg)
 
     def gradient(self, u, ubar, x, reg=False, **kw):
         a, am, an, scalar = _alpha_arg(x)
@@ -328,28 +457,13 @@ class TVSolver:
         """Vector-Jacobian product of u = denoise(f, x) for the cotangent gu = dL/du (bpltv_vjp): (grad_f, grad_x).
         u, gu: (O, N, M) batches; x: a float or an (n, m) parameter.  grad_f has the shape of u (None unless want_f),
         grad_x the type / shape of x (None unless want_alpha).  gu = u - ubar gives gradient(u, ubar, x, reg) bitwise."""
-        if not (want_f or want_alpha):
-            raise ValueError("vjp: want_f and want_alpha are both False")
-        a, am, an, scalar = _alpha_arg(x)
-        p = self.params(**kw)
-        u = self._batch(u, "u")
-        gu = self._batch(gu, "gu")
-        gf = np.empty((self.O, self.N, self.M)) if want_f else None
-        ga = np.empty(am * an) if want_alpha else None
-        self._check(self._lib.bpltv_vjp(self._h, _ptr(u), _ptr(a), am, an, int(bool(reg)), C.byref(p), _ptr(gu),
-                                        _ptr(gf) if want_f else None, _ptr(ga) if want_alpha else None))
-        if ga is not None:
-            ga = float(ga[0]) if scalar else ga.reshape(an, am)
-        return gf, ga
+        return self._vjp(_TV, "vjp", x, gu, (want_f, want_alpha), kw, u=u, reg=reg)
 
     def vjp_device(self, u_ptr, alpha_ptr, am, an, gu_ptr, grad_f_ptr, grad_alpha_ptr, reg=False, **kw):
         """bpltv_vjp_device: u, gu and grad_f (M*N*O doubles), the parameter and grad_alpha (am*an doubles, column
         major) all resident in HBM (raw device pointers, e.g. torch tensors' .data_ptr()); either output pointer may
         be 0 / None, not both."""
-        p = self.params(**kw)
-        self._check(self._lib.bpltv_vjp_device(self._h, C.c_void_p(u_ptr), C.c_void_p(alpha_ptr), int(am), int(an),
-                                               int(bool(reg)), C.byref(p), C.c_void_p(gu_ptr),
-                                               C.c_void_p(grad_f_ptr or None), C.c_void_p(grad_alpha_ptr or None)))
+        self._vjp_device(_TV, u_ptr, alpha_ptr, am, an, gu_ptr, (grad_f_ptr, grad_alpha_ptr), kw, reg=reg)
 
     # -- per-pixel data-fidelity weight (bpltv_weighted_*) ------------------------------------------------------
     def _weight(self, w):
@@ -365,74 +479,32 @@ class TVSolver:
     def weighted_denoise(self, x, w, fetch=True, **kw):
         """min_u 0.5 sum w (u - f)^2 + sum alpha |grad u| on the resident f (bpltv_weighted_denoise).  x: as denoise;
         w >= 0: (N, M) or (O, N, M).  w = 1 everywhere is denoise(x) bit for bit."""
-        a, am, an, _ = _alpha_arg(x)
-        wa, wo = self._weight(w)
-        p = self.params(**kw)
-        u = np.empty((self.O, self.N, self.M)) if fetch else None
-        self._check(self._lib.bpltv_weighted_denoise(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p),
-                                                     _ptr(u) if fetch else None))
-        return u
+        return self._solve(_WEIGHTED, x, fetch, kw, w=w)
 
     def weighted_denoise_device(self, w_ptr, wo, alpha_ptr, am=1, an=1, **kw):
         """bpltv_weighted_denoise_device: w (wo planes of M*N doubles, wo = 1 or O) and the parameter (am x an doubles)
         already resident in HBM; the result stays on the device (u_device_ptr / copy_u_device)."""
-        p = self.params(**kw)
-        self._check(self._lib.bpltv_weighted_denoise_device(self._h, C.c_void_p(w_ptr), int(wo), C.c_void_p(alpha_ptr),
-                                                            int(am), int(an), C.byref(p)))
+        self._solve_device(_WEIGHTED, alpha_ptr, am, an, kw, w_ptr=w_ptr, wo=wo)
 
     def weighted_vjp(self, u, f, x, w, gu, want_f=True, want_alpha=True, want_w=True, **kw):
         """Vector-Jacobian product of u = weighted_denoise(f, x, w) for the cotangent gu (bpltv_weighted_vjp):
         (grad_f, grad_x, grad_w).  u, gu: (O, N, M); f: (O, N, M), or None when grad_w is not wanted; w > 0: (N, M) or
         (O, N, M).  grad_w has the shape of w -- for (N, M) the sum over the images; an output not wanted is None."""
-        if not (want_f or want_alpha or want_w):
-            raise ValueError("weighted_vjp: want_f, want_alpha and want_w are all False")
-        a, am, an, scalar = _alpha_arg(x)
-        wa, wo = self._weight(w)
-        p = self.params(**kw)
-        u = self._batch(u, "u")
-        gu = self._batch(gu, "gu")
-        if want_w and f is None:
-            raise ValueError("weighted_vjp: grad_w needs f")
-        f = self._batch(f, "f") if f is not None else None
-        gf = np.empty((self.O, self.N, self.M)) if want_f else None
-        ga = np.empty(am * an) if want_alpha else None
-        gw = np.empty(wa.shape) if want_w else None
-        self._check(self._lib.bpltv_weighted_vjp(self._h, _ptr(u), _ptr(f) if f is not None else None, _ptr(wa), wo,
-                                                 _ptr(a), am, an, C.byref(p), _ptr(gu),
-                                                 _ptr(gf) if want_f else None, _ptr(ga) if want_alpha else None,
-                                                 _ptr(gw) if want_w else None))
-        if ga is not None:
-            ga = float(ga[0]) if scalar else ga.reshape(an, am)
-        return gf, ga, gw
+        return self._vjp(_WEIGHTED, "weighted_vjp", x, gu, (want_f, want_alpha, want_w), kw, w=w, u=u, f=f)
 
     def weighted_vjp_device(self, u_ptr, f_ptr, w_ptr, wo, alpha_ptr, am, an, gu_ptr, grad_f_ptr, grad_alpha_ptr,
                             grad_w_ptr, **kw):
         """bpltv_weighted_vjp_device: every array resident in HBM (raw device pointers); any output pointer may be
         0 / None, not all three; f_ptr may be 0 / None only if grad_w_ptr is."""
-        p = self.params(**kw)
-        self._check(self._lib.bpltv_weighted_vjp_device(self._h, C.c_void_p(u_ptr), C.c_void_p(f_ptr or None),
-                                                        C.c_void_p(w_ptr), int(wo), C.c_void_p(alpha_ptr), int(am),
-                                                        int(an), C.byref(p), C.c_void_p(gu_ptr),
-                                                        C.c_void_p(grad_f_ptr or None),
-                                                        C.c_void_p(grad_alpha_ptr or None),
-                                                        C.c_void_p(grad_w_ptr or None)))
+        self._vjp_device(_WEIGHTED, u_ptr, alpha_ptr, am, an, gu_ptr, (grad_f_ptr, grad_alpha_ptr, grad_w_ptr), kw,
+                         w_ptr=w_ptr, wo=wo, f_ptr=f_ptr)
 
     # -- reverse mode through the iterations (bpltv_unrolled_*) --------------------------------------------------
     # Every *_unrolled_tape_doubles, *_unrolled_denoise* and *_unrolled_vjp* method takes checkpoint_every=C on top of the
     # params keywords (option "tape_checkpoint", DESIGN.md section 4.10): None / 0 the full tape, C >= 1 the iteration state
     # every C iterations instead of a tape -- the sweep then recomputes each segment's tape, same bits, one more forward
     # solve -- and -1 the spacing of least memory (auto_checkpoint_every).  Solve, sweep and tape_doubles of one tape take the
-    # same value.
-    def _taped_params(self, kw, **model):
-        """params(**kw) without checkpoint_every=, which becomes the handle's tape_checkpoint option right before the
-        ABI call; absent means 0, so a handle shared between calls never inherits a spacing.  A spacing set here is taken
-        back when the method returns (_restores_full_tape), so the handle keeps none for direct ABI calls either."""
-        c = kw.pop("checkpoint_every", None)
-        p = self.params(**model, **kw)
-        self.set_option("tape_checkpoint", 0 if c is None else c)
-        self._spacing_set = bool(c)
-        return p
-
+    # same value.  The taped cores set the option (_taped_params) and take it back in their own finally (_full_tape).
     @staticmethod
     def auto_checkpoint_every(maxiter, model="tv"):
         """The spacing checkpoint_every=-1 stands for: ceil(sqrt(nplanes * maxiter / tape_planes)) in [1, maxiter], which
@@ -450,54 +522,30 @@ class TVSolver:
 
     def unrolled_tape_doubles(self, **kw):
         """Doubles of the tape an unrolled solve with these params records: 2 * maxiter * M*N*O."""
-        p = self._taped_params(kw)
-        n = C.c_ulonglong(0)
-        self._check(self._lib.bpltv_unrolled_tape_doubles(self._h, C.byref(p), C.byref(n)))
-        return int(n.value)
+        return self._tape_doubles(_UNROLLED, kw)
 
     def unrolled_denoise(self, x, fetch=True, **kw):
         """denoise(x) with rho = 0 -- the same u bit for bit -- that also records the tape of the iterations in the
         handle, for unrolled_vjp with the same x and params (bpltv_unrolled_denoise)."""
-        a, am, an, _ = _alpha_arg(x)
-        p = self._taped_params(kw)
-        u = np.empty((self.O, self.N, self.M)) if fetch else None
-        self._check(self._lib.bpltv_unrolled_denoise(self._h, _ptr(a), am, an, C.byref(p), _ptr(u) if fetch else None))
-        return u
+        return self._solve(_UNROLLED, x, fetch, kw)
 
     def unrolled_denoise_device(self, alpha_ptr, am=1, an=1, tape_ptr=None, **kw):
         """bpltv_unrolled_denoise_device: the parameter resident in HBM, the result left there (u_device_ptr /
         copy_u_device); tape_ptr: a caller-owned HBM buffer of unrolled_tape_doubles(**kw) doubles, or None / 0 for
         the handle's own tape."""
-        p = self._taped_params(kw)
-        self._check(self._lib.bpltv_unrolled_denoise_device(self._h, C.c_void_p(alpha_ptr), int(am), int(an),
-                                                            C.byref(p), C.c_void_p(tape_ptr or None)))
+        self._solve_device(_UNROLLED, alpha_ptr, am, an, kw, tape_ptr=tape_ptr)
 
     def unrolled_vjp(self, x, gu, want_f=True, want_alpha=True, **kw):
         """Vector-Jacobian product of the maxiter-step map u = unrolled_denoise(x) for the cotangent gu = dL/du, by a
         reverse sweep over the handle's tape (bpltv_unrolled_vjp): (grad_f, grad_x).  x and the params must be those
         of the solve.  gu: (O, N, M); grad_f has its shape (None unless want_f), grad_x the type / shape of x (None
         unless want_alpha)."""
-        if not (want_f or want_alpha):
-            raise ValueError("unrolled_vjp: want_f and want_alpha are both False")
-        a, am, an, scalar = _alpha_arg(x)
-        p = self._taped_params(kw)
-        gu = self._batch(gu, "gu")
-        gf = np.empty((self.O, self.N, self.M)) if want_f else None
-        ga = np.empty(am * an) if want_alpha else None
-        self._check(self._lib.bpltv_unrolled_vjp(self._h, _ptr(a), am, an, C.byref(p), _ptr(gu),
-                                                 _ptr(gf) if want_f else None, _ptr(ga) if want_alpha else None))
-        if ga is not None:
-            ga = float(ga[0]) if scalar else ga.reshape(an, am)
-        return gf, ga
+        return self._vjp(_UNROLLED, "unrolled_vjp", x, gu, (want_f, want_alpha), kw)
 
     def unrolled_vjp_device(self, tape_ptr, alpha_ptr, am, an, gu_ptr, grad_f_ptr, grad_alpha_ptr, **kw):
         """bpltv_unrolled_vjp_device: the tape (None / 0: the handle's own), the parameter, gu and the outputs resident
         in HBM (raw device pointers); either output pointer may be 0 / None, not both."""
-        p = self._taped_params(kw)
-        self._check(self._lib.bpltv_unrolled_vjp_device(self._h, C.c_void_p(tape_ptr or None), C.c_void_p(alpha_ptr),
-                                                        int(am), int(an), C.byref(p), C.c_void_p(gu_ptr),
-                                                        C.c_void_p(grad_f_ptr or None),
-                                                        C.c_void_p(grad_alpha_ptr or None)))
+        self._vjp_device(_UNROLLED, tape_ptr, alpha_ptr, am, an, gu_ptr, (grad_f_ptr, grad_alpha_ptr), kw)
 
     # -- channel-coupled TV for colour images (bpltv_color_*) ------------------------------------------------------
     # The handle's O planes are O / channels colour images of `channels` consecutive planes; x is one parameter shared by the
@@ -505,94 +553,49 @@ class TVSolver:
     def color_denoise(self, x, channels, fetch=True, **kw):
         """Vectorial TV: the channels of a colour image share one projection per pixel (bpltv_color_denoise).  No tape, any
         maxiter >= 1; u is bitwise color_unrolled_denoise's."""
-        a, am, an, _ = _alpha_arg(x)
-        p = self.params(**kw)
-        u = np.empty((self.O, self.N, self.M)) if fetch else None
-        self._check(self._lib.bpltv_color_denoise(self._h, int(channels), _ptr(a), am, an, C.byref(p), _ptr(u) if fetch else None))
-        return u
+        return self._solve(_COLOR, x, fetch, kw, channels=channels)
 
     def color_denoise_device(self, channels, alpha_ptr, am=1, an=1, **kw):
         """bpltv_color_denoise_device: the parameter resident in HBM, the result left there (u_device_ptr / copy_u_device)."""
-        p = self.params(**kw)
-        self._check(self._lib.bpltv_color_denoise_device(self._h, int(channels), C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p)))
+        self._solve_device(_COLOR, alpha_ptr, am, an, kw, channels=channels)
 
     def color_unrolled_denoise(self, x, channels, fetch=True, **kw):
         """color_denoise that also records the tape of the iterations in the handle, for color_unrolled_vjp with the same
         x, channels and params (bpltv_color_unrolled_denoise)."""
-        a, am, an, _ = _alpha_arg(x)
-        p = self._taped_params(kw)
-        u = np.empty((self.O, self.N, self.M)) if fetch else None
-        self._check(self._lib.bpltv_color_unrolled_denoise(self._h, int(channels), _ptr(a), am, an, C.byref(p),
-                                                           _ptr(u) if fetch else None))
-        return u
+        return self._solve(_COLOR_UNROLLED, x, fetch, kw, channels=channels)
 
     def color_unrolled_denoise_device(self, channels, alpha_ptr, am=1, an=1, tape_ptr=None, **kw):
         """bpltv_color_unrolled_denoise_device: the parameter resident in HBM, the result left there; tape_ptr: a
         caller-owned HBM buffer of unrolled_tape_doubles(**kw) doubles, or None / 0 for the handle's colour tape."""
-        p = self._taped_params(kw)
-        self._check(self._lib.bpltv_color_unrolled_denoise_device(self._h, int(channels), C.c_void_p(alpha_ptr), int(am), int(an),
-                                                                  C.byref(p), C.c_void_p(tape_ptr or None)))
+        self._solve_device(_COLOR_UNROLLED, alpha_ptr, am, an, kw, channels=channels, tape_ptr=tape_ptr)
 
     def color_unrolled_vjp(self, x, channels, gu, want_f=True, want_alpha=True, **kw):
         """Vector-Jacobian product of the maxiter-step map u = color_unrolled_denoise(x, channels) for the cotangent gu, by
         a reverse sweep over the handle's colour tape (bpltv_color_unrolled_vjp): (grad_f, grad_x), as unrolled_vjp."""
-        if not (want_f or want_alpha):
-            raise ValueError("color_unrolled_vjp: want_f and want_alpha are both False")
-        a, am, an, scalar = _alpha_arg(x)
-        p = self._taped_params(kw)
-        gu = self._batch(gu, "gu")
-        gf = np.empty((self.O, self.N, self.M)) if want_f else None
-        ga = np.empty(am * an) if want_alpha else None
-        self._check(self._lib.bpltv_color_unrolled_vjp(self._h, int(channels), _ptr(a), am, an, C.byref(p), _ptr(gu),
-                                                       _ptr(gf) if want_f else None, _ptr(ga) if want_alpha else None))
-        if ga is not None:
-            ga = float(ga[0]) if scalar else ga.reshape(an, am)
-        return gf, ga
+        return self._vjp(_COLOR_UNROLLED, "color_unrolled_vjp", x, gu, (want_f, want_alpha), kw, channels=channels)
 
     def color_unrolled_vjp_device(self, channels, tape_ptr, alpha_ptr, am, an, gu_ptr, grad_f_ptr, grad_alpha_ptr, **kw):
         """bpltv_color_unrolled_vjp_device: the tape (None / 0: the handle's own), the parameter, gu and the outputs
         resident in HBM (raw device pointers); either output pointer may be 0 / None, not both."""
-        p = self._taped_params(kw)
-        self._check(self._lib.bpltv_color_unrolled_vjp_device(self._h, int(channels), C.c_void_p(tape_ptr or None),
-                                                              C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p),
-                                                              C.c_void_p(gu_ptr), C.c_void_p(grad_f_ptr or None),
-                                                              C.c_void_p(grad_alpha_ptr or None)))
+        self._vjp_device(_COLOR_UNROLLED, tape_ptr, alpha_ptr, am, an, gu_ptr, (grad_f_ptr, grad_alpha_ptr), kw,
+                         channels=channels)
 
     def color_unrolled_jvp(self, x, channels, df=None, dalpha=None, want_u=False, **kw):
         """Jacobian-vector product of the maxiter-step map u = color_denoise(x, channels) of the resident f
         (bpltv_color_unrolled_jvp): a tangent sweep through the channel-coupled iterations, no tape -- the linear map whose
         transpose color_unrolled_vjp computes.  Tangents, result and want_u as unrolled_jvp; channels = 1 is unrolled_jvp
         bit for bit."""
-        a, am, an, scalar = _alpha_arg(x)
-        df, dalpha, K, batched = self._tangents("color_unrolled_jvp", df, dalpha, () if scalar else (an, am))
-        p = self.params(**kw)
-        du = np.empty((K, self.O, self.N, self.M))
-        u = np.empty((self.O, self.N, self.M)) if want_u else None
-        self._check(self._lib.bpltv_color_unrolled_jvp(self._h, int(channels), _ptr(a), am, an, C.byref(p), K,
-                                                       _ptr(df) if df is not None else None,
-                                                       _ptr(dalpha) if dalpha is not None else None, _ptr(du),
-                                                       _ptr(u) if want_u else None))
-        du = du if batched else du[0]
-        return (du, u) if want_u else du
+        return self._jvp(_COLOR_UNROLLED, "color_unrolled_jvp", x, df, dalpha, kw, channels=channels, want_u=want_u)
 
     def color_unrolled_jvp_device(self, channels, alpha_ptr, am, an, df_ptr, dalpha_ptr, du_ptr, u_ptr=None, ndir=1, **kw):
         """bpltv_color_unrolled_jvp_device: as unrolled_jvp_device, for colour images of `channels` planes."""
-        p = self.params(**kw)
-        self._check(self._lib.bpltv_color_unrolled_jvp_device(self._h, int(channels), C.c_void_p(alpha_ptr), int(am), int(an),
-                                                              C.byref(p), int(ndir), C.c_void_p(df_ptr or None),
-                                                              C.c_void_p(dalpha_ptr or None), C.c_void_p(du_ptr),
-                                                              C.c_void_p(u_ptr or None)))
+        self._jvp_device(_COLOR_UNROLLED, alpha_ptr, am, an, (df_ptr, dalpha_ptr), du_ptr, ndir, kw, channels=channels,
+                         u_ptr=u_ptr)
 
     def color_unrolled_gauss_newton(self, x, channels, **kw):
         """Gauss-Newton model of the maxiter-step loss 0.5||u_K(x) - ubar||^2 of the channel-coupled solve, over all planes
         (bpltv_color_unrolled_gauss_newton): (cost, grad, H) as unrolled_gauss_newton."""
-        a, am, an, scalar = _alpha_arg(x)
-        p = self.params(**kw)
-        P = am * an
-        cost, grad, H = C.c_double(0.0), np.empty(P), np.empty((P, P))
-        self._check(self._lib.bpltv_color_unrolled_gauss_newton(self._h, int(channels), _ptr(a), am, an, C.byref(p),
-                                                                C.byref(cost), _ptr(grad), _ptr(H)))
-        return float(cost.value), (float(grad[0]) if scalar else grad.reshape(an, am)), H
+        return self._gauss_newton(_COLOR_UNROLLED, x, kw, channels=channels)
 
     # -- channel-coupled TV with a per-pixel fidelity weight (bpltv_color_weighted_*) ------------------------------
     # w >= 0, zeros allowed: (N, M) -- one plane for every plane of the batch -- or (O, N, M), one per plane (per channel).  The
@@ -601,135 +604,68 @@ class TVSolver:
         """Vectorial TV with the fidelity 0.5 sum_c w_c (u_c - f_c)^2 (bpltv_color_weighted_denoise): colour inpainting,
         demosaicing, a variance per channel.  No tape; u is bitwise color_weighted_unrolled_denoise's, and with w = 1
         color_denoise's."""
-        a, am, an, _ = _alpha_arg(x)
-        wa, wo = self._weight(w)
-        p = self.params(**kw)
-        u = np.empty((self.O, self.N, self.M)) if fetch else None
-        self._check(self._lib.bpltv_color_weighted_denoise(self._h, int(channels), _ptr(wa), wo, _ptr(a), am, an, C.byref(p),
-                                                           _ptr(u) if fetch else None))
-        return u
+        return self._solve(_COLOR_WEIGHTED, x, fetch, kw, w=w, channels=channels)
 
     def color_weighted_denoise_device(self, channels, w_ptr, wo, alpha_ptr, am=1, an=1, **kw):
         """bpltv_color_weighted_denoise_device: w (wo planes) and the parameter resident in HBM, the result left there."""
-        p = self.params(**kw)
-        self._check(self._lib.bpltv_color_weighted_denoise_device(self._h, int(channels), C.c_void_p(w_ptr), int(wo),
-                                                                  C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p)))
+        self._solve_device(_COLOR_WEIGHTED, alpha_ptr, am, an, kw, w_ptr=w_ptr, wo=wo, channels=channels)
 
     def color_weighted_unrolled_denoise(self, x, channels, w, fetch=True, **kw):
         """color_weighted_denoise that also records the tape of the iterations in the handle, for
         color_weighted_unrolled_vjp with the same x, channels, w and params (bpltv_color_weighted_unrolled_denoise)."""
-        a, am, an, _ = _alpha_arg(x)
-        wa, wo = self._weight(w)
-        p = self._taped_params(kw)
-        u = np.empty((self.O, self.N, self.M)) if fetch else None
-        self._check(self._lib.bpltv_color_weighted_unrolled_denoise(self._h, int(channels), _ptr(wa), wo, _ptr(a), am, an,
-                                                                    C.byref(p), _ptr(u) if fetch else None))
-        return u
+        return self._solve(_COLOR_WEIGHTED_UNROLLED, x, fetch, kw, w=w, channels=channels)
 
     def color_weighted_unrolled_denoise_device(self, channels, w_ptr, wo, alpha_ptr, am=1, an=1, tape_ptr=None, **kw):
         """bpltv_color_weighted_unrolled_denoise_device: w (wo planes) and the parameter resident in HBM, the result left
         there; tape_ptr: a caller-owned HBM buffer of weighted_unrolled_tape_doubles(**kw) doubles, or None / 0 for the
         handle's colour-weighted tape."""
-        p = self._taped_params(kw)
-        self._check(self._lib.bpltv_color_weighted_unrolled_denoise_device(self._h, int(channels), C.c_void_p(w_ptr), int(wo),
-                                                                           C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p),
-                                                                           C.c_void_p(tape_ptr or None)))
+        self._solve_device(_COLOR_WEIGHTED_UNROLLED, alpha_ptr, am, an, kw, w_ptr=w_ptr, wo=wo, channels=channels,
+                           tape_ptr=tape_ptr)
 
     def color_weighted_unrolled_vjp(self, x, channels, w, gu, want_f=True, want_alpha=True, want_w=True, **kw):
         """Vector-Jacobian product of the maxiter-step map u = color_weighted_unrolled_denoise(x, channels, w) for the
         cotangent gu, by a reverse sweep over the handle's colour-weighted tape (bpltv_color_weighted_unrolled_vjp):
         (grad_f, grad_x, grad_w), as weighted_unrolled_vjp.  grad_w has the shape of w -- for (N, M) the sum over the planes."""
-        if not (want_f or want_alpha or want_w):
-            raise ValueError("color_weighted_unrolled_vjp: want_f, want_alpha and want_w are all False")
-        a, am, an, scalar = _alpha_arg(x)
-        wa, wo = self._weight(w)
-        p = self._taped_params(kw)
-        gu = self._batch(gu, "gu")
-        gf = np.empty((self.O, self.N, self.M)) if want_f else None
-        ga = np.empty(am * an) if want_alpha else None
-        gw = np.empty(wa.shape) if want_w else None
-        self._check(self._lib.bpltv_color_weighted_unrolled_vjp(self._h, int(channels), _ptr(wa), wo, _ptr(a), am, an, C.byref(p),
-                                                                _ptr(gu), _ptr(gf) if want_f else None,
-                                                                _ptr(ga) if want_alpha else None,
-                                                                _ptr(gw) if want_w else None))
-        if ga is not None:
-            ga = float(ga[0]) if scalar else ga.reshape(an, am)
-        return gf, ga, gw
+        return self._vjp(_COLOR_WEIGHTED_UNROLLED, "color_weighted_unrolled_vjp", x, gu, (want_f, want_alpha, want_w), kw, w=w,
+                         channels=channels)
 
     def color_weighted_unrolled_vjp_device(self, channels, tape_ptr, w_ptr, wo, alpha_ptr, am, an, gu_ptr, grad_f_ptr,
                                            grad_alpha_ptr, grad_w_ptr, **kw):
         """bpltv_color_weighted_unrolled_vjp_device: the tape (None / 0: the handle's own), w, the parameter, gu and the
         outputs resident in HBM (raw device pointers); any output pointer may be 0 / None, not all three."""
-        p = self._taped_params(kw)
-        self._check(self._lib.bpltv_color_weighted_unrolled_vjp_device(self._h, int(channels), C.c_void_p(tape_ptr or None),
-                                                                       C.c_void_p(w_ptr), int(wo), C.c_void_p(alpha_ptr),
-                                                                       int(am), int(an), C.byref(p), C.c_void_p(gu_ptr),
-                                                                       C.c_void_p(grad_f_ptr or None),
-                                                                       C.c_void_p(grad_alpha_ptr or None),
-                                                                       C.c_void_p(grad_w_ptr or None)))
+        self._vjp_device(_COLOR_WEIGHTED_UNROLLED, tape_ptr, alpha_ptr, am, an, gu_ptr, (grad_f_ptr, grad_alpha_ptr,
+                         grad_w_ptr), kw, w_ptr=w_ptr, wo=wo, channels=channels)
 
     # -- reverse mode through the weighted iterations (bpltv_weighted_unrolled_*) --------------------------------
     def weighted_unrolled_tape_doubles(self, **kw):
         """Doubles of the tape a weighted unrolled solve with these params records: 3 * maxiter * M*N*O."""
-        p = self._taped_params(kw)
-        n = C.c_ulonglong(0)
-        self._check(self._lib.bpltv_weighted_unrolled_tape_doubles(self._h, C.byref(p), C.byref(n)))
-        return int(n.value)
+        return self._tape_doubles(_WEIGHTED_UNROLLED, kw)
 
     def weighted_unrolled_denoise(self, x, w, fetch=True, **kw):
         """weighted_denoise(x, w) -- the same u bit for bit, w >= 0 with zeros allowed -- that also records the tape of
         the iterations in the handle, for weighted_unrolled_vjp with the same x, w and params
         (bpltv_weighted_unrolled_denoise)."""
-        a, am, an, _ = _alpha_arg(x)
-        wa, wo = self._weight(w)
-        p = self._taped_params(kw)
-        u = np.empty((self.O, self.N, self.M)) if fetch else None
-        self._check(self._lib.bpltv_weighted_unrolled_denoise(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p),
-                                                              _ptr(u) if fetch else None))
-        return u
+        return self._solve(_WEIGHTED_UNROLLED, x, fetch, kw, w=w)
 
     def weighted_unrolled_denoise_device(self, w_ptr, wo, alpha_ptr, am=1, an=1, tape_ptr=None, **kw):
         """bpltv_weighted_unrolled_denoise_device: w (wo planes) and the parameter resident in HBM, the result left
         there; tape_ptr: a caller-owned HBM buffer of weighted_unrolled_tape_doubles(**kw) doubles, or None / 0 for the
         handle's own weighted tape."""
-        p = self._taped_params(kw)
-        self._check(self._lib.bpltv_weighted_unrolled_denoise_device(self._h, C.c_void_p(w_ptr), int(wo),
-                                                                     C.c_void_p(alpha_ptr), int(am), int(an),
-                                                                     C.byref(p), C.c_void_p(tape_ptr or None)))
+        self._solve_device(_WEIGHTED_UNROLLED, alpha_ptr, am, an, kw, w_ptr=w_ptr, wo=wo, tape_ptr=tape_ptr)
 
     def weighted_unrolled_vjp(self, x, w, gu, want_f=True, want_alpha=True, want_w=True, **kw):
         """Vector-Jacobian product of the maxiter-step map u = weighted_unrolled_denoise(x, w) for the cotangent gu, by
         a reverse sweep over the handle's weighted tape (bpltv_weighted_unrolled_vjp): (grad_f, grad_x, grad_w).  x, w
         and the params must be those of the solve; w >= 0, zeros allowed.  grad_w has the shape of w -- for (N, M) the
         sum over the images; an output not wanted is None."""
-        if not (want_f or want_alpha or want_w):
-            raise ValueError("weighted_unrolled_vjp: want_f, want_alpha and want_w are all False")
-        a, am, an, scalar = _alpha_arg(x)
-        wa, wo = self._weight(w)
-        p = self._taped_params(kw)
-        gu = self._batch(gu, "gu")
-        gf = np.empty((self.O, self.N, self.M)) if want_f else None
-        ga = np.empty(am * an) if want_alpha else None
-        gw = np.empty(wa.shape) if want_w else None
-        self._check(self._lib.bpltv_weighted_unrolled_vjp(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p), _ptr(gu),
-                                                          _ptr(gf) if want_f else None,
-                                                          _ptr(ga) if want_alpha else None,
-                                                          _ptr(gw) if want_w else None))
-        if ga is not None:
-            ga = float(ga[0]) if scalar else ga.reshape(an, am)
-        return gf, ga, gw
+        return self._vjp(_WEIGHTED_UNROLLED, "weighted_unrolled_vjp", x, gu, (want_f, want_alpha, want_w), kw, w=w)
 
     def weighted_unrolled_vjp_device(self, tape_ptr, w_ptr, wo, alpha_ptr, am, an, gu_ptr, grad_f_ptr, grad_alpha_ptr,
                                      grad_w_ptr, **kw):
         """bpltv_weighted_unrolled_vjp_device: the tape (None / 0: the handle's own), w, the parameter, gu and the
         outputs resident in HBM (raw device pointers); any output pointer may be 0 / None, not all three."""
-        p = self._taped_params(kw)
-        self._check(self._lib.bpltv_weighted_unrolled_vjp_device(self._h, C.c_void_p(tape_ptr or None),
-                                                                 C.c_void_p(w_ptr), int(wo), C.c_void_p(alpha_ptr),
-                                                                 int(am), int(an), C.byref(p), C.c_void_p(gu_ptr),
-                                                                 C.c_void_p(grad_f_ptr or None),
-                                                                 C.c_void_p(grad_alpha_ptr or None),
-                                                                 C.c_void_p(grad_w_ptr or None)))
+        self._vjp_device(_WEIGHTED_UNROLLED, tape_ptr, alpha_ptr, am, an, gu_ptr, (grad_f_ptr, grad_alpha_ptr, grad_w_ptr), kw,
+                         w_ptr=w_ptr, wo=wo)
 
     # -- TV-L1: the data term w |u - f|, for impulse noise (bpltv_lone_*) ------------------------------------------
     # w >= 0, zeros allowed: (N, M) or (O, N, M).  The tape has the weighted tape's size: weighted_unrolled_tape_doubles.
@@ -737,65 +673,33 @@ class TVSolver:
         """TV-L1 denoising of the resident f (bpltv_lone_denoise): min sum w |u - f| + sum alpha |grad u|, maxiter iterations
         of the weighted recurrence with a soft threshold around f as the primal step.  Removes isolated outliers exactly
         and keeps the contrast of the rest.  No tape; u is bitwise l1_unrolled_denoise's."""
-        a, am, an, _ = _alpha_arg(x)
-        wa, wo = self._weight(w)
-        p = self.params(**kw)
-        u = np.empty((self.O, self.N, self.M)) if fetch else None
-        self._check(self._lib.bpltv_lone_denoise(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p), _ptr(u) if fetch else None))
-        return u
+        return self._solve(_L1, x, fetch, kw, w=w)
 
     def l1_denoise_device(self, w_ptr, wo, alpha_ptr, am=1, an=1, **kw):
         """bpltv_lone_denoise_device: w (wo planes) and the parameter resident in HBM, the result left there."""
-        p = self.params(**kw)
-        self._check(self._lib.bpltv_lone_denoise_device(self._h, C.c_void_p(w_ptr), int(wo), C.c_void_p(alpha_ptr), int(am),
-                                                      int(an), C.byref(p)))
+        self._solve_device(_L1, alpha_ptr, am, an, kw, w_ptr=w_ptr, wo=wo)
 
     def l1_unrolled_denoise(self, x, w, fetch=True, **kw):
         """l1_denoise(x, w) -- the same u bit for bit -- that also records the tape of the iterations in the handle, for
         l1_unrolled_vjp with the same x, w and params (bpltv_lone_unrolled_denoise)."""
-        a, am, an, _ = _alpha_arg(x)
-        wa, wo = self._weight(w)
-        p = self._taped_params(kw)
-        u = np.empty((self.O, self.N, self.M)) if fetch else None
-        self._check(self._lib.bpltv_lone_unrolled_denoise(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p),
-                                                        _ptr(u) if fetch else None))
-        return u
+        return self._solve(_L1_UNROLLED, x, fetch, kw, w=w)
 
     def l1_unrolled_denoise_device(self, w_ptr, wo, alpha_ptr, am=1, an=1, tape_ptr=None, **kw):
         """bpltv_lone_unrolled_denoise_device: w (wo planes) and the parameter resident in HBM, the result left there;
         tape_ptr: a caller-owned HBM buffer of weighted_unrolled_tape_doubles(**kw) doubles, or None / 0 for the handle's
         own L1 tape."""
-        p = self._taped_params(kw)
-        self._check(self._lib.bpltv_lone_unrolled_denoise_device(self._h, C.c_void_p(w_ptr), int(wo), C.c_void_p(alpha_ptr),
-                                                               int(am), int(an), C.byref(p), C.c_void_p(tape_ptr or None)))
+        self._solve_device(_L1_UNROLLED, alpha_ptr, am, an, kw, w_ptr=w_ptr, wo=wo, tape_ptr=tape_ptr)
 
     def l1_unrolled_vjp(self, x, w, gu, want_f=True, want_alpha=True, want_w=True, **kw):
         """Vector-Jacobian product of the maxiter-step map u = l1_unrolled_denoise(x, w) for the cotangent gu, by a reverse
         sweep over the handle's L1 tape (bpltv_lone_unrolled_vjp): (grad_f, grad_x, grad_w), as weighted_unrolled_vjp."""
-        if not (want_f or want_alpha or want_w):
-            raise ValueError("l1_unrolled_vjp: want_f, want_alpha and want_w are all False")
-        a, am, an, scalar = _alpha_arg(x)
-        wa, wo = self._weight(w)
-        p = self._taped_params(kw)
-        gu = self._batch(gu, "gu")
-        gf = np.empty((self.O, self.N, self.M)) if want_f else None
-        ga = np.empty(am * an) if want_alpha else None
-        gw = np.empty(wa.shape) if want_w else None
-        self._check(self._lib.bpltv_lone_unrolled_vjp(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p), _ptr(gu),
-                                                    _ptr(gf) if want_f else None, _ptr(ga) if want_alpha else None,
-                                                    _ptr(gw) if want_w else None))
-        if ga is not None:
-            ga = float(ga[0]) if scalar else ga.reshape(an, am)
-        return gf, ga, gw
+        return self._vjp(_L1_UNROLLED, "l1_unrolled_vjp", x, gu, (want_f, want_alpha, want_w), kw, w=w)
 
     def l1_unrolled_vjp_device(self, tape_ptr, w_ptr, wo, alpha_ptr, am, an, gu_ptr, grad_f_ptr, grad_alpha_ptr, grad_w_ptr, **kw):
         """bpltv_lone_unrolled_vjp_device: the tape (None / 0: the handle's own), w, the parameter, gu and the outputs resident
         in HBM (raw device pointers); any output pointer may be 0 / None, not all three."""
-        p = self._taped_params(kw)
-        self._check(self._lib.bpltv_lone_unrolled_vjp_device(self._h, C.c_void_p(tape_ptr or None), C.c_void_p(w_ptr), int(wo),
-                                                           C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p),
-                                                           C.c_void_p(gu_ptr), C.c_void_p(grad_f_ptr or None),
-                                                           C.c_void_p(grad_alpha_ptr or None), C.c_void_p(grad_w_ptr or None)))
+        self._vjp_device(_L1_UNROLLED, tape_ptr, alpha_ptr, am, an, gu_ptr, (grad_f_ptr, grad_alpha_ptr, grad_w_ptr), kw,
+                         w_ptr=w_ptr, wo=wo)
 
     # -- TV-KL: the data term w (u - f log u), for Poisson noise (bpltv_kl_*) ------------------------------------------
     # f finite and >= 0 (zero counts allowed); w >= 0, zeros allowed: (N, M) or (O, N, M).  The tape has the weighted tape's size.
@@ -803,65 +707,33 @@ class TVSolver:
         """TV-KL denoising of the resident f (bpltv_kl_denoise): min sum w (u - f log u) + sum alpha |grad u| over u >= 0,
         maxiter iterations of the weighted recurrence with the closed-form prox of the Kullback-Leibler divergence as the primal
         step.  The model for photon counts.  No tape; u is bitwise kl_unrolled_denoise's."""
-        a, am, an, _ = _alpha_arg(x)
-        wa, wo = self._weight(w)
-        p = self.params(**kw)
-        u = np.empty((self.O, self.N, self.M)) if fetch else None
-        self._check(self._lib.bpltv_kl_denoise(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p), _ptr(u) if fetch else None))
-        return u
+        return self._solve(_KL, x, fetch, kw, w=w)
 
     def kl_denoise_device(self, w_ptr, wo, alpha_ptr, am=1, an=1, **kw):
         """bpltv_kl_denoise_device: w (wo planes) and the parameter resident in HBM, the result left there."""
-        p = self.params(**kw)
-        self._check(self._lib.bpltv_kl_denoise_device(self._h, C.c_void_p(w_ptr), int(wo), C.c_void_p(alpha_ptr), int(am),
-                                                      int(an), C.byref(p)))
+        self._solve_device(_KL, alpha_ptr, am, an, kw, w_ptr=w_ptr, wo=wo)
 
     def kl_unrolled_denoise(self, x, w, fetch=True, **kw):
         """kl_denoise(x, w) -- the same u bit for bit -- that also records the tape of the iterations in the handle, for
         kl_unrolled_vjp with the same x, w and params (bpltv_kl_unrolled_denoise)."""
-        a, am, an, _ = _alpha_arg(x)
-        wa, wo = self._weight(w)
-        p = self._taped_params(kw)
-        u = np.empty((self.O, self.N, self.M)) if fetch else None
-        self._check(self._lib.bpltv_kl_unrolled_denoise(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p),
-                                                        _ptr(u) if fetch else None))
-        return u
+        return self._solve(_KL_UNROLLED, x, fetch, kw, w=w)
 
     def kl_unrolled_denoise_device(self, w_ptr, wo, alpha_ptr, am=1, an=1, tape_ptr=None, **kw):
         """bpltv_kl_unrolled_denoise_device: w (wo planes) and the parameter resident in HBM, the result left there;
         tape_ptr: a caller-owned HBM buffer of weighted_unrolled_tape_doubles(**kw) doubles, or None / 0 for the handle's
         own KL tape."""
-        p = self._taped_params(kw)
-        self._check(self._lib.bpltv_kl_unrolled_denoise_device(self._h, C.c_void_p(w_ptr), int(wo), C.c_void_p(alpha_ptr),
-                                                               int(am), int(an), C.byref(p), C.c_void_p(tape_ptr or None)))
+        self._solve_device(_KL_UNROLLED, alpha_ptr, am, an, kw, w_ptr=w_ptr, wo=wo, tape_ptr=tape_ptr)
 
     def kl_unrolled_vjp(self, x, w, gu, want_f=True, want_alpha=True, want_w=True, **kw):
         """Vector-Jacobian product of the maxiter-step map u = kl_unrolled_denoise(x, w) for the cotangent gu, by a reverse
         sweep over the handle's KL tape (bpltv_kl_unrolled_vjp): (grad_f, grad_x, grad_w), as weighted_unrolled_vjp."""
-        if not (want_f or want_alpha or want_w):
-            raise ValueError("kl_unrolled_vjp: want_f, want_alpha and want_w are all False")
-        a, am, an, scalar = _alpha_arg(x)
-        wa, wo = self._weight(w)
-        p = self._taped_params(kw)
-        gu = self._batch(gu, "gu")
-        gf = np.empty((self.O, self.N, self.M)) if want_f else None
-        ga = np.empty(am * an) if want_alpha else None
-        gw = np.empty(wa.shape) if want_w else None
-        self._check(self._lib.bpltv_kl_unrolled_vjp(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p), _ptr(gu),
-                                                    _ptr(gf) if want_f else None, _ptr(ga) if want_alpha else None,
-                                                    _ptr(gw) if want_w else None))
-        if ga is not None:
-            ga = float(ga[0]) if scalar else ga.reshape(an, am)
-        return gf, ga, gw
+        return self._vjp(_KL_UNROLLED, "kl_unrolled_vjp", x, gu, (want_f, want_alpha, want_w), kw, w=w)
 
     def kl_unrolled_vjp_device(self, tape_ptr, w_ptr, wo, alpha_ptr, am, an, gu_ptr, grad_f_ptr, grad_alpha_ptr, grad_w_ptr, **kw):
         """bpltv_kl_unrolled_vjp_device: the tape (None / 0: the handle's own), w, the parameter, gu and the outputs resident
         in HBM (raw device pointers); any output pointer may be 0 / None, not all three."""
-        p = self._taped_params(kw)
-        self._check(self._lib.bpltv_kl_unrolled_vjp_device(self._h, C.c_void_p(tape_ptr or None), C.c_void_p(w_ptr), int(wo),
-                                                           C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p),
-                                                           C.c_void_p(gu_ptr), C.c_void_p(grad_f_ptr or None),
-                                                           C.c_void_p(grad_alpha_ptr or None), C.c_void_p(grad_w_ptr or None)))
+        self._vjp_device(_KL_UNROLLED, tape_ptr, alpha_ptr, am, an, gu_ptr, (grad_f_ptr, grad_alpha_ptr, grad_w_ptr), kw,
+                         w_ptr=w_ptr, wo=wo)
 
     # -- forward mode (bpltv_jvp / bpltv_gauss_newton) -------------------------------------------------------
     def _tangents(self, what, df, dalpha, ashape):
@@ -904,58 +776,27 @@ class TVSolver:
         whose transpose vjp computes.  df: (O, N, M), or (K, O, N, M) for K directions solved against one
         factorisation; dalpha: shaped like x, or with a leading K; either may be None (zero), not both.  Returns du
         of shape (O, N, M), or (K, O, N, M) when a leading K was given."""
-        a, am, an, scalar = _alpha_arg(x)
-        df, dalpha, K, batched = self._tangents("jvp", df, dalpha, () if scalar else (an, am))
-        p = self.params(**kw)
-        u = self._batch(u, "u")
-        du = np.empty((K, self.O, self.N, self.M))
-        self._check(self._lib.bpltv_jvp(self._h, _ptr(u), _ptr(a), am, an, int(bool(reg)), C.byref(p), K,
-                                        _ptr(df) if df is not None else None,
-                                        _ptr(dalpha) if dalpha is not None else None, _ptr(du)))
-        return du if batched else du[0]
+        return self._jvp(_TV, "jvp", x, df, dalpha, kw, u=u, reg=reg)
 
     def jvp_device(self, u_ptr, alpha_ptr, am, an, df_ptr, dalpha_ptr, du_ptr, ndir=1, reg=False, **kw):
         """bpltv_jvp_device: u (M*N*O doubles), the parameter (am*an), df and du (ndir*M*N*O) and dalpha (ndir*am*an)
         all resident in HBM (raw device pointers); either tangent pointer may be 0 / None, not both."""
-        p = self.params(**kw)
-        self._check(self._lib.bpltv_jvp_device(self._h, C.c_void_p(u_ptr), C.c_void_p(alpha_ptr), int(am), int(an),
-                                               int(bool(reg)), C.byref(p), int(ndir), C.c_void_p(df_ptr or None),
-                                               C.c_void_p(dalpha_ptr or None), C.c_void_p(du_ptr)))
+        self._jvp_device(_TV, alpha_ptr, am, an, (df_ptr, dalpha_ptr), du_ptr, ndir, kw, u_ptr=u_ptr, reg=reg)
 
     def jvp_each(self, u, alphas, df=None, dalphas=None, reg=False, **kw):
         """jvp with image k's own parameter alphas[k] (bpltv_jvp_each).  dalphas: shaped like alphas, or with a leading
         K; df and the result as in jvp."""
-        a, am, an = self._each_arg(alphas)
-        df, dalphas, K, batched = self._tangents("jvp_each", df, dalphas, a.shape)
-        p = self.params(**kw)
-        u = self._batch(u, "u")
-        du = np.empty((K, self.O, self.N, self.M))
-        self._check(self._lib.bpltv_jvp_each(self._h, _ptr(u), _ptr(a), am, an, int(bool(reg)), C.byref(p), K,
-                                             _ptr(df) if df is not None else None,
-                                             _ptr(dalphas) if dalphas is not None else None, _ptr(du)))
-        return du if batched else du[0]
+        return self._jvp(_TV_EACH, "jvp_each", alphas, df, dalphas, kw, u=u, reg=reg)
 
     def jvp_each_device(self, u_ptr, alphas_ptr, am, an, df_ptr, dalphas_ptr, du_ptr, ndir=1, reg=False, **kw):
         """bpltv_jvp_each_device: as jvp_device with O parameter blocks (O*am*an doubles) and ndir*O tangent blocks."""
-        p = self.params(**kw)
-        self._check(self._lib.bpltv_jvp_each_device(self._h, C.c_void_p(u_ptr), C.c_void_p(alphas_ptr), int(am),
-                                                    int(an), int(bool(reg)), C.byref(p), int(ndir),
-                                                    C.c_void_p(df_ptr or None), C.c_void_p(dalphas_ptr or None),
-                                                    C.c_void_p(du_ptr)))
+        self._jvp_device(_TV_EACH, alphas_ptr, am, an, (df_ptr, dalphas_ptr), du_ptr, ndir, kw, u_ptr=u_ptr, reg=reg)
 
     def gauss_newton(self, u, ubar, x, reg=False, **kw):
         """Gauss-Newton model of 0.5||u(x) - ubar||^2 (bpltv_gauss_newton): (grad, H) with grad = J^T (u - ubar) shaped
         like x and H = J^T J of shape (P, P), P = x.size, ordered as x's column-major (Julia) entries -- numpy's
         x.ravel().  A float or an (n, m) patch parameter with at most 16 entries."""
-        a, am, an, scalar = _alpha_arg(x)
-        p = self.params(**kw)
-        u = self._batch(u, "u")
-        ubar = self._batch(ubar, "ubar")
-        P = am * an
-        grad, H = np.empty(P), np.empty((P, P))
-        self._check(self._lib.bpltv_gauss_newton(self._h, _ptr(u), _ptr(ubar), _ptr(a), am, an, int(bool(reg)),
-                                                 C.byref(p), _ptr(grad), _ptr(H)))
-        return (float(grad[0]) if scalar else grad.reshape(an, am)), H
+        return self._gauss_newton(_TV, x, kw, u=u, ubar=ubar, reg=reg)
 
     # -- forward mode through the iterations (bpltv_unrolled_jvp / bpltv_unrolled_gauss_newton) ---------------
     def unrolled_jvp(self, x, df=None, dalpha=None, want_u=False, **kw):
@@ -964,89 +805,22 @@ class TVSolver:
         (O, N, M), or (K, O, N, M) for K directions; dalpha: shaped like x, or with a leading K; either may be None
         (zero), not both.  Returns du of shape (O, N, M), or (K, O, N, M) when a leading K was given; with want_u,
         (du, u) with u = denoise(x) bit for bit."""
-        a, am, an, scalar = _alpha_arg(x)
-        df, dalpha, K, batched = self._tangents("unrolled_jvp", df, dalpha, () if scalar else (an, am))
-        p = self.params(**kw)
-        du = np.empty((K, self.O, self.N, self.M))
-        u = np.empty((self.O, self.N, self.M)) if want_u else None
-        self._check(self._lib.bpltv_unrolled_jvp(self._h, _ptr(a), am, an, C.byref(p), K,
-                                                 _ptr(df) if df is not None else None,
-                                                 _ptr(dalpha) if dalpha is not None else None, _ptr(du),
-                                                 _ptr(u) if want_u else None))
-        du = du if batched else du[0]
-        return (du, u) if want_u else du
+        return self._jvp(_UNROLLED, "unrolled_jvp", x, df, dalpha, kw, want_u=want_u)
 
     def unrolled_jvp_device(self, alpha_ptr, am, an, df_ptr, dalpha_ptr, du_ptr, u_ptr=None, ndir=1, **kw):
         """bpltv_unrolled_jvp_device: the parameter (am*an doubles), df and du (ndir*M*N*O), dalpha (ndir*am*an) and u
         (M*N*O) all resident in HBM (raw device pointers); either tangent pointer may be 0 / None, not both; u_ptr may
         be 0 / None."""
-        p = self.params(**kw)
-        self._check(self._lib.bpltv_unrolled_jvp_device(self._h, C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p),
-                                                        int(ndir), C.c_void_p(df_ptr or None),
-                                                        C.c_void_p(dalpha_ptr or None), C.c_void_p(du_ptr),
-                                                        C.c_void_p(u_ptr or None)))
+        self._jvp_device(_UNROLLED, alpha_ptr, am, an, (df_ptr, dalpha_ptr), du_ptr, ndir, kw, u_ptr=u_ptr)
 
     def unrolled_gauss_newton(self, x, **kw):
         """Gauss-Newton model of the maxiter-step loss 0.5||u_K(x) - ubar||^2 on the resident dataset
         (bpltv_unrolled_gauss_newton): (cost, grad, H) with grad = J^T (u_K - ubar) shaped like x and H = J^T J of shape
         (P, P), P = x.size, ordered as numpy's x.ravel(); J by P tangent sweeps.  A float or an (n, m) patch parameter
         with at most 16 entries."""
-        a, am, an, scalar = _alpha_arg(x)
-        p = self.params(**kw)
-        P = am * an
-        cost, grad, H = C.c_double(0.0), np.empty(P), np.empty((P, P))
-        self._check(self._lib.bpltv_unrolled_gauss_newton(self._h, _ptr(a), am, an, C.byref(p),
-                                                          C.byref(cost), _ptr(grad), _ptr(H)))
-        return float(cost.value), (float(grad[0]) if scalar else grad.reshape(an, am)), H
+        return self._gauss_newton(_UNROLLED, x, kw)
 
     # -- forward mode through the weighted iterations (bpltv_weighted_unrolled_jvp / _gauss_newton) -----------
-    def _weighted_jvp(self, what, fn, x, w, df, dalpha, dw, want_u, kw):
-        """weighted_unrolled_jvp and its TV-L1 / TV-KL twins: the tangents as stacks of K directions, one call of fn."""
-        a, am, an, scalar = _alpha_arg(x)
-        wa, wo = self._weight(w)
-        if df is None and dalpha is None and dw is None:
-            raise ValueError("%s: df, dalpha and dw are all None" % what)
-        K, batched = None, False
-        if df is not None or dalpha is not None:
-            df, dalpha, K, batched = self._tangents(what, df, dalpha, () if scalar else (an, am))
-        if dw is not None:
-            dw = np.ascontiguousarray(dw, dtype=np.float64)
-            if dw.shape == wa.shape:
-                dw = dw[None]
-            elif dw.shape[1:] == wa.shape:
-                batched = True
-            else:
-                raise ValueError("%s: dw has shape %s, expected %s or (K,) + %s" % (what, dw.shape, wa.shape, wa.shape))
-            if K is None:
-                K = dw.shape[0]
-            if K < 1 or dw.shape[0] != K:
-                raise ValueError("%s: the tangents hold different numbers of directions" % what)
-        p = self.params(**kw)
-        du = np.empty((K, self.O, self.N, self.M))
-        u = np.empty((self.O, self.N, self.M)) if want_u else None
-        self._check(fn(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p), K,
-                       _ptr(df) if df is not None else None,
-                       _ptr(dalpha) if dalpha is not None else None,
-                       _ptr(dw) if dw is not None else None, _ptr(du),
-                       _ptr(u) if want_u else None))
-        du = du if batched else du[0]
-        return (du, u) if want_u else du
-
-    def _weighted_jvp_device(self, fn, w_ptr, wo, alpha_ptr, am, an, df_ptr, dalpha_ptr, dw_ptr, du_ptr, u_ptr, ndir, kw):
-        p = self.params(**kw)
-        self._check(fn(self._h, C.c_void_p(w_ptr), int(wo), C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p), int(ndir),
-                       C.c_void_p(df_ptr or None), C.c_void_p(dalpha_ptr or None), C.c_void_p(dw_ptr or None),
-                       C.c_void_p(du_ptr), C.c_void_p(u_ptr or None)))
-
-    def _weighted_gauss_newton(self, fn, x, w, kw):
-        a, am, an, scalar = _alpha_arg(x)
-        wa, wo = self._weight(w)
-        p = self.params(**kw)
-        P = am * an
-        cost, grad, H = C.c_double(0.0), np.empty(P), np.empty((P, P))
-        self._check(fn(self._h, _ptr(wa), wo, _ptr(a), am, an, C.byref(p), C.byref(cost), _ptr(grad), _ptr(H)))
-        return float(cost.value), (float(grad[0]) if scalar else grad.reshape(an, am)), H
-
     def weighted_unrolled_jvp(self, x, w, df=None, dalpha=None, dw=None, want_u=False, **kw):
         """Jacobian-vector product of the maxiter-step map u = weighted_unrolled_denoise(x, w) of the resident f
         (bpltv_weighted_unrolled_jvp): a tangent sweep through the weighted iterations, no tape -- the linear map whose
@@ -1054,21 +828,21 @@ class TVSolver:
         directions; dalpha: shaped like x, or with a leading K; dw: shaped like w, or with a leading K; any may be None
         (zero), not all three.  Returns du of shape (O, N, M), or (K, O, N, M) when a leading K was given; with want_u,
         (du, u) with u = weighted_denoise(x, w) bit for bit.  The step table (gamma = min w) is held fixed."""
-        return self._weighted_jvp("weighted_unrolled_jvp", self._lib.bpltv_weighted_unrolled_jvp, x, w, df, dalpha, dw, want_u, kw)
+        return self._jvp(_WEIGHTED_UNROLLED, "weighted_unrolled_jvp", x, df, dalpha, kw, w=w, dw=dw, want_u=want_u)
 
     def weighted_unrolled_jvp_device(self, w_ptr, wo, alpha_ptr, am, an, df_ptr, dalpha_ptr, dw_ptr, du_ptr, u_ptr=None,
                                      ndir=1, **kw):
         """bpltv_weighted_unrolled_jvp_device: w (wo planes), the parameter (am*an doubles), df and du (ndir*M*N*O), dalpha
         (ndir*am*an), dw (ndir*M*N*wo) and u (M*N*O) all resident in HBM (raw device pointers); any tangent pointer may be
         0 / None, not all three; u_ptr may be 0 / None."""
-        self._weighted_jvp_device(self._lib.bpltv_weighted_unrolled_jvp_device, w_ptr, wo, alpha_ptr, am, an, df_ptr, dalpha_ptr,
-                                  dw_ptr, du_ptr, u_ptr, ndir, kw)
+        self._jvp_device(_WEIGHTED_UNROLLED, alpha_ptr, am, an, (df_ptr, dalpha_ptr, dw_ptr), du_ptr, ndir, kw, w_ptr=w_ptr,
+                         wo=wo, u_ptr=u_ptr)
 
     def weighted_unrolled_gauss_newton(self, x, w, **kw):
         """Gauss-Newton model of the maxiter-step loss 0.5||u_K(x) - ubar||^2 of the weighted iterations on the resident
         dataset (bpltv_weighted_unrolled_gauss_newton): (cost, grad, H) as unrolled_gauss_newton's, J by P tangent sweeps
         in the parameter.  A float or an (n, m) patch parameter with at most 16 entries; w >= 0, zeros allowed."""
-        return self._weighted_gauss_newton(self._lib.bpltv_weighted_unrolled_gauss_newton, x, w, kw)
+        return self._gauss_newton(_WEIGHTED_UNROLLED, x, kw, w=w)
 
     # -- forward mode through the TV-L1 and the TV-KL iterations (bpltv_lone_unrolled_jvp, bpltv_kl_unrolled_jvp) -----
     def l1_unrolled_jvp(self, x, w, df=None, dalpha=None, dw=None, want_u=False, **kw):
@@ -1076,34 +850,34 @@ class TVSolver:
         tangent sweep through the TV-L1 iterations, no tape -- the linear map whose transpose l1_unrolled_vjp computes, with
         its conventions (a pixel held at f moves with f alone).  Arguments and result as weighted_unrolled_jvp; with want_u,
         (du, u) with u = l1_denoise(x, w) bit for bit."""
-        return self._weighted_jvp("l1_unrolled_jvp", self._lib.bpltv_lone_unrolled_jvp, x, w, df, dalpha, dw, want_u, kw)
+        return self._jvp(_L1_UNROLLED, "l1_unrolled_jvp", x, df, dalpha, kw, w=w, dw=dw, want_u=want_u)
 
     def l1_unrolled_jvp_device(self, w_ptr, wo, alpha_ptr, am, an, df_ptr, dalpha_ptr, dw_ptr, du_ptr, u_ptr=None, ndir=1, **kw):
         """bpltv_lone_unrolled_jvp_device: everything resident in HBM (raw device pointers), as weighted_unrolled_jvp_device."""
-        self._weighted_jvp_device(self._lib.bpltv_lone_unrolled_jvp_device, w_ptr, wo, alpha_ptr, am, an, df_ptr, dalpha_ptr,
-                                  dw_ptr, du_ptr, u_ptr, ndir, kw)
+        self._jvp_device(_L1_UNROLLED, alpha_ptr, am, an, (df_ptr, dalpha_ptr, dw_ptr), du_ptr, ndir, kw, w_ptr=w_ptr, wo=wo,
+                         u_ptr=u_ptr)
 
     def l1_unrolled_gauss_newton(self, x, w, **kw):
         """Gauss-Newton model of the maxiter-step loss 0.5||u_K(x) - ubar||^2 of the TV-L1 iterations on the resident dataset
         (bpltv_lone_unrolled_gauss_newton): (cost, grad, H) as weighted_unrolled_gauss_newton's."""
-        return self._weighted_gauss_newton(self._lib.bpltv_lone_unrolled_gauss_newton, x, w, kw)
+        return self._gauss_newton(_L1_UNROLLED, x, kw, w=w)
 
     def kl_unrolled_jvp(self, x, w, df=None, dalpha=None, dw=None, want_u=False, **kw):
         """Jacobian-vector product of the maxiter-step map u = kl_denoise(x, w) of the resident f >= 0 (bpltv_kl_unrolled_jvp): a
         tangent sweep through the TV-KL iterations, no tape -- the linear map whose transpose kl_unrolled_vjp computes, with
         its convention (a pixel clamped at zero passes nothing).  Arguments and result as weighted_unrolled_jvp; with want_u,
         (du, u) with u = kl_denoise(x, w) bit for bit."""
-        return self._weighted_jvp("kl_unrolled_jvp", self._lib.bpltv_kl_unrolled_jvp, x, w, df, dalpha, dw, want_u, kw)
+        return self._jvp(_KL_UNROLLED, "kl_unrolled_jvp", x, df, dalpha, kw, w=w, dw=dw, want_u=want_u)
 
     def kl_unrolled_jvp_device(self, w_ptr, wo, alpha_ptr, am, an, df_ptr, dalpha_ptr, dw_ptr, du_ptr, u_ptr=None, ndir=1, **kw):
         """bpltv_kl_unrolled_jvp_device: everything resident in HBM (raw device pointers), as weighted_unrolled_jvp_device."""
-        self._weighted_jvp_device(self._lib.bpltv_kl_unrolled_jvp_device, w_ptr, wo, alpha_ptr, am, an, df_ptr, dalpha_ptr,
-                                  dw_ptr, du_ptr, u_ptr, ndir, kw)
+        self._jvp_device(_KL_UNROLLED, alpha_ptr, am, an, (df_ptr, dalpha_ptr, dw_ptr), du_ptr, ndir, kw, w_ptr=w_ptr, wo=wo,
+                         u_ptr=u_ptr)
 
     def kl_unrolled_gauss_newton(self, x, w, **kw):
         """Gauss-Newton model of the maxiter-step loss 0.5||u_K(x) - ubar||^2 of the TV-KL iterations on the resident dataset
         (bpltv_kl_unrolled_gauss_newton): (cost, grad, H) as weighted_unrolled_gauss_newton's."""
-        return self._weighted_gauss_newton(self._lib.bpltv_kl_unrolled_gauss_newton, x, w, kw)
+        return self._gauss_newton(_KL_UNROLLED, x, kw, w=w)
 
     # -- one parameter per image (bpltv_denoise_each / bpltv_vjp_each) ---------------------------------------
     def _each_arg(self, alphas):
@@ -1122,106 +896,54 @@ class TVSolver:
     def denoise_each(self, alphas, fetch=True, **kw):
         """denoise with image k's own parameter alphas[k] (bpltv_denoise_each); u[k] is bitwise a one-image solve of
         (f[k], alphas[k])."""
-        a, am, an = self._each_arg(alphas)
-        p = self.params(**kw)
-        u = np.empty((self.O, self.N, self.M)) if fetch else None
-        self._check(self._lib.bpltv_denoise_each(self._h, _ptr(a), am, an, C.byref(p), _ptr(u) if fetch else None))
-        return u
+        return self._solve(_TV_EACH, alphas, fetch, kw)
 
     def denoise_each_device(self, alphas_ptr, am=1, an=1, **kw):
         """bpltv_denoise_each_device: O parameter blocks (O*am*an doubles, block k column major at k*am*an) resident in
         HBM at `alphas_ptr`; the result stays on the device (u_device_ptr / copy_u_device)."""
-        p = self.params(**kw)
-        self._check(self._lib.bpltv_denoise_each_device(self._h, C.c_void_p(alphas_ptr), int(am), int(an), C.byref(p)))
+        self._solve_device(_TV_EACH, alphas_ptr, am, an, kw)
 
     def vjp_each(self, u, alphas, gu, reg=False, want_f=True, want_alpha=True, **kw):
         """vjp with image k's own parameter alphas[k] (bpltv_vjp_each): (grad_f, grad_alphas).  grad_alphas has the shape
         of alphas; grad_alphas[k] is image k's term alone, not summed over the images."""
-        if not (want_f or want_alpha):
-            raise ValueError("vjp_each: want_f and want_alpha are both False")
-        a, am, an = self._each_arg(alphas)
-        p = self.params(**kw)
-        u = self._batch(u, "u")
-        gu = self._batch(gu, "gu")
-        gf = np.empty((self.O, self.N, self.M)) if want_f else None
-        ga = np.empty(a.shape) if want_alpha else None
-        self._check(self._lib.bpltv_vjp_each(self._h, _ptr(u), _ptr(a), am, an, int(bool(reg)), C.byref(p), _ptr(gu),
-                                             _ptr(gf) if want_f else None, _ptr(ga) if want_alpha else None))
-        return gf, ga
+        return self._vjp(_TV_EACH, "vjp_each", alphas, gu, (want_f, want_alpha), kw, u=u, reg=reg)
 
     def vjp_each_device(self, u_ptr, alphas_ptr, am, an, gu_ptr, grad_f_ptr, grad_alphas_ptr, reg=False, **kw):
         """bpltv_vjp_each_device: u, gu and grad_f (M*N*O doubles), the O parameter blocks and their O gradients
         (O*am*an doubles each) all resident in HBM; either output pointer may be 0 / None, not both."""
-        p = self.params(**kw)
-        self._check(self._lib.bpltv_vjp_each_device(self._h, C.c_void_p(u_ptr), C.c_void_p(alphas_ptr), int(am),
-                                                    int(an), int(bool(reg)), C.byref(p), C.c_void_p(gu_ptr),
-                                                    C.c_void_p(grad_f_ptr or None), C.c_void_p(grad_alphas_ptr or None)))
+        self._vjp_device(_TV_EACH, u_ptr, alphas_ptr, am, an, gu_ptr, (grad_f_ptr, grad_alphas_ptr), kw, reg=reg)
 
     # -- one parameter per image through the iterations (bpltv_unrolled_*_each) ----------------------------------
     def unrolled_denoise_each(self, alphas, fetch=True, **kw):
         """unrolled_denoise with image k's own parameter alphas[k] (bpltv_unrolled_denoise_each): denoise_each's u bit for
         bit, and the handle's tape, recorded per image, for unrolled_vjp_each with the same alphas and params."""
-        a, am, an = self._each_arg(alphas)
-        p = self._taped_params(kw)
-        u = np.empty((self.O, self.N, self.M)) if fetch else None
-        self._check(self._lib.bpltv_unrolled_denoise_each(self._h, _ptr(a), am, an, C.byref(p),
-                                                          _ptr(u) if fetch else None))
-        return u
+        return self._solve(_UNROLLED_EACH, alphas, fetch, kw)
 
     def unrolled_denoise_each_device(self, alphas_ptr, am=1, an=1, tape_ptr=None, **kw):
         """bpltv_unrolled_denoise_each_device: O parameter blocks (O*am*an doubles, block k column major at k*am*an)
         resident in HBM, the result left there; tape_ptr as in unrolled_denoise_device."""
-        p = self._taped_params(kw)
-        self._check(self._lib.bpltv_unrolled_denoise_each_device(self._h, C.c_void_p(alphas_ptr), int(am), int(an),
-                                                                 C.byref(p), C.c_void_p(tape_ptr or None)))
+        self._solve_device(_UNROLLED_EACH, alphas_ptr, am, an, kw, tape_ptr=tape_ptr)
 
     def unrolled_vjp_each(self, alphas, gu, want_f=True, want_alpha=True, **kw):
         """unrolled_vjp with image k's own parameter alphas[k], over the handle's per-image tape
         (bpltv_unrolled_vjp_each): (grad_f, grad_alphas).  grad_alphas has the shape of alphas; grad_alphas[k] is image
         k's term alone, not summed over the images."""
-        if not (want_f or want_alpha):
-            raise ValueError("unrolled_vjp_each: want_f and want_alpha are both False")
-        a, am, an = self._each_arg(alphas)
-        p = self._taped_params(kw)
-        gu = self._batch(gu, "gu")
-        gf = np.empty((self.O, self.N, self.M)) if want_f else None
-        ga = np.empty(a.shape) if want_alpha else None
-        self._check(self._lib.bpltv_unrolled_vjp_each(self._h, _ptr(a), am, an, C.byref(p), _ptr(gu),
-                                                      _ptr(gf) if want_f else None, _ptr(ga) if want_alpha else None))
-        return gf, ga
+        return self._vjp(_UNROLLED_EACH, "unrolled_vjp_each", alphas, gu, (want_f, want_alpha), kw)
 
     def unrolled_vjp_each_device(self, tape_ptr, alphas_ptr, am, an, gu_ptr, grad_f_ptr, grad_alphas_ptr, **kw):
         """bpltv_unrolled_vjp_each_device: as unrolled_vjp_device with O parameter blocks and their O gradients (O*am*an
         doubles each) resident in HBM; either output pointer may be 0 / None, not both."""
-        p = self._taped_params(kw)
-        self._check(self._lib.bpltv_unrolled_vjp_each_device(self._h, C.c_void_p(tape_ptr or None),
-                                                             C.c_void_p(alphas_ptr), int(am), int(an), C.byref(p),
-                                                             C.c_void_p(gu_ptr), C.c_void_p(grad_f_ptr or None),
-                                                             C.c_void_p(grad_alphas_ptr or None)))
+        self._vjp_device(_UNROLLED_EACH, tape_ptr, alphas_ptr, am, an, gu_ptr, (grad_f_ptr, grad_alphas_ptr), kw)
 
     def unrolled_jvp_each(self, alphas, df=None, dalphas=None, want_u=False, **kw):
         """unrolled_jvp with image k's own parameter alphas[k] (bpltv_unrolled_jvp_each).  dalphas: shaped like alphas,
         or with a leading K; df, want_u and the result as in unrolled_jvp (u = denoise_each(alphas) bit for bit)."""
-        a, am, an = self._each_arg(alphas)
-        df, dalphas, K, batched = self._tangents("unrolled_jvp_each", df, dalphas, a.shape)
-        p = self.params(**kw)
-        du = np.empty((K, self.O, self.N, self.M))
-        u = np.empty((self.O, self.N, self.M)) if want_u else None
-        self._check(self._lib.bpltv_unrolled_jvp_each(self._h, _ptr(a), am, an, C.byref(p), K,
-                                                      _ptr(df) if df is not None else None,
-                                                      _ptr(dalphas) if dalphas is not None else None, _ptr(du),
-                                                      _ptr(u) if want_u else None))
-        du = du if batched else du[0]
-        return (du, u) if want_u else du
+        return self._jvp(_UNROLLED_EACH, "unrolled_jvp_each", alphas, df, dalphas, kw, want_u=want_u)
 
     def unrolled_jvp_each_device(self, alphas_ptr, am, an, df_ptr, dalphas_ptr, du_ptr, u_ptr=None, ndir=1, **kw):
         """bpltv_unrolled_jvp_each_device: as unrolled_jvp_device with O parameter blocks (O*am*an doubles) and ndir*O
         tangent blocks, direction first."""
-        p = self.params(**kw)
-        self._check(self._lib.bpltv_unrolled_jvp_each_device(self._h, C.c_void_p(alphas_ptr), int(am), int(an),
-                                                             C.byref(p), int(ndir), C.c_void_p(df_ptr or None),
-                                                             C.c_void_p(dalphas_ptr or None), C.c_void_p(du_ptr),
-                                                             C.c_void_p(u_ptr or None)))
+        self._jvp_device(_UNROLLED_EACH, alphas_ptr, am, an, (df_ptr, dalphas_ptr), du_ptr, ndir, kw, u_ptr=u_ptr)
 
     # -- one block of three weights per image (bpltv_sumregs_denoise_each / bpltv_sumregs_vjp_each) ---------------
     def _sr_each_arg(self, alphas):
@@ -1241,164 +963,82 @@ class TVSolver:
     def sumregs_denoise_each(self, alphas, fetch=True, **kw):
         """sumregs_denoise with image k's own three weights alphas[k] (bpltv_sumregs_denoise_each); u[k] is bitwise a
         one-image solve of (f[k], alphas[k])."""
-        a, am, an = self._sr_each_arg(alphas)
-        p = self.params(_sumregs=True, **kw)
-        u = np.empty((self.O, self.N, self.M)) if fetch else None
-        self._check(self._lib.bpltv_sumregs_denoise_each(self._h, _ptr(a), am, an, C.byref(p),
-                                                         _ptr(u) if fetch else None))
-        return u
+        return self._solve(_SUMREGS_EACH, alphas, fetch, kw)
 
     def sumregs_denoise_each_device(self, alphas_ptr, am=1, an=1, **kw):
         """bpltv_sumregs_denoise_each_device: O parameter blocks (O*3*am*an doubles, a C-contiguous (O, 3, an, am)
         array) resident in HBM at `alphas_ptr`; the result stays on the device (u_device_ptr / copy_u_device)."""
-        p = self.params(_sumregs=True, **kw)
-        self._check(self._lib.bpltv_sumregs_denoise_each_device(self._h, C.c_void_p(alphas_ptr), int(am), int(an),
-                                                                C.byref(p)))
+        self._solve_device(_SUMREGS_EACH, alphas_ptr, am, an, kw)
 
     def sumregs_vjp_each(self, u, alphas, gu, reg=False, want_f=True, want_alpha=True, **kw):
         """sumregs_vjp with image k's own block alphas[k] (bpltv_sumregs_vjp_each): (grad_f, grad_alphas).  grad_alphas
         has the shape of alphas; grad_alphas[k] is image k's term alone, not summed over the images."""
-        if not (want_f or want_alpha):
-            raise ValueError("sumregs_vjp_each: want_f and want_alpha are both False")
-        a, am, an = self._sr_each_arg(alphas)
-        u = self._batch(u, "u")
-        gu = self._batch(gu, "gu")
-        p = self.params(_sumregs=True, **kw)
-        gf = np.empty((self.O, self.N, self.M)) if want_f else None
-        ga = np.empty(a.shape) if want_alpha else None
-        self._check(self._lib.bpltv_sumregs_vjp_each(self._h, _ptr(u), _ptr(a), am, an, int(bool(reg)), C.byref(p),
-                                                     _ptr(gu), _ptr(gf) if want_f else None,
-                                                     _ptr(ga) if want_alpha else None))
-        return gf, ga
+        return self._vjp(_SUMREGS_EACH, "sumregs_vjp_each", alphas, gu, (want_f, want_alpha), kw, u=u, reg=reg,
+                         arrays_first=True)
 
     def sumregs_vjp_each_device(self, u_ptr, alphas_ptr, am, an, gu_ptr, grad_f_ptr, grad_alphas_ptr, reg=False, **kw):
         """bpltv_sumregs_vjp_each_device: u, gu and grad_f (M*N*O doubles), the O parameter blocks and their O gradients
         (O*3*am*an doubles each) all resident in HBM; either output pointer may be 0 / None, not both."""
-        p = self.params(_sumregs=True, **kw)
-        self._check(self._lib.bpltv_sumregs_vjp_each_device(self._h, C.c_void_p(u_ptr), C.c_void_p(alphas_ptr), int(am),
-                                                            int(an), int(bool(reg)), C.byref(p), C.c_void_p(gu_ptr),
-                                                            C.c_void_p(grad_f_ptr or None),
-                                                            C.c_void_p(grad_alphas_ptr or None)))
+        self._vjp_device(_SUMREGS_EACH, u_ptr, alphas_ptr, am, an, gu_ptr, (grad_f_ptr, grad_alphas_ptr), kw, reg=reg)
 
     def sumregs_jvp_each(self, u, alphas, df=None, dalphas=None, reg=False, **kw):
         """sumregs_jvp with image k's own block alphas[k] (bpltv_sumregs_jvp_each).  dalphas: shaped like alphas, or
         with a leading K; df and the result as in sumregs_jvp."""
-        a, am, an = self._sr_each_arg(alphas)
-        df, dalphas, K, batched = self._tangents("sumregs_jvp_each", df, dalphas, a.shape)
-        p = self.params(_sumregs=True, **kw)
-        u = self._batch(u, "u")
-        du = np.empty((K, self.O, self.N, self.M))
-        self._check(self._lib.bpltv_sumregs_jvp_each(self._h, _ptr(u), _ptr(a), am, an, int(bool(reg)), C.byref(p), K,
-                                                     _ptr(df) if df is not None else None,
-                                                     _ptr(dalphas) if dalphas is not None else None, _ptr(du)))
-        return du if batched else du[0]
+        return self._jvp(_SUMREGS_EACH, "sumregs_jvp_each", alphas, df, dalphas, kw, u=u, reg=reg)
 
     def sumregs_jvp_each_device(self, u_ptr, alphas_ptr, am, an, df_ptr, dalphas_ptr, du_ptr, ndir=1, reg=False, **kw):
         """bpltv_sumregs_jvp_each_device: as sumregs_jvp_device with O parameter blocks (O*3*am*an doubles) and ndir*O
         tangent blocks."""
-        p = self.params(_sumregs=True, **kw)
-        self._check(self._lib.bpltv_sumregs_jvp_each_device(self._h, C.c_void_p(u_ptr), C.c_void_p(alphas_ptr), int(am),
-                                                            int(an), int(bool(reg)), C.byref(p), int(ndir),
-                                                            C.c_void_p(df_ptr or None), C.c_void_p(dalphas_ptr or None),
-                                                            C.c_void_p(du_ptr)))
+        self._jvp_device(_SUMREGS_EACH, alphas_ptr, am, an, (df_ptr, dalphas_ptr), du_ptr, ndir, kw, u_ptr=u_ptr, reg=reg)
 
     # -- reverse mode through the sum-of-regularisers iterations (bpltv_sumregs_unrolled_*) ------------------------
     def sumregs_unrolled_tape_doubles(self, **kw):
         """Doubles of the tape a sum-of-regularisers unrolled solve with these params records: 6 * maxiter * M*N*O."""
-        p = self._taped_params(kw, _sumregs=True)
-        n = C.c_ulonglong(0)
-        self._check(self._lib.bpltv_sumregs_unrolled_tape_doubles(self._h, C.byref(p), C.byref(n)))
-        return int(n.value)
+        return self._tape_doubles(_SUMREGS_UNROLLED, kw)
 
     def sumregs_unrolled_denoise(self, x, fetch=True, **kw):
         """sumregs_denoise(x) with rho = 0 -- the same u bit for bit -- that also records the tape of the iterations in
         the handle, for sumregs_unrolled_vjp with the same x and params (bpltv_sumregs_unrolled_denoise)."""
-        a, am, an, _ = _sr_alpha_arg(x)
-        p = self._taped_params(kw, _sumregs=True)
-        u = np.empty((self.O, self.N, self.M)) if fetch else None
-        self._check(self._lib.bpltv_sumregs_unrolled_denoise(self._h, _ptr(a), am, an, C.byref(p),
-                                                             _ptr(u) if fetch else None))
-        return u
+        return self._solve(_SUMREGS_UNROLLED, x, fetch, kw)
 
     def sumregs_unrolled_denoise_device(self, alpha_ptr, am=1, an=1, tape_ptr=None, **kw):
         """bpltv_sumregs_unrolled_denoise_device: the parameter (3*am*an doubles) resident in HBM, the result left there
         (u_device_ptr / copy_u_device); tape_ptr: a caller-owned HBM buffer of sumregs_unrolled_tape_doubles(**kw)
         doubles, or None / 0 for the handle's own tape."""
-        p = self._taped_params(kw, _sumregs=True)
-        self._check(self._lib.bpltv_sumregs_unrolled_denoise_device(self._h, C.c_void_p(alpha_ptr), int(am), int(an),
-                                                                    C.byref(p), C.c_void_p(tape_ptr or None)))
+        self._solve_device(_SUMREGS_UNROLLED, alpha_ptr, am, an, kw, tape_ptr=tape_ptr)
 
     def sumregs_unrolled_vjp(self, x, gu, want_f=True, want_alpha=True, **kw):
         """Vector-Jacobian product of the maxiter-step map u = sumregs_unrolled_denoise(x) for the cotangent gu = dL/du,
         by a reverse sweep over the handle's tape (bpltv_sumregs_unrolled_vjp): (grad_f, grad_x).  x and the params must
         be those of the solve.  gu: (O, N, M); grad_f has its shape (None unless want_f), grad_x the shape of x (None
         unless want_alpha)."""
-        if not (want_f or want_alpha):
-            raise ValueError("sumregs_unrolled_vjp: want_f and want_alpha are both False")
-        a, am, an, vec = _sr_alpha_arg(x)
-        p = self._taped_params(kw, _sumregs=True)
-        gu = self._batch(gu, "gu")
-        gf = np.empty((self.O, self.N, self.M)) if want_f else None
-        ga = np.empty(3 * am * an) if want_alpha else None
-        self._check(self._lib.bpltv_sumregs_unrolled_vjp(self._h, _ptr(a), am, an, C.byref(p), _ptr(gu),
-                                                         _ptr(gf) if want_f else None,
-                                                         _ptr(ga) if want_alpha else None))
-        if ga is not None and not vec:
-            ga = ga.reshape(3, an, am)
-        return gf, ga
+        return self._vjp(_SUMREGS_UNROLLED, "sumregs_unrolled_vjp", x, gu, (want_f, want_alpha), kw)
 
     def sumregs_unrolled_vjp_device(self, tape_ptr, alpha_ptr, am, an, gu_ptr, grad_f_ptr, grad_alpha_ptr, **kw):
         """bpltv_sumregs_unrolled_vjp_device: the tape (None / 0: the handle's own), the parameter, gu and the outputs
         resident in HBM (raw device pointers); either output pointer may be 0 / None, not both."""
-        p = self._taped_params(kw, _sumregs=True)
-        self._check(self._lib.bpltv_sumregs_unrolled_vjp_device(self._h, C.c_void_p(tape_ptr or None),
-                                                                C.c_void_p(alpha_ptr), int(am), int(an), C.byref(p),
-                                                                C.c_void_p(gu_ptr), C.c_void_p(grad_f_ptr or None),
-                                                                C.c_void_p(grad_alpha_ptr or None)))
+        self._vjp_device(_SUMREGS_UNROLLED, tape_ptr, alpha_ptr, am, an, gu_ptr, (grad_f_ptr, grad_alpha_ptr), kw)
 
     def sumregs_unrolled_denoise_each(self, alphas, fetch=True, **kw):
         """sumregs_unrolled_denoise with image k's own three weights alphas[k] (bpltv_sumregs_unrolled_denoise_each):
         sumregs_denoise_each's u bit for bit, and the handle's tape, recorded per image."""
-        a, am, an = self._sr_each_arg(alphas)
-        p = self._taped_params(kw, _sumregs=True)
-        u = np.empty((self.O, self.N, self.M)) if fetch else None
-        self._check(self._lib.bpltv_sumregs_unrolled_denoise_each(self._h, _ptr(a), am, an, C.byref(p),
-                                                                  _ptr(u) if fetch else None))
-        return u
+        return self._solve(_SUMREGS_UNROLLED_EACH, alphas, fetch, kw)
 
     def sumregs_unrolled_denoise_each_device(self, alphas_ptr, am=1, an=1, tape_ptr=None, **kw):
         """bpltv_sumregs_unrolled_denoise_each_device: O parameter blocks (a C-contiguous (O, 3, an, am) array) resident
         in HBM, the result left there; tape_ptr as in sumregs_unrolled_denoise_device."""
-        p = self._taped_params(kw, _sumregs=True)
-        self._check(self._lib.bpltv_sumregs_unrolled_denoise_each_device(self._h, C.c_void_p(alphas_ptr), int(am),
-                                                                         int(an), C.byref(p),
-                                                                         C.c_void_p(tape_ptr or None)))
+        self._solve_device(_SUMREGS_UNROLLED_EACH, alphas_ptr, am, an, kw, tape_ptr=tape_ptr)
 
     def sumregs_unrolled_vjp_each(self, alphas, gu, want_f=True, want_alpha=True, **kw):
         """sumregs_unrolled_vjp with image k's own block alphas[k], over the handle's per-image tape
         (bpltv_sumregs_unrolled_vjp_each): (grad_f, grad_alphas).  grad_alphas has the shape of alphas; grad_alphas[k]
         is image k's term alone, not summed over the images."""
-        if not (want_f or want_alpha):
-            raise ValueError("sumregs_unrolled_vjp_each: want_f and want_alpha are both False")
-        a, am, an = self._sr_each_arg(alphas)
-        p = self._taped_params(kw, _sumregs=True)
-        gu = self._batch(gu, "gu")
-        gf = np.empty((self.O, self.N, self.M)) if want_f else None
-        ga = np.empty(a.shape) if want_alpha else None
-        self._check(self._lib.bpltv_sumregs_unrolled_vjp_each(self._h, _ptr(a), am, an, C.byref(p), _ptr(gu),
-                                                              _ptr(gf) if want_f else None,
-                                                              _ptr(ga) if want_alpha else None))
-        return gf, ga
+        return self._vjp(_SUMREGS_UNROLLED_EACH, "sumregs_unrolled_vjp_each", alphas, gu, (want_f, want_alpha), kw)
 
     def sumregs_unrolled_vjp_each_device(self, tape_ptr, alphas_ptr, am, an, gu_ptr, grad_f_ptr, grad_alphas_ptr, **kw):
         """bpltv_sumregs_unrolled_vjp_each_device: as sumregs_unrolled_vjp_device with O parameter blocks and their O
         gradients (O*3*am*an doubles each) resident in HBM; either output pointer may be 0 / None, not both."""
-        p = self._taped_params(kw, _sumregs=True)
-        self._check(self._lib.bpltv_sumregs_unrolled_vjp_each_device(self._h, C.c_void_p(tape_ptr or None),
-                                                                     C.c_void_p(alphas_ptr), int(am), int(an),
-                                                                     C.byref(p), C.c_void_p(gu_ptr),
-                                                                     C.c_void_p(grad_f_ptr or None),
-                                                                     C.c_void_p(grad_alphas_ptr or None)))
+        self._vjp_device(_SUMREGS_UNROLLED_EACH, tape_ptr, alphas_ptr, am, an, gu_ptr, (grad_f_ptr, grad_alphas_ptr), kw)
 
     def sweep(self, alphas, fetch_u=False, **kw):
         """costs[k] = 0.5*||denoise(f, alphas[k]) - ubar||^2 for K parameters in one batched solve
@@ -1478,6 +1118,40 @@ class TVSolver:
         s = _lib.BpltvStats()
         self._check(self._lib.bpltv_stats(self._h, C.byref(s)))
         return s.as_dict()
+
+
+class _Model(typing.NamedTuple):
+    """What tells one model's entries from another's; a core (TVSolver._solve, _vjp, _jvp, ...) reads nothing else."""
+    prefix: str               # the entries are bpltv_<prefix><op>[_each][_device]
+    parse: typing.Callable    # x -> (a, am, an[, scalar]): _alpha_arg, _sr_alpha_arg, TVSolver._each_arg or TVSolver._sr_each_arg
+    slices: int = 1           # parameter slices: 3 for the sum-of-regularisers model
+    w: bool = False           # takes the fidelity weight (w, wo) in front of the parameter, and returns grad_w / takes dw
+    channels: bool = False    # takes the channel count right after the handle
+    sumregs: bool = False     # its params start from bpltv_sumregs_default_params
+    taped: bool = False       # unrolled: solve and vjp take checkpoint_every= and a tape, jvp and gauss_newton sweep the iterations
+    each: bool = False        # one parameter block per image
+
+    def entry(self, op, device=False):
+        return "bpltv_%s%s%s%s" % (self.prefix, op, "_each" if self.each else "", "_device" if device else "")
+
+    def unrolled(self):
+        return self._replace(prefix=self.prefix + "unrolled_", taped=True)
+
+
+# one row per model: a new data term or model is a row here and its public methods' docstrings on TVSolver
+_TV = _Model("", _alpha_arg)
+_TV_EACH = _Model("", TVSolver._each_arg, each=True)
+_SUMREGS = _Model("sumregs_", _sr_alpha_arg, slices=3, sumregs=True)
+_SUMREGS_EACH = _Model("sumregs_", TVSolver._sr_each_arg, slices=3, sumregs=True, each=True)
+_WEIGHTED = _Model("weighted_", _alpha_arg, w=True)
+_L1 = _Model("lone_", _alpha_arg, w=True)
+_KL = _Model("kl_", _alpha_arg, w=True)
+_COLOR = _Model("color_", _alpha_arg, channels=True)
+_COLOR_WEIGHTED = _Model("color_weighted_", _alpha_arg, w=True, channels=True)
+_UNROLLED, _UNROLLED_EACH = _TV.unrolled(), _TV_EACH.unrolled()
+_SUMREGS_UNROLLED, _SUMREGS_UNROLLED_EACH = _SUMREGS.unrolled(), _SUMREGS_EACH.unrolled()
+_WEIGHTED_UNROLLED, _L1_UNROLLED, _KL_UNROLLED = _WEIGHTED.unrolled(), _L1.unrolled(), _KL.unrolled()
+_COLOR_UNROLLED, _COLOR_WEIGHTED_UNROLLED = _COLOR.unrolled(), _COLOR_WEIGHTED.unrolled()
 
 
 # ---------------------------------------------------------------------------------------------
@@ -1612,8 +1286,3 @@ def L2CostFunction(u, true_):
     results already fetched; inside evaluate the loss is reduced on the GPU)."""
     d = np.asarray(u, dtype=np.float64) - np.asarray(true_, dtype=np.float64)
     return 0.5 * float(np.sum(d * d))
-
-
-for _name in [n for n in vars(TVSolver) if re.search(r"unrolled_(tape_doubles|denoise|vjp)", n)]:
-    setattr(TVSolver, _name, _restores_full_tape(getattr(TVSolver, _name)))
-del _name
