@@ -89,6 +89,13 @@ def test_a_mask_makes_acceleration_a_no_op(gpu_solver_cls, name):
 
 
 # ---- 2. u and the gradients against the twin ------------------------------------------------------------------------------
+def _bounds(gf0, ga0, gw0, alpha, w, B, Cc, N, M):
+    """(grad_f, grad_alpha, grad_w): 1e-11 * max|gf0|; 1e-11 * max|ga0| * B * pixels_per_entry, ga0 the per-pixel terms; 1e-11 *
+    max|gw0|, times O = B * Cc for a one-plane weight (tests/test_gpu_tile_depths.py imports them)."""
+    return (1e-11 * float(np.abs(gf0).max()), 1e-11 * float(np.abs(ga0).max()) * B * ur.pixels_per_entry(alpha, M, N),
+            1e-11 * float(np.abs(gw0).max()) * (B * Cc if np.ndim(w) == 2 else 1))
+
+
 @pytest.mark.parametrize("wkind", ["real", "mask", "mosaic"])
 @pytest.mark.parametrize("kind", cw.KINDS)
 @pytest.mark.parametrize("name", sorted(cw.SHAPES))
@@ -115,9 +122,7 @@ def test_u_and_gradients_match_the_twin(gpu_solver_cls, name, kind, wkind):
         gf, ga, gw = s.color_weighted_unrolled_vjp(alpha, Cc, w, gu, maxiter=K)
         st = s.stats()
         assert st["adjoint_method"] == "color-weighted-unrolled" and st["adjoint_ms"] > 0.0 and st["iterations"] == K, st
-        bf = 1e-11 * float(np.abs(gf0).max())
-        ba = 1e-11 * float(np.abs(ga0).max()) * B * ur.pixels_per_entry(alpha, M, N)
-        bw = 1e-11 * float(np.abs(gw0).max()) * (B * Cc if w.ndim == 2 else 1)
+        bf, ba, bw = _bounds(gf0, ga0, gw0, alpha, w, B, Cc, N, M)
         du = float(np.abs(u - u0).max())
         df = float(np.abs(gf - gf0).max())
         da = float(np.abs(np.asarray(ga) - np.asarray(ur.reduce_alpha(ga0, alpha))).max())

@@ -7,7 +7,8 @@ most one region."""
 REGION = 32       # TV_R, SRUN_R
 MAX_T = 32        # PDHG_MAX_T: step rows one launch keeps in LDS
 SR_FWD_CAP = 7    # (SRUN_R - 1) / 4: the sum of regularisers' halo 2T must leave a core
-REV_CAP = {"tv": 8, "weighted": 8, "sumregs": 4, "color1": 8, "color2": 6, "color3": 4, "color4": 3}   # TV_REV_T, SRUN_REV_T, color_rev_t
+REV_CAP = {"tv": 8, "weighted": 8, "sumregs": 4, "color1": 8, "color2": 6, "color3": 4, "color4": 3,   # TV_REV_T, SRUN_REV_T, color_rev_t
+           "l1": 8, "kl": 8, "color_weighted2": 5, "color_weighted3": 2, "color_weighted4": 1}          # TV_REV_T, color_weighted_rev_t
 MODELS = tuple(sorted(REV_CAP))
 
 
