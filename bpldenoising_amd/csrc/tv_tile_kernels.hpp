@@ -71,6 +71,22 @@
 //                 and grad_w there, which the tape cannot give, are dropped)
 // and dL/df = gf + gx after the last step (x_0 = f, y_0 = 0).  The two tails agree to rounding only at w = 1
 // (tests/test_gpu_weighted_unrolled.py).  The weighted sweep needs no w > 0: a mask (w in {0, 1}) gets gradients in f, alpha, w.
+//
+// What the lines above leave open, as the kernels and oracle/taped_oracle.c have it (tests/test_gpu_taped_bits.py holds forward and
+// tape to that oracle bit for bit and both sweeps to it within the families' bounds, on data that sit on every decision below):
+//     G^T y  = (y1[i-1,j] - y1[i,j]) + (y2[i,j-1] - y2[i,j]), a neighbour outside the image is 0; y1 of the last image row and
+//              y2 of the last column are 0 because G's rows there are (forward: they never leave 0; reverse: gz enters as 0)
+//     G x    = (x[i+1,j] - x[i,j], x[i,j+1] - x[i,j]), 0 at i = M-1 / j = N-1 (pdhg_x_pass / pdhg_y_pass of oracle/bpltv_oracle.c)
+//     1 + omega_k is the table's fifth entry wherever it appears (xbar, dxb, gxn); tau_k*c is one product, formed first
+//     sign(x_new - f) is three-way, +1 / -1 / 0, in the tangent and in the reverse tail; sign 0 adds -tau*0 to gw: nothing
+//     the tape holds z before the projection (and x_new); ga += dot only where out
+// Ties.  out = n2 > alpha^2 is strict: a dual exactly on the ball is not projected and passes its tangent and cotangent whole,
+// in all three kernels (8-bit data reach n2 == alpha^2 only by construction, n2 == 0 on every flat patch: rsqrt_nr(0) must reach
+// no result, also in a wave whose other lanes project).  L1: m == 0 holds the pixel at f; act is read off x_new, f and w and not
+// off m, so a step let through that rounds back to f counts as held (forward and sweeps agree: both read x_new); w == 0 with
+// d == 0 -- every pixel without data in iteration 0, and on flat patches later -- is act with sign 0.  KL: x_new == 0 exactly
+// needs w f == 0 and c <= 0, then D == 0 and q = 0: tangent and reverse pass nothing through the data step, gw gets exactly 0 from
+// it and du of a pixel clamped in the last iteration is exactly 0; 0/0 is never formed.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -37,10 +37,11 @@
  * (L = sqrt(8) bound on ||grad||, gamma = 1 strong convexity of the fidelity term).
  * Row k = {tau, sigma, omega, 1/(1+tau), 1+omega} used in iteration k.
  * ---------------------------------------------------------------------------------------- */
-BPLO_API void bplo_step_table_L(int maxiter, double tau0, double sigma0, int accel, double L, double *tab)
+/* gamma: the strong convexity the acceleration uses -- 1 (TV), min w (the weighted model), 0 (TV-L1, TV-KL: omega = 1 and
+ * constant steps).  2.0 * 1.0 * tau is 2.0 * tau exactly, so gamma = 1 is the table this function always made. */
+BPLO_API void bplo_step_table_gamma(int maxiter, double tau0, double sigma0, int accel, double L, double gamma, double *tab)
 {
     double tau = tau0 / L, sigma = sigma0 / L;
-    const double gamma = 1.0;
     for (int k = 0; k < maxiter; ++k) {
         double omega = accel ? 1.0 / sqrt(1.0 + 2.0 * gamma * tau) : 1.0;
         tab[5 * k + 0] = tau;
@@ -53,6 +54,11 @@ BPLO_API void bplo_step_table_L(int maxiter, double tau0, double sigma0, int acc
             sigma = sigma / omega;
         }
     }
+}
+
+BPLO_API void bplo_step_table_L(int maxiter, double tau0, double sigma0, int accel, double L, double *tab)
+{
+    bplo_step_table_gamma(maxiter, tau0, sigma0, accel, L, 1.0, tab);
 }
 
 BPLO_API void bplo_step_table(int maxiter, double tau0, double sigma0, int accel, double *tab)

@@ -16,7 +16,7 @@ _lib = None
 
 def build(force=False):
     """Compile the C restatement with gcc (oracle/Makefile)."""
-    srcs = [os.path.join(_HERE, f) for f in ("bpltv_oracle.c", "sumregs_oracle.c", "Makefile")]
+    srcs = [os.path.join(_HERE, f) for f in ("bpltv_oracle.c", "sumregs_oracle.c", "taped_oracle.c", "Makefile")]
     if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < max(os.path.getmtime(f) for f in srcs):
         subprocess.check_call(["make", "-C", _HERE, "-s", "-B", "libbpltv_oracle.so"])
     return _SO
@@ -394,5 +394,129 @@ def rsqrt_nr(x):
     return lib().bplo_rsqrt_nr(float(x))
 
 
+# ---------------------------------------------------------------------------------------------------
+# The one-plane taped family (oracle/taped_oracle.c; the header comment of bpldenoising_amd/csrc/tv_tile_kernels.hpp).
+# Batches are (O, N, M), the parameter is a full (N, M) map (np_twin.alpha_to_map), a weight is (N, M) or (O, N, M), the tape is
+# (K, 2 or 3, O, N, M) -- the library's layout [k][z1, z2 (, x+)][image][pixel].
+# ---------------------------------------------------------------------------------------------------
+TAPED_MODELS = {"tv": 0, "weighted": 1, "l1": 2, "kl": 3}
+TAPED_COUNTERS = ("m0_w_pos", "m0_w0_first", "m0_w0_later", "n2_tie", "n2_tie_first", "n2_zero_beside_projected", "x_zero", "D_zero",
+                  "let_through_but_x_eq_f", "x_eq_f_w0_later")
+_sz = C.c_size_t
+_llp = C.POINTER(C.c_longlong)
+
+
+def _taped_fn(name, argtypes):
+    fn = getattr(lib(), name)
+    fn.restype = C.c_int
+    fn.argtypes = argtypes
+    return fn
+
+
+def taped_step_table(model, w, K, tau0=5.0, sigma0=0.99 / 5, accel=True):
+    """(K, 5) step table of a taped solve: bplo_step_table_gamma on L = sqrt(8) with gamma = 1 (tv), min over all of w (weighted)
+    or 0 (l1, kl), as the library's taped models choose."""
+    gamma = {"tv": 1.0, "l1": 0.0, "kl": 0.0}.get(model)
+    if gamma is None:
+        gamma = float(np.min(w))
+    tab = np.empty((max(K, 1), 5))
+    fn = lib().bplo_step_table_gamma
+    fn.restype = None
+    fn.argtypes = [C.c_int, C.c_double, C.c_double, C.c_int, C.c_double, C.c_double, _dp]
+    fn(K, tau0, sigma0, int(accel), float(np.sqrt(8.0)), gamma, _p(tab))
+    return tab[:K]
+
+
+def _taped_args(model, f, amap, w):
+    f = _c(f)
+    assert f.ndim == 3, f.shape
+    O, N, M = f.shape
+    amap = _c(amap)
+    assert amap.shape == (N, M), amap.shape
+    if model == "tv":
+        assert w is None
+        return f, amap, None, 0, (O, N, M)
+    w = _c(w)
+    assert w.shape in ((N, M), (O, N, M)), w.shape
+    return f, amap, w, (N * M if w.ndim == 3 else 0), (O, N, M)
+
+
+def _taped_plane(a, shape, what):
+    """A tangent in the shape of w ((N, M) or (O, N, M)) or of f, contiguous, or None."""
+    if a is None:
+        return None
+    a = _c(a)
+    assert a.shape == tuple(shape), (what, a.shape, shape)
+    return a
+
+
+def taped_forward(model, f, amap, w, K, tab=None, counters=True):
+    """(u, tape, counters): K iterations of `model` from x = f, y = 0; counters: a dict over TAPED_COUNTERS (pixel-iterations of
+    each degenerate class, on the oracle's own values), or None."""
+    f, amap, w, ws, (O, N, M) = _taped_args(model, f, amap, w)
+    tab = _c(taped_step_table(model, w, K) if tab is None else tab)
+    u = np.empty_like(f)
+    tape = np.empty((K, 2 if model == "tv" else 3, O, N, M))
+    cnt = (C.c_longlong * len(TAPED_COUNTERS))() if counters else None
+    fn = _taped_fn("bplo_taped_forward", [C.c_int] * 4 + [_dp, _dp, _dp, _sz, C.c_int, _dp, _dp, _dp, _llp])
+    rc = fn(TAPED_MODELS[model], M, N, O, _p(f), _p(amap), _p(w), ws, K, _p(tab), _p(u), _p(tape), cnt)
+    if rc:
+        raise RuntimeError("bplo_taped_forward rc=%d" % rc)
+    return u, tape, (dict(zip(TAPED_COUNTERS, (int(v) for v in cnt))) if counters else None)
+
+
+def taped_tangent(model, f, amap, w, K, df=None, dam=None, dw=None, tab=None):
+    """(du, u): the tangent sweep beside the forward's own iterations; df: (O, N, M), dam: (N, M), dw: shaped like w; None: zero."""
+    f, amap, w, ws, (O, N, M) = _taped_args(model, f, amap, w)
+    tab = _c(taped_step_table(model, w, K) if tab is None else tab)
+    df = _taped_plane(df, f.shape, "df")
+    dam = _taped_plane(dam, amap.shape, "dam")
+    dw = _taped_plane(dw, w.shape, "dw") if w is not None else None
+    u = np.empty_like(f)
+    du = np.empty_like(f)
+    fn = _taped_fn("bplo_taped_tangent", [C.c_int] * 4 + [_dp, _dp, _dp, _sz, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp])
+    rc = fn(TAPED_MODELS[model], M, N, O, _p(f), _p(amap), _p(w), ws, K, _p(tab), _p(df), _p(dam), _p(dw), _p(du), _p(u))
+    if rc:
+        raise RuntimeError("bplo_taped_tangent rc=%d" % rc)
+    return du, u
+
+
+def taped_reverse(model, tape, f, amap, w, gu, tab=None):
+    """(grad_f, ga, gw): dL/df and the per-pixel, per-image terms (O, N, M) of dL/dalpha and dL/dw (None for tv) for the cotangent
+    gu, over whatever tape is given (the oracle's or the library's): every decision is read off the tape, f and w."""
+    f, amap, w, ws, (O, N, M) = _taped_args(model, f, amap, w)
+    tape = _c(tape)
+    K = tape.shape[0]
+    assert tape.shape == (K, 2 if model == "tv" else 3, O, N, M), tape.shape
+    tab = _c(taped_step_table(model, w, K) if tab is None else tab)
+    gu = _taped_plane(gu, f.shape, "gu")
+    gf = np.empty_like(f)
+    ga = np.empty_like(f)
+    gw = np.empty_like(f) if w is not None else None
+    fn = _taped_fn("bplo_taped_reverse", [C.c_int] * 4 + [_dp, _dp, _dp, _dp, _sz, C.c_int, _dp, _dp, _dp, _dp, _dp])
+    rc = fn(TAPED_MODELS[model], M, N, O, _p(tape), _p(f), _p(amap), _p(w), ws, K, _p(tab), _p(gu), _p(gf), _p(ga), _p(gw))
+    if rc:
+        raise RuntimeError("bplo_taped_reverse rc=%d" % rc)
+    return gf, ga, gw
+
+
 def max_threads():
     return lib().bplo_max_threads()
+
+
+def taped_decisions(model, tape, f, amap, w, tab=None):
+    """(projected, data): boolean (O, N, M) maps of where the sweeps over `tape` pass anything at all -- a dual projected in at
+    least one iteration (else ga gets nothing), and the data step passing into gw in at least one iteration (l1: x+ != f; kl:
+    D > 0; weighted: always; None for tv) -- decided by the sweeps' own expressions, fma included."""
+    f, amap, w, ws, (O, N, M) = _taped_args(model, f, amap, w)
+    tape = _c(tape)
+    K = tape.shape[0]
+    assert tape.shape == (K, 2 if model == "tv" else 3, O, N, M), tape.shape
+    tab = _c(taped_step_table(model, w, K) if tab is None else tab)
+    pr = np.empty_like(f)
+    da = np.empty_like(f) if w is not None else None
+    fn = _taped_fn("bplo_taped_decisions", [C.c_int] * 4 + [_dp, _dp, _dp, _dp, _sz, C.c_int, _dp, _dp, _dp])
+    rc = fn(TAPED_MODELS[model], M, N, O, _p(tape), _p(f), _p(amap), _p(w), ws, K, _p(tab), _p(pr), _p(da))
+    if rc:
+        raise RuntimeError("bplo_taped_decisions rc=%d" % rc)
+    return pr != 0, (da != 0 if da is not None else None)
